@@ -10,14 +10,23 @@ intra-slice -> UEs.step -> intent observation and reward).  Workload at N=1: BAS
 configuration the north_star's throughput target is quoted on (mult_slice, 10 slices / 100 UEs / 135 RBGs, batch 4096,
 PF intra-slice + ib_sched intent reward); with N GPUs every rank steps its own 4096 envs (weak scaling; N=8 is
 configs[3], batch 32768 sharded 8x).  Inputs (scenario, SE and traffic pools) are resident in HBM before the timed
-region.  Prints ONE JSON line on rank 0.
+region; the same arguments give the same inputs in every run.  Prints ONE JSON line on rank 0.
 
-What is timed, each as blocks of EXACTLY K steps between barrier + device sync on both sides (MAX over ranks); a block
-is repeated until ~20 ms of stepping are sampled, the median block is reported (`repeats`, min / max beside it):
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: it builds the workload, warms up with W TTIs, times ONE call of
+EXACTLY K steps between barrier + device sync on both sides (MAX over ranks) and prints the line:
 
   value / roofline   the headline, SURVEY 8(d)'s streaming step kernel: `ranenv_rollout` (the K TTIs of the device
                      policy enqueued in one call): launches of up to 10 TTIs over 3 batch partitions on 3 HIP streams
                      (RANENV_PERSIST=1: as persistent work-queue launches, a tie for this kernel; the line says which ran)
+
+--dump-outputs DIR writes what that timed call handed back after its last TTI -- obs_inter, obs_intra (float32), reward
+(float64), done (as float32) -- as DIR/<name>.npy, so that two builds can be compared output for output.
+
+--full adds everything else, each as blocks of EXACTLY K steps, a block repeated until ~20 ms of stepping are sampled, the
+median block reported (`repeats`, min / max beside it): the headline's per-launch kernel timestamps (roofline.dominant_kernel,
+from the same K steps repeated with timing on), the recorded counter figures, the CPU baseline and:
   single_stream      the same K TTIs as env.step() in a loop: one launch per TTI on one stream (mixed blocks: one block per env
                      of more than 64 slice members + one per two envs of at most 64, the whole batch resident in one round)
   pipelined_step     a learner in the loop: external inter-slice scores produced from each half's last observation
@@ -180,12 +189,39 @@ def build_line(args, world, batch, label, env_sizes, alg_bytes_env_step, times, 
                workload_extra="", extras=None, persistent=False):
     """The ONE JSON line.  `value` and `roofline.frac` share the wall clock of the timed region (the median block: the
     whole TTI of the whole batch); the step kernel's per-launch duration (the dispatch's own timestamps, from the same
-    K steps repeated with timing on) is listed beside it -- with partitions `parts` launches of batch/parts envs overlap."""
+    K steps repeated with timing on) is listed beside it -- with partitions `parts` launches of batch/parts envs overlap.
+    `kms` None (a plain run: no profiled repeat): the line without the per-launch figures."""
     S, U, R = env_sizes
     st = block_stats(times, batch * world * args.steps, args.steps)
     ms_per_step = st["ms_per_step"]
     alg_bytes = alg_bytes_env_step * batch                       # per TTI of one rank's batch
     achieved = alg_bytes / (ms_per_step * 1e-3) / 1e9            # per-GPU GB/s on the wall clock
+    timing = (f"blocks of exactly {args.steps} steps, each between barrier + device sync (MAX over ranks); value = median of "
+              f"{st['repeats']} blocks" if len(times) > 1 else
+              f"one block of exactly {args.steps} steps (one ranenv_rollout call) after {args.warmup} warm-up steps, between "
+              "barrier + device sync (MAX over ranks)")
+    if kms is None:
+        line = {
+            "metric": "env-steps/s (batched TTIs) at mult_slice 10-slice/100-UE; 1->8 GPU scaling"
+                      + (" [device-policy rollout over batch partitions; step-by-step and learner-in-the-loop schedules beside it]"
+                         if parts > 1 else ""),
+            "value": st["value"], "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "repeats": st["repeats"], "timing": timing,
+            "config": {"workload": (f"BASELINE.json configs[{args.config}]" if args.config != 5 else "NOT a BASELINE config") + f": {label}; batch {batch} per GPU; SE replayed from "
+                                   f"an HBM pool of {args.traces}x{args.trace_len} float32 tiles{workload_extra}",
+                       "batch_per_gpu": batch, "global_batch": batch * world, "n_slices": S, "n_ues": U, "n_rbs": R,
+                       "parallelism": f"episodes sharded over {world} GPU(s), metrics all_gather only",
+                       "launch": ("ranenv_rollout as persistent work-queue launches" if persistent else
+                                  f"ranenv_rollout over {parts} batch partition(s) on {parts} HIP stream(s)"),
+                       "se_mode": "stream", "se_layout": getattr(args, "se_layout", None)},
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "clock": "wall clock of the timed region (same as value)",
+                         "algorithmic_bytes_per_env_step": alg_bytes_env_step, "algorithmic_bytes_per_tti": alg_bytes},
+            "metrics": metrics,
+        }
+        line.update(extras or {})
+        return line
     launch_ms, n_launches = kms["step"], kms["n_launches"]
     ttis_per_launch = kms.get("n_ttis", n_launches) / max(1, n_launches)      # inside a rollout a launch covers several TTIs
     env_ttis_per_launch = kms.get("n_env_ttis", batch / parts * kms.get("n_ttis", n_launches)) / max(1, n_launches)
@@ -215,8 +251,7 @@ def build_line(args, world, batch, label, env_sizes, alg_bytes_env_step, times, 
         "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "repeats": st["repeats"], "value_min": st["value_min"], "value_max": st["value_max"],
-        "timing": f"blocks of exactly {args.steps} steps, each between barrier + device sync (MAX over ranks); value = median of "
-                  f"{st['repeats']} blocks",
+        "timing": timing,
         "config": {"workload": (f"BASELINE.json configs[{args.config}]" if args.config != 5 else "NOT a BASELINE config") + f": {label}; batch {batch} per GPU; SE replayed from "
                                f"an HBM pool of {args.traces}x{args.trace_len} float32 tiles{workload_extra}",
                    "batch_per_gpu": batch, "global_batch": batch * world, "n_slices": S, "n_ues": U,
@@ -332,6 +367,28 @@ def other_config_block(cfg, device, args, rank, se_pool, timing, pmc_block=None)
     return st
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays) -> dict:
+    """arrays (name -> numpy array, batch first) as out_dir/<name>.npy.  Beyond DUMP_LIMIT_BYTES in all, the same fixed, seeded
+    sample of envs is kept of every array; returns what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_LIMIT_BYTES:
+        batch = min(a.shape[0] for a in arrays.values())
+        keep = max(1, int(batch * DUMP_LIMIT_BYTES // total))
+        rows = np.sort(np.random.default_rng(0).choice(batch, size=keep, replace=False))
+    written = {}
+    for name, a in arrays.items():
+        if rows is not None:
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return {"dir": out_dir, "arrays": written, "env_sample": None if rows is None else int(len(rows))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -352,6 +409,11 @@ def main():
                     help="batch partitions on their own HIP streams (default: 3 on one GPU, 2 per rank in a multi-GPU run, "
                          "1 when the batch does not fill the CUs)")
     ap.add_argument("--ranges", type=int, default=2, help="ranges of the batch the pipelined_step variant alternates between")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: its profiled repeat (roofline.dominant_kernel), the comparison "
+                         "schedules, se_gather, other_configs and the CPU baseline (the --no-* options below thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed call returned after its last TTI (obs_inter, obs_intra, reward, done) as DIR/<name>.npy")
     ap.add_argument("--cpu-envs", type=int, default=256)
     ap.add_argument("--cpu-steps", type=int, default=6000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -434,33 +496,53 @@ def main():
     K = args.steps
     extras = {}
 
-    def rollout_variant():
-        """warm-up, the timed blocks of one ranenv_rollout(K) each, then the same K steps with per-launch timestamps."""
+    dumped = {}
+
+    def rollout_variant(headline):
+        """warm-up, then the timed ranenv_rollout(K): the headline ONE call of exactly K steps (what it returned kept for
+        --dump-outputs), any other variant blocks of one call each; with --full then the same K steps with per-launch timestamps."""
         env.set_partitions(parts)
         env.reset()
-        env.rollout(max(1, args.warmup))
-        # (the timed schedule itself is warmed by timed_blocks: its first block of K steps -- same call, same launches, class lists and queues of the
-        # persistent rollout already built -- only sizes the sample and is not among the blocks `value` is the median of)
         local = []
-        times = timed_blocks(lambda: env.rollout(K), sync, barrier, max_over_ranks, local_out=local)
-        env.profile_begin()
-        env.rollout(K)
-        kms = env.profile_end()
-        kms["persistent"] = bool(env.get_option("last_rollout_persistent"))     # (reported by the library, not inferred)
-        kms["local_block_s"] = float(np.median(local))                            # this rank's own median block, before the barrier
-        return times, kms
+        if headline:
+            # the warm-up's W TTIs: when W >= K its last call is the timed call's own (the launches ranenv_rollout picks depend on K)
+            W = max(1, args.warmup)
+            if W % K:
+                env.rollout(W % K)
+            for _ in range(W // K):
+                env.rollout(K)
+            ret = []
+            times = [timed_steps(lambda: ret.append(env.rollout(K)), 1, sync, barrier, max_over_ranks, local_out=local)]
+            if args.dump_outputs:
+                obs, reward, done = ret[0]          # (the env's own buffers: copied before anything steps again)
+                dumped.update({"obs_inter": obs["obs_inter"].float().cpu().numpy(), "obs_intra": obs["obs_intra"].float().cpu().numpy(),
+                               "reward": reward.double().cpu().numpy(), "done": done.float().cpu().numpy()})
+        else:
+            env.rollout(max(1, args.warmup))
+            # (the timed schedule itself is warmed by timed_blocks: its first block of K steps -- same call, same launches, class lists and queues of the
+            # persistent rollout already built -- only sizes the sample and is not among the blocks `value` is the median of)
+            times = timed_blocks(lambda: env.rollout(K), sync, barrier, max_over_ranks, local_out=local)
+        persistent = bool(env.get_option("last_rollout_persistent"))     # (reported by the library, not inferred)
+        kms = None
+        if args.full:
+            env.profile_begin()
+            env.rollout(K)
+            kms = env.profile_end()
+            kms["persistent"] = bool(env.get_option("last_rollout_persistent"))
+        return times, kms, persistent, float(np.median(local))          # (this rank's own median block, before the barrier)
 
     times = kms = None
+    persistent = False
     gathered = None
     if not args.only_gather:
         gm(local_metrics(env.reward, env.views(), env.done, 1))   # warm torch's reduction kernels / RCCL
-        times, kms = rollout_variant()
+        times, kms, persistent, local_block_s = rollout_variant(headline=True)
         # metrics: the only collective, once per reporting interval, outside the timed K steps ...
         gathered = gm(local_metrics(env.reward, env.views(), env.done, K))
         if use_dist:
             # what the collective itself saw, and every GPU's own clock (its median block up to its own device sync)
             alg_tti = env.algorithmic_bytes_per_env_step("stream") * batch
-            mine = torch.tensor([kms["local_block_s"]], dtype=torch.float64, device=device)
+            mine = torch.tensor([local_block_s], dtype=torch.float64, device=device)
             per_rank_s = gm(mine)[:, 0].tolist()
             extras["ranks_seen"] = {"world_size": dist.get_world_size(), "all_gather_rows": int(gathered.shape[0]),
                                     "backend": dist.get_backend()}
@@ -468,12 +550,12 @@ def main():
                                  "roofline_frac": [alg_tti * K / t / (HBM_PEAK_GBS * 1e9) for t in per_rank_s],
                                  "note": "every rank's own median block of K steps up to its own device sync (before the closing "
                                          "barrier), gathered with the metrics collective; roofline.frac above uses the MAX-over-ranks clock"}
-        if use_dist:      # ... and one variant with it inside: K steps + the all_gather of the interval's accumulators
+        if use_dist and args.full:      # ... and one variant with it inside: K steps + the all_gather of the interval's accumulators
             tg = timed_blocks(lambda: (env.rollout(K), gm(local_metrics(env.reward, env.views(), env.done, K))),
                               sync, barrier, max_over_ranks)
             extras["with_metrics_gather"] = dict(block_stats(tg, batch * world * K, K),
                                                  note="the K-step block plus one all_gather of the 8 float64 accumulators per rank")
-        if not args.no_single_stream:
+        if args.full and not args.no_single_stream:
             alg = env.algorithmic_bytes_per_env_step("stream")
             if parts > 1:      # one launch per TTI on one stream (what a caller that joins every TTI gets)
                 env.set_partitions(1)
@@ -531,7 +613,7 @@ def main():
             env.set_policy(wl.policy, wl.intra)
 
     pmc = None
-    if rank == 0 and os.path.exists(os.path.join(REPO, PMC_FILE)):
+    if args.full and rank == 0 and os.path.exists(os.path.join(REPO, PMC_FILE)):
         try:
             pj = json.load(open(os.path.join(REPO, PMC_FILE)))
             if pj.get("batch") == batch and pj.get("config") == args.config:
@@ -539,21 +621,21 @@ def main():
         except Exception:
             pmc = None
 
-    if not args.no_gather:
+    if (args.full or args.only_gather) and not args.no_gather:
         try:
             env.set_se_mode("gather")
         except _lib.RanEnvError as e:
             extras["se_gather"] = {"skipped": f"sidecars not built: {e}"}
         else:
-            tg, kg = rollout_variant()
-            if rank == 0:
+            tg, kg, pg, _ = rollout_variant(headline=args.only_gather)
+            if rank == 0 and kg is not None:
                 extras["se_gather"] = gather_block(env, batch, world, K, tg, kg, parts, pmc)
             if args.only_gather:
-                times, kms = tg, kg
+                times, kms, persistent = tg, kg, pg
                 gathered = gm(local_metrics(env.reward, env.views(), env.done, K))
             env.set_se_mode("stream")
 
-    if world == 1 and args.config == 2 and args.batch is None and not args.no_other_configs and not args.only_gather:
+    if args.full and world == 1 and args.config == 2 and args.batch is None and not args.no_other_configs and not args.only_gather:
         sync()
         pool = wl.se_pool
         others = {}
@@ -566,7 +648,8 @@ def main():
         extras["other_configs"] = others
 
     if rank == 0:
-        persistent = bool(kms.get("persistent"))        # option last_rollout_persistent, read right behind the profiled call
+        if kms is not None:
+            persistent = bool(kms.get("persistent"))    # option last_rollout_persistent, read right behind the profiled call
         line = build_line(args, world, batch, label, (env.S, env.U, env.R),
                           env.algorithmic_bytes_per_env_step("gather" if args.only_gather else "stream"),
                           times, kms, parts, pmc, summarize(gathered.cpu()), persistent=persistent,
@@ -577,7 +660,7 @@ def main():
             line["rehearsal"] = f"{world} ranks sharing ONE GPU over gloo: a plumbing check of the multi-rank path, not a scaling measurement"
         if args.only_gather:
             line["config"]["se_mode"] = "gather (profiling aid: value and roofline are the gather mode's, not the headline)"
-        if world == 1 and not args.no_cpu_baseline and not args.only_gather:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.only_gather:
             line["cpu_baseline"] = cpu_baseline(wl, args.cpu_envs, args.cpu_steps)
             try:      # the reference's own Python for a full step: it never travels, so it is a recorded figure (tools/time_reference_python.py)
                 rp = json.load(open(os.path.join(REPO, REFPY_FILE)))
@@ -589,6 +672,8 @@ def main():
                               "not measured in this run", what=rp.get("what"), source=REFPY_FILE)
             except Exception:
                 pass
+        if args.dump_outputs:
+            line["outputs"] = dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """History files of this build read by the reference's own result scripts (build container only: needs /root/reference).
 
-    python tests/golden/check_reference_readers.py
+    python tests/golden/check_reference_readers.py [--write-golden]
 
 Two of the reference's real agents (agents/marr.py MARR, agents/mapf.py MAPF) play the same two 30-TTI episodes on this
 build's MARLCommEnv facade with ``save_hist=True`` (the reference's plugins, INTEGRATION.md section 2's shim, the CPU stand-in
@@ -11,7 +11,9 @@ results/gen_results.py is asked what it asks of its own runs:
     slice_req must be identical across the agents' files of an episode -- i.e. this build's exogenous inputs do not depend on
     the actions, and its files compare equal under np.array_equal the way the reference compares them;
   * calc_slice_violations / calc_intent_distance / calc_throughput_slice / calc_total_throughput (:770-1022) run on every file.
-Exit status 0 = all of it held.  tests/test_reference_goldens_r3.py runs this in a subprocess when the reference is there.
+Exit status 0 = all of it held.  With ``--write-golden`` the files that passed are then recorded in
+tests/golden/reference_readers.npz (per agent and episode: the agent's actions and every history field, the two
+RB x UE fields as per-UE sums), which tests/test_reference_goldens_r3.py replays without the reference.
 """
 from __future__ import annotations
 
@@ -77,6 +79,29 @@ def main():
             assert np.asarray(grs.calc_total_throughput(data, "pkt_effective_thr", np.arange(5))).shape[0] == steps
             n += 1
     print(f"fair_comparison_check passed for marr / mapf over {n_ep} episodes; {n} history files read by the reference's functions")
+    if "--write-golden" in sys.argv[1:]:
+        write_golden(steps, n_ep)
+
+
+def write_golden(steps, n_ep):
+    """The history files the reference's readers just accepted, as a fixture (run from the directory holding hist/)."""
+    import json
+    out = {"cfg": np.array([steps, n_ep])}
+    for name in ("marr", "mapf"):
+        for ep in range(n_ep):
+            data = np.load(f"hist/mult_slice/{name}/ep_{ep}.npz", allow_pickle=True)
+            p = f"{name}_ep{ep}_"
+            for k in data.files:
+                if k == "slice_req":
+                    out[p + k] = np.array(json.dumps([{s: (v["name"] if v else None) for s, v in r.items()} for r in data[k]]))
+                elif k in ("spectral_efficiencies", "sched_decision"):
+                    out[p + k + "_shape"] = np.array(data[k].shape)
+                    out[p + k + "_sum"] = data[k].sum(axis=-1)
+                else:
+                    out[p + k] = np.asarray(data[k], dtype=np.float64)
+    path = os.path.join(HERE, "reference_readers.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":

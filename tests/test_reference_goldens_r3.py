@@ -170,14 +170,66 @@ def test_what_separates_the_per_file_metrics_from_the_live_ones():
     assert A.shape == (3, 60, 4) and (A[:, :, 0] > 0).sum() > 100 and (A[:, :, 0] < A[:, :, 0].max()).sum() > 20
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/results"), reason="the reference is mounted in the build container only")
-def test_reference_result_scripts_read_this_builds_history_files():
-    """tests/golden/check_reference_readers.py in a subprocess (it puts the reference's packages and stand-ins into
-    sys.modules): the real MARR and MAPF play the same episodes on the facade with save_hist; the reference's own
-    fair_comparison_check (results/gen_results.py:1587-1635) then finds the exogenous inputs identical across the agents' files,
-    and its violation / distance / throughput functions read every file."""
-    import subprocess
-    import sys
-    out = subprocess.run([sys.executable, os.path.join(GOLDEN, "check_reference_readers.py")], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
-    assert "fair_comparison_check passed" in out.stdout
+def test_reference_result_scripts_read_this_builds_history_files(tmp_path, monkeypatch):
+    """tests/golden/reference_readers.npz holds the history files on which the reference's own readers passed when the
+    fixture was made (tests/golden/check_reference_readers.py --write-golden: the real MARR and MAPF played the same two
+    episodes on the facade with save_hist; fair_comparison_check, results/gen_results.py:1587-1635, found the exogenous inputs
+    identical across the agents' files, and its violation / distance / throughput functions read every file).  Here the
+    agents' recorded actions play the same episodes on the facade with this build's plugins and the CPU oracle under it; the
+    files written must be those files, field by field, and fair_comparison_check's condition must hold across them."""
+    import importlib.util
+    from intent_radio_sched_multi_slice_amd import comm_env
+    from intent_radio_sched_multi_slice_amd.history import HIST_KEYS
+    from tests.test_gpu_reference_agents import _Agent
+    spec = importlib.util.spec_from_file_location("gen_golden_agents", os.path.join(GOLDEN, "gen_golden_agents.py"))
+    gga = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gga)          # defines OracleDevice; its main() (which needs the reference) is not run
+    monkeypatch.setattr(comm_env, "BatchedRanEnv", gga.OracleDevice)
+    fx = load_golden("reference_readers")
+    steps, n_ep = (int(x) for x in fx["cfg"])
+    files = {}
+    for name, fixed in (("marr", 0), ("mapf", 1)):      # fixed intra-slice: MARR "rr" (marr.py:62-70), MAPF "pf" (mapf.py:126-134)
+        cfg = dict(comm_env.DEFAULT_CONFIGS["mult_slice"], max_number_steps=steps)
+        env = comm_env.MARLCommEnv(plugins.MimicQuadriga, plugins.MultSliceTraffic, plugins.SimpleMobility, plugins.MultSliceAssociation,
+                                   "mult_slice", name, 10, root_path=str(tmp_path), initial_episode_number=0, simu_name="mult_slice",
+                                   save_hist=True, max_episode_number=n_ep, enable_random_episodes=False, config=cfg, max_ues_slice=5)
+        ce = env.comm_env
+        S = ce.max_number_slices
+        agent = _Agent(env, ce.max_number_ues, S, ce.max_number_basestations, ce.num_available_rbs, max_ues_slice=5, rbs_per_rbg=5,
+                       sort=False)
+        env.set_agent_functions(agent.obs_space_format, agent.action_format, agent.calculate_reward, None, None)
+        env.reset(seed=10, options={"initial_episode": 0})
+        for ep in range(n_ep):
+            for t in range(steps):
+                action = {"player_0": fx[f"{name}_ep{ep}_agent_action"][t].copy()}
+                action.update({f"player_{s + 1}": fixed for s in range(S)})
+                env.step(action)
+            if ep + 1 < n_ep:
+                env.reset()
+            files[name, ep] = np.load(os.path.join(tmp_path, "hist", "mult_slice", name, f"ep_{ep}.npz"), allow_pickle=True)
+        env.close()
+    for (name, ep), data in files.items():
+        p = f"{name}_ep{ep}_"
+        assert set(data.files) == set(HIST_KEYS)
+        for k in HIST_KEYS:
+            v = data[k]
+            if k == "slice_req":
+                got = [{s: (r["name"] if r else None) for s, r in req.items()} for req in v]
+                assert got == json.loads(str(fx[p + k])), (name, ep)
+            elif k in ("spectral_efficiencies", "sched_decision"):
+                assert v.shape == tuple(fx[p + k + "_shape"]), (name, ep, k)
+                np.testing.assert_array_equal(v.sum(axis=-1), fx[p + k + "_sum"], err_msg=str((name, ep, k)))
+            elif k == "obs":
+                np.testing.assert_allclose(np.stack([o["player_0"]["observations"] for o in v]), fx[p + k], rtol=0, atol=1e-5)
+            elif k == "reward":
+                np.testing.assert_allclose([r["player_0"] for r in v], fx[p + k], rtol=0, atol=1e-9)
+            elif k == "agent_action":
+                np.testing.assert_array_equal(np.stack([a["player_0"] for a in v]), fx[p + k])
+            else:
+                np.testing.assert_array_equal(v, fx[p + k], err_msg=str((name, ep, k)))
+    for ep in range(n_ep):                               # what fair_comparison_check compares with np.array_equal
+        a, b = files["marr", ep], files["mapf", ep]
+        for k in ("pkt_incoming", "mobility", "spectral_efficiencies", "basestation_ue_assoc", "basestation_slice_assoc",
+                  "slice_ue_assoc"):
+            assert np.array_equal(a[k], b[k]), (ep, k)
+        assert json.loads(str(fx[f"marr_ep{ep}_slice_req"])) == json.loads(str(fx[f"mapf_ep{ep}_slice_req"]))

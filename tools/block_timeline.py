@@ -1,5 +1,5 @@
 """What a block of K TTIs between two device syncs spends outside the steady state: from a rocprofv3 --kernel-trace CSV of
-`bench.py --steps K --no-gather --no-single-stream --no-other-configs --no-cpu-baseline` (the headline's rollout: launches over 3 partitions,
+`bench.py --full --steps K --no-gather --no-single-stream --no-other-configs --no-cpu-baseline` (the headline's rollout: launches over 3 partitions,
 or -- rollouts of 16...64 TTIs, the auto rule -- one persistent launch per workgroup class).
     python tools/block_timeline.py <p_kernel_trace.csv> <K> [steady-state us per TTI]
 Launches of the step kernel are grouped into blocks (a pause of > 30 us on every queue = the host's sync between two blocks); per

@@ -10,7 +10,7 @@ REPS=${REPS:-2}
 for rep in $(seq 1 $REPS); do for spec in "$@"; do v=${spec%%@*}; n=$(basename $v .so); envs=""; xargs=""
   if [ "$spec" != "$v" ]; then IFS=, read -ra kv <<< "${spec#*@}"; for e in "${kv[@]}"; do if [ "${e%%=*}" = NAME ]; then n=${e#*=}; elif [ "${e:0:2}" = "--" ]; then xargs="$xargs ${e//:/ }"; else envs="$envs $e"; fi; done; fi
   for K in ${KS:-20 200}; do
-  env $envs RANENV_LIB=$PWD/$v timeout -k 10 300 python3 bench.py --steps $K --warmup $((K/4)) --no-cpu-baseline ${BENCH_FLAGS:---no-single-stream --no-other-configs} $xargs > $out/${n}_K${K}_r${rep}.json 2> $out/${n}_K${K}_r${rep}.err || { echo FAILED $spec; tail -3 $out/${n}_K${K}_r${rep}.err; exit 1; }
+  env $envs RANENV_LIB=$PWD/$v timeout -k 10 300 python3 bench.py --full --steps $K --warmup $((K/4)) --no-cpu-baseline ${BENCH_FLAGS:---no-single-stream --no-other-configs} $xargs > $out/${n}_K${K}_r${rep}.json 2> $out/${n}_K${K}_r${rep}.err || { echo FAILED $spec; tail -3 $out/${n}_K${K}_r${rep}.err; exit 1; }
 done; done; done
 python3 - "$out" "$@" <<'PY'
 import glob, json, sys, os

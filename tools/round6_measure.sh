@@ -15,15 +15,15 @@ step() {  # name timeout cmd...
 }
 if [ -z "$2" ] || [ "$2" = tests ]; then step pytest_gpu 900 python3 -m pytest tests -q -m gpu; fi
 if [ $part = all ] || [ $part = bench ]; then
-step bench 900 python3 bench.py
-step bench_driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5
-for K in 10 100; do step bench_k$K 300 python3 bench.py --steps $K --warmup $((K/4 + 1)) --no-cpu-baseline --no-other-configs; done
-RANENV_PERSIST=1 step bench_persist 600 python3 bench.py --no-cpu-baseline --no-other-configs
-step bench_cfg1 300 python3 bench.py --config 1 --no-cpu-baseline
-step bench_cfg4 300 python3 bench.py --config 4 --no-cpu-baseline
-step bench_native 400 python3 bench.py --config native --no-cpu-baseline
-step bench_philox 300 python3 bench.py --traffic philox --no-cpu-baseline --no-gather --no-other-configs
-step rehearse2 400 python3 bench.py --gpus 2 --rehearse-on-one-gpu --traces 40 --trace-len 100 --no-cpu-baseline --steps 20 --warmup 5
+step bench 900 python3 bench.py --full
+step bench_driver 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5
+for K in 10 100; do step bench_k$K 300 python3 bench.py --full --steps $K --warmup $((K/4 + 1)) --no-cpu-baseline --no-other-configs; done
+RANENV_PERSIST=1 step bench_persist 600 python3 bench.py --full --no-cpu-baseline --no-other-configs
+step bench_cfg1 300 python3 bench.py --full --config 1 --no-cpu-baseline
+step bench_cfg4 300 python3 bench.py --full --config 4 --no-cpu-baseline
+step bench_native 400 python3 bench.py --full --config native --no-cpu-baseline
+step bench_philox 300 python3 bench.py --full --traffic philox --no-cpu-baseline --no-gather --no-other-configs
+step rehearse2 400 python3 bench.py --full --gpus 2 --rehearse-on-one-gpu --traces 40 --trace-len 100 --no-cpu-baseline --steps 20 --warmup 5
 fi
 if [ $part = all ] || [ $part = pmc ]; then
 K=100; CALLS=2; TT=$((10 + K * CALLS))
@@ -45,10 +45,10 @@ python3 tools/pmc_summary.py $out/pmc_native_sq $out/pmc_native_sq2 > $out/pmc_n
 python3 tools/pmc_summary.py $out/pmc_config1_sq $out/pmc_config1_sq2 > $out/pmc_config1_summary.txt
 fi
 if [ $part = all ] || [ $part = prof ]; then
-step prof_stream 400 rocprofv3 --kernel-trace --stats -d $out/prof_stream -o p --output-format csv -- python3 bench.py --steps 200 --no-cpu-baseline --no-single-stream --no-gather --no-other-configs
-step prof_stream_k20 400 rocprofv3 --kernel-trace --stats -d $out/prof_stream_k20 -o p --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-single-stream --no-gather --no-other-configs
-step prof_gather 400 rocprofv3 --kernel-trace --stats -d $out/prof_gather -o p --output-format csv -- python3 bench.py --steps 200 --no-cpu-baseline --only-gather --no-other-configs
-step prof_steploop 400 rocprofv3 --kernel-trace -d $out/prof_steploop -o p --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-gather --no-other-configs
+step prof_stream 400 rocprofv3 --kernel-trace --stats -d $out/prof_stream -o p --output-format csv -- python3 bench.py --full --steps 200 --no-cpu-baseline --no-single-stream --no-gather --no-other-configs
+step prof_stream_k20 400 rocprofv3 --kernel-trace --stats -d $out/prof_stream_k20 -o p --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-single-stream --no-gather --no-other-configs
+step prof_gather 400 rocprofv3 --kernel-trace --stats -d $out/prof_gather -o p --output-format csv -- python3 bench.py --full --steps 200 --no-cpu-baseline --only-gather --no-other-configs
+step prof_steploop 400 rocprofv3 --kernel-trace -d $out/prof_steploop -o p --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-gather --no-other-configs
 python3 tools/steploop_timeline.py $out/prof_steploop/p_kernel_trace.csv 20 > $out/steploop_timeline.txt 2>&1 || python3 tools/steploop_timeline.py $(ls $out/prof_steploop/*/p_kernel_trace.csv | head -1) 20 > $out/steploop_timeline.txt 2>&1
 cat $out/steploop_timeline.txt
 fi

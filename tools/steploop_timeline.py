@@ -1,5 +1,5 @@
 """Where the trainer-facing schedules lose time: from a rocprofv3 --kernel-trace CSV of
-`bench.py --steps K --no-gather --no-other-configs --no-cpu-baseline` (headline rollout, then the env.step() loop -- one launch of
+`bench.py --full --steps K --no-gather --no-other-configs --no-cpu-baseline` (headline rollout, then the env.step() loop -- one launch of
 ranenv_core_kernel_mixed<NP, false, false> per TTI on one stream --, then the learner loop -- ranenv_core_kernel<0, NP, false> per range and
 TTI on the ranges' own streams, a torch policy kernel in between):
     python tools/steploop_timeline.py <p_kernel_trace.csv> [K]
