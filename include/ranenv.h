@@ -57,7 +57,9 @@ enum {
     RANENV_E_NOMEM = -4
 };
 
-enum { RANENV_POLICY_EXTERNAL = 0, RANENV_POLICY_MARR = 1, RANENV_POLICY_MAPF = 2 };
+enum { RANENV_POLICY_EXTERNAL = 0, RANENV_POLICY_MARR = 1, RANENV_POLICY_MAPF = 2, RANENV_POLICY_NETWORK = 3 };
+enum { RANENV_ACT_TANH = 0, RANENV_ACT_RELU = 1 };
+enum { RANENV_NET_IN_OBS = 0, RANENV_NET_IN_MASK_OBS = 1 };
 enum { RANENV_INTRA_RR = 0, RANENV_INTRA_PF = 1, RANENV_INTRA_MT = 2, RANENV_INTRA_PER_SLICE = 255 };
 enum { RANENV_SE_STREAM = 0, RANENV_SE_GATHER = 1 };
 enum { RANENV_METRIC_THROUGHPUT = 0, RANENV_METRIC_RELIABILITY = 1, RANENV_METRIC_LATENCY = 2 };
@@ -199,6 +201,52 @@ int ranenv_set_episodes(ranenv_handle h, const ranenv_episode *host_episodes, vo
 /* Inter-slice policy computed on the device when the step gets no scores, and the
  * intra-slice scheduler (RANENV_INTRA_PER_SLICE = take it from the step's intra_choice). */
 int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra);
+
+/* Trained policy networks on the device (RANENV_POLICY_NETWORK): IBSched's RLlib policy pair (agents/ib_sched.py:394-470,
+ * agents/ray_agent.py:338-345,409-430) as caller-supplied MLPs, run by one batched launch per net in front of every TTI that
+ * gets no inter-slice scores -- ranenv_step / _step_range / _step_part (for their env range, on their stream) and every TTI of
+ * ranenv_rollout (per partition, one TTI per launch, auto-reset included: the policy of the next TTI reads the new episode's
+ * first observation).  Its actions feed the step exactly as caller-made scores / intra choices would.
+ *
+ *   ranenv_mlp: n_hidden Linear + activation layers (1..4, widths 1..512), then one output Linear, torch's layout:
+ *     dims[0] input, dims[1..n_hidden] hidden widths, dims[n_hidden + 1] output; weight[i] float32 [dims[i+1]][dims[i]],
+ *     bias[i] float32 [dims[i+1]], device pointers (copied into a handle-owned packed buffer by ranenv_set_policy_network;
+ *     they may be freed afterwards).
+ *   inter net: input obs_inter [10*S] (RANENV_NET_IN_OBS), output [2*S] = (mean, log_std) of TorchActionMaskModel with
+ *     free_log_std off.  With the sorted mask m of adapters.sorted_action_mask (position j < S - sum(mask_inter) is masked;
+ *     agents/masked_action_distribution.py:30-36) the score at position j is -1 where masked, else
+ *       deterministic  clamp(mean_j, -1, 1)                       (normalize_actions maps Box[-1, 1] onto itself, then clips)
+ *       stochastic     clamp(mean_j + exp(log_std_j) * z_j, -1, 1)  (float64 arithmetic on the float32 outputs)
+ *   intra net (NULL = the fixed_intra of ranenv_set_policy): one row per (env, slice), input obs_intra[b][s] [2*Us+9]
+ *     (RANENV_NET_IN_OBS) or [mask_intra[b][s] as float (Us), obs_intra[b][s]] (RANENV_NET_IN_MASK_OBS: RLlib's flattened Dict,
+ *     keys sorted); output 3 logits (RR, PF, MT).  Deterministic: argmax (lowest index on ties); stochastic: the smallest i with
+ *     u * (e_0 + e_1 + e_2) < e_0 + ... + e_i, e_i = exp(l_i - max l) in float64.
+ *   Noise: out = Philox-4x32-10(counter = (env_id_base + env, episode_number[env], step_number[env], 0x504F4C00 + slice),
+ *     key = (seed lo, seed hi)) -- step_number as it is before the TTI the action is for, env_id_base that of
+ *     ranenv_set_traffic_generator (0 if never set) -- then
+ *       u1 = (out[0] + 1) * 2^-32,  u2 = out[1] * 2^-32,  z = sqrt(-2 ln u1) * cos(2 pi u2)   (double)
+ *       u  = out[2] * 2^-32                                                                    (intra draw)
+ *     a function of those numbers alone: independent of launches, partitions and ranges.
+ *   Layers are GEMMs on the f32-input matrix cores (exact f32 products, f32 accumulation); results match a float32 torch
+ *   forward to rounding, not bit for bit.
+ * ranenv_set_policy_network validates the shapes against S / Us (RANENV_E_INVALID); it does not change the policy:
+ * ranenv_set_policy(h, RANENV_POLICY_NETWORK, fixed_intra) does.  Under that policy a TTI without scores and without a bound
+ * net fails with RANENV_E_STATE, one without the obs_inter buffer (or obs_intra with an intra net) with RANENV_E_INVALID: the
+ * nets read the observation in those buffers.  stochastic != 0 samples, 0 takes the mode.
+ * ranenv_get_policy_actions: device pointers to the last actions, scores float64 [B][S] (the step's input: sorted positions
+ * as obs_inter lists the slices) and intra uint8 [B][S] (by slice index; NULL without an intra net). */
+typedef struct {
+    int32_t n_hidden;         /* 1..4                                          */
+    int32_t activation;       /* RANENV_ACT_TANH / RANENV_ACT_RELU              */
+    int32_t input_layout;     /* RANENV_NET_IN_OBS / RANENV_NET_IN_MASK_OBS     */
+    int32_t reserved;
+    int32_t dims[6];
+    const float *weight[5];
+    const float *bias[5];
+} ranenv_mlp;
+int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed,
+                              void *stream);
+int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra);
 
 /* CommunicationEnv.reset for the envs with env_mask[b] != 0 (NULL = all): fresh buffers,
  * step 0, observation of the zero raw state with the episode's first SE tile.

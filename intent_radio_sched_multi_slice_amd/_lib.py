@@ -12,7 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RANENV_LIB") or os.path.join(_HERE, "csrc", "libranenv_hip.so")
 
 ABI_VERSION = 9
-POLICY_EXTERNAL, POLICY_MARR, POLICY_MAPF = 0, 1, 2
+POLICY_EXTERNAL, POLICY_MARR, POLICY_MAPF, POLICY_NETWORK = 0, 1, 2, 3
+ACT_TANH, ACT_RELU = 0, 1
+NET_IN_OBS, NET_IN_MASK_OBS = 0, 1
+NET_MAX_HIDDEN, NET_MAX_WIDTH = 4, 512
 INTRA_RR, INTRA_PF, INTRA_MT, INTRA_PER_SLICE = 0, 1, 2, 255
 F_CLEAR_HISTORY_ON_RESET, F_NO_RAW_OUTPUT, F_SYNC_CHECK, F_SCALE_PER_ELEMENT = 0x1, 0x2, 0x4, 0x8
 SE_STREAM, SE_GATHER = 0, 1
@@ -28,6 +31,7 @@ EXPORTS = (
     "ranenv_step_range", "ranenv_set_se_mode", "ranenv_get_se_sidecars", "ranenv_step_part", "ranenv_wait_part",
     "ranenv_get_partition", "ranenv_get_part_stream", "ranenv_autoreset_part", "ranenv_set_option", "ranenv_get_option", "ranenv_profile_work", "ranenv_bind_se_gather_from_power",
     "ranenv_bind_se_pool_quad", "ranenv_se_retile_quad", "ranenv_packed_step_fits", "ranenv_selftest_ddiv",
+    "ranenv_set_policy_network", "ranenv_get_policy_actions",
 )
 
 
@@ -73,6 +77,12 @@ VIEW_FIELDS = (
     ("mask_inter", "i1", "BS"), ("mask_intra", "i1", "BSK"), ("policy_scores", "f8", "BS"),
     ("episode_number", "i4", "B"), ("episodes", "i4", "BE"),
 )
+
+
+class Mlp(C.Structure):
+    """ranenv_mlp: n_hidden Linear + activation layers and an output Linear, torch layout, device pointers."""
+    _fields_ = [("n_hidden", C.c_int32), ("activation", C.c_int32), ("input_layout", C.c_int32), ("reserved", C.c_int32),
+                ("dims", C.c_int32 * 6), ("weight", C.c_void_p * 5), ("bias", C.c_void_p * 5)]
 
 
 class Views(C.Structure):
@@ -144,6 +154,8 @@ def load() -> C.CDLL:
     lib.ranenv_packed_step_fits.argtypes = [C.POINTER(Config), C.c_int64, C.c_int64]
     lib.ranenv_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.ranenv_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+    lib.ranenv_set_policy_network.argtypes = [C.c_void_p, C.POINTER(Mlp), C.POINTER(Mlp), C.c_int32, C.c_uint64, C.c_void_p]
+    lib.ranenv_get_policy_actions.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     if lib.ranenv_abi_version() != ABI_VERSION:
         raise RanEnvError(f"ABI mismatch: library {lib.ranenv_abi_version()} != binding {ABI_VERSION}")
     _lib = lib

@@ -264,3 +264,118 @@ class MarlBatchEnv:
         term["__all__"] = d
         trunc = {p: torch.zeros_like(d) for p in term}
         return self._obs(), rew, term, trunc, {}
+
+
+# --------------------------------------------------------------------------------------------
+# trained IBSched policies on the device (RANENV_POLICY_NETWORK): the normative restatement and the checkpoint reader
+# --------------------------------------------------------------------------------------------
+POLICY_TAG = 0x504F4C00          # counter word c3 of the policy's Philox draws: tag + slice (include/ranenv.h)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox-4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11) on numpy arrays (broadcast): the generator of the device's
+    policy noise.  Returns four uint64 arrays holding 32-bit words."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = np.broadcast_arrays(*(np.asarray(c, dtype=np.uint64) & m32 for c in (c0, c1, c2, c3)))
+    k0, k1 = np.uint64(k0 & 0xFFFFFFFF), np.uint64(k1 & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0, c1, c2, c3
+
+
+def _mlp_forward(x: torch.Tensor, layers, activation: str) -> torch.Tensor:
+    act = torch.tanh if activation == "tanh" else torch.relu
+    for i, (w, b) in enumerate(layers):
+        x = x @ w.t() + b
+        if i < len(layers) - 1:
+            x = act(x)
+    return x
+
+
+def ibsched_policy_actions(obs_inter, mask_inter, inter, obs_intra=None, mask_intra=None, intra=None, stochastic: bool = False,
+                           seed: int = 0, intra_input: str = "obs", activation: Optional[str] = None, env_ids=None, episode=None,
+                           step=None):
+    """What the device computes under RANENV_POLICY_NETWORK, in plain torch / numpy (the normative statement the GPU tests
+    compare against; include/ranenv.h spells out the same rules).
+
+    ``obs_inter`` [B, 10*S], ``mask_inter`` [B, S]; ``obs_intra`` [B, S, 2*Us+9], ``mask_intra`` [B, S, Us] (intra net only);
+    nets as for ``batched_env.policy_net_layers``.  Forward in float32, epilogue in float64:
+      inter: (mean, log_std) = net(obs); with the sorted mask (``sorted_action_mask``) a masked position scores -1, the others
+             clamp(mean, -1, 1), or when ``stochastic`` clamp(mean + exp(log_std) * z, -1, 1) with z = Box-Muller of Philox words
+             0 and 1 at counter (env_ids + b, episode[b], step[b], POLICY_TAG + position), key = seed;
+      intra: argmax of the 3 logits (lowest index on ties), or the categorical draw of Philox word 2 at (..., POLICY_TAG + slice).
+    ``env_ids`` / ``episode`` / ``step``: [B] (the env's id base + index, views' episode_number and step_number before the TTI).
+    Returns (scores float64 [B, S], intra uint8 [B, S] or None) as CPU tensors."""
+    from .batched_env import policy_net_layers
+    obs_inter = torch.as_tensor(obs_inter).detach().cpu().to(torch.float32)
+    B, S = obs_inter.shape[0], obs_inter.shape[1] // 10
+    layers, act = policy_net_layers(inter, activation, 10 * S, 2 * S)
+    out = _mlp_forward(obs_inter, [(w.cpu(), b.cpu()) for w, b in layers], act).to(torch.float64)
+    mean, log_std = out[:, :S], out[:, S:]
+    masked = sorted_action_mask(torch.as_tensor(mask_inter).cpu()) == 0
+    draws = None
+    if stochastic:
+        if env_ids is None or episode is None or step is None:
+            raise ValueError("stochastic actions need env_ids, episode and step")
+        col = lambda a: np.asarray(torch.as_tensor(a).cpu().numpy(), dtype=np.int64).reshape(B, 1)  # noqa: E731
+        c3 = POLICY_TAG + np.arange(S, dtype=np.int64)[None, :]
+        draws = philox4x32_10(col(env_ids), col(episode), col(step), c3, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+        u1 = (draws[0].astype(np.float64) + 1.0) * 2.0 ** -32
+        u2 = draws[1].astype(np.float64) * 2.0 ** -32
+        z = torch.from_numpy(np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2))
+        mean = mean + torch.exp(log_std) * z
+    scores = torch.where(masked, torch.full_like(mean, -1.0), mean.clamp(-1.0, 1.0))
+    if intra is None:
+        return scores, None
+    obs_intra = torch.as_tensor(obs_intra).detach().cpu().to(torch.float32)
+    Us = (obs_intra.shape[-1] - 9) // 2
+    x = obs_intra.reshape(B * S, -1)
+    if intra_input == "mask_obs":
+        x = torch.cat([torch.as_tensor(mask_intra).cpu().reshape(B * S, Us).to(torch.float32), x], dim=1)
+    elif intra_input != "obs":
+        raise ValueError("intra_input must be 'obs' or 'mask_obs'")
+    il, iact = policy_net_layers(intra, activation, x.shape[1], 3)
+    lg = _mlp_forward(x, [(w.cpu(), b.cpu()) for w, b in il], iact).reshape(B, S, 3)
+    if not stochastic:
+        l0, l1, l2 = lg[..., 0], lg[..., 1], lg[..., 2]
+        ch = (l1 > l0).to(torch.uint8)
+        best = torch.where(l1 > l0, l1, l0)
+        ch = torch.where(l2 > best, torch.full_like(ch, 2), ch)
+        return scores, ch
+    ld = lg.to(torch.float64)
+    mx = ld.max(dim=-1, keepdim=True).values
+    e = torch.exp(ld - mx)
+    c0, c1 = e[..., 0], e[..., 0] + e[..., 1]
+    t = torch.from_numpy(draws[2].astype(np.float64) * 2.0 ** -32) * (c1 + e[..., 2])
+    ch = torch.where(t < c0, 0, torch.where(t < c1, 1, 2)).to(torch.uint8)
+    return scores, ch
+
+
+def rllib_fcnet_layers(state_dict, prefix: str = "internal_model."):
+    """The (W, b) layers of an RLlib ``FullyConnectedNetwork`` policy head from a torch state dict: keys
+    ``{prefix}_hidden_layers.{i}._model.0.{weight,bias}`` then ``{prefix}_logits._model.0.{weight,bias}`` (the value branch,
+    ``_value_branch*``, is not part of the actor and is skipped).  Any other key under ``prefix`` -- a free_log_std vector, a
+    different model class -- raises ValueError, as do missing layers.  Keys outside ``prefix`` are ignored.  The activation
+    is not in a state dict: RLlib's default ``fcnet_activation`` is "tanh"."""
+    hidden, logits = {}, {}
+    for key, val in state_dict.items():
+        if not key.startswith(prefix):
+            continue
+        rest = key[len(prefix):]
+        parts = rest.split(".")
+        if parts[0].startswith("_value_branch"):
+            continue
+        if len(parts) == 5 and parts[0] == "_hidden_layers" and parts[1].isdigit() and parts[2:4] == ["_model", "0"] \
+                and parts[4] in ("weight", "bias"):
+            hidden.setdefault(int(parts[1]), {})[parts[4]] = torch.as_tensor(val)
+        elif len(parts) == 4 and parts[0] == "_logits" and parts[1:3] == ["_model", "0"] and parts[3] in ("weight", "bias"):
+            logits[parts[3]] = torch.as_tensor(val)
+        else:
+            raise ValueError(f"not a FullyConnectedNetwork key: {key!r}")
+    if not hidden or set(logits) != {"weight", "bias"}:
+        raise ValueError(f"no FullyConnectedNetwork under {prefix!r}: hidden layers {sorted(hidden)}, logits {sorted(logits)}")
+    if sorted(hidden) != list(range(len(hidden))) or any(set(v) != {"weight", "bias"} for v in hidden.values()):
+        raise ValueError(f"hidden layers under {prefix!r} are incomplete: {sorted(hidden)}")
+    return [(hidden[i]["weight"], hidden[i]["bias"]) for i in range(len(hidden))] + [(logits["weight"], logits["bias"])]

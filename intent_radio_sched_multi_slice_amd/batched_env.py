@@ -24,11 +24,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (F_CLEAR_HISTORY_ON_RESET, F_NO_RAW_OUTPUT, F_SYNC_CHECK, INTRA_MT, INTRA_PER_SLICE, INTRA_PF, INTRA_RR,
-                   POLICY_EXTERNAL, POLICY_MAPF, POLICY_MARR, SE_GATHER, SE_STREAM, RanEnvError)
+from ._lib import (ACT_RELU, ACT_TANH, F_CLEAR_HISTORY_ON_RESET, F_NO_RAW_OUTPUT, F_SYNC_CHECK, INTRA_MT, INTRA_PER_SLICE, INTRA_PF,
+                   INTRA_RR, NET_IN_MASK_OBS, NET_IN_OBS, NET_MAX_HIDDEN, NET_MAX_WIDTH, POLICY_EXTERNAL, POLICY_MAPF, POLICY_MARR,
+                   POLICY_NETWORK, SE_GATHER, SE_STREAM, RanEnvError)
 from .scenario import MAX_AGE_CAP_DEFAULT, ScenarioTables
 
-_TORCH_DT = {"i1": torch.int8, "i4": torch.int32, "i8": torch.int64, "f8": torch.float64, "f4": torch.float32}
+_TORCH_DT = {"u1": torch.uint8, "i1": torch.int8, "i4": torch.int32, "i8": torch.int64, "f8": torch.float64, "f4": torch.float32}
 
 
 class _DevArray:
@@ -36,7 +37,7 @@ class _DevArray:
 
     def __init__(self, ptr: int, shape, typestr: str, owner):
         self.__cuda_array_interface__ = {
-            "shape": tuple(int(x) for x in shape), "typestr": "<" + typestr if typestr != "i1" else "|i1",
+            "shape": tuple(int(x) for x in shape), "typestr": "<" + typestr if typestr not in ("i1", "u1") else "|" + typestr,
             "data": (int(ptr), False), "version": 2, "strides": None,
         }
         self._owner = owner
@@ -44,6 +45,58 @@ class _DevArray:
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+NET_ACTIVATIONS = {"tanh": ACT_TANH, "relu": ACT_RELU}
+NET_INPUTS = {"obs": NET_IN_OBS, "mask_obs": NET_IN_MASK_OBS}
+
+
+def policy_net_layers(net, activation: Optional[str] = None, in_dim: Optional[int] = None, out_dim: Optional[int] = None):
+    """A policy MLP as the device runs it: ``([(W [out, in], b [out]), ...], activation)`` with float32 tensors, hidden layers
+    first, the output layer last.  ``net``: a ``torch.nn.Sequential`` of ``Linear`` layers with ``Tanh`` or ``ReLU`` between
+    them (one kind), or a list of ``(W, b)`` pairs with ``activation`` "tanh" (default: RLlib's and SB3's) or "relu".
+    Raises ValueError unless there are 1..4 hidden layers of widths 1..512, consecutive shapes chain, and the input / output
+    widths equal ``in_dim`` / ``out_dim`` where given."""
+    if isinstance(net, torch.nn.Module):
+        if not isinstance(net, torch.nn.Sequential):
+            raise ValueError("a policy net module must be a torch.nn.Sequential of Linear and Tanh / ReLU")
+        layers, acts, want_linear = [], set(), True
+        for m in net:
+            if isinstance(m, torch.nn.Linear) and want_linear:
+                b = m.bias if m.bias is not None else torch.zeros(m.out_features, device=m.weight.device)
+                layers.append((m.weight.detach(), b.detach()))
+            elif isinstance(m, (torch.nn.Tanh, torch.nn.ReLU)) and not want_linear:
+                acts.add("tanh" if isinstance(m, torch.nn.Tanh) else "relu")
+            else:
+                raise ValueError(f"unexpected module {type(m).__name__}: expected Linear, activation, Linear, ..., Linear")
+            want_linear = not want_linear
+        if want_linear or len(acts) > 1:
+            raise ValueError("a policy net ends with a Linear layer and uses one activation")
+        if activation is not None and acts and activation not in acts:
+            raise ValueError(f"activation {activation!r} given for a net with {acts.pop()!r}")
+        activation = acts.pop() if acts else activation
+    else:
+        layers = [(torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w),
+                   torch.as_tensor(np.asarray(b) if not isinstance(b, torch.Tensor) else b)) for w, b in net]
+    activation = "tanh" if activation is None else activation
+    if activation not in NET_ACTIVATIONS:
+        raise ValueError(f"unknown activation {activation!r} (tanh, relu)")
+    if not 2 <= len(layers) <= NET_MAX_HIDDEN + 1:
+        raise ValueError(f"{len(layers) - 1} hidden layers: 1..{NET_MAX_HIDDEN} are supported")
+    out = []
+    for i, (w, b) in enumerate(layers):
+        if w.dim() != 2 or b.dim() != 1 or b.shape[0] != w.shape[0]:
+            raise ValueError(f"layer {i}: weight {tuple(w.shape)} / bias {tuple(b.shape)} are not a Linear's [out, in] / [out]")
+        if i > 0 and w.shape[1] != out[-1][0].shape[0]:
+            raise ValueError(f"layer {i}: input width {w.shape[1]} after a layer of width {out[-1][0].shape[0]}")
+        if i < len(layers) - 1 and not 1 <= w.shape[0] <= NET_MAX_WIDTH:
+            raise ValueError(f"hidden width {w.shape[0]}: 1..{NET_MAX_WIDTH} are supported")
+        out.append((w.detach().to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous()))
+    if in_dim is not None and out[0][0].shape[1] != in_dim:
+        raise ValueError(f"input width {out[0][0].shape[1]}, the observation has {in_dim}")
+    if out_dim is not None and out[-1][0].shape[0] != out_dim:
+        raise ValueError(f"output width {out[-1][0].shape[0]}, expected {out_dim}")
+    return out, activation
 
 
 class BatchedRanEnv:
@@ -272,6 +325,54 @@ class BatchedRanEnv:
     def set_policy(self, policy: int = POLICY_EXTERNAL, fixed_intra: int = INTRA_PER_SLICE):
         self._check(self._lib.ranenv_set_policy(self._h, int(policy), int(fixed_intra)), "ranenv_set_policy")
         self.policy, self.fixed_intra = int(policy), int(fixed_intra)
+
+    def net_input_dims(self, intra_input: str = "obs"):
+        """Input widths of the policy nets: (inter, intra) for the intra input layout "obs" or "mask_obs"."""
+        if intra_input not in NET_INPUTS:
+            raise ValueError(f"intra_input must be one of {sorted(NET_INPUTS)}")
+        return 10 * self.S, self.W + (self.Us if intra_input == "mask_obs" else 0)
+
+    def set_policy_network(self, inter, intra=None, stochastic: bool = False, seed: int = 0, intra_input: str = "obs",
+                           activation: Optional[str] = None, fixed_intra: Optional[int] = None):
+        """Run trained IBSched policy nets on the device in front of every TTI (RANENV_POLICY_NETWORK, include/ranenv.h):
+        ``inter`` -> 2*S outputs (mean, log_std of the masked Gaussian), ``intra`` (None = ``fixed_intra``) -> 3 logits per
+        (env, slice) from ``obs_intra`` ("obs") or ``[mask_intra, obs_intra]`` ("mask_obs", RLlib's flattened Dict).  Nets as
+        for ``policy_net_layers``.  Switches the policy to NETWORK: ``step()`` / ``rollout()`` / ``evaluate()`` then need no
+        actions.  ``stochastic``: sample (Philox noise keyed by ``seed``) instead of taking the mode."""
+        in_inter, in_intra = self.net_input_dims(intra_input)
+        nets = [policy_net_layers(inter, activation, in_inter, 2 * self.S)]
+        if intra is not None:
+            nets.append(policy_net_layers(intra, activation, in_intra, 3))
+        structs, keep = [], []
+        for k, (layers, act) in enumerate(nets):
+            m = _lib.Mlp()
+            m.n_hidden, m.activation = len(layers) - 1, NET_ACTIVATIONS[act]
+            m.input_layout = NET_INPUTS[intra_input] if k == 1 else NET_IN_OBS
+            m.dims[0] = layers[0][0].shape[1]
+            for i, (w, b) in enumerate(layers):
+                w, b = w.to(self.device).contiguous(), b.to(self.device).contiguous()
+                keep += [w, b]
+                m.dims[i + 1] = w.shape[0]
+                m.weight[i], m.bias[i] = w.data_ptr(), b.data_ptr()
+            structs.append(m)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_set_policy_network(self._h, C.byref(structs[0]), C.byref(structs[1]) if intra is not None else None,
+                                                            1 if stochastic else 0, int(seed) & (2 ** 64 - 1), self._stream()),
+                        "ranenv_set_policy_network")
+        self._keep["policy_net"] = keep        # (the library copies on the current stream; keep the sources until it has)
+        self._policy_views = None
+        self.set_policy(POLICY_NETWORK, self.fixed_intra if fixed_intra is None else fixed_intra)
+
+    def policy_actions(self) -> Dict[str, Optional[torch.Tensor]]:
+        """Zero-copy views of the last actions of the policy nets: ``scores`` float64 [B, S] (what the step read, in the
+        sorted order of obs_inter) and ``intra`` uint8 [B, S] (by slice; None without an intra net)."""
+        if getattr(self, "_policy_views", None) is None:
+            sc, ic = C.c_void_p(), C.c_void_p()
+            self._check(self._lib.ranenv_get_policy_actions(self._h, C.byref(sc), C.byref(ic)), "ranenv_get_policy_actions")
+            self._policy_views = {
+                "scores": torch.as_tensor(_DevArray(sc.value, (self.B, self.S), "f8", self), device=self.device),
+                "intra": None if not ic.value else torch.as_tensor(_DevArray(ic.value, (self.B, self.S), "u1", self), device=self.device)}
+        return self._policy_views
 
     _EP_DTYPE = [("scenario", "<i4"), ("se_len", "<i4"), ("se_base", "<i8"), ("se_offset", "<i4"), ("trf_len", "<i4"),
                  ("trf_base", "<i8"), ("trf_offset", "<i4"), ("reserved", "<i4")]
@@ -593,7 +694,7 @@ class BatchedRanEnv:
         self.n_parts = int(n_parts)
 
     def rollout(self, n_steps: int):
-        """``n_steps`` TTIs under the device policy enqueued in one call (MARR / MAPF evaluation runs): the launches of
+        """``n_steps`` TTIs under the device policy enqueued in one call (MARR / MAPF / policy-network evaluation runs): the launches of
         ``n_steps`` calls of ``step()``, joined with the current stream only before the first and after the last TTI
         -- except that one launch takes its envs through up to n_steps / 4 (at most 10) TTIs where nothing has to happen in
         between (no head kernel; with auto-reset: up to the TTI at which an episode of the batch ends).  Same results bit

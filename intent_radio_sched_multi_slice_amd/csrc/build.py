@@ -1,8 +1,9 @@
 """Build libranenv_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
-Five objects, compiled in parallel, then linked:
+Six objects, compiled in parallel, then linked:
   ranenv_step.hip x 3   the builds of the step kernel for row widths NP = 8, 10, 16 (-DRANENV_NP=...)
   ranenv_aux.hip        the small kernels (class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination)
+  ranenv_policy.hip     the policy networks (RANENV_POLICY_NETWORK: MLP forwards on the f32 matrix cores)
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants
@@ -20,10 +21,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 HDR = os.path.join(REPO, "include", "ranenv.h")
 OUT = os.path.join(HERE, "libranenv_hip.so")
-SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_internal.h")
+SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_internal.h")
 # (object name, source, extra flags)
 UNITS = (("step_np10", "ranenv_step.hip", ("-DRANENV_NP=10",)), ("step_np8", "ranenv_step.hip", ("-DRANENV_NP=8",)),
-         ("step_np16", "ranenv_step.hip", ("-DRANENV_NP=16",)), ("aux", "ranenv_aux.hip", ()), ("host", "ranenv_host.cpp", ()))
+         ("step_np16", "ranenv_step.hip", ("-DRANENV_NP=16",)), ("aux", "ranenv_aux.hip", ()),
+         # (the policy network's MFMA accumulators in VGPRs: the library's kernels use no AGPRs, tests/test_kernel_resources.py)
+         ("policy", "ranenv_policy.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")), ("host", "ranenv_host.cpp", ()))
 CFLAGS = ("-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-pass-failed",
           "-ffp-contract=off",     # numpy rounds a*b and +c separately; fma() is written out where it is exact
           "-mllvm", "-amdgpu-atomic-optimizer-strategy=None",   # the kernel's few atomic adds come from one lane each

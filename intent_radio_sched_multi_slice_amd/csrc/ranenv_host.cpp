@@ -93,6 +93,12 @@ struct ranenv {
     std::vector<hipEvent_t> part_done, part_in;
     std::vector<int> part_lo;
     hipEvent_t ev_in = nullptr;
+    // policy networks (ranenv_set_policy_network): packed weights, and the actions the step reads under RANENV_POLICY_NETWORK
+    PolicyNet net_inter{}, net_intra{};
+    bool net_on = false, net_has_intra = false;
+    int net_stochastic = 0; unsigned long long net_seed = 0;
+    float *d_net_w = nullptr; long long net_cap = 0;      // floats
+    double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
     std::string err;
 };
 
@@ -1024,10 +1030,120 @@ int ranenv_set_episodes(ranenv_handle h, const ranenv_episode *eps, void *stream
 int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (policy < RANENV_POLICY_EXTERNAL || policy > RANENV_POLICY_MAPF) return fail(h, RANENV_E_INVALID, "unknown policy %d", policy);
+    if (policy < RANENV_POLICY_EXTERNAL || policy > RANENV_POLICY_NETWORK) return fail(h, RANENV_E_INVALID, "unknown policy %d", policy);
     if (!(fixed_intra == RANENV_INTRA_RR || fixed_intra == RANENV_INTRA_PF || fixed_intra == RANENV_INTRA_MT || fixed_intra == RANENV_INTRA_PER_SLICE))
         return fail(h, RANENV_E_INVALID, "unknown intra-slice scheduler %d", fixed_intra);
     h->kp.policy = policy; h->kp.fixed_intra = fixed_intra;
+    return RANENV_OK;
+}
+
+// ---- policy networks (RANENV_POLICY_NETWORK) --------------------------------------------------------------------------------
+// Validate one ranenv_mlp against the handle's sizes and lay it out in the packed buffer from float `off` on (widths padded to 32).
+static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNet &net, long long &off)
+{
+    const int S = h->cfg.n_slices, Us = h->cfg.max_ues_slice;
+    const char *who = intra ? "intra" : "inter";
+    if (m->n_hidden < 1 || m->n_hidden > NET_MAX_LAYERS - 1) return fail(h, RANENV_E_INVALID, "%s net: %d hidden layers (1..%d)", who, m->n_hidden, NET_MAX_LAYERS - 1);
+    if (m->activation != RANENV_ACT_TANH && m->activation != RANENV_ACT_RELU) return fail(h, RANENV_E_INVALID, "%s net: unknown activation %d", who, m->activation);
+    int in_dim = 10 * S;
+    if (!intra && m->input_layout != RANENV_NET_IN_OBS) return fail(h, RANENV_E_INVALID, "inter net: input layout %d (only RANENV_NET_IN_OBS)", m->input_layout);
+    if (intra) {
+        if (m->input_layout == RANENV_NET_IN_OBS) in_dim = 2 * Us + 9;
+        else if (m->input_layout == RANENV_NET_IN_MASK_OBS) in_dim = 3 * Us + 9;
+        else return fail(h, RANENV_E_INVALID, "intra net: unknown input layout %d", m->input_layout);
+    }
+    const int out_dim = intra ? 3 : 2 * S, L = m->n_hidden + 1;
+    if (m->dims[0] != in_dim) return fail(h, RANENV_E_INVALID, "%s net: input width %d, the observation has %d", who, m->dims[0], in_dim);
+    for (int i = 1; i < L; i++)
+        if (m->dims[i] < 1 || m->dims[i] > NET_MAX_WIDTH) return fail(h, RANENV_E_INVALID, "%s net: hidden width %d (1..%d)", who, m->dims[i], NET_MAX_WIDTH);
+    if (m->dims[L] != out_dim) return fail(h, RANENV_E_INVALID, "%s net: output width %d, expected %d", who, m->dims[L], out_dim);
+    for (int i = 0; i < L; i++)
+        if (!m->weight[i] || !m->bias[i]) return fail(h, RANENV_E_INVALID, "%s net: layer %d has no weight / bias", who, i);
+    net = PolicyNet{};
+    net.n_layers = L; net.act = m->activation; net.layout = m->input_layout; net.in_dim = in_dim; net.out_dim = out_dim;
+    for (int l = 0; l < L; l++) {
+        net.kp[l] = (m->dims[l] + 31) / 32 * 32; net.np[l] = (m->dims[l + 1] + 31) / 32 * 32;
+        net.w_off[l] = off; off += (long long)net.kp[l] * net.np[l];
+        net.b_off[l] = off; off += net.np[l];
+    }
+    return RANENV_OK;
+}
+
+static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, hipStream_t s)
+{
+    for (int l = 0; l < net.n_layers; l++) {
+        const int K = m->dims[l], N = m->dims[l + 1];
+        HIP_TRY(h, hipMemcpy2DAsync(h->d_net_w + net.w_off[l], sizeof(float) * net.kp[l], m->weight[l], sizeof(float) * K, sizeof(float) * K, N,
+                                    hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_net_w + net.b_off[l], m->bias[l], sizeof(float) * N, hipMemcpyDeviceToDevice, s));
+    }
+    return RANENV_OK;
+}
+
+// Under RANENV_POLICY_NETWORK a TTI without caller scores steps with the nets' actions: point kp at them.  1 = the nets must run
+// in front of the TTI, 0 = not this policy / caller scores, < 0 = error.
+static int net_use(ranenv_handle h, KP &kp)
+{
+    if (kp.scores || h->kp.policy != RANENV_POLICY_NETWORK) return 0;
+    if (!h->net_on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!kp.obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
+    if (h->net_has_intra && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
+    kp.scores = h->d_net_scores;
+    if (h->net_has_intra) { kp.intra = h->d_net_intra; kp.fixed_intra = RANENV_INTRA_PER_SLICE; }
+    return 1;
+}
+
+static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
+{
+    PolicyIO io{};
+    io.B = h->cfg.batch; io.S = h->cfg.n_slices; io.Us = h->cfg.max_ues_slice; io.W = 2 * io.Us + 9;
+    io.stochastic = h->net_stochastic; io.env_id_base = h->kp.env_id_base; io.seed = h->net_seed;
+    io.obs_inter = kp.obs_inter; io.obs_intra = kp.obs_intra;
+    io.mask_inter = ST_mask_inter(h->kp); io.mask_intra = ST_mask_intra(h->kp);
+    io.episode_no = ST_episode_no(h->kp); io.step_no = ST_step_no(h->kp);
+    io.scores = h->d_net_scores; io.intra = h->d_net_intra;
+    return launch_policy(s, h->net_inter, h->net_has_intra ? &h->net_intra : nullptr, io, e0, n);
+}
+
+int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice net is required (intra may be NULL)");
+    PolicyNet ni{}, na{};
+    long long off = 0;
+    int rc = net_layout(h, inter, false, ni, off);
+    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, true, na, off);
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream_;
+    const size_t BS = (size_t)h->cfg.batch * h->cfg.n_slices;
+    if (!h->d_net_scores) {
+        rc = dev_alloc(h, &h->d_net_scores, BS);
+        if (rc == RANENV_OK) rc = dev_alloc(h, &h->d_net_intra, BS);
+        if (rc != RANENV_OK) return rc;
+    }
+    if (off > h->net_cap) {
+        // (the launches of earlier TTIs may still read the old buffer: it stays allocated until ranenv_destroy)
+        rc = dev_alloc(h, &h->d_net_w, (size_t)off);
+        if (rc != RANENV_OK) return rc;
+        h->net_cap = off;
+    } else {
+        HIP_TRY(h, hipMemsetAsync(h->d_net_w, 0, sizeof(float) * (size_t)off, s));
+    }
+    ni.w = h->d_net_w; na.w = h->d_net_w;
+    rc = net_copy(h, inter, ni, s);
+    if (rc == RANENV_OK && intra) rc = net_copy(h, intra, na, s);
+    if (rc != RANENV_OK) return rc;
+    h->net_inter = ni; h->net_intra = na; h->net_has_intra = intra != nullptr;
+    h->net_stochastic = stochastic != 0; h->net_seed = seed; h->net_on = true;
+    return RANENV_OK;
+}
+
+int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra)
+{
+    if (!h || !dev_scores || !dev_intra) return fail(h, RANENV_E_INVALID, "null argument");
+    if (!h->net_on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
+    *dev_scores = h->d_net_scores; *dev_intra = h->net_has_intra ? h->d_net_intra : nullptr;
     return RANENV_OK;
 }
 
@@ -1071,9 +1187,13 @@ int ranenv_step(ranenv_handle h, const double *scores, const uint8_t *intra, con
     KP kp = h->kp;
     kp.env_mask = nullptr; kp.se_tiles = se_tiles; kp.scores = scores; kp.intra = intra; kp.traffic_bits = traffic_bits;
     kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = done;
+    const int net = net_use(h, kp);
+    if (net < 0) return net;
     rc = compact_for(h, kp, (hipStream_t)stream, &kp.compact);
     if (rc != RANENV_OK) return rc;
-    hipError_t e = launch<MODE_STEP>(h, kp, (hipStream_t)stream);
+    hipError_t e = net ? net_launch(h, kp, 0, h->cfg.batch, (hipStream_t)stream) : hipSuccess;
+    if (e != hipSuccess) return fail(h, RANENV_E_HIP, "policy network launch: %s", hipGetErrorString(e));
+    e = launch<MODE_STEP>(h, kp, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "step launch: %s", hipGetErrorString(e));
     shadow_steps_add(h, 0, h->cfg.batch, 1, done, (hipStream_t)stream);
     return RANENV_OK;
@@ -1111,9 +1231,12 @@ int ranenv_step_range(ranenv_handle h, int32_t env_first, int32_t env_count, con
     kp.env_mask = nullptr; kp.se_tiles = se_tiles; kp.scores = scores; kp.intra = intra; kp.traffic_bits = traffic_bits;
     kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = done;
     finalize_kp(h, kp);
+    const int net = net_use(h, kp);
+    if (net < 0) return net;
     rc = compact_for(h, kp, (hipStream_t)stream, &kp.compact);
     if (rc != RANENV_OK) return rc;
-    hipError_t e = launch_range<MODE_STEP>(h, kp, env_first, env_count, (hipStream_t)stream);
+    hipError_t e = net ? net_launch(h, kp, env_first, env_count, (hipStream_t)stream) : hipSuccess;
+    if (e == hipSuccess) e = launch_range<MODE_STEP>(h, kp, env_first, env_count, (hipStream_t)stream);
     if (e == hipSuccess && (h->cfg.flags & RANENV_F_SYNC_CHECK)) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "step launch (envs [%d,%d)): %s", env_first, env_first + env_count, hipGetErrorString(e));
     shadow_steps_add(h, env_first, env_first + env_count, 1, done, (hipStream_t)stream);
@@ -1339,7 +1462,7 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
     int rc = check_ready(h, nullptr, nullptr, true);
     if (rc != RANENV_OK) return rc;
     if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
-    if (h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "a rollout needs a device policy (ranenv_set_policy MARR / MAPF)");
+    if (h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "a rollout needs a device policy (ranenv_set_policy MARR / MAPF / NETWORK)");
     const bool have_se = h->kp.se_pool != nullptr || (h->se_mode == RANENV_SE_GATHER && h->d_se_mean != nullptr);
     if (!have_se || (!h->kp.trf_pool && !h->kp.trf_gen)) return fail(h, RANENV_E_STATE, "a rollout replays the bound SE pool and traffic pool / generator");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1351,6 +1474,9 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
     hipStream_t stream = (hipStream_t)stream_;
     h->last_rollout_persistent = 0; h->last_rollout_launches = 0;
     finalize_kp(h, kp);
+    // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
+    const int net = net_use(h, kp);
+    if (net < 0) return net;
     rc = compact_for(h, kp, stream, &kp.compact);
     if (rc != RANENV_OK) return rc;
     if (kp.compact) kp.compact = 2;                 // (2: the streaming kernels may step compactly too, see launch_range)
@@ -1390,7 +1516,7 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
     // (auto: not when episodes end at many different TTIs inside this call -- per-env episode lengths, envs reset at different times:
     // every episode end ends the persistent launches, re-sorts the envs and reads the class counts back; the launch-per-chunk
     // rollout follows the ends per partition without a host sync)
-    bool persist_ok = persist_wanted && !scale_per_element(h) && kp.compact != 0 && !(kp.head_obs || kp.head_reward) && (h->cfg.batch >> PERSIST_ENV_BITS) == 0 &&
+    bool persist_ok = persist_wanted && !net && !scale_per_element(h) && kp.compact != 0 && !(kp.head_obs || kp.head_reward) && (h->cfg.batch >> PERSIST_ENV_BITS) == 0 &&
                       !stream_capturing(stream);      // (it reads the class counts back)
     if (persist_ok && h->persist < 0 && follow) {
         std::vector<int> ends;
@@ -1438,7 +1564,7 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
     // the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more and lengthen the
     // drain at the rollout's end, where the workgroups that waited for a free slot run last and alone).
     int fuse = h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
-    if (kp.head_obs || kp.head_reward) fuse = 1;
+    if (kp.head_obs || kp.head_reward || net) fuse = 1;
     auto max_steps_of = [&](int b) { return h->host_max_steps.empty() ? h->cfg.max_steps : h->host_max_steps[(size_t)b]; };
     // Every partition walks through the n_steps TTIs in launches of its own: `pdone[k]` TTIs are enqueued for partition k.
     const int np = h->n_parts > 1 ? h->n_parts : 1;
@@ -1479,7 +1605,8 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
             KP kpk = kp;
             kpk.n_tti = n_tti;
             h->last_rollout_launches++;
-            hipError_t le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
+            hipError_t le = net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
+            if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
             if (le != hipSuccess || !follow) return le;
             bool any = false;
             for (int b = e0; b < e0 + n; b++) {

@@ -164,7 +164,32 @@ struct AdvanceArgs {
     const double *acc; double *ep_acc; int32_t *ep_n; int ep_slots;   // episode metrics: running sums -> per-episode log
 };
 
-enum { PERSIST_ENV_BITS = 20 };           // persistent rollout: queue item = env | TTIs done << 20
+// Policy network (ranenv_policy.hip): one MLP as packed in the handle's buffer.  Every width is padded with zeros to a multiple of
+// 32 (padded rows of W and entries of b are 0, so padded activations are act(0) = 0 and padded inputs add nothing).
+enum { NET_MAX_LAYERS = 5, NET_MAX_WIDTH = 512, NET_ROWS = 32 };   // NET_ROWS: GEMM rows (envs / env x slice) per workgroup
+struct PolicyNet {
+    const float *w;                       // packed [layer]: W [np][kp] row-major, then b [np]
+    long long w_off[NET_MAX_LAYERS], b_off[NET_MAX_LAYERS];
+    int kp[NET_MAX_LAYERS], np[NET_MAX_LAYERS];
+    int n_layers;                         // Linear layers: hidden ones + the output layer
+    int act;                              // RANENV_ACT_*
+    int layout;                           // RANENV_NET_IN_*
+    int in_dim, out_dim;                  // unpadded
+};
+struct PolicyIO {
+    int B, S, Us, W;                      // W = 2 * Us + 9
+    int stochastic, env_id_base;
+    unsigned long long seed;
+    const float *obs_inter, *obs_intra;
+    const int8_t *mask_inter, *mask_intra;
+    const int32_t *episode_no, *step_no;
+    double *scores; uint8_t *intra;
+};
+// Enqueue the inter net (and the intra net when `intra` is non-null) for envs [e0, e0 + n_envs).
+hipError_t launch_policy(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &, int e0, int n_envs);
+size_t policy_lds_bytes(const PolicyNet &);
+
+enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block
 
 // ---------------------------------------------------------------------------------------------

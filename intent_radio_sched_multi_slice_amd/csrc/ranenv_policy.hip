@@ -1,0 +1,188 @@
+// ranenv_policy.hip -- IBSched's trained policy networks on the device (RANENV_POLICY_NETWORK, include/ranenv.h): the inter-slice
+// actor (masked diagonal Gaussian, agents/action_mask_model.py + agents/masked_action_distribution.py) and the intra-slice actors
+// (Discrete(3), agents/ib_sched.py:394-470) as batched MLP forwards, one launch per net in front of a TTI.
+//
+// Every layer is a GEMM  Y[row][n] = act(sum_k X[row][k] W[n][k] + b[n])  with row = env (inter) or env x slice (intra), on the
+// f32-input matrix cores (v_mfma_f32_16x16x4_f32: exact f32 products, f32 accumulation).  A workgroup owns NET_ROWS = 32 rows: their
+// activations stay in LDS from the observation to the epilogue (two buffers of 32 x 516 floats at most), the weights are shared by
+// all workgroups and come from L2.  Its four waves take the layer's 32-column tiles in turn; a wave's tile is 2 x 2 MFMA blocks of
+// 16 x 16, four independent accumulators.  Per 16 k: one float4 of W per lane and block column (lane l: row c = l & 15 of the block,
+// k = 4 (l >> 4) .. + 3), one float4 of X per block row from LDS, 16 MFMAs -- MFMA j of the step sums k = 4q + j, the same
+// permutation on both operands.  The next W float4s are requested before the current step's MFMAs.
+#include "ranenv_numeric.hpp"
+
+#include <mutex>
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// LDS row stride in floats for a width x (a multiple of 32): = 4 mod 64, so that the 16 rows x 4 k of an operand load fall into
+// distinct banks
+__host__ __device__ inline int net_ld(int x) { return x + ((x & 63) ? 36 : 4); }
+
+__host__ __device__ inline int net_ld_max(const PolicyNet &net)
+{
+    int m = net_ld(net.np[net.n_layers - 1]);
+    for (int l = 0; l < net.n_layers; l++) m = net_ld(net.kp[l]) > m ? net_ld(net.kp[l]) : m;
+    return m;
+}
+
+// kind 0: inter net, n_rows = envs; kind 1: intra net, n_rows = envs x S (row g of the launch = env e0 + g / S, slice g % S)
+__global__ void __launch_bounds__(256) ranenv_policy_kernel(PolicyNet net, PolicyIO io, int kind, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = lane >> 4, c = lane & 15;
+    const int row0 = (int)blockIdx.x * NET_ROWS;
+    const int S = io.S;
+    float *cur = lds, *nxt = lds + NET_ROWS * net_ld_max(net);
+
+    // ---- observation rows -> LDS (zeros beyond the input and beyond the launch's rows) ----------------------------------
+    {
+        const int K0 = net.kp[0], ld0 = net_ld(K0);
+        for (int i = tid; i < NET_ROWS * K0; i += 256) {
+            const int r = i / K0, k = i - r * K0, g = row0 + r;
+            float v = 0.0f;
+            if (g < n_rows && k < net.in_dim) {
+                if (kind == 0) {
+                    v = io.obs_inter[(size_t)(e0 + g) * (size_t)(10 * S) + k];
+                } else {
+                    const size_t es = (size_t)e0 * S + g;
+                    if (net.layout == RANENV_NET_IN_MASK_OBS)
+                        v = k < io.Us ? (float)io.mask_intra[es * io.Us + k] : io.obs_intra[es * io.W + (k - io.Us)];
+                    else
+                        v = io.obs_intra[es * io.W + k];
+                }
+            }
+            cur[r * ld0 + k] = v;
+        }
+    }
+    __syncthreads();
+
+    // ---- layers ---------------------------------------------------------------------------------------------------------
+    for (int l = 0; l < net.n_layers; l++) {
+        const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N);
+        const bool last = l == net.n_layers - 1;
+        const float *W = net.w + net.w_off[l], *bias = net.w + net.b_off[l];
+        for (int nt = wave; nt < N / 32; nt += 4) {
+            f32x4 acc[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            const float4 *w0 = (const float4 *)(W + (size_t)(nt * 32 + c) * K) + q;
+            const float4 *w1 = (const float4 *)(W + (size_t)(nt * 32 + 16 + c) * K) + q;
+            const float *x0 = cur + c * ldi + 4 * q, *x1 = cur + (16 + c) * ldi + 4 * q;
+            float4 b0 = w0[0], b1 = w1[0];
+            for (int k0 = 0; k0 < K; k0 += 16) {
+                const int kn = (k0 + 16 < K ? k0 + 16 : k0) >> 2;
+                const float4 nb0 = w0[kn], nb1 = w1[kn];
+                const float4 a0 = *(const float4 *)(x0 + k0), a1 = *(const float4 *)(x1 + k0);
+                const float av[2][4] = {{a0.x, a0.y, a0.z, a0.w}, {a1.x, a1.y, a1.z, a1.w}};
+                const float bv[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+#pragma unroll
+                    for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                        for (int ni = 0; ni < 2; ni++)
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mi][j], bv[ni][j], acc[mi][ni], 0, 0, 0);
+                b0 = nb0; b1 = nb1;
+            }
+            // C/D map of the 16x16 block: column = lane & 15, row = 4 (lane >> 4) + register
+#pragma unroll
+            for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                for (int ni = 0; ni < 2; ni++) {
+                    const int col = nt * 32 + ni * 16 + c;
+                    const float bb = bias[col];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        float v = acc[mi][ni][r] + bb;
+                        if (!last) v = net.act == RANENV_ACT_RELU ? fmaxf(v, 0.0f) : tanhf(v);
+                        nxt[(mi * 16 + q * 4 + r) * ldo + col] = v;
+                    }
+                }
+        }
+        __syncthreads();
+        float *t = cur; cur = nxt; nxt = t;
+    }
+
+    // ---- epilogue: actions ----------------------------------------------------------------------------------------------
+    const int ld = net_ld(net.np[net.n_layers - 1]);
+    const unsigned k0 = (unsigned)io.seed, k1 = (unsigned)(io.seed >> 32);
+    if (kind == 0) {
+        for (int i = tid; i < NET_ROWS * S; i += 256) {
+            const int r = i / S, j = i - r * S, g = row0 + r;
+            if (g >= n_rows) continue;
+            const int e = e0 + g;
+            int n_act = 0;
+            for (int s = 0; s < S; s++) n_act += io.mask_inter[(size_t)e * S + s] != 0 ? 1 : 0;
+            double score = -1.0;                       // masked position (sorted mask: the first S - n_act positions)
+            if (j >= S - n_act) {
+                double m = (double)cur[r * ld + j];
+                if (io.stochastic) {
+                    unsigned o[4];
+                    philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], 0x504F4C00u + (unsigned)j,
+                                  k0, k1, o);
+                    const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
+                    const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+                    m = m + exp((double)cur[r * ld + S + j]) * z;
+                }
+                score = m < -1.0 ? -1.0 : (m > 1.0 ? 1.0 : m);
+            }
+            io.scores[(size_t)e * S + j] = score;
+        }
+    } else {
+        for (int r = tid; r < NET_ROWS; r += 256) {
+            const int g = row0 + r;
+            if (g >= n_rows) continue;
+            const size_t es = (size_t)e0 * S + g;
+            const int e = (int)(es / (size_t)S), s = (int)(es - (size_t)e * S);
+            const float l0 = cur[r * ld], l1 = cur[r * ld + 1], l2 = cur[r * ld + 2];
+            int ch = 0;
+            if (!io.stochastic) {
+                float best = l0;
+                if (l1 > best) { ch = 1; best = l1; }
+                if (l2 > best) ch = 2;
+            } else {
+                unsigned o[4];
+                philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], 0x504F4C00u + (unsigned)s,
+                              k0, k1, o);
+                const double mx = fmax(fmax((double)l0, (double)l1), (double)l2);
+                const double x0 = exp((double)l0 - mx), x1 = exp((double)l1 - mx), x2 = exp((double)l2 - mx);
+                const double c0 = x0, c1 = x0 + x1, t = (double)o[2] * 0x1p-32 * (c1 + x2);
+                ch = t < c0 ? 0 : (t < c1 ? 1 : 2);
+            }
+            io.intra[es] = (uint8_t)ch;
+        }
+    }
+}
+
+}  // namespace
+
+namespace ranenv_dev {
+
+size_t policy_lds_bytes(const PolicyNet &net) { return sizeof(float) * 2 * NET_ROWS * (size_t)net_ld_max(net); }
+
+hipError_t launch_policy(hipStream_t s, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &io, int e0, int n_envs)
+{
+    static std::once_flag once;
+    static hipError_t attr = hipSuccess;
+    std::call_once(once, [] {      // (up to 2 x 32 x 516 floats = 129 KB of dynamic LDS)
+        attr = hipFuncSetAttribute((const void *)ranenv_policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
+    });
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(ranenv_policy_kernel, dim3((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS)), dim3(256), policy_lds_bytes(inter), s,
+                       inter, io, 0, e0, n_envs);
+    if (intra) {
+        const int rows = n_envs * io.S;
+        hipLaunchKernelGGL(ranenv_policy_kernel, dim3((unsigned)((rows + NET_ROWS - 1) / NET_ROWS)), dim3(256), policy_lds_bytes(*intra), s,
+                           *intra, io, 1, e0, rows);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace ranenv_dev

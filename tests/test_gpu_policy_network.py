@@ -1,0 +1,326 @@
+"""Trained IBSched policy nets on the device (RANENV_POLICY_NETWORK): the kernel's actions against the torch restatement
+(adapters.ibsched_policy_actions), the env driven by them against the CPU oracle, and every schedule (step / rollout /
+partitions / auto-reset / evaluate) giving the same results."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+pytestmark = pytest.mark.gpu
+
+NETS = {"64x64": [64, 64], "512x3": [512, 512, 512]}
+SIZES = {"S10U100": dict(n_slices=10, n_ues=100, n_rbs=135, rbs_per_rbg=1, max_ues_slice=10),
+         "S5U25": dict(n_slices=5, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=10)}
+
+
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+
+
+def _workload(size, B, max_steps=1000, trace_len=64):
+    from intent_radio_sched_multi_slice_amd import _lib
+    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
+    return make_mult_slice_workload(B, torch.device("cuda", 0), policy=_lib.POLICY_MAPF, intra=_lib.INTRA_PF, n_scenarios=8,
+                                    n_traces=8, trace_len=trace_len, max_steps=max_steps, **SIZES[size])
+
+
+def _mlp(dims, act, seed):
+    g = torch.Generator().manual_seed(seed)
+    mods = []
+    for i in range(len(dims) - 1):
+        lin = torch.nn.Linear(dims[i], dims[i + 1])
+        with torch.no_grad():
+            bound = 1.0 / np.sqrt(dims[i])
+            lin.weight.copy_((torch.rand(lin.weight.shape, generator=g) * 2 - 1) * bound)
+            lin.bias.copy_((torch.rand(lin.bias.shape, generator=g) * 2 - 1) * bound)
+        mods.append(lin)
+        if i < len(dims) - 2:
+            mods.append(torch.nn.Tanh() if act == "tanh" else torch.nn.ReLU())
+    return torch.nn.Sequential(*mods)
+
+
+def _nets(env, widths, intra_input="obs", seed=5):
+    inter = _mlp([10 * env.S] + widths + [2 * env.S], "tanh", seed)
+    n_in = env.W + (env.Us if intra_input == "mask_obs" else 0)
+    intra = _mlp([n_in] + widths + [3], "relu", seed + 1)
+    return inter, intra
+
+
+def _snapshot(env):
+    v = env.views()
+    return dict(obs_inter=env.obs_inter.clone(), obs_intra=env.obs_intra.clone(), mask_inter=v["mask_inter"].clone(),
+                mask_intra=v["mask_intra"].clone(), episode=v["episode_number"].clone(), step=v["step_number"].clone())
+
+
+def _reference(env, snap, inter, intra, stochastic, seed, intra_input):
+    from intent_radio_sched_multi_slice_amd import adapters
+    return adapters.ibsched_policy_actions(snap["obs_inter"], snap["mask_inter"], inter, snap["obs_intra"], snap["mask_intra"], intra,
+                                           stochastic=stochastic, seed=seed, intra_input=intra_input,
+                                           env_ids=np.arange(env.B), episode=snap["episode"], step=snap["step"])
+
+
+def _intra_safe(env, snap, intra, stochastic, seed, intra_input):
+    """Rows whose choice is not within 1e-4 of a tie (top-two logit gap, or the draw's distance to a boundary)."""
+    from intent_radio_sched_multi_slice_amd import adapters
+    x = snap["obs_intra"].cpu().reshape(env.B * env.S, -1)
+    if intra_input == "mask_obs":
+        x = torch.cat([snap["mask_intra"].cpu().reshape(env.B * env.S, -1).float(), x], dim=1)
+    with torch.no_grad():
+        lg = intra(x).double().reshape(env.B, env.S, 3)
+    if not stochastic:
+        top = lg.sort(dim=-1, descending=True).values
+        return (top[..., 0] - top[..., 1]) > 1e-4
+    c0, c1, c2, _ = adapters.philox4x32_10(np.arange(env.B)[:, None], snap["episode"].cpu().numpy()[:, None],
+                                           snap["step"].cpu().numpy()[:, None], adapters.POLICY_TAG + np.arange(env.S)[None, :],
+                                           seed & 0xFFFFFFFF, seed >> 32)
+    p = torch.softmax(lg, dim=-1)
+    u = torch.from_numpy(c2.astype(np.float64) * 2.0 ** -32)
+    return ((u - p[..., 0]).abs() > 1e-4) & ((u - p[..., 0] - p[..., 1]).abs() > 1e-4)
+
+
+@pytest.mark.parametrize("stochastic", [False, True])
+@pytest.mark.parametrize("size", list(SIZES))
+@pytest.mark.parametrize("net", list(NETS))
+def test_forward_matches_restatement(net, size, stochastic):
+    _need_gpu()
+    B = 96
+    wl = _workload(size, B)
+    env = wl.env
+    intra_input = "mask_obs" if size == "S5U25" else "obs"
+    inter, intra = _nets(env, NETS[net], intra_input)
+    seed = 0x1234_5678_9ABC
+    env.set_policy_network(inter, intra, stochastic=stochastic, seed=seed, intra_input=intra_input)
+    env.reset()
+    checked = 0
+    for t in range(4):
+        snap = _snapshot(env)
+        env.step()
+        pa = env.policy_actions()
+        ref_s, ref_i = _reference(env, snap, inter, intra, stochastic, seed, intra_input)
+        dev_s = pa["scores"].cpu()
+        assert (dev_s.abs() <= 1.0).all()
+        torch.testing.assert_close(dev_s, ref_s, rtol=0, atol=1e-5)
+        # the step consumed exactly these scores
+        assert torch.equal(env.views()["policy_scores"].cpu(), dev_s)
+        safe = _intra_safe(env, snap, intra, stochastic, seed, intra_input)
+        dev_i = pa["intra"].cpu()
+        assert int(dev_i.max()) <= 2
+        assert torch.equal(dev_i[safe], ref_i[safe]), (t, int((dev_i[safe] != ref_i[safe]).sum()))
+        checked += int(safe.sum())
+    assert checked > 0.9 * 4 * B * env.S
+    env.close()
+
+
+@pytest.mark.parametrize("size", list(SIZES))
+@pytest.mark.parametrize("net", list(NETS))
+def test_env_parity_with_oracle(net, size):
+    """The device's own actions fed into the CPU oracle along 50 TTIs: integers exact, observation 1e-5, rewards 1e-9."""
+    _need_gpu()
+    from oracle import pyoracle
+    B, steps = 8, 50
+    wl = _workload(size, B, trace_len=64)
+    env = wl.env
+    inter, intra = _nets(env, NETS[net])
+    env.set_policy_network(inter, intra, stochastic=True, seed=3)
+    cfg = pyoracle.make_cfg(env.S, env.U, env.R, env.G, env.Us, max_steps=1000)
+    se_host = wl.se_pool.transpose(1, 2).contiguous().cpu().numpy()
+    trf_host = wl.traffic_pool.cpu().numpy().astype(np.float64)
+    eps = env.episodes
+    oenvs = []
+    for b in range(B):
+        e = pyoracle.OracleEnv(cfg)
+        e.set_scenario(wl.tables, int(wl.scenario[b]))
+        e.reset(se_host[int(eps["se_base"][b] + eps["se_offset"][b] % wl.trace_len)])
+        oenvs.append(e)
+    env.reset()
+    for t in range(steps):
+        obs, rew, done = env.step()
+        pa = env.policy_actions()
+        sc, ic = pa["scores"].cpu().numpy(), pa["intra"].cpu().numpy().astype(np.int32)
+        v = {k: x.cpu().numpy() for k, x in env.views().items()}
+        oi, rw = obs["obs_inter"].cpu().numpy(), rew.cpu().numpy()
+        for b, e in enumerate(oenvs):
+            tile = int(eps["se_base"][b] + (eps["se_offset"][b] + t) % wl.trace_len)
+            row = int(eps["trf_base"][b] + (eps["trf_offset"][b] + t) % wl.trace_len)
+            e.step(sc[b].copy(), ic[b].copy(), se_host[tile], trf_host[row])
+            raw, o = e.raw(), e.obs()
+            for k in ("pkt_effective_thr", "dropped_pkts", "pkt_throughputs"):
+                assert np.array_equal(v[k][b], raw[k]), (k, t, b)
+            np.testing.assert_allclose(oi[b], o["obs_inter"], rtol=0, atol=1e-5)
+            np.testing.assert_allclose(rw[b], o["reward"], rtol=0, atol=1e-9)
+    env.close()
+
+
+_KEYS = ("pkt_effective_thr", "dropped_pkts", "queue_pkts", "queue_age_sum", "rb_start", "rb_count", "win_sent", "step_number",
+         "episode_number", "policy_scores", "mask_inter", "mask_intra")
+
+
+def _episode_table(env):
+    eps = env.episodes
+    env.set_episode_table(scenario=eps["scenario"], se_base=eps["se_base"], se_len=eps["se_len"], se_offset=eps["se_offset"],
+                          trf_base=eps["trf_base"], trf_len=eps["trf_len"], trf_offset=eps["trf_offset"])
+    env.enable_autoreset(0, env.B, episode_numbers=np.arange(env.B, dtype=np.int32))
+
+
+def _same_state(a, b, tables):
+    va, vb = a.views(), b.views()
+    scen = va["episodes"][:, 0].to(torch.int64)                 # as on the device: auto-reset may have moved on
+    in_slice = torch.as_tensor(tables.ue_slice >= 0, device=a.device)[scen]
+    for k in _KEYS:
+        if k == "win_sent":      # of a UE outside every slice (after a reset into another scenario): read by no observation
+            assert torch.equal(va[k][in_slice], vb[k][in_slice]), k
+        else:
+            assert torch.equal(va[k], vb[k]), k
+    assert torch.equal(a.obs_inter, b.obs_inter) and torch.equal(a.obs_intra, b.obs_intra)
+    assert torch.equal(a.reward, b.reward) and torch.equal(a.done, b.done)
+    pa, pb = a.policy_actions(), b.policy_actions()
+    assert torch.equal(pa["scores"], pb["scores"]) and torch.equal(pa["intra"], pb["intra"])
+
+
+@pytest.mark.parametrize("autoreset", [False, True])
+@pytest.mark.parametrize("size", list(SIZES))
+@pytest.mark.parametrize("net", list(NETS))
+def test_rollout_equals_steps(net, size, autoreset):
+    """rollout(K) over 1, 2 and 3 partitions == K calls of step(), stochastic actions included; with auto-reset across
+    episode ends (episodes of 7 TTIs, K = 17)."""
+    _need_gpu()
+    B, K = 48, 17
+    max_steps = 7 if autoreset else 1000
+    wl = _workload(size, B, max_steps=max_steps)
+    ref = wl.env
+    inter, intra = _nets(ref, NETS[net])
+    ref.set_policy_network(inter, intra, stochastic=True, seed=11)
+    if autoreset:
+        _episode_table(ref)
+    ref.reset()
+    for _ in range(K):
+        ref.step()
+    for parts in (1, 2, 3):
+        env = _workload(size, B, max_steps=max_steps).env
+        env.set_policy_network(inter, intra, stochastic=True, seed=11)
+        if autoreset:
+            _episode_table(env)
+        env.set_partitions(parts)
+        env.reset()
+        env.rollout(K)
+        torch.cuda.synchronize()
+        assert env.get_option("last_rollout_persistent") == 0
+        _same_state(ref, env, wl.tables)
+        env.close()
+    ref.close()
+
+
+def test_stochastic_seed():
+    """The same seed reproduces the draws exactly, another seed changes them; deterministic mode ignores the seed."""
+    _need_gpu()
+    runs = {}
+    for key, (st, seed) in {"a": (True, 1), "a2": (True, 1), "b": (True, 2), "d1": (False, 1), "d2": (False, 2)}.items():
+        env = _workload("S5U25", 64).env
+        inter, intra = _nets(env, [64, 64])
+        env.set_policy_network(inter, intra, stochastic=st, seed=seed)
+        env.reset()
+        env.rollout(5)
+        pa = env.policy_actions()
+        runs[key] = (pa["scores"].cpu(), pa["intra"].cpu(), env.reward.cpu())
+        env.close()
+    assert all(torch.equal(x, y) for x, y in zip(runs["a"], runs["a2"]))
+    assert not torch.equal(runs["a"][0], runs["b"][0]) and not torch.equal(runs["a"][1], runs["b"][1])
+    assert all(torch.equal(x, y) for x, y in zip(runs["d1"], runs["d2"]))
+
+
+def test_policy_network_without_intra_net_uses_fixed_intra():
+    _need_gpu()
+    from intent_radio_sched_multi_slice_amd import _lib
+    a, b = _workload("S5U25", 32).env, _workload("S5U25", 32).env
+    inter, _ = _nets(a, [64, 64])
+    a.set_policy_network(inter, None, fixed_intra=_lib.INTRA_MT)
+    assert a.policy_actions()["intra"] is None
+    a.reset()
+    a.step()
+    b.set_policy(_lib.POLICY_EXTERNAL, _lib.INTRA_MT)
+    b.reset()
+    b.step(a.policy_actions()["scores"].clone())
+    for k in _KEYS:
+        assert torch.equal(a.views()[k], b.views()[k]), k
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("size", list(SIZES))
+def test_evaluate_equals_step_loop(size):
+    """evaluate() under the network policy (2 episodes per env) == a step() loop with auto-reset."""
+    _need_gpu()
+    B, n_ep, max_steps = 32, 2, 9
+    out = []
+    for mode in ("evaluate", "steps"):
+        env = _workload(size, B, max_steps=max_steps).env
+        inter, intra = _nets(env, [64, 64])
+        env.set_policy_network(inter, intra, stochastic=True, seed=9)
+        _episode_table(env)
+        env.enable_metrics(n_ep)
+        if mode == "evaluate":
+            res = env.evaluate(n_ep)
+        else:
+            env.reset()
+            for _ in range(n_ep * max_steps):
+                env.step()
+            torch.cuda.synchronize()
+            log = env.episode_metrics()["episode_log"][:, :n_ep].cpu().numpy()
+            res = {name: log[:, :, k] for k, name in enumerate(env.METRIC_NAMES)}
+        out.append(res)
+        env.close()
+    assert np.all(out[0]["ttis"] == max_steps)
+    for k in out[0]:
+        np.testing.assert_array_equal(out[0][k], out[1][k], err_msg=k)
+
+
+def test_error_paths():
+    _need_gpu()
+    from intent_radio_sched_multi_slice_amd import _lib
+    from intent_radio_sched_multi_slice_amd._lib import RanEnvError
+    env = _workload("S5U25", 16).env
+    lib, h = env._lib, env._h
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    env.set_policy(_lib.POLICY_NETWORK, _lib.INTRA_PF)
+    env.reset()
+    with pytest.raises(RanEnvError, match=r"\(-3\)"):
+        env.rollout(3)
+    with pytest.raises(RanEnvError, match=r"\(-3\)"):
+        env.step()
+    d, c = C.c_void_p(), C.c_void_p()
+    assert lib.ranenv_get_policy_actions(h, C.byref(d), C.byref(c)) == -3
+    # bad shapes straight through the C ABI: RANENV_E_INVALID, nothing bound
+    inter, intra = _nets(env, [64, 64])
+    keep = [p.detach().cuda().contiguous() for p in inter.parameters()]
+
+    def mlp(dims, n_hidden=1, act=_lib.ACT_TANH, layout=_lib.NET_IN_OBS):
+        m = _lib.Mlp()
+        m.n_hidden, m.activation, m.input_layout = n_hidden, act, layout
+        for i, x in enumerate(dims):
+            m.dims[i] = x
+        for i in range(5):
+            m.weight[i] = keep[0].data_ptr()
+            m.bias[i] = keep[1].data_ptr()
+        return m
+    S = env.S
+    bad = [mlp([10 * S + 1, 64, 2 * S]), mlp([10 * S, 600, 2 * S]), mlp([10 * S, 64, 2 * S + 1]), mlp([10 * S, 64, 2 * S], n_hidden=0),
+           mlp([10 * S, 8, 8, 8, 8, 8], n_hidden=5), mlp([10 * S, 64, 2 * S], act=7), mlp([10 * S, 64, 2 * S], layout=1)]
+    for m in bad:
+        assert lib.ranenv_set_policy_network(h, C.byref(m), None, 0, 0, stream) == -1
+    good = mlp([10 * S, 64, 2 * S])
+    assert lib.ranenv_set_policy_network(h, C.byref(good), C.byref(mlp([env.W, 64, 4])), 0, 0, stream) == -1
+    with pytest.raises(RanEnvError, match=r"\(-3\)"):
+        env.rollout(3)
+    # a bound net needs the observation buffers
+    env.set_policy_network(inter, intra)
+    assert lib.ranenv_rollout(h, 2, None, None, C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), stream) == -1
+    assert lib.ranenv_rollout(h, 2, C.c_void_p(env.obs_inter.data_ptr()), None, C.c_void_p(env.reward.data_ptr()),
+                              C.c_void_p(env.done.data_ptr()), stream) == -1
+    env.rollout(2)
+    torch.cuda.synchronize()
+    env.close()
