@@ -222,8 +222,8 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra);
  *     keys sorted); output 3 logits (RR, PF, MT).  Deterministic: argmax (lowest index on ties); stochastic: the smallest i with
  *     u * (e_0 + e_1 + e_2) < e_0 + ... + e_i, e_i = exp(l_i - max l) in float64.
  *   Noise: out = Philox-4x32-10(counter = (env_id_base + env, episode_number[env], step_number[env], 0x504F4C00 + slice),
- *     key = (seed lo, seed hi)) -- step_number as it is before the TTI the action is for, env_id_base that of
- *     ranenv_set_traffic_generator (0 if never set) -- then
+ *     key = (seed lo, seed hi)) -- step_number as it is before the TTI the action is for, env_id_base that of the last
+ *     ranenv_set_traffic_generator call that enabled the generator (0 if none; disabling it keeps the base) -- then
  *       u1 = (out[0] + 1) * 2^-32,  u2 = out[1] * 2^-32,  z = sqrt(-2 ln u1) * cos(2 pi u2)   (double)
  *       u  = out[2] * 2^-32                                                                    (intra draw)
  *     a function of those numbers alone: independent of launches, partitions and ranges.
@@ -404,7 +404,8 @@ int ranenv_get_views(ranenv_handle h, ranenv_views *out);
  * number, step, UE): a function of those alone, never of the actions (the reference checks that exogenous inputs
  * are identical across agents, results/gen_results.py:1587-1635).  Statistically, not bit-wise, equal to numpy's
  * Generator.poisson stream; an explicit dev_traffic_bits argument of a step still takes precedence.
- * Slice traffic must lie in (0, 128] Mbps (256-entry inversion tables, rebuilt whenever scenarios are loaded). */
+ * Slice traffic must lie in (0, 128] Mbps (256-entry inversion tables, rebuilt whenever scenarios are loaded).
+ * enable = 0 goes back to the traffic pool and ignores seed and env_id_base: the handle keeps the last env_id_base. */
 int ranenv_set_traffic_generator(ranenv_handle h, int32_t enable, uint64_t seed, int32_t env_id_base, void *stream);
 /* Diagnostic: copy the generator's inversion tables to the host: cdf [n_scenarios][S][256] uint64
  * (floor(P(X <= k) * 2^64)), guide [n_scenarios][S][64] uint8.  A draw is the smallest k with u < cdf[k], where

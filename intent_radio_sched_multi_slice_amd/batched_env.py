@@ -148,6 +148,7 @@ class BatchedRanEnv:
         self._p_out = (_ptr(self.obs_inter), _ptr(self.obs_intra), _ptr(self.reward), _ptr(self.done))
         self._step_fn = self._lib.ranenv_step
         self.policy, self.fixed_intra = POLICY_MARR, INTRA_RR      # the library's defaults (ranenv_create)
+        self.traffic_seed, self.env_id_base = None, 0
         self._recorder = None
         self._autoreset = False
         self.term_obs_inter = self.term_obs_intra = self.term_head_obs = None
@@ -395,11 +396,15 @@ class BatchedRanEnv:
     def set_traffic_generator(self, seed: int, env_id_base: int = 0, enable: bool = True):
         """Draw the offered traffic on the device -- Poisson(slice Mbps) * 1e6 bits per UE and TTI
         (traffics/mult_slice.py:24-32), Philox-4x32-10 keyed (seed; env_id_base + env, episode, step, UE) --
-        instead of replaying the traffic pool."""
+        instead of replaying the traffic pool.  ``enable=False`` goes back to the pool and keeps the last ``env_id_base``."""
         with torch.cuda.device(self.device):
             self._check(self._lib.ranenv_set_traffic_generator(self._h, 1 if enable else 0, int(seed) & (2 ** 64 - 1),
                                                                int(env_id_base), self._stream()), "ranenv_set_traffic_generator")
-        self.traffic_seed, self.env_id_base = (int(seed) & (2 ** 64 - 1), int(env_id_base)) if enable else (None, 0)
+        # (disabling keeps the env id base: the policy noise and the random auto-reset draws stay keyed by it)
+        if enable:
+            self.traffic_seed, self.env_id_base = int(seed) & (2 ** 64 - 1), int(env_id_base)
+        else:
+            self.traffic_seed = None
 
     def poisson_tables(self):
         """Diagnostic: the traffic generator's inversion tables -> (cdf uint64 [NS, S, 256], guide uint8 [NS, S, 64])."""
