@@ -767,8 +767,8 @@ class BatchedRanEnv:
         return {name: log[:, :, k].copy() for k, name in enumerate(self.METRIC_NAMES)}
 
     def set_option(self, key: str, value: int) -> None:
-        """A tuning / debug knob of the launch schedule (include/ranenv.h, "Options": compact, fuse, fuse_first0..9, late,
-        row_width, small_batch, persist).  None of them changes a result."""
+        """A tuning / debug knob of the launch schedule; the keys are the table "Options" in include/ranenv.h.  None of them
+        changes a result."""
         self._check(self._lib.ranenv_set_option(self._h, key.encode(), int(value)), f"ranenv_set_option({key})")
 
     def get_option(self, key: str) -> int:

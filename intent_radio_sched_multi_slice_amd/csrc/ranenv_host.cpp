@@ -25,13 +25,33 @@ struct ranenv {
     ranenv_config cfg;
     KP kp;
     std::vector<void *> allocs;
+    std::string err;
+    int nt = 0;                                 // threads of the core kernel (one per UE, whole waves)
+    int nslot = 0;                              // threads of the head kernel (one per slot, whole waves)
+    int n_cus = 256;                            // compute units of the device (ranenv_create)
+    // pools
+    bool have_scenarios = false;
+    int64_t se_tiles_n = 0, trf_rows_n = 0;   // extents of the bound pools (0 = none)
+    unsigned long long *d_pois_cdf = nullptr; uint8_t *d_pois_guide = nullptr;
+    std::vector<double> slice_traffic;          // [NS][S] host copy (traffic generator tables)
+    std::vector<int32_t> slice_has_req;
+    std::vector<int32_t> members_host; int32_t *d_members = nullptr;      // [NS] UEs in slices per scenario
+    // SE gather mode (ranenv_set_se_mode): sidecars of the bound pool, owned by the handle
+    int se_mode = RANENV_SE_STREAM;
+    double *d_se_mean = nullptr; float *d_se_um = nullptr; int se_rp = 0;
+    // compact steps (KP::compact): allowed while UEs outside every slice provably receive no traffic
+    bool idle_check_dirty = true, pool_idle_zero = false, table_idle_zero = false;
+    bool idle_state_clean = true;               // no step so far can have given an idle UE packets (else: full width until a full reset)
+    int *d_violations = nullptr;
+    // episodes and auto-reset
     ranenv_episode *d_episodes = nullptr;
-    bool have_scenarios = false, have_episodes = false;
+    bool have_episodes = false;
     ranenv_episode *d_ep_table = nullptr; int ep_table_first = 0, ep_table_n = 0;     // auto-reset: episode number -> descriptor
     int ar_initial = 0, ar_max = 0, ar_random = 0; unsigned long long ar_seed = 0; bool ar_on = false;
     uint8_t *d_ar_mask = nullptr;
-    double *d_acc = nullptr, *d_ep_acc = nullptr; int32_t *d_ep_n = nullptr; int ep_slots = 0;   // ranenv_enable_metrics
+    int32_t *d_max_steps = nullptr;
     std::vector<int32_t> host_max_steps;        // copy of ranenv_set_max_steps' array (the multi-episode rollout follows the step counters)
+    double *d_acc = nullptr, *d_ep_acc = nullptr; int32_t *d_ep_n = nullptr; int ep_slots = 0;   // ranenv_enable_metrics
     // Host shadow of the per-env step counters (what they will be once everything enqueued so far has run): `done` is a function of
     // the counter alone (step >= the env's episode length), so ranenv_autoreset knows WITHOUT reading anything back whether an episode
     // ended at the TTI just enqueued -- and enqueues nothing when none did (an RL loop calls it behind every step: three small launches
@@ -39,25 +59,7 @@ struct ranenv {
     // (a masked reset by the caller).
     std::vector<int32_t> sh_steps; bool sh_valid = false;
     const uint8_t *last_done = nullptr;         // the `done` buffer the steps write (the shortcut applies to that buffer only)
-    int autoreset_shortcut = 0;                 // option "autoreset_shortcut" (default 0: ranenv_autoreset reads dev_done, every env with a non-zero flag restarts)
-    unsigned long long *d_pois_cdf = nullptr; uint8_t *d_pois_guide = nullptr; int32_t *d_max_steps = nullptr;
-    std::vector<double> slice_traffic;          // [NS][S] host copy (traffic generator tables)
-    std::vector<int32_t> slice_has_req;
-    int64_t se_tiles_n = 0, trf_rows_n = 0;   // extents of the bound pools (0 = none)
-    // SE gather mode (ranenv_set_se_mode): sidecars of the bound pool, owned by the handle
-    int se_mode = RANENV_SE_STREAM;
-    double *d_se_mean = nullptr; float *d_se_um = nullptr; int se_rp = 0;
-    // compact steps (KP::compact): allowed while UEs outside every slice provably receive no traffic
-    int persist = -1;              // ranenv_rollout as one persistent work-queue launch per workgroup class (option "persist"):
-                                   // 0 never, 1 whenever possible, -1 (default) where it was measured to win: SE gather mode with a
-                                   // batch that fills the CUs, and either mode with a batch of <= 2 waves per SIMD
-    int persist_chunk = 10;        // TTIs of an env between two visits of the work queue
-    int n_cus = 256;               // compute units of the device (ranenv_create)
-    bool pack = true;              // two envs per wave where the sizes allow (option "pack")
-    int mix = 1;                   // whole-batch step launches of two-wave workgroups as mixed blocks (option "mix"): 0 never, 1 where the
-                                   // batch does not fit the chip anyway (auto), 2 also for batches that do (tests)
-    int persist_grid = 0;          // experiment: cap on the workgroups of a persistent launch, in wave slots (0 = what the chip holds)
-    std::vector<int32_t> members_host; int32_t *d_members = nullptr;      // [NS] UEs in slices per scenario
+    // persistent launches, and the class lists they share with mixed blocks
     int32_t *d_plist = nullptr, *d_pcount = nullptr; PersistCtl *d_pctl = nullptr; unsigned long long *d_pslots = nullptr;
     int p_nclass = 0, p_cap = 0;
     std::vector<int32_t> pcount_host; bool pclass_dirty = true, pcount_host_stale = true;
@@ -66,26 +68,8 @@ struct ranenv {
     int *h_perr = nullptr;         // sticky error word of the persistent launches, in host memory the device can write (a wait gave up)
     int *d_perr_dev = nullptr;     // ... its address as the device sees it
     int perr_seen = 0;             // ... what of it has been reported
-    int persist_inject = 0;        // test hook (option "persist_inject_abort"): the next persistent launch finds its abort word set
     int last_rollout_persistent = 0, last_rollout_launches = 0;   // what the last ranenv_rollout call ran (read-only options)
     int p_wave_slots[2] = {0, 0};  // wave slots per CU of the persistent kernel (streaming, gather build), from the occupancy query
-    long long prof_env_ttis = 0;   // env-TTIs covered by the launches timed since ranenv_profile_begin
-    int fuse = 0;                  // TTIs per launch inside ranenv_rollout: 0 = chosen per rollout, n = at most n (1 = off)
-    std::vector<int> fuse_first;   // override of the length of partition k's first launch of a rollout (RANENV_FUSE_FIRST=a,b,c)
-    long long prof_ttis = 0;       // TTIs covered by the launches timed since ranenv_profile_begin
-    bool compact_enabled = true, idle_check_dirty = true, pool_idle_zero = false, table_idle_zero = false;
-    bool idle_state_clean = true;               // no step so far can have given an idle UE packets (else: full width until a full reset)
-    int *d_violations = nullptr;
-    int nt = 0;                                 // threads of the core kernel (one per UE, whole waves)
-    int np = 16;                                // row width of the step kernel's build: max(S, Us) rounded up to 8, 10 or 16
-    int nslot = 0;                              // threads of the head kernel (one per slot, whole waves)
-    int tiny_step = 1;                          // option "tiny_step": one-TTI step launches of a batch at <= 2 waves per SIMD run the whole-row build
-    bool small_batch = false;                   // at most 8 workgroups per CU: the 128-VGPR build with the deeper SE queue
-    // ranenv_profile_begin / _end: the dispatch's own start / stop timestamps of every step-kernel launch
-    // (hipExtLaunchKernel's events: valid with further launches queued behind, unlike events recorded between launches)
-    bool prof_on = false;
-    std::vector<hipEvent_t> prof_ev;            // pairs (start, stop), one per launch
-    size_t prof_used = 0;
     // batch partitions (ranenv_set_partitions): envs [part_lo[k], part_lo[k+1]) are stepped by their own launch on
     // their own stream, so that one partition's ramp and tail run under the other partitions' steady state
     int n_parts = 1;
@@ -93,13 +77,36 @@ struct ranenv {
     std::vector<hipEvent_t> part_done, part_in;
     std::vector<int> part_lo;
     hipEvent_t ev_in = nullptr;
+    // ranenv_profile_begin / _end: the dispatch's own start / stop timestamps of every step-kernel launch
+    // (hipExtLaunchKernel's events: valid with further launches queued behind, unlike events recorded between launches)
+    bool prof_on = false;
+    std::vector<hipEvent_t> prof_ev;            // pairs (start, stop), one per launch
+    size_t prof_used = 0;
+    long long prof_ttis = 0;       // TTIs covered by the launches timed since ranenv_profile_begin
+    long long prof_env_ttis = 0;   // env-TTIs covered by the launches timed since ranenv_profile_begin
     // policy networks (ranenv_set_policy_network): packed weights, and the actions the step reads under RANENV_POLICY_NETWORK
     PolicyNet net_inter{}, net_intra{};
     bool net_on = false, net_has_intra = false;
     int net_stochastic = 0; unsigned long long net_seed = 0;
     float *d_net_w = nullptr; long long net_cap = 0;      // floats
     double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
-    std::string err;
+    // options (the table `options` below, include/ranenv.h "Options")
+    bool compact_enabled = true;                // option "compact"
+    int fuse = 0;                  // TTIs per launch inside ranenv_rollout: 0 = chosen per rollout, n = at most n (1 = off)
+    std::vector<int> fuse_first;   // override of the length of partition k's first launch of a rollout (RANENV_FUSE_FIRST=a,b,c)
+    int np = 16;                                // row width of the step kernel's build: max(S, Us) rounded up to 8, 10 or 16
+    bool small_batch = false;                   // at most 8 workgroups per CU: the 128-VGPR build with the deeper SE queue
+    int tiny_step = 1;                          // option "tiny_step": one-TTI step launches of a batch at <= 2 waves per SIMD run the whole-row build
+    int persist = -1;              // ranenv_rollout as one persistent work-queue launch per workgroup class (option "persist"):
+                                   // 0 never, 1 whenever possible, -1 (default) where it was measured to win: SE gather mode with a
+                                   // batch that fills the CUs, and either mode with a batch of <= 2 waves per SIMD
+    int persist_chunk = 10;        // TTIs of an env between two visits of the work queue
+    int persist_grid = 0;          // experiment: cap on the workgroups of a persistent launch, in wave slots (0 = what the chip holds)
+    bool pack = true;              // two envs per wave where the sizes allow (option "pack")
+    int mix = 1;                   // whole-batch step launches of two-wave workgroups as mixed blocks (option "mix"): 0 never, 1 where the
+                                   // batch does not fit the chip anyway (auto), 2 also for batches that do (tests)
+    int persist_inject = 0;        // test hook (option "persist_inject_abort"): the next persistent launch finds its abort word set
+    int autoreset_shortcut = 0;                 // option "autoreset_shortcut" (default 0: ranenv_autoreset reads dev_done, every env with a non-zero flag restarts)
 };
 
 namespace {
@@ -186,35 +193,29 @@ int build_poisson_tables(ranenv_handle h, hipStream_t stream)
     return RANENV_OK;
 }
 
-bool persist_tiny(ranenv_handle h);
 // RANENV_F_SCALE_PER_ELEMENT: every step / dense launch runs the lean build compiled for that convention -- no mixed blocks, packed
 // waves, small-batch / whole-row builds or persistent launches (those exist for the default convention only)
 bool scale_per_element(ranenv_handle h) { return (h->cfg.flags & RANENV_F_SCALE_PER_ELEMENT) != 0; }
 
-// The build of the step kernel for this handle and launch: SE gather or streaming (lean / small-batch / whole-row), one or several TTIs.
-template <int MODE>
-void launch_kernels(ranenv_handle h, const KP &kp, dim3 grid, dim3 block, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, bool gather)
+// A batch whose widest blocks all together stay within 2 waves per SIMD (8 per CU): one class, and -- streaming -- the build
+// with the whole SE row in flight.
+bool persist_tiny(ranenv_handle h)
 {
-    StepLaunch l;
-    l.np = h->np; l.mode = MODE; l.many = MODE == MODE_STEP && kp.n_tti > 1; l.gather = gather; l.build = SB_LEAN;
-    // RANENV_F_SCALE_PER_ELEMENT: the lean builds with the other rounding of the masked SE sum (MODE_PE); a reset sums no masked row
-    if (MODE != MODE_RESET && scale_per_element(h)) {
-        if (gather && MODE != MODE_STEP) return;
-        l.mode = MODE | MODE_PE; l.build = gather ? SB_GATHER : SB_LEAN;
-    } else if (gather) {
-        if (MODE == MODE_DENSE) return;
-        l.build = SB_GATHER;
-    } else if (MODE == MODE_STEP && !l.many && h->tiny_step && persist_tiny(h)) {      // a batch at <= 2 waves per SIMD: the whole-row build
-        l.build = SB_TINY1;
-    } else if (h->small_batch) {
-        l.build = SB_SMALL;
-    }
-    (void)launch_step(l, grid, block, stream, ev0, ev1, kp);
+    return (long long)h->cfg.batch * (h->nt / WAVE) <= 8ll * h->n_cus;
 }
 
+bool stream_capturing(hipStream_t stream)      // (an error of the query itself counts as "capturing": the careful path)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); return true; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// Must the handle's other streams wait for `stream`?  Not when it holds nothing: then no signal has to cross between two hardware
+// queues.  (hipStreamQuery is illegal on a capturing stream: a caller that graph-captures its step keeps the event.)
+bool stream_busy(hipStream_t stream) { return stream_capturing(stream) || hipStreamQuery(stream) != hipSuccess; }
+
 int persist_prepare(ranenv_handle h, hipStream_t stream, bool need_host_counts);
-bool persist_tiny(ranenv_handle h);
-bool stream_capturing(hipStream_t stream);
 
 // Packed waves address a per-env row as (uniform array base) + (32-bit row + lane offset), see row_at<2>: every array they
 // address that way must stay below 4 GB.  True for every size a packed step makes sense at (the reference's: megabytes); a handle
@@ -233,72 +234,81 @@ bool pack_fits_32_of(const ranenv_config &cfg, long long trf_rows_n, long long s
 }
 bool pack_fits_32(ranenv_handle h) { return pack_fits_32_of(h->cfg, h->trf_rows_n, h->se_tiles_n); }
 
-// One launch of the step kernel for envs [e0, e0 + n) on `stream` (+ the head kernel when bound).
-template <int MODE>
-hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t stream)
+// Under ranenv_profile_begin: the next (start, stop) pair of the event pool, for a launch of n envs through n_tti TTIs
+hipError_t prof_events(ranenv_handle h, int n, int n_tti, hipEvent_t *ev0, hipEvent_t *ev1)
 {
-    kp.e0 = e0;
-    const dim3 grid((unsigned)n), block((unsigned)h->nt);
-    // SE gather mode: tiles replayed from the pool are read through the sidecars; explicit per-step tiles and dense
-    // sched_decisions (whole rows are needed) keep the streaming kernel
-    bool gather = false;
-    if constexpr (MODE != MODE_DENSE) gather = h->se_mode == RANENV_SE_GATHER && kp.se_tiles == nullptr;
+    *ev0 = nullptr; *ev1 = nullptr;
+    if (!h->prof_on) return hipSuccess;
+    while (h->prof_ev.size() < h->prof_used + 2) {
+        hipEvent_t e = nullptr;
+        const hipError_t ce = hipEventCreate(&e);
+        if (ce != hipSuccess) return ce;
+        h->prof_ev.push_back(e);
+    }
+    *ev0 = h->prof_ev[h->prof_used]; *ev1 = h->prof_ev[h->prof_used + 1];
+    h->prof_used += 2; h->prof_ttis += n_tti; h->prof_env_ttis += (long long)n * n_tti;
+    return hipSuccess;
+}
+
+// The build of the step kernel for one launch of envs [e0, e0 + n), with its grid and block; `kp` gets what every kernel of the
+// launch reads from it (the compact flag, the SE gather sidecars).  SB_MIXED: the class lists are the caller's to sort and bind.
+struct StepPlan { StepLaunch l; dim3 grid, block; };
+template <int MODE>
+StepPlan step_plan(ranenv_handle h, KP &kp, int e0, int n, bool gather)
+{
+    // RANENV_F_SCALE_PER_ELEMENT: the lean builds with the other rounding of the masked SE sum (MODE_PE); a reset sums no masked row
+    const bool pe = MODE != MODE_RESET && scale_per_element(h);
+    const bool many = MODE == MODE_STEP && kp.n_tti > 1;
     // Compact steps pay off for the gather kernels throughout (-3...-7 %).  The streaming kernels want lane = UE: their row
     // loads are coalesced in that order (a wave reads 256 contiguous bytes per RB; slice members first scatters its lanes
     // over the whole 400-byte row), so they step compactly only where it was measured to win: under ranenv_rollout's
     // overlapping partitions (-4 %; +15 % for two alternating ranges, +1.5 % for one launch per TTI).
     // Mixed blocks (ranenv_core_kernel_mixed): the whole batch in one launch of one block per wide env + one per two narrow envs -- all of it
     // resident in one round.  For launches of the whole batch of two-wave workgroups, where a compact step is exact.
+    // (whole-batch launches only: for the ranges of a partitioned batch per-range lists were built and measured -- two alternating
+    // ranges 47.8 against 48.0 us per TTI in gather mode, and the streaming kernel loses the lane = UE order it wants there: dropped)
     bool mixed = false;
-    if constexpr (MODE == MODE_STEP) {
-        // (whole-batch launches only: for the ranges of a partitioned batch per-range lists were built and measured -- two alternating
-        // ranges 47.8 against 48.0 us per TTI in gather mode, and the streaming kernel loses the lane = UE order it wants there: dropped)
-        mixed = !scale_per_element(h) && h->mix != 0 && kp.compact != 0 && h->nt == 2 * WAVE && e0 == 0 && n == h->cfg.batch && kp.env_mask == nullptr &&
+    if constexpr (MODE == MODE_STEP)
+        mixed = !pe && h->mix != 0 && kp.compact != 0 && h->nt == 2 * WAVE && e0 == 0 && n == h->cfg.batch && kp.env_mask == nullptr &&
                 (h->mix == 2 || !persist_tiny(h)) && RANENV_DIAG == 0;
-        if (mixed && persist_prepare(h, stream, false) != RANENV_OK) return hipErrorUnknown;
-    }
     if (!mixed && !gather && kp.compact != 2) kp.compact = 0;
     if (kp.compact) kp.compact = 1;
     if (gather) {
         kp.se_pool = h->d_se_um; kp.se_stride = (long long)h->cfg.n_ues * h->se_rp;
         kp.se_mean_pool = h->d_se_mean; kp.se_rp = h->se_rp;
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (h->prof_on) {                              // two more events from the pool
-        while (h->prof_ev.size() < h->prof_used + 2) {
-            hipEvent_t e = nullptr;
-            const hipError_t ce = hipEventCreate(&e);
-            if (ce != hipSuccess) return ce;
-            h->prof_ev.push_back(e);
-        }
-        ev0 = h->prof_ev[h->prof_used]; ev1 = h->prof_ev[h->prof_used + 1];
-        h->prof_used += 2;
-        h->prof_ttis += MODE == MODE_STEP ? kp.n_tti : 1;
-        h->prof_env_ttis += (long long)n * (MODE == MODE_STEP ? kp.n_tti : 1);
+    const dim3 grid((unsigned)n), block((unsigned)h->nt);
+    if (mixed) return {{h->np, SB_MIXED, MODE_STEP, many, gather}, grid, dim3(2 * WAVE)};      // (grid: an upper bound of wide + ceil(narrow / 2))
+    // packed waves: two envs per wave for envs of <= 32 UEs / <= 8 slices (see ranenv_core_kernel_packed)
+    if (MODE == MODE_STEP && !pe && h->pack && h->np == 8 && h->cfg.n_ues <= 32 && h->nt == WAVE && (n & 1) == 0 && kp.env_mask == nullptr && pack_fits_32(h))
+        return {{8, SB_PACKED, MODE_STEP, many, gather}, dim3((unsigned)(n / 2)), dim3(WAVE)};
+    // SE gather mode, else -- one-TTI steps of a batch at <= 2 waves per SIMD -- the whole-row build, else the small-batch or the lean build
+    StepLaunch l{h->np, SB_LEAN, pe ? MODE | MODE_PE : MODE, many, gather};
+    if (gather) l.build = SB_GATHER;
+    else if (!pe && MODE == MODE_STEP && !many && h->tiny_step && persist_tiny(h)) l.build = SB_TINY1;
+    else if (!pe && h->small_batch) l.build = SB_SMALL;
+    return {l, grid, block};
+}
+
+// One launch of the step kernel for envs [e0, e0 + n) on `stream` (+ the head kernel when bound).
+template <int MODE>
+hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t stream)
+{
+    kp.e0 = e0;
+    // SE gather mode: tiles replayed from the pool are read through the sidecars; explicit per-step tiles and dense
+    // sched_decisions (whole rows are needed) keep the streaming kernel
+    const bool gather = MODE != MODE_DENSE && h->se_mode == RANENV_SE_GATHER && kp.se_tiles == nullptr;
+    const StepPlan p = step_plan<MODE>(h, kp, e0, n, gather);
+    KP ks = kp;
+    if (p.l.build == SB_MIXED) {
+        if (persist_prepare(h, stream, false) != RANENV_OK) return hipErrorUnknown;
+        ks.p_list = h->d_plist + (size_t)h->cfg.batch; ks.m_list = h->d_plist; ks.m_counts = h->d_pcount;
     }
-    if constexpr (MODE == MODE_STEP) {
-        if (mixed) {
-            const int B = h->cfg.batch;
-            KP kq = kp;
-            kq.p_list = h->d_plist + (size_t)B; kq.m_list = h->d_plist; kq.m_counts = h->d_pcount;
-            const dim3 mgrid((unsigned)n), mblock((unsigned)(2 * WAVE));       // (an upper bound of wide + ceil(narrow / 2))
-            const StepLaunch l{h->np, SB_MIXED, MODE_STEP, kq.n_tti > 1, gather};
-            (void)launch_step(l, mgrid, mblock, stream, ev0, ev1, kq);
-            if (kp.head_obs || kp.head_reward) launch_head(stream, grid, dim3((unsigned)h->nslot), kp);
-            return hipGetLastError();
-        }
-        // packed waves: two envs per wave for envs of <= 32 UEs / <= 8 slices (see ranenv_core_kernel_packed)
-        if (!scale_per_element(h) && h->pack && h->np == 8 && h->cfg.n_ues <= 32 && h->nt == WAVE && (n & 1) == 0 && kp.env_mask == nullptr && pack_fits_32(h)) {
-            KP kq = kp;
-            const dim3 pgrid((unsigned)(n / 2)), pblock((unsigned)WAVE);
-            const StepLaunch l{8, SB_PACKED, MODE_STEP, kq.n_tti > 1, gather};
-            (void)launch_step(l, pgrid, pblock, stream, ev0, ev1, kq);
-            if (kp.head_obs || kp.head_reward) launch_head(stream, grid, dim3((unsigned)h->nslot), kp);
-            return hipGetLastError();
-        }
-    }
-    launch_kernels<MODE>(h, kp, grid, block, stream, ev0, ev1, gather);
-    if (kp.head_obs || kp.head_reward) launch_head(stream, grid, dim3((unsigned)h->nslot), kp);
+    hipEvent_t ev0, ev1;
+    const hipError_t pe = prof_events(h, n, MODE == MODE_STEP ? kp.n_tti : 1, &ev0, &ev1);
+    if (pe != hipSuccess) return pe;
+    (void)launch_step(p.l, p.grid, p.block, stream, ev0, ev1, ks);
+    if (kp.head_obs || kp.head_reward) launch_head(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp);
     return hipGetLastError();
 }
 
@@ -351,13 +361,7 @@ hipError_t for_partitions(ranenv_handle h, hipStream_t stream, bool join_in, boo
         if (h->cfg.flags & RANENV_F_SYNC_CHECK) return hipStreamSynchronize(stream);
         return hipSuccess;
     }
-    // (nothing pending on the caller's stream = nothing for the partitions to wait for: no event round trip between the queues)
-    // (hipStreamQuery is illegal on a capturing stream: a caller that graph-captures its step keeps the event)
-    if (join_in) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-        if (cs == hipStreamCaptureStatusNone && hipStreamQuery(stream) == hipSuccess) join_in = false;
-    }
+    join_in = join_in && stream_busy(stream);
     if (join_in) {
         le = hipEventRecord(h->ev_in, stream);
         if (le != hipSuccess) return le;
@@ -384,14 +388,28 @@ hipError_t for_partitions(ranenv_handle h, hipStream_t stream, bool join_in, boo
     return hipSuccess;
 }
 
-void finalize_kp(ranenv_handle, KP &kp) { kp.n_tti = 1; }      // (what every launch of a call shares: one TTI unless ranenv_rollout says more)
-
 template <int MODE>
-hipError_t launch(ranenv_handle h, KP kp, hipStream_t stream, bool join_in = true, bool join_out = true)
+hipError_t launch(ranenv_handle h, const KP &kp, hipStream_t stream)
 {
-    finalize_kp(h, kp);
-    return for_partitions(h, stream, join_in, join_out,
-                          [&](int e0, int n, hipStream_t s) { return launch_range<MODE>(h, kp, e0, n, s); });
+    return for_partitions(h, stream, true, true, [&](int e0, int n, hipStream_t s) { return launch_range<MODE>(h, kp, e0, n, s); });
+}
+
+// A call's kernel arguments: the handle's, with every per-call input null, the call's outputs, and one TTI (ranenv_rollout says more)
+KP call_kp(ranenv_handle h, float *obs_inter, float *obs_intra, double *reward, uint8_t *done)
+{
+    KP kp = h->kp;
+    kp.env_mask = nullptr; kp.se_tiles = nullptr; kp.scores = nullptr; kp.intra = nullptr; kp.traffic_bits = nullptr; kp.dense = nullptr;
+    kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = done;
+    kp.n_tti = 1;
+    return kp;
+}
+
+// The reset behind a step (auto-reset): the envs whose episode ended restart.  The step's rewards and done flags stay, those of the
+// alternative heads too (head_obs gets the new episode's first observation); full width.
+KP reset_behind(ranenv_handle h, KP kp)
+{
+    kp.env_mask = h->d_ar_mask; kp.reward = nullptr; kp.done = nullptr; kp.head_reward = nullptr; kp.compact = 0;
+    return kp;
 }
 
 // Auto-reset: the arguments of the advance kernel for this handle's tables and the caller's buffers
@@ -455,20 +473,6 @@ hipError_t ensure_streams(ranenv_handle h, size_t n)      // handle-owned stream
     }
     if (!h->ev_in) return hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming);
     return hipSuccess;
-}
-
-// A batch whose widest blocks all together stay within 2 waves per SIMD (8 per CU): one class, and -- streaming -- the build
-// with the whole SE row in flight.
-bool persist_tiny(ranenv_handle h)
-{
-    return (long long)h->cfg.batch * (h->nt / WAVE) <= 8ll * h->n_cus;
-}
-
-bool stream_capturing(hipStream_t stream)      // (an error of the query itself counts as "capturing": the careful path)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); return true; }
-    return cs != hipStreamCaptureStatusNone;
 }
 
 // The buffers of the work queues (once per handle) and, whenever scenarios / episodes changed, the envs sorted by class.
@@ -538,11 +542,9 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
     const int B = h->cfg.batch, NC = h->p_nclass;
     const bool gather = h->se_mode == RANENV_SE_GATHER;
     kp.n_tti = n_tti; kp.compact = 1; kp.e0 = 0;
-    // (a chunk is always shorter than the launch: an env's FIRST chunk is then 1...chunk TTIs long by a hash of its index, and the envs
-    // reach their chunk ends -- a wait for their stores, a look at the queues -- at different TTIs instead of never: there they find the env cursors exhausted
-    // and remember it; without a chunk end all workgroups finish together and walk the 8 exhausted cursors with 41 000 device-scope fetch-adds.  Measured, round 6: rollouts of
-    // 6 / 8 / 10 TTIs with the default chunk of 10 cost 8-9 % MORE than the launch-per-chunk rollout, with a chunk below the rollout's length
-    // 6-7 % LESS, profiles/r06_ab_log.txt)
+    // (a chunk is always shorter than the launch, so that the envs reach a chunk end inside it and find the exhausted env cursors
+    // there, at different TTIs: without one all workgroups finish together and walk those cursors at once -- DESIGN.md 4.4, "Short
+    // rollouts", profiles/r06_ab_log.txt)
     kp.p_chunk = h->persist_chunk < n_tti ? h->persist_chunk : (n_tti > 1 ? n_tti - 1 : 1);
     kp.p_cap = h->p_cap; kp.p_err = h->d_perr_dev;
     if (gather) {
@@ -564,14 +566,8 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
     if (demand == 0) return RANENV_OK;
     hipError_t e = ensure_streams(h, (size_t)(n_used > 1 ? n_used : 1));
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "persistent rollout, streams: %s", hipGetErrorString(e));
-    // (the other classes' streams pick up behind what the caller's stream holds -- unless it holds nothing: then there is nothing to
-    // wait for, and no signal has to cross between two hardware queues before the largest class may start; not while capturing)
-    bool join_in = n_used > 1;
-    if (join_in) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-        if (cs == hipStreamCaptureStatusNone && hipStreamQuery(stream) == hipSuccess) join_in = false;
-    }
+    // (the other classes' streams pick up behind what the caller's stream holds)
+    const bool join_in = n_used > 1 && stream_busy(stream);
     if (join_in) HIP_TRY(h, hipEventRecord(h->ev_in, stream));
     int k = 0;                                     // stream index: 0 = the caller's
     for (int c = NC - 1; c >= 0; c--) {
@@ -583,28 +579,19 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
         hipStream_t s = k == 0 ? stream : h->part_stream[(size_t)k];
         if (k > 0 && join_in) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_in, 0));
         KP kc = kp;
-        // (the envs are NOT bound to workgroups statically, although at B 4096 the grids equal the class sizes -- 5119 of 5120 wave slots: two-wave blocks
-        // do not pack perfectly among one-wave blocks, a few dozen workgroups start late, and an env bound to one of those would wait for a whole
-        // rollout of somebody else; through the cursors the resident workgroups pick those envs up at their chunk ends.  Measured, round 6:
-        // block i <- list[i] costs +21 % per TTI at K = 20 and +27 % at K = 200 in gather mode, profiles/r06_ab_log.txt.  Nor is a launch ever ONE chunk,
-        // not even for a batch whose every env has a resident workgroup of its own (configs[1]: round 5 ran those as one chunk): see kp.p_chunk above --
-        // with chunks configs[1] steps 1.2-1.5 % faster at K = 10 / 20)
+        // (the envs are NOT bound to workgroups statically, although at B 4096 the grids equal the class sizes: a few dozen workgroups
+        // start late, and an env bound to one of those would wait for a whole rollout of somebody else -- DESIGN.md 4.4,
+        // profiles/r06_ab_log.txt.  Nor is a launch ever ONE chunk, not even for a batch whose every env has a resident workgroup of its
+        // own (configs[1]): see kp.p_chunk above)
         kc.p_list = h->d_plist + (size_t)c * B; kc.p_count = n; kc.p_ctl = h->d_pctl + c;
         kc.p_slots = h->d_pslots + (size_t)c * 8 * (size_t)h->p_cap;
         if (h->persist_inject) {                   // test hook: this launch finds a wait already given up
             const int one = 1;
             HIP_TRY(h, hipMemcpyAsync(&kc.p_ctl->abort, &one, sizeof(int), hipMemcpyHostToDevice, s));      // (the DEVICE then raises the host-visible word)
         }
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (h->prof_on) {
-            while (h->prof_ev.size() < h->prof_used + 2) {
-                hipEvent_t pe = nullptr;
-                HIP_TRY(h, hipEventCreate(&pe));
-                h->prof_ev.push_back(pe);
-            }
-            ev0 = h->prof_ev[h->prof_used]; ev1 = h->prof_ev[h->prof_used + 1];
-            h->prof_used += 2; h->prof_ttis += n_tti; h->prof_env_ttis += (long long)n * n_tti;
-        }
+        hipEvent_t ev0, ev1;
+        e = prof_events(h, n, n_tti, &ev0, &ev1);
+        if (e != hipSuccess) return fail(h, RANENV_E_HIP, "hipEventCreate(&pe): %s", hipGetErrorString(e));
         const dim3 grid((unsigned)g), block((unsigned)((c + 1) * WAVE));
         (void)launch_step(StepLaunch{h->np, (!gather && tiny) ? SB_PERSIST_TINY : SB_PERSIST, MODE_STEP, true, gather}, grid, block, s, ev0, ev1, kc);
         if (k > 0) HIP_TRY(h, hipEventRecord(h->part_done[(size_t)k], s));
@@ -619,46 +606,98 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
     return RANENV_OK;
 }
 
-// Tuning / debug options (include/ranenv.h, "Options"): ONE setter behind ranenv_set_option, and ONE place where the
+// Replace the SE gather sidecars by fresh ones for nt tiles (the old ones are released first, behind a device synchronisation), and
+// enqueue fill(t0, n) for tiles [t0, t0 + n) in chunks that keep grid.x far below its limit.  A failed fill launch is the caller's to report.
+template <typename Fill>
+int se_sidecars_rebuild(ranenv_handle h, size_t nt, Fill fill)
+{
+    const int U = h->cfg.n_ues, Rp = (h->cfg.n_rbs + 7) & ~7;
+    auto drop = [&](void *ptr) {
+        if (!ptr) return;
+        for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == ptr) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
+        (void)hipFree(ptr);
+    };
+    HIP_TRY(h, hipDeviceSynchronize());
+    drop(h->d_se_mean); drop(h->d_se_um); h->d_se_mean = nullptr; h->d_se_um = nullptr;
+    void *pm = nullptr, *pu = nullptr;
+    hipError_t e = hipMalloc(&pm, nt * (size_t)U * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&pu, nt * (size_t)U * (size_t)Rp * sizeof(float));
+    if (e != hipSuccess) {
+        if (pm) (void)hipFree(pm);
+        return fail(h, RANENV_E_NOMEM, "SE gather sidecars (%zu tiles: %.2f GB): %s", nt,
+                    (double)(nt * (size_t)U * (8 + 4 * (size_t)Rp)) / 1e9, hipGetErrorString(e));
+    }
+    h->allocs.push_back(pm); h->allocs.push_back(pu);
+    h->d_se_mean = (double *)pm; h->d_se_um = (float *)pu; h->se_rp = Rp;
+    for (size_t t0 = 0; t0 < nt; t0 += 1u << 20) fill(t0, nt - t0 < (1u << 20) ? nt - t0 : (size_t)(1u << 20));
+    return RANENV_OK;
+}
+
+// Tuning / debug options (include/ranenv.h, "Options"): ONE table of the keys behind ranenv_set_option / _get_option, and ONE place where the
 // process environment is read (ranenv_create -> apply_env_options: RANENV_<KEY IN CAPITALS>=value presets the same
 // options for handles created afterwards; the test suite and the A/B tools run whole passes under them).
 // None of them changes a result: they select a launch schedule or a build of the step kernel.
+struct Option {
+    const char *key;
+    bool env;                                   // preset from RANENV_<KEY IN CAPITALS>
+    int (*set)(ranenv_handle, long long);       // stores a value, clamped / normalised, or refuses it
+    long long (*get)(ranenv_handle);            // reads it back (null: not readable)
+};
+using H = ranenv_handle;
+const Option options[] = {
+    {"compact", true, [](H h, long long v) { h->compact_enabled = v != 0; return 0; }, [](H h) -> long long { return h->compact_enabled ? 1 : 0; }},
+    {"fuse", true, [](H h, long long v) { h->fuse = v < 0 ? 0 : (v > 64 ? 64 : (int)v); return 0; }, [](H h) -> long long { return h->fuse; }},
+    {"row_width", true, [](H h, long long v) {
+         const int m = h->cfg.n_slices > h->cfg.max_ues_slice ? h->cfg.n_slices : h->cfg.max_ues_slice;
+         if (!((v == 8 || v == 10 || v == 16) && v >= m))
+             return fail(h, RANENV_E_INVALID, "row_width must be 8, 10 or 16 and >= max(S, Us) = %d", m);
+         h->np = (int)v;
+         return 0;
+     }, [](H h) -> long long { return h->np; }},
+    {"small_batch", true, [](H h, long long v) { h->small_batch = v != 0; return 0; }, [](H h) -> long long { return h->small_batch ? 1 : 0; }},
+    {"tiny_step", true, [](H h, long long v) { h->tiny_step = v != 0 ? 1 : 0; return 0; }, [](H h) -> long long { return h->tiny_step; }},
+    {"persist", true, [](H h, long long v) { h->persist = v < 0 ? -1 : (v != 0 ? 1 : 0); return 0; }, [](H h) -> long long { return h->persist; }},
+    {"persist_chunk", true, [](H h, long long v) { h->persist_chunk = v < 1 ? 1 : (v > 1000 ? 1000 : (int)v); return 0; },
+     [](H h) -> long long { return h->persist_chunk; }},
+    {"persist_grid", true, [](H h, long long v) { h->persist_grid = v < 0 ? 0 : (int)v; return 0; }, [](H h) -> long long { return h->persist_grid; }},
+    {"pack", true, [](H h, long long v) { h->pack = v != 0; return 0; }, [](H h) -> long long { return h->pack ? 1 : 0; }},
+    {"mix", true, [](H h, long long v) { h->mix = v < 0 ? 0 : (v > 2 ? 2 : (int)v); h->pclass_dirty = true; return 0; },
+     [](H h) -> long long { return h->mix; }},
+    // test hook, see persist_check_errors
+    {"persist_inject_abort", false, [](H h, long long v) { h->persist_inject = v != 0 ? 1 : 0; return 0; }, nullptr},
+    {"autoreset_shortcut", true, [](H h, long long v) { h->autoreset_shortcut = v != 0 ? 1 : 0; return 0; },
+     [](H h) -> long long { return h->autoreset_shortcut; }},
+};
+
+const Option *find_option(const std::string &k)
+{
+    for (const Option &o : options) if (k == o.key) return &o;
+    return nullptr;
+}
+
+// "fuse_first0" ... "fuse_first9": the index, else -1
+int fuse_first_index(const std::string &k)
+{
+    return k.rfind("fuse_first", 0) == 0 && k.size() == 11 && k[10] >= '0' && k[10] <= '9' ? k[10] - '0' : -1;
+}
+
 int set_option(ranenv_handle h, const std::string &k, long long v)
 {
-    if (k == "compact") { h->compact_enabled = v != 0; return RANENV_OK; }
-    if (k == "fuse") { h->fuse = v < 0 ? 0 : (v > 64 ? 64 : (int)v); return RANENV_OK; }
-    if (k == "row_width") {
-        const int m = h->cfg.n_slices > h->cfg.max_ues_slice ? h->cfg.n_slices : h->cfg.max_ues_slice;
-        if (!((v == 8 || v == 10 || v == 16) && v >= m))
-            return fail(h, RANENV_E_INVALID, "row_width must be 8, 10 or 16 and >= max(S, Us) = %d", m);
-        h->np = (int)v;
-        return RANENV_OK;
-    }
-    if (k == "small_batch") { h->small_batch = v != 0; return RANENV_OK; }
-    if (k == "tiny_step") { h->tiny_step = v != 0 ? 1 : 0; return RANENV_OK; }
-    if (k == "persist") { h->persist = v < 0 ? -1 : (v != 0 ? 1 : 0); return RANENV_OK; }
-    if (k == "persist_chunk") { h->persist_chunk = v < 1 ? 1 : (v > 1000 ? 1000 : (int)v); return RANENV_OK; }
-    if (k == "persist_grid") { h->persist_grid = v < 0 ? 0 : (int)v; return RANENV_OK; }
-    if (k == "pack") { h->pack = v != 0; return RANENV_OK; }
-    if (k == "mix") { h->mix = v < 0 ? 0 : (v > 2 ? 2 : (int)v); h->pclass_dirty = true; return RANENV_OK; }
-    if (k == "persist_inject_abort") { h->persist_inject = v != 0 ? 1 : 0; return RANENV_OK; }     // test hook, see persist_check_errors
-    if (k == "autoreset_shortcut") { h->autoreset_shortcut = v != 0 ? 1 : 0; return RANENV_OK; }
-    if (k.rfind("fuse_first", 0) == 0 && k.size() == 11 && k[10] >= '0' && k[10] <= '9') {
-        const size_t i = (size_t)(k[10] - '0');
-        if (h->fuse_first.size() <= i) h->fuse_first.resize(i + 1, 0);
-        h->fuse_first[i] = v < 0 ? 0 : (int)v;
-        return RANENV_OK;
-    }
-    return fail(h, RANENV_E_INVALID, "unknown option '%s'", k.c_str());
+    if (const Option *o = find_option(k)) return o->set(h, v);
+    const int i = fuse_first_index(k);
+    if (i < 0) return fail(h, RANENV_E_INVALID, "unknown option '%s'", k.c_str());
+    if (h->fuse_first.size() <= (size_t)i) h->fuse_first.resize((size_t)i + 1, 0);
+    h->fuse_first[(size_t)i] = v < 0 ? 0 : (int)v;
+    return RANENV_OK;
 }
 
 void apply_env_options(ranenv_handle h)
 {
-    static const char *const keys[] = {"compact", "fuse", "row_width", "small_batch", "tiny_step", "persist", "persist_chunk", "persist_grid", "pack", "mix", "autoreset_shortcut"};
-    for (const char *key : keys) {
+    for (const Option &o : options) {
+        if (!o.env) continue;
         std::string name = "RANENV_";
-        for (const char *c = key; *c; c++) name += (char)toupper((unsigned char)*c);
-        if (const char *v = getenv(name.c_str())) (void)set_option(h, key, atoll(v));      // (an unusable value is ignored)
+        for (const char *c = o.key; *c; c++) name += (char)toupper((unsigned char)*c);
+        if (const char *v = getenv(name.c_str())) (void)o.set(h, atoll(v));      // (an unusable value is ignored)
     }
     if (const char *ff = getenv("RANENV_FUSE_FIRST")) {      // a list: a,b,c = partitions 0, 1, 2
         int i = 0;
@@ -773,17 +812,8 @@ int ranenv_get_option(ranenv_handle h, const char *key, int64_t *value)
 {
     if (!h || !key || !value) return fail(h, RANENV_E_INVALID, "null argument");
     const std::string k(key);
-    if (k == "compact") *value = h->compact_enabled ? 1 : 0;
-    else if (k == "fuse") *value = h->fuse;
-    else if (k == "row_width") *value = h->np;
-    else if (k == "small_batch") *value = h->small_batch ? 1 : 0;
-    else if (k == "tiny_step") *value = h->tiny_step;
-    else if (k == "persist") *value = h->persist;
-    else if (k == "persist_chunk") *value = h->persist_chunk;
-    else if (k == "persist_grid") *value = h->persist_grid;
-    else if (k == "pack") *value = h->pack ? 1 : 0;
-    else if (k == "mix") *value = h->mix;
-    else if (k == "autoreset_shortcut") *value = h->autoreset_shortcut;
+    const Option *o = find_option(k);
+    if (o && o->get) *value = o->get(h);
     else if (k.rfind("persist_stat_", 0) == 0) {      // keep / push / pop / fresh / idle_polls, summed over classes and XCDs
         static const char *const names[] = {"keep", "push", "pop", "fresh", "idle_polls"};
         int which = -1;
@@ -805,8 +835,7 @@ int ranenv_get_option(ranenv_handle h, const char *key, int64_t *value)
     }
     else if (k == "last_rollout_persistent") *value = h->last_rollout_persistent;      // what the last ranenv_rollout call ran:
     else if (k == "last_rollout_launches") *value = h->last_rollout_launches;          // 1 = persistent work-queue launches; step-kernel launches enqueued
-    else if (k.rfind("fuse_first", 0) == 0 && k.size() == 11 && k[10] >= '0' && k[10] <= '9')
-        *value = (size_t)(k[10] - '0') < h->fuse_first.size() ? h->fuse_first[(size_t)(k[10] - '0')] : 0;
+    else if (const int i = fuse_first_index(k); i >= 0) *value = (size_t)i < h->fuse_first.size() ? h->fuse_first[(size_t)i] : 0;
     else return fail(h, RANENV_E_INVALID, "unknown option '%s'", key);
     return RANENV_OK;
 }
@@ -1005,21 +1034,24 @@ int ranenv_bind_traffic_pool(ranenv_handle h, const int32_t *dev_pool, int64_t n
     return RANENV_OK;
 }
 
+static int check_episode(ranenv_handle h, const ranenv_episode &e, const char *what, long long idx)
+{
+    if (e.scenario < 0 || e.scenario >= h->cfg.n_scenarios) return fail(h, RANENV_E_INVALID, "%s %lld: scenario %d outside pool of %d", what, idx, e.scenario, h->cfg.n_scenarios);
+    if (e.se_len < 1 || e.se_offset < 0 || e.se_offset >= e.se_len || e.se_base < 0 || e.trf_len < 1 ||
+        e.trf_offset < 0 || e.trf_offset >= e.trf_len || e.trf_base < 0)
+        return fail(h, RANENV_E_INVALID, "%s %lld: need len >= 1, 0 <= offset < len, base >= 0", what, idx);
+    if (h->se_tiles_n > 0 && e.se_base + e.se_len > h->se_tiles_n)
+        return fail(h, RANENV_E_INVALID, "%s %lld: SE trace [%lld,+%d) exceeds the bound pool of %lld tiles", what, idx, (long long)e.se_base, e.se_len, (long long)h->se_tiles_n);
+    if (h->kp.trf_pool && e.trf_base + e.trf_len > h->trf_rows_n)
+        return fail(h, RANENV_E_INVALID, "%s %lld: traffic trace [%lld,+%d) exceeds the bound pool of %lld rows", what, idx, (long long)e.trf_base, e.trf_len, (long long)h->trf_rows_n);
+    return RANENV_OK;
+}
+
 int ranenv_set_episodes(ranenv_handle h, const ranenv_episode *eps, void *stream_)
 {
     if (!h || !eps) return fail(h, RANENV_E_INVALID, "null argument");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    for (int b = 0; b < h->cfg.batch; b++) {
-        const ranenv_episode &e = eps[b];
-        if (e.scenario < 0 || e.scenario >= h->cfg.n_scenarios) return fail(h, RANENV_E_INVALID, "env %d: scenario %d outside pool of %d", b, e.scenario, h->cfg.n_scenarios);
-        if (e.se_len < 1 || e.se_offset < 0 || e.se_offset >= e.se_len || e.se_base < 0 || e.trf_len < 1 ||
-            e.trf_offset < 0 || e.trf_offset >= e.trf_len || e.trf_base < 0)
-            return fail(h, RANENV_E_INVALID, "env %d: need len >= 1, 0 <= offset < len, base >= 0", b);
-        if (h->se_tiles_n > 0 && e.se_base + e.se_len > h->se_tiles_n)
-            return fail(h, RANENV_E_INVALID, "env %d: SE trace [%lld,+%d) exceeds the bound pool of %lld tiles", b, (long long)e.se_base, e.se_len, (long long)h->se_tiles_n);
-        if (h->kp.trf_pool && e.trf_base + e.trf_len > h->trf_rows_n)
-            return fail(h, RANENV_E_INVALID, "env %d: traffic trace [%lld,+%d) exceeds the bound pool of %lld rows", b, (long long)e.trf_base, e.trf_len, (long long)h->trf_rows_n);
-    }
+    for (int b = 0; b < h->cfg.batch; b++) { const int rc = check_episode(h, eps[b], "env", b); if (rc != RANENV_OK) return rc; }
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(h, hipMemcpyAsync(h->d_episodes, eps, sizeof(ranenv_episode) * (size_t)h->cfg.batch, hipMemcpyHostToDevice, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
@@ -1160,15 +1192,56 @@ static int check_ready(ranenv_handle h, const float *se_tiles, const double *tra
     return RANENV_OK;
 }
 
+static int check_part(ranenv_handle h, int32_t part)
+{
+    if (part < 0 || part >= h->n_parts || h->part_lo.empty()) return fail(h, RANENV_E_INVALID, "partition %d outside [0,%d) (ranenv_set_partitions)", part, h->n_parts);
+    return RANENV_OK;
+}
+
+// The partition's stream picks up behind what the caller's stream holds now (the producer of the scores) -- unless the
+// caller works on the partition's stream itself (ranenv_get_part_stream): then stream order is all that is needed, and
+// no signal crosses between hardware queues (a cross-queue dependency costs ~15 us each way on this GPU)
+static int part_handoff(ranenv_handle h, int32_t part, hipStream_t stream)
+{
+    hipStream_t ps = h->part_stream[(size_t)part];
+    if (stream != ps) {
+        HIP_TRY(h, hipEventRecord(h->part_in[(size_t)part], stream));
+        HIP_TRY(h, hipStreamWaitEvent(ps, h->part_in[(size_t)part], 0));
+    }
+    return RANENV_OK;
+}
+
+// What ranenv_step and ranenv_step_range open with, for envs [env_first, env_first + env_count): the checks, the call's KP with
+// compact steps decided, and under RANENV_POLICY_NETWORK the nets' launch, whose status lands in *net_err (the callers word its
+// failure differently).
+static int step_begin(ranenv_handle h, int32_t env_first, int32_t env_count, const double *scores, const uint8_t *intra,
+                      const double *traffic_bits, const float *se_tiles, float *obs_inter, float *obs_intra, double *reward,
+                      uint8_t *done, hipStream_t stream, KP *kp, hipError_t *net_err)
+{
+    int rc = check_ready(h, se_tiles, traffic_bits, true);
+    if (rc != RANENV_OK) return rc;
+    if (env_first < 0 || env_count < 1 || (long long)env_first + env_count > h->cfg.batch)
+        return fail(h, RANENV_E_INVALID, "envs [%d,%d) outside the batch of %d", env_first, env_first + env_count, h->cfg.batch);
+    if (!scores && h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "policy is EXTERNAL but no inter-slice scores were given");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    *kp = call_kp(h, obs_inter, obs_intra, reward, done);
+    kp->se_tiles = se_tiles; kp->scores = scores; kp->intra = intra; kp->traffic_bits = traffic_bits;
+    const int net = net_use(h, *kp);
+    if (net < 0) return net;
+    rc = compact_for(h, *kp, stream, &kp->compact);
+    if (rc != RANENV_OK) return rc;
+    *net_err = net ? net_launch(h, *kp, env_first, env_count, stream) : hipSuccess;
+    return RANENV_OK;
+}
+
 int ranenv_reset(ranenv_handle h, const uint8_t *env_mask, const float *se_tiles, float *obs_inter, float *obs_intra,
                  double *reward, void *stream)
 {
     int rc = check_ready(h, se_tiles, nullptr, false);
     if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    KP kp = h->kp;
-    kp.env_mask = env_mask; kp.se_tiles = se_tiles; kp.scores = nullptr; kp.intra = nullptr; kp.traffic_bits = nullptr;
-    kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = nullptr;
+    KP kp = call_kp(h, obs_inter, obs_intra, reward, nullptr);
+    kp.env_mask = env_mask; kp.se_tiles = se_tiles;
     hipError_t e = launch<MODE_RESET>(h, kp, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "reset launch: %s", hipGetErrorString(e));
     if (env_mask == nullptr) h->idle_state_clean = true;        // every queue of the batch is empty again
@@ -1180,18 +1253,11 @@ int ranenv_reset(ranenv_handle h, const uint8_t *env_mask, const float *se_tiles
 int ranenv_step(ranenv_handle h, const double *scores, const uint8_t *intra, const double *traffic_bits,
                 const float *se_tiles, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream)
 {
-    int rc = check_ready(h, se_tiles, traffic_bits, true);
+    KP kp;
+    hipError_t e;
+    const int rc = step_begin(h, 0, h ? h->cfg.batch : 0, scores, intra, traffic_bits, se_tiles, obs_inter, obs_intra, reward, done,
+                              (hipStream_t)stream, &kp, &e);
     if (rc != RANENV_OK) return rc;
-    if (!scores && h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "policy is EXTERNAL but no inter-slice scores were given");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    KP kp = h->kp;
-    kp.env_mask = nullptr; kp.se_tiles = se_tiles; kp.scores = scores; kp.intra = intra; kp.traffic_bits = traffic_bits;
-    kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = done;
-    const int net = net_use(h, kp);
-    if (net < 0) return net;
-    rc = compact_for(h, kp, (hipStream_t)stream, &kp.compact);
-    if (rc != RANENV_OK) return rc;
-    hipError_t e = net ? net_launch(h, kp, 0, h->cfg.batch, (hipStream_t)stream) : hipSuccess;
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "policy network launch: %s", hipGetErrorString(e));
     e = launch<MODE_STEP>(h, kp, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "step launch: %s", hipGetErrorString(e));
@@ -1207,9 +1273,8 @@ int ranenv_step_dense(ranenv_handle h, const uint8_t *dense, const double *traff
     if (!dense) return fail(h, RANENV_E_INVALID, "null sched_decision");
     if (!se_tiles && !h->kp.se_pool) return fail(h, RANENV_E_STATE, "a dense step reads whole SE rows: it needs explicit tiles or an RB-major pool (this handle has gather sidecars only)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    KP kp = h->kp;
-    kp.env_mask = nullptr; kp.se_tiles = se_tiles; kp.scores = nullptr; kp.intra = nullptr; kp.traffic_bits = traffic_bits;
-    kp.dense = dense; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = done;
+    KP kp = call_kp(h, obs_inter, obs_intra, reward, done);
+    kp.se_tiles = se_tiles; kp.traffic_bits = traffic_bits; kp.dense = dense;
     h->idle_state_clean = false;                 // (a dense decision is the facade's path: explicit traffic, any UE)
     hipError_t e = launch<MODE_DENSE>(h, kp, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "dense step launch: %s", hipGetErrorString(e));
@@ -1221,21 +1286,11 @@ int ranenv_step_range(ranenv_handle h, int32_t env_first, int32_t env_count, con
                       const double *traffic_bits, const float *se_tiles, float *obs_inter, float *obs_intra, double *reward,
                       uint8_t *done, void *stream)
 {
-    int rc = check_ready(h, se_tiles, traffic_bits, true);
+    KP kp;
+    hipError_t e;
+    const int rc = step_begin(h, env_first, env_count, scores, intra, traffic_bits, se_tiles, obs_inter, obs_intra, reward, done,
+                              (hipStream_t)stream, &kp, &e);
     if (rc != RANENV_OK) return rc;
-    if (env_first < 0 || env_count < 1 || (long long)env_first + env_count > h->cfg.batch)
-        return fail(h, RANENV_E_INVALID, "envs [%d,%d) outside the batch of %d", env_first, env_first + env_count, h->cfg.batch);
-    if (!scores && h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "policy is EXTERNAL but no inter-slice scores were given");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    KP kp = h->kp;
-    kp.env_mask = nullptr; kp.se_tiles = se_tiles; kp.scores = scores; kp.intra = intra; kp.traffic_bits = traffic_bits;
-    kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = done;
-    finalize_kp(h, kp);
-    const int net = net_use(h, kp);
-    if (net < 0) return net;
-    rc = compact_for(h, kp, (hipStream_t)stream, &kp.compact);
-    if (rc != RANENV_OK) return rc;
-    hipError_t e = net ? net_launch(h, kp, env_first, env_count, (hipStream_t)stream) : hipSuccess;
     if (e == hipSuccess) e = launch_range<MODE_STEP>(h, kp, env_first, env_count, (hipStream_t)stream);
     if (e == hipSuccess && (h->cfg.flags & RANENV_F_SYNC_CHECK)) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "step launch (envs [%d,%d)): %s", env_first, env_first + env_count, hipGetErrorString(e));
@@ -1247,18 +1302,14 @@ int ranenv_step_part(ranenv_handle h, int32_t part, const double *scores, const 
                      const float *se_tiles, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream_)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (part < 0 || part >= h->n_parts || h->part_lo.empty()) return fail(h, RANENV_E_INVALID, "partition %d outside [0,%d) (ranenv_set_partitions)", part, h->n_parts);
-    hipStream_t stream = (hipStream_t)stream_, ps = h->part_stream[(size_t)part];
+    int rc = check_part(h, part);
+    if (rc != RANENV_OK) return rc;
+    hipStream_t ps = h->part_stream[(size_t)part];
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    // the partition's stream picks up behind what the caller's stream holds now (the producer of the scores) -- unless the
-    // caller works on the partition's stream itself (ranenv_get_part_stream): then stream order is all that is needed, and
-    // no signal crosses between hardware queues (a cross-queue dependency costs ~15 us each way on this GPU)
-    if (stream != ps) {
-        HIP_TRY(h, hipEventRecord(h->part_in[(size_t)part], stream));
-        HIP_TRY(h, hipStreamWaitEvent(ps, h->part_in[(size_t)part], 0));
-    }
-    const int rc = ranenv_step_range(h, h->part_lo[(size_t)part], h->part_lo[(size_t)part + 1] - h->part_lo[(size_t)part], scores, intra,
-                                     traffic_bits, se_tiles, obs_inter, obs_intra, reward, done, ps);
+    rc = part_handoff(h, part, (hipStream_t)stream_);
+    if (rc != RANENV_OK) return rc;
+    rc = ranenv_step_range(h, h->part_lo[(size_t)part], h->part_lo[(size_t)part + 1] - h->part_lo[(size_t)part], scores, intra,
+                           traffic_bits, se_tiles, obs_inter, obs_intra, reward, done, ps);
     if (rc != RANENV_OK) return rc;
     // ... and leaves an event for ranenv_wait_part
     HIP_TRY(h, hipEventRecord(h->part_done[(size_t)part], ps));
@@ -1268,7 +1319,8 @@ int ranenv_step_part(ranenv_handle h, int32_t part, const double *scores, const 
 int ranenv_wait_part(ranenv_handle h, int32_t part, void *stream_)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (part < 0 || part >= h->n_parts || h->part_lo.empty()) return fail(h, RANENV_E_INVALID, "partition %d outside [0,%d) (ranenv_set_partitions)", part, h->n_parts);
+    const int rc = check_part(h, part);
+    if (rc != RANENV_OK) return rc;
     if ((hipStream_t)stream_ != h->part_stream[(size_t)part])
         HIP_TRY(h, hipStreamWaitEvent((hipStream_t)stream_, h->part_done[(size_t)part], 0));
     return RANENV_OK;
@@ -1277,7 +1329,8 @@ int ranenv_wait_part(ranenv_handle h, int32_t part, void *stream_)
 int ranenv_get_part_stream(ranenv_handle h, int32_t part, void **stream)
 {
     if (!h || !stream) return fail(h, RANENV_E_INVALID, "null argument");
-    if (part < 0 || part >= h->n_parts || h->part_lo.empty()) return fail(h, RANENV_E_INVALID, "partition %d outside [0,%d) (ranenv_set_partitions)", part, h->n_parts);
+    const int rc = check_part(h, part);
+    if (rc != RANENV_OK) return rc;
     *stream = (void *)h->part_stream[(size_t)part];
     return RANENV_OK;
 }
@@ -1306,32 +1359,13 @@ int ranenv_set_se_mode(ranenv_handle h, int32_t mode, void *stream_)
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t stream = (hipStream_t)stream_;
-    const int U = h->cfg.n_ues, R = h->cfg.n_rbs, Rp = (R + 7) & ~7;
-    const size_t nt = (size_t)h->se_tiles_n;
-    // (re)build the sidecars for the pool as it is now: older ones are released first
-    auto drop = [&](void *ptr) {
-        if (!ptr) return;
-        for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == ptr) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
-        (void)hipFree(ptr);
-    };
-    HIP_TRY(h, hipDeviceSynchronize());
-    drop(h->d_se_mean); drop(h->d_se_um); h->d_se_mean = nullptr; h->d_se_um = nullptr;
-    void *pm = nullptr, *pu = nullptr;
-    hipError_t e = hipMalloc(&pm, nt * (size_t)U * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&pu, nt * (size_t)U * (size_t)Rp * sizeof(float));
-    if (e != hipSuccess) {
-        if (pm) (void)hipFree(pm);
-        return fail(h, RANENV_E_NOMEM, "SE gather sidecars (%zu tiles: %.2f GB): %s", nt,
-                    (double)(nt * (size_t)U * (8 + 4 * (size_t)Rp)) / 1e9, hipGetErrorString(e));
-    }
-    h->allocs.push_back(pm); h->allocs.push_back(pu);
-    h->d_se_mean = (double *)pm; h->d_se_um = (float *)pu; h->se_rp = Rp;
-    for (size_t t0 = 0; t0 < nt; t0 += 1u << 20) {              // grid.x stays far below its limit
-        const size_t n = nt - t0 < (1u << 20) ? nt - t0 : (1u << 20);
-        launch_se_sidecar(stream, (unsigned)n, (unsigned)h->nt, h->kp.se_pool, (long long)h->kp.se_stride, (long long)t0, U, R, Rp, h->kp.se_quad,
-                          h->d_se_mean, h->d_se_um);
-    }
-    e = hipGetLastError();
+    // (re)build the sidecars for the pool as it is now
+    const int rc = se_sidecars_rebuild(h, (size_t)h->se_tiles_n, [&](size_t t0, size_t n) {
+        launch_se_sidecar(stream, (unsigned)n, (unsigned)h->nt, h->kp.se_pool, (long long)h->kp.se_stride, (long long)t0, h->cfg.n_ues,
+                          h->cfg.n_rbs, h->se_rp, h->kp.se_quad, h->d_se_mean, h->d_se_um);
+    });
+    if (rc != RANENV_OK) return rc;
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "SE sidecar launch: %s", hipGetErrorString(e));
     // The sidecars are read by launches on other streams (the partitions' own): a one-off multi-GB build that started with a
     // device synchronisation also ends with one, instead of an event every partition stream would have to wait for.
@@ -1348,30 +1382,12 @@ int ranenv_bind_se_gather_from_power(ranenv_handle h, const double *dev_power, i
     if (!(noise_power > 0.0)) return fail(h, RANENV_E_INVALID, "noise_power must be positive");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t stream = (hipStream_t)stream_;
-    const int U = h->cfg.n_ues, R = h->cfg.n_rbs, Rp = (R + 7) & ~7;
-    const size_t nt = (size_t)n_tiles;
-    auto drop = [&](void *ptr) {
-        if (!ptr) return;
-        for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == ptr) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
-        (void)hipFree(ptr);
-    };
-    HIP_TRY(h, hipDeviceSynchronize());
-    drop(h->d_se_mean); drop(h->d_se_um); h->d_se_mean = nullptr; h->d_se_um = nullptr;
-    void *pm = nullptr, *pu = nullptr;
-    hipError_t e = hipMalloc(&pm, nt * (size_t)U * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&pu, nt * (size_t)U * (size_t)Rp * sizeof(float));
-    if (e != hipSuccess) {
-        if (pm) (void)hipFree(pm);
-        return fail(h, RANENV_E_NOMEM, "SE gather sidecars (%zu tiles: %.2f GB): %s", nt, (double)(nt * (size_t)U * (8 + 4 * (size_t)Rp)) / 1e9, hipGetErrorString(e));
-    }
-    h->allocs.push_back(pm); h->allocs.push_back(pu);
-    h->d_se_mean = (double *)pm; h->d_se_um = (float *)pu; h->se_rp = Rp;
-    for (size_t t0 = 0; t0 < nt; t0 += 1u << 20) {
-        const size_t n = nt - t0 < (1u << 20) ? nt - t0 : (1u << 20);
-        launch_se_sidecar_from_power(stream, (unsigned)n, (unsigned)h->nt, dev_power, (long long)t0, U, R, Rp, tx_power_per_rb, noise_power,
-                                     h->d_se_mean, h->d_se_um);
-    }
-    e = hipGetLastError();
+    const int rc = se_sidecars_rebuild(h, (size_t)n_tiles, [&](size_t t0, size_t n) {
+        launch_se_sidecar_from_power(stream, (unsigned)n, (unsigned)h->nt, dev_power, (long long)t0, h->cfg.n_ues, h->cfg.n_rbs, h->se_rp,
+                                     tx_power_per_rb, noise_power, h->d_se_mean, h->d_se_um);
+    });
+    if (rc != RANENV_OK) return rc;
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "SE sidecar-from-power launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(stream));        // (read by launches on other streams; the power array may be freed by the caller now)
     h->kp.se_pool = nullptr; h->kp.se_stride = 0;    // no RB-major pool: pooled tiles exist as sidecars only
@@ -1437,23 +1453,131 @@ int ranenv_set_partitions(ranenv_handle h, int32_t n_parts)
     if (n_parts < 1 || n_parts > 16 || n_parts > h->cfg.batch) return fail(h, RANENV_E_INVALID, "n_parts must be in [1, min(16, batch)]");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipDeviceSynchronize());
-    while ((int)h->part_stream.size() < n_parts) {
-        hipStream_t st = nullptr; hipEvent_t ev = nullptr;
-        HIP_TRY(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        h->part_stream.push_back(st);
-        HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        h->part_done.push_back(ev);
-        ev = nullptr;
-        HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        h->part_in.push_back(ev);
-    }
-    if (!h->ev_in) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+    HIP_TRY(h, ensure_streams(h, (size_t)n_parts));
     h->part_lo.assign((size_t)n_parts + 1, 0);
     // (an even batch is cut into even ranges where that is possible: packed waves step two envs each, ranenv_core_kernel_packed)
     const int B = h->cfg.batch, unit = (B % 2 == 0 && B / 2 >= n_parts) ? 2 : 1;
     const int base = (B / unit) / n_parts, rem = (B / unit) % n_parts;
     for (int k = 0; k < n_parts; k++) h->part_lo[k + 1] = h->part_lo[k] + unit * (base + (k < rem ? 1 : 0));
     h->n_parts = n_parts;
+    return RANENV_OK;
+}
+
+// ---- ranenv_rollout ---------------------------------------------------------------------------------------------------------------
+// What its two schedules share.  With auto-reset on, an env whose episode ends inside the rollout moves on to its next episode
+// without the host: the advance kernel + the step kernel in RESET mode follow that TTI's step on the partition's stream.  They are
+// only enqueued for TTIs at which some env of the partition finishes: the step counters are read once at the start and followed on
+// the host (nothing but this rollout changes them until it returns).
+struct Rollout {
+    int n_steps = 0;
+    KP kp{};                       // the step's
+    int net = 0;                   // the policy nets run in front of every TTI
+    bool follow = false;           // auto-reset on: the host's copy of the step counters, the advance kernel's arguments, the reset's KP
+    std::vector<int32_t> steps;
+    AdvanceArgs adv{};
+    KP kpr{};
+};
+
+// TTIs from now until the first episode of envs [lo, hi) ends, that TTI included, between 1 and n.  `n_ends`: at how many different
+// TTIs before the n-th episodes end (counted up to 3).
+static int ttis_to_end(ranenv_handle h, const Rollout &r, int lo, int hi, int n, int *n_ends = nullptr)
+{
+    int first = n, ends[3], k = 0;
+    for (int b = lo; b < hi; b++) {
+        const int d = max_steps_of_env(h, b) - r.steps[(size_t)b];
+        if (d < first) first = d;
+        if (n_ends && d < n && k < 3 && std::find(ends, ends + k, d) == ends + k) ends[k++] = d;
+    }
+    if (n_ends) *n_ends = k;
+    return first < 1 ? 1 : first;
+}
+
+// n_tti TTIs of envs [e0, e0 + n) were enqueued on `s`: the host's step counters advance by n_tti, and the envs whose episode
+// ended restart, on the host and -- advance kernel, reset -- on `s`
+static hipError_t follow_episode_ends(ranenv_handle h, Rollout &r, int e0, int n, int n_tti, hipStream_t s)
+{
+    if (!r.follow) return hipSuccess;
+    bool any = false;
+    for (int b = e0; b < e0 + n; b++) {
+        r.steps[(size_t)b] += n_tti;
+        if (r.steps[(size_t)b] >= max_steps_of_env(h, b)) { any = true; r.steps[(size_t)b] = 0; }
+    }
+    if (!any) return hipSuccess;
+    AdvanceArgs a = r.adv; a.e0 = e0;
+    h->pclass_dirty = true;                        // the restarted envs' scenarios
+    launch_advance(s, (unsigned)n, a);
+    return launch_range<MODE_RESET>(h, r.kpr, e0, n, s);
+}
+
+// Option "persist": one persistent work-queue launch per workgroup class for all the TTIs up to the next episode end
+// (ranenv_persist_kernel), on the caller's stream (+ one handle-owned stream per further class), whatever the partitions.
+static int rollout_persistent(ranenv_handle h, Rollout &r, hipStream_t stream)
+{
+    h->last_rollout_persistent = 1;
+    for (int done_ttis = 0; done_ttis < r.n_steps;) {
+        int n_tti = r.n_steps - done_ttis;
+        if (r.follow) n_tti = ttis_to_end(h, r, 0, h->cfg.batch, n_tti);
+        if (n_tti >= (1 << (31 - PERSIST_ENV_BITS))) n_tti = (1 << (31 - PERSIST_ENV_BITS)) - 1;
+        int rc = persist_prepare(h, stream, true);
+        if (rc != RANENV_OK) return rc;
+        rc = persist_launch(h, r.kp, n_tti, stream);
+        if (rc != RANENV_OK) return rc;
+        done_ttis += n_tti;
+        const hipError_t re = follow_episode_ends(h, r, 0, h->cfg.batch, n_tti, stream);
+        if (re != hipSuccess) return fail(h, RANENV_E_HIP, "persistent rollout, reset launch: %s", hipGetErrorString(re));
+    }
+    return RANENV_OK;
+}
+
+// Every partition walks through the TTIs in launches of its own, on its own stream
+static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
+{
+    const int n_steps = r.n_steps;
+    // A launch takes its envs through several TTIs where nothing has to happen in between (see step_loop): no head kernel
+    // behind every step, and -- with auto-reset -- no episode end before the launch's last TTI.  How many: a quarter of
+    // the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more and lengthen the
+    // drain at the rollout's end, where the workgroups that waited for a free slot run last and alone).
+    int fuse = h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
+    if (r.kp.head_obs || r.kp.head_reward || r.net) fuse = 1;
+    // `pdone[k]` TTIs are enqueued for partition k
+    const int np = h->n_parts > 1 ? h->n_parts : 1;
+    std::vector<int> pdone((size_t)np, 0), pn((size_t)np, 0);
+    auto part_of = [&](int e0) { for (int k = 0; k < np; k++) if (np > 1 && h->part_lo[k] == e0) return k; return 0; };
+    for (int round = 0;; round++) {
+        bool any_left = false, last = true;
+        for (int k = 0; k < np; k++) {
+            const int left = n_steps - pdone[(size_t)k];
+            int n_tti = left < fuse ? left : fuse;
+            if (round == 0 && fuse > 1 && np > 1) {
+                // The partitions' first launches differ in length, the one enqueued last (the highest partition) starting with a
+                // single TTI: its workgroups are the ones that find the slots taken, and after one short launch its late starters are
+                // through instead of holding its chain up for a whole long one; from then on the partitions' launch boundaries no
+                // longer coincide (profiles/r03_ab_log.txt).  RANENV_FUSE_FIRST=a,b,c overrides (0 = the common length).
+                int first = k == np - 1 ? 1 : ((k & 1) ? (3 * fuse + 4) / 5 : fuse);
+                if (!h->fuse_first.empty()) first = (size_t)k < h->fuse_first.size() ? h->fuse_first[(size_t)k] : 0;
+                if (first > 0 && first < n_tti) n_tti = first;
+            }
+            if (r.follow && n_tti > 1)
+                n_tti = ttis_to_end(h, r, np > 1 ? h->part_lo[k] : 0, np > 1 ? h->part_lo[k + 1] : h->cfg.batch, n_tti);
+            pn[(size_t)k] = n_tti > 0 ? n_tti : 0;
+            if (pn[(size_t)k] > 0) any_left = true;
+            if (pdone[(size_t)k] + pn[(size_t)k] < n_steps) last = false;
+        }
+        if (!any_left) break;
+        const hipError_t e = for_partitions(h, stream, round == 0, last, [&](int e0, int n, hipStream_t s) -> hipError_t {
+            const int n_tti = pn[(size_t)part_of(e0)];
+            if (n_tti == 0) return hipSuccess;                                    // this partition is through
+            KP kpk = r.kp;
+            kpk.n_tti = n_tti;
+            h->last_rollout_launches++;
+            hipError_t le = r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
+            if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
+            if (le != hipSuccess) return le;
+            return follow_episode_ends(h, r, e0, n, n_tti, s);
+        });
+        if (e != hipSuccess) return fail(h, RANENV_E_HIP, "rollout, round %d of launches: %s", round, hipGetErrorString(e));
+        for (int k = 0; k < np; k++) pdone[(size_t)k] += pn[(size_t)k];
+    }
     return RANENV_OK;
 }
 
@@ -1468,161 +1592,46 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     rc = persist_check_errors(h);                  // (of the persistent launches of earlier calls that have completed)
     if (rc != RANENV_OK) return rc;
-    KP kp = h->kp;
-    kp.env_mask = nullptr; kp.se_tiles = nullptr; kp.scores = nullptr; kp.intra = nullptr; kp.traffic_bits = nullptr;
-    kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = reward; kp.done = done;
     hipStream_t stream = (hipStream_t)stream_;
+    Rollout r;
+    r.n_steps = n_steps;
+    r.kp = call_kp(h, obs_inter, obs_intra, reward, done);
     h->last_rollout_persistent = 0; h->last_rollout_launches = 0;
-    finalize_kp(h, kp);
     // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
-    const int net = net_use(h, kp);
-    if (net < 0) return net;
-    rc = compact_for(h, kp, stream, &kp.compact);
+    r.net = net_use(h, r.kp);
+    if (r.net < 0) return r.net;
+    rc = compact_for(h, r.kp, stream, &r.kp.compact);
     if (rc != RANENV_OK) return rc;
-    if (kp.compact) kp.compact = 2;                 // (2: the streaming kernels may step compactly too, see launch_range)
-    // With auto-reset on, an env whose episode ends inside the rollout moves on to its next episode without the host:
-    // the advance kernel + the step kernel in RESET mode follow that TTI's step on the partition's stream.  They are only
-    // enqueued for TTIs at which some env of the partition finishes: the step counters are read once here and followed
-    // on the host (nothing but this rollout changes them until it returns).
-    std::vector<int32_t> steps;
-    AdvanceArgs adv{};
-    KP kpr = kp;
-    if (h->ar_on) {
+    if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_plan)
+    r.follow = h->ar_on;
+    if (r.follow) {
         if (!done) return fail(h, RANENV_E_INVALID, "a rollout with auto-reset needs the done buffer");
+        std::vector<int32_t> &steps = r.steps;
         steps.resize((size_t)h->cfg.batch);
         HIP_TRY(h, hipStreamSynchronize(stream));
         HIP_TRY(h, hipMemcpy(steps.data(), ST_step_no(h->kp), sizeof(int32_t) * steps.size(), hipMemcpyDeviceToHost));
-        adv = advance_args(h, done, obs_inter, obs_intra, nullptr, nullptr, nullptr);
-        kpr.env_mask = h->d_ar_mask; kpr.reward = nullptr; kpr.done = nullptr; kpr.compact = 0;
-        kpr.head_reward = nullptr;               // the terminal transition's head rewards stay, like reward / done
+        r.adv = advance_args(h, done, obs_inter, obs_intra, nullptr, nullptr, nullptr);
+        r.kpr = reset_behind(h, r.kp);
     }
-    const bool follow = h->ar_on;
-    // Option "persist": one persistent work-queue launch per workgroup class for all the TTIs up to the next episode end
-    // (ranenv_persist_kernel), on the caller's stream (+ one handle-owned stream per further class), whatever the partitions.
-    // Needs compact steps (the classes are those of the compact lane order) and no head kernel behind every TTI.
-    // (auto, streaming: rollouts of 4...64 TTIs of a batch the chip holds at once -- see below)
+    // The persistent rollout needs compact steps (the classes are those of the compact lane order) and no head kernel behind every TTI.
+    // Auto: where it was measured to win or tie (profiles/r04_ab_log.txt, r05_ab_log.txt, r06_ab_log.txt): SE gather mode
+    // up to ~2x what the chip holds (beyond, every chunk swaps envs), either mode at <= 2 waves per SIMD, and streaming rollouts of 4...64
+    // TTIs at <= 20 envs per CU (the streaming kernel is bound by HBM either way: larger batches and longer rollouts tie or lose).
     const bool stream_short = h->se_mode != RANENV_SE_GATHER && !h->small_batch && (long long)h->cfg.batch <= 20ll * h->n_cus && n_steps >= 4 && n_steps <= 64;
     const bool persist_wanted = (RANENV_DIAG == 0 || RANENV_DIAG == 12) && (h->persist == 1 || (h->persist < 0 && ((h->se_mode == RANENV_SE_GATHER && !h->small_batch && (long long)h->cfg.batch <= 44ll * h->n_cus) || persist_tiny(h) || stream_short)));
-    // (auto: where it was measured to win or tie -- profiles/r04_ab_log.txt.  Gather mode: B 1024 -4...-6 %, 2048 -1 %, 4096 -6 %, 8192 -2 % per
-    // TTI; a batch of several times what the chip holds -- 16 384 one-wave envs at the reference's own size -- swaps at every chunk and
-    // loses 7 %.  Streaming: -10 % at <= 2 waves per SIMD with the whole-row build; at B 4096 a tie: six same-box pairs against the
-    // launches of <= 10 TTIs over three partitions, between -5 and +6 % for rollouts of 200 TTIs (mean +0.2 %) and between -1 and +4 % for
-    // rollouts of 20 (mean +0.6 %) -- the streaming kernel is bound by HBM either way -- so there it stayed off unless asked for.
-    // Round 5, RB-quad-major pool + non-temporal tile loads: same-box pairs on five boxes (profiles/r05_ab_log.txt) give -0.5...-3 % for
-    // rollouts of 20 (mean -1.6 %), -5 % for 16, about -1 % for 40...100, a tie at 200 and +9 % for rollouts of 10 (the staggered first chunk is
-    // most of such a call); B 8192 loses 7 % (more workgroups than slots: every chunk swaps).  Hence: on for 16...64 TTIs at <= 20 envs per CU.
-    // Round 6: what made the short rollouts lose was the chunk, not the schedule -- with a chunk shorter than the launch (persist_launch) rollouts of 6 / 8 / 10 / 12
-    // TTIs are 9 / 9 / 10 / 6 % ahead of the launch-per-chunk rollout (gather mode, always persistent at this size: 12-14 % ahead of itself); 5 and 4 TTIs: 7 and 4 % ahead, 3 a tie, 2 behind by 16 %: on from 4 TTIs.)
     // (auto: not when episodes end at many different TTIs inside this call -- per-env episode lengths, envs reset at different times:
     // every episode end ends the persistent launches, re-sorts the envs and reads the class counts back; the launch-per-chunk
     // rollout follows the ends per partition without a host sync)
-    bool persist_ok = persist_wanted && !net && !scale_per_element(h) && kp.compact != 0 && !(kp.head_obs || kp.head_reward) && (h->cfg.batch >> PERSIST_ENV_BITS) == 0 &&
-                      !stream_capturing(stream);      // (it reads the class counts back)
-    if (persist_ok && h->persist < 0 && follow) {
-        std::vector<int> ends;
-        for (int b = 0; b < h->cfg.batch && ends.size() <= 2; b++) {
-            const int d = max_steps_of_env(h, b) - steps[(size_t)b];
-            if (d < n_steps && std::find(ends.begin(), ends.end(), d) == ends.end()) ends.push_back(d);
-        }
-        if (ends.size() > 2) persist_ok = false;
+    bool persist_ok = persist_wanted && !r.net && !scale_per_element(h) && r.kp.compact != 0 && !(r.kp.head_obs || r.kp.head_reward) &&
+                      (h->cfg.batch >> PERSIST_ENV_BITS) == 0 && !stream_capturing(stream);      // (it reads the class counts back)
+    if (persist_ok && h->persist < 0 && r.follow) {
+        int n_ends = 0;
+        (void)ttis_to_end(h, r, 0, h->cfg.batch, n_steps, &n_ends);
+        if (n_ends > 2) persist_ok = false;
     }
-    if (persist_ok) {
-        h->last_rollout_persistent = 1;
-        for (int done_ttis = 0; done_ttis < n_steps;) {
-            int n_tti = n_steps - done_ttis;
-            if (follow) {
-                for (int b = 0; b < h->cfg.batch; b++) {
-                    const int d = max_steps_of_env(h, b) - steps[(size_t)b];
-                    if (d < n_tti) n_tti = d;
-                }
-                if (n_tti < 1) n_tti = 1;
-            }
-            if (n_tti >= (1 << (31 - PERSIST_ENV_BITS))) n_tti = (1 << (31 - PERSIST_ENV_BITS)) - 1;
-            rc = persist_prepare(h, stream, true);
-            if (rc != RANENV_OK) return rc;
-            rc = persist_launch(h, kp, n_tti, stream);
-            if (rc != RANENV_OK) return rc;
-            done_ttis += n_tti;
-            if (!follow) continue;
-            bool any = false;
-            for (int b = 0; b < h->cfg.batch; b++) {
-                steps[(size_t)b] += n_tti;
-                if (steps[(size_t)b] >= max_steps_of_env(h, b)) { any = true; steps[(size_t)b] = 0; }
-            }
-            if (!any) continue;
-            h->pclass_dirty = true;               // the restarted envs' scenarios
-            launch_advance(stream, (unsigned)h->cfg.batch, adv);
-            const hipError_t re = launch_range<MODE_RESET>(h, kpr, 0, h->cfg.batch, stream);
-            if (re != hipSuccess) return fail(h, RANENV_E_HIP, "persistent rollout, reset launch: %s", hipGetErrorString(re));
-        }
-        if (follow) { h->sh_steps = steps; h->sh_valid = true; h->last_done = done; }      // (read from the device above, followed exactly since)
-        else shadow_steps_add(h, 0, h->cfg.batch, n_steps, done, stream);
-        return RANENV_OK;
-    }
-    // A launch takes its envs through several TTIs where nothing has to happen in between (see step_loop): no head kernel
-    // behind every step, and -- with auto-reset -- no episode end before the launch's last TTI.  How many: a quarter of
-    // the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more and lengthen the
-    // drain at the rollout's end, where the workgroups that waited for a free slot run last and alone).
-    int fuse = h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
-    if (kp.head_obs || kp.head_reward || net) fuse = 1;
-    auto max_steps_of = [&](int b) { return h->host_max_steps.empty() ? h->cfg.max_steps : h->host_max_steps[(size_t)b]; };
-    // Every partition walks through the n_steps TTIs in launches of its own: `pdone[k]` TTIs are enqueued for partition k.
-    const int np = h->n_parts > 1 ? h->n_parts : 1;
-    std::vector<int> pdone((size_t)np, 0), pn((size_t)np, 0);
-    auto part_of = [&](int e0) { for (int k = 0; k < np; k++) if (np > 1 && h->part_lo[k] == e0) return k; return 0; };
-    for (int round = 0;; round++) {
-        bool any_left = false, last = true;
-        for (int k = 0; k < np; k++) {
-            const int left = n_steps - pdone[(size_t)k];
-            int n_tti = left < fuse ? left : fuse;
-            if (round == 0 && fuse > 1 && np > 1) {
-                // The partitions' first launches differ in length, the one enqueued last (the highest partition)
-                // starting with a single TTI: it is the one whose workgroups find the slots taken (4096 envs want
-                // 3738), and after one short launch its late starters are through instead of holding its chain up for a
-                // whole long one; from then on the partitions' launch boundaries no longer coincide (K = 20: -2 % streaming,
-                // -4 % gather; profiles/r03_ab_log.txt).  RANENV_FUSE_FIRST=a,b,c overrides (0 = the common length).
-                int first = k == np - 1 ? 1 : ((k & 1) ? (3 * fuse + 4) / 5 : fuse);
-                if (!h->fuse_first.empty()) first = (size_t)k < h->fuse_first.size() ? h->fuse_first[(size_t)k] : 0;
-                if (first > 0 && first < n_tti) n_tti = first;
-            }
-            if (follow && n_tti > 1) {
-                int to_end = n_tti;              // TTIs until the first episode of the partition ends (that TTI included)
-                const int lo = np > 1 ? h->part_lo[k] : 0, hi = np > 1 ? h->part_lo[k + 1] : h->cfg.batch;
-                for (int b = lo; b < hi; b++) {
-                    const int d = max_steps_of(b) - steps[(size_t)b];
-                    if (d < to_end) to_end = d;
-                }
-                n_tti = to_end < 1 ? 1 : to_end;
-            }
-            pn[(size_t)k] = n_tti > 0 ? n_tti : 0;
-            if (pn[(size_t)k] > 0) any_left = true;
-            if (pdone[(size_t)k] + pn[(size_t)k] < n_steps) last = false;
-        }
-        if (!any_left) break;
-        const hipError_t e = for_partitions(h, stream, round == 0, last, [&](int e0, int n, hipStream_t s) -> hipError_t {
-            const int n_tti = pn[(size_t)part_of(e0)];
-            if (n_tti == 0) return hipSuccess;                                    // this partition is through
-            KP kpk = kp;
-            kpk.n_tti = n_tti;
-            h->last_rollout_launches++;
-            hipError_t le = net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
-            if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
-            if (le != hipSuccess || !follow) return le;
-            bool any = false;
-            for (int b = e0; b < e0 + n; b++) {
-                steps[(size_t)b] += n_tti;
-                if (steps[(size_t)b] >= max_steps_of(b)) { any = true; steps[(size_t)b] = 0; }
-            }
-            if (!any) return hipSuccess;
-            AdvanceArgs a = adv; a.e0 = e0;
-            h->pclass_dirty = true;
-            launch_advance(s, (unsigned)n, a);
-            return launch_range<MODE_RESET>(h, kpr, e0, n, s);
-        });
-        if (e != hipSuccess) return fail(h, RANENV_E_HIP, "rollout, round %d of launches: %s", round, hipGetErrorString(e));
-        for (int k = 0; k < np; k++) pdone[(size_t)k] += pn[(size_t)k];
-    }
-    if (follow) { h->sh_steps = steps; h->sh_valid = true; h->last_done = done; }
+    rc = persist_ok ? rollout_persistent(h, r, stream) : rollout_chunks(h, r, stream);
+    if (rc != RANENV_OK) return rc;
+    if (r.follow) { h->sh_steps = r.steps; h->sh_valid = true; h->last_done = done; }      // (read from the device above, followed exactly since)
     else shadow_steps_add(h, 0, h->cfg.batch, n_steps, done, stream);
     return RANENV_OK;
 }
@@ -1699,19 +1708,6 @@ int ranenv_set_max_steps(ranenv_handle h, const int32_t *host_max_steps, void *s
     return RANENV_OK;
 }
 
-static int check_episode(ranenv_handle h, const ranenv_episode &e, const char *what, long long idx)
-{
-    if (e.scenario < 0 || e.scenario >= h->cfg.n_scenarios) return fail(h, RANENV_E_INVALID, "%s %lld: scenario %d outside pool of %d", what, idx, e.scenario, h->cfg.n_scenarios);
-    if (e.se_len < 1 || e.se_offset < 0 || e.se_offset >= e.se_len || e.se_base < 0 || e.trf_len < 1 ||
-        e.trf_offset < 0 || e.trf_offset >= e.trf_len || e.trf_base < 0)
-        return fail(h, RANENV_E_INVALID, "%s %lld: need len >= 1, 0 <= offset < len, base >= 0", what, idx);
-    if (h->se_tiles_n > 0 && e.se_base + e.se_len > h->se_tiles_n)
-        return fail(h, RANENV_E_INVALID, "%s %lld: SE trace [%lld,+%d) exceeds the bound pool of %lld tiles", what, idx, (long long)e.se_base, e.se_len, (long long)h->se_tiles_n);
-    if (h->kp.trf_pool && e.trf_base + e.trf_len > h->trf_rows_n)
-        return fail(h, RANENV_E_INVALID, "%s %lld: traffic trace [%lld,+%d) exceeds the bound pool of %lld rows", what, idx, (long long)e.trf_base, e.trf_len, (long long)h->trf_rows_n);
-    return RANENV_OK;
-}
-
 int ranenv_set_episode_table(ranenv_handle h, const ranenv_episode *host_table, int32_t first_episode, int32_t n_episodes, void *stream_)
 {
     if (!h || !host_table) return fail(h, RANENV_E_INVALID, "null argument");
@@ -1752,31 +1748,52 @@ int ranenv_set_autoreset(ranenv_handle h, int32_t enable, int32_t initial_episod
     return RANENV_OK;
 }
 
-int ranenv_autoreset(ranenv_handle h, const uint8_t *dev_done, float *obs_inter, float *obs_intra,
-                     float *term_obs_inter, float *term_obs_intra, float *term_obs_head, void *stream_)
+// The checks of ranenv_autoreset / _part (`part`: the partition of ranenv_autoreset_part, checked in its place among the others)
+static int autoreset_ready(ranenv_handle h, const uint8_t *dev_done, const int32_t *part)
 {
     if (!h || !dev_done) return fail(h, RANENV_E_INVALID, "null argument");
     if (!h->ar_on) return fail(h, RANENV_E_STATE, "auto-reset is not configured (ranenv_set_autoreset)");
-    int rc = check_ready(h, nullptr, nullptr, false);
+    int rc = part ? check_part(h, *part) : RANENV_OK;
+    if (rc != RANENV_OK) return rc;
+    rc = check_ready(h, nullptr, nullptr, false);
     if (rc != RANENV_OK) return rc;
     if (!h->kp.se_pool && !(h->se_mode == RANENV_SE_GATHER && h->d_se_mean))
         return fail(h, RANENV_E_STATE, "auto-reset needs a bound SE pool (the reset observes the new episode's first tile)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t stream = (hipStream_t)stream_;
-    // no episode ended at the TTI enqueued last (the host follows the step counters, see ranenv::sh_steps): nothing to enqueue
-    {
-        const int due = shadow_due(h, 0, h->cfg.batch, dev_done, stream);
-        if (due == 0) return RANENV_OK;
-        if (due < 0) h->sh_valid = false;        // (the device decides by flags the host cannot follow: the shadow ends here)
-        else shadow_reset_due(h, 0, h->cfg.batch);
-    }
-    const AdvanceArgs a = advance_args(h, dev_done, obs_inter, obs_intra, term_obs_inter, term_obs_intra, term_obs_head);
+    return RANENV_OK;
+}
+
+// `due` envs of [lo, hi) ended their episode at the TTI enqueued last (shadow_due, -1 = unknown): false = none did, nothing to
+// enqueue (the host follows the step counters, see ranenv::sh_steps); true = enqueue the auto-reset, which the shadow follows --
+// unless the device decides by flags the host cannot follow: then the shadow ends here
+static bool autoreset_due(ranenv_handle h, int lo, int hi, int due)
+{
+    if (due == 0) return false;
+    if (due < 0) h->sh_valid = false;
+    else shadow_reset_due(h, lo, hi);
+    return true;
+}
+
+// Enqueue the advance kernel of envs [e0, e0 + n) on `s`; returns the KP of the reset that has to follow it
+static KP autoreset_advance(ranenv_handle h, int e0, int n, const uint8_t *dev_done, float *obs_inter, float *obs_intra,
+                            float *term_obs_inter, float *term_obs_intra, float *term_obs_head, hipStream_t s)
+{
+    AdvanceArgs a = advance_args(h, dev_done, obs_inter, obs_intra, term_obs_inter, term_obs_intra, term_obs_head);
+    a.e0 = e0;
     h->pclass_maybe = true;                      // (scenarios of the restarted envs, if any: the advance kernel sets the device's flag)
-    launch_advance(stream, (unsigned)h->cfg.batch, a);
-    KP kp = h->kp;
-    kp.env_mask = h->d_ar_mask; kp.se_tiles = nullptr; kp.scores = nullptr; kp.intra = nullptr; kp.traffic_bits = nullptr;
-    kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = nullptr; kp.done = nullptr;   // the step's rewards stay
-    kp.head_reward = nullptr;                    // ... those of the alternative heads too (head_obs gets the new episode's first observation)
+    launch_advance(s, (unsigned)n, a);
+    return reset_behind(h, call_kp(h, obs_inter, obs_intra, nullptr, nullptr));
+}
+
+int ranenv_autoreset(ranenv_handle h, const uint8_t *dev_done, float *obs_inter, float *obs_intra,
+                     float *term_obs_inter, float *term_obs_intra, float *term_obs_head, void *stream_)
+{
+    const int rc = autoreset_ready(h, dev_done, nullptr);
+    if (rc != RANENV_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int B = h->cfg.batch;
+    if (!autoreset_due(h, 0, B, shadow_due(h, 0, B, dev_done, stream))) return RANENV_OK;
+    const KP kp = autoreset_advance(h, 0, B, dev_done, obs_inter, obs_intra, term_obs_inter, term_obs_intra, term_obs_head, stream);
     const hipError_t e = launch<MODE_RESET>(h, kp, stream);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "auto-reset launch: %s", hipGetErrorString(e));
     return RANENV_OK;
@@ -1785,38 +1802,17 @@ int ranenv_autoreset(ranenv_handle h, const uint8_t *dev_done, float *obs_inter,
 int ranenv_autoreset_part(ranenv_handle h, int32_t part, const uint8_t *dev_done, float *obs_inter, float *obs_intra,
                           float *term_obs_inter, float *term_obs_intra, float *term_obs_head, void *stream_)
 {
-    if (!h || !dev_done) return fail(h, RANENV_E_INVALID, "null argument");
-    if (!h->ar_on) return fail(h, RANENV_E_STATE, "auto-reset is not configured (ranenv_set_autoreset)");
-    if (part < 0 || part >= h->n_parts || h->part_lo.empty()) return fail(h, RANENV_E_INVALID, "partition %d outside [0,%d) (ranenv_set_partitions)", part, h->n_parts);
-    int rc = check_ready(h, nullptr, nullptr, false);
+    int rc = autoreset_ready(h, dev_done, &part);
     if (rc != RANENV_OK) return rc;
-    if (!h->kp.se_pool && !(h->se_mode == RANENV_SE_GATHER && h->d_se_mean))
-        return fail(h, RANENV_E_STATE, "auto-reset needs a bound SE pool (the reset observes the new episode's first tile)");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t stream = (hipStream_t)stream_, ps = h->part_stream[(size_t)part];
     const int e0 = h->part_lo[(size_t)part], n = h->part_lo[(size_t)part + 1] - e0;
-    {
-        const int due = stream_capturing(stream) ? -1 : shadow_due(h, e0, e0 + n, dev_done, ps);
-        if (due == 0) {                            // (no episode of this range ended: see ranenv_autoreset)
-            HIP_TRY(h, hipEventRecord(h->part_done[(size_t)part], ps));                    // ranenv_wait_part still finds its event
-            return RANENV_OK;
-        }
-        if (due < 0) h->sh_valid = false;
-        else shadow_reset_due(h, e0, e0 + n);
+    if (!autoreset_due(h, e0, e0 + n, stream_capturing(stream) ? -1 : shadow_due(h, e0, e0 + n, dev_done, ps))) {
+        HIP_TRY(h, hipEventRecord(h->part_done[(size_t)part], ps));                    // ranenv_wait_part still finds its event
+        return RANENV_OK;
     }
-    if (stream != ps) {
-        HIP_TRY(h, hipEventRecord(h->part_in[(size_t)part], stream));
-        HIP_TRY(h, hipStreamWaitEvent(ps, h->part_in[(size_t)part], 0));
-    }
-    AdvanceArgs a = advance_args(h, dev_done, obs_inter, obs_intra, term_obs_inter, term_obs_intra, term_obs_head);
-    a.e0 = e0;
-    h->pclass_maybe = true;
-    launch_advance(ps, (unsigned)n, a);
-    KP kp = h->kp;
-    kp.env_mask = h->d_ar_mask; kp.se_tiles = nullptr; kp.scores = nullptr; kp.intra = nullptr; kp.traffic_bits = nullptr;
-    kp.dense = nullptr; kp.obs_inter = obs_inter; kp.obs_intra = obs_intra; kp.reward = nullptr; kp.done = nullptr;
-    kp.head_reward = nullptr; kp.compact = 0;
-    finalize_kp(h, kp);
+    rc = part_handoff(h, part, stream);
+    if (rc != RANENV_OK) return rc;
+    const KP kp = autoreset_advance(h, e0, n, dev_done, obs_inter, obs_intra, term_obs_inter, term_obs_intra, term_obs_head, ps);
     const hipError_t e = launch_range<MODE_RESET>(h, kp, e0, n, ps);
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "auto-reset launch (partition %d): %s", part, hipGetErrorString(e));
     HIP_TRY(h, hipEventRecord(h->part_done[(size_t)part], ps));

@@ -513,6 +513,19 @@ def test_options_are_set_and_read_back_and_unknown_keys_fail():
         env.set_option(key, val)
         assert env.get_option(key) == val, key
     assert env.get_option("fuse_first0") == 0
+    # values outside a key's range are clamped / normalised on the way in
+    clamped = (("fuse", 100, 64), ("fuse", -1, 0), ("persist", -7, -1), ("persist", 5, 1), ("persist_chunk", 0, 1),
+               ("persist_chunk", 5000, 1000), ("persist_grid", -3, 0), ("mix", 9, 2), ("mix", -1, 0), ("tiny_step", 3, 1),
+               ("pack", 2, 1), ("compact", 5, 1), ("autoreset_shortcut", 2, 1), ("fuse_first2", -4, 0))
+    before = {key: env.get_option(key) for key, _, _ in clamped}
+    for key, val, stored in clamped:
+        env.set_option(key, val)
+        assert env.get_option(key) == stored, (key, val)
+    for key, val in before.items():
+        env.set_option(key, val)               # (the rollout below steps under the settings of above)
+    env.set_option("persist_inject_abort", 0)
+    with pytest.raises(RanEnvError):
+        env.get_option("persist_inject_abort")  # (settable, not readable)
     with pytest.raises(RanEnvError):
         env.set_option("no_such_knob", 1)
     with pytest.raises(RanEnvError):

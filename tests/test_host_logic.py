@@ -294,9 +294,10 @@ def test_create_rejects_unknown_flag_bits():
         assert ("unknown bits in flags" in msg) == bad, (hex(flags), st, msg)
 
 
-def test_options_table_in_the_header_matches_the_library_and_the_environment_is_read_in_one_place():
+def test_options_table_of_the_library_matches_the_header_and_the_environment_is_read_in_one_place():
     """VERDICT r3 hygiene: every knob of the launch schedule is an option documented in include/ranenv.h ("Options"); the keys
-    the library accepts are exactly the documented ones, and the library's host side (csrc/ranenv_host.cpp) reads the process environment in ONE function; no other translation unit reads it at all."""
+    of the library's options table (csrc/ranenv_host.cpp) are exactly the documented ones, every settable key but the test hook is
+    preset from RANENV_<KEY>, and the host side reads the process environment in ONE function; no other translation unit reads it at all."""
     import re
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     hdr = open(os.path.join(repo, "include", "ranenv.h")).read()
@@ -306,20 +307,26 @@ def test_options_table_in_the_header_matches_the_library_and_the_environment_is_
         assert "getenv(" not in open(os.path.join(csrc, other)).read(), other
     table = hdr[hdr.index("/* Options:"):hdr.index("int ranenv_set_option")]
     documented = set(re.findall(r'^ \*\s+(?:\.\.\. )?"(\w+)"', table, flags=re.M))
+    # the options table of the host side: one row per key, {"key", preset from RANENV_<KEY>?, setter, getter}
+    rows_src = src[src.index("const Option options[]"):src.index("\n};", src.index("const Option options[]"))]
+    rows = dict(re.findall(r'\{"(\w+)", (true|false),', rows_src))
+    assert len(rows) == len(re.findall(r'\{"\w+"', rows_src))
+    accepted = set(rows)
     setter = src[src.index("int set_option(ranenv_handle h"):src.index("void apply_env_options")]
-    accepted = set(re.findall(r'k == "(\w+)"', setter))
-    if 'k.rfind("fuse_first"' in setter:
+    if "fuse_first_index(k)" in setter:
         accepted |= {"fuse_first0", "fuse_first9"}
     read_only = {"persist_errors", "persist_stat_keep", "last_rollout_persistent"}          # (answered by ranenv_get_option only)
     no_env = {"persist_inject_abort"}                            # (a test hook: set per handle only)
     assert accepted <= documented, accepted - documented
     assert documented - accepted <= read_only, documented - accepted - read_only
     accepted -= no_env
+    assert {k for k, env in rows.items() if env == "false"} == no_env
     # every documented env variable is RANENV_<KEY>, and getenv appears inside apply_env_options only
     env_fn = src[src.index("void apply_env_options"):src.index("}  // namespace", src.index("void apply_env_options"))]
     assert src.count("getenv(") == env_fn.count("getenv(") == 2
+    assert "for (const Option &o : options)" in env_fn and '"RANENV_"' in env_fn and '"RANENV_FUSE_FIRST"' in env_fn
     for key in accepted - {"fuse_first0", "fuse_first9"}:
-        assert f'"{key}"' in env_fn, key
+        assert rows[key] == "true", key
         assert "RANENV_" + key.upper() in table, key
 
 
