@@ -120,7 +120,7 @@ typedef struct {
     const int32_t *slice_buffer_latency; /* [n][S] TTIs                             */
     const int32_t *slice_message_size;   /* [n][S] bits                             */
     const int32_t *slice_nparams;        /* [n][S] 0..3                             */
-    const int32_t *param_metric;         /* [n][S][3] RANENV_METRIC_*               */
+    const int32_t *param_metric;         /* [n][S][3] RANENV_METRIC_*, each once per slice */
     const int32_t *param_op;             /* [n][S][3] RANENV_OP_*                   */
     const double  *param_value;          /* [n][S][3]                               */
     const int32_t *sorted_slices;        /* [n][S] IBSched.sorted_slices            */
@@ -176,7 +176,10 @@ int ranenv_abi_version(void);
 int ranenv_create(const ranenv_config *cfg, ranenv_handle *out);
 int ranenv_destroy(ranenv_handle h);
 
-/* Copy `count` scenario rows (host) into the pool at rows [first, first+count). */
+/* Copy `count` scenario rows (host) into the pool at rows [first, first+count).
+ * A slice may declare every metric at most once among its slice_nparams parameters: the reference adds one drift
+ * term per parameter (intent_drift_calc, agents/common.py), the step kernel keeps one (operator, value) per metric.
+ * Rows with two parameters on one metric are refused with RANENV_E_INVALID and nothing is copied. */
 int ranenv_load_scenarios(ranenv_handle h, int32_t first, int32_t count,
                           const ranenv_scenario_tables *host_tables, void *stream);
 

@@ -883,10 +883,13 @@ int ranenv_load_scenarios(ranenv_handle h, int32_t first, int32_t count, const r
             if (k < npar && (m < 0 || m > 2 || op < 0 || op > 4)) return fail(h, RANENV_E_INVALID, "bad intent parameter (metric %d, op %d)", m, op);
             pi[(i * 3 + k) * 2] = m; pi[(i * 3 + k) * 2 + 1] = op; pf[i * 3 + k] = t->param_value[i * 3 + k];
         }
-        // the same by metric, as intent_drift_calc walks the parameters (agents/common.py:132-335: a later one for the same metric wins)
+        // the same by metric, which is the table the step kernel reads.  intent_drift_calc ACCUMULATES once per parameter (agents/common.py:
+        // `observations[...] +=`), so two parameters on one metric would add up there while one by-metric entry holds a single (op, value):
+        // such a table is refused (include/ranenv.h), as ScenarioTables.set_from_reference refuses the request it would come from
         for (int m = 0; m < 3; m++) { bmi[(i * 3 + m) * 2] = 0; bmi[(i * 3 + m) * 2 + 1] = 0; bmf[i * 3 + m] = 1.0; }
         for (int k = 0; k < npar; k++) {
             const int m = t->param_metric[i * 3 + k];
+            if (bmi[(i * 3 + m) * 2]) return fail(h, RANENV_E_INVALID, "scenario %zu slice %zu declares metric %d twice: one parameter per metric and slice", i / S, i % S, m);
             bmi[(i * 3 + m) * 2] = 1; bmi[(i * 3 + m) * 2 + 1] = t->param_op[i * 3 + k]; bmf[i * 3 + m] = t->param_value[i * 3 + k];
         }
         for (int k = 0; k < nues; k++) {

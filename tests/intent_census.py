@@ -1,0 +1,270 @@
+"""Helper, not a test module: replays directed cases (tests/directed_intents.py) on the CPU oracle, restates intent drift,
+observation head and reward in plain numpy float64 from the ``raw()`` histories, and counts which branches the inputs take.
+
+``restate`` follows agents/common.py (intent_drift_calc, calculate_slice_ue_obs, calculate_reward_no_mask) and
+agents/ib_sched.py (obs_space_format) directly, not oracle/ranenv_oracle.c: it is a second, independent statement of the
+same rules, which the planted variants of tests/test_intent_branches_cpu.py then bend one at a time.
+"""
+from __future__ import annotations
+
+from collections import Counter
+from typing import Dict, List, Optional
+
+import numpy as np
+
+from oracle import pyoracle
+from tests import directed_intents as di
+
+OUTCOMES = ("over", "band", "violated")
+METRICS = ("throughput", "reliability", "latency")
+OP_NAMES = ("GE", "LE", "EQ", "GT", "LT")
+REWARD_BRANCHES = ("none_negative", "priority_negative", "other_negative")
+VARIANTS = ("gt_as_ge", "lt_as_le", "eq_as_ge", "band_without_1_minus_o", "overfulfill_fixed", "norm_traffic_fixed",
+            "norm_ues_fixed", "norm_se_fixed", "later_parameter_wins", "latency_denominator", "reward_two_without_minus_1")
+
+_OPS = {0: np.greater_equal, 1: np.less_equal, 2: np.equal, 3: np.greater, 4: np.less}
+
+
+def restate(tabs, sc: int, window: List[dict], se_mean: np.ndarray, scal: dict, variant: Optional[str] = None,
+            census: Optional[Counter] = None):
+    """Drift [S, Us, 3], obs_inter [S * 10] and reward [S + 1] of one env at one TTI.  ``window``: the raw observations the
+    agent's deque holds, newest first (at most hist_depth; each a dict of [U] float64 sent / dropped / occ / lat)."""
+    S, Us = tabs.n_slices, tabs.max_ues_slice
+    o = 0.2 if variant == "overfulfill_fixed" else scal["overfulfill"]
+    norm_traffic = 120.0 if variant == "norm_traffic_fixed" else scal["norm_traffic"]
+    norm_ues = 5.0 if variant == "norm_ues_fixed" else scal["norm_ues"]
+    norm_se = 40.0 if variant == "norm_se_fixed" else scal["norm_se"]
+    ops = dict(_OPS)
+    if variant == "gt_as_ge": ops[3] = np.greater_equal
+    if variant == "lt_as_le": ops[4] = np.less_equal
+    if variant == "eq_as_ge": ops[2] = np.greater_equal
+    r0 = window[0]
+    drift = np.zeros((S, Us, 3))
+    with np.errstate(divide="ignore", invalid="ignore"):       # np.where evaluates the side it does not take, too
+        for s in range(S):
+            if not tabs.slice_has_req[sc, s]:
+                continue
+            n = int(tabs.slice_nues[sc, s])
+            ues = tabs.slice_ues[sc, s, :n]
+            for p in range(int(tabs.slice_nparams[sc, s])):
+                m, op, value = int(tabs.param_metric[sc, s, p]), int(tabs.param_op[sc, s, p]), float(tabs.param_value[sc, s, p])
+                if m == 0:
+                    x = r0["sent"][ues] * float(tabs.slice_message_size[sc, s]) / 1e6
+                    empty = np.isclose(r0["occ"][ues], 0.0)
+                    if len(window) > 1:
+                        empty = empty | np.isclose(window[1]["occ"][ues], 0.0)
+                    x = np.where(empty, value * (1.1 + o), x)
+                    ok = ops[op](x, value)
+                    over = ok & (x > value * (1.0 + o))
+                    term = np.where(ok, np.where(over, 1.0, (x - value) / (value * o)), -(value - x) / value)
+                elif m == 1:
+                    sent_w = np.sum([r["sent"][ues] for r in window], axis=0)
+                    drop_w = np.sum([r["dropped"][ues] for r in window], axis=0)
+                    pkts = r0["occ"][ues] * float(tabs.slice_buffer_size[sc, s]) + drop_w + sent_w
+                    x = np.where(pkts != 0.0, drop_w / np.where(pkts != 0.0, pkts, 1.0), 0.0)
+                    band = (100.0 - value) / 100.0
+                    ok = ops[op](100.0 * (1.0 - x), value)
+                    over = ok & (x < (band if variant == "band_without_1_minus_o" else band * (1.0 - o)))
+                    term = np.where(ok, np.where(over, 1.0, (band - x) / (band * o)), -(x - band) / (value / 100.0))
+                else:
+                    x = r0["lat"][ues]
+                    max_latency = float(tabs.slice_buffer_latency[sc, s])
+                    ok = ops[op](x, value)
+                    over = ok & (x < value * (1.0 - o))
+                    den = max_latency if variant == "latency_denominator" else max_latency - value
+                    term = np.where(ok, np.where(over, 1.0, (value - x) / (value * o)), -(x - value) / den)
+                if variant == "later_parameter_wins":
+                    drift[s, :n, m] = term
+                else:
+                    drift[s, :n, m] += term
+                if census is not None:
+                    census[("cell", m, "over")] += int(over.sum())
+                    census[("cell", m, "band")] += int((ok & ~over).sum())
+                    census[("cell", m, "violated")] += int((~ok).sum())
+                    census[("op", m, op, True)] += int(ok.sum())
+                    census[("op", m, op, False)] += int((~ok).sum())
+    # obs_space_format: the inter-slice rows in sorted order
+    obs_inter = np.zeros(S * 10)
+    values = np.full((S, 3), -2.0)          # calculate_slice_ue_obs marks an undeclared metric with -2 ...
+    for pos in range(S):
+        s = int(tabs.sorted_slices[sc, pos])
+        n = int(tabs.slice_nues[sc, s])
+        if n > 0 and tabs.slice_has_req[sc, s]:
+            for p in range(int(tabs.slice_nparams[sc, s])):
+                m = int(tabs.param_metric[sc, s, p])
+                values[s, m] = np.mean(drift[s, :n, m])
+        elif n > 0 and census is not None:
+            census[("alloc", "ues_without_requirement")] += 1
+    declared = ~np.isclose(values, -2.0)    # ... and obs_space_format reads the mark back with np.isclose: a declared metric whose
+    values[~declared] = 0.0                 # mean drift is -2 (possible: a violated drift is unbounded below) counts as undeclared
+    for pos in range(S):
+        s = int(tabs.sorted_slices[sc, pos])
+        n = int(tabs.slice_nues[sc, s])
+        ues = tabs.slice_ues[sc, s, :n]
+        row = obs_inter[pos * 10:pos * 10 + 10]
+        row[0:3] = values[s]; row[3:6] = declared[s]
+        row[6] = tabs.slice_priority[sc, s] if n != 0 else 0.0
+        row[7] = (tabs.slice_traffic[sc, s] if tabs.slice_active[sc, s] == 1 else 0.0) / norm_traffic
+        row[8] = n / norm_ues
+        row[9] = (np.mean(se_mean[ues]) if n > 0 else 0.0) / norm_se
+    # calculate_reward_no_mask over the active slices, in slice order
+    active = tabs.slice_active[sc] != 0
+    act = np.where(active, values.min(axis=1), 0.0)       # an undeclared metric stands as 0.0 in the row: it takes part in the minimum
+    prio = np.where(active, tabs.slice_priority[sc], 0.0)
+    reward = np.zeros(S + 1)
+    if not np.any(act < 0):
+        reward[0] = np.mean(act); branch = "none_negative"
+    elif np.any(prio * act < 0):
+        reward[0] = np.mean(act[prio * act < 0]) - (0.0 if variant == "reward_two_without_minus_1" else 1.0); branch = "priority_negative"
+    else:
+        reward[0] = np.mean(act[act < 0]); branch = "other_negative"
+    for s in range(S):
+        reward[s + 1] = values[s][declared[s]].min() if declared[s].any() else 0.0
+    if census is not None:
+        census[("reward", branch)] += 1
+        census[("env_steps",)] += 1
+        if not active.any():
+            census[("alloc", "no_active_slice")] += 1
+    return drift, obs_inter, reward
+
+
+def _inter_allocation_census(tabs, sc, scores, n_rbgs, census):
+    """scores_to_rbs + round_int_equal_sum (agents/common.py:442-505): did the floors already add up to the target?"""
+    active = tabs.slice_active[sc]
+    if active.sum() == 0:
+        return
+    action = np.where(active != 0, np.asarray(scores, dtype=np.float64)[tabs.sorted_slices[sc]], -1.0)
+    tot = np.sum(action + 1.0)
+    v = n_rbgs * (action + 1.0) / tot if tot != 0.0 else (n_rbgs / np.sum(active)) * active
+    nz = v[v != 0.0]
+    if len(nz) and n_rbgs - int(np.floor(n_rbgs * nz / np.sum(nz)).sum()) == 0:
+        census[("alloc", "nothing_left_to_hand_out")] += 1
+    if tot == 0.0:
+        census[("alloc", "all_scores_minus_one")] += 1
+
+
+def replay(case: dict, census: Optional[Counter] = None, keep: bool = True, tables=None, extra=None):
+    """Run one directed case on the oracle.  Returns a dict: the materialised inputs, ``oenvs``, and per TTI ``steps[t]`` =
+    (scores [B, S], intra [B, S], [per env (rb_count, raw, obs, drift, window, se_mean[, extra(oracle env, b)])])."""
+    c = case
+    d, scen, se_pool, trf = di.materialise(c)
+    tabs = d.tables if tables is None else tables
+    S, U, R, G, Us, B, T = c["S"], c["U"], c["R"], c["G"], c["Us"], c["B"], c["steps"]
+    cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=T, hist_depth=c["D"], **c["scalars"])
+    oenvs, windows = [], []
+    for b in range(B):
+        o = pyoracle.OracleEnv(cfg); o.set_scale_per_element(c["per_element"]); o.set_scenario(tabs, int(scen[b])); o.reset(se_pool[b * T])
+        oenvs.append(o)
+        windows.append([dict(sent=np.zeros(U), dropped=np.zeros(U), occ=np.zeros(U), lat=np.zeros(U))])
+    steps = []
+    for t in range(T):
+        if c["policy"] == 0:
+            sc, ic = di.external_action(c, t)
+            if c["intra"] != 255:               # the caller's scores with one intra scheduler for all slices
+                ic = np.full_like(ic, c["intra"])
+        else:
+            sc = np.stack([o.policy_marr() if c["policy"] == 1 else o.policy_mapf() for o in oenvs])
+            ic = np.full((B, S), c["intra"], dtype=np.uint8)
+        per_env = []
+        for b, o in enumerate(oenvs):
+            _, count, _ = o.action_format(sc[b], ic[b], want_dense=False)
+            tile = se_pool[b * T + t]
+            o.step(sc[b], ic[b], tile, trf[b * T + t])
+            raw = o.raw()
+            windows[b] = ([dict(sent=raw["pkt_effective_thr"], dropped=raw["dropped_pkts"], occ=raw["buffer_occupancies"],
+                                lat=raw["buffer_latencies"])] + windows[b])[:c["D"]]
+            se_mean = np.array([np.mean(tile[u].astype(np.float64)) for u in range(U)])
+            if census is not None:
+                _inter_allocation_census(tabs, int(scen[b]), sc[b], R // G, census)
+            per_env.append((count, raw, o.obs(), o.drift(), list(windows[b]), se_mean) + (() if extra is None else (extra(o, b),)))
+        steps.append((sc, ic, per_env))
+        if not keep and t > 0:
+            steps[t - 1] = None
+    return dict(case=c, directed=d, tables=tabs, scen=scen, se_pool=se_pool, trf=trf, oenvs=oenvs, steps=steps)
+
+
+def replay_fuzz_case(k: int, per_element: bool = False):
+    """The oracle half of tests/test_gpu_fuzz.py's case ``k`` (same draws in the same order), in replay()'s form: the
+    template-only inputs the directed ones are measured against."""
+    from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
+    from tests.common import poisson_traffic_rows
+    from tests.synth import se_tile
+    from tests.test_gpu_fuzz import _draw_case
+    c = _draw_case(k)
+    S, U, R, G, Us, D, T = c["S"], c["U"], c["R"], c["G"], c["Us"], c["D"], c["steps"]
+    rng = np.random.default_rng(500 + k)
+    tabs = generate_scaled_scenarios(4, seed=40 + k, n_slices=S, n_ues=U, max_ues_slice=Us,
+                                     min_slices=max(1, min(S, U // max(1, Us)) // 2), min_ues=max(1, Us // 3))
+    B = 7
+    scen = rng.integers(0, tabs.n_scenarios, B)
+    se_pool = np.stack([se_tile(300 + k, t, U, R, low_se_every=c["low_se"]) for t in range(B * T)])
+    trf = np.floor(np.concatenate([poisson_traffic_rows(tabs, int(scen[b]), rng, T) for b in range(B)]) * c["load"])
+    cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=T, hist_depth=D)
+    oenvs, windows = [], []
+    for b in range(B):
+        o = pyoracle.OracleEnv(cfg); o.set_scale_per_element(per_element); o.set_scenario(tabs, int(scen[b])); o.reset(se_pool[b * T])
+        oenvs.append(o)
+        windows.append([dict(sent=np.zeros(U), dropped=np.zeros(U), occ=np.zeros(U), lat=np.zeros(U))])
+    steps = []
+    for t in range(T):
+        if c["how"] == "external":
+            sc = rng.uniform(-1, 1, (B, S))
+            sc[rng.random((B, S)) < 0.15] = -1.0
+            ic = rng.integers(0, 3, (B, S)).astype(np.uint8)
+        else:
+            sc = np.stack([o.policy_marr() if c["policy"] == 1 else o.policy_mapf() for o in oenvs])
+            ic = np.full((B, S), c["intra"], dtype=np.uint8)
+        per_env = []
+        for b, o in enumerate(oenvs):
+            _, count, _ = o.action_format(sc[b], ic[b], want_dense=False)
+            tile = se_pool[b * T + t]
+            o.step(sc[b], ic[b], tile, trf[b * T + t])
+            raw = o.raw()
+            windows[b] = ([dict(sent=raw["pkt_effective_thr"], dropped=raw["dropped_pkts"], occ=raw["buffer_occupancies"],
+                                lat=raw["buffer_latencies"])] + windows[b])[:D]
+            per_env.append((count, raw, o.obs(), o.drift(), list(windows[b]), np.mean(tile.astype(np.float64), axis=1)))
+        steps.append((sc, ic, per_env))
+    return dict(case=dict(c, scalars=dict(di.DEFAULT_SCALARS), name=f"fuzz-{k}"), tables=tabs, scen=scen, se_pool=se_pool, trf=trf,
+                oenvs=oenvs, steps=steps)
+
+
+def largest_difference(run, variant: Optional[str] = None):
+    """max |restatement - oracle| over a run: (drift, obs_inter, reward).  NaN against a number counts as infinite."""
+    worst = [0.0, 0.0, 0.0]
+    for sc_, ic_, per_env in run["steps"]:
+        for b, (count, raw, obs, drift, window, se_mean) in enumerate(per_env):
+            got = restate(run["tables"], int(run["scen"][b]), window, se_mean, run["case"]["scalars"], variant=variant)
+            for i, (x, y) in enumerate(zip(got, (drift, obs["obs_inter"], obs["reward"]))):
+                with np.errstate(invalid="ignore"):
+                    e = np.where(x == y, 0.0, np.abs(x - y))
+                e = np.where(np.isnan(x) & np.isnan(y), 0.0, np.where(np.isnan(e), np.inf, e))
+                worst[i] = max(worst[i], float(e.max()) if e.size else 0.0)
+    return tuple(worst)
+
+
+def census_of(cases=di.CASES) -> Counter:
+    """Branch counts of the directed cases, from the numpy restatement (which test_intent_branches_cpu.py holds equal to the
+    oracle's drift, observation and reward on the same inputs)."""
+    cen: Counter = Counter()
+    for c in cases:
+        run = replay(c, census=cen)
+        for sc_, ic_, per_env in run["steps"]:
+            for b, (count, raw, obs, drift, window, se_mean) in enumerate(per_env):
+                restate(run["tables"], int(run["scen"][b]), window, se_mean, c["scalars"], census=cen)
+    return cen
+
+
+def format_census(cen: Counter) -> str:
+    out = [f"env-steps {cen[('env_steps',)]}"]
+    for m, name in enumerate(METRICS):
+        tot = sum(cen[("cell", m, oc)] for oc in OUTCOMES)
+        out.append(f"{name:12s} evaluations {tot:7d}: " + ", ".join(f"{oc} {cen[('cell', m, oc)]} ({100.0 * cen[('cell', m, oc)] / max(tot, 1):.1f} %)" for oc in OUTCOMES))
+        out.append(" " * 13 + "operators fulfilled/violated: " + ", ".join(f"{OP_NAMES[op]} {cen[('op', m, op, True)]}/{cen[('op', m, op, False)]}" for op in range(5)))
+    n = max(cen[("env_steps",)], 1)
+    out.append("reward branches: " + ", ".join(f"{br} {cen[('reward', br)]} ({100.0 * cen[('reward', br)] / n:.1f} %)" for br in REWARD_BRANCHES))
+    out.append("allocation: " + ", ".join(f"{k[1]} {v}" for k, v in sorted(cen.items()) if k[0] == "alloc"))
+    return "\n".join(out)
+
+
+if __name__ == "__main__":
+    print(format_census(census_of()))

@@ -1,0 +1,158 @@
+"""CPU: do the directed intent inputs (tests/directed_intents.py) reach every branch, and would a comparison with the
+oracle on them notice a kernel that is subtly wrong?
+
+Three parts, oracle only:
+
+* the census conditions: on the directed cases every (metric, outcome) cell, every operator on every metric (fulfilled
+  and violated) and every reward branch is populated.  These are conditions on the *inputs*; they keep
+  tests/test_gpu_intent_branches.py from passing vacuously.
+* tests/intent_census.restate -- drift, inter-slice observation and reward in plain numpy float64 from the ``raw()``
+  histories, written from agents/common.py and agents/ib_sched.py -- equals the oracle on the directed cases (1e-12).
+* planted variants of that restatement, each one plausible slip of a kernel: on the directed inputs every one of them
+  differs from the oracle by more than the bar of the device tests (1e-5 in an observation or 1e-9 in a reward) in at
+  least one compared value.
+
+Measured on the template-only inputs of tests/test_gpu_fuzz.py (all 24 cases, oracle half): of the eleven variants they
+separate two -- ``latency_denominator`` (largest difference 0.19 in a drift) and ``reward_two_without_minus_1`` (1.0).
+They do NOT separate the other nine: ``gt_as_ge``, ``lt_as_le``, ``eq_as_ge`` (no template uses those operators),
+``band_without_1_minus_o`` (no reliability evaluation of theirs is fulfilled without being over-fulfilled),
+``overfulfill_fixed`` and the three ``norm_*_fixed`` (every handle has the defaults), ``later_parameter_wins`` (no
+template declares a metric twice).  test_template_inputs_do_not_separate_most_variants pins that measurement.
+"""
+from collections import Counter
+
+import numpy as np
+import pytest
+
+from tests import directed_intents as di
+from tests import intent_census as ic
+
+OBS_TOL, REW_TOL = 1e-5, 1e-9
+SEPARATED_BY_TEMPLATES = ("latency_denominator", "reward_two_without_minus_1")
+
+
+@pytest.fixture(scope="module")
+def directed_runs():
+    return [ic.replay(c) for c in di.CASES] + [ic.replay(di.RANGE_INTENT_CASE)]
+
+
+@pytest.fixture(scope="module")
+def census(directed_runs):
+    cen = Counter()
+    for run in directed_runs[:len(di.CASES)]:                # (the range intents are not part of the device tests)
+        c = run["case"]
+        for t, (sc, ic_, per_env) in enumerate(run["steps"]):
+            for b, (count, raw, obs, drift, window, se_mean) in enumerate(per_env):
+                ic._inter_allocation_census(run["tables"], int(run["scen"][b]), sc[b], c["R"] // c["G"], cen)
+                ic.restate(run["tables"], int(run["scen"][b]), window, se_mean, c["scalars"], census=cen)
+    print("\n" + ic.format_census(cen))
+    return cen
+
+
+def test_every_metric_outcome_cell_is_populated(census):
+    """At least 200 evaluations and at least 5 % of the metric's evaluations over-fulfilled, in the band, and violated."""
+    for m, name in enumerate(ic.METRICS):
+        total = sum(census[("cell", m, oc)] for oc in ic.OUTCOMES)
+        for oc in ic.OUTCOMES:
+            n = census[("cell", m, oc)]
+            assert n >= 200 and n >= 0.05 * total, (name, oc, n, total)
+
+
+def test_every_operator_is_fulfilled_and_violated_on_every_metric(census):
+    for m, name in enumerate(ic.METRICS):
+        for op in range(5):
+            for ok in (True, False):
+                assert census[("op", m, op, ok)] >= 20, (name, ic.OP_NAMES[op], "fulfilled" if ok else "violated", census[("op", m, op, ok)])
+
+
+def test_every_reward_branch_and_allocation_case_is_populated(census):
+    steps = census[("env_steps",)]
+    assert steps >= 2000
+    for br in ic.REWARD_BRANCHES:
+        assert census[("reward", br)] >= 0.10 * steps, (br, census[("reward", br)], steps)
+    for what in ("ues_without_requirement", "nothing_left_to_hand_out", "all_scores_minus_one", "no_active_slice"):
+        assert census[("alloc", what)] >= 10, (what, census[("alloc", what)])
+
+
+def test_directed_tables_hold_what_they_promise():
+    """One, two and three parameters in every metric order, all five operators on all three metrics, inactive slices with
+    UEs, slices with UEs and no requirement, slices without UEs, both priorities -- in the tables themselves."""
+    orders, ops, roles, prios = set(), set(), Counter(), set()
+    for c in di.CASES:
+        t = di.materialise(c)[0].tables
+        for i in range(t.n_scenarios):
+            for s in range(t.n_slices):
+                n, np_ = int(t.slice_nues[i, s]), int(t.slice_nparams[i, s])
+                roles["no_ue"] += n == 0
+                roles["no_requirement"] += n > 0 and not t.slice_has_req[i, s]
+                roles["inactive_with_ues"] += n > 0 and not t.slice_active[i, s] and bool(t.slice_has_req[i, s])
+                if t.slice_has_req[i, s] and n > 0:
+                    orders.add(tuple(t.param_metric[i, s, :np_])); prios.add(float(t.slice_priority[i, s]))
+                    ops.update((int(t.param_metric[i, s, p]), int(t.param_op[i, s, p])) for p in range(np_))
+    assert orders == set(di.METRIC_ORDERS)
+    assert ops == {(m, op) for m in range(3) for op in range(5)}
+    assert prios == {0.0, 1.0} and min(roles.values()) >= 3, roles
+
+
+def test_the_numpy_restatement_equals_the_oracle(directed_runs):
+    for run in directed_runs:
+        worst = ic.largest_difference(run)
+        assert max(worst) <= 1e-12, (run["case"]["name"], worst)
+
+
+def test_the_oracle_is_finite_and_below_256_on_the_directed_cases(directed_runs):
+    """Requirement values 100 (reliability) and 0 (latency) appear with the operators under which no 0 / 0 arises; a NaN in
+    the expected values would make a comparison with the device say less than it seems to.  And every observation stays
+    below 256 in magnitude: the device tests hold float32 observations to 1e-5 absolute, and half a float32 ulp is 1.5e-5
+    from 256 on -- no float32 output could meet the bar there (a violated or band drift is unbounded: (value - x) / (value o))."""
+    for run in directed_runs:
+        for sc, ic_, per_env in run["steps"]:
+            for count, raw, obs, drift, window, se_mean in per_env:
+                assert max(np.abs(obs["obs_inter"]).max(), np.abs(obs["obs_intra"]).max()) < 256.0, run["case"]["name"]
+                assert np.isfinite(drift).all() and np.isfinite(obs["obs_inter"]).all() and np.isfinite(obs["obs_intra"]).all()
+                assert np.isfinite(obs["reward"]).all()
+
+
+def _separates(runs, variant):
+    """(does any run tell the variant from the oracle, largest differences seen); stops at the first run that does."""
+    worst = np.zeros(3)
+    for r in runs:
+        worst = np.maximum(worst, ic.largest_difference(r, variant))
+        if worst[0] > OBS_TOL or worst[1] > OBS_TOL or worst[2] > REW_TOL:
+            return True, worst
+    return False, worst
+
+
+@pytest.mark.parametrize("variant", ic.VARIANTS)
+def test_a_planted_variant_differs_from_the_oracle_on_the_directed_inputs(directed_runs, variant):
+    hit, worst = _separates(directed_runs, variant)
+    print(variant, "largest |variant - oracle| (drift, obs_inter, reward):", worst)
+    assert hit, (variant, worst)
+    if variant != "later_parameter_wins":       # ... and on the cases the device runs, without the range intents
+        assert _separates(directed_runs[:len(di.CASES)], variant)[0], variant
+
+
+def test_template_inputs_do_not_separate_most_variants():
+    """The measurement of the module docstring: the oracle half of tests/test_gpu_fuzz.py, all 24 cases."""
+    runs = [ic.replay_fuzz_case(k) for k in range(24)]
+    assert max(max(ic.largest_difference(r)) for r in runs) <= 1e-12
+    separated = tuple(v for v in ic.VARIANTS if _separates(runs, v)[0])
+    assert separated == SEPARATED_BY_TEMPLATES, separated
+
+
+def test_a_range_intent_accumulates_in_the_oracle_and_is_refused_by_the_tables():
+    """Two parameters on one metric: the oracle adds both drift terms, as the reference does; set_from_reference refuses
+    the request (and ranenv_load_scenarios the table: tests/test_gpu_intent_branches.py)."""
+    from intent_radio_sched_multi_slice_amd.scenario import OP_UFUNC, ScenarioTables
+    run = ic.replay(di.RANGE_INTENT_CASE)
+    t = run["tables"]
+    assert np.any((t.slice_nparams == 2) & (t.param_metric[:, :, 0] == t.param_metric[:, :, 1]) & (t.slice_nues > 0))
+    assert max(ic.largest_difference(run)) <= 1e-12                                  # the sum of both terms
+    assert ic.largest_difference(run, "later_parameter_wins")[0] > OBS_TOL           # not the second term alone
+    tabs = ScenarioTables.empty(1, 2, 4, 2)
+    par = lambda op, v: {"name": "throughput", "value": v, "unit": "", "operator": OP_UFUNC[op]}
+    req = {"slice_0": {"name": "range", "priority": 0, "parameters": {"par1": par(0, 10.0), "par2": par(1, 50.0)},
+                       "ues": {"buffer_size": 64, "buffer_latency": 10, "message_size": 8192, "mobility": 0, "traffic": 20}},
+           "slice_1": {}}
+    with pytest.raises(ValueError, match="once per slice"):
+        tabs.set_from_reference(0, np.ones((1, 2)), np.eye(2, 4), req)
