@@ -1,0 +1,125 @@
+"""The reference's PPO loop in miniature with the host out of sample collection: `collect()` leaves a whole training batch on the GPU.
+
+    python examples/train_ppo_on_device.py [--batch 4096] [--ttis 64] [--iters 10] [--epochs 4] [--minibatch 65536]
+
+The reference trains IBSched with RLlib PPO + GAE (agents/ray_agent.py:154-166,301-375): two shared policies -- the inter-slice agent
+("player_0", masked diagonal Gaussian over S scores) and the intra-slice agents ("player_{s+1}", Discrete(3)) -- each a
+FullyConnectedNetwork with a value branch.  Here per iteration:
+
+  1. `env.collect(T)`: T TTIs of B envs under the actors ON THE DEVICE; observations, masks, sampled actions, log-probabilities,
+     value predictions, rewards, dones, GAE advantages and value targets stay in HBM (no host work between two TTIs);
+  2. `--epochs` passes of minibatch SGD in torch over the recorded batch with PPO's clipped surrogate, value loss and entropy bonus
+     (clip 0.2, vf coefficient 0.5, entropy coefficient 0.01, gradient clip 0.5, lr 3e-4, gamma 0.99, lambda 0.95: the reference's
+     defaults); intra rows of inactive slices (mask_inter 0) are dropped, as the reference's env gives those agents no step;
+  3. `set_policy_network` / `set_value_network` with the new weights.
+
+An example of the API, not a tuned trainer: minibatches are far larger than the reference's 64 so that the SGD side does not drown
+the measurement in tiny kernels.  Prints env-steps/s with the updates included, the share of collection in it, and the mean
+inter-slice reward per iteration.
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from intent_radio_sched_multi_slice_amd._lib import INTRA_PF, POLICY_MAPF
+from intent_radio_sched_multi_slice_amd.adapters import masked_gaussian_params, sorted_action_mask
+from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
+
+CLIP, VF_COEFF, ENT_COEFF, GRAD_CLIP, LR, GAMMA, LAMBDA = 0.2, 0.5, 0.01, 0.5, 3e-4, 0.99, 0.95
+
+
+def mlp(n_in, n_out, width=64):
+    return torch.nn.Sequential(torch.nn.Linear(n_in, width), torch.nn.Tanh(), torch.nn.Linear(width, width), torch.nn.Tanh(),
+                               torch.nn.Linear(width, n_out))
+
+
+def ppo_loss(logp, logp_old, entropy, value, adv, vtarg):
+    adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    ratio = torch.exp(logp - logp_old)
+    surrogate = torch.minimum(ratio * adv, ratio.clamp(1.0 - CLIP, 1.0 + CLIP) * adv)
+    return -surrogate.mean() + VF_COEFF * (value - vtarg).pow(2).mean() - ENT_COEFF * entropy.mean()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--ttis", type=int, default=64, help="TTIs per collect() call: the train batch is batch x ttis env-steps")
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--minibatch", type=int, default=65536)
+    ap.add_argument("--episode-len", type=int, default=100)
+    ap.add_argument("--se-mode", choices=("stream", "gather"), default="gather")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    B, T, L = args.batch, args.ttis, args.episode_len
+    n_ep = 64
+    wl = make_mult_slice_workload(B, dev, policy=POLICY_MAPF, intra=INTRA_PF, n_scenarios=n_ep, n_traces=n_ep, trace_len=L, max_steps=L)
+    env = wl.env
+    S, W = env.S, env.W
+    env.set_se_mode(args.se_mode)
+    ep = np.arange(n_ep)
+    env.set_episode_table(scenario=ep, se_base=ep * L, se_len=L, trf_base=ep * L, trf_len=L)
+    env.enable_autoreset(0, n_ep, random_episodes=True, seed=7, episode_numbers=np.arange(B) % n_ep)
+
+    torch.manual_seed(0)
+    pi_inter, vf_inter, pi_intra, vf_intra = mlp(10 * S, 2 * S).to(dev), mlp(10 * S, 1).to(dev), mlp(W, 3).to(dev), mlp(W, 1).to(dev)
+    with torch.no_grad():
+        pi_inter[-1].bias[S:].fill_(-0.5)          # initial log_std
+    params = [p for m in (pi_inter, vf_inter, pi_intra, vf_intra) for p in m.parameters()]
+    opt = torch.optim.Adam(params, lr=LR)
+
+    def bind(it):
+        env.set_policy_network(pi_inter, pi_intra, stochastic=True, seed=1000 + it)
+        env.set_value_network(vf_inter, vf_intra)
+
+    bind(0)
+    env.reset()
+    torch.cuda.synchronize()
+    t_collect, t0 = 0.0, time.perf_counter()
+    for it in range(args.iters):
+        tc = time.perf_counter()
+        rec = env.collect(T, gamma=GAMMA, lam=LAMBDA)
+        torch.cuda.synchronize()
+        t_collect += time.perf_counter() - tc
+        # ---- the recorded batch, flattened over (TTI, env) -- views, no copies; the next collect() overwrites them ----
+        N = T * B
+        obs0, act0 = rec["obs_inter"].reshape(N, 10 * S), rec["action_inter"].reshape(N, S).to(torch.float32)
+        mask0 = sorted_action_mask(rec["mask_inter"].reshape(N, S))
+        logp0, adv0, vt0 = rec["logp"][..., 0].reshape(N), rec["adv"][..., 0].reshape(N), rec["vtarg"][..., 0].reshape(N)
+        live = (rec["mask_inter"] != 0).reshape(N * S).nonzero().squeeze(1)          # intra rows of active slices only
+        obs1, act1 = rec["obs_intra"].reshape(N * S, W), rec["action_intra"].reshape(N * S).to(torch.int64)
+        logp1, adv1, vt1 = rec["logp"][..., 1:].reshape(N * S), rec["adv"][..., 1:].reshape(N * S), rec["vtarg"][..., 1:].reshape(N * S)
+        for _ in range(args.epochs):
+            perm0, perm1 = torch.randperm(N, device=dev), live[torch.randperm(live.numel(), device=dev)]
+            n_mb = max(1, N // args.minibatch)
+            for i0, i1 in zip(perm0.chunk(n_mb), perm1.chunk(n_mb)):
+                out = pi_inter(obs0[i0])
+                mean, std = masked_gaussian_params(out[:, :S], out[:, S:], mask0[i0])
+                dist = torch.distributions.Normal(mean, std)
+                loss = ppo_loss(dist.log_prob(act0[i0]).sum(-1), logp0[i0], (dist.entropy() * mask0[i0]).sum(-1),
+                                vf_inter(obs0[i0])[:, 0], adv0[i0], vt0[i0])
+                cat = torch.distributions.Categorical(logits=pi_intra(obs1[i1]))
+                loss = loss + ppo_loss(cat.log_prob(act1[i1]), logp1[i1], cat.entropy(), vf_intra(obs1[i1])[:, 0], adv1[i1], vt1[i1])
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                torch.nn.utils.clip_grad_norm_(params, GRAD_CLIP)
+                opt.step()
+        r = rec["reward"][..., 0].mean().item()
+        bind(it + 1)
+        print(f"iteration {it + 1:3d}: mean inter-slice reward {r:+.4f}, {int(rec['done'].sum())} episode ends", flush=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    n = B * T * args.iters
+    print(f"{B} envs x {T} TTIs x {args.iters} iterations, {args.epochs} epochs of minibatch {args.minibatch} each (SE mode {args.se_mode}): "
+          f"{n / dt / 1e6:.2f} M env-steps/s with the updates included; collection alone {n / t_collect / 1e6:.2f} M env-steps/s "
+          f"({100 * t_collect / dt:.0f} % of the time)")
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

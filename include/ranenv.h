@@ -384,6 +384,67 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *dev_obs_inter, float
  * on its partition's stream, before its next TTI -- the reference's evaluation loop over many episodes
  * (simu.py:547-566) without the host between two TTIs.  dev_done is required then. */
 
+/* PPO sample collection on the device (the reference trains IBSched with RLlib PPO + GAE, agents/ray_agent.py:154-166,301-375):
+ * a rollout under the policy nets that leaves the whole training batch in caller-owned device memory, so that a learner touches
+ * the device once per n_steps TTIs instead of once per TTI.
+ *
+ * ranenv_set_value_network: the critics, in the same ranenv_mlp form as the actors: inter input [10*S] -> 1 output; intra (NULL =
+ *   none) input as the bound intra actor's layout -> 1 output per (env, slice).  An intra critic without a bound intra actor, or
+ *   with another input_layout than the actor's, is RANENV_E_INVALID.  The weights go into a packed buffer of their own:
+ *   re-binding the actors does not disturb the critics and vice versa.
+ *
+ * ranenv_trajectory: caller-owned device pointers, [t]-major; slot t = the t-th TTI of the call for every env.  Any pointer may
+ *   be NULL (= not recorded); adv / vtarg need reward, vf and done.
+ *     obs_inter    f32 [T][B][10*S]        the observation the TTI's action was computed from
+ *     obs_intra    f32 [T][B][S][2*Us+9]   same, per slice     } these three are written only with an intra actor bound
+ *     mask_intra   i8  [T][B][S][Us]       that TTI's mask     } (left untouched otherwise)
+ *     action_intra u8  [T][B][S]           by slice            }
+ *     mask_inter   i8  [T][B][S]           that TTI's mask (mask_inter[b][s] != 0 also says which intra rows are live)
+ *     action_inter f64 [T][B][S]           sorted positions as obs_inter lists them: the UNCLAMPED sample mean + exp(log_std) z
+ *                                          (mode: mean) where active, exactly -1 where masked; the step consumed its clamp to [-1, 1]
+ *     logp         f32 [T][B][S+1]         column 0 player_0, column s+1 player_{s+1}; columns 1..S are 0 without an intra actor
+ *     vf           f32 [T+1][B][S+1]       value predictions, same columns; slot T: the critics on the observation left after the
+ *                                          last TTI (bootstrap); columns 1..S are 0 without an intra critic
+ *     reward       f64 [T][B][S+1]         the step's reward row
+ *     done         u8  [T][B]              the step's done flag
+ *     adv, vtarg   f32 [T][B][S+1]         GAE advantages and value targets
+ *   Arithmetic (float64 from the float32 net outputs, each result rounded once to float32, nothing contracted):
+ *     inter logp = sum over the active positions j, ascending, of ((-0.5 z_j) z_j - log_std_j) - 0.5 ln(2 pi), then
+ *                  + n_masked * (ln(1e9) - 0.5 ln(2 pi))      -- z_j the Box-Muller draw the action used (0 in the mode), the
+ *                  masked term what Normal(-1, 1e-9) gives at exactly -1: TorchDiagGaussian.logp of
+ *                  agents/masked_action_distribution.py:30-36,53-54 evaluated in float64
+ *     intra logp = (l_c - max l) - ln((exp(l_0 - max l) + exp(l_1 - max l)) + exp(l_2 - max l)),  c the recorded choice
+ *     GAE, per (env, column), t from T-1 down to 0, a_next = 0 above T-1:
+ *       nd = done[t][b] ? 0.0 : 1.0;   delta = (reward + (gamma * (double)vf[t+1]) * nd) - (double)vf[t];
+ *       a = delta + ((gamma * lambda) * nd) * a_next;   adv = (float)a;   vtarg = (float)(a + (double)vf[t]);
+ *     done ends the episode as in the reference (simu.py:559-564 reports it as terminated): no bootstrap across it; under
+ *     auto-reset vf[t+1] then belongs to the new episode's first observation and is not used.
+ *
+ * ranenv_collect: ranenv_rollout of n_steps TTIs that records.  Needs policy NETWORK with bound actors and an inter critic (else
+ *   RANENV_E_STATE), dev_obs_inter (dev_obs_intra with intra nets), bound pools / generator.  Any number of partitions, with and
+ *   without auto-reset, both SE modes, stochastic or not.  The env state, the caller's output buffers and
+ *   ranenv_get_policy_actions afterwards are bit for bit what ranenv_rollout leaves under the same nets and seed.  Per TTI and
+ *   partition: one launch per agent kind (actor, record, critic; the critic in a launch of its own for wide nets, option
+ *   "collect_split"), then the step, which writes reward / done straight into slot t
+ *   (copied to dev_reward / dev_done after the last TTI); behind the last TTI one more critic pass fills vf[T], then the GAE pass.
+ * ranenv_gae: the GAE pass alone over [n_steps][B][n_cols] buffers (other gamma / lambda, or the caller's own values). */
+typedef struct {
+    float *obs_inter, *obs_intra;
+    int8_t *mask_inter, *mask_intra;
+    double *action_inter;
+    uint8_t *action_intra;
+    float *logp, *vf;
+    double *reward;
+    uint8_t *done;
+    float *adv, *vtarg;
+} ranenv_trajectory;
+#define RANENV_TRAJECTORY_BYTES 96
+int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, void *stream);
+int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, double gamma, double lambda, float *dev_obs_inter,
+                   float *dev_obs_intra, double *dev_reward, uint8_t *dev_done, void *stream);
+int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *dev_reward, const float *dev_vf, const uint8_t *dev_done,
+               double gamma, double lambda, float *dev_adv, float *dev_vtarg, void *stream);
+
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,
  * results/gen_results.py:874-1022, kept as running sums so that a rollout needs no per-TTI read-back).  Per env 8
  * float64 sums over the TTIs of the current episode (a reset zeroes them):
@@ -494,6 +555,8 @@ int ranenv_autoreset_part(ranenv_handle h, int32_t part, const uint8_t *dev_done
  *                                                 (host-visible memory, no device sync), clears the queues, sets "persist" to 0 for the handle and
  *                                                 fails with RANENV_E_STATE: the envs have advanced different numbers of TTIs, reset the batch
  *   "persist_inject_abort" (no env variable)      test hook: 1 = the next persistent launch finds a wait already given up
+ *   "collect_split" RANENV_COLLECT_SPLIT -1       ranenv_collect: 1 = every critic runs as a launch of its own behind its actor's, 0 = fused into
+ *                                                 the actor's launch, -1 = fused where actor + critic weights are <= 3 MB (they share an XCD's L2)
  *   "autoreset_shortcut" RANENV_AUTORESET_SHORTCUT 0  1: ranenv_autoreset / _part trust the host's shadow of the step counters (see ranenv_autoreset) and
  *                                                 enqueue nothing at a TTI at which no episode ended; 0: the device reads dev_done every time.
  *                                                 (This one selects whose flags count -- with 1 the caller must not modify dev_done.)

@@ -70,6 +70,15 @@ class Mlp(C.Structure):
                 ("dims", C.c_int32 * 6), ("weight", C.c_void_p * 5), ("bias", C.c_void_p * 5)]
 
 
+TRAJECTORY_FIELDS = ("obs_inter", "obs_intra", "mask_inter", "mask_intra", "action_inter", "action_intra", "logp", "vf", "reward", "done",
+                     "adv", "vtarg")
+
+
+class Trajectory(C.Structure):
+    """ranenv_trajectory: caller-owned device pointers of a ranenv_collect record, [t]-major (NULL = not recorded)."""
+    _fields_ = [(n, C.c_void_p) for n in TRAJECTORY_FIELDS]
+
+
 class Views(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in VIEW_FIELDS]
 
@@ -125,6 +134,9 @@ FUNCTIONS = {
     "ranenv_selftest_ddiv": (C.c_int, [_P, _P, _P, _P, _I64, _P]),
     "ranenv_set_policy_network": (C.c_int, [_P, C.POINTER(Mlp), C.POINTER(Mlp), _I32, C.c_uint64, _P]),
     "ranenv_get_policy_actions": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "ranenv_set_value_network": (C.c_int, [_P, C.POINTER(Mlp), C.POINTER(Mlp), _P]),
+    "ranenv_collect": (C.c_int, [_P, _I32, C.POINTER(Trajectory), _F64, _F64] + [_P] * 5),
+    "ranenv_gae": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _F64, _F64, _P, _P, _P]),
 }
 EXPORTS = tuple(FUNCTIONS)
 

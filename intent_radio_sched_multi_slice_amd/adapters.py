@@ -353,6 +353,98 @@ def ibsched_policy_actions(obs_inter, mask_inter, inter, obs_intra=None, mask_in
     return scores, ch
 
 
+def ibsched_policy_noise(env_ids, episode, step, S: int, seed: int):
+    """The policy's draws for [B] envs: (z float64 [B, S], the Box-Muller draw of position j; u float64 [B, S], the uniform of
+    slice s's categorical draw), from Philox words 0 / 1 and 2 at counter (env id, episode, step, POLICY_TAG + j), key = seed."""
+    col = lambda a: np.asarray(torch.as_tensor(a).cpu().numpy(), dtype=np.int64).reshape(-1, 1)  # noqa: E731
+    c3 = POLICY_TAG + np.arange(S, dtype=np.int64)[None, :]
+    d = philox4x32_10(col(env_ids), col(episode), col(step), c3, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    u1 = (d[0].astype(np.float64) + 1.0) * 2.0 ** -32
+    u2 = d[1].astype(np.float64) * 2.0 ** -32
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2), d[2].astype(np.float64) * 2.0 ** -32
+
+
+HALF_LN_2PI = 0.9189385332046727      # 0.5 ln(2 pi)
+LN_1E9 = 20.72326583694641            # ln(1e9)
+
+
+def ibsched_policy_logp(inter_out, mask_inter, z=None, logits=None, choice=None):
+    """The log-probabilities ``collect()`` records, restated in numpy float64 (include/ranenv.h has the same rules).
+
+    ``inter_out`` float32 [B, 2S] = the inter net's (mean | log_std), ``mask_inter`` [B, S], ``z`` [B, S] the draws the actions
+    used (None = the mode: z = 0):  sum over the active sorted positions j, ascending, of ((-0.5 z_j) z_j - log_std_j) - 0.5 ln 2 pi,
+    then + n_masked (ln 1e9 - 0.5 ln 2 pi) -- TorchDiagGaussian.logp of agents/masked_action_distribution.py:30-36,53-54 at the
+    action mean + exp(log_std) z (masked: Normal(-1, 1e-9) at exactly -1).
+    ``logits`` float32 [B, S, 3] with ``choice`` [B, S]: (l_c - max l) - ln(sum_i exp(l_i - max l)).
+    Returns (logp_inter float32 [B], logp_intra float32 [B, S] or None) as numpy arrays (float64 rounded once)."""
+    as_np = lambda a, dt: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)  # noqa: E731
+    out = as_np(inter_out, np.float64)
+    S = out.shape[1] // 2
+    ls = out[:, S:]
+    active = sorted_action_mask(torch.as_tensor(as_np(mask_inter, np.int64))).numpy() != 0
+    zz = np.zeros_like(ls) if z is None else as_np(z, np.float64)
+    lp = np.zeros(out.shape[0], dtype=np.float64)
+    for j in range(S):                                          # ascending positions, as the kernel sums them
+        lp = lp + np.where(active[:, j], ((-0.5 * zz[:, j]) * zz[:, j] - ls[:, j]) - HALF_LN_2PI, 0.0)
+    lp = lp + (S - active.sum(axis=1)).astype(np.float64) * (LN_1E9 - HALF_LN_2PI)
+    lp_intra = None
+    if logits is not None:
+        lg = as_np(logits, np.float64)
+        mx = lg.max(axis=-1)
+        tot = (np.exp(lg[..., 0] - mx) + np.exp(lg[..., 1] - mx)) + np.exp(lg[..., 2] - mx)
+        lc = np.take_along_axis(lg, as_np(choice, np.int64)[..., None], -1)[..., 0]
+        lp_intra = ((lc - mx) - np.log(tot)).astype(np.float32)
+    return lp.astype(np.float32), lp_intra
+
+
+def gae(reward, vf, done, gamma: float = 0.99, lam: float = 0.95):
+    """Generalised advantage estimation as the device computes it (ranenv_collect / ranenv_gae), in numpy float64 with the same
+    operations in the same order: ``reward`` [T, B, C], ``vf`` [T + 1, B, C] (slot T = bootstrap), ``done`` [T, B] ->
+    (adv, vtarg) float32 [T, B, C].  ``done`` is terminal as in the reference (simu.py:559-564): nothing is carried across it."""
+    as_np = lambda a, dt: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)  # noqa: E731
+    r, v, d = as_np(reward, np.float64), as_np(vf, np.float64), as_np(done, np.uint8)
+    T = r.shape[0]
+    adv, vtarg = np.empty(r.shape, dtype=np.float32), np.empty(r.shape, dtype=np.float32)
+    a_next = np.zeros(r.shape[1:], dtype=np.float64)
+    gamma, gl = float(gamma), float(gamma) * float(lam)
+    for t in range(T - 1, -1, -1):
+        nd = np.where(d[t] != 0, 0.0, 1.0)[:, None]
+        delta = (r[t] + (gamma * v[t + 1]) * nd) - v[t]
+        a = delta + (gl * nd) * a_next
+        adv[t] = a.astype(np.float32)
+        vtarg[t] = (a + v[t]).astype(np.float32)
+        a_next = a
+    return adv, vtarg
+
+
+def rllib_fcnet_value_layers(state_dict, prefix: str = "internal_model."):
+    """The critic of an RLlib ``FullyConnectedNetwork`` as (W, b) layers from a torch state dict: with a separate value branch
+    (``vf_share_layers`` off) ``{prefix}_value_branch_separate.{i}._model.0.{weight,bias}`` then
+    ``{prefix}_value_branch._model.0.{weight,bias}``; with shared layers the actor's ``{prefix}_hidden_layers.{i}...`` then
+    ``_value_branch``.  Strict like ``rllib_fcnet_layers``: any other key under ``prefix`` raises ValueError (``_logits`` belongs
+    to the actor and is skipped), as do a missing head or incomplete layers.  The key names rest on RLlib's source as
+    ``rllib_fcnet_layers`` assumes it; no real checkpoint has been read."""
+    sep, hidden, head = {}, {}, {}
+    for key, val in state_dict.items():
+        if not key.startswith(prefix):
+            continue
+        parts = key[len(prefix):].split(".")
+        if len(parts) == 5 and parts[0] in ("_hidden_layers", "_value_branch_separate") and parts[1].isdigit() \
+                and parts[2:4] == ["_model", "0"] and parts[4] in ("weight", "bias"):
+            (hidden if parts[0] == "_hidden_layers" else sep).setdefault(int(parts[1]), {})[parts[4]] = torch.as_tensor(val)
+        elif len(parts) == 4 and parts[0] in ("_logits", "_value_branch") and parts[1:3] == ["_model", "0"] and parts[3] in ("weight", "bias"):
+            if parts[0] == "_value_branch":
+                head[parts[3]] = torch.as_tensor(val)
+        else:
+            raise ValueError(f"not a FullyConnectedNetwork key: {key!r}")
+    body = sep if sep else hidden
+    if not body or set(head) != {"weight", "bias"}:
+        raise ValueError(f"no FullyConnectedNetwork value branch under {prefix!r}: layers {sorted(body)}, head {sorted(head)}")
+    if sorted(body) != list(range(len(body))) or any(set(v) != {"weight", "bias"} for v in body.values()):
+        raise ValueError(f"value layers under {prefix!r} are incomplete: {sorted(body)}")
+    return [(body[i]["weight"], body[i]["bias"]) for i in range(len(body))] + [(head["weight"], head["bias"])]
+
+
 def rllib_fcnet_layers(state_dict, prefix: str = "internal_model."):
     """The (W, b) layers of an RLlib ``FullyConnectedNetwork`` policy head from a torch state dict: keys
     ``{prefix}_hidden_layers.{i}._model.0.{weight,bias}`` then ``{prefix}_logits._model.0.{weight,bias}`` (the value branch,

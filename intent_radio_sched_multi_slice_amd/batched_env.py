@@ -364,6 +364,90 @@ class BatchedRanEnv:
         self._policy_views = None
         self.set_policy(POLICY_NETWORK, self.fixed_intra if fixed_intra is None else fixed_intra)
 
+    def _mlp_struct(self, layers, act: str, layout: int, keep: list):
+        m = _lib.Mlp()
+        m.n_hidden, m.activation, m.input_layout = len(layers) - 1, NET_ACTIVATIONS[act], layout
+        m.dims[0] = layers[0][0].shape[1]
+        for i, (w, b) in enumerate(layers):
+            w, b = w.to(self.device).contiguous(), b.to(self.device).contiguous()
+            keep += [w, b]
+            m.dims[i + 1] = w.shape[0]
+            m.weight[i], m.bias[i] = w.data_ptr(), b.data_ptr()
+        return m
+
+    def set_value_network(self, inter, intra=None, activation: Optional[str] = None):
+        """Bind the critics that ``collect()`` evaluates beside the actors (ranenv_set_value_network): ``inter`` maps the
+        inter-slice observation [10*S] to one value, ``intra`` (None = no intra critic: those columns of ``vf`` are 0) the
+        intra actor's input row -- the layout given to ``set_policy_network`` -- to one value per (env, slice).  Nets as for
+        ``policy_net_layers``.  Bind the actors first when there is an intra critic; re-binding either pair leaves the other."""
+        keep: list = []
+        layers, act = policy_net_layers(inter, activation, 10 * self.S, 1)
+        structs = [self._mlp_struct(layers, act, NET_IN_OBS, keep)]
+        if intra is not None:
+            layers, act = policy_net_layers(intra, activation, None, 1)
+            layout = NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS
+            structs.append(self._mlp_struct(layers, act, layout, keep))
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_set_value_network(self._h, C.byref(structs[0]), C.byref(structs[1]) if intra is not None else None,
+                                                           self._stream()), "ranenv_set_value_network")
+        self._keep["value_net"] = keep         # (the library copies on the current stream; keep the sources until it has)
+
+    TRAJECTORY_SHAPES = {      # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S, Us, W)
+        "obs_inter": (torch.float32, 0, lambda B, S, Us, W: (B, 10 * S)), "obs_intra": (torch.float32, 0, lambda B, S, Us, W: (B, S, W)),
+        "mask_inter": (torch.int8, 0, lambda B, S, Us, W: (B, S)), "mask_intra": (torch.int8, 0, lambda B, S, Us, W: (B, S, Us)),
+        "action_inter": (torch.float64, 0, lambda B, S, Us, W: (B, S)), "action_intra": (torch.uint8, 0, lambda B, S, Us, W: (B, S)),
+        "logp": (torch.float32, 0, lambda B, S, Us, W: (B, S + 1)), "vf": (torch.float32, 1, lambda B, S, Us, W: (B, S + 1)),
+        "reward": (torch.float64, 0, lambda B, S, Us, W: (B, S + 1)), "done": (torch.uint8, 0, lambda B, S, Us, W: (B,)),
+        "adv": (torch.float32, 0, lambda B, S, Us, W: (B, S + 1)), "vtarg": (torch.float32, 0, lambda B, S, Us, W: (B, S + 1)),
+    }
+
+    def collect(self, n_steps: int, gamma: float = 0.99, lam: float = 0.95, record=_lib.TRAJECTORY_FIELDS) -> Dict[str, torch.Tensor]:
+        """``rollout(n_steps)`` under the policy nets that leaves a PPO batch on the device (ranenv_collect, include/ranenv.h):
+        a dict of ``[n_steps, B, ...]`` tensors named as ranenv_trajectory's fields (``vf`` has ``n_steps + 1`` slots, the last
+        one the bootstrap value), restricted to ``record``.  ``adv`` / ``vtarg`` are GAE(``gamma``, ``lam``) of the recorded
+        ``reward`` / ``vf`` / ``done``.  Needs ``set_policy_network`` and ``set_value_network``.  The tensors are allocated once
+        per (n_steps, record) and REUSED: the next ``collect`` of that shape overwrites them.  ``obs_intra`` / ``mask_intra`` /
+        ``action_intra`` are only written with an intra actor bound.  The env's state, ``env.reward`` / ``env.done`` / the
+        observation buffers and ``policy_actions()`` afterwards are those of ``rollout(n_steps)``."""
+        if self._recorder is not None:
+            raise RanEnvError("collect() does not return between TTIs: the recorder needs step()")
+        n_steps = int(n_steps)
+        traj = _lib.Trajectory()
+        out: Dict[str, torch.Tensor] = {}
+        if n_steps >= 1:
+            unknown = set(record) - set(_lib.TRAJECTORY_FIELDS)
+            if unknown:
+                raise ValueError(f"unknown trajectory fields {sorted(unknown)}")
+            key = (n_steps, tuple(f for f in _lib.TRAJECTORY_FIELDS if f in set(record)))
+            cache = self._keep.setdefault("trajectories", {})
+            if key not in cache:
+                cache[key] = {f: torch.zeros((n_steps + self.TRAJECTORY_SHAPES[f][1],) + self.TRAJECTORY_SHAPES[f][2](self.B, self.S, self.Us, self.W),
+                                             dtype=self.TRAJECTORY_SHAPES[f][0], device=self.device) for f in key[1]}
+            out = cache[key]
+            for f, t in out.items():
+                setattr(traj, f, t.data_ptr())
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_collect(self._h, n_steps, C.byref(traj), float(gamma), float(lam), *self._p_out, self._stream()),
+                        "ranenv_collect")
+        return out
+
+    def gae(self, reward: torch.Tensor, vf: torch.Tensor, done: torch.Tensor, gamma: float = 0.99, lam: float = 0.95,
+            adv: Optional[torch.Tensor] = None, vtarg: Optional[torch.Tensor] = None):
+        """The GAE pass alone (ranenv_gae): ``reward`` float64 [T, B, C], ``vf`` float32 [T + 1, B, C], ``done`` uint8 [T, B] on the
+        device -> (``adv``, ``vtarg``) float32 [T, B, C], written into the given tensors or new ones."""
+        T, B, Cn = reward.shape
+        if B != self.B or tuple(vf.shape) != (T + 1, B, Cn) or tuple(done.shape) != (T, B):
+            raise RanEnvError(f"gae: reward {tuple(reward.shape)}, vf {tuple(vf.shape)}, done {tuple(done.shape)} do not fit [T, {self.B}, C]")
+        reward = self._dev(reward, torch.float64, (T, B, Cn), "reward")
+        vf = self._dev(vf, torch.float32, (T + 1, B, Cn), "vf")
+        done = self._dev(done, torch.uint8, (T, B), "done")
+        adv = torch.empty((T, B, Cn), dtype=torch.float32, device=self.device) if adv is None else self._dev(adv, torch.float32, (T, B, Cn), "adv")
+        vtarg = torch.empty((T, B, Cn), dtype=torch.float32, device=self.device) if vtarg is None else self._dev(vtarg, torch.float32, (T, B, Cn), "vtarg")
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_gae(self._h, T, Cn, _ptr(reward), _ptr(vf), _ptr(done), float(gamma), float(lam), _ptr(adv), _ptr(vtarg),
+                                             self._stream()), "ranenv_gae")
+        return adv, vtarg
+
     def policy_actions(self) -> Dict[str, Optional[torch.Tensor]]:
         """Zero-copy views of the last actions of the policy nets: ``scores`` float64 [B, S] (what the step read, in the
         sorted order of obs_inter) and ``intra`` uint8 [B, S] (by slice; None without an intra net)."""

@@ -393,9 +393,47 @@ __global__ void __launch_bounds__(256) ranenv_ddiv_selftest_kernel(const double 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Generalised advantage estimation over a recorded trajectory (ranenv_collect / ranenv_gae; the arithmetic is spelled out in
+// include/ranenv.h).  Lane = (env, column): every [t] slice is read as contiguous lines.  The recurrence is a chain of n_steps
+// dependent float64 multiplies and adds per lane; slot t - 1's reward / value / done do not depend on it and are requested before
+// slot t's step of the chain is evaluated.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ranenv_gae_kernel(int n_steps, int B, int n_cols, const double *reward, const float *vf, const uint8_t *done,
+                                                         double gamma, double lambda, float *adv, float *vtarg)
+{
+    const long long n = (long long)B * n_cols, i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long b = i / n_cols;
+    const double gl = gamma * lambda;
+    double a_next = 0.0, v1 = (double)vf[(long long)n_steps * n + i];
+    double r = reward[(long long)(n_steps - 1) * n + i], v0 = (double)vf[(long long)(n_steps - 1) * n + i];
+    uint8_t d = done[(long long)(n_steps - 1) * B + b];
+    for (int t = n_steps - 1; t >= 0; t--) {
+        double rp = 0.0, vp = 0.0;
+        uint8_t dp = 0;
+        if (t > 0) { rp = reward[(long long)(t - 1) * n + i]; vp = (double)vf[(long long)(t - 1) * n + i]; dp = done[(long long)(t - 1) * B + b]; }
+        const double nd = d ? 0.0 : 1.0;
+        const double delta = (r + (gamma * v1) * nd) - v0;
+        const double a = delta + (gl * nd) * a_next;
+        if (adv) adv[(long long)t * n + i] = (float)a;
+        if (vtarg) vtarg[(long long)t * n + i] = (float)(a + v0);
+        a_next = a; v1 = v0;
+        r = rp; v0 = vp; d = dp;
+    }
+}
+
 }  // namespace
 
 namespace ranenv_dev {
+
+void launch_gae(hipStream_t s, int n_steps, int B, int n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,
+                double lambda, float *adv, float *vtarg)
+{
+    const long long n = (long long)B * n_cols;
+    hipLaunchKernelGGL(ranenv_gae_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_steps, B, n_cols, reward, vf, done, gamma, lambda,
+                       adv, vtarg);
+}
 
 void launch_ddiv_selftest(hipStream_t s, const double *a, const double *b, double *fast, double *ieee, long long n)
 {

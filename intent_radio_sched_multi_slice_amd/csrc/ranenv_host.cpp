@@ -90,6 +90,11 @@ struct ranenv {
     int net_stochastic = 0; unsigned long long net_seed = 0;
     float *d_net_w = nullptr; long long net_cap = 0;      // floats
     double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
+    // critics (ranenv_set_value_network), packed like the actors in a buffer of their own
+    PolicyNet val_inter{}, val_intra{};
+    bool val_on = false, val_has_intra = false;
+    float *d_val_w = nullptr; long long val_cap = 0;
+    int collect_split = -1;        // option "collect_split": the critic of ranenv_collect in a launch of its own (1), fused behind the actor (0), -1 = by weight size
     // options (the table `options` below, include/ranenv.h "Options")
     bool compact_enabled = true;                // option "compact"
     int fuse = 0;                  // TTIs per launch inside ranenv_rollout: 0 = chosen per rollout, n = at most n (1 = off)
@@ -665,6 +670,7 @@ const Option options[] = {
      [](H h) -> long long { return h->mix; }},
     // test hook, see persist_check_errors
     {"persist_inject_abort", false, [](H h, long long v) { h->persist_inject = v != 0 ? 1 : 0; return 0; }, nullptr},
+    {"collect_split", true, [](H h, long long v) { h->collect_split = v < 0 ? -1 : (v != 0 ? 1 : 0); return 0; }, [](H h) -> long long { return h->collect_split; }},
     {"autoreset_shortcut", true, [](H h, long long v) { h->autoreset_shortcut = v != 0 ? 1 : 0; return 0; },
      [](H h) -> long long { return h->autoreset_shortcut; }},
 };
@@ -1074,10 +1080,10 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra)
 
 // ---- policy networks (RANENV_POLICY_NETWORK) --------------------------------------------------------------------------------
 // Validate one ranenv_mlp against the handle's sizes and lay it out in the packed buffer from float `off` on (widths padded to 32).
-static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNet &net, long long &off)
+static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNet &net, long long &off, bool critic = false)
 {
     const int S = h->cfg.n_slices, Us = h->cfg.max_ues_slice;
-    const char *who = intra ? "intra" : "inter";
+    const char *who = critic ? (intra ? "intra value" : "inter value") : (intra ? "intra" : "inter");
     if (m->n_hidden < 1 || m->n_hidden > NET_MAX_LAYERS - 1) return fail(h, RANENV_E_INVALID, "%s net: %d hidden layers (1..%d)", who, m->n_hidden, NET_MAX_LAYERS - 1);
     if (m->activation != RANENV_ACT_TANH && m->activation != RANENV_ACT_RELU) return fail(h, RANENV_E_INVALID, "%s net: unknown activation %d", who, m->activation);
     int in_dim = 10 * S;
@@ -1087,7 +1093,7 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNe
         else if (m->input_layout == RANENV_NET_IN_MASK_OBS) in_dim = 3 * Us + 9;
         else return fail(h, RANENV_E_INVALID, "intra net: unknown input layout %d", m->input_layout);
     }
-    const int out_dim = intra ? 3 : 2 * S, L = m->n_hidden + 1;
+    const int out_dim = critic ? 1 : (intra ? 3 : 2 * S), L = m->n_hidden + 1;
     if (m->dims[0] != in_dim) return fail(h, RANENV_E_INVALID, "%s net: input width %d, the observation has %d", who, m->dims[0], in_dim);
     for (int i = 1; i < L; i++)
         if (m->dims[i] < 1 || m->dims[i] > NET_MAX_WIDTH) return fail(h, RANENV_E_INVALID, "%s net: hidden width %d (1..%d)", who, m->dims[i], NET_MAX_WIDTH);
@@ -1104,13 +1110,14 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNe
     return RANENV_OK;
 }
 
-static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, hipStream_t s)
+static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, hipStream_t s, float *dst = nullptr)
 {
+    if (!dst) dst = h->d_net_w;
     for (int l = 0; l < net.n_layers; l++) {
         const int K = m->dims[l], N = m->dims[l + 1];
-        HIP_TRY(h, hipMemcpy2DAsync(h->d_net_w + net.w_off[l], sizeof(float) * net.kp[l], m->weight[l], sizeof(float) * K, sizeof(float) * K, N,
+        HIP_TRY(h, hipMemcpy2DAsync(dst + net.w_off[l], sizeof(float) * net.kp[l], m->weight[l], sizeof(float) * K, sizeof(float) * K, N,
                                     hipMemcpyDeviceToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(h->d_net_w + net.b_off[l], m->bias[l], sizeof(float) * N, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(dst + net.b_off[l], m->bias[l], sizeof(float) * N, hipMemcpyDeviceToDevice, s));
     }
     return RANENV_OK;
 }
@@ -1128,7 +1135,7 @@ static int net_use(ranenv_handle h, KP &kp)
     return 1;
 }
 
-static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
+static PolicyIO net_io(ranenv_handle h, const KP &kp)
 {
     PolicyIO io{};
     io.B = h->cfg.batch; io.S = h->cfg.n_slices; io.Us = h->cfg.max_ues_slice; io.W = 2 * io.Us + 9;
@@ -1137,7 +1144,12 @@ static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipSt
     io.mask_inter = ST_mask_inter(h->kp); io.mask_intra = ST_mask_intra(h->kp);
     io.episode_no = ST_episode_no(h->kp); io.step_no = ST_step_no(h->kp);
     io.scores = h->d_net_scores; io.intra = h->d_net_intra;
-    return launch_policy(s, h->net_inter, h->net_has_intra ? &h->net_intra : nullptr, io, e0, n);
+    return io;
+}
+
+static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
+{
+    return launch_policy(s, h->net_inter, h->net_has_intra ? &h->net_intra : nullptr, net_io(h, kp), e0, n);
 }
 
 int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed, void *stream_)
@@ -1179,6 +1191,36 @@ int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **de
     if (!h || !dev_scores || !dev_intra) return fail(h, RANENV_E_INVALID, "null argument");
     if (!h->net_on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
     *dev_scores = h->d_net_scores; *dev_intra = h->net_has_intra ? h->d_net_intra : nullptr;
+    return RANENV_OK;
+}
+
+int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice value net is required (intra may be NULL)");
+    if (intra && !(h->net_on && h->net_has_intra)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
+    if (intra && intra->input_layout != h->net_intra.layout)
+        return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, h->net_intra.layout);
+    PolicyNet ni{}, na{};
+    long long off = 0;
+    int rc = net_layout(h, inter, false, ni, off, true);
+    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, true, na, off, true);
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream_;
+    if (off > h->val_cap) {
+        // (the launches of earlier calls may still read the old buffer: it stays allocated until ranenv_destroy)
+        rc = dev_alloc(h, &h->d_val_w, (size_t)off);
+        if (rc != RANENV_OK) return rc;
+        h->val_cap = off;
+    } else {
+        HIP_TRY(h, hipMemsetAsync(h->d_val_w, 0, sizeof(float) * (size_t)off, s));
+    }
+    ni.w = h->d_val_w; na.w = h->d_val_w;
+    rc = net_copy(h, inter, ni, s, h->d_val_w);
+    if (rc == RANENV_OK && intra) rc = net_copy(h, intra, na, s, h->d_val_w);
+    if (rc != RANENV_OK) return rc;
+    h->val_inter = ni; h->val_intra = na; h->val_has_intra = intra != nullptr; h->val_on = true;
     return RANENV_OK;
 }
 
@@ -1479,6 +1521,7 @@ struct Rollout {
     std::vector<int32_t> steps;
     AdvanceArgs adv{};
     KP kpr{};
+    const ranenv_trajectory *rec = nullptr;      // ranenv_collect: the record (null: a plain rollout)
 };
 
 // TTIs from now until the first episode of envs [lo, hi) ends, that TTI included, between 1 and n.  `n_ends`: at how many different
@@ -1497,7 +1540,7 @@ static int ttis_to_end(ranenv_handle h, const Rollout &r, int lo, int hi, int n,
 
 // n_tti TTIs of envs [e0, e0 + n) were enqueued on `s`: the host's step counters advance by n_tti, and the envs whose episode
 // ended restart, on the host and -- advance kernel, reset -- on `s`
-static hipError_t follow_episode_ends(ranenv_handle h, Rollout &r, int e0, int n, int n_tti, hipStream_t s)
+static hipError_t follow_episode_ends(ranenv_handle h, Rollout &r, int e0, int n, int n_tti, hipStream_t s, const uint8_t *done = nullptr)
 {
     if (!r.follow) return hipSuccess;
     bool any = false;
@@ -1507,6 +1550,7 @@ static hipError_t follow_episode_ends(ranenv_handle h, Rollout &r, int e0, int n
     }
     if (!any) return hipSuccess;
     AdvanceArgs a = r.adv; a.e0 = e0;
+    if (done) a.done = done;                       // (ranenv_collect: the step wrote the flags into the record's slot)
     h->pclass_dirty = true;                        // the restarted envs' scenarios
     launch_advance(s, (unsigned)n, a);
     return launch_range<MODE_RESET>(h, r.kpr, e0, n, s);
@@ -1530,6 +1574,52 @@ static int rollout_persistent(ranenv_handle h, Rollout &r, hipStream_t stream)
         if (re != hipSuccess) return fail(h, RANENV_E_HIP, "persistent rollout, reset launch: %s", hipGetErrorString(re));
     }
     return RANENV_OK;
+}
+
+constexpr long long COLLECT_FUSED_MAX_BYTES = 3ll << 20;      // actor + critic weights that share an XCD's 4 MB of L2 with the activations' traffic
+
+// ranenv_collect: TTI `t` of a partition's own count for envs [e0, e0 + n) on `s`.  The recording policy launches (actors, record,
+// critics) write slot t; the step writes its reward row and done flag straight into slot t (the kernels index them by env; the
+// reset behind an episode end writes neither, reset_behind), and the advance kernel reads that slot's flags.  Behind the call's
+// last TTI -- and behind its reset, if any -- the critics run once more on the observation as it stands: vf[T].
+static hipError_t collect_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
+{
+    const ranenv_trajectory &tr = *r.rec;
+    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, Us = (size_t)h->cfg.max_ues_slice, W = 2 * Us + 9, ts = (size_t)t;
+    const bool ia = h->net_has_intra, vc = tr.vf != nullptr, ic = vc && h->val_has_intra;
+    PolicyRec rec{};
+    rec.obs_inter = tr.obs_inter ? tr.obs_inter + ts * B * 10 * S : nullptr;
+    rec.mask_inter = tr.mask_inter ? tr.mask_inter + ts * B * S : nullptr;
+    rec.action_inter = tr.action_inter ? tr.action_inter + ts * B * S : nullptr;
+    if (ia) {
+        rec.obs_intra = tr.obs_intra ? tr.obs_intra + ts * B * S * W : nullptr;
+        rec.mask_intra = tr.mask_intra ? tr.mask_intra + ts * B * S * Us : nullptr;
+        rec.action_intra = tr.action_intra ? tr.action_intra + ts * B * S : nullptr;
+    }
+    rec.logp = tr.logp ? tr.logp + ts * B * (S + 1) : nullptr;
+    rec.vf = vc ? tr.vf + ts * B * (S + 1) : nullptr;
+    rec.intra_actor = ia ? 1 : 0; rec.intra_critic = ic ? 1 : 0;
+    if (tr.reward) kpk.reward = tr.reward + ts * B * (S + 1);
+    if (tr.done) kpk.done = tr.done + ts * B;
+    const PolicyIO io = net_io(h, kpk);
+    const PolicyNet *intra = ia ? &h->net_intra : nullptr, *vinter = vc ? &h->val_inter : nullptr, *vintra = ic ? &h->val_intra : nullptr;
+    // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
+    // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").
+    auto split = [&](const PolicyNet &a, const PolicyNet *v) {
+        if (!v) return 0;
+        if (h->collect_split >= 0) return h->collect_split;
+        auto floats = [](const PolicyNet &x) { return x.b_off[x.n_layers - 1] + x.np[x.n_layers - 1] - x.w_off[0]; };
+        return (floats(a) + floats(*v)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
+    };
+    rec.split = split(h->net_inter, vinter) | (ia ? split(h->net_intra, vintra) << 1 : 0);
+    hipError_t le = launch_policy_collect(s, h->net_inter, intra, vinter, vintra, io, rec, e0, n);
+    if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
+    if (le == hipSuccess) le = follow_episode_ends(h, r, e0, n, 1, s, kpk.done);
+    if (le != hipSuccess || t + 1 < r.n_steps || !vc) return le;
+    PolicyRec last{};
+    last.vf = tr.vf + (ts + 1) * B * (S + 1);
+    last.intra_critic = rec.intra_critic; last.critic_only = 1;
+    return launch_policy_collect(s, h->net_inter, intra, vinter, vintra, io, last, e0, n);
 }
 
 // Every partition walks through the TTIs in launches of its own, on its own stream
@@ -1573,6 +1663,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
             KP kpk = r.kp;
             kpk.n_tti = n_tti;
             h->last_rollout_launches++;
+            if (r.rec) return collect_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
             hipError_t le = r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
             if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
             if (le != hipSuccess) return le;
@@ -1584,7 +1675,9 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
     return RANENV_OK;
 }
 
-int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream_)
+// ranenv_rollout, and with `traj` ranenv_collect (gamma / lambda: its GAE pass)
+static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream_,
+                       const ranenv_trajectory *traj, double gamma, double lambda)
 {
     int rc = check_ready(h, nullptr, nullptr, true);
     if (rc != RANENV_OK) return rc;
@@ -1603,6 +1696,7 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
     // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
     r.net = net_use(h, r.kp);
     if (r.net < 0) return r.net;
+    r.rec = traj;
     rc = compact_for(h, r.kp, stream, &r.kp.compact);
     if (rc != RANENV_OK) return rc;
     if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_plan)
@@ -1634,8 +1728,54 @@ int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *ob
     }
     rc = persist_ok ? rollout_persistent(h, r, stream) : rollout_chunks(h, r, stream);
     if (rc != RANENV_OK) return rc;
+    if (traj) {
+        // (the partitions have joined the caller's stream)  The caller's reward / done hold the last TTI's values, as after a rollout
+        const size_t B = (size_t)h->cfg.batch, C = (size_t)h->cfg.n_slices + 1, last = (size_t)n_steps - 1;
+        if (traj->reward && reward)
+            HIP_TRY(h, hipMemcpyAsync(reward, traj->reward + last * B * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
+        if (traj->done && done) HIP_TRY(h, hipMemcpyAsync(done, traj->done + last * B, B, hipMemcpyDeviceToDevice, stream));
+        if (traj->adv || traj->vtarg) {
+            launch_gae(stream, n_steps, h->cfg.batch, (int)C, traj->reward, traj->vf, traj->done, gamma, lambda, traj->adv, traj->vtarg);
+            HIP_TRY(h, hipGetLastError());
+        }
+    }
     if (r.follow) { h->sh_steps = r.steps; h->sh_valid = true; h->last_done = done; }      // (read from the device above, followed exactly since)
     else shadow_steps_add(h, 0, h->cfg.batch, n_steps, done, stream);
+    return RANENV_OK;
+}
+
+int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream)
+{
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, nullptr, 0.0, 0.0);
+}
+
+static_assert(sizeof(ranenv_trajectory) == RANENV_TRAJECTORY_BYTES, "ranenv_trajectory: 12 device pointers");
+
+int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, double gamma, double lambda, float *obs_inter,
+                   float *obs_intra, double *reward, uint8_t *done, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!traj) return fail(h, RANENV_E_INVALID, "null trajectory");
+    if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
+    if ((traj->adv || traj->vtarg) && !(traj->reward && traj->vf && traj->done))
+        return fail(h, RANENV_E_INVALID, "adv / vtarg need the record's reward, vf and done");
+    if (h->kp.policy != RANENV_POLICY_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect needs policy NETWORK (ranenv_set_policy)");
+    if (!h->net_on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!h->val_on) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
+    if (h->val_has_intra && !(h->net_has_intra && h->net_intra.layout == h->val_intra.layout))
+        return fail(h, RANENV_E_STATE, "the intra value net was bound for another intra policy net (bind it again, ranenv_set_value_network)");
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, traj, gamma, lambda);
+}
+
+int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,
+               double lambda, float *adv, float *vtarg, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n_steps < 1 || n_cols < 1) return fail(h, RANENV_E_INVALID, "n_steps and n_cols must be >= 1");
+    if (!reward || !vf || !done) return fail(h, RANENV_E_INVALID, "GAE reads reward, vf and done");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    launch_gae((hipStream_t)stream, n_steps, h->cfg.batch, n_cols, reward, vf, done, gamma, lambda, adv, vtarg);
+    HIP_TRY(h, hipGetLastError());
     return RANENV_OK;
 }
 

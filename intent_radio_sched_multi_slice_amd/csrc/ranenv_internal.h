@@ -187,6 +187,20 @@ struct PolicyIO {
 };
 // Enqueue the inter net (and the intra net when `intra` is non-null) for envs [e0, e0 + n_envs).
 hipError_t launch_policy(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &, int e0, int n_envs);
+// ranenv_collect: what the policy launch of one TTI records, every pointer already at that TTI's slot of the caller's ranenv_trajectory
+// (null = not recorded), and the critics it runs behind the actors for the same rows.
+struct PolicyRec {
+    float *obs_inter, *obs_intra; int8_t *mask_inter, *mask_intra;
+    double *action_inter; uint8_t *action_intra;
+    float *logp, *vf;                     // [B][S + 1] of the slot: column 0 by the inter launch, column s + 1 by the intra launch
+    int intra_actor, intra_critic;        // 0: the inter launch writes zeros into columns 1..S of logp / vf
+    int critic_only;                      // the pass behind the last TTI: no actors, no record, vf of the observation as it stands
+    int split;                            // host side only: bit 0 / 1 = the inter / intra critic runs as a launch of its own behind the actor's
+};
+// The recording launches of one TTI: actor + critic stack per agent kind in one launch each (`vinter` / `vintra` null = no critic of that
+// kind; `intra` null = no intra actor, then `vintra` is null too).  critic_only: the critics alone.
+hipError_t launch_policy_collect(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyNet *vinter, const PolicyNet *vintra,
+                                 const PolicyIO &, const PolicyRec &, int e0, int n_envs);
 size_t policy_lds_bytes(const PolicyNet &);
 
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
@@ -250,6 +264,8 @@ void launch_se_from_power(hipStream_t, unsigned blocks, const double *power, flo
 void launch_ddiv_selftest(hipStream_t, const double *a, const double *b, double *fast, double *ieee, long long n);
 void launch_head(hipStream_t, dim3 grid, dim3 block, const KP &);
 void launch_advance(hipStream_t, unsigned n_envs, const AdvanceArgs &);
+void launch_gae(hipStream_t, int n_steps, int B, int n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,
+                double lambda, float *adv, float *vtarg);
 void launch_idle_traffic(hipStream_t, unsigned n_eps, const ranenv_episode *eps, const int32_t *pool, int U, const int32_t *lane_slice,
                          const int32_t *lane_ue, int *violations);
 

@@ -28,39 +28,40 @@ __host__ __device__ inline int net_ld_max(const PolicyNet &net)
     return m;
 }
 
-// kind 0: inter net, n_rows = envs; kind 1: intra net, n_rows = envs x S (row g of the launch = env e0 + g / S, slice g % S)
-__global__ void __launch_bounds__(256) ranenv_policy_kernel(PolicyNet net, PolicyIO io, int kind, int e0, int n_rows)
+// Observation rows of `net`'s input -> LDS (zeros beyond the input and beyond the launch's rows).  REC: the rows are written to the
+// record's slot on the way (the observation the TTI's action is computed from).
+template <bool REC>
+__device__ __forceinline__ void net_load_rows(const PolicyNet &net, const PolicyIO &io, const PolicyRec &rec, int kind, int e0, int row0, int n_rows,
+                                              float *cur, int tid)
 {
-    extern __shared__ float lds[];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = lane >> 4, c = lane & 15;
-    const int row0 = (int)blockIdx.x * NET_ROWS;
     const int S = io.S;
-    float *cur = lds, *nxt = lds + NET_ROWS * net_ld_max(net);
-
-    // ---- observation rows -> LDS (zeros beyond the input and beyond the launch's rows) ----------------------------------
-    {
-        const int K0 = net.kp[0], ld0 = net_ld(K0);
-        for (int i = tid; i < NET_ROWS * K0; i += 256) {
-            const int r = i / K0, k = i - r * K0, g = row0 + r;
-            float v = 0.0f;
-            if (g < n_rows && k < net.in_dim) {
-                if (kind == 0) {
-                    v = io.obs_inter[(size_t)(e0 + g) * (size_t)(10 * S) + k];
+    const int K0 = net.kp[0], ld0 = net_ld(K0);
+    for (int i = tid; i < NET_ROWS * K0; i += 256) {
+        const int r = i / K0, k = i - r * K0, g = row0 + r;
+        float v = 0.0f;
+        if (g < n_rows && k < net.in_dim) {
+            if (kind == 0) {
+                v = io.obs_inter[(size_t)(e0 + g) * (size_t)(10 * S) + k];
+                if (REC && rec.obs_inter) rec.obs_inter[(size_t)(e0 + g) * (size_t)(10 * S) + k] = v;
+            } else {
+                const size_t es = (size_t)e0 * S + g;
+                const int ko = net.layout == RANENV_NET_IN_MASK_OBS ? k - io.Us : k;
+                if (ko < 0) {
+                    v = (float)io.mask_intra[es * io.Us + k];
                 } else {
-                    const size_t es = (size_t)e0 * S + g;
-                    if (net.layout == RANENV_NET_IN_MASK_OBS)
-                        v = k < io.Us ? (float)io.mask_intra[es * io.Us + k] : io.obs_intra[es * io.W + (k - io.Us)];
-                    else
-                        v = io.obs_intra[es * io.W + k];
+                    v = io.obs_intra[es * io.W + ko];
+                    if (REC && rec.obs_intra) rec.obs_intra[es * io.W + ko] = v;
                 }
             }
-            cur[r * ld0 + k] = v;
         }
+        cur[r * ld0 + k] = v;
     }
-    __syncthreads();
+}
 
-    // ---- layers ---------------------------------------------------------------------------------------------------------
+// The layers of `net` on the 32 rows in `cur`; on return `cur` holds the output layer's rows (stride net_ld(np[last])).
+__device__ __forceinline__ void net_layers(const PolicyNet &net, float *&cur, float *&nxt, int lane, int wave)
+{
+    const int q = lane >> 4, c = lane & 15;
     for (int l = 0; l < net.n_layers; l++) {
         const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N);
         const bool last = l == net.n_layers - 1;
@@ -108,18 +109,54 @@ __global__ void __launch_bounds__(256) ranenv_policy_kernel(PolicyNet net, Polic
         __syncthreads();
         float *t = cur; cur = nxt; nxt = t;
     }
+}
+
+constexpr double HALF_LN_2PI = 0.9189385332046727;      // 0.5 ln(2 pi)
+constexpr double LN_1E9 = 20.72326583694641;            // ln(1e9): -ln of the masked positions' std
+
+// kind 0: inter net, n_rows = envs; kind 1: intra net, n_rows = envs x S (row g of the launch = env e0 + g / S, slice g % S).
+// REC (ranenv_collect): the same actor forward and epilogue -- the actions do not differ by a bit -- which also writes the TTI's record
+// (observation and mask rows on their way into LDS; unclamped action, log-probability beside the handle's action buffers), then the
+// critic `vnet` (n_layers 0 = none) on the same 32 rows, re-read from L2, through the same two LDS buffers.
+template <bool REC>
+__device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNet &vnet, const PolicyIO &io, const PolicyRec &rec, int kind, int e0,
+                                            int n_rows, float *lds)
+{
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row0 = (int)blockIdx.x * NET_ROWS;
+    const int S = io.S;
+    int ldm = net_ld_max(net);
+    if (REC && vnet.n_layers > 0) { const int lv = net_ld_max(vnet); ldm = lv > ldm ? lv : ldm; }
+    float *cur = lds, *nxt = lds + NET_ROWS * ldm;
+
+    if (!REC || !rec.critic_only) {
+    if (REC) {      // the masks of this TTI
+        if (kind == 0 && rec.mask_inter)
+            for (int i = tid; i < NET_ROWS * S; i += 256)
+                if (row0 + i / S < n_rows) rec.mask_inter[(size_t)(e0 + row0) * S + i] = io.mask_inter[(size_t)(e0 + row0) * S + i];
+        if (kind == 1 && rec.mask_intra)
+            for (int i = tid; i < NET_ROWS * io.Us; i += 256)
+                if (row0 + i / io.Us < n_rows) {
+                    const size_t o = ((size_t)e0 * S + row0) * io.Us + i;
+                    rec.mask_intra[o] = io.mask_intra[o];
+                }
+    }
+    net_load_rows<REC>(net, io, rec, kind, e0, row0, n_rows, cur, tid);
+    __syncthreads();
+    net_layers(net, cur, nxt, lane, wave);
 
     // ---- epilogue: actions ----------------------------------------------------------------------------------------------
     const int ld = net_ld(net.np[net.n_layers - 1]);
     const unsigned k0 = (unsigned)io.seed, k1 = (unsigned)(io.seed >> 32);
     if (kind == 0) {
+        double *zrow = (double *)nxt;                  // REC: the draws z [32][S] for the rows' log-probabilities (the idle LDS buffer)
         for (int i = tid; i < NET_ROWS * S; i += 256) {
             const int r = i / S, j = i - r * S, g = row0 + r;
             if (g >= n_rows) continue;
             const int e = e0 + g;
             int n_act = 0;
             for (int s = 0; s < S; s++) n_act += io.mask_inter[(size_t)e * S + s] != 0 ? 1 : 0;
-            double score = -1.0;                       // masked position (sorted mask: the first S - n_act positions)
+            double score = -1.0, raw = -1.0, z = 0.0;  // masked position (sorted mask: the first S - n_act positions)
             if (j >= S - n_act) {
                 double m = (double)cur[r * ld + j];
                 if (io.stochastic) {
@@ -127,12 +164,37 @@ __global__ void __launch_bounds__(256) ranenv_policy_kernel(PolicyNet net, Polic
                     philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], 0x504F4C00u + (unsigned)j,
                                   k0, k1, o);
                     const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
-                    const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+                    z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
                     m = m + exp((double)cur[r * ld + S + j]) * z;
                 }
+                raw = m;
                 score = m < -1.0 ? -1.0 : (m > 1.0 ? 1.0 : m);
             }
             io.scores[(size_t)e * S + j] = score;
+            if (REC) {
+                if (rec.action_inter) rec.action_inter[(size_t)e * S + j] = raw;
+                zrow[i] = z;
+            }
+        }
+        if (REC && rec.logp) {
+            __syncthreads();
+            for (int r = tid; r < NET_ROWS; r += 256) {
+                const int g = row0 + r;
+                if (g >= n_rows) continue;
+                const int e = e0 + g;
+                int n_act = 0;
+                for (int s = 0; s < S; s++) n_act += io.mask_inter[(size_t)e * S + s] != 0 ? 1 : 0;
+                double lp = 0.0;
+                for (int j = S - n_act; j < S; j++) {
+                    const double z = zrow[r * S + j];
+                    lp += ((-0.5 * z) * z - (double)cur[r * ld + S + j]) - HALF_LN_2PI;
+                }
+                lp += (double)(S - n_act) * (LN_1E9 - HALF_LN_2PI);
+                float *out = rec.logp + (size_t)e * (S + 1);
+                out[0] = (float)lp;
+                if (!rec.intra_actor)
+                    for (int s = 0; s < S; s++) out[1 + s] = 0.0f;
+            }
         }
     } else {
         for (int r = tid; r < NET_ROWS; r += 256) {
@@ -156,8 +218,57 @@ __global__ void __launch_bounds__(256) ranenv_policy_kernel(PolicyNet net, Polic
                 ch = t < c0 ? 0 : (t < c1 ? 1 : 2);
             }
             io.intra[es] = (uint8_t)ch;
+            if (REC) {
+                if (rec.action_intra) rec.action_intra[es] = (uint8_t)ch;
+                if (rec.logp) {
+                    const double mx = fmax(fmax((double)l0, (double)l1), (double)l2);
+                    const double sum = (exp((double)l0 - mx) + exp((double)l1 - mx)) + exp((double)l2 - mx);
+                    const double lc = (double)(ch == 0 ? l0 : (ch == 1 ? l1 : l2));
+                    rec.logp[(size_t)e * (S + 1) + 1 + s] = (float)((lc - mx) - log(sum));
+                }
+            }
         }
     }
+    }
+
+    // ---- critic: the same rows through `vnet`, one value per row ------------------------------------------------------------
+    if (REC && rec.vf) {
+        if (vnet.n_layers > 0) {
+            __syncthreads();                           // (the epilogue read both buffers)
+            cur = lds; nxt = lds + NET_ROWS * ldm;
+            const PolicyRec none{};
+            net_load_rows<false>(vnet, io, none, kind, e0, row0, n_rows, cur, tid);
+            __syncthreads();
+            net_layers(vnet, cur, nxt, lane, wave);
+            const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
+            for (int r = tid; r < NET_ROWS; r += 256) {
+                const int g = row0 + r;
+                if (g >= n_rows) continue;
+                if (kind == 0) {
+                    float *out = rec.vf + (size_t)(e0 + g) * (S + 1);
+                    out[0] = cur[r * ldv];
+                    if (!rec.intra_critic)
+                        for (int s = 0; s < S; s++) out[1 + s] = 0.0f;
+                } else {
+                    const size_t es = (size_t)e0 * S + g;
+                    const size_t e = es / (size_t)S;
+                    rec.vf[e * (S + 1) + 1 + (es - e * S)] = cur[r * ldv];
+                }
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) ranenv_policy_kernel(PolicyNet net, PolicyIO io, int kind, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    policy_body<false>(net, net, io, PolicyRec{}, kind, e0, n_rows, lds);
+}
+
+__global__ void __launch_bounds__(256) ranenv_policy_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, int kind, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    policy_body<true>(net, vnet, io, rec, kind, e0, n_rows, lds);
 }
 
 }  // namespace
@@ -182,6 +293,39 @@ hipError_t launch_policy(hipStream_t s, const PolicyNet &inter, const PolicyNet 
         hipLaunchKernelGGL(ranenv_policy_kernel, dim3((unsigned)((rows + NET_ROWS - 1) / NET_ROWS)), dim3(256), policy_lds_bytes(*intra), s,
                            *intra, io, 1, e0, rows);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_collect(hipStream_t s, const PolicyNet &inter, const PolicyNet *intra, const PolicyNet *vinter, const PolicyNet *vintra,
+                                 const PolicyIO &io, const PolicyRec &rec, int e0, int n_envs)
+{
+    static std::once_flag once;
+    static hipError_t attr = hipSuccess;
+    std::call_once(once, [] {
+        attr = hipFuncSetAttribute((const void *)ranenv_policy_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
+    });
+    if (attr != hipSuccess) return attr;
+    const PolicyNet none{};               // (n_layers 0: no critic of that kind)
+    auto lds_of = [](const PolicyNet &a, const PolicyNet &v) {
+        const size_t x = policy_lds_bytes(a), y = v.n_layers > 0 ? policy_lds_bytes(v) : 0;
+        return x > y ? x : y;
+    };
+    // one kind's launch(es): actor + critic fused, or -- split -- the actor's launch, then the critic alone (the kernel's critic_only mode)
+    auto kind_launch = [&](int kind, const PolicyNet &a, const PolicyNet *vp, int rows, bool split) {
+        const dim3 grid((unsigned)((rows + NET_ROWS - 1) / NET_ROWS));
+        if (!split || rec.critic_only || !vp) {
+            const PolicyNet &v = vp ? *vp : none;
+            hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid, dim3(256), lds_of(a, v), s, a, v, io, rec, kind, e0, rows);
+            return;
+        }
+        hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid, dim3(256), lds_of(a, none), s, a, none, io, rec, kind, e0, rows);
+        PolicyRec crit{};
+        crit.vf = rec.vf; crit.intra_critic = rec.intra_critic; crit.critic_only = 1;
+        hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid, dim3(256), lds_of(a, *vp), s, a, *vp, io, crit, kind, e0, rows);
+    };
+    if (!rec.critic_only || vinter) kind_launch(0, inter, vinter, n_envs, (rec.split & 1) != 0);
+    if (intra && (!rec.critic_only || vintra)) kind_launch(1, *intra, vintra, n_envs * io.S, (rec.split & 2) != 0);
     return hipGetLastError();
 }
 

@@ -1,0 +1,200 @@
+"""The host side of PPO sample collection, without a GPU: adapters.gae against the definition it abbreviates, the RLlib critic reader,
+adapters.ibsched_policy_logp against torch.distributions, the C ABI's new exports and the rebuilt library's new kernels."""
+from __future__ import annotations
+
+import ctypes
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
+
+
+# ---- GAE ------------------------------------------------------------------------------------------------------------------------
+def _gae_by_definition(r, v, d, gamma, lam):
+    """adv_t = sum_k (gamma lambda)^k delta_{t+k}, cut behind the first done at or after t; delta_t = r_t + gamma v_{t+1} (1 - done_t) - v_t.
+    Returns (adv, sum of the absolute terms) in float64, each [T, B, C]."""
+    T = r.shape[0]
+    nd = np.where(d != 0, 0.0, 1.0)[:, :, None]
+    delta = r + gamma * v[1:] * nd - v[:-1]
+    mag = np.abs(r) + gamma * np.abs(v[1:]) * nd + np.abs(v[:-1])
+    adv, tot = np.zeros_like(r), np.zeros_like(r)
+    for t in range(T):
+        alive = np.ones(r.shape[1:], dtype=np.float64)
+        for k in range(T - t):
+            w = (gamma * lam) ** k
+            adv[t] += alive * w * delta[t + k]
+            tot[t] += alive * w * mag[t + k]
+            alive = alive * nd[t + k]
+    return adv, tot
+
+
+def _gae_case(rng, T, B, C, kind):
+    r = rng.standard_normal((T, B, C)) * rng.choice([0.1, 1.0, 10.0])
+    v = (rng.standard_normal((T + 1, B, C)) * rng.choice([0.1, 1.0, 10.0])).astype(np.float32)
+    d = np.zeros((T, B), dtype=np.uint8)
+    if kind == "random":
+        d = (rng.random((T, B)) < 0.15).astype(np.uint8)
+    elif kind == "first":
+        d[0] = 1
+    elif kind == "last":
+        d[T - 1] = 1
+    elif kind == "consecutive":
+        d[T // 2:T // 2 + 3] = 1
+        d[0, ::2] = 1
+        if T > 1:
+            d[1, ::2] = 1
+    return r, v, d
+
+
+@pytest.mark.parametrize("gamma,lam", [(0.99, 0.95), (0.6, 0.95), (0.999, 1.0), (0.99, 1.0), (0.9, 0.0)])
+@pytest.mark.parametrize("kind", ["none", "random", "first", "last", "consecutive"])
+def test_gae_equals_its_definition(kind, gamma, lam):
+    """The recurrence and the explicit sum differ only in summation order and in how the powers are formed: their distance is
+    bounded by T * 2^-52 * the sum of the absolute terms (computed here), plus the float32 rounding of the result."""
+    from intent_radio_sched_multi_slice_amd import adapters
+    rng = np.random.default_rng(sum(map(ord, kind)) * 1000 + int(gamma * 1000) + int(lam * 100))
+    for T in (1, 2, 7, 60, 200):
+        r, v, d = _gae_case(rng, T, 6, 3, kind)
+        adv, vtarg = adapters.gae(r, v, d, gamma, lam)
+        assert adv.dtype == np.float32 and vtarg.dtype == np.float32 and adv.shape == r.shape
+        want, tot = _gae_by_definition(r, v.astype(np.float64), d, gamma, lam)
+        bound = T * 2.0 ** -52 * tot
+        # (the float32 result is the rounding of a float64 value within `bound` of `want`)
+        assert np.all(np.abs(adv.astype(np.float64) - want) <= bound + 2.0 ** -24 * (np.abs(want) + bound) + 2.0 ** -149), (kind, T)
+        wv = want + v[:-1].astype(np.float64)
+        assert np.all(np.abs(vtarg.astype(np.float64) - wv) <= bound + 2.0 ** -24 * (np.abs(wv) + bound) + 2.0 ** -149), (kind, T)
+        if kind == "first":        # nothing crosses a done: slot 0 is its own delta without a bootstrap
+            assert np.array_equal(adv[0], (r[0] - v[0].astype(np.float64)).astype(np.float32))
+
+
+def test_gae_accepts_torch_tensors():
+    from intent_radio_sched_multi_slice_amd import adapters
+    rng = np.random.default_rng(3)
+    r, v, d = _gae_case(rng, 9, 4, 2, "random")
+    a, b = adapters.gae(r, v, d), adapters.gae(torch.from_numpy(r), torch.from_numpy(v), torch.from_numpy(d))
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+# ---- the RLlib critic reader ------------------------------------------------------------------------------------------------
+def _fc(prefix, name, n_in, n_out, seed):
+    g = torch.Generator().manual_seed(seed)
+    return {f"{prefix}{name}._model.0.weight": torch.randn(n_out, n_in, generator=g), f"{prefix}{name}._model.0.bias": torch.randn(n_out, generator=g)}
+
+
+def _state_dict(prefix="internal_model.", separate=True):
+    sd = {}
+    for i, (a, b) in enumerate([(50, 64), (64, 32)]):
+        sd.update(_fc(prefix, f"_hidden_layers.{i}", a, b, i))
+        if separate:
+            sd.update(_fc(prefix, f"_value_branch_separate.{i}", a, b, 10 + i))
+    sd.update(_fc(prefix, "_logits", 32, 10, 20))
+    sd.update(_fc(prefix, "_value_branch", 32, 1, 21))
+    return sd
+
+
+def test_rllib_value_layers_separate_and_shared():
+    from intent_radio_sched_multi_slice_amd import adapters
+    from intent_radio_sched_multi_slice_amd.batched_env import policy_net_layers
+    for separate in (True, False):
+        sd = _state_dict(separate=separate)
+        sd["other_model.weight"] = torch.zeros(3)                # outside the prefix: ignored
+        layers = adapters.rllib_fcnet_value_layers(sd)
+        body = "_value_branch_separate" if separate else "_hidden_layers"
+        assert [tuple(w.shape) for w, _ in layers] == [(64, 50), (32, 64), (1, 32)]
+        for i in range(2):
+            assert torch.equal(layers[i][0], sd[f"internal_model.{body}.{i}._model.0.weight"])
+            assert torch.equal(layers[i][1], sd[f"internal_model.{body}.{i}._model.0.bias"])
+        assert torch.equal(layers[2][0], sd["internal_model._value_branch._model.0.weight"])
+        out, act = policy_net_layers(layers, in_dim=50, out_dim=1)
+        assert act == "tanh" and len(out) == 3
+        # the actor reader still sees the same dict its way
+        assert [tuple(w.shape) for w, _ in adapters.rllib_fcnet_layers(sd)] == [(64, 50), (32, 64), (10, 32)]
+
+
+def test_rllib_value_layers_are_strict():
+    from intent_radio_sched_multi_slice_amd import adapters
+    sd = _state_dict()
+    sd["internal_model.log_std"] = torch.zeros(5)
+    with pytest.raises(ValueError, match="not a FullyConnectedNetwork key"):
+        adapters.rllib_fcnet_value_layers(sd)
+    sd = {k: v for k, v in _state_dict().items() if "_value_branch._model" not in k}
+    with pytest.raises(ValueError, match="head"):
+        adapters.rllib_fcnet_value_layers(sd)
+    sd = {k: v for k, v in _state_dict().items() if "_value_branch_separate.0._model.0.bias" not in k}
+    with pytest.raises(ValueError, match="incomplete"):
+        adapters.rllib_fcnet_value_layers(sd)
+    sd = {k: v for k, v in _state_dict().items() if "_value_branch_separate.0." not in k}
+    with pytest.raises(ValueError, match="incomplete"):
+        adapters.rllib_fcnet_value_layers(sd)
+    with pytest.raises(ValueError):
+        adapters.rllib_fcnet_value_layers(_state_dict(), prefix="nothing_here.")
+
+
+# ---- log-probabilities ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("stochastic", [False, True])
+def test_policy_logp_matches_torch_distributions(stochastic):
+    """Against Normal(mean, std).log_prob(action).sum(-1) with the reference's masking (mean -1, std 1e-9 where the sorted mask is
+    0; agents/masked_action_distribution.py:30-36) in float64, and against log_softmax.  Tolerance: the float32 rounding of the
+    result plus 1e-12 S (1 + max z^2) for ((a - mean) / std)^2 re-formed from the action."""
+    from intent_radio_sched_multi_slice_amd import adapters
+    rng = np.random.default_rng(5)
+    B, S = 200, 10
+    out = rng.standard_normal((B, 2 * S)).astype(np.float32)
+    mask = (rng.random((B, S)) < 0.6).astype(np.int8)
+    mask[0] = 0
+    mask[1] = 1
+    z = None
+    if stochastic:
+        z, _ = adapters.ibsched_policy_noise(np.arange(B), np.zeros(B), np.arange(B) % 7, S, 0xABCDEF0123)
+        assert z.shape == (B, S) and abs(z.mean()) < 0.1 and 0.9 < z.std() < 1.1
+    logits = (rng.standard_normal((B, S, 3)) * 3).astype(np.float32)
+    choice = rng.integers(0, 3, (B, S))
+    lp, lpi = adapters.ibsched_policy_logp(out, mask, z, logits, choice)
+    assert lp.dtype == np.float32 and lpi.dtype == np.float32
+    o = torch.from_numpy(out).double()
+    sm = adapters.sorted_action_mask(torch.from_numpy(mask))
+    mean, std = adapters.masked_gaussian_params(o[:, :S], o[:, S:], sm)
+    action = mean if z is None else torch.where(sm == 0, mean, mean + std * torch.from_numpy(z))
+    want = torch.distributions.Normal(mean, std).log_prob(action).sum(-1).numpy()
+    zmax = 0.0 if z is None else (z * z).max(axis=1)
+    assert np.all(np.abs(lp.astype(np.float64) - want) <= 2.0 ** -24 * np.abs(want) + 1e-12 * S * (1.0 + zmax))
+    assert lp[0] == np.float32(S * (adapters.LN_1E9 - adapters.HALF_LN_2PI))          # an all-masked row: the constant exactly
+    want_i = torch.log_softmax(torch.from_numpy(logits).double(), dim=-1).gather(-1, torch.from_numpy(choice)[..., None])[..., 0].numpy()
+    assert np.all(np.abs(lpi.astype(np.float64) - want_i) <= 2.0 ** -24 * np.abs(want_i) + 1e-12)
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------------
+def test_header_and_binding_agree_on_the_new_exports():
+    from intent_radio_sched_multi_slice_amd import _lib
+    from intent_radio_sched_multi_slice_amd.csrc import build
+    build.build()
+    lib = _lib.load()
+    header = open(os.path.join(REPO, "include", "ranenv.h")).read()
+    declared = set(re.findall(r"\b(ranenv_[a-z_]+)\s*\(", header))
+    for name in ("ranenv_set_value_network", "ranenv_collect", "ranenv_gae"):
+        assert name in declared and name in _lib.EXPORTS and hasattr(lib, name), name
+    fields = re.search(r"typedef struct \{([^}]*)\} ranenv_trajectory;", header).group(1)
+    names = re.findall(r"\*\s*([a-z_]+)", fields)
+    assert tuple(names) == _lib.TRAJECTORY_FIELDS == tuple(n for n, _ in _lib.Trajectory._fields_)
+    size = int(re.search(r"#define RANENV_TRAJECTORY_BYTES (\d+)", header).group(1))       # (a static_assert ties it to sizeof in the library)
+    assert ctypes.sizeof(_lib.Trajectory) == size == 8 * len(names)
+
+
+def test_new_kernels_have_no_scratch_and_no_spills():
+    from intent_radio_sched_multi_slice_amd.csrc import build as hip_build
+    import kernel_resources
+    hip_build.build()
+    by = {k["name"]: k for k in kernel_resources.kernel_resources()}
+    for want in ("ranenv_policy_collect_kernel", "ranenv_gae_kernel", "ranenv_policy_kernel"):
+        hits = [k for n, k in by.items() if want in n]
+        assert hits, (want, sorted(by)[:8])
+        for k in hits:
+            assert k.get("private_segment_fixed_size", 0) == 0 and k.get("vgpr_spill_count", 0) == 0 and k.get("agpr_count", 0) == 0, k
