@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define RANENV_ABI_VERSION 9
+#define RANENV_ABI_VERSION 10
 
 enum {
     RANENV_OK = 0,
@@ -57,7 +57,8 @@ enum {
     RANENV_E_NOMEM = -4
 };
 
-enum { RANENV_POLICY_EXTERNAL = 0, RANENV_POLICY_MARR = 1, RANENV_POLICY_MAPF = 2, RANENV_POLICY_NETWORK = 3 };
+enum { RANENV_POLICY_EXTERNAL = 0, RANENV_POLICY_MARR = 1, RANENV_POLICY_MAPF = 2, RANENV_POLICY_NETWORK = 3, RANENV_POLICY_HEAD_NETWORK = 4 };
+enum { RANENV_HEAD_DIST_GAUSS_CLIP = 0, RANENV_HEAD_DIST_GAUSS_TANH = 1 };
 enum { RANENV_ACT_TANH = 0, RANENV_ACT_RELU = 1 };
 enum { RANENV_NET_IN_OBS = 0, RANENV_NET_IN_MASK_OBS = 1 };
 enum { RANENV_INTRA_RR = 0, RANENV_INTRA_PF = 1, RANENV_INTRA_MT = 2, RANENV_INTRA_PER_SLICE = 255 };
@@ -237,7 +238,8 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra);
  * net fails with RANENV_E_STATE, one without the obs_inter buffer (or obs_intra with an intra net) with RANENV_E_INVALID: the
  * nets read the observation in those buffers.  stochastic != 0 samples, 0 takes the mode.
  * ranenv_get_policy_actions: device pointers to the last actions, scores float64 [B][S] (the step's input: sorted positions
- * as obs_inter lists the slices) and intra uint8 [B][S] (by slice index; NULL without an intra net). */
+ * as obs_inter lists the slices) and intra uint8 [B][S] (by slice index; NULL without an intra net).  The head policies below
+ * write their scores to the same buffer; the call works once either kind of net is bound. */
 typedef struct {
     int32_t n_hidden;         /* 1..4                                          */
     int32_t activation;       /* RANENV_ACT_TANH / RANENV_ACT_RELU              */
@@ -603,6 +605,77 @@ int ranenv_launch_info(ranenv_handle h, int32_t *grid, int32_t *block, int32_t *
  *   dev_reward_head float64 [B][2]     [0] SchedTWC.calculate_reward, [1] SchedColORAN.calculate_reward
  * NULL, NULL unbinds.  The heads read pkt_throughputs, so they refuse RANENV_F_NO_RAW_OUTPUT. */
 int ranenv_bind_head_outputs(ranenv_handle h, float *dev_obs_head, double *dev_reward_head);
+
+/* Head policies (RANENV_POLICY_HEAD_NETWORK): the learned baselines SchedTWC / SchedColORAN -- in the reference SB3 PPO / SAC
+ * MlpPolicy agents (agents/sched_twc.py:111-133, agents/sched_colran.py, agents/sb3_sched.py) that read the head observation and
+ * emit the player_0 action -- as a caller-supplied MLP run by one batched launch in front of every TTI that gets no inter-slice
+ * scores: ranenv_step / _step_range / _step_part (their env range, their stream) and every TTI of ranenv_rollout (per partition,
+ * one TTI per launch, no persistent launch; auto-reset included: the reset launch refreshes dev_obs_head, so the first action of
+ * a new episode reads the new episode's first observation).  The intra-slice scheduler is the fixed_intra of ranenv_set_policy
+ * (the reference: RR).
+ *   actor: a ranenv_mlp of 1..4 hidden layers (widths 1..512, tanh / relu: SB3's defaults [64, 64] tanh for PPO and [256, 256] relu
+ *     for SAC fit; wider nets are RANENV_E_INVALID), input_layout RANENV_NET_IN_OBS, dims[0] = 10*S: the row of the bound
+ *     dev_obs_head as the head kernel left it behind the previous TTI or reset.  One row per env.  The scores go to the buffer
+ *     ranenv_get_policy_actions returns (float64 [B][S]); the step reads them exactly as it reads a caller's dev_inter_scores: it
+ *     applies the slice permutation and the inactive-slice rule (agents/ib_sched.py:247-255) itself, so nothing is masked here.
+ *     Float64 arithmetic on the float32 net outputs, nothing contracted:
+ *   RANENV_HEAD_DIST_GAUSS_CLIP -- SB3 PPO ActorCriticPolicy, squash_output off.  Output [S] = mean; dev_log_std float32 [S] (device
+ *     pointer, required, copied into the handle) is the policy's state-independent log_std parameter.
+ *       score_j = clamp(a_j, -1, 1);  a_j = mean_j (mode: predict(deterministic=True) and its np.clip),
+ *                                     a_j = mean_j + exp(log_std_j) * z_j (stochastic)
+ *   RANENV_HEAD_DIST_GAUSS_TANH -- SB3 SAC Actor.  Output [2*S] = (mu | log_std), the mu and log_std Linear layers stacked;
+ *     dev_log_std must be NULL.  ls_j = clamp(log_std_j, -20, 2);
+ *       score_j = tanh(mu_j) (mode),  tanh(mu_j + exp(ls_j) * z_j) (stochastic)
+ *     SB3's unscale_action is the identity on Box[-1, 1] up to one float32 rounding of a + 1; the device does NOT reproduce that
+ *     rounding.
+ *   Noise: Philox-4x32-10(counter = (env_id_base + env, episode_number[env], step_number[env], 0x48454100 + j), key = (seed lo,
+ *     seed hi)), u1, u2, z by the Box-Muller transform of the IBSched nets above: a function of those numbers alone, independent of
+ *     launches, partitions and ranges.
+ *   stable-baselines3 is not part of this project's test environment: the forward above is restated from SB3's documented module
+ *   layout, parity with SB3 itself is UNPINNED (as for RLlib above).
+ * ranenv_set_head_policy_network validates (RANENV_E_INVALID) and copies the weights into a packed buffer of its own: IBSched nets
+ * and head nets can both stay bound; ranenv_set_policy(h, RANENV_POLICY_HEAD_NETWORK, fixed_intra) selects them.  Under that policy
+ * a TTI without scores fails with RANENV_E_STATE while no head net or no dev_obs_head is bound.
+ * ranenv_set_head_value_network: the critic [10*S] -> 1, in a buffer of its own.
+ *
+ * ranenv_collect_head: ranenv_rollout of n_steps TTIs under the head actor that records a PPO batch, like ranenv_collect.
+ *   ranenv_head_trajectory: caller-owned device pointers, [t]-major, any of them NULL (= not recorded):
+ *     obs_head    f32 [T][B][10*S]   the observation the TTI's action was computed from
+ *     action      f64 [T][B][S]      a_j above, UNCLAMPED (the step consumed its clamp)
+ *     logp        f32 [T][B]         sum over j = 0..S-1, ascending, of ((-0.5 z_j) z_j - log_std_j) - 0.5 ln(2 pi)  (z_j = 0 in the
+ *                                    mode; every position counts, nothing is masked), float64, rounded once
+ *     vf          f32 [T+1][B]       the critic on that observation; slot T: on the observation left after the last TTI
+ *     reward_head f64 [T][B][2]      the head kernel's pair, written straight into the slot (the bound dev_reward_head gets the last
+ *                                    TTI's pair after the call)
+ *     done        u8  [T][B]
+ *     adv, vtarg  f32 [T][B]         GAE, the recurrence of ranenv_collect above, on column reward_col of reward_head
+ *                                    (0 = SchedTWC, 1 = SchedColORAN); they need reward_head, vf and done
+ *   Only GAUSS_CLIP (PPO) collects: GAUSS_TANH gives RANENV_E_INVALID (SAC is off-policy and needs no log-probabilities).  No head
+ *   net, no head critic or another policy than HEAD_NETWORK: RANENV_E_STATE (ranenv_collect under HEAD_NETWORK likewise).  Env
+ *   state, the caller's output buffers, head buffers and metrics afterwards are bit for bit what ranenv_rollout leaves under the
+ *   same net and seed.  The critic is fused behind the actor or split off as for ranenv_collect (option "collect_split").
+ *
+ * Episode sums of the two head rewards: when episode metrics are enabled AND dev_reward_head is bound, the head kernel adds the
+ *   TTI's (r_twc, r_colran) to a per-env pair float64 [B][2] (one add per TTI, in TTI order; a reset of the env zeroes it), and
+ *   under auto-reset a finished episode's pair is appended to a log [B][episode_slots][2] at the slot index of ranenv_get_metrics'
+ *   log: the mean episode reward SB3's EvalCallback selects best_model by (sched_twc.py:93-103).  Allocated by whichever of
+ *   ranenv_enable_metrics / ranenv_bind_head_outputs completes the pair, zeroed by ranenv_enable_metrics.
+ *   ranenv_get_head_metrics returns the device pointers (NULL while they do not exist; episode_log NULL with 0 slots). */
+typedef struct {
+    float *obs_head;
+    double *action;
+    float *logp, *vf;
+    double *reward_head;
+    uint8_t *done;
+    float *adv, *vtarg;
+} ranenv_head_trajectory;
+#define RANENV_HEAD_TRAJECTORY_BYTES 64
+int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int32_t dist, const float *dev_log_std, int32_t stochastic,
+                                   uint64_t seed, void *stream);
+int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, void *stream);
+int ranenv_get_head_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t *episode_slots);
+int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, int32_t reward_col, double gamma, double lambda,
+                        float *dev_obs_inter, float *dev_obs_intra, double *dev_reward, uint8_t *dev_done, void *stream);
 /* SchedColORAN's slice-name table (sched_colran.py:356-367) as data: host array [count][S], bit 0 = eMBB,
  * bit 1 = URLLC, for scenario-pool rows [first, first+count).  Default 0 (no reward term). */
 int ranenv_set_slice_usecase(ranenv_handle h, int32_t first, int32_t count, const int32_t *usecase, void *stream);

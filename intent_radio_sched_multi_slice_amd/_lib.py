@@ -11,8 +11,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RANENV_LIB") or os.path.join(_HERE, "csrc", "libranenv_hip.so")
 
-ABI_VERSION = 9
-POLICY_EXTERNAL, POLICY_MARR, POLICY_MAPF, POLICY_NETWORK = 0, 1, 2, 3
+ABI_VERSION = 10
+POLICY_EXTERNAL, POLICY_MARR, POLICY_MAPF, POLICY_NETWORK, POLICY_HEAD_NETWORK = 0, 1, 2, 3, 4
+HEAD_DIST_GAUSS_CLIP, HEAD_DIST_GAUSS_TANH = 0, 1
 ACT_TANH, ACT_RELU = 0, 1
 NET_IN_OBS, NET_IN_MASK_OBS = 0, 1
 NET_MAX_HIDDEN, NET_MAX_WIDTH = 4, 512
@@ -79,6 +80,14 @@ class Trajectory(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TRAJECTORY_FIELDS]
 
 
+HEAD_TRAJECTORY_FIELDS = ("obs_head", "action", "logp", "vf", "reward_head", "done", "adv", "vtarg")
+
+
+class HeadTrajectory(C.Structure):
+    """ranenv_head_trajectory: caller-owned device pointers of a ranenv_collect_head record, [t]-major (NULL = not recorded)."""
+    _fields_ = [(n, C.c_void_p) for n in HEAD_TRAJECTORY_FIELDS]
+
+
 class Views(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in VIEW_FIELDS]
 
@@ -137,6 +146,10 @@ FUNCTIONS = {
     "ranenv_set_value_network": (C.c_int, [_P, C.POINTER(Mlp), C.POINTER(Mlp), _P]),
     "ranenv_collect": (C.c_int, [_P, _I32, C.POINTER(Trajectory), _F64, _F64] + [_P] * 5),
     "ranenv_gae": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _F64, _F64, _P, _P, _P]),
+    "ranenv_set_head_policy_network": (C.c_int, [_P, C.POINTER(Mlp), _I32, _P, _I32, C.c_uint64, _P]),
+    "ranenv_set_head_value_network": (C.c_int, [_P, C.POINTER(Mlp), _P]),
+    "ranenv_get_head_metrics": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "ranenv_collect_head": (C.c_int, [_P, _I32, C.POINTER(HeadTrajectory), _I32, _F64, _F64] + [_P] * 5),
 }
 EXPORTS = tuple(FUNCTIONS)
 

@@ -9,6 +9,8 @@
 * ``marl_obs_dict`` / ``marl_reward_dict``: one env of the batch in the dict layout RLlib's policies
   of the reference consume (``player_0`` = inter-slice agent, ``player_{s+1}`` = intra-slice agents,
   agents/ib_sched.py:160-200, simu.py:559-566).
+* ``head_policy_actions`` / ``head_policy_logp`` / ``sb3_ppo_layers`` / ``sb3_sac_actor_layers``: trained SchedTWC / SchedColORAN
+  policies on the device (``BatchedRanEnv.set_head_policy_network``): the normative restatement and the SB3 state-dict readers.
 """
 from __future__ import annotations
 
@@ -471,3 +473,125 @@ def rllib_fcnet_layers(state_dict, prefix: str = "internal_model."):
     if sorted(hidden) != list(range(len(hidden))) or any(set(v) != {"weight", "bias"} for v in hidden.values()):
         raise ValueError(f"hidden layers under {prefix!r} are incomplete: {sorted(hidden)}")
     return [(hidden[i]["weight"], hidden[i]["bias"]) for i in range(len(hidden))] + [(logits["weight"], logits["bias"])]
+
+
+# --------------------------------------------------------------------------------------------
+# the learned baselines SchedTWC / SchedColORAN on the device (RANENV_POLICY_HEAD_NETWORK): the normative restatement and the
+# SB3 state-dict readers.  stable-baselines3 is not part of the test environment: the key names and the forward are restated from
+# SB3's documented module layout, parity with SB3 itself is UNPINNED.
+# --------------------------------------------------------------------------------------------
+HEAD_TAG = 0x48454100            # counter word c3 of the head policy's Philox draws: tag + position (include/ranenv.h)
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0      # SAC's clamp of the actor's log_std output
+
+
+def head_policy_noise(env_ids, episode, step, S: int, seed: int):
+    """The head policy's draws z float64 [B, S]: Box-Muller of Philox words 0 / 1 at counter (env id, episode, step, HEAD_TAG + j),
+    key = seed."""
+    col = lambda a: np.asarray(torch.as_tensor(a).cpu().numpy(), dtype=np.int64).reshape(-1, 1)  # noqa: E731
+    c3 = HEAD_TAG + np.arange(S, dtype=np.int64)[None, :]
+    d = philox4x32_10(col(env_ids), col(episode), col(step), c3, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    u1 = (d[0].astype(np.float64) + 1.0) * 2.0 ** -32
+    u2 = d[1].astype(np.float64) * 2.0 ** -32
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+
+
+def head_policy_actions(head_obs, actor, dist: str = "gauss_clip", log_std=None, stochastic: bool = False, seed: int = 0,
+                        activation: Optional[str] = None, env_ids=None, episode=None, step=None):
+    """What the device computes under RANENV_POLICY_HEAD_NETWORK, in plain torch / numpy (the normative statement the GPU tests
+    compare against; include/ranenv.h spells out the same rules).
+
+    ``head_obs`` [B, 10*S]; ``actor`` as for ``batched_env.policy_net_layers``.  Forward in float32, epilogue in float64:
+      "gauss_clip" (SB3 PPO): mean = net(obs) [S], ``log_std`` [S] the policy's parameter; a = mean, or when ``stochastic``
+          mean + exp(log_std) * z; score = clamp(a, -1, 1);
+      "gauss_tanh" (SB3 SAC): (mu | log_std) = net(obs) [2S], log_std clamped to [-20, 2]; a = mu, or mu + exp(log_std) * z;
+          score = tanh(a);
+      z = ``head_policy_noise`` at (env_ids + b, episode[b], step[b]).  Nothing is masked: the step applies the slice rules.
+    Returns (scores float64 [B, S], a float64 [B, S] -- the unclamped / unsquashed action) as CPU tensors."""
+    from .batched_env import policy_net_layers
+    head_obs = torch.as_tensor(head_obs).detach().cpu().to(torch.float32)
+    B, S = head_obs.shape[0], head_obs.shape[1] // 10
+    if dist not in ("gauss_clip", "gauss_tanh"):
+        raise ValueError("dist must be 'gauss_clip' or 'gauss_tanh'")
+    if (dist == "gauss_clip") != (log_std is not None):
+        raise ValueError("log_std is required for gauss_clip and must be None for gauss_tanh")
+    if activation is None and not isinstance(actor, torch.nn.Module):
+        activation = "tanh" if dist == "gauss_clip" else "relu"
+    layers, act = policy_net_layers(actor, activation, 10 * S, S if dist == "gauss_clip" else 2 * S)
+    out = _mlp_forward(head_obs, [(w.cpu(), b.cpu()) for w, b in layers], act).to(torch.float64)
+    if dist == "gauss_clip":
+        a = out
+        ls = torch.as_tensor(log_std).detach().cpu().to(torch.float32).to(torch.float64).reshape(1, S)
+    else:
+        a, ls = out[:, :S], out[:, S:].clamp(LOG_STD_MIN, LOG_STD_MAX)
+    if stochastic:
+        if env_ids is None or episode is None or step is None:
+            raise ValueError("stochastic actions need env_ids, episode and step")
+        a = a + torch.exp(ls) * torch.from_numpy(head_policy_noise(env_ids, episode, step, S, seed))
+    scores = a.clamp(-1.0, 1.0) if dist == "gauss_clip" else torch.tanh(a)
+    return scores, a
+
+
+def head_policy_logp(log_std, z=None, B: Optional[int] = None):
+    """The log-probability ``collect_head()`` records ("gauss_clip" only), restated in numpy float64: the sum over ALL positions
+    j = 0..S-1, ascending, of ((-0.5 z_j) z_j - log_std_j) - 0.5 ln 2 pi -- no masked term -- rounded once to float32.
+    ``log_std`` float32 [S]; ``z`` [B, S] the draws the actions used (None = the mode, z = 0: give ``B``).  Returns float32 [B]."""
+    as_np = lambda a, dt: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)  # noqa: E731
+    ls = as_np(log_std, np.float32).astype(np.float64).reshape(-1)
+    zz = np.zeros((int(B), ls.shape[0])) if z is None else as_np(z, np.float64)
+    lp = np.zeros(zz.shape[0], dtype=np.float64)
+    for j in range(ls.shape[0]):                                # ascending positions, as the kernel sums them
+        lp = lp + (((-0.5 * zz[:, j]) * zz[:, j] - ls[j]) - HALF_LN_2PI)
+    return lp.astype(np.float32)
+
+
+def _sb3_sequential(state_dict, prefix: str, what: str):
+    """(W, b) of the Linear layers of an SB3 ``create_mlp`` Sequential under ``prefix`` (indices 0, 2, 4, ...: activations between)."""
+    found = {}
+    for key, val in state_dict.items():
+        if not key.startswith(prefix):
+            continue
+        parts = key[len(prefix):].split(".")
+        if len(parts) != 2 or not parts[0].isdigit() or int(parts[0]) % 2 or parts[1] not in ("weight", "bias"):
+            raise ValueError(f"not a key of an SB3 MLP under {prefix!r}: {key!r}")
+        found.setdefault(int(parts[0]) // 2, {})[parts[1]] = torch.as_tensor(val)
+    if not found or sorted(found) != list(range(len(found))) or any(set(v) != {"weight", "bias"} for v in found.values()):
+        raise ValueError(f"{what}: the layers under {prefix!r} are missing or incomplete: {sorted(found)}")
+    return [(found[i]["weight"], found[i]["bias"]) for i in range(len(found))]
+
+
+def _sb3_linear(state_dict, name: str):
+    if f"{name}.weight" not in state_dict or f"{name}.bias" not in state_dict:
+        raise ValueError(f"no {name}.weight / {name}.bias in the state dict")
+    return torch.as_tensor(state_dict[f"{name}.weight"]), torch.as_tensor(state_dict[f"{name}.bias"])
+
+
+def sb3_ppo_layers(state_dict):
+    """An SB3 ``PPO`` ``MlpPolicy`` (``ActorCriticPolicy``, separate ``net_arch`` for pi and vf) from ``policy.state_dict()``:
+    returns (actor layers, log_std [S], critic layers) with actor = ``mlp_extractor.policy_net.{0,2,..}`` then ``action_net``,
+    critic = ``mlp_extractor.value_net.{0,2,..}`` then ``value_net``, and the ``log_std`` parameter.  Any other key (a features
+    extractor with weights, a shared trunk) raises ValueError, as do missing ones.  The activation is not in a state dict: SB3's
+    default is tanh.  Key names restated from SB3's documented module layout: no real checkpoint has been read."""
+    known = ("mlp_extractor.policy_net.", "mlp_extractor.value_net.", "action_net.", "value_net.")
+    for key in state_dict:
+        if key != "log_std" and not key.startswith(known):
+            raise ValueError(f"not a key of an SB3 PPO MlpPolicy: {key!r}")
+    if "log_std" not in state_dict:
+        raise ValueError("no log_std in the state dict (a PPO policy for a Box action space has one)")
+    actor = _sb3_sequential(state_dict, "mlp_extractor.policy_net.", "actor") + [_sb3_linear(state_dict, "action_net")]
+    critic = _sb3_sequential(state_dict, "mlp_extractor.value_net.", "critic") + [_sb3_linear(state_dict, "value_net")]
+    return actor, torch.as_tensor(state_dict["log_std"]), critic
+
+
+def sb3_sac_actor_layers(state_dict):
+    """The actor of an SB3 ``SAC`` ``MlpPolicy`` from ``policy.state_dict()``: ``actor.latent_pi.{0,2,..}`` then the ``actor.mu``
+    and ``actor.log_std`` Linear layers STACKED into one output layer (mu | log_std), the form "gauss_tanh" takes.  Keys outside
+    ``actor.`` (the critics, their targets) are ignored; any other key under ``actor.`` raises ValueError, as do missing ones.
+    SB3's default activation for SAC is relu.  Key names restated from SB3's documented module layout."""
+    for key in state_dict:
+        if key.startswith("actor.") and not key.startswith(("actor.latent_pi.", "actor.mu.", "actor.log_std.")):
+            raise ValueError(f"not a key of an SB3 SAC actor: {key!r}")
+    body = _sb3_sequential(state_dict, "actor.latent_pi.", "actor")
+    (wm, bm), (wl, bl) = _sb3_linear(state_dict, "actor.mu"), _sb3_linear(state_dict, "actor.log_std")
+    if wm.shape != wl.shape:
+        raise ValueError(f"actor.mu {tuple(wm.shape)} and actor.log_std {tuple(wl.shape)} differ in shape")
+    return body + [(torch.cat([wm, wl], dim=0), torch.cat([bm, bl], dim=0))]

@@ -25,8 +25,8 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_RELU, ACT_TANH, F_CLEAR_HISTORY_ON_RESET, F_NO_RAW_OUTPUT, F_SYNC_CHECK, INTRA_MT, INTRA_PER_SLICE, INTRA_PF,
-                   INTRA_RR, NET_IN_MASK_OBS, NET_IN_OBS, NET_MAX_HIDDEN, NET_MAX_WIDTH, POLICY_EXTERNAL, POLICY_MAPF, POLICY_MARR,
-                   POLICY_NETWORK, SE_GATHER, SE_STREAM, RanEnvError)
+                   INTRA_RR, NET_IN_MASK_OBS, NET_IN_OBS, NET_MAX_HIDDEN, NET_MAX_WIDTH, POLICY_EXTERNAL, POLICY_HEAD_NETWORK, POLICY_MAPF,
+                   POLICY_MARR, POLICY_NETWORK, SE_GATHER, SE_STREAM, RanEnvError)
 from .scenario import MAX_AGE_CAP_DEFAULT, ScenarioTables
 
 _TORCH_DT = {"u1": torch.uint8, "i1": torch.int8, "i4": torch.int32, "i8": torch.int64, "f8": torch.float64, "f4": torch.float32}
@@ -49,6 +49,8 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 NET_ACTIVATIONS = {"tanh": ACT_TANH, "relu": ACT_RELU}
 NET_INPUTS = {"obs": NET_IN_OBS, "mask_obs": NET_IN_MASK_OBS}
+HEAD_DISTS = {"gauss_clip": _lib.HEAD_DIST_GAUSS_CLIP, "gauss_tanh": _lib.HEAD_DIST_GAUSS_TANH}
+HEAD_REWARDS = {"twc": 0, "colran": 1}
 
 
 def policy_net_layers(net, activation: Optional[str] = None, in_dim: Optional[int] = None, out_dim: Optional[int] = None):
@@ -447,6 +449,109 @@ class BatchedRanEnv:
             self._check(self._lib.ranenv_gae(self._h, T, Cn, _ptr(reward), _ptr(vf), _ptr(done), float(gamma), float(lam), _ptr(adv), _ptr(vtarg),
                                              self._stream()), "ranenv_gae")
         return adv, vtarg
+
+    # -- the learned baselines SchedTWC / SchedColORAN (RANENV_POLICY_HEAD_NETWORK) ------------------------------------------------
+    def set_head_policy_network(self, actor, dist: str = "gauss_clip", log_std=None, stochastic: bool = False, seed: int = 0,
+                                activation: Optional[str] = None, allow_sorted: bool = False, fixed_intra: Optional[int] = None):
+        """Run a trained SchedTWC / SchedColORAN actor on the device in front of every TTI (RANENV_POLICY_HEAD_NETWORK,
+        include/ranenv.h): ``actor`` maps ``head_obs`` [10*S] to S outputs (``dist`` "gauss_clip": SB3 PPO, the mean; ``log_std``
+        [S] is the policy's parameter) or 2*S outputs ("gauss_tanh": SB3 SAC, (mu | log_std); ``log_std`` must be None).  Nets as
+        for ``policy_net_layers`` (``activation`` default: tanh for gauss_clip, relu for gauss_tanh -- SB3's).  Needs
+        ``enable_heads()``.  Switches the policy to HEAD_NETWORK with round-robin inside the slices (``fixed_intra``: another).
+        SchedTWC runs IBSched without slice sorting (sched_twc.py:75-82): scenario tables whose ``sorted_slices`` is not the
+        identity raise RanEnvError unless ``allow_sorted``."""
+        if dist not in HEAD_DISTS:
+            raise ValueError(f"dist must be one of {sorted(HEAD_DISTS)}")
+        if getattr(self, "head_obs", None) is None:
+            raise RanEnvError("set_head_policy_network needs enable_heads(): the actor reads head_obs")
+        if self.tables is not None and not allow_sorted:
+            ss = np.asarray(self.tables.sorted_slices)
+            if not np.array_equal(ss, np.broadcast_to(np.arange(ss.shape[-1]), ss.shape)):
+                raise RanEnvError("the scenario tables sort the slices; SchedTWC / SchedColORAN run with enable_sort_slices=False "
+                                  "(pass allow_sorted=True to run the head policy on sorted positions anyway)")
+        if (dist == "gauss_clip") != (log_std is not None):
+            raise ValueError("log_std is required for gauss_clip and must be None for gauss_tanh")
+        if activation is None and not isinstance(actor, torch.nn.Module):
+            activation = "tanh" if dist == "gauss_clip" else "relu"
+        layers, act = policy_net_layers(actor, activation, 10 * self.S, self.S if dist == "gauss_clip" else 2 * self.S)
+        keep: list = []
+        m = self._mlp_struct(layers, act, NET_IN_OBS, keep)
+        ls = None
+        if log_std is not None:
+            ls = torch.as_tensor(log_std).detach().to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(ls.shape) != (self.S,):
+                raise ValueError(f"log_std: expected shape ({self.S},), got {tuple(ls.shape)}")
+            keep.append(ls)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_set_head_policy_network(self._h, C.byref(m), HEAD_DISTS[dist], _ptr(ls), 1 if stochastic else 0,
+                                                                 int(seed) & (2 ** 64 - 1), self._stream()), "ranenv_set_head_policy_network")
+        self._keep["head_policy_net"] = keep   # (the library copies on the current stream; keep the sources until it has)
+        self._policy_views = None
+        self.set_policy(POLICY_HEAD_NETWORK, INTRA_RR if fixed_intra is None else fixed_intra)
+
+    def set_head_value_network(self, critic, activation: Optional[str] = None):
+        """Bind the critic ``collect_head()`` evaluates beside the head actor (ranenv_set_head_value_network): ``head_obs`` [10*S]
+        -> one value.  Nets as for ``policy_net_layers``."""
+        keep: list = []
+        layers, act = policy_net_layers(critic, activation, 10 * self.S, 1)
+        m = self._mlp_struct(layers, act, NET_IN_OBS, keep)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_set_head_value_network(self._h, C.byref(m), self._stream()), "ranenv_set_head_value_network")
+        self._keep["head_value_net"] = keep
+
+    HEAD_TRAJECTORY_SHAPES = {     # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S)
+        "obs_head": (torch.float32, 0, lambda B, S: (B, 10 * S)), "action": (torch.float64, 0, lambda B, S: (B, S)),
+        "logp": (torch.float32, 0, lambda B, S: (B,)), "vf": (torch.float32, 1, lambda B, S: (B,)),
+        "reward_head": (torch.float64, 0, lambda B, S: (B, 2)), "done": (torch.uint8, 0, lambda B, S: (B,)),
+        "adv": (torch.float32, 0, lambda B, S: (B,)), "vtarg": (torch.float32, 0, lambda B, S: (B,)),
+    }
+
+    def collect_head(self, n_steps: int, reward: str = "twc", gamma: float = 0.99, lam: float = 0.95,
+                     record=_lib.HEAD_TRAJECTORY_FIELDS) -> Dict[str, torch.Tensor]:
+        """``rollout(n_steps)`` under the head actor that leaves a PPO batch on the device (ranenv_collect_head, include/ranenv.h):
+        a dict of ``[n_steps, B, ...]`` tensors named as ranenv_head_trajectory's fields (``vf`` has ``n_steps + 1`` slots),
+        restricted to ``record``.  ``adv`` / ``vtarg`` are GAE(``gamma``, ``lam``) on the ``reward`` column ("twc" / "colran") of
+        ``reward_head``.  Needs a "gauss_clip" ``set_head_policy_network`` and ``set_head_value_network``.  The tensors are
+        allocated once per (n_steps, record) and REUSED.  Everything else afterwards is as after ``rollout(n_steps)``."""
+        if self._recorder is not None:
+            raise RanEnvError("collect_head() does not return between TTIs: the recorder needs step()")
+        if reward not in HEAD_REWARDS:
+            raise ValueError(f"reward must be one of {sorted(HEAD_REWARDS)}")
+        n_steps = int(n_steps)
+        traj = _lib.HeadTrajectory()
+        out: Dict[str, torch.Tensor] = {}
+        if n_steps >= 1:
+            unknown = set(record) - set(_lib.HEAD_TRAJECTORY_FIELDS)
+            if unknown:
+                raise ValueError(f"unknown trajectory fields {sorted(unknown)}")
+            key = (n_steps, tuple(f for f in _lib.HEAD_TRAJECTORY_FIELDS if f in set(record)))
+            cache = self._keep.setdefault("head_trajectories", {})
+            if key not in cache:
+                shp = self.HEAD_TRAJECTORY_SHAPES
+                cache[key] = {f: torch.zeros((n_steps + shp[f][1],) + shp[f][2](self.B, self.S), dtype=shp[f][0], device=self.device)
+                              for f in key[1]}
+            out = cache[key]
+            for f, t in out.items():
+                setattr(traj, f, t.data_ptr())
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_collect_head(self._h, n_steps, C.byref(traj), HEAD_REWARDS[reward], float(gamma), float(lam),
+                                                      *self._p_out, self._stream()), "ranenv_collect_head")
+        return out
+
+    def head_episode_metrics(self) -> Dict[str, torch.Tensor]:
+        """Zero-copy views of the episode sums of the two head rewards (columns: SchedTWC, SchedColORAN): ``running`` [B, 2]
+        (current episode) and ``episode_log`` [B, slots, 2] (finished episodes, the rows of ``episode_metrics()``'s log; absent with
+        0 slots).  They exist once both ``enable_metrics()`` and ``enable_heads()`` were called; after ``evaluate(n)`` the log's
+        first n rows are the episodes it returned."""
+        run, log = C.c_void_p(), C.c_void_p()
+        slots = C.c_int32()
+        self._check(self._lib.ranenv_get_head_metrics(self._h, C.byref(run), C.byref(log), C.byref(slots)), "ranenv_get_head_metrics")
+        if not run.value:
+            raise RanEnvError("head episode metrics need enable_metrics() and enable_heads()")
+        out = {"running": torch.as_tensor(_DevArray(run.value, (self.B, 2), "f8", self), device=self.device)}
+        if slots.value > 0 and log.value:
+            out["episode_log"] = torch.as_tensor(_DevArray(log.value, (self.B, slots.value, 2), "f8", self), device=self.device)
+        return out
 
     def policy_actions(self) -> Dict[str, Optional[torch.Tensor]]:
         """Zero-copy views of the last actions of the policy nets: ``scores`` float64 [B, S] (what the step read, in the

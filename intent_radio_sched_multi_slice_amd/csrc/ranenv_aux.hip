@@ -146,12 +146,13 @@ DEVFN double np_sum_seq(const double *a, int n)
     return res;
 }
 
-__global__ void __launch_bounds__(CORE_NT) ranenv_head_kernel(const KP p)
+__global__ void __launch_bounds__(CORE_NT) ranenv_head_kernel(const KP p, double *head_acc, int reset)
 {
     __shared__ SharedHead sh;
     auto wave_sync = []() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
     const int e = p.e0 + blockIdx.x, tid = threadIdx.x;
     if (p.env_mask != nullptr && p.env_mask[e] == 0) return;
+    if (head_acc && reset && tid == 0) { head_acc[(size_t)e * 2 + 0] = 0.0; head_acc[(size_t)e * 2 + 1] = 0.0; }   // a new episode's sums
     const int S = p.S, U = p.U, D = p.D;
     const int sc = __builtin_amdgcn_readfirstlane(p.episodes[e].scenario);
     const int hlen = __builtin_amdgcn_readfirstlane(ST_hist_len(p)[e]);      // counters after this TTI's push
@@ -301,6 +302,10 @@ __global__ void __launch_bounds__(CORE_NT) ranenv_head_kernel(const KP p)
         }
         p.head_reward[(size_t)e * 2 + 0] = r_twc;
         p.head_reward[(size_t)e * 2 + 1] = r_col;
+        if (head_acc && !reset) {      // episode sums of the two head rewards: one add per TTI, in TTI order
+            head_acc[(size_t)e * 2 + 0] += r_twc;
+            head_acc[(size_t)e * 2 + 1] += r_col;
+        }
     }
 }
 
@@ -342,6 +347,7 @@ __global__ void __launch_bounds__(64) ranenv_advance_kernel(const AdvanceArgs a)
     if (a.acc) {          // the finished episode's sums go to the env's log (the reset that follows zeroes the running sums)
         const int n = a.ep_n[e];                  // read by every thread of this one wave before thread 8 stores
         if (tid < 8 && n < a.ep_slots) a.ep_acc[((size_t)e * a.ep_slots + n) * 8 + tid] = a.acc[(size_t)e * 8 + tid];
+        if (a.head_acc && tid >= 16 && tid < 18 && n < a.ep_slots) a.head_ep_acc[((size_t)e * a.ep_slots + n) * 2 + (tid - 16)] = a.head_acc[(size_t)e * 2 + (tid - 16)];
         if (tid == 8) a.ep_n[e] = n + 1;
     }
     if (a.term_inter) for (int i = tid; i < a.n_inter; i += 64) a.term_inter[(size_t)e * a.n_inter + i] = a.obs_inter[(size_t)e * a.n_inter + i];
@@ -399,20 +405,23 @@ __global__ void __launch_bounds__(256) ranenv_ddiv_selftest_kernel(const double 
 // dependent float64 multiplies and adds per lane; slot t - 1's reward / value / done do not depend on it and are requested before
 // slot t's step of the chain is evaluated.
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) ranenv_gae_kernel(int n_steps, int B, int n_cols, const double *reward, const float *vf, const uint8_t *done,
-                                                         double gamma, double lambda, float *adv, float *vtarg)
+__global__ void __launch_bounds__(256) ranenv_gae_kernel(int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf,
+                                                         const uint8_t *done, double gamma, double lambda, float *adv, float *vtarg)
 {
     const long long n = (long long)B * n_cols, i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const long long b = i / n_cols;
+    // the reward of (t, env, column): rows of reward_stride doubles per env (= n_cols: packed, as ranenv_gae's; ranenv_collect_head
+    // reads one column of the [T][B][2] head rewards)
+    const long long rn = (long long)B * reward_stride, ri = b * reward_stride + (i - b * n_cols);
     const double gl = gamma * lambda;
     double a_next = 0.0, v1 = (double)vf[(long long)n_steps * n + i];
-    double r = reward[(long long)(n_steps - 1) * n + i], v0 = (double)vf[(long long)(n_steps - 1) * n + i];
+    double r = reward[(long long)(n_steps - 1) * rn + ri], v0 = (double)vf[(long long)(n_steps - 1) * n + i];
     uint8_t d = done[(long long)(n_steps - 1) * B + b];
     for (int t = n_steps - 1; t >= 0; t--) {
         double rp = 0.0, vp = 0.0;
         uint8_t dp = 0;
-        if (t > 0) { rp = reward[(long long)(t - 1) * n + i]; vp = (double)vf[(long long)(t - 1) * n + i]; dp = done[(long long)(t - 1) * B + b]; }
+        if (t > 0) { rp = reward[(long long)(t - 1) * rn + ri]; vp = (double)vf[(long long)(t - 1) * n + i]; dp = done[(long long)(t - 1) * B + b]; }
         const double nd = d ? 0.0 : 1.0;
         const double delta = (r + (gamma * v1) * nd) - v0;
         const double a = delta + (gl * nd) * a_next;
@@ -427,12 +436,12 @@ __global__ void __launch_bounds__(256) ranenv_gae_kernel(int n_steps, int B, int
 
 namespace ranenv_dev {
 
-void launch_gae(hipStream_t s, int n_steps, int B, int n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,
-                double lambda, float *adv, float *vtarg)
+void launch_gae(hipStream_t s, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,
+                double gamma, double lambda, float *adv, float *vtarg)
 {
     const long long n = (long long)B * n_cols;
-    hipLaunchKernelGGL(ranenv_gae_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_steps, B, n_cols, reward, vf, done, gamma, lambda,
-                       adv, vtarg);
+    hipLaunchKernelGGL(ranenv_gae_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_steps, B, n_cols, reward, reward_stride, vf, done,
+                       gamma, lambda, adv, vtarg);
 }
 
 void launch_ddiv_selftest(hipStream_t s, const double *a, const double *b, double *fast, double *ieee, long long n)
@@ -465,7 +474,10 @@ void launch_se_from_power(hipStream_t s, unsigned blocks, const double *power, f
 {
     hipLaunchKernelGGL(ranenv_se_from_power_kernel, dim3(blocks), dim3(256), 0, s, power, se, n, tx_per_rb, noise);
 }
-void launch_head(hipStream_t s, dim3 grid, dim3 block, const KP &kp) { hipLaunchKernelGGL(ranenv_head_kernel, grid, block, 0, s, kp); }
+void launch_head(hipStream_t s, dim3 grid, dim3 block, const KP &kp, double *head_acc, int reset)
+{
+    hipLaunchKernelGGL(ranenv_head_kernel, grid, block, 0, s, kp, head_acc, reset);
+}
 void launch_advance(hipStream_t s, unsigned n_envs, const AdvanceArgs &a) { hipLaunchKernelGGL(ranenv_advance_kernel, dim3(n_envs), dim3(64), 0, s, a); }
 void launch_idle_traffic(hipStream_t s, unsigned n_eps, const ranenv_episode *eps, const int32_t *pool, int U, const int32_t *lane_slice,
                          const int32_t *lane_ue, int *violations)

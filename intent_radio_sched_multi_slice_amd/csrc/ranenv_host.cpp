@@ -94,6 +94,15 @@ struct ranenv {
     PolicyNet val_inter{}, val_intra{};
     bool val_on = false, val_has_intra = false;
     float *d_val_w = nullptr; long long val_cap = 0;
+    // head policies (ranenv_set_head_policy_network / _value_network): SchedTWC / SchedColORAN's actor and critic on the head observation,
+    // packed in buffers of their own; the scores share d_net_scores (one policy acts at a time)
+    PolicyNet head_net{}, head_val{};
+    bool head_on = false, head_val_on = false;
+    int head_dist = 0, head_stochastic = 0; unsigned long long head_seed = 0;
+    float *d_head_w = nullptr; long long head_cap = 0;
+    float *d_head_val_w = nullptr; long long head_val_cap = 0;
+    float *d_head_log_std = nullptr;
+    double *d_head_acc = nullptr, *d_head_ep_acc = nullptr;      // episode sums of the two head rewards [B][2], their log [B][ep_slots][2]
     int collect_split = -1;        // option "collect_split": the critic of ranenv_collect in a launch of its own (1), fused behind the actor (0), -1 = by weight size
     // options (the table `options` below, include/ranenv.h "Options")
     bool compact_enabled = true;                // option "compact"
@@ -313,7 +322,9 @@ hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t strea
     const hipError_t pe = prof_events(h, n, MODE == MODE_STEP ? kp.n_tti : 1, &ev0, &ev1);
     if (pe != hipSuccess) return pe;
     (void)launch_step(p.l, p.grid, p.block, stream, ev0, ev1, ks);
-    if (kp.head_obs || kp.head_reward) launch_head(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp);
+    if (kp.head_obs || kp.head_reward)
+        launch_head(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp, (h->kp.acc && h->kp.head_reward) ? h->d_head_acc : nullptr,
+                    MODE == MODE_RESET ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -433,6 +444,8 @@ AdvanceArgs advance_args(ranenv_handle h, const uint8_t *dev_done, float *obs_in
     a.e0 = 0;
     a.cls_flag = h->d_cls_flag;
     a.acc = h->kp.acc; a.ep_acc = h->d_ep_acc; a.ep_n = h->d_ep_n; a.ep_slots = h->ep_slots;
+    const bool head_sums = h->kp.acc && h->kp.head_reward && h->d_head_acc && h->d_head_ep_acc;
+    a.head_acc = head_sums ? h->d_head_acc : nullptr; a.head_ep_acc = head_sums ? h->d_head_ep_acc : nullptr;
     return a;
 }
 
@@ -1071,7 +1084,7 @@ int ranenv_set_episodes(ranenv_handle h, const ranenv_episode *eps, void *stream
 int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (policy < RANENV_POLICY_EXTERNAL || policy > RANENV_POLICY_NETWORK) return fail(h, RANENV_E_INVALID, "unknown policy %d", policy);
+    if (policy < RANENV_POLICY_EXTERNAL || policy > RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_INVALID, "unknown policy %d", policy);
     if (!(fixed_intra == RANENV_INTRA_RR || fixed_intra == RANENV_INTRA_PF || fixed_intra == RANENV_INTRA_MT || fixed_intra == RANENV_INTRA_PER_SLICE))
         return fail(h, RANENV_E_INVALID, "unknown intra-slice scheduler %d", fixed_intra);
     h->kp.policy = policy; h->kp.fixed_intra = fixed_intra;
@@ -1080,20 +1093,21 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra)
 
 // ---- policy networks (RANENV_POLICY_NETWORK) --------------------------------------------------------------------------------
 // Validate one ranenv_mlp against the handle's sizes and lay it out in the packed buffer from float `off` on (widths padded to 32).
-static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNet &net, long long &off, bool critic = false)
+// head_out > 0: a head net (input the head observation [10*S], `head_out` outputs).
+static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNet &net, long long &off, bool critic = false, int head_out = 0)
 {
     const int S = h->cfg.n_slices, Us = h->cfg.max_ues_slice;
-    const char *who = critic ? (intra ? "intra value" : "inter value") : (intra ? "intra" : "inter");
+    const char *who = head_out ? (critic ? "head value" : "head") : critic ? (intra ? "intra value" : "inter value") : (intra ? "intra" : "inter");
     if (m->n_hidden < 1 || m->n_hidden > NET_MAX_LAYERS - 1) return fail(h, RANENV_E_INVALID, "%s net: %d hidden layers (1..%d)", who, m->n_hidden, NET_MAX_LAYERS - 1);
     if (m->activation != RANENV_ACT_TANH && m->activation != RANENV_ACT_RELU) return fail(h, RANENV_E_INVALID, "%s net: unknown activation %d", who, m->activation);
     int in_dim = 10 * S;
-    if (!intra && m->input_layout != RANENV_NET_IN_OBS) return fail(h, RANENV_E_INVALID, "inter net: input layout %d (only RANENV_NET_IN_OBS)", m->input_layout);
+    if (!intra && m->input_layout != RANENV_NET_IN_OBS) return fail(h, RANENV_E_INVALID, "%s net: input layout %d (only RANENV_NET_IN_OBS)", who, m->input_layout);
     if (intra) {
         if (m->input_layout == RANENV_NET_IN_OBS) in_dim = 2 * Us + 9;
         else if (m->input_layout == RANENV_NET_IN_MASK_OBS) in_dim = 3 * Us + 9;
         else return fail(h, RANENV_E_INVALID, "intra net: unknown input layout %d", m->input_layout);
     }
-    const int out_dim = critic ? 1 : (intra ? 3 : 2 * S), L = m->n_hidden + 1;
+    const int out_dim = head_out ? head_out : (critic ? 1 : (intra ? 3 : 2 * S)), L = m->n_hidden + 1;
     if (m->dims[0] != in_dim) return fail(h, RANENV_E_INVALID, "%s net: input width %d, the observation has %d", who, m->dims[0], in_dim);
     for (int i = 1; i < L; i++)
         if (m->dims[i] < 1 || m->dims[i] > NET_MAX_WIDTH) return fail(h, RANENV_E_INVALID, "%s net: hidden width %d (1..%d)", who, m->dims[i], NET_MAX_WIDTH);
@@ -1126,6 +1140,12 @@ static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, 
 // in front of the TTI, 0 = not this policy / caller scores, < 0 = error.
 static int net_use(ranenv_handle h, KP &kp)
 {
+    if (!kp.scores && h->kp.policy == RANENV_POLICY_HEAD_NETWORK) {
+        if (!h->head_on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
+        if (!h->kp.head_obs) return fail(h, RANENV_E_STATE, "the head policy network reads dev_obs_head: none is bound (ranenv_bind_head_outputs)");
+        kp.scores = h->d_net_scores;
+        return 1;
+    }
     if (kp.scores || h->kp.policy != RANENV_POLICY_NETWORK) return 0;
     if (!h->net_on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
     if (!kp.obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
@@ -1147,9 +1167,30 @@ static PolicyIO net_io(ranenv_handle h, const KP &kp)
     return io;
 }
 
+static HeadIO head_io(ranenv_handle h)
+{
+    HeadIO io{};
+    io.B = h->cfg.batch; io.S = h->cfg.n_slices; io.dist = h->head_dist;
+    io.stochastic = h->head_stochastic; io.env_id_base = h->kp.env_id_base; io.seed = h->head_seed;
+    io.obs_head = h->kp.head_obs; io.log_std = h->head_dist == RANENV_HEAD_DIST_GAUSS_CLIP ? h->d_head_log_std : nullptr;
+    io.episode_no = ST_episode_no(h->kp); io.step_no = ST_step_no(h->kp);
+    io.scores = h->d_net_scores;
+    return io;
+}
+
 static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
 {
+    if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return launch_head_policy(s, h->head_net, head_io(h), e0, n);
     return launch_policy(s, h->net_inter, h->net_has_intra ? &h->net_intra : nullptr, net_io(h, kp), e0, n);
+}
+
+// The buffers the nets' actions go to and the step reads them from (IBSched nets and head nets share them: one policy acts at a time)
+static int net_action_buffers(ranenv_handle h)
+{
+    if (h->d_net_scores) return RANENV_OK;
+    const size_t BS = (size_t)h->cfg.batch * h->cfg.n_slices;
+    const int rc = dev_alloc(h, &h->d_net_scores, BS);
+    return rc == RANENV_OK ? dev_alloc(h, &h->d_net_intra, BS) : rc;
 }
 
 int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed, void *stream_)
@@ -1163,12 +1204,8 @@ int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ra
     if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream_;
-    const size_t BS = (size_t)h->cfg.batch * h->cfg.n_slices;
-    if (!h->d_net_scores) {
-        rc = dev_alloc(h, &h->d_net_scores, BS);
-        if (rc == RANENV_OK) rc = dev_alloc(h, &h->d_net_intra, BS);
-        if (rc != RANENV_OK) return rc;
-    }
+    rc = net_action_buffers(h);
+    if (rc != RANENV_OK) return rc;
     if (off > h->net_cap) {
         // (the launches of earlier TTIs may still read the old buffer: it stays allocated until ranenv_destroy)
         rc = dev_alloc(h, &h->d_net_w, (size_t)off);
@@ -1189,8 +1226,8 @@ int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ra
 int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra)
 {
     if (!h || !dev_scores || !dev_intra) return fail(h, RANENV_E_INVALID, "null argument");
-    if (!h->net_on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
-    *dev_scores = h->d_net_scores; *dev_intra = h->net_has_intra ? h->d_net_intra : nullptr;
+    if (!h->net_on && !h->head_on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
+    *dev_scores = h->d_net_scores; *dev_intra = (h->net_on && h->net_has_intra) ? h->d_net_intra : nullptr;
     return RANENV_OK;
 }
 
@@ -1221,6 +1258,60 @@ int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ran
     if (rc == RANENV_OK && intra) rc = net_copy(h, intra, na, s, h->d_val_w);
     if (rc != RANENV_OK) return rc;
     h->val_inter = ni; h->val_intra = na; h->val_has_intra = intra != nullptr; h->val_on = true;
+    return RANENV_OK;
+}
+
+// One head net into its packed buffer (grown when needed; the old one stays allocated until ranenv_destroy: launches of earlier
+// calls may still read it)
+static int head_net_bind(ranenv_handle h, const ranenv_mlp *m, PolicyNet &net, long long off, float **buf, long long *cap, hipStream_t s)
+{
+    if (off > *cap) {
+        const int rc = dev_alloc(h, buf, (size_t)off);
+        if (rc != RANENV_OK) return rc;
+        *cap = off;
+    } else {
+        HIP_TRY(h, hipMemsetAsync(*buf, 0, sizeof(float) * (size_t)off, s));
+    }
+    net.w = *buf;
+    return net_copy(h, m, net, s, *buf);
+}
+
+int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int32_t dist, const float *dev_log_std, int32_t stochastic,
+                                   uint64_t seed, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!actor) return fail(h, RANENV_E_INVALID, "the head actor is required");
+    if (dist != RANENV_HEAD_DIST_GAUSS_CLIP && dist != RANENV_HEAD_DIST_GAUSS_TANH) return fail(h, RANENV_E_INVALID, "unknown head distribution %d", dist);
+    if (dist == RANENV_HEAD_DIST_GAUSS_CLIP && !dev_log_std) return fail(h, RANENV_E_INVALID, "GAUSS_CLIP needs dev_log_std [S]");
+    if (dist == RANENV_HEAD_DIST_GAUSS_TANH && dev_log_std) return fail(h, RANENV_E_INVALID, "GAUSS_TANH takes log_std from the net: dev_log_std must be NULL");
+    const int S = h->cfg.n_slices;
+    PolicyNet net{};
+    long long off = 0;
+    int rc = net_layout(h, actor, false, net, off, false, dist == RANENV_HEAD_DIST_GAUSS_TANH ? 2 * S : S);
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream_;
+    rc = net_action_buffers(h);
+    if (rc == RANENV_OK && !h->d_head_log_std) rc = dev_alloc(h, &h->d_head_log_std, (size_t)S);
+    if (rc == RANENV_OK) rc = head_net_bind(h, actor, net, off, &h->d_head_w, &h->head_cap, s);
+    if (rc != RANENV_OK) return rc;
+    if (dev_log_std) HIP_TRY(h, hipMemcpyAsync(h->d_head_log_std, dev_log_std, sizeof(float) * (size_t)S, hipMemcpyDeviceToDevice, s));
+    h->head_net = net; h->head_dist = dist; h->head_stochastic = stochastic != 0; h->head_seed = seed; h->head_on = true;
+    return RANENV_OK;
+}
+
+int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!critic) return fail(h, RANENV_E_INVALID, "the head critic is required");
+    PolicyNet net{};
+    long long off = 0;
+    int rc = net_layout(h, critic, false, net, off, true, 1);
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    rc = head_net_bind(h, critic, net, off, &h->d_head_val_w, &h->head_val_cap, (hipStream_t)stream_);
+    if (rc != RANENV_OK) return rc;
+    h->head_val = net; h->head_val_on = true;
     return RANENV_OK;
 }
 
@@ -1522,6 +1613,7 @@ struct Rollout {
     AdvanceArgs adv{};
     KP kpr{};
     const ranenv_trajectory *rec = nullptr;      // ranenv_collect: the record (null: a plain rollout)
+    const ranenv_head_trajectory *hrec = nullptr;   // ranenv_collect_head: the record
 };
 
 // TTIs from now until the first episode of envs [lo, hi) ends, that TTI included, between 1 and n.  `n_ends`: at how many different
@@ -1578,6 +1670,14 @@ static int rollout_persistent(ranenv_handle h, Rollout &r, hipStream_t stream)
 
 constexpr long long COLLECT_FUSED_MAX_BYTES = 3ll << 20;      // actor + critic weights that share an XCD's 4 MB of L2 with the activations' traffic
 
+static int collect_split_of(ranenv_handle h, const PolicyNet &a, const PolicyNet *v)
+{
+    if (!v) return 0;
+    if (h->collect_split >= 0) return h->collect_split;
+    auto floats = [](const PolicyNet &x) { return x.b_off[x.n_layers - 1] + x.np[x.n_layers - 1] - x.w_off[0]; };
+    return (floats(a) + floats(*v)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
+}
+
 // ranenv_collect: TTI `t` of a partition's own count for envs [e0, e0 + n) on `s`.  The recording policy launches (actors, record,
 // critics) write slot t; the step writes its reward row and done flag straight into slot t (the kernels index them by env; the
 // reset behind an episode end writes neither, reset_behind), and the advance kernel reads that slot's flags.  Behind the call's
@@ -1605,12 +1705,7 @@ static hipError_t collect_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0
     const PolicyNet *intra = ia ? &h->net_intra : nullptr, *vinter = vc ? &h->val_inter : nullptr, *vintra = ic ? &h->val_intra : nullptr;
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
     // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").
-    auto split = [&](const PolicyNet &a, const PolicyNet *v) {
-        if (!v) return 0;
-        if (h->collect_split >= 0) return h->collect_split;
-        auto floats = [](const PolicyNet &x) { return x.b_off[x.n_layers - 1] + x.np[x.n_layers - 1] - x.w_off[0]; };
-        return (floats(a) + floats(*v)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
-    };
+    auto split = [&](const PolicyNet &a, const PolicyNet *v) { return collect_split_of(h, a, v); };
     rec.split = split(h->net_inter, vinter) | (ia ? split(h->net_intra, vintra) << 1 : 0);
     hipError_t le = launch_policy_collect(s, h->net_inter, intra, vinter, vintra, io, rec, e0, n);
     if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
@@ -1620,6 +1715,32 @@ static hipError_t collect_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0
     last.vf = tr.vf + (ts + 1) * B * (S + 1);
     last.intra_critic = rec.intra_critic; last.critic_only = 1;
     return launch_policy_collect(s, h->net_inter, intra, vinter, vintra, io, last, e0, n);
+}
+
+// ranenv_collect_head: the same for the head actor and critic.  The head kernel behind the step writes its reward pair straight into
+// slot t (the reset behind an episode end writes none), the step its done flag.
+static hipError_t collect_head_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
+{
+    const ranenv_head_trajectory &tr = *r.hrec;
+    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, ts = (size_t)t;
+    const bool vc = tr.vf != nullptr;
+    HeadRec rec{};
+    rec.obs_head = tr.obs_head ? tr.obs_head + ts * B * 10 * S : nullptr;
+    rec.action = tr.action ? tr.action + ts * B * S : nullptr;
+    rec.logp = tr.logp ? tr.logp + ts * B : nullptr;
+    rec.vf = vc ? tr.vf + ts * B : nullptr;
+    if (tr.reward_head) kpk.head_reward = tr.reward_head + ts * B * 2;
+    if (tr.done) kpk.done = tr.done + ts * B;
+    const HeadIO io = head_io(h);
+    const PolicyNet *critic = vc ? &h->head_val : nullptr;
+    rec.split = collect_split_of(h, h->head_net, critic);
+    hipError_t le = launch_head_policy_collect(s, h->head_net, critic, io, rec, e0, n);
+    if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
+    if (le == hipSuccess) le = follow_episode_ends(h, r, e0, n, 1, s, kpk.done);
+    if (le != hipSuccess || t + 1 < r.n_steps || !vc) return le;
+    HeadRec last{};
+    last.vf = tr.vf + (ts + 1) * B; last.critic_only = 1;
+    return launch_head_policy_collect(s, h->head_net, critic, io, last, e0, n);
 }
 
 // Every partition walks through the TTIs in launches of its own, on its own stream
@@ -1664,6 +1785,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
             kpk.n_tti = n_tti;
             h->last_rollout_launches++;
             if (r.rec) return collect_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
+            if (r.hrec) return collect_head_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
             hipError_t le = r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
             if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
             if (le != hipSuccess) return le;
@@ -1677,7 +1799,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
 
 // ranenv_rollout, and with `traj` ranenv_collect (gamma / lambda: its GAE pass)
 static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream_,
-                       const ranenv_trajectory *traj, double gamma, double lambda)
+                       const ranenv_trajectory *traj, double gamma, double lambda, const ranenv_head_trajectory *htraj = nullptr, int reward_col = 0)
 {
     int rc = check_ready(h, nullptr, nullptr, true);
     if (rc != RANENV_OK) return rc;
@@ -1696,7 +1818,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
     r.net = net_use(h, r.kp);
     if (r.net < 0) return r.net;
-    r.rec = traj;
+    r.rec = traj; r.hrec = htraj;
     rc = compact_for(h, r.kp, stream, &r.kp.compact);
     if (rc != RANENV_OK) return rc;
     if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_plan)
@@ -1735,7 +1857,19 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
             HIP_TRY(h, hipMemcpyAsync(reward, traj->reward + last * B * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
         if (traj->done && done) HIP_TRY(h, hipMemcpyAsync(done, traj->done + last * B, B, hipMemcpyDeviceToDevice, stream));
         if (traj->adv || traj->vtarg) {
-            launch_gae(stream, n_steps, h->cfg.batch, (int)C, traj->reward, traj->vf, traj->done, gamma, lambda, traj->adv, traj->vtarg);
+            launch_gae(stream, n_steps, h->cfg.batch, (int)C, traj->reward, (int)C, traj->vf, traj->done, gamma, lambda, traj->adv, traj->vtarg);
+            HIP_TRY(h, hipGetLastError());
+        }
+    }
+    if (htraj) {
+        // The bound head rewards and the caller's done hold the last TTI's values, as after a rollout
+        const size_t B = (size_t)h->cfg.batch, last = (size_t)n_steps - 1;
+        if (htraj->reward_head && h->kp.head_reward)
+            HIP_TRY(h, hipMemcpyAsync(h->kp.head_reward, htraj->reward_head + last * B * 2, sizeof(double) * B * 2, hipMemcpyDeviceToDevice, stream));
+        if (htraj->done && done) HIP_TRY(h, hipMemcpyAsync(done, htraj->done + last * B, B, hipMemcpyDeviceToDevice, stream));
+        if (htraj->adv || htraj->vtarg) {
+            launch_gae(stream, n_steps, h->cfg.batch, 1, htraj->reward_head + reward_col, 2, htraj->vf, htraj->done, gamma, lambda, htraj->adv,
+                       htraj->vtarg);
             HIP_TRY(h, hipGetLastError());
         }
     }
@@ -1767,6 +1901,25 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
     return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, traj, gamma, lambda);
 }
 
+static_assert(sizeof(ranenv_head_trajectory) == RANENV_HEAD_TRAJECTORY_BYTES, "ranenv_head_trajectory: 8 device pointers");
+
+int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, int32_t reward_col, double gamma, double lambda,
+                        float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!traj) return fail(h, RANENV_E_INVALID, "null trajectory");
+    if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
+    if (reward_col != 0 && reward_col != 1) return fail(h, RANENV_E_INVALID, "reward_col %d (0 = SchedTWC, 1 = SchedColORAN)", reward_col);
+    if ((traj->adv || traj->vtarg) && !(traj->reward_head && traj->vf && traj->done))
+        return fail(h, RANENV_E_INVALID, "adv / vtarg need the record's reward_head, vf and done");
+    if (h->kp.policy != RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect_head needs policy HEAD_NETWORK (ranenv_set_policy)");
+    if (!h->head_on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
+    if (h->head_dist != RANENV_HEAD_DIST_GAUSS_CLIP)
+        return fail(h, RANENV_E_INVALID, "only GAUSS_CLIP (PPO) head policies collect: SAC is off-policy and records no log-probabilities");
+    if (!h->head_val_on) return fail(h, RANENV_E_STATE, "no head value network bound (ranenv_set_head_value_network)");
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, nullptr, gamma, lambda, traj, reward_col);
+}
+
 int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,
                double lambda, float *adv, float *vtarg, void *stream)
 {
@@ -1774,9 +1927,19 @@ int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *r
     if (n_steps < 1 || n_cols < 1) return fail(h, RANENV_E_INVALID, "n_steps and n_cols must be >= 1");
     if (!reward || !vf || !done) return fail(h, RANENV_E_INVALID, "GAE reads reward, vf and done");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    launch_gae((hipStream_t)stream, n_steps, h->cfg.batch, n_cols, reward, vf, done, gamma, lambda, adv, vtarg);
+    launch_gae((hipStream_t)stream, n_steps, h->cfg.batch, n_cols, reward, n_cols, vf, done, gamma, lambda, adv, vtarg);
     HIP_TRY(h, hipGetLastError());
     return RANENV_OK;
+}
+
+// Episode sums of the two head rewards: they exist once episode metrics are enabled AND head rewards are bound; whichever call
+// completes the pair allocates (zeroed).
+static int head_sums_alloc(ranenv_handle h)
+{
+    if (!h->kp.acc || !h->kp.head_reward || h->d_head_acc) return RANENV_OK;
+    const size_t B = (size_t)h->cfg.batch;
+    if (h->ep_slots > 0 && dev_alloc(h, &h->d_head_ep_acc, B * (size_t)h->ep_slots * 2) != RANENV_OK) return RANENV_E_NOMEM;
+    return dev_alloc(h, &h->d_head_acc, B * 2);
 }
 
 int ranenv_enable_metrics(ranenv_handle h, int32_t episode_slots, void *stream_)
@@ -1797,6 +1960,18 @@ int ranenv_enable_metrics(ranenv_handle h, int32_t episode_slots, void *stream_)
     HIP_TRY(h, hipMemsetAsync(h->d_ep_n, 0, sizeof(int32_t) * B, stream));
     if (h->d_ep_acc) HIP_TRY(h, hipMemsetAsync(h->d_ep_acc, 0, sizeof(double) * B * (size_t)h->ep_slots * 8, stream));
     h->kp.acc = h->d_acc;
+    if (head_sums_alloc(h) != RANENV_OK) return RANENV_E_NOMEM;
+    if (h->d_head_acc) HIP_TRY(h, hipMemsetAsync(h->d_head_acc, 0, sizeof(double) * B * 2, stream));
+    if (h->d_head_ep_acc) HIP_TRY(h, hipMemsetAsync(h->d_head_ep_acc, 0, sizeof(double) * B * (size_t)h->ep_slots * 2, stream));
+    return RANENV_OK;
+}
+
+int ranenv_get_head_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t *episode_slots)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (dev_running) *dev_running = h->d_head_acc;
+    if (dev_episode_log) *dev_episode_log = h->d_head_ep_acc;
+    if (episode_slots) *episode_slots = h->d_head_acc ? h->ep_slots : 0;
     return RANENV_OK;
 }
 
@@ -1985,7 +2160,8 @@ int ranenv_bind_head_outputs(ranenv_handle h, float *dev_obs_head, double *dev_r
     if ((dev_obs_head || dev_reward_head) && (h->cfg.flags & RANENV_F_NO_RAW_OUTPUT))
         return fail(h, RANENV_E_STATE, "the heads read pkt_throughputs: not available with RANENV_F_NO_RAW_OUTPUT");
     h->kp.head_obs = dev_obs_head; h->kp.head_reward = dev_reward_head;
-    return RANENV_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return head_sums_alloc(h);
 }
 
 int ranenv_set_slice_usecase(ranenv_handle h, int32_t first, int32_t count, const int32_t *usecase, void *stream_)

@@ -162,6 +162,7 @@ struct AdvanceArgs {
     int e0;                                       // first env of this launch (batch partitions)
     int *cls_flag;                                // set when an env restarts: the class lists of the mixed / persistent launches are stale
     const double *acc; double *ep_acc; int32_t *ep_n; int ep_slots;   // episode metrics: running sums -> per-episode log
+    const double *head_acc; double *head_ep_acc;                      // ... and the head rewards' pair [B][2] -> [B][ep_slots][2] (null: none)
 };
 
 // Policy network (ranenv_policy.hip): one MLP as packed in the handle's buffer.  Every width is padded with zeros to a multiple of
@@ -202,6 +203,27 @@ struct PolicyRec {
 hipError_t launch_policy_collect(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyNet *vinter, const PolicyNet *vintra,
                                  const PolicyIO &, const PolicyRec &, int e0, int n_envs);
 size_t policy_lds_bytes(const PolicyNet &);
+// Head policies (RANENV_POLICY_HEAD_NETWORK): one row per env, input the bound head observation, scores into the handle's score buffer
+struct HeadIO {
+    int B, S;
+    int dist;                             // RANENV_HEAD_DIST_*
+    int stochastic, env_id_base;
+    unsigned long long seed;
+    const float *obs_head;                // [B][10*S] the bound head observation
+    const float *log_std;                 // [S] GAUSS_CLIP: the policy's state-independent parameter (null for GAUSS_TANH)
+    const int32_t *episode_no, *step_no;
+    double *scores;                       // [B][S]
+};
+// ranenv_collect_head: what the head policy launch of one TTI records, every pointer at that TTI's slot (null = not recorded)
+struct HeadRec {
+    float *obs_head; double *action;      // [B][10*S], [B][S] (unclamped)
+    float *logp, *vf;                     // [B]
+    int critic_only;                      // the pass behind the last TTI: vf of the observation as it stands
+    int split;                            // host side only: the critic runs as a launch of its own behind the actor's
+};
+hipError_t launch_head_policy(hipStream_t, const PolicyNet &actor, const HeadIO &, int e0, int n_envs);
+hipError_t launch_head_policy_collect(hipStream_t, const PolicyNet &actor, const PolicyNet *critic, const HeadIO &, const HeadRec &, int e0,
+                                      int n_envs);
 
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block
@@ -262,10 +284,13 @@ void launch_se_sidecar_from_power(hipStream_t, unsigned n_tiles, unsigned block,
 void launch_se_retile_quad(hipStream_t, unsigned blocks, const float *src, float *dst, long long n_quads, int U, int R);
 void launch_se_from_power(hipStream_t, unsigned blocks, const double *power, float *se, long long n, double tx_per_rb, double noise);
 void launch_ddiv_selftest(hipStream_t, const double *a, const double *b, double *fast, double *ieee, long long n);
-void launch_head(hipStream_t, dim3 grid, dim3 block, const KP &);
+// head_acc: the per-env running pair of the two head rewards [B][2] or null; reset != 0: the launch follows a reset (the pair of the
+// envs under the mask is zeroed), else a step (this TTI's rewards are added)
+void launch_head(hipStream_t, dim3 grid, dim3 block, const KP &, double *head_acc, int reset);
 void launch_advance(hipStream_t, unsigned n_envs, const AdvanceArgs &);
-void launch_gae(hipStream_t, int n_steps, int B, int n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,
-                double lambda, float *adv, float *vtarg);
+// reward_stride: doubles between two (env, column) entries' rewards' rows, i.e. reward[(t * B + b) * reward_stride + c] (n_cols: packed)
+void launch_gae(hipStream_t, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,
+                double gamma, double lambda, float *adv, float *vtarg);
 void launch_idle_traffic(hipStream_t, unsigned n_eps, const ranenv_episode *eps, const int32_t *pool, int U, const int32_t *lane_slice,
                          const int32_t *lane_ue, int *violations);
 

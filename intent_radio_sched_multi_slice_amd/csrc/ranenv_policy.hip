@@ -9,6 +9,8 @@
 // 16 x 16, four independent accumulators.  Per 16 k: one float4 of W per lane and block column (lane l: row c = l & 15 of the block,
 // k = 4 (l >> 4) .. + 3), one float4 of X per block row from LDS, 16 MFMAs -- MFMA j of the step sums k = 4q + j, the same
 // permutation on both operands.  The next W float4s are requested before the current step's MFMAs.
+// A third agent kind, "head" (RANENV_POLICY_HEAD_NETWORK: the SB3 actors of SchedTWC / SchedColORAN on the head observation), shares
+// the layer loop and has kernels of its own below.
 #include "ranenv_numeric.hpp"
 
 #include <mutex>
@@ -271,6 +273,118 @@ __global__ void __launch_bounds__(256) ranenv_policy_collect_kernel(PolicyNet ne
     policy_body<true>(net, vnet, io, rec, kind, e0, n_rows, lds);
 }
 
+// ---- head policies (RANENV_POLICY_HEAD_NETWORK): SchedTWC / SchedColORAN's SB3 actors ---------------------------------------------
+// One row per env: the row of the bound head observation [10*S], as the head kernel left it behind the previous TTI or reset,
+// through the same layer loop; an epilogue of its own.  No masking here: the step kernel applies the slice permutation and the
+// inactive-slice rule to these scores as it does to a caller's.
+constexpr unsigned HEAD_TAG = 0x48454100u;              // "HEA\0": counter word c3 of the head policy's Philox draws, + position
+
+template <bool REC>
+__device__ __forceinline__ void head_load_rows(const PolicyNet &net, const HeadIO &io, const HeadRec &rec, int e0, int row0, int n_rows, float *cur,
+                                               int tid)
+{
+    const int K0 = net.kp[0], ld0 = net_ld(K0), W = 10 * io.S;
+    for (int i = tid; i < NET_ROWS * K0; i += 256) {
+        const int r = i / K0, k = i - r * K0, g = row0 + r;
+        float v = 0.0f;
+        if (g < n_rows && k < W) {
+            v = io.obs_head[(size_t)(e0 + g) * (size_t)W + k];
+            if (REC && rec.obs_head) rec.obs_head[(size_t)(e0 + g) * (size_t)W + k] = v;
+        }
+        cur[r * ld0 + k] = v;
+    }
+}
+
+// REC (ranenv_collect_head): the same forward and epilogue -- the scores do not differ by a bit -- which also writes the TTI's record
+// (observation rows on their way into LDS, unclamped action, log-probability), then the critic `vnet` (n_layers 0 = none) on the
+// same 32 rows.
+template <bool REC>
+__device__ __forceinline__ void head_body(const PolicyNet &net, const PolicyNet &vnet, const HeadIO &io, const HeadRec &rec, int e0, int n_rows,
+                                          float *lds)
+{
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row0 = (int)blockIdx.x * NET_ROWS;
+    const int S = io.S;
+    int ldm = net_ld_max(net);
+    if (REC && vnet.n_layers > 0) { const int lv = net_ld_max(vnet); ldm = lv > ldm ? lv : ldm; }
+    float *cur = lds, *nxt = lds + NET_ROWS * ldm;
+
+    if (!REC || !rec.critic_only) {
+        head_load_rows<REC>(net, io, rec, e0, row0, n_rows, cur, tid);
+        __syncthreads();
+        net_layers(net, cur, nxt, lane, wave);
+
+        const int ld = net_ld(net.np[net.n_layers - 1]);
+        const unsigned k0 = (unsigned)io.seed, k1 = (unsigned)(io.seed >> 32);
+        const bool squash = io.dist == RANENV_HEAD_DIST_GAUSS_TANH;
+        double *zrow = (double *)nxt;                  // REC: the draws z [32][S] for the rows' log-probabilities (the idle LDS buffer)
+        for (int i = tid; i < NET_ROWS * S; i += 256) {
+            const int r = i / S, j = i - r * S, g = row0 + r;
+            if (g >= n_rows) continue;
+            const int e = e0 + g;
+            double a = (double)cur[r * ld + j], z = 0.0;
+            if (io.stochastic) {
+                double ls;
+                if (squash) {
+                    ls = (double)cur[r * ld + S + j];
+                    ls = ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls);
+                } else {
+                    ls = (double)io.log_std[j];
+                }
+                unsigned o[4];
+                philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], HEAD_TAG + (unsigned)j, k0, k1, o);
+                const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
+                z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+                a = a + exp(ls) * z;
+            }
+            io.scores[(size_t)e * S + j] = squash ? tanh(a) : (a < -1.0 ? -1.0 : (a > 1.0 ? 1.0 : a));
+            if (REC) {
+                if (rec.action) rec.action[(size_t)e * S + j] = a;
+                zrow[i] = z;
+            }
+        }
+        if (REC && rec.logp) {
+            __syncthreads();
+            for (int r = tid; r < NET_ROWS; r += 256) {
+                const int g = row0 + r;
+                if (g >= n_rows) continue;
+                double lp = 0.0;
+                for (int j = 0; j < S; j++) {
+                    const double z = zrow[r * S + j];
+                    lp += ((-0.5 * z) * z - (double)io.log_std[j]) - HALF_LN_2PI;
+                }
+                rec.logp[e0 + g] = (float)lp;
+            }
+        }
+    }
+
+    if (REC && rec.vf && vnet.n_layers > 0) {
+        __syncthreads();                               // (the epilogue read both buffers)
+        cur = lds; nxt = lds + NET_ROWS * ldm;
+        const HeadRec none{};
+        head_load_rows<false>(vnet, io, none, e0, row0, n_rows, cur, tid);
+        __syncthreads();
+        net_layers(vnet, cur, nxt, lane, wave);
+        const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
+        for (int r = tid; r < NET_ROWS; r += 256) {
+            const int g = row0 + r;
+            if (g < n_rows) rec.vf[e0 + g] = cur[r * ldv];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) ranenv_head_policy_kernel(PolicyNet net, HeadIO io, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    head_body<false>(net, net, io, HeadRec{}, e0, n_rows, lds);
+}
+
+__global__ void __launch_bounds__(256) ranenv_head_policy_collect_kernel(PolicyNet net, PolicyNet vnet, HeadIO io, HeadRec rec, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    head_body<true>(net, vnet, io, rec, e0, n_rows, lds);
+}
+
 }  // namespace
 
 namespace ranenv_dev {
@@ -326,6 +440,49 @@ hipError_t launch_policy_collect(hipStream_t s, const PolicyNet &inter, const Po
     };
     if (!rec.critic_only || vinter) kind_launch(0, inter, vinter, n_envs, (rec.split & 1) != 0);
     if (intra && (!rec.critic_only || vintra)) kind_launch(1, *intra, vintra, n_envs * io.S, (rec.split & 2) != 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_head_policy(hipStream_t s, const PolicyNet &actor, const HeadIO &io, int e0, int n_envs)
+{
+    static std::once_flag once;
+    static hipError_t attr = hipSuccess;
+    std::call_once(once, [] {
+        attr = hipFuncSetAttribute((const void *)ranenv_head_policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
+    });
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(ranenv_head_policy_kernel, dim3((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS)), dim3(256), policy_lds_bytes(actor), s, actor,
+                       io, e0, n_envs);
+    return hipGetLastError();
+}
+
+hipError_t launch_head_policy_collect(hipStream_t s, const PolicyNet &actor, const PolicyNet *critic, const HeadIO &io, const HeadRec &rec, int e0,
+                                      int n_envs)
+{
+    static std::once_flag once;
+    static hipError_t attr = hipSuccess;
+    std::call_once(once, [] {
+        attr = hipFuncSetAttribute((const void *)ranenv_head_policy_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
+    });
+    if (attr != hipSuccess) return attr;
+    const PolicyNet none{};               // (n_layers 0: no critic)
+    auto lds_of = [](const PolicyNet &a, const PolicyNet &v) {
+        const size_t x = policy_lds_bytes(a), y = v.n_layers > 0 ? policy_lds_bytes(v) : 0;
+        return x > y ? x : y;
+    };
+    const dim3 grid((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS));
+    // actor + critic fused, or -- split -- the actor's launch, then the critic alone (the kernel's critic_only mode)
+    if (!rec.split || rec.critic_only || !critic) {
+        const PolicyNet &v = critic ? *critic : none;
+        hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid, dim3(256), lds_of(actor, v), s, actor, v, io, rec, e0, n_envs);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid, dim3(256), lds_of(actor, none), s, actor, none, io, rec, e0, n_envs);
+    HeadRec crit{};
+    crit.vf = rec.vf; crit.critic_only = 1;
+    hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid, dim3(256), lds_of(actor, *critic), s, actor, *critic, io, crit, e0, n_envs);
     return hipGetLastError();
 }
 

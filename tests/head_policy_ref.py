@@ -1,0 +1,179 @@
+"""A float64 statement of RANENV_POLICY_HEAD_NETWORK with a rigorous error bound: the high-precision twin of
+``adapters.head_policy_actions`` / ``head_policy_logp``, built on ``policy_ref.mlp64`` (which gives every net output ``y`` a bound
+``t`` on its distance to ANY float32 evaluation of the same net).
+
+    gauss_clip   a = mean (+ exp(log_std) z);  score = clamp(a, -1, 1)
+                 log_std is a float32 parameter, exact in float64: the bound of a is t_mean (+ 1e-12 (1 + sd |z|), the double
+                 transcendental libraries, as in policy_ref.inter_epilogue)
+    gauss_tanh   ls = clamp(log_std, -20, 2), a = mu (+ exp(ls) z);  score = tanh(a)
+                 the bound of ls is t_log_std (the clamp is 1-Lipschitz), that of a is t_mu + sd |z| expm1(t_ls) (+ the same 1e-12 term)
+    clamp and tanh are 1-Lipschitz: the score's bound is that of a (+ 1e-12 for the double tanh), and exactly 0 where the clamp
+    saturates on both sides of the interval.
+    logp (gauss_clip)  sum over all S positions of ((-0.5 z) z - log_std) - 0.5 ln 2 pi: only z carries an error:
+                       1e-12 S (1 + max z^2) + 2^-24 |logp| (the record's single rounding to float32)
+    vf                 |vf - y| <= t + 2^-24 |y|
+
+Also the shared fixtures of the head-policy tests: nets in SB3's shapes whose output layer is scaled up so that the clamp, the tanh
+and SAC's log_std clamp are all exercised, and injected observations.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from tests import policy_ref as pr
+
+HEAD_TAG = 0x48454100
+HALF_LN_2PI = 0.9189385332046727
+NETS = {"64x64": ([64, 64], "tanh"), "256x256": ([256, 256], "relu"), "512x3": ([512, 512, 512], "tanh")}
+OUT_SCALE = 6.0           # on the output layer: |mean| crosses 1 and SAC's log_std leaves [-20, 2] on a good share of the rows
+
+
+def mlp(dims, act, seed, out_scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    mods = []
+    for i in range(len(dims) - 1):
+        lin = torch.nn.Linear(dims[i], dims[i + 1])
+        with torch.no_grad():
+            bound = 1.0 / np.sqrt(dims[i]) * (out_scale if i == len(dims) - 2 else 1.0)
+            lin.weight.copy_((torch.rand(lin.weight.shape, generator=g) * 2 - 1) * bound)
+            lin.bias.copy_((torch.rand(lin.bias.shape, generator=g) * 2 - 1) * bound)
+        mods.append(lin)
+        if i < len(dims) - 2:
+            mods.append(torch.nn.Tanh() if act == "tanh" else torch.nn.ReLU())
+    return torch.nn.Sequential(*mods)
+
+
+def head_nets(S, net, dist, seed=21):
+    """(actor, log_std or None, critic) for a net of NETS and a dist: the actor's output layer scaled by OUT_SCALE (larger scales
+    would push the float32 evaluations' own differences towards the 1e-5 the GPU tests allow against the restatement)."""
+    widths, act = NETS[net]
+    actor = mlp([10 * S] + widths + [S if dist == "gauss_clip" else 2 * S], act, seed, OUT_SCALE)
+    if dist == "gauss_tanh":       # the log_std half sits higher, so that a share of it lies above SAC's upper clamp at 2 for every net
+        with torch.no_grad():
+            actor[-1].bias[S:] += 1.0
+    g = torch.Generator().manual_seed(seed + 1)
+    log_std = ((torch.rand(S, generator=g) * 2 - 1) * 1.5).to(torch.float32) if dist == "gauss_clip" else None
+    critic = mlp([10 * S] + widths + [1], act, seed + 2)
+    return actor, log_std, critic
+
+
+def injected_head_obs(rng, B, S):
+    return pr.injected_inputs(rng, B, S, 1)[0]
+
+
+def layers_of(net):
+    from intent_radio_sched_multi_slice_amd.batched_env import policy_net_layers
+    return policy_net_layers(net)
+
+
+def noise(env_ids, episode, step, S, seed):
+    """z float64 [B, S] of the head policy's Philox counters."""
+    from intent_radio_sched_multi_slice_amd.adapters import philox4x32_10
+    col = lambda a: np.asarray(pr._np(a, np.int64), dtype=np.int64).reshape(-1, 1) & 0xFFFFFFFF  # noqa: E731
+    c3 = HEAD_TAG + np.arange(S, dtype=np.int64)[None, :]
+    d = philox4x32_10(col(env_ids), col(episode), col(step), c3, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    u1 = (d[0].astype(np.float64) + 1.0) * 2.0 ** -32
+    u2 = d[1].astype(np.float64) * 2.0 ** -32
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+
+
+class HeadRef:
+    """The float64 reference of one TTI's head actions.  ``actor``: a net as for policy_net_layers; ``z`` [B, S] (stochastic)."""
+
+    def __init__(self, head_obs, actor, dist, log_std=None, z=None, forward=None):
+        forward = forward or pr.mlp64
+        x = pr._np(head_obs, np.float32)
+        B, S = x.shape[0], x.shape[1] // 10
+        out, t = forward(x, *layers_of(actor))
+        if dist == "gauss_clip":
+            a, bound = out.copy(), t.copy()
+            ls, t_ls = np.broadcast_to(pr._np(log_std, np.float32).astype(np.float64), (B, S)), np.zeros((B, S))
+        else:
+            a, bound = out[:, :S].copy(), t[:, :S].copy()
+            ls, t_ls = np.clip(out[:, S:], -20.0, 2.0), t[:, S:]
+        if z is not None:
+            sd = np.exp(ls)
+            a = a + sd * z
+            bound = bound + sd * np.abs(z) * np.expm1(t_ls) + 1e-12 * (1.0 + sd * np.abs(z))
+        self.B, self.S = B, S
+        self.action, self.action_bound = a, bound
+        self.log_std, self.log_std_bound = ls, t_ls
+        if dist == "gauss_clip":
+            self.scores = np.clip(a, -1.0, 1.0)
+            self.score_bound = np.where(np.abs(a) - bound > 1.0, 0.0, bound)      # clamped on both sides: exactly -1 or 1
+        else:
+            self.scores = np.tanh(a)
+            self.score_bound = bound + 1e-12
+
+
+def logp_ref(log_std, z, B):
+    """(logp float64 [B], bound [B]) of gauss_clip's recorded log-probability."""
+    ls = pr._np(log_std, np.float32).astype(np.float64)
+    S = ls.shape[0]
+    zz = np.zeros((B, S)) if z is None else np.asarray(z, dtype=np.float64)
+    lp = (-0.5 * zz * zz - ls[None, :] - HALF_LN_2PI).sum(axis=1)
+    return lp, 1e-12 * S * (1.0 + np.max(zz * zz, axis=1)) + 2.0 ** -24 * np.abs(lp)
+
+
+def value_ref(head_obs, critic):
+    y, t = pr.mlp64(pr._np(head_obs, np.float32), *layers_of(critic))
+    return y[:, 0], t[:, 0] + 2.0 ** -24 * np.abs(y[:, 0])
+
+
+def check_scores(ref: HeadRef, scores, what=""):
+    """Every (env, position) of the device's scores within the bound; returns the worst error / bound ratio."""
+    sc = pr._np(scores)
+    err = np.abs(sc - ref.scores)
+    bad = ~(err <= ref.score_bound)
+    if bad.any():
+        b, j = np.argwhere(bad)[0]
+        raise AssertionError(f"{what}: {int(bad.sum())} scores outside the bound; first env {int(b)} position {int(j)}: device {sc[b, j]!r} "
+                             f"reference {ref.scores[b, j]!r} bound {ref.score_bound[b, j]:.3g}")
+    nz = ref.score_bound > 0
+    return float(np.max(err[nz] / ref.score_bound[nz])) if nz.any() else 0.0
+
+
+# ---- GPU fixtures -----------------------------------------------------------------------------------------------------------------
+SIZES = {"S10U100": dict(n_slices=10, n_ues=100, n_rbs=135, rbs_per_rbg=1, max_ues_slice=10),
+         "S5U25": dict(n_slices=5, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=10)}
+EPISODE_LENGTHS = (5, 7, 8, 12, 24, 6)      # per env, cyclic: episodes end at different TTIs, several at TTI 24
+
+
+def usecase_of(tables, seed=3):
+    return (np.random.default_rng(seed).integers(0, 4, tables.slice_active.shape) * (tables.slice_has_req != 0)).astype(np.int32)
+
+
+def make_env(size, net, dist, B, stochastic=True, seed=11, autoreset=False, parts=1, se_mode="stream", critic=True, metrics=None,
+             unsorted=True, trace_len=64, bind=True):
+    """A reset env with heads enabled under the head nets of (size, net, dist).  ``unsorted``: the scenario tables are reloaded with
+    sorted_slices = identity (SchedTWC's enable_sort_slices=False), else left sorted and bound with allow_sorted.  ``metrics``:
+    episode slots of enable_metrics (None: off).  autoreset: per-env episode lengths EPISODE_LENGTHS.
+    Returns (workload, env, (actor, log_std, critic))."""
+    from intent_radio_sched_multi_slice_amd import _lib
+    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
+    wl = make_mult_slice_workload(B, torch.device("cuda", 0), policy=_lib.POLICY_MAPF, intra=_lib.INTRA_RR, n_scenarios=8, n_traces=8,
+                                  trace_len=trace_len, max_steps=1000, **SIZES[size])
+    env = wl.env
+    if unsorted:
+        wl.tables.sorted_slices[...] = np.arange(env.S, dtype=np.int32)
+        env.load_scenarios(wl.tables)
+    env.set_se_mode(se_mode)
+    env.enable_heads(usecase_of(wl.tables))
+    actor, log_std, vnet = head_nets(env.S, net, dist)
+    if bind:
+        env.set_head_policy_network(actor, dist, log_std, stochastic=stochastic, seed=seed, allow_sorted=not unsorted)
+        if critic:
+            env.set_head_value_network(vnet)
+    if autoreset:
+        eps = env.episodes
+        env.set_episode_table(scenario=eps["scenario"], se_base=eps["se_base"], se_len=eps["se_len"], se_offset=eps["se_offset"],
+                              trf_base=eps["trf_base"], trf_len=eps["trf_len"], trf_offset=eps["trf_offset"])
+        env.set_max_steps(np.asarray(EPISODE_LENGTHS, dtype=np.int32)[np.arange(B) % len(EPISODE_LENGTHS)])
+        env.enable_autoreset(0, B, episode_numbers=np.arange(B, dtype=np.int32))
+    if metrics is not None:
+        env.enable_metrics(metrics)
+    if parts > 1:
+        env.set_partitions(parts)
+    env.reset()
+    return wl, env, (actor, log_std, vnet)
