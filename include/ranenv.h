@@ -462,6 +462,40 @@ int ranenv_enable_metrics(ranenv_handle h, int32_t episode_slots, void *stream);
 int ranenv_get_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t **dev_episodes_done,
                        int32_t *episode_slots);
 
+/* Per-slice episode metrics on the device: what the paper's per-slice figures derive per TTI from the history files
+ * (results/gen_results.py:236-259,550-625 via calc_slice_violations(..., slice_per_metric=True) :874-970, distance :1007-1018 and
+ * calc_total_throughput :791-809), kept per (env, slice) so that a whole evaluation needs no per-TTI read-back.  A small kernel
+ * behind every step adds this TTI's share to running [B][S][RANENV_SLICE_METRIC_COLS] float64; s is the slice INDEX (not the
+ * sorted position), and which slice type sits at an index differs from scenario to scenario.  Columns:
+ *   [0] active_ttis      1 if the slice is active (slice_active of its scenario row: basestation_slice_assoc, :901-905)
+ *   [1] violations       1 if active and the minimum drift over the declared metrics < 0 (:925,951-956)
+ *   [2] viol_throughput  [3] viol_reliability  [4] viol_latency
+ *                        1 if active, that metric is declared and its drift < 0 (:927-949; order = RANENV_METRIC_*)
+ *   [5] distance         min(minimum declared drift, 0) if active (:1007-1018)
+ *   [6] pkts_incoming  [7] pkts_capacity  [8] pkts_sent  [9] pkts_dropped
+ *                        sums of pkt_incoming, pkt_throughputs, pkt_effective_thr, dropped_pkts over the slice's UEs (integers, exact)
+ * An inactive slice may have UEs, a request and therefore a drift: it counts nowhere in [0]..[5].
+ * Sources: nothing of the intent-drift arithmetic is repeated.  The minimum declared drift is the step's float64 dev_reward[e][s+1];
+ * the per-metric drifts and their declared flags are the step's float32 dev_obs_intra[e][s][0..2] and [3..5].  The sign of a float32
+ * drift equals that of the float64 one unless |drift| < 1.4e-45 (it then rounds to zero and is no violation in [2]..[4], while [1]
+ * still sees the float64 sign).  One writer per cell and TTI, TTIs in stream order: the sums are bit for bit the same whatever the
+ * launch path (step, ranges, partitions, rollout, collect), and [1], [8], [9] summed over the slices equal sums [2], [6], [7] above.
+ * Rules:
+ *   - the episode slots are those of ranenv_enable_metrics: ranenv_enable_slice_metrics without it is RANENV_E_STATE;
+ *     ranenv_enable_metrics(h, slots >= 0, ...) while slice metrics are on zeroes both kinds; slots < 0 switches both off;
+ *   - a handle with RANENV_F_NO_RAW_OUTPUT cannot enable them (RANENV_E_INVALID): [6] and [7] read the raw outputs;
+ *   - while on, a step, rollout or collect call without dev_reward or dev_obs_intra is RANENV_E_INVALID;
+ *   - while on, ranenv_rollout runs one TTI per launch and takes no persistent launch, as with bound head outputs (option
+ *     "last_rollout_persistent" reads 0); switched off, every call enqueues exactly what it enqueues without this feature;
+ *   - a reset (masked resets included) zeroes the rows of the envs it resets.  Under auto-reset a finished episode's [S][10] block is
+ *     appended to episode_log [B][slots][S][10] at the slot of the 8-sum log, and the scenario-pool row the episode was played on
+ *     to episode_scenario [B][slots] (int32; -1 = nothing logged there yet); episodes beyond the slots are only counted.
+ * ranenv_get_slice_metrics returns device pointers (the two logs NULL with 0 slots) and the column count. */
+#define RANENV_SLICE_METRIC_COLS 10
+int ranenv_enable_slice_metrics(ranenv_handle h, int32_t enable, void *stream);
+int ranenv_get_slice_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t **dev_episode_scenario,
+                             int32_t *n_cols);
+
 int ranenv_get_views(ranenv_handle h, ranenv_views *out);
 
 /* Offered traffic drawn on the device instead of replayed from the traffic pool: for every UE of a slice with

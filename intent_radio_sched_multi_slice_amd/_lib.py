@@ -20,6 +20,7 @@ NET_MAX_HIDDEN, NET_MAX_WIDTH = 4, 512
 INTRA_RR, INTRA_PF, INTRA_MT, INTRA_PER_SLICE = 0, 1, 2, 255
 F_CLEAR_HISTORY_ON_RESET, F_NO_RAW_OUTPUT, F_SYNC_CHECK, F_SCALE_PER_ELEMENT = 0x1, 0x2, 0x4, 0x8
 SE_STREAM, SE_GATHER = 0, 1
+SLICE_METRIC_COLS = 10
 
 class RanEnvError(RuntimeError):
     pass
@@ -150,6 +151,8 @@ FUNCTIONS = {
     "ranenv_set_head_value_network": (C.c_int, [_P, C.POINTER(Mlp), _P]),
     "ranenv_get_head_metrics": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "ranenv_collect_head": (C.c_int, [_P, _I32, C.POINTER(HeadTrajectory), _I32, _F64, _F64] + [_P] * 5),
+    "ranenv_enable_slice_metrics": (C.c_int, [_P, _I32, _P]),
+    "ranenv_get_slice_metrics": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
 }
 EXPORTS = tuple(FUNCTIONS)
 

@@ -911,9 +911,48 @@ class BatchedRanEnv:
         With auto-reset a finished episode's sums are appended to the env's log of ``episode_slots`` rows."""
         self._check(self._lib.ranenv_enable_metrics(self._h, int(episode_slots), self._stream()), "ranenv_enable_metrics")
         self._metric_views = None
+        self._slice_metric_views = None
 
     def disable_metrics(self) -> None:
+        """Switches the episode metrics off, the per-slice ones with them."""
         self._check(self._lib.ranenv_enable_metrics(self._h, -1, self._stream()), "ranenv_enable_metrics")
+        self._slice_metrics_on = False
+
+    SLICE_METRIC_NAMES = ("active_ttis", "violations", "viol_throughput", "viol_reliability", "viol_latency", "distance",
+                          "pkts_incoming", "pkts_capacity", "pkts_sent", "pkts_dropped")
+
+    def enable_slice_metrics(self) -> None:
+        """Per-(env, slice) running sums over the TTIs of the current episode, kept by a small kernel behind every step
+        (include/ranenv.h "Per-slice episode metrics": the per-slice quantities of results/gen_results.py:874-970, :791-809,
+        :1007-1018; columns as SLICE_METRIC_NAMES, slices in index order).  Needs enable_metrics() first: the episode slots
+        are its.  While on, rollout() runs one TTI per launch."""
+        self._check(self._lib.ranenv_enable_slice_metrics(self._h, 1, self._stream()), "ranenv_enable_slice_metrics")
+        self._slice_metric_views = None
+        self._slice_metrics_on = True
+
+    def disable_slice_metrics(self) -> None:
+        self._check(self._lib.ranenv_enable_slice_metrics(self._h, 0, self._stream()), "ranenv_enable_slice_metrics")
+        self._slice_metrics_on = False
+
+    def slice_episode_metrics(self) -> Dict[str, torch.Tensor]:
+        """Zero-copy views: ``running`` [B, S, 10] (current episode), and with episode slots ``episode_log`` [B, slots, S, 10]
+        (finished episodes, in order) and ``episode_scenario`` [B, slots] int32 (the scenario-pool row each logged episode
+        was played on, -1 = empty slot); columns as SLICE_METRIC_NAMES."""
+        if getattr(self, "_slice_metric_views", None) is None:
+            run, log, scn = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            ncol = C.c_int32()
+            self._check(self._lib.ranenv_get_slice_metrics(self._h, C.byref(run), C.byref(log), C.byref(scn), C.byref(ncol)),
+                        "ranenv_get_slice_metrics")
+            K = ncol.value
+            if K != len(self.SLICE_METRIC_NAMES):
+                raise RanEnvError(f"the library keeps {K} per-slice columns, the binding names {len(self.SLICE_METRIC_NAMES)}")
+            out = {"running": torch.as_tensor(_DevArray(run.value, (self.B, self.S, K), "f8", self), device=self.device)}
+            if log.value:
+                slots = int(self.episode_metrics()["episode_log"].shape[1])
+                out["episode_log"] = torch.as_tensor(_DevArray(log.value, (self.B, slots, self.S, K), "f8", self), device=self.device)
+                out["episode_scenario"] = torch.as_tensor(_DevArray(scn.value, (self.B, slots), "i4", self), device=self.device)
+            self._slice_metric_views = out
+        return self._slice_metric_views
 
     def episode_metrics(self) -> Dict[str, torch.Tensor]:
         """Zero-copy views: ``running`` [B, 8] (current episode), ``episode_log`` [B, slots, 8] (finished episodes, in
@@ -929,15 +968,20 @@ class BatchedRanEnv:
             self._metric_views = out
         return self._metric_views
 
-    def evaluate(self, n_episodes: int, max_steps=None) -> Dict[str, np.ndarray]:
+    def evaluate(self, n_episodes: int, max_steps=None, per_slice: bool = False) -> Dict[str, np.ndarray]:
         """The reference's test loop for its baseline agents (simu.py:547-566 over ``max_episode - initial_episode``
         episodes; the numbers results/gen_results.py:874-1022 turns into the paper's violation / distance figures), for
         the whole batch on the device: reset, then one rollout long enough for every env to finish ``n_episodes``
         episodes under the device policy, episode ends handled by auto-reset.  Needs enable_autoreset(...) and
         enable_metrics(slots >= n_episodes).  Returns {metric: float64 [B, n_episodes]} with the names of METRIC_NAMES;
-        row b holds env b's episodes in the order it played them (from the episode number given to enable_autoreset)."""
+        row b holds env b's episodes in the order it played them (from the episode number given to enable_autoreset).
+        ``per_slice`` (needs enable_slice_metrics()): the result gains ``"slice"``, float64 [B, n_episodes, S, 10] with the
+        columns of SLICE_METRIC_NAMES, and ``"scenario"``, int32 [B, n_episodes]: the scenario-pool row of every episode,
+        which says what slice type each slice index was (scenario.slice_type_report aggregates by type)."""
         if not self._autoreset:
             raise RanEnvError("evaluate() needs enable_autoreset(): it runs through episode ends on the device")
+        if per_slice and not getattr(self, "_slice_metrics_on", False):
+            raise RanEnvError("evaluate(per_slice=True) needs enable_slice_metrics()")
         m = self.episode_metrics()
         if "episode_log" not in m or m["episode_log"].shape[1] < n_episodes:
             raise RanEnvError(f"evaluate({n_episodes}) needs enable_metrics(episode_slots >= {n_episodes})")
@@ -945,7 +989,9 @@ class BatchedRanEnv:
             self.set_max_steps(max_steps)
         me = getattr(self, "max_steps_env", None)
         longest = int(self.max_steps) if me is None else int(me.max())
-        self.enable_metrics(m["episode_log"].shape[1])      # zero the sums and the log
+        self.enable_metrics(m["episode_log"].shape[1])      # zero the sums and the log (the per-slice ones too while they are on)
+        m = self.episode_metrics()
+        sm = self.slice_episode_metrics() if per_slice else None
         self.reset()
         self.rollout(n_episodes * longest)
         torch.cuda.synchronize(self.device)
@@ -953,7 +999,11 @@ class BatchedRanEnv:
         if done.min() < n_episodes:
             raise RanEnvError(f"an env finished only {int(done.min())} of {n_episodes} episodes: per-env max_steps longer than assumed")
         log = m["episode_log"][:, :n_episodes].cpu().numpy()
-        return {name: log[:, :, k].copy() for k, name in enumerate(self.METRIC_NAMES)}
+        out = {name: log[:, :, k].copy() for k, name in enumerate(self.METRIC_NAMES)}
+        if per_slice:
+            out["slice"] = sm["episode_log"][:, :n_episodes].cpu().numpy()
+            out["scenario"] = sm["episode_scenario"][:, :n_episodes].cpu().numpy()
+        return out
 
     def set_option(self, key: str, value: int) -> None:
         """A tuning / debug knob of the launch schedule; the keys are the table "Options" in include/ranenv.h.  None of them

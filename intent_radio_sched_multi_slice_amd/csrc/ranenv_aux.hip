@@ -310,6 +310,46 @@ __global__ void __launch_bounds__(CORE_NT) ranenv_head_kernel(const KP p, double
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-slice episode metrics (ranenv_enable_slice_metrics; the columns are spelled out in include/ranenv.h): what the paper's
+// per-slice figures read per TTI (results/gen_results.py:874-970, :791-809, :1007-1018), kept as running sums per (env, slice).
+// Launched behind the step kernel for the same envs on the same stream and restates nothing of it: the minimum declared drift is
+// the step's reward[e][s + 1], the per-metric drifts and their declared flags are its obs_intra[e][s][0..5], the packet counts its
+// raw per-UE outputs.  One workgroup = one env, thread = slot (slice in INDEX order, UE position), as the head kernel; the four
+// packet sums run over a slice's 16 lanes on one DPP row.  Lane k < 10 of a slice owns column k: one writer per cell and TTI,
+// TTIs in stream order, so the sums do not depend on the launch path.  reset != 0: the launch follows a reset and zeroes the rows
+// of the envs under the mask.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(CORE_NT) ranenv_slice_metrics_kernel(const KP p, double *slice_acc, int reset)
+{
+    const int e = p.e0 + blockIdx.x, tid = threadIdx.x;
+    if (p.env_mask != nullptr && p.env_mask[e] == 0) return;
+    const int S = p.S, U = p.U;
+    const int s = tid / GRP, pos = tid % GRP;
+    if (s >= S) return;                                    // (whole rows of 16 lanes leave: the DPP sums below stay inside a row)
+    double *cell = slice_acc + ((size_t)e * S + s) * RANENV_SLICE_METRIC_COLS + pos;
+    if (reset) { if (pos < RANENV_SLICE_METRIC_COLS) *cell = 0.0; return; }
+    const int sc = __builtin_amdgcn_readfirstlane(p.episodes[e].scenario);
+    const int ue = TB_slot_ue(p)[(size_t)sc * S * GRP + tid];
+    int inc = 0, cap = 0, sent = 0, drop = 0;
+    if (ue >= 0) {
+        const size_t su = (size_t)e * U + ue;
+        inc = ST_pkt_incoming(p)[su]; cap = ST_pkt_throughputs(p)[su]; sent = ST_pkt_effective_thr(p)[su]; drop = ST_dropped_pkts(p)[su];
+    }
+    inc = row16_sum(inc); cap = row16_sum(cap); sent = row16_sum(sent); drop = row16_sum(drop);
+    const bool active = TB_slice_i32(p)[((size_t)sc * S + s) * 8 + 0] != 0;
+    const double dmin = p.reward[(size_t)e * (S + 1) + s + 1];                 // minimum over the declared metrics (0.0: none declared)
+    const float *oa = p.obs_intra + ((size_t)e * S + s) * (size_t)(2 * p.Us + 9);
+    double add;
+    if (pos >= 6) add = (double)(pos == 6 ? inc : (pos == 7 ? cap : (pos == 8 ? sent : drop)));
+    else if (!active) add = 0.0;                           // an inactive slice may have UEs, a request and a drift: it counts nowhere
+    else if (pos == 0) add = 1.0;
+    else if (pos == 1) add = dmin < 0.0 ? 1.0 : 0.0;
+    else if (pos == 5) add = dmin < 0.0 ? dmin : 0.0;
+    else add = (oa[pos + 1] > 0.0f && oa[pos - 2] < 0.0f) ? 1.0 : 0.0;       // metric pos - 2: declared flag [3 + m], drift [m]
+    if (pos < RANENV_SLICE_METRIC_COLS) *cell += add;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Channel ingest: received power -> spectral efficiency (channels/quadriga.py:56-69), elementwise.
 // 8 B read + 4 B written per element; two elements per thread and grid-stride, 16-byte loads.
 // ---------------------------------------------------------------------------------------------
@@ -348,6 +388,10 @@ __global__ void __launch_bounds__(64) ranenv_advance_kernel(const AdvanceArgs a)
         const int n = a.ep_n[e];                  // read by every thread of this one wave before thread 8 stores
         if (tid < 8 && n < a.ep_slots) a.ep_acc[((size_t)e * a.ep_slots + n) * 8 + tid] = a.acc[(size_t)e * 8 + tid];
         if (a.head_acc && tid >= 16 && tid < 18 && n < a.ep_slots) a.head_ep_acc[((size_t)e * a.ep_slots + n) * 2 + (tid - 16)] = a.head_acc[(size_t)e * 2 + (tid - 16)];
+        if (a.slice_acc && n < a.ep_slots) {      // ... and its per-slice block, with the scenario row it was played on (the slice index means another slice type in every scenario)
+            for (int i = tid; i < a.n_slice; i += 64) a.slice_ep_acc[((size_t)e * a.ep_slots + n) * a.n_slice + i] = a.slice_acc[(size_t)e * a.n_slice + i];
+            if (tid == 9) a.slice_ep_scenario[(size_t)e * a.ep_slots + n] = a.episodes[e].scenario;      // (thread 0 installs the next descriptor below)
+        }
         if (tid == 8) a.ep_n[e] = n + 1;
     }
     if (a.term_inter) for (int i = tid; i < a.n_inter; i += 64) a.term_inter[(size_t)e * a.n_inter + i] = a.obs_inter[(size_t)e * a.n_inter + i];
@@ -477,6 +521,10 @@ void launch_se_from_power(hipStream_t s, unsigned blocks, const double *power, f
 void launch_head(hipStream_t s, dim3 grid, dim3 block, const KP &kp, double *head_acc, int reset)
 {
     hipLaunchKernelGGL(ranenv_head_kernel, grid, block, 0, s, kp, head_acc, reset);
+}
+void launch_slice_metrics(hipStream_t s, dim3 grid, dim3 block, const KP &kp, double *slice_acc, int reset)
+{
+    hipLaunchKernelGGL(ranenv_slice_metrics_kernel, grid, block, 0, s, kp, slice_acc, reset);
 }
 void launch_advance(hipStream_t s, unsigned n_envs, const AdvanceArgs &a) { hipLaunchKernelGGL(ranenv_advance_kernel, dim3(n_envs), dim3(64), 0, s, a); }
 void launch_idle_traffic(hipStream_t s, unsigned n_eps, const ranenv_episode *eps, const int32_t *pool, int U, const int32_t *lane_slice,

@@ -52,6 +52,8 @@ struct ranenv {
     int32_t *d_max_steps = nullptr;
     std::vector<int32_t> host_max_steps;        // copy of ranenv_set_max_steps' array (the multi-episode rollout follows the step counters)
     double *d_acc = nullptr, *d_ep_acc = nullptr; int32_t *d_ep_n = nullptr; int ep_slots = 0;   // ranenv_enable_metrics
+    double *d_slice_acc = nullptr, *d_slice_ep_acc = nullptr; int32_t *d_slice_ep_scn = nullptr;    // ranenv_enable_slice_metrics: [B][S][10], [B][ep_slots][S][10], [B][ep_slots]
+    bool slice_on = false;                      // ... switched on (the slice-metrics kernel follows every step and reset; off with kp.acc)
     // Host shadow of the per-env step counters (what they will be once everything enqueued so far has run): `done` is a function of
     // the counter alone (step >= the env's episode length), so ranenv_autoreset knows WITHOUT reading anything back whether an episode
     // ended at the TTI just enqueued -- and enqueues nothing when none did (an RL loop calls it behind every step: three small launches
@@ -304,7 +306,17 @@ StepPlan step_plan(ranenv_handle h, KP &kp, int e0, int n, bool gather)
     return {l, grid, block};
 }
 
-// One launch of the step kernel for envs [e0, e0 + n) on `stream` (+ the head kernel when bound).
+// Per-slice episode metrics are kept: the slice-metrics kernel follows every step and reset, one TTI per step launch
+bool slice_metrics_on(ranenv_handle h) { return h->slice_on && h->kp.acc != nullptr && h->d_slice_acc != nullptr; }
+// ... then a call that steps needs the two outputs that kernel reads
+int slice_metrics_outputs(ranenv_handle h, const float *obs_intra, const double *reward)
+{
+    if (slice_metrics_on(h) && (!obs_intra || !reward))
+        return fail(h, RANENV_E_INVALID, "per-slice metrics read the step's dev_reward and dev_obs_intra: both are needed while they are on");
+    return RANENV_OK;
+}
+
+// One launch of the step kernel for envs [e0, e0 + n) on `stream` (+ the head kernel when bound, + the slice-metrics kernel when on).
 template <int MODE>
 hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t stream)
 {
@@ -325,6 +337,8 @@ hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t strea
     if (kp.head_obs || kp.head_reward)
         launch_head(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp, (h->kp.acc && h->kp.head_reward) ? h->d_head_acc : nullptr,
                     MODE == MODE_RESET ? 1 : 0);
+    if (slice_metrics_on(h))
+        launch_slice_metrics(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp, h->d_slice_acc, MODE == MODE_RESET ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -446,6 +460,9 @@ AdvanceArgs advance_args(ranenv_handle h, const uint8_t *dev_done, float *obs_in
     a.acc = h->kp.acc; a.ep_acc = h->d_ep_acc; a.ep_n = h->d_ep_n; a.ep_slots = h->ep_slots;
     const bool head_sums = h->kp.acc && h->kp.head_reward && h->d_head_acc && h->d_head_ep_acc;
     a.head_acc = head_sums ? h->d_head_acc : nullptr; a.head_ep_acc = head_sums ? h->d_head_ep_acc : nullptr;
+    const bool slice_sums = slice_metrics_on(h) && h->d_slice_ep_acc && h->d_slice_ep_scn;
+    a.slice_acc = slice_sums ? h->d_slice_acc : nullptr; a.slice_ep_acc = slice_sums ? h->d_slice_ep_acc : nullptr;
+    a.slice_ep_scenario = slice_sums ? h->d_slice_ep_scn : nullptr; a.n_slice = S * RANENV_SLICE_METRIC_COLS;
     return a;
 }
 
@@ -1359,6 +1376,8 @@ static int step_begin(ranenv_handle h, int32_t env_first, int32_t env_count, con
     if (env_first < 0 || env_count < 1 || (long long)env_first + env_count > h->cfg.batch)
         return fail(h, RANENV_E_INVALID, "envs [%d,%d) outside the batch of %d", env_first, env_first + env_count, h->cfg.batch);
     if (!scores && h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "policy is EXTERNAL but no inter-slice scores were given");
+    rc = slice_metrics_outputs(h, obs_intra, reward);
+    if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     *kp = call_kp(h, obs_inter, obs_intra, reward, done);
     kp->se_tiles = se_tiles; kp->scores = scores; kp->intra = intra; kp->traffic_bits = traffic_bits;
@@ -1407,6 +1426,8 @@ int ranenv_step_dense(ranenv_handle h, const uint8_t *dense, const double *traff
     int rc = check_ready(h, se_tiles, traffic_bits, true);
     if (rc != RANENV_OK) return rc;
     if (!dense) return fail(h, RANENV_E_INVALID, "null sched_decision");
+    rc = slice_metrics_outputs(h, obs_intra, reward);
+    if (rc != RANENV_OK) return rc;
     if (!se_tiles && !h->kp.se_pool) return fail(h, RANENV_E_STATE, "a dense step reads whole SE rows: it needs explicit tiles or an RB-major pool (this handle has gather sidecars only)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     KP kp = call_kp(h, obs_inter, obs_intra, reward, done);
@@ -1752,7 +1773,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
     // the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more and lengthen the
     // drain at the rollout's end, where the workgroups that waited for a free slot run last and alone).
     int fuse = h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
-    if (r.kp.head_obs || r.kp.head_reward || r.net) fuse = 1;
+    if (r.kp.head_obs || r.kp.head_reward || r.net || slice_metrics_on(h)) fuse = 1;
     // `pdone[k]` TTIs are enqueued for partition k
     const int np = h->n_parts > 1 ? h->n_parts : 1;
     std::vector<int> pdone((size_t)np, 0), pn((size_t)np, 0);
@@ -1804,6 +1825,8 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     int rc = check_ready(h, nullptr, nullptr, true);
     if (rc != RANENV_OK) return rc;
     if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
+    rc = slice_metrics_outputs(h, obs_intra, reward);
+    if (rc != RANENV_OK) return rc;
     if (h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "a rollout needs a device policy (ranenv_set_policy MARR / MAPF / NETWORK)");
     const bool have_se = h->kp.se_pool != nullptr || (h->se_mode == RANENV_SE_GATHER && h->d_se_mean != nullptr);
     if (!have_se || (!h->kp.trf_pool && !h->kp.trf_gen)) return fail(h, RANENV_E_STATE, "a rollout replays the bound SE pool and traffic pool / generator");
@@ -1841,7 +1864,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     // (auto: not when episodes end at many different TTIs inside this call -- per-env episode lengths, envs reset at different times:
     // every episode end ends the persistent launches, re-sorts the envs and reads the class counts back; the launch-per-chunk
     // rollout follows the ends per partition without a host sync)
-    bool persist_ok = persist_wanted && !r.net && !scale_per_element(h) && r.kp.compact != 0 && !(r.kp.head_obs || r.kp.head_reward) &&
+    bool persist_ok = persist_wanted && !r.net && !scale_per_element(h) && r.kp.compact != 0 && !(r.kp.head_obs || r.kp.head_reward) && !slice_metrics_on(h) &&
                       (h->cfg.batch >> PERSIST_ENV_BITS) == 0 && !stream_capturing(stream);      // (it reads the class counts back)
     if (persist_ok && h->persist < 0 && r.follow) {
         int n_ends = 0;
@@ -1942,10 +1965,20 @@ static int head_sums_alloc(ranenv_handle h)
     return dev_alloc(h, &h->d_head_acc, B * 2);
 }
 
+// Per-slice sums, their log and the log's scenario rows (-1: no episode logged in that slot) start from zero
+static int slice_sums_zero(ranenv_handle h, hipStream_t stream)
+{
+    const size_t B = (size_t)h->cfg.batch, n = (size_t)h->cfg.n_slices * RANENV_SLICE_METRIC_COLS;
+    HIP_TRY(h, hipMemsetAsync(h->d_slice_acc, 0, sizeof(double) * B * n, stream));
+    if (h->d_slice_ep_acc) HIP_TRY(h, hipMemsetAsync(h->d_slice_ep_acc, 0, sizeof(double) * B * (size_t)h->ep_slots * n, stream));
+    if (h->d_slice_ep_scn) HIP_TRY(h, hipMemsetAsync(h->d_slice_ep_scn, 0xff, sizeof(int32_t) * B * (size_t)h->ep_slots, stream));
+    return RANENV_OK;
+}
+
 int ranenv_enable_metrics(ranenv_handle h, int32_t episode_slots, void *stream_)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (episode_slots < 0) { h->kp.acc = nullptr; return RANENV_OK; }      // off (what was accumulated stays readable)
+    if (episode_slots < 0) { h->kp.acc = nullptr; h->slice_on = false; return RANENV_OK; }      // off, the per-slice sums too (what was accumulated stays readable)
     if (h->d_acc && episode_slots != h->ep_slots)
         return fail(h, RANENV_E_STATE, "episode metrics were enabled with %d slots per env", h->ep_slots);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1963,6 +1996,36 @@ int ranenv_enable_metrics(ranenv_handle h, int32_t episode_slots, void *stream_)
     if (head_sums_alloc(h) != RANENV_OK) return RANENV_E_NOMEM;
     if (h->d_head_acc) HIP_TRY(h, hipMemsetAsync(h->d_head_acc, 0, sizeof(double) * B * 2, stream));
     if (h->d_head_ep_acc) HIP_TRY(h, hipMemsetAsync(h->d_head_ep_acc, 0, sizeof(double) * B * (size_t)h->ep_slots * 2, stream));
+    if (h->slice_on) return slice_sums_zero(h, stream);
+    return RANENV_OK;
+}
+
+int ranenv_enable_slice_metrics(ranenv_handle h, int32_t enable, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!enable) { h->slice_on = false; return RANENV_OK; }      // off (what was accumulated stays readable)
+    if (h->cfg.flags & RANENV_F_NO_RAW_OUTPUT)
+        return fail(h, RANENV_E_INVALID, "per-slice metrics read pkt_incoming and pkt_throughputs: not available with RANENV_F_NO_RAW_OUTPUT");
+    if (!h->kp.acc) return fail(h, RANENV_E_STATE, "per-slice metrics take their episode slots from ranenv_enable_metrics: call it first");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t B = (size_t)h->cfg.batch, n = (size_t)h->cfg.n_slices * RANENV_SLICE_METRIC_COLS;
+    if (!h->d_slice_acc) {
+        if (h->ep_slots > 0 && (dev_alloc(h, &h->d_slice_ep_acc, B * (size_t)h->ep_slots * n) != RANENV_OK ||
+                                dev_alloc(h, &h->d_slice_ep_scn, B * (size_t)h->ep_slots) != RANENV_OK)) return RANENV_E_NOMEM;
+        if (dev_alloc(h, &h->d_slice_acc, B * n) != RANENV_OK) return RANENV_E_NOMEM;
+    }
+    h->slice_on = true;
+    return slice_sums_zero(h, (hipStream_t)stream_);
+}
+
+int ranenv_get_slice_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t **dev_episode_scenario, int32_t *n_cols)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!h->d_slice_acc) return fail(h, RANENV_E_STATE, "per-slice metrics are not enabled (ranenv_enable_slice_metrics)");
+    if (dev_running) *dev_running = h->d_slice_acc;
+    if (dev_episode_log) *dev_episode_log = h->d_slice_ep_acc;
+    if (dev_episode_scenario) *dev_episode_scenario = h->d_slice_ep_scn;
+    if (n_cols) *n_cols = RANENV_SLICE_METRIC_COLS;
     return RANENV_OK;
 }
 

@@ -163,6 +163,7 @@ struct AdvanceArgs {
     int *cls_flag;                                // set when an env restarts: the class lists of the mixed / persistent launches are stale
     const double *acc; double *ep_acc; int32_t *ep_n; int ep_slots;   // episode metrics: running sums -> per-episode log
     const double *head_acc; double *head_ep_acc;                      // ... and the head rewards' pair [B][2] -> [B][ep_slots][2] (null: none)
+    const double *slice_acc; double *slice_ep_acc; int32_t *slice_ep_scenario; int n_slice;   // ... and the per-slice sums [B][n_slice = S * 10] -> [B][ep_slots][n_slice], with the finished episode's scenario row [B][ep_slots] (null: none)
 };
 
 // Policy network (ranenv_policy.hip): one MLP as packed in the handle's buffer.  Every width is padded with zeros to a multiple of
@@ -287,6 +288,9 @@ void launch_ddiv_selftest(hipStream_t, const double *a, const double *b, double 
 // head_acc: the per-env running pair of the two head rewards [B][2] or null; reset != 0: the launch follows a reset (the pair of the
 // envs under the mask is zeroed), else a step (this TTI's rewards are added)
 void launch_head(hipStream_t, dim3 grid, dim3 block, const KP &, double *head_acc, int reset);
+// Per-slice episode sums [B][S][RANENV_SLICE_METRIC_COLS] behind a step (reset == 0: this TTI's share is added; reads kp.reward and kp.obs_intra)
+// or behind a reset (reset != 0: the rows of the envs under kp.env_mask are zeroed); block = the head kernel's
+void launch_slice_metrics(hipStream_t, dim3 grid, dim3 block, const KP &, double *slice_acc, int reset);
 void launch_advance(hipStream_t, unsigned n_envs, const AdvanceArgs &);
 // reward_stride: doubles between two (env, column) entries' rewards' rows, i.e. reward[(t * B + b) * reward_stride + c] (n_cols: packed)
 void launch_gae(hipStream_t, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,

@@ -95,6 +95,99 @@ def slice_usecase_from_req(slice_req: dict, n_slices: int) -> np.ndarray:
         if req:
             out[s] = SLICE_USECASE.get(req.get("name", ""), 0)
     return out
+
+
+def slice_type_from_req(slice_req: dict, n_slices: int) -> np.ndarray:
+    """[S] int32 index into SLICE_TYPE_NAMES of every slice of a reference ``slice_req`` dict (-1 for empty or unknown slices)."""
+    out = np.full(n_slices, -1, dtype=np.int32)
+    for s in range(n_slices):
+        req = (slice_req or {}).get(f"slice_{s}", {})
+        if req and req.get("name", "") in SLICE_TYPE_NAMES:
+            out[s] = SLICE_TYPE_NAMES.index(req["name"])
+    return out
+
+
+def _slice_signature(tables, i: int, s: int) -> tuple:
+    n = int(tables.slice_nparams[i, s])
+    params = sorted((int(tables.param_metric[i, s, k]), int(tables.param_op[i, s, k]), float(tables.param_value[i, s, k])) for k in range(n))
+    return (float(tables.slice_priority[i, s]), float(tables.slice_traffic[i, s]), int(tables.slice_buffer_size[i, s]),
+            int(tables.slice_buffer_latency[i, s]), int(tables.slice_message_size[i, s]), tuple(params))
+
+
+def slice_type_from_tables(tables) -> np.ndarray:
+    """[NS, S] int32 index into SLICE_TYPE_NAMES of every slice of ``tables`` that has a request and whose priority, traffic,
+    buffer, message size and intent parameters are those of one of the ten templates (-1 otherwise).  For tables that no longer
+    carry the request dicts (fixtures, generate_scaled_scenarios); with the dicts at hand use slice_type_from_req."""
+    n = len(SLICE_TEMPLATES)
+    ref = ScenarioTables.empty(1, n, n, 1)
+    ref.set_from_reference(0, np.ones((1, n)), np.eye(n), {f"slice_{k}": slice_template_dict(k) for k in range(n)}, True)
+    sig = {_slice_signature(ref, 0, k): k for k in range(n)}
+    if len(sig) != n:
+        raise AssertionError("two slice templates share every table entry")
+    out = np.full((tables.n_scenarios, tables.n_slices), -1, dtype=np.int32)
+    for i in range(tables.n_scenarios):
+        for s in range(tables.n_slices):
+            if tables.slice_has_req[i, s]:
+                out[i, s] = sig.get(_slice_signature(tables, i, s), -1)
+    return out
+
+
+SLICE_REPORT_METRICS = ("throughput", "reliability", "latency")      # RANENV_METRIC_* order = columns 2..4 of the per-slice sums
+
+
+def slice_type_report(slice_log: np.ndarray, scenario: np.ndarray, slice_type: np.ndarray, tables: "ScenarioTables",
+                      priority_only: bool = False) -> dict:
+    """Per-slice episode sums (BatchedRanEnv.evaluate(per_slice=True): ``slice_log`` [..., S, 10], ``scenario`` [...] the
+    scenario-pool row of every block) aggregated by slice type, the way results/gen_results.py reports them.
+
+    ``slice_type`` [NS, S]: index into SLICE_TYPE_NAMES of every (scenario, slice), -1 = none (slice_type_from_req per row).
+    ``priority_only``: only slices whose request has priority != 0 count (calc_slice_violations(priority=True)).
+    Returns
+      ``violations_per_slice_type``  {type name: slice-TTIs in violation}          gen_results.py:951-964
+      ``violations_slice_metric``    {type name: {metric name: slice-TTIs}}        :927-949
+    both without zero entries, as the reference builds them, and
+      ``capacity_mbit`` / ``served_mbit`` / ``requested_mbit``  {type name: Mbit}: packets x slice_message_size / 1e6, the
+    arithmetic of calc_total_throughput (:791-809) for pkt_throughputs / pkt_effective_thr / pkt_incoming (message size 0
+    where the slice has no request), with their sums over all slices under ``total_network_throughput``,
+    ``total_network_eff_throughput`` and ``total_network_requested_throughput``."""
+    log = np.asarray(slice_log, dtype=np.float64)
+    scn = np.asarray(scenario)
+    st = np.asarray(slice_type)
+    S = log.shape[-2]
+    if log.shape[:-2] != scn.shape or log.shape[-1] != 10 or st.shape[1] != S:
+        raise ValueError("slice_log [..., S, 10], scenario [...] and slice_type [NS, S] do not fit")
+    log = log.reshape(-1, S, 10)
+    scn = scn.reshape(-1).astype(np.int64)
+    keep = scn >= 0                                                   # (-1: an episode slot nothing was logged in)
+    log, scn = log[keep], scn[keep]
+    typ = st[scn]                                                     # [N, S]
+    msg = np.where(tables.slice_has_req[scn] != 0, tables.slice_message_size[scn], 0).astype(np.float64)
+    use = typ >= 0
+    if priority_only:
+        use = use & (tables.slice_has_req[scn] != 0) & (tables.slice_priority[scn] != 0)
+    out = {"violations_per_slice_type": {}, "violations_slice_metric": {},
+           "capacity_mbit": {}, "served_mbit": {}, "requested_mbit": {}}
+    mbit = {"capacity_mbit": log[:, :, 7] * msg / 1e6, "served_mbit": log[:, :, 8] * msg / 1e6, "requested_mbit": log[:, :, 6] * msg / 1e6}
+    for ti, name in enumerate(SLICE_TYPE_NAMES):
+        sel = use & (typ == ti)
+        if not sel.any():
+            continue
+        v = int(round(log[:, :, 1][sel].sum()))
+        if v:
+            out["violations_per_slice_type"][name] = v
+        per = {mn: int(round(log[:, :, 2 + k][sel].sum())) for k, mn in enumerate(SLICE_REPORT_METRICS)}
+        per = {k: c for k, c in per.items() if c}
+        if per:
+            out["violations_slice_metric"][name] = per
+        for key, arr in mbit.items():
+            out[key][name] = float(arr[sel].sum())
+    sel_all = use if priority_only else np.ones_like(use)
+    out["total_network_throughput"] = float(mbit["capacity_mbit"][sel_all].sum())
+    out["total_network_eff_throughput"] = float(mbit["served_mbit"][sel_all].sum())
+    out["total_network_requested_throughput"] = float(mbit["requested_mbit"][sel_all].sum())
+    return out
+
+
 MAX_AGE_CAP_DEFAULT = max(t[4] for t in SLICE_TEMPLATES)  # 400 TTIs (uav_app_case_1)
 
 
