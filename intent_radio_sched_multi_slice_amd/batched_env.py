@@ -346,18 +346,8 @@ class BatchedRanEnv:
         nets = [policy_net_layers(inter, activation, in_inter, 2 * self.S)]
         if intra is not None:
             nets.append(policy_net_layers(intra, activation, in_intra, 3))
-        structs, keep = [], []
-        for k, (layers, act) in enumerate(nets):
-            m = _lib.Mlp()
-            m.n_hidden, m.activation = len(layers) - 1, NET_ACTIVATIONS[act]
-            m.input_layout = NET_INPUTS[intra_input] if k == 1 else NET_IN_OBS
-            m.dims[0] = layers[0][0].shape[1]
-            for i, (w, b) in enumerate(layers):
-                w, b = w.to(self.device).contiguous(), b.to(self.device).contiguous()
-                keep += [w, b]
-                m.dims[i + 1] = w.shape[0]
-                m.weight[i], m.bias[i] = w.data_ptr(), b.data_ptr()
-            structs.append(m)
+        keep: list = []
+        structs = [self._mlp_struct(layers, act, NET_INPUTS[intra_input] if k == 1 else NET_IN_OBS, keep) for k, (layers, act) in enumerate(nets)]
         with torch.cuda.device(self.device):
             self._check(self._lib.ranenv_set_policy_network(self._h, C.byref(structs[0]), C.byref(structs[1]) if intra is not None else None,
                                                             1 if stochastic else 0, int(seed) & (2 ** 64 - 1), self._stream()),
@@ -413,24 +403,28 @@ class BatchedRanEnv:
         observation buffers and ``policy_actions()`` afterwards are those of ``rollout(n_steps)``."""
         if self._recorder is not None:
             raise RanEnvError("collect() does not return between TTIs: the recorder needs step()")
+        return self._collect("collect", n_steps, record, _lib.Trajectory, _lib.TRAJECTORY_FIELDS, self.TRAJECTORY_SHAPES, "trajectories",
+                             (self.B, self.S, self.Us, self.W), self._lib.ranenv_collect, (float(gamma), float(lam)))
+
+    def _collect(self, name, n_steps, record, struct, fields, shapes, cache_key, sizes, call, args) -> Dict[str, torch.Tensor]:
+        """``collect`` / ``collect_head``: the record's tensors (cached per (n_steps, record)), their pointers in ``struct``, the C call."""
         n_steps = int(n_steps)
-        traj = _lib.Trajectory()
+        traj = struct()
         out: Dict[str, torch.Tensor] = {}
         if n_steps >= 1:
-            unknown = set(record) - set(_lib.TRAJECTORY_FIELDS)
+            unknown = set(record) - set(fields)
             if unknown:
                 raise ValueError(f"unknown trajectory fields {sorted(unknown)}")
-            key = (n_steps, tuple(f for f in _lib.TRAJECTORY_FIELDS if f in set(record)))
-            cache = self._keep.setdefault("trajectories", {})
+            key = (n_steps, tuple(f for f in fields if f in set(record)))
+            cache = self._keep.setdefault(cache_key, {})
             if key not in cache:
-                cache[key] = {f: torch.zeros((n_steps + self.TRAJECTORY_SHAPES[f][1],) + self.TRAJECTORY_SHAPES[f][2](self.B, self.S, self.Us, self.W),
-                                             dtype=self.TRAJECTORY_SHAPES[f][0], device=self.device) for f in key[1]}
+                cache[key] = {f: torch.zeros((n_steps + shapes[f][1],) + shapes[f][2](*sizes), dtype=shapes[f][0], device=self.device)
+                              for f in key[1]}
             out = cache[key]
             for f, t in out.items():
                 setattr(traj, f, t.data_ptr())
         with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_collect(self._h, n_steps, C.byref(traj), float(gamma), float(lam), *self._p_out, self._stream()),
-                        "ranenv_collect")
+            self._check(call(self._h, n_steps, C.byref(traj), *args, *self._p_out, self._stream()), f"ranenv_{name}")
         return out
 
     def gae(self, reward: torch.Tensor, vf: torch.Tensor, done: torch.Tensor, gamma: float = 0.99, lam: float = 0.95,
@@ -517,26 +511,8 @@ class BatchedRanEnv:
             raise RanEnvError("collect_head() does not return between TTIs: the recorder needs step()")
         if reward not in HEAD_REWARDS:
             raise ValueError(f"reward must be one of {sorted(HEAD_REWARDS)}")
-        n_steps = int(n_steps)
-        traj = _lib.HeadTrajectory()
-        out: Dict[str, torch.Tensor] = {}
-        if n_steps >= 1:
-            unknown = set(record) - set(_lib.HEAD_TRAJECTORY_FIELDS)
-            if unknown:
-                raise ValueError(f"unknown trajectory fields {sorted(unknown)}")
-            key = (n_steps, tuple(f for f in _lib.HEAD_TRAJECTORY_FIELDS if f in set(record)))
-            cache = self._keep.setdefault("head_trajectories", {})
-            if key not in cache:
-                shp = self.HEAD_TRAJECTORY_SHAPES
-                cache[key] = {f: torch.zeros((n_steps + shp[f][1],) + shp[f][2](self.B, self.S), dtype=shp[f][0], device=self.device)
-                              for f in key[1]}
-            out = cache[key]
-            for f, t in out.items():
-                setattr(traj, f, t.data_ptr())
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_collect_head(self._h, n_steps, C.byref(traj), HEAD_REWARDS[reward], float(gamma), float(lam),
-                                                      *self._p_out, self._stream()), "ranenv_collect_head")
-        return out
+        return self._collect("collect_head", n_steps, record, _lib.HeadTrajectory, _lib.HEAD_TRAJECTORY_FIELDS, self.HEAD_TRAJECTORY_SHAPES,
+                             "head_trajectories", (self.B, self.S), self._lib.ranenv_collect_head, (HEAD_REWARDS[reward], float(gamma), float(lam)))
 
     def head_episode_metrics(self) -> Dict[str, torch.Tensor]:
         """Zero-copy views of the episode sums of the two head rewards (columns: SchedTWC, SchedColORAN): ``running`` [B, 2]

@@ -1110,11 +1110,16 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra)
 
 // ---- policy networks (RANENV_POLICY_NETWORK) --------------------------------------------------------------------------------
 // Validate one ranenv_mlp against the handle's sizes and lay it out in the packed buffer from float `off` on (widths padded to 32).
-// head_out > 0: a head net (input the head observation [10*S], `head_out` outputs).
-static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNet &net, long long &off, bool critic = false, int head_out = 0)
+enum NetRole { NET_INTER, NET_INTRA, NET_INTER_VALUE, NET_INTRA_VALUE, NET_HEAD_CLIP, NET_HEAD_TANH, NET_HEAD_VALUE };
+static const struct { const char *who; bool intra; int out_s, out_1; } NET_ROLES[] = {      // intra: the input is a slice's row, else the (head)
+    {"inter", false, 2, 0}, {"intra", true, 0, 3}, {"inter value", false, 0, 1}, {"intra value", true, 0, 1},      // observation [10*S];
+    {"head", false, 1, 0}, {"head", false, 2, 0}, {"head value", false, 0, 1}};                                    // output width out_s * S + out_1
+
+static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, PolicyNet &net, long long &off)
 {
     const int S = h->cfg.n_slices, Us = h->cfg.max_ues_slice;
-    const char *who = head_out ? (critic ? "head value" : "head") : critic ? (intra ? "intra value" : "inter value") : (intra ? "intra" : "inter");
+    const char *who = NET_ROLES[role].who;
+    const bool intra = NET_ROLES[role].intra;
     if (m->n_hidden < 1 || m->n_hidden > NET_MAX_LAYERS - 1) return fail(h, RANENV_E_INVALID, "%s net: %d hidden layers (1..%d)", who, m->n_hidden, NET_MAX_LAYERS - 1);
     if (m->activation != RANENV_ACT_TANH && m->activation != RANENV_ACT_RELU) return fail(h, RANENV_E_INVALID, "%s net: unknown activation %d", who, m->activation);
     int in_dim = 10 * S;
@@ -1124,7 +1129,7 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNe
         else if (m->input_layout == RANENV_NET_IN_MASK_OBS) in_dim = 3 * Us + 9;
         else return fail(h, RANENV_E_INVALID, "intra net: unknown input layout %d", m->input_layout);
     }
-    const int out_dim = head_out ? head_out : (critic ? 1 : (intra ? 3 : 2 * S)), L = m->n_hidden + 1;
+    const int out_dim = NET_ROLES[role].out_s * S + NET_ROLES[role].out_1, L = m->n_hidden + 1;
     if (m->dims[0] != in_dim) return fail(h, RANENV_E_INVALID, "%s net: input width %d, the observation has %d", who, m->dims[0], in_dim);
     for (int i = 1; i < L; i++)
         if (m->dims[i] < 1 || m->dims[i] > NET_MAX_WIDTH) return fail(h, RANENV_E_INVALID, "%s net: hidden width %d (1..%d)", who, m->dims[i], NET_MAX_WIDTH);
@@ -1141,14 +1146,33 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, bool intra, PolicyNe
     return RANENV_OK;
 }
 
-static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, hipStream_t s, float *dst = nullptr)
+static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, hipStream_t s, float *dst)
 {
-    if (!dst) dst = h->d_net_w;
     for (int l = 0; l < net.n_layers; l++) {
         const int K = m->dims[l], N = m->dims[l + 1];
         HIP_TRY(h, hipMemcpy2DAsync(dst + net.w_off[l], sizeof(float) * net.kp[l], m->weight[l], sizeof(float) * K, sizeof(float) * K, N,
                                     hipMemcpyDeviceToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(dst + net.b_off[l], m->bias[l], sizeof(float) * N, hipMemcpyDeviceToDevice, s));
+    }
+    return RANENV_OK;
+}
+
+// The nets laid out in `floats` floats (net_layout; a null `m`: none) into the packed buffer *buf: grown when needed -- the outgrown
+// one stays allocated until ranenv_destroy, the launches of earlier calls may still read it -- else zeroed; then the layers are copied.
+struct NetSrc { const ranenv_mlp *m; PolicyNet *net; };
+static int net_bind(ranenv_handle h, float **buf, long long *cap, long long floats, hipStream_t s, std::initializer_list<NetSrc> nets)
+{
+    if (floats > *cap) {
+        const int rc = dev_alloc(h, buf, (size_t)floats);
+        if (rc != RANENV_OK) return rc;
+        *cap = floats;
+    } else {
+        HIP_TRY(h, hipMemsetAsync(*buf, 0, sizeof(float) * (size_t)floats, s));
+    }
+    for (const NetSrc &n : nets) {
+        n.net->w = *buf;
+        const int rc = n.m ? net_copy(h, n.m, *n.net, s, *buf) : RANENV_OK;
+        if (rc != RANENV_OK) return rc;
     }
     return RANENV_OK;
 }
@@ -1172,32 +1196,32 @@ static int net_use(ranenv_handle h, KP &kp)
     return 1;
 }
 
+static bool head_policy(ranenv_handle h) { return h->kp.policy == RANENV_POLICY_HEAD_NETWORK; }
+
+// The policy launches' inputs and outputs under the handle's policy (NETWORK, or HEAD_NETWORK: the head observation as obs_inter)
 static PolicyIO net_io(ranenv_handle h, const KP &kp)
 {
+    const bool head = head_policy(h);
     PolicyIO io{};
     io.B = h->cfg.batch; io.S = h->cfg.n_slices; io.Us = h->cfg.max_ues_slice; io.W = 2 * io.Us + 9;
-    io.stochastic = h->net_stochastic; io.env_id_base = h->kp.env_id_base; io.seed = h->net_seed;
-    io.obs_inter = kp.obs_inter; io.obs_intra = kp.obs_intra;
-    io.mask_inter = ST_mask_inter(h->kp); io.mask_intra = ST_mask_intra(h->kp);
-    io.episode_no = ST_episode_no(h->kp); io.step_no = ST_step_no(h->kp);
-    io.scores = h->d_net_scores; io.intra = h->d_net_intra;
-    return io;
-}
-
-static HeadIO head_io(ranenv_handle h)
-{
-    HeadIO io{};
-    io.B = h->cfg.batch; io.S = h->cfg.n_slices; io.dist = h->head_dist;
-    io.stochastic = h->head_stochastic; io.env_id_base = h->kp.env_id_base; io.seed = h->head_seed;
-    io.obs_head = h->kp.head_obs; io.log_std = h->head_dist == RANENV_HEAD_DIST_GAUSS_CLIP ? h->d_head_log_std : nullptr;
+    io.env_id_base = h->kp.env_id_base;
     io.episode_no = ST_episode_no(h->kp); io.step_no = ST_step_no(h->kp);
     io.scores = h->d_net_scores;
+    if (head) {
+        io.dist = h->head_dist; io.stochastic = h->head_stochastic; io.seed = h->head_seed;
+        io.obs_inter = h->kp.head_obs; io.log_std = h->head_dist == RANENV_HEAD_DIST_GAUSS_CLIP ? h->d_head_log_std : nullptr;
+        return io;
+    }
+    io.stochastic = h->net_stochastic; io.seed = h->net_seed;
+    io.obs_inter = kp.obs_inter; io.obs_intra = kp.obs_intra;
+    io.mask_inter = ST_mask_inter(h->kp); io.mask_intra = ST_mask_intra(h->kp);
+    io.intra = h->d_net_intra;
     return io;
 }
 
 static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
 {
-    if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return launch_head_policy(s, h->head_net, head_io(h), e0, n);
+    if (head_policy(h)) return launch_head_policy(s, h->head_net, net_io(h, kp), e0, n);
     return launch_policy(s, h->net_inter, h->net_has_intra ? &h->net_intra : nullptr, net_io(h, kp), e0, n);
 }
 
@@ -1216,24 +1240,12 @@ int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ra
     if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice net is required (intra may be NULL)");
     PolicyNet ni{}, na{};
     long long off = 0;
-    int rc = net_layout(h, inter, false, ni, off);
-    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, true, na, off);
+    int rc = net_layout(h, inter, NET_INTER, ni, off);
+    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, NET_INTRA, na, off);
     if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t s = (hipStream_t)stream_;
     rc = net_action_buffers(h);
-    if (rc != RANENV_OK) return rc;
-    if (off > h->net_cap) {
-        // (the launches of earlier TTIs may still read the old buffer: it stays allocated until ranenv_destroy)
-        rc = dev_alloc(h, &h->d_net_w, (size_t)off);
-        if (rc != RANENV_OK) return rc;
-        h->net_cap = off;
-    } else {
-        HIP_TRY(h, hipMemsetAsync(h->d_net_w, 0, sizeof(float) * (size_t)off, s));
-    }
-    ni.w = h->d_net_w; na.w = h->d_net_w;
-    rc = net_copy(h, inter, ni, s);
-    if (rc == RANENV_OK && intra) rc = net_copy(h, intra, na, s);
+    if (rc == RANENV_OK) rc = net_bind(h, &h->d_net_w, &h->net_cap, off, (hipStream_t)stream_, {{inter, &ni}, {intra, &na}});
     if (rc != RANENV_OK) return rc;
     h->net_inter = ni; h->net_intra = na; h->net_has_intra = intra != nullptr;
     h->net_stochastic = stochastic != 0; h->net_seed = seed; h->net_on = true;
@@ -1257,40 +1269,14 @@ int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ran
         return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, h->net_intra.layout);
     PolicyNet ni{}, na{};
     long long off = 0;
-    int rc = net_layout(h, inter, false, ni, off, true);
-    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, true, na, off, true);
+    int rc = net_layout(h, inter, NET_INTER_VALUE, ni, off);
+    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, NET_INTRA_VALUE, na, off);
     if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t s = (hipStream_t)stream_;
-    if (off > h->val_cap) {
-        // (the launches of earlier calls may still read the old buffer: it stays allocated until ranenv_destroy)
-        rc = dev_alloc(h, &h->d_val_w, (size_t)off);
-        if (rc != RANENV_OK) return rc;
-        h->val_cap = off;
-    } else {
-        HIP_TRY(h, hipMemsetAsync(h->d_val_w, 0, sizeof(float) * (size_t)off, s));
-    }
-    ni.w = h->d_val_w; na.w = h->d_val_w;
-    rc = net_copy(h, inter, ni, s, h->d_val_w);
-    if (rc == RANENV_OK && intra) rc = net_copy(h, intra, na, s, h->d_val_w);
+    rc = net_bind(h, &h->d_val_w, &h->val_cap, off, (hipStream_t)stream_, {{inter, &ni}, {intra, &na}});
     if (rc != RANENV_OK) return rc;
     h->val_inter = ni; h->val_intra = na; h->val_has_intra = intra != nullptr; h->val_on = true;
     return RANENV_OK;
-}
-
-// One head net into its packed buffer (grown when needed; the old one stays allocated until ranenv_destroy: launches of earlier
-// calls may still read it)
-static int head_net_bind(ranenv_handle h, const ranenv_mlp *m, PolicyNet &net, long long off, float **buf, long long *cap, hipStream_t s)
-{
-    if (off > *cap) {
-        const int rc = dev_alloc(h, buf, (size_t)off);
-        if (rc != RANENV_OK) return rc;
-        *cap = off;
-    } else {
-        HIP_TRY(h, hipMemsetAsync(*buf, 0, sizeof(float) * (size_t)off, s));
-    }
-    net.w = *buf;
-    return net_copy(h, m, net, s, *buf);
 }
 
 int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int32_t dist, const float *dev_log_std, int32_t stochastic,
@@ -1304,13 +1290,13 @@ int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int
     const int S = h->cfg.n_slices;
     PolicyNet net{};
     long long off = 0;
-    int rc = net_layout(h, actor, false, net, off, false, dist == RANENV_HEAD_DIST_GAUSS_TANH ? 2 * S : S);
+    int rc = net_layout(h, actor, dist == RANENV_HEAD_DIST_GAUSS_TANH ? NET_HEAD_TANH : NET_HEAD_CLIP, net, off);
     if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream_;
     rc = net_action_buffers(h);
     if (rc == RANENV_OK && !h->d_head_log_std) rc = dev_alloc(h, &h->d_head_log_std, (size_t)S);
-    if (rc == RANENV_OK) rc = head_net_bind(h, actor, net, off, &h->d_head_w, &h->head_cap, s);
+    if (rc == RANENV_OK) rc = net_bind(h, &h->d_head_w, &h->head_cap, off, s, {{actor, &net}});
     if (rc != RANENV_OK) return rc;
     if (dev_log_std) HIP_TRY(h, hipMemcpyAsync(h->d_head_log_std, dev_log_std, sizeof(float) * (size_t)S, hipMemcpyDeviceToDevice, s));
     h->head_net = net; h->head_dist = dist; h->head_stochastic = stochastic != 0; h->head_seed = seed; h->head_on = true;
@@ -1323,10 +1309,10 @@ int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, voi
     if (!critic) return fail(h, RANENV_E_INVALID, "the head critic is required");
     PolicyNet net{};
     long long off = 0;
-    int rc = net_layout(h, critic, false, net, off, true, 1);
+    int rc = net_layout(h, critic, NET_HEAD_VALUE, net, off);
     if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = head_net_bind(h, critic, net, off, &h->d_head_val_w, &h->head_val_cap, (hipStream_t)stream_);
+    rc = net_bind(h, &h->d_head_val_w, &h->head_val_cap, off, (hipStream_t)stream_, {{critic, &net}});
     if (rc != RANENV_OK) return rc;
     h->head_val = net; h->head_val_on = true;
     return RANENV_OK;
@@ -1625,6 +1611,15 @@ int ranenv_set_partitions(ranenv_handle h, int32_t n_parts)
 // without the host: the advance kernel + the step kernel in RESET mode follow that TTI's step on the partition's stream.  They are
 // only enqueued for TTIs at which some env of the partition finishes: the step counters are read once at the start and followed on
 // the host (nothing but this rollout changes them until it returns).
+// ranenv_collect / ranenv_collect_head: the caller's record, from either public struct
+struct Record {
+    PolicyRec rec{};               // slot 0 of what the policy launches write (head: obs_inter / action_inter are its obs_head / action, cols = 1)
+    double *reward = nullptr;      // [T][B][reward_cols] the step's reward rows / the head kernel's pairs, written straight into the slots
+    int reward_cols = 0, gae_col = 0;      // GAE runs on rec.cols columns from column gae_col on
+    uint8_t *done = nullptr;
+    float *adv = nullptr, *vtarg = nullptr;
+};
+
 struct Rollout {
     int n_steps = 0;
     KP kp{};                       // the step's
@@ -1633,8 +1628,7 @@ struct Rollout {
     std::vector<int32_t> steps;
     AdvanceArgs adv{};
     KP kpr{};
-    const ranenv_trajectory *rec = nullptr;      // ranenv_collect: the record (null: a plain rollout)
-    const ranenv_head_trajectory *hrec = nullptr;   // ranenv_collect_head: the record
+    const Record *rec = nullptr;   // ranenv_collect / _head: the record (null: a plain rollout)
 };
 
 // TTIs from now until the first episode of envs [lo, hi) ends, that TTI included, between 1 and n.  `n_ends`: at how many different
@@ -1699,69 +1693,50 @@ static int collect_split_of(ranenv_handle h, const PolicyNet &a, const PolicyNet
     return (floats(a) + floats(*v)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
 }
 
-// ranenv_collect: TTI `t` of a partition's own count for envs [e0, e0 + n) on `s`.  The recording policy launches (actors, record,
-// critics) write slot t; the step writes its reward row and done flag straight into slot t (the kernels index them by env; the
-// reset behind an episode end writes neither, reset_behind), and the advance kernel reads that slot's flags.  Behind the call's
-// last TTI -- and behind its reset, if any -- the critics run once more on the observation as it stands: vf[T].
+// ranenv_collect / ranenv_collect_head: TTI `t` of a partition's own count for envs [e0, e0 + n) on `s`.  The recording policy launches
+// (actors, record, critics) write slot t; the step writes its reward row (under a head policy: the head kernel behind it its reward
+// pair) and done flag straight into slot t (the kernels index them by env; the reset behind an episode end writes neither,
+// reset_behind), and the advance kernel reads that slot's flags.  Behind the call's last TTI -- and behind its reset, if any -- the
+// critics run once more on the observation as it stands: vf[T].
 static hipError_t collect_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
 {
-    const ranenv_trajectory &tr = *r.rec;
-    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, Us = (size_t)h->cfg.max_ues_slice, W = 2 * Us + 9, ts = (size_t)t;
-    const bool ia = h->net_has_intra, vc = tr.vf != nullptr, ic = vc && h->val_has_intra;
+    const Record &tr = *r.rec;
+    const bool head = head_policy(h);
+    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, Us = (size_t)h->cfg.max_ues_slice, W = 2 * Us + 9, C = (size_t)tr.rec.cols;
+    const bool ia = !head && h->net_has_intra, vc = tr.rec.vf != nullptr, ic = vc && !head && h->val_has_intra;
+    auto slot = [&](auto *p, size_t t_, size_t stride) { return p ? p + t_ * B * stride : nullptr; };
+    const size_t ts = (size_t)t;
     PolicyRec rec{};
-    rec.obs_inter = tr.obs_inter ? tr.obs_inter + ts * B * 10 * S : nullptr;
-    rec.mask_inter = tr.mask_inter ? tr.mask_inter + ts * B * S : nullptr;
-    rec.action_inter = tr.action_inter ? tr.action_inter + ts * B * S : nullptr;
+    rec.obs_inter = slot(tr.rec.obs_inter, ts, 10 * S);
+    rec.mask_inter = slot(tr.rec.mask_inter, ts, S);
+    rec.action_inter = slot(tr.rec.action_inter, ts, S);
     if (ia) {
-        rec.obs_intra = tr.obs_intra ? tr.obs_intra + ts * B * S * W : nullptr;
-        rec.mask_intra = tr.mask_intra ? tr.mask_intra + ts * B * S * Us : nullptr;
-        rec.action_intra = tr.action_intra ? tr.action_intra + ts * B * S : nullptr;
+        rec.obs_intra = slot(tr.rec.obs_intra, ts, S * W);
+        rec.mask_intra = slot(tr.rec.mask_intra, ts, S * Us);
+        rec.action_intra = slot(tr.rec.action_intra, ts, S);
     }
-    rec.logp = tr.logp ? tr.logp + ts * B * (S + 1) : nullptr;
-    rec.vf = vc ? tr.vf + ts * B * (S + 1) : nullptr;
-    rec.intra_actor = ia ? 1 : 0; rec.intra_critic = ic ? 1 : 0;
-    if (tr.reward) kpk.reward = tr.reward + ts * B * (S + 1);
-    if (tr.done) kpk.done = tr.done + ts * B;
+    rec.logp = slot(tr.rec.logp, ts, C);
+    rec.vf = slot(tr.rec.vf, ts, C);
+    rec.cols = (int)C; rec.intra_actor = ia ? 1 : 0; rec.intra_critic = ic ? 1 : 0;
+    if (tr.reward) (head ? kpk.head_reward : kpk.reward) = slot(tr.reward, ts, (size_t)tr.reward_cols);
+    if (tr.done) kpk.done = slot(tr.done, ts, 1);
     const PolicyIO io = net_io(h, kpk);
-    const PolicyNet *intra = ia ? &h->net_intra : nullptr, *vinter = vc ? &h->val_inter : nullptr, *vintra = ic ? &h->val_intra : nullptr;
+    const PolicyNet &actor = head ? h->head_net : h->net_inter, *intra = ia ? &h->net_intra : nullptr;
+    const PolicyNet *critic = vc ? (head ? &h->head_val : &h->val_inter) : nullptr, *vintra = ic ? &h->val_intra : nullptr;
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
     // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").
-    auto split = [&](const PolicyNet &a, const PolicyNet *v) { return collect_split_of(h, a, v); };
-    rec.split = split(h->net_inter, vinter) | (ia ? split(h->net_intra, vintra) << 1 : 0);
-    hipError_t le = launch_policy_collect(s, h->net_inter, intra, vinter, vintra, io, rec, e0, n);
+    rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, h->net_intra, vintra) << 1 : 0);
+    auto launch = [&](const PolicyRec &rc) {
+        return head ? launch_head_policy_collect(s, actor, critic, io, rc, e0, n) : launch_policy_collect(s, actor, intra, critic, vintra, io, rc, e0, n);
+    };
+    hipError_t le = launch(rec);
     if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
     if (le == hipSuccess) le = follow_episode_ends(h, r, e0, n, 1, s, kpk.done);
     if (le != hipSuccess || t + 1 < r.n_steps || !vc) return le;
     PolicyRec last{};
-    last.vf = tr.vf + (ts + 1) * B * (S + 1);
-    last.intra_critic = rec.intra_critic; last.critic_only = 1;
-    return launch_policy_collect(s, h->net_inter, intra, vinter, vintra, io, last, e0, n);
-}
-
-// ranenv_collect_head: the same for the head actor and critic.  The head kernel behind the step writes its reward pair straight into
-// slot t (the reset behind an episode end writes none), the step its done flag.
-static hipError_t collect_head_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
-{
-    const ranenv_head_trajectory &tr = *r.hrec;
-    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, ts = (size_t)t;
-    const bool vc = tr.vf != nullptr;
-    HeadRec rec{};
-    rec.obs_head = tr.obs_head ? tr.obs_head + ts * B * 10 * S : nullptr;
-    rec.action = tr.action ? tr.action + ts * B * S : nullptr;
-    rec.logp = tr.logp ? tr.logp + ts * B : nullptr;
-    rec.vf = vc ? tr.vf + ts * B : nullptr;
-    if (tr.reward_head) kpk.head_reward = tr.reward_head + ts * B * 2;
-    if (tr.done) kpk.done = tr.done + ts * B;
-    const HeadIO io = head_io(h);
-    const PolicyNet *critic = vc ? &h->head_val : nullptr;
-    rec.split = collect_split_of(h, h->head_net, critic);
-    hipError_t le = launch_head_policy_collect(s, h->head_net, critic, io, rec, e0, n);
-    if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
-    if (le == hipSuccess) le = follow_episode_ends(h, r, e0, n, 1, s, kpk.done);
-    if (le != hipSuccess || t + 1 < r.n_steps || !vc) return le;
-    HeadRec last{};
-    last.vf = tr.vf + (ts + 1) * B; last.critic_only = 1;
-    return launch_head_policy_collect(s, h->head_net, critic, io, last, e0, n);
+    last.vf = slot(tr.rec.vf, ts + 1, C);
+    last.cols = rec.cols; last.intra_critic = rec.intra_critic; last.critic_only = 1;
+    return launch(last);
 }
 
 // Every partition walks through the TTIs in launches of its own, on its own stream
@@ -1806,7 +1781,6 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
             kpk.n_tti = n_tti;
             h->last_rollout_launches++;
             if (r.rec) return collect_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
-            if (r.hrec) return collect_head_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
             hipError_t le = r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
             if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
             if (le != hipSuccess) return le;
@@ -1818,9 +1792,9 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
     return RANENV_OK;
 }
 
-// ranenv_rollout, and with `traj` ranenv_collect (gamma / lambda: its GAE pass)
+// ranenv_rollout, and with `rec` ranenv_collect / ranenv_collect_head (gamma / lambda: their GAE pass)
 static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream_,
-                       const ranenv_trajectory *traj, double gamma, double lambda, const ranenv_head_trajectory *htraj = nullptr, int reward_col = 0)
+                       const Record *rec = nullptr, double gamma = 0.0, double lambda = 0.0)
 {
     int rc = check_ready(h, nullptr, nullptr, true);
     if (rc != RANENV_OK) return rc;
@@ -1841,7 +1815,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
     r.net = net_use(h, r.kp);
     if (r.net < 0) return r.net;
-    r.rec = traj; r.hrec = htraj;
+    r.rec = rec;
     rc = compact_for(h, r.kp, stream, &r.kp.compact);
     if (rc != RANENV_OK) return rc;
     if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_plan)
@@ -1873,26 +1847,17 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     }
     rc = persist_ok ? rollout_persistent(h, r, stream) : rollout_chunks(h, r, stream);
     if (rc != RANENV_OK) return rc;
-    if (traj) {
-        // (the partitions have joined the caller's stream)  The caller's reward / done hold the last TTI's values, as after a rollout
-        const size_t B = (size_t)h->cfg.batch, C = (size_t)h->cfg.n_slices + 1, last = (size_t)n_steps - 1;
-        if (traj->reward && reward)
-            HIP_TRY(h, hipMemcpyAsync(reward, traj->reward + last * B * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
-        if (traj->done && done) HIP_TRY(h, hipMemcpyAsync(done, traj->done + last * B, B, hipMemcpyDeviceToDevice, stream));
-        if (traj->adv || traj->vtarg) {
-            launch_gae(stream, n_steps, h->cfg.batch, (int)C, traj->reward, (int)C, traj->vf, traj->done, gamma, lambda, traj->adv, traj->vtarg);
-            HIP_TRY(h, hipGetLastError());
-        }
-    }
-    if (htraj) {
-        // The bound head rewards and the caller's done hold the last TTI's values, as after a rollout
-        const size_t B = (size_t)h->cfg.batch, last = (size_t)n_steps - 1;
-        if (htraj->reward_head && h->kp.head_reward)
-            HIP_TRY(h, hipMemcpyAsync(h->kp.head_reward, htraj->reward_head + last * B * 2, sizeof(double) * B * 2, hipMemcpyDeviceToDevice, stream));
-        if (htraj->done && done) HIP_TRY(h, hipMemcpyAsync(done, htraj->done + last * B, B, hipMemcpyDeviceToDevice, stream));
-        if (htraj->adv || htraj->vtarg) {
-            launch_gae(stream, n_steps, h->cfg.batch, 1, htraj->reward_head + reward_col, 2, htraj->vf, htraj->done, gamma, lambda, htraj->adv,
-                       htraj->vtarg);
+    if (rec) {
+        // (the partitions have joined the caller's stream)  The caller's reward -- under a head policy: the bound head rewards -- and
+        // done hold the last TTI's values, as after a rollout
+        const size_t B = (size_t)h->cfg.batch, C = (size_t)rec->reward_cols, last = (size_t)n_steps - 1;
+        double *last_reward = head_policy(h) ? h->kp.head_reward : reward;
+        if (rec->reward && last_reward)
+            HIP_TRY(h, hipMemcpyAsync(last_reward, rec->reward + last * B * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
+        if (rec->done && done) HIP_TRY(h, hipMemcpyAsync(done, rec->done + last * B, B, hipMemcpyDeviceToDevice, stream));
+        if (rec->adv || rec->vtarg) {
+            launch_gae(stream, n_steps, h->cfg.batch, rec->rec.cols, rec->reward + rec->gae_col, (int)C, rec->rec.vf, rec->done, gamma, lambda,
+                       rec->adv, rec->vtarg);
             HIP_TRY(h, hipGetLastError());
         }
     }
@@ -1903,7 +1868,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
 
 int ranenv_rollout(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream)
 {
-    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, nullptr, 0.0, 0.0);
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream);
 }
 
 static_assert(sizeof(ranenv_trajectory) == RANENV_TRAJECTORY_BYTES, "ranenv_trajectory: 12 device pointers");
@@ -1921,7 +1886,12 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
     if (!h->val_on) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
     if (h->val_has_intra && !(h->net_has_intra && h->net_intra.layout == h->val_intra.layout))
         return fail(h, RANENV_E_STATE, "the intra value net was bound for another intra policy net (bind it again, ranenv_set_value_network)");
-    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, traj, gamma, lambda);
+    Record rec;
+    rec.rec.obs_inter = traj->obs_inter; rec.rec.obs_intra = traj->obs_intra; rec.rec.mask_inter = traj->mask_inter; rec.rec.mask_intra = traj->mask_intra;
+    rec.rec.action_inter = traj->action_inter; rec.rec.action_intra = traj->action_intra; rec.rec.logp = traj->logp; rec.rec.vf = traj->vf;
+    rec.rec.cols = rec.reward_cols = h->cfg.n_slices + 1;
+    rec.reward = traj->reward; rec.done = traj->done; rec.adv = traj->adv; rec.vtarg = traj->vtarg;
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec, gamma, lambda);
 }
 
 static_assert(sizeof(ranenv_head_trajectory) == RANENV_HEAD_TRAJECTORY_BYTES, "ranenv_head_trajectory: 8 device pointers");
@@ -1940,7 +1910,11 @@ int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_traj
     if (h->head_dist != RANENV_HEAD_DIST_GAUSS_CLIP)
         return fail(h, RANENV_E_INVALID, "only GAUSS_CLIP (PPO) head policies collect: SAC is off-policy and records no log-probabilities");
     if (!h->head_val_on) return fail(h, RANENV_E_STATE, "no head value network bound (ranenv_set_head_value_network)");
-    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, nullptr, gamma, lambda, traj, reward_col);
+    Record rec;
+    rec.rec.obs_inter = traj->obs_head; rec.rec.action_inter = traj->action; rec.rec.logp = traj->logp; rec.rec.vf = traj->vf;
+    rec.rec.cols = 1; rec.reward_cols = 2; rec.gae_col = reward_col;
+    rec.reward = traj->reward_head; rec.done = traj->done; rec.adv = traj->adv; rec.vtarg = traj->vtarg;
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec, gamma, lambda);
 }
 
 int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,

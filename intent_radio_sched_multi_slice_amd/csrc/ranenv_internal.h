@@ -178,53 +178,41 @@ struct PolicyNet {
     int layout;                           // RANENV_NET_IN_*
     int in_dim, out_dim;                  // unpadded
 };
+// One launch's inputs and action outputs.  A head policy's launch (RANENV_POLICY_HEAD_NETWORK: one row per env, scores into the same
+// buffer) has the bound head observation [B][10*S] as its obs_inter and reads no masks.
 struct PolicyIO {
     int B, S, Us, W;                      // W = 2 * Us + 9
+    int dist;                             // head: RANENV_HEAD_DIST_*
     int stochastic, env_id_base;
     unsigned long long seed;
     const float *obs_inter, *obs_intra;
+    const float *log_std;                 // head, GAUSS_CLIP: [S] the policy's state-independent parameter (null for GAUSS_TANH)
     const int8_t *mask_inter, *mask_intra;
     const int32_t *episode_no, *step_no;
     double *scores; uint8_t *intra;
 };
-// Enqueue the inter net (and the intra net when `intra` is non-null) for envs [e0, e0 + n_envs).
-hipError_t launch_policy(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &, int e0, int n_envs);
-// ranenv_collect: what the policy launch of one TTI records, every pointer already at that TTI's slot of the caller's ranenv_trajectory
-// (null = not recorded), and the critics it runs behind the actors for the same rows.
+// ranenv_collect / ranenv_collect_head: what the policy launch of one TTI records, every pointer already at that TTI's slot of the
+// caller's trajectory (null = not recorded), and the critics it runs behind the actors for the same rows.  A head record: obs_inter =
+// its obs_head, action_inter = its action, cols = 1.
 struct PolicyRec {
     float *obs_inter, *obs_intra; int8_t *mask_inter, *mask_intra;
     double *action_inter; uint8_t *action_intra;
-    float *logp, *vf;                     // [B][S + 1] of the slot: column 0 by the inter launch, column s + 1 by the intra launch
+    float *logp, *vf;                     // [B][cols] of the slot: column 0 by the inter / head launch, column s + 1 by the intra launch
+    int cols;                             // S + 1, head: 1
     int intra_actor, intra_critic;        // 0: the inter launch writes zeros into columns 1..S of logp / vf
     int critic_only;                      // the pass behind the last TTI: no actors, no record, vf of the observation as it stands
-    int split;                            // host side only: bit 0 / 1 = the inter / intra critic runs as a launch of its own behind the actor's
+    int split;                            // host side only: bit 0 / 1 = the inter (head) / intra critic runs as a launch of its own behind the actor's
 };
-// The recording launches of one TTI: actor + critic stack per agent kind in one launch each (`vinter` / `vintra` null = no critic of that
-// kind; `intra` null = no intra actor, then `vintra` is null too).  critic_only: the critics alone.
+// Enqueue the inter net (and the intra net when `intra` is non-null) / the head actor for envs [e0, e0 + n_envs).
+hipError_t launch_policy(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &, int e0, int n_envs);
+hipError_t launch_head_policy(hipStream_t, const PolicyNet &actor, const PolicyIO &, int e0, int n_envs);
+// The recording launches of one TTI: actor + critic stack per agent kind in one launch each (`vinter` / `vintra` / `critic` null = no
+// critic of that kind; `intra` null = no intra actor, then `vintra` is null too).  critic_only: the critics alone.
 hipError_t launch_policy_collect(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyNet *vinter, const PolicyNet *vintra,
                                  const PolicyIO &, const PolicyRec &, int e0, int n_envs);
-size_t policy_lds_bytes(const PolicyNet &);
-// Head policies (RANENV_POLICY_HEAD_NETWORK): one row per env, input the bound head observation, scores into the handle's score buffer
-struct HeadIO {
-    int B, S;
-    int dist;                             // RANENV_HEAD_DIST_*
-    int stochastic, env_id_base;
-    unsigned long long seed;
-    const float *obs_head;                // [B][10*S] the bound head observation
-    const float *log_std;                 // [S] GAUSS_CLIP: the policy's state-independent parameter (null for GAUSS_TANH)
-    const int32_t *episode_no, *step_no;
-    double *scores;                       // [B][S]
-};
-// ranenv_collect_head: what the head policy launch of one TTI records, every pointer at that TTI's slot (null = not recorded)
-struct HeadRec {
-    float *obs_head; double *action;      // [B][10*S], [B][S] (unclamped)
-    float *logp, *vf;                     // [B]
-    int critic_only;                      // the pass behind the last TTI: vf of the observation as it stands
-    int split;                            // host side only: the critic runs as a launch of its own behind the actor's
-};
-hipError_t launch_head_policy(hipStream_t, const PolicyNet &actor, const HeadIO &, int e0, int n_envs);
-hipError_t launch_head_policy_collect(hipStream_t, const PolicyNet &actor, const PolicyNet *critic, const HeadIO &, const HeadRec &, int e0,
+hipError_t launch_head_policy_collect(hipStream_t, const PolicyNet &actor, const PolicyNet *critic, const PolicyIO &, const PolicyRec &, int e0,
                                       int n_envs);
+size_t policy_lds_bytes(const PolicyNet &);
 
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block

@@ -10,10 +10,8 @@
 // k = 4 (l >> 4) .. + 3), one float4 of X per block row from LDS, 16 MFMAs -- MFMA j of the step sums k = 4q + j, the same
 // permutation on both operands.  The next W float4s are requested before the current step's MFMAs.
 // A third agent kind, "head" (RANENV_POLICY_HEAD_NETWORK: the SB3 actors of SchedTWC / SchedColORAN on the head observation), shares
-// the layer loop and has kernels of its own below.
+// everything but its distribution: a compile-time branch of the one body below.
 #include "ranenv_numeric.hpp"
-
-#include <mutex>
 
 namespace {
 
@@ -115,12 +113,41 @@ __device__ __forceinline__ void net_layers(const PolicyNet &net, float *&cur, fl
 
 constexpr double HALF_LN_2PI = 0.9189385332046727;      // 0.5 ln(2 pi)
 constexpr double LN_1E9 = 20.72326583694641;            // ln(1e9): -ln of the masked positions' std
+constexpr unsigned POLICY_TAG = 0x504F4C00u;            // "POL\0" / "HEA\0": counter word c3 of the IBSched / head policies' Philox draws,
+constexpr unsigned HEAD_TAG = 0x48454100u;              // + position (inter, head) or slice (intra)
 
-// kind 0: inter net, n_rows = envs; kind 1: intra net, n_rows = envs x S (row g of the launch = env e0 + g / S, slice g % S).
-// REC (ranenv_collect): the same actor forward and epilogue -- the actions do not differ by a bit -- which also writes the TTI's record
-// (observation and mask rows on their way into LDS; unclamped action, log-probability beside the handle's action buffers), then the
-// critic `vnet` (n_layers 0 = none) on the same 32 rows, re-read from L2, through the same two LDS buffers.
-template <bool REC>
+// The Philox words of (env e, its episode and step, `tag`) under the launch's seed
+__device__ __forceinline__ void draw_words(const PolicyIO &io, int e, unsigned tag, unsigned (&o)[4])
+{
+    philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], tag, (unsigned)io.seed,
+                  (unsigned)(io.seed >> 32), o);
+}
+
+// ... and the standard normal draw from them (Box-Muller on words 0 and 1)
+__device__ __forceinline__ double gauss_draw(const PolicyIO &io, int e, unsigned tag)
+{
+    unsigned o[4];
+    draw_words(io, e, tag, o);
+    const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+__device__ __forceinline__ int active_slices(const PolicyIO &io, int e)
+{
+    int n_act = 0;
+    for (int s = 0; s < io.S; s++) n_act += io.mask_inter[(size_t)e * io.S + s] != 0 ? 1 : 0;
+    return n_act;
+}
+
+// One workgroup's 32 rows of a launch through `net` and its epilogue.  kind 0: inter net, n_rows = envs; kind 1: intra net, n_rows =
+// envs x S (row g of the launch = env e0 + g / S, slice g % S).  HEAD (compile time; kind 0): a head policy -- one row per env, the
+// launch's io.obs_inter is the bound head observation [10*S], as the head kernel left it behind the previous TTI or reset; no masking
+// (the step kernel applies the slice permutation and the inactive-slice rule to these scores as it does to a caller's), a clipped or
+// tanh-squashed Gaussian (io.dist), and one column of logp / vf.
+// REC (ranenv_collect / ranenv_collect_head): the same actor forward and epilogue -- the actions do not differ by a bit -- which also
+// writes the TTI's record (observation and mask rows on their way into LDS; unclamped action, log-probability beside the handle's action
+// buffers), then the critic `vnet` (n_layers 0 = none) on the same 32 rows, re-read from L2, through the same two LDS buffers.
+template <bool HEAD, bool REC>
 __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNet &vnet, const PolicyIO &io, const PolicyRec &rec, int kind, int e0,
                                             int n_rows, float *lds)
 {
@@ -132,7 +159,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
     float *cur = lds, *nxt = lds + NET_ROWS * ldm;
 
     if (!REC || !rec.critic_only) {
-    if (REC) {      // the masks of this TTI
+    if (!HEAD && REC) {      // the masks of this TTI
         if (kind == 0 && rec.mask_inter)
             for (int i = tid; i < NET_ROWS * S; i += 256)
                 if (row0 + i / S < n_rows) rec.mask_inter[(size_t)(e0 + row0) * S + i] = io.mask_inter[(size_t)(e0 + row0) * S + i];
@@ -149,28 +176,41 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
 
     // ---- epilogue: actions ----------------------------------------------------------------------------------------------
     const int ld = net_ld(net.np[net.n_layers - 1]);
-    const unsigned k0 = (unsigned)io.seed, k1 = (unsigned)(io.seed >> 32);
     if (kind == 0) {
         double *zrow = (double *)nxt;                  // REC: the draws z [32][S] for the rows' log-probabilities (the idle LDS buffer)
         for (int i = tid; i < NET_ROWS * S; i += 256) {
             const int r = i / S, j = i - r * S, g = row0 + r;
             if (g >= n_rows) continue;
             const int e = e0 + g;
-            int n_act = 0;
-            for (int s = 0; s < S; s++) n_act += io.mask_inter[(size_t)e * S + s] != 0 ? 1 : 0;
-            double score = -1.0, raw = -1.0, z = 0.0;  // masked position (sorted mask: the first S - n_act positions)
-            if (j >= S - n_act) {
-                double m = (double)cur[r * ld + j];
+            double score, raw, z = 0.0;
+            if (HEAD) {
+                const bool squash = io.dist == RANENV_HEAD_DIST_GAUSS_TANH;
+                double a = (double)cur[r * ld + j];
                 if (io.stochastic) {
-                    unsigned o[4];
-                    philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], 0x504F4C00u + (unsigned)j,
-                                  k0, k1, o);
-                    const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
-                    z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-                    m = m + exp((double)cur[r * ld + S + j]) * z;
+                    double ls;
+                    if (squash) {
+                        ls = (double)cur[r * ld + S + j];
+                        ls = ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls);
+                    } else {
+                        ls = (double)io.log_std[j];
+                    }
+                    z = gauss_draw(io, e, HEAD_TAG + (unsigned)j);
+                    a = a + exp(ls) * z;
                 }
-                raw = m;
-                score = m < -1.0 ? -1.0 : (m > 1.0 ? 1.0 : m);
+                raw = a;
+                score = squash ? tanh(a) : (a < -1.0 ? -1.0 : (a > 1.0 ? 1.0 : a));
+            } else {
+                const int n_act = active_slices(io, e);
+                score = -1.0; raw = -1.0;              // masked position (sorted mask: the first S - n_act positions)
+                if (j >= S - n_act) {
+                    double m = (double)cur[r * ld + j];
+                    if (io.stochastic) {
+                        z = gauss_draw(io, e, POLICY_TAG + (unsigned)j);
+                        m = m + exp((double)cur[r * ld + S + j]) * z;
+                    }
+                    raw = m;
+                    score = m < -1.0 ? -1.0 : (m > 1.0 ? 1.0 : m);
+                }
             }
             io.scores[(size_t)e * S + j] = score;
             if (REC) {
@@ -184,17 +224,16 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                 const int g = row0 + r;
                 if (g >= n_rows) continue;
                 const int e = e0 + g;
-                int n_act = 0;
-                for (int s = 0; s < S; s++) n_act += io.mask_inter[(size_t)e * S + s] != 0 ? 1 : 0;
+                const int j0 = HEAD ? 0 : S - active_slices(io, e);      // the active positions: j0 .. S - 1
                 double lp = 0.0;
-                for (int j = S - n_act; j < S; j++) {
+                for (int j = j0; j < S; j++) {
                     const double z = zrow[r * S + j];
-                    lp += ((-0.5 * z) * z - (double)cur[r * ld + S + j]) - HALF_LN_2PI;
+                    lp += ((-0.5 * z) * z - (double)(HEAD ? io.log_std[j] : cur[r * ld + S + j])) - HALF_LN_2PI;
                 }
-                lp += (double)(S - n_act) * (LN_1E9 - HALF_LN_2PI);
-                float *out = rec.logp + (size_t)e * (S + 1);
+                if (!HEAD) lp += (double)j0 * (LN_1E9 - HALF_LN_2PI);
+                float *out = rec.logp + (size_t)e * rec.cols;
                 out[0] = (float)lp;
-                if (!rec.intra_actor)
+                if (!HEAD && !rec.intra_actor)
                     for (int s = 0; s < S; s++) out[1 + s] = 0.0f;
             }
         }
@@ -212,8 +251,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                 if (l2 > best) ch = 2;
             } else {
                 unsigned o[4];
-                philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], 0x504F4C00u + (unsigned)s,
-                              k0, k1, o);
+                draw_words(io, e, POLICY_TAG + (unsigned)s, o);
                 const double mx = fmax(fmax((double)l0, (double)l1), (double)l2);
                 const double x0 = exp((double)l0 - mx), x1 = exp((double)l1 - mx), x2 = exp((double)l2 - mx);
                 const double c0 = x0, c1 = x0 + x1, t = (double)o[2] * 0x1p-32 * (c1 + x2);
@@ -226,7 +264,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                     const double mx = fmax(fmax((double)l0, (double)l1), (double)l2);
                     const double sum = (exp((double)l0 - mx) + exp((double)l1 - mx)) + exp((double)l2 - mx);
                     const double lc = (double)(ch == 0 ? l0 : (ch == 1 ? l1 : l2));
-                    rec.logp[(size_t)e * (S + 1) + 1 + s] = (float)((lc - mx) - log(sum));
+                    rec.logp[(size_t)e * rec.cols + 1 + s] = (float)((lc - mx) - log(sum));
                 }
             }
         }
@@ -234,28 +272,26 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
     }
 
     // ---- critic: the same rows through `vnet`, one value per row ------------------------------------------------------------
-    if (REC && rec.vf) {
-        if (vnet.n_layers > 0) {
-            __syncthreads();                           // (the epilogue read both buffers)
-            cur = lds; nxt = lds + NET_ROWS * ldm;
-            const PolicyRec none{};
-            net_load_rows<false>(vnet, io, none, kind, e0, row0, n_rows, cur, tid);
-            __syncthreads();
-            net_layers(vnet, cur, nxt, lane, wave);
-            const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
-            for (int r = tid; r < NET_ROWS; r += 256) {
-                const int g = row0 + r;
-                if (g >= n_rows) continue;
-                if (kind == 0) {
-                    float *out = rec.vf + (size_t)(e0 + g) * (S + 1);
-                    out[0] = cur[r * ldv];
-                    if (!rec.intra_critic)
-                        for (int s = 0; s < S; s++) out[1 + s] = 0.0f;
-                } else {
-                    const size_t es = (size_t)e0 * S + g;
-                    const size_t e = es / (size_t)S;
-                    rec.vf[e * (S + 1) + 1 + (es - e * S)] = cur[r * ldv];
-                }
+    if (REC && rec.vf && vnet.n_layers > 0) {
+        __syncthreads();                               // (the epilogue read both buffers)
+        cur = lds; nxt = lds + NET_ROWS * ldm;
+        const PolicyRec none{};
+        net_load_rows<false>(vnet, io, none, kind, e0, row0, n_rows, cur, tid);
+        __syncthreads();
+        net_layers(vnet, cur, nxt, lane, wave);
+        const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
+        for (int r = tid; r < NET_ROWS; r += 256) {
+            const int g = row0 + r;
+            if (g >= n_rows) continue;
+            if (kind == 0) {
+                float *out = rec.vf + (size_t)(e0 + g) * rec.cols;
+                out[0] = cur[r * ldv];
+                if (!HEAD && !rec.intra_critic)
+                    for (int s = 0; s < S; s++) out[1 + s] = 0.0f;
+            } else {
+                const size_t es = (size_t)e0 * S + g;
+                const size_t e = es / (size_t)S;
+                rec.vf[e * rec.cols + 1 + (es - e * S)] = cur[r * ldv];
             }
         }
     }
@@ -264,125 +300,55 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
 __global__ void __launch_bounds__(256) ranenv_policy_kernel(PolicyNet net, PolicyIO io, int kind, int e0, int n_rows)
 {
     extern __shared__ float lds[];
-    policy_body<false>(net, net, io, PolicyRec{}, kind, e0, n_rows, lds);
+    policy_body<false, false>(net, net, io, PolicyRec{}, kind, e0, n_rows, lds);
 }
 
 __global__ void __launch_bounds__(256) ranenv_policy_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, int kind, int e0, int n_rows)
 {
     extern __shared__ float lds[];
-    policy_body<true>(net, vnet, io, rec, kind, e0, n_rows, lds);
+    policy_body<false, true>(net, vnet, io, rec, kind, e0, n_rows, lds);
 }
 
-// ---- head policies (RANENV_POLICY_HEAD_NETWORK): SchedTWC / SchedColORAN's SB3 actors ---------------------------------------------
-// One row per env: the row of the bound head observation [10*S], as the head kernel left it behind the previous TTI or reset,
-// through the same layer loop; an epilogue of its own.  No masking here: the step kernel applies the slice permutation and the
-// inactive-slice rule to these scores as it does to a caller's.
-constexpr unsigned HEAD_TAG = 0x48454100u;              // "HEA\0": counter word c3 of the head policy's Philox draws, + position
-
-template <bool REC>
-__device__ __forceinline__ void head_load_rows(const PolicyNet &net, const HeadIO &io, const HeadRec &rec, int e0, int row0, int n_rows, float *cur,
-                                               int tid)
-{
-    const int K0 = net.kp[0], ld0 = net_ld(K0), W = 10 * io.S;
-    for (int i = tid; i < NET_ROWS * K0; i += 256) {
-        const int r = i / K0, k = i - r * K0, g = row0 + r;
-        float v = 0.0f;
-        if (g < n_rows && k < W) {
-            v = io.obs_head[(size_t)(e0 + g) * (size_t)W + k];
-            if (REC && rec.obs_head) rec.obs_head[(size_t)(e0 + g) * (size_t)W + k] = v;
-        }
-        cur[r * ld0 + k] = v;
-    }
-}
-
-// REC (ranenv_collect_head): the same forward and epilogue -- the scores do not differ by a bit -- which also writes the TTI's record
-// (observation rows on their way into LDS, unclamped action, log-probability), then the critic `vnet` (n_layers 0 = none) on the
-// same 32 rows.
-template <bool REC>
-__device__ __forceinline__ void head_body(const PolicyNet &net, const PolicyNet &vnet, const HeadIO &io, const HeadRec &rec, int e0, int n_rows,
-                                          float *lds)
-{
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row0 = (int)blockIdx.x * NET_ROWS;
-    const int S = io.S;
-    int ldm = net_ld_max(net);
-    if (REC && vnet.n_layers > 0) { const int lv = net_ld_max(vnet); ldm = lv > ldm ? lv : ldm; }
-    float *cur = lds, *nxt = lds + NET_ROWS * ldm;
-
-    if (!REC || !rec.critic_only) {
-        head_load_rows<REC>(net, io, rec, e0, row0, n_rows, cur, tid);
-        __syncthreads();
-        net_layers(net, cur, nxt, lane, wave);
-
-        const int ld = net_ld(net.np[net.n_layers - 1]);
-        const unsigned k0 = (unsigned)io.seed, k1 = (unsigned)(io.seed >> 32);
-        const bool squash = io.dist == RANENV_HEAD_DIST_GAUSS_TANH;
-        double *zrow = (double *)nxt;                  // REC: the draws z [32][S] for the rows' log-probabilities (the idle LDS buffer)
-        for (int i = tid; i < NET_ROWS * S; i += 256) {
-            const int r = i / S, j = i - r * S, g = row0 + r;
-            if (g >= n_rows) continue;
-            const int e = e0 + g;
-            double a = (double)cur[r * ld + j], z = 0.0;
-            if (io.stochastic) {
-                double ls;
-                if (squash) {
-                    ls = (double)cur[r * ld + S + j];
-                    ls = ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls);
-                } else {
-                    ls = (double)io.log_std[j];
-                }
-                unsigned o[4];
-                philox4x32_10((unsigned)(io.env_id_base + e), (unsigned)io.episode_no[e], (unsigned)io.step_no[e], HEAD_TAG + (unsigned)j, k0, k1, o);
-                const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
-                z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-                a = a + exp(ls) * z;
-            }
-            io.scores[(size_t)e * S + j] = squash ? tanh(a) : (a < -1.0 ? -1.0 : (a > 1.0 ? 1.0 : a));
-            if (REC) {
-                if (rec.action) rec.action[(size_t)e * S + j] = a;
-                zrow[i] = z;
-            }
-        }
-        if (REC && rec.logp) {
-            __syncthreads();
-            for (int r = tid; r < NET_ROWS; r += 256) {
-                const int g = row0 + r;
-                if (g >= n_rows) continue;
-                double lp = 0.0;
-                for (int j = 0; j < S; j++) {
-                    const double z = zrow[r * S + j];
-                    lp += ((-0.5 * z) * z - (double)io.log_std[j]) - HALF_LN_2PI;
-                }
-                rec.logp[e0 + g] = (float)lp;
-            }
-        }
-    }
-
-    if (REC && rec.vf && vnet.n_layers > 0) {
-        __syncthreads();                               // (the epilogue read both buffers)
-        cur = lds; nxt = lds + NET_ROWS * ldm;
-        const HeadRec none{};
-        head_load_rows<false>(vnet, io, none, e0, row0, n_rows, cur, tid);
-        __syncthreads();
-        net_layers(vnet, cur, nxt, lane, wave);
-        const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
-        for (int r = tid; r < NET_ROWS; r += 256) {
-            const int g = row0 + r;
-            if (g < n_rows) rec.vf[e0 + g] = cur[r * ldv];
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) ranenv_head_policy_kernel(PolicyNet net, HeadIO io, int e0, int n_rows)
+__global__ void __launch_bounds__(256) ranenv_head_policy_kernel(PolicyNet net, PolicyIO io, int e0, int n_rows)
 {
     extern __shared__ float lds[];
-    head_body<false>(net, net, io, HeadRec{}, e0, n_rows, lds);
+    policy_body<true, false>(net, net, io, PolicyRec{}, 0, e0, n_rows, lds);
 }
 
-__global__ void __launch_bounds__(256) ranenv_head_policy_collect_kernel(PolicyNet net, PolicyNet vnet, HeadIO io, HeadRec rec, int e0, int n_rows)
+__global__ void __launch_bounds__(256) ranenv_head_policy_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, int e0, int n_rows)
 {
     extern __shared__ float lds[];
-    head_body<true>(net, vnet, io, rec, e0, n_rows, lds);
+    policy_body<true, true>(net, vnet, io, rec, 0, e0, n_rows, lds);
+}
+
+// The kernel's dynamic LDS limit raised to the widest net's need (2 x 32 x 516 floats = 129 KB), once per kernel
+template <auto KERNEL>
+hipError_t lds_attr()
+{
+    static const hipError_t attr = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
+    return attr;
+}
+
+dim3 grid_of(int rows) { return dim3((unsigned)((rows + NET_ROWS - 1) / NET_ROWS)); }
+
+// One agent kind's recording launch(es) of a TTI: actor + critic `vp` (null: none) fused, or -- split -- the actor's launch, then the
+// critic alone (the kernel's critic_only mode)
+template <bool HEAD>
+void collect_launch(hipStream_t s, int kind, const PolicyNet &a, const PolicyNet *vp, const PolicyIO &io, const PolicyRec &rec, int e0, int rows,
+                    bool split)
+{
+    const PolicyNet none{};               // (n_layers 0: no critic)
+    auto launch = [&](const PolicyNet &v, const PolicyRec &rc) {
+        const size_t x = ranenv_dev::policy_lds_bytes(a), y = v.n_layers > 0 ? ranenv_dev::policy_lds_bytes(v) : 0, lds = x > y ? x : y;
+        if constexpr (HEAD) hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid_of(rows), dim3(256), lds, s, a, v, io, rc, e0, rows);
+        else hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid_of(rows), dim3(256), lds, s, a, v, io, rc, kind, e0, rows);
+    };
+    if (!split || rec.critic_only || !vp) return launch(vp ? *vp : none, rec);
+    launch(none, rec);
+    PolicyRec crit{};
+    crit.vf = rec.vf; crit.cols = rec.cols; crit.intra_critic = rec.intra_critic; crit.critic_only = 1;
+    launch(*vp, crit);
 }
 
 }  // namespace
@@ -393,96 +359,33 @@ size_t policy_lds_bytes(const PolicyNet &net) { return sizeof(float) * 2 * NET_R
 
 hipError_t launch_policy(hipStream_t s, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &io, int e0, int n_envs)
 {
-    static std::once_flag once;
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] {      // (up to 2 x 32 x 516 floats = 129 KB of dynamic LDS)
-        attr = hipFuncSetAttribute((const void *)ranenv_policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
-    });
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(ranenv_policy_kernel, dim3((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS)), dim3(256), policy_lds_bytes(inter), s,
-                       inter, io, 0, e0, n_envs);
-    if (intra) {
-        const int rows = n_envs * io.S;
-        hipLaunchKernelGGL(ranenv_policy_kernel, dim3((unsigned)((rows + NET_ROWS - 1) / NET_ROWS)), dim3(256), policy_lds_bytes(*intra), s,
-                           *intra, io, 1, e0, rows);
-    }
+    if (const hipError_t attr = lds_attr<ranenv_policy_kernel>(); attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(ranenv_policy_kernel, grid_of(n_envs), dim3(256), policy_lds_bytes(inter), s, inter, io, 0, e0, n_envs);
+    if (intra) hipLaunchKernelGGL(ranenv_policy_kernel, grid_of(n_envs * io.S), dim3(256), policy_lds_bytes(*intra), s, *intra, io, 1, e0, n_envs * io.S);
     return hipGetLastError();
 }
 
 hipError_t launch_policy_collect(hipStream_t s, const PolicyNet &inter, const PolicyNet *intra, const PolicyNet *vinter, const PolicyNet *vintra,
                                  const PolicyIO &io, const PolicyRec &rec, int e0, int n_envs)
 {
-    static std::once_flag once;
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] {
-        attr = hipFuncSetAttribute((const void *)ranenv_policy_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
-    });
-    if (attr != hipSuccess) return attr;
-    const PolicyNet none{};               // (n_layers 0: no critic of that kind)
-    auto lds_of = [](const PolicyNet &a, const PolicyNet &v) {
-        const size_t x = policy_lds_bytes(a), y = v.n_layers > 0 ? policy_lds_bytes(v) : 0;
-        return x > y ? x : y;
-    };
-    // one kind's launch(es): actor + critic fused, or -- split -- the actor's launch, then the critic alone (the kernel's critic_only mode)
-    auto kind_launch = [&](int kind, const PolicyNet &a, const PolicyNet *vp, int rows, bool split) {
-        const dim3 grid((unsigned)((rows + NET_ROWS - 1) / NET_ROWS));
-        if (!split || rec.critic_only || !vp) {
-            const PolicyNet &v = vp ? *vp : none;
-            hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid, dim3(256), lds_of(a, v), s, a, v, io, rec, kind, e0, rows);
-            return;
-        }
-        hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid, dim3(256), lds_of(a, none), s, a, none, io, rec, kind, e0, rows);
-        PolicyRec crit{};
-        crit.vf = rec.vf; crit.intra_critic = rec.intra_critic; crit.critic_only = 1;
-        hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid, dim3(256), lds_of(a, *vp), s, a, *vp, io, crit, kind, e0, rows);
-    };
-    if (!rec.critic_only || vinter) kind_launch(0, inter, vinter, n_envs, (rec.split & 1) != 0);
-    if (intra && (!rec.critic_only || vintra)) kind_launch(1, *intra, vintra, n_envs * io.S, (rec.split & 2) != 0);
+    if (const hipError_t attr = lds_attr<ranenv_policy_collect_kernel>(); attr != hipSuccess) return attr;
+    if (!rec.critic_only || vinter) collect_launch<false>(s, 0, inter, vinter, io, rec, e0, n_envs, (rec.split & 1) != 0);
+    if (intra && (!rec.critic_only || vintra)) collect_launch<false>(s, 1, *intra, vintra, io, rec, e0, n_envs * io.S, (rec.split & 2) != 0);
     return hipGetLastError();
 }
 
-hipError_t launch_head_policy(hipStream_t s, const PolicyNet &actor, const HeadIO &io, int e0, int n_envs)
+hipError_t launch_head_policy(hipStream_t s, const PolicyNet &actor, const PolicyIO &io, int e0, int n_envs)
 {
-    static std::once_flag once;
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] {
-        attr = hipFuncSetAttribute((const void *)ranenv_head_policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
-    });
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(ranenv_head_policy_kernel, dim3((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS)), dim3(256), policy_lds_bytes(actor), s, actor,
-                       io, e0, n_envs);
+    if (const hipError_t attr = lds_attr<ranenv_head_policy_kernel>(); attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(ranenv_head_policy_kernel, grid_of(n_envs), dim3(256), policy_lds_bytes(actor), s, actor, io, e0, n_envs);
     return hipGetLastError();
 }
 
-hipError_t launch_head_policy_collect(hipStream_t s, const PolicyNet &actor, const PolicyNet *critic, const HeadIO &io, const HeadRec &rec, int e0,
+hipError_t launch_head_policy_collect(hipStream_t s, const PolicyNet &actor, const PolicyNet *critic, const PolicyIO &io, const PolicyRec &rec, int e0,
                                       int n_envs)
 {
-    static std::once_flag once;
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] {
-        attr = hipFuncSetAttribute((const void *)ranenv_head_policy_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
-    });
-    if (attr != hipSuccess) return attr;
-    const PolicyNet none{};               // (n_layers 0: no critic)
-    auto lds_of = [](const PolicyNet &a, const PolicyNet &v) {
-        const size_t x = policy_lds_bytes(a), y = v.n_layers > 0 ? policy_lds_bytes(v) : 0;
-        return x > y ? x : y;
-    };
-    const dim3 grid((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS));
-    // actor + critic fused, or -- split -- the actor's launch, then the critic alone (the kernel's critic_only mode)
-    if (!rec.split || rec.critic_only || !critic) {
-        const PolicyNet &v = critic ? *critic : none;
-        hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid, dim3(256), lds_of(actor, v), s, actor, v, io, rec, e0, n_envs);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid, dim3(256), lds_of(actor, none), s, actor, none, io, rec, e0, n_envs);
-    HeadRec crit{};
-    crit.vf = rec.vf; crit.critic_only = 1;
-    hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid, dim3(256), lds_of(actor, *critic), s, actor, *critic, io, crit, e0, n_envs);
+    if (const hipError_t attr = lds_attr<ranenv_head_policy_collect_kernel>(); attr != hipSuccess) return attr;
+    collect_launch<true>(s, 0, actor, critic, io, rec, e0, n_envs, (rec.split & 1) != 0);
     return hipGetLastError();
 }
 

@@ -210,6 +210,52 @@ def test_fused_and_split_critic_launches_agree(net):
         assert np.array_equal(runs[0][k], runs[1][k]) and np.array_equal(runs[0][k], runs[2][k]), k
 
 
+def test_a_critic_wider_and_deeper_than_its_actor():
+    """Actors [48] (padded to 64: the other branch of the LDS row stride) under critics [96, 96], so that the workgroup's LDS buffers are
+    sized by the critic and not by the actor; B = 40 (two workgroups of env rows with a tail of 8, 200 intra rows), T = 3 with
+    episodes ending at its last TTI.  Fused and split give one record; vf (intra columns and the bootstrap slot included) and logp
+    lie within the float64 bounds of collect_ref."""
+    _need_gpu()
+    B, n, seed, layout = 40, 3, 0x1234_5678_9ABC, "mask_obs"
+    lengths = np.asarray((3, 2, 5, 1), dtype=np.int32)[np.arange(B) % 4]
+
+    def make():
+        _, env, _ = cr.make_env("S5U25", "64x64", B, stochastic=True, seed=seed, autoreset=True, intra_input=layout)
+        a_inter, a_intra, _, _ = cr.nets(env.S, env.Us, [48], layout, seed=31)
+        _, _, v_inter, v_intra = cr.nets(env.S, env.Us, [96, 96], layout, seed=31)
+        env.set_policy_network(a_inter, a_intra, stochastic=True, seed=seed, intra_input=layout)
+        env.set_value_network(v_inter, v_intra)
+        env.set_max_steps(lengths)
+        env.reset()
+        return env, (a_inter, a_intra, v_inter, v_intra)
+
+    ref, _ = make()                # the Philox counters of every TTI, from a step() loop
+    counters = []
+    for _ in range(n):
+        v = ref.views()
+        counters.append((v["episode_number"].cpu().numpy().copy(), v["step_number"].cpu().numpy().copy()))
+        ref.step()
+    ref.close()
+    runs = []
+    for split in (0, 1):
+        env, (a_inter, a_intra, v_inter, v_intra) = make()
+        env.set_option("collect_split", split)
+        rec = _cpu(env.collect(n))
+        runs.append(rec)
+        assert rec["done"][-1].any() and not rec["done"][-1].all()
+        worst = {}
+        for t in range(n):
+            r, _ = cr.check_actor_record(rec, t, a_inter, a_intra, True, seed, counters[t][0], counters[t][1], layout)
+            r["vf"] = cr.check_values(rec["vf"][t], rec["obs_inter"][t], rec["obs_intra"][t], rec["mask_intra"][t], v_inter, v_intra, layout, f"vf[{t}]")
+            for k, x in r.items():
+                worst[k] = max(worst.get(k, 0.0), x)
+        worst["vf_T"] = cr.check_values(rec["vf"][n], env.obs_inter, env.obs_intra, env.views()["mask_intra"], v_inter, v_intra, layout, "vf[T]")
+        print(f"split {split}: worst error / bound: {worst}")
+        env.close()
+    for k in FIELDS:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+
+
 def test_null_fields_are_skipped():
     """A call that records only reward / vf / done / adv / vtarg gives the same five arrays as the full call."""
     _need_gpu()

@@ -372,6 +372,62 @@ def test_gae_on_the_other_column_null_fields_and_split_launches(autoreset):
     full.close()
 
 
+def test_a_critic_wider_and_deeper_than_its_actor():
+    """Actor [48] (padded to 64: the other branch of the LDS row stride) under a critic [96, 96], so that the workgroup's LDS buffers are
+    sized by the critic and not by the actor; B = 40 (two workgroups, a tail of 8), T = 3 with episodes ending at its last TTI.
+    Fused and split give one record; vf (the bootstrap slot included), logp and the unclamped action lie within the float64 bounds."""
+    _need_gpu()
+    B, n = 40, 3
+    lengths = np.asarray((3, 2, 5, 1), dtype=np.int32)[np.arange(B) % 4]
+
+    def make():
+        _, env, (_, log_std, _) = hr.make_env("S5U25", "64x64", "gauss_clip", B, stochastic=True, seed=SEED, autoreset=True)
+        actor = hr.mlp([10 * env.S, 48, env.S], "tanh", 41, hr.OUT_SCALE)
+        critic = hr.mlp([10 * env.S, 96, 96, 1], "tanh", 43)
+        env.set_head_policy_network(actor, "gauss_clip", log_std, stochastic=True, seed=SEED)
+        env.set_head_value_network(critic)
+        env.set_max_steps(lengths)
+        env.reset()
+        return env, (actor, log_std, critic)
+
+    ref, _ = make()                # the Philox counters of every TTI, from a step() loop
+    counters = []
+    for _ in range(n):
+        v = ref.views()
+        counters.append((v["episode_number"].cpu().numpy().copy(), v["step_number"].cpu().numpy().copy()))
+        ref.step()
+    ref.close()
+    recs = []
+    for split in (0, 1):
+        env, (actor, log_std, critic) = make()
+        env.set_option("collect_split", split)
+        r = {k: x.cpu().numpy().copy() for k, x in env.collect_head(n).items()}
+        recs.append(r)
+        assert r["done"][-1].any() and not r["done"][-1].all()
+        worst = {"logp": 0.0, "vf": 0.0, "action": 0.0}
+        for t in range(n + 1):
+            obs = r["obs_head"][t] if t < n else env.head_obs.cpu().numpy()
+            y, bound = hr.value_ref(obs, critic)
+            err = np.abs(r["vf"][t] - y)
+            assert np.all(err <= bound), f"vf[{t}]: worst {np.max(err / bound):.3g} of the bound"
+            worst["vf"] = max(worst["vf"], float(np.max(err / bound)))
+            if t == n:
+                break
+            z = hr.noise(np.arange(B), counters[t][0], counters[t][1], env.S, SEED)
+            a = hr.HeadRef(obs, actor, "gauss_clip", log_std, z)
+            err = np.abs(r["action"][t] - a.action)
+            assert np.all(err <= a.action_bound), f"action[{t}]"
+            worst["action"] = max(worst["action"], float(np.max(err / a.action_bound)))
+            lp, lb = hr.logp_ref(log_std, z, B)
+            err = np.abs(r["logp"][t].astype(np.float64) - lp)
+            assert np.all(err <= lb), f"logp[{t}]: worst {np.max(err / lb):.3g} of the bound"
+            worst["logp"] = max(worst["logp"], float(np.max(err / lb)))
+        print(f"split {split}: worst error / bound {worst}")
+        env.close()
+    for k in recs[0]:
+        assert np.array_equal(recs[0][k], recs[1][k]), k
+
+
 # ---- 7. error paths, through the C ABI ------------------------------------------------------------------------------------------------
 def test_error_paths():
     _need_gpu()
