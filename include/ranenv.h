@@ -710,6 +710,85 @@ int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, voi
 int ranenv_get_head_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t *episode_slots);
 int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, int32_t reward_col, double gamma, double lambda,
                         float *dev_obs_inter, float *dev_obs_intra, double *dev_reward, uint8_t *dev_done, void *stream);
+
+/* Off-policy collection (SAC): the reference builds every SB3 agent in two flavours, agent_type "ppo" and "sac"
+ * (agents/sched_twc.py:111-133, agents/sched_colran.py:111-133, agents/sb3_sched.py:104-120, agents/sb3_pf_sched.py); the SAC
+ * flavour is SB3's SAC("MlpPolicy", ...): an Actor (RANENV_HEAD_DIST_GAUSS_TANH above), two ContinuousCritic Q-nets and their
+ * target copies, a ReplayBuffer, uniform minibatches, and per minibatch the soft Bellman target.  What of that needs no gradient
+ * runs here: the replay ring, the sampler, the target.  The learner's losses, optimiser and polyak update stay with the caller.
+ * stable-baselines3 is not part of this project's test environment: everything below is restated from SB3's documented module
+ * layout, parity with SB3 itself is UNPINNED (as for the head policies above).
+ *
+ * ranenv_replay: the ring, caller-owned device memory as for ranenv_trajectory; all five pointers are required.
+ *     capacity    C >= 2 slots; the k-th TTI recorded since binding goes to slot k % C
+ *     obs         f32 [C][B][10*S]   the head observation the TTI's action was computed from
+ *     next_obs    f32 [C][B][10*S]   the row of the bound dev_obs_head as the head kernel left it behind that TTI's step, BEFORE
+ *                                    any auto-reset of that env: for a transition with done != 0 the terminal observation (the one
+ *                                    ranenv_autoreset hands out as dev_term_obs_head, SB3's infos["terminal_observation"]), for
+ *                                    every other transition bit for bit the next slot's obs
+ *     action      f64 [C][B][S]      the score the step CONSUMED: tanh(a) (GAUSS_TANH), clamp(a, -1, 1) (GAUSS_CLIP) -- not the
+ *                                    unclamped sample ranenv_collect_head records
+ *     reward_head f64 [C][B][2]      the head kernel's pair (SchedTWC, SchedColORAN), written straight into the slot
+ *     done        u8  [C][B]
+ * ranenv_bind_replay: NULL unbinds; binding zeroes the write count.  capacity < 2 or a NULL pointer: RANENV_E_INVALID.  Rows move as
+ *   8-byte words: obs, next_obs, action, reward_head, the bound dev_obs_head and the sampler's dev_obs / dev_next_obs must be 8-byte
+ *   aligned (RANENV_E_INVALID otherwise; any allocator's blocks are).
+ * ranenv_collect_replay: ranenv_rollout of n_steps TTIs under RANENV_POLICY_HEAD_NETWORK that records every TTI into the ring:
+ *   either distribution, stochastic or not, any number of partitions, with and without auto-reset, both SE modes; no critic, no
+ *   log-probability, value or GAE work.  Per TTI and partition, on the partition's stream: the actor runs, the observation rows it read
+ *   and its scores are copied into the slot, the step and the head kernel write the slot's reward_head and done,
+ *   the observation rows are copied into the slot's next_obs, then -- auto-reset -- the envs whose episode ended restart.  Env
+ *   state, the caller's output buffers, the bound head buffers, episode / head / slice metrics and ranenv_get_policy_actions
+ *   afterwards are bit for bit what ranenv_rollout leaves under the same net and seed.  n_steps < 1 or n_steps > capacity:
+ *   RANENV_E_INVALID; no ring bound, another policy than HEAD_NETWORK, no head net or no head outputs bound: RANENV_E_STATE.
+ * ranenv_get_replay_count: TTIs recorded since binding (a host counter: what the calls so far have enqueued).
+ *
+ * ranenv_replay_sample: n transitions drawn uniformly (with replacement) from the filled part of the ring.  Row i of a call:
+ *     (o0, o1, ..) = Philox-4x32-10(counter = (i lo, i hi, draw lo, draw hi), key = (seed lo, seed hi));  u = o1 << 32 | o0
+ *     N = min(written, C) * B;  index = floor(u * N / 2^64) (the high word of the 128-bit product);  slot = index / B, env = index % B
+ *   -- a function of (seed, draw, i, N) alone.  While the ring is not yet full its filled slots are 0 .. written - 1: no unfilled
+ *   row can be drawn.  Outputs, in the learner's dtypes: dev_obs / dev_next_obs f32 [n][10*S] and dev_done u8 [n] copied,
+ *   dev_action f32 [n][S] and dev_reward f32 [n] = reward_head[reward_col] each rounded once to float32, dev_index i64 [n] (may
+ *   be NULL: for a prioritised scheme of the caller's).  Nothing recorded yet or no ring: RANENV_E_STATE; reward_col not 0 / 1,
+ *   n < 1 or a NULL output other than dev_index: RANENV_E_INVALID.
+ *
+ * ranenv_set_sac_critics: q1, q2 = SB3's ContinuousCritic members (qf0, qf1; bind the TARGET critics): ranenv_mlp of 1..4 hidden
+ *   layers, widths 1..512, input [obs (10*S) | action (S)], dims[0] = 11*S, one output, both of the same shape (else
+ *   RANENV_E_INVALID).  Copied into a packed buffer of their own: rebinding the actor leaves them as they are and vice versa.
+ * ranenv_sac_targets: the soft Bellman target of n rows of caller memory (any rows: they need not come from the ring), under the
+ *   bound head actor -- GAUSS_TANH, else RANENV_E_STATE, as is no critics bound -- and the bound critics.  n < 1 or a NULL
+ *   dev_next_obs / dev_reward / dev_done / dev_target: RANENV_E_INVALID.  Per row i, float64 arithmetic on the float32 net
+ *   outputs, nothing contracted, every output rounded once:
+ *     (mu | log_std) = actor(next_obs_i);   ls_j = clamp(log_std_j, -20, 2)
+ *     z_j  = Box-Muller draw (u1, u2, z as for the head policies) of Philox-4x32-10(counter = (i lo, i hi, draw lo, 0x53414300 + j),
+ *            key = (seed lo, seed hi));  0 when stochastic == 0
+ *     g_j  = mu_j + exp(ls_j) * z_j;   a_j = tanh(g_j);   a32_j = (float)a_j                       -> dev_next_action [n][S] or NULL
+ *     logp = sum over j ascending of ((((-0.5 z_j) z_j - ls_j) - 0.5 ln(2 pi)) - log((1.0 - a_j * a_j) + 1e-6))
+ *                                                                                                  -> dev_next_logp [n] or NULL
+ *            (SB3's SquashedDiagGaussianDistribution: the Gaussian's log-probability of the kept pre-tanh sample, epsilon 1e-6)
+ *     q1, q2 = Q1([next_obs_i | a32]), Q2([next_obs_i | a32])                                      -> dev_q [n][2] or NULL
+ *     target = (float)(reward_i + (done_i ? 0.0 : 1.0) * (gamma * (fmin((double)q1, (double)q2) - ent_coef * logp)))
+ *   Rows are independent: a call on the first m rows of the same arrays gives those rows bit for bit. */
+typedef struct {
+    int32_t capacity;
+    int32_t reserved;
+    float   *obs;
+    float   *next_obs;
+    double  *action;
+    double  *reward_head;
+    uint8_t *done;
+} ranenv_replay;
+#define RANENV_REPLAY_BYTES 48
+int ranenv_bind_replay(ranenv_handle h, const ranenv_replay *ring);
+int ranenv_collect_replay(ranenv_handle h, int32_t n_steps, float *dev_obs_inter, float *dev_obs_intra, double *dev_reward, uint8_t *dev_done,
+                          void *stream);
+int ranenv_get_replay_count(ranenv_handle h, int64_t *written);
+int ranenv_replay_sample(ranenv_handle h, int64_t n, uint64_t seed, uint64_t draw, int32_t reward_col, float *dev_obs, float *dev_action,
+                         float *dev_reward, float *dev_next_obs, uint8_t *dev_done, int64_t *dev_index, void *stream);
+int ranenv_set_sac_critics(ranenv_handle h, const ranenv_mlp *q1, const ranenv_mlp *q2, void *stream);
+int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, const float *dev_reward, const uint8_t *dev_done, double gamma,
+                       double ent_coef, int32_t stochastic, uint64_t seed, uint64_t draw, float *dev_target, float *dev_next_action,
+                       float *dev_next_logp, float *dev_q, void *stream);
 /* SchedColORAN's slice-name table (sched_colran.py:356-367) as data: host array [count][S], bit 0 = eMBB,
  * bit 1 = URLLC, for scenario-pool rows [first, first+count).  Default 0 (no reward term). */
 int ranenv_set_slice_usecase(ranenv_handle h, int32_t first, int32_t count, const int32_t *usecase, void *stream);

@@ -89,6 +89,11 @@ class HeadTrajectory(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in HEAD_TRAJECTORY_FIELDS]
 
 
+class Replay(C.Structure):
+    """ranenv_replay: the caller-owned replay ring of ranenv_collect_replay, [slot]-major device pointers (all required)."""
+    _fields_ = [("capacity", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_void_p) for n in ("obs", "next_obs", "action", "reward_head", "done")]
+
+
 class Views(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in VIEW_FIELDS]
 
@@ -153,6 +158,12 @@ FUNCTIONS = {
     "ranenv_collect_head": (C.c_int, [_P, _I32, C.POINTER(HeadTrajectory), _I32, _F64, _F64] + [_P] * 5),
     "ranenv_enable_slice_metrics": (C.c_int, [_P, _I32, _P]),
     "ranenv_get_slice_metrics": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "ranenv_bind_replay": (C.c_int, [_P, C.POINTER(Replay)]),
+    "ranenv_collect_replay": (C.c_int, [_P, _I32] + [_P] * 5),
+    "ranenv_get_replay_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "ranenv_replay_sample": (C.c_int, [_P, _I64, C.c_uint64, C.c_uint64, _I32] + [_P] * 7),
+    "ranenv_set_sac_critics": (C.c_int, [_P, C.POINTER(Mlp), C.POINTER(Mlp), _P]),
+    "ranenv_sac_targets": (C.c_int, [_P, _I64, _P, _P, _P, _F64, _F64, _I32, C.c_uint64, C.c_uint64] + [_P] * 5),
 }
 EXPORTS = tuple(FUNCTIONS)
 

@@ -544,6 +544,72 @@ def head_policy_logp(log_std, z=None, B: Optional[int] = None):
     return lp.astype(np.float32)
 
 
+# --------------------------------------------------------------------------------------------
+# Off-policy (SAC) collection: the sampler's index rule and the soft Bellman target, restated (include/ranenv.h)
+# --------------------------------------------------------------------------------------------
+SAC_TAG = 0x53414300             # counter word c3 of the target's Philox draws: tag + position
+
+
+def replay_sample_index(n: int, seed: int, draw: int, written: int, capacity: int, B: int) -> np.ndarray:
+    """The ring rows ``replay_sample()`` draws: int64 [n], row i = floor(u_i * N / 2^64) with N = min(written, capacity) * B and
+    u_i = o1 << 32 | o0 of Philox-4x32-10(counter = (i lo, i hi, draw lo, draw hi), key = seed).  slot = index // B, env = index % B."""
+    i = np.arange(int(n), dtype=np.uint64)
+    d = philox4x32_10(i & np.uint64(0xFFFFFFFF), i >> np.uint64(32), int(draw) & 0xFFFFFFFF, (int(draw) >> 32) & 0xFFFFFFFF,
+                      int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    N = min(int(written), int(capacity)) * int(B)
+    return np.array([((int(hi) << 32 | int(lo)) * N) >> 64 for lo, hi in zip(d[0], d[1])], dtype=np.int64)
+
+
+def sac_target_noise(n: int, S: int, seed: int, draw: int) -> np.ndarray:
+    """The target's draws z float64 [n, S]: Box-Muller of Philox words 0 / 1 at counter (row lo, row hi, draw lo, SAC_TAG + j),
+    key = seed."""
+    i = np.arange(int(n), dtype=np.uint64).reshape(-1, 1)
+    c3 = SAC_TAG + np.arange(S, dtype=np.int64)[None, :]
+    d = philox4x32_10(i & np.uint64(0xFFFFFFFF), i >> np.uint64(32), int(draw) & 0xFFFFFFFF, c3, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    u1 = (d[0].astype(np.float64) + 1.0) * 2.0 ** -32
+    u2 = d[1].astype(np.float64) * 2.0 ** -32
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+
+
+def sac_targets_torch(next_obs, reward, done, actor, q1, q2, gamma: float = 0.99, ent_coef: float = 0.0, stochastic: bool = True,
+                      seed: int = 0, draw: int = 0, activation: Optional[str] = None, device=None):
+    """What ``BatchedRanEnv.sac_targets`` computes, in plain torch / numpy (the normative statement; include/ranenv.h spells out the
+    same rules): SB3 SAC's target  r + gamma (1 - d) (min(Q1', Q2')(s', a') - ent_coef log pi(a'|s'))  with a' ~ pi(.|s').
+
+    ``next_obs`` [n, 10*S], ``reward`` [n], ``done`` [n]; ``actor`` -> (mu | log_std) [2S], ``q1`` / ``q2``: [obs | action] [11S] ->
+    1, as for ``batched_env.policy_net_layers`` (lists of (W, b): ``activation`` default relu).  Forwards in float32 (on ``device``:
+    default the CPU), epilogue in float64, every output rounded once to float32:
+      ls = clamp(log_std, -20, 2); g = mu + exp(ls) z (z = ``sac_target_noise``, 0 in the mode); a = tanh(g); a32 = float32(a)
+      logp = sum_j ((((-0.5 z) z - ls) - 0.5 ln 2 pi) - log((1 - a a) + 1e-6))   (the Gaussian's log-probability of g, SB3's epsilon)
+      target = float32(reward + (0 if done else 1) (gamma (min(Q1, Q2)([next_obs | a32]) - ent_coef logp)))
+    Returns a dict of CPU tensors: ``target`` [n], ``next_action`` [n, S], ``next_logp`` [n], ``q`` [n, 2] float32, and float64
+    ``mu`` / ``log_std`` (clamped) / ``z`` / ``logp64`` for inspection."""
+    from .batched_env import policy_net_layers
+    dev = torch.device("cpu") if device is None else torch.device(device)
+    x = torch.as_tensor(next_obs).detach().to(device=dev, dtype=torch.float32)
+    n, S = x.shape[0], x.shape[1] // 10
+    default = lambda net: activation if activation is not None or isinstance(net, torch.nn.Module) else "relu"  # noqa: E731
+    nets = [policy_net_layers(net, default(net), k, o) for net, k, o in ((actor, 10 * S, 2 * S), (q1, 11 * S, 1), (q2, 11 * S, 1))]
+    fwd = lambda inp, k: _mlp_forward(inp, [(w.to(dev), b.to(dev)) for w, b in nets[k][0]], nets[k][1])  # noqa: E731
+    out = fwd(x, 0).to(torch.float64)
+    mu, ls = out[:, :S], out[:, S:].clamp(LOG_STD_MIN, LOG_STD_MAX)
+    z = torch.from_numpy(sac_target_noise(n, S, seed, draw)).to(dev) if stochastic else torch.zeros_like(mu)
+    a = torch.tanh(mu + torch.exp(ls) * z)
+    a32 = a.to(torch.float32)
+    logp = torch.zeros(n, dtype=torch.float64, device=dev)
+    for j in range(S):                                          # ascending positions, as the kernel sums them
+        logp = logp + ((((-0.5 * z[:, j]) * z[:, j] - ls[:, j]) - HALF_LN_2PI) - torch.log((1.0 - a[:, j] * a[:, j]) + 1e-6))
+    xa = torch.cat([x, a32], dim=1)
+    q = torch.cat([fwd(xa, 1), fwd(xa, 2)], dim=1)
+    qmin = torch.minimum(q[:, 0].to(torch.float64), q[:, 1].to(torch.float64))
+    r = torch.as_tensor(reward).detach().to(device=dev, dtype=torch.float32).to(torch.float64)
+    nd = torch.where(torch.as_tensor(done).detach().to(dev) != 0, 0.0, 1.0).to(torch.float64)
+    target = (r + nd * (float(gamma) * (qmin - float(ent_coef) * logp))).to(torch.float32)
+    cpu = lambda t: t.detach().cpu()  # noqa: E731
+    return {"target": cpu(target), "next_action": cpu(a32), "next_logp": cpu(logp.to(torch.float32)), "q": cpu(q), "mu": cpu(mu), "log_std": cpu(ls),
+            "z": cpu(z), "logp64": cpu(logp)}
+
+
 def _sb3_sequential(state_dict, prefix: str, what: str):
     """(W, b) of the Linear layers of an SB3 ``create_mlp`` Sequential under ``prefix`` (indices 0, 2, 4, ...: activations between)."""
     found = {}

@@ -514,6 +514,107 @@ class BatchedRanEnv:
         return self._collect("collect_head", n_steps, record, _lib.HeadTrajectory, _lib.HEAD_TRAJECTORY_FIELDS, self.HEAD_TRAJECTORY_SHAPES,
                              "head_trajectories", (self.B, self.S), self._lib.ranenv_collect_head, (HEAD_REWARDS[reward], float(gamma), float(lam)))
 
+    # -- off-policy (SAC) collection: replay ring, sampler, targets (include/ranenv.h "Off-policy collection") ----------------------
+    REPLAY_SHAPES = {          # field -> (dtype, shape of one slot in terms of B, S)
+        "obs": (torch.float32, lambda B, S: (B, 10 * S)), "next_obs": (torch.float32, lambda B, S: (B, 10 * S)),
+        "action": (torch.float64, lambda B, S: (B, S)), "reward_head": (torch.float64, lambda B, S: (B, 2)),
+        "done": (torch.uint8, lambda B, S: (B,)),
+    }
+
+    def bind_replay(self, capacity: int) -> Dict[str, torch.Tensor]:
+        """Allocate and bind a replay ring of ``capacity`` TTIs (ranenv_bind_replay): a dict of ``[capacity, B, ...]`` tensors
+        ``obs`` / ``next_obs`` float32 [.., 10*S], ``action`` float64 [.., S] (the score the step consumed), ``reward_head`` float64
+        [.., 2], ``done`` uint8.  The k-th TTI recorded since binding goes to slot ``k % capacity``; binding zeroes the count."""
+        capacity = int(capacity)
+        ring = {f: torch.zeros((max(capacity, 0),) + shape(self.B, self.S), dtype=dt, device=self.device) for f, (dt, shape) in self.REPLAY_SHAPES.items()}
+        st = _lib.Replay()
+        st.capacity = capacity
+        for f, t in ring.items():
+            setattr(st, f, t.data_ptr())
+        self._check(self._lib.ranenv_bind_replay(self._h, C.byref(st)), "ranenv_bind_replay")
+        self._keep["replay"] = ring
+        return ring
+
+    def unbind_replay(self) -> None:
+        self._check(self._lib.ranenv_bind_replay(self._h, None), "ranenv_bind_replay")
+        self._keep.pop("replay", None)
+
+    def collect_replay(self, n_steps: int):
+        """``rollout(n_steps)`` under the head actor (either dist) that records every TTI into the bound replay ring
+        (ranenv_collect_replay); ``n_steps`` may not exceed the ring's capacity.  Everything else afterwards is as after
+        ``rollout(n_steps)``.  Returns the last TTI's (obs, reward, done)."""
+        if self._recorder is not None:
+            raise RanEnvError("collect_replay() does not return between TTIs: the recorder needs step()")
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_collect_replay(self._h, int(n_steps), *self._p_out, self._stream()), "ranenv_collect_replay")
+        return self._obs(), self.reward, self.done
+
+    def replay_count(self) -> int:
+        """TTIs recorded into the ring since ``bind_replay`` (ranenv_get_replay_count)."""
+        n = C.c_int64()
+        self._check(self._lib.ranenv_get_replay_count(self._h, C.byref(n)), "ranenv_get_replay_count")
+        return int(n.value)
+
+    def replay_sample(self, n: int, seed: int = 0, draw: int = 0, reward: str = "twc") -> Dict[str, torch.Tensor]:
+        """``n`` transitions drawn uniformly from the filled part of the ring (ranenv_replay_sample), in the learner's dtypes: ``obs``
+        / ``next_obs`` float32 [n, 10*S], ``action`` float32 [n, S], ``reward`` float32 [n] (column "twc" / "colran" of
+        ``reward_head``), ``done`` uint8 [n], ``index`` int64 [n] (slot * B + env).  A function of (``seed``, ``draw``, the fill)
+        alone.  The tensors are allocated once per ``n`` and REUSED."""
+        if reward not in HEAD_REWARDS:
+            raise ValueError(f"reward must be one of {sorted(HEAD_REWARDS)}")
+        n = int(n)
+        cache = self._keep.setdefault("replay_samples", {})
+        if n >= 1 and n not in cache:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            cache[n] = {"obs": torch.zeros((n, 10 * self.S), **f32), "action": torch.zeros((n, self.S), **f32), "reward": torch.zeros(n, **f32),
+                        "next_obs": torch.zeros((n, 10 * self.S), **f32), "done": torch.zeros(n, dtype=torch.uint8, device=self.device),
+                        "index": torch.zeros(n, dtype=torch.int64, device=self.device)}
+        out = cache.get(n, {})
+        m64 = 2 ** 64 - 1
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_replay_sample(self._h, n, int(seed) & m64, int(draw) & m64, HEAD_REWARDS[reward],
+                                                       *(_ptr(out.get(f)) for f in ("obs", "action", "reward", "next_obs", "done", "index")),
+                                                       self._stream()), "ranenv_replay_sample")
+        return out
+
+    def set_sac_critics(self, q1, q2, activation: Optional[str] = None):
+        """Bind SAC's two Q-nets -- the learner's TARGET critics -- for ``sac_targets()`` (ranenv_set_sac_critics): each maps
+        ``[obs (10*S) | action (S)]`` to one value; both of one shape.  Nets as for ``policy_net_layers`` (lists of (W, b):
+        ``activation`` default relu, SB3's for SAC).  Re-binding them leaves the actor as it is and vice versa."""
+        keep: list = []
+        structs = []
+        for q in (q1, q2):
+            act_q = activation if activation is not None or isinstance(q, torch.nn.Module) else "relu"
+            layers, act = policy_net_layers(q, act_q, 11 * self.S, 1)
+            structs.append(self._mlp_struct(layers, act, NET_IN_OBS, keep))
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_set_sac_critics(self._h, C.byref(structs[0]), C.byref(structs[1]), self._stream()), "ranenv_set_sac_critics")
+        self._keep["sac_critics"] = keep       # (the library copies on the current stream; keep the sources until it has)
+
+    def sac_targets(self, next_obs, reward, done, gamma: float = 0.99, ent_coef: float = 0.0, stochastic: bool = True, seed: int = 0,
+                    draw: int = 0, outputs=("target", "next_action", "next_logp", "q")) -> Dict[str, torch.Tensor]:
+        """SAC's soft Bellman target of ``n`` rows on the device (ranenv_sac_targets): ``next_obs`` float32 [n, 10*S], ``reward``
+        float32 [n], ``done`` uint8 [n] -- a ``replay_sample()`` or any other rows -- under the bound "gauss_tanh" head actor and
+        ``set_sac_critics``: a' ~ pi(.|next_obs), ``target`` = reward + gamma (1 - done) (min(Q1, Q2)(next_obs, a') - ent_coef
+        log pi(a')).  Returns new float32 tensors ``target`` [n], ``next_action`` [n, S], ``next_logp`` [n], ``q`` [n, 2]
+        (restricted to ``outputs``; ``target`` always).  The noise is a function of (``seed``, ``draw``, row)."""
+        n = int(next_obs.shape[0])
+        next_obs = self._dev(next_obs, torch.float32, (n, 10 * self.S), "next_obs")
+        reward = self._dev(reward, torch.float32, (n,), "reward")
+        done = self._dev(done, torch.uint8, (n,), "done")
+        shapes = {"target": (n,), "next_action": (n, self.S), "next_logp": (n,), "q": (n, 2)}
+        unknown = set(outputs) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        out = {f: torch.empty(shapes[f], dtype=torch.float32, device=self.device) for f in shapes if f == "target" or f in set(outputs)}
+        m64 = 2 ** 64 - 1
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_sac_targets(self._h, n, _ptr(next_obs), _ptr(reward), _ptr(done), float(gamma), float(ent_coef),
+                                                     1 if stochastic else 0, int(seed) & m64, int(draw) & m64,
+                                                     *(_ptr(out.get(f)) for f in ("target", "next_action", "next_logp", "q")), self._stream()),
+                        "ranenv_sac_targets")
+        return out
+
     def head_episode_metrics(self) -> Dict[str, torch.Tensor]:
         """Zero-copy views of the episode sums of the two head rewards (columns: SchedTWC, SchedColORAN): ``running`` [B, 2]
         (current episode) and ``episode_log`` [B, slots, 2] (finished episodes, the rows of ``episode_metrics()``'s log; absent with

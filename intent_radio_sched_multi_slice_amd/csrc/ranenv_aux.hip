@@ -476,9 +476,65 @@ __global__ void __launch_bounds__(256) ranenv_gae_kernel(int n_steps, int B, int
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Off-policy collection (ranenv_collect_replay / ranenv_replay_sample; the rules are spelled out in include/ranenv.h).
+// ---------------------------------------------------------------------------------------------
+// A partition's rows of the head observation / of the actor's scores -> their slot of the replay ring: contiguous ranges of 8-byte words
+__global__ void __launch_bounds__(256) ranenv_copy_words_kernel(unsigned long long *dst0, const unsigned long long *src0, long long n0,
+                                                                unsigned long long *dst1, const unsigned long long *src1, long long n1)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n0 + n1; i += (long long)gridDim.x * blockDim.x) {
+        if (i < n0) dst0[i] = src0[i];
+        else dst1[i - n0] = src1[i - n0];
+    }
+}
+
+// Uniform minibatch: GRP lanes per sampled row.  Lane 0 of the group draws the index once and hands it to the others; an observation
+// row is 40 * S bytes -- always a multiple of 8, not always of 16 (S = 5: 200) -- so rows move as 8-byte words.
+__global__ void __launch_bounds__(256) ranenv_replay_sample_kernel(const ReplaySampleArgs a)
+{
+    const int tid = (int)threadIdx.x, l = tid & (GRP - 1);
+    const long long i = (long long)blockIdx.x * (256 / GRP) + (tid >> 4);
+    if (i >= a.n) return;                              // (a whole group at a time)
+    unsigned lo = 0, hi = 0;
+    if (l == 0) {
+        unsigned o[4];
+        philox4x32_10((unsigned)i, (unsigned)((unsigned long long)i >> 32), (unsigned)a.draw, (unsigned)(a.draw >> 32), (unsigned)a.seed,
+                      (unsigned)(a.seed >> 32), o);
+        const unsigned long long u = ((unsigned long long)o[1] << 32) | o[0];
+        const unsigned long long idx = __umul64hi(u, (unsigned long long)a.n_rows);      // floor(u * n_rows / 2^64) < n_rows
+        lo = (unsigned)idx; hi = (unsigned)(idx >> 32);
+    }
+    lo = __shfl(lo, 0, GRP); hi = __shfl(hi, 0, GRP);
+    const size_t row = ((size_t)hi << 32) | lo, S = (size_t)a.S, out = (size_t)i;
+    const unsigned long long *so = (const unsigned long long *)(a.ring_obs + row * 10 * S), *sn = (const unsigned long long *)(a.ring_next_obs + row * 10 * S);
+    unsigned long long *po = (unsigned long long *)(a.obs + out * 10 * S), *pn = (unsigned long long *)(a.next_obs + out * 10 * S);
+    for (int w = l; w < 5 * a.S; w += GRP) { po[w] = so[w]; pn[w] = sn[w]; }
+    for (int j = l; j < a.S; j += GRP) a.action[out * S + j] = (float)a.ring_action[row * S + j];
+    if (l == 0) {
+        a.reward[out] = (float)a.ring_reward[row * 2 + a.reward_col];
+        a.done[out] = a.ring_done[row];
+        if (a.index) a.index[out] = (long long)row;
+    }
+}
+
 }  // namespace
 
 namespace ranenv_dev {
+
+void launch_copy_words(hipStream_t s, unsigned long long *dst0, const unsigned long long *src0, long long n0, unsigned long long *dst1,
+                       const unsigned long long *src1, long long n1)
+{
+    long long blocks = (n0 + n1 + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(ranenv_copy_words_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, dst0, src0, n0, dst1, src1, n1);
+}
+
+void launch_replay_sample(hipStream_t s, const ReplaySampleArgs &a)
+{
+    const long long per = 256 / GRP;
+    hipLaunchKernelGGL(ranenv_replay_sample_kernel, dim3((unsigned)((a.n + per - 1) / per)), dim3(256), 0, s, a);
+}
 
 void launch_gae(hipStream_t s, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,
                 double gamma, double lambda, float *adv, float *vtarg)

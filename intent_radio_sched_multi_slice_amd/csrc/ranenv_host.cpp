@@ -105,6 +105,12 @@ struct ranenv {
     float *d_head_val_w = nullptr; long long head_val_cap = 0;
     float *d_head_log_std = nullptr;
     double *d_head_acc = nullptr, *d_head_ep_acc = nullptr;      // episode sums of the two head rewards [B][2], their log [B][ep_slots][2]
+    // off-policy collection (ranenv_bind_replay / ranenv_set_sac_critics): the caller's ring and how many TTIs it has taken, SAC's two
+    // Q-nets packed in a buffer of their own
+    ranenv_replay ring{}; bool ring_on = false; long long ring_written = 0;
+    PolicyNet sac_q1{}, sac_q2{};
+    bool sac_on = false;
+    float *d_sac_w = nullptr; long long sac_cap = 0;
     int collect_split = -1;        // option "collect_split": the critic of ranenv_collect in a launch of its own (1), fused behind the actor (0), -1 = by weight size
     // options (the table `options` below, include/ranenv.h "Options")
     bool compact_enabled = true;                // option "compact"
@@ -1110,10 +1116,11 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra)
 
 // ---- policy networks (RANENV_POLICY_NETWORK) --------------------------------------------------------------------------------
 // Validate one ranenv_mlp against the handle's sizes and lay it out in the packed buffer from float `off` on (widths padded to 32).
-enum NetRole { NET_INTER, NET_INTRA, NET_INTER_VALUE, NET_INTRA_VALUE, NET_HEAD_CLIP, NET_HEAD_TANH, NET_HEAD_VALUE };
+enum NetRole { NET_INTER, NET_INTRA, NET_INTER_VALUE, NET_INTRA_VALUE, NET_HEAD_CLIP, NET_HEAD_TANH, NET_HEAD_VALUE, NET_SAC_Q };
 static const struct { const char *who; bool intra; int out_s, out_1; } NET_ROLES[] = {      // intra: the input is a slice's row, else the (head)
     {"inter", false, 2, 0}, {"intra", true, 0, 3}, {"inter value", false, 0, 1}, {"intra value", true, 0, 1},      // observation [10*S];
-    {"head", false, 1, 0}, {"head", false, 2, 0}, {"head value", false, 0, 1}};                                    // output width out_s * S + out_1
+    {"head", false, 1, 0}, {"head", false, 2, 0}, {"head value", false, 0, 1},                                     // output width out_s * S + out_1
+    {"SAC critic", false, 0, 1}};                                                                                  // (input: [observation | action], 11*S)
 
 static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, PolicyNet &net, long long &off)
 {
@@ -1122,7 +1129,7 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, Policy
     const bool intra = NET_ROLES[role].intra;
     if (m->n_hidden < 1 || m->n_hidden > NET_MAX_LAYERS - 1) return fail(h, RANENV_E_INVALID, "%s net: %d hidden layers (1..%d)", who, m->n_hidden, NET_MAX_LAYERS - 1);
     if (m->activation != RANENV_ACT_TANH && m->activation != RANENV_ACT_RELU) return fail(h, RANENV_E_INVALID, "%s net: unknown activation %d", who, m->activation);
-    int in_dim = 10 * S;
+    int in_dim = role == NET_SAC_Q ? 11 * S : 10 * S;
     if (!intra && m->input_layout != RANENV_NET_IN_OBS) return fail(h, RANENV_E_INVALID, "%s net: input layout %d (only RANENV_NET_IN_OBS)", who, m->input_layout);
     if (intra) {
         if (m->input_layout == RANENV_NET_IN_OBS) in_dim = 2 * Us + 9;
@@ -1629,6 +1636,7 @@ struct Rollout {
     AdvanceArgs adv{};
     KP kpr{};
     const Record *rec = nullptr;   // ranenv_collect / _head: the record (null: a plain rollout)
+    bool replay = false;           // ranenv_collect_replay: every TTI goes to the handle's replay ring
 };
 
 // TTIs from now until the first episode of envs [lo, hi) ends, that TTI included, between 1 and n.  `n_ends`: at how many different
@@ -1739,6 +1747,31 @@ static hipError_t collect_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0
     return launch(last);
 }
 
+// ranenv_collect_replay: TTI `t` of a partition's own count for envs [e0, e0 + n) on `s`, into slot (TTIs recorded so far + t) % C of the
+// ring.  The plain actor launch and step; between them the partition's rows -- one contiguous range of the slot -- are copied: the
+// observation the action was computed from and the scores the step consumes; the step's done flags and the head
+// kernel's reward pair go straight into the slot (as in collect_tti); then the observation the head kernel left, BEFORE the reset behind
+// an episode end refreshes it: the terminal observation of the envs that finished, the next slot's obs of all others.
+static hipError_t replay_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
+{
+    const ranenv_replay &ring = h->ring;
+    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices;
+    const size_t slot = (size_t)((h->ring_written + t) % ring.capacity) * B, at = slot + (size_t)e0;      // the slot's first row, the range's
+    typedef unsigned long long word;
+    const long long obs_words = (long long)n * 5 * (long long)S;      // a row: 10 * S floats
+    const word *head_rows = (const word *)(h->kp.head_obs + (size_t)e0 * 10 * S);
+    hipError_t le = net_launch(h, kpk, e0, n, s);
+    if (le != hipSuccess) return le;
+    kpk.head_reward = ring.reward_head + slot * 2;      // (the kernels index both by env)
+    kpk.done = ring.done + slot;
+    launch_copy_words(s, (word *)(ring.obs + at * 10 * S), head_rows, obs_words,      // (one launch for both: the actor only read the observation)
+                      (word *)(ring.action + at * S), (const word *)(h->d_net_scores + (size_t)e0 * S), (long long)n * (long long)S);
+    le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
+    if (le != hipSuccess) return le;
+    launch_copy_words(s, (word *)(ring.next_obs + at * 10 * S), head_rows, obs_words, nullptr, nullptr, 0);
+    return follow_episode_ends(h, r, e0, n, 1, s, kpk.done);
+}
+
 // Every partition walks through the TTIs in launches of its own, on its own stream
 static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
 {
@@ -1781,6 +1814,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
             kpk.n_tti = n_tti;
             h->last_rollout_launches++;
             if (r.rec) return collect_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
+            if (r.replay) return replay_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
             hipError_t le = r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
             if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
             if (le != hipSuccess) return le;
@@ -1794,7 +1828,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
 
 // ranenv_rollout, and with `rec` ranenv_collect / ranenv_collect_head (gamma / lambda: their GAE pass)
 static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream_,
-                       const Record *rec = nullptr, double gamma = 0.0, double lambda = 0.0)
+                       const Record *rec = nullptr, double gamma = 0.0, double lambda = 0.0, bool replay = false)
 {
     int rc = check_ready(h, nullptr, nullptr, true);
     if (rc != RANENV_OK) return rc;
@@ -1815,7 +1849,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
     r.net = net_use(h, r.kp);
     if (r.net < 0) return r.net;
-    r.rec = rec;
+    r.rec = rec; r.replay = replay;
     rc = compact_for(h, r.kp, stream, &r.kp.compact);
     if (rc != RANENV_OK) return rc;
     if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_plan)
@@ -1860,6 +1894,14 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
                        rec->adv, rec->vtarg);
             HIP_TRY(h, hipGetLastError());
         }
+    }
+    if (replay) {
+        // (the partitions have joined the caller's stream)  As after a rollout: the bound head rewards and the caller's done hold the last TTI's
+        const size_t B = (size_t)h->cfg.batch, last = (size_t)((h->ring_written + n_steps - 1) % h->ring.capacity);
+        if (h->kp.head_reward)
+            HIP_TRY(h, hipMemcpyAsync(h->kp.head_reward, h->ring.reward_head + last * B * 2, sizeof(double) * B * 2, hipMemcpyDeviceToDevice, stream));
+        if (done) HIP_TRY(h, hipMemcpyAsync(done, h->ring.done + last * B, B, hipMemcpyDeviceToDevice, stream));
+        h->ring_written += n_steps;
     }
     if (r.follow) { h->sh_steps = r.steps; h->sh_valid = true; h->last_done = done; }      // (read from the device above, followed exactly since)
     else shadow_steps_add(h, 0, h->cfg.batch, n_steps, done, stream);
@@ -1915,6 +1957,106 @@ int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_traj
     rec.rec.cols = 1; rec.reward_cols = 2; rec.gae_col = reward_col;
     rec.reward = traj->reward_head; rec.done = traj->done; rec.adv = traj->adv; rec.vtarg = traj->vtarg;
     return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec, gamma, lambda);
+}
+
+// ---- off-policy collection (SAC): replay ring, sampler, targets -------------------------------------------------------------------
+static_assert(sizeof(ranenv_replay) == RANENV_REPLAY_BYTES, "ranenv_replay: two int32 and 5 device pointers");
+
+static bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
+
+int ranenv_bind_replay(ranenv_handle h, const ranenv_replay *ring)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!ring) { h->ring = ranenv_replay{}; h->ring_on = false; h->ring_written = 0; return RANENV_OK; }
+    if (ring->capacity < 2) return fail(h, RANENV_E_INVALID, "replay ring: capacity %d (>= 2 slots)", ring->capacity);
+    if (!ring->obs || !ring->next_obs || !ring->action || !ring->reward_head || !ring->done)
+        return fail(h, RANENV_E_INVALID, "replay ring: obs, next_obs, action, reward_head and done are all required");
+    if (!aligned8(ring->obs) || !aligned8(ring->next_obs) || !aligned8(ring->action) || !aligned8(ring->reward_head))
+        return fail(h, RANENV_E_INVALID, "replay ring: the arrays must be 8-byte aligned");
+    h->ring = *ring; h->ring_on = true; h->ring_written = 0;
+    return RANENV_OK;
+}
+
+int ranenv_get_replay_count(ranenv_handle h, int64_t *written)
+{
+    if (!h || !written) return fail(h, RANENV_E_INVALID, "null argument");
+    *written = h->ring_on ? h->ring_written : 0;
+    return RANENV_OK;
+}
+
+int ranenv_collect_replay(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
+    if (!h->ring_on) return fail(h, RANENV_E_STATE, "no replay ring bound (ranenv_bind_replay)");
+    if (n_steps > h->ring.capacity) return fail(h, RANENV_E_INVALID, "n_steps %d exceeds the ring's capacity %d", n_steps, h->ring.capacity);
+    if (h->kp.policy != RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect_replay needs policy HEAD_NETWORK (ranenv_set_policy)");
+    if (!h->head_on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
+    if (!h->kp.head_obs) return fail(h, RANENV_E_STATE, "the replay ring records dev_obs_head: none is bound (ranenv_bind_head_outputs)");
+    if (!aligned8(h->kp.head_obs)) return fail(h, RANENV_E_INVALID, "the replay ring copies dev_obs_head as 8-byte words: it must be 8-byte aligned");
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, nullptr, 0.0, 0.0, true);
+}
+
+int ranenv_replay_sample(ranenv_handle h, int64_t n, uint64_t seed, uint64_t draw, int32_t reward_col, float *dev_obs, float *dev_action,
+                         float *dev_reward, float *dev_next_obs, uint8_t *dev_done, int64_t *dev_index, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n < 1 || n > (int64_t)0x7FFFFFFF * (256 / GRP)) return fail(h, RANENV_E_INVALID, "n must be >= 1 (and fit one launch)");
+    if (reward_col != 0 && reward_col != 1) return fail(h, RANENV_E_INVALID, "reward_col %d (0 = SchedTWC, 1 = SchedColORAN)", reward_col);
+    if (!dev_obs || !dev_action || !dev_reward || !dev_next_obs || !dev_done) return fail(h, RANENV_E_INVALID, "replay sample: only dev_index may be NULL");
+    if (!aligned8(dev_obs) || !aligned8(dev_next_obs)) return fail(h, RANENV_E_INVALID, "replay sample: dev_obs / dev_next_obs must be 8-byte aligned");
+    if (!h->ring_on || h->ring_written == 0) return fail(h, RANENV_E_STATE, "the replay ring holds no transitions (ranenv_bind_replay, ranenv_collect_replay)");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    ReplaySampleArgs a{};
+    const long long filled = h->ring_written < h->ring.capacity ? h->ring_written : h->ring.capacity;
+    a.n = n; a.n_rows = filled * h->cfg.batch; a.B = h->cfg.batch; a.S = h->cfg.n_slices; a.reward_col = reward_col;
+    a.seed = seed; a.draw = draw;
+    a.ring_obs = h->ring.obs; a.ring_next_obs = h->ring.next_obs; a.ring_action = h->ring.action; a.ring_reward = h->ring.reward_head;
+    a.ring_done = h->ring.done;
+    a.obs = dev_obs; a.action = dev_action; a.reward = dev_reward; a.next_obs = dev_next_obs; a.done = dev_done; a.index = (long long *)dev_index;
+    launch_replay_sample((hipStream_t)stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return RANENV_OK;
+}
+
+int ranenv_set_sac_critics(ranenv_handle h, const ranenv_mlp *q1, const ranenv_mlp *q2, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!q1 || !q2) return fail(h, RANENV_E_INVALID, "both SAC critics are required");
+    if (q1->n_hidden != q2->n_hidden || q1->activation != q2->activation) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape");
+    PolicyNet n1{}, n2{};
+    long long off = 0;
+    int rc = net_layout(h, q1, NET_SAC_Q, n1, off);
+    if (rc == RANENV_OK) rc = net_layout(h, q2, NET_SAC_Q, n2, off);
+    if (rc != RANENV_OK) return rc;
+    for (int l = 0; l <= q1->n_hidden + 1; l++)
+        if (q1->dims[l] != q2->dims[l]) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape (width %d: %d and %d)", l, q1->dims[l], q2->dims[l]);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    rc = net_bind(h, &h->d_sac_w, &h->sac_cap, off, (hipStream_t)stream_, {{q1, &n1}, {q2, &n2}});
+    if (rc != RANENV_OK) return rc;
+    h->sac_q1 = n1; h->sac_q2 = n2; h->sac_on = true;
+    return RANENV_OK;
+}
+
+int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, const float *dev_reward, const uint8_t *dev_done, double gamma,
+                       double ent_coef, int32_t stochastic, uint64_t seed, uint64_t draw, float *dev_target, float *dev_next_action,
+                       float *dev_next_logp, float *dev_q, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n < 1 || n > (int64_t)0x7FFFFFFF * NET_ROWS) return fail(h, RANENV_E_INVALID, "n must be >= 1 (and fit one launch)");
+    if (!dev_next_obs || !dev_reward || !dev_done || !dev_target) return fail(h, RANENV_E_INVALID, "SAC targets: next_obs, reward, done and target are required");
+    if (!h->head_on || h->head_dist != RANENV_HEAD_DIST_GAUSS_TANH)
+        return fail(h, RANENV_E_STATE, "SAC targets need a GAUSS_TANH head actor (ranenv_set_head_policy_network)");
+    if (!h->sac_on) return fail(h, RANENV_E_STATE, "no SAC critics bound (ranenv_set_sac_critics)");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    SacArgs a{};
+    a.n = n; a.S = h->cfg.n_slices;
+    a.next_obs = dev_next_obs; a.reward = dev_reward; a.done = dev_done;
+    a.gamma = gamma; a.ent_coef = ent_coef; a.stochastic = stochastic != 0; a.seed = seed; a.draw = draw;
+    a.target = dev_target; a.next_action = dev_next_action; a.next_logp = dev_next_logp; a.q = dev_q;
+    const hipError_t le = launch_sac_targets((hipStream_t)stream, h->head_net, h->sac_q1, h->sac_q2, a);
+    if (le != hipSuccess) return fail(h, RANENV_E_HIP, "SAC target launch: %s", hipGetErrorString(le));
+    return RANENV_OK;
 }
 
 int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *reward, const float *vf, const uint8_t *done, double gamma,

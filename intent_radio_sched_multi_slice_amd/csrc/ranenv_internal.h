@@ -213,6 +213,16 @@ hipError_t launch_policy_collect(hipStream_t, const PolicyNet &inter, const Poli
 hipError_t launch_head_policy_collect(hipStream_t, const PolicyNet &actor, const PolicyNet *critic, const PolicyIO &, const PolicyRec &, int e0,
                                       int n_envs);
 size_t policy_lds_bytes(const PolicyNet &);
+// ranenv_sac_targets: one call's rows and outputs (include/ranenv.h spells out the arithmetic).  The actor is a GAUSS_TANH head net,
+// q1 / q2 two nets of one shape on [next_obs | action].
+struct SacArgs {
+    long long n; int S;
+    const float *next_obs, *reward; const uint8_t *done;      // [n][10*S], [n], [n]
+    double gamma, ent_coef;
+    int stochastic; unsigned long long seed, draw;
+    float *target, *next_action, *next_logp, *q;              // [n]; [n][S], [n], [n][2] or null
+};
+hipError_t launch_sac_targets(hipStream_t, const PolicyNet &actor, const PolicyNet &q1, const PolicyNet &q2, const SacArgs &);
 
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block
@@ -285,5 +295,16 @@ void launch_gae(hipStream_t, int n_steps, int B, int n_cols, const double *rewar
                 double gamma, double lambda, float *adv, float *vtarg);
 void launch_idle_traffic(hipStream_t, unsigned n_eps, const ranenv_episode *eps, const int32_t *pool, int U, const int32_t *lane_slice,
                          const int32_t *lane_ue, int *violations);
+// ranenv_collect_replay: up to two ranges of 8-byte words copied device to device in one launch (n1 = 0: one range)
+void launch_copy_words(hipStream_t, unsigned long long *dst0, const unsigned long long *src0, long long n0, unsigned long long *dst1,
+                       const unsigned long long *src1, long long n1);
+// ranenv_replay_sample: n rows gathered from the ring's first n_rows = min(written, C) * B transitions
+struct ReplaySampleArgs {
+    long long n, n_rows; int B, S, reward_col;
+    unsigned long long seed, draw;
+    const float *ring_obs, *ring_next_obs; const double *ring_action, *ring_reward; const uint8_t *ring_done;
+    float *obs, *action, *reward, *next_obs; uint8_t *done; long long *index;
+};
+void launch_replay_sample(hipStream_t, const ReplaySampleArgs &);
 
 }  // namespace ranenv_dev

@@ -321,6 +321,103 @@ __global__ void __launch_bounds__(256) ranenv_head_policy_collect_kernel(PolicyN
     policy_body<true, true>(net, vnet, io, rec, 0, e0, n_rows, lds);
 }
 
+// ---- SAC's soft Bellman target (ranenv_sac_targets; the arithmetic is spelled out in include/ranenv.h) -----------------------------
+constexpr unsigned SAC_TAG = 0x53414300u;               // "SAC\0": counter word c3 of the target's Philox draws, + position
+
+// The critics' input rows [next_obs | a32] of the workgroup's 32 rows -> `dst` (zeros beyond the input and beyond the call's rows):
+// the observation re-read from L2, the actions from the registers of the threads that computed them (position tid + 256 k)
+__device__ __forceinline__ void sac_critic_rows(const PolicyNet &q, const SacArgs &a, long long row0, const float (&a32)[2], float *dst, int tid)
+{
+    const int S = a.S, K0 = q.kp[0], ld0 = net_ld(K0);
+    for (int i = tid; i < NET_ROWS * K0; i += 256) {
+        const int r = i / K0, k = i - r * K0;
+        if (k >= 10 * S && k < 11 * S) continue;
+        const long long g = row0 + r;
+        dst[r * ld0 + k] = (g < a.n && k < 10 * S) ? a.next_obs[(size_t)g * (size_t)(10 * S) + k] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int i = tid + 256 * k;
+        if (i < NET_ROWS * S) dst[(i / S) * ld0 + 10 * S + (i % S)] = a32[k];
+    }
+}
+
+// A workgroup owns 32 rows: the actor on next_obs, the squashed-Gaussian epilogue (a', log pi), then the two critics on [next_obs | a']
+// through the same two LDS buffers, then the target.  S <= 16: a thread owns at most two (row, position) pairs.
+__global__ void __launch_bounds__(256) ranenv_sac_target_kernel(PolicyNet actor, PolicyNet q1, PolicyNet q2, SacArgs a)
+{
+    extern __shared__ float lds[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)blockIdx.x * NET_ROWS;
+    const int S = a.S;
+    int ldm = net_ld_max(actor);
+    { const int lq = net_ld_max(q1); ldm = lq > ldm ? lq : ldm; }
+    float *cur = lds, *nxt = lds + NET_ROWS * ldm;
+
+    {
+        const int K0 = actor.kp[0], ld0 = net_ld(K0);
+        for (int i = tid; i < NET_ROWS * K0; i += 256) {
+            const int r = i / K0, k = i - r * K0;
+            const long long g = row0 + r;
+            cur[r * ld0 + k] = (g < a.n && k < actor.in_dim) ? a.next_obs[(size_t)g * (size_t)(10 * S) + k] : 0.0f;
+        }
+    }
+    __syncthreads();
+    net_layers(actor, cur, nxt, lane, wave);
+
+    // ---- epilogue: a' = tanh(mu + exp(ls) z) and the positions' terms of log pi(a') (the idle LDS buffer) ------------------------
+    const int ld = net_ld(actor.np[actor.n_layers - 1]);
+    double *term = (double *)nxt;
+    float a32[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int i = tid + 256 * k;
+        if (i >= NET_ROWS * S) continue;
+        const int r = i / S, j = i - r * S;
+        const long long g = row0 + r;
+        if (g >= a.n) continue;
+        double ls = (double)cur[r * ld + S + j];
+        ls = ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls);
+        double z = 0.0;
+        if (a.stochastic) {
+            unsigned o[4];
+            philox4x32_10((unsigned)g, (unsigned)((unsigned long long)g >> 32), (unsigned)a.draw, SAC_TAG + (unsigned)j, (unsigned)a.seed,
+                          (unsigned)(a.seed >> 32), o);
+            const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
+            z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        }
+        const double gj = (double)cur[r * ld + j] + exp(ls) * z;
+        const double aj = tanh(gj);
+        a32[k] = (float)aj;
+        term[i] = ((((-0.5 * z) * z - ls) - HALF_LN_2PI)) - log((1.0 - aj * aj) + 1e-6);
+        if (a.next_action) a.next_action[(size_t)g * S + j] = a32[k];
+    }
+    __syncthreads();
+    const long long gr = row0 + tid;                   // threads 0..31: the row's log pi, Q values and target
+    const bool own = tid < NET_ROWS && gr < a.n;
+    double lp = 0.0;
+    if (own) {
+        for (int j = 0; j < S; j++) lp += term[tid * S + j];
+        if (a.next_logp) a.next_logp[gr] = (float)lp;
+    }
+
+    // ---- the critics ---------------------------------------------------------------------------------------------------------------
+    const int ldq = net_ld(q1.np[q1.n_layers - 1]);
+    sac_critic_rows(q1, a, row0, a32, cur, tid);
+    __syncthreads();                                   // (... and the terms are read: the critic's layers overwrite them)
+    net_layers(q1, cur, nxt, lane, wave);
+    const float v1 = own ? cur[tid * ldq] : 0.0f;
+    sac_critic_rows(q2, a, row0, a32, nxt, tid);       // (into the idle buffer: threads 0..31 may still be reading Q1's rows)
+    __syncthreads();
+    { float *t = cur; cur = nxt; nxt = t; }
+    net_layers(q2, cur, nxt, lane, wave);
+    if (!own) return;
+    const float v2 = cur[tid * ldq];
+    if (a.q) { a.q[(size_t)gr * 2] = v1; a.q[(size_t)gr * 2 + 1] = v2; }
+    const double nd = a.done[gr] ? 0.0 : 1.0;
+    a.target[gr] = (float)((double)a.reward[gr] + nd * (a.gamma * (fmin((double)v1, (double)v2) - a.ent_coef * lp)));
+}
+
 // The kernel's dynamic LDS limit raised to the widest net's need (2 x 32 x 516 floats = 129 KB), once per kernel
 template <auto KERNEL>
 hipError_t lds_attr()
@@ -386,6 +483,14 @@ hipError_t launch_head_policy_collect(hipStream_t s, const PolicyNet &actor, con
 {
     if (const hipError_t attr = lds_attr<ranenv_head_policy_collect_kernel>(); attr != hipSuccess) return attr;
     collect_launch<true>(s, 0, actor, critic, io, rec, e0, n_envs, (rec.split & 1) != 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_sac_targets(hipStream_t s, const PolicyNet &actor, const PolicyNet &q1, const PolicyNet &q2, const SacArgs &a)
+{
+    if (const hipError_t attr = lds_attr<ranenv_sac_target_kernel>(); attr != hipSuccess) return attr;
+    const size_t x = policy_lds_bytes(actor), y = policy_lds_bytes(q1), lds = x > y ? x : y;
+    hipLaunchKernelGGL(ranenv_sac_target_kernel, dim3((unsigned)((a.n + NET_ROWS - 1) / NET_ROWS)), dim3(256), lds, s, actor, q1, q2, a);
     return hipGetLastError();
 }
 
