@@ -343,16 +343,8 @@ class BatchedRanEnv:
         for ``policy_net_layers``.  Switches the policy to NETWORK: ``step()`` / ``rollout()`` / ``evaluate()`` then need no
         actions.  ``stochastic``: sample (Philox noise keyed by ``seed``) instead of taking the mode."""
         in_inter, in_intra = self.net_input_dims(intra_input)
-        nets = [policy_net_layers(inter, activation, in_inter, 2 * self.S)]
-        if intra is not None:
-            nets.append(policy_net_layers(intra, activation, in_intra, 3))
-        keep: list = []
-        structs = [self._mlp_struct(layers, act, NET_INPUTS[intra_input] if k == 1 else NET_IN_OBS, keep) for k, (layers, act) in enumerate(nets)]
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_set_policy_network(self._h, C.byref(structs[0]), C.byref(structs[1]) if intra is not None else None,
-                                                            1 if stochastic else 0, int(seed) & (2 ** 64 - 1), self._stream()),
-                        "ranenv_set_policy_network")
-        self._keep["policy_net"] = keep        # (the library copies on the current stream; keep the sources until it has)
+        self._set_nets("policy_net", "ranenv_set_policy_network", [(inter, activation, in_inter, 2 * self.S, NET_IN_OBS),
+                       (intra, activation, in_intra, 3, NET_INPUTS[intra_input])], 1 if stochastic else 0, int(seed) & (2 ** 64 - 1))
         self._policy_views = None
         self.set_policy(POLICY_NETWORK, self.fixed_intra if fixed_intra is None else fixed_intra)
 
@@ -367,22 +359,27 @@ class BatchedRanEnv:
             m.weight[i], m.bias[i] = w.data_ptr(), b.data_ptr()
         return m
 
+    def _set_nets(self, key: str, call: str, nets, *args, keep=()):
+        """One ``ranenv_set_*`` call that binds nets: per ranenv_mlp argument ``(net, activation, in_dim, out_dim, input layout)`` --
+        a ``None`` net is passed as NULL, a callable layout is asked with the net's layers -- then ``args``, then the stream."""
+        keep, structs = list(keep), []
+        for net, activation, in_dim, out_dim, layout in nets:
+            if net is None:
+                structs.append(None)
+                continue
+            layers, act = policy_net_layers(net, activation, in_dim, out_dim)
+            structs.append(C.byref(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep)))
+        with torch.cuda.device(self.device):
+            self._check(getattr(self._lib, call)(self._h, *structs, *args, self._stream()), call)
+        self._keep[key] = keep                 # (the library copies on the current stream; keep the sources until it has)
+
     def set_value_network(self, inter, intra=None, activation: Optional[str] = None):
         """Bind the critics that ``collect()`` evaluates beside the actors (ranenv_set_value_network): ``inter`` maps the
         inter-slice observation [10*S] to one value, ``intra`` (None = no intra critic: those columns of ``vf`` are 0) the
         intra actor's input row -- the layout given to ``set_policy_network`` -- to one value per (env, slice).  Nets as for
         ``policy_net_layers``.  Bind the actors first when there is an intra critic; re-binding either pair leaves the other."""
-        keep: list = []
-        layers, act = policy_net_layers(inter, activation, 10 * self.S, 1)
-        structs = [self._mlp_struct(layers, act, NET_IN_OBS, keep)]
-        if intra is not None:
-            layers, act = policy_net_layers(intra, activation, None, 1)
-            layout = NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS
-            structs.append(self._mlp_struct(layers, act, layout, keep))
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_set_value_network(self._h, C.byref(structs[0]), C.byref(structs[1]) if intra is not None else None,
-                                                           self._stream()), "ranenv_set_value_network")
-        self._keep["value_net"] = keep         # (the library copies on the current stream; keep the sources until it has)
+        self._set_nets("value_net", "ranenv_set_value_network", [(inter, activation, 10 * self.S, 1, NET_IN_OBS), (intra, activation, None, 1,
+                       lambda layers: NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS)])
 
     TRAJECTORY_SHAPES = {      # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S, Us, W)
         "obs_inter": (torch.float32, 0, lambda B, S, Us, W: (B, 10 * S)), "obs_intra": (torch.float32, 0, lambda B, S, Us, W: (B, S, W)),
@@ -467,31 +464,21 @@ class BatchedRanEnv:
             raise ValueError("log_std is required for gauss_clip and must be None for gauss_tanh")
         if activation is None and not isinstance(actor, torch.nn.Module):
             activation = "tanh" if dist == "gauss_clip" else "relu"
-        layers, act = policy_net_layers(actor, activation, 10 * self.S, self.S if dist == "gauss_clip" else 2 * self.S)
-        keep: list = []
-        m = self._mlp_struct(layers, act, NET_IN_OBS, keep)
         ls = None
         if log_std is not None:
             ls = torch.as_tensor(log_std).detach().to(device=self.device, dtype=torch.float32).contiguous()
             if tuple(ls.shape) != (self.S,):
                 raise ValueError(f"log_std: expected shape ({self.S},), got {tuple(ls.shape)}")
-            keep.append(ls)
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_set_head_policy_network(self._h, C.byref(m), HEAD_DISTS[dist], _ptr(ls), 1 if stochastic else 0,
-                                                                 int(seed) & (2 ** 64 - 1), self._stream()), "ranenv_set_head_policy_network")
-        self._keep["head_policy_net"] = keep   # (the library copies on the current stream; keep the sources until it has)
+        self._set_nets("head_policy_net", "ranenv_set_head_policy_network",
+                       [(actor, activation, 10 * self.S, self.S if dist == "gauss_clip" else 2 * self.S, NET_IN_OBS)],
+                       HEAD_DISTS[dist], _ptr(ls), 1 if stochastic else 0, int(seed) & (2 ** 64 - 1), keep=[ls])
         self._policy_views = None
         self.set_policy(POLICY_HEAD_NETWORK, INTRA_RR if fixed_intra is None else fixed_intra)
 
     def set_head_value_network(self, critic, activation: Optional[str] = None):
         """Bind the critic ``collect_head()`` evaluates beside the head actor (ranenv_set_head_value_network): ``head_obs`` [10*S]
         -> one value.  Nets as for ``policy_net_layers``."""
-        keep: list = []
-        layers, act = policy_net_layers(critic, activation, 10 * self.S, 1)
-        m = self._mlp_struct(layers, act, NET_IN_OBS, keep)
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_set_head_value_network(self._h, C.byref(m), self._stream()), "ranenv_set_head_value_network")
-        self._keep["head_value_net"] = keep
+        self._set_nets("head_value_net", "ranenv_set_head_value_network", [(critic, activation, 10 * self.S, 1, NET_IN_OBS)])
 
     HEAD_TRAJECTORY_SHAPES = {     # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S)
         "obs_head": (torch.float32, 0, lambda B, S: (B, 10 * S)), "action": (torch.float64, 0, lambda B, S: (B, S)),
@@ -581,15 +568,8 @@ class BatchedRanEnv:
         """Bind SAC's two Q-nets -- the learner's TARGET critics -- for ``sac_targets()`` (ranenv_set_sac_critics): each maps
         ``[obs (10*S) | action (S)]`` to one value; both of one shape.  Nets as for ``policy_net_layers`` (lists of (W, b):
         ``activation`` default relu, SB3's for SAC).  Re-binding them leaves the actor as it is and vice versa."""
-        keep: list = []
-        structs = []
-        for q in (q1, q2):
-            act_q = activation if activation is not None or isinstance(q, torch.nn.Module) else "relu"
-            layers, act = policy_net_layers(q, act_q, 11 * self.S, 1)
-            structs.append(self._mlp_struct(layers, act, NET_IN_OBS, keep))
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_set_sac_critics(self._h, C.byref(structs[0]), C.byref(structs[1]), self._stream()), "ranenv_set_sac_critics")
-        self._keep["sac_critics"] = keep       # (the library copies on the current stream; keep the sources until it has)
+        self._set_nets("sac_critics", "ranenv_set_sac_critics", [
+            (q, activation if activation is not None or isinstance(q, torch.nn.Module) else "relu", 11 * self.S, 1, NET_IN_OBS) for q in (q1, q2)])
 
     def sac_targets(self, next_obs, reward, done, gamma: float = 0.99, ent_coef: float = 0.0, stochastic: bool = True, seed: int = 0,
                     draw: int = 0, outputs=("target", "next_action", "next_logp", "q")) -> Dict[str, torch.Tensor]:

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -86,31 +87,19 @@ struct ranenv {
     size_t prof_used = 0;
     long long prof_ttis = 0;       // TTIs covered by the launches timed since ranenv_profile_begin
     long long prof_env_ttis = 0;   // env-TTIs covered by the launches timed since ranenv_profile_begin
-    // policy networks (ranenv_set_policy_network): packed weights, and the actions the step reads under RANENV_POLICY_NETWORK
-    PolicyNet net_inter{}, net_intra{};
-    bool net_on = false, net_has_intra = false;
+    // The nets of one ranenv_set_*_network call, packed in a buffer of their own: an outgrown buffer stays allocated until ranenv_destroy
+    struct NetSlot { PolicyNet a{}, b{}; bool on = false, has_b = false; float *w = nullptr; long long cap = 0; };      // cap: floats
+    // ranenv_set_policy_network (inter, intra) and ranenv_set_value_network (their critics); ranenv_set_head_policy_network /
+    // _head_value_network: SchedTWC / SchedColORAN's actor and critic on the head observation; ranenv_set_sac_critics (q1, q2)
+    NetSlot actor, value, head, head_value, sac;
+    // ... and the actions the step reads under RANENV_POLICY_NETWORK / _HEAD_NETWORK (shared: one policy acts at a time)
     int net_stochastic = 0; unsigned long long net_seed = 0;
-    float *d_net_w = nullptr; long long net_cap = 0;      // floats
     double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
-    // critics (ranenv_set_value_network), packed like the actors in a buffer of their own
-    PolicyNet val_inter{}, val_intra{};
-    bool val_on = false, val_has_intra = false;
-    float *d_val_w = nullptr; long long val_cap = 0;
-    // head policies (ranenv_set_head_policy_network / _value_network): SchedTWC / SchedColORAN's actor and critic on the head observation,
-    // packed in buffers of their own; the scores share d_net_scores (one policy acts at a time)
-    PolicyNet head_net{}, head_val{};
-    bool head_on = false, head_val_on = false;
     int head_dist = 0, head_stochastic = 0; unsigned long long head_seed = 0;
-    float *d_head_w = nullptr; long long head_cap = 0;
-    float *d_head_val_w = nullptr; long long head_val_cap = 0;
     float *d_head_log_std = nullptr;
     double *d_head_acc = nullptr, *d_head_ep_acc = nullptr;      // episode sums of the two head rewards [B][2], their log [B][ep_slots][2]
-    // off-policy collection (ranenv_bind_replay / ranenv_set_sac_critics): the caller's ring and how many TTIs it has taken, SAC's two
-    // Q-nets packed in a buffer of their own
+    // off-policy collection (ranenv_bind_replay): the caller's ring and how many TTIs it has taken
     ranenv_replay ring{}; bool ring_on = false; long long ring_written = 0;
-    PolicyNet sac_q1{}, sac_q2{};
-    bool sac_on = false;
-    float *d_sac_w = nullptr; long long sac_cap = 0;
     int collect_split = -1;        // option "collect_split": the critic of ranenv_collect in a launch of its own (1), fused behind the actor (0), -1 = by weight size
     // options (the table `options` below, include/ranenv.h "Options")
     bool compact_enabled = true;                // option "compact"
@@ -1164,23 +1153,30 @@ static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, 
     return RANENV_OK;
 }
 
-// The nets laid out in `floats` floats (net_layout; a null `m`: none) into the packed buffer *buf: grown when needed -- the outgrown
-// one stays allocated until ranenv_destroy, the launches of earlier calls may still read it -- else zeroed; then the layers are copied.
-struct NetSrc { const ranenv_mlp *m; PolicyNet *net; };
-static int net_bind(ranenv_handle h, float **buf, long long *cap, long long floats, hipStream_t s, std::initializer_list<NetSrc> nets)
+// One ranenv_set_*_network call: the slot's nets (`b.m` null: one) validated and laid out -- an error so far precedes every HIP call --
+// then `extra` (what else the setter checks or allocates), then the packed buffer: grown when needed -- the outgrown one stays allocated
+// until ranenv_destroy, the launches of earlier calls may still read it -- else zeroed; the layers are copied.  The slot changes on success only.
+struct NetSrc { const ranenv_mlp *m; NetRole role; };
+static int net_set(ranenv_handle h, ranenv::NetSlot &slot, NetSrc a, NetSrc b, hipStream_t s, const std::function<int()> &extra = nullptr)
 {
-    if (floats > *cap) {
-        const int rc = dev_alloc(h, buf, (size_t)floats);
-        if (rc != RANENV_OK) return rc;
-        *cap = floats;
+    PolicyNet na{}, nb{};
+    long long floats = 0;
+    int rc = net_layout(h, a.m, a.role, na, floats);
+    if (rc == RANENV_OK && b.m) rc = net_layout(h, b.m, b.role, nb, floats);
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (extra && (rc = extra()) != RANENV_OK) return rc;
+    if (floats > slot.cap) {
+        if ((rc = dev_alloc(h, &slot.w, (size_t)floats)) != RANENV_OK) return rc;
+        slot.cap = floats;
     } else {
-        HIP_TRY(h, hipMemsetAsync(*buf, 0, sizeof(float) * (size_t)floats, s));
+        HIP_TRY(h, hipMemsetAsync(slot.w, 0, sizeof(float) * (size_t)floats, s));
     }
-    for (const NetSrc &n : nets) {
-        n.net->w = *buf;
-        const int rc = n.m ? net_copy(h, n.m, *n.net, s, *buf) : RANENV_OK;
-        if (rc != RANENV_OK) return rc;
-    }
+    na.w = nb.w = slot.w;
+    rc = net_copy(h, a.m, na, s, slot.w);
+    if (rc == RANENV_OK && b.m) rc = net_copy(h, b.m, nb, s, slot.w);
+    if (rc != RANENV_OK) return rc;
+    slot.a = na; slot.b = nb; slot.has_b = b.m != nullptr; slot.on = true;
     return RANENV_OK;
 }
 
@@ -1189,17 +1185,17 @@ static int net_bind(ranenv_handle h, float **buf, long long *cap, long long floa
 static int net_use(ranenv_handle h, KP &kp)
 {
     if (!kp.scores && h->kp.policy == RANENV_POLICY_HEAD_NETWORK) {
-        if (!h->head_on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
+        if (!h->head.on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
         if (!h->kp.head_obs) return fail(h, RANENV_E_STATE, "the head policy network reads dev_obs_head: none is bound (ranenv_bind_head_outputs)");
         kp.scores = h->d_net_scores;
         return 1;
     }
     if (kp.scores || h->kp.policy != RANENV_POLICY_NETWORK) return 0;
-    if (!h->net_on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!h->actor.on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
     if (!kp.obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
-    if (h->net_has_intra && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
+    if (h->actor.has_b && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
     kp.scores = h->d_net_scores;
-    if (h->net_has_intra) { kp.intra = h->d_net_intra; kp.fixed_intra = RANENV_INTRA_PER_SLICE; }
+    if (h->actor.has_b) { kp.intra = h->d_net_intra; kp.fixed_intra = RANENV_INTRA_PER_SLICE; }
     return 1;
 }
 
@@ -1228,8 +1224,8 @@ static PolicyIO net_io(ranenv_handle h, const KP &kp)
 
 static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
 {
-    if (head_policy(h)) return launch_head_policy(s, h->head_net, net_io(h, kp), e0, n);
-    return launch_policy(s, h->net_inter, h->net_has_intra ? &h->net_intra : nullptr, net_io(h, kp), e0, n);
+    if (head_policy(h)) return launch_head_policy(s, h->head.a, net_io(h, kp), e0, n);
+    return launch_policy(s, h->actor.a, h->actor.has_b ? &h->actor.b : nullptr, net_io(h, kp), e0, n);
 }
 
 // The buffers the nets' actions go to and the step reads them from (IBSched nets and head nets share them: one policy acts at a time)
@@ -1241,49 +1237,32 @@ static int net_action_buffers(ranenv_handle h)
     return rc == RANENV_OK ? dev_alloc(h, &h->d_net_intra, BS) : rc;
 }
 
-int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed, void *stream_)
+int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice net is required (intra may be NULL)");
-    PolicyNet ni{}, na{};
-    long long off = 0;
-    int rc = net_layout(h, inter, NET_INTER, ni, off);
-    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, NET_INTRA, na, off);
+    const int rc = net_set(h, h->actor, {inter, NET_INTER}, {intra, NET_INTRA}, (hipStream_t)stream, [&] { return net_action_buffers(h); });
     if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = net_action_buffers(h);
-    if (rc == RANENV_OK) rc = net_bind(h, &h->d_net_w, &h->net_cap, off, (hipStream_t)stream_, {{inter, &ni}, {intra, &na}});
-    if (rc != RANENV_OK) return rc;
-    h->net_inter = ni; h->net_intra = na; h->net_has_intra = intra != nullptr;
-    h->net_stochastic = stochastic != 0; h->net_seed = seed; h->net_on = true;
+    h->net_stochastic = stochastic != 0; h->net_seed = seed;
     return RANENV_OK;
 }
 
 int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra)
 {
     if (!h || !dev_scores || !dev_intra) return fail(h, RANENV_E_INVALID, "null argument");
-    if (!h->net_on && !h->head_on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
-    *dev_scores = h->d_net_scores; *dev_intra = (h->net_on && h->net_has_intra) ? h->d_net_intra : nullptr;
+    if (!h->actor.on && !h->head.on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
+    *dev_scores = h->d_net_scores; *dev_intra = (h->actor.on && h->actor.has_b) ? h->d_net_intra : nullptr;
     return RANENV_OK;
 }
 
-int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, void *stream_)
+int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice value net is required (intra may be NULL)");
-    if (intra && !(h->net_on && h->net_has_intra)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
-    if (intra && intra->input_layout != h->net_intra.layout)
-        return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, h->net_intra.layout);
-    PolicyNet ni{}, na{};
-    long long off = 0;
-    int rc = net_layout(h, inter, NET_INTER_VALUE, ni, off);
-    if (rc == RANENV_OK && intra) rc = net_layout(h, intra, NET_INTRA_VALUE, na, off);
-    if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = net_bind(h, &h->d_val_w, &h->val_cap, off, (hipStream_t)stream_, {{inter, &ni}, {intra, &na}});
-    if (rc != RANENV_OK) return rc;
-    h->val_inter = ni; h->val_intra = na; h->val_has_intra = intra != nullptr; h->val_on = true;
-    return RANENV_OK;
+    if (intra && !(h->actor.on && h->actor.has_b)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
+    if (intra && intra->input_layout != h->actor.b.layout)
+        return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, h->actor.b.layout);
+    return net_set(h, h->value, {inter, NET_INTER_VALUE}, {intra, NET_INTRA_VALUE}, (hipStream_t)stream);
 }
 
 int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int32_t dist, const float *dev_log_std, int32_t stochastic,
@@ -1294,35 +1273,24 @@ int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int
     if (dist != RANENV_HEAD_DIST_GAUSS_CLIP && dist != RANENV_HEAD_DIST_GAUSS_TANH) return fail(h, RANENV_E_INVALID, "unknown head distribution %d", dist);
     if (dist == RANENV_HEAD_DIST_GAUSS_CLIP && !dev_log_std) return fail(h, RANENV_E_INVALID, "GAUSS_CLIP needs dev_log_std [S]");
     if (dist == RANENV_HEAD_DIST_GAUSS_TANH && dev_log_std) return fail(h, RANENV_E_INVALID, "GAUSS_TANH takes log_std from the net: dev_log_std must be NULL");
-    const int S = h->cfg.n_slices;
-    PolicyNet net{};
-    long long off = 0;
-    int rc = net_layout(h, actor, dist == RANENV_HEAD_DIST_GAUSS_TANH ? NET_HEAD_TANH : NET_HEAD_CLIP, net, off);
-    if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t S = (size_t)h->cfg.n_slices;
     hipStream_t s = (hipStream_t)stream_;
-    rc = net_action_buffers(h);
-    if (rc == RANENV_OK && !h->d_head_log_std) rc = dev_alloc(h, &h->d_head_log_std, (size_t)S);
-    if (rc == RANENV_OK) rc = net_bind(h, &h->d_head_w, &h->head_cap, off, s, {{actor, &net}});
+    const int rc = net_set(h, h->head, {actor, dist == RANENV_HEAD_DIST_GAUSS_TANH ? NET_HEAD_TANH : NET_HEAD_CLIP}, {nullptr, NET_HEAD_CLIP}, s, [&] {
+        int ra = net_action_buffers(h);
+        if (ra == RANENV_OK && !h->d_head_log_std) ra = dev_alloc(h, &h->d_head_log_std, S);
+        if (ra == RANENV_OK && dev_log_std) HIP_TRY(h, hipMemcpyAsync(h->d_head_log_std, dev_log_std, sizeof(float) * S, hipMemcpyDeviceToDevice, s));
+        return ra;
+    });
     if (rc != RANENV_OK) return rc;
-    if (dev_log_std) HIP_TRY(h, hipMemcpyAsync(h->d_head_log_std, dev_log_std, sizeof(float) * (size_t)S, hipMemcpyDeviceToDevice, s));
-    h->head_net = net; h->head_dist = dist; h->head_stochastic = stochastic != 0; h->head_seed = seed; h->head_on = true;
+    h->head_dist = dist; h->head_stochastic = stochastic != 0; h->head_seed = seed;
     return RANENV_OK;
 }
 
-int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, void *stream_)
+int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!critic) return fail(h, RANENV_E_INVALID, "the head critic is required");
-    PolicyNet net{};
-    long long off = 0;
-    int rc = net_layout(h, critic, NET_HEAD_VALUE, net, off);
-    if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = net_bind(h, &h->d_head_val_w, &h->head_val_cap, off, (hipStream_t)stream_, {{critic, &net}});
-    if (rc != RANENV_OK) return rc;
-    h->head_val = net; h->head_val_on = true;
-    return RANENV_OK;
+    return net_set(h, h->head_value, {critic, NET_HEAD_VALUE}, {nullptr, NET_HEAD_VALUE}, (hipStream_t)stream);
 }
 
 static int check_ready(ranenv_handle h, const float *se_tiles, const double *traffic_bits, bool need_traffic)
@@ -1618,13 +1586,22 @@ int ranenv_set_partitions(ranenv_handle h, int32_t n_parts)
 // without the host: the advance kernel + the step kernel in RESET mode follow that TTI's step on the partition's stream.  They are
 // only enqueued for TTIs at which some env of the partition finishes: the step counters are read once at the start and followed on
 // the host (nothing but this rollout changes them until it returns).
-// ranenv_collect / ranenv_collect_head: the caller's record, from either public struct
+// What a rollout records beside stepping.  ranenv_collect / ranenv_collect_head: the caller's record, from either public struct
 struct Record {
     PolicyRec rec{};               // slot 0 of what the policy launches write (head: obs_inter / action_inter are its obs_head / action, cols = 1)
-    double *reward = nullptr;      // [T][B][reward_cols] the step's reward rows / the head kernel's pairs, written straight into the slots
-    int reward_cols = 0, gae_col = 0;      // GAE runs on rec.cols columns from column gae_col on
-    uint8_t *done = nullptr;
+    int gae_col = 0;               // GAE(gamma, lambda) runs on rec.cols columns of the reward rows from column gae_col on
+    double gamma = 0.0, lambda = 0.0;
     float *adv = nullptr, *vtarg = nullptr;
+};
+// ... or ranenv_collect_replay's ring; and, either way, where the step writes a TTI's done flags and reward rows (under a head policy: the
+// head kernel its reward pairs) instead of the caller's buffers: slot (first + t) % slots of [slots][B] / [slots][B][reward_cols]
+struct Recording {
+    const Record *ppo = nullptr;
+    const ranenv_replay *ring = nullptr;
+    uint8_t *done = nullptr; double *reward = nullptr;      // (null: not recorded)
+    int reward_cols = 0;
+    long long first = 0, slots = 1;
+    size_t slot(int t) const { return (size_t)((first + t) % slots); }
 };
 
 struct Rollout {
@@ -1635,8 +1612,7 @@ struct Rollout {
     std::vector<int32_t> steps;
     AdvanceArgs adv{};
     KP kpr{};
-    const Record *rec = nullptr;   // ranenv_collect / _head: the record (null: a plain rollout)
-    bool replay = false;           // ranenv_collect_replay: every TTI goes to the handle's replay ring
+    const Recording *rec = nullptr;      // (null: a plain rollout)
 };
 
 // TTIs from now until the first episode of envs [lo, hi) ends, that TTI included, between 1 and n.  `n_ends`: at how many different
@@ -1665,7 +1641,7 @@ static hipError_t follow_episode_ends(ranenv_handle h, Rollout &r, int e0, int n
     }
     if (!any) return hipSuccess;
     AdvanceArgs a = r.adv; a.e0 = e0;
-    if (done) a.done = done;                       // (ranenv_collect: the step wrote the flags into the record's slot)
+    if (done) a.done = done;                       // (a recording rollout: the step wrote the flags into the slot)
     h->pclass_dirty = true;                        // the restarted envs' scenarios
     launch_advance(s, (unsigned)n, a);
     return launch_range<MODE_RESET>(h, r.kpr, e0, n, s);
@@ -1701,75 +1677,71 @@ static int collect_split_of(ranenv_handle h, const PolicyNet &a, const PolicyNet
     return (floats(a) + floats(*v)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
 }
 
-// ranenv_collect / ranenv_collect_head: TTI `t` of a partition's own count for envs [e0, e0 + n) on `s`.  The recording policy launches
-// (actors, record, critics) write slot t; the step writes its reward row (under a head policy: the head kernel behind it its reward
-// pair) and done flag straight into slot t (the kernels index them by env; the reset behind an episode end writes neither,
-// reset_behind), and the advance kernel reads that slot's flags.  Behind the call's last TTI -- and behind its reset, if any -- the
-// critics run once more on the observation as it stands: vf[T].
-static hipError_t collect_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
+// ranenv_collect / ranenv_collect_head: the recording policy launches (actors, record, critics) of envs [e0, e0 + n) on `s` into slot t of
+// the record, or -- critic_only -- the critics alone on the observation as it stands: vf[t]
+static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kpk, int t, bool critic_only, int e0, int n, hipStream_t s)
 {
-    const Record &tr = *r.rec;
     const bool head = head_policy(h);
     const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, Us = (size_t)h->cfg.max_ues_slice, W = 2 * Us + 9, C = (size_t)tr.rec.cols;
-    const bool ia = !head && h->net_has_intra, vc = tr.rec.vf != nullptr, ic = vc && !head && h->val_has_intra;
-    auto slot = [&](auto *p, size_t t_, size_t stride) { return p ? p + t_ * B * stride : nullptr; };
-    const size_t ts = (size_t)t;
+    const bool ia = !head && h->actor.has_b, vc = tr.rec.vf != nullptr, ic = vc && !head && h->value.has_b;
+    auto slot = [&](auto *p, size_t stride) { return p ? p + (size_t)t * B * stride : nullptr; };
     PolicyRec rec{};
-    rec.obs_inter = slot(tr.rec.obs_inter, ts, 10 * S);
-    rec.mask_inter = slot(tr.rec.mask_inter, ts, S);
-    rec.action_inter = slot(tr.rec.action_inter, ts, S);
-    if (ia) {
-        rec.obs_intra = slot(tr.rec.obs_intra, ts, S * W);
-        rec.mask_intra = slot(tr.rec.mask_intra, ts, S * Us);
-        rec.action_intra = slot(tr.rec.action_intra, ts, S);
+    rec.vf = slot(tr.rec.vf, C);
+    rec.cols = (int)C; rec.intra_critic = ic ? 1 : 0; rec.critic_only = critic_only ? 1 : 0;
+    if (!critic_only) {
+        rec.obs_inter = slot(tr.rec.obs_inter, 10 * S);
+        rec.mask_inter = slot(tr.rec.mask_inter, S);
+        rec.action_inter = slot(tr.rec.action_inter, S);
+        if (ia) {
+            rec.obs_intra = slot(tr.rec.obs_intra, S * W);
+            rec.mask_intra = slot(tr.rec.mask_intra, S * Us);
+            rec.action_intra = slot(tr.rec.action_intra, S);
+        }
+        rec.logp = slot(tr.rec.logp, C);
+        rec.intra_actor = ia ? 1 : 0;
     }
-    rec.logp = slot(tr.rec.logp, ts, C);
-    rec.vf = slot(tr.rec.vf, ts, C);
-    rec.cols = (int)C; rec.intra_actor = ia ? 1 : 0; rec.intra_critic = ic ? 1 : 0;
-    if (tr.reward) (head ? kpk.head_reward : kpk.reward) = slot(tr.reward, ts, (size_t)tr.reward_cols);
-    if (tr.done) kpk.done = slot(tr.done, ts, 1);
-    const PolicyIO io = net_io(h, kpk);
-    const PolicyNet &actor = head ? h->head_net : h->net_inter, *intra = ia ? &h->net_intra : nullptr;
-    const PolicyNet *critic = vc ? (head ? &h->head_val : &h->val_inter) : nullptr, *vintra = ic ? &h->val_intra : nullptr;
+    const PolicyNet &actor = head ? h->head.a : h->actor.a, *intra = ia ? &h->actor.b : nullptr;
+    const PolicyNet *critic = vc ? (head ? &h->head_value.a : &h->value.a) : nullptr, *vintra = ic ? &h->value.b : nullptr;
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
     // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").
-    rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, h->net_intra, vintra) << 1 : 0);
-    auto launch = [&](const PolicyRec &rc) {
-        return head ? launch_head_policy_collect(s, actor, critic, io, rc, e0, n) : launch_policy_collect(s, actor, intra, critic, vintra, io, rc, e0, n);
-    };
-    hipError_t le = launch(rec);
-    if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
-    if (le == hipSuccess) le = follow_episode_ends(h, r, e0, n, 1, s, kpk.done);
-    if (le != hipSuccess || t + 1 < r.n_steps || !vc) return le;
-    PolicyRec last{};
-    last.vf = slot(tr.rec.vf, ts + 1, C);
-    last.cols = rec.cols; last.intra_critic = rec.intra_critic; last.critic_only = 1;
-    return launch(last);
+    if (!critic_only) rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, h->actor.b, vintra) << 1 : 0);
+    const PolicyIO io = net_io(h, kpk);
+    return head ? launch_head_policy_collect(s, actor, critic, io, rec, e0, n) : launch_policy_collect(s, actor, intra, critic, vintra, io, rec, e0, n);
 }
 
-// ranenv_collect_replay: TTI `t` of a partition's own count for envs [e0, e0 + n) on `s`, into slot (TTIs recorded so far + t) % C of the
-// ring.  The plain actor launch and step; between them the partition's rows -- one contiguous range of the slot -- are copied: the
-// observation the action was computed from and the scores the step consumes; the step's done flags and the head
-// kernel's reward pair go straight into the slot (as in collect_tti); then the observation the head kernel left, BEFORE the reset behind
-// an episode end refreshes it: the terminal observation of the envs that finished, the next slot's obs of all others.
-static hipError_t replay_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
+// One launch of a partition's walk: TTI `t` of its own count, kpk.n_tti TTIs (one under a policy net or a recording), for envs
+// [e0, e0 + n) on `s`.  The order on the stream is the content of two rules.  The ring's next_obs is copied BEFORE the reset behind an
+// episode end refreshes the head observation: the terminal observation of the envs that finished, the next slot's obs of all others.
+// The record's vf[T] is computed BEHIND that reset: the value of the observation the next call starts from.
+static hipError_t rollout_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0, int n, hipStream_t s)
 {
-    const ranenv_replay &ring = h->ring;
-    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices;
-    const size_t slot = (size_t)((h->ring_written + t) % ring.capacity) * B, at = slot + (size_t)e0;      // the slot's first row, the range's
-    typedef unsigned long long word;
-    const long long obs_words = (long long)n * 5 * (long long)S;      // a row: 10 * S floats
-    const word *head_rows = (const word *)(h->kp.head_obs + (size_t)e0 * 10 * S);
-    hipError_t le = net_launch(h, kpk, e0, n, s);
+    const Recording *rec = r.rec;
+    const Record *ppo = rec ? rec->ppo : nullptr;
+    const ranenv_replay *ring = rec ? rec->ring : nullptr;
+    const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, row = rec ? rec->slot(t) * B : 0;      // the slot's first row
+    // 1. the policy: recording (actors, record, critics), plain, or none
+    hipError_t le = ppo ? collect_policy(h, *ppo, kpk, t, false, e0, n, s) : (r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess);
     if (le != hipSuccess) return le;
-    kpk.head_reward = ring.reward_head + slot * 2;      // (the kernels index both by env)
-    kpk.done = ring.done + slot;
-    launch_copy_words(s, (word *)(ring.obs + at * 10 * S), head_rows, obs_words,      // (one launch for both: the actor only read the observation)
-                      (word *)(ring.action + at * S), (const word *)(h->d_net_scores + (size_t)e0 * S), (long long)n * (long long)S);
+    // 2. the step's done flags and reward rows go straight into the slot (the kernels index them by env; the reset writes neither, reset_behind)
+    if (rec && rec->reward) (head_policy(h) ? kpk.head_reward : kpk.reward) = rec->reward + row * (size_t)rec->reward_cols;
+    if (rec && rec->done) kpk.done = rec->done + row;
+    // 3. ring: the partition's rows -- one contiguous range of the slot -- of the observation the action was computed from and of the scores
+    // the step consumes (one launch for both: the actor only read the observation)
+    typedef unsigned long long word;
+    const size_t at = row + (size_t)e0;
+    const long long obs_words = (long long)n * 5 * (long long)S;      // a row: 10 * S floats
+    const word *head_rows = ring ? (const word *)(h->kp.head_obs + (size_t)e0 * 10 * S) : nullptr;
+    if (ring)
+        launch_copy_words(s, (word *)(ring->obs + at * 10 * S), head_rows, obs_words, (word *)(ring->action + at * S),
+                          (const word *)(h->d_net_scores + (size_t)e0 * S), (long long)n * (long long)S);
+    // 4. the step;  5. ring: the observation the head kernel left;  6. the episode ends, by the slot's flags
     le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
     if (le != hipSuccess) return le;
-    launch_copy_words(s, (word *)(ring.next_obs + at * 10 * S), head_rows, obs_words, nullptr, nullptr, 0);
-    return follow_episode_ends(h, r, e0, n, 1, s, kpk.done);
+    if (ring) launch_copy_words(s, (word *)(ring->next_obs + at * 10 * S), head_rows, obs_words, nullptr, nullptr, 0);
+    le = follow_episode_ends(h, r, e0, n, kpk.n_tti, s, kpk.done);
+    // 7. record, behind the call's last TTI: the critics once more
+    if (le != hipSuccess || !ppo || !ppo->rec.vf || t + 1 < r.n_steps) return le;
+    return collect_policy(h, *ppo, kpk, t + 1, true, e0, n, s);
 }
 
 // Every partition walks through the TTIs in launches of its own, on its own stream
@@ -1813,12 +1785,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
             KP kpk = r.kp;
             kpk.n_tti = n_tti;
             h->last_rollout_launches++;
-            if (r.rec) return collect_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
-            if (r.replay) return replay_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
-            hipError_t le = r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess;
-            if (le == hipSuccess) le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
-            if (le != hipSuccess) return le;
-            return follow_episode_ends(h, r, e0, n, n_tti, s);
+            return rollout_tti(h, r, kpk, pdone[(size_t)part_of(e0)], e0, n, s);
         });
         if (e != hipSuccess) return fail(h, RANENV_E_HIP, "rollout, round %d of launches: %s", round, hipGetErrorString(e));
         for (int k = 0; k < np; k++) pdone[(size_t)k] += pn[(size_t)k];
@@ -1826,9 +1793,9 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
     return RANENV_OK;
 }
 
-// ranenv_rollout, and with `rec` ranenv_collect / ranenv_collect_head (gamma / lambda: their GAE pass)
+// ranenv_rollout, and with `rec` ranenv_collect / ranenv_collect_head / ranenv_collect_replay
 static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream_,
-                       const Record *rec = nullptr, double gamma = 0.0, double lambda = 0.0, bool replay = false)
+                       const Recording *rec = nullptr)
 {
     int rc = check_ready(h, nullptr, nullptr, true);
     if (rc != RANENV_OK) return rc;
@@ -1849,7 +1816,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
     r.net = net_use(h, r.kp);
     if (r.net < 0) return r.net;
-    r.rec = rec; r.replay = replay;
+    r.rec = rec;
     rc = compact_for(h, r.kp, stream, &r.kp.compact);
     if (rc != RANENV_OK) return rc;
     if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_plan)
@@ -1884,24 +1851,17 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     if (rec) {
         // (the partitions have joined the caller's stream)  The caller's reward -- under a head policy: the bound head rewards -- and
         // done hold the last TTI's values, as after a rollout
-        const size_t B = (size_t)h->cfg.batch, C = (size_t)rec->reward_cols, last = (size_t)n_steps - 1;
+        const size_t B = (size_t)h->cfg.batch, C = (size_t)rec->reward_cols, last = rec->slot(n_steps - 1) * B;
         double *last_reward = head_policy(h) ? h->kp.head_reward : reward;
         if (rec->reward && last_reward)
-            HIP_TRY(h, hipMemcpyAsync(last_reward, rec->reward + last * B * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
-        if (rec->done && done) HIP_TRY(h, hipMemcpyAsync(done, rec->done + last * B, B, hipMemcpyDeviceToDevice, stream));
-        if (rec->adv || rec->vtarg) {
-            launch_gae(stream, n_steps, h->cfg.batch, rec->rec.cols, rec->reward + rec->gae_col, (int)C, rec->rec.vf, rec->done, gamma, lambda,
-                       rec->adv, rec->vtarg);
+            HIP_TRY(h, hipMemcpyAsync(last_reward, rec->reward + last * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
+        if (rec->done && done) HIP_TRY(h, hipMemcpyAsync(done, rec->done + last, B, hipMemcpyDeviceToDevice, stream));
+        if (const Record *ppo = rec->ppo; ppo && (ppo->adv || ppo->vtarg)) {
+            launch_gae(stream, n_steps, h->cfg.batch, ppo->rec.cols, rec->reward + ppo->gae_col, (int)C, ppo->rec.vf, rec->done, ppo->gamma,
+                       ppo->lambda, ppo->adv, ppo->vtarg);
             HIP_TRY(h, hipGetLastError());
         }
-    }
-    if (replay) {
-        // (the partitions have joined the caller's stream)  As after a rollout: the bound head rewards and the caller's done hold the last TTI's
-        const size_t B = (size_t)h->cfg.batch, last = (size_t)((h->ring_written + n_steps - 1) % h->ring.capacity);
-        if (h->kp.head_reward)
-            HIP_TRY(h, hipMemcpyAsync(h->kp.head_reward, h->ring.reward_head + last * B * 2, sizeof(double) * B * 2, hipMemcpyDeviceToDevice, stream));
-        if (done) HIP_TRY(h, hipMemcpyAsync(done, h->ring.done + last * B, B, hipMemcpyDeviceToDevice, stream));
-        h->ring_written += n_steps;
+        if (rec->ring) h->ring_written += n_steps;
     }
     if (r.follow) { h->sh_steps = r.steps; h->sh_valid = true; h->last_done = done; }      // (read from the device above, followed exactly since)
     else shadow_steps_add(h, 0, h->cfg.batch, n_steps, done, stream);
@@ -1924,16 +1884,17 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
     if ((traj->adv || traj->vtarg) && !(traj->reward && traj->vf && traj->done))
         return fail(h, RANENV_E_INVALID, "adv / vtarg need the record's reward, vf and done");
     if (h->kp.policy != RANENV_POLICY_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect needs policy NETWORK (ranenv_set_policy)");
-    if (!h->net_on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
-    if (!h->val_on) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
-    if (h->val_has_intra && !(h->net_has_intra && h->net_intra.layout == h->val_intra.layout))
+    if (!h->actor.on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!h->value.on) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
+    if (h->value.has_b && !(h->actor.has_b && h->actor.b.layout == h->value.b.layout))
         return fail(h, RANENV_E_STATE, "the intra value net was bound for another intra policy net (bind it again, ranenv_set_value_network)");
-    Record rec;
-    rec.rec.obs_inter = traj->obs_inter; rec.rec.obs_intra = traj->obs_intra; rec.rec.mask_inter = traj->mask_inter; rec.rec.mask_intra = traj->mask_intra;
-    rec.rec.action_inter = traj->action_inter; rec.rec.action_intra = traj->action_intra; rec.rec.logp = traj->logp; rec.rec.vf = traj->vf;
-    rec.rec.cols = rec.reward_cols = h->cfg.n_slices + 1;
-    rec.reward = traj->reward; rec.done = traj->done; rec.adv = traj->adv; rec.vtarg = traj->vtarg;
-    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec, gamma, lambda);
+    Record ppo;
+    ppo.rec.obs_inter = traj->obs_inter; ppo.rec.obs_intra = traj->obs_intra; ppo.rec.mask_inter = traj->mask_inter; ppo.rec.mask_intra = traj->mask_intra;
+    ppo.rec.action_inter = traj->action_inter; ppo.rec.action_intra = traj->action_intra; ppo.rec.logp = traj->logp; ppo.rec.vf = traj->vf;
+    ppo.rec.cols = h->cfg.n_slices + 1;
+    ppo.gamma = gamma; ppo.lambda = lambda; ppo.adv = traj->adv; ppo.vtarg = traj->vtarg;
+    const Recording rec{&ppo, nullptr, traj->done, traj->reward, ppo.rec.cols, 0, n_steps};
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec);
 }
 
 static_assert(sizeof(ranenv_head_trajectory) == RANENV_HEAD_TRAJECTORY_BYTES, "ranenv_head_trajectory: 8 device pointers");
@@ -1948,15 +1909,16 @@ int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_traj
     if ((traj->adv || traj->vtarg) && !(traj->reward_head && traj->vf && traj->done))
         return fail(h, RANENV_E_INVALID, "adv / vtarg need the record's reward_head, vf and done");
     if (h->kp.policy != RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect_head needs policy HEAD_NETWORK (ranenv_set_policy)");
-    if (!h->head_on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
+    if (!h->head.on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
     if (h->head_dist != RANENV_HEAD_DIST_GAUSS_CLIP)
         return fail(h, RANENV_E_INVALID, "only GAUSS_CLIP (PPO) head policies collect: SAC is off-policy and records no log-probabilities");
-    if (!h->head_val_on) return fail(h, RANENV_E_STATE, "no head value network bound (ranenv_set_head_value_network)");
-    Record rec;
-    rec.rec.obs_inter = traj->obs_head; rec.rec.action_inter = traj->action; rec.rec.logp = traj->logp; rec.rec.vf = traj->vf;
-    rec.rec.cols = 1; rec.reward_cols = 2; rec.gae_col = reward_col;
-    rec.reward = traj->reward_head; rec.done = traj->done; rec.adv = traj->adv; rec.vtarg = traj->vtarg;
-    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec, gamma, lambda);
+    if (!h->head_value.on) return fail(h, RANENV_E_STATE, "no head value network bound (ranenv_set_head_value_network)");
+    Record ppo;
+    ppo.rec.obs_inter = traj->obs_head; ppo.rec.action_inter = traj->action; ppo.rec.logp = traj->logp; ppo.rec.vf = traj->vf;
+    ppo.rec.cols = 1; ppo.gae_col = reward_col;
+    ppo.gamma = gamma; ppo.lambda = lambda; ppo.adv = traj->adv; ppo.vtarg = traj->vtarg;
+    const Recording rec{&ppo, nullptr, traj->done, traj->reward_head, 2, 0, n_steps};
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec);
 }
 
 // ---- off-policy collection (SAC): replay ring, sampler, targets -------------------------------------------------------------------
@@ -1991,10 +1953,11 @@ int ranenv_collect_replay(ranenv_handle h, int32_t n_steps, float *obs_inter, fl
     if (!h->ring_on) return fail(h, RANENV_E_STATE, "no replay ring bound (ranenv_bind_replay)");
     if (n_steps > h->ring.capacity) return fail(h, RANENV_E_INVALID, "n_steps %d exceeds the ring's capacity %d", n_steps, h->ring.capacity);
     if (h->kp.policy != RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect_replay needs policy HEAD_NETWORK (ranenv_set_policy)");
-    if (!h->head_on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
+    if (!h->head.on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
     if (!h->kp.head_obs) return fail(h, RANENV_E_STATE, "the replay ring records dev_obs_head: none is bound (ranenv_bind_head_outputs)");
     if (!aligned8(h->kp.head_obs)) return fail(h, RANENV_E_INVALID, "the replay ring copies dev_obs_head as 8-byte words: it must be 8-byte aligned");
-    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, nullptr, 0.0, 0.0, true);
+    const Recording rec{nullptr, &h->ring, h->ring.done, h->ring.reward_head, 2, h->ring_written, h->ring.capacity};
+    return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec);
 }
 
 int ranenv_replay_sample(ranenv_handle h, int64_t n, uint64_t seed, uint64_t draw, int32_t reward_col, float *dev_obs, float *dev_action,
@@ -2019,23 +1982,16 @@ int ranenv_replay_sample(ranenv_handle h, int64_t n, uint64_t seed, uint64_t dra
     return RANENV_OK;
 }
 
-int ranenv_set_sac_critics(ranenv_handle h, const ranenv_mlp *q1, const ranenv_mlp *q2, void *stream_)
+int ranenv_set_sac_critics(ranenv_handle h, const ranenv_mlp *q1, const ranenv_mlp *q2, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!q1 || !q2) return fail(h, RANENV_E_INVALID, "both SAC critics are required");
     if (q1->n_hidden != q2->n_hidden || q1->activation != q2->activation) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape");
-    PolicyNet n1{}, n2{};
-    long long off = 0;
-    int rc = net_layout(h, q1, NET_SAC_Q, n1, off);
-    if (rc == RANENV_OK) rc = net_layout(h, q2, NET_SAC_Q, n2, off);
-    if (rc != RANENV_OK) return rc;
-    for (int l = 0; l <= q1->n_hidden + 1; l++)
-        if (q1->dims[l] != q2->dims[l]) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape (width %d: %d and %d)", l, q1->dims[l], q2->dims[l]);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    rc = net_bind(h, &h->d_sac_w, &h->sac_cap, off, (hipStream_t)stream_, {{q1, &n1}, {q2, &n2}});
-    if (rc != RANENV_OK) return rc;
-    h->sac_q1 = n1; h->sac_q2 = n2; h->sac_on = true;
-    return RANENV_OK;
+    return net_set(h, h->sac, {q1, NET_SAC_Q}, {q2, NET_SAC_Q}, (hipStream_t)stream, [&] {      // (each critic is valid by itself here)
+        for (int l = 0; l <= q1->n_hidden + 1; l++)
+            if (q1->dims[l] != q2->dims[l]) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape (width %d: %d and %d)", l, q1->dims[l], q2->dims[l]);
+        return (int)RANENV_OK;
+    });
 }
 
 int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, const float *dev_reward, const uint8_t *dev_done, double gamma,
@@ -2045,16 +2001,16 @@ int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, co
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (n < 1 || n > (int64_t)0x7FFFFFFF * NET_ROWS) return fail(h, RANENV_E_INVALID, "n must be >= 1 (and fit one launch)");
     if (!dev_next_obs || !dev_reward || !dev_done || !dev_target) return fail(h, RANENV_E_INVALID, "SAC targets: next_obs, reward, done and target are required");
-    if (!h->head_on || h->head_dist != RANENV_HEAD_DIST_GAUSS_TANH)
+    if (!h->head.on || h->head_dist != RANENV_HEAD_DIST_GAUSS_TANH)
         return fail(h, RANENV_E_STATE, "SAC targets need a GAUSS_TANH head actor (ranenv_set_head_policy_network)");
-    if (!h->sac_on) return fail(h, RANENV_E_STATE, "no SAC critics bound (ranenv_set_sac_critics)");
+    if (!h->sac.on) return fail(h, RANENV_E_STATE, "no SAC critics bound (ranenv_set_sac_critics)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     SacArgs a{};
     a.n = n; a.S = h->cfg.n_slices;
     a.next_obs = dev_next_obs; a.reward = dev_reward; a.done = dev_done;
     a.gamma = gamma; a.ent_coef = ent_coef; a.stochastic = stochastic != 0; a.seed = seed; a.draw = draw;
     a.target = dev_target; a.next_action = dev_next_action; a.next_logp = dev_next_logp; a.q = dev_q;
-    const hipError_t le = launch_sac_targets((hipStream_t)stream, h->head_net, h->sac_q1, h->sac_q2, a);
+    const hipError_t le = launch_sac_targets((hipStream_t)stream, h->head.a, h->sac.a, h->sac.b, a);
     if (le != hipSuccess) return fail(h, RANENV_E_HIP, "SAC target launch: %s", hipGetErrorString(le));
     return RANENV_OK;
 }

@@ -28,34 +28,52 @@ __host__ __device__ inline int net_ld_max(const PolicyNet &net)
     return m;
 }
 
+// The workgroup's 32 LDS rows of K0 columns at `dst` (stride net_ld(K0)) from at(row, column); columns [skip0, skip1) are left to the caller
+template <class F>
+__device__ __forceinline__ void load_rows(int K0, int skip0, int skip1, float *dst, int tid, F at)
+{
+    const int ld0 = net_ld(K0);
+    for (int i = tid; i < NET_ROWS * K0; i += 256) {
+        const int r = i / K0, k = i - r * K0;
+        if (k >= skip0 && k < skip1) continue;
+        dst[r * ld0 + k] = at(r, k);
+    }
+}
+
+// Element (g, k) of the dense float array src [n][width], 0 beyond column `cols` and beyond row n.  `rec` non-null: a copy of the
+// array in the making, the element is written there on the way.
+__device__ __forceinline__ float dense_at(const float *src, float *rec, long long g, long long n, int width, int cols, int k)
+{
+    if (g >= n || k >= cols) return 0.0f;
+    const size_t at = (size_t)g * (size_t)width + k;
+    const float v = src[at];
+    if (rec) rec[at] = v;
+    return v;
+}
+
+// Rows first .. first + 31 of such an array -> LDS with zero padding
+__device__ __forceinline__ void load_dense_rows(const float *src, long long first, long long n, int width, int cols, int K0, int skip0, int skip1, float *dst, int tid)
+{
+    load_rows(K0, skip0, skip1, dst, tid, [&](int r, int k) { return dense_at(src, nullptr, first + r, n, width, cols, k); });
+}
+
 // Observation rows of `net`'s input -> LDS (zeros beyond the input and beyond the launch's rows).  REC: the rows are written to the
 // record's slot on the way (the observation the TTI's action is computed from).
 template <bool REC>
 __device__ __forceinline__ void net_load_rows(const PolicyNet &net, const PolicyIO &io, const PolicyRec &rec, int kind, int e0, int row0, int n_rows,
                                               float *cur, int tid)
 {
-    const int S = io.S;
-    const int K0 = net.kp[0], ld0 = net_ld(K0);
-    for (int i = tid; i < NET_ROWS * K0; i += 256) {
-        const int r = i / K0, k = i - r * K0, g = row0 + r;
-        float v = 0.0f;
-        if (g < n_rows && k < net.in_dim) {
-            if (kind == 0) {
-                v = io.obs_inter[(size_t)(e0 + g) * (size_t)(10 * S) + k];
-                if (REC && rec.obs_inter) rec.obs_inter[(size_t)(e0 + g) * (size_t)(10 * S) + k] = v;
-            } else {
-                const size_t es = (size_t)e0 * S + g;
-                const int ko = net.layout == RANENV_NET_IN_MASK_OBS ? k - io.Us : k;
-                if (ko < 0) {
-                    v = (float)io.mask_intra[es * io.Us + k];
-                } else {
-                    v = io.obs_intra[es * io.W + ko];
-                    if (REC && rec.obs_intra) rec.obs_intra[es * io.W + ko] = v;
-                }
-            }
-        }
-        cur[r * ld0 + k] = v;
-    }
+    load_rows(net.kp[0], 0, 0, cur, tid, [&](int r, int k) {
+        const int g = row0 + r;
+        if (kind == 0) return dense_at(io.obs_inter, REC ? rec.obs_inter : nullptr, e0 + g, e0 + n_rows, 10 * io.S, net.in_dim, k);
+        if (g >= n_rows || k >= net.in_dim) return 0.0f;
+        const size_t es = (size_t)e0 * io.S + g;
+        const int ko = net.layout == RANENV_NET_IN_MASK_OBS ? k - io.Us : k;
+        if (ko < 0) return (float)io.mask_intra[es * io.Us + k];
+        const float v = io.obs_intra[es * io.W + ko];
+        if (REC && rec.obs_intra) rec.obs_intra[es * io.W + ko] = v;
+        return v;
+    });
 }
 
 // The layers of `net` on the 32 rows in `cur`; on return `cur` holds the output layer's rows (stride net_ld(np[last])).
@@ -123,14 +141,22 @@ __device__ __forceinline__ void draw_words(const PolicyIO &io, int e, unsigned t
                   (unsigned)(io.seed >> 32), o);
 }
 
-// ... and the standard normal draw from them (Box-Muller on words 0 and 1)
+// ... and the standard normal draw from words 0 and 1 (Box-Muller)
+__device__ __forceinline__ double box_muller(const unsigned (&o)[4])
+{
+    const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
 __device__ __forceinline__ double gauss_draw(const PolicyIO &io, int e, unsigned tag)
 {
     unsigned o[4];
     draw_words(io, e, tag, o);
-    const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
-    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    return box_muller(o);
 }
+
+// The Gaussian sample, and SB3's clamp of a squashed Gaussian's log_std in front of it (HEAD / GAUSS_TANH and the SAC target: a = tanh(sample))
+__device__ __forceinline__ double gauss_sample(double mu, double ls, double z) { return mu + exp(ls) * z; }
+__device__ __forceinline__ double clamp_log_std(double ls) { return ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls); }
 
 __device__ __forceinline__ int active_slices(const PolicyIO &io, int e)
 {
@@ -187,15 +213,9 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                 const bool squash = io.dist == RANENV_HEAD_DIST_GAUSS_TANH;
                 double a = (double)cur[r * ld + j];
                 if (io.stochastic) {
-                    double ls;
-                    if (squash) {
-                        ls = (double)cur[r * ld + S + j];
-                        ls = ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls);
-                    } else {
-                        ls = (double)io.log_std[j];
-                    }
+                    const double ls = squash ? clamp_log_std((double)cur[r * ld + S + j]) : (double)io.log_std[j];
                     z = gauss_draw(io, e, HEAD_TAG + (unsigned)j);
-                    a = a + exp(ls) * z;
+                    a = gauss_sample(a, ls, z);
                 }
                 raw = a;
                 score = squash ? tanh(a) : (a < -1.0 ? -1.0 : (a > 1.0 ? 1.0 : a));
@@ -206,7 +226,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                     double m = (double)cur[r * ld + j];
                     if (io.stochastic) {
                         z = gauss_draw(io, e, POLICY_TAG + (unsigned)j);
-                        m = m + exp((double)cur[r * ld + S + j]) * z;
+                        m = gauss_sample(m, (double)cur[r * ld + S + j], z);
                     }
                     raw = m;
                     score = m < -1.0 ? -1.0 : (m > 1.0 ? 1.0 : m);
@@ -328,13 +348,8 @@ constexpr unsigned SAC_TAG = 0x53414300u;               // "SAC\0": counter word
 // the observation re-read from L2, the actions from the registers of the threads that computed them (position tid + 256 k)
 __device__ __forceinline__ void sac_critic_rows(const PolicyNet &q, const SacArgs &a, long long row0, const float (&a32)[2], float *dst, int tid)
 {
-    const int S = a.S, K0 = q.kp[0], ld0 = net_ld(K0);
-    for (int i = tid; i < NET_ROWS * K0; i += 256) {
-        const int r = i / K0, k = i - r * K0;
-        if (k >= 10 * S && k < 11 * S) continue;
-        const long long g = row0 + r;
-        dst[r * ld0 + k] = (g < a.n && k < 10 * S) ? a.next_obs[(size_t)g * (size_t)(10 * S) + k] : 0.0f;
-    }
+    const int S = a.S, ld0 = net_ld(q.kp[0]);
+    load_dense_rows(a.next_obs, row0, a.n, 10 * S, 10 * S, q.kp[0], 10 * S, 11 * S, dst, tid);
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         const int i = tid + 256 * k;
@@ -354,14 +369,7 @@ __global__ void __launch_bounds__(256) ranenv_sac_target_kernel(PolicyNet actor,
     { const int lq = net_ld_max(q1); ldm = lq > ldm ? lq : ldm; }
     float *cur = lds, *nxt = lds + NET_ROWS * ldm;
 
-    {
-        const int K0 = actor.kp[0], ld0 = net_ld(K0);
-        for (int i = tid; i < NET_ROWS * K0; i += 256) {
-            const int r = i / K0, k = i - r * K0;
-            const long long g = row0 + r;
-            cur[r * ld0 + k] = (g < a.n && k < actor.in_dim) ? a.next_obs[(size_t)g * (size_t)(10 * S) + k] : 0.0f;
-        }
-    }
+    load_dense_rows(a.next_obs, row0, a.n, 10 * S, actor.in_dim, actor.kp[0], 0, 0, cur, tid);
     __syncthreads();
     net_layers(actor, cur, nxt, lane, wave);
 
@@ -376,18 +384,15 @@ __global__ void __launch_bounds__(256) ranenv_sac_target_kernel(PolicyNet actor,
         const int r = i / S, j = i - r * S;
         const long long g = row0 + r;
         if (g >= a.n) continue;
-        double ls = (double)cur[r * ld + S + j];
-        ls = ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls);
+        const double ls = clamp_log_std((double)cur[r * ld + S + j]);
         double z = 0.0;
         if (a.stochastic) {
             unsigned o[4];
             philox4x32_10((unsigned)g, (unsigned)((unsigned long long)g >> 32), (unsigned)a.draw, SAC_TAG + (unsigned)j, (unsigned)a.seed,
                           (unsigned)(a.seed >> 32), o);
-            const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
-            z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+            z = box_muller(o);
         }
-        const double gj = (double)cur[r * ld + j] + exp(ls) * z;
-        const double aj = tanh(gj);
+        const double aj = tanh(gauss_sample((double)cur[r * ld + j], ls, z));
         a32[k] = (float)aj;
         term[i] = ((((-0.5 * z) * z - ls) - HALF_LN_2PI)) - log((1.0 - aj * aj) + 1e-6);
         if (a.next_action) a.next_action[(size_t)g * S + j] = a32[k];

@@ -20,7 +20,7 @@ from tests import policy_ref as pr
 NETS = {"64x64": [64, 64], "512x3": [512, 512, 512]}
 SIZES = {"S10U100": dict(n_slices=10, n_ues=100, n_rbs=135, rbs_per_rbg=1, max_ues_slice=10),
          "S5U25": dict(n_slices=5, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=10)}
-HALF_LN_2PI = 0.9189385332046727
+HALF_LN_2PI = pr.HALF_LN_2PI
 LN_1E9 = 20.72326583694641
 EPISODE_LENGTHS = (5, 7, 8, 12, 24, 6)      # per env, cyclic: episodes end at different TTIs, several at TTI 24 (the call's last)
 
@@ -109,10 +109,7 @@ def check_actor_record(rec, t, a_inter, a_intra, stochastic, seed, episode, step
     z = np.zeros_like(mean)
     bound = t_mean.copy()
     if stochastic:
-        d = pr.philox_draws(np.arange(B), episode, step, S, seed)
-        u1 = (d[0].astype(np.float64) + 1.0) * 2.0 ** -32
-        u2 = d[1].astype(np.float64) * 2.0 ** -32
-        z = np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+        z = pr.gauss_noise(pr.POLICY_TAG, np.arange(B), episode, step, S, seed)
         sd = np.exp(ls)
         mean = mean + sd * z
         bound = bound + sd * np.abs(z) * np.expm1(t_ls) + 1e-12 * (1.0 + sd * np.abs(z))

@@ -24,7 +24,6 @@ import torch
 from tests import policy_ref as pr
 
 HEAD_TAG = 0x48454100
-HALF_LN_2PI = 0.9189385332046727
 NETS = {"64x64": ([64, 64], "tanh"), "256x256": ([256, 256], "relu"), "512x3": ([512, 512, 512], "tanh")}
 OUT_SCALE = 6.0           # on the output layer: |mean| crosses 1 and SAC's log_std leaves [-20, 2] on a good share of the rows
 
@@ -69,13 +68,7 @@ def layers_of(net):
 
 def noise(env_ids, episode, step, S, seed):
     """z float64 [B, S] of the head policy's Philox counters."""
-    from intent_radio_sched_multi_slice_amd.adapters import philox4x32_10
-    col = lambda a: np.asarray(pr._np(a, np.int64), dtype=np.int64).reshape(-1, 1) & 0xFFFFFFFF  # noqa: E731
-    c3 = HEAD_TAG + np.arange(S, dtype=np.int64)[None, :]
-    d = philox4x32_10(col(env_ids), col(episode), col(step), c3, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
-    u1 = (d[0].astype(np.float64) + 1.0) * 2.0 ** -32
-    u2 = d[1].astype(np.float64) * 2.0 ** -32
-    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+    return pr.gauss_noise(HEAD_TAG, env_ids, episode, step, S, seed)
 
 
 class HeadRef:
@@ -97,6 +90,7 @@ class HeadRef:
             a = a + sd * z
             bound = bound + sd * np.abs(z) * np.expm1(t_ls) + 1e-12 * (1.0 + sd * np.abs(z))
         self.B, self.S = B, S
+        self.out, self.out_t = out, t
         self.action, self.action_bound = a, bound
         self.log_std, self.log_std_bound = ls, t_ls
         if dist == "gauss_clip":
@@ -112,7 +106,7 @@ def logp_ref(log_std, z, B):
     ls = pr._np(log_std, np.float32).astype(np.float64)
     S = ls.shape[0]
     zz = np.zeros((B, S)) if z is None else np.asarray(z, dtype=np.float64)
-    lp = (-0.5 * zz * zz - ls[None, :] - HALF_LN_2PI).sum(axis=1)
+    lp = (-0.5 * zz * zz - ls[None, :] - pr.HALF_LN_2PI).sum(axis=1)
     return lp, 1e-12 * S * (1.0 + np.max(zz * zz, axis=1)) + 2.0 ** -24 * np.abs(lp)
 
 

@@ -10,7 +10,7 @@ evaluation of the same net, and the epilogue's bounds follow from it).
              2e-10 relative (2^-52 / 1e-6), hence 1e-9 per position:
                  t_logp = sum_j (t_ls_j + 2 t_a_j + 1e-9) + 1e-12 S (1 + max z^2) + 2^-24 |logp|
     critics  input [next_obs | a32]: the float64 forward runs on a, and the input bound t0 = t_a + 2^-24 |a| of the action columns (0 of
-             the observation's) is carried through the layers by ``mlp64_in``.  q_k: t_qk + 2^-24 |q_k|
+             the observation's) is carried through the layers by ``mlp64``'s ``t0``.  q_k: t_qk + 2^-24 |q_k|
     min      1-Lipschitz: t_q = max(t_q1, t_q2) + 2^-24 |q|
     target   reward + (1 - d) gamma (min - ent_coef logp):  gamma (1 - d) (t_q + ent_coef t_logp) + 2^-24 |target|  (+ 2^-50 of the
              magnitudes: the float64 evaluations' own rounding).  Rows with done = 1: the bound is that rounding alone, and reward is
@@ -26,8 +26,7 @@ import torch
 from tests import head_policy_ref as hp
 from tests import policy_ref as pr
 
-U32 = pr.U32
-HALF_LN_2PI = 0.9189385332046727
+U32, HALF_LN_2PI = pr.U32, pr.HALF_LN_2PI
 SLIPS = ("sum_not_min", "no_epsilon", "no_entropy", "through_done", "unclamped_log_std")
 OUT_SCALE = 0.5           # on the actor's output layer (head_policy_ref's is 6), and the observations' largest scale: chosen so that
 OBS_SCALE = 0.3           # the target's bound stays below 1e-3 (1 + |target|) on the shared inputs (tests/test_sac_cpu.py holds them to it)
@@ -38,33 +37,6 @@ GAMMA, ENT_COEF = 0.99, 0.2
 CASES = {"64x64": (5, [64, 64], "tanh", [64, 64], "tanh"),              # critic input 55 -> padded 64
          "256x256": (10, [256, 256], "relu", [256, 256], "relu"),       # SB3's SAC default; 110 -> 128
          "odd": (5, [48], "tanh", [96, 96], "relu")}
-
-
-def mlp64_in(x, t0, layers, act: str):
-    """``policy_ref.mlp64`` for inputs that carry a bound of their own: ``x`` [R, K] float64 with |device input - x| <= ``t0`` [R, K]."""
-    h = np.asarray(x, dtype=np.float64)
-    t = np.asarray(t0, dtype=np.float64)
-    m = np.abs(h) + t
-    for i, (w, b) in enumerate(layers):
-        w, b = pr._np(w), pr._np(b)
-        aw = np.abs(w)
-        z = h @ w.T + b
-        a = m @ aw.T + np.abs(b)
-        K = pr.pad32(w.shape[1])
-        t = t @ aw.T + (K + 2) * U32 * a + 2.0 ** -50 * a + K * 2.0 ** -125
-        if i < len(layers) - 1:
-            if act == "tanh":
-                t = t / np.cosh(np.maximum(np.abs(z) - t, 0.0)) ** 2
-                z = np.tanh(z)
-                t = t + pr.TANH_ULPS * 2.0 ** -23 * np.abs(z) + 2.0 ** -126
-            elif act == "relu":
-                t = np.where(z < -t, 0.0, t)
-                z = np.maximum(z, 0.0)
-            else:
-                raise ValueError(act)
-        h = z
-        m = np.abs(h) + t
-    return h, t
 
 
 def noise(n, S, seed, draw):
@@ -79,16 +51,14 @@ class SacRef:
         assert slip is None or slip in SLIPS, slip
         x = pr._np(next_obs, np.float32).astype(np.float64)
         n, S = x.shape[0], x.shape[1] // 10
-        out, t = pr.mlp64(x, *hp.layers_of(actor))
-        mu, t_mu = out[:, :S], t[:, :S]
-        ls = out[:, S:] if slip == "unclamped_log_std" else np.clip(out[:, S:], -20.0, 2.0)
-        t_ls = t[:, S:]
         zz = np.zeros((n, S)) if z is None else np.asarray(z, dtype=np.float64)
-        sd = np.exp(ls)
-        g = mu + sd * zz
-        t_g = t_mu + sd * np.abs(zz) * np.expm1(t_ls) + 1e-12 * (1.0 + sd * np.abs(zz))
-        a = np.tanh(g)
-        t_a = t_g + 1e-12
+        head = hp.HeadRef(next_obs, actor, "gauss_tanh", z=zz)     # (z = 0 in the mode: the kernel adds exp(ls) 0 too)
+        out, mu = head.out, head.out[:, :S]
+        ls, t_ls, g, a, t_a = head.log_std, head.log_std_bound, head.action, head.scores, head.score_bound
+        if slip == "unclamped_log_std":      # its own line: the sample, the action and their bound again, from the raw log_std
+            ls, sd = out[:, S:], np.exp(out[:, S:])
+            g, t_g = mu + sd * zz, head.out_t[:, :S] + sd * np.abs(zz) * np.expm1(t_ls) + 1e-12 * (1.0 + sd * np.abs(zz))
+            a, t_a = np.tanh(g), t_g + 1e-12
         eps = 0.0 if slip == "no_epsilon" else 1e-6
         with np.errstate(divide="ignore"):
             terms = (((-0.5 * zz) * zz - ls) - HALF_LN_2PI) - np.log((1.0 - a * a) + eps)
@@ -101,7 +71,7 @@ class SacRef:
         xa, t0 = np.concatenate([x, a], axis=1), np.concatenate([np.zeros_like(x), t_in], axis=1)
         q, t_q = [], []
         for net in (q1, q2):
-            y, ty = mlp64_in(xa, t0, *hp.layers_of(net))
+            y, ty = pr.mlp64(xa, *hp.layers_of(net), t0)
             q.append(y[:, 0])
             t_q.append(ty[:, 0])
         q, t_q = np.stack(q, axis=1), np.stack(t_q, axis=1)

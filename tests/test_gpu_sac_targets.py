@@ -80,6 +80,26 @@ def test_targets_lie_inside_the_float64_bounds(case, stochastic):
     env.close()
 
 
+@pytest.mark.parametrize("case", ["odd", "256x256"])
+def test_the_target_and_the_head_policy_share_one_squashed_gaussian_epilogue(case):
+    """The mode of the SAC target's a' on an observation IS the score a deterministic "gauss_tanh" head policy steps with on it: the
+    same weights through the same layers, tanh of the same double.  B = 40: one full workgroup of rows and a tail of 8."""
+    _need_gpu()
+    B = 40
+    env, _ = _env(case, B)
+    env.set_head_policy_network(sr.sac_nets(case)[0], "gauss_tanh", stochastic=False)
+    env.reset()
+    snapshot = env.head_obs.clone()
+    env.step()
+    zeros = torch.zeros(B, dtype=torch.float32, device=env.device)
+    got = env.sac_targets(snapshot, zeros, zeros.to(torch.uint8), stochastic=False)["next_action"]
+    scores = env.policy_actions()["scores"].to(torch.float32)
+    torch.cuda.synchronize()
+    assert got.shape == (B, env.S) and bool(torch.any(got != 0))
+    assert np.array_equal(got.cpu().numpy(), scores.cpu().numpy())
+    env.close()
+
+
 def test_actor_and_critics_keep_buffers_of_their_own():
     _need_gpu()
     case = "64x64"
