@@ -183,14 +183,32 @@ def replay(case: dict, census: Optional[Counter] = None, keep: bool = True, tabl
     return dict(case=c, directed=d, tables=tabs, scen=scen, se_pool=se_pool, trf=trf, oenvs=oenvs, steps=steps)
 
 
+def draw_fuzz_case(k):
+    """Case ``k`` of tests/test_gpu_fuzz.py: shape, window depth, load level and the way the TTIs are issued, from a fixed seed."""
+    rng = np.random.default_rng(9000 + k)
+    S = int(rng.integers(1, 17))
+    Us = int(rng.integers(1, 17))
+    U = int(rng.integers(max(2, Us), 257))
+    G = int(rng.choice([1, 1, 2, 3, 5, 8]))
+    # every numpy pairwise shape: below 8, one leaf with and without tail, two, three and four leaves
+    R = int(rng.choice([rng.integers(G, 8 * G + 1), rng.integers(8, 129), rng.integers(129, 257), rng.integers(257, 489)]))
+    R = max(R, G)
+    D = int(rng.choice([10, 10, 1, 2, 7]))
+    load = float(rng.choice([0.2, 1.0, 1.0, 6.0]))        # multiplies the Poisson rows: idle, nominal, congested
+    low_se = int(rng.choice([0, 0, 3]))                  # every third UE has nearly no capacity
+    how = ["external", "device_steps", "device_rollout"][k % 3]
+    policy, intra = [(2, 1), (1, 0), (2, 2), (2, 0)][int(rng.integers(0, 4))]
+    steps = int(rng.choice([12, 12, 30, 48]))            # the shortest latency budget is 20 TTIs: the longer runs expire packets
+    return dict(S=S, U=U, R=R, G=G, Us=Us, D=D, load=load, low_se=low_se, how=how, policy=policy, intra=intra, steps=steps)
+
+
 def replay_fuzz_case(k: int, per_element: bool = False):
     """The oracle half of tests/test_gpu_fuzz.py's case ``k`` (same draws in the same order), in replay()'s form: the
     template-only inputs the directed ones are measured against."""
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
     from tests.common import poisson_traffic_rows
     from tests.synth import se_tile
-    from tests.test_gpu_fuzz import _draw_case
-    c = _draw_case(k)
+    c = draw_fuzz_case(k)
     S, U, R, G, Us, D, T = c["S"], c["U"], c["R"], c["G"], c["Us"], c["D"], c["steps"]
     rng = np.random.default_rng(500 + k)
     tabs = generate_scaled_scenarios(4, seed=40 + k, n_slices=S, n_ues=U, max_ues_slice=Us,

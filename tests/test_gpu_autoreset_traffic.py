@@ -5,20 +5,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests.common import OBS_TOL, REW_TOL
+from tests.gpu_common import need_gpu, small_workload
+
 pytestmark = pytest.mark.gpu
-
-OBS_TOL, REW_TOL = 1e-5, 1e-9
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _small_workload(B, steps, **kw):
-    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
-    return make_mult_slice_workload(B, torch.device("cuda", 0), policy=2, intra=1, n_scenarios=6, n_traces=12, trace_len=10,
-                                    n_slices=5, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=10, max_steps=steps, **kw)
 
 
 @pytest.mark.parametrize("random_episodes", [False, True])
@@ -26,10 +16,10 @@ def test_three_consecutive_episodes_with_device_autoreset_vs_oracle(random_episo
     """B = 64, episode lengths staggered per env (30..50 TTIs), three episodes each, no host-side reset: at `done` the
     device picks the next episode (sequential / counter-based random), installs its descriptor and resets.  The oracle
     side replays the same rule on the host."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     B, L, n_ep, first = 64, 10, 12, 3
-    wl = _small_workload(B, 50)
+    wl = small_workload(B, 50)
     env, tabs = wl.env, wl.tables
     S, U, R = env.S, env.U, env.R
     # episode table: episode n -> scenario n % 6 (associations/mult_slice.py:444-452 with 6 scenarios), its own channel trace
@@ -104,11 +94,11 @@ def test_three_consecutive_episodes_with_device_autoreset_vs_oracle(random_episo
 def test_traffic_generator_tables_and_draws_match_the_numpy_restatement():
     """The device draws equal the numpy restatement (Philox KAT-checked, same inversion tables) bit for bit; the tables
     are Poisson CDFs (against scipy.stats) and the draws have Poisson mean and variance."""
-    _need_gpu()
+    need_gpu()
     from scipy import stats
     from oracle import pyoracle
     B, steps, seed, base = 48, 40, 0x1234567890ABCDEF, 1000
-    wl = _small_workload(B, steps)
+    wl = small_workload(B, steps)
     env, tabs = wl.env, wl.tables
     env.set_traffic_generator(seed, env_id_base=base)
     cdf, guide = env.poisson_tables()
@@ -157,10 +147,10 @@ def test_traffic_generator_tables_and_draws_match_the_numpy_restatement():
 def test_generated_traffic_is_deterministic_and_independent_of_the_actions():
     """results/gen_results.py:1587-1635: pkt_incoming must be identical across agents for the same (seed, episode).
     Same seed, different policies -> identical offered traffic; another seed -> different; a re-run -> identical."""
-    _need_gpu()
+    need_gpu()
     runs = {}
     for name, policy, intra, seed in (("mapf", 2, 1, 7), ("marr", 1, 0, 7), ("mapf_again", 2, 1, 7), ("other_seed", 2, 1, 8)):
-        wl = _small_workload(32, 25)
+        wl = small_workload(32, 25)
         env = wl.env
         env.set_policy(policy, intra)
         env.set_traffic_generator(seed)
@@ -178,11 +168,11 @@ def test_generated_traffic_is_deterministic_and_independent_of_the_actions():
 
 
 def test_marl_batch_env_is_the_reference_layout_on_device_tensors():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.adapters import MarlBatchEnv, masked_gaussian_params, sorted_action_mask
     from oracle import pyoracle
     B, steps = 16, 12
-    wl = _small_workload(B, steps)
+    wl = small_workload(B, steps)
     env, tabs = wl.env, wl.tables
     S, U, R, Us = env.S, env.U, env.R, env.Us
     menv = MarlBatchEnv(env)
@@ -229,10 +219,10 @@ def test_marl_batch_env_is_the_reference_layout_on_device_tensors():
 def test_head_vec_env_with_device_autoreset_costs_one_copy_per_step():
     """HeadVecEnv over an env with an episode table: finished envs restart on the device, infos carry the terminal
     observation, the next observation is the new episode's first one."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.adapters import HeadVecEnv
     B, steps = 8, 6
-    wl = _small_workload(B, steps)
+    wl = small_workload(B, steps)
     env = wl.env
     ep_no = np.arange(0, 6)
     env.set_episode_table(scenario=ep_no % 6, se_base=ep_no * 10, se_len=10, trf_base=(ep_no % 6) * 10, trf_len=10)
@@ -257,12 +247,12 @@ def test_autoreset_enqueues_nothing_when_no_episode_ended_and_the_same_as_ever_w
     """`done` is a function of the step counter alone, and the host follows the counters (include/ranenv.h, ranenv_autoreset): behind
     a TTI at which no episode ended the call enqueues nothing; with flags the host cannot follow (another buffer than the steps'
     `done`) it asks the device as before.  Same state either way, and the launch counts say which path ran."""
-    _need_gpu()
+    need_gpu()
     import ctypes as C
     B, steps = 64, 26
     outs, launches = [], []
     for follow in (True, False):
-        wl = _small_workload(B, steps)
+        wl = small_workload(B, steps)
         env, tabs = wl.env, wl.tables
         n_ep = 12
         ep = np.arange(n_ep)
@@ -302,7 +292,7 @@ def test_autoreset_shadow_follows_random_call_sequences(seed):
     themselves and hand the counters back), full resets, masked resets and new per-env episode lengths (after which the host
     cannot know the counters until the next full reset or rollout).  Handle A uses the library as a trainer would; handle B hands
     every auto-reset a COPY of `done`, which the host cannot follow, so the device decides.  Same state after every call."""
-    _need_gpu()
+    need_gpu()
     import ctypes as C
     B, n_ep, n_ranges = 48, 12, 3
     rng = np.random.default_rng(seed)
@@ -317,7 +307,7 @@ def test_autoreset_shadow_follows_random_call_sequences(seed):
         else: plan.append(("max_steps", rng.integers(3, 10, B).astype(np.int32)))
     envs = []
     for follow in (True, False):
-        wl = _small_workload(B, 7)
+        wl = small_workload(B, 7)
         env, tabs = wl.env, wl.tables
         ep = np.arange(n_ep)
         env.set_episode_table(scenario=(ep * 5) % tabs.n_scenarios, se_base=(ep % 4) * wl.trace_len, se_len=wl.trace_len, se_offset=ep % wl.trace_len,

@@ -4,33 +4,19 @@ exactly, determinism, error paths, NULL fields."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-from tests import collect_ref as cr  # noqa: E402
+from tests import collect_ref as cr
+from tests.gpu_common import LOOSE_WIN_SENT_AND_SE, assert_same_state, need_gpu, to_host
 
 pytestmark = pytest.mark.gpu
 
 T = 24
 FIELDS = ("obs_inter", "obs_intra", "mask_inter", "mask_intra", "action_inter", "action_intra", "logp", "vf", "reward", "done", "adv", "vtarg")
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-
-
-def _cpu(rec):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().copy() for k, v in rec.items()}
 
 
 def _layout(size):
@@ -45,7 +31,7 @@ def _layout(size):
 def test_record_is_the_step_loop(net, size, stochastic, autoreset, se_mode):
     """collect(T) over 1 and 3 partitions records, TTI by TTI, what a step() loop on a twin env sees: observations and masks before
     the step, the actions it consumed, its reward and done -- bit for bit, every row."""
-    _need_gpu()
+    need_gpu()
     B = 48
     kw = dict(stochastic=stochastic, autoreset=autoreset, se_mode=se_mode, intra_input=_layout(size))
     _, ref, _ = cr.make_env(size, net, B, **kw)
@@ -74,16 +60,13 @@ def test_record_is_the_step_loop(net, size, stochastic, autoreset, se_mode):
     ref.close()
 
 
-_KEYS_LOOSE = ("win_sent", "se_mean")      # of a UE outside every slice (after a reset into another scenario): read by no observation
-
-
 @pytest.mark.parametrize("autoreset", [False, True])
 @pytest.mark.parametrize("size", list(cr.SIZES))
 @pytest.mark.parametrize("net", list(cr.NETS))
 def test_nothing_else_moved(net, size, autoreset):
     """After collect(T): every view, the caller's outputs and policy_actions() are those after rollout(T) on the twin; one more
     step() on both keeps them equal (the host's shadow of the step counters and the done buffer it belongs to)."""
-    _need_gpu()
+    need_gpu()
     B = 48
     for parts in (1, 3):
         kw = dict(stochastic=True, autoreset=autoreset, parts=parts, intra_input=_layout(size))
@@ -95,16 +78,7 @@ def test_nothing_else_moved(net, size, autoreset):
             if extra:
                 a.step()
                 b.step()
-            torch.cuda.synchronize()
-            va, vb = a.views(), b.views()
-            in_slice = torch.as_tensor(wl.tables.ue_slice >= 0, device=a.device)[va["episodes"][:, 0].to(torch.int64)]
-            for k in va:
-                x, y = (va[k][in_slice], vb[k][in_slice]) if k in _KEYS_LOOSE else (va[k], vb[k])
-                assert torch.equal(x, y), (k, parts, extra)
-            for k in ("obs_inter", "obs_intra", "reward", "done"):
-                assert torch.equal(getattr(a, k), getattr(b, k)), (k, parts, extra)
-            pa, pb = a.policy_actions(), b.policy_actions()
-            assert torch.equal(pa["scores"], pb["scores"]) and torch.equal(pa["intra"], pb["intra"])
+            assert_same_state(a, b, wl.tables, (parts, extra), loose=LOOSE_WIN_SENT_AND_SE, actions=("scores", "intra"))
         a.close()
         b.close()
 
@@ -115,13 +89,13 @@ def test_nothing_else_moved(net, size, autoreset):
 def test_logp_and_values_within_the_float64_bounds(net, size, stochastic):
     """Every slot's vf, logp and unclamped action_inter against the float64 nets on the RECORDED observations (bounds: collect_ref);
     vf[T] against the critics on the observation buffers as they stand after the call."""
-    _need_gpu()
+    need_gpu()
     B, seed = 64, 0x1234_5678_9ABC
     layout = _layout(size)
     _, env, (a_inter, a_intra, v_inter, v_intra) = cr.make_env(size, net, B, stochastic=stochastic, seed=seed, intra_input=layout)
     v = env.views()
     episode, step0 = v["episode_number"].cpu().numpy().copy(), v["step_number"].cpu().numpy().copy()
-    rec = _cpu(env.collect(T))
+    rec = to_host(env.collect(T))
     worst, n_all_masked = {}, 0
     for t in range(T):
         r, n = cr.check_actor_record(rec, t, a_inter, a_intra, stochastic, seed, episode, step0 + t, layout)
@@ -136,10 +110,10 @@ def test_logp_and_values_within_the_float64_bounds(net, size, stochastic):
 
 def test_values_without_an_intra_critic_and_without_intra_nets():
     """No intra critic: columns 1..S of vf are 0; no intra actor: columns 1..S of logp are 0 too and the intra fields stay untouched."""
-    _need_gpu()
+    need_gpu()
     B = 32
     _, env, (a_inter, a_intra, v_inter, _) = cr.make_env("S5U25", "64x64", B, intra_critic=False)
-    rec = _cpu(env.collect(6))
+    rec = to_host(env.collect(6))
     for t in range(6):
         cr.check_values(rec["vf"][t], rec["obs_inter"][t], None, None, v_inter, None)
     assert np.any(rec["logp"][:, :, 1:] != 0.0)
@@ -148,7 +122,7 @@ def test_values_without_an_intra_critic_and_without_intra_nets():
     out = env.collect(6)
     out["obs_intra"].fill_(7.0)
     out["action_intra"].fill_(9)
-    rec = _cpu(env.collect(6))
+    rec = to_host(env.collect(6))
     assert np.all(rec["logp"][:, :, 1:] == 0.0) and np.all(rec["vf"][:, :, 1:] == 0.0)
     assert np.all(rec["obs_intra"] == 7.0) and np.all(rec["action_intra"] == 9)
     cr.check_values(rec["vf"][6], env.obs_inter, None, None, v_inter, None)
@@ -162,11 +136,11 @@ GAMMA_LAMBDA = [(0.99, 0.95), (0.6, 0.95), (0.999, 1.0), (0.9, 0.0)]
 @pytest.mark.parametrize("size", list(cr.SIZES))
 def test_gae_equals_the_numpy_statement_exactly(size, autoreset):
     """adv / vtarg of the call, and of ranenv_gae with other (gamma, lambda) on the same record, equal adapters.gae bit for bit."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import adapters
     _, env, _ = cr.make_env(size, "64x64", 48, autoreset=autoreset, parts=3, intra_input=_layout(size))
     out = env.collect(T, gamma=0.99, lam=0.95)
-    rec = _cpu(out)
+    rec = to_host(out)
     assert bool(rec["done"].any()) == autoreset
     adv, vtarg = adapters.gae(rec["reward"], rec["vf"], rec["done"], 0.99, 0.95)
     assert np.array_equal(rec["adv"], adv) and np.array_equal(rec["vtarg"], vtarg)
@@ -182,11 +156,11 @@ def test_gae_equals_the_numpy_statement_exactly(size, autoreset):
 @pytest.mark.parametrize("autoreset", [False, True])
 def test_determinism_and_partitions(autoreset):
     """The same seed twice gives identical buffers; 1 against 3 partitions gives identical buffers; another seed does not."""
-    _need_gpu()
+    need_gpu()
     runs = {}
     for key, (parts, seed) in {"a": (1, 11), "a2": (1, 11), "p3": (3, 11), "other": (1, 12)}.items():
         _, env, _ = cr.make_env("S10U100", "64x64", 48, seed=seed, autoreset=autoreset, parts=parts)
-        runs[key] = _cpu(env.collect(T))
+        runs[key] = to_host(env.collect(T))
         env.close()
     for k in FIELDS:
         assert np.array_equal(runs["a"][k], runs["a2"][k]), k
@@ -198,13 +172,13 @@ def test_determinism_and_partitions(autoreset):
 def test_fused_and_split_critic_launches_agree(net):
     """Option collect_split changes a schedule, never a result: the critic fused into its actor's launch, as a launch of its own, and
     the library's own choice give identical records."""
-    _need_gpu()
+    need_gpu()
     runs = []
     for split in (0, 1, -1):
         _, env, _ = cr.make_env("S5U25", net, 48, autoreset=True, parts=3)
         assert env.get_option("collect_split") == -1
         env.set_option("collect_split", split)
-        runs.append(_cpu(env.collect(T)))
+        runs.append(to_host(env.collect(T)))
         env.close()
     for k in FIELDS:
         assert np.array_equal(runs[0][k], runs[1][k]) and np.array_equal(runs[0][k], runs[2][k]), k
@@ -215,7 +189,7 @@ def test_a_critic_wider_and_deeper_than_its_actor():
     sized by the critic and not by the actor; B = 40 (two workgroups of env rows with a tail of 8, 200 intra rows), T = 3 with
     episodes ending at its last TTI.  Fused and split give one record; vf (intra columns and the bootstrap slot included) and logp
     lie within the float64 bounds of collect_ref."""
-    _need_gpu()
+    need_gpu()
     B, n, seed, layout = 40, 3, 0x1234_5678_9ABC, "mask_obs"
     lengths = np.asarray((3, 2, 5, 1), dtype=np.int32)[np.arange(B) % 4]
 
@@ -240,7 +214,7 @@ def test_a_critic_wider_and_deeper_than_its_actor():
     for split in (0, 1):
         env, (a_inter, a_intra, v_inter, v_intra) = make()
         env.set_option("collect_split", split)
-        rec = _cpu(env.collect(n))
+        rec = to_host(env.collect(n))
         runs.append(rec)
         assert rec["done"][-1].any() and not rec["done"][-1].all()
         worst = {}
@@ -258,11 +232,11 @@ def test_a_critic_wider_and_deeper_than_its_actor():
 
 def test_null_fields_are_skipped():
     """A call that records only reward / vf / done / adv / vtarg gives the same five arrays as the full call."""
-    _need_gpu()
+    need_gpu()
     five = ("reward", "vf", "done", "adv", "vtarg")
     _, a, _ = cr.make_env("S5U25", "64x64", 48, autoreset=True, parts=3)
     _, b, _ = cr.make_env("S5U25", "64x64", 48, autoreset=True, parts=3)
-    full, part = _cpu(a.collect(T)), _cpu(b.collect(T, record=five))
+    full, part = to_host(a.collect(T)), to_host(b.collect(T, record=five))
     assert set(part) == set(five)
     for k in five:
         assert np.array_equal(full[k], part[k]), k
@@ -272,7 +246,7 @@ def test_null_fields_are_skipped():
 
 
 def test_error_paths():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
     _, env, _ = cr.make_env("S5U25", "64x64", 16, critics=False)

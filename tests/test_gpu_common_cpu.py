@@ -1,0 +1,214 @@
+"""The shared assertions of tests/gpu_common.py without a device: on stub envs (CPU tensors behind the attributes the helpers
+read) they pass on equal state and fail on every kind of difference the private copies they replaced would have caught."""
+import os
+import types
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from tests import gpu_common as gc
+from tests.common import OBS_TOL, PKT_COUNTS, REW_TOL, oracle_envs, poisson_traffic_rows
+from tests.synth import se_tile
+
+
+class _StubEnv:
+    device = torch.device("cpu")
+
+    def __init__(self, views, outputs, raw=None, actions=None, metrics=None):
+        self._views, self._raw, self._actions, self._metrics = views, raw, actions, metrics
+        for k, x in outputs.items():
+            setattr(self, k, x)
+
+    def views(self):
+        return self._views
+
+    def raw_observation(self):
+        return self._raw
+
+    def policy_actions(self):
+        return self._actions
+
+    def episode_metrics(self):
+        return self._metrics
+
+
+# ---- assert_same_state ---------------------------------------------------------------------------------------------------------------
+B, U = 3, 4
+TABLES = types.SimpleNamespace(ue_slice=np.array([[0, 0, 1, 1], [0, 1, 1, -1]]))      # UE 3 is outside every slice in scenario 1 only
+SCENARIO = [0, 1, 1]
+OUT_OF_SLICE = [(1, 3), (2, 3)]
+LOOSE_SETS = {"se_mean": gc.LOOSE_SE_MEAN, "win_sent": gc.LOOSE_WIN_SENT, "win_sent_and_se": gc.LOOSE_WIN_SENT_AND_SE,
+              "windows_and_se": gc.LOOSE_WINDOWS_AND_SE}
+PER_UE = ("queue_pkts", "win_sent", "win_dropped", "se_mean")
+
+
+def _state():
+    g = torch.Generator().manual_seed(1)
+    views = {k: torch.randint(1, 9, (B, U), generator=g).to(torch.float64 if k == "se_mean" else torch.int32) for k in PER_UE}
+    views["step_number"] = torch.tensor([5, 5, 2], dtype=torch.int32)
+    views["episodes"] = torch.tensor([[s, 7] for s in SCENARIO], dtype=torch.int32)
+    outputs = dict(obs_inter=torch.rand((B, 20), generator=g), obs_intra=torch.rand((B, 2, 17), generator=g),
+                   reward=torch.rand((B, 3), generator=g, dtype=torch.float64), done=torch.zeros(B, dtype=torch.uint8),
+                   head_obs=torch.rand((B, 20), generator=g))
+    return _StubEnv(views, outputs, actions=dict(scores=torch.rand((B, 2), generator=g, dtype=torch.float64),
+                                                 intra=torch.ones((B, 2), dtype=torch.uint8)),
+                    metrics=dict(running=torch.rand((B, 8), generator=g, dtype=torch.float64)))
+
+
+def _bump(x, at):
+    x[at] = x[at] + 1
+
+
+def _differs(loose, change, **kw):
+    a, b = _state(), _state()
+    change(b)
+    with pytest.raises(AssertionError):
+        gc.assert_same_state(a, b, TABLES, "stub", loose=loose, **kw)
+
+
+def test_in_slice_mask_follows_the_scenario_on_the_device():
+    assert gc.in_slice_mask(TABLES, _state()).tolist() == [[True] * 4, [True, True, True, False], [True, True, True, False]]
+
+
+@pytest.mark.parametrize("name", list(LOOSE_SETS))
+def test_assert_same_state_is_exact_except_for_loose_keys_outside_every_slice(name):
+    loose = LOOSE_SETS[name]
+    everything = dict(outputs=gc.OUTPUTS + ("head_obs",), actions=("scores", "intra"), metrics={"episode_metrics": ("running",)})
+    gc.assert_same_state(_state(), _state(), TABLES, "equal", loose=loose, **everything)
+    for k in PER_UE:
+        for at in [(b, u) for b in range(B) for u in range(U)]:
+            change = lambda e, k=k, at=at: _bump(e.views()[k], at)
+            if k in loose and at in OUT_OF_SLICE:      # stale there by design: the one difference that is let through
+                a, b = _state(), _state()
+                change(b)
+                gc.assert_same_state(a, b, TABLES, (k, at), loose=loose)
+            else:
+                _differs(loose, change)
+    for b in range(B):
+        _differs(loose, lambda e, b=b: _bump(e.views()["step_number"], b))
+    _differs(loose, lambda e: _bump(e.views()["episodes"], (0, 1)))
+    # a key list: the listed keys are compared, loose or strict as above, and the others are not
+    keys = ("queue_pkts", "win_sent")
+    _differs(loose, lambda e: _bump(e.views()["queue_pkts"], (1, 3)), keys=keys)
+    _differs(loose, lambda e: _bump(e.views()["win_sent"], (2, 0)), keys=keys)
+    a, b = _state(), _state()
+    _bump(b.views()["win_dropped"], (0, 0))
+    gc.assert_same_state(a, b, TABLES, "unlisted", loose=loose, keys=keys)
+    # whatever else the caller asks for
+    for k in gc.OUTPUTS:
+        _differs(loose, lambda e, k=k: _bump(getattr(e, k), 1))
+    _differs(loose, lambda e: _bump(e.head_obs, (2, 0)), outputs=gc.OUTPUTS + ("head_obs",))
+    for k in ("scores", "intra"):
+        _differs(loose, lambda e, k=k: _bump(e.policy_actions()[k], (0, 1)), actions=("scores", "intra"))
+    _differs(loose, lambda e: _bump(e.episode_metrics()["running"], (1, 7)), metrics={"episode_metrics": ("running",)})
+
+
+def test_comparable_views_blanks_the_mean_se_outside_every_slice_only():
+    wl = types.SimpleNamespace(env=_state(), tables=TABLES)
+    v, raw = gc.comparable_views(wl), wl.env.views()
+    for k in raw:
+        want = raw[k].clone()
+        if k == "se_mean":
+            for at in OUT_OF_SLICE:
+                want[at] = 0
+        assert torch.equal(v[k], want), k
+
+
+# ---- assert_matches_oracle -----------------------------------------------------------------------------------------------------------
+def _oracle_pair():
+    """The smallest shape of tests/test_gpu_parity.py: two oracle envs stepped twice under the caller's scores."""
+    from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
+    S, U_, R, G, Us = 3, 7, 5, 1, 4
+    tabs = generate_scaled_scenarios(3, seed=5, n_slices=S, n_ues=U_, max_ues_slice=Us, min_slices=1, min_ues=1)
+    rng = np.random.default_rng(7)
+    scen = rng.integers(0, tabs.n_scenarios, 2)
+    oenvs = oracle_envs(tabs, scen, (S, U_, R, G, Us), 4)
+    trf = [poisson_traffic_rows(tabs, int(sc), rng, 2) for sc in scen]
+    counts = None
+    for b, o in enumerate(oenvs):
+        o.reset(se_tile(90, 0, U_, R))
+    for t in range(2):
+        sc, ic = rng.uniform(-1, 1, (2, S)), rng.integers(0, 3, (2, S)).astype(np.uint8)
+        counts = [o.action_format(sc[b], ic[b], want_dense=False)[1] for b, o in enumerate(oenvs)]
+        for b, o in enumerate(oenvs):
+            o.step(sc[b], ic[b], se_tile(90, t, U_, R), trf[b][t])
+    return oenvs, counts
+
+
+def _stub_of(oenvs, counts):
+    raws, obs = [o.raw() for o in oenvs], [o.obs() for o in oenvs]
+    stack = lambda rows, dtype: torch.as_tensor(np.stack([np.asarray(r) for r in rows])).to(dtype)
+    views = {k: stack([r[k] for r in raws], torch.int32) for k in PKT_COUNTS}
+    views["rb_count"] = stack(counts, torch.int32)
+    raw = {k: stack([r[k] for r in raws], torch.float64) for k in ("buffer_occupancies", "buffer_latencies")}
+    outputs = dict(obs_inter=stack([o["obs_inter"] for o in obs], torch.float32), obs_intra=stack([o["obs_intra"] for o in obs], torch.float32),
+                   reward=stack([o["reward"] for o in obs], torch.float64))
+    return _StubEnv(views, outputs, raw=raw)
+
+
+def test_assert_matches_oracle_passes_on_the_oracles_own_outputs_and_fails_on_each_perturbation():
+    oenvs, counts = _oracle_pair()
+    assert sum(int(o.raw()["pkt_incoming"].sum()) for o in oenvs) > 0
+
+    def check(change=None, as_dict=False, **kw):
+        env = _stub_of(oenvs, counts)
+        if change is not None:
+            change(env)
+        obs = dict(obs_inter=env.obs_inter, obs_intra=env.obs_intra)
+        gc.assert_matches_oracle(env, obs, env.reward, dict(enumerate(oenvs)) if as_dict else oenvs, "stub", **kw)
+        gc.assert_matches_oracle(env, None, None, oenvs, "stub, the env's own buffers", **kw)
+
+    check()
+    check(as_dict=True, rb_count=dict(enumerate(counts)))
+    check(rb_count=counts, buffers=False)
+
+    def ulp(x, at):
+        x[at] = float(np.nextafter(float(x[at]), np.inf))
+
+    def shift(x, by):
+        flat = x.view(-1)
+        k = int(flat.abs().argmin())
+        flat[k] = flat[k] + by
+
+    perturbations = [lambda e, k=k: _bump(e.views()[k], (1, 2)) for k in PKT_COUNTS]
+    perturbations += [lambda e: ulp(e.raw_observation()["buffer_occupancies"], (0, 3)),
+                      lambda e: ulp(e.raw_observation()["buffer_latencies"], (1, 0)),
+                      lambda e: shift(e.obs_inter, 2 * OBS_TOL), lambda e: shift(e.obs_intra, -2 * OBS_TOL),
+                      lambda e: shift(e.reward, 2 * REW_TOL)]
+    for change in perturbations:
+        with pytest.raises(AssertionError):
+            check(change)
+    with pytest.raises(AssertionError):
+        check(lambda e: _bump(e.views()["rb_count"], (0, 0)), rb_count=counts)
+    check(lambda e: ulp(e.raw_observation()["buffer_occupancies"], (0, 3)), buffers=False)      # switched off by the caller: not compared
+
+
+# ---- select_build --------------------------------------------------------------------------------------------------------------------
+KNOBS = ("RANENV_SMALL_BATCH", "RANENV_PACK", "RANENV_MIX", "RANENV_SE_MODE")
+# what the build fixture of test_gpu_parity.py, _select_build of test_gpu_intent_branches.py and test_gpu_fuzz.py set for the name
+BUILD_KNOBS = {
+    "lean": ("0", "0", "0", None),
+    "small": ("1", "0", "0", None),
+    "gather": ("1", "0", "0", "gather"),
+    "packed": ("0", "1", "0", None),
+    "packed-gather": ("0", "1", "0", "gather"),
+    "mixed": ("0", "0", "2", None),
+    "mixed-gather": ("0", "0", "2", "gather"),
+    "per-element": ("1", "0", "0", None),
+    "per-element-gather": ("1", "0", "0", "gather"),
+}
+
+
+@pytest.mark.parametrize("build", list(BUILD_KNOBS))
+def test_select_build_sets_the_knobs_each_module_set(build, monkeypatch):
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    gc.select_build(monkeypatch, build)
+    assert tuple(os.environ.get(k) for k in KNOBS) == BUILD_KNOBS[build]
+
+
+def test_select_build_refuses_an_unknown_name(monkeypatch):
+    with pytest.raises(AssertionError):
+        gc.select_build(monkeypatch, "packed_gather")

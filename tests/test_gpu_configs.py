@@ -6,16 +6,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.common import comparable_views
+from tests.common import OBS_TOL, PKT_COUNTS, REW_TOL
+from tests.gpu_common import LOOSE_SE_MEAN, assert_matches_oracle, assert_same_state, comparable_views, need_gpu
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL, REW_TOL = 1e-5, 1e-9
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 def _follow_oracle(wl, sample, steps):
@@ -37,22 +31,16 @@ def _follow_oracle(wl, sample, steps):
     env.reset()
     for t in range(steps):
         obs, rew, done = env.step()
-        g = {k: x.cpu().numpy() for k, x in env.views().items()}
-        oi, oa, rw = obs["obs_inter"].cpu().numpy(), obs["obs_intra"].cpu().numpy(), rew.cpu().numpy()
+        scores = env.views()["policy_scores"].cpu().numpy()
+        counts = {}
         for b, o in oenvs.items():
             tile = int(eps["se_base"][b] + (eps["se_offset"][b] + t) % L)
             row = int(eps["trf_base"][b] + (eps["trf_offset"][b] + t) % L)
             sc = o.policy_mapf() if wl.policy == 2 else o.policy_marr()
-            np.testing.assert_allclose(g["policy_scores"][b], sc, rtol=0, atol=1e-12)
-            _, count, _ = o.action_format(sc, intra, want_dense=False)
-            assert np.array_equal(g["rb_count"][b], count), (t, b)
+            np.testing.assert_allclose(scores[b], sc, rtol=0, atol=1e-12)
+            counts[b] = o.action_format(sc, intra, want_dense=False)[1]
             o.step(sc, intra, se_host[tile], trf_host[row])
-            raw, oo = o.raw(), o.obs()
-            for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
-                assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (t, b, name)
-            np.testing.assert_allclose(oi[b], oo["obs_inter"], rtol=0, atol=OBS_TOL)
-            np.testing.assert_allclose(oa[b], oo["obs_intra"], rtol=0, atol=OBS_TOL)
-            np.testing.assert_allclose(rw[b], oo["reward"], rtol=0, atol=REW_TOL)
+        assert_matches_oracle(env, obs, rew, oenvs, t, buffers=False, rb_count=counts)
     return oenvs
 
 
@@ -81,7 +69,7 @@ def _conservation(wl, steps):
 def test_config4_seq_sweep_vs_oracle():
     """mult_slice_seq: 10 scenario groups of consecutive episodes; every env of a group replays the group's
     association but its own channel trace (associations/mult_slice_seq.py:38-46, channels/quadriga_seq.py:28-39)."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_seq_workload
     wl = make_mult_slice_seq_workload(40, torch.device("cuda", 0), channels_per_scenario=4, n_traces=40, trace_len=12,
                                       max_steps=30)
@@ -97,7 +85,7 @@ def test_config4_seq_sweep_vs_oracle():
 
 
 def test_config4_full_batch_properties():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, label = make_bench_workload(4, torch.device("cuda", 0), n_traces=40, trace_len=30)
     assert wl.env.B == 8192 and "mult_slice_seq" in label
@@ -108,7 +96,7 @@ def test_config4_full_batch_properties():
 
 
 def test_config1_marr_rr_vs_oracle_and_properties():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, label = make_bench_workload(1, torch.device("cuda", 0), n_traces=20, trace_len=16)
     assert wl.env.B == 1024 and "round-robin" in label
@@ -122,9 +110,9 @@ def test_rollout_and_partitions_equal_repeated_steps(policy, intra, parts):
     """ranenv_rollout(n) over batch partitions = n x ranenv_step on one stream: every state array, the raw outputs and
     the last TTI's observation / reward bit for bit (the partitions are ranges of independent envs on their own HIP
     streams; joined steps in between must keep the order with the caller's stream)."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
-    outs = []
+    envs = {}
     for mode in ("steps", "rollout"):
         wl = make_mult_slice_workload(100, torch.device("cuda", 0), policy=policy, intra=intra, n_scenarios=8, n_traces=10, trace_len=9,
                                       max_steps=60)
@@ -135,26 +123,22 @@ def test_rollout_and_partitions_equal_repeated_steps(policy, intra, parts):
         if mode == "steps":
             for t in range(13 + 1 + 25):
                 env.step()
-            mid = None
         else:
             env.rollout(13)
             env.step()                                        # a joined step between two rollouts
             mid = env.views()["step_number"].clone()           # read on the caller's stream: ordered behind the partitions
             env.rollout(25)
-        v = comparable_views(wl)
-        outs.append((v, env.obs_inter.clone(), env.obs_intra.clone(), env.reward.clone(), env.done.clone(), mid))
-        env.close()
-    (va, oia, oaa, ra, da, _), (vb, oib, oab, rb, db, mid) = outs
+        envs[mode] = env
     assert int(mid.min()) == 14 and int(mid.max()) == 14
-    for k in va:
-        assert torch.equal(va[k], vb[k]), k
-    assert torch.equal(oia, oib) and torch.equal(oaa, oab) and torch.equal(ra, rb) and torch.equal(da, db)
+    assert_same_state(envs["steps"], envs["rollout"], wl.tables, (policy, intra, parts), loose=LOOSE_SE_MEAN)
+    for env in envs.values():
+        env.close()
 
 
 def test_partitioned_steps_with_external_inputs_vs_oracle():
     """Partitions under the ordinary step(): inputs produced on the caller's stream right before the call, outputs
     consumed right after it; masked reset and the head kernel go through the same partitioned launch."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     from oracle import pyoracle
     B, steps = 24, 10
@@ -197,7 +181,7 @@ def test_partitioned_steps_with_external_inputs_vs_oracle():
 def test_full_batch_episode_rollout_over_partitions_equals_single_stream_steps():
     """BASELINE configs[2] at full size for a whole 1000-TTI episode: four ranenv_rollout(250) calls over 3 batch
     partitions (the schedule bench.py times) leave exactly the state 1000 single-stream step() calls leave."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
@@ -253,21 +237,6 @@ def _headline_sample(wl, per_class=6):
     return sorted(set(sample)), members
 
 
-def _compare_with_oracle(env, oenvs, max_pkts, where):
-    """views (raw outputs, queue lengths), both observations and the rewards of the mirrored envs; `max_pkts[b]`: [U]."""
-    g = {k: x.cpu().numpy() for k, x in env.views().items()}
-    oi, oa, rw = env.obs_inter.cpu().numpy(), env.obs_intra.cpu().numpy(), env.reward.cpu().numpy()
-    for b, o in oenvs.items():
-        raw, oo = o.raw(), o.obs()
-        for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
-            assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (where, b, name)
-        mp = max_pkts[b].astype(np.float64)
-        assert np.array_equal(g["queue_pkts"][b].astype(np.float64), np.rint(raw["buffer_occupancies"] * mp)), (where, b, "queue_pkts")
-        np.testing.assert_allclose(oi[b], oo["obs_inter"], rtol=0, atol=OBS_TOL, err_msg=str((where, b)))
-        np.testing.assert_allclose(oa[b].reshape(-1), np.asarray(oo["obs_intra"]).reshape(-1), rtol=0, atol=OBS_TOL, err_msg=str((where, b)))
-        np.testing.assert_allclose(rw[b], oo["reward"], rtol=0, atol=REW_TOL, err_msg=str((where, b)))
-
-
 def _partition_bounds(B, parts, unit=1):
     """ranenv_set_partitions' cut of the batch (an even batch into even ranges where possible: unit 2)."""
     base, rem = divmod(B // unit, parts)
@@ -312,13 +281,17 @@ def _mirror_rollouts_with_the_oracle(wl, sample, calls, se_mode, where, after_ca
                 o.step(score(o), intra, se_host[tpos[int(eps["se_base"][b] + (eps["se_offset"][b] + t) % L)]], bits)
             t += 1
         torch.cuda.synchronize()
-        _compare_with_oracle(env, oenvs, max_pkts, (where, se_mode, "after TTI", t))
+        tag = (where, se_mode, "after TTI", t)
+        assert_matches_oracle(env, None, None, oenvs, tag, buffers=False)
+        queue = env.views()["queue_pkts"].cpu().numpy().astype(np.float64)      # queue lengths, from the oracle's occupancies
+        for b, o in oenvs.items():
+            assert np.array_equal(queue[b], np.rint(o.raw()["buffer_occupancies"] * max_pkts[b].astype(np.float64))), (tag, b, "queue_pkts")
     assert int(env.views()["step_number"].min()) == t == sum(calls)
 
 
 @pytest.mark.parametrize("se_mode", ["stream", "gather"])
 def test_config2_headline_schedule_vs_oracle(se_mode):
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, label = make_bench_workload(2, torch.device("cuda", 0), n_traces=64, trace_len=80)
     env = wl.env
@@ -344,7 +317,7 @@ def test_config2_headline_schedule_with_the_device_traffic_generator_vs_oracle()
     """`bench.py --traffic philox`: the headline schedule with the offered traffic drawn on the device (Poisson by table inversion of
     Philox-4x32-10 keyed (seed; env, episode, TTI, UE), traffics/mult_slice.py:24-32 in distribution); the oracle is fed the numpy
     restatement's draws for the mirrored envs."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, _ = make_bench_workload(2, torch.device("cuda", 0), n_traces=64, trace_len=80, traffic="philox")
@@ -376,7 +349,7 @@ def test_config1_bench_schedule_vs_oracle(se_mode):
     """BASELINE configs[1] (B 1024, MARR + round-robin) as bench.py runs it: a batch at <= 2 waves per SIMD, so ranenv_rollout is ONE
     persistent launch of one chunk -- streaming: ranenv_persist_kernel_tiny, the whole SE row in flight and the next TTI's tile
     requested a TTI ahead.  The test fails if the auto rule stops selecting that launch."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, label = make_bench_workload(1, torch.device("cuda", 0), n_traces=64, trace_len=80)
     env = wl.env
@@ -407,7 +380,7 @@ def test_config4_bench_schedule_vs_oracle(se_mode):
     """BASELINE configs[4] (mult_slice_seq sweep, B 8192, mixed active-slice masks) as bench.py runs it: three partitions, launches of up
     to 10 TTIs (streaming) / persistent launches per class (gather).  Mirrored: an env of each of the 10 scenario groups from every
     partition, and the partitions' first and last envs."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, label = make_bench_workload(4, torch.device("cuda", 0), n_traces=64, trace_len=80)
     env = wl.env
@@ -444,7 +417,7 @@ def _native_sample(B, parts):
 def test_native_size_bench_schedule_vs_oracle(se_mode):
     """The reference's own size (env_config/mult_slice.yml:2-14, agents/ib_sched.py:50,56: what every reference agent trains at) as
     bench.py --config native runs it: B 16 384, three partitions, TWO envs per wave (ranenv_core_kernel_packed), MAPF + PF."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, label = make_bench_workload(5, torch.device("cuda", 0), n_traces=64, trace_len=80)
     env = wl.env
@@ -464,7 +437,7 @@ def test_bench_schedule_across_an_episode_end_vs_oracle(config):
     """The headline schedule (configs[2]) and the native-size one (two envs per wave) with device auto-reset: every env's episode (37
     TTIs here) ends inside the rollouts, the advance + RESET launches follow that TTI on the partition's own stream, the fused
     launches end there."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     wl, _ = make_bench_workload(config, torch.device("cuda", 0), n_traces=64, trace_len=80)
@@ -531,6 +504,6 @@ def test_bench_schedule_across_an_episode_end_vs_oracle(config):
             mp = np.asarray(tabs.ue_max_pkts)[scen_of(cur[b])].astype(np.float64)
             assert np.array_equal(g["queue_pkts"][b].astype(np.float64), np.rint(raw["buffer_occupancies"] * mp)), (total, b)
             if tstep[b] > 0:
-                for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
+                for name in PKT_COUNTS:
                     assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (total, b, name)
     env.close()

@@ -15,40 +15,17 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.common import load_golden, tables_from
+from tests.gpu_common import env_from_eval_fixture, need_gpu
 from tests.synth import se_tile
 
 pytestmark = pytest.mark.gpu
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _env_from_fixture(flags=0, B=2):
-    from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
-    fx = load_golden("eval_metrics")
-    S, U, R, G, Us, seed, steps, n_ep = (int(x) for x in fx["cfg"])
-    tabs = tables_from(fx)
-    env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us, n_scenarios=tabs.n_scenarios,
-                        max_steps=steps, flags=flags)
-    env.load_scenarios(tabs)
-    se = np.stack([np.ascontiguousarray(se_tile(seed + ep, t, U, R).T) for ep in range(n_ep) for t in range(steps)])
-    env.bind_se_pool(torch.as_tensor(se, device=env.device))
-    env.bind_traffic_pool(torch.as_tensor(fx["traffic"].reshape(n_ep * steps, U).astype(np.int32), device=env.device))
-    ep = np.arange(n_ep)
-    env.set_episode_table(scenario=fx["scen_ids"], se_base=ep * steps, se_len=steps, trf_base=ep * steps, trf_len=steps)
-    env.set_policy(2, 1)                                   # MAPF + PF on the device
-    env.enable_autoreset(0, n_ep, episode_numbers=np.zeros(B, dtype=np.int32))
-    return fx, env, (S, U, R, steps, n_ep)
-
-
 @pytest.mark.parametrize("window", ["live", "restarted"])
 def test_per_tti_device_metrics_equal_the_reference_evaluation_code(window):
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import F_CLEAR_HISTORY_ON_RESET
-    fx, env, (S, U, R, steps, n_ep) = _env_from_fixture(F_CLEAR_HISTORY_ON_RESET if window == "restarted" else 0)
+    fx, _, env, (S, U, R, steps, n_ep) = env_from_eval_fixture(F_CLEAR_HISTORY_ON_RESET if window == "restarted" else 0)
     want = fx["live_deque" if window == "live" else "restarted_with_reset"]          # [ep, t, (viol, prio viol, dist, prio dist)]
     env.enable_metrics(n_ep)
     env.reset()
@@ -81,8 +58,8 @@ def test_per_tti_device_metrics_equal_the_reference_evaluation_code(window):
 
 def test_evaluate_sums_equal_the_reference_evaluation_code():
     """BatchedRanEnv.evaluate (one rollout through 3 episodes per env, over 2 partitions) -> per-episode sums."""
-    _need_gpu()
-    fx, env, (S, U, R, steps, n_ep) = _env_from_fixture()
+    need_gpu()
+    fx, _, env, (S, U, R, steps, n_ep) = env_from_eval_fixture()
     env.enable_metrics(n_ep)
     env.set_partitions(2)
     res = env.evaluate(n_ep)
@@ -104,10 +81,9 @@ def test_recorder_follows_the_device_through_three_episodes(tmp_path):
     """BatchedRanEnv.record + device auto-reset: one history file per episode, named by the episode number the device
     moved to, each holding that episode's own scenario / channel trace / steps; the arrays are the fixture's (the inputs
     the reference's evaluation code was run on)."""
-    _need_gpu()
-    fx, env, (S, U, R, steps, n_ep) = _env_from_fixture()
+    need_gpu()
+    fx, tabs, env, (S, U, R, steps, n_ep) = env_from_eval_fixture()
     seed = int(fx["cfg"][5])
-    tabs = tables_from(fx)
     rec = env.record([1], root_path=str(tmp_path), simu_name="mult_slice", agent_name="mapf", episode_numbers=[0])
     env.reset()
     for _ in range(n_ep * steps):
@@ -135,7 +111,7 @@ def test_recorder_follows_the_device_through_three_episodes(tmp_path):
 def test_recorder_with_masked_resets_and_per_env_episode_lengths(tmp_path):
     """Every recorded env keeps its own step counter: a masked reset restarts only the masked env's trace, envs with
     different max_steps write files of their own length."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     wl = make_mult_slice_workload(4, torch.device("cuda", 0), policy=2, intra=1, n_scenarios=6, n_traces=12, trace_len=10,
                                   n_slices=5, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=10, max_steps=9)

@@ -5,14 +5,11 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests.common import rb_major
+from tests.gpu_common import need_gpu
 from tests.synth import se_tile
 
 pytestmark = pytest.mark.gpu
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 class _RawAgent:
@@ -46,7 +43,7 @@ class _RawAgent:
 @pytest.mark.parametrize("config", ["plumbing", "mult_slice"])
 def test_facade_matches_oracle(config, per_element):
     """(per_element: the facade created with RANENV_F_SCALE_PER_ELEMENT against the oracle in that convention)"""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib, plugins
     from intent_radio_sched_multi_slice_amd.comm_env import DEFAULT_CONFIGS, MARLCommEnv
     from intent_radio_sched_multi_slice_amd.scenario import ScenarioTables
@@ -112,7 +109,7 @@ def test_facade_matches_oracle(config, per_element):
 def test_full_batch_properties():
     """B = 4096 (BASELINE.json configs[2]): RB conservation, queue conservation, window sums,
     bounds, and run-to-run determinism."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
@@ -164,8 +161,7 @@ def test_full_episode_vs_oracle():
     """A whole 1000-TTI episode at the headline sizes (buffer_latency up to 400 TTIs, so the per-UE age
     list wraps and long-lived packets expire), MAPF + PF on the device, against the oracle: integer state
     every 50 TTIs, observation and reward at the end, done exactly at max_steps."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
     from oracle import pyoracle
@@ -181,7 +177,7 @@ def test_full_episode_vs_oracle():
     env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us,
                         n_scenarios=tabs.n_scenarios, max_steps=steps)
     env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(np.ascontiguousarray(np.swapaxes(se_pool, -1, -2)), device=env.device))
+    env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
     env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
     env.set_episodes(scenario=scen, se_base=np.arange(B) * L, se_len=L, trf_base=np.arange(B) * L, trf_len=L)
     env.set_policy(2, 1)
@@ -221,7 +217,7 @@ def test_full_batch_long_run():
     """B = 4096 for a whole 1000-TTI episode plus a reset: packets are conserved over the run, the age list
     (401 entries per UE) wraps, long-queued packets expire, everything stays finite and in bounds, and the
     episode ends exactly at max_steps."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)

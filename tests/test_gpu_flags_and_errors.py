@@ -6,16 +6,12 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-from tests.common import poisson_traffic_rows
+
+from tests.common import OBS_TOL, REW_TOL, oracle_envs, poisson_traffic_rows, rb_major
+from tests.gpu_common import assert_matches_oracle, need_gpu
 from tests.synth import se_tile
 
 pytestmark = pytest.mark.gpu
-OBS_TOL, REW_TOL = 1e-5, 1e-9
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
 
 
 def _setup(flags=0, steps=12, B=4, seed=3, hist_depth=10):
@@ -30,26 +26,16 @@ def _setup(flags=0, steps=12, B=4, seed=3, hist_depth=10):
     env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us,
                         n_scenarios=tabs.n_scenarios, max_steps=steps, flags=flags, hist_depth=hist_depth)
     env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(np.ascontiguousarray(np.swapaxes(se_pool, -1, -2)), device=env.device))
+    env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
     env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
     env.set_episodes(scenario=scen, se_base=np.arange(B) * steps, se_len=steps, trf_base=np.arange(B) * steps, trf_len=steps)
     return env, tabs, scen, se_pool, trf, (S, U, R, G, Us)
 
 
-def _oracles(tabs, scen, dims, steps, hist_depth=10):
-    from oracle import pyoracle
-    S, U, R, G, Us = dims
-    cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=steps, hist_depth=hist_depth)
-    out = []
-    for b in range(len(scen)):
-        o = pyoracle.OracleEnv(cfg); o.set_scenario(tabs, int(scen[b])); out.append(o)
-    return out
-
-
 def test_clear_history_on_reset_matches_a_fresh_env():
     """RANENV_F_CLEAR_HISTORY_ON_RESET: after reset the 10-TTI window is empty, i.e. the env behaves like a
     newly created one (the reference's deque is never cleared, agents/ib_sched.py:51; this flag is the opt-in)."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     steps = 12
     env, tabs, scen, se_pool, trf, dims = _setup(flags=_lib.F_CLEAR_HISTORY_ON_RESET, steps=steps)
@@ -61,7 +47,7 @@ def test_clear_history_on_reset_matches_a_fresh_env():
     env.reset()
     v = env.views()
     assert int(v["hist_len"].max()) == 1 and int(v["win_sent"].abs().max()) == 0 and int(v["win_dropped"].abs().max()) == 0
-    oenvs = _oracles(tabs, scen, dims, steps)          # fresh oracles: empty deque
+    oenvs = oracle_envs(tabs, scen, dims, steps)        # fresh oracles: empty deque
     for b, o in enumerate(oenvs):
         o.reset(se_pool[b * steps])
     for t in range(6):
@@ -76,7 +62,7 @@ def test_clear_history_on_reset_matches_a_fresh_env():
 
 
 def test_no_raw_output_flag_only_skips_the_two_arrays():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     a, *_ = _setup(flags=0)
     b, *_ = _setup(flags=_lib.F_NO_RAW_OUTPUT)
@@ -98,7 +84,7 @@ def test_no_raw_output_flag_only_skips_the_two_arrays():
 def test_sync_check_flag_changes_nothing_but_the_waiting():
     """RANENV_F_SYNC_CHECK: every launch waits for its kernels (an asynchronous fault would be reported by the call that
     caused it); results are those of the ordinary, enqueue-only mode."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     a, *_ = _setup(flags=0)
     b, *_ = _setup(flags=_lib.F_SYNC_CHECK)
@@ -119,7 +105,7 @@ def test_shorter_trace_mid_episode_cannot_read_past_the_pool():
     """A trace position persisted under a longer trace is reduced when set_episodes installs a shorter one mid-episode
     (no reset in between): the next step reads tile 0 of the new trace -- inside the bound pool -- not position 9 of a
     4-tile trace."""
-    _need_gpu()
+    need_gpu()
     steps, B = 12, 4
     env, tabs, scen, se_pool, trf, dims = _setup(steps=steps, B=B)
     S, U, R, G, Us = dims
@@ -145,7 +131,7 @@ def test_shorter_trace_mid_episode_cannot_read_past_the_pool():
 
 
 def test_done_flag_and_step_counter():
-    _need_gpu()
+    need_gpu()
     steps = 5
     env, *_ = _setup(steps=steps)
     env.set_policy(1, 0)
@@ -160,7 +146,7 @@ def test_done_flag_and_step_counter():
 
 
 def test_errors_are_reported_not_swallowed():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv, RanEnvError
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
     with pytest.raises(RanEnvError, match="unsupported sizes"):
@@ -233,7 +219,7 @@ def test_se_from_power_matches_the_reference_formula():
     """Channel ingest kernel vs the expression of channels/quadriga.py:56-69 in numpy float64, stored float32.
     log2 may differ from numpy's in the last float64 bit, so the float32 results are allowed to differ by one
     float32 ulp in rare rounding ties; everything else must be identical."""
-    _need_gpu()
+    need_gpu()
     from oracle.pyoracle import quadriga_se_from_power          # the checker lives on the oracle side of the wall
     from intent_radio_sched_multi_slice_amd.workloads import quadriga_pool_from_power
     rng = np.random.default_rng(5)
@@ -255,7 +241,7 @@ def test_alternative_heads_vs_oracle(hist_depth):
     to the reference's classes by tests/golden/heads_*.npz), in closed loop: external scores, round-robin
     inside the slices as their action_format does, a masked reset in the middle.  hist_depth 5: an odd deque
     length, where the oldest TTI of the heads' doubled window counts once."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.scenario import SLICE_TEMPLATES, SLICE_USECASE
     steps = 16
     env, tabs, scen, se_pool, trf, dims = _setup(steps=steps, B=6, seed=9, hist_depth=hist_depth)
@@ -271,7 +257,7 @@ def test_alternative_heads_vs_oracle(hist_depth):
                 uc[i, s] = SLICE_USECASE[name]
     env.enable_heads(uc)
     env.set_policy(0, 0)                       # scores from the caller, round-robin intra-slice
-    oenvs = _oracles(tabs, scen, dims, steps, hist_depth)
+    oenvs = oracle_envs(tabs, scen, dims, steps, hist_depth)
     env.reset()
     for b, o in enumerate(oenvs):
         o.reset(se_pool[b * steps])
@@ -310,7 +296,7 @@ def test_alternative_heads_vs_oracle(hist_depth):
 def test_trainer_adapters():
     """HeadVecEnv follows the VecEnv protocol (shapes, dtypes, auto-reset with terminal_observation) and hands
     out the head kernel's numbers; the MARL dicts are the batched tensors of one env under the reference's keys."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.adapters import HeadVecEnv, marl_obs_dict, marl_reward_dict
     steps = 5
     env, tabs, scen, se_pool, trf, dims = _setup(steps=steps, B=4, seed=13)
@@ -344,10 +330,9 @@ def test_degenerate_scenarios_vs_oracle():
     """No active slice at all (IBSched.action_format's `if np.sum(basestation_slice_assoc) != 0` guard,
     agents/ib_sched.py:240-246: the allocation stays all-zero), an active slice without UEs, a single UE owning every
     RB, and all of it next to an ordinary scenario in one batch: against the oracle, all four policies."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import ScenarioTables, generate_scaled_scenarios, slice_template_dict
-    from oracle import pyoracle
     S, U, R, G, Us, steps = 5, 25, 135, 5, 5, 8
     tabs = ScenarioTables.empty(4, S, U, Us)                                    # row 0: nothing active
     bsa = np.zeros((1, S)); sua = np.zeros((S, U)); bsa[0, 2] = 1               # row 1: slice 2 active, but no UE in it
@@ -366,14 +351,13 @@ def test_degenerate_scenarios_vs_oracle():
     for policy, intra in ((1, 0), (2, 1), (2, 2), (0, 255)):
         env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us, n_scenarios=4, max_steps=steps)
         env.load_scenarios(tabs)
-        env.bind_se_pool(torch.as_tensor(np.ascontiguousarray(np.swapaxes(se_pool, -1, -2)), device=env.device))
+        env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
         env.bind_traffic_pool(torch.as_tensor(trf.reshape(B * steps, U).astype(np.int32), device=env.device))
         env.set_episodes(scenario=np.arange(B), se_base=0, se_len=steps, trf_base=np.arange(B) * steps, trf_len=steps)
         env.set_policy(policy, intra)
-        cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=steps)
-        oenvs = []
-        for b in range(B):
-            o = pyoracle.OracleEnv(cfg); o.set_scenario(tabs, b); o.reset(se_pool[0]); oenvs.append(o)
+        oenvs = oracle_envs(tabs, range(B), (S, U, R, G, Us), steps)
+        for o in oenvs:
+            o.reset(se_pool[0])
         env.reset()
         for t in range(steps):
             if policy == 0:
@@ -381,22 +365,17 @@ def test_degenerate_scenarios_vs_oracle():
                 obs, rew, done = env.step(sc, ic)
             else:
                 obs, rew, done = env.step()
-            g = {k: x.cpu().numpy() for k, x in env.views().items()}
+            counts = []
             for b, o in enumerate(oenvs):
                 if policy == 0:
                     scb, icb = sc[b], ic[b].astype(np.int32)
                 else:
                     scb = o.policy_mapf() if policy == 2 else o.policy_marr()
                     icb = np.full(S, intra, dtype=np.int32)
-                _, count, _ = o.action_format(scb, icb, want_dense=False)
-                assert np.array_equal(g["rb_count"][b], count), (policy, t, b)
+                counts.append(o.action_format(scb, icb, want_dense=False)[1])
                 o.step(scb, icb, se_pool[t], trf[b, t])
-                raw, oo = o.raw(), o.obs()
-                for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
-                    assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (policy, t, b, name)
-                np.testing.assert_allclose(obs["obs_inter"][b].cpu().numpy(), oo["obs_inter"], rtol=0, atol=1e-5)
-                np.testing.assert_allclose(obs["obs_intra"][b].cpu().numpy(), oo["obs_intra"], rtol=0, atol=1e-5)
-                np.testing.assert_allclose(rew[b].cpu().numpy(), oo["reward"], rtol=0, atol=1e-9)
+            assert_matches_oracle(env, obs, rew, oenvs, (policy, t), buffers=False, rb_count=counts)
+            g = {"rb_count": env.views()["rb_count"].cpu().numpy()}
             assert int(g["rb_count"][0].sum()) == 0 and int(g["rb_count"][1].sum()) == 0      # nobody to give RBs to
             assert int(g["rb_count"][2, 7]) == R and int(g["rb_count"][2].sum()) == R          # one UE owns the carrier
         env.close()
@@ -406,8 +385,7 @@ def test_partitioned_step_survives_stream_capture():
     """the partition join asked hipStreamQuery about the caller's stream, which is illegal while that stream is
     capturing.  A learner that graph-captures `env.step()` (partitions on handle-owned streams joined by events: a fork and
     a join inside the capture) must get a graph that replays to the same state as eager steps."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     outs = []
@@ -452,8 +430,7 @@ def test_graph_captured_mixed_step_follows_scenario_changes_between_replays():
     captured while the lists were clean holds no sort; when set_episodes / reset change the envs' scenarios between replays the
     replayed launch would step an env that now has more than 64 slice members with ONE narrow wave (lanes >= 64 never stepped).
     Inside a capture the sort is therefore always enqueued in front of the mixed launch."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     B = 512
@@ -496,8 +473,7 @@ def test_autoreset_loop_resorts_the_mixed_blocks_only_when_an_env_restarted():
     """The same lists in an eager auto-reset loop: the advance kernel raises a device flag when an env restarts, the (one-block)
     sort in front of the next mixed launch looks at it -- no host read-back of `done`.  Episodes of 5 TTIs whose scenarios change
     class at every restart, against the same loop with mixed blocks off."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     B, n_ep, L = 300, 12, 16
@@ -532,8 +508,7 @@ def test_a_persistent_launch_that_gave_up_is_reported_cleared_and_the_rollout_fa
     envs after their first chunk while ranenv_rollout kept returning RANENV_OK.  Now the next rollout call sees the sticky error word
     (host-visible), clears the queues, switches the persistent rollout off for the handle and FAILS; after a reset the handle steps
     again -- through the launch-per-chunk rollout -- and agrees with a handle that never had the fault."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
@@ -570,8 +545,7 @@ def test_a_persistent_launch_that_gave_up_is_reported_cleared_and_the_rollout_fa
 def test_the_very_first_step_of_a_handle_can_be_captured():
     """The examination of the traffic pool for compact steps reads a flag back (a stream synchronisation): a step captured BEFORE any eager
     step must not run it inside the capture -- it steps at full width instead, with the same results."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     outs = []
@@ -600,8 +574,7 @@ def test_graph_captured_step_with_device_autoreset_replays_through_episode_ends(
     lists -- the host's shortcut (nothing enqueued when its shadow of the step counters says no episode ended) must not apply inside a
     capture, and the shadow ends there: replays through several episode ends equal eager steps, and eager steps behind the replays
     carry on correctly."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     outs = []
@@ -650,8 +623,7 @@ def test_autoreset_reads_the_callers_done_flags_unless_the_shortcut_was_opted_in
     """ranenv_autoreset's contract is "every env with dev_done != 0 restarts".  The host-shadow shortcut (nothing enqueued
     when the host's copy of the step counters says no episode ended) is opt-in (option autoreset_shortcut, default 0): a caller that
     ORs its own truncation flags into the buffer between the step and the call gets those envs restarted."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     import ctypes as C
     from intent_radio_sched_multi_slice_amd.batched_env import _ptr
     dev = torch.device("cuda", 0)
@@ -699,8 +671,7 @@ def test_masked_reset_after_a_persistent_abort_does_not_leave_a_stale_step_shado
     valid although the envs had advanced different numbers of TTIs.  A caller that answers the error with a MASKED reset (or none) and
     carries on with env.step() + ranenv_autoreset (shortcut on) must get resets at the TTIs the DEVICE's counters say -- the same as a
     handle that reached the same device state without the fault."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     dev = torch.device("cuda", 0)
     wa, a, n_ep = _autoreset_workload(dev, flags=_lib.F_CLEAR_HISTORY_ON_RESET)
@@ -750,8 +721,7 @@ def test_guard_free_division_equals_ieee_division_on_the_kernels_operand_domain(
     kernels use it: divisors that are positive normal numbers (packet sizes, UE / RB / slice counts, window lengths, 1e6, sums of weights, the
     validated normalisers in [1e-30, 1e30]), dividends that are finite and >= 0.  Checked inside the shipped build (ranenv_selftest_ddiv) on
     random and edge operands; explicit traffic -- the one caller-supplied dividend that may be inf / huge -- does not go through ddiv at all."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     import ctypes as C
     from intent_radio_sched_multi_slice_amd import _lib
     lib = _lib.load()

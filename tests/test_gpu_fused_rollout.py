@@ -9,21 +9,9 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_se_gather_and_ranges import _bench_like, _short_episode_setup
+from tests.gpu_common import LOOSE_SE_MEAN, assert_same_state, bench_like, need_gpu, short_episode_setup
 
 pytestmark = pytest.mark.gpu
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _same(a, b, what=""):
-    for k, x in a.views().items():
-        assert torch.equal(x, b.views()[k]), (what, k)
-    assert torch.equal(a.obs_inter, b.obs_inter) and torch.equal(a.obs_intra, b.obs_intra), what
-    assert torch.equal(a.reward, b.reward) and torch.equal(a.done, b.done), what
 
 
 @pytest.mark.parametrize("se_mode", ["stream", "gather"])
@@ -31,11 +19,11 @@ def _same(a, b, what=""):
 def test_fused_rollouts_equal_one_launch_per_tti(monkeypatch, se_mode, parts):
     """BASELINE configs[2]'s shape, 512 envs: rollouts of 1, 2, 7, 23 and 45 TTIs (launches of up to 1, 1, 1, 5 and 10
     TTIs, the last one of a rollout shorter) against the same rollouts with RANENV_FUSE=1."""
-    _need_gpu()
+    need_gpu()
     monkeypatch.delenv("RANENV_FUSE", raising=False)          # (`a` runs the default policy whatever knob the suite runs under)
-    a = _bench_like(512, se_mode == "gather")
+    a = bench_like(512, se_mode == "gather")
     monkeypatch.setenv("RANENV_FUSE", "1")
-    b = _bench_like(512, se_mode == "gather")
+    b = bench_like(512, se_mode == "gather")
     monkeypatch.delenv("RANENV_FUSE")
     for wl in (a, b):
         wl.env.enable_metrics(0)
@@ -44,7 +32,7 @@ def test_fused_rollouts_equal_one_launch_per_tti(monkeypatch, se_mode, parts):
     for K in (1, 2, 7, 23, 45):
         a.env.rollout(K); b.env.rollout(K)
         torch.cuda.synchronize()
-        _same(a.env, b.env, (se_mode, parts, K))
+        assert_same_state(a.env, b.env, None, (se_mode, parts, K), loose=())
         assert torch.equal(a.env.episode_metrics()["running"], b.env.episode_metrics()["running"]), K
     assert int(a.env.views()["step_number"][0]) == 1 + 2 + 7 + 23 + 45
     a.env.close(); b.env.close()
@@ -53,10 +41,10 @@ def test_fused_rollouts_equal_one_launch_per_tti(monkeypatch, se_mode, parts):
 def test_a_fused_launch_covers_the_ttis_it_says(monkeypatch):
     """The profile counters: a rollout of 40 TTIs over 3 partitions is launches of up to 10 TTIs, the partitions' first ones
     of different lengths; with RANENV_FUSE=1 it is 3 x 40 launches of one."""
-    _need_gpu()
+    need_gpu()
     monkeypatch.delenv("RANENV_FUSE", raising=False)          # (the default policy, whatever knob the suite runs under)
     monkeypatch.delenv("RANENV_FUSE_FIRST", raising=False)
-    a = _bench_like(96, False)
+    a = bench_like(96, False)
     a.env.set_option("persist", 0)                            # (a batch this small would run as one persistent launch: below)
     a.env.reset(); a.env.set_partitions(3)
     # first launches of 10 / 6 / 1 TTIs (partition 0 / 1 / 2), then 10s: 10+10+10+10, 6+10+10+10+4, 1+10+10+10+9
@@ -73,7 +61,7 @@ def test_a_fused_launch_covers_the_ttis_it_says(monkeypatch):
         assert (pa["n_launches"], pa["n_ttis"], pa["n_env_ttis"]) == (1, 40, 96 * 40)
     a.env.close()
     monkeypatch.setenv("RANENV_FUSE", "1")
-    b = _bench_like(96, False)
+    b = bench_like(96, False)
     b.env.set_option("persist", 0)
     b.env.reset(); b.env.set_partitions(3)
     b.env.profile_begin(); b.env.rollout(40); pb = b.env.profile_end()
@@ -88,13 +76,13 @@ def test_fused_rollouts_across_device_autoresets(monkeypatch, se_mode, staggered
     the episodes end (13 = 10 + 3 inside a rollout of 40 ...), the advance + reset launches follow, the next launch starts
     the new episodes; with per-env episode lengths between 5 and 13 some episode ends almost every TTI and the launches
     shrink accordingly.  Same state, observations, episode numbers and per-episode metric sums as one launch per TTI."""
-    _need_gpu()
+    need_gpu()
     monkeypatch.delenv("RANENV_FUSE", raising=False)
     envs = []
     for fuse in (None, "1"):
         if fuse:
             monkeypatch.setenv("RANENV_FUSE", fuse)
-        env, tabs, se_pool, trf, start, dims = _short_episode_setup(48, 13, False, se_mode)
+        env, tabs, se_pool, trf, start, dims = short_episode_setup(48, 13, False, se_mode)
         if fuse:
             monkeypatch.delenv("RANENV_FUSE")
         if staggered:
@@ -127,7 +115,7 @@ def test_fused_rollouts_across_device_autoresets(monkeypatch, se_mode, staggered
 def test_fused_rollout_with_the_traffic_drawn_on_the_device(monkeypatch):
     """The Philox / Poisson generator is keyed by (env, episode, TTI, UE): a launch that runs several TTIs draws what the
     same TTIs draw one launch at a time."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_bench_workload
     monkeypatch.delenv("RANENV_FUSE", raising=False)
     envs = []
@@ -142,7 +130,7 @@ def test_fused_rollout_with_the_traffic_drawn_on_the_device(monkeypatch):
     a, b = envs
     a.rollout(48); b.rollout(48)
     torch.cuda.synchronize()
-    _same(a, b, "philox")
+    assert_same_state(a, b, None, "philox", loose=())
     assert int(a.views()["pkt_incoming"].sum()) > 0
     a.close(); b.close()
 
@@ -164,19 +152,6 @@ def _persist_pair(B, se_mode, setup, **opts):
     return out
 
 
-def _same_state(a, b, where):
-    va, vb = a.env.views(), b.env.views()
-    scen = va["episodes"][:, 0].to(torch.int64)                 # as on the device: auto-reset may have moved on
-    in_slice = torch.as_tensor(a.tables.ue_slice >= 0, device=a.env.device)[scen]
-    for k in va:
-        if k == "se_mean":                                      # of UEs outside every slice: not kept up by compact steps
-            assert torch.equal(va[k][in_slice], vb[k][in_slice]), (where, k)
-        else:
-            assert torch.equal(va[k], vb[k]), (where, k)
-    assert torch.equal(a.env.obs_inter, b.env.obs_inter) and torch.equal(a.env.obs_intra, b.env.obs_intra), where
-    assert torch.equal(a.env.reward, b.env.reward) and torch.equal(a.env.done, b.env.done), where
-
-
 @pytest.mark.parametrize("se_mode", ["stream", "gather"])
 @pytest.mark.parametrize("B,opts", [(300, {}),                                           # everything resident: nobody ever waits
                                     (300, {"persist_grid": 96, "persist_chunk": 3}),      # ~4 envs per workgroup: hand-overs all the time
@@ -188,7 +163,7 @@ def test_persistent_rollout_equals_the_launch_per_chunk_rollout(se_mode, B, opts
     <= 10 TTIs per partition.  Same numbers bit for bit after every call, whatever the grid: with a grid far smaller than the
     batch every chunk of every env is handed from one workgroup to another through the per-XCD ready queues (stale-L1 and
     cross-XCD hazards would show up as wrong state here), with the default grid the queues are hardly touched."""
-    _need_gpu()
+    need_gpu()
     a, b = _persist_pair(B, se_mode, lambda wl: wl.env.set_partitions(3), **opts)
     a.env.reset(); b.env.reset()
     t = 0
@@ -196,11 +171,11 @@ def test_persistent_rollout_equals_the_launch_per_chunk_rollout(se_mode, B, opts
         a.env.rollout(k); b.env.rollout(k)
         torch.cuda.synchronize()
         t += k
-        _same_state(a, b, (se_mode, B, t))
+        assert_same_state(a.env, b.env, a.tables, (se_mode, B, t), loose=LOOSE_SE_MEAN)
     a.env.step(); b.env.step()                              # a joined step behind a persistent rollout, then another rollout
     a.env.rollout(12); b.env.rollout(12)
     torch.cuda.synchronize()
-    _same_state(a, b, (se_mode, B, "tail"))
+    assert_same_state(a.env, b.env, a.tables, (se_mode, B, "tail"), loose=LOOSE_SE_MEAN)
     assert b.env.get_option("persist_errors") == 0
     a.env.close(); b.env.close()
 
@@ -209,7 +184,7 @@ def test_persistent_rollout_equals_the_launch_per_chunk_rollout(se_mode, B, opts
 def test_persistent_rollout_through_episode_ends(se_mode):
     """With device auto-reset a persistent launch ends at the TTI at which the first episode of the batch ends; the advance +
     RESET launches follow and the envs are sorted into classes again (their scenarios changed).  Per-env episode lengths."""
-    _need_gpu()
+    need_gpu()
     B, n_ep = 600, 40
 
     def setup(wl):
@@ -225,7 +200,7 @@ def test_persistent_rollout_through_episode_ends(se_mode):
     for k in (30, 9, 50, 21):
         a.env.rollout(k); b.env.rollout(k)
         torch.cuda.synchronize()
-        _same_state(a, b, (se_mode, k))
+        assert_same_state(a.env, b.env, a.tables, (se_mode, k), loose=LOOSE_SE_MEAN)
         ma, mb = a.env.episode_metrics(), b.env.episode_metrics()
         assert torch.equal(ma["episodes_done"], mb["episodes_done"]) and torch.equal(ma["episode_log"], mb["episode_log"])
     assert int(a.env.episode_metrics()["episodes_done"].min()) >= 2
@@ -241,7 +216,7 @@ def test_two_envs_per_wave_equal_one_env_per_wave_at_the_reference_size(se_mode,
     stepped two per wave (lanes 0-31 / 32-63, ranenv_core_kernel_packed).  Same numbers bit for bit as one env per wave: rollouts
     over 3 partitions (even ranges), single steps, external scores + per-slice intra choice, device auto-resets that change the
     scenario, the device traffic generator."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     n_ep = 24
@@ -283,6 +258,7 @@ def test_two_envs_per_wave_equal_one_env_per_wave_at_the_reference_size(se_mode,
 
 
 def _snap(env):
+    """(not assert_same_state: the two envs of a comparison never exist together, and the mean SE is left out altogether)"""
     torch.cuda.synchronize()
     d = {k: v.clone() for k, v in env.views().items() if k != "se_mean"}
     d.update(obs_inter=env.obs_inter.clone(), obs_intra=env.obs_intra.clone(), reward=env.reward.clone(), done=env.done.clone())
@@ -297,7 +273,7 @@ def test_mixed_blocks_equal_one_workgroup_per_env(se_mode, B):
     most 64 (a wave each, no block barrier between them) -- ranenv_core_kernel_mixed -- against one two-wave workgroup per env:
     single steps and multi-TTI launches (a rollout on one stream), device policy and external scores, bit for bit.  B = 37: forced
     (mix = 2), an odd number of narrow envs (the last block's second wave has none)."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     outs = []

@@ -4,44 +4,22 @@ a step loop, noise, the episode sums of the head rewards, collect_head, and the 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import sys
+import functools
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-from tests import head_policy_ref as hr  # noqa: E402
+from tests import head_policy_ref as hr
+from tests.common import OBS_TOL, REW_TOL
+from tests.gpu_common import HEAD_OUTPUTS, LOOSE_WINDOWS_AND_SE, OUTPUTS, assert_same_state, need_gpu
 
 pytestmark = pytest.mark.gpu
 
 T = 24
 SEED = 0x1234_5678_9ABC
-OBS_TOL, REW_TOL = 1e-5, 1e-9
-# State of a UE outside every slice (after a reset into another scenario): read by no observation, and not kept up by compact steps
-# (include/ranenv.h), which a rollout and a step loop choose differently.  Compared for the UEs in a slice, exactly.
-_KEYS_LOOSE = ("win_sent", "win_dropped", "se_mean")
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-
-
-def _state_equal(wl, a, b, what):
-    torch.cuda.synchronize()
-    va, vb = a.views(), b.views()
-    in_slice = torch.as_tensor(wl.tables.ue_slice >= 0, device=a.device)[va["episodes"][:, 0].to(torch.int64)]
-    for k in va:
-        x, y = (va[k][in_slice], vb[k][in_slice]) if k in _KEYS_LOOSE else (va[k], vb[k])
-        assert torch.equal(x, y), (k, what)
-    for k in ("obs_inter", "obs_intra", "reward", "done", "head_obs", "head_reward"):
-        assert torch.equal(getattr(a, k), getattr(b, k)), (k, what)
-    assert torch.equal(a.policy_actions()["scores"], b.policy_actions()["scores"]), what
+_state_equal = functools.partial(assert_same_state, loose=LOOSE_WINDOWS_AND_SE, outputs=OUTPUTS + HEAD_OUTPUTS, actions=("scores",))
 
 
 # ---- 1. forward ---------------------------------------------------------------------------------------------------------------------
@@ -52,7 +30,7 @@ def _state_equal(wl, a, b, what):
 def test_forward_within_the_float64_bound(net, size, dist, stochastic):
     """Injected head observations written into the bound buffer before a step: every (env, position) of the device's scores lies
     within the twin's bound, and within 1e-5 of the float32 restatement."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import adapters
     B = 70                                                   # (not a multiple of the 32 rows of a workgroup)
     _, env, (actor, log_std, _) = hr.make_env(size, net, dist, B, stochastic=stochastic, seed=SEED)
@@ -83,7 +61,7 @@ def test_forward_within_the_float64_bound(net, size, dist, stochastic):
 def test_env_parity_with_oracle(size, net, dist, unsorted):
     """The device's own scores (round-robin inside the slices) fed into the CPU oracle along 50 TTIs: integers exact, obs_inter
     1e-5, rewards 1e-9, head observation and head rewards at the tolerances of the reference-agent tests."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     B, steps = 9, 50
     wl, env, _ = hr.make_env(size, net, dist, B, stochastic=True, seed=3, unsorted=unsorted)
@@ -131,7 +109,7 @@ def test_env_parity_with_oracle(size, net, dist, unsorted):
 def test_rollout_is_the_step_loop(size, autoreset, se_mode):
     """rollout(T) with 1, 2 and 3 partitions leaves env state, outputs, head buffers, scores and the head rewards' episode sums bit
     for bit as T calls of step() do, with episode ends inside the rollout."""
-    _need_gpu()
+    need_gpu()
     B = 50
     kw = dict(stochastic=True, seed=SEED, autoreset=autoreset, se_mode=se_mode, metrics=8)
     wl, ref, _ = hr.make_env(size, "64x64", "gauss_clip", B, **kw)
@@ -143,7 +121,7 @@ def test_rollout_is_the_step_loop(size, autoreset, se_mode):
     for parts in (1, 2, 3):
         _, env, _ = hr.make_env(size, "64x64", "gauss_clip", B, parts=parts, **kw)
         env.rollout(T)
-        _state_equal(wl, env, ref, (parts,))
+        _state_equal(env, ref, wl.tables, (parts,))
         ma, mb = env.head_episode_metrics(), ref.head_episode_metrics()
         assert torch.equal(ma["running"], mb["running"]) and torch.equal(ma["episode_log"], mb["episode_log"]), parts
         assert torch.equal(env.episode_metrics()["episode_log"], ref.episode_metrics()["episode_log"])
@@ -154,7 +132,7 @@ def test_rollout_is_the_step_loop(size, autoreset, se_mode):
 # ---- 4. noise -----------------------------------------------------------------------------------------------------------------------
 def test_noise_depends_on_the_counters_alone():
     """Stochastic runs with one seed are identical across partition counts and step_range splits; another seed differs."""
-    _need_gpu()
+    need_gpu()
     B, n = 70, 6
     runs = {}
     for name, parts, seed in (("whole", 1, 5), ("parts3", 3, 5), ("ranges", 1, 5), ("other", 1, 6)):
@@ -172,7 +150,7 @@ def test_noise_depends_on_the_counters_alone():
     wl, whole, sc = runs["whole"]
     for name in ("parts3", "ranges"):
         assert torch.equal(runs[name][2], sc), name
-        _state_equal(wl, runs[name][1], whole, name)
+        _state_equal(runs[name][1], whole, wl.tables, name)
     assert not torch.equal(runs["other"][2], sc)
     assert float((runs["other"][2] - sc).abs().max()) > 1e-3
     for _, env, _ in runs.values():
@@ -198,7 +176,7 @@ def _episode_sums(env, n_ttis, slots):
 
 @pytest.mark.parametrize("size", list(hr.SIZES))
 def test_head_reward_sums_equal_a_sequential_sum(size):
-    _need_gpu()
+    need_gpu()
     B, slots, n = 50, 12, 52                                 # the longest episodes (24 TTIs) end twice
     _, env, _ = hr.make_env(size, "64x64", "gauss_clip", B, stochastic=True, seed=SEED, autoreset=True, metrics=slots)
     run, log, n_done = _episode_sums(env, n, slots)
@@ -219,7 +197,7 @@ def test_head_reward_sums_equal_a_sequential_sum(size):
 
 
 def test_evaluate_fills_the_head_log_with_the_same_episodes():
-    _need_gpu()
+    need_gpu()
     B, n_ep, slots = 48, 2, 12
     kw = dict(stochastic=True, seed=SEED, autoreset=True, metrics=slots)
     _, env, _ = hr.make_env("S5U25", "64x64", "gauss_clip", B, **kw)
@@ -236,7 +214,7 @@ def test_evaluate_fills_the_head_log_with_the_same_episodes():
 
 
 def test_head_sums_exist_only_with_metrics_and_heads():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
 
@@ -273,7 +251,7 @@ def test_record_is_the_step_loop_and_state_is_the_rollouts(size, stochastic, aut
     """collect_head(T) over 1 and 3 partitions records, TTI by TTI, what a step() loop on a twin sees; logp and vf lie within the
     float64 bounds; adv / vtarg equal adapters.gae on the recorded column bit for bit for both columns; everything else is as after
     rollout(T), and one more step() keeps it so."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import adapters
     B = 50
     kw = dict(stochastic=stochastic, seed=SEED, autoreset=autoreset, metrics=8)
@@ -326,7 +304,7 @@ def test_record_is_the_step_loop_and_state_is_the_rollouts(size, stochastic, aut
             if extra:
                 env.step()
                 roll.step()
-            _state_equal(wl, env, roll, (parts, extra))
+            _state_equal(env, roll, wl.tables, (parts, extra))
             ma, mb = env.head_episode_metrics(), roll.head_episode_metrics()
             assert torch.equal(ma["running"], mb["running"]) and torch.equal(ma["episode_log"], mb["episode_log"]), (parts, extra)
             assert torch.equal(env.episode_metrics()["running"], roll.episode_metrics()["running"])
@@ -339,7 +317,7 @@ def test_record_is_the_step_loop_and_state_is_the_rollouts(size, stochastic, aut
 def test_gae_on_the_other_column_null_fields_and_split_launches(autoreset):
     """reward="colran" runs GAE on column 1; fields left out of the record are not written and change nothing else; the critic fused
     behind the actor and in a launch of its own (option collect_split) give the same record bit for bit."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import adapters
     B = 50
     kw = dict(stochastic=True, seed=SEED, autoreset=autoreset)
@@ -376,7 +354,7 @@ def test_a_critic_wider_and_deeper_than_its_actor():
     """Actor [48] (padded to 64: the other branch of the LDS row stride) under a critic [96, 96], so that the workgroup's LDS buffers are
     sized by the critic and not by the actor; B = 40 (two workgroups, a tail of 8), T = 3 with episodes ending at its last TTI.
     Fused and split give one record; vf (the bootstrap slot included), logp and the unclamped action lie within the float64 bounds."""
-    _need_gpu()
+    need_gpu()
     B, n = 40, 3
     lengths = np.asarray((3, 2, 5, 1), dtype=np.int32)[np.arange(B) % 4]
 
@@ -430,7 +408,7 @@ def test_a_critic_wider_and_deeper_than_its_actor():
 
 # ---- 7. error paths, through the C ABI ------------------------------------------------------------------------------------------------
 def test_error_paths():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
     E_INVALID, E_STATE = -1, -3

@@ -5,12 +5,13 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests.gpu_common import need_gpu
+
 pytestmark = pytest.mark.gpu
 
 
 def test_batched_recorder_writes_reference_history_files(tmp_path):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.history import HIST_KEYS
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     from oracle import pyoracle

@@ -23,11 +23,11 @@ torch = pytest.importorskip("torch")
 
 from tests import directed_intents as di
 from tests import intent_census as ic
+from tests.common import OBS_TOL, PKT_COUNTS, REW_TOL, tti_metrics
+from tests.gpu_common import device_env_of_run, need_gpu, select_build
 
 pytestmark = pytest.mark.gpu
 
-OBS_TOL = 1e-5
-REW_TOL = 1e-9
 ULP_BOUND = 1
 _SEEN = {"ulp": 0, "entries": 0, "pairs": 0, "abs_small": 0.0}
 
@@ -38,35 +38,6 @@ BUILDS = {      # the switches of tests/test_gpu_fuzz.py; the cases at which eac
     "packed": ("packable", "one-slice", "no-remainder"),               # two envs per wave: U <= 32 and S, Us <= 8
     "mixed": ("partial-wave",),                                        # mixed blocks: 64 < U <= 128
 }
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _select_build(monkeypatch, build):
-    monkeypatch.setenv("RANENV_SMALL_BATCH", "0" if build in ("lean", "packed", "mixed") else "1")
-    monkeypatch.setenv("RANENV_PACK", "1" if build == "packed" else "0")
-    monkeypatch.setenv("RANENV_MIX", "2" if build == "mixed" else "0")
-    if build == "gather":
-        monkeypatch.setenv("RANENV_SE_MODE", "gather")
-
-
-def _device_env(run, max_steps=None):
-    from intent_radio_sched_multi_slice_amd import _lib
-    from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
-    c, tabs = run["case"], run["tables"]
-    T, B = c["steps"], c["B"]
-    env = BatchedRanEnv(batch=B, n_slices=c["S"], n_ues=c["U"], n_rbs=c["R"], rbs_per_rbg=c["G"], max_ues_slice=c["Us"],
-                        n_scenarios=tabs.n_scenarios, max_steps=T if max_steps is None else max_steps, hist_depth=c["D"],
-                        flags=_lib.F_SCALE_PER_ELEMENT if c["per_element"] else 0, **c["scalars"])
-    env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(np.ascontiguousarray(np.swapaxes(run["se_pool"], -1, -2)), device=env.device))
-    env.bind_traffic_pool(torch.as_tensor(run["trf"].astype(np.int32), device=env.device))
-    env.set_episodes(scenario=run["scen"], se_base=np.arange(B) * T, se_len=T, trf_base=np.arange(B) * T, trf_len=T)
-    env.set_policy(c["policy"], c["intra"])
-    return env
 
 
 def _ordered(x32):
@@ -111,7 +82,7 @@ def _check_env(run, t, b, g, obs_inter, obs_intra, rew, expected, what=""):
     tag = (run["case"]["name"], what, "TTI", t, "env", b, "scenario", int(run["scen"][b]))
     if g is not None:
         assert np.array_equal(g["rb_count"][b], count), (tag, "rb_count")
-        for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
+        for name in PKT_COUNTS:
             assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (tag, name)
     _check_obs("obs_inter", obs_inter[b], oo["obs_inter"], tag, run)
     _check_obs("obs_intra", obs_intra[b], oo["obs_intra"], tag, run)
@@ -150,10 +121,10 @@ def _run_of(name, **override):
 @pytest.mark.parametrize("build,name", [(b, n) for b, names in BUILDS.items() for n in names])
 def test_directed_case_vs_oracle(build, name, monkeypatch):
     """step() per TTI: the caller's scores and intra choices, or MARR / MAPF with each intra scheduler on the device."""
-    _need_gpu()
-    _select_build(monkeypatch, build)
+    need_gpu()
+    select_build(monkeypatch, build)
     run = _run_of(name)
-    env = _device_env(run)
+    env = device_env_of_run(run)
     env.reset()
     for t in range(run["case"]["steps"]):
         obs, rew, done = _step(run, env, t)
@@ -165,9 +136,9 @@ def test_directed_case_vs_oracle(build, name, monkeypatch):
 @pytest.mark.parametrize("policy,intra", [(1, 0), (1, 1), (1, 2), (2, 0), (2, 1), (2, 2)])
 def test_device_policies_with_each_intra_scheduler(policy, intra):
     """MARR and MAPF with round-robin, proportional-fair and max-throughput inside the slices, non-default scalars."""
-    _need_gpu()
+    need_gpu()
     run = _run_of("ref-all-scalars", policy=policy, intra=intra, B=7, steps=20)
-    env = _device_env(run)
+    env = device_env_of_run(run)
     env.reset()
     for t in range(run["case"]["steps"]):
         obs, rew, done = env.step()
@@ -182,10 +153,10 @@ def test_launch_paths(name, path, hist_depth):
     """The same TTIs issued as ranges on their own streams, as rollouts over three partitions and as persistent
     work-queue rollouts, with observation windows 1, 2 and 10 deep (the reliability drift sums the window, the throughput
     drift reads the previous TTI's occupancy)."""
-    _need_gpu()
+    need_gpu()
     run = _run_of(name, D=hist_depth)
     c = run["case"]
-    env = _device_env(run)
+    env = device_env_of_run(run)
     T = c["steps"]
     if path == "step_range":
         ranges = env.set_ranges(2)
@@ -223,7 +194,7 @@ def test_one_pass_through_a_device_autoreset():
     """Episodes of 9 TTIs over the directed scenarios, the next one installed and reset on the device: the 10-TTI window and
     the previous TTI's occupancy restart there (the agent's deque survives a reset and takes one all-zero entry), compared
     per TTI through two episode ends of every env."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     base = _run_of("ref-overfulfill-0.5")
     c, d, tabs = base["case"], base["directed"], base["tables"]
@@ -232,7 +203,7 @@ def test_one_pass_through_a_device_autoreset():
     se_pool = di.se_tiles(611, n_ep * L, U, R)
     trf = np.concatenate([d.traffic_rows(e % tabs.n_scenarios, rng, L, 1.5) for e in range(n_ep)])
     run = dict(base, se_pool=se_pool, trf=trf, scen=np.arange(B) % tabs.n_scenarios)
-    env = _device_env(dict(run, case=dict(c, steps=L)), max_steps=L)
+    env = device_env_of_run(dict(run, case=dict(c, steps=L)), max_steps=L)
     ep = np.arange(n_ep)
     env.set_episode_table(scenario=ep % tabs.n_scenarios, se_base=ep * L, se_len=L, trf_base=ep * L, trf_len=L)
     start = np.arange(B) % n_ep
@@ -273,13 +244,13 @@ def test_one_pass_through_a_device_autoreset():
 def test_alternative_heads_on_the_directed_scenarios(name, hist_depth):
     """ranenv_head_kernel (SchedTWC / SchedColORAN: the drift over the doubled window) against OracleEnv.heads, round-robin
     inside the slices as their action_format does; the bars of tests/test_gpu_flags_and_errors.py's head test."""
-    _need_gpu()
+    need_gpu()
     case = di.CASE_BY_NAME[name]
     tabs = di.materialise(case)[0].tables
     uc = (np.random.default_rng(3).integers(0, 4, tabs.slice_active.shape) * (tabs.slice_has_req != 0)).astype(np.int32)
     scen = np.arange(case["B"]) % case["n_scen"]
     run = ic.replay(dict(case, D=hist_depth, intra=0), extra=lambda o, b: o.heads(uc[scen[b]]))
-    env = _device_env(run)                       # (policy 0 with intra 0: the caller's scores, round-robin)
+    env = device_env_of_run(run)                       # (policy 0 with intra 0: the caller's scores, round-robin)
     env.enable_heads(uc)
     env.reset()
     saw_neg = saw_col = False
@@ -297,25 +268,14 @@ def test_alternative_heads_on_the_directed_scenarios(name, hist_depth):
     env.close()
 
 
-def _tti_metrics(oo, raw, active):
-    """What one TTI adds to the running sums (include/ranenv.h: ACTIVE slices in violation = minimum intent drift < 0,
-    undeclared metrics as 0; the same for priority slices; the distances are the sums of those negative minima).
-    ``active``: slice_active in the rows' sorted order -- an inactive slice with UEs has a drift row, and no part in the reward."""
-    rows = oo["obs_inter"].reshape(-1, 10)
-    ao, prio = np.where(active, rows[:, 0:3].min(axis=1), 0.0), rows[:, 6]
-    neg, pneg = ao < 0.0, prio * ao < 0.0
-    return np.array([1.0, oo["reward"][0], neg.sum(), pneg.sum(), ao[neg].sum(), ao[pneg].sum(),
-                     raw["pkt_effective_thr"].sum(), raw["dropped_pkts"].sum()])
-
-
 def test_evaluate_sums_violations_and_distances_of_the_directed_drifts():
     """evaluate(): one episode per env in one rollout; violation counts exact, reward and distance sums within 1e-9 a TTI."""
-    _need_gpu()
+    need_gpu()
     run = _run_of("ref-overfulfill-0.5")
     c, tabs = run["case"], run["tables"]
     B, T = c["B"], c["steps"]
     assert np.any((tabs.slice_active == 0) & (tabs.slice_has_req != 0) & (tabs.slice_nues > 0))     # an inactive slice with a drift row
-    env = _device_env(run)
+    env = device_env_of_run(run)
     env.set_episode_table(scenario=run["scen"], se_base=np.arange(B) * T, se_len=T, trf_base=np.arange(B) * T, trf_len=T)
     env.enable_autoreset(0, B, episode_numbers=np.arange(B))
     env.enable_metrics(1)
@@ -324,7 +284,7 @@ def test_evaluate_sums_violations_and_distances_of_the_directed_drifts():
     for t in range(T):
         for b, pe in enumerate(run["steps"][t][2]):
             sc = int(run["scen"][b])
-            exp[b] += _tti_metrics(pe[2], pe[1], tabs.slice_active[sc][tabs.sorted_slices[sc]] != 0)
+            exp[b] += tti_metrics(pe[2], pe[1], tabs.slice_active[sc][tabs.sorted_slices[sc]] != 0)
     got = np.stack([res[n][:, 0] for n in env.METRIC_NAMES], axis=1)
     assert np.array_equal(got[:, [0, 2, 3, 6, 7]], exp[:, [0, 2, 3, 6, 7]]), (got, exp)
     np.testing.assert_allclose(got[:, [1, 4, 5]], exp[:, [1, 4, 5]], rtol=0, atol=REW_TOL * T)
@@ -336,10 +296,10 @@ def test_two_parameters_on_one_metric_are_refused():
     """The reference adds one drift term per parameter; the step kernel keeps one (operator, value) per metric.  The C ABI
     therefore refuses a table with a range intent (include/ranenv.h), as set_from_reference refuses the request, and the
     handle goes on with the tables it had."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import RanEnvError
     run = _run_of("ref-overfulfill-0.5")
-    env = _device_env(run)
+    env = device_env_of_run(run)
     bad = di.materialise(di.RANGE_INTENT_CASE)[0].tables
     assert (bad.n_scenarios, bad.n_slices, bad.n_ues) == (run["tables"].n_scenarios, env.S, env.U)
     with pytest.raises(RanEnvError, match="declares metric 0 twice"):
@@ -354,7 +314,7 @@ def test_two_parameters_on_one_metric_are_refused():
 def test_float32_ulp_summary():
     """Largest distance between a device observation and the float32 rounding of the oracle's value, over every entry the
     tests above compared (runs last in this file; with -s it prints the figures)."""
-    _need_gpu()
+    need_gpu()
     print(f"\ncompared (env, TTI) pairs: {_SEEN['pairs']}; observation entries: {_SEEN['entries']}; largest float32 ulp distance "
           f"(|oracle| >= 2^-6): {_SEEN['ulp']}; largest |device - float32(oracle)| below 2^-6: {_SEEN['abs_small']:.3e}")
     assert _SEEN["ulp"] <= ULP_BOUND

@@ -6,36 +6,17 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests.common import tti_metrics
+from tests.gpu_common import need_gpu, small_workload
+
 pytestmark = pytest.mark.gpu
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _small_workload(B, steps, **kw):
-    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
-    return make_mult_slice_workload(B, torch.device("cuda", 0), policy=2, intra=1, n_scenarios=6, n_traces=12, trace_len=10,
-                                    n_slices=5, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=10, max_steps=steps, **kw)
-
-
-def _tti_metrics(o):
-    """What one TTI adds to the running sums, from the oracle's formatted observation (agents/common.py:389-427 names:
-    active_observations = per-slice minimum drift, undeclared metrics count as 0) and raw metrics."""
-    oo, raw = o.obs(), o.raw()
-    rows = oo["obs_inter"].reshape(-1, 10)
-    ao, prio = rows[:, 0:3].min(axis=1), rows[:, 6]
-    neg, pneg = ao < 0.0, prio * ao < 0.0
-    return np.array([1.0, oo["reward"][0], neg.sum(), pneg.sum(), ao[neg].sum(), ao[pneg].sum(),
-                     raw["pkt_effective_thr"].sum(), raw["dropped_pkts"].sum()])
-
-
 def test_running_sums_match_per_tti_sums_from_the_oracle():
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     B, steps = 12, 40
-    wl = _small_workload(B, steps)
+    wl = small_workload(B, steps)
     env, tabs = wl.env, wl.tables
     S, U, R = env.S, env.U, env.R
     env.enable_metrics(0)
@@ -58,7 +39,7 @@ def test_running_sums_match_per_tti_sums_from_the_oracle():
         env.step()
         for b, o in enumerate(oenvs):
             o.step(o.policy_mapf(), intra, se_host[tile(b, t)], trf_host[trow(b, t)])
-            exp[b] += _tti_metrics(o)
+            exp[b] += tti_metrics(o.obs(), o.raw())
         got = m["running"].cpu().numpy()
         assert np.array_equal(got[:, [0, 2, 3, 6, 7]], exp[:, [0, 2, 3, 6, 7]]), t          # counts: exact
         np.testing.assert_allclose(got[:, [1, 4, 5]], exp[:, [1, 4, 5]], rtol=0, atol=1e-9 * (t + 1))
@@ -81,11 +62,11 @@ def test_rollout_through_episode_ends_equals_stepwise_autoreset(parts, random_ep
     """Two identical batches, staggered episode lengths (17..29 TTIs), 100 TTIs = 3 to 5 episodes per env: one stepped
     with step() (auto-reset after every step, the path the oracle test covers), the other by two rollout() calls that run
     through the episode ends.  State, outputs, episode numbers and the per-episode metric logs must be identical."""
-    _need_gpu()
+    need_gpu()
     B, L, n_ep, first, total = 48, 10, 12, 3, 100
     envs = []
     for k in range(2):
-        wl = _small_workload(B, 50)
+        wl = small_workload(B, 50)
         env = wl.env
         ep_no = np.arange(first, first + n_ep)
         env.set_episode_table(scenario=ep_no % 6, se_base=(ep_no % 12) * L, se_len=L, se_offset=ep_no % L,
@@ -126,10 +107,10 @@ def test_rollout_through_episode_ends_equals_stepwise_autoreset(parts, random_ep
 def test_evaluate_runs_whole_episodes_on_the_device_and_matches_the_oracle():
     """evaluate(): reset + one rollout through n episodes per env; the per-episode sums against an oracle that plays the
     same episodes (sequential episode numbers, equal lengths)."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     B, L, n_ep, first, steps, n_eval = 8, 10, 12, 3, 20, 3
-    wl = _small_workload(B, steps)
+    wl = small_workload(B, steps)
     env, tabs = wl.env, wl.tables
     S, U, R = env.S, env.U, env.R
     ep_no = np.arange(first, first + n_ep)
@@ -157,7 +138,7 @@ def test_evaluate_runs_whole_episodes_on_the_device_and_matches_the_oracle():
             for t in range(steps):
                 o.step(o.policy_mapf(), intra, se_host[int(r["se_base"] + (r["se_offset"] + t) % r["se_len"])],
                        trf_host[int(r["trf_base"] + (r["trf_offset"] + t) % r["trf_len"])])
-                exp += _tti_metrics(o)
+                exp += tti_metrics(o.obs(), o.raw())
             got = np.array([res[n][b, k] for n in env.METRIC_NAMES])
             assert np.array_equal(got[[0, 2, 3, 6, 7]], exp[[0, 2, 3, 6, 7]]), (b, k, got, exp)
             np.testing.assert_allclose(got[[1, 4, 5]], exp[[1, 4, 5]], rtol=0, atol=1e-8)
@@ -168,9 +149,9 @@ def test_evaluate_runs_whole_episodes_on_the_device_and_matches_the_oracle():
 
 
 def test_metrics_api_errors():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
-    wl = _small_workload(4, 10)
+    wl = small_workload(4, 10)
     env = wl.env
     with pytest.raises(RanEnvError, match="not enabled"):
         env.episode_metrics()

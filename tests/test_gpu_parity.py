@@ -9,18 +9,11 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.common import TRACE_CASES, load_golden, poisson_traffic_rows, tables_from
+from tests.common import OBS_TOL, PKT_COUNTS, TRACE_CASES, load_golden, oracle_envs, poisson_traffic_rows, rb_major, tables_from
+from tests.gpu_common import assert_matches_oracle, need_gpu, select_build
 from tests.synth import se_tile
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL = 1e-5
-REW_TOL = 1e-9
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 @pytest.fixture(params=["lean", "small", "gather", "packed", "packed-gather", "mixed", "mixed-gather"])
@@ -35,11 +28,7 @@ def build(request, monkeypatch):
     "mixed" / "mixed-gather": whole-batch steps of two-wave workgroups (U > 64) as mixed blocks -- one block per env of more than 64
     slice members, one per two envs of at most 64 (ranenv_core_kernel_mixed) -- forced for these small batches (RANENV_MIX=2); the
     other builds run with RANENV_MIX=0."""
-    monkeypatch.setenv("RANENV_SMALL_BATCH", "0" if request.param in ("lean", "packed", "packed-gather", "mixed", "mixed-gather") else "1")
-    monkeypatch.setenv("RANENV_PACK", "1" if request.param.startswith("packed") else "0")
-    monkeypatch.setenv("RANENV_MIX", "2" if request.param.startswith("mixed") else "0")
-    if request.param.endswith("gather"):
-        monkeypatch.setenv("RANENV_SE_MODE", "gather")
+    select_build(monkeypatch, request.param)
     return "gather" if request.param.endswith("gather") else request.param
 
 
@@ -48,22 +37,23 @@ def _env(**kw):
     return BatchedRanEnv(**kw)
 
 
-def _rb_major(se_ue_major):
-    return np.ascontiguousarray(np.swapaxes(se_ue_major, -1, -2))
+class _GoldenTti:
+    """TTI k of a trace fixture in the form of an oracle env that has just stepped it: raw() and obs()."""
 
+    def __init__(self, fx, k):
+        self.fx, self.k = fx, k
 
-def _cmp_raw(env, b, raw, tag):
-    v = env.views()
-    for name, key in (("pkt_incoming", "pkt_incoming"), ("pkt_throughputs", "pkt_throughputs"),
-                      ("pkt_effective_thr", "pkt_effective_thr"), ("dropped_pkts", "dropped_pkts")):
-        got = v[name][b].cpu().numpy().astype(np.float64)
-        assert np.array_equal(got, raw[key]), (tag, name, got, raw[key])
+    def raw(self):
+        return {n: self.fx[n][self.k] for n in PKT_COUNTS + ("buffer_occupancies", "buffer_latencies")}
+
+    def obs(self):
+        return {n: self.fx[n][self.k] for n in ("obs_inter", "obs_intra", "reward")}
 
 
 @pytest.mark.parametrize("case", TRACE_CASES)
 def test_golden_traces(case, build):
     """Closed-loop traces whose agent side was produced by the reference's own code."""
-    _need_gpu()
+    need_gpu()
     fx = load_golden(case)
     cfg = fx["cfg"]
     S, U, R, G, Us = (int(x) for x in cfg[:5])
@@ -81,37 +71,28 @@ def test_golden_traces(case, build):
         get_se = (lambda t: np.full((U, R), 2.0, dtype=np.float32)) if plumbing else \
             (lambda t: se_tile(seed + ep, t, U, R))
         if pooled:
-            env.bind_se_pool(torch.as_tensor(np.stack([_rb_major(get_se(t)) for t in range(steps_per_ep)]), device=env.device))
+            env.bind_se_pool(torch.as_tensor(np.stack([rb_major(get_se(t)) for t in range(steps_per_ep)]), device=env.device))
             assert env.se_mode == "gather"
             env.set_episodes(scenario=int(idx), se_base=0, se_len=steps_per_ep)
         else:
             env.set_episodes(scenario=int(idx))
-        se0 = np.broadcast_to(_rb_major(get_se(0)), (B, R, U))
+        se0 = np.broadcast_to(rb_major(get_se(0)), (B, R, U))
         obs = env.reset(se_tiles=None if pooled else se0)
         got = np.concatenate([obs["obs_inter"][1].cpu().numpy(), obs["obs_intra"][1].cpu().numpy().ravel()])
         np.testing.assert_allclose(got, fx["reset_obs"][ep], rtol=0, atol=OBS_TOL)
         for t in range(steps_per_ep):
-            se = None if pooled else np.broadcast_to(_rb_major(get_se(t)), (B, R, U))
+            se = None if pooled else np.broadcast_to(rb_major(get_se(t)), (B, R, U))
             sc = np.broadcast_to(fx["scores"][k], (B, S))
             ic = np.broadcast_to(fx["intra"][k].astype(np.uint8), (B, S))
             tr = np.broadcast_to(fx["traffic"][k], (B, U))
             obs, rew, done = env.step(sc, ic, tr, se)
             v = env.views()
-            for b in (0, 1, B - 1):
-                tag = (case, ep, t, b)
-                cnt = v["rb_count"][b].cpu().numpy()
-                st = v["rb_start"][b].cpu().numpy()
-                assert np.array_equal(cnt, fx["rb_count"][k]), tag
-                used = cnt > 0
-                assert np.array_equal(st[used], fx["rb_start"][k][used]), tag
-                _cmp_raw(env, b, {n: fx[n][k] for n in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr",
-                                                        "dropped_pkts")}, tag)
-                ro = env.raw_observation()
-                assert np.array_equal(ro["buffer_occupancies"][b].cpu().numpy(), fx["buffer_occupancies"][k]), tag
-                assert np.array_equal(ro["buffer_latencies"][b].cpu().numpy(), fx["buffer_latencies"][k]), tag
-                np.testing.assert_allclose(obs["obs_inter"][b].cpu().numpy(), fx["obs_inter"][k], rtol=0, atol=OBS_TOL)
-                np.testing.assert_allclose(obs["obs_intra"][b].cpu().numpy(), fx["obs_intra"][k], rtol=0, atol=OBS_TOL)
-                np.testing.assert_allclose(rew[b].cpu().numpy(), fx["reward"][k], rtol=0, atol=REW_TOL)
+            sample = (0, 1, B - 1)
+            assert_matches_oracle(env, obs, rew, {b: _GoldenTti(fx, k) for b in sample}, (case, ep, t),
+                                  rb_count={b: fx["rb_count"][k] for b in sample})
+            used = fx["rb_count"][k] > 0
+            for b in sample:
+                assert np.array_equal(v["rb_start"][b].cpu().numpy()[used], fx["rb_start"][k][used]), (case, ep, t, b)
             assert int(done[0]) == (1 if t == steps_per_ep - 1 else 0)
             k += 1
         assert np.array_equal(v["mask_inter"][0].cpu().numpy(), fx["mask_inter"][k - 1])
@@ -119,24 +100,12 @@ def test_golden_traces(case, build):
     env.close()
 
 
-def _oracle_batch(tabs, scen, S, U, R, G, Us, steps):
-    from oracle import pyoracle
-    cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=steps)
-    envs = []
-    for b in range(len(scen)):
-        e = pyoracle.OracleEnv(cfg)
-        e.set_scenario(tabs, int(scen[b]))
-        envs.append(e)
-    return envs
-
-
 @pytest.mark.parametrize("policy,intra", [(1, 0), (2, 1), (0, 255), (2, 2)])
 @pytest.mark.parametrize("size", ["ref", "scaled"])
 def test_batch_vs_oracle(policy, intra, size, build):
     """B envs on distinct scenarios/traces from HBM pools, device policies, against the oracle."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
-    from oracle import pyoracle
     if size == "ref":
         S, U, R, G, Us, B = 5, 25, 135, 5, 5, 24
         tabs = generate_scaled_scenarios(6, seed=3, n_slices=S, n_ues=U, max_ues_slice=Us, min_slices=3, min_ues=2)
@@ -156,12 +125,12 @@ def test_batch_vs_oracle(policy, intra, size, build):
     env = _env(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us,
                n_scenarios=tabs.n_scenarios, max_steps=steps)
     env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(_rb_major(se_pool), device=env.device))
+    env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
     env.bind_traffic_pool(torch.as_tensor(trf_rows.astype(np.int32), device=env.device))
     env.set_episodes(scenario=scen, se_base=se_trace * trace_len, se_len=trace_len, se_offset=se_off,
                      trf_base=np.arange(B) * trace_len, trf_len=trace_len, trf_offset=trf_off)
     env.set_policy(policy, intra)
-    oenvs = _oracle_batch(tabs, scen, S, U, R, G, Us, steps)
+    oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps)
     t0 = np.zeros(B, dtype=np.int64)   # global step at which env b's current episode started
     tile_of = lambda b, t: int(se_trace[b] * trace_len + (se_off[b] + t - t0[b]) % trace_len)
     row_of = lambda b, t: int(b * trace_len + (trf_off[b] + t - t0[b]) % trace_len)
@@ -177,11 +146,8 @@ def test_batch_vs_oracle(policy, intra, size, build):
         else:
             sc, ic = None, np.full((B, S), intra, dtype=np.uint8)
             obs, rew, done = env.step()
-        v = env.views()
-        ro = env.raw_observation()
-        g = {k: x.cpu().numpy() for k, x in v.items()}
-        gro = {k: x.cpu().numpy() for k, x in ro.items()}
-        goi, goa, grw = obs["obs_inter"].cpu().numpy(), obs["obs_intra"].cpu().numpy(), rew.cpu().numpy()
+        g = {k: env.views()[k].cpu().numpy() for k in ("policy_scores", "rb_start")}
+        counts = []
         for b in range(B):
             oe = oenvs[b]
             if policy == 1:
@@ -193,18 +159,9 @@ def test_batch_vs_oracle(policy, intra, size, build):
             np.testing.assert_allclose(g["policy_scores"][b], s_b, rtol=0, atol=1e-12)
             start, count, _ = oe.action_format(s_b, ic[b], want_dense=False)
             oe.step(s_b, ic[b], se_pool[tile_of(b, t)], trf_rows[row_of(b, t)])
-            tag = (size, policy, intra, t, b)
-            assert np.array_equal(g["rb_count"][b], count), tag
-            assert np.array_equal(g["rb_start"][b][count > 0], start[count > 0]), tag
-            raw = oe.raw()
-            for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
-                assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (tag, name)
-            assert np.array_equal(gro["buffer_occupancies"][b], raw["buffer_occupancies"]), tag
-            assert np.array_equal(gro["buffer_latencies"][b], raw["buffer_latencies"]), tag
-            o = oe.obs()
-            np.testing.assert_allclose(goi[b], o["obs_inter"], rtol=0, atol=OBS_TOL, err_msg=str(tag))
-            np.testing.assert_allclose(goa[b], o["obs_intra"], rtol=0, atol=OBS_TOL, err_msg=str(tag))
-            np.testing.assert_allclose(grw[b], o["reward"], rtol=0, atol=REW_TOL, err_msg=str(tag))
+            assert np.array_equal(g["rb_start"][b][count > 0], start[count > 0]), (size, policy, intra, t, b)
+            counts.append(count)
+        assert_matches_oracle(env, obs, rew, oenvs, (size, policy, intra, t), rb_count=counts)
         if t == 17:   # masked reset of every third env mid-episode (deque survives, buffers do not)
             mask = (np.arange(B) % 3 == 0).astype(np.uint8)
             before = obs["obs_inter"].cpu().numpy().copy()
@@ -232,9 +189,8 @@ def test_shapes_vs_oracle(shape, variant, build):
     a partial last wave of UEs, a full 16 x 16 slot grid; with the caller's scores / schedulers
     (allocation at the head of every step) and with MAPF + PF on the device (allocation at the head of the step or,
     for a hashed half of the envs, at the tail of the step before)."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
-    from oracle import pyoracle
     S, U, R, G, Us = (shape[k] for k in ("S", "U", "R", "G", "Us"))
     D = shape.get("D", 10)
     tabs = generate_scaled_scenarios(3, seed=5, n_slices=S, n_ues=U, max_ues_slice=Us, min_slices=max(1, S // 2),
@@ -246,15 +202,14 @@ def test_shapes_vs_oracle(shape, variant, build):
     env = _env(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us,
                n_scenarios=tabs.n_scenarios, max_steps=steps, hist_depth=D)
     env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(_rb_major(se_pool), device=env.device))
+    env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
     trf = np.concatenate([poisson_traffic_rows(tabs, int(scen[b]), rng, steps) for b in range(B)])
     env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
     env.set_episodes(scenario=scen, se_base=np.arange(B) * steps, se_len=steps, trf_base=np.arange(B) * steps, trf_len=steps)
     env.set_policy(0, 255) if variant == "external" else env.set_policy(2, 1)
-    ocfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=steps, hist_depth=D)
-    oenvs = []
-    for b in range(B):
-        o = pyoracle.OracleEnv(ocfg); o.set_scenario(tabs, int(scen[b])); o.reset(se_pool[b * steps]); oenvs.append(o)
+    oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps, hist_depth=D)
+    for b, o in enumerate(oenvs):
+        o.reset(se_pool[b * steps])
     env.reset()
     for t in range(steps):
         if variant == "external":
@@ -263,18 +218,11 @@ def test_shapes_vs_oracle(shape, variant, build):
         else:
             sc = np.stack([o.policy_mapf() for o in oenvs]); ic = np.ones((B, S), dtype=np.uint8)
             obs, rew, done = env.step()
-        g = {k: x.cpu().numpy() for k, x in env.views().items()}
+        counts = []
         for b, o in enumerate(oenvs):
-            _, count, _ = o.action_format(sc[b], ic[b], want_dense=False)
-            assert np.array_equal(g["rb_count"][b], count), (shape, variant, t, b)
+            counts.append(o.action_format(sc[b], ic[b], want_dense=False)[1])
             o.step(sc[b], ic[b], se_pool[b * steps + t], trf[b * steps + t])
-            raw = o.raw()
-            for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
-                assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (shape, variant, t, b, name)
-            oo = o.obs()
-            np.testing.assert_allclose(obs["obs_inter"][b].cpu().numpy(), oo["obs_inter"], rtol=0, atol=OBS_TOL)
-            np.testing.assert_allclose(obs["obs_intra"][b].cpu().numpy(), oo["obs_intra"], rtol=0, atol=OBS_TOL)
-            np.testing.assert_allclose(rew[b].cpu().numpy(), oo["reward"], rtol=0, atol=REW_TOL)
+        assert_matches_oracle(env, obs, rew, oenvs, (shape, variant, t), buffers=False, rb_count=counts)
     env.close()
 
 
@@ -283,7 +231,7 @@ def test_policy_switching_vs_oracle(build):
     allocation) or at the tail of the step before (device policy, half of the envs).  Walk through every
     hand-over: external -> MARR+RR -> MAPF+PF (set_policy in between) -> external -> dense -> MAPF+PF
     -> masked reset -> MT."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
     S, U, R, G, Us, B = 5, 25, 135, 1, 5, 8
     tabs = generate_scaled_scenarios(4, seed=11, n_slices=S, n_ues=U, max_ues_slice=Us, min_slices=3, min_ues=2)
@@ -297,10 +245,10 @@ def test_policy_switching_vs_oracle(build):
     env = _env(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us,
                n_scenarios=tabs.n_scenarios, max_steps=steps)
     env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(_rb_major(se_pool), device=env.device))
+    env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
     env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
     env.set_episodes(scenario=scen, se_base=np.arange(B) * steps, se_len=steps, trf_base=np.arange(B) * steps, trf_len=steps)
-    oenvs = _oracle_batch(tabs, scen, S, U, R, G, Us, steps)
+    oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps)
     env.reset()
     for b in range(B):
         oenvs[b].reset(se_pool[b * steps])
@@ -327,7 +275,7 @@ def test_policy_switching_vs_oracle(build):
                 start, count, _ = oenvs[b].action_format(sc[b], ic[b], want_dense=False)
                 for u in range(U):
                     dense[b, u, start[u]:start[u] + count[u]] = 1
-            tiles = np.stack([_rb_major(se_pool[i][None])[0] for i in idx])
+            tiles = np.stack([rb_major(se_pool[i][None])[0] for i in idx])
             obs, rew, done = env.step_dense(dense, trf[idx].astype(np.float64), tiles)
         else:
             pol, intra = dev[what]
@@ -335,17 +283,10 @@ def test_policy_switching_vs_oracle(build):
             sc = np.stack([o.policy_marr() if pol == 1 else o.policy_mapf() for o in oenvs])
             ic = np.full((B, S), intra, dtype=np.uint8)
             obs, rew, done = env.step()
-        g = {k: x.cpu().numpy() for k, x in env.views().items()}
+        counts = []
         for b, o in enumerate(oenvs):
-            _, count, _ = o.action_format(sc[b], ic[b], want_dense=False)
-            assert np.array_equal(g["rb_count"][b], count), (what, t, b)
+            counts.append(o.action_format(sc[b], ic[b], want_dense=False)[1])
             o.step(sc[b], ic[b], se_pool[idx[b]], trf[idx[b]])
-            raw = o.raw()
-            for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
-                assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (what, t, b, name)
-            oo = o.obs()
-            np.testing.assert_allclose(obs["obs_inter"][b].cpu().numpy(), oo["obs_inter"], rtol=0, atol=OBS_TOL)
-            np.testing.assert_allclose(obs["obs_intra"][b].cpu().numpy(), oo["obs_intra"], rtol=0, atol=OBS_TOL)
-            np.testing.assert_allclose(rew[b].cpu().numpy(), oo["reward"], rtol=0, atol=REW_TOL)
+        assert_matches_oracle(env, obs, rew, oenvs, (what, t), buffers=False, rb_count=counts)
         t += 1
     env.close()

@@ -10,16 +10,14 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests.common import OBS_TOL, REW_TOL
+from tests.gpu_common import LOOSE_WIN_SENT, assert_same_state, need_gpu
+
 pytestmark = pytest.mark.gpu
 
 NETS = {"64x64": [64, 64], "512x3": [512, 512, 512]}
 SIZES = {"S10U100": dict(n_slices=10, n_ues=100, n_rbs=135, rbs_per_rbg=1, max_ues_slice=10),
          "S5U25": dict(n_slices=5, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=10)}
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
 
 
 def _workload(size, B, max_steps=1000, trace_len=64):
@@ -87,7 +85,7 @@ def _intra_safe(env, snap, intra, stochastic, seed, intra_input):
 @pytest.mark.parametrize("size", list(SIZES))
 @pytest.mark.parametrize("net", list(NETS))
 def test_forward_matches_restatement(net, size, stochastic):
-    _need_gpu()
+    need_gpu()
     B = 96
     wl = _workload(size, B)
     env = wl.env
@@ -120,7 +118,7 @@ def test_forward_matches_restatement(net, size, stochastic):
 @pytest.mark.parametrize("net", list(NETS))
 def test_env_parity_with_oracle(net, size):
     """The device's own actions fed into the CPU oracle along 50 TTIs: integers exact, observation 1e-5, rewards 1e-9."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     B, steps = 8, 50
     wl = _workload(size, B, trace_len=64)
@@ -151,8 +149,8 @@ def test_env_parity_with_oracle(net, size):
             raw, o = e.raw(), e.obs()
             for k in ("pkt_effective_thr", "dropped_pkts", "pkt_throughputs"):
                 assert np.array_equal(v[k][b], raw[k]), (k, t, b)
-            np.testing.assert_allclose(oi[b], o["obs_inter"], rtol=0, atol=1e-5)
-            np.testing.assert_allclose(rw[b], o["reward"], rtol=0, atol=1e-9)
+            np.testing.assert_allclose(oi[b], o["obs_inter"], rtol=0, atol=OBS_TOL)
+            np.testing.assert_allclose(rw[b], o["reward"], rtol=0, atol=REW_TOL)
     env.close()
 
 
@@ -167,28 +165,13 @@ def _episode_table(env):
     env.enable_autoreset(0, env.B, episode_numbers=np.arange(env.B, dtype=np.int32))
 
 
-def _same_state(a, b, tables):
-    va, vb = a.views(), b.views()
-    scen = va["episodes"][:, 0].to(torch.int64)                 # as on the device: auto-reset may have moved on
-    in_slice = torch.as_tensor(tables.ue_slice >= 0, device=a.device)[scen]
-    for k in _KEYS:
-        if k == "win_sent":      # of a UE outside every slice (after a reset into another scenario): read by no observation
-            assert torch.equal(va[k][in_slice], vb[k][in_slice]), k
-        else:
-            assert torch.equal(va[k], vb[k]), k
-    assert torch.equal(a.obs_inter, b.obs_inter) and torch.equal(a.obs_intra, b.obs_intra)
-    assert torch.equal(a.reward, b.reward) and torch.equal(a.done, b.done)
-    pa, pb = a.policy_actions(), b.policy_actions()
-    assert torch.equal(pa["scores"], pb["scores"]) and torch.equal(pa["intra"], pb["intra"])
-
-
 @pytest.mark.parametrize("autoreset", [False, True])
 @pytest.mark.parametrize("size", list(SIZES))
 @pytest.mark.parametrize("net", list(NETS))
 def test_rollout_equals_steps(net, size, autoreset):
     """rollout(K) over 1, 2 and 3 partitions == K calls of step(), stochastic actions included; with auto-reset across
     episode ends (episodes of 7 TTIs, K = 17)."""
-    _need_gpu()
+    need_gpu()
     B, K = 48, 17
     max_steps = 7 if autoreset else 1000
     wl = _workload(size, B, max_steps=max_steps)
@@ -210,14 +193,14 @@ def test_rollout_equals_steps(net, size, autoreset):
         env.rollout(K)
         torch.cuda.synchronize()
         assert env.get_option("last_rollout_persistent") == 0
-        _same_state(ref, env, wl.tables)
+        assert_same_state(ref, env, wl.tables, parts, loose=LOOSE_WIN_SENT, keys=_KEYS, actions=("scores", "intra"))
         env.close()
     ref.close()
 
 
 def test_stochastic_seed():
     """The same seed reproduces the draws exactly, another seed changes them; deterministic mode ignores the seed."""
-    _need_gpu()
+    need_gpu()
     runs = {}
     for key, (st, seed) in {"a": (True, 1), "a2": (True, 1), "b": (True, 2), "d1": (False, 1), "d2": (False, 2)}.items():
         env = _workload("S5U25", 64).env
@@ -234,7 +217,7 @@ def test_stochastic_seed():
 
 
 def test_policy_network_without_intra_net_uses_fixed_intra():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     a, b = _workload("S5U25", 32).env, _workload("S5U25", 32).env
     inter, _ = _nets(a, [64, 64])
@@ -254,7 +237,7 @@ def test_policy_network_without_intra_net_uses_fixed_intra():
 @pytest.mark.parametrize("size", list(SIZES))
 def test_evaluate_equals_step_loop(size):
     """evaluate() under the network policy (2 episodes per env) == a step() loop with auto-reset."""
-    _need_gpu()
+    need_gpu()
     B, n_ep, max_steps = 32, 2, 9
     out = []
     for mode in ("evaluate", "steps"):
@@ -280,7 +263,7 @@ def test_evaluate_equals_step_loop(size):
 
 
 def test_error_paths():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
     env = _workload("S5U25", 16).env

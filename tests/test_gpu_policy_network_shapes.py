@@ -15,18 +15,13 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests import policy_ref as pr  # noqa: E402
-from tests.test_policy_ref_cpu import GRID, make_inter_net, make_net  # noqa: E402
+from tests import policy_ref as pr
+from tests.common import OBS_TOL, REW_TOL
+from tests.gpu_common import GRID, make_inter_net, make_net, need_gpu
 
 pytestmark = pytest.mark.gpu
 
-OBS_TOL, REW_TOL = 1e-5, 1e-9
 STATS = {"pairs": 0}          # (config, row) pairs compared, reported at the end of the module
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
 
 
 def _workload(S, Us, B, max_steps=1000, seed=10, U=None, R=25, G=1, trace_len=32):
@@ -92,7 +87,7 @@ def _check(env, ref, rows=None, min_safe=0.9):
 # ---- injected-input forward over the grid -------------------------------------------------------------------------------
 @pytest.mark.parametrize("k", range(len(GRID)))
 def test_injected_forward_matches_float64(k):
-    _need_gpu()
+    need_gpu()
     cfg = GRID[k]
     S, Us, B, iw, ia, aw, aa, layout, st = cfg
     wl = _workload(S, Us, B, seed=20 + k)
@@ -142,7 +137,7 @@ def _outside_untouched(env, lo, hi):
 
 
 def test_partitioned_rollout_matches_float64():
-    _need_gpu()
+    need_gpu()
     wl = _workload(*CFG_RANGES[:3], seed=31)
     env = wl.env
     inter, intra = _nets(env, CFG_RANGES, 7)
@@ -166,7 +161,7 @@ def test_partitioned_rollout_matches_float64():
 
 
 def test_ranges_step_async_and_step_range_match_float64():
-    _need_gpu()
+    need_gpu()
     wl = _workload(*CFG_RANGES[:3], seed=32)
     env = wl.env
     inter, intra = _nets(env, CFG_RANGES, 8)
@@ -198,7 +193,7 @@ def test_ranges_step_async_and_step_range_match_float64():
 
 # ---- noise keying --------------------------------------------------------------------------------------------------------
 def test_noise_keyed_by_env_id_base_and_far_episode_numbers():
-    _need_gpu()
+    need_gpu()
     cfg = (5, 10, 33, [64], "tanh", [96], "tanh", "obs", True)
     B, first, base, seed = 33, 0x5A5A_0000, 1000, 0xFEDC_BA98_7654_3210
     wl = _workload(5, 10, B, max_steps=4, seed=33)
@@ -230,7 +225,7 @@ def test_noise_keyed_by_env_id_base_and_far_episode_numbers():
 
 # ---- rebinding nets on one handle -------------------------------------------------------------------------------------------
 def test_rebind_in_place_inter_only_and_larger():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     S, Us, B = 10, 10, 33
     wl = _workload(S, Us, B, seed=34)
@@ -259,7 +254,7 @@ def test_rebind_in_place_inter_only_and_larger():
 
 def test_rebind_right_after_partitioned_rollout():
     """set_policy_network issued behind a partitioned rollout without a host sync == the same sequence with a sync."""
-    _need_gpu()
+    need_gpu()
     cfg_a = (5, 10, 100, [512, 512], "tanh", [512, 33], "relu", "obs", True)
     cfg_b = (5, 10, 100, [33], "relu", [7], "tanh", "obs", True)
     out = []
@@ -310,7 +305,7 @@ def _draw_net_case(k):
 
 @pytest.mark.parametrize("k", range(N_FUZZ))
 def test_network_policy_fuzz_vs_oracle(k):
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     c = _draw_net_case(k)
     S, Us, B, steps = c["S"], c["Us"], c["B"], c["steps"]
@@ -386,5 +381,5 @@ def test_network_policy_fuzz_vs_oracle(k):
 
 def test_zz_report_pairs():
     """Not a check: prints how many (config, row) pairs this module compared with the float64 reference."""
-    _need_gpu()
+    need_gpu()
     print(f"\npolicy-network shapes: {STATS['pairs']} (config, row) pairs compared")

@@ -10,71 +10,14 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests.agents_common import OracleIBSched
+from tests.gpu_common import need_gpu
+
 pytestmark = pytest.mark.gpu
 
 
-class OracleIBSched:
-    """IBSched (agents/ib_sched.py) with the oracle's agent-side functions behind the reference's method names."""
-
-    def __init__(self, env, max_number_ues, max_number_slices, max_number_basestations, num_available_rbs, seed=0,
-                 max_ues_slice=5, rbs_per_rbg=1):
-        from oracle import pyoracle
-        self.env = env
-        self.max_number_ues, self.max_number_slices = max_number_ues, max_number_slices
-        self.max_number_basestations, self.num_available_rbs = max_number_basestations, num_available_rbs
-        ce = env.comm_env
-        self.S, self.U, self.R, self.Us = max_number_slices, max_number_ues, int(num_available_rbs[0]), max_ues_slice
-        self.cfg = pyoracle.make_cfg(self.S, self.U, self.R, rbs_per_rbg, self.Us, bandwidth_hz=float(ce.bandwidths[0]),
-                                     max_steps=ce.max_number_steps)
-        self.orc = pyoracle.OracleEnv(self.cfg)
-        self._scenario_key = None
-        self.last_sched = np.zeros((1, self.U, self.R))
-
-    def _sync_scenario(self, raw):
-        """slice_req / associations come with the raw observation; buffer parameters are read off
-        env.comm_env.ues (agents/common.py:581-582,591)."""
-        from intent_radio_sched_multi_slice_amd.scenario import ScenarioTables
-        ues = self.env.comm_env.ues
-        key = (raw["slice_ue_assoc"].tobytes(), ues.pkt_sizes.tobytes(), ues.max_buffer_pkts.tobytes())
-        if key != self._scenario_key:
-            t = ScenarioTables.empty(1, self.S, self.U, self.Us)
-            t.set_from_reference(0, raw["basestation_slice_assoc"], raw["slice_ue_assoc"], raw["slice_req"], True,
-                                 (ues.pkt_sizes, ues.max_buffer_pkts, np.array([b.max_packets_age for b in ues.buffers])))
-            self.tables = t
-            self.orc.set_scenario(t, 0)
-            self._scenario_key = key
-
-    def obs_space_format(self, raw):
-        self._sync_scenario(raw)
-        self.orc.agent_observe(raw["pkt_effective_thr"], raw["dropped_pkts"], raw["buffer_occupancies"],
-                               raw["buffer_latencies"], raw["spectral_efficiencies"][0].astype(np.float32),
-                               raw["sched_decision"][0].sum(axis=1))
-        o = self.orc.obs()
-        out = {"player_0": {"observations": o["obs_inter"], "action_mask": o["mask_inter"]}}
-        for s in range(self.S):
-            out[f"player_{s + 1}"] = {"observations": o["obs_intra"][s], "action_mask": o["mask_intra"][s]}
-        self._last = o
-        return out
-
-    def calculate_reward(self, obs):
-        return {f"player_{i}": float(self._last["reward"][i]) for i in range(self.S + 1)}
-
-    def action_format(self, action):
-        scores = np.asarray(action["player_0"], dtype=np.float64)
-        intra = np.array([int(action[f"player_{s + 1}"]) for s in range(self.S)], dtype=np.int32)
-        _, _, dense = self.orc.action_format(scores, intra, want_dense=True)
-        return dense[None].astype(np.float64)
-
-    def step(self, obs, t):
-        """A policy: MAPF scores (agents/mapf.py:41-111), intra-slice scheduler cycling through RR / PF / MT."""
-        a = {"player_0": self.orc.policy_mapf()}
-        a.update({f"player_{s + 1}": (s + t) % 3 for s in range(self.S)})
-        return a
-
-
 def test_ibsched_protocol_agent_through_the_facade_matches_a_cpu_closed_loop(tmp_path):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import plugins
     from intent_radio_sched_multi_slice_amd.comm_env import DEFAULT_CONFIGS, MARLCommEnv
     from intent_radio_sched_multi_slice_amd.history import HIST_KEYS

@@ -15,103 +15,23 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.common import load_golden
-from tests.test_gpu_protocol_agent import OracleIBSched
+from tests.agents_common import _Agent, replay_fixture
+from tests.common import OBS_TOL, REW_TOL, load_golden, rb_major
+from tests.gpu_common import need_gpu
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL, REW_TOL = 1e-5, 1e-9
-
-
-class _Agent(OracleIBSched):
-    """IBSched's protocol; ``sort`` = enable_sort_slices (MARR / MAPF wrap an IBSched built with it off, agents/marr.py:30-37)."""
-
-    def __init__(self, *a, sort=True, **k):
-        super().__init__(*a, **k)
-        self._sort = sort
-
-    def _sync_scenario(self, raw):
-        from intent_radio_sched_multi_slice_amd.scenario import ScenarioTables
-        ues = self.env.comm_env.ues
-        key = (raw["slice_ue_assoc"].tobytes(), ues.pkt_sizes.tobytes(), ues.max_buffer_pkts.tobytes())
-        if key != self._scenario_key:
-            t = ScenarioTables.empty(1, self.S, self.U, self.Us)
-            t.set_from_reference(0, raw["basestation_slice_assoc"], raw["slice_ue_assoc"], raw["slice_req"], self._sort,
-                                 (ues.pkt_sizes, ues.max_buffer_pkts, np.array([b.max_packets_age for b in ues.buffers])))
-            self.tables = t
-            self.orc.set_scenario(t, 0)
-            self._scenario_key = key
 
 
 @pytest.mark.parametrize("name", ["ib_sched", "marr", "mapf"])
 def test_fixture_of_the_real_reference_agents_replays_on_the_gpu_facade(name, tmp_path):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     replay_fixture(name, tmp_path)
-
-
-def replay_fixture(name, tmp_path):
-    """(also run by tests/test_reference_agents_cpu.py with the CPU stand-in under the facade)"""
-    from intent_radio_sched_multi_slice_amd import plugins
-    from intent_radio_sched_multi_slice_amd.comm_env import DEFAULT_CONFIGS, MARLCommEnv
-    fx = load_golden("agents_on_facade")
-    S, U, R, G, Us, seed, steps = (int(x) for x in fx["cfg"])
-    cfg = dict(DEFAULT_CONFIGS["mult_slice"], max_number_steps=steps)
-    env = MARLCommEnv(plugins.MimicQuadriga, plugins.MultSliceTraffic, plugins.SimpleMobility, plugins.MultSliceAssociation,
-                      "mult_slice", name, seed, root_path=str(tmp_path), config=cfg, max_episode_number=2, max_ues_slice=Us)
-    ce = env.comm_env
-    marl = name == "ib_sched"
-    agent = _Agent(env, ce.max_number_ues, ce.max_number_slices, ce.max_number_basestations, ce.num_available_rbs,
-                   max_ues_slice=Us, rbs_per_rbg=G, sort=marl)
-    env.set_agent_functions(agent.obs_space_format, agent.action_format, agent.calculate_reward, None, None)
-    fixed = {"ib_sched": None, "marr": 0, "mapf": 1}[name]      # MARR: fixed_intra "rr" (marr.py:62-70), MAPF: "pf" (mapf.py:126-134)
-
-    def flat(o):
-        if marl:
-            return (np.concatenate([o["player_0"]["observations"]] + [o[f"player_{s + 1}"]["observations"] for s in range(S)]),
-                    np.concatenate([o["player_0"]["action_mask"]] + [o[f"player_{s + 1}"]["action_mask"] for s in range(S)]))
-        return np.asarray(o["player_0"]["observations"]), None
-
-    obs, _ = env.reset(seed=seed, options={"initial_episode": 0})
-    assert np.array_equal(ce.slice_ue_assoc, fx[f"{name}_slice_ue_assoc"])
-    assert {k: (v["name"] if v else None) for k, v in ce.slice_req.items()} == json.loads(str(fx[f"{name}_slice_names"]))
-    assert np.array_equal(np.stack([ce.ues.pkt_sizes, ce.ues.max_buffer_pkts, ce.ues.max_buffer_latencies]), fx[f"{name}_ues"])
-    o, m = flat(obs)
-    np.testing.assert_allclose(o, fx[f"{name}_reset_obs"], rtol=0, atol=OBS_TOL)
-    if marl:
-        assert np.array_equal(m, fx[f"{name}_reset_mask"])
-    for t in range(steps):
-        a = fx[f"{name}_action"][t]
-        action = {"player_0": a[:S].copy()}
-        action.update({f"player_{s + 1}": int(a[S + s]) if marl else fixed for s in range(S)})
-        obs, reward, term, trunc, info = env.step(action)
-        raw = env._last_raw
-        sched = np.asarray(raw["sched_decision"])[0]
-        cnt = sched.sum(axis=1).astype(np.int32)
-        assert np.array_equal(cnt, fx[f"{name}_rb_count"][t]), (name, t)
-        st = np.array([int(np.nonzero(sched[u])[0][0]) if cnt[u] else 0 for u in range(U)])
-        assert np.array_equal(st, fx[f"{name}_rb_start"][t]), (name, t)
-        assert np.array_equal(env._last_traffic, fx[f"{name}_traffic"][t]), (name, t)
-        np.testing.assert_array_equal(np.asarray(raw["spectral_efficiencies"])[0].sum(axis=1), fx[f"{name}_se_sum"][t])
-        for k in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts", "buffer_occupancies", "buffer_latencies"):
-            assert np.array_equal(raw[k], fx[f"{name}_{k}"][t]), (name, t, k)
-        o, m = flat(obs)
-        np.testing.assert_allclose(o, fx[f"{name}_obs"][t], rtol=0, atol=OBS_TOL, err_msg=str((name, t)))
-        if marl:
-            assert np.array_equal(m, fx[f"{name}_mask"][t])
-            rw = np.array([reward[f"player_{i}"] for i in range(S + 1)])
-        else:
-            rw = np.array([reward["player_0"]])
-        np.testing.assert_allclose(rw, fx[f"{name}_reward"][t], rtol=0, atol=REW_TOL, err_msg=str((name, t)))
-    assert term["__all__"]
-    env.close()
 
 
 def test_batched_marl_view_carries_the_reference_spaces():
     """adapters.MarlBatchEnv.observation_space / action_space against IBSched.get_obs_space / get_action_space as the
     reference's class returned them (agents/ib_sched.py:394-470)."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.adapters import MarlBatchEnv, describe_space
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     fx = load_golden("agents_on_facade")
@@ -137,8 +57,7 @@ def test_fixture_of_the_real_head_agents_replays_on_the_gpu_facade(name, col, tm
     observation of 10 values per slice and their own rewards, IBSched's action_format with round-robin inside the slices)
     ran on the facade when the fixture was made.  Replayed here: the fixture's actions through the GPU facade with this build's
     plugins, the head kernel (ranenv_bind_head_outputs) producing the observation and both rewards every TTI."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import plugins
     from intent_radio_sched_multi_slice_amd.comm_env import DEFAULT_CONFIGS, MARLCommEnv
     from intent_radio_sched_multi_slice_amd.scenario import slice_usecase_from_req
@@ -207,8 +126,7 @@ def test_fused_step_kernel_against_the_real_agents_episode(name, B):
     returned, TTI after TTI, in closed loop.  RB ranges, packets and occupancies exact, observations 1e-5, rewards 1e-9.
     B = 4: at this size -- the reference's own -- an even batch is stepped two envs per wave (ranenv_core_kernel_packed); the envs
     compared are the second half of wave 0 (1), the first half of wave 0 (0) and the first half of wave 1 (2)."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import ScenarioTables
     fx = load_golden("agents_on_facade")
@@ -259,8 +177,7 @@ def test_head_vec_env_against_the_real_head_agents_episode(name, reward):
     """adapters.HeadVecEnv (the SB3 VecEnv view: head kernel + IBSched's action_format with round-robin on the device, SE and
     traffic replayed from HBM pools) on the episode the real SchedTWC / SchedColORAN played: their observation and reward
     at every TTI."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.adapters import HeadVecEnv
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import ScenarioTables, slice_usecase_from_req
@@ -272,7 +189,7 @@ def test_head_vec_env_against_the_real_head_agents_episode(name, reward):
     B = 2
     env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us, n_scenarios=1, max_steps=steps)
     env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(np.ascontiguousarray(np.swapaxes(se[1:], 1, 2)), device=env.device))    # the steps' tiles
+    env.bind_se_pool(torch.as_tensor(rb_major(se[1:]), device=env.device))    # the steps' tiles
     env.bind_traffic_pool(torch.as_tensor(traffic.astype(np.int32), device=env.device))
     env.set_episodes(scenario=0, se_base=0, se_len=steps, trf_base=0, trf_len=steps)
     venv = HeadVecEnv(env, reward=reward, slice_usecase=slice_usecase_from_req(req, S)[None])

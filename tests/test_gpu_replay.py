@@ -4,49 +4,28 @@ a rollout leaves, the sampler against the numpy index rule, and the error rules 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import sys
+import functools
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-from tests import head_policy_ref as hr  # noqa: E402
+from tests import head_policy_ref as hr
+from tests.gpu_common import HEAD_OUTPUTS, LOOSE_WINDOWS_AND_SE, OUTPUTS, assert_same_state, need_gpu
 
 pytestmark = pytest.mark.gpu
 
 B, CAP, T = 48, 7, 5          # a 16-row tail workgroup; two calls of 5 TTIs: the second wraps
 SEED = 0x1234_5678_9ABC
 SENTINEL = {"obs": -7.0, "next_obs": -7.0, "action": -7.0, "reward_head": -7.0, "done": 255}
-_KEYS_LOOSE = ("win_sent", "win_dropped", "se_mean")      # of UEs outside every slice: see tests/test_gpu_head_policy.py
 # (size, dist, stochastic, autoreset, se_mode)
 CONFIGS = [(size, dist, True, ar, "stream") for size in hr.SIZES for dist in ("gauss_clip", "gauss_tanh") for ar in (False, True)]
 CONFIGS += [("S5U25", "gauss_tanh", True, True, "gather"), ("S5U25", "gauss_tanh", False, True, "stream")]
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-
-
-def _state_equal(wl, a, b, what):
-    torch.cuda.synchronize()
-    va, vb = a.views(), b.views()
-    in_slice = torch.as_tensor(wl.tables.ue_slice >= 0, device=a.device)[va["episodes"][:, 0].to(torch.int64)]
-    for k in va:
-        x, y = (va[k][in_slice], vb[k][in_slice]) if k in _KEYS_LOOSE else (va[k], vb[k])
-        assert torch.equal(x, y), (k, what)
-    for k in ("obs_inter", "obs_intra", "reward", "done", "head_obs", "head_reward"):
-        assert torch.equal(getattr(a, k), getattr(b, k)), (k, what)
-    assert torch.equal(a.policy_actions()["scores"], b.policy_actions()["scores"]), what
-    ma, mb = a.head_episode_metrics(), b.head_episode_metrics()
-    assert torch.equal(ma["running"], mb["running"]) and torch.equal(ma["episode_log"], mb["episode_log"]), what
-    ea, eb = a.episode_metrics(), b.episode_metrics()
-    assert torch.equal(ea["running"], eb["running"]) and torch.equal(ea["episode_log"], eb["episode_log"]), what
+_state_equal = functools.partial(assert_same_state, loose=LOOSE_WINDOWS_AND_SE, outputs=OUTPUTS + HEAD_OUTPUTS, actions=("scores",),
+                                 metrics={"head_episode_metrics": ("running", "episode_log"), "episode_metrics": ("running", "episode_log")})
 
 
 def _bound_ring(env, cap=CAP):
@@ -74,7 +53,7 @@ def _step_loop(ref, n):
 
 @pytest.mark.parametrize("size,dist,stochastic,autoreset,se_mode", CONFIGS)
 def test_ring_is_the_step_loop_and_state_is_the_rollouts(size, dist, stochastic, autoreset, se_mode):
-    _need_gpu()
+    need_gpu()
     kw = dict(stochastic=stochastic, seed=SEED, autoreset=autoreset, se_mode=se_mode, metrics=8, critic=False)
     wl, ref, _ = hr.make_env(size, "64x64", dist, B, **kw)
     want = _step_loop(ref, 2 * T)
@@ -104,17 +83,17 @@ def test_ring_is_the_step_loop_and_state_is_the_rollouts(size, dist, stochastic,
                         assert torch.equal(t[slot], want[f][ks[-1]]), (f, slot, parts, call)
                     else:       # not yet written
                         assert bool((t[slot] == SENTINEL[f]).all()), (f, slot, parts, call)
-            _state_equal(wl, env, roll, (parts, call))
+            _state_equal(env, roll, wl.tables, (parts, call))
         env.step()
         roll.step()
-        _state_equal(wl, env, roll, (parts, "one more step"))
+        _state_equal(env, roll, wl.tables, (parts, "one more step"))
         env.close()
         roll.close()
     ref.close()
 
 
 def test_sampler_follows_the_index_rule_and_gathers_the_rows():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import adapters
     _, env, _ = hr.make_env("S5U25", "64x64", "gauss_tanh", B, stochastic=True, seed=SEED, autoreset=True, critic=False)
     ring = _bound_ring(env)
@@ -144,7 +123,7 @@ def test_sampler_follows_the_index_rule_and_gathers_the_rows():
 
 
 def test_error_rules():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     E_INVALID, E_STATE = -1, -3
     wl, env, (actor, log_std, critic) = hr.make_env("S5U25", "64x64", "gauss_tanh", B, bind=False)

@@ -4,29 +4,20 @@ properties -- terminal rows, the mode, prefixes, optional outputs, independent w
 from __future__ import annotations
 
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-from tests import head_policy_ref as hr  # noqa: E402
-from tests import sac_ref as sr  # noqa: E402
+from tests import head_policy_ref as hr
+from tests import sac_ref as sr
+from tests.gpu_common import need_gpu, to_host
 
 pytestmark = pytest.mark.gpu
 
 SEED, DRAW = 77, 3
 SIZE_OF = {5: "S5U25", 10: "S10U100"}
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
 
 
 def _env(case, B=8):
@@ -39,15 +30,10 @@ def _env(case, B=8):
     return env, (actor, q1, q2)
 
 
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: t.cpu().numpy().copy() for k, t in out.items()}
-
-
 @pytest.mark.parametrize("stochastic", [True, False])
 @pytest.mark.parametrize("case", sorted(sr.CASES))
 def test_targets_lie_inside_the_float64_bounds(case, stochastic):
-    _need_gpu()
+    need_gpu()
     env, nets = _env(case)
     obs, reward, done = sr.sac_inputs(case)
     n, S = sr.N_ROWS, env.S
@@ -55,7 +41,7 @@ def test_targets_lie_inside_the_float64_bounds(case, stochastic):
     ref = sr.SacRef(obs, reward, done, *nets, sr.GAMMA, sr.ENT_COEF, z)
     args = (torch.as_tensor(obs), torch.as_tensor(reward), torch.as_tensor(done))
     kw = dict(gamma=sr.GAMMA, ent_coef=sr.ENT_COEF, stochastic=stochastic, seed=SEED, draw=DRAW)
-    got = _host(env.sac_targets(*args, **kw))
+    got = to_host(env.sac_targets(*args, **kw))
     assert got["target"].shape == (n,) and got["next_action"].shape == (n, S) and got["next_logp"].shape == (n,) and got["q"].shape == (n, 2)
     for k in ("next_action", "next_logp", "q", "target"):
         v, want, bound = got[k].astype(np.float64), getattr(ref, k), getattr(ref, k + "_bound")
@@ -69,13 +55,13 @@ def test_targets_lie_inside_the_float64_bounds(case, stochastic):
         assert np.array_equal(ref.z, np.zeros_like(ref.z))
     # the prefix property: rows are independent
     m = 33
-    part = _host(env.sac_targets(*(a[:m] for a in args), **kw))
+    part = to_host(env.sac_targets(*(a[:m] for a in args), **kw))
     assert all(np.array_equal(part[k], got[k][:m]) for k in got), "prefix"
     # optional outputs set to NULL leave the target as it is
-    only = _host(env.sac_targets(*args, outputs=("target",), **kw))
+    only = to_host(env.sac_targets(*args, outputs=("target",), **kw))
     assert set(only) == {"target"} and np.array_equal(only["target"], got["target"])
     # another draw / seed: other noise (stochastic), the same values (mode)
-    other = _host(env.sac_targets(*args, **dict(kw, draw=DRAW + 1)))
+    other = to_host(env.sac_targets(*args, **dict(kw, draw=DRAW + 1)))
     assert np.array_equal(other["next_action"], got["next_action"]) != stochastic
     env.close()
 
@@ -84,7 +70,7 @@ def test_targets_lie_inside_the_float64_bounds(case, stochastic):
 def test_the_target_and_the_head_policy_share_one_squashed_gaussian_epilogue(case):
     """The mode of the SAC target's a' on an observation IS the score a deterministic "gauss_tanh" head policy steps with on it: the
     same weights through the same layers, tanh of the same double.  B = 40: one full workgroup of rows and a tail of 8."""
-    _need_gpu()
+    need_gpu()
     B = 40
     env, _ = _env(case, B)
     env.set_head_policy_network(sr.sac_nets(case)[0], "gauss_tanh", stochastic=False)
@@ -101,34 +87,34 @@ def test_the_target_and_the_head_policy_share_one_squashed_gaussian_epilogue(cas
 
 
 def test_actor_and_critics_keep_buffers_of_their_own():
-    _need_gpu()
+    need_gpu()
     case = "64x64"
     env, (actor, q1, q2) = _env(case)
     obs, reward, done = sr.sac_inputs(case)
     S = env.S
     args = (torch.as_tensor(obs), torch.as_tensor(reward), torch.as_tensor(done))
     kw = dict(gamma=sr.GAMMA, ent_coef=sr.ENT_COEF, stochastic=True, seed=SEED, draw=DRAW)
-    first = _host(env.sac_targets(*args, **kw))
+    first = to_host(env.sac_targets(*args, **kw))
     # a larger actor (its packed buffer grows): the critics still answer as the reference says
     wide = hr.mlp([10 * S, 128, 128, 2 * S], "tanh", 99, sr.OUT_SCALE)
     env.set_head_policy_network(wide, "gauss_tanh", stochastic=True, seed=1)
     ref = sr.SacRef(obs, reward, done, wide, q1, q2, sr.GAMMA, sr.ENT_COEF, sr.noise(sr.N_ROWS, S, SEED, DRAW))
-    got = _host(env.sac_targets(*args, **kw))
+    got = to_host(env.sac_targets(*args, **kw))
     sr.check_outputs(ref, got, "wide actor")
     assert not np.array_equal(got["q"], first["q"])
     # back to the first actor: bit for bit the first answer; rebinding the critics (swapped) leaves the actor's part as it is
     env.set_head_policy_network(actor, "gauss_tanh", stochastic=True, seed=1)
-    back = _host(env.sac_targets(*args, **kw))
+    back = to_host(env.sac_targets(*args, **kw))
     assert all(np.array_equal(back[k], first[k]) for k in first)
     env.set_sac_critics(q2, q1)
-    swapped = _host(env.sac_targets(*args, **kw))
+    swapped = to_host(env.sac_targets(*args, **kw))
     assert np.array_equal(swapped["q"], first["q"][:, ::-1]) and np.array_equal(swapped["target"], first["target"])
     assert np.array_equal(swapped["next_action"], first["next_action"]) and np.array_equal(swapped["next_logp"], first["next_logp"])
     env.close()
 
 
 def test_error_rules():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     E_INVALID, E_STATE = -1, -3
     case = "64x64"

@@ -12,37 +12,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.common import poisson_traffic_rows
+from tests.common import oracle_envs, poisson_traffic_rows, rb_major
+from tests.gpu_common import assert_matches_oracle, need_gpu
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL = 1e-5
-REW_TOL = 1e-9
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _rb_major(se_ue_major):
-    return np.ascontiguousarray(np.swapaxes(se_ue_major, -1, -2))
-
-
-def _compare(env, obs, rew, oenvs, tag):
-    g = {k: x.cpu().numpy() for k, x in env.views().items()}
-    ro = {k: x.cpu().numpy() for k, x in env.raw_observation().items()}
-    goi, goa, grw = obs["obs_inter"].cpu().numpy(), obs["obs_intra"].cpu().numpy(), rew.cpu().numpy()
-    for b, o in enumerate(oenvs):
-        raw = o.raw()
-        for name in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
-            assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (tag, b, name)
-        assert np.array_equal(ro["buffer_occupancies"][b], raw["buffer_occupancies"]), (tag, b)
-        assert np.array_equal(ro["buffer_latencies"][b], raw["buffer_latencies"]), (tag, b)
-        oo = o.obs()
-        np.testing.assert_allclose(goi[b], oo["obs_inter"], rtol=0, atol=OBS_TOL, err_msg=str((tag, b)))
-        np.testing.assert_allclose(goa[b], oo["obs_intra"], rtol=0, atol=OBS_TOL, err_msg=str((tag, b)))
-        np.testing.assert_allclose(grw[b], oo["reward"], rtol=0, atol=REW_TOL, err_msg=str((tag, b)))
 
 
 @pytest.mark.parametrize("se_mode", ["stream", "gather"])
@@ -51,7 +24,7 @@ def test_flagged_device_vs_flagged_oracle(size, se_mode, monkeypatch):
     """One-TTI launches with the caller's scores, multi-TTI launches under MAPF + PF (ranenv_rollout), dense sched_decisions:
     every launch of a flagged handle against the flagged oracle, and an unflagged handle on the same inputs against the default
     one.  (Random allocations rarely land on a disagreement of the two: the next tests provoke them.)"""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
@@ -78,14 +51,12 @@ def test_flagged_device_vs_flagged_oracle(size, se_mode, monkeypatch):
         env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us, n_scenarios=tabs.n_scenarios,
                             max_steps=steps, flags=_lib.F_SCALE_PER_ELEMENT if flagged else 0)
         env.load_scenarios(tabs)
-        env.bind_se_pool(torch.as_tensor(_rb_major(se_pool), device=env.device))
+        env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
         env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
         env.set_episodes(scenario=scen, se_base=np.arange(B) * steps, se_len=steps, trf_base=np.arange(B) * steps, trf_len=steps)
-        ocfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=steps)
-        oenvs = []
-        for b in range(B):
-            o = pyoracle.OracleEnv(ocfg); o.set_scale_per_element(flagged); o.set_scenario(tabs, int(scen[b]))
-            o.reset(se_pool[b * steps]); oenvs.append(o)
+        oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps, per_element=flagged)
+        for b, o in enumerate(oenvs):
+            o.reset(se_pool[b * steps])
         env.reset()
         envs[flagged] = (env, oenvs)
     assert envs[True][0].se_mode == ("gather" if se_mode == "gather" else "stream")
@@ -105,7 +76,7 @@ def test_flagged_device_vs_flagged_oracle(size, se_mode, monkeypatch):
                     start, count, _ = o.action_format(sc_ext[b], ic_ext[b], want_dense=False)
                     for u in range(U):
                         dense[b, u, start[u]:start[u] + count[u]] = 1
-                tiles = np.stack([_rb_major(se_pool[b * steps + t][None])[0] for b in range(B)])
+                tiles = np.stack([rb_major(se_pool[b * steps + t][None])[0] for b in range(B)])
                 obs, rew, _ = env.step_dense(dense, trf[[b * steps + t for b in range(B)]].astype(np.float64), tiles)
                 for b, o in enumerate(oenvs):
                     o.step(sc_ext[b], ic_ext[b], se_pool[b * steps + t], trf[b * steps + t])
@@ -119,7 +90,7 @@ def test_flagged_device_vs_flagged_oracle(size, se_mode, monkeypatch):
                 for b, o in enumerate(oenvs):
                     for j in range(k):
                         o.step(o.policy_mapf(), ic, se_pool[b * steps + t + j], trf[b * steps + t + j])
-            _compare(env, obs, rew, oenvs, (size, se_mode, "flag" if flagged else "default", what, t))
+            assert_matches_oracle(env, obs, rew, oenvs, (size, se_mode, "flag" if flagged else "default", what, t))
         t += k
     for env, _ in envs.values():
         env.close()
@@ -132,7 +103,7 @@ def test_range_launches_where_the_conventions_disagree(se_mode, monkeypatch):
     slice every RB and round-robin splits them -- 5 UEs x 27 RBs of SE 5.0, or 1 UE x 135 RBs of SE 3.0 / 6.0, are such cases.  The
     candidates are found with the oracle (both conventions, one step each); the device then steps them in ranges (env.step, the
     one-TTI build) and must follow the flagged oracle with the flag and the default oracle without."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
@@ -173,18 +144,18 @@ def test_range_launches_where_the_conventions_disagree(se_mode, monkeypatch):
         env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us, n_scenarios=tabs.n_scenarios,
                             max_steps=8, flags=_lib.F_SCALE_PER_ELEMENT if flagged else 0)
         env.load_scenarios(tabs)
-        env.bind_se_pool(torch.as_tensor(_rb_major(tiles), device=env.device))
+        env.bind_se_pool(torch.as_tensor(rb_major(tiles), device=env.device))
         env.set_episodes(scenario=np.array([c[0] for c in cases]), se_base=np.array([c[2] for c in cases]), se_len=1)
         env.set_policy(0, 255)
-        oenvs = []
-        for sc_i, sl, ti in cases:
-            o = pyoracle.OracleEnv(ocfg); o.set_scale_per_element(flagged); o.set_scenario(tabs, sc_i); o.reset(tiles[ti]); oenvs.append(o)
+        oenvs = oracle_envs(tabs, [c[0] for c in cases], (S, U, R, G, Us), 8, per_element=flagged)
+        for o, (_, _, ti) in zip(oenvs, cases):
+            o.reset(tiles[ti])
         env.reset()
         for t in range(3):
             obs, rew, _ = env.step(scores, icb, trf)
             for b, o in enumerate(oenvs):
                 o.step(scores[b], icb[b], tiles[cases[b][2]], trf[b])
-            _compare(env, obs, rew, oenvs, (se_mode, "flag" if flagged else "default", t))
+            assert_matches_oracle(env, obs, rew, oenvs, (se_mode, "flag" if flagged else "default", t))
         got = env.views()["pkt_throughputs"].cpu().numpy().astype(np.float64)
         if flagged:
             with_flag = got
@@ -197,7 +168,7 @@ def test_range_launches_where_the_conventions_disagree(se_mode, monkeypatch):
 def test_the_packet_the_two_conventions_disagree_on():
     """BW 100 MHz, R 135, SE 1.0 on 54 RBs from RB 77, 512-bit packets: 54e8 / 135 = 4e7 bits exactly; the scaled sum gives
     78 125 packets, the sum of scaled elements 78 124 (each 1e8 / 135 product is rounded down a little).  Dense launches."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios

@@ -9,21 +9,11 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.common import comparable_views, poisson_traffic_rows
+from tests.common import OBS_TOL, REW_TOL, oracle_envs, poisson_traffic_rows, rb_major
+from tests.gpu_common import LOOSE_SE_MEAN, assert_same_state, bench_like, comparable_views, need_gpu, short_episode_setup
 from tests.synth import se_tile
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL, REW_TOL = 1e-5, 1e-9
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def _rb_major(a):
-    return np.ascontiguousarray(np.swapaxes(a, -1, -2))
 
 
 @pytest.mark.parametrize("shape", [dict(U=7, R=5), dict(U=37, R=100), dict(U=100, R=135), dict(U=128, R=300),
@@ -32,7 +22,7 @@ def test_gather_sidecars_are_numpy_means_and_the_transposed_pool(shape):
     """row_mean[tile][u] must be np.mean(SE[u, :]) of the float32 tile in float64 -- numpy's pairwise order, every
     shape of it -- bit for bit (the oracle's orc_np_sum is the checker); ue_major is the tile transposed, rows
     zero-padded to a multiple of 8."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from oracle import pyoracle
     U, R = shape["U"], shape["R"]
@@ -40,7 +30,7 @@ def test_gather_sidecars_are_numpy_means_and_the_transposed_pool(shape):
     n_tiles = 9
     pool = np.stack([se_tile(11, t, U, R) for t in range(n_tiles)])          # [tiles, U, R]
     env = BatchedRanEnv(batch=2, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=1, max_ues_slice=Us, n_scenarios=1, max_steps=4)
-    env.bind_se_pool(torch.as_tensor(_rb_major(pool), device=env.device))
+    env.bind_se_pool(torch.as_tensor(rb_major(pool), device=env.device))
     env.set_se_mode("gather")
     sc = env.se_sidecars()
     mean, um = sc["row_mean"].cpu().numpy(), sc["ue_major"].cpu().numpy()
@@ -55,20 +45,12 @@ def test_gather_sidecars_are_numpy_means_and_the_transposed_pool(shape):
     env.close()
 
 
-def _bench_like(B, gather, seed=10, n_traces=16, trace_len=24, steps=1000):
-    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
-    wl = make_mult_slice_workload(B, torch.device("cuda", 0), n_scenarios=32, n_traces=n_traces, trace_len=trace_len,
-                                  seed=seed, max_steps=steps)
-    wl.env.set_se_mode("gather" if gather else "stream")      # (explicit: the RANENV_SE_MODE knob may have switched it at bind)
-    return wl
-
-
 def test_gather_equals_stream_at_full_size():
     """BASELINE configs[2] (B 4096, S 10 / U 100 / R 135, MAPF + PF) stepped 40 TTIs in both SE modes -- step by step and
     as a rollout over 3 partitions: every state array, observation and reward must be bit-identical."""
-    _need_gpu()
+    need_gpu()
     B, T = 4096, 40
-    a, b, c = _bench_like(B, False), _bench_like(B, True), _bench_like(B, True)
+    a, b, c = bench_like(B, False), bench_like(B, True), bench_like(B, True)
     assert (a.env.se_mode, b.env.se_mode) == ("stream", "gather")
     a.env.reset(); b.env.reset(); c.env.reset()
     assert torch.equal(a.env.obs_inter, b.env.obs_inter) and torch.equal(a.env.obs_intra, b.env.obs_intra)
@@ -97,9 +79,9 @@ def test_gather_equals_stream_at_full_size():
 def test_gather_mode_keeps_streaming_for_explicit_tiles_and_dense_steps():
     """In gather mode a step with explicit se_tiles and a dense step still read whole rows (streaming kernel): same
     results as an env in stream mode; rebinding a pool falls back to stream."""
-    _need_gpu()
+    need_gpu()
     B = 6
-    a, b = _bench_like(B, False, steps=8), _bench_like(B, True, steps=8)
+    a, b = bench_like(B, False, steps=8), bench_like(B, True, steps=8)
     U, R, S = a.env.U, a.env.R, a.env.S
     rng = np.random.default_rng(3)
     a.env.set_policy(0, 255); b.env.set_policy(0, 255)
@@ -110,7 +92,7 @@ def test_gather_mode_keeps_streaming_for_explicit_tiles_and_dense_steps():
         if t % 3 == 0:      # pooled tile
             a.env.step(sc, ic); b.env.step(sc, ic)
         elif t % 3 == 1:    # explicit tile
-            se = torch.as_tensor(np.stack([_rb_major(se_tile(77 + t, e, U, R)) for e in range(B)]), device=a.env.device)
+            se = torch.as_tensor(np.stack([rb_major(se_tile(77 + t, e, U, R)) for e in range(B)]), device=a.env.device)
             a.env.step(sc, ic, se_tiles=se); b.env.step(sc, ic, se_tiles=se)
         else:               # dense decision made from the pooled tile's allocation of the other env
             st, cn = a.env.views()["rb_start"].cpu().numpy(), a.env.views()["rb_count"].cpu().numpy()
@@ -134,10 +116,9 @@ def test_two_halves_stepped_alternately_with_scores_from_the_callers_stream(se_m
     of a half are produced from that half's last observation (a stand-in policy: a function of the observation, so any
     ordering slip between the streams changes the numbers) -- on the caller's one stream (events join the streams) or on
     the half's own stream (range_stream: stream order alone) --, 30 TTIs, against the oracle."""
-    _need_gpu()
+    need_gpu()
     import contextlib
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
-    from oracle import pyoracle
     S, U, R, G, Us, B, steps = 10, 100, 135, 1, 10, 48, 30
     tabs = generate_scaled_scenarios(6, seed=4)
     rng = np.random.default_rng(17)
@@ -150,7 +131,7 @@ def test_two_halves_stepped_alternately_with_scores_from_the_callers_stream(se_m
     env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us,
                         n_scenarios=tabs.n_scenarios, max_steps=steps)
     env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(_rb_major(se_pool), device=env.device))
+    env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
     env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
     env.set_episodes(scenario=scen, se_base=se_trace * trace_len, se_len=trace_len, se_offset=se_off,
                      trf_base=np.arange(B) * trace_len, trf_len=trace_len)
@@ -160,11 +141,9 @@ def test_two_halves_stepped_alternately_with_scores_from_the_callers_stream(se_m
     ranges = env.set_ranges(2)
     assert ranges == [(0, 24), (24, 48)]
     on = (lambda k: torch.cuda.stream(env.range_stream(k))) if policy_on == "range" else (lambda k: contextlib.nullcontext())
-    cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=steps)
-    oenvs = []
-    for b in range(B):
-        o = pyoracle.OracleEnv(cfg); o.set_scenario(tabs, int(scen[b]))
-        o.reset(se_pool[se_trace[b] * trace_len + se_off[b]]); oenvs.append(o)
+    oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps)
+    for b, o in enumerate(oenvs):
+        o.reset(se_pool[se_trace[b] * trace_len + se_off[b]])
     env.reset()
 
     def policy_dev(obs_inter):               # [n, S*10] float32 -> [n, S] float64 in [-1, 1], on the current stream
@@ -227,9 +206,9 @@ def test_two_halves_stepped_alternately_with_scores_from_the_callers_stream(se_m
 
 
 def test_step_range_argument_checks():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
-    wl = _bench_like(8, False, steps=4)
+    wl = bench_like(8, False, steps=4)
     env = wl.env
     with pytest.raises(RanEnvError, match="set_ranges"):
         env.step_async(0)
@@ -254,10 +233,9 @@ def test_device_policy_with_a_random_intra_choice_every_step():
     """ranenv_step(scores = NULL, intra_choice = X_t) with fixed_intra = PER_SLICE: MAPF scores on the device, the
     caller picks every slice's scheduler anew every TTI.  An allocation made ahead at the end of TTI t would have used
     X_t for TTI t+1."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
     from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
-    from oracle import pyoracle
     S, U, R, G, Us, B, steps = 5, 25, 135, 5, 5, 32, 24
     tabs = generate_scaled_scenarios(6, seed=3, n_slices=S, n_ues=U, max_ues_slice=Us, min_slices=3, min_ues=2)
     rng = np.random.default_rng(5)
@@ -268,14 +246,13 @@ def test_device_policy_with_a_random_intra_choice_every_step():
         env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us,
                             n_scenarios=tabs.n_scenarios, max_steps=steps)
         env.load_scenarios(tabs)
-        env.bind_se_pool(torch.as_tensor(_rb_major(se_pool), device=env.device))
+        env.bind_se_pool(torch.as_tensor(rb_major(se_pool), device=env.device))
         env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
         env.set_episodes(scenario=scen, se_base=np.arange(B) * steps, se_len=steps, trf_base=np.arange(B) * steps, trf_len=steps)
         env.set_policy(policy, 255)
-        cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=steps)
-        oenvs = []
-        for b in range(B):
-            o = pyoracle.OracleEnv(cfg); o.set_scenario(tabs, int(scen[b])); o.reset(se_pool[b * steps]); oenvs.append(o)
+        oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps)
+        for b, o in enumerate(oenvs):
+            o.reset(se_pool[b * steps])
         env.reset()
         for t in range(steps):
             ic = rng.integers(0, 3, (B, S)).astype(np.uint8)
@@ -296,7 +273,7 @@ def test_device_policy_with_a_random_intra_choice_every_step():
 def test_head_reward_of_the_terminal_transition_survives_the_device_autoreset():
     """HeadVecEnv with device auto-reset must hand SB3 the reward of the terminal transition, not the reward of the
     freshly reset state: same rewards (and dones) as the host-side reset path at every step, including `done` steps."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.adapters import HeadVecEnv
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
 
@@ -332,34 +309,6 @@ def test_head_reward_of_the_terminal_transition_survives_the_device_autoreset():
 
 
 # ---------------------------------------------------------------------------------------------- compact steps
-def _short_episode_setup(B, steps, idle_traffic, se_mode="stream", flags=0):
-    """B envs over a table of 6 episodes that alternate between scenarios (a UE idle in one episode is in a slice in the
-    next), `steps` TTIs per episode, auto-reset on the device, MAPF + PF."""
-    from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
-    from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
-    S, U, R, G, Us = 5, 25, 135, 5, 5
-    tabs = generate_scaled_scenarios(6, seed=3, n_slices=S, n_ues=U, max_ues_slice=Us, min_slices=3, min_ues=2)
-    rng = np.random.default_rng(23)
-    n_ep, L = 6, steps
-    se_pool = np.stack([se_tile(81 + ep, t, U, R) for ep in range(n_ep) for t in range(L)])
-    trf = np.concatenate([poisson_traffic_rows(tabs, ep % tabs.n_scenarios, rng, L) for ep in range(n_ep)])
-    if idle_traffic:                       # bits for every UE, in a slice or not
-        trf = trf + rng.poisson(3, trf.shape) * 1e6
-    env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us, n_scenarios=tabs.n_scenarios,
-                        max_steps=steps, flags=flags)
-    env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(_rb_major(se_pool), device=env.device))
-    env.bind_traffic_pool(torch.as_tensor(trf.astype(np.int32), device=env.device))
-    ep = np.arange(n_ep)
-    env.set_episode_table(scenario=ep % tabs.n_scenarios, se_base=ep * L, se_len=L, trf_base=ep * L, trf_len=L)
-    env.set_policy(2, 1)
-    if se_mode == "gather":
-        env.set_se_mode("gather")
-    start = np.arange(B) % n_ep
-    env.enable_autoreset(0, n_ep, episode_numbers=start)
-    return env, tabs, se_pool, trf, start, (S, U, R, G, Us, n_ep, L)
-
-
 @pytest.mark.parametrize("steps,idle_traffic,se_mode", [(4, False, "stream"), (4, False, "gather"), (13, False, "stream"),
                                                          (4, True, "stream"), (13, True, "gather")])
 def test_compact_steps_against_the_oracle_through_scenario_changes(steps, idle_traffic, se_mode):
@@ -368,10 +317,10 @@ def test_compact_steps_against_the_oracle_through_scenario_changes(steps, idle_t
     a UE that sat out an episode comes back with exactly the zeros it would have pushed into its window (MAPF and PF read
     it).  With bits for idle UEs in the pool the steps must stay full width: those UEs queue, age and drop packets like
     the reference's.  Everything against the oracle, which steps every UE every TTI."""
-    _need_gpu()
+    need_gpu()
     from oracle import pyoracle
     B = 12
-    env, tabs, se_pool, trf, start, (S, U, R, G, Us, n_ep, L) = _short_episode_setup(B, steps, idle_traffic, se_mode)
+    env, tabs, se_pool, trf, start, (S, U, R, G, Us, n_ep, L) = short_episode_setup(B, steps, idle_traffic, se_mode)
     cfg = pyoracle.make_cfg(S, U, R, G, Us, max_steps=10 ** 6)
     oenvs, cur, tstep = [], start.copy(), np.zeros(B, dtype=int)
     for b in range(B):
@@ -409,27 +358,17 @@ def test_compact_steps_against_the_oracle_through_scenario_changes(steps, idle_t
 def test_compact_and_full_width_steps_agree_at_full_size(monkeypatch):
     """BASELINE configs[2] for 30 TTIs with compact steps (default) and with RANENV_COMPACT=0: identical state,
     observations and rewards; only the mean SE of UEs outside every slice (read by nobody) is not kept up."""
-    _need_gpu()
-    a = _bench_like(4096, False)
+    need_gpu()
+    a = bench_like(4096, False)
     monkeypatch.setenv("RANENV_COMPACT", "0")
-    b = _bench_like(4096, False)
+    b = bench_like(4096, False)
     monkeypatch.delenv("RANENV_COMPACT")
     a.env.reset(); b.env.reset()
     a.env.set_partitions(3)
     a.env.rollout(30)
     for _ in range(30):
         b.env.step()
-    torch.cuda.synchronize()
-    scen = torch.as_tensor(a.scenario, device=a.env.device)
-    in_slice = torch.as_tensor(a.tables.ue_slice >= 0, device=a.env.device)[scen]
-    for k, x in a.env.views().items():
-        y = b.env.views()[k]
-        if k == "se_mean":
-            assert torch.equal(x[in_slice], y[in_slice]), k
-        else:
-            assert torch.equal(x, y), k
-    assert torch.equal(a.env.obs_inter, b.env.obs_inter) and torch.equal(a.env.obs_intra, b.env.obs_intra)
-    assert torch.equal(a.env.reward, b.env.reward)
+    assert_same_state(a.env, b.env, a.tables, "compact / full width", loose=LOOSE_SE_MEAN, outputs=("obs_inter", "obs_intra", "reward"))
     a.env.close(); b.env.close()
 
 
@@ -439,10 +378,10 @@ def test_ranges_with_device_autoreset_equal_whole_batch_steps(se_mode):
     stream (ranenv_autoreset_part).  Same numbers as env.step() with auto-reset (checked against the oracle elsewhere): state,
     observations, terminal observations, rewards and done flags at every TTI, three episodes of 5 TTIs per env, the
     scenario changing at every reset."""
-    _need_gpu()
+    need_gpu()
     envs = []
     for _ in range(2):
-        env, tabs, se_pool, trf, start, dims = _short_episode_setup(16, 5, False, se_mode)
+        env, tabs, se_pool, trf, start, dims = short_episode_setup(16, 5, False, se_mode)
         env.reset()
         envs.append(env)
     a, b = envs
@@ -474,11 +413,11 @@ def test_clearing_resets_then_compact_rollouts_then_full_width_steps_keep_the_wi
     scenario where some UE is idle; more than hist_depth compact TTIs follow, then full-width steps (env.step() in the
     streaming mode, or a step with explicit traffic).  The idle UE's catch-up must not give up ring values of the era
     before the clear: win_sent / win_dropped (and everything else) equal those of a handle that never steps compactly."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import F_CLEAR_HISTORY_ON_RESET
     outs = []
     for compact in (1, 0):
-        env, tabs, se_pool, trf, start, (S, U, R, G, Us, n_ep, L) = _short_episode_setup(12, 28, False, se_mode,
+        env, tabs, se_pool, trf, start, (S, U, R, G, Us, n_ep, L) = short_episode_setup(12, 28, False, se_mode,
                                                                                            flags=F_CLEAR_HISTORY_ON_RESET)
         env.set_option("compact", compact)
         assert env.get_option("compact") == compact
@@ -505,9 +444,9 @@ def test_clearing_resets_then_compact_rollouts_then_full_width_steps_keep_the_wi
 
 
 def test_options_are_set_and_read_back_and_unknown_keys_fail():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
-    a = _bench_like(64, False)
+    a = bench_like(64, False)
     env = a.env
     for key, val in (("compact", 0), ("fuse", 7), ("row_width", 16), ("small_batch", 1), ("fuse_first1", 4), ("persist", 1), ("persist_chunk", 7)):
         env.set_option(key, val)
@@ -541,7 +480,7 @@ def test_gather_only_ingest_from_power_equals_pool_then_gather():
     """ranenv_bind_se_gather_from_power (channels/quadriga.py:56-76 for a gather-only user): the sidecars straight from QuaDRiGa
     received power are bit for bit those built from the RB-major pool ranenv_se_from_power writes, a handle without any RB-major
     pool resets / steps / rolls out / auto-resets to the same state, and what needs whole rows says so."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import RanEnvError
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload, quadriga_pool_from_power
     dev = torch.device("cuda", 0)

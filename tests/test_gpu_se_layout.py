@@ -6,19 +6,14 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.common import comparable_views
+from tests.gpu_common import comparable_views, need_gpu
 
 pytestmark = pytest.mark.gpu
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
 @pytest.mark.parametrize("U,R", [(100, 135), (25, 135), (7, 5), (256, 419), (33, 8), (64, 130)])
 def test_retile_quad_is_an_index_transform(U, R):
-    _need_gpu()
+    need_gpu()
     import ctypes as C
     from intent_radio_sched_multi_slice_amd import _lib
     lib = _lib.load()
@@ -42,7 +37,7 @@ def test_retile_quad_is_an_index_transform(U, R):
 def test_quad_pool_equals_rb_major_pool_bit_for_bit(shape, se_mode):
     """reset, step(), rollouts over partitions (launches of several TTIs / persistent launches), a step with the caller's scores, a
     dense step from the pool, auto-reset: the same state, observations and rewards from both layouts."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     outs = []
@@ -81,7 +76,7 @@ def test_quad_pool_equals_rb_major_pool_bit_for_bit(shape, se_mode):
 
 def test_quad_pool_sidecars_and_pooled_tiles():
     """The gather sidecars built from a quad pool are those built from the RB-major pool; pooled_tiles() hands tiles back RB-major."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)
     side = []
@@ -98,7 +93,7 @@ def test_quad_pool_sidecars_and_pooled_tiles():
 
 
 def test_bad_quad_pool_arguments_are_refused():
-    _need_gpu()
+    need_gpu()
     import ctypes as C
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
@@ -119,7 +114,7 @@ def test_one_pool_copy_is_shared_zero_copy_between_workloads(monkeypatch):
     """bench.py keeps ONE copy of the SE pool: a workload built with keep_rb_major=False hands out the RB-quad-major tensor that is
     bound (the RB-major tensor the generator wrote is dropped), a second workload binds that very tensor without copying, and both replay the
     same tiles as a workload that kept the RB-major pool."""
-    _need_gpu()
+    need_gpu()
     monkeypatch.delenv("RANENV_SE_LAYOUT", raising=False)        # (the default layout, whatever the suite's pass presets)
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     dev = torch.device("cuda", 0)

@@ -8,7 +8,7 @@
 4. bit for bit across the launch paths, and nothing else moves when they are switched on;
 5. reset, episode ends, slots, evaluate(), switching off;  6. the error paths.
 
-Bars as everywhere: integers exact, float64 drifts within REW_TOL = 1e-9 per TTI.
+Bars as everywhere: integers exact, float64 drifts within REW_TOL (1e-9) per TTI.
 """
 from __future__ import annotations
 
@@ -19,53 +19,26 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests import slice_metrics_ref as smr  # noqa: E402
-from tests.common import load_golden, tables_from  # noqa: E402
-from tests.synth import se_tile  # noqa: E402
+from tests import slice_metrics_ref as smr
+from tests.common import REW_TOL, load_golden
+from tests.gpu_common import LOOSE_WINDOWS_AND_SE, assert_same_state, device_env_of_run, env_from_eval_fixture, need_gpu
 
 pytestmark = pytest.mark.gpu
 
-REW_TOL = 1e-9
 INT_COLS = [0, 1, 2, 3, 4, 6, 7, 8, 9]
 E_INVALID, E_STATE = -1, -3
-# State of a UE outside every slice: read by no observation and not kept up by compact steps (include/ranenv.h), which a rollout
-# and a step loop choose differently.  Compared for the UEs in a slice.
-_KEYS_LOOSE = ("win_sent", "win_dropped", "se_mean")
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 # ---- 1 / 2: the reference's evaluation code ------------------------------------------------------------------------------------------
-def _env_from_fixture(flags=0, B=2):
-    from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
-    fx = load_golden("eval_metrics")
-    S, U, R, G, Us, seed, steps, n_ep = (int(x) for x in fx["cfg"])
-    tabs = tables_from(fx)
-    env = BatchedRanEnv(batch=B, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G, max_ues_slice=Us, n_scenarios=tabs.n_scenarios,
-                        max_steps=steps, flags=flags)
-    env.load_scenarios(tabs)
-    se = np.stack([np.ascontiguousarray(se_tile(seed + ep, t, U, R).T) for ep in range(n_ep) for t in range(steps)])
-    env.bind_se_pool(torch.as_tensor(se, device=env.device))
-    env.bind_traffic_pool(torch.as_tensor(fx["traffic"].reshape(n_ep * steps, U).astype(np.int32), device=env.device))
-    ep = np.arange(n_ep)
-    env.set_episode_table(scenario=fx["scen_ids"], se_base=ep * steps, se_len=steps, trf_base=ep * steps, trf_len=steps)
-    env.set_policy(2, 1)                                   # MAPF + PF on the device
-    env.enable_autoreset(0, n_ep, episode_numbers=np.zeros(B, dtype=np.int32))
-    return fx, tabs, env, (S, U, R, steps, n_ep)
-
-
 def _msg_sizes(tabs, scen):
     return np.where(tabs.slice_has_req[scen] != 0, tabs.slice_message_size[scen], 0).astype(np.float64)
 
 
 @pytest.mark.parametrize("window", ["live", "restarted"])
 def test_per_tti_shares_equal_the_reference_evaluation_code(window):
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd._lib import F_CLEAR_HISTORY_ON_RESET
-    fx, tabs, env, (S, U, R, steps, n_ep) = _env_from_fixture(F_CLEAR_HISTORY_ON_RESET if window == "restarted" else 0)
+    fx, tabs, env, (S, U, R, steps, n_ep) = env_from_eval_fixture(F_CLEAR_HISTORY_ON_RESET if window == "restarted" else 0)
     sx = load_golden("slice_metrics")
     assert np.array_equal(sx["cfg"], fx["cfg"]) and np.array_equal(sx["scen_ids"], fx["scen_ids"])
     tag = "live_deque" if window == "live" else "restarted_with_reset"
@@ -110,8 +83,8 @@ def test_per_tti_shares_equal_the_reference_evaluation_code(window):
 def test_evaluate_per_slice_is_consistent_with_the_eight_sums():
     """evaluate(per_slice=True) over two partitions: the per-slice columns summed over the slices against the per-env sums of the
     same run, and the result without per_slice is today's dict."""
-    _need_gpu()
-    fx, tabs, env, (S, U, R, steps, n_ep) = _env_from_fixture()
+    need_gpu()
+    fx, tabs, env, (S, U, R, steps, n_ep) = env_from_eval_fixture()
     env.enable_metrics(n_ep)
     env.enable_slice_metrics()
     env.set_partitions(2)
@@ -145,27 +118,12 @@ def test_evaluate_per_slice_is_consistent_with_the_eight_sums():
 
 
 # ---- 3: the oracle on the directed intents -------------------------------------------------------------------------------------------
-def _device_env(run, max_steps=None, flags=0):
-    from intent_radio_sched_multi_slice_amd.batched_env import BatchedRanEnv
-    c, tabs = run["case"], run["tables"]
-    T, B = c["steps"], c["B"]
-    env = BatchedRanEnv(batch=B, n_slices=c["S"], n_ues=c["U"], n_rbs=c["R"], rbs_per_rbg=c["G"], max_ues_slice=c["Us"],
-                        n_scenarios=tabs.n_scenarios, max_steps=T if max_steps is None else max_steps, hist_depth=c["D"],
-                        flags=flags, **c["scalars"])
-    env.load_scenarios(tabs)
-    env.bind_se_pool(torch.as_tensor(np.ascontiguousarray(np.swapaxes(run["se_pool"], -1, -2)), device=env.device))
-    env.bind_traffic_pool(torch.as_tensor(run["trf"].astype(np.int32), device=env.device))
-    env.set_episodes(scenario=run["scen"], se_base=np.arange(B) * T, se_len=T, trf_base=np.arange(B) * T, trf_len=T)
-    env.set_policy(c["policy"], c["intra"])
-    return env
-
-
 @pytest.mark.parametrize("name", smr.DEVICE_CASES)
 def test_directed_case_sums_equal_the_oracle(name):
-    _need_gpu()
+    need_gpu()
     run = smr.run_of(name)
     c = run["case"]
-    env = _device_env(run)
+    env = device_env_of_run(run, flags=0)
     env.enable_metrics(0)
     env.enable_slice_metrics()
     env.reset()
@@ -186,10 +144,10 @@ def test_directed_case_sums_equal_the_oracle(name):
 def test_range_intent_tables_stay_refused_with_slice_metrics_on():
     """RANGE_INTENT_CASE is the oracle's alone: the C ABI refuses a table that declares a metric twice (include/ranenv.h), with
     slice metrics on as without, and the handle goes on summing on the tables it had."""
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import RanEnvError
     run = smr.run_of("ref-overfulfill-0.5")
-    env = _device_env(run)
+    env = device_env_of_run(run, flags=0)
     env.enable_metrics(0)
     env.enable_slice_metrics()
     bad = smr.run_of("range-intent")["tables"]
@@ -261,13 +219,14 @@ def _drive(env, path):
 
 
 def _assert_same(a, b, what):
+    """(not assert_same_state: these are _snapshot dicts of metric sums, of envs that are closed by now)"""
     assert sorted(a) == sorted(b), what
     for k in a:
         assert torch.equal(a[k], b[k]), (what, k, int((a[k] != b[k]).sum()))
 
 
 def test_sums_are_bit_identical_across_launch_paths():
-    _need_gpu()
+    need_gpu()
     _, ref = _mapf_env()
     _drive(ref, "step")
     want = _snapshot(ref)
@@ -288,19 +247,12 @@ def test_sums_are_bit_identical_across_launch_paths():
 def test_nothing_else_moves_when_slice_metrics_are_on(path, parts):
     """Observations, reward, done, every view and the eight sums with slice metrics on are those of the same run without them
     (where the rollout then fuses TTIs into one launch and takes persistent launches, and with them on does neither)."""
-    _need_gpu()
+    need_gpu()
     wl, on = _mapf_env(parts=parts, slice_on=True)
     _, off = _mapf_env(parts=parts, slice_on=False)
     _drive(on, path)
     _drive(off, path)
-    torch.cuda.synchronize()
-    va, vb = on.views(), off.views()
-    in_slice = torch.as_tensor(wl.tables.ue_slice >= 0, device=on.device)[va["episodes"][:, 0].to(torch.int64)]
-    for k in va:
-        x, y = (va[k][in_slice], vb[k][in_slice]) if k in _KEYS_LOOSE else (va[k], vb[k])
-        assert torch.equal(x, y), (k, path)
-    for k in ("obs_inter", "obs_intra", "reward", "done"):
-        assert torch.equal(getattr(on, k), getattr(off, k)), (k, path)
+    assert_same_state(on, off, wl.tables, path, loose=LOOSE_WINDOWS_AND_SE)
     _assert_same(_snapshot(on, False), _snapshot(off, False), path)
     if path == "rollout":
         assert on.get_option("last_rollout_persistent") == 0
@@ -309,7 +261,7 @@ def test_nothing_else_moves_when_slice_metrics_are_on(path, parts):
 
 
 def test_collect_adds_what_the_rollout_under_the_same_nets_adds():
-    _need_gpu()
+    need_gpu()
     from tests import collect_ref as cr
     B, snaps = 24, {}
     for what, parts in (("step", 1), ("rollout", 1), ("collect", 1), ("collect3", 3)):
@@ -332,7 +284,7 @@ def test_collect_adds_what_the_rollout_under_the_same_nets_adds():
 
 
 def test_collect_head_adds_what_the_rollout_under_the_same_head_net_adds():
-    _need_gpu()
+    need_gpu()
     from tests import head_policy_ref as hr
     B, snaps = 24, {}
     for what, parts in (("step", 1), ("rollout", 3), ("collect_head", 1), ("collect_head3", 3)):
@@ -363,7 +315,7 @@ def _plain_env(B=4, max_steps=9, flags=0, **kw):
 
 
 def test_a_masked_reset_zeroes_only_the_masked_envs():
-    _need_gpu()
+    need_gpu()
     _, env = _plain_env(max_steps=100)
     env.enable_metrics(0)
     env.enable_slice_metrics()
@@ -384,7 +336,7 @@ def test_a_masked_reset_zeroes_only_the_masked_envs():
 
 def test_per_env_episode_lengths_slots_and_overflow():
     """max_steps [9, 5, 7, 9], two slots, 18 TTIs in one rollout: env 1 ends three episodes -- the third is only counted."""
-    _need_gpu()
+    need_gpu()
     wl, env = _plain_env()
     eps = env.episodes
     env.set_episode_table(scenario=eps["scenario"], se_base=eps["se_base"], se_len=eps["se_len"], se_offset=eps["se_offset"],
@@ -415,7 +367,7 @@ def test_per_env_episode_lengths_slots_and_overflow():
 
 
 def test_evaluate_twice_and_switching_off():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd.batched_env import RanEnvError
     _, env = _plain_env()
     eps = env.episodes
@@ -458,7 +410,7 @@ def test_evaluate_twice_and_switching_off():
 
 # ---- 6: errors -----------------------------------------------------------------------------------------------------------------------
 def test_error_paths_and_rollout_schedule():
-    _need_gpu()
+    need_gpu()
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.batched_env import RanEnvError
     _, env = _plain_env(B=8, max_steps=1000)

@@ -5,7 +5,6 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -13,10 +12,9 @@ import pytest
 torch = pytest.importorskip("torch")
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
 
-from intent_radio_sched_multi_slice_amd import _lib, adapters  # noqa: E402
-from tests import head_policy_ref as hr  # noqa: E402
+from intent_radio_sched_multi_slice_amd import _lib, adapters
+from tests import head_policy_ref as hr
 
 S, B, SEED = 5, 77, 0x0123_4567_89AB_CDEF
 

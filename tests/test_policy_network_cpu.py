@@ -11,8 +11,8 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from intent_radio_sched_multi_slice_amd import _lib, adapters  # noqa: E402
-from intent_radio_sched_multi_slice_amd.batched_env import policy_net_layers  # noqa: E402
+from intent_radio_sched_multi_slice_amd import _lib, adapters
+from intent_radio_sched_multi_slice_amd.batched_env import policy_net_layers
 
 
 def _seq(dims, act=torch.nn.Tanh):

@@ -9,51 +9,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from intent_radio_sched_multi_slice_amd import adapters  # noqa: E402
-from intent_radio_sched_multi_slice_amd.batched_env import policy_net_layers  # noqa: E402
-from tests import policy_ref as pr  # noqa: E402
-
-# (S, Us, B, inter hidden widths, inter activation, intra hidden widths, intra activation, intra layout, stochastic):
-# the grid of tests/test_gpu_policy_network_shapes.py
-GRID = [
-    (10, 10, 33, [7], "relu", [1], "tanh", "obs", False),
-    (5, 10, 100, [512, 1, 512], "tanh", [33, 512, 96, 7], "relu", "mask_obs", True),
-    (1, 1, 1, [32], "tanh", [96], "tanh", "obs", True),
-    (16, 16, 31, [160, 480], "relu", [511], "relu", "mask_obs", False),
-    (13, 5, 100, [100, 255, 64], "tanh", [480, 160], "tanh", "obs", True),
-    (10, 10, 100, [511], "relu", [7, 33], "relu", "obs", True),
-    (5, 10, 31, [256, 256], "tanh", [64, 64, 64, 64], "tanh", "mask_obs", False),
-    (16, 16, 33, [33], "tanh", [100, 1], "relu", "obs", True),
-    (13, 5, 1, [96, 96, 96], "relu", [255], "tanh", "mask_obs", True),
-    (1, 1, 100, [480], "tanh", [32, 160], "relu", "mask_obs", False),
-    (10, 10, 31, [512, 512], "tanh", [1, 512, 1], "relu", "obs", False),
-    (5, 10, 33, [64, 7, 255, 33], "tanh", [1], "relu", "obs", True),
-]
-
-
-def make_net(dims, act, seed, gain=1.0):
-    """A torch.nn.Sequential MLP with uniform(+-gain / sqrt(fan_in)) weights and biases."""
-    g = torch.Generator().manual_seed(seed)
-    mods = []
-    for i in range(len(dims) - 1):
-        lin = torch.nn.Linear(dims[i], dims[i + 1])
-        with torch.no_grad():
-            bound = gain / np.sqrt(dims[i])
-            lin.weight.copy_((torch.rand(lin.weight.shape, generator=g) * 2 - 1) * bound)
-            lin.bias.copy_((torch.rand(lin.bias.shape, generator=g) * 2 - 1) * bound)
-        mods.append(lin)
-        if i < len(dims) - 2:
-            mods.append(torch.nn.Tanh() if act == "tanh" else torch.nn.ReLU())
-    return torch.nn.Sequential(*mods)
-
-
-def make_inter_net(S, widths, act, seed):
-    """An inter-slice net whose log_std outputs sit around -1, as a trained policy's do (std well below 1, so that the
-    noise moves the scores without clamping most of them)."""
-    net = make_net([10 * S] + list(widths) + [2 * S], act, seed)
-    with torch.no_grad():
-        net[-1].bias[S:] -= 1.0
-    return net
+from intent_radio_sched_multi_slice_amd import adapters
+from intent_radio_sched_multi_slice_amd.batched_env import policy_net_layers
+from tests import policy_ref as pr
+from tests.gpu_common import GRID, make_inter_net, make_net      # the grid of tests/test_gpu_policy_network_shapes.py
 
 
 def _case(cfg, seed=0):

@@ -12,7 +12,7 @@ torch = pytest.importorskip("torch")
 
 from intent_radio_sched_multi_slice_amd import comm_env
 from tests.common import GOLDEN
-from tests.test_gpu_reference_agents import replay_fixture
+from tests.agents_common import replay_fixture
 
 
 def _oracle_device():

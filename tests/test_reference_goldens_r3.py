@@ -180,7 +180,7 @@ def test_reference_result_scripts_read_this_builds_history_files(tmp_path, monke
     import importlib.util
     from intent_radio_sched_multi_slice_amd import comm_env
     from intent_radio_sched_multi_slice_amd.history import HIST_KEYS
-    from tests.test_gpu_reference_agents import _Agent
+    from tests.agents_common import _Agent
     spec = importlib.util.spec_from_file_location("gen_golden_agents", os.path.join(GOLDEN, "gen_golden_agents.py"))
     gga = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gga)          # defines OracleDevice; its main() (which needs the reference) is not run
