@@ -1,6 +1,6 @@
 """The reference's PPO loop in miniature with the host out of sample collection: `collect()` leaves a whole training batch on the GPU.
 
-    python examples/train_ppo_on_device.py [--batch 4096] [--ttis 64] [--iters 10] [--epochs 4] [--minibatch 65536]
+    python examples/train_ppo_on_device.py [--batch 4096] [--ttis 64] [--iters 10] [--epochs 4] [--minibatch 65536] [--non-shared]
 
 The reference trains IBSched with RLlib PPO + GAE (agents/ray_agent.py:154-166,301-375): two shared policies -- the inter-slice agent
 ("player_0", masked diagonal Gaussian over S scores) and the intra-slice agents ("player_{s+1}", Discrete(3)) -- each a
@@ -14,7 +14,8 @@ FullyConnectedNetwork with a value branch.  Here per iteration:
   3. `set_policy_network` / `set_value_network` with the new weights.
 
 An example of the API, not a tuned trainer: minibatches are far larger than the reference's 64 so that the SGD side does not drown
-the measurement in tiny kernels.  Prints env-steps/s with the updates included, the share of collection in it, and the mean
+the measurement in tiny kernels.  `--non-shared` is the reference's `shared_policies=False` (agents/ray_agent.py:432-460): S intra
+actor / critic pairs, pair s trained on slice s's rows and on column s + 1 of logp / vf / adv / vtarg, bound as lists.  Prints env-steps/s with the updates included, the share of collection in it, and the mean
 inter-slice reward per iteration.
 """
 import argparse
@@ -54,6 +55,7 @@ def main():
     ap.add_argument("--minibatch", type=int, default=65536)
     ap.add_argument("--episode-len", type=int, default=100)
     ap.add_argument("--se-mode", choices=("stream", "gather"), default="gather")
+    ap.add_argument("--non-shared", action="store_true", help="one intra actor / critic pair per slice instead of one for all")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     B, T, L = args.batch, args.ttis, args.episode_len
@@ -67,15 +69,17 @@ def main():
     env.enable_autoreset(0, n_ep, random_episodes=True, seed=7, episode_numbers=np.arange(B) % n_ep)
 
     torch.manual_seed(0)
-    pi_inter, vf_inter, pi_intra, vf_intra = mlp(10 * S, 2 * S).to(dev), mlp(10 * S, 1).to(dev), mlp(W, 3).to(dev), mlp(W, 1).to(dev)
+    pi_inter, vf_inter = mlp(10 * S, 2 * S).to(dev), mlp(10 * S, 1).to(dev)
+    n_intra = S if args.non_shared else 1          # pair s for slice index s (player_{s+1}), or one pair for every slice
+    pi_intra, vf_intra = [mlp(W, 3).to(dev) for _ in range(n_intra)], [mlp(W, 1).to(dev) for _ in range(n_intra)]
     with torch.no_grad():
         pi_inter[-1].bias[S:].fill_(-0.5)          # initial log_std
-    params = [p for m in (pi_inter, vf_inter, pi_intra, vf_intra) for p in m.parameters()]
+    params = [p for m in (pi_inter, vf_inter, *pi_intra, *vf_intra) for p in m.parameters()]
     opt = torch.optim.Adam(params, lr=LR)
 
     def bind(it):
-        env.set_policy_network(pi_inter, pi_intra, stochastic=True, seed=1000 + it)
-        env.set_value_network(vf_inter, vf_intra)
+        env.set_policy_network(pi_inter, pi_intra if args.non_shared else pi_intra[0], stochastic=True, seed=1000 + it)
+        env.set_value_network(vf_inter, vf_intra if args.non_shared else vf_intra[0])
 
     bind(0)
     env.reset()
@@ -91,20 +95,26 @@ def main():
         obs0, act0 = rec["obs_inter"].reshape(N, 10 * S), rec["action_inter"].reshape(N, S).to(torch.float32)
         mask0 = sorted_action_mask(rec["mask_inter"].reshape(N, S))
         logp0, adv0, vt0 = rec["logp"][..., 0].reshape(N), rec["adv"][..., 0].reshape(N), rec["vtarg"][..., 0].reshape(N)
-        live = (rec["mask_inter"] != 0).reshape(N * S).nonzero().squeeze(1)          # intra rows of active slices only
-        obs1, act1 = rec["obs_intra"].reshape(N * S, W), rec["action_intra"].reshape(N * S).to(torch.int64)
-        logp1, adv1, vt1 = rec["logp"][..., 1:].reshape(N * S), rec["adv"][..., 1:].reshape(N * S), rec["vtarg"][..., 1:].reshape(N * S)
+        # intra rows of active slices only; per pair: all slices' rows (shared), or slice s's rows and columns (non-shared)
+        intra_sets = []
+        for s in (range(S) if args.non_shared else [slice(None)]):
+            cols = slice(1, None) if not args.non_shared else slice(s + 1, s + 2)
+            intra_sets.append(((rec["mask_inter"][:, :, s] != 0).reshape(-1).nonzero().squeeze(1), rec["obs_intra"][:, :, s].reshape(-1, W),
+                               rec["action_intra"][:, :, s].reshape(-1).to(torch.int64), rec["logp"][..., cols].reshape(-1),
+                               rec["adv"][..., cols].reshape(-1), rec["vtarg"][..., cols].reshape(-1)))
         for _ in range(args.epochs):
-            perm0, perm1 = torch.randperm(N, device=dev), live[torch.randperm(live.numel(), device=dev)]
+            perm0 = torch.randperm(N, device=dev)
             n_mb = max(1, N // args.minibatch)
-            for i0, i1 in zip(perm0.chunk(n_mb), perm1.chunk(n_mb)):
+            perms = [live[torch.randperm(live.numel(), device=dev)].chunk(n_mb) for live, *_ in intra_sets]
+            for i0, *i1s in zip(perm0.chunk(n_mb), *perms):
                 out = pi_inter(obs0[i0])
                 mean, std = masked_gaussian_params(out[:, :S], out[:, S:], mask0[i0])
                 dist = torch.distributions.Normal(mean, std)
                 loss = ppo_loss(dist.log_prob(act0[i0]).sum(-1), logp0[i0], (dist.entropy() * mask0[i0]).sum(-1),
                                 vf_inter(obs0[i0])[:, 0], adv0[i0], vt0[i0])
-                cat = torch.distributions.Categorical(logits=pi_intra(obs1[i1]))
-                loss = loss + ppo_loss(cat.log_prob(act1[i1]), logp1[i1], cat.entropy(), vf_intra(obs1[i1])[:, 0], adv1[i1], vt1[i1])
+                for pi, vf, i1, (_, obs1, act1, logp1, adv1, vt1) in zip(pi_intra, vf_intra, i1s, intra_sets):
+                    cat = torch.distributions.Categorical(logits=pi(obs1[i1]))
+                    loss = loss + ppo_loss(cat.log_prob(act1[i1]), logp1[i1], cat.entropy(), vf(obs1[i1])[:, 0], adv1[i1], vt1[i1])
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
                 torch.nn.utils.clip_grad_norm_(params, GRAD_CLIP)

@@ -253,6 +253,31 @@ int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ra
                               void *stream);
 int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra);
 
+/* Non-shared intra policies (the reference's shared_policies=False, agents/ray_agent.py:432-460: one RLlib policy
+ * intra_slice_sched_{s} per slice, player_{s+1} -> intra_slice_sched_{s}): S intra actors / critics instead of one.
+ *
+ *   actors[s] / critics[s] serve slice INDEX s -- player_{s+1}, the index of obs_intra[b][s] and of the uint8 [B][S] intra
+ *     actions; not the sorted position.  n must equal S.  n == 0 with a NULL array unbinds that per-slice set; unbinding the
+ *     actors unbinds the per-slice critics with them.
+ *   Each net is validated as ranenv_set_policy_network's intra net / ranenv_set_value_network's intra critic, and all n must
+ *     agree in n_hidden, dims, activation and input_layout (RLlib builds them from one model config); anything else is
+ *     RANENV_E_INVALID.  Every validation error precedes every device call; the handle changes on success only.  The copies go
+ *     into a packed buffer of the set's own, the S nets at equal stride (an outgrown buffer lives until ranenv_destroy).
+ *   ranenv_set_intra_policy_networks needs a bound inter net (ranenv_set_policy_network; else RANENV_E_STATE) and acts with
+ *     that call's stochastic and seed.  While per-slice actors are bound they stand where the shared intra net stands: the step
+ *     reads the nets' intra choices, ranenv_get_policy_actions returns the intra pointer, obs_intra is required.  A later
+ *     ranenv_set_policy_network says what the intra policy is through its intra argument, NULL included: it unbinds both
+ *     per-slice sets.  A later ranenv_set_value_network unbinds the per-slice critics only.
+ *   Critics of either kind need a bound intra actor of either kind with the same input_layout (RANENV_E_INVALID).  A shared
+ *     actor with per-slice critics and per-slice actors with a shared critic are both valid.
+ *   The intra launch of a TTI then has S x ceil(envs / 32) workgroups, each on 32 envs' rows of ONE slice with that slice's
+ *     weights -- still one launch per TTI, partition and agent kind -- in ranenv_step / _step_range / _step_part, ranenv_rollout
+ *     and ranenv_collect alike.  Arithmetic, noise counters, the record and its log-probabilities are those above: S copies of
+ *     one net give bit for bit what that net gives as the shared one.  Option "collect_split" = -1 weighs one slice's actor +
+ *     critic (what the co-resident workgroups of a launch walk). */
+int ranenv_set_intra_policy_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *actors, void *stream);
+int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *critics, void *stream);
+
 /* CommunicationEnv.reset for the envs with env_mask[b] != 0 (NULL = all): fresh buffers,
  * step 0, observation of the zero raw state with the episode's first SE tile.
  * Outputs may be NULL. dev_se_tiles: [B][U*R] explicit tiles or NULL to use the pool. */

@@ -164,6 +164,8 @@ FUNCTIONS = {
     "ranenv_replay_sample": (C.c_int, [_P, _I64, C.c_uint64, C.c_uint64, _I32] + [_P] * 7),
     "ranenv_set_sac_critics": (C.c_int, [_P, C.POINTER(Mlp), C.POINTER(Mlp), _P]),
     "ranenv_sac_targets": (C.c_int, [_P, _I64, _P, _P, _P, _F64, _F64, _I32, C.c_uint64, C.c_uint64] + [_P] * 5),
+    "ranenv_set_intra_policy_networks": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), _P]),
+    "ranenv_set_intra_value_networks": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), _P]),
 }
 EXPORTS = tuple(FUNCTIONS)
 

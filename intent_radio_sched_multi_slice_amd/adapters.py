@@ -309,8 +309,9 @@ def ibsched_policy_actions(obs_inter, mask_inter, inter, obs_intra=None, mask_in
              0 and 1 at counter (env_ids + b, episode[b], step[b], POLICY_TAG + position), key = seed;
       intra: argmax of the 3 logits (lowest index on ties), or the categorical draw of Philox word 2 at (..., POLICY_TAG + slice).
     ``env_ids`` / ``episode`` / ``step``: [B] (the env's id base + index, views' episode_number and step_number before the TTI).
+    ``intra`` may be a list of S nets (non-shared intra policies): slice index s's rows go through ``intra[s]``.
     Returns (scores float64 [B, S], intra uint8 [B, S] or None) as CPU tensors."""
-    from .batched_env import policy_net_layers
+    from .batched_env import per_slice_nets, policy_net_layers
     obs_inter = torch.as_tensor(obs_inter).detach().cpu().to(torch.float32)
     B, S = obs_inter.shape[0], obs_inter.shape[1] // 10
     layers, act = policy_net_layers(inter, activation, 10 * S, 2 * S)
@@ -338,8 +339,18 @@ def ibsched_policy_actions(obs_inter, mask_inter, inter, obs_intra=None, mask_in
         x = torch.cat([torch.as_tensor(mask_intra).cpu().reshape(B * S, Us).to(torch.float32), x], dim=1)
     elif intra_input != "obs":
         raise ValueError("intra_input must be 'obs' or 'mask_obs'")
-    il, iact = policy_net_layers(intra, activation, x.shape[1], 3)
-    lg = _mlp_forward(x, [(w.cpu(), b.cpu()) for w, b in il], iact).reshape(B, S, 3)
+    nets = per_slice_nets(intra)
+    if nets is None:
+        il, iact = policy_net_layers(intra, activation, x.shape[1], 3)
+        lg = _mlp_forward(x, [(w.cpu(), b.cpu()) for w, b in il], iact).reshape(B, S, 3)
+    else:
+        if len(nets) != S:
+            raise ValueError(f"{len(nets)} intra nets given: one per slice is {S}")
+        per = []
+        for s, net in enumerate(nets):
+            il, iact = policy_net_layers(net, activation, x.shape[1], 3)
+            per.append(_mlp_forward(x.reshape(B, S, -1)[:, s], [(w.cpu(), b.cpu()) for w, b in il], iact))
+        lg = torch.stack(per, dim=1)
     if not stochastic:
         l0, l1, l2 = lg[..., 0], lg[..., 1], lg[..., 2]
         ch = (l1 > l0).to(torch.uint8)
@@ -417,6 +428,21 @@ def gae(reward, vf, done, gamma: float = 0.99, lam: float = 0.95):
         vtarg[t] = (a + v[t]).astype(np.float32)
         a_next = a
     return adv, vtarg
+
+
+def rllib_per_slice_layers(weights_by_policy, S: int, policy_prefix: str = "intra_slice_sched_"):
+    """The S intra policies of a non-shared IBSched checkpoint (agents/ray_agent.py:432-460) from ``{policy_id: state_dict}`` as
+    ``Algorithm.get_weights()`` returns it: ``(actors, critics)``, two lists of S layer stacks in slice order -- entry s from
+    policy ``{policy_prefix}{s}``, which acts for ``player_{s+1}`` -- read with ``rllib_fcnet_layers`` /
+    ``rllib_fcnet_value_layers``.  A missing policy raises KeyError naming it."""
+    actors, critics = [], []
+    for s in range(int(S)):
+        name = f"{policy_prefix}{s}"
+        if name not in weights_by_policy:
+            raise KeyError(name)
+        actors.append(rllib_fcnet_layers(weights_by_policy[name]))
+        critics.append(rllib_fcnet_value_layers(weights_by_policy[name]))
+    return actors, critics
 
 
 def rllib_fcnet_value_layers(state_dict, prefix: str = "internal_model."):

@@ -101,6 +101,33 @@ def policy_net_layers(net, activation: Optional[str] = None, in_dim: Optional[in
     return out, activation
 
 
+def _depth(x) -> int:
+    """Dimensions of a tensor, an array or a nested list, by its first entries"""
+    if isinstance(x, (torch.Tensor, np.ndarray)):
+        return x.ndim
+    return 1 + _depth(x[0]) if isinstance(x, (list, tuple)) and len(x) > 0 else int(isinstance(x, (list, tuple)))
+
+
+def _is_layer(x) -> bool:
+    """A ``(W, b)`` pair: a 2-D weight and a 1-D bias (tensors, arrays or nested lists)"""
+    return isinstance(x, (list, tuple)) and len(x) == 2 and [_depth(x[0]), _depth(x[1])] == [2, 1]
+
+
+def per_slice_nets(intra):
+    """``intra`` as a list of nets, one per slice index, when it is one -- a list or tuple whose entries are themselves nets: modules,
+    or lists of ``(W, b)`` pairs -- else None: a single net (which may itself be a list of ``(W, b)`` pairs) or None.  Decided by
+    where the ``(W, b)`` pairs sit, whatever holds the numbers: a single net's first entry is a pair, a list of nets' first entry
+    is a list whose first entry is one."""
+    if not isinstance(intra, (list, tuple)) or len(intra) == 0:
+        return None
+    first = intra[0]
+    if isinstance(first, torch.nn.Module):
+        return list(intra)
+    if not _is_layer(first) and isinstance(first, (list, tuple)) and len(first) > 0 and _is_layer(first[0]):
+        return list(intra)
+    return None
+
+
 class BatchedRanEnv:
     def __init__(self, batch: int, n_slices: int, n_ues: int, n_rbs: int, rbs_per_rbg: int = 1,
                  max_ues_slice: Optional[int] = None, n_scenarios: int = 1, bandwidth_hz: float = 100e6,
@@ -156,6 +183,7 @@ class BatchedRanEnv:
         self.term_obs_inter = self.term_obs_intra = self.term_head_obs = None
         self.se_mode = "stream"
         self._ranges = None          # set_ranges(): [(lo, hi)] for step_async / step_wait
+        self._intra_layout = None    # input layout of the intra actor bound by set_policy_network (None: none)
         # (the views are handed out once, here: ranenv_get_views ends the library's host shadow of the step counters -- the views are writable --,
         # and a first views() call in the middle of an auto-reset loop would switch the shortcut of enable_autoreset off until the next full reset)
         self.views()
@@ -341,10 +369,16 @@ class BatchedRanEnv:
         ``inter`` -> 2*S outputs (mean, log_std of the masked Gaussian), ``intra`` (None = ``fixed_intra``) -> 3 logits per
         (env, slice) from ``obs_intra`` ("obs") or ``[mask_intra, obs_intra]`` ("mask_obs", RLlib's flattened Dict).  Nets as
         for ``policy_net_layers``.  Switches the policy to NETWORK: ``step()`` / ``rollout()`` / ``evaluate()`` then need no
-        actions.  ``stochastic``: sample (Philox noise keyed by ``seed``) instead of taking the mode."""
+        actions.  ``stochastic``: sample (Philox noise keyed by ``seed``) instead of taking the mode.
+        ``intra`` may be a list of S nets of one shape, non-shared intra policies (the reference's ``shared_policies=False``):
+        ``intra[s]`` serves slice index s, i.e. ``player_{s+1}`` (ranenv_set_intra_policy_networks)."""
         in_inter, in_intra = self.net_input_dims(intra_input)
+        per_slice = self._net_list(per_slice_nets(intra), activation, in_intra, 3, NET_INPUTS[intra_input])
         self._set_nets("policy_net", "ranenv_set_policy_network", [(inter, activation, in_inter, 2 * self.S, NET_IN_OBS),
-                       (intra, activation, in_intra, 3, NET_INPUTS[intra_input])], 1 if stochastic else 0, int(seed) & (2 ** 64 - 1))
+                       (None if per_slice else intra, activation, in_intra, 3, NET_INPUTS[intra_input])], 1 if stochastic else 0,
+                       int(seed) & (2 ** 64 - 1))
+        self._set_net_list("intra_policy_nets", "ranenv_set_intra_policy_networks", per_slice)
+        self._intra_layout = None if intra is None else NET_INPUTS[intra_input]
         self._policy_views = None
         self.set_policy(POLICY_NETWORK, self.fixed_intra if fixed_intra is None else fixed_intra)
 
@@ -373,13 +407,48 @@ class BatchedRanEnv:
             self._check(getattr(self._lib, call)(self._h, *structs, *args, self._stream()), call)
         self._keep[key] = keep                 # (the library copies on the current stream; keep the sources until it has)
 
+    def _net_list(self, nets, activation, in_dim, out_dim, layout):
+        """A list of S nets as the argument of a ``ranenv_set_intra_*_networks`` call: ``(array of ranenv_mlp pointers, what to
+        keep alive)``, or None for None.  Raises ValueError -- before any library call: a per-slice bind is two of
+        them, and the first one drops the previous set -- unless there are S valid nets of one shape and activation."""
+        if nets is None:
+            return None
+        if len(nets) != self.S:
+            raise ValueError(f"{len(nets)} intra nets given: one per slice is {self.S}")
+        keep, structs, first = [], [], None
+        for i, net in enumerate(nets):
+            layers, act = policy_net_layers(net, activation, in_dim, out_dim)
+            shape = ([tuple(w.shape) for w, _ in layers], act)
+            first = shape if first is None else first
+            if shape != first:
+                raise ValueError(f"intra net {i} ({shape[0]}, {shape[1]}) differs from net 0 ({first[0]}, {first[1]}): "
+                                 "the nets per slice have one shape and one activation")
+            structs.append(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep))
+        return (C.POINTER(_lib.Mlp) * len(structs))(*[C.pointer(m) for m in structs]), keep + structs
+
+    def _set_net_list(self, key: str, call: str, net_list):
+        self._keep.pop(key, None)              # (the call in front of this one has unbound the set)
+        if net_list is None:
+            return
+        with torch.cuda.device(self.device):
+            self._check(getattr(self._lib, call)(self._h, self.S, net_list[0], self._stream()), call)
+        self._keep[key] = net_list[1]
+
     def set_value_network(self, inter, intra=None, activation: Optional[str] = None):
         """Bind the critics that ``collect()`` evaluates beside the actors (ranenv_set_value_network): ``inter`` maps the
         inter-slice observation [10*S] to one value, ``intra`` (None = no intra critic: those columns of ``vf`` are 0) the
         intra actor's input row -- the layout given to ``set_policy_network`` -- to one value per (env, slice).  Nets as for
-        ``policy_net_layers``.  Bind the actors first when there is an intra critic; re-binding either pair leaves the other."""
-        self._set_nets("value_net", "ranenv_set_value_network", [(inter, activation, 10 * self.S, 1, NET_IN_OBS), (intra, activation, None, 1,
-                       lambda layers: NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS)])
+        ``policy_net_layers``.  Bind the actors first when there is an intra critic; re-binding either pair leaves the other.
+        ``intra`` may be a list of S critics of one shape, ``intra[s]`` for slice index s (ranenv_set_intra_value_networks), with
+        shared or per-slice intra actors alike."""
+        layout = lambda layers: NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS  # noqa: E731
+        per_slice = self._net_list(per_slice_nets(intra), activation, None, 1, layout)
+        if per_slice is not None and self._intra_layout != per_slice[0][0].contents.input_layout:
+            raise ValueError("intra critics per slice read the intra actor's input row: " + (
+                "no intra actor is bound (set_policy_network)" if self._intra_layout is None else "its intra_input is the other layout"))
+        self._set_nets("value_net", "ranenv_set_value_network", [(inter, activation, 10 * self.S, 1, NET_IN_OBS),
+                       (None if per_slice else intra, activation, None, 1, layout)])
+        self._set_net_list("intra_value_nets", "ranenv_set_intra_value_networks", per_slice)
 
     TRAJECTORY_SHAPES = {      # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S, Us, W)
         "obs_inter": (torch.float32, 0, lambda B, S, Us, W: (B, 10 * S)), "obs_intra": (torch.float32, 0, lambda B, S, Us, W: (B, S, W)),

@@ -92,6 +92,11 @@ struct ranenv {
     // ranenv_set_policy_network (inter, intra) and ranenv_set_value_network (their critics); ranenv_set_head_policy_network /
     // _head_value_network: SchedTWC / SchedColORAN's actor and critic on the head observation; ranenv_set_sac_critics (q1, q2)
     NetSlot actor, value, head, head_value, sac;
+    // ranenv_set_intra_policy_networks / _intra_value_networks: S intra actors / critics, one per slice index, at equal stride in the
+    // slot's buffer (`a` describes slice 0's copy and carries the stride).  While on they stand where actor.b / value.b stand.
+    NetSlot actor_ps, value_ps;
+    const PolicyNet *intra_actor() const { return actor_ps.on ? &actor_ps.a : (actor.on && actor.has_b ? &actor.b : nullptr); }
+    const PolicyNet *intra_critic() const { return value_ps.on ? &value_ps.a : (value.on && value.has_b ? &value.b : nullptr); }
     // ... and the actions the step reads under RANENV_POLICY_NETWORK / _HEAD_NETWORK (shared: one policy acts at a time)
     int net_stochastic = 0; unsigned long long net_seed = 0;
     double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
@@ -1193,9 +1198,9 @@ static int net_use(ranenv_handle h, KP &kp)
     if (kp.scores || h->kp.policy != RANENV_POLICY_NETWORK) return 0;
     if (!h->actor.on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
     if (!kp.obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
-    if (h->actor.has_b && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
+    if (h->intra_actor() && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
     kp.scores = h->d_net_scores;
-    if (h->actor.has_b) { kp.intra = h->d_net_intra; kp.fixed_intra = RANENV_INTRA_PER_SLICE; }
+    if (h->intra_actor()) { kp.intra = h->d_net_intra; kp.fixed_intra = RANENV_INTRA_PER_SLICE; }
     return 1;
 }
 
@@ -1225,7 +1230,7 @@ static PolicyIO net_io(ranenv_handle h, const KP &kp)
 static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
 {
     if (head_policy(h)) return launch_head_policy(s, h->head.a, net_io(h, kp), e0, n);
-    return launch_policy(s, h->actor.a, h->actor.has_b ? &h->actor.b : nullptr, net_io(h, kp), e0, n);
+    return launch_policy(s, h->actor.a, h->intra_actor(), net_io(h, kp), e0, n);
 }
 
 // The buffers the nets' actions go to and the step reads them from (IBSched nets and head nets share them: one policy acts at a time)
@@ -1244,14 +1249,73 @@ int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ra
     const int rc = net_set(h, h->actor, {inter, NET_INTER}, {intra, NET_INTRA}, (hipStream_t)stream, [&] { return net_action_buffers(h); });
     if (rc != RANENV_OK) return rc;
     h->net_stochastic = stochastic != 0; h->net_seed = seed;
+    h->actor_ps.on = h->value_ps.on = false;      // (`intra`, NULL included, says what the intra policy is now)
     return RANENV_OK;
+}
+
+// ranenv_set_intra_policy_networks / _intra_value_networks: n = S nets of one shape into `slot`'s buffer at equal stride, by net_set's
+// rules -- every validation error precedes every HIP call, the buffer grows (the outgrown one stays until ranenv_destroy) or is zeroed,
+// the slot changes on success only
+static int net_set_per_slice(ranenv_handle h, ranenv::NetSlot &slot, int32_t n, const ranenv_mlp *const *nets, NetRole role, hipStream_t s)
+{
+    const char *who = NET_ROLES[role].who;
+    if (n != h->cfg.n_slices) return fail(h, RANENV_E_INVALID, "%s nets per slice: %d given, the handle has %d slices", who, n, h->cfg.n_slices);
+    if (!nets) return fail(h, RANENV_E_INVALID, "%s nets per slice: null array", who);
+    PolicyNet net{};
+    for (int32_t i = 0; i < n; i++) {
+        const ranenv_mlp *m = nets[i], *m0 = nets[0];
+        if (!m) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d is null", who, i);
+        PolicyNet ni{};
+        long long floats = 0;
+        const int rc = net_layout(h, m, role, ni, floats);
+        if (rc != RANENV_OK) return rc;
+        bool same = m->n_hidden == m0->n_hidden && m->activation == m0->activation && m->input_layout == m0->input_layout;
+        for (int l = 0; same && l <= m->n_hidden + 1; l++) same = m->dims[l] == m0->dims[l];
+        if (!same) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d differs from net 0 in shape, activation or input layout", who, i);
+        if (i == 0) { net = ni; net.slice_stride = floats; }
+    }
+    const long long total = net.slice_stride * n;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (total > slot.cap) {
+        const int rc = dev_alloc(h, &slot.w, (size_t)total);
+        if (rc != RANENV_OK) return rc;
+        slot.cap = total;
+    } else {
+        HIP_TRY(h, hipMemsetAsync(slot.w, 0, sizeof(float) * (size_t)total, s));
+    }
+    net.w = slot.w;
+    for (int32_t i = 0; i < n; i++) {
+        const int rc = net_copy(h, nets[i], net, s, slot.w + (size_t)i * (size_t)net.slice_stride);
+        if (rc != RANENV_OK) return rc;
+    }
+    slot.a = net; slot.b = PolicyNet{}; slot.has_b = false; slot.on = true;
+    return RANENV_OK;
+}
+
+int ranenv_set_intra_policy_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *actors, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n == 0 && !actors) { h->actor_ps.on = h->value_ps.on = false; return RANENV_OK; }
+    if (!h->actor.on) return fail(h, RANENV_E_STATE, "intra policy nets per slice need a bound inter net (ranenv_set_policy_network)");
+    return net_set_per_slice(h, h->actor_ps, n, actors, NET_INTRA, (hipStream_t)stream);
+}
+
+int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *critics, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n == 0 && !critics) { h->value_ps.on = false; return RANENV_OK; }
+    const PolicyNet *ia = h->intra_actor();
+    if (!ia) return fail(h, RANENV_E_INVALID, "intra value nets need a bound intra policy net (ranenv_set_policy_network / ranenv_set_intra_policy_networks)");
+    if (n == h->cfg.n_slices && critics && critics[0] && critics[0]->input_layout != ia->layout)
+        return fail(h, RANENV_E_INVALID, "intra value nets: input layout %d, the intra policy net has %d", critics[0]->input_layout, ia->layout);
+    return net_set_per_slice(h, h->value_ps, n, critics, NET_INTRA_VALUE, (hipStream_t)stream);
 }
 
 int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra)
 {
     if (!h || !dev_scores || !dev_intra) return fail(h, RANENV_E_INVALID, "null argument");
     if (!h->actor.on && !h->head.on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
-    *dev_scores = h->d_net_scores; *dev_intra = (h->actor.on && h->actor.has_b) ? h->d_net_intra : nullptr;
+    *dev_scores = h->d_net_scores; *dev_intra = (h->actor.on && h->intra_actor()) ? h->d_net_intra : nullptr;
     return RANENV_OK;
 }
 
@@ -1259,10 +1323,13 @@ int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ran
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice value net is required (intra may be NULL)");
-    if (intra && !(h->actor.on && h->actor.has_b)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
-    if (intra && intra->input_layout != h->actor.b.layout)
-        return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, h->actor.b.layout);
-    return net_set(h, h->value, {inter, NET_INTER_VALUE}, {intra, NET_INTRA_VALUE}, (hipStream_t)stream);
+    const PolicyNet *ia = h->intra_actor();
+    if (intra && !(h->actor.on && ia)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
+    if (intra && intra->input_layout != ia->layout)
+        return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, ia->layout);
+    const int rc = net_set(h, h->value, {inter, NET_INTER_VALUE}, {intra, NET_INTRA_VALUE}, (hipStream_t)stream);
+    if (rc == RANENV_OK) h->value_ps.on = false;      // (`intra`, NULL included, says what the intra critic is now)
+    return rc;
 }
 
 int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int32_t dist, const float *dev_log_std, int32_t stochastic,
@@ -1683,7 +1750,7 @@ static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kp
 {
     const bool head = head_policy(h);
     const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, Us = (size_t)h->cfg.max_ues_slice, W = 2 * Us + 9, C = (size_t)tr.rec.cols;
-    const bool ia = !head && h->actor.has_b, vc = tr.rec.vf != nullptr, ic = vc && !head && h->value.has_b;
+    const bool ia = !head && h->intra_actor(), vc = tr.rec.vf != nullptr, ic = vc && !head && h->intra_critic();
     auto slot = [&](auto *p, size_t stride) { return p ? p + (size_t)t * B * stride : nullptr; };
     PolicyRec rec{};
     rec.vf = slot(tr.rec.vf, C);
@@ -1700,11 +1767,12 @@ static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kp
         rec.logp = slot(tr.rec.logp, C);
         rec.intra_actor = ia ? 1 : 0;
     }
-    const PolicyNet &actor = head ? h->head.a : h->actor.a, *intra = ia ? &h->actor.b : nullptr;
-    const PolicyNet *critic = vc ? (head ? &h->head_value.a : &h->value.a) : nullptr, *vintra = ic ? &h->value.b : nullptr;
+    const PolicyNet &actor = head ? h->head.a : h->actor.a, *intra = ia ? h->intra_actor() : nullptr;
+    const PolicyNet *critic = vc ? (head ? &h->head_value.a : &h->value.a) : nullptr, *vintra = ic ? h->intra_critic() : nullptr;
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
-    // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").
-    if (!critic_only) rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, h->actor.b, vintra) << 1 : 0);
+    // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").  Nets per
+    // slice count with one slice's copy: the co-resident workgroups of a sliced launch mostly walk one slice's weights.
+    if (!critic_only) rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, *intra, vintra) << 1 : 0);
     const PolicyIO io = net_io(h, kpk);
     return head ? launch_head_policy_collect(s, actor, critic, io, rec, e0, n) : launch_policy_collect(s, actor, intra, critic, vintra, io, rec, e0, n);
 }
@@ -1886,7 +1954,7 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
     if (h->kp.policy != RANENV_POLICY_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect needs policy NETWORK (ranenv_set_policy)");
     if (!h->actor.on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
     if (!h->value.on) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
-    if (h->value.has_b && !(h->actor.has_b && h->actor.b.layout == h->value.b.layout))
+    if (h->intra_critic() && !(h->intra_actor() && h->intra_actor()->layout == h->intra_critic()->layout))
         return fail(h, RANENV_E_STATE, "the intra value net was bound for another intra policy net (bind it again, ranenv_set_value_network)");
     Record ppo;
     ppo.rec.obs_inter = traj->obs_inter; ppo.rec.obs_intra = traj->obs_intra; ppo.rec.mask_inter = traj->mask_inter; ppo.rec.mask_intra = traj->mask_intra;

@@ -177,6 +177,8 @@ struct PolicyNet {
     int act;                              // RANENV_ACT_*
     int layout;                           // RANENV_NET_IN_*
     int in_dim, out_dim;                  // unpadded
+    long long slice_stride;               // sliced intra launches (non-shared intra policies): floats between two consecutive slices' packed
+                                          // copies, slice s's at w + s * slice_stride; 0 = one net for all slices.  Read by no other kernel
 };
 // One launch's inputs and action outputs.  A head policy's launch (RANENV_POLICY_HEAD_NETWORK: one row per env, scores into the same
 // buffer) has the bound head observation [B][10*S] as its obs_inter and reads no masks.
@@ -203,7 +205,8 @@ struct PolicyRec {
     int critic_only;                      // the pass behind the last TTI: no actors, no record, vf of the observation as it stands
     int split;                            // host side only: bit 0 / 1 = the inter (head) / intra critic runs as a launch of its own behind the actor's
 };
-// Enqueue the inter net (and the intra net when `intra` is non-null) / the head actor for envs [e0, e0 + n_envs).
+// Enqueue the inter net (and the intra net when `intra` is non-null) / the head actor for envs [e0, e0 + n_envs).  An intra net with a
+// slice_stride -- in the recording launches: or an intra critic with one -- takes the sliced kernels (one workgroup column per slice).
 hipError_t launch_policy(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &, int e0, int n_envs);
 hipError_t launch_head_policy(hipStream_t, const PolicyNet &actor, const PolicyIO &, int e0, int n_envs);
 // The recording launches of one TTI: actor + critic stack per agent kind in one launch each (`vinter` / `vintra` / `critic` null = no

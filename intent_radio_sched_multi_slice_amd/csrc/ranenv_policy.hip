@@ -58,16 +58,16 @@ __device__ __forceinline__ void load_dense_rows(const float *src, long long firs
 }
 
 // Observation rows of `net`'s input -> LDS (zeros beyond the input and beyond the launch's rows).  REC: the rows are written to the
-// record's slot on the way (the observation the TTI's action is computed from).
-template <bool REC>
+// record's slot on the way (the observation the TTI's action is computed from).  SLICED (kind 1): row g is (env e0 + g, slice `sl`).
+template <bool REC, bool SLICED = false>
 __device__ __forceinline__ void net_load_rows(const PolicyNet &net, const PolicyIO &io, const PolicyRec &rec, int kind, int e0, int row0, int n_rows,
-                                              float *cur, int tid)
+                                              float *cur, int tid, int sl = 0)
 {
     load_rows(net.kp[0], 0, 0, cur, tid, [&](int r, int k) {
         const int g = row0 + r;
         if (kind == 0) return dense_at(io.obs_inter, REC ? rec.obs_inter : nullptr, e0 + g, e0 + n_rows, 10 * io.S, net.in_dim, k);
         if (g >= n_rows || k >= net.in_dim) return 0.0f;
-        const size_t es = (size_t)e0 * io.S + g;
+        const size_t es = SLICED ? (size_t)(e0 + g) * io.S + sl : (size_t)e0 * io.S + g;
         const int ko = net.layout == RANENV_NET_IN_MASK_OBS ? k - io.Us : k;
         if (ko < 0) return (float)io.mask_intra[es * io.Us + k];
         const float v = io.obs_intra[es * io.W + ko];
@@ -76,14 +76,14 @@ __device__ __forceinline__ void net_load_rows(const PolicyNet &net, const Policy
     });
 }
 
-// The layers of `net` on the 32 rows in `cur`; on return `cur` holds the output layer's rows (stride net_ld(np[last])).
-__device__ __forceinline__ void net_layers(const PolicyNet &net, float *&cur, float *&nxt, int lane, int wave)
+// The layers of `net`, its packed copy at `wb`, on the 32 rows in `cur`; on return `cur` holds the output layer's rows (stride net_ld(np[last])).
+__device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb, float *&cur, float *&nxt, int lane, int wave)
 {
     const int q = lane >> 4, c = lane & 15;
     for (int l = 0; l < net.n_layers; l++) {
         const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N);
         const bool last = l == net.n_layers - 1;
-        const float *W = net.w + net.w_off[l], *bias = net.w + net.b_off[l];
+        const float *W = wb + net.w_off[l], *bias = wb + net.b_off[l];
         for (int nt = wave; nt < N / 32; nt += 4) {
             f32x4 acc[2][2];
 #pragma unroll
@@ -128,6 +128,7 @@ __device__ __forceinline__ void net_layers(const PolicyNet &net, float *&cur, fl
         float *t = cur; cur = nxt; nxt = t;
     }
 }
+__device__ __forceinline__ void net_layers(const PolicyNet &net, float *&cur, float *&nxt, int lane, int wave) { net_layers(net, net.w, cur, nxt, lane, wave); }
 
 constexpr double HALF_LN_2PI = 0.9189385332046727;      // 0.5 ln(2 pi)
 constexpr double LN_1E9 = 20.72326583694641;            // ln(1e9): -ln of the masked positions' std
@@ -173,13 +174,19 @@ __device__ __forceinline__ int active_slices(const PolicyIO &io, int e)
 // REC (ranenv_collect / ranenv_collect_head): the same actor forward and epilogue -- the actions do not differ by a bit -- which also
 // writes the TTI's record (observation and mask rows on their way into LDS; unclamped action, log-probability beside the handle's action
 // buffers), then the critic `vnet` (n_layers 0 = none) on the same 32 rows, re-read from L2, through the same two LDS buffers.
-template <bool HEAD, bool REC>
+// SLICED (compile time; kind 1, non-shared intra policies): a grid of S x tiles workgroups, tiles = ceil(n_rows / 32) with n_rows = envs.
+// Workgroup sl * tiles + tile owns slice sl of envs e0 + 32 tile .. + 31 -- row g = 32 tile + r of the launch is (env e0 + g, slice sl) --
+// and reads slice sl's copy of each net, net.w + sl * net.slice_stride (stride 0: one net for all slices).  Slice-major numbering: the
+// workgroups resident at one time mostly walk one slice's weights (measured against tile * S + sl: never slower, 7 % faster with [512] x 3
+// nets at B 16 384 S 5).
+template <bool HEAD, bool REC, bool SLICED = false>
 __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNet &vnet, const PolicyIO &io, const PolicyRec &rec, int kind, int e0,
                                             int n_rows, float *lds)
 {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row0 = (int)blockIdx.x * NET_ROWS;
     const int S = io.S;
+    const int tiles = SLICED ? (n_rows + NET_ROWS - 1) / NET_ROWS : 1, sl = SLICED ? (int)blockIdx.x / tiles : 0;
+    const int row0 = (SLICED ? (int)blockIdx.x - sl * tiles : (int)blockIdx.x) * NET_ROWS;
     int ldm = net_ld_max(net);
     if (REC && vnet.n_layers > 0) { const int lv = net_ld_max(vnet); ldm = lv > ldm ? lv : ldm; }
     float *cur = lds, *nxt = lds + NET_ROWS * ldm;
@@ -192,13 +199,13 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         if (kind == 1 && rec.mask_intra)
             for (int i = tid; i < NET_ROWS * io.Us; i += 256)
                 if (row0 + i / io.Us < n_rows) {
-                    const size_t o = ((size_t)e0 * S + row0) * io.Us + i;
+                    const size_t o = SLICED ? ((size_t)(e0 + row0 + i / io.Us) * S + sl) * io.Us + i % io.Us : ((size_t)e0 * S + row0) * io.Us + i;
                     rec.mask_intra[o] = io.mask_intra[o];
                 }
     }
-    net_load_rows<REC>(net, io, rec, kind, e0, row0, n_rows, cur, tid);
+    net_load_rows<REC, SLICED>(net, io, rec, kind, e0, row0, n_rows, cur, tid, sl);
     __syncthreads();
-    net_layers(net, cur, nxt, lane, wave);
+    net_layers(net, SLICED ? net.w + sl * net.slice_stride : net.w, cur, nxt, lane, wave);
 
     // ---- epilogue: actions ----------------------------------------------------------------------------------------------
     const int ld = net_ld(net.np[net.n_layers - 1]);
@@ -261,8 +268,8 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         for (int r = tid; r < NET_ROWS; r += 256) {
             const int g = row0 + r;
             if (g >= n_rows) continue;
-            const size_t es = (size_t)e0 * S + g;
-            const int e = (int)(es / (size_t)S), s = (int)(es - (size_t)e * S);
+            const size_t es = SLICED ? (size_t)(e0 + g) * S + sl : (size_t)e0 * S + g;
+            const int e = SLICED ? e0 + g : (int)(es / (size_t)S), s = SLICED ? sl : (int)(es - (size_t)e * S);
             const float l0 = cur[r * ld], l1 = cur[r * ld + 1], l2 = cur[r * ld + 2];
             int ch = 0;
             if (!io.stochastic) {
@@ -296,9 +303,9 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         __syncthreads();                               // (the epilogue read both buffers)
         cur = lds; nxt = lds + NET_ROWS * ldm;
         const PolicyRec none{};
-        net_load_rows<false>(vnet, io, none, kind, e0, row0, n_rows, cur, tid);
+        net_load_rows<false, SLICED>(vnet, io, none, kind, e0, row0, n_rows, cur, tid, sl);
         __syncthreads();
-        net_layers(vnet, cur, nxt, lane, wave);
+        net_layers(vnet, SLICED ? vnet.w + sl * vnet.slice_stride : vnet.w, cur, nxt, lane, wave);
         const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
         for (int r = tid; r < NET_ROWS; r += 256) {
             const int g = row0 + r;
@@ -309,8 +316,8 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                 if (!HEAD && !rec.intra_critic)
                     for (int s = 0; s < S; s++) out[1 + s] = 0.0f;
             } else {
-                const size_t es = (size_t)e0 * S + g;
-                const size_t e = es / (size_t)S;
+                const size_t es = SLICED ? (size_t)(e0 + g) * S + sl : (size_t)e0 * S + g;
+                const size_t e = SLICED ? (size_t)(e0 + g) : es / (size_t)S;
                 rec.vf[e * rec.cols + 1 + (es - e * S)] = cur[r * ldv];
             }
         }
@@ -327,6 +334,19 @@ __global__ void __launch_bounds__(256) ranenv_policy_collect_kernel(PolicyNet ne
 {
     extern __shared__ float lds[];
     policy_body<false, true>(net, vnet, io, rec, kind, e0, n_rows, lds);
+}
+
+// Non-shared intra policies: the intra launch (kind 1) with one workgroup column per slice; n_envs rows per slice
+__global__ void __launch_bounds__(256) ranenv_policy_sliced_kernel(PolicyNet net, PolicyIO io, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, false, true>(net, net, io, PolicyRec{}, 1, e0, n_envs, lds);
+}
+
+__global__ void __launch_bounds__(256) ranenv_policy_sliced_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, true, true>(net, vnet, io, rec, 1, e0, n_envs, lds);
 }
 
 __global__ void __launch_bounds__(256) ranenv_head_policy_kernel(PolicyNet net, PolicyIO io, int e0, int n_rows)
@@ -434,16 +454,21 @@ hipError_t lds_attr()
 
 dim3 grid_of(int rows) { return dim3((unsigned)((rows + NET_ROWS - 1) / NET_ROWS)); }
 
+// An intra launch is sliced -- rows = envs, S x tiles workgroups -- when its actor or its critic has a copy per slice
+bool sliced(const PolicyNet &a, const PolicyNet *v) { return a.slice_stride != 0 || (v && v->slice_stride != 0); }
+dim3 grid_sliced(int n_envs, int S) { return dim3((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS) * (unsigned)S); }
+
 // One agent kind's recording launch(es) of a TTI: actor + critic `vp` (null: none) fused, or -- split -- the actor's launch, then the
-// critic alone (the kernel's critic_only mode)
-template <bool HEAD>
+// critic alone (the kernel's critic_only mode).  SLICED: rows = envs (see policy_body).
+template <bool HEAD, bool SLICED = false>
 void collect_launch(hipStream_t s, int kind, const PolicyNet &a, const PolicyNet *vp, const PolicyIO &io, const PolicyRec &rec, int e0, int rows,
                     bool split)
 {
     const PolicyNet none{};               // (n_layers 0: no critic)
     auto launch = [&](const PolicyNet &v, const PolicyRec &rc) {
         const size_t x = ranenv_dev::policy_lds_bytes(a), y = v.n_layers > 0 ? ranenv_dev::policy_lds_bytes(v) : 0, lds = x > y ? x : y;
-        if constexpr (HEAD) hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid_of(rows), dim3(256), lds, s, a, v, io, rc, e0, rows);
+        if constexpr (SLICED) hipLaunchKernelGGL(ranenv_policy_sliced_collect_kernel, grid_sliced(rows, io.S), dim3(256), lds, s, a, v, io, rc, e0, rows);
+        else if constexpr (HEAD) hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid_of(rows), dim3(256), lds, s, a, v, io, rc, e0, rows);
         else hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid_of(rows), dim3(256), lds, s, a, v, io, rc, kind, e0, rows);
     };
     if (!split || rec.critic_only || !vp) return launch(vp ? *vp : none, rec);
@@ -463,7 +488,11 @@ hipError_t launch_policy(hipStream_t s, const PolicyNet &inter, const PolicyNet 
 {
     if (const hipError_t attr = lds_attr<ranenv_policy_kernel>(); attr != hipSuccess) return attr;
     hipLaunchKernelGGL(ranenv_policy_kernel, grid_of(n_envs), dim3(256), policy_lds_bytes(inter), s, inter, io, 0, e0, n_envs);
-    if (intra) hipLaunchKernelGGL(ranenv_policy_kernel, grid_of(n_envs * io.S), dim3(256), policy_lds_bytes(*intra), s, *intra, io, 1, e0, n_envs * io.S);
+    if (intra && sliced(*intra, nullptr)) {
+        if (const hipError_t attr = lds_attr<ranenv_policy_sliced_kernel>(); attr != hipSuccess) return attr;
+        hipLaunchKernelGGL(ranenv_policy_sliced_kernel, grid_sliced(n_envs, io.S), dim3(256), policy_lds_bytes(*intra), s, *intra, io, e0, n_envs);
+    } else if (intra)
+        hipLaunchKernelGGL(ranenv_policy_kernel, grid_of(n_envs * io.S), dim3(256), policy_lds_bytes(*intra), s, *intra, io, 1, e0, n_envs * io.S);
     return hipGetLastError();
 }
 
@@ -472,7 +501,13 @@ hipError_t launch_policy_collect(hipStream_t s, const PolicyNet &inter, const Po
 {
     if (const hipError_t attr = lds_attr<ranenv_policy_collect_kernel>(); attr != hipSuccess) return attr;
     if (!rec.critic_only || vinter) collect_launch<false>(s, 0, inter, vinter, io, rec, e0, n_envs, (rec.split & 1) != 0);
-    if (intra && (!rec.critic_only || vintra)) collect_launch<false>(s, 1, *intra, vintra, io, rec, e0, n_envs * io.S, (rec.split & 2) != 0);
+    if (intra && (!rec.critic_only || vintra)) {
+        if (sliced(*intra, vintra)) {
+            if (const hipError_t attr = lds_attr<ranenv_policy_sliced_collect_kernel>(); attr != hipSuccess) return attr;
+            collect_launch<false, true>(s, 1, *intra, vintra, io, rec, e0, n_envs, (rec.split & 2) != 0);
+        } else
+            collect_launch<false>(s, 1, *intra, vintra, io, rec, e0, n_envs * io.S, (rec.split & 2) != 0);
+    }
     return hipGetLastError();
 }
 
