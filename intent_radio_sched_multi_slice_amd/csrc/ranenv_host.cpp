@@ -8,7 +8,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -87,16 +86,16 @@ struct ranenv {
     size_t prof_used = 0;
     long long prof_ttis = 0;       // TTIs covered by the launches timed since ranenv_profile_begin
     long long prof_env_ttis = 0;   // env-TTIs covered by the launches timed since ranenv_profile_begin
-    // The nets of one ranenv_set_*_network call, packed in a buffer of their own: an outgrown buffer stays allocated until ranenv_destroy
-    struct NetSlot { PolicyNet a{}, b{}; bool on = false, has_b = false; float *w = nullptr; long long cap = 0; };      // cap: floats
-    // ranenv_set_policy_network (inter, intra) and ranenv_set_value_network (their critics); ranenv_set_head_policy_network /
-    // _head_value_network: SchedTWC / SchedColORAN's actor and critic on the head observation; ranenv_set_sac_critics (q1, q2)
-    NetSlot actor, value, head, head_value, sac;
-    // ranenv_set_intra_policy_networks / _intra_value_networks: S intra actors / critics, one per slice index, at equal stride in the
-    // slot's buffer (`a` describes slice 0's copy and carries the stride).  While on they stand where actor.b / value.b stand.
-    NetSlot actor_ps, value_ps;
-    const PolicyNet *intra_actor() const { return actor_ps.on ? &actor_ps.a : (actor.on && actor.has_b ? &actor.b : nullptr); }
-    const PolicyNet *intra_critic() const { return value_ps.on ? &value_ps.a : (value.on && value.has_b ? &value.b : nullptr); }
+    // One bound net: its layout, and its packed weights in a buffer of the slot's own (cap floats; an outgrown buffer stays allocated
+    // until ranenv_destroy).  A net per slice is S copies of one layout at net.slice_stride in that buffer, `net` describing slice 0's.
+    struct NetSlot { PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; };
+    // ranenv_set_policy_network (actor, actor_intra: the shared intra net) and ranenv_set_intra_policy_networks (actor_ps: one intra net
+    // per slice, standing where the shared one stands while on); the same three for their critics (ranenv_set_value_network,
+    // ranenv_set_intra_value_networks); ranenv_set_head_policy_network / _head_value_network: SchedTWC / SchedColORAN's actor and critic
+    // on the head observation; ranenv_set_sac_critics
+    NetSlot actor, actor_intra, actor_ps, value, value_intra, value_ps, head, head_value, sac_q1, sac_q2;
+    const PolicyNet *intra_actor() const { return actor_ps.on ? &actor_ps.net : (actor_intra.on ? &actor_intra.net : nullptr); }
+    const PolicyNet *intra_critic() const { return value_ps.on ? &value_ps.net : (value_intra.on ? &value_intra.net : nullptr); }
     // ... and the actions the step reads under RANENV_POLICY_NETWORK / _HEAD_NETWORK (shared: one policy acts at a time)
     int net_stochastic = 0; unsigned long long net_seed = 0;
     double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
@@ -1158,30 +1157,55 @@ static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, 
     return RANENV_OK;
 }
 
-// One ranenv_set_*_network call: the slot's nets (`b.m` null: one) validated and laid out -- an error so far precedes every HIP call --
-// then `extra` (what else the setter checks or allocates), then the packed buffer: grown when needed -- the outgrown one stays allocated
-// until ranenv_destroy, the launches of earlier calls may still read it -- else zeroed; the layers are copied.  The slot changes on success only.
-struct NetSrc { const ranenv_mlp *m; NetRole role; };
-static int net_set(ranenv_handle h, ranenv::NetSlot &slot, NetSrc a, NetSrc b, hipStream_t s, const std::function<int()> &extra = nullptr)
+// Binding has two phases, and every ranenv_set_*_network call goes through them in one order: net_plan for all of its nets and its own
+// argument checks -- an error so far precedes every HIP call and leaves every slot as it was --, hipSetDevice, its own allocations,
+// net_commit for all of its nets.
+// PLAN: `copies` nets of one role (one, or one per slice) validated and laid out: net_layout's checks for every copy, and all copies of
+// one shape, activation and input layout.  No HIP call, nothing of the handle changes.
+struct NetBind {
+    ranenv::NetSlot *slot; const ranenv_mlp *const *nets; int copies; NetRole role;
+    PolicyNet net; long long floats;      // the plan: copy 0's layout with the copies' stride (one copy: 0), floats of all copies
+};
+static int net_plan(ranenv_handle h, NetBind *binds, int n)
 {
-    PolicyNet na{}, nb{};
-    long long floats = 0;
-    int rc = net_layout(h, a.m, a.role, na, floats);
-    if (rc == RANENV_OK && b.m) rc = net_layout(h, b.m, b.role, nb, floats);
-    if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (extra && (rc = extra()) != RANENV_OK) return rc;
-    if (floats > slot.cap) {
-        if ((rc = dev_alloc(h, &slot.w, (size_t)floats)) != RANENV_OK) return rc;
-        slot.cap = floats;
-    } else {
-        HIP_TRY(h, hipMemsetAsync(slot.w, 0, sizeof(float) * (size_t)floats, s));
+    for (NetBind *b = binds; b < binds + n; b++) {
+        const char *who = NET_ROLES[b->role].who;
+        long long floats = 0;
+        for (int i = 0; i < b->copies; i++) {
+            const ranenv_mlp *m = b->nets[i], *m0 = b->nets[0];
+            if (!m) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d is null", who, i);
+            PolicyNet ni{};
+            floats = 0;
+            if (const int rc = net_layout(h, m, b->role, ni, floats); rc != RANENV_OK) return rc;
+            bool same = m->n_hidden == m0->n_hidden && m->activation == m0->activation && m->input_layout == m0->input_layout;
+            for (int l = 0; same && l <= m->n_hidden + 1; l++) same = m->dims[l] == m0->dims[l];
+            if (!same) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d differs from net 0 in shape, activation or input layout", who, i);
+            if (i == 0) b->net = ni;
+        }
+        b->net.slice_stride = b->copies > 1 ? floats : 0;
+        b->floats = floats * b->copies;
     }
-    na.w = nb.w = slot.w;
-    rc = net_copy(h, a.m, na, s, slot.w);
-    if (rc == RANENV_OK && b.m) rc = net_copy(h, b.m, nb, s, slot.w);
-    if (rc != RANENV_OK) return rc;
-    slot.a = na; slot.b = nb; slot.has_b = b.m != nullptr; slot.on = true;
+    return RANENV_OK;
+}
+
+// COMMIT, on the caller's stream without a host sync: every slot's buffer grown -- the outgrown one stays allocated, the launches of
+// earlier calls may still read it -- or zeroed over the new nets' extent; then every copy's layers; then the slots change, all or none.
+static int net_commit(ranenv_handle h, NetBind *binds, int n, hipStream_t s)
+{
+    for (NetBind *b = binds; b < binds + n; b++) {
+        ranenv::NetSlot &slot = *b->slot;
+        if (b->floats > slot.cap) {
+            if (const int rc = dev_alloc(h, &slot.w, (size_t)b->floats); rc != RANENV_OK) return rc;
+            slot.cap = b->floats;
+        } else {
+            HIP_TRY(h, hipMemsetAsync(slot.w, 0, sizeof(float) * (size_t)b->floats, s));
+        }
+        b->net.w = slot.w;
+    }
+    for (NetBind *b = binds; b < binds + n; b++)
+        for (int i = 0; i < b->copies; i++)
+            if (const int rc = net_copy(h, b->nets[i], b->net, s, b->slot->w + (size_t)i * (size_t)b->net.slice_stride); rc != RANENV_OK) return rc;
+    for (NetBind *b = binds; b < binds + n; b++) { b->slot->net = b->net; b->slot->on = true; }
     return RANENV_OK;
 }
 
@@ -1229,8 +1253,9 @@ static PolicyIO net_io(ranenv_handle h, const KP &kp)
 
 static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
 {
-    if (head_policy(h)) return launch_head_policy(s, h->head.a, net_io(h, kp), e0, n);
-    return launch_policy(s, h->actor.a, h->intra_actor(), net_io(h, kp), e0, n);
+    const bool head = head_policy(h);
+    const PolicyNets nets{head, head ? &h->head.net : &h->actor.net, head ? nullptr : h->intra_actor(), nullptr, nullptr};
+    return launch_policy(s, nets, net_io(h, kp), nullptr, e0, n);
 }
 
 // The buffers the nets' actions go to and the step reads them from (IBSched nets and head nets share them: one policy acts at a time)
@@ -1246,50 +1271,29 @@ int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ra
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice net is required (intra may be NULL)");
-    const int rc = net_set(h, h->actor, {inter, NET_INTER}, {intra, NET_INTRA}, (hipStream_t)stream, [&] { return net_action_buffers(h); });
+    NetBind b[2] = {{&h->actor, &inter, 1, NET_INTER}, {&h->actor_intra, &intra, 1, NET_INTRA}};
+    const int n = intra ? 2 : 1;
+    int rc = net_plan(h, b, n);
     if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((rc = net_action_buffers(h)) != RANENV_OK) return rc;
+    if ((rc = net_commit(h, b, n, (hipStream_t)stream)) != RANENV_OK) return rc;
     h->net_stochastic = stochastic != 0; h->net_seed = seed;
-    h->actor_ps.on = h->value_ps.on = false;      // (`intra`, NULL included, says what the intra policy is now)
+    h->actor_intra.on = intra != nullptr;         // (`intra`, NULL included, says what the intra policy is now)
+    h->actor_ps.on = h->value_ps.on = false;
     return RANENV_OK;
 }
 
-// ranenv_set_intra_policy_networks / _intra_value_networks: n = S nets of one shape into `slot`'s buffer at equal stride, by net_set's
-// rules -- every validation error precedes every HIP call, the buffer grows (the outgrown one stays until ranenv_destroy) or is zeroed,
-// the slot changes on success only
-static int net_set_per_slice(ranenv_handle h, ranenv::NetSlot &slot, int32_t n, const ranenv_mlp *const *nets, NetRole role, hipStream_t s)
+// ranenv_set_intra_policy_networks / _intra_value_networks: n = S nets of one shape at equal stride in `slot`'s buffer
+static int net_set_copies(ranenv_handle h, ranenv::NetSlot &slot, int32_t n, const ranenv_mlp *const *nets, NetRole role, hipStream_t s)
 {
     const char *who = NET_ROLES[role].who;
     if (n != h->cfg.n_slices) return fail(h, RANENV_E_INVALID, "%s nets per slice: %d given, the handle has %d slices", who, n, h->cfg.n_slices);
     if (!nets) return fail(h, RANENV_E_INVALID, "%s nets per slice: null array", who);
-    PolicyNet net{};
-    for (int32_t i = 0; i < n; i++) {
-        const ranenv_mlp *m = nets[i], *m0 = nets[0];
-        if (!m) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d is null", who, i);
-        PolicyNet ni{};
-        long long floats = 0;
-        const int rc = net_layout(h, m, role, ni, floats);
-        if (rc != RANENV_OK) return rc;
-        bool same = m->n_hidden == m0->n_hidden && m->activation == m0->activation && m->input_layout == m0->input_layout;
-        for (int l = 0; same && l <= m->n_hidden + 1; l++) same = m->dims[l] == m0->dims[l];
-        if (!same) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d differs from net 0 in shape, activation or input layout", who, i);
-        if (i == 0) { net = ni; net.slice_stride = floats; }
-    }
-    const long long total = net.slice_stride * n;
+    NetBind b{&slot, nets, n, role};
+    if (const int rc = net_plan(h, &b, 1); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (total > slot.cap) {
-        const int rc = dev_alloc(h, &slot.w, (size_t)total);
-        if (rc != RANENV_OK) return rc;
-        slot.cap = total;
-    } else {
-        HIP_TRY(h, hipMemsetAsync(slot.w, 0, sizeof(float) * (size_t)total, s));
-    }
-    net.w = slot.w;
-    for (int32_t i = 0; i < n; i++) {
-        const int rc = net_copy(h, nets[i], net, s, slot.w + (size_t)i * (size_t)net.slice_stride);
-        if (rc != RANENV_OK) return rc;
-    }
-    slot.a = net; slot.b = PolicyNet{}; slot.has_b = false; slot.on = true;
-    return RANENV_OK;
+    return net_commit(h, &b, 1, s);
 }
 
 int ranenv_set_intra_policy_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *actors, void *stream)
@@ -1297,7 +1301,7 @@ int ranenv_set_intra_policy_networks(ranenv_handle h, int32_t n, const ranenv_ml
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (n == 0 && !actors) { h->actor_ps.on = h->value_ps.on = false; return RANENV_OK; }
     if (!h->actor.on) return fail(h, RANENV_E_STATE, "intra policy nets per slice need a bound inter net (ranenv_set_policy_network)");
-    return net_set_per_slice(h, h->actor_ps, n, actors, NET_INTRA, (hipStream_t)stream);
+    return net_set_copies(h, h->actor_ps, n, actors, NET_INTRA, (hipStream_t)stream);
 }
 
 int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *critics, void *stream)
@@ -1308,7 +1312,7 @@ int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp
     if (!ia) return fail(h, RANENV_E_INVALID, "intra value nets need a bound intra policy net (ranenv_set_policy_network / ranenv_set_intra_policy_networks)");
     if (n == h->cfg.n_slices && critics && critics[0] && critics[0]->input_layout != ia->layout)
         return fail(h, RANENV_E_INVALID, "intra value nets: input layout %d, the intra policy net has %d", critics[0]->input_layout, ia->layout);
-    return net_set_per_slice(h, h->value_ps, n, critics, NET_INTRA_VALUE, (hipStream_t)stream);
+    return net_set_copies(h, h->value_ps, n, critics, NET_INTRA_VALUE, (hipStream_t)stream);
 }
 
 int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra)
@@ -1327,9 +1331,14 @@ int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ran
     if (intra && !(h->actor.on && ia)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
     if (intra && intra->input_layout != ia->layout)
         return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, ia->layout);
-    const int rc = net_set(h, h->value, {inter, NET_INTER_VALUE}, {intra, NET_INTRA_VALUE}, (hipStream_t)stream);
-    if (rc == RANENV_OK) h->value_ps.on = false;      // (`intra`, NULL included, says what the intra critic is now)
-    return rc;
+    NetBind b[2] = {{&h->value, &inter, 1, NET_INTER_VALUE}, {&h->value_intra, &intra, 1, NET_INTRA_VALUE}};
+    const int n = intra ? 2 : 1;
+    if (const int rc = net_plan(h, b, n); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (const int rc = net_commit(h, b, n, (hipStream_t)stream); rc != RANENV_OK) return rc;
+    h->value_intra.on = intra != nullptr;         // (`intra`, NULL included, says what the intra critic is now)
+    h->value_ps.on = false;
+    return RANENV_OK;
 }
 
 int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int32_t dist, const float *dev_log_std, int32_t stochastic,
@@ -1342,13 +1351,14 @@ int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int
     if (dist == RANENV_HEAD_DIST_GAUSS_TANH && dev_log_std) return fail(h, RANENV_E_INVALID, "GAUSS_TANH takes log_std from the net: dev_log_std must be NULL");
     const size_t S = (size_t)h->cfg.n_slices;
     hipStream_t s = (hipStream_t)stream_;
-    const int rc = net_set(h, h->head, {actor, dist == RANENV_HEAD_DIST_GAUSS_TANH ? NET_HEAD_TANH : NET_HEAD_CLIP}, {nullptr, NET_HEAD_CLIP}, s, [&] {
-        int ra = net_action_buffers(h);
-        if (ra == RANENV_OK && !h->d_head_log_std) ra = dev_alloc(h, &h->d_head_log_std, S);
-        if (ra == RANENV_OK && dev_log_std) HIP_TRY(h, hipMemcpyAsync(h->d_head_log_std, dev_log_std, sizeof(float) * S, hipMemcpyDeviceToDevice, s));
-        return ra;
-    });
+    NetBind b{&h->head, &actor, 1, dist == RANENV_HEAD_DIST_GAUSS_TANH ? NET_HEAD_TANH : NET_HEAD_CLIP};
+    int rc = net_plan(h, &b, 1);
     if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((rc = net_action_buffers(h)) != RANENV_OK) return rc;
+    if (!h->d_head_log_std && (rc = dev_alloc(h, &h->d_head_log_std, S)) != RANENV_OK) return rc;
+    if (dev_log_std) HIP_TRY(h, hipMemcpyAsync(h->d_head_log_std, dev_log_std, sizeof(float) * S, hipMemcpyDeviceToDevice, s));
+    if ((rc = net_commit(h, &b, 1, s)) != RANENV_OK) return rc;
     h->head_dist = dist; h->head_stochastic = stochastic != 0; h->head_seed = seed;
     return RANENV_OK;
 }
@@ -1357,7 +1367,10 @@ int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, voi
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!critic) return fail(h, RANENV_E_INVALID, "the head critic is required");
-    return net_set(h, h->head_value, {critic, NET_HEAD_VALUE}, {nullptr, NET_HEAD_VALUE}, (hipStream_t)stream);
+    NetBind b{&h->head_value, &critic, 1, NET_HEAD_VALUE};
+    if (const int rc = net_plan(h, &b, 1); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return net_commit(h, &b, 1, (hipStream_t)stream);
 }
 
 static int check_ready(ranenv_handle h, const float *se_tiles, const double *traffic_bits, bool need_traffic)
@@ -1767,14 +1780,13 @@ static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kp
         rec.logp = slot(tr.rec.logp, C);
         rec.intra_actor = ia ? 1 : 0;
     }
-    const PolicyNet &actor = head ? h->head.a : h->actor.a, *intra = ia ? h->intra_actor() : nullptr;
-    const PolicyNet *critic = vc ? (head ? &h->head_value.a : &h->value.a) : nullptr, *vintra = ic ? h->intra_critic() : nullptr;
+    const PolicyNet &actor = head ? h->head.net : h->actor.net, *intra = ia ? h->intra_actor() : nullptr;
+    const PolicyNet *critic = vc ? (head ? &h->head_value.net : &h->value.net) : nullptr, *vintra = ic ? h->intra_critic() : nullptr;
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
     // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").  Nets per
     // slice count with one slice's copy: the co-resident workgroups of a sliced launch mostly walk one slice's weights.
     if (!critic_only) rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, *intra, vintra) << 1 : 0);
-    const PolicyIO io = net_io(h, kpk);
-    return head ? launch_head_policy_collect(s, actor, critic, io, rec, e0, n) : launch_policy_collect(s, actor, intra, critic, vintra, io, rec, e0, n);
+    return launch_policy(s, PolicyNets{head, &actor, intra, critic, vintra}, net_io(h, kpk), &rec, e0, n);
 }
 
 // One launch of a partition's walk: TTI `t` of its own count, kpk.n_tti TTIs (one under a policy net or a recording), for envs
@@ -2055,11 +2067,12 @@ int ranenv_set_sac_critics(ranenv_handle h, const ranenv_mlp *q1, const ranenv_m
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!q1 || !q2) return fail(h, RANENV_E_INVALID, "both SAC critics are required");
     if (q1->n_hidden != q2->n_hidden || q1->activation != q2->activation) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape");
-    return net_set(h, h->sac, {q1, NET_SAC_Q}, {q2, NET_SAC_Q}, (hipStream_t)stream, [&] {      // (each critic is valid by itself here)
-        for (int l = 0; l <= q1->n_hidden + 1; l++)
-            if (q1->dims[l] != q2->dims[l]) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape (width %d: %d and %d)", l, q1->dims[l], q2->dims[l]);
-        return (int)RANENV_OK;
-    });
+    NetBind b[2] = {{&h->sac_q1, &q1, 1, NET_SAC_Q}, {&h->sac_q2, &q2, 1, NET_SAC_Q}};
+    if (const int rc = net_plan(h, b, 2); rc != RANENV_OK) return rc;
+    for (int l = 0; l <= q1->n_hidden + 1; l++)      // (each critic is valid by itself here)
+        if (q1->dims[l] != q2->dims[l]) return fail(h, RANENV_E_INVALID, "the two SAC critics differ in shape (width %d: %d and %d)", l, q1->dims[l], q2->dims[l]);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return net_commit(h, b, 2, (hipStream_t)stream);
 }
 
 int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, const float *dev_reward, const uint8_t *dev_done, double gamma,
@@ -2071,14 +2084,14 @@ int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, co
     if (!dev_next_obs || !dev_reward || !dev_done || !dev_target) return fail(h, RANENV_E_INVALID, "SAC targets: next_obs, reward, done and target are required");
     if (!h->head.on || h->head_dist != RANENV_HEAD_DIST_GAUSS_TANH)
         return fail(h, RANENV_E_STATE, "SAC targets need a GAUSS_TANH head actor (ranenv_set_head_policy_network)");
-    if (!h->sac.on) return fail(h, RANENV_E_STATE, "no SAC critics bound (ranenv_set_sac_critics)");
+    if (!h->sac_q2.on) return fail(h, RANENV_E_STATE, "no SAC critics bound (ranenv_set_sac_critics)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     SacArgs a{};
     a.n = n; a.S = h->cfg.n_slices;
     a.next_obs = dev_next_obs; a.reward = dev_reward; a.done = dev_done;
     a.gamma = gamma; a.ent_coef = ent_coef; a.stochastic = stochastic != 0; a.seed = seed; a.draw = draw;
     a.target = dev_target; a.next_action = dev_next_action; a.next_logp = dev_next_logp; a.q = dev_q;
-    const hipError_t le = launch_sac_targets((hipStream_t)stream, h->head.a, h->sac.a, h->sac.b, a);
+    const hipError_t le = launch_sac_targets((hipStream_t)stream, h->head.net, h->sac_q1.net, h->sac_q2.net, a);
     if (le != hipSuccess) return fail(h, RANENV_E_HIP, "SAC target launch: %s", hipGetErrorString(le));
     return RANENV_OK;
 }

@@ -205,16 +205,13 @@ struct PolicyRec {
     int critic_only;                      // the pass behind the last TTI: no actors, no record, vf of the observation as it stands
     int split;                            // host side only: bit 0 / 1 = the inter (head) / intra critic runs as a launch of its own behind the actor's
 };
-// Enqueue the inter net (and the intra net when `intra` is non-null) / the head actor for envs [e0, e0 + n_envs).  An intra net with a
-// slice_stride -- in the recording launches: or an intra critic with one -- takes the sliced kernels (one workgroup column per slice).
-hipError_t launch_policy(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &, int e0, int n_envs);
-hipError_t launch_head_policy(hipStream_t, const PolicyNet &actor, const PolicyIO &, int e0, int n_envs);
-// The recording launches of one TTI: actor + critic stack per agent kind in one launch each (`vinter` / `vintra` / `critic` null = no
-// critic of that kind; `intra` null = no intra actor, then `vintra` is null too).  critic_only: the critics alone.
-hipError_t launch_policy_collect(hipStream_t, const PolicyNet &inter, const PolicyNet *intra, const PolicyNet *vinter, const PolicyNet *vintra,
-                                 const PolicyIO &, const PolicyRec &, int e0, int n_envs);
-hipError_t launch_head_policy_collect(hipStream_t, const PolicyNet &actor, const PolicyNet *critic, const PolicyIO &, const PolicyRec &, int e0,
-                                      int n_envs);
+// The nets of one TTI's policy launches.  head: `actor` / `critic` are the head policy's (one launch, no intra nets), else the inter
+// pair.  Null: intra = no intra actor (then vintra is null too), critic / vintra = no critic of that kind.
+struct PolicyNets { bool head; const PolicyNet *actor, *intra, *critic, *vintra; };
+// THE policy launch entry, for envs [e0, e0 + n_envs).  rec null: the acting launches (actors only; the critics are not read).  rec
+// non-null: the recording launches -- actor + critic per agent kind fused, or split by rec's bits; critic_only: the critics alone.  An
+// intra launch whose actor or critic has a slice_stride takes the sliced kernels (one workgroup column per slice).
+hipError_t launch_policy(hipStream_t, const PolicyNets &, const PolicyIO &, const PolicyRec *rec, int e0, int n_envs);
 size_t policy_lds_bytes(const PolicyNet &);
 // ranenv_sac_targets: one call's rows and outputs (include/ranenv.h spells out the arithmetic).  The actor is a GAUSS_TANH head net,
 // q1 / q2 two nets of one shape on [next_obs | action].

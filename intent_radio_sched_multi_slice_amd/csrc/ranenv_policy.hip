@@ -57,8 +57,22 @@ __device__ __forceinline__ void load_dense_rows(const float *src, long long firs
     load_rows(K0, skip0, skip1, dst, tid, [&](int r, int k) { return dense_at(src, nullptr, first + r, n, width, cols, k); });
 }
 
+// THE ROW MAP: which env `e` and slice `s` row g of a launch from env e0 on belongs to, and es = e * S + s, the row of the
+// [B][S] arrays.  kind 0 (inter, head): row g = env e0 + g (s = 0).  kind 1 (intra): row g = e0 * S + g of the flat env x S rows, or
+// -- SLICED, the workgroup's slice `sl` -- (env e0 + g, slice sl).  Every site of policy_body that addresses by row goes through here.
+struct RowAt { int e, s; size_t es; };
+template <bool SLICED>
+__device__ __forceinline__ RowAt row_at(int kind, int e0, int S, int sl, int g)
+{
+    if (kind == 0) return {e0 + g, 0, (size_t)(e0 + g) * S};
+    if (SLICED) return {e0 + g, sl, (size_t)(e0 + g) * S + sl};
+    const size_t es = (size_t)e0 * S + g;
+    const int e = (int)(es / (size_t)S);
+    return {e, (int)(es - (size_t)e * S), es};
+}
+
 // Observation rows of `net`'s input -> LDS (zeros beyond the input and beyond the launch's rows).  REC: the rows are written to the
-// record's slot on the way (the observation the TTI's action is computed from).  SLICED (kind 1): row g is (env e0 + g, slice `sl`).
+// record's slot on the way (the observation the TTI's action is computed from).  `sl`: a sliced launch's slice (see row_at).
 template <bool REC, bool SLICED = false>
 __device__ __forceinline__ void net_load_rows(const PolicyNet &net, const PolicyIO &io, const PolicyRec &rec, int kind, int e0, int row0, int n_rows,
                                               float *cur, int tid, int sl = 0)
@@ -67,7 +81,7 @@ __device__ __forceinline__ void net_load_rows(const PolicyNet &net, const Policy
         const int g = row0 + r;
         if (kind == 0) return dense_at(io.obs_inter, REC ? rec.obs_inter : nullptr, e0 + g, e0 + n_rows, 10 * io.S, net.in_dim, k);
         if (g >= n_rows || k >= net.in_dim) return 0.0f;
-        const size_t es = SLICED ? (size_t)(e0 + g) * io.S + sl : (size_t)e0 * io.S + g;
+        const size_t es = row_at<SLICED>(1, e0, io.S, sl, g).es;
         const int ko = net.layout == RANENV_NET_IN_MASK_OBS ? k - io.Us : k;
         if (ko < 0) return (float)io.mask_intra[es * io.Us + k];
         const float v = io.obs_intra[es * io.W + ko];
@@ -199,7 +213,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         if (kind == 1 && rec.mask_intra)
             for (int i = tid; i < NET_ROWS * io.Us; i += 256)
                 if (row0 + i / io.Us < n_rows) {
-                    const size_t o = SLICED ? ((size_t)(e0 + row0 + i / io.Us) * S + sl) * io.Us + i % io.Us : ((size_t)e0 * S + row0) * io.Us + i;
+                    const size_t o = row_at<SLICED>(1, e0, S, sl, row0 + i / io.Us).es * io.Us + i % io.Us;
                     rec.mask_intra[o] = io.mask_intra[o];
                 }
     }
@@ -268,8 +282,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         for (int r = tid; r < NET_ROWS; r += 256) {
             const int g = row0 + r;
             if (g >= n_rows) continue;
-            const size_t es = SLICED ? (size_t)(e0 + g) * S + sl : (size_t)e0 * S + g;
-            const int e = SLICED ? e0 + g : (int)(es / (size_t)S), s = SLICED ? sl : (int)(es - (size_t)e * S);
+            const auto [e, s, es] = row_at<SLICED>(1, e0, S, sl, g);
             const float l0 = cur[r * ld], l1 = cur[r * ld + 1], l2 = cur[r * ld + 2];
             int ch = 0;
             if (!io.stochastic) {
@@ -316,9 +329,8 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                 if (!HEAD && !rec.intra_critic)
                     for (int s = 0; s < S; s++) out[1 + s] = 0.0f;
             } else {
-                const size_t es = SLICED ? (size_t)(e0 + g) * S + sl : (size_t)e0 * S + g;
-                const size_t e = SLICED ? (size_t)(e0 + g) : es / (size_t)S;
-                rec.vf[e * rec.cols + 1 + (es - e * S)] = cur[r * ldv];
+                const RowAt at = row_at<SLICED>(1, e0, S, sl, g);
+                rec.vf[(size_t)at.e * rec.cols + 1 + at.s] = cur[r * ldv];
             }
         }
     }
@@ -443,39 +455,46 @@ __global__ void __launch_bounds__(256) ranenv_sac_target_kernel(PolicyNet actor,
     a.target[gr] = (float)((double)a.reward[gr] + nd * (a.gamma * (fmin((double)v1, (double)v2) - a.ent_coef * lp)));
 }
 
-// The kernel's dynamic LDS limit raised to the widest net's need (2 x 32 x 516 floats = 129 KB), once per kernel
-template <auto KERNEL>
-hipError_t lds_attr()
+// Enqueue KERNEL, its dynamic LDS limit raised to the widest net's need (2 x 32 x 516 floats = 129 KB) once per kernel
+template <auto KERNEL, class... A>
+hipError_t launch_kernel(dim3 grid, size_t lds, hipStream_t s, const A &...args)
 {
     static const hipError_t attr = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        (int)(sizeof(float) * 2 * NET_ROWS * net_ld(NET_MAX_WIDTH)));
-    return attr;
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, s, args...);
+    return hipSuccess;
 }
 
-dim3 grid_of(int rows) { return dim3((unsigned)((rows + NET_ROWS - 1) / NET_ROWS)); }
+using ranenv_dev::policy_lds_bytes;
 
-// An intra launch is sliced -- rows = envs, S x tiles workgroups -- when its actor or its critic has a copy per slice
-bool sliced(const PolicyNet &a, const PolicyNet *v) { return a.slice_stride != 0 || (v && v->slice_stride != 0); }
-dim3 grid_sliced(int n_envs, int S) { return dim3((unsigned)((n_envs + NET_ROWS - 1) / NET_ROWS) * (unsigned)S); }
-
-// One agent kind's recording launch(es) of a TTI: actor + critic `vp` (null: none) fused, or -- split -- the actor's launch, then the
-// critic alone (the kernel's critic_only mode).  SLICED: rows = envs (see policy_body).
-template <bool HEAD, bool SLICED = false>
-void collect_launch(hipStream_t s, int kind, const PolicyNet &a, const PolicyNet *vp, const PolicyIO &io, const PolicyRec &rec, int e0, int rows,
-                    bool split)
+// One agent kind's launch(es) of a TTI for envs [e0, e0 + n_envs): the actor `a` alone (rec null), or the recording launch -- actor +
+// critic `vp` (null: none) fused, or, split, the actor's launch and then the critic alone (the kernel's critic_only mode).  THE GEOMETRY:
+// kind 0 has one row per env; an intra launch (kind 1) has the flat env x S rows, or -- sliced, when its actor or its critic has a copy
+// per slice -- one row per env in S x tiles workgroups (see policy_body).
+hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, const PolicyNet *vp, const PolicyIO &io, const PolicyRec *rec,
+                       int e0, int n_envs, bool split)
 {
+    const bool sl = kind == 1 && (a.slice_stride != 0 || (vp && vp->slice_stride != 0));
+    const int rows = kind == 1 && !sl ? n_envs * io.S : n_envs;
+    const dim3 grid((unsigned)((rows + NET_ROWS - 1) / NET_ROWS) * (sl ? (unsigned)io.S : 1u));
+    if (!rec) {
+        if (sl) return launch_kernel<ranenv_policy_sliced_kernel>(grid, policy_lds_bytes(a), s, a, io, e0, rows);
+        if (head) return launch_kernel<ranenv_head_policy_kernel>(grid, policy_lds_bytes(a), s, a, io, e0, rows);
+        return launch_kernel<ranenv_policy_kernel>(grid, policy_lds_bytes(a), s, a, io, kind, e0, rows);
+    }
     const PolicyNet none{};               // (n_layers 0: no critic)
     auto launch = [&](const PolicyNet &v, const PolicyRec &rc) {
-        const size_t x = ranenv_dev::policy_lds_bytes(a), y = v.n_layers > 0 ? ranenv_dev::policy_lds_bytes(v) : 0, lds = x > y ? x : y;
-        if constexpr (SLICED) hipLaunchKernelGGL(ranenv_policy_sliced_collect_kernel, grid_sliced(rows, io.S), dim3(256), lds, s, a, v, io, rc, e0, rows);
-        else if constexpr (HEAD) hipLaunchKernelGGL(ranenv_head_policy_collect_kernel, grid_of(rows), dim3(256), lds, s, a, v, io, rc, e0, rows);
-        else hipLaunchKernelGGL(ranenv_policy_collect_kernel, grid_of(rows), dim3(256), lds, s, a, v, io, rc, kind, e0, rows);
+        const size_t x = policy_lds_bytes(a), y = v.n_layers > 0 ? policy_lds_bytes(v) : 0, lds = x > y ? x : y;
+        if (sl) return launch_kernel<ranenv_policy_sliced_collect_kernel>(grid, lds, s, a, v, io, rc, e0, rows);
+        if (head) return launch_kernel<ranenv_head_policy_collect_kernel>(grid, lds, s, a, v, io, rc, e0, rows);
+        return launch_kernel<ranenv_policy_collect_kernel>(grid, lds, s, a, v, io, rc, kind, e0, rows);
     };
-    if (!split || rec.critic_only || !vp) return launch(vp ? *vp : none, rec);
-    launch(none, rec);
+    if (!split || rec->critic_only || !vp) return launch(vp ? *vp : none, *rec);
+    if (const hipError_t e = launch(none, *rec); e != hipSuccess) return e;
     PolicyRec crit{};
-    crit.vf = rec.vf; crit.cols = rec.cols; crit.intra_critic = rec.intra_critic; crit.critic_only = 1;
-    launch(*vp, crit);
+    crit.vf = rec->vf; crit.cols = rec->cols; crit.intra_critic = rec->intra_critic; crit.critic_only = 1;
+    return launch(*vp, crit);
 }
 
 }  // namespace
@@ -484,54 +503,22 @@ namespace ranenv_dev {
 
 size_t policy_lds_bytes(const PolicyNet &net) { return sizeof(float) * 2 * NET_ROWS * (size_t)net_ld_max(net); }
 
-hipError_t launch_policy(hipStream_t s, const PolicyNet &inter, const PolicyNet *intra, const PolicyIO &io, int e0, int n_envs)
+hipError_t launch_policy(hipStream_t s, const PolicyNets &n, const PolicyIO &io, const PolicyRec *rec, int e0, int n_envs)
 {
-    if (const hipError_t attr = lds_attr<ranenv_policy_kernel>(); attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(ranenv_policy_kernel, grid_of(n_envs), dim3(256), policy_lds_bytes(inter), s, inter, io, 0, e0, n_envs);
-    if (intra && sliced(*intra, nullptr)) {
-        if (const hipError_t attr = lds_attr<ranenv_policy_sliced_kernel>(); attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(ranenv_policy_sliced_kernel, grid_sliced(n_envs, io.S), dim3(256), policy_lds_bytes(*intra), s, *intra, io, e0, n_envs);
-    } else if (intra)
-        hipLaunchKernelGGL(ranenv_policy_kernel, grid_of(n_envs * io.S), dim3(256), policy_lds_bytes(*intra), s, *intra, io, 1, e0, n_envs * io.S);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_collect(hipStream_t s, const PolicyNet &inter, const PolicyNet *intra, const PolicyNet *vinter, const PolicyNet *vintra,
-                                 const PolicyIO &io, const PolicyRec &rec, int e0, int n_envs)
-{
-    if (const hipError_t attr = lds_attr<ranenv_policy_collect_kernel>(); attr != hipSuccess) return attr;
-    if (!rec.critic_only || vinter) collect_launch<false>(s, 0, inter, vinter, io, rec, e0, n_envs, (rec.split & 1) != 0);
-    if (intra && (!rec.critic_only || vintra)) {
-        if (sliced(*intra, vintra)) {
-            if (const hipError_t attr = lds_attr<ranenv_policy_sliced_collect_kernel>(); attr != hipSuccess) return attr;
-            collect_launch<false, true>(s, 1, *intra, vintra, io, rec, e0, n_envs, (rec.split & 2) != 0);
-        } else
-            collect_launch<false>(s, 1, *intra, vintra, io, rec, e0, n_envs * io.S, (rec.split & 2) != 0);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_head_policy(hipStream_t s, const PolicyNet &actor, const PolicyIO &io, int e0, int n_envs)
-{
-    if (const hipError_t attr = lds_attr<ranenv_head_policy_kernel>(); attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(ranenv_head_policy_kernel, grid_of(n_envs), dim3(256), policy_lds_bytes(actor), s, actor, io, e0, n_envs);
-    return hipGetLastError();
-}
-
-hipError_t launch_head_policy_collect(hipStream_t s, const PolicyNet &actor, const PolicyNet *critic, const PolicyIO &io, const PolicyRec &rec, int e0,
-                                      int n_envs)
-{
-    if (const hipError_t attr = lds_attr<ranenv_head_policy_collect_kernel>(); attr != hipSuccess) return attr;
-    collect_launch<true>(s, 0, actor, critic, io, rec, e0, n_envs, (rec.split & 1) != 0);
-    return hipGetLastError();
+    const bool critics = rec && rec->critic_only;      // the critics' pass: a kind without a critic has no launch
+    const PolicyNet *critic = rec ? n.critic : nullptr, *vintra = rec ? n.vintra : nullptr;
+    const int split = rec ? rec->split : 0;
+    hipError_t e = hipSuccess;
+    if (!critics || critic) e = launch_kind(s, n.head, 0, *n.actor, critic, io, rec, e0, n_envs, (split & 1) != 0);
+    if (e == hipSuccess && n.intra && (!critics || vintra)) e = launch_kind(s, false, 1, *n.intra, vintra, io, rec, e0, n_envs, (split & 2) != 0);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_sac_targets(hipStream_t s, const PolicyNet &actor, const PolicyNet &q1, const PolicyNet &q2, const SacArgs &a)
 {
-    if (const hipError_t attr = lds_attr<ranenv_sac_target_kernel>(); attr != hipSuccess) return attr;
     const size_t x = policy_lds_bytes(actor), y = policy_lds_bytes(q1), lds = x > y ? x : y;
-    hipLaunchKernelGGL(ranenv_sac_target_kernel, dim3((unsigned)((a.n + NET_ROWS - 1) / NET_ROWS)), dim3(256), lds, s, actor, q1, q2, a);
-    return hipGetLastError();
+    const hipError_t e = launch_kernel<ranenv_sac_target_kernel>(dim3((unsigned)((a.n + NET_ROWS - 1) / NET_ROWS)), lds, s, actor, q1, q2, a);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 }  // namespace ranenv_dev

@@ -453,6 +453,41 @@ def test_a_shared_net_afterwards_and_unbinding():
     env.close()
 
 
+@pytest.mark.parametrize("per_slice_between", [False, True], ids=["pair", "per-slice-between"])
+@pytest.mark.parametrize("widths", [[40], [96, 7]], ids=["40", "96x7"])
+def test_an_inter_critic_alone_behind_a_critic_pair(widths, per_slice_between):
+    """set_value_network(v_inter2, None) behind a critic pair -- and behind per-slice critics bound in between -- leaves no intra critic:
+    columns 1..S of the next record's vf are exactly 0, and the record is, bit for bit, that of a fresh env bound to (v_inter2, None)
+    from the start and taken through the same two collect(2) calls.  B = 33: one full tile of 32 rows and a one-row tail."""
+    need_gpu()
+    case = (5, 5, 33, widths, "tanh", "obs")
+    S = case[0]
+    inter, intras, v_inter, v_intras = ps.make_nets(case, 990)
+    v_inter2 = make_net([10 * S] + widths + [1], "tanh", 995)
+    recs = {}
+    for how in ("rebound", "fresh"):
+        wl, env = _env(case, 101)
+        env.set_policy_network(inter, intras[0], stochastic=True, seed=SEED, intra_input="obs")
+        if how == "rebound":
+            env.set_value_network(v_inter, v_intras[0])
+        else:
+            env.set_value_network(v_inter2, None)
+        env.reset()
+        first = to_host(env.collect(2))
+        if how == "rebound":
+            assert np.any(first["vf"][..., 1:] != 0.0)
+            if per_slice_between:
+                env.set_value_network(v_inter, v_intras)
+            env.set_value_network(v_inter2, None)
+        recs[how] = to_host(env.collect(2))
+        env.close()
+    assert np.all(recs["rebound"]["vf"][..., 1:] == 0.0)
+    assert np.any(recs["rebound"]["vf"][..., 0] != 0.0) and np.any(recs["rebound"]["logp"][..., 1:] != 0.0)
+    assert np.array_equal(recs["rebound"]["vf"][..., 0], recs["fresh"]["vf"][..., 0])
+    for name in FIELDS:
+        assert np.array_equal(recs["rebound"][name], recs["fresh"][name]), name
+
+
 def test_rebind_larger_then_smaller_right_after_a_partitioned_rollout():
     """Per-slice sets re-bound behind partitioned rollouts without a host sync == the same sequence with syncs; the last, smaller set --
     copied in place over the larger one's buffer -- then acts as the twin says (stale weights or padding would show)."""
