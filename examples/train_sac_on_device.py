@@ -1,6 +1,7 @@
 """SAC in miniature on SchedColORAN's head with the host out of the data path: replay ring, minibatches and Bellman targets on the GPU.
 
     python examples/train_sac_on_device.py [--batch 4096] [--ttis 16] [--iters 10] [--grad-steps 8] [--minibatch 65536] [--capacity 64]
+    python examples/train_sac_on_device.py --agent sb3_sched|sb3_pf_sched      (IBSchedSB3: obs_inter, reward[:, 0], RR / PF intra)
 
 The reference builds its SB3 agents in a "sac" flavour beside "ppo" (agents/sched_colran.py:111-133, agents/sched_twc.py:111-133,
 agents/sb3_sched.py:104-120): SB3's SAC("MlpPolicy", ...) -- an actor with a tanh-squashed Gaussian, two Q-nets and their polyak-averaged
@@ -30,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from intent_radio_sched_multi_slice_amd._lib import INTRA_RR, POLICY_MAPF
+from intent_radio_sched_multi_slice_amd._lib import INTRA_PF, INTRA_RR, POLICY_MAPF
 from intent_radio_sched_multi_slice_amd.adapters import sac_targets_torch
 from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
 
@@ -65,6 +66,9 @@ def main():
     ap.add_argument("--episode-len", type=int, default=100)
     ap.add_argument("--check", action="store_true", help="compare the first minibatch's targets with adapters.sac_targets_torch")
     ap.add_argument("--se-mode", choices=("stream", "gather"), default="gather")
+    ap.add_argument("--agent", default="colran", choices=("colran", "sb3_sched", "sb3_pf_sched"),
+                    help="colran: SchedColORAN's head; sb3_sched / sb3_pf_sched: the reference's IBSchedSB3 on IBSched's player_0 observation "
+                         "and reward (agents/sb3_sched.py, agents/sb3_pf_sched.py), round-robin / proportional fair inside the slices")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     B, T, L, G, N = args.batch, args.ttis, args.episode_len, args.grad_steps, args.minibatch
@@ -72,10 +76,15 @@ def main():
     wl = make_mult_slice_workload(B, dev, policy=POLICY_MAPF, intra=INTRA_RR, n_scenarios=n_ep, n_traces=n_ep, trace_len=L, max_steps=L)
     env = wl.env
     S = env.S
-    wl.tables.sorted_slices[...] = np.arange(S, dtype=np.int32)     # SchedColORAN runs with enable_sort_slices=False
-    env.load_scenarios(wl.tables)
+    inter = args.agent != "colran"
+    if not inter:
+        wl.tables.sorted_slices[...] = np.arange(S, dtype=np.int32)     # SchedColORAN runs with enable_sort_slices=False
+        env.load_scenarios(wl.tables)
     env.set_se_mode(args.se_mode)
-    env.enable_heads(np.ones_like(wl.tables.slice_active, dtype=np.int32))
+    if not inter:
+        env.enable_heads(np.ones_like(wl.tables.slice_active, dtype=np.int32))
+    observation, reward, col = ("inter", "ibsched", 0) if inter else ("head", "colran", 1)
+    intra = INTRA_PF if args.agent == "sb3_pf_sched" else INTRA_RR
     ep = np.arange(n_ep)
     env.set_episode_table(scenario=ep, se_base=ep * L, se_len=L, trf_base=ep * L, trf_len=L)
     env.enable_autoreset(0, n_ep, random_episodes=True, seed=7, episode_numbers=np.arange(B) % n_ep)
@@ -89,11 +98,11 @@ def main():
     target_entropy = -float(S)
 
     def bind(it):
-        env.set_head_policy_network(actor, "gauss_tanh", stochastic=True, seed=1000 + it)
+        env.set_head_policy_network(actor, "gauss_tanh", stochastic=True, seed=1000 + it, fixed_intra=intra, observation=observation)
         env.set_sac_critics(q1_t, q2_t)
 
+    bind(0)                                  # (first: choosing the observation source unbinds a ring)
     ring = env.bind_replay(args.capacity)
-    bind(0)
     env.reset()
     torch.cuda.synchronize()
     t_collect = t_device = 0.0
@@ -106,7 +115,7 @@ def main():
         for g in range(G):
             draw = it * G + g
             td = time.perf_counter()
-            mb = env.replay_sample(N, seed=11, draw=draw, reward="colran")
+            mb = env.replay_sample(N, seed=11, draw=draw, reward=reward)
             alpha = float(log_alpha.exp())
             target = env.sac_targets(mb["next_obs"], mb["reward"], mb["done"], gamma=GAMMA, ent_coef=alpha, stochastic=True, seed=13, draw=draw,
                                      outputs=("target",))["target"]
@@ -139,7 +148,7 @@ def main():
                         pt.mul_(1.0 - TAU).add_(p, alpha=TAU)
         bind(it + 1)
         last = (env.replay_count() - 1) % args.capacity
-        print(f"iteration {it + 1:3d}: mean SchedColORAN reward of the last TTI {ring['reward_head'][last, :, 1].mean().item():+.4f}, "
+        print(f"iteration {it + 1:3d}: mean {'SchedColORAN' if not inter else args.agent} reward of the last TTI {ring['reward_head'][last, :, col].mean().item():+.4f}, "
               f"alpha {float(log_alpha.exp()):.3f}, critic loss {loss_q.item():.4f}", flush=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0

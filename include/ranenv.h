@@ -666,8 +666,9 @@ int ranenv_launch_info(ranenv_handle h, int32_t *grid, int32_t *block, int32_t *
 int ranenv_bind_head_outputs(ranenv_handle h, float *dev_obs_head, double *dev_reward_head);
 
 /* Head policies (RANENV_POLICY_HEAD_NETWORK): the learned baselines SchedTWC / SchedColORAN -- in the reference SB3 PPO / SAC
- * MlpPolicy agents (agents/sched_twc.py:111-133, agents/sched_colran.py, agents/sb3_sched.py) that read the head observation and
- * emit the player_0 action -- as a caller-supplied MLP run by one batched launch in front of every TTI that gets no inter-slice
+ * MlpPolicy agents (agents/sched_twc.py:111-133, agents/sched_colran.py) that read the head observation and emit the player_0
+ * action; agents/sb3_sched.py and agents/sb3_pf_sched.py are the same SB3 agents on IBSched's own player_0 observation, see
+ * "Head policy source" below -- as a caller-supplied MLP run by one batched launch in front of every TTI that gets no inter-slice
  * scores: ranenv_step / _step_range / _step_part (their env range, their stream) and every TTI of ranenv_rollout (per partition,
  * one TTI per launch, no persistent launch; auto-reset included: the reset launch refreshes dev_obs_head, so the first action of
  * a new episode reads the new episode's first observation).  The intra-slice scheduler is the fixed_intra of ranenv_set_policy
@@ -709,10 +710,39 @@ int ranenv_bind_head_outputs(ranenv_handle h, float *dev_obs_head, double *dev_r
  *     done        u8  [T][B]
  *     adv, vtarg  f32 [T][B]         GAE, the recurrence of ranenv_collect above, on column reward_col of reward_head
  *                                    (0 = SchedTWC, 1 = SchedColORAN); they need reward_head, vf and done
+ *     Under RANENV_HEAD_SRC_INTER: obs_head holds the obs_inter rows, reward_head is f64 [T][B][S+1], the step's reward rows, and
+ *     reward_col is 0..S (see "Head policy source").
  *   Only GAUSS_CLIP (PPO) collects: GAUSS_TANH gives RANENV_E_INVALID (SAC is off-policy and needs no log-probabilities).  No head
  *   net, no head critic or another policy than HEAD_NETWORK: RANENV_E_STATE (ranenv_collect under HEAD_NETWORK likewise).  Env
  *   state, the caller's output buffers, head buffers and metrics afterwards are bit for bit what ranenv_rollout leaves under the
  *   same net and seed.  The critic is fused behind the actor or split off as for ranenv_collect (option "collect_split").
+ *
+ * Head policy source.  IBSchedSB3 (agents/sb3_sched.py, round-robin inside the slices; agents/sb3_pf_sched.py, proportional fair) is
+ *   the same SB3 PPO / SAC MlpPolicy, but on IBSched's own player_0 terms, IBSched built with its defaults (enable_sort_slices=True,
+ *   agents/ib_sched.py:37):
+ *     observation  obs_space_format(obs)["player_0"]["observations"] (sb3_sched.py:159-162): the [10*S] inter-slice row of
+ *                  dev_obs_inter, slices in sorted positions; the action mask is dropped
+ *     reward       calculate_reward(...)["player_0"] (sb3_sched.py:164-167; ib_sched.py:206-221; common.py:381-439): column 0 of the
+ *                  step's reward row, whose episode sum is column [1] of the episode metrics
+ *     action       IBSched.action_format with fixed_intra "rr" / "pf" (sb3_sched.py:169-177, sb3_pf_sched.py:169-177): the fixed_intra
+ *                  of ranenv_set_policy, a step with inter scores and no intra choices
+ *   ranenv_set_head_policy_source selects where the head nets' rows and the recorded rewards come from; a property of the handle,
+ *   like the distribution; any other value than the two below is RANENV_E_INVALID.
+ *     RANENV_HEAD_SRC_HEAD  (default)  the bound dev_obs_head and the head kernel's reward pair: everything as described above
+ *     RANENV_HEAD_SRC_INTER            under RANENV_POLICY_HEAD_NETWORK the actor (and ranenv_collect_head's critic) read rows
+ *       [e0, e0 + n) of the CALL's dev_obs_inter as the previous step or reset left them, on the call's stream, as
+ *       RANENV_POLICY_NETWORK does; without that buffer: RANENV_E_INVALID.  dev_obs_head is not required: unbound, no head kernel is
+ *       launched; bound, it runs and writes as before and nothing reads its rows.  The scores go to ranenv_get_policy_actions'
+ *       buffer by sorted position, unmasked; the step applies the slice permutation and the inactive-slice rule.  Distributions,
+ *       epilogue, noise counters and tag are unchanged.  ranenv_collect_head: obs_head receives the obs_inter rows the actions were
+ *       computed from, reward_head the step's rows f64 [T][B][S+1] (the caller's dev_reward gets the last TTI's rows after the
+ *       call, as for ranenv_collect), reward_col is 0..S (0 = player_0, what IBSchedSB3 trains on), vf[T] is computed on the
+ *       observation left behind the last TTI's auto-reset.  Replay: obs / next_obs are obs_inter rows -- for done != 0 next_obs is
+ *       the row as the step left it BEFORE the auto-reset's reset overwrites it (ranenv_autoreset's dev_term_obs_inter), elsewhere
+ *       bit for bit the next slot's obs --, reward_head is f64 [C][B][S+1], ranenv_replay_sample takes reward_col 0..S, and the
+ *       call's dev_obs_inter must be 8-byte aligned.  ranenv_sac_targets works on caller rows and is the same under both sources.
+ *   The source may be changed between calls.  CHANGING it unbinds a bound replay ring (ranenv_bind_replay(h, NULL): the ring's
+ *   reward rows change width); setting the value the handle already has changes nothing.
  *
  * Episode sums of the two head rewards: when episode metrics are enabled AND dev_reward_head is bound, the head kernel adds the
  *   TTI's (r_twc, r_colran) to a per-env pair float64 [B][2] (one add per TTI, in TTI order; a reset of the env zeroes it), and
@@ -732,14 +762,17 @@ typedef struct {
 int ranenv_set_head_policy_network(ranenv_handle h, const ranenv_mlp *actor, int32_t dist, const float *dev_log_std, int32_t stochastic,
                                    uint64_t seed, void *stream);
 int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, void *stream);
+#define RANENV_HEAD_SRC_HEAD  0   /* default: the bound dev_obs_head, the head kernel's reward pair */
+#define RANENV_HEAD_SRC_INTER 1   /* IBSchedSB3: the call's dev_obs_inter rows, the step's reward rows */
+int ranenv_set_head_policy_source(ranenv_handle h, int32_t source);
 int ranenv_get_head_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t *episode_slots);
 int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, int32_t reward_col, double gamma, double lambda,
                         float *dev_obs_inter, float *dev_obs_intra, double *dev_reward, uint8_t *dev_done, void *stream);
 
 /* Off-policy collection (SAC): the reference builds every SB3 agent in two flavours, agent_type "ppo" and "sac"
- * (agents/sched_twc.py:111-133, agents/sched_colran.py:111-133, agents/sb3_sched.py:104-120, agents/sb3_pf_sched.py); the SAC
- * flavour is SB3's SAC("MlpPolicy", ...): an Actor (RANENV_HEAD_DIST_GAUSS_TANH above), two ContinuousCritic Q-nets and their
- * target copies, a ReplayBuffer, uniform minibatches, and per minibatch the soft Bellman target.  What of that needs no gradient
+ * (agents/sched_twc.py:111-133, agents/sched_colran.py:111-133 on the head observation; agents/sb3_sched.py:104-120,
+ * agents/sb3_pf_sched.py on IBSched's player_0 observation, RANENV_HEAD_SRC_INTER above); the SAC flavour is SB3's
+ * SAC("MlpPolicy", ...): an Actor (RANENV_HEAD_DIST_GAUSS_TANH above), two ContinuousCritic Q-nets and their target copies, a ReplayBuffer, uniform minibatches, and per minibatch the soft Bellman target.  What of that needs no gradient
  * runs here: the replay ring, the sampler, the target.  The learner's losses, optimiser and polyak update stay with the caller.
  * stable-baselines3 is not part of this project's test environment: everything below is restated from SB3's documented module
  * layout, parity with SB3 itself is UNPINNED (as for the head policies above).
@@ -755,6 +788,7 @@ int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_traj
  *                                    unclamped sample ranenv_collect_head records
  *     reward_head f64 [C][B][2]      the head kernel's pair (SchedTWC, SchedColORAN), written straight into the slot
  *     done        u8  [C][B]
+ *   Under RANENV_HEAD_SRC_INTER ("Head policy source" above): obs / next_obs hold obs_inter rows, reward_head is f64 [C][B][S+1].
  * ranenv_bind_replay: NULL unbinds; binding zeroes the write count.  capacity < 2 or a NULL pointer: RANENV_E_INVALID.  Rows move as
  *   8-byte words: obs, next_obs, action, reward_head, the bound dev_obs_head and the sampler's dev_obs / dev_next_obs must be 8-byte
  *   aligned (RANENV_E_INVALID otherwise; any allocator's blocks are).

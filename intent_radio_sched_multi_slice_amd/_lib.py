@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("RANENV_LIB") or os.path.join(_HERE, "csrc", "libranen
 ABI_VERSION = 10
 POLICY_EXTERNAL, POLICY_MARR, POLICY_MAPF, POLICY_NETWORK, POLICY_HEAD_NETWORK = 0, 1, 2, 3, 4
 HEAD_DIST_GAUSS_CLIP, HEAD_DIST_GAUSS_TANH = 0, 1
+HEAD_SRC_HEAD, HEAD_SRC_INTER = 0, 1
 ACT_TANH, ACT_RELU = 0, 1
 NET_IN_OBS, NET_IN_MASK_OBS = 0, 1
 NET_MAX_HIDDEN, NET_MAX_WIDTH = 4, 512
@@ -166,6 +167,7 @@ FUNCTIONS = {
     "ranenv_sac_targets": (C.c_int, [_P, _I64, _P, _P, _P, _F64, _F64, _I32, C.c_uint64, C.c_uint64] + [_P] * 5),
     "ranenv_set_intra_policy_networks": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), _P]),
     "ranenv_set_intra_value_networks": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), _P]),
+    "ranenv_set_head_policy_source": (C.c_int, [_P, _I32]),
 }
 EXPORTS = tuple(FUNCTIONS)
 

@@ -6,6 +6,9 @@
   (agents/sched_twc.py:415-422).  It follows the ``stable_baselines3.common.vec_env.VecEnv`` protocol
   (``num_envs``, ``reset``, ``step_async`` / ``step_wait`` / ``step``, auto-reset with
   ``infos[i]["terminal_observation"]``) and subclasses it when stable-baselines3 is importable.
+* ``InterVecEnv``: the same protocol for the reference's IBSchedSB3 (agents/sb3_sched.py, agents/sb3_pf_sched.py), whose SB3 agent
+  sees IBSched's own ``player_0`` observation and reward: ``obs_inter``, ``reward[:, 0]``, round-robin or proportional fair inside
+  the slices.  The host-paced view of ``set_head_policy_network(observation="inter")``.
 * ``marl_obs_dict`` / ``marl_reward_dict``: one env of the batch in the dict layout RLlib's policies
   of the reference consume (``player_0`` = inter-slice agent, ``player_{s+1}`` = intra-slice agents,
   agents/ib_sched.py:160-200, simu.py:559-566).
@@ -19,7 +22,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from ._lib import INTRA_RR, POLICY_EXTERNAL
+from ._lib import INTRA_PF, INTRA_RR, POLICY_EXTERNAL
 from .batched_env import BatchedRanEnv
 
 try:  # optional: real base class and spaces when the trainer stack is installed
@@ -80,28 +83,19 @@ def describe_space(sp) -> dict:
     return {"shape": list(sp.shape), "low": float(np.min(sp.low)), "high": float(np.max(sp.high)), "dtype": np.dtype(sp.dtype).name}
 
 
-class HeadVecEnv(_VecEnvBase):
-    """B environments as one vector env for a single-agent trainer.
+class _SingleAgentVecEnv(_VecEnvBase):
+    """The VecEnv protocol of HeadVecEnv and InterVecEnv: B environments as one vector env for a single-agent trainer whose action is
+    the inter-slice scores under a fixed intra-slice scheduler.  A subclass says which of the env's buffers are the agent's
+    observation, its reward column and its terminal observation (``_observation`` / ``_reward_column`` / ``_terminal``)."""
 
-    ``reward``: "twc" (SchedTWC.calculate_reward) or "colran" (SchedColORAN.calculate_reward).
-    ``slice_usecase``: [n_scenarios, S] eMBB / URLLC bits, needed by the "colran" reward
-    (scenario.slice_usecase_from_req).  The env must already have scenarios, pools and episodes set.
-    """
-
-    def __init__(self, env: BatchedRanEnv, reward: str = "twc", slice_usecase=None):
-        if reward not in ("twc", "colran"):
-            raise ValueError("reward must be 'twc' or 'colran'")
+    def _open(self, env: BatchedRanEnv, fixed_intra: int, observation_space, action_space):
         self.env = env
-        self._col = 0 if reward == "twc" else 1
-        env.enable_heads(slice_usecase)
-        env.set_policy(POLICY_EXTERNAL, INTRA_RR)
+        env.set_policy(POLICY_EXTERNAL, fixed_intra)
         self.num_envs = env.B
-        S = env.S
-        self.observation_space = _box(-np.inf, np.inf, (10 * S,), np.float32)       # sched_twc.py:430-433
-        self.action_space = _box(-1.0, 1.0, (S,), np.float64)                        # ib_sched.py:394-403
+        self.observation_space, self.action_space = observation_space, action_space
         if _VecEnvBase is not object:
-            super().__init__(self.num_envs, self.observation_space, self.action_space)
-        self._intra = torch.zeros((env.B, S), dtype=torch.uint8, device=env.device)
+            _VecEnvBase.__init__(self, self.num_envs, self.observation_space, self.action_space)
+        self._intra = torch.zeros((env.B, env.S), dtype=torch.uint8, device=env.device)
         self._actions: Optional[torch.Tensor] = None
 
     # -- VecEnv protocol ------------------------------------------------------------------------
@@ -113,7 +107,7 @@ class HeadVecEnv(_VecEnvBase):
 
     def reset(self):
         self.env.reset()
-        return self.env.head_obs.cpu().numpy()
+        return self._observation().cpu().numpy()
 
     def step_async(self, actions):
         a = torch.as_tensor(np.asarray(actions), dtype=torch.float64, device=self.env.device)
@@ -128,28 +122,29 @@ class HeadVecEnv(_VecEnvBase):
         _, _, done = env.step(self._actions, self._intra)
         self._actions = None
         infos: List[Dict] = [{} for _ in range(self.num_envs)]
+        head_obs = self._observation()
         if env._autoreset:
             # one packed D2H: [observation (already the next episode's first one where done) | reward | done]
-            n = env.head_obs.shape[1]
-            packed = torch.cat([env.head_obs.to(torch.float64), env.head_reward[:, self._col:self._col + 1],
+            n = head_obs.shape[1]
+            packed = torch.cat([head_obs.to(torch.float64), self._reward_column()[:, None],
                                 done.to(torch.float64)[:, None]], dim=1).cpu().numpy()
             obs, rew, dones = packed[:, :n].astype(np.float32), packed[:, n].astype(np.float32), packed[:, n + 1] != 0
             if dones.any():                                     # rare (once per episode and env): fetch the terminal rows
                 idx = np.nonzero(dones)[0]
-                term = env.term_head_obs[torch.as_tensor(idx, device=env.device)].cpu().numpy()
+                term = self._terminal()[torch.as_tensor(idx, device=env.device)].cpu().numpy()
                 for j, i in enumerate(idx):
                     infos[i]["terminal_observation"] = term[j]
                     infos[i]["TimeLimit.truncated"] = False
             return obs, rew, dones, infos
-        obs = env.head_obs.cpu().numpy()
-        rew = env.head_reward[:, self._col].cpu().numpy().astype(np.float32)
+        obs = head_obs.cpu().numpy()
+        rew = self._reward_column().cpu().numpy().astype(np.float32)
         dones = done.cpu().numpy().astype(bool)
         if dones.any():                                         # auto-reset from the host, as DummyVecEnv does
             for i in np.nonzero(dones)[0]:
                 infos[i]["terminal_observation"] = obs[i].copy()
                 infos[i]["TimeLimit.truncated"] = False
             env.reset(env_mask=dones.astype(np.uint8))
-            obs[dones] = env.head_obs.cpu().numpy()[dones]
+            obs[dones] = self._observation().cpu().numpy()[dones]
         return obs, rew, dones, infos
 
     def step(self, actions):
@@ -174,6 +169,59 @@ class HeadVecEnv(_VecEnvBase):
 
     def seed(self, seed=None):
         return [None] * self.num_envs
+
+
+class HeadVecEnv(_SingleAgentVecEnv):
+    """B environments as one vector env for a single-agent trainer.
+
+    ``reward``: "twc" (SchedTWC.calculate_reward) or "colran" (SchedColORAN.calculate_reward).
+    ``slice_usecase``: [n_scenarios, S] eMBB / URLLC bits, needed by the "colran" reward
+    (scenario.slice_usecase_from_req).  The env must already have scenarios, pools and episodes set.
+    """
+
+    def __init__(self, env: BatchedRanEnv, reward: str = "twc", slice_usecase=None):
+        if reward not in ("twc", "colran"):
+            raise ValueError("reward must be 'twc' or 'colran'")
+        self._col = 0 if reward == "twc" else 1
+        env.enable_heads(slice_usecase)
+        S = env.S
+        self._open(env, INTRA_RR, _box(-np.inf, np.inf, (10 * S,), np.float32),      # sched_twc.py:430-433
+                   _box(-1.0, 1.0, (S,), np.float64))                                 # ib_sched.py:394-403
+
+    def _observation(self):
+        return self.env.head_obs
+
+    def _reward_column(self):
+        return self.env.head_reward[:, self._col]
+
+    def _terminal(self):
+        return self.env.term_head_obs
+
+
+class InterVecEnv(_SingleAgentVecEnv):
+    """The reference's IBSchedSB3 as a vector env (agents/sb3_sched.py; ``intra="pf"``: agents/sb3_pf_sched.py): the SB3 agent acts on
+    IBSched's own player_0 terms -- observation ``obs_inter`` [10*S], slices in sorted positions, the action mask dropped
+    (sb3_sched.py:159-162); reward ``reward[:, 0]`` (:164-167); action = inter-slice scores by sorted position with round-robin
+    ("rr") or proportional fair ("pf") inside the slices (:169-177); terminal observations from ``term_obs_inter``.  Spaces as
+    MarlBatchEnv declares them for player_0.  The env must already have scenarios, pools and episodes set; no ``enable_heads()``."""
+
+    INTRA = {"rr": INTRA_RR, "pf": INTRA_PF}
+
+    def __init__(self, env: BatchedRanEnv, intra: str = "rr"):
+        if intra not in self.INTRA:
+            raise ValueError("intra must be 'rr' or 'pf'")
+        S = env.S
+        self._open(env, self.INTRA[intra], _box(-1, np.inf, (S * 10,), np.float32),  # ib_sched.py:413-470, player_0
+                   _box(-1, 1, (S,), np.float64))                                     # ib_sched.py:394-403
+
+    def _observation(self):
+        return self.env.obs_inter
+
+    def _reward_column(self):
+        return self.env.reward[:, 0]
+
+    def _terminal(self):
+        return self.env.term_obs_inter
 
 
 def marl_obs_dict(env: BatchedRanEnv, b: int) -> Dict[str, Dict[str, np.ndarray]]:

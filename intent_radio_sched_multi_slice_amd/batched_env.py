@@ -51,6 +51,23 @@ NET_ACTIVATIONS = {"tanh": ACT_TANH, "relu": ACT_RELU}
 NET_INPUTS = {"obs": NET_IN_OBS, "mask_obs": NET_IN_MASK_OBS}
 HEAD_DISTS = {"gauss_clip": _lib.HEAD_DIST_GAUSS_CLIP, "gauss_tanh": _lib.HEAD_DIST_GAUSS_TANH}
 HEAD_REWARDS = {"twc": 0, "colran": 1}
+HEAD_SOURCES = {"head": _lib.HEAD_SRC_HEAD, "inter": _lib.HEAD_SRC_INTER}
+# reward names per head policy source -> column of the recorded reward rows ("inter": the step's rows, column 0 = player_0)
+HEAD_SOURCE_REWARDS = {"head": HEAD_REWARDS, "inter": {"ibsched": 0}}
+
+
+def head_reward_column(observation: str, reward: Optional[str] = None) -> int:
+    """The column ``collect_head`` / ``replay_sample`` select for ``reward`` under the head policy source ``observation``: "twc" /
+    "colran" of the head kernel's pair under "head", "ibsched" (IBSched's player_0 reward, what IBSchedSB3 trains on) of the step's
+    reward row under "inter".  None: the source's first name.  Any other combination raises ValueError."""
+    if observation not in HEAD_SOURCE_REWARDS:
+        raise ValueError(f"observation must be one of {sorted(HEAD_SOURCE_REWARDS)}")
+    names = HEAD_SOURCE_REWARDS[observation]
+    if reward is None:
+        return next(iter(names.values()))
+    if reward not in names:
+        raise ValueError(f"reward must be one of {sorted(names)} under the head policy source {observation!r}")
+    return names[reward]
 
 
 def policy_net_layers(net, activation: Optional[str] = None, in_dim: Optional[int] = None, out_dim: Optional[int] = None):
@@ -184,6 +201,7 @@ class BatchedRanEnv:
         self.se_mode = "stream"
         self._ranges = None          # set_ranges(): [(lo, hi)] for step_async / step_wait
         self._intra_layout = None    # input layout of the intra actor bound by set_policy_network (None: none)
+        self.head_observation = "head"      # what the head nets read (set_head_policy_network): "head" = head_obs, "inter" = obs_inter
         # (the views are handed out once, here: ranenv_get_views ends the library's host shadow of the step counters -- the views are writable --,
         # and a first views() call in the middle of an auto-reset loop would switch the shortcut of enable_autoreset off until the next full reset)
         self.views()
@@ -512,19 +530,28 @@ class BatchedRanEnv:
 
     # -- the learned baselines SchedTWC / SchedColORAN (RANENV_POLICY_HEAD_NETWORK) ------------------------------------------------
     def set_head_policy_network(self, actor, dist: str = "gauss_clip", log_std=None, stochastic: bool = False, seed: int = 0,
-                                activation: Optional[str] = None, allow_sorted: bool = False, fixed_intra: Optional[int] = None):
+                                activation: Optional[str] = None, allow_sorted: bool = False, fixed_intra: Optional[int] = None,
+                                observation: str = "head"):
         """Run a trained SchedTWC / SchedColORAN actor on the device in front of every TTI (RANENV_POLICY_HEAD_NETWORK,
         include/ranenv.h): ``actor`` maps ``head_obs`` [10*S] to S outputs (``dist`` "gauss_clip": SB3 PPO, the mean; ``log_std``
         [S] is the policy's parameter) or 2*S outputs ("gauss_tanh": SB3 SAC, (mu | log_std); ``log_std`` must be None).  Nets as
         for ``policy_net_layers`` (``activation`` default: tanh for gauss_clip, relu for gauss_tanh -- SB3's).  Needs
         ``enable_heads()``.  Switches the policy to HEAD_NETWORK with round-robin inside the slices (``fixed_intra``: another).
         SchedTWC runs IBSched without slice sorting (sched_twc.py:75-82): scenario tables whose ``sorted_slices`` is not the
-        identity raise RanEnvError unless ``allow_sorted``."""
+        identity raise RanEnvError unless ``allow_sorted``.
+        ``observation`` "inter" (ranenv_set_head_policy_source): the reference's IBSchedSB3, ``sb3_sched`` -- and with
+        ``fixed_intra=INTRA_PF`` ``sb3_pf_sched`` --, the same SB3 actor on IBSched's own player_0 observation: it reads ``obs_inter``
+        (slices in sorted positions, IBSched's default: no ``allow_sorted`` check), needs no ``enable_heads()``, and ``collect_head`` /
+        the replay ring record the step's ``[S + 1]`` reward rows, whose column 0 (``reward="ibsched"``) is its reward.  The source
+        in force is ``self.head_observation``; changing it unbinds a bound replay ring."""
+        if observation not in HEAD_SOURCES:
+            raise ValueError(f"observation must be one of {sorted(HEAD_SOURCES)}")
         if dist not in HEAD_DISTS:
             raise ValueError(f"dist must be one of {sorted(HEAD_DISTS)}")
-        if getattr(self, "head_obs", None) is None:
+        inter = observation == "inter"
+        if not inter and getattr(self, "head_obs", None) is None:
             raise RanEnvError("set_head_policy_network needs enable_heads(): the actor reads head_obs")
-        if self.tables is not None and not allow_sorted:
+        if self.tables is not None and not allow_sorted and not inter:
             ss = np.asarray(self.tables.sorted_slices)
             if not np.array_equal(ss, np.broadcast_to(np.arange(ss.shape[-1]), ss.shape)):
                 raise RanEnvError("the scenario tables sort the slices; SchedTWC / SchedColORAN run with enable_sort_slices=False "
@@ -542,11 +569,15 @@ class BatchedRanEnv:
                        [(actor, activation, 10 * self.S, self.S if dist == "gauss_clip" else 2 * self.S, NET_IN_OBS)],
                        HEAD_DISTS[dist], _ptr(ls), 1 if stochastic else 0, int(seed) & (2 ** 64 - 1), keep=[ls])
         self._policy_views = None
+        self._check(self._lib.ranenv_set_head_policy_source(self._h, HEAD_SOURCES[observation]), "ranenv_set_head_policy_source")
+        if observation != self.head_observation:
+            self._keep.pop("replay", None)         # (the library has unbound the ring: its reward rows change width)
+        self.head_observation = observation
         self.set_policy(POLICY_HEAD_NETWORK, INTRA_RR if fixed_intra is None else fixed_intra)
 
     def set_head_value_network(self, critic, activation: Optional[str] = None):
         """Bind the critic ``collect_head()`` evaluates beside the head actor (ranenv_set_head_value_network): ``head_obs`` [10*S]
-        -> one value.  Nets as for ``policy_net_layers``."""
+        (``obs_inter`` under the head policy source "inter") -> one value.  Nets as for ``policy_net_layers``."""
         self._set_nets("head_value_net", "ranenv_set_head_value_network", [(critic, activation, 10 * self.S, 1, NET_IN_OBS)])
 
     HEAD_TRAJECTORY_SHAPES = {     # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S)
@@ -556,19 +587,28 @@ class BatchedRanEnv:
         "adv": (torch.float32, 0, lambda B, S: (B,)), "vtarg": (torch.float32, 0, lambda B, S: (B,)),
     }
 
-    def collect_head(self, n_steps: int, reward: str = "twc", gamma: float = 0.99, lam: float = 0.95,
+    def _head_shapes(self, shapes, cache_key):
+        """A head record's / ring's shapes under the source in force: "inter" widens ``reward_head`` to the step's [S + 1] row."""
+        if self.head_observation != "inter":
+            return shapes, cache_key
+        wide = dict(shapes)
+        wide["reward_head"] = shapes["reward_head"][:-1] + (lambda B, S: (B, S + 1),)
+        return wide, "inter_" + cache_key
+
+    def collect_head(self, n_steps: int, reward: Optional[str] = None, gamma: float = 0.99, lam: float = 0.95,
                      record=_lib.HEAD_TRAJECTORY_FIELDS) -> Dict[str, torch.Tensor]:
         """``rollout(n_steps)`` under the head actor that leaves a PPO batch on the device (ranenv_collect_head, include/ranenv.h):
         a dict of ``[n_steps, B, ...]`` tensors named as ranenv_head_trajectory's fields (``vf`` has ``n_steps + 1`` slots),
-        restricted to ``record``.  ``adv`` / ``vtarg`` are GAE(``gamma``, ``lam``) on the ``reward`` column ("twc" / "colran") of
-        ``reward_head``.  Needs a "gauss_clip" ``set_head_policy_network`` and ``set_head_value_network``.  The tensors are
+        restricted to ``record``.  ``adv`` / ``vtarg`` are GAE(``gamma``, ``lam``) on the ``reward`` column ("twc" / "colran"; None =
+        "twc") of ``reward_head``.  Under the head policy source "inter" ``obs_head`` holds the ``obs_inter`` rows, ``reward_head`` is
+        the step's ``[n_steps, B, S + 1]`` rows and ``reward`` is "ibsched" (column 0; None = that); a name of the other source raises.  Needs a "gauss_clip" ``set_head_policy_network`` and ``set_head_value_network``.  The tensors are
         allocated once per (n_steps, record) and REUSED.  Everything else afterwards is as after ``rollout(n_steps)``."""
         if self._recorder is not None:
             raise RanEnvError("collect_head() does not return between TTIs: the recorder needs step()")
-        if reward not in HEAD_REWARDS:
-            raise ValueError(f"reward must be one of {sorted(HEAD_REWARDS)}")
-        return self._collect("collect_head", n_steps, record, _lib.HeadTrajectory, _lib.HEAD_TRAJECTORY_FIELDS, self.HEAD_TRAJECTORY_SHAPES,
-                             "head_trajectories", (self.B, self.S), self._lib.ranenv_collect_head, (HEAD_REWARDS[reward], float(gamma), float(lam)))
+        col = head_reward_column(self.head_observation, reward)
+        shapes, cache_key = self._head_shapes(self.HEAD_TRAJECTORY_SHAPES, "head_trajectories")
+        return self._collect("collect_head", n_steps, record, _lib.HeadTrajectory, _lib.HEAD_TRAJECTORY_FIELDS, shapes,
+                             cache_key, (self.B, self.S), self._lib.ranenv_collect_head, (col, float(gamma), float(lam)))
 
     # -- off-policy (SAC) collection: replay ring, sampler, targets (include/ranenv.h "Off-policy collection") ----------------------
     REPLAY_SHAPES = {          # field -> (dtype, shape of one slot in terms of B, S)
@@ -580,9 +620,11 @@ class BatchedRanEnv:
     def bind_replay(self, capacity: int) -> Dict[str, torch.Tensor]:
         """Allocate and bind a replay ring of ``capacity`` TTIs (ranenv_bind_replay): a dict of ``[capacity, B, ...]`` tensors
         ``obs`` / ``next_obs`` float32 [.., 10*S], ``action`` float64 [.., S] (the score the step consumed), ``reward_head`` float64
-        [.., 2], ``done`` uint8.  The k-th TTI recorded since binding goes to slot ``k % capacity``; binding zeroes the count."""
+        [.., 2] (under the head policy source "inter": [.., S + 1], the step's reward rows, and ``obs`` / ``next_obs`` hold ``obs_inter``
+        rows), ``done`` uint8.  The k-th TTI recorded since binding goes to slot ``k % capacity``; binding zeroes the count."""
         capacity = int(capacity)
-        ring = {f: torch.zeros((max(capacity, 0),) + shape(self.B, self.S), dtype=dt, device=self.device) for f, (dt, shape) in self.REPLAY_SHAPES.items()}
+        shapes, _ = self._head_shapes(self.REPLAY_SHAPES, "")
+        ring = {f: torch.zeros((max(capacity, 0),) + shape(self.B, self.S), dtype=dt, device=self.device) for f, (dt, shape) in shapes.items()}
         st = _lib.Replay()
         st.capacity = capacity
         for f, t in ring.items():
@@ -611,13 +653,12 @@ class BatchedRanEnv:
         self._check(self._lib.ranenv_get_replay_count(self._h, C.byref(n)), "ranenv_get_replay_count")
         return int(n.value)
 
-    def replay_sample(self, n: int, seed: int = 0, draw: int = 0, reward: str = "twc") -> Dict[str, torch.Tensor]:
+    def replay_sample(self, n: int, seed: int = 0, draw: int = 0, reward: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """``n`` transitions drawn uniformly from the filled part of the ring (ranenv_replay_sample), in the learner's dtypes: ``obs``
         / ``next_obs`` float32 [n, 10*S], ``action`` float32 [n, S], ``reward`` float32 [n] (column "twc" / "colran" of
-        ``reward_head``), ``done`` uint8 [n], ``index`` int64 [n] (slot * B + env).  A function of (``seed``, ``draw``, the fill)
+        ``reward_head``; under the head policy source "inter": "ibsched", column 0; None = the source's first), ``done`` uint8 [n], ``index`` int64 [n] (slot * B + env).  A function of (``seed``, ``draw``, the fill)
         alone.  The tensors are allocated once per ``n`` and REUSED."""
-        if reward not in HEAD_REWARDS:
-            raise ValueError(f"reward must be one of {sorted(HEAD_REWARDS)}")
+        col = head_reward_column(self.head_observation, reward)
         n = int(n)
         cache = self._keep.setdefault("replay_samples", {})
         if n >= 1 and n not in cache:
@@ -628,7 +669,7 @@ class BatchedRanEnv:
         out = cache.get(n, {})
         m64 = 2 ** 64 - 1
         with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_replay_sample(self._h, n, int(seed) & m64, int(draw) & m64, HEAD_REWARDS[reward],
+            self._check(self._lib.ranenv_replay_sample(self._h, n, int(seed) & m64, int(draw) & m64, col,
                                                        *(_ptr(out.get(f)) for f in ("obs", "action", "reward", "next_obs", "done", "index")),
                                                        self._stream()), "ranenv_replay_sample")
         return out

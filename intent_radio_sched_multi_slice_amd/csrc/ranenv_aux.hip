@@ -512,7 +512,7 @@ __global__ void __launch_bounds__(256) ranenv_replay_sample_kernel(const ReplayS
     for (int w = l; w < 5 * a.S; w += GRP) { po[w] = so[w]; pn[w] = sn[w]; }
     for (int j = l; j < a.S; j += GRP) a.action[out * S + j] = (float)a.ring_action[row * S + j];
     if (l == 0) {
-        a.reward[out] = (float)a.ring_reward[row * 2 + a.reward_col];
+        a.reward[out] = (float)a.ring_reward[row * (size_t)a.reward_cols + a.reward_col];
         a.done[out] = a.ring_done[row];
         if (a.index) a.index[out] = (long long)row;
     }

@@ -100,6 +100,7 @@ struct ranenv {
     int net_stochastic = 0; unsigned long long net_seed = 0;
     double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
     int head_dist = 0, head_stochastic = 0; unsigned long long head_seed = 0;
+    int head_src = RANENV_HEAD_SRC_HEAD;        // ranenv_set_head_policy_source: where the head nets' rows and the recorded rewards come from
     float *d_head_log_std = nullptr;
     double *d_head_acc = nullptr, *d_head_ep_acc = nullptr;      // episode sums of the two head rewards [B][2], their log [B][ep_slots][2]
     // off-policy collection (ranenv_bind_replay): the caller's ring and how many TTIs it has taken
@@ -1215,7 +1216,10 @@ static int net_use(ranenv_handle h, KP &kp)
 {
     if (!kp.scores && h->kp.policy == RANENV_POLICY_HEAD_NETWORK) {
         if (!h->head.on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
-        if (!h->kp.head_obs) return fail(h, RANENV_E_STATE, "the head policy network reads dev_obs_head: none is bound (ranenv_bind_head_outputs)");
+        if (h->head_src == RANENV_HEAD_SRC_INTER) {
+            if (!kp.obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
+        } else if (!h->kp.head_obs)
+            return fail(h, RANENV_E_STATE, "the head policy network reads dev_obs_head: none is bound (ranenv_bind_head_outputs)");
         kp.scores = h->d_net_scores;
         return 1;
     }
@@ -1229,8 +1233,12 @@ static int net_use(ranenv_handle h, KP &kp)
 }
 
 static bool head_policy(ranenv_handle h) { return h->kp.policy == RANENV_POLICY_HEAD_NETWORK; }
+// ... with RANENV_HEAD_SRC_INTER (IBSchedSB3): the head nets read the call's obs_inter rows, a recording takes the step's reward rows
+static bool head_inter(ranenv_handle h) { return head_policy(h) && h->head_src == RANENV_HEAD_SRC_INTER; }
+static int head_reward_cols(ranenv_handle h) { return h->head_src == RANENV_HEAD_SRC_INTER ? h->cfg.n_slices + 1 : 2; }
 
-// The policy launches' inputs and outputs under the handle's policy (NETWORK, or HEAD_NETWORK: the head observation as obs_inter)
+// The policy launches' inputs and outputs under the handle's policy (NETWORK, or HEAD_NETWORK: the head observation -- or, by the head
+// policy source, the call's own obs_inter -- as obs_inter)
 static PolicyIO net_io(ranenv_handle h, const KP &kp)
 {
     const bool head = head_policy(h);
@@ -1241,7 +1249,7 @@ static PolicyIO net_io(ranenv_handle h, const KP &kp)
     io.scores = h->d_net_scores;
     if (head) {
         io.dist = h->head_dist; io.stochastic = h->head_stochastic; io.seed = h->head_seed;
-        io.obs_inter = h->kp.head_obs; io.log_std = h->head_dist == RANENV_HEAD_DIST_GAUSS_CLIP ? h->d_head_log_std : nullptr;
+        io.obs_inter = head_inter(h) ? kp.obs_inter : h->kp.head_obs; io.log_std = h->head_dist == RANENV_HEAD_DIST_GAUSS_CLIP ? h->d_head_log_std : nullptr;
         return io;
     }
     io.stochastic = h->net_stochastic; io.seed = h->net_seed;
@@ -1373,6 +1381,16 @@ int ranenv_set_head_value_network(ranenv_handle h, const ranenv_mlp *critic, voi
     return net_commit(h, &b, 1, (hipStream_t)stream);
 }
 
+int ranenv_set_head_policy_source(ranenv_handle h, int32_t source)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (source != RANENV_HEAD_SRC_HEAD && source != RANENV_HEAD_SRC_INTER) return fail(h, RANENV_E_INVALID, "unknown head policy source %d", source);
+    if (source == h->head_src) return RANENV_OK;
+    h->head_src = source;
+    h->ring = ranenv_replay{}; h->ring_on = false; h->ring_written = 0;      // (its reward rows change width)
+    return RANENV_OK;
+}
+
 static int check_ready(ranenv_handle h, const float *se_tiles, const double *traffic_bits, bool need_traffic)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
@@ -1419,11 +1437,11 @@ static int step_begin(ranenv_handle h, int32_t env_first, int32_t env_count, con
     if (!scores && h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "policy is EXTERNAL but no inter-slice scores were given");
     rc = slice_metrics_outputs(h, obs_intra, reward);
     if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
     *kp = call_kp(h, obs_inter, obs_intra, reward, done);
     kp->se_tiles = se_tiles; kp->scores = scores; kp->intra = intra; kp->traffic_bits = traffic_bits;
     const int net = net_use(h, *kp);
     if (net < 0) return net;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
     rc = compact_for(h, *kp, stream, &kp->compact);
     if (rc != RANENV_OK) return rc;
     *net_err = net ? net_launch(h, *kp, env_first, env_count, stream) : hipSuccess;
@@ -1673,8 +1691,8 @@ struct Record {
     double gamma = 0.0, lambda = 0.0;
     float *adv = nullptr, *vtarg = nullptr;
 };
-// ... or ranenv_collect_replay's ring; and, either way, where the step writes a TTI's done flags and reward rows (under a head policy: the
-// head kernel its reward pairs) instead of the caller's buffers: slot (first + t) % slots of [slots][B] / [slots][B][reward_cols]
+// ... or ranenv_collect_replay's ring; and, either way, where the step writes a TTI's done flags and reward rows (under a head policy
+// with source HEAD: the head kernel its reward pairs) instead of the caller's buffers: slot (first + t) % slots of [slots][B] / [slots][B][reward_cols]
 struct Recording {
     const Record *ppo = nullptr;
     const ranenv_replay *ring = nullptr;
@@ -1803,18 +1821,18 @@ static hipError_t rollout_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0
     hipError_t le = ppo ? collect_policy(h, *ppo, kpk, t, false, e0, n, s) : (r.net ? net_launch(h, kpk, e0, n, s) : hipSuccess);
     if (le != hipSuccess) return le;
     // 2. the step's done flags and reward rows go straight into the slot (the kernels index them by env; the reset writes neither, reset_behind)
-    if (rec && rec->reward) (head_policy(h) ? kpk.head_reward : kpk.reward) = rec->reward + row * (size_t)rec->reward_cols;
+    if (rec && rec->reward) (head_policy(h) && !head_inter(h) ? kpk.head_reward : kpk.reward) = rec->reward + row * (size_t)rec->reward_cols;
     if (rec && rec->done) kpk.done = rec->done + row;
     // 3. ring: the partition's rows -- one contiguous range of the slot -- of the observation the action was computed from and of the scores
     // the step consumes (one launch for both: the actor only read the observation)
     typedef unsigned long long word;
     const size_t at = row + (size_t)e0;
     const long long obs_words = (long long)n * 5 * (long long)S;      // a row: 10 * S floats
-    const word *head_rows = ring ? (const word *)(h->kp.head_obs + (size_t)e0 * 10 * S) : nullptr;
+    const word *head_rows = ring ? (const word *)((head_inter(h) ? kpk.obs_inter : h->kp.head_obs) + (size_t)e0 * 10 * S) : nullptr;
     if (ring)
         launch_copy_words(s, (word *)(ring->obs + at * 10 * S), head_rows, obs_words, (word *)(ring->action + at * S),
                           (const word *)(h->d_net_scores + (size_t)e0 * S), (long long)n * (long long)S);
-    // 4. the step;  5. ring: the observation the head kernel left;  6. the episode ends, by the slot's flags
+    // 4. the step;  5. ring: the observation the head kernel (source INTER: the step) left;  6. the episode ends, by the slot's flags
     le = launch_range<MODE_STEP>(h, kpk, e0, n, s);
     if (le != hipSuccess) return le;
     if (ring) launch_copy_words(s, (word *)(ring->next_obs + at * 10 * S), head_rows, obs_words, nullptr, nullptr, 0);
@@ -1883,6 +1901,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     rc = slice_metrics_outputs(h, obs_intra, reward);
     if (rc != RANENV_OK) return rc;
     if (h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "a rollout needs a device policy (ranenv_set_policy MARR / MAPF / NETWORK)");
+    if (head_inter(h) && h->head.on && !obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
     const bool have_se = h->kp.se_pool != nullptr || (h->se_mode == RANENV_SE_GATHER && h->d_se_mean != nullptr);
     if (!have_se || (!h->kp.trf_pool && !h->kp.trf_gen)) return fail(h, RANENV_E_STATE, "a rollout replays the bound SE pool and traffic pool / generator");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1929,10 +1948,10 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     rc = persist_ok ? rollout_persistent(h, r, stream) : rollout_chunks(h, r, stream);
     if (rc != RANENV_OK) return rc;
     if (rec) {
-        // (the partitions have joined the caller's stream)  The caller's reward -- under a head policy: the bound head rewards -- and
+        // (the partitions have joined the caller's stream)  The caller's reward -- under a head policy with source HEAD: the bound head rewards -- and
         // done hold the last TTI's values, as after a rollout
         const size_t B = (size_t)h->cfg.batch, C = (size_t)rec->reward_cols, last = rec->slot(n_steps - 1) * B;
-        double *last_reward = head_policy(h) ? h->kp.head_reward : reward;
+        double *last_reward = head_policy(h) && !head_inter(h) ? h->kp.head_reward : reward;
         if (rec->reward && last_reward)
             HIP_TRY(h, hipMemcpyAsync(last_reward, rec->reward + last * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
         if (rec->done && done) HIP_TRY(h, hipMemcpyAsync(done, rec->done + last, B, hipMemcpyDeviceToDevice, stream));
@@ -1979,13 +1998,25 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
 
 static_assert(sizeof(ranenv_head_trajectory) == RANENV_HEAD_TRAJECTORY_BYTES, "ranenv_head_trajectory: 8 device pointers");
 
+// ranenv_collect_head / ranenv_replay_sample: the column of the recorded reward rows, by the head policy source
+static int head_reward_col_check(ranenv_handle h, int32_t reward_col)
+{
+    if (h->head_src == RANENV_HEAD_SRC_INTER) {
+        if (reward_col < 0 || reward_col > h->cfg.n_slices)
+            return fail(h, RANENV_E_INVALID, "reward_col %d (source INTER: 0 = player_0 .. %d of the step's reward row)", reward_col, h->cfg.n_slices);
+        return RANENV_OK;
+    }
+    if (reward_col != 0 && reward_col != 1) return fail(h, RANENV_E_INVALID, "reward_col %d (0 = SchedTWC, 1 = SchedColORAN)", reward_col);
+    return RANENV_OK;
+}
+
 int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, int32_t reward_col, double gamma, double lambda,
                         float *obs_inter, float *obs_intra, double *reward, uint8_t *done, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!traj) return fail(h, RANENV_E_INVALID, "null trajectory");
     if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
-    if (reward_col != 0 && reward_col != 1) return fail(h, RANENV_E_INVALID, "reward_col %d (0 = SchedTWC, 1 = SchedColORAN)", reward_col);
+    if (const int rc = head_reward_col_check(h, reward_col); rc != RANENV_OK) return rc;
     if ((traj->adv || traj->vtarg) && !(traj->reward_head && traj->vf && traj->done))
         return fail(h, RANENV_E_INVALID, "adv / vtarg need the record's reward_head, vf and done");
     if (h->kp.policy != RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect_head needs policy HEAD_NETWORK (ranenv_set_policy)");
@@ -1997,7 +2028,7 @@ int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_traj
     ppo.rec.obs_inter = traj->obs_head; ppo.rec.action_inter = traj->action; ppo.rec.logp = traj->logp; ppo.rec.vf = traj->vf;
     ppo.rec.cols = 1; ppo.gae_col = reward_col;
     ppo.gamma = gamma; ppo.lambda = lambda; ppo.adv = traj->adv; ppo.vtarg = traj->vtarg;
-    const Recording rec{&ppo, nullptr, traj->done, traj->reward_head, 2, 0, n_steps};
+    const Recording rec{&ppo, nullptr, traj->done, traj->reward_head, head_reward_cols(h), 0, n_steps};
     return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec);
 }
 
@@ -2034,9 +2065,14 @@ int ranenv_collect_replay(ranenv_handle h, int32_t n_steps, float *obs_inter, fl
     if (n_steps > h->ring.capacity) return fail(h, RANENV_E_INVALID, "n_steps %d exceeds the ring's capacity %d", n_steps, h->ring.capacity);
     if (h->kp.policy != RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect_replay needs policy HEAD_NETWORK (ranenv_set_policy)");
     if (!h->head.on) return fail(h, RANENV_E_STATE, "policy HEAD_NETWORK but no head policy network bound (ranenv_set_head_policy_network)");
-    if (!h->kp.head_obs) return fail(h, RANENV_E_STATE, "the replay ring records dev_obs_head: none is bound (ranenv_bind_head_outputs)");
-    if (!aligned8(h->kp.head_obs)) return fail(h, RANENV_E_INVALID, "the replay ring copies dev_obs_head as 8-byte words: it must be 8-byte aligned");
-    const Recording rec{nullptr, &h->ring, h->ring.done, h->ring.reward_head, 2, h->ring_written, h->ring.capacity};
+    if (head_inter(h)) {
+        if (!obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
+        if (!aligned8(obs_inter)) return fail(h, RANENV_E_INVALID, "the replay ring copies dev_obs_inter as 8-byte words: it must be 8-byte aligned");
+    } else {
+        if (!h->kp.head_obs) return fail(h, RANENV_E_STATE, "the replay ring records dev_obs_head: none is bound (ranenv_bind_head_outputs)");
+        if (!aligned8(h->kp.head_obs)) return fail(h, RANENV_E_INVALID, "the replay ring copies dev_obs_head as 8-byte words: it must be 8-byte aligned");
+    }
+    const Recording rec{nullptr, &h->ring, h->ring.done, h->ring.reward_head, head_reward_cols(h), h->ring_written, h->ring.capacity};
     return rollout_run(h, n_steps, obs_inter, obs_intra, reward, done, stream, &rec);
 }
 
@@ -2045,14 +2081,14 @@ int ranenv_replay_sample(ranenv_handle h, int64_t n, uint64_t seed, uint64_t dra
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (n < 1 || n > (int64_t)0x7FFFFFFF * (256 / GRP)) return fail(h, RANENV_E_INVALID, "n must be >= 1 (and fit one launch)");
-    if (reward_col != 0 && reward_col != 1) return fail(h, RANENV_E_INVALID, "reward_col %d (0 = SchedTWC, 1 = SchedColORAN)", reward_col);
+    if (const int rc = head_reward_col_check(h, reward_col); rc != RANENV_OK) return rc;
     if (!dev_obs || !dev_action || !dev_reward || !dev_next_obs || !dev_done) return fail(h, RANENV_E_INVALID, "replay sample: only dev_index may be NULL");
     if (!aligned8(dev_obs) || !aligned8(dev_next_obs)) return fail(h, RANENV_E_INVALID, "replay sample: dev_obs / dev_next_obs must be 8-byte aligned");
     if (!h->ring_on || h->ring_written == 0) return fail(h, RANENV_E_STATE, "the replay ring holds no transitions (ranenv_bind_replay, ranenv_collect_replay)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     ReplaySampleArgs a{};
     const long long filled = h->ring_written < h->ring.capacity ? h->ring_written : h->ring.capacity;
-    a.n = n; a.n_rows = filled * h->cfg.batch; a.B = h->cfg.batch; a.S = h->cfg.n_slices; a.reward_col = reward_col;
+    a.n = n; a.n_rows = filled * h->cfg.batch; a.B = h->cfg.batch; a.S = h->cfg.n_slices; a.reward_col = reward_col; a.reward_cols = head_reward_cols(h);
     a.seed = seed; a.draw = draw;
     a.ring_obs = h->ring.obs; a.ring_next_obs = h->ring.next_obs; a.ring_action = h->ring.action; a.ring_reward = h->ring.reward_head;
     a.ring_done = h->ring.done;

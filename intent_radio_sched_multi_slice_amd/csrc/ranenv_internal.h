@@ -301,6 +301,7 @@ void launch_copy_words(hipStream_t, unsigned long long *dst0, const unsigned lon
 // ranenv_replay_sample: n rows gathered from the ring's first n_rows = min(written, C) * B transitions
 struct ReplaySampleArgs {
     long long n, n_rows; int B, S, reward_col;
+    int reward_cols;                      // doubles per ring reward row: 2 (the head kernel's pair) or S + 1 (the step's row, RANENV_HEAD_SRC_INTER)
     unsigned long long seed, draw;
     const float *ring_obs, *ring_next_obs; const double *ring_action, *ring_reward; const uint8_t *ring_done;
     float *obs, *action, *reward, *next_obs; uint8_t *done; long long *index;
