@@ -376,6 +376,48 @@ int ranenv_bind_se_gather_from_power(ranenv_handle h, const double *dev_power, i
 /* Diagnostic: the gather mode's sidecars: row_mean [n_tiles][U] float64, ue_major [n_tiles][U][row_floats] float32. */
 int ranenv_get_se_sidecars(ranenv_handle h, double **dev_row_mean, float **dev_ue_major, int32_t *row_floats);
 
+/* Scenario load: the agent-independent figures of the evaluation (results/gen_results.py: ues_spectral_efficiencies :260-276,
+ * throughput_per_rb :277-358, rbs_needed_slice / rbs_needed_total :361-497, plot_rbs_needed_network_scenarios :1251-1451).  They are a
+ * function of the pooled tiles and the scenario rows alone; no env is stepped, and nothing a step, rollout or collect call
+ * enqueues changes.
+ *
+ * ranenv_build_se_stats builds (or rebuilds) the per-tile statistics of the float32 pool bound now, either layout, any
+ * tile_stride: handle-owned float64 [n_tiles][4][U], per UE over its R RBs, in float64 on the float32 values:
+ *     [0] np.mean   numpy's pairwise order: bit for bit the gather sidecar's row_mean
+ *     [1] np.std    population (ddof = 0): sqrt(pairwise_sum((x - mean) * (x - mean)) / R), the same order over the squares
+ *     [2] np.min    [3] np.max
+ *   One streaming pass over the pool (the row is walked twice; the second walk re-reads what the workgroup has just loaded).
+ *   RANENV_E_STATE without a bound float32 pool -- a handle fed by ranenv_bind_se_gather_from_power alone has none.  Binding a
+ *   pool (ranenv_bind_se_pool / _quad / _gather_from_power) drops the statistics, as it drops the gather mode; the memory is
+ *   reused by the next build.  The call returns when the statistics are complete.
+ * ranenv_get_se_stats hands out the array (RANENV_E_STATE while none is built).
+ *
+ * ranenv_rbs_needed evaluates n_episodes descriptors (host memory; only scenario and the three se_ fields are read) over steps
+ * t = 0 .. n_steps - 1, step t on tile se_base + (se_offset + t) % se_len and the descriptor's own scenario row.  Per slice s in
+ * INDEX order, with member[u] = (ue_slice[u] == s), den their count, sums over all U entries in numpy's pairwise order:
+ *     avg_se = sum(mean * member) / den, min_se = sum((mean - std) * member) / den, max_se = sum((mean + std) * member) / den
+ *     (0 where den is 0), thr = slice_has_req ? slice_traffic : 0, per_rb = (bandwidth_hz / 1e6) / R, and
+ *   dev_slice   [n_episodes][n_steps][S][RANENV_LOAD_SLICE_COLS] float64:
+ *     [0] avg_needed = thr * den / (per_rb * avg_se) where avg_se > 0, else 0
+ *     [1] min_needed = the same with max_se          [2] max_needed = the same with min_se, then clipped to R -- the only clipped
+ *         column; where min_se <= 0 it is 0, not R, as in the reference
+ *     [3..5] throughput_per_rb = sum(stat * member) * (bandwidth_hz / 1e6) / (den * R) for stat = mean, min, max (0 where den is 0)
+ *   dev_network [n_episodes][n_steps][3]: columns [0..2] added over slices 0 .. S-1 one after the other
+ *   dev_episode_mean [n_episodes][3]: np.mean of the network rows over the steps -- numpy's pairwise recursion over the n_steps
+ *     values of a column, divided by n_steps: bit for bit np.mean's up to 8192 steps (beyond that numpy itself adds up blocks of
+ *     8192 and the last bits may differ).  [0] is the reference's total_avg_needed_rbs, by which it ranks scenarios.  More than R
+ *     there: no agent can meet that episode's intents on average.
+ *   dev_slice and dev_network may be NULL (the episode means come out the same); dev_episode_mean is required.  All caller-owned
+ *   device memory.  Everything is validated before the first device call: NULL arguments, n_episodes < 1, n_steps < 1,
+ *   n_episodes * n_steps >= 2^31, a scenario outside the pool, se_len < 1, an offset outside [0, se_len), a trace outside the pool
+ *   the statistics were built from: RANENV_E_INVALID; no scenarios loaded or no statistics built: RANENV_E_STATE.  The call
+ *   returns when the results are complete. */
+#define RANENV_LOAD_SLICE_COLS 6
+int ranenv_build_se_stats(ranenv_handle h, void *stream);
+int ranenv_get_se_stats(ranenv_handle h, double **dev_stats, int64_t *n_tiles);
+int ranenv_rbs_needed(ranenv_handle h, const ranenv_episode *host_episodes, int32_t n_episodes, int32_t n_steps, double *dev_slice,
+                      double *dev_network, double *dev_episode_mean, void *stream);
+
 /* Per-launch timing: between ranenv_profile_begin and ranenv_profile_end every launch of the step kernel carries its
  * dispatch's own start / stop timestamps (hipExtLaunchKernel events, valid with further launches queued behind it).
  * ranenv_profile_end waits for the device and returns the average duration in ms over n_launches launches (with

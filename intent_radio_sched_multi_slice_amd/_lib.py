@@ -22,6 +22,7 @@ INTRA_RR, INTRA_PF, INTRA_MT, INTRA_PER_SLICE = 0, 1, 2, 255
 F_CLEAR_HISTORY_ON_RESET, F_NO_RAW_OUTPUT, F_SYNC_CHECK, F_SCALE_PER_ELEMENT = 0x1, 0x2, 0x4, 0x8
 SE_STREAM, SE_GATHER = 0, 1
 SLICE_METRIC_COLS = 10
+LOAD_SLICE_COLS = 6
 
 class RanEnvError(RuntimeError):
     pass
@@ -168,6 +169,9 @@ FUNCTIONS = {
     "ranenv_set_intra_policy_networks": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), _P]),
     "ranenv_set_intra_value_networks": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), _P]),
     "ranenv_set_head_policy_source": (C.c_int, [_P, _I32]),
+    "ranenv_build_se_stats": (C.c_int, [_P, _P]),
+    "ranenv_get_se_stats": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "ranenv_rbs_needed": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(FUNCTIONS)
 

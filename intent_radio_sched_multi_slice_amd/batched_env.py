@@ -353,6 +353,49 @@ class BatchedRanEnv:
         return {"row_mean": torch.as_tensor(_DevArray(mean.value, (n, self.U), "f8", self), device=self.device),
                 "ue_major": torch.as_tensor(_DevArray(um.value, (n, self.U, rp.value), "f4", self), device=self.device)}
 
+    # ------------------------------------------------------------------------------------------
+    # scenario load: the agent-independent figures of results/gen_results.py, without a single env step
+    def se_tile_stats(self, rebuild: bool = False) -> torch.Tensor:
+        """Per-tile statistics of the bound SE pool, zero copy: float64 [n_tiles, 4, U] = np.mean, np.std (population), np.min,
+        np.max of every UE's SE over the R RBs, bit for bit numpy's on the float64 of the float32 values.  Built on first use for
+        the pool bound now (one streaming pass; ``rebuild``: again, after the pool's contents changed); binding another pool
+        drops them.  The reference's ``ues_spectral_efficiencies`` (gen_results.py:260-276) at TTI t of an episode is row
+        ``se_base + (se_offset + t) % se_len``."""
+        stats, n = C.c_void_p(), C.c_int64()
+        with torch.cuda.device(self.device):
+            if rebuild or self._lib.ranenv_get_se_stats(self._h, C.byref(stats), C.byref(n)) != 0:
+                self._check(self._lib.ranenv_build_se_stats(self._h, self._stream()), "ranenv_build_se_stats")
+            self._check(self._lib.ranenv_get_se_stats(self._h, C.byref(stats), C.byref(n)), "ranenv_get_se_stats")
+        return torch.as_tensor(_DevArray(stats.value, (int(n.value), 4, self.U), "f8", self), device=self.device)
+
+    def scenario_load(self, episodes=None, n_steps: Optional[int] = None, per_step: bool = False) -> Dict[str, torch.Tensor]:
+        """How many RBs the network would need to serve every slice's requested traffic (gen_results.py:361-497, :1251-1451), per
+        episode descriptor, from the tile statistics and the scenario rows alone.  ``episodes``: a structured array as
+        ``set_episode_table`` / ``episode_descriptors`` keep them (default: the bound episode table, else the envs' current
+        descriptors); ``n_steps``: TTIs per episode (default ``max_steps``).  -> ``episode_mean`` float64 [n, 3]: the mean over the
+        steps of the network's (avg, min, max) needed RBs -- column 0 is what the reference ranks scenarios by
+        (``scenario.rank_by_load``), and more than R there means no agent can meet that episode's intents on average.  With
+        ``per_step`` also ``per_step_network`` [n, T, 3] and ``per_step_slice`` [n, T, S, 6] (avg / min / max needed RBs, then the
+        capacity per RB in Mbps from the mean / min / max SE; the columns are spelled out in include/ranenv.h)."""
+        if episodes is None:
+            episodes = getattr(self, "episode_table", None)
+            if episodes is None:
+                episodes = self.episode_descriptors()
+        if episodes is None:
+            raise RanEnvError("scenario_load: no episodes given and none set (set_episode_table / set_episodes)")
+        eps = np.ascontiguousarray(np.atleast_1d(episodes), dtype=self._EP_DTYPE)
+        n, T = int(eps.shape[0]), int(self.max_steps if n_steps is None else n_steps)
+        self.se_tile_stats()
+        out = {"episode_mean": torch.empty((n, 3), dtype=torch.float64, device=self.device)}
+        if per_step:
+            out["per_step_slice"] = torch.empty((n, max(T, 0), self.S, _lib.LOAD_SLICE_COLS), dtype=torch.float64, device=self.device)
+            out["per_step_network"] = torch.empty((n, max(T, 0), 3), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_rbs_needed(self._h, C.c_void_p(eps.ctypes.data), n, T, _ptr(out.get("per_step_slice")),
+                                                    _ptr(out.get("per_step_network")), _ptr(out["episode_mean"]), self._stream()),
+                        "ranenv_rbs_needed")
+        return out
+
     def bind_traffic_pool(self, traffic_pool: torch.Tensor):
         """int32 [rows, U] offered bits per UE and TTI (traffics/mult_slice.py:26-32)."""
         if traffic_pool.dtype != torch.int32 or traffic_pool.device != self.device or not traffic_pool.is_contiguous():

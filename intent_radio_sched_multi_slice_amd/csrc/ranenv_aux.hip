@@ -70,6 +70,38 @@ __global__ void __launch_bounds__(256) ranenv_se_retile_quad_kernel(const float 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-tile statistics of the SE pool (ranenv_build_se_stats): what the scenario load figures read of a tile
+// (results/gen_results.py:260-497, :1251-1451), per UE over its R RBs, in float64 on the float32 values:
+//   stats[tile][0][u] = np.mean  -- row_sums' `full` / R: the gather sidecar's row_mean bit for bit
+//   stats[tile][1][u] = np.std   -- sqrt(pairwise_sum((x - mean) * (x - mean)) / R), population (ddof = 0): the same leaves over the squares
+//   stats[tile][2][u], [3][u] = np.min, np.max (the quad layout's padding behind RB R-1 is never shown to them)
+// The sidecar kernel's launch shape: one workgroup per tile, thread = UE; stat-major rows, so a wave stores whole lines.  The
+// deviations need the mean first: the row is walked twice, and the second walk re-reads what this workgroup has just pulled
+// through L2 (plain loads: SeStream<4> carries no non-temporal bit).  Plain / and sqrt: correctly rounded in this build.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(CORE_NT) ranenv_se_tile_stats_kernel(const float *pool, long long stride, long long tile0, int U, int R, int quad,
+                                                                       double *stats)
+{
+    const long long t = tile0 + blockIdx.x;
+    const float *tile = pool + (size_t)t * (size_t)stride;
+    const int tid = threadIdx.x;
+    const int u = tid < U ? tid : U - 1;
+    SeStream<4> se;
+    se.init(tile, U, u, R, quad != 0);
+    double sum = 0.0, none = 0.0;
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    row_sums(se, R, RowNoPart(), sum, none, []() {}, 1.0, RowIdentity(), [&](float x) { lo = x < lo ? x : lo; hi = x > hi ? x : hi; });
+    const double mean = sum / (double)R;
+    se.init(tile, U, u, R, quad != 0);
+    double sq = 0.0;
+    row_sums(se, R, RowNoPart(), sq, none, []() {}, 1.0, [mean](double d) { const double e = d - mean; return e * e; });
+    if (tid < U) {
+        double *out = stats + (size_t)t * 4 * (size_t)U + tid;
+        out[0] = mean; out[(size_t)U] = sqrt(sq / (double)R); out[2 * (size_t)U] = (double)lo; out[3 * (size_t)U] = (double)hi;
+    }
+}
+
 // Gather-only ingest (ranenv_bind_se_gather_from_power): the same two sidecars straight from QuaDRiGa received power
 // (channels/quadriga.py:56-69), without an RB-major float32 pool ever existing.  The float32 SE of an element is what
 // ranenv_se_from_power would have stored; the mean runs through row_sums over those float32 values, so both sidecars are bit for
@@ -133,17 +165,53 @@ struct SharedHead {
     double terms[3 * GRP], nw[3 * GRP];   // the reward's terms and weights (one lane fills them: LDS, not 784 B of scratch per lane)
 };
 
-// numpy pairwise_sum of n < 128 doubles by one lane
-DEVFN double np_sum_seq(const double *a, int n)
+// numpy pairwise_sum of n <= 128 doubles by one lane: a leaf of its recursion over elements a(0) .. a(n - 1)
+template <typename Elem>
+DEVFN double np_leaf(Elem a, int n)
 {
-    if (n < 8) { double r = 0.0; for (int i = 0; i < n; i++) r += a[i]; return r; }
+    if (n < 8) { double r = 0.0; for (int i = 0; i < n; i++) r += a(i); return r; }
     double r[8];
-    for (int j = 0; j < 8; j++) r[j] = a[j];
+    for (int j = 0; j < 8; j++) r[j] = a(j);
     int i = 8;
-    for (; i < n - (n % 8); i += 8) for (int j = 0; j < 8; j++) r[j] += a[i + j];
+    for (; i < n - (n % 8); i += 8) for (int j = 0; j < 8; j++) r[j] += a(i + j);
     double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += a[i];
+    for (; i < n; i++) res += a(i);
     return res;
+}
+DEVFN double np_sum_seq(const double *a, int n) { return np_leaf([a](int i) { return a[i]; }, n); }
+
+// numpy pairwise_sum of any n by one lane: above 128 elements numpy halves the range at a multiple of 8 and adds the two halves'
+// sums, left + right.  The recursion is walked with an explicit stack of frames in LDS (`stack`: PW_DEPTH frames of this lane's own;
+// a kernel that recursed would need scratch): a range of 2^31 elements is 25 frames deep.
+struct PwFrame { int off, n, right_next; double left; };
+enum { PW_DEPTH = 26 };
+template <typename Elem>
+DEVFN double np_pairwise(Elem a, int n, PwFrame *stack)
+{
+    int top = 0;
+    stack[0].off = 0; stack[0].n = n; stack[0].right_next = 0;
+    for (;;) {
+        const int off = stack[top].off, len = stack[top].n;
+        if (len > 128) {                           // descend into the left half
+            int h = len / 2; h -= h % 8;
+            stack[top + 1].off = off; stack[top + 1].n = h; stack[top + 1].right_next = 0;
+            top += 1;
+            continue;
+        }
+        double v = np_leaf([&](int i) { return a(off + i); }, len);
+        for (;;) {                                 // hand the finished range's sum to its parent
+            if (top == 0) return v;
+            top -= 1;
+            if (!stack[top].right_next) {          // it was the left half: keep it, walk the right half
+                int h = stack[top].n / 2; h -= h % 8;
+                stack[top].left = v; stack[top].right_next = 1;
+                stack[top + 1].off = stack[top].off + h; stack[top + 1].n = stack[top].n - h; stack[top + 1].right_next = 0;
+                top += 1;
+                break;
+            }
+            v = stack[top].left + v;
+        }
+    }
 }
 
 __global__ void __launch_bounds__(CORE_NT) ranenv_head_kernel(const KP p, double *head_acc, int reset)
@@ -347,6 +415,78 @@ __global__ void __launch_bounds__(CORE_NT) ranenv_slice_metrics_kernel(const KP 
     else if (pos == 5) add = dmin < 0.0 ? dmin : 0.0;
     else add = (oa[pos + 1] > 0.0f && oa[pos - 2] < 0.0f) ? 1.0 : 0.0;       // metric pos - 2: declared flag [3 + m], drift [m]
     if (pos < RANENV_SLICE_METRIC_COLS) *cell += add;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Scenario load (ranenv_rbs_needed; the columns are spelled out in include/ranenv.h): the RBs a slice would need to serve its
+// intent's traffic and its capacity per RB (results/gen_results.py:277-497, :1251-1451), from the tile statistics and the scenario
+// row alone -- no env is stepped.  One workgroup = one (episode, step); thread u holds UE u's four statistics.  Lane 6 s + k then adds
+// row k (mean, mean - std, mean + std, min, max, the membership itself) times slice s's membership over ALL U entries, the zeros in
+// place, in numpy's pairwise order (np.sum(x * slice_ues, axis=1)); lane s makes slice s's divisions, three lanes add the slices up
+// in index order.  Small and cold: ~100 lanes walk an LDS row each.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(CORE_NT) ranenv_rbs_needed_kernel(const RbsArgs a)
+{
+    __shared__ double rows[5][CORE_NT];
+    __shared__ int slc[CORE_NT];
+    __shared__ double sums[GRP][6], need[GRP][3];
+    __shared__ PwFrame stack[6 * GRP][3];             // U <= 256: one split at most
+    const int tid = threadIdx.x, S = a.S, U = a.U;
+    const int ei = (int)(blockIdx.x / (unsigned)a.n_steps), t = (int)(blockIdx.x - (unsigned)ei * (unsigned)a.n_steps);
+    const ranenv_episode ep = a.eps[ei];
+    const double *st = a.stats + (size_t)se_tile_of(ep, t) * 4 * (size_t)U;
+    if (tid < U) {
+        const double mean = st[tid], sd = st[(size_t)U + tid];
+        rows[0][tid] = mean; rows[1][tid] = mean - sd; rows[2][tid] = mean + sd;
+        rows[3][tid] = st[2 * (size_t)U + tid]; rows[4][tid] = st[3 * (size_t)U + tid];
+        slc[tid] = a.ue_slice[(size_t)ep.scenario * U + tid];
+    }
+    __syncthreads();
+    if (tid < 6 * S) {
+        const int s = tid / 6, k = tid - 6 * s;
+        const double *row = rows[k < 5 ? k : 0];
+        sums[s][k] = np_pairwise([&](int i) { const double m = slc[i] == s ? 1.0 : 0.0; return k < 5 ? row[i] * m : m; }, U, stack[tid]);
+    }
+    __syncthreads();
+    if (tid < S) {
+        const int s = tid;
+        const size_t trow = (size_t)ep.scenario * S + s;
+        const double den = sums[s][5], R = (double)a.R;
+        const bool some = den != 0.0;
+        const double avg_se = some ? sums[s][0] / den : 0.0, min_se = some ? sums[s][1] / den : 0.0, max_se = some ? sums[s][2] / den : 0.0;
+        const double thr = a.slice_i32[trow * 8 + 1] != 0 ? a.slice_f64[trow * 2 + 1] : 0.0;
+        const double per_rb = a.bw_mhz / R, want = thr * den;
+        const double avg_n = avg_se > 0.0 ? want / (per_rb * avg_se) : 0.0;
+        const double min_n = max_se > 0.0 ? want / (per_rb * max_se) : 0.0;
+        double max_n = min_se > 0.0 ? want / (per_rb * min_se) : 0.0;       // (not R where the low SE is not positive: the reference's rule)
+        max_n = max_n > R ? R : max_n;                                      // the only column that is clipped, per slice
+        need[s][0] = avg_n; need[s][1] = min_n; need[s][2] = max_n;
+        if (a.slice_out) {
+            double *o = a.slice_out + ((size_t)blockIdx.x * S + s) * RANENV_LOAD_SLICE_COLS;
+            o[0] = avg_n; o[1] = min_n; o[2] = max_n;
+            o[3] = some ? (sums[s][0] * a.bw_mhz) / (den * R) : 0.0;
+            o[4] = some ? (sums[s][3] * a.bw_mhz) / (den * R) : 0.0;
+            o[5] = some ? (sums[s][4] * a.bw_mhz) / (den * R) : 0.0;
+        }
+    }
+    __syncthreads();
+    if (tid < 3) {
+        double r = need[0][tid];
+        for (int s = 1; s < S; s++) r = r + need[s][tid];
+        a.net_out[(size_t)blockIdx.x * 3 + tid] = r;
+    }
+}
+
+// np.mean over an episode's T network rows, per column: numpy's pairwise recursion over T, divided by T (np.mean's bits up to T = 8192,
+// where numpy starts adding up buffer-sized blocks).  One workgroup per episode.
+__global__ void __launch_bounds__(WAVE) ranenv_rbs_episode_mean_kernel(const double *net, int n_steps, double *episode_mean)
+{
+    __shared__ PwFrame stack[3][PW_DEPTH];
+    const int tid = threadIdx.x;
+    if (tid >= 3) return;
+    const double *col = net + (size_t)blockIdx.x * (size_t)n_steps * 3 + tid;
+    const double sum = np_pairwise([col](int i) { return col[(size_t)i * 3]; }, n_steps, stack[tid]);
+    episode_mean[(size_t)blockIdx.x * 3 + tid] = sum / (double)n_steps;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -560,6 +700,16 @@ void launch_se_sidecar(hipStream_t s, unsigned n_tiles, unsigned block, const fl
                        int quad, double *mean, float *um)
 {
     hipLaunchKernelGGL(ranenv_se_sidecar_kernel, dim3(n_tiles), dim3(block), 0, s, pool, stride, tile0, U, R, Rp, quad, mean, um);
+}
+void launch_se_tile_stats(hipStream_t s, unsigned n_tiles, unsigned block, const float *pool, long long stride, long long tile0, int U, int R,
+                          int quad, double *stats)
+{
+    hipLaunchKernelGGL(ranenv_se_tile_stats_kernel, dim3(n_tiles), dim3(block), 0, s, pool, stride, tile0, U, R, quad, stats);
+}
+void launch_rbs_needed(hipStream_t s, unsigned n_episodes, unsigned block, const RbsArgs &a, double *episode_mean)
+{
+    hipLaunchKernelGGL(ranenv_rbs_needed_kernel, dim3(n_episodes * (unsigned)a.n_steps), dim3(block), 0, s, a);
+    hipLaunchKernelGGL(ranenv_rbs_episode_mean_kernel, dim3(n_episodes), dim3(WAVE), 0, s, a.net_out, a.n_steps, episode_mean);
 }
 void launch_se_sidecar_from_power(hipStream_t s, unsigned n_tiles, unsigned block, const double *power, long long tile0, int U, int R, int Rp,
                                   double tx, double noise, double *mean, float *um)

@@ -39,6 +39,11 @@ struct ranenv {
     // SE gather mode (ranenv_set_se_mode): sidecars of the bound pool, owned by the handle
     int se_mode = RANENV_SE_STREAM;
     double *d_se_mean = nullptr; float *d_se_um = nullptr; int se_rp = 0;
+    // scenario load (ranenv_build_se_stats / ranenv_rbs_needed): per-tile statistics of the bound pool [se_stats_n][4][U] (se_stats_n = 0: none
+    // valid; the buffer of se_stats_cap tiles stays for the next build), and the call's staging: descriptors, network rows
+    double *d_se_stats = nullptr; int64_t se_stats_n = 0, se_stats_cap = 0;
+    ranenv_episode *d_load_eps = nullptr; int64_t load_eps_cap = 0;
+    double *d_load_net = nullptr; int64_t load_net_cap = 0;
     // compact steps (KP::compact): allowed while UEs outside every slice provably receive no traffic
     bool idle_check_dirty = true, pool_idle_zero = false, table_idle_zero = false;
     bool idle_state_clean = true;               // no step so far can have given an idle UE packets (else: full width until a full reset)
@@ -643,15 +648,33 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
 
 // Replace the SE gather sidecars by fresh ones for nt tiles (the old ones are released first, behind a device synchronisation), and
 // enqueue fill(t0, n) for tiles [t0, t0 + n) in chunks that keep grid.x far below its limit.  A failed fill launch is the caller's to report.
+void dev_drop(ranenv_handle h, void *ptr)        // release one of the handle's allocations ahead of ranenv_destroy
+{
+    if (!ptr) return;
+    for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == ptr) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
+    (void)hipFree(ptr);
+}
+
+// A handle-owned scratch buffer of at least `count` elements (contents undefined; an outgrown one is released, nothing is running on it:
+// its users end with a stream synchronisation)
+template <typename T>
+int dev_grow(ranenv_handle h, T **buf, int64_t *cap, int64_t count, const char *what)
+{
+    if (*buf && *cap >= count) return RANENV_OK;
+    dev_drop(h, *buf); *buf = nullptr; *cap = 0;
+    void *ptr = nullptr;
+    const hipError_t e = hipMalloc(&ptr, (size_t)count * sizeof(T));
+    if (e != hipSuccess) return fail(h, RANENV_E_NOMEM, "%s (%.3f GB): %s", what, (double)count * sizeof(T) / 1e9, hipGetErrorString(e));
+    h->allocs.push_back(ptr);
+    *buf = (T *)ptr; *cap = count;
+    return RANENV_OK;
+}
+
 template <typename Fill>
 int se_sidecars_rebuild(ranenv_handle h, size_t nt, Fill fill)
 {
     const int U = h->cfg.n_ues, Rp = (h->cfg.n_rbs + 7) & ~7;
-    auto drop = [&](void *ptr) {
-        if (!ptr) return;
-        for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == ptr) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
-        (void)hipFree(ptr);
-    };
+    auto drop = [&](void *ptr) { dev_drop(h, ptr); };
     HIP_TRY(h, hipDeviceSynchronize());
     drop(h->d_se_mean); drop(h->d_se_um); h->d_se_mean = nullptr; h->d_se_um = nullptr;
     void *pm = nullptr, *pu = nullptr;
@@ -1024,6 +1047,7 @@ int ranenv_bind_se_pool(ranenv_handle h, const float *dev_pool, int64_t n_tiles,
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     h->se_mode = RANENV_SE_STREAM;             // the sidecars describe the pool they were built from
+    h->se_stats_n = 0;                         // ... and so do the tile statistics
     if (dev_pool == nullptr) {
         h->kp.se_pool = nullptr; h->kp.se_stride = 0; h->se_tiles_n = 0; h->kp.se_quad = 0;
         return RANENV_OK;
@@ -1043,7 +1067,7 @@ int ranenv_bind_se_pool_quad(ranenv_handle h, const float *dev_pool, int64_t n_t
     if (n_tiles < 1 || tile_stride < need || (tile_stride & 3) != 0 || ((uintptr_t)dev_pool & 15) != 0)
         return fail(h, RANENV_E_INVALID, "RB-quad-major SE pool needs n_tiles >= 1, tile_stride >= ceil(R/4)*U*4 = %lld floats and a multiple of 4, "
                     "and a 16-byte aligned pool", (long long)need);
-    h->se_mode = RANENV_SE_STREAM;
+    h->se_mode = RANENV_SE_STREAM; h->se_stats_n = 0;
     h->kp.se_pool = dev_pool; h->kp.se_stride = tile_stride; h->se_tiles_n = n_tiles; h->kp.se_quad = 1;
     h->have_episodes = false;
     return RANENV_OK;
@@ -1607,7 +1631,7 @@ int ranenv_bind_se_gather_from_power(ranenv_handle h, const double *dev_power, i
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "SE sidecar-from-power launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(stream));        // (read by launches on other streams; the power array may be freed by the caller now)
     h->kp.se_pool = nullptr; h->kp.se_stride = 0;    // no RB-major pool: pooled tiles exist as sidecars only
-    h->se_tiles_n = n_tiles; h->se_mode = RANENV_SE_GATHER;
+    h->se_tiles_n = n_tiles; h->se_mode = RANENV_SE_GATHER; h->se_stats_n = 0;
     h->have_episodes = false;                        // descriptors are re-validated against the new tile count
     return RANENV_OK;
 }
@@ -1619,6 +1643,83 @@ int ranenv_get_se_sidecars(ranenv_handle h, double **dev_row_mean, float **dev_u
     if (dev_row_mean) *dev_row_mean = h->d_se_mean;
     if (dev_ue_major) *dev_ue_major = h->d_se_um;
     if (row_floats) *row_floats = h->se_rp;
+    return RANENV_OK;
+}
+
+int ranenv_build_se_stats(ranenv_handle h, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!h->kp.se_pool || h->se_tiles_n < 1)
+        return fail(h, RANENV_E_STATE, "the tile statistics are built from a bound float32 SE pool (ranenv_bind_se_pool / ranenv_bind_se_pool_quad)%s",
+                    h->d_se_mean && h->se_tiles_n > 0 ? ": this handle's sidecars came straight from power" : "");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t stream = (hipStream_t)stream_;
+    const int U = h->cfg.n_ues;
+    h->se_stats_n = 0;
+    if (!h->d_se_stats || h->se_stats_cap < h->se_tiles_n) HIP_TRY(h, hipDeviceSynchronize());       // (an earlier caller may still read the old array)
+    int64_t cap = h->se_stats_cap * 4 * U;
+    const int rc = dev_grow(h, &h->d_se_stats, &cap, h->se_tiles_n * 4 * U, "SE tile statistics");
+    h->se_stats_cap = h->d_se_stats ? cap / (4 * U) : 0;
+    if (rc != RANENV_OK) return rc;
+    const size_t nt = (size_t)h->se_tiles_n;
+    for (size_t t0 = 0; t0 < nt; t0 += 1u << 20)
+        launch_se_tile_stats(stream, (unsigned)(nt - t0 < (1u << 20) ? nt - t0 : (size_t)(1u << 20)), (unsigned)h->nt, h->kp.se_pool,
+                             (long long)h->kp.se_stride, (long long)t0, U, h->cfg.n_rbs, h->kp.se_quad, h->d_se_stats);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, RANENV_E_HIP, "SE tile statistics launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(stream));        // (read by ranenv_rbs_needed calls on any stream, and handed out by ranenv_get_se_stats)
+    h->se_stats_n = h->se_tiles_n;
+    return RANENV_OK;
+}
+
+int ranenv_get_se_stats(ranenv_handle h, double **dev_stats, int64_t *n_tiles)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (h->se_stats_n < 1) return fail(h, RANENV_E_STATE, "no SE tile statistics for the pool bound now (ranenv_build_se_stats builds them)");
+    if (dev_stats) *dev_stats = h->d_se_stats;
+    if (n_tiles) *n_tiles = h->se_stats_n;
+    return RANENV_OK;
+}
+
+int ranenv_rbs_needed(ranenv_handle h, const ranenv_episode *eps, int32_t n_episodes, int32_t n_steps, double *dev_slice, double *dev_network,
+                      double *dev_episode_mean, void *stream_)
+{
+    // ---- everything is validated before the first device call ----
+    if (!h || !eps || !dev_episode_mean) return fail(h, RANENV_E_INVALID, "null argument");
+    if (!h->have_scenarios) return fail(h, RANENV_E_STATE, "load scenarios first");
+    if (h->se_stats_n < 1) return fail(h, RANENV_E_STATE, "no SE tile statistics for the pool bound now (ranenv_build_se_stats builds them)");
+    if (n_episodes < 1) return fail(h, RANENV_E_INVALID, "n_episodes must be >= 1, got %d", n_episodes);
+    if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1, got %d", n_steps);
+    if ((long long)n_episodes * n_steps >= (1ll << 31))
+        return fail(h, RANENV_E_INVALID, "n_episodes * n_steps = %lld: one call takes fewer than 2^31 (episode, step) pairs", (long long)n_episodes * n_steps);
+    for (int i = 0; i < n_episodes; i++) {
+        const ranenv_episode &e = eps[i];
+        if (e.scenario < 0 || e.scenario >= h->cfg.n_scenarios)
+            return fail(h, RANENV_E_INVALID, "episode %d: scenario %d outside pool of %d", i, e.scenario, h->cfg.n_scenarios);
+        if (e.se_len < 1 || e.se_offset < 0 || e.se_offset >= e.se_len || e.se_base < 0)
+            return fail(h, RANENV_E_INVALID, "episode %d: need se_len >= 1, 0 <= se_offset < se_len, se_base >= 0", i);
+        if (e.se_base + e.se_len > h->se_stats_n)
+            return fail(h, RANENV_E_INVALID, "episode %d: SE trace [%lld,+%d) exceeds the pool of %lld tiles the statistics were built from", i,
+                        (long long)e.se_base, e.se_len, (long long)h->se_stats_n);
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t stream = (hipStream_t)stream_;
+    const int S = h->cfg.n_slices, U = h->cfg.n_ues;
+    int rc = dev_grow(h, &h->d_load_eps, &h->load_eps_cap, (int64_t)n_episodes, "scenario load descriptors");
+    if (rc == RANENV_OK && !dev_network) rc = dev_grow(h, &h->d_load_net, &h->load_net_cap, (int64_t)n_episodes * n_steps * 3, "scenario load network rows");
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_load_eps, eps, sizeof(ranenv_episode) * (size_t)n_episodes, hipMemcpyHostToDevice, stream));
+    RbsArgs a;
+    a.eps = h->d_load_eps; a.n_steps = n_steps; a.stats = h->d_se_stats;
+    a.ue_slice = h->kp.tab.ue + (size_t)6 * (size_t)h->kp.NSU;      // set 1 of the per-UE tables: entry u = UE u (ranenv_internal.h, Tables::ue)
+    a.slice_i32 = h->kp.tab.slice_i32; a.slice_f64 = h->kp.tab.slice_f64;
+    a.S = S; a.U = U; a.R = h->cfg.n_rbs; a.bw_mhz = h->cfg.bandwidth_hz / 1e6;
+    a.slice_out = dev_slice; a.net_out = dev_network ? dev_network : h->d_load_net;
+    const int lanes = 6 * S > h->nt ? 6 * S : h->nt;                // one thread per UE, and 6 per slice for the sums
+    launch_rbs_needed(stream, (unsigned)n_episodes, (unsigned)((lanes + WAVE - 1) / WAVE * WAVE), a, dev_episode_mean);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, RANENV_E_HIP, "scenario load launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(stream));        // the staging buffers are the handle's: free for the next call
     return RANENV_OK;
 }
 

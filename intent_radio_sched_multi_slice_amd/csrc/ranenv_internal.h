@@ -1,7 +1,8 @@
 // ranenv_internal.h -- what the translation units of libranenv_hip.so share: the kernel-argument block (KP) and the structures it
 // points to, the slab accessors, and the LAUNCH TABLE -- the functions through which the host side of the ABI (ranenv_host.cpp)
 // reaches the kernels, which live in ranenv_step.hip (one object per row width NP, -DRANENV_NP=8 / 10 / 16: they compile in parallel)
-// and ranenv_aux.hip (the small kernels: class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination).
+// and ranenv_aux.hip (the small kernels: class sort, sidecars, tile statistics, re-tiling, ingest, heads, episode advance, traffic examination,
+// scenario load).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -281,6 +282,21 @@ void launch_se_sidecar(hipStream_t, unsigned n_tiles, unsigned block, const floa
 void launch_se_sidecar_from_power(hipStream_t, unsigned n_tiles, unsigned block, const double *power, long long tile0, int U, int R, int Rp,
                                   double tx, double noise, double *mean, float *um);
 void launch_se_retile_quad(hipStream_t, unsigned blocks, const float *src, float *dst, long long n_quads, int U, int R);
+// ranenv_build_se_stats: stats [n][4][U] (mean, std, min, max per UE over the R RBs) of tiles [tile0, tile0 + n_tiles), the sidecar launch's shape
+void launch_se_tile_stats(hipStream_t, unsigned n_tiles, unsigned block, const float *pool, long long stride, long long tile0, int U, int R,
+                          int quad, double *stats);
+// ranenv_rbs_needed: n_episodes * n_steps workgroups of `block` >= U threads write the per-step rows, then one workgroup per episode
+// its mean row (n_episodes * n_steps < 2^31: the host checks)
+struct RbsArgs {
+    const ranenv_episode *eps; int n_steps;
+    const double *stats;                  // [tiles][4][U]
+    const int32_t *ue_slice;              // [NS][U], entry u = UE u
+    const int32_t *slice_i32; const double *slice_f64;      // Tables' rows
+    int S, U, R; double bw_mhz;
+    double *slice_out;                    // [n_ep][T][S][RANENV_LOAD_SLICE_COLS] or null
+    double *net_out;                      // [n_ep][T][3]
+};
+void launch_rbs_needed(hipStream_t, unsigned n_episodes, unsigned block, const RbsArgs &, double *episode_mean);
 void launch_se_from_power(hipStream_t, unsigned blocks, const double *power, float *se, long long n, double tx_per_rb, double noise);
 void launch_ddiv_selftest(hipStream_t, const double *a, const double *b, double *fast, double *ieee, long long n);
 // head_acc: the per-env running pair of the two head rewards [B][2] or null; reset != 0: the launch follows a reset (the pair of the

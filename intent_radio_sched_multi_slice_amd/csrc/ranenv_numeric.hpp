@@ -93,6 +93,10 @@ DEVFN double np_sum_lds(const double *row, int n)
 }
 DEVFN double np_sum16_lds(const double *row, int n) { return np_sum_lds<16>(row, n); }
 
+// The pooled tile an episode replays at TTI t (include/ranenv.h, ranenv_episode) for a kernel that is handed t.  The step kernels carry
+// the position from TTI to TTI instead (ST_se_pos: the offset at a reset, one further and wrapped per step): the same sequence.
+DEVFN long long se_tile_of(const ranenv_episode &ep, int t) { return ep.se_base + ((long long)ep.se_offset + t) % ep.se_len; }
+
 DEVFN bool d_apply_op(int op, double a, double b)
 {
     switch (op) {
@@ -326,10 +330,19 @@ struct SeStreamLane {
 // no register during the rest of the stream.
 // PE (RANENV_F_SCALE_PER_ELEMENT): `part` = sum of (sched * se) * scale with every product rounded on its own before it is added, as
 // np.sum(sched * se * (BW / R)) would; without it the caller scales the sum (-ffp-contract=off: the product below is not fused).
-template <bool PE = false, typename Src, typename InFn, typename Hook>
-DEVFN void row_sums(Src &st, int R, InFn in, double &full, double &part, Hook after_issue, const double scale = 1.0)
+// The tile statistics (ranenv_se_tile_stats_kernel) walk the same leaves through the same queue with two more hooks: `map` turns an
+// element (as a double) into what is summed -- the squared deviation of np.std --, and `see` is shown every float of the row, and
+// none of the padding behind RB R-1, before it is mapped (the running minimum and maximum).  RowNoPart as `in`: no masked sum is
+// kept at all (`part` comes back 0).  The defaults are the identity and nothing: the step kernels' sums are what they were.
+struct RowIdentity { DEVFN double operator()(double d) const { return d; } };
+struct RowBlind { DEVFN void operator()(float) const {} };
+struct RowNoPart { DEVFN bool operator()(int) const { return false; } };
+template <bool PE = false, typename Src, typename InFn, typename Hook, typename MapFn = RowIdentity, typename SeeFn = RowBlind>
+DEVFN void row_sums(Src &st, int R, InFn in, double &full, double &part, Hook after_issue, const double scale = 1.0, MapFn map = MapFn(),
+                    SeeFn see = SeeFn())
 {
     constexpr int SE_NQ = Src::NSLOT;
+    constexpr bool HAVE_PART = !std::is_same<InFn, RowNoPart>::value;
     const RowPlan pl = make_row_plan(R);
     const int tail = R & 7, G = R >> 3;
     const int GT = G + (tail > 0 ? 1 : 0);                   // groups requested in all (the partial one included)
@@ -350,10 +363,11 @@ DEVFN void row_sums(Src &st, int R, InFn in, double &full, double &part, Hook af
         for (int j = 0; j < 8; j++) {
             // part += sched * se with sched in {0, 1}: one fused multiply-add is exact here (the product is
             // either x or 0), and cheaper than selecting a 64-bit addend
-            const double d = (double)x[j];
+            see(x[j]);
+            const double d = map((double)x[j]);
             f[j] += d;
 #if RANENV_DIAG != 11      /* ablation 11: the full sum alone (what a stream costs without the masked half) */
-            g[j] = fma(PE ? d * scale : d, in(r0 + j) ? 1.0 : 0.0, g[j]);
+            if constexpr (HAVE_PART) g[j] = fma(PE ? d * scale : d, in(r0 + j) ? 1.0 : 0.0, g[j]);
 #endif
         }
         if (--left_in_leaf == 0) {
@@ -372,9 +386,10 @@ DEVFN void row_sums(Src &st, int R, InFn in, double &full, double &part, Hook af
 #pragma unroll
         for (int j = 0; j < 7; j++) {
             if (j < tail) {
-                const double d = (double)x[j];
+                see(x[j]);
+                const double d = map((double)x[j]);
                 fr += d;
-                gr = fma(PE ? d * scale : d, in(r0 + j) ? 1.0 : 0.0, gr);
+                if constexpr (HAVE_PART) gr = fma(PE ? d * scale : d, in(r0 + j) ? 1.0 : 0.0, gr);
             }
         }
         fold(pl.n_leaves - 1);

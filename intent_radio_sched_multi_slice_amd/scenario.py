@@ -218,6 +218,15 @@ def stable_sort_slices(slice_nues: np.ndarray, slice_traffic: np.ndarray, slice_
     return np.argsort(key, kind="stable").astype(np.int32)
 
 
+def rank_by_load(total_avg) -> Tuple[int, int, int]:
+    """(heaviest, median, lightest) index of a list of episodes' mean needed RBs (``scenario_load``'s ``episode_mean[:, 0]``),
+    picked as plot_rbs_needed_network_scenarios picks its three scenarios (results/gen_results.py:1401-1403)."""
+    a = np.asarray(total_avg, dtype=np.float64).reshape(-1)
+    if a.size == 0:
+        raise ValueError("rank_by_load needs at least one episode")
+    return int(np.argmax(a)), int(np.argsort(a)[len(a) // 2]), int(np.argmin(a))
+
+
 _I32_SLICE = ("slice_active", "slice_has_req", "slice_nues", "slice_buffer_size",
               "slice_buffer_latency", "slice_message_size", "slice_nparams", "sorted_slices")
 _F64_SLICE = ("slice_priority", "slice_traffic")
