@@ -563,6 +563,60 @@ int ranenv_enable_slice_metrics(ranenv_handle h, int32_t enable, void *stream);
 int ranenv_get_slice_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t **dev_episode_scenario,
                              int32_t *n_cols);
 
+/* Device traces: the per-TTI history of selected envs (what hist/{scenario}/{agent}/ep_N.npz holds, results/gen_results.py:88-108),
+ * recorded by a small kernel behind every step into a ring the caller owns -- inside ranenv_rollout, ranenv_collect*, ranenv_step,
+ * ranenv_step_range / _part alike, with no host work between two TTIs.
+ * ranenv_trace: n_envs recorded envs, `capacity` rows each.  `envs` is a HOST array int32[n_envs] (validated and copied: it may go
+ * after the call); recorded env envs[i] owns column i.  Every other pointer is caller-owned device memory, [capacity][n_envs][...]
+ * row-major, NULL = not recorded:
+ *   pkt_incoming, pkt_throughputs, pkt_effective_thr, dropped_pkts, queue_pkts, rb_start, rb_count   int32 [U]: the views' rows
+ *   queue_age_sum    int64 [U]
+ *   se               float32 [R][U], RB-major (the reference's order): the tile the step just consumed -- the call's explicit tile
+ *                    of the env, else the pool tile at the position the step read (se_base + (se_offset + t) % se_len of the
+ *                    episode descriptor as it is on the device), de-interleaved from an RB-quad-major pool.  In SE gather mode the
+ *                    bound pool is read (the gather sidecars are not)
+ *   reward           float64 [S+1]: the step's dev_reward row (inside ranenv_collect: the slot the step wrote)
+ *   scores           float64 [S]: the inter-slice scores the step used (the views' policy_scores row)
+ *   intra            uint8 [S]: the intra-slice scheduler the step used for slice s -- the fixed one, or under
+ *                    RANENV_INTRA_PER_SLICE the caller's dev_intra / the intra net's action (RANENV_INTRA_RR where there is none)
+ *   obs_inter        float32 [10*S], obs_intra float32 [S][2*Us+9]: the step's outputs (at an episode end: the terminal observation)
+ *   step_number      int32: the TTI's index inside its episode (0 = the first step after a reset)
+ *   episode_number   int32: the views' episode_number      scenario   int32: the scenario-pool row of the episode descriptor
+ *   done             uint8: the step's dev_done flag
+ * The recording launch sits behind the step (and head) kernel and in front of everything that follows an episode end: the row of
+ * the TTI at which an episode ends carries the finished episode's descriptor and the terminal observation.  A reset records nothing.
+ * Library-owned, per recorded env: count (rows written) and lost (rows that did not fit), int32 [n_envs] each.  Env envs[i]'s
+ * k-th recorded TTI is row k of column i.  A full ring stops recording and counts into lost: it never wraps and nothing is
+ * written at or beyond row `capacity`.
+ * ranenv_bind_trace: tr NULL unbinds.  n_envs outside [1, batch], capacity < 1, a NULL envs, an env outside the batch or listed
+ *   twice: RANENV_E_INVALID, as are pkt_incoming / pkt_throughputs on a handle with RANENV_F_NO_RAW_OUTPUT.  Binding zeroes count / lost
+ *   and ends with a stream synchronisation (the list goes to the device).  On error the handle keeps the trace it had.
+ * While a trace is bound:
+ *   - a stepping call (ranenv_step, _step_range, _step_part, _rollout, _collect*) without an output buffer the trace records from
+ *     (dev_obs_inter, dev_obs_intra, dev_reward, dev_done) is RANENV_E_INVALID; with `se` recorded, a call without explicit tiles on
+ *     a handle without a bound float32 pool (ranenv_bind_se_gather_from_power alone) is RANENV_E_STATE.  Both precede every launch;
+ *   - ranenv_rollout runs one TTI per launch and takes no persistent launch, as with slice metrics on; unbound, every call
+ *     enqueues exactly what it enqueues without this feature;
+ *   - ranenv_step_dense records nothing (it has neither scores nor an intra choice).
+ * ranenv_get_trace_counts returns device pointers to count / lost (RANENV_E_STATE while no trace is bound); ranenv_reset_trace
+ * zeroes both: the next recorded TTI of every env is row 0 again. */
+typedef struct {
+    int32_t n_envs, capacity;
+    const int32_t *envs;                  /* HOST */
+    int32_t *pkt_incoming, *pkt_throughputs, *pkt_effective_thr, *dropped_pkts, *queue_pkts, *rb_start, *rb_count;
+    int64_t *queue_age_sum;
+    float *se;
+    double *reward, *scores;
+    uint8_t *intra;
+    float *obs_inter, *obs_intra;
+    int32_t *step_number, *episode_number, *scenario;
+    uint8_t *done;
+} ranenv_trace;
+#define RANENV_TRACE_BYTES 160
+int ranenv_bind_trace(ranenv_handle h, const ranenv_trace *tr, void *stream);
+int ranenv_get_trace_counts(ranenv_handle h, int32_t **dev_count, int32_t **dev_lost);
+int ranenv_reset_trace(ranenv_handle h, void *stream);
+
 int ranenv_get_views(ranenv_handle h, ranenv_views *out);
 
 /* Offered traffic drawn on the device instead of replayed from the traffic pool: for every UE of a slice with

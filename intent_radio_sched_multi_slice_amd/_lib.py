@@ -96,6 +96,21 @@ class Replay(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_void_p) for n in ("obs", "next_obs", "action", "reward_head", "done")]
 
 
+# ranenv_trace's device buffers in declaration order: name -> (typestr, trailing shape in the letters of BatchedRanEnv.bind_trace)
+TRACE_FIELDS = (
+    ("pkt_incoming", "i4", "U"), ("pkt_throughputs", "i4", "U"), ("pkt_effective_thr", "i4", "U"), ("dropped_pkts", "i4", "U"),
+    ("queue_pkts", "i4", "U"), ("rb_start", "i4", "U"), ("rb_count", "i4", "U"), ("queue_age_sum", "i8", "U"), ("se", "f4", "RU"),
+    ("reward", "f8", "P"), ("scores", "f8", "S"), ("intra", "u1", "S"), ("obs_inter", "f4", "I"), ("obs_intra", "f4", "SW"),
+    ("step_number", "i4", ""), ("episode_number", "i4", ""), ("scenario", "i4", ""), ("done", "u1", ""),
+)
+
+
+class Trace(C.Structure):
+    """ranenv_trace: the caller-owned ring of ranenv_bind_trace, [capacity][n_envs][...] device pointers (NULL = not recorded) and
+    the HOST list of recorded envs."""
+    _fields_ = [("n_envs", C.c_int32), ("capacity", C.c_int32), ("envs", C.c_void_p)] + [(n, C.c_void_p) for n, _, _ in TRACE_FIELDS]
+
+
 class Views(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in VIEW_FIELDS]
 
@@ -172,6 +187,9 @@ FUNCTIONS = {
     "ranenv_build_se_stats": (C.c_int, [_P, _P]),
     "ranenv_get_se_stats": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "ranenv_rbs_needed": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "ranenv_bind_trace": (C.c_int, [_P, C.POINTER(Trace), _P]),
+    "ranenv_get_trace_counts": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "ranenv_reset_trace": (C.c_int, [_P, _P]),
 }
 EXPORTS = tuple(FUNCTIONS)
 

@@ -895,6 +895,58 @@ class BatchedRanEnv:
         self._recorder = HistoryRecorder(self, envs, root_path, simu_name, agent_name, episode_numbers, marl)
         return self._recorder
 
+    def bind_trace(self, envs, capacity: int, se: bool = True, guard_rows: int = 0):
+        """Record the per-TTI history of the listed envs ON THE DEVICE, behind every step of whatever call steps them --
+        ``rollout()``, ``evaluate()``, ``collect()``, ``collect_head()``, ``collect_replay()``, ``step()``, ``step_async()``, with or
+        without partitions -- into a ring of ``capacity`` rows per env (ranenv_bind_trace, include/ranenv.h): the rows
+        ``record()`` gathers under ``step()``, plus the intra-slice choice an intra net made, and per row the step index, episode
+        number, scenario and ``done``.  A full ring stops recording and counts the rows it lost.  ``se=False`` leaves the SE tile
+        (4 R U of a row's bytes) out; such a trace cannot ``write()`` history files.  ``guard_rows``: rows allocated behind the
+        ring and filled with 0xA5 bytes that the library is not told about (``trace.guard``: a check that nothing writes there).
+        Returns the DeviceTrace (history.py: ``.buffers``, ``.counts()``, ``.episodes()``, ``.write()``).  While bound, a rollout runs
+        one TTI per launch and no persistent launch, as with slice metrics on."""
+        from .history import DeviceTrace
+        if self.tables is None:
+            raise RanEnvError("bind_trace() needs load_scenarios first")
+        envs = [int(e) for e in envs]
+        n, cap, guard_rows = len(envs), int(capacity), int(guard_rows)
+        dims = {"U": (self.U,), "RU": (self.R, self.U), "P": (self.S + 1,), "S": (self.S,), "I": (10 * self.S,), "SW": (self.S, self.W),
+                "": ()}
+        tr = _lib.Trace()
+        tr.n_envs, tr.capacity = n, cap
+        ids = np.ascontiguousarray(envs, dtype=np.int32)
+        tr.envs = ids.ctypes.data
+        full = {}
+        if n >= 1 and cap >= 1 and guard_rows >= 0:        # (else: nothing to allocate; the library words the refusal)
+            for name, ts, shp in _lib.TRACE_FIELDS:
+                if name == "se" and not se:
+                    continue
+                full[name] = torch.zeros((cap + guard_rows, n) + dims[shp], dtype=_TORCH_DT[ts], device=self.device)
+                if guard_rows:
+                    full[name][cap:].view(torch.uint8).fill_(0xA5)
+                setattr(tr, name, full[name].data_ptr())
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_bind_trace(self._h, C.byref(tr), self._stream()), "ranenv_bind_trace")
+        self._keep["trace"] = full
+        cnt, lost = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.ranenv_get_trace_counts(self._h, C.byref(cnt), C.byref(lost)), "ranenv_get_trace_counts")
+        d_cnt = torch.as_tensor(_DevArray(cnt.value, (n,), "i4", self), device=self.device)
+        d_lost = torch.as_tensor(_DevArray(lost.value, (n,), "i4", self), device=self.device)
+
+        def reset():
+            self._check(self._lib.ranenv_reset_trace(self._h, self._stream()), "ranenv_reset_trace")
+
+        self._trace = DeviceTrace(envs, cap, {k: b[:cap] for k, b in full.items()}, lambda: (d_cnt.cpu().numpy(), d_lost.cpu().numpy()),
+                                  self.tables, self.R, self.Us, guard={k: b[cap:] for k, b in full.items()}, reset_fn=reset)
+        return self._trace
+
+    def unbind_trace(self) -> None:
+        """Stop recording (ranenv_bind_trace with NULL).  The DeviceTrace handed out keeps its buffers and can still be read and
+        written, its counters included, until the next ``bind_trace``."""
+        self._check(self._lib.ranenv_bind_trace(self._h, None, self._stream()), "ranenv_bind_trace")
+        self._trace = None
+        self._keep.pop("trace", None)
+
     # ------------------------------------------------------------------------------------------
     def _obs(self):
         return self._obs_dict

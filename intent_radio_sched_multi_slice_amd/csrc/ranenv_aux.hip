@@ -418,6 +418,93 @@ __global__ void __launch_bounds__(CORE_NT) ranenv_slice_metrics_kernel(const KP 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Device traces (ranenv_bind_trace; the row is spelled out in include/ranenv.h): one row of the caller's ring per recorded env and
+// TTI, a pure copy of what the step just left.  Launched behind the step (and head) kernel for the recorded envs of the launch's
+// range, in front of whatever follows an episode end: the env's row still holds the finished episode's descriptor, the step's done
+// flag and the terminal observation.  One workgroup = one recorded env; it owns the env's column and its two counters (one launch
+// per env and TTI, TTIs in stream order: no atomics).  The tile is 4 R U bytes of a row's 4 R U + 36 U + 4 S (2 Us + 9) + 57 S + 21: it
+// is split across the whole workgroup, lane = UE fastest, so that every store instruction writes consecutive floats of one RB row
+// -- from an RB-major source (the pool, or the call's explicit tile) a linear copy, from an RB-quad-major pool one 16-byte load
+// per (quad, UE) and up to four stores, one into each of the quad's RB rows (the pad RBs behind R - 1 are dropped).  The position
+// of the tile is the one the step read: the counter it left behind, minus one.  A full ring: the row is counted as lost, nothing
+// is written.
+// ---------------------------------------------------------------------------------------------
+// The pool tile env e's last step read: ST_se_pos is where its NEXT step reads, so one behind it, around the trace's end
+DEVFN size_t trace_tile_no(const KP &p, int e)
+{
+    const ranenv_episode ep = p.episodes[e];
+    int pos = ST_se_pos(p)[e];
+    pos = (pos < 1 || pos > ep.se_len ? ep.se_len : pos) - 1;
+    return (size_t)(ep.se_base + (long long)(pos < 0 ? 0 : pos));
+}
+
+__global__ void __launch_bounds__(CORE_NT) ranenv_trace_kernel(const KP p, const TraceArgs a)
+{
+    const int i = a.first + (int)blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const int e = __builtin_amdgcn_readfirstlane(a.env[i]), col = __builtin_amdgcn_readfirstlane(a.slot[i]);
+    const int row = __builtin_amdgcn_readfirstlane(a.count[col]);
+    const ranenv_trace &o = a.out;
+    if (row >= o.capacity || row < 0) {
+        if (tid == 0) a.lost[col] += 1;
+        return;
+    }
+    const int S = p.S, U = p.U, R = p.R, W = 2 * p.Us + 9;
+    const size_t at = (size_t)row * (size_t)o.n_envs + (size_t)col;      // this row's index in every buffer
+    for (int u = tid; u < U; u += nt) {
+        const size_t su = (size_t)e * U + u, du = at * U + u;
+        if (o.pkt_incoming) o.pkt_incoming[du] = ST_pkt_incoming(p)[su];
+        if (o.pkt_throughputs) o.pkt_throughputs[du] = ST_pkt_throughputs(p)[su];
+        if (o.pkt_effective_thr) o.pkt_effective_thr[du] = ST_pkt_effective_thr(p)[su];
+        if (o.dropped_pkts) o.dropped_pkts[du] = ST_dropped_pkts(p)[su];
+        if (o.queue_pkts) o.queue_pkts[du] = ST_queue_pkts(p)[su];
+        if (o.rb_start) o.rb_start[du] = ST_rb_start(p)[su];
+        if (o.rb_count) o.rb_count[du] = ST_rb_count(p)[su];
+        if (o.queue_age_sum) o.queue_age_sum[du] = ST_queue_age_sum(p)[su];
+    }
+    if (o.se) {
+        float *dst = o.se + at * (size_t)R * U;
+        if (p.se_tiles != nullptr || !a.se_quad) {
+            const float *src;
+            if (p.se_tiles != nullptr) src = p.se_tiles + (size_t)e * U * R;
+            else src = a.se_pool + trace_tile_no(p, e) * (size_t)a.se_stride;
+            for (int k = tid; k < R * U; k += nt) dst[k] = src[k];
+        } else {
+            const se_v4f *src = (const se_v4f *)(a.se_pool + trace_tile_no(p, e) * (size_t)a.se_stride);
+            const int Rq = (R + 3) >> 2;
+            for (int k = tid; k < Rq * U; k += nt) {                     // k = quad * U + UE
+                const int q = k / U, u = k - q * U, r = 4 * q;
+                const se_v4f v = src[k];
+                float *d = dst + (size_t)r * U + u;
+                d[0] = v.x;
+                if (r + 1 < R) d[(size_t)U] = v.y;
+                if (r + 2 < R) d[2 * (size_t)U] = v.z;
+                if (r + 3 < R) d[3 * (size_t)U] = v.w;
+            }
+        }
+    }
+    if (o.reward) for (int k = tid; k <= S; k += nt) o.reward[at * (S + 1) + k] = p.reward[(size_t)e * (S + 1) + k];
+    if (o.scores) for (int k = tid; k < S; k += nt) o.scores[at * S + k] = ST_policy_scores(p)[(size_t)e * S + k];
+    if (o.intra)
+        for (int k = tid; k < S; k += nt) {                              // what intra_alloc took for slice k
+            int c = p.fixed_intra;
+            if (c == RANENV_INTRA_PER_SLICE) c = p.intra ? (int)p.intra[(size_t)e * S + k] : RANENV_INTRA_RR;
+            o.intra[at * S + k] = (uint8_t)c;
+        }
+    if (o.obs_inter) for (int k = tid; k < 10 * S; k += nt) o.obs_inter[at * 10 * S + k] = p.obs_inter[(size_t)e * 10 * S + k];
+    if (o.obs_intra) for (int k = tid; k < S * W; k += nt) o.obs_intra[at * S * W + k] = p.obs_intra[(size_t)e * S * W + k];
+    const int step_new = ST_step_no(p)[e];
+    if (tid == 0) {
+        if (o.step_number) o.step_number[at] = step_new - 1;
+        if (o.episode_number) o.episode_number[at] = ST_episode_no(p)[e];
+        if (o.scenario) o.scenario[at] = p.episodes[e].scenario;
+        const int max_steps_e = p.max_steps_env ? p.max_steps_env[e] : p.max_steps;
+        if (o.done) o.done[at] = p.done ? p.done[e] : (uint8_t)(step_new >= max_steps_e ? 1 : 0);
+    }
+    __syncthreads();                       // every wave has formed its addresses from `row` before it moves on
+    if (tid == 0) a.count[col] = row + 1;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Scenario load (ranenv_rbs_needed; the columns are spelled out in include/ranenv.h): the RBs a slice would need to serve its
 // intent's traffic and its capacity per RB (results/gen_results.py:277-497, :1251-1451), from the tile statistics and the scenario
 // row alone -- no env is stepped.  One workgroup = one (episode, step); thread u holds UE u's four statistics.  Lane 6 s + k then adds
@@ -731,6 +818,10 @@ void launch_head(hipStream_t s, dim3 grid, dim3 block, const KP &kp, double *hea
 void launch_slice_metrics(hipStream_t s, dim3 grid, dim3 block, const KP &kp, double *slice_acc, int reset)
 {
     hipLaunchKernelGGL(ranenv_slice_metrics_kernel, grid, block, 0, s, kp, slice_acc, reset);
+}
+void launch_trace(hipStream_t s, unsigned n, const KP &kp, const TraceArgs &a)
+{
+    hipLaunchKernelGGL(ranenv_trace_kernel, dim3(n), dim3(CORE_NT), 0, s, kp, a);
 }
 void launch_advance(hipStream_t s, unsigned n_envs, const AdvanceArgs &a) { hipLaunchKernelGGL(ranenv_advance_kernel, dim3(n_envs), dim3(64), 0, s, a); }
 void launch_idle_traffic(hipStream_t s, unsigned n_eps, const ranenv_episode *eps, const int32_t *pool, int U, const int32_t *lane_slice,

@@ -59,6 +59,11 @@ struct ranenv {
     double *d_acc = nullptr, *d_ep_acc = nullptr; int32_t *d_ep_n = nullptr; int ep_slots = 0;   // ranenv_enable_metrics
     double *d_slice_acc = nullptr, *d_slice_ep_acc = nullptr; int32_t *d_slice_ep_scn = nullptr;    // ranenv_enable_slice_metrics: [B][S][10], [B][ep_slots][S][10], [B][ep_slots]
     bool slice_on = false;                      // ... switched on (the slice-metrics kernel follows every step and reset; off with kp.acc)
+    // ranenv_bind_trace: the caller's ring, the recorded envs in ascending order with the column each owns (host copies and, in one
+    // device array of 4 * trace_cap words: envs, columns, count, lost), an outgrown array staying allocated until ranenv_destroy
+    ranenv_trace trace{}; bool trace_on = false;
+    std::vector<int32_t> trace_env, trace_slot;
+    int32_t *d_trace = nullptr; int trace_cap = 0;
     // Host shadow of the per-env step counters (what they will be once everything enqueued so far has run): `done` is a function of
     // the counter alone (step >= the env's episode length), so ranenv_autoreset knows WITHOUT reading anything back whether an episode
     // ended at the TTI just enqueued -- and enqueues nothing when none did (an RL loop calls it behind every step: three small launches
@@ -321,7 +326,34 @@ int slice_metrics_outputs(ranenv_handle h, const float *obs_intra, const double 
     return RANENV_OK;
 }
 
-// One launch of the step kernel for envs [e0, e0 + n) on `stream` (+ the head kernel when bound, + the slice-metrics kernel when on).
+// A trace is bound: the trace kernel follows every step launch, one TTI per step launch (the conditions slice metrics impose)
+bool trace_on(ranenv_handle h) { return h->trace_on; }
+// ... then a call that steps needs the outputs that kernel copies, and -- for the tile -- a float32 pool or the call's own tiles
+int trace_outputs(ranenv_handle h, const float *se_tiles, const float *obs_inter, const float *obs_intra, const double *reward, const uint8_t *done)
+{
+    if (!trace_on(h)) return RANENV_OK;
+    const ranenv_trace &t = h->trace;
+    if ((t.obs_inter && !obs_inter) || (t.obs_intra && !obs_intra) || (t.reward && !reward) || (t.done && !done))
+        return fail(h, RANENV_E_INVALID, "the bound trace copies the step's dev_obs_inter, dev_obs_intra, dev_reward and dev_done: each one it records is needed while it is bound");
+    if (t.se && !se_tiles && !h->kp.se_pool)
+        return fail(h, RANENV_E_STATE, "the bound trace records SE tiles: this handle has gather sidecars only (ranenv_bind_se_gather_from_power) and the call gives no explicit tiles");
+    return RANENV_OK;
+}
+// The trace kernel for the recorded envs inside [e0, e0 + n): a range of the ascending list
+void launch_trace_range(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t stream)
+{
+    const auto lo = std::lower_bound(h->trace_env.begin(), h->trace_env.end(), e0), hi = std::lower_bound(lo, h->trace_env.end(), e0 + n);
+    if (lo == hi) return;
+    TraceArgs a{};
+    a.env = h->d_trace; a.slot = h->d_trace + h->trace_cap; a.first = (int)(lo - h->trace_env.begin());
+    a.count = h->d_trace + 2 * (size_t)h->trace_cap; a.lost = h->d_trace + 3 * (size_t)h->trace_cap;
+    a.se_pool = h->kp.se_pool; a.se_stride = h->kp.se_stride; a.se_quad = h->kp.se_quad;
+    a.out = h->trace;
+    launch_trace(stream, (unsigned)(hi - lo), kp, a);
+}
+
+// One launch of the step kernel for envs [e0, e0 + n) on `stream` (+ the head kernel when bound, + the slice-metrics kernel when on,
+// + the trace kernel behind a step while a trace is bound).
 template <int MODE>
 hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t stream)
 {
@@ -344,6 +376,7 @@ hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t strea
                     MODE == MODE_RESET ? 1 : 0);
     if (slice_metrics_on(h))
         launch_slice_metrics(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp, h->d_slice_acc, MODE == MODE_RESET ? 1 : 0);
+    if (MODE == MODE_STEP && trace_on(h)) launch_trace_range(h, kp, e0, n, stream);
     return hipGetLastError();
 }
 
@@ -1461,6 +1494,8 @@ static int step_begin(ranenv_handle h, int32_t env_first, int32_t env_count, con
     if (!scores && h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "policy is EXTERNAL but no inter-slice scores were given");
     rc = slice_metrics_outputs(h, obs_intra, reward);
     if (rc != RANENV_OK) return rc;
+    rc = trace_outputs(h, se_tiles, obs_inter, obs_intra, reward, done);
+    if (rc != RANENV_OK) return rc;
     *kp = call_kp(h, obs_inter, obs_intra, reward, done);
     kp->se_tiles = se_tiles; kp->scores = scores; kp->intra = intra; kp->traffic_bits = traffic_bits;
     const int net = net_use(h, *kp);
@@ -1952,7 +1987,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
     // the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more and lengthen the
     // drain at the rollout's end, where the workgroups that waited for a free slot run last and alone).
     int fuse = h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
-    if (r.kp.head_obs || r.kp.head_reward || r.net || slice_metrics_on(h)) fuse = 1;
+    if (r.kp.head_obs || r.kp.head_reward || r.net || slice_metrics_on(h) || trace_on(h)) fuse = 1;
     // `pdone[k]` TTIs are enqueued for partition k
     const int np = h->n_parts > 1 ? h->n_parts : 1;
     std::vector<int> pdone((size_t)np, 0), pn((size_t)np, 0);
@@ -2001,6 +2036,8 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
     rc = slice_metrics_outputs(h, obs_intra, reward);
     if (rc != RANENV_OK) return rc;
+    rc = trace_outputs(h, nullptr, obs_inter, obs_intra, reward, done);
+    if (rc != RANENV_OK) return rc;
     if (h->kp.policy == RANENV_POLICY_EXTERNAL) return fail(h, RANENV_E_STATE, "a rollout needs a device policy (ranenv_set_policy MARR / MAPF / NETWORK)");
     if (head_inter(h) && h->head.on && !obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
     const bool have_se = h->kp.se_pool != nullptr || (h->se_mode == RANENV_SE_GATHER && h->d_se_mean != nullptr);
@@ -2039,7 +2076,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     // (auto: not when episodes end at many different TTIs inside this call -- per-env episode lengths, envs reset at different times:
     // every episode end ends the persistent launches, re-sorts the envs and reads the class counts back; the launch-per-chunk
     // rollout follows the ends per partition without a host sync)
-    bool persist_ok = persist_wanted && !r.net && !scale_per_element(h) && r.kp.compact != 0 && !(r.kp.head_obs || r.kp.head_reward) && !slice_metrics_on(h) &&
+    bool persist_ok = persist_wanted && !r.net && !scale_per_element(h) && r.kp.compact != 0 && !(r.kp.head_obs || r.kp.head_reward) && !slice_metrics_on(h) && !trace_on(h) &&
                       (h->cfg.batch >> PERSIST_ENV_BITS) == 0 && !stream_capturing(stream);      // (it reads the class counts back)
     if (persist_ok && h->persist < 0 && r.follow) {
         int n_ends = 0;
@@ -2287,6 +2324,64 @@ int ranenv_enable_metrics(ranenv_handle h, int32_t episode_slots, void *stream_)
     if (h->d_head_acc) HIP_TRY(h, hipMemsetAsync(h->d_head_acc, 0, sizeof(double) * B * 2, stream));
     if (h->d_head_ep_acc) HIP_TRY(h, hipMemsetAsync(h->d_head_ep_acc, 0, sizeof(double) * B * (size_t)h->ep_slots * 2, stream));
     if (h->slice_on) return slice_sums_zero(h, stream);
+    return RANENV_OK;
+}
+
+static_assert(sizeof(ranenv_trace) == RANENV_TRACE_BYTES, "ranenv_trace: two int32 and 19 pointers");
+
+int ranenv_bind_trace(ranenv_handle h, const ranenv_trace *tr, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!tr) { h->trace_on = false; h->trace = ranenv_trace{}; h->trace_env.clear(); h->trace_slot.clear(); return RANENV_OK; }
+    const int B = h->cfg.batch, n = tr->n_envs;
+    if (n < 1 || n > B) return fail(h, RANENV_E_INVALID, "trace: n_envs %d outside [1,%d]", n, B);
+    if (tr->capacity < 1) return fail(h, RANENV_E_INVALID, "trace: capacity %d < 1", tr->capacity);
+    if (!tr->envs) return fail(h, RANENV_E_INVALID, "trace: null env list");
+    if ((tr->pkt_incoming || tr->pkt_throughputs) && (h->cfg.flags & RANENV_F_NO_RAW_OUTPUT))
+        return fail(h, RANENV_E_INVALID, "trace: pkt_incoming and pkt_throughputs are not available with RANENV_F_NO_RAW_OUTPUT");
+    std::vector<std::pair<int32_t, int32_t>> order((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (tr->envs[i] < 0 || tr->envs[i] >= B) return fail(h, RANENV_E_INVALID, "trace: env %d (entry %d) outside the batch of %d", tr->envs[i], i, B);
+        order[(size_t)i] = {tr->envs[i], i};
+    }
+    std::sort(order.begin(), order.end());
+    for (int i = 1; i < n; i++)
+        if (order[(size_t)i].first == order[(size_t)i - 1].first) return fail(h, RANENV_E_INVALID, "trace: env %d is listed twice", order[(size_t)i].first);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t stream = (hipStream_t)stream_;
+    int32_t *d = h->d_trace; int cap = h->trace_cap;
+    if (n > cap) {
+        if (dev_alloc(h, &d, 4 * (size_t)n) != RANENV_OK) return RANENV_E_NOMEM;
+        cap = n;
+    }
+    std::vector<int32_t> words(2 * (size_t)cap, 0);
+    for (int i = 0; i < n; i++) { words[(size_t)i] = order[(size_t)i].first; words[(size_t)cap + i] = order[(size_t)i].second; }
+    HIP_TRY(h, hipMemcpyAsync(d, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(h, hipMemsetAsync(d + 2 * (size_t)cap, 0, sizeof(int32_t) * 2 * (size_t)cap, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    h->d_trace = d; h->trace_cap = cap;
+    h->trace_env.resize((size_t)n); h->trace_slot.resize((size_t)n);
+    for (int i = 0; i < n; i++) { h->trace_env[(size_t)i] = order[(size_t)i].first; h->trace_slot[(size_t)i] = order[(size_t)i].second; }
+    h->trace = *tr; h->trace.envs = nullptr;       // (the caller's host array is not kept)
+    h->trace_on = true;
+    return RANENV_OK;
+}
+
+int ranenv_get_trace_counts(ranenv_handle h, int32_t **dev_count, int32_t **dev_lost)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!h->trace_on) return fail(h, RANENV_E_STATE, "no trace is bound (ranenv_bind_trace)");
+    if (dev_count) *dev_count = h->d_trace + 2 * (size_t)h->trace_cap;
+    if (dev_lost) *dev_lost = h->d_trace + 3 * (size_t)h->trace_cap;
+    return RANENV_OK;
+}
+
+int ranenv_reset_trace(ranenv_handle h, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!h->trace_on) return fail(h, RANENV_E_STATE, "no trace is bound (ranenv_bind_trace)");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipMemsetAsync(h->d_trace + 2 * (size_t)h->trace_cap, 0, sizeof(int32_t) * 2 * (size_t)h->trace_cap, (hipStream_t)stream));
     return RANENV_OK;
 }
 

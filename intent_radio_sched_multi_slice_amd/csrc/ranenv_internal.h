@@ -305,6 +305,17 @@ void launch_head(hipStream_t, dim3 grid, dim3 block, const KP &, double *head_ac
 // Per-slice episode sums [B][S][RANENV_SLICE_METRIC_COLS] behind a step (reset == 0: this TTI's share is added; reads kp.reward and kp.obs_intra)
 // or behind a reset (reset != 0: the rows of the envs under kp.env_mask are zeroed); block = the head kernel's
 void launch_slice_metrics(hipStream_t, dim3 grid, dim3 block, const KP &, double *slice_acc, int reset);
+// Device traces (ranenv_bind_trace): one row of every recorded env of a step launch's range.  `env` / `slot`: the recorded envs in
+// ascending order and the column each owns; the launch covers entries [first, first + n) of them, one workgroup each.  The pool is
+// the bound float32 one (RB-major or RB-quad-major) whatever the SE mode -- never the gather kernels' UE-major copy that KP carries
+// there.  Reads the step's outputs through kp (collect's redirected reward / done slots included).
+struct TraceArgs {
+    const int32_t *env, *slot; int first;
+    int32_t *count, *lost;
+    const float *se_pool; long long se_stride; int se_quad;
+    ranenv_trace out;                     // (out.envs is the caller's host array: not read on the device)
+};
+void launch_trace(hipStream_t, unsigned n, const KP &, const TraceArgs &);
 void launch_advance(hipStream_t, unsigned n_envs, const AdvanceArgs &);
 // reward_stride: doubles between two (env, column) entries' rewards' rows, i.e. reward[(t * B + b) * reward_stride + c] (n_cols: packed)
 void launch_gae(hipStream_t, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,

@@ -4,13 +4,16 @@ arrays are indexed ``[step, ...]``, ``spectral_efficiencies`` and ``sched_decisi
 ``(steps, 1, U, R)`` (:262-265, :629), ``slice_ue_assoc`` is ``(steps, S, U)`` (:279), ``reward[idx]["player_0"]`` for
 multi-agent runs (:162), ``slice_req[step]["slice_k"]`` dicts (:422-426)).
 
-Two producers: the B = 1 facade (comm_env.MARLCommEnv, ``save_hist=True``) and the batched recorder below, which
-keeps the traces of selected envs of a BatchedRanEnv on the device and writes one file per env at ``done``.
+Three producers: the B = 1 facade (comm_env.MARLCommEnv, ``save_hist=True``); the batched recorder below, which keeps the
+traces of selected envs of a BatchedRanEnv on the device and writes one file per env at ``done`` -- paced by the host, under
+``step()`` only --; and DeviceTrace, the ring a kernel of the library fills behind every step of whatever call steps the envs
+(``rollout``, ``evaluate``, ``collect*``, ``step``), cut into episodes and written afterwards.  The two batched producers turn the
+recorded rows of one env's episode into the 16-key dict with one function, ``rows_to_hist``.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -43,6 +46,57 @@ def write_episode_npz(path: str, hist: Dict[str, Sequence]) -> str:
             out[k] = np.asarray(v)
     np.savez_compressed(path, **out)
     return path
+
+
+# what a recorded row holds per env (HistoryRecorder's device buffers, DeviceTrace's ring): name -> trailing shape
+ROW_KEYS = ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts", "queue_pkts", "queue_age_sum", "rb_start",
+            "rb_count", "se", "reward", "scores", "intra", "obs_inter", "obs_intra")
+
+
+def rows_to_hist(rows: Dict[str, np.ndarray], tables, scen: int, R: int, Us: int, marl: bool = True) -> Dict[str, Sequence]:
+    """The 16-key history dict (``write_episode_npz``'s input) of ONE env's episode from its recorded rows on the host:
+    ``rows[k]`` = ``[T, ...]`` for every k of ROW_KEYS (``se`` RB-major ``[T, R, U]``), played on scenario-pool row ``scen`` of
+    ``tables``."""
+    T = len(rows["reward"])
+    S, U = tables.n_slices, tables.n_ues
+    bua, bsa, sua, req = tables.to_reference(scen)
+    max_pkts = tables.ue_max_pkts[scen].astype(np.float64)
+    q = rows["queue_pkts"][:T].astype(np.float64)
+    age = rows["queue_age_sum"][:T].astype(np.float64)
+    lat = np.where(q > 0, age / np.maximum(q, 1.0), 0.0)
+    st, cn = rows["rb_start"][:T], rows["rb_count"][:T]
+    r = np.arange(R)[None, None, :]
+    sched = ((r >= st[:, :, None]) & (r < (st + cn)[:, :, None])).astype(np.float64)[:, None]   # (T, 1, U, R)
+    se = np.swapaxes(rows["se"][:T], 1, 2).astype(np.float64)[:, None]                           # (T, 1, U, R)
+    mask_inter = np.asarray(tables.slice_active[scen], dtype=np.int8)
+    nues = tables.slice_nues[scen]
+    obs, rew, act = [], [], []
+    for t in range(T):
+        if marl:
+            o = {"player_0": {"observations": rows["obs_inter"][t].astype(np.float64), "action_mask": mask_inter}}
+            for s in range(S):
+                o[f"player_{s + 1}"] = {"observations": rows["obs_intra"][t, s].astype(np.float64),
+                                        "action_mask": (np.arange(Us) < nues[s]).astype(np.int8)}
+            obs.append(o)
+            rew.append({f"player_{j}": float(rows["reward"][t, j]) for j in range(S + 1)})
+            a = {"player_0": rows["scores"][t].copy()}
+            a.update({f"player_{s + 1}": int(rows["intra"][t, s]) for s in range(S)})
+            act.append(a)
+        else:
+            obs.append(rows["obs_inter"][t].astype(np.float64))
+            rew.append(float(rows["reward"][t, 0]))
+            act.append(rows["scores"][t].copy())
+    rep = lambda a: np.repeat(np.asarray(a)[None], T, axis=0)
+    return {
+        "pkt_incoming": rows["pkt_incoming"][:T].astype(np.float64),
+        "pkt_throughputs": rows["pkt_throughputs"][:T].astype(np.float64),
+        "pkt_effective_thr": rows["pkt_effective_thr"][:T].astype(np.float64),
+        "buffer_occupancies": q / max_pkts[None, :], "buffer_latencies": lat,
+        "dropped_pkts": rows["dropped_pkts"][:T].astype(np.float64),
+        "mobility": np.ones((T, U, 2)), "spectral_efficiencies": se,
+        "basestation_ue_assoc": rep(bua), "basestation_slice_assoc": rep(bsa), "slice_ue_assoc": rep(sua),
+        "sched_decision": sched, "reward": rew, "slice_req": [req] * T, "obs": obs, "agent_action": act,
+    }
 
 
 class HistoryRecorder:
@@ -157,52 +211,102 @@ class HistoryRecorder:
         which = list(range(len(self.envs))) if which is None else list(which)
         Tmax = int(self.t[which].max()) if which else 0
         host = {k: b[:Tmax].cpu().numpy() for k, b in self.buf.items()}
-        S, U, R, Us = env.S, env.U, env.R, env.Us
         paths = []
         for k in which:
             T = int(self.t[k])
-            scen = int(self._desc["scenario"][k])
-            bua, bsa, sua, req = env.tables.to_reference(scen)
-            max_pkts = env.tables.ue_max_pkts[scen].astype(np.float64)
-            q = host["queue_pkts"][:T, k].astype(np.float64)
-            age = host["queue_age_sum"][:T, k].astype(np.float64)
-            lat = np.where(q > 0, age / np.maximum(q, 1.0), 0.0)
-            st, cn = host["rb_start"][:T, k], host["rb_count"][:T, k]
-            r = np.arange(R)[None, None, :]
-            sched = ((r >= st[:, :, None]) & (r < (st + cn)[:, :, None])).astype(np.float64)[:, None]   # (T, 1, U, R)
-            se = np.swapaxes(host["se"][:T, k], 1, 2).astype(np.float64)[:, None]                        # (T, 1, U, R)
-            mask_inter = np.asarray(env.tables.slice_active[scen], dtype=np.int8)
-            nues = env.tables.slice_nues[scen]
-            obs, rew, act = [], [], []
-            for t in range(T):
-                if self.marl:
-                    o = {"player_0": {"observations": host["obs_inter"][t, k].astype(np.float64), "action_mask": mask_inter}}
-                    for s in range(S):
-                        o[f"player_{s + 1}"] = {"observations": host["obs_intra"][t, k, s].astype(np.float64),
-                                                "action_mask": (np.arange(Us) < nues[s]).astype(np.int8)}
-                    obs.append(o)
-                    rew.append({f"player_{j}": float(host["reward"][t, k, j]) for j in range(S + 1)})
-                    a = {"player_0": host["scores"][t, k].copy()}
-                    a.update({f"player_{s + 1}": int(host["intra"][t, k, s]) for s in range(S)})
-                    act.append(a)
-                else:
-                    obs.append(host["obs_inter"][t, k].astype(np.float64))
-                    rew.append(float(host["reward"][t, k, 0]))
-                    act.append(host["scores"][t, k].copy())
-            rep = lambda a: np.repeat(np.asarray(a)[None], T, axis=0)
-            hist = {
-                "pkt_incoming": host["pkt_incoming"][:T, k].astype(np.float64),
-                "pkt_throughputs": host["pkt_throughputs"][:T, k].astype(np.float64),
-                "pkt_effective_thr": host["pkt_effective_thr"][:T, k].astype(np.float64),
-                "buffer_occupancies": q / max_pkts[None, :], "buffer_latencies": lat,
-                "dropped_pkts": host["dropped_pkts"][:T, k].astype(np.float64),
-                "mobility": np.ones((T, U, 2)), "spectral_efficiencies": se,
-                "basestation_ue_assoc": rep(bua), "basestation_slice_assoc": rep(bsa), "slice_ue_assoc": rep(sua),
-                "sched_decision": sched, "reward": rew, "slice_req": [req] * T, "obs": obs, "agent_action": act,
-            }
+            hist = rows_to_hist({name: a[:T, k] for name, a in host.items()}, env.tables, int(self._desc["scenario"][k]), env.R, env.Us,
+                                self.marl)
             paths.append(write_episode_npz(hist_path(self.root_path, self.simu_name, self.agent_name,
                                                      self.episode_numbers[k]), hist))
             if not env._autoreset:
                 self.episode_numbers[k] += 1
+        self.written += paths
+        return paths
+
+
+class TraceEpisode(NamedTuple):
+    """Rows [start, stop) of one recorded env's column: one episode, or -- ``complete`` False -- what was recorded of one that had
+    not ended (the rows behind the last ``done``)."""
+    start: int
+    stop: int
+    episode_number: int
+    scenario: int
+    complete: bool
+
+
+def cut_episodes(done: np.ndarray, episode_number: np.ndarray, scenario: np.ndarray) -> List[TraceEpisode]:
+    """One env's recorded rows cut at ``done``: every row with the flag set ends an episode, which takes its number and scenario
+    from that row (the finished episode's: the device installs the next one behind it)."""
+    out, start = [], 0
+    for t in np.nonzero(np.asarray(done))[0]:
+        out.append(TraceEpisode(start, int(t) + 1, int(episode_number[t]), int(scenario[t]), True))
+        start = int(t) + 1
+    if start < len(done):
+        out.append(TraceEpisode(start, len(done), int(episode_number[start]), int(scenario[start]), False))
+    return out
+
+
+class DeviceTrace:
+    """The ring of ``BatchedRanEnv.bind_trace``: ``buffers[k]`` = ``[capacity, n_envs, ...]`` (torch tensors the library's trace
+    kernel writes; numpy arrays work as well: the host side below only reads them), column i = env ``envs[i]``, row k = that env's
+    k-th recorded TTI.  ``counts_fn() -> (count, lost)``: rows written / rows that did not fit, per recorded env."""
+
+    BOOKKEEPING = ("step_number", "episode_number", "scenario", "done")
+
+    def __init__(self, envs: Sequence[int], capacity: int, buffers: Dict[str, object], counts_fn: Callable, tables, R: int, Us: int,
+                 guard: Optional[Dict[str, object]] = None, reset_fn: Optional[Callable] = None):
+        self.envs = [int(e) for e in envs]
+        self.capacity = int(capacity)
+        self.buffers, self.guard = buffers, guard or {}
+        self._counts_fn, self._reset_fn = counts_fn, reset_fn
+        self.tables, self.R, self.Us = tables, int(R), int(Us)
+        self.written: List[str] = []
+
+    def counts(self) -> Dict[str, np.ndarray]:
+        """``{"count", "lost"}``: int32 [n_envs] on the host (one small device-to-host copy)."""
+        count, lost = self._counts_fn()
+        return {"count": np.asarray(count, dtype=np.int32), "lost": np.asarray(lost, dtype=np.int32)}
+
+    def reset(self) -> None:
+        """Start again at row 0 of every column (count and lost zeroed on the device; the rows stay until overwritten)."""
+        if self._reset_fn is None:
+            raise RuntimeError("this trace has no device ring to reset")
+        self._reset_fn()
+
+    def rows(self, names: Optional[Sequence[str]] = None) -> Dict[str, np.ndarray]:
+        """Host copies of the first max(count) rows of the named buffers (all by default)."""
+        n = int(self.counts()["count"].max(initial=0))
+        out = {}
+        for k in (self.buffers if names is None else names):
+            b = self.buffers[k][:n]
+            out[k] = b.cpu().numpy() if hasattr(b, "cpu") else np.asarray(b)
+        return out
+
+    def episodes(self, rows: Optional[Dict[str, np.ndarray]] = None) -> List[List[TraceEpisode]]:
+        """Per recorded env the row ranges of its episodes, cut at ``done``; a trailing unfinished one has ``complete=False``."""
+        missing = [k for k in self.BOOKKEEPING[1:] if k not in self.buffers]
+        if missing:
+            raise ValueError(f"the trace does not record {missing}")
+        rows = self.rows(self.BOOKKEEPING[1:]) if rows is None else rows
+        count = self.counts()["count"]
+        return [cut_episodes(rows["done"][:count[i], i], rows["episode_number"][:count[i], i], rows["scenario"][:count[i], i])
+                for i in range(len(self.envs))]
+
+    def write(self, root_path: str = ".", simu_name: str = "mult_slice", agent_name: str = "agent", marl: bool = True,
+              episode_numbers: Optional[Sequence[int]] = None) -> List[str]:
+        """One reference-format npz per COMPLETE recorded episode, ``hist/{simu_name}/{agent_name}/ep_{episode_number}.npz`` with
+        the number the device recorded.  ``episode_numbers`` (as ``record()``'s, for runs without device auto-reset, where the
+        device's episode counter does not move): recorded env i's j-th complete episode is named ``episode_numbers[i] + j``
+        instead.  Returns the paths, per env in episode order (also appended to ``.written``)."""
+        missing = [k for k in ROW_KEYS if k not in self.buffers]
+        if missing:
+            raise ValueError(f"the trace does not record {missing}: no history file can be written from it")
+        rows = self.rows()
+        paths = []
+        for i, eps in enumerate(self.episodes(rows)):
+            for j, ep in enumerate(x for x in eps if x.complete):
+                number = ep.episode_number if episode_numbers is None else int(episode_numbers[i]) + j
+                hist = rows_to_hist({k: rows[k][ep.start:ep.stop, i] for k in ROW_KEYS}, self.tables, ep.scenario, self.R, self.Us, marl)
+                paths.append(write_episode_npz(hist_path(root_path, simu_name, agent_name, number), hist))
         self.written += paths
         return paths

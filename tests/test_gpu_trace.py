@@ -1,0 +1,330 @@
+"""Device traces (ranenv_bind_trace, include/ranenv.h; history.DeviceTrace): the per-TTI history rows a kernel copies behind every
+step, inside rollout / evaluate / collect as under step().  Everything recorded is a pure copy, so every comparison here is
+np.array_equal / torch.equal, with no tolerance.  The reference side is the existing HistoryRecorder (env.record) under a step()
+loop on a twin env built from the same arguments."""
+from __future__ import annotations
+
+import functools
+import os
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from tests.gpu_common import need_gpu, short_episode_setup
+
+pytestmark = pytest.mark.gpu
+
+SMALL = dict(n_slices=3, n_ues=12, n_rbs=10, max_ues_slice=4)        # R % 4 = 2: the last quad holds two pad RBs
+NATIVE = dict(n_slices=5, n_ues=25, n_rbs=25, max_ues_slice=5)       # R % 4 = 1: three pad RBs
+N = 16                    # TTIs per run; the channel traces are TRACE_LEN long, so the tile index wraps
+TRACE_LEN = 7
+
+
+def _workload(shape, layout="rb", gather=False, B=8, steps=N):
+    """B envs under MAPF + PF whose episodes last `steps` TTIs, on channel traces shorter than that.  The traffic is four times the
+    workload's (the same for every twin): at these few UEs the workload's own load never fills a buffer, and a trace of rows
+    without a dropped packet would not tell a zero row from a recorded one."""
+    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
+    wl = make_mult_slice_workload(B, torch.device("cuda", 0), policy=2, intra=1, n_scenarios=4, n_traces=3, trace_len=TRACE_LEN,
+                                  rbs_per_rbg=1, max_steps=steps, se_layout=layout, **shape)
+    eps = wl.env.episodes
+    wl.env.bind_traffic_pool(wl.traffic_pool * 4)
+    wl.env.set_episodes(**{k: eps[k] for k in ("scenario", "se_base", "se_len", "se_offset", "trf_base", "trf_len", "trf_offset")})      # (a new pool unsets them)
+    wl.env.set_se_mode("gather" if gather else "stream")
+    return wl
+
+
+def _same(a, b):
+    """Two entries of a history file: arrays by value and dtype, dicts key by key, object arrays element by element."""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, np.ndarray) and a.dtype == object:
+        return isinstance(b, np.ndarray) and b.dtype == object and a.shape == b.shape and all(_same(x, y) for x, y in zip(a.ravel(), b.ravel()))
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.dtype == b.dtype and np.array_equal(a, b)
+    return type(a) is type(b) and a == b
+
+
+def _assert_same_files(path_a, path_b):
+    from intent_radio_sched_multi_slice_amd.history import HIST_KEYS
+    a, b = np.load(path_a, allow_pickle=True), np.load(path_b, allow_pickle=True)
+    assert set(a.files) == set(b.files) == set(HIST_KEYS)
+    for k in HIST_KEYS:
+        assert _same(a[k], b[k]), (os.path.basename(path_a), k)
+    return a
+
+
+def _host_rows(trace):
+    torch.cuda.synchronize()
+    return trace.rows(), trace.counts()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 1. equal files
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,layout,gather", [(SMALL, "rb", False), (SMALL, "quad", False), (NATIVE, "rb", False), (NATIVE, "quad", False),
+                                                 (NATIVE, "quad", True)], ids=["S3-rb", "S3-quad", "S5-rb", "S5-quad", "S5-quad-gather"])
+def test_rollout_trace_writes_the_recorders_files(tmp_path, shape, layout, gather):
+    need_gpu()
+    B = 8
+    envs, numbers = [5, 0, B - 1], [10, 11, 12]
+    a = _workload(shape, layout, gather)
+    assert a.trace_len < N and a.se_offset[envs].any()                     # the tile index wraps, from a non-zero offset
+    rec = a.env.record(envs, root_path=str(tmp_path / "a"), simu_name="mult_slice", agent_name="mapf", episode_numbers=numbers)
+    a.env.reset()
+    for _ in range(N):
+        a.env.step()
+    assert len(rec.written) == len(envs)
+    b = _workload(shape, layout, gather)
+    trace = b.env.bind_trace(envs, N)
+    b.env.reset()
+    b.env.rollout(N)
+    torch.cuda.synchronize()
+    assert b.env.get_option("last_rollout_persistent") == 0 and b.env.get_option("last_rollout_launches") == N
+    c = trace.counts()
+    assert c["count"].tolist() == [N] * 3 and c["lost"].tolist() == [0] * 3
+    written = trace.write(str(tmp_path / "b"), "mult_slice", "mapf", episode_numbers=numbers)
+    assert [os.path.basename(p) for p in written] == [f"ep_{n}.npz" for n in numbers]
+    dropped = allocated = False
+    for n in numbers:
+        f = _assert_same_files(tmp_path / "a" / "hist" / "mult_slice" / "mapf" / f"ep_{n}.npz",
+                               tmp_path / "b" / "hist" / "mult_slice" / "mapf" / f"ep_{n}.npz")
+        # twin A's file is worth comparing with: an off-by-one tile or a row of zeros would differ from it
+        se = f["spectral_efficiencies"]
+        assert se.shape == (N, 1, b.env.U, b.env.R) and all(not np.array_equal(se[t], se[t + 1]) for t in range(N - 1)), n
+        dropped |= bool((f["dropped_pkts"] > 0).any())
+        allocated |= bool((f["sched_decision"] > 0).any())
+    assert dropped and allocated
+    a.env.close(); b.env.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 2. episode ends on the device
+# ----------------------------------------------------------------------------------------------------------------------
+def test_episode_ends_inside_a_rollout(tmp_path):
+    """Auto-reset over an episode table, per-env episode lengths, a rollout through three episodes of the shortest env: the trace is
+    cut where the recorder flushed, and the row at `done` still carries the finished episode's number, scenario and terminal
+    observation.  (Starts [0, 1, 3, 2]: the recorded envs 0 and 2 play episodes 0, 1, 2 and 3, 4 -- no file is written twice.)"""
+    need_gpu()
+    B, steps, envs = 4, 10, [2, 0]
+    lengths, start = np.asarray([3, 5, 4, 6], dtype=np.int32), np.asarray([0, 1, 3, 2], dtype=np.int32)
+
+    def make():
+        env, tabs, *_ = short_episode_setup(B, 6, idle_traffic=False)
+        env.set_max_steps(lengths)
+        env.enable_autoreset(0, 6, episode_numbers=start)
+        return env
+
+    a = make()
+    rec = a.record(envs, root_path=str(tmp_path / "a"), simu_name="mult_slice", agent_name="mapf")
+    flushed, now, flush = [], [0], rec.flush
+
+    def spy(which=None):
+        flushed.extend((k, now[0], int(rec.t[k]), int(rec.episode_numbers[k]), int(rec._desc["scenario"][k])) for k in which)
+        return flush(which)
+
+    rec.flush = spy
+    a.reset()
+    for t in range(steps):
+        now[0] = t
+        a.step()
+    b = make()
+    trace = b.bind_trace(envs, steps)
+    b.reset()
+    b.rollout(steps)
+    rows, counts = _host_rows(trace)
+    assert counts["count"].tolist() == [steps, steps]
+    eps = trace.episodes()
+    for i, e in enumerate(envs):
+        want = [f for f in flushed if f[0] == i]
+        done_eps = [x for x in eps[i] if x.complete]
+        assert len(want) == (3 if e == 0 else 2) and len(done_eps) == len(want)
+        for x, (_, t_end, length, number, scen) in zip(done_eps, want):
+            assert (x.stop, x.stop - x.start, x.episode_number, x.scenario) == (t_end + 1, length, number, scen) and length == lengths[e]
+            last = x.stop - 1
+            assert rows["done"][last, i] == 1 and not rows["done"][x.start:last, i].any()
+            assert rows["step_number"][x.start:x.stop, i].tolist() == list(range(length))
+            assert (rows["episode_number"][x.start:x.stop, i] == number).all() and (rows["scenario"][x.start:x.stop, i] == scen).all()
+        tail = eps[i][-1]
+        assert not tail.complete and tail.stop == steps and tail.episode_number == want[-1][3] + 1
+    written = trace.write(str(tmp_path / "b"), "mult_slice", "mapf")
+    assert sorted(os.path.basename(p) for p in written) == [f"ep_{n}.npz" for n in range(5)] and len(rec.written) == 5
+    for n in range(5):
+        f = _assert_same_files(tmp_path / "a" / "hist" / "mult_slice" / "mapf" / f"ep_{n}.npz",
+                               tmp_path / "b" / "hist" / "mult_slice" / "mapf" / f"ep_{n}.npz")
+        assert len(f["reward"]) == (3 if n < 3 else 4)
+    a.close(); b.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 3. full ring, 4. partitions: against one unclipped, unpartitioned run
+# ----------------------------------------------------------------------------------------------------------------------
+RING_ENVS = [6, 1, 3]
+
+
+@functools.lru_cache(maxsize=None)
+def _reference_rows():
+    wl = _workload(SMALL, "quad")
+    trace = wl.env.bind_trace(RING_ENVS, N)
+    wl.env.reset()
+    wl.env.rollout(N)
+    rows, counts = _host_rows(trace)
+    wl.env.close()
+    assert counts["count"].tolist() == [N] * 3 and (rows["dropped_pkts"] > 0).any() and (rows["rb_count"] > 0).any()
+    return rows
+
+
+def test_full_ring_stops_and_counts_what_it_lost():
+    need_gpu()
+    cap = 5
+    wl = _workload(SMALL, "quad")
+    trace = wl.env.bind_trace(RING_ENVS, cap, guard_rows=1)
+    wl.env.reset()
+    wl.env.rollout(N)
+    rows, counts = _host_rows(trace)
+    assert counts["count"].tolist() == [cap] * 3 and counts["lost"].tolist() == [N - cap] * 3
+    want = _reference_rows()
+    assert set(rows) == set(want)
+    for k in want:
+        assert rows[k].shape[0] == cap and np.array_equal(rows[k], want[k][:cap]), k
+    for k, g in trace.guard.items():
+        assert g.shape[0] == 1 and bool((g.contiguous().view(torch.uint8) == 0xA5).all()), k
+    trace.reset()                                         # the ring starts again at row 0
+    wl.env.rollout(2)
+    torch.cuda.synchronize()
+    c = trace.counts()
+    assert c["count"].tolist() == [2] * 3 and c["lost"].tolist() == [0] * 3
+    wl.env.close()
+
+
+def test_partitions_record_the_same_rows():
+    need_gpu()
+    wl = _workload(SMALL, "quad")
+    wl.env.set_partitions(2)                              # envs [0, 4) and [4, 8): 1 and 3 in the first range, 6 in the second
+    trace = wl.env.bind_trace(RING_ENVS, N)
+    wl.env.reset()
+    wl.env.rollout(N)
+    rows, counts = _host_rows(trace)
+    want = _reference_rows()
+    assert counts["count"].tolist() == [N] * 3 and counts["lost"].tolist() == [0] * 3
+    for k in want:
+        assert np.array_equal(rows[k], want[k]), k
+    wl.env.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 5. policy nets, 6. collect()
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("stochastic", [False, True])
+def test_policy_net_actions_are_recorded(stochastic):
+    """Under trained nets the row holds what the nets chose: the scores and the intra net's action the step consumed.  Deterministic
+    nets, and -- the mode of these random intra nets being one scheduler everywhere, which a constant would reproduce -- sampled
+    ones (Philox noise keyed by the seed: as repeatable)."""
+    need_gpu()
+    from tests import collect_ref as cr
+    B, T, envs = 8, 6, [7, 2, 4]
+    _, a, _ = cr.make_env("S5U25", "64x64", B, stochastic=stochastic, critics=False)
+    trace = a.bind_trace(envs, T)
+    idx = torch.as_tensor(envs, device=a.device)
+    scores, intra = [], []
+    for _ in range(T):
+        a.step()
+        scores.append(a.views()["policy_scores"].index_select(0, idx).clone())
+        intra.append(a.policy_actions()["intra"].index_select(0, idx).clone())
+    rows, counts = _host_rows(trace)
+    assert counts["count"].tolist() == [T] * 3
+    if stochastic:
+        assert torch.stack(intra).unique().numel() > 1     # (the intra net does choose: no constant would reproduce its actions)
+    assert np.array_equal(rows["scores"], torch.stack(scores).cpu().numpy())
+    assert np.array_equal(rows["intra"], torch.stack(intra).cpu().numpy())
+    _, b, _ = cr.make_env("S5U25", "64x64", B, stochastic=stochastic, critics=False)
+    twin = b.bind_trace(envs, T)
+    b.rollout(T)
+    rows_b, _ = _host_rows(twin)
+    for k in rows:
+        assert np.array_equal(rows[k], rows_b[k]), k
+    a.close(); b.close()
+
+
+def test_collect_records_the_trajectorys_rows():
+    need_gpu()
+    from tests import collect_ref as cr
+    B, T, envs = 12, 12, [10, 1, 6]                        # episode lengths 24, 7, 5 (collect_ref.EPISODE_LENGTHS)
+    _, env, _ = cr.make_env("S5U25", "64x64", B, stochastic=True, autoreset=True)
+    trace = env.bind_trace(envs, T, se=False)
+    rec = env.collect(T)
+    rows, counts = _host_rows(trace)
+    assert counts["count"].tolist() == [T] * 3 and "se" not in rows
+    reward, done, obs = (rec[k].cpu().numpy()[:, envs] for k in ("reward", "done", "obs_inter"))
+    assert done.any() and not done.all()
+    assert np.array_equal(rows["reward"], reward) and np.array_equal(rows["done"], done)
+    for t in range(T - 1):
+        go_on = done[t] == 0
+        assert go_on.any() and np.array_equal(rows["obs_inter"][t][go_on], obs[t + 1][go_on]), t
+    with pytest.raises(ValueError):
+        trace.write(".")                                   # no tiles recorded: no history file
+    env.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 7. explicit tiles, 8. errors
+# ----------------------------------------------------------------------------------------------------------------------
+def test_explicit_tiles_are_the_tiles_recorded():
+    need_gpu()
+    wl = _workload(SMALL, "quad")
+    env, envs, T = wl.env, [3, 7], 3
+    trace = env.bind_trace(envs, T)
+    env.reset()
+    g = torch.Generator(device=env.device); g.manual_seed(5)
+    tiles = [torch.rand((env.B, env.R, env.U), generator=g, device=env.device) * 20 for _ in range(T)]
+    for t in range(T):
+        env.step(se_tiles=tiles[t])
+    rows, counts = _host_rows(trace)
+    assert counts["count"].tolist() == [T] * 2
+    assert np.array_equal(rows["se"], torch.stack(tiles)[:, envs].cpu().numpy())
+    env.close()
+
+
+def test_errors_leave_the_handle_usable():
+    need_gpu()
+    from intent_radio_sched_multi_slice_amd._lib import RanEnvError
+    from intent_radio_sched_multi_slice_amd.workloads import quadriga_pool_from_power
+    wl = _workload(SMALL, "rb")
+    env = wl.env
+    for bad in ([0, env.B], [-1], [1, 2, 1], []):
+        with pytest.raises(RanEnvError, match=r"\(-1\)"):                 # RANENV_E_INVALID
+            env.bind_trace(bad, 4)
+    with pytest.raises(RanEnvError, match=r"\(-1\)"):
+        env.bind_trace([0], 0)
+    env.reset(); env.rollout(3); torch.cuda.synchronize()                 # nothing was bound: the handle steps as ever
+    assert int(env.views()["step_number"].min()) == 3
+    trace = env.bind_trace([2], 4)
+    with pytest.raises(RanEnvError, match=r"\(-1\)"):
+        env.bind_trace([2, 2], 4)                                         # a refused bind keeps the trace that was bound
+    env.rollout(2); torch.cuda.synchronize()
+    assert trace.counts()["count"].tolist() == [2]
+    # a handle whose tiles exist as gather sidecars only cannot record them
+    g = torch.Generator(device=env.device); g.manual_seed(3)
+    power = torch.rand((3 * TRACE_LEN, env.R, env.U), generator=g, device=env.device, dtype=torch.float64) * 4e-11 + 1e-14
+    eps = env.episodes
+    env.bind_se_gather_from_power(power)
+    env.set_episodes(**{k: eps[k] for k in ("scenario", "se_base", "se_len", "se_offset", "trf_base", "trf_len", "trf_offset")})
+    trace = env.bind_trace([2], 4)
+    env.reset()
+    with pytest.raises(RanEnvError, match=r"\(-3\)"):                     # RANENV_E_STATE
+        env.rollout(2)
+    with pytest.raises(RanEnvError, match=r"\(-3\)"):
+        env.step()
+    tile = quadriga_pool_from_power(power, env.R)[:env.B].contiguous()
+    env.step(se_tiles=tile)                                               # explicit tiles are recorded all the same
+    rows, counts = _host_rows(trace)
+    assert counts["count"].tolist() == [1] and np.array_equal(rows["se"][0, 0], tile[2].cpu().numpy())
+    trace = env.bind_trace([2], 4, se=False)
+    env.rollout(2); torch.cuda.synchronize()
+    assert trace.counts()["count"].tolist() == [2]
+    env.unbind_trace()
+    env.rollout(2); torch.cuda.synchronize()
+    assert trace.counts()["count"].tolist() == [2]
+    env.close()
