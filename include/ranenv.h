@@ -599,7 +599,8 @@ int ranenv_get_slice_metrics(ranenv_handle h, double **dev_running, double **dev
  *     enqueues exactly what it enqueues without this feature;
  *   - ranenv_step_dense records nothing (it has neither scores nor an intra choice).
  * ranenv_get_trace_counts returns device pointers to count / lost (RANENV_E_STATE while no trace is bound); ranenv_reset_trace
- * zeroes both: the next recorded TTI of every env is row 0 again. */
+ * zeroes both: the next recorded TTI of every env is row 0 again.  The caller may write the counters itself in stream order
+ * (zero one env's pair: that env alone starts again at row 0). */
 typedef struct {
     int32_t n_envs, capacity;
     const int32_t *envs;                  /* HOST */

@@ -195,7 +195,7 @@ class BatchedRanEnv:
         self._step_fn = self._lib.ranenv_step
         self.policy, self.fixed_intra = POLICY_MARR, INTRA_RR      # the library's defaults (ranenv_create)
         self.traffic_seed, self.env_id_base = None, 0
-        self._recorder = None
+        self._recorder = self._trace = None      # record() / bind_trace(): a handle holds one trace, the recorder's or the caller's
         self._autoreset = False
         self.term_obs_inter = self.term_obs_intra = self.term_head_obs = None
         self.se_mode = "stream"
@@ -871,9 +871,9 @@ class BatchedRanEnv:
         self._check(self._lib.ranenv_set_autoreset(self._h, 0, 0, 0, 0, 0, None, self._stream()), "ranenv_set_autoreset")
         self._autoreset = False
 
-    def _after_step(self, se, ic):
+    def _after_step(self):
         if self._recorder is not None:
-            self._recorder.on_step(se, ic, self.done)
+            self._recorder.on_step(self.done)
         if self._autoreset:
             st = self._lib.ranenv_autoreset(self._h, _ptr(self.done), _ptr(self.obs_inter), _ptr(self.obs_intra),
                                             _ptr(self.term_obs_inter), _ptr(self.term_obs_intra), _ptr(self.term_head_obs),
@@ -883,31 +883,37 @@ class BatchedRanEnv:
 
     def record(self, envs, root_path: str = ".", simu_name: str = "mult_slice", agent_name: str = "agent",
                episode_numbers=None, marl: bool = True):
-        """Keep the traces of the listed envs on the device and write ``hist/{simu_name}/{agent_name}/ep_{n}.npz``
-        (the 16 keys of results/gen_results.py:88-108) whenever one of them reports ``done``.  ``record(None)``
-        stops recording.  Returns the recorder (``.written`` lists the files)."""
-        if envs is None:
+        """Record the listed envs into a device trace (``bind_trace``) and, under ``step()``, write
+        ``hist/{simu_name}/{agent_name}/ep_{n}.npz`` (the 16 keys of results/gen_results.py:88-108) at the TTI one of them reports
+        ``done``.  ``record(None)`` stops recording and unbinds that trace.  Returns the recorder (``.written`` lists the files)."""
+        if self._recorder is not None:
             self._recorder = None
+            self.unbind_trace()
+        if envs is None:
             return None
         from .history import HistoryRecorder
         if self.tables is None or self.episodes is None:
             raise RanEnvError("record() needs load_scenarios + set_episodes first")
+        if self._trace is not None:
+            raise RanEnvError("record() binds a trace of its own and a handle holds one: unbind_trace() first")
         self._recorder = HistoryRecorder(self, envs, root_path, simu_name, agent_name, episode_numbers, marl)
         return self._recorder
 
     def bind_trace(self, envs, capacity: int, se: bool = True, guard_rows: int = 0):
         """Record the per-TTI history of the listed envs ON THE DEVICE, behind every step of whatever call steps them --
         ``rollout()``, ``evaluate()``, ``collect()``, ``collect_head()``, ``collect_replay()``, ``step()``, ``step_async()``, with or
-        without partitions -- into a ring of ``capacity`` rows per env (ranenv_bind_trace, include/ranenv.h): the rows
-        ``record()`` gathers under ``step()``, plus the intra-slice choice an intra net made, and per row the step index, episode
-        number, scenario and ``done``.  A full ring stops recording and counts the rows it lost.  ``se=False`` leaves the SE tile
-        (4 R U of a row's bytes) out; such a trace cannot ``write()`` history files.  ``guard_rows``: rows allocated behind the
+        without partitions -- into a ring of ``capacity`` rows per env (ranenv_bind_trace, include/ranenv.h): what a history file
+        holds of a TTI, and per row the step index, episode number, scenario and ``done``.  A full ring stops recording and counts
+        the rows it lost.  ``se=False`` leaves the SE tile (4 R U of a row's bytes) out; such a trace cannot ``write()`` history
+        files.  ``record()`` binds one of its own: not both at a time.  ``guard_rows``: rows allocated behind the
         ring and filled with 0xA5 bytes that the library is not told about (``trace.guard``: a check that nothing writes there).
         Returns the DeviceTrace (history.py: ``.buffers``, ``.counts()``, ``.episodes()``, ``.write()``).  While bound, a rollout runs
         one TTI per launch and no persistent launch, as with slice metrics on."""
         from .history import DeviceTrace
         if self.tables is None:
             raise RanEnvError("bind_trace() needs load_scenarios first")
+        if self._recorder is not None:
+            raise RanEnvError("bind_trace(): record() holds the handle's trace: record(None) first")
         envs = [int(e) for e in envs]
         n, cap, guard_rows = len(envs), int(capacity), int(guard_rows)
         dims = {"U": (self.U,), "RU": (self.R, self.U), "P": (self.S + 1,), "S": (self.S,), "I": (10 * self.S,), "SW": (self.S, self.W),
@@ -933,8 +939,13 @@ class BatchedRanEnv:
         d_cnt = torch.as_tensor(_DevArray(cnt.value, (n,), "i4", self), device=self.device)
         d_lost = torch.as_tensor(_DevArray(lost.value, (n,), "i4", self), device=self.device)
 
-        def reset():
-            self._check(self._lib.ranenv_reset_trace(self._h, self._stream()), "ranenv_reset_trace")
+        def reset(columns=None):
+            if columns is None:
+                self._check(self._lib.ranenv_reset_trace(self._h, self._stream()), "ranenv_reset_trace")
+            else:                                          # the library's counters, written in stream order
+                cols = torch.as_tensor(list(columns), dtype=torch.int64, device=self.device)
+                d_cnt.index_fill_(0, cols, 0)
+                d_lost.index_fill_(0, cols, 0)
 
         self._trace = DeviceTrace(envs, cap, {k: b[:cap] for k, b in full.items()}, lambda: (d_cnt.cpu().numpy(), d_lost.cpu().numpy()),
                                   self.tables, self.R, self.Us, guard={k: b[cap:] for k, b in full.items()}, reset_fn=reset)
@@ -943,6 +954,8 @@ class BatchedRanEnv:
     def unbind_trace(self) -> None:
         """Stop recording (ranenv_bind_trace with NULL).  The DeviceTrace handed out keeps its buffers and can still be read and
         written, its counters included, until the next ``bind_trace``."""
+        if self._recorder is not None:
+            raise RanEnvError("unbind_trace(): the bound trace is record()'s: record(None) stops recording and unbinds it")
         self._check(self._lib.ranenv_bind_trace(self._h, None, self._stream()), "ranenv_bind_trace")
         self._trace = None
         self._keep.pop("trace", None)
@@ -973,7 +986,7 @@ class BatchedRanEnv:
             if st != 0:
                 self._check(st, "ranenv_step")
             if self._recorder is not None or self._autoreset:
-                self._after_step(None, None)
+                self._after_step()
             return self._obs(), self.reward, self.done
         sc = self._dev(inter_scores, torch.float64, (self.B, self.S), "inter_scores")
         ic = self._dev(intra_choice, torch.uint8, (self.B, self.S), "intra_choice")
@@ -985,7 +998,7 @@ class BatchedRanEnv:
                                                self._stream()), "ranenv_step")
         self._keep["last_inputs"] = (sc, ic, tr, se)
         if self._recorder is not None or self._autoreset:
-            self._after_step(se, ic)
+            self._after_step()
         return self._obs(), self.reward, self.done
 
     # -- a learner in the loop: ranges of the batch stepped alternately on their own streams -------------------------

@@ -4,11 +4,11 @@ arrays are indexed ``[step, ...]``, ``spectral_efficiencies`` and ``sched_decisi
 ``(steps, 1, U, R)`` (:262-265, :629), ``slice_ue_assoc`` is ``(steps, S, U)`` (:279), ``reward[idx]["player_0"]`` for
 multi-agent runs (:162), ``slice_req[step]["slice_k"]`` dicts (:422-426)).
 
-Three producers: the B = 1 facade (comm_env.MARLCommEnv, ``save_hist=True``); the batched recorder below, which keeps the
-traces of selected envs of a BatchedRanEnv on the device and writes one file per env at ``done`` -- paced by the host, under
-``step()`` only --; and DeviceTrace, the ring a kernel of the library fills behind every step of whatever call steps the envs
-(``rollout``, ``evaluate``, ``collect*``, ``step``), cut into episodes and written afterwards.  The two batched producers turn the
-recorded rows of one env's episode into the 16-key dict with one function, ``rows_to_hist``.
+Two producers: the B = 1 facade (comm_env.MARLCommEnv, ``save_hist=True``), and DeviceTrace, the ring a kernel of the library fills
+behind every step of whatever call steps selected envs of a BatchedRanEnv (``rollout``, ``evaluate``, ``collect*``, ``step``), cut
+into episodes and written afterwards by ``write()`` -- or, under ``step()`` only, at the TTI an episode ends by HistoryRecorder
+(``BatchedRanEnv.record``), which paces such a ring from the host.  Both ways the recorded rows of one env's episode become the
+16-key dict in ``rows_to_hist``.
 """
 from __future__ import annotations
 
@@ -48,7 +48,7 @@ def write_episode_npz(path: str, hist: Dict[str, Sequence]) -> str:
     return path
 
 
-# what a recorded row holds per env (HistoryRecorder's device buffers, DeviceTrace's ring): name -> trailing shape
+# what a history file takes from a recorded row of DeviceTrace's ring (the ring adds DeviceTrace.BOOKKEEPING)
 ROW_KEYS = ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts", "queue_pkts", "queue_age_sum", "rb_start",
             "rb_count", "se", "reward", "scores", "intra", "obs_inter", "obs_intra")
 
@@ -100,124 +100,69 @@ def rows_to_hist(rows: Dict[str, np.ndarray], tables, scen: int, R: int, Us: int
 
 
 class HistoryRecorder:
-    """Traces of selected envs of a BatchedRanEnv, accumulated on the device (a few small gathers on the env's
-    stream after every step), written as reference-format history files when the env reports ``done``.
+    """``BatchedRanEnv.record``: the host pacer of a DeviceTrace of the listed envs (bound here, one ring row per TTI of the longest
+    episode among them when recording starts).  Under ``step()`` it reads the recorded envs' ``done`` every TTI, writes a
+    reference-format history file at the TTI an env's episode ends and restarts that env's column of the ring.
 
-    Every recorded env has its own step counter: envs may be reset under a mask, run episodes of different lengths
-    (``set_max_steps``) or move on to their next episode on the device (``enable_autoreset``: the recorder then takes
-    the episode number, the scenario and the channel trace of a new episode from the descriptors the device installed).
-    ``episode_numbers[i]`` is the episode number env ``envs[i]`` is playing when recording starts; it names the file and,
-    without device auto-reset, is advanced by one after every write.  Association / intent columns come from the
-    scenario pool row the env replays; the agent action recorded is the inter-slice score vector the step used and the
-    intra-slice scheduler choices.
+    Every recorded env has its own step counter ``t`` (a host mirror of the ring's row count): envs may be reset under a mask, run
+    episodes of different lengths (``set_max_steps``) or move on to their next episode on the device (``enable_autoreset``: the
+    file is then named by the episode number the ring recorded).  ``episode_numbers[i]`` is the episode number env ``envs[i]`` is
+    playing when recording starts; without device auto-reset it names the file and is advanced by one after every write.
+    Association / intent columns come from the scenario pool row the ring recorded; the agent action recorded is the inter-slice
+    score vector and the intra-slice schedulers the step used.
     """
 
     def __init__(self, env, envs: Sequence[int], root_path: str = ".", simu_name: str = "mult_slice",
                  agent_name: str = "agent", episode_numbers: Optional[Sequence[int]] = None, marl: bool = True):
         import torch
-        self._torch = torch
         self.env = env
-        self.idx = torch.as_tensor(list(envs), dtype=torch.int64, device=env.device)
         self.envs = [int(e) for e in envs]
         if any(e < 0 or e >= env.B for e in self.envs):
             raise ValueError("recorded env index outside the batch")
         self.root_path, self.simu_name, self.agent_name, self.marl = root_path, simu_name, agent_name, marl
         self.episode_numbers = list(episode_numbers) if episode_numbers is not None else [0] * len(self.envs)
         me = getattr(env, "max_steps_env", None)
-        n, U, S = len(self.envs), env.U, env.S
-        T = self.T = int(env.max_steps if me is None else np.asarray(me)[self.envs].max())
-        z = lambda *sh, dt=torch.int32: torch.zeros(sh, dtype=dt, device=env.device)
-        self.buf = {
-            "pkt_incoming": z(T, n, U), "pkt_throughputs": z(T, n, U), "pkt_effective_thr": z(T, n, U),
-            "dropped_pkts": z(T, n, U), "queue_pkts": z(T, n, U), "queue_age_sum": z(T, n, U, dt=torch.int64),
-            "rb_start": z(T, n, U), "rb_count": z(T, n, U),
-            "se": z(T, n, env.R, U, dt=torch.float32),
-            "reward": z(T, n, S + 1, dt=torch.float64), "scores": z(T, n, S, dt=torch.float64),
-            "intra": z(T, n, S, dt=torch.uint8),
-            "obs_inter": z(T, n, S * 10, dt=torch.float32), "obs_intra": z(T, n, S, env.W, dt=torch.float32),
-        }
-        self.t = np.zeros(n, dtype=np.int64)                 # steps recorded of every slot's current episode
-        self._cols = torch.arange(n, device=env.device)
-        self._stale = np.zeros(n, dtype=bool)                # the slot's episode changed on the device: re-read its descriptor
-        self._desc = None
-        self._refresh(np.arange(n))
+        self.T = int(env.max_steps if me is None else np.asarray(me)[self.envs].max())
+        self.trace = env.bind_trace(self.envs, capacity=self.T)
+        self.idx = torch.as_tensor(self.envs, dtype=torch.int64, device=env.device)
+        self.t = np.zeros(len(self.envs), dtype=np.int64)    # steps recorded of every slot's current episode
         self.written: List[str] = []
 
-    def _refresh(self, slots):
-        """(Re-)read the episode descriptors -- scenario, channel trace -- of the given slots as they are on the device."""
-        eps = self.env.episode_descriptors()
-        if self._desc is None:
-            self._desc = np.array(eps[self.envs])
-        else:
-            self._desc[slots] = eps[np.asarray(self.envs)[slots]]
-        if self.env._autoreset:
-            num = self.env.views()["episode_number"].index_select(0, self.idx).cpu().numpy()
-            for k in slots:
-                self.episode_numbers[k] = int(num[k])
-        self._stale[slots] = False
+    def _restart(self, slots: Sequence[int]):
+        if len(slots):
+            self.trace.reset(slots)
+            self.t[slots] = 0
 
     def on_reset(self, env_mask=None):
         """Called by BatchedRanEnv.reset: the masked envs (all without a mask) start an episode; what was recorded of
         their unfinished one is dropped."""
-        if env_mask is None:
-            slots = np.arange(len(self.envs))
-        else:
-            m = env_mask.index_select(0, self.idx).cpu().numpy() if hasattr(env_mask, "index_select") else np.asarray(env_mask)[self.envs]
-            slots = np.nonzero(m)[0]
-        self.t[slots] = 0
-        if len(slots):
-            self._refresh(slots)
+        m = np.ones(len(self.envs)) if env_mask is None else env_mask.index_select(0, self.idx).cpu().numpy()
+        self._restart(np.nonzero(m)[0].tolist())
 
-    def on_step(self, se_tiles, intra_choice, done):
-        """Called by BatchedRanEnv.step after the launch (and before an auto-reset is enqueued); ``se_tiles`` = explicit
-        tiles of this step or None (pool)."""
-        torch, env, i = self._torch, self.env, self.idx
-        if self._stale.any():
-            self._refresh(np.nonzero(self._stale)[0])
+    def on_step(self, done):
+        """Called by BatchedRanEnv.step after the launch (and before an auto-reset is enqueued)."""
         if (self.t >= self.T).any():
             raise RuntimeError("recorder: an env ran past the longest episode length known when recording started "
                                "(set_max_steps after record()?)")
-        tt, cols = torch.as_tensor(self.t, device=env.device), self._cols
-        v = env.views()
-        for k in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts", "queue_pkts", "queue_age_sum",
-                  "rb_start", "rb_count"):
-            self.buf[k][tt, cols] = v[k].index_select(0, i)
-        self.buf["scores"][tt, cols] = v["policy_scores"].index_select(0, i)
-        self.buf["reward"][tt, cols] = env.reward.index_select(0, i)
-        self.buf["obs_inter"][tt, cols] = env.obs_inter.index_select(0, i)
-        self.buf["obs_intra"][tt, cols] = env.obs_intra.index_select(0, i)
-        if intra_choice is not None:
-            self.buf["intra"][tt, cols] = intra_choice.index_select(0, i)
-        else:
-            self.buf["intra"][tt, cols] = int(env.fixed_intra if env.fixed_intra != 255 else 0)
-        if se_tiles is not None:
-            self.buf["se"][tt, cols] = se_tiles.index_select(0, i)
-        else:
-            d = self._desc
-            tile = d["se_base"] + (d["se_offset"] + self.t) % d["se_len"]
-            self.buf["se"][tt, cols] = env.pooled_tiles(torch.as_tensor(tile, device=env.device))
         self.t += 1
-        d = done.index_select(0, i).cpu().numpy().astype(bool)         # recording is a diagnostic mode: one small sync
-        if d.any():
-            which = [k for k in range(len(self.envs)) if d[k]]
+        which = np.nonzero(done.index_select(0, self.idx).cpu().numpy())[0].tolist()      # recording is a diagnostic mode: one small sync
+        if which:
             self.flush(which)
-            self.t[which] = 0
-            if env._autoreset:
-                self._stale[which] = True                              # the device installs the next episode after this call
+            self._restart(which)
 
     def flush(self, which: Optional[Sequence[int]] = None) -> List[str]:
-        """Write the steps recorded so far of the current episode of recorder slots ``which`` (all by default)."""
+        """Write the steps recorded so far of the current episode of recorder slots ``which`` (all by default; a slot with none
+        is passed over)."""
         env = self.env
-        which = list(range(len(self.envs))) if which is None else list(which)
-        Tmax = int(self.t[which].max()) if which else 0
-        host = {k: b[:Tmax].cpu().numpy() for k, b in self.buf.items()}
+        which = [k for k in (range(len(self.envs)) if which is None else which) if self.t[k] > 0]
+        rows = self.trace.rows(n=int(self.t[which].max(initial=0)))
         paths = []
         for k in which:
             T = int(self.t[k])
-            hist = rows_to_hist({name: a[:T, k] for name, a in host.items()}, env.tables, int(self._desc["scenario"][k]), env.R, env.Us,
+            number = int(rows["episode_number"][T - 1, k]) if env._autoreset else self.episode_numbers[k]
+            hist = rows_to_hist({name: rows[name][:T, k] for name in ROW_KEYS}, env.tables, int(rows["scenario"][T - 1, k]), env.R, env.Us,
                                 self.marl)
-            paths.append(write_episode_npz(hist_path(self.root_path, self.simu_name, self.agent_name,
-                                                     self.episode_numbers[k]), hist))
+            paths.append(write_episode_npz(hist_path(self.root_path, self.simu_name, self.agent_name, number), hist))
             if not env._autoreset:
                 self.episode_numbers[k] += 1
         self.written += paths
@@ -267,15 +212,17 @@ class DeviceTrace:
         count, lost = self._counts_fn()
         return {"count": np.asarray(count, dtype=np.int32), "lost": np.asarray(lost, dtype=np.int32)}
 
-    def reset(self) -> None:
-        """Start again at row 0 of every column (count and lost zeroed on the device; the rows stay until overwritten)."""
+    def reset(self, columns: Optional[Sequence[int]] = None) -> None:
+        """Start again at row 0 of every column, or of the listed ones only (count and lost zeroed on the device, in stream order;
+        the rows stay until overwritten)."""
         if self._reset_fn is None:
             raise RuntimeError("this trace has no device ring to reset")
-        self._reset_fn()
+        self._reset_fn(columns)
 
-    def rows(self, names: Optional[Sequence[str]] = None) -> Dict[str, np.ndarray]:
-        """Host copies of the first max(count) rows of the named buffers (all by default)."""
-        n = int(self.counts()["count"].max(initial=0))
+    def rows(self, names: Optional[Sequence[str]] = None, n: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Host copies of the first ``n`` rows (default: max(count), one more small copy to learn it) of the named buffers (all by
+        default)."""
+        n = int(self.counts()["count"].max(initial=0)) if n is None else n
         out = {}
         for k in (self.buffers if names is None else names):
             b = self.buffers[k][:n]

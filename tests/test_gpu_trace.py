@@ -1,7 +1,9 @@
 """Device traces (ranenv_bind_trace, include/ranenv.h; history.DeviceTrace): the per-TTI history rows a kernel copies behind every
 step, inside rollout / evaluate / collect as under step().  Everything recorded is a pure copy, so every comparison here is
-np.array_equal / torch.equal, with no tolerance.  The reference side is the existing HistoryRecorder (env.record) under a step()
-loop on a twin env built from the same arguments."""
+np.array_equal / torch.equal, with no tolerance.  env.record() paces such a trace from the host under a step() loop, so a file
+comparison between it and rollout() with a bound trace says that the schedule (step loop against rollout, partitions) does not change
+a file; what a file must hold is stated against a host copy of the SE pool, the env's views after a twin step() loop and the
+episode table (and, for every row, against the CPU oracle in tests/test_gpu_history.py)."""
 from __future__ import annotations
 
 import functools
@@ -77,7 +79,10 @@ def test_rollout_trace_writes_the_recorders_files(tmp_path, shape, layout, gathe
     for _ in range(N):
         a.env.step()
     assert len(rec.written) == len(envs)
+    last = {k: a.env.views()[k].cpu().numpy() for k in ("rb_count", "pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts")}
     b = _workload(shape, layout, gather)
+    pool, eps = b.se_pool.cpu().numpy(), b.env.episodes    # the RB-major tensor the pool was bound from: [tiles, R, U], no kernel writes it
+    assert pool.shape[1:] == (b.env.R, b.env.U)
     trace = b.env.bind_trace(envs, N)
     b.env.reset()
     b.env.rollout(N)
@@ -88,11 +93,19 @@ def test_rollout_trace_writes_the_recorders_files(tmp_path, shape, layout, gathe
     written = trace.write(str(tmp_path / "b"), "mult_slice", "mapf", episode_numbers=numbers)
     assert [os.path.basename(p) for p in written] == [f"ep_{n}.npz" for n in numbers]
     dropped = allocated = False
-    for n in numbers:
+    for e, n in zip(envs, numbers):
+        # the schedule does not change a file: the step() loop under record() against rollout() with a bound trace
         f = _assert_same_files(tmp_path / "a" / "hist" / "mult_slice" / "mapf" / f"ep_{n}.npz",
                                tmp_path / "b" / "hist" / "mult_slice" / "mapf" / f"ep_{n}.npz")
-        # twin A's file is worth comparing with: an off-by-one tile or a row of zeros would differ from it
         se = f["spectral_efficiencies"]
+        for t in range(N):                                 # the tile the step read, pad RBs of a quad pool de-interleaved: [U, R] of the pool's [R, U]
+            tile = int(eps["se_base"][e] + (eps["se_offset"][e] + t) % eps["se_len"][e])
+            assert np.array_equal(se[t, 0], pool[tile].T.astype(np.float64)), (n, t)
+        if e == envs[0]:                                   # the last row against the env's own state behind the twin's last step()
+            assert np.array_equal(f["sched_decision"][N - 1, 0].sum(axis=1), last["rb_count"][e].astype(np.float64))
+            for k in ("pkt_incoming", "pkt_throughputs", "pkt_effective_thr", "dropped_pkts"):
+                assert np.array_equal(f[k][N - 1], last[k][e].astype(np.float64)), k
+        # the files are worth comparing: an off-by-one tile or a row of zeros would show
         assert se.shape == (N, 1, b.env.U, b.env.R) and all(not np.array_equal(se[t], se[t + 1]) for t in range(N - 1)), n
         dropped |= bool((f["dropped_pkts"] > 0).any())
         allocated |= bool((f["sched_decision"] > 0).any())
@@ -105,8 +118,9 @@ def test_rollout_trace_writes_the_recorders_files(tmp_path, shape, layout, gathe
 # ----------------------------------------------------------------------------------------------------------------------
 def test_episode_ends_inside_a_rollout(tmp_path):
     """Auto-reset over an episode table, per-env episode lengths, a rollout through three episodes of the shortest env: the trace is
-    cut where the recorder flushed, and the row at `done` still carries the finished episode's number, scenario and terminal
-    observation.  (Starts [0, 1, 3, 2]: the recorded envs 0 and 2 play episodes 0, 1, 2 and 3, 4 -- no file is written twice.)"""
+    cut where the recorder flushed, and the row at `done` still carries the finished episode's number, its scenario (the episode
+    table's row of that number) and terminal observation.  (Starts [0, 1, 3, 2]: the recorded envs 0 and 2 play episodes 0, 1, 2
+    and 3, 4 -- no file is written twice.)"""
     need_gpu()
     B, steps, envs = 4, 10, [2, 0]
     lengths, start = np.asarray([3, 5, 4, 6], dtype=np.int32), np.asarray([0, 1, 3, 2], dtype=np.int32)
@@ -115,22 +129,24 @@ def test_episode_ends_inside_a_rollout(tmp_path):
         env, tabs, *_ = short_episode_setup(B, 6, idle_traffic=False)
         env.set_max_steps(lengths)
         env.enable_autoreset(0, 6, episode_numbers=start)
-        return env
+        return env, tabs
 
-    a = make()
+    a, tabs = make()
     rec = a.record(envs, root_path=str(tmp_path / "a"), simu_name="mult_slice", agent_name="mapf")
     flushed, now, flush = [], [0], rec.flush
 
     def spy(which=None):
-        flushed.extend((k, now[0], int(rec.t[k]), int(rec.episode_numbers[k]), int(rec._desc["scenario"][k])) for k in which)
-        return flush(which)
+        steps_recorded = [int(rec.t[k]) for k in which]
+        paths = flush(which)
+        flushed.extend((k, now[0], T, int(os.path.basename(p)[3:-4])) for k, T, p in zip(which, steps_recorded, paths))
+        return paths
 
     rec.flush = spy
     a.reset()
     for t in range(steps):
         now[0] = t
         a.step()
-    b = make()
+    b, _ = make()
     trace = b.bind_trace(envs, steps)
     b.reset()
     b.rollout(steps)
@@ -141,14 +157,17 @@ def test_episode_ends_inside_a_rollout(tmp_path):
         want = [f for f in flushed if f[0] == i]
         done_eps = [x for x in eps[i] if x.complete]
         assert len(want) == (3 if e == 0 else 2) and len(done_eps) == len(want)
-        for x, (_, t_end, length, number, scen) in zip(done_eps, want):
-            assert (x.stop, x.stop - x.start, x.episode_number, x.scenario) == (t_end + 1, length, number, scen) and length == lengths[e]
+        for j, (x, (_, t_end, length, number)) in enumerate(zip(done_eps, want)):
+            scen = number % tabs.n_scenarios               # (short_episode_setup's table: episode n plays scenario n mod n_scenarios)
+            assert number == start[e] + j and length == lengths[e]
+            assert (x.stop, x.stop - x.start, x.episode_number, x.scenario) == (t_end + 1, lengths[e], number, scen)
             last = x.stop - 1
             assert rows["done"][last, i] == 1 and not rows["done"][x.start:last, i].any()
             assert rows["step_number"][x.start:x.stop, i].tolist() == list(range(length))
             assert (rows["episode_number"][x.start:x.stop, i] == number).all() and (rows["scenario"][x.start:x.stop, i] == scen).all()
         tail = eps[i][-1]
         assert not tail.complete and tail.stop == steps and tail.episode_number == want[-1][3] + 1
+        assert rec.t[i] == tail.stop - tail.start          # the recorder's host mirror of its own ring
     written = trace.write(str(tmp_path / "b"), "mult_slice", "mapf")
     assert sorted(os.path.basename(p) for p in written) == [f"ep_{n}.npz" for n in range(5)] and len(rec.written) == 5
     for n in range(5):
@@ -328,3 +347,44 @@ def test_errors_leave_the_handle_usable():
     env.rollout(2); torch.cuda.synchronize()
     assert trace.counts()["count"].tolist() == [2]
     env.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 9. one trace per handle: the recorder's or the caller's
+# ----------------------------------------------------------------------------------------------------------------------
+def test_recorder_and_callers_trace_exclude_each_other(tmp_path):
+    need_gpu()
+    from intent_radio_sched_multi_slice_amd._lib import RanEnvError
+    envs, numbers, steps = [2, 0], [4, 9], 6
+
+    def record_an_episode(env, root):
+        rec = env.record(envs, root_path=str(root), simu_name="mult_slice", agent_name="mapf", episode_numbers=numbers)
+        env.reset()
+        for _ in range(steps):
+            env.step()
+        assert [os.path.basename(p) for p in rec.written] == [f"ep_{n}.npz" for n in numbers]
+        return rec.written
+
+    env = _workload(SMALL, "quad", B=4, steps=steps).env
+    env.record(envs, root_path=str(tmp_path / "unused"))
+    with pytest.raises(RanEnvError, match="record"):
+        env.bind_trace([1], steps)                           # recording: the handle's trace is the recorder's
+    with pytest.raises(RanEnvError, match="record"):
+        env.unbind_trace()
+    env.record(None)
+    trace = env.bind_trace([1], steps)                       # ... and free again
+    with pytest.raises(RanEnvError, match="trace"):
+        env.record(envs, root_path=str(tmp_path / "unused"))
+    env.reset(); env.rollout(3); torch.cuda.synchronize()
+    assert trace.counts()["count"].tolist() == [3]           # both refusals left the caller's trace bound
+    env.unbind_trace()
+    later = record_an_episode(env, tmp_path / "later")
+    # a twin that never bound or refused anything, taken through the same TTIs (by default a reset keeps the policy's 10-TTI window)
+    fresh_env = _workload(SMALL, "quad", B=4, steps=steps).env
+    fresh_env.reset(); fresh_env.rollout(3)
+    fresh = record_an_episode(fresh_env, tmp_path / "fresh")
+    for x, y in zip(later, fresh):
+        f = _assert_same_files(x, y)
+        assert len(f["reward"]) == steps and (f["sched_decision"] > 0).any()
+    assert not os.path.exists(tmp_path / "unused")
+    env.close(); fresh_env.close()

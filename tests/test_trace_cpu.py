@@ -1,6 +1,7 @@
 """Device traces, the parts that need no GPU: header and bindings agree, DeviceTrace's host side (cutting recorded rows into
-episodes, writing history files) on synthetic numpy rows, the row-to-dict function both batched producers share pinned against a
-restatement of what HistoryRecorder.flush did before it was shared, and a planted slip: rows whose SE is one TTI late are caught by
+episodes, restarting single columns, writing history files) on synthetic numpy rows, the row-to-dict function of DeviceTrace.write
+and HistoryRecorder.flush pinned against a restatement of what HistoryRecorder.flush did when it was the only producer, and a
+planted slip: rows whose SE is one TTI late are caught by
 the file comparison of tests/test_gpu_trace.py -- under that test's conditions on its inputs, and not without them."""
 from __future__ import annotations
 
@@ -43,8 +44,15 @@ def _rows(T, n, seed=0, done_at=()):
 
 def _trace(rows, count, envs, tables, lost=None):
     from intent_radio_sched_multi_slice_amd.history import DeviceTrace
-    count = np.asarray(count, dtype=np.int32)
-    return DeviceTrace(envs, len(rows["done"]), rows, lambda: (count, np.zeros_like(count) if lost is None else lost), tables, R, Us)
+    count = np.asarray(count, dtype=np.int32)               # (an int32 array is kept as it is: the caller plays the device on it)
+    lost = np.zeros_like(count) if lost is None else lost
+
+    def reset(columns=None):
+        sel = slice(None) if columns is None else list(columns)
+        count[sel] = 0
+        lost[sel] = 0
+
+    return DeviceTrace(envs, len(rows["done"]), rows, lambda: (count, lost), tables, R, Us, reset_fn=reset)
 
 
 def _flush_before_the_refactor(host, k, T, tables, scen, marl):
@@ -185,35 +193,75 @@ def test_rows_to_hist_is_what_flush_did(marl):
 
 
 def test_recorder_and_trace_write_identical_bytes(tmp_path):
-    """HistoryRecorder.flush (driven with a stub env: it only reads host copies of its buffers) and DeviceTrace.write on the same rows."""
-    from intent_radio_sched_multi_slice_amd.history import HistoryRecorder, ROW_KEYS
+    """HistoryRecorder.flush over a numpy-backed DeviceTrace (a stub env hands it out of bind_trace) and DeviceTrace.write on the same
+    rows.  The ring's counters stay at zero: flush goes by the recorder's host mirror `t` and reads neither."""
+    pytest.importorskip("torch")
+    from intent_radio_sched_multi_slice_amd.history import HistoryRecorder
     tables = _tables()
     T, envs = 5, [3, 1]
     rows = _rows(T, 2, seed=3, done_at=[(T - 1, 0), (T - 1, 1)])
     rows["episode_number"][:, 0], rows["episode_number"][:, 1], rows["scenario"][:] = 8, 9, [2, 1]
 
-    class Host:                                            # what flush() asks of a device buffer: [:n].cpu().numpy()
-        def __init__(self, a): self.a = a
-        def __getitem__(self, i): return Host(self.a[i])
-        def cpu(self): return self
-        def numpy(self): return self.a
-
     class Env:
-        pass
+        B, max_steps, device = 4, T, "cpu"
+
+        def bind_trace(self, which, capacity):
+            assert capacity == T
+            return _trace(rows, [0, 0], which, tables)
 
     env = Env()
-    env.tables, env.S, env.U, env.R, env.Us, env._autoreset = tables, S, U, R, Us, True
-    rec = HistoryRecorder.__new__(HistoryRecorder)
-    rec.env, rec.envs, rec.marl, rec.written = env, envs, True, []
-    rec.root_path, rec.simu_name, rec.agent_name = str(tmp_path / "a"), "mult_slice", "mapf"
-    rec.buf = {k: Host(rows[k]) for k in ROW_KEYS}
-    rec.t, rec.episode_numbers = np.asarray([T, T]), [8, 9]
-    rec._desc = np.zeros(2, dtype=[("scenario", "<i4")]); rec._desc["scenario"] = [2, 1]
-    pa = rec.flush()
+    env.tables, env.R, env.Us = tables, R, Us
     pb = _trace(rows, [T, T], envs, tables).write(str(tmp_path / "b"), "mult_slice", "mapf")
-    assert [os.path.basename(p) for p in pa] == [os.path.basename(p) for p in pb] == ["ep_8.npz", "ep_9.npz"]
-    for a, b in zip(pa, pb):
-        assert open(a, "rb").read() == open(b, "rb").read()
+    # device auto-reset: the ring's episode_number names the file; without: episode_numbers, advanced by one after the write
+    for autoreset, first, after in ((True, [0, 0], [0, 0]), (False, [8, 9], [9, 10])):
+        env._autoreset = autoreset
+        rec = HistoryRecorder(env, envs, str(tmp_path / f"a{autoreset:d}"), "mult_slice", "mapf", episode_numbers=first)
+        assert rec.T == T and rec.envs == envs and rec.t.tolist() == [0, 0] and rec.flush() == []
+        rec.t[:] = T
+        pa = rec.flush()
+        assert rec.written == pa and rec.episode_numbers == after
+        assert [os.path.basename(p) for p in pa] == [os.path.basename(p) for p in pb] == ["ep_8.npz", "ep_9.npz"]
+        for x, y in zip(pa, pb):
+            assert open(x, "rb").read() == open(y, "rb").read()
+
+
+def test_reset_of_one_column_leaves_the_others(tmp_path):
+    """DeviceTrace.reset(columns): three columns with 4, 2 and 3 rows, column 1 restarted, two more rows recorded in every column
+    (the test plays the device: a row goes to row count[i] of column i)."""
+    from intent_radio_sched_multi_slice_amd.history import ROW_KEYS, TraceEpisode, rows_to_hist
+    tables = _tables()
+    rows = _rows(8, 3, seed=6, done_at=[(3, 0), (2, 2)])
+    more = _rows(2, 3, seed=7, done_at=[(1, 1), (1, 2)])
+    rows["episode_number"][:], rows["scenario"][:] = [4, 6, 7], [1, 0, 2]
+    more["episode_number"][:], more["scenario"][:] = [5, 9, 8], [0, 2, 1]
+    before = {k: v.copy() for k, v in rows.items()}
+    count, lost = np.asarray([4, 2, 3], dtype=np.int32), np.asarray([0, 5, 1], dtype=np.int32)
+    tr = _trace(rows, count, [7, 3, 5], tables, lost=lost)
+    tr.reset([1])
+    assert tr.counts()["count"].tolist() == [4, 0, 3] and tr.counts()["lost"].tolist() == [0, 0, 1]
+    assert tr.episodes()[1] == []
+    for j in range(2):
+        for i in range(3):
+            for k in rows:
+                rows[k][count[i], i] = more[k][j, i]
+            count[i] += 1
+    assert tr.counts()["count"].tolist() == [6, 2, 5]
+    assert tr.episodes() == [[TraceEpisode(0, 4, 4, 1, True), TraceEpisode(4, 6, 5, 0, False)],
+                             [TraceEpisode(0, 2, 9, 2, True)],
+                             [TraceEpisode(0, 3, 7, 2, True), TraceEpisode(3, 5, 8, 1, True)]]
+    for k in rows:                                         # columns 0 and 2 kept what they had; column 1 starts again at row 0
+        assert np.array_equal(rows[k][:4, 0], before[k][:4, 0]) and np.array_equal(rows[k][:3, 2], before[k][:3, 2]), k
+        assert np.array_equal(rows[k][:2, 1], more[k][:, 1]), k
+    paths = tr.write(str(tmp_path), "mult_slice", "mapf")
+    assert [os.path.basename(p) for p in paths] == ["ep_4.npz", "ep_9.npz", "ep_7.npz", "ep_8.npz"]
+    for path, src, scen in zip(paths, ({k: before[k][:4, 0] for k in ROW_KEYS}, {k: more[k][:, 1] for k in ROW_KEYS},
+                                       {k: before[k][:3, 2] for k in ROW_KEYS}, {k: more[k][:, 2] for k in ROW_KEYS}), (1, 2, 2, 1)):
+        data, want = np.load(path, allow_pickle=True), rows_to_hist(src, tables, scen, R, Us)
+        for key in ("spectral_efficiencies", "pkt_incoming", "sched_decision", "slice_ue_assoc"):
+            assert np.array_equal(data[key], want[key]), (path, key)
+        assert [data["reward"][t]["player_0"] for t in range(len(want["reward"]))] == [r["player_0"] for r in want["reward"]]
+    tr.reset()                                             # no columns: everything, as before
+    assert tr.counts()["count"].tolist() == [0, 0, 0] and tr.counts()["lost"].tolist() == [0, 0, 0]
 
 
 # ---- a planted slip -----------------------------------------------------------------------------------------------------------------

@@ -1,17 +1,20 @@
-"""What a device trace costs, and what it replaces: B 4096, S 10 / U 100 / R 100 under MAPF + PF (workloads.make_mult_slice_workload),
+"""What a device trace costs, under rollout() and paced by the host under record(): B 4096, S 10 / U 100 / R 100 under MAPF + PF (workloads.make_mult_slice_workload),
 16 envs traced.
 
 Writes one JSON record to profiles/trace_probe.json (and prints it).  Every block in a child process of its own, the blocks
 ALTERNATED inside one job (--alternations rounds), medians over all samples of a block:
   (a) trace_ms        rollout(K) with the trace bound (BatchedRanEnv.bind_trace: one TTI per launch + one small launch per TTI)
-  (b) recorder_ms     what it replaces: the step() loop under record() (HistoryRecorder: fourteen gathers, a host-side tile index
-                      and one done.cpu() per TTI); episodes longer than the loop, so that no file is written inside the timing
+  (b) recorder_ms     the step() loop under record() (HistoryRecorder: the same trace, and one done.cpu() per TTI to write an env's
+                      file at the TTI its episode ends); episodes longer than the loop, so that no file is written inside the timing.
+                      With --baseline-repo (a checkout of the parent commit with its library built) the parent's record() as
+                      well, twice per round: `recorder_parent_ms`, `recorder_parent_vs_parent` (the spread of its two series) and
+                      `recorder_not_slower`: recorder_ms / recorder_parent_ms - 1 <= that spread
   (c) plain_this_ms   rollout(K) with nothing bound, this build
   (d) plain_parent_ms the same with the parent commit's library (--baseline-lib, loaded through RANENV_LIB), measured twice per
                       round: `parent_vs_parent` is the spread of the two parent series (ratio of their medians)
 and the ratios a/b and c/d (`untaxed_within_spread`: |c/d - 1| <= that spread).  No threshold is attached to (a).
 
-    python tools/trace_probe.py [--steps 200] [--reps 3] [--alternations 3] [--baseline-lib parent.so]
+    python tools/trace_probe.py [--steps 200] [--reps 3] [--alternations 3] [--baseline-lib parent.so] [--baseline-repo parent_checkout]
 """
 from __future__ import annotations
 
@@ -84,13 +87,16 @@ def measure(block, steps, reps):
     return info
 
 
-def _child(block, steps, reps, lib):
+def _child(block, steps, reps, lib, repo=REPO):
     env = dict(os.environ)
     if lib:
         env["RANENV_LIB"] = os.path.abspath(lib)
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", block, "--steps", str(steps), "--reps", str(reps)]
+    cmd = [sys.executable, os.path.join(os.path.abspath(repo), "tools", "trace_probe.py"), "--child", block, "--steps", str(steps),
+           "--reps", str(reps)]
     res = subprocess.run(cmd, env=env, check=True, capture_output=True, text=True, timeout=600)
-    return json.loads(res.stdout.strip().splitlines()[-1])
+    out = json.loads(res.stdout.strip().splitlines()[-1])
+    print(f"{block} ({'parent library' if lib else 'parent checkout' if repo != REPO else 'this build'}): {out['ms']}", file=sys.stderr, flush=True)
+    return out
 
 
 def main():
@@ -99,6 +105,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--alternations", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None)
+    ap.add_argument("--baseline-repo", default=None)
     ap.add_argument("--child", default=None, choices=("plain", "trace", "recorder"))
     ap.add_argument("--out", default=OUT)
     args = ap.parse_args()
@@ -107,7 +114,7 @@ def main():
         return
     # every measurement in a process of its own: the parent of them all never opens the GPU
     record = {"probe": "trace", "size": SIZE, "traced_envs": TRACED, "steps": args.steps, "reps": args.reps, "alternations": args.alternations}
-    series = {"plain_this": [], "parent_a": [], "parent_b": [], "trace": [], "recorder": []}
+    series = {"plain_this": [], "parent_a": [], "parent_b": [], "trace": [], "recorder": [], "recorder_parent_a": [], "recorder_parent_b": []}
     sched = {}
     for _ in range(args.alternations):
         if args.baseline_lib:
@@ -121,7 +128,11 @@ def main():
         r = _child("trace", args.steps, args.reps, None)
         series["trace"] += r["ms"]
         sched["trace"] = {k: r[k] for k in ("persistent", "launches", "rows", "lost", "ring_bytes")}
+        if args.baseline_repo:
+            series["recorder_parent_a"] += _child("recorder", args.steps, 1, None, args.baseline_repo)["ms"]
         series["recorder"] += _child("recorder", args.steps, 1, None)["ms"]
+        if args.baseline_repo:
+            series["recorder_parent_b"] += _child("recorder", args.steps, 1, None, args.baseline_repo)["ms"]
     med = {k: statistics.median(x) for k, x in series.items() if x}
     B = SIZE["batch"]
     record.update({"samples_ms": series, "schedule": sched, "trace_ms": med["trace"], "recorder_ms": med["recorder"],
@@ -134,6 +145,11 @@ def main():
         spread = abs(med["parent_a"] / med["parent_b"] - 1.0)
         record.update({"plain_parent_ms": parent, "parent_vs_parent": spread, "c_over_d": med["plain_this"] / parent,
                        "untaxed_within_spread": abs(med["plain_this"] / parent - 1.0) <= spread})
+    if args.baseline_repo:
+        parent = statistics.median(series["recorder_parent_a"] + series["recorder_parent_b"])
+        spread = abs(med["recorder_parent_a"] / med["recorder_parent_b"] - 1.0)
+        record.update({"recorder_parent_ms": parent, "recorder_parent_vs_parent": spread, "recorder_over_parent": med["recorder"] / parent,
+                       "recorder_not_slower": med["recorder"] / parent - 1.0 <= spread})
     line = json.dumps(record)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
