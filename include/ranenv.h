@@ -720,6 +720,12 @@ int ranenv_autoreset_part(ranenv_handle h, int32_t part, const uint8_t *dev_done
  *                                                 (This one selects whose flags count -- with 1 the caller must not modify dev_done.)
  *   "last_rollout_persistent" / "last_rollout_launches" (read only)   what the last ranenv_rollout call ran: 1 = persistent work-queue
  *                                                 launches (else launches of <= 10 TTIs per partition); how many step-kernel launches it enqueued
+ *   "step_launches_<build>" / "step_launches_<build>_many" (read only)   which build of the step kernel the handle's step launches ran, <build> one of
+ *                                                 lean, small, gather, tiny1, mixed, packed, persist, persist_tiny: launches of the step kernel in step mode
+ *                                                 that succeeded since ranenv_create (resets and dense launches are not counted), and the share of them
+ *                                                 that took their envs through several TTIs.  They count ENQUEUES: under stream capture a launch counts once,
+ *                                                 when it is captured, and not when the graph is replayed.  ranenv_set_option refuses them as unknown.
+ *                                                 A launch whose build has no kernel fails its call with RANENV_E_HIP, the build named in the message
  *   "persist_stat_keep" / "_push" / "_pop" / "_fresh" / "_idle_polls" (read only)   queue statistics of the persistent launches so far, summed over
  *                                                 classes and XCDs: chunk ends at which the workgroup kept its env, envs put down, envs taken
  *                                                 from a ready queue, envs taken fresh, spins on a slot whose pusher had not written yet

@@ -1290,6 +1290,17 @@ class BatchedRanEnv:
         self._check(self._lib.ranenv_get_option(self._h, key.encode(), C.byref(v)), f"ranenv_get_option({key})")
         return int(v.value)
 
+    STEP_BUILDS = ("lean", "small", "gather", "tiny1", "mixed", "packed", "persist", "persist_tiny")
+
+    def step_launches(self) -> Dict[str, int]:
+        """Which build of the step kernel this handle's step launches ran: per build in STEP_BUILDS the launches enqueued since
+        create under "<build>", and those of several TTIs under "<build>_many" (the read-only options "step_launches_*")."""
+        out = {}
+        for b in self.STEP_BUILDS:
+            out[b] = self.get_option("step_launches_" + b)
+            out[b + "_many"] = self.get_option("step_launches_" + b + "_many")
+        return out
+
     def launch_info(self):
         g, b, l = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._lib.ranenv_launch_info(self._h, C.byref(g), C.byref(b), C.byref(l)), "ranenv_launch_info")

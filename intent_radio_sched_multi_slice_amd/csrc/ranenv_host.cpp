@@ -18,6 +18,7 @@ using namespace ranenv_dev;
 
 namespace {
 thread_local std::string g_last_error;
+constexpr int N_STEP_BUILDS = SB_PERSIST_TINY + 1;          // (StepBuild, ranenv_internal.h)
 
 }  // namespace
 
@@ -81,6 +82,10 @@ struct ranenv {
     int *d_perr_dev = nullptr;     // ... its address as the device sees it
     int perr_seen = 0;             // ... what of it has been reported
     int last_rollout_persistent = 0, last_rollout_launches = 0;   // what the last ranenv_rollout call ran (read-only options)
+    // MODE_STEP launches of the step kernel that succeeded since ranenv_create, per StepBuild; [1]: those of several TTIs (read-only options
+    // "step_launches_<build>" / "..._many").  Enqueues: a replayed graph counts once, at its capture.
+    uint64_t step_launches[N_STEP_BUILDS][2] = {};
+    std::string launch_note;       // a failed step launch: which build had no kernel (appended to the call's error message by fail())
     int p_wave_slots[2] = {0, 0};  // wave slots per CU of the persistent kernel (streaming, gather build), from the occupancy query
     // batch partitions (ranenv_set_partitions): envs [part_lo[k], part_lo[k+1]) are stepped by their own launch on
     // their own stream, so that one partition's ramp and tail run under the other partitions' steady state
@@ -144,8 +149,10 @@ int fail(ranenv_handle h, int code, const char *fmt, ...)
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
-    if (h) h->err = buf;
-    g_last_error = buf;
+    std::string msg = buf;
+    if (h && !h->launch_note.empty()) { msg += " [" + h->launch_note + "]"; h->launch_note.clear(); }
+    if (h) h->err = msg;
+    g_last_error = msg;
     return code;
 }
 
@@ -276,6 +283,26 @@ hipError_t prof_events(ranenv_handle h, int n, int n_tti, hipEvent_t *ev0, hipEv
     return hipSuccess;
 }
 
+// Names of the builds, in StepBuild's order (the read-only options "step_launches_<build>", the message of a failed launch)
+const char *const step_build_names[N_STEP_BUILDS] = {"lean", "small", "gather", "tiny1", "mixed", "packed", "persist", "persist_tiny"};
+
+// launch_step with its result kept: a success of a MODE_STEP launch is counted for its build, a failure (no kernel for that build, mode
+// and flag combination: a slip of the dispatch) leaves the build's name for the message of the call that fails
+hipError_t launch_step_counted(ranenv_handle h, const StepLaunch &l, dim3 grid, dim3 block, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const KP &kp)
+{
+    const hipError_t e = launch_step(l, grid, block, s, ev0, ev1, kp);
+    const bool known = l.build >= 0 && l.build < N_STEP_BUILDS;
+    if (e == hipSuccess) {
+        if (known && (l.mode & 3) == MODE_STEP) h->step_launches[l.build][l.many ? 1 : 0]++;
+    } else {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "step kernel build '%s' (row width %d, mode %d, %s, %s): %s", known ? step_build_names[l.build] : "?", l.np, l.mode,
+                 l.many ? "several TTIs" : "one TTI", l.gather ? "gather" : "stream", hipGetErrorString(e));
+        h->launch_note = buf;
+    }
+    return e;
+}
+
 // The build of the step kernel for one launch of envs [e0, e0 + n), with its grid and block; `kp` gets what every kernel of the
 // launch reads from it (the compact flag, the SE gather sidecars).  SB_MIXED: the class lists are the caller's to sort and bind.
 struct StepPlan { StepLaunch l; dim3 grid, block; };
@@ -370,7 +397,8 @@ hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t strea
     hipEvent_t ev0, ev1;
     const hipError_t pe = prof_events(h, n, MODE == MODE_STEP ? kp.n_tti : 1, &ev0, &ev1);
     if (pe != hipSuccess) return pe;
-    (void)launch_step(p.l, p.grid, p.block, stream, ev0, ev1, ks);
+    const hipError_t le = launch_step_counted(h, p.l, p.grid, p.block, stream, ev0, ev1, ks);
+    if (le != hipSuccess) return le;
     if (kp.head_obs || kp.head_reward)
         launch_head(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp, (h->kp.acc && h->kp.head_reward) ? h->d_head_acc : nullptr,
                     MODE == MODE_RESET ? 1 : 0);
@@ -666,7 +694,8 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
         e = prof_events(h, n, n_tti, &ev0, &ev1);
         if (e != hipSuccess) return fail(h, RANENV_E_HIP, "hipEventCreate(&pe): %s", hipGetErrorString(e));
         const dim3 grid((unsigned)g), block((unsigned)((c + 1) * WAVE));
-        (void)launch_step(StepLaunch{h->np, (!gather && tiny) ? SB_PERSIST_TINY : SB_PERSIST, MODE_STEP, true, gather}, grid, block, s, ev0, ev1, kc);
+        e = launch_step_counted(h, StepLaunch{h->np, (!gather && tiny) ? SB_PERSIST_TINY : SB_PERSIST, MODE_STEP, true, gather}, grid, block, s, ev0, ev1, kc);
+        if (e != hipSuccess) return fail(h, RANENV_E_HIP, "persistent rollout launch: %s", hipGetErrorString(e));
         if (k > 0) HIP_TRY(h, hipEventRecord(h->part_done[(size_t)k], s));
         k++;
     }
@@ -927,6 +956,15 @@ int ranenv_get_option(ranenv_handle h, const char *key, int64_t *value)
     }
     else if (k == "last_rollout_persistent") *value = h->last_rollout_persistent;      // what the last ranenv_rollout call ran:
     else if (k == "last_rollout_launches") *value = h->last_rollout_launches;          // 1 = persistent work-queue launches; step-kernel launches enqueued
+    else if (k.rfind("step_launches_", 0) == 0) {      // MODE_STEP launches per build since ranenv_create; "..._many": those of several TTIs
+        std::string b = k.substr(14);
+        const bool many_only = b.size() > 5 && b.compare(b.size() - 5, 5, "_many") == 0;
+        if (many_only) b.resize(b.size() - 5);
+        int which = -1;
+        for (int i = 0; i < N_STEP_BUILDS; i++) if (b == step_build_names[i]) which = i;
+        if (which < 0) return fail(h, RANENV_E_INVALID, "unknown option '%s'", key);
+        *value = (int64_t)(h->step_launches[which][1] + (many_only ? 0 : h->step_launches[which][0]));
+    }
     else if (const int i = fuse_first_index(k); i >= 0) *value = (size_t)i < h->fuse_first.size() ? h->fuse_first[(size_t)i] : 0;
     else return fail(h, RANENV_E_INVALID, "unknown option '%s'", key);
     return RANENV_OK;

@@ -202,6 +202,55 @@ def draw_fuzz_case(k):
     return dict(S=S, U=U, R=R, G=G, Us=Us, D=D, load=load, low_se=low_se, how=how, policy=policy, intra=intra, steps=steps)
 
 
+def even_cut(B: int, parts: int):
+    """ranenv_set_partitions' cut of an even batch: ranges of whole pairs of envs, the first ones a pair longer."""
+    base, rem = divmod(B // 2, parts)
+    lo = [0]
+    for k in range(parts):
+        lo.append(lo[-1] + 2 * (base + (1 if k < rem else 0)))
+    return lo
+
+
+def draw_fuzz_case_for(build: str, k: int):
+    """Case ``k`` of tests/test_gpu_fuzz.py's "packed*" and "mixed*" columns: draw_fuzz_case's fields on a seed stream of their own,
+    with the shape drawn inside what the build needs (csrc/ranenv_host.cpp: step_plan) -- none of draw_fuzz_case's first 24 shapes is
+    packable and few can run mixed blocks.  "packed*": two envs per wave -- S and Us in 1..8 (row width 8), U <= 32 (one wave per
+    env), an even batch ``B``, and for device_rollout a number of partitions ``parts`` whose ranges are all even.  "mixed*": 64 < U
+    <= 128 (two waves per env) and whole-batch launches, so device_rollout runs unpartitioned.  The rest as draw_fuzz_case."""
+    kind = build.split("-")[0]
+    assert kind in ("packed", "mixed"), build
+    rng = np.random.default_rng([9000 + k, 1 if kind == "packed" else 2])
+    if kind == "packed":
+        S = int(rng.integers(1, 9))
+        Us = int(rng.integers(1, 9))
+        U = int(rng.integers(max(2, Us), 33))
+        B = int(rng.choice([6, 8, 10]))
+        parts = int(rng.choice([p for p in (2, 3) if B // 2 >= p]))
+    else:
+        S = int(rng.integers(1, 17))
+        Us = int(rng.integers(1, 17))
+        U = int(rng.integers(65, 129))
+        B, parts = 7, 1
+    G = int(rng.choice([1, 1, 2, 3, 5, 8]))
+    R = int(rng.choice([rng.integers(G, 8 * G + 1), rng.integers(8, 129), rng.integers(129, 257), rng.integers(257, 489)]))
+    R = max(R, G)
+    D = int(rng.choice([10, 10, 1, 2, 7]))
+    load = float(rng.choice([0.2, 1.0, 1.0, 6.0]))
+    low_se = int(rng.choice([0, 0, 3]))
+    how = ["external", "device_steps", "device_rollout"][k % 3]
+    policy, intra = [(2, 1), (1, 0), (2, 2), (2, 0)][int(rng.integers(0, 4))]
+    steps = int(rng.choice([12, 12, 30, 48]))
+    return dict(S=S, U=U, R=R, G=G, Us=Us, D=D, load=load, low_se=low_se, how=how, policy=policy, intra=intra, steps=steps, B=B, parts=parts)
+
+
+def fuzz_scenarios(c: dict, seed: int):
+    """The scenario tables tests/test_gpu_fuzz.py generates for a drawn case (the generator needs room for its smallest scenario)."""
+    from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
+    S, U, Us = c["S"], c["U"], c["Us"]
+    return generate_scaled_scenarios(4, seed=seed, n_slices=S, n_ues=U, max_ues_slice=Us, min_slices=max(1, min(S, U // max(1, Us)) // 2),
+                                     min_ues=max(1, Us // 3))
+
+
 def replay_fuzz_case(k: int, per_element: bool = False):
     """The oracle half of tests/test_gpu_fuzz.py's case ``k`` (same draws in the same order), in replay()'s form: the
     template-only inputs the directed ones are measured against."""

@@ -186,18 +186,19 @@ def test_assert_matches_oracle_passes_on_the_oracles_own_outputs_and_fails_on_ea
 
 
 # ---- select_build --------------------------------------------------------------------------------------------------------------------
-KNOBS = ("RANENV_SMALL_BATCH", "RANENV_PACK", "RANENV_MIX", "RANENV_SE_MODE")
+KNOBS = ("RANENV_SMALL_BATCH", "RANENV_PACK", "RANENV_MIX", "RANENV_SE_MODE", "RANENV_TINY_STEP")
 # what the build fixture of test_gpu_parity.py, _select_build of test_gpu_intent_branches.py and test_gpu_fuzz.py set for the name
 BUILD_KNOBS = {
-    "lean": ("0", "0", "0", None),
-    "small": ("1", "0", "0", None),
-    "gather": ("1", "0", "0", "gather"),
-    "packed": ("0", "1", "0", None),
-    "packed-gather": ("0", "1", "0", "gather"),
-    "mixed": ("0", "0", "2", None),
-    "mixed-gather": ("0", "0", "2", "gather"),
-    "per-element": ("1", "0", "0", None),
-    "per-element-gather": ("1", "0", "0", "gather"),
+    "lean": ("0", "0", "0", None, "0"),
+    "small": ("1", "0", "0", None, "0"),
+    "tiny1": ("1", "0", "0", None, "1"),
+    "gather": ("1", "0", "0", "gather", None),
+    "packed": ("0", "1", "0", None, None),
+    "packed-gather": ("0", "1", "0", "gather", None),
+    "mixed": ("0", "0", "2", None, None),
+    "mixed-gather": ("0", "0", "2", "gather", None),
+    "per-element": ("1", "0", "0", None, None),
+    "per-element-gather": ("1", "0", "0", "gather", None),
 }
 
 
@@ -212,3 +213,125 @@ def test_select_build_sets_the_knobs_each_module_set(build, monkeypatch):
 def test_select_build_refuses_an_unknown_name(monkeypatch):
     with pytest.raises(AssertionError):
         gc.select_build(monkeypatch, "packed_gather")
+
+
+def test_select_build_leaves_the_tiny_step_knob_alone_for_the_other_names(monkeypatch):
+    for build in BUILD_KNOBS:
+        if build not in ("lean", "small", "tiny1"):
+            monkeypatch.setenv("RANENV_TINY_STEP", "7")
+            gc.select_build(monkeypatch, build)
+            assert os.environ["RANENV_TINY_STEP"] == "7", build
+
+
+# ---- launches_since / assert_build_ran -----------------------------------------------------------------------------------------------
+class _CountingEnv:
+    """step_launches() of a handle: all sixteen keys, cumulative."""
+
+    def __init__(self):
+        self.n = {k: 0 for b in gc.STEP_BUILDS for k in (b, b + "_many")}
+
+    def launch(self, build, times=1, many=False):
+        self.n[build] += times
+        if many:
+            self.n[build + "_many"] += times
+
+    def step_launches(self):
+        return dict(self.n)
+
+
+def test_launches_since_is_a_snapshot_or_a_delta():
+    env = _CountingEnv()
+    env.launch("tiny1", 3)
+    before = gc.launches_since(env)
+    assert len(before) == 16 and before["tiny1"] == 3 and before["lean"] == 0
+    env.launch("lean", 2, many=True)
+    assert before["lean"] == 0                                   # (a copy: the snapshot does not move)
+    d = gc.launches_since(env, before)
+    assert d["lean"] == 2 and d["lean_many"] == 2 and d["tiny1"] == 0 and sum(d.values()) == 4
+
+
+def test_assert_build_ran_passes_on_the_named_build_and_fails_on_every_other_outcome():
+    env = _CountingEnv()
+    env.launch("tiny1", 5)                                       # (before the snapshot: never counted)
+    before = gc.launches_since(env)
+    with pytest.raises(AssertionError, match="did not run"):     # nothing launched
+        gc.assert_build_ran(env, before, "lean")
+    env.launch("lean", 4)
+    # pass: by name, with the count, with many=False
+    gc.assert_build_ran(env, before, "lean")
+    d = gc.assert_build_ran(env, before, "lean", many=False, count=4)
+    assert d["lean"] == 4
+    # wrong build: the message prints the whole delta
+    with pytest.raises(AssertionError, match=r"build lean ran.*'lean': 4"):
+        gc.assert_build_ran(env, before, "small")
+    # wrong many, either way
+    with pytest.raises(AssertionError, match="several TTIs"):
+        gc.assert_build_ran(env, before, "lean", many=True)
+    env.launch("lean", 1, many=True)
+    with pytest.raises(AssertionError, match="several TTIs"):    # 1 of 5: neither all nor none
+        gc.assert_build_ran(env, before, "lean", many=True)
+    with pytest.raises(AssertionError, match="several TTIs"):
+        gc.assert_build_ran(env, before, "lean", many=False)
+    gc.assert_build_ran(env, before, "lean", count=5)
+    # wrong count
+    with pytest.raises(AssertionError, match="launch count"):
+        gc.assert_build_ran(env, before, "lean", count=4)
+    # two builds: one name fails, the tuple passes and wants both
+    env.launch("persist", 2, many=True)
+    with pytest.raises(AssertionError, match="build persist ran"):
+        gc.assert_build_ran(env, before, "lean")
+    gc.assert_build_ran(env, before, ("lean", "persist"), count=7)
+    with pytest.raises(AssertionError, match="build gather did not run"):
+        gc.assert_build_ran(env, before, ("lean", "persist", "gather"))
+    with pytest.raises(AssertionError, match="launch count"):
+        gc.assert_build_ran(env, before, ("lean", "persist"), count=5)
+    # builds that may run beside the named one: let through, counted, and still not enough on their own
+    gc.assert_build_ran(env, before, "lean", also=("persist", "tiny1"), count=7)
+    with pytest.raises(AssertionError, match="build small did not run"):
+        gc.assert_build_ran(env, before, "small", also=("lean", "persist"))
+    # a fresh snapshot starts from here
+    after = gc.launches_since(env)
+    env.launch("persist", 1, many=True)
+    gc.assert_build_ran(env, after, "persist", many=True, count=1)
+    with pytest.raises(AssertionError):
+        gc.assert_build_ran(env, after, "not-a-build")
+
+
+# ---- build_for -----------------------------------------------------------------------------------------------------------------------
+class _ShapeEnv:
+    def __init__(self, S, U, Us, B, **options):
+        self.S, self.U, self.Us, self.B = S, U, Us, B
+        self.options = dict(dict(compact=1, tiny_step=1, small_batch=0), **options)
+
+    def get_option(self, key):
+        return self.options[key]
+
+
+def test_build_for_names_the_build_where_the_shape_fits_and_the_fallback_where_not():
+    ref, wide, grid = _ShapeEnv(5, 25, 5, 8), _ShapeEnv(10, 100, 10, 7), _ShapeEnv(16, 256, 16, 6)
+    assert gc.step_shape(ref) == (64, 8) and gc.step_shape(wide) == (128, 10) and gc.step_shape(grid) == (256, 16)
+    assert gc.step_shape(_ShapeEnv(9, 25, 5, 8)) == (128, 10)              # (nine slices: two waves of slice-table words)
+    # packed waves: row width 8, at most 32 UEs, one wave, an even launch, no env mask
+    assert gc.build_for(ref, "packed") == gc.build_for(ref, "packed-gather") == gc.build_for(ref, "packed", many=True, n=4, partitions=2) == "packed"
+    assert gc.build_for(ref, "packed", explicit_traffic=True, explicit_se=True) == "packed"
+    assert gc.build_for(ref, "packed", n=3, partitions=2) == gc.build_for(ref, "packed", masked=True) == gc.build_for(wide, "packed") == "tiny1"
+    assert gc.build_for(_ShapeEnv(5, 25, 5, 7), "packed") == gc.build_for(_ShapeEnv(5, 33, 5, 8), "packed") == "tiny1"
+    assert gc.build_for(ref, "packed-gather", masked=True) == "gather" and gc.build_for(wide, "packed", many=True) == "lean"
+    # mixed blocks: two waves, the whole batch in one launch, a compact step
+    assert gc.build_for(wide, "mixed") == gc.build_for(wide, "mixed-gather", many=True) == "mixed"
+    for kw in (dict(n=3, partitions=2), dict(partitions=3), dict(masked=True), dict(explicit_traffic=True)):
+        assert gc.build_for(wide, "mixed", **kw) == "tiny1" and gc.build_for(wide, "mixed-gather", **kw) == "gather", kw
+    assert gc.build_for(_ShapeEnv(10, 100, 10, 7, compact=0), "mixed") == gc.build_for(ref, "mixed") == gc.build_for(grid, "mixed") == "tiny1"
+    assert gc.build_for(wide, "mixed-gather", explicit_traffic=True, explicit_se=True) == "tiny1"
+    # the streaming names: what the knobs on the handle select, and the name has to agree with them
+    assert gc.build_for(_ShapeEnv(5, 25, 5, 8, tiny_step=0), "lean") == gc.build_for(_ShapeEnv(5, 25, 5, 8, tiny_step=0), "lean", many=True) == "lean"
+    assert gc.build_for(_ShapeEnv(5, 25, 5, 8, tiny_step=0, small_batch=1), "small") == "small"
+    assert gc.build_for(_ShapeEnv(5, 25, 5, 8, small_batch=1), "tiny1") == "tiny1" and gc.build_for(_ShapeEnv(5, 25, 5, 8, small_batch=1), "tiny1", many=True) == "small"
+    for env, name in ((ref, "lean"), (_ShapeEnv(5, 25, 5, 8, tiny_step=0, small_batch=1), "lean"), (_ShapeEnv(5, 25, 5, 8, tiny_step=0), "small"),
+                      (_ShapeEnv(5, 25, 5, 8, tiny_step=0), "tiny1")):
+        with pytest.raises(AssertionError, match="did not reach the handle"):
+            gc.build_for(env, name)
+    # the per-element rounding has lean and gather builds only
+    assert gc.build_for(ref, "per-element") == gc.build_for(wide, "mixed", per_element=True) == gc.build_for(ref, "packed", per_element=True) == "lean"
+    assert gc.build_for(ref, "per-element-gather", many=True) == "gather" and gc.build_for(ref, "per-element-gather", explicit_se=True) == "lean"
+    assert gc.build_for(ref, "gather") == "gather" and gc.build_for(ref, "gather", explicit_se=True) == "tiny1"

@@ -7,7 +7,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests.common import OBS_TOL, PKT_COUNTS, REW_TOL
-from tests.gpu_common import LOOSE_SE_MEAN, assert_matches_oracle, assert_same_state, comparable_views, need_gpu
+from tests.gpu_common import LOOSE_SE_MEAN, assert_build_ran, assert_matches_oracle, assert_same_state, comparable_views, launches_since, need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -363,12 +363,15 @@ def test_config1_bench_schedule_vs_oracle(se_mode):
     assert len(sample) >= 32
 
     launches = []
+    before = launches_since(env)
 
     def one_persistent_launch(k):
         assert env.get_option("last_rollout_persistent") == 1, "configs[1] no longer runs the persistent launch"
         launches.append(env.get_option("last_rollout_launches"))
         assert launches[-1] == 1, launches              # one class, one launch for all k TTIs
     _mirror_rollouts_with_the_oracle(wl, sample, ROLLOUT_CALLS, se_mode, "configs[1]", after_call=one_persistent_launch)
+    # ... and the launch counters name the kernel: the whole-row persistent build when streaming, the gather persistent build else
+    assert_build_ran(env, before, "persist_tiny" if se_mode == "stream" else "persist", many=True, count=sum(launches))
     # ... and by the dispatch's own bookkeeping: one launch covered all the TTIs of a call
     env.profile_begin(); env.rollout(13); kms = env.profile_end()
     assert kms["n_launches"] == 1 and kms["n_ttis"] == 13 and kms["n_env_ttis"] == 13 * 1024, kms
@@ -397,8 +400,19 @@ def test_config4_bench_schedule_vs_oracle(se_mode):
         sample += [int(idx[0]), int(idx[-1])]
     sample = sorted(set(sample))
     assert len(sample) >= 32 and set(wl.scenario[sample].tolist()) == set(range(10))
-    _mirror_rollouts_with_the_oracle(wl, sample, ROLLOUT_CALLS, se_mode, "configs[4]")
+    before, calls = launches_since(env), []
+    _mirror_rollouts_with_the_oracle(wl, sample, ROLLOUT_CALLS, se_mode, "configs[4]",
+                                     after_call=lambda k: calls.append((env.get_option("last_rollout_persistent"), env.get_option("last_rollout_launches"))))
     assert env.get_option("last_rollout_persistent") == (1 if se_mode == "gather" else 0)
+    # the launch counters: streaming, the partitions' launches run the lean build (the small-batch one where the suite's knob forces
+    # it); in gather mode every call of the auto rule is persistent launches of the gather build
+    if se_mode == "stream":
+        assert [p for p, n in calls] == [0] * len(ROLLOUT_CALLS)
+        d = assert_build_ran(env, before, "small" if env.get_option("small_batch") == 1 else "lean", count=sum(n for p, n in calls))
+        assert 0 < d["lean_many"] + d["small_many"] < sum(n for p, n in calls)          # launches of several TTIs, and of one
+    else:
+        chunked = any(p == 0 for p, n in calls)
+        assert_build_ran(env, before, ("persist", "gather") if chunked else "persist", count=sum(n for p, n in calls))
     env.close()
 
 
@@ -427,8 +441,12 @@ def test_native_size_bench_schedule_vs_oracle(se_mode):
     _bench_options(env)
     sample, lo = _native_sample(16384, 3)
     assert lo == [0, 5462, 10924, 16384] and len(sample) >= 32
-    _mirror_rollouts_with_the_oracle(wl, sample, ROLLOUT_CALLS, se_mode, "native")
+    before, launches = launches_since(env), []
+    _mirror_rollouts_with_the_oracle(wl, sample, ROLLOUT_CALLS, se_mode, "native", after_call=lambda k: launches.append(env.get_option("last_rollout_launches")))
     assert env.get_option("last_rollout_persistent") == 0 and env.get_option("pack") == 1
+    # not the knob but the launches: every one of them ran packed waves, those of several TTIs included
+    d = assert_build_ran(env, before, "packed", count=sum(launches))
+    assert d["packed_many"] >= len([k for k in ROLLOUT_CALLS if k > 1])
     env.close()
 
 

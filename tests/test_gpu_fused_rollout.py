@@ -9,7 +9,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.gpu_common import LOOSE_SE_MEAN, assert_same_state, bench_like, need_gpu, short_episode_setup
+from tests.gpu_common import LOOSE_SE_MEAN, assert_build_ran, assert_same_state, bench_like, launches_since, need_gpu, short_episode_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -235,6 +235,7 @@ def test_two_envs_per_wave_equal_one_env_per_wave_at_the_reference_size(se_mode,
         if B > 2:
             env.set_partitions(3)
         env.reset()
+        before = launches_since(env)
         snaps = []
         env.rollout(9); snaps.append(_snap(env))
         env.step(); snaps.append(_snap(env))
@@ -250,6 +251,13 @@ def test_two_envs_per_wave_equal_one_env_per_wave_at_the_reference_size(se_mode,
         env.rollout(12); snaps.append(_snap(env))
         m = env.episode_metrics()
         snaps.append({"done_eps": m["episodes_done"].clone(), "log": m["episode_log"].clone(), "run": m["running"].clone()})
+        # the launch counters: with the option on every step launch ran packed waves (of one TTI and of several); off, none did
+        d = launches_since(env, before)
+        if pack:
+            assert_build_ran(env, before, "packed")
+            assert 0 < d["packed_many"] < d["packed"], d
+        else:
+            assert d["packed"] == 0 and sum(d[b] for b in ("lean", "small", "gather", "tiny1")) > 0, d
         outs.append(snaps)
         env.close()
     for i, (x, y) in enumerate(zip(*outs)):
@@ -281,8 +289,10 @@ def test_mixed_blocks_equal_one_workgroup_per_env(se_mode, B):
         wl = make_mult_slice_workload(B, dev, n_scenarios=32, n_traces=16, trace_len=24, max_steps=1000)
         env = wl.env
         env.set_option("mix", mix); env.set_option("persist", 0)
+        env.set_option("compact", 1)             # (mixed blocks are compact steps: whatever knob the suite runs under)
         env.set_se_mode(se_mode)
         env.reset()
+        before = launches_since(env)
         snaps = []
         for _ in range(4):
             env.step()
@@ -302,6 +312,13 @@ def test_mixed_blocks_equal_one_workgroup_per_env(se_mode, B):
         else:
             env.set_policy(2, 1); env.step()
         snaps.append(_snap(env))
+        # the launch counters: forced, every step launch ran mixed blocks (of one TTI and of several); switched off, none did
+        d = launches_since(env, before)
+        if mix:
+            assert_build_ran(env, before, "mixed")
+            assert 0 < d["mixed_many"] < d["mixed"], d
+        else:
+            assert d["mixed"] == 0 and sum(d[b] for b in ("lean", "small", "gather", "tiny1")) > 0, d
         outs.append(snaps)
         env.close()
     for i, (x, y) in enumerate(zip(*outs)):

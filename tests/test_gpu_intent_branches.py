@@ -24,81 +24,20 @@ torch = pytest.importorskip("torch")
 from tests import directed_intents as di
 from tests import intent_census as ic
 from tests.common import OBS_TOL, PKT_COUNTS, REW_TOL, tti_metrics
-from tests.gpu_common import device_env_of_run, need_gpu, select_build
+from tests.gpu_common import ULP_BOUND, assert_build_ran, build_for, device_env_of_run, launches_since, need_gpu, select_build
+from tests.gpu_common import SEEN as _SEEN, check_all as _check_all, check_env as _check_env, check_obs as _check_obs
 
 pytestmark = pytest.mark.gpu
 
-ULP_BOUND = 1
-_SEEN = {"ulp": 0, "entries": 0, "pairs": 0, "abs_small": 0.0}
 
 BUILDS = {      # the switches of tests/test_gpu_fuzz.py; the cases at which each build's own path applies
     "lean": tuple(c["name"] for c in di.CASES),
     "small": ("ref-default", "ref-all-scalars", "packable", "partial-wave", "one-slice"),
+    "tiny1": ("ref-default", "ref-all-scalars", "packable", "partial-wave", "one-slice"),      # the whole-row build: what "small" ran before it named its own
     "gather": ("ref-all-scalars", "ref-overfulfill-0.5", "partial-wave", "grid-16x16", "no-remainder"),
     "packed": ("packable", "one-slice", "no-remainder"),               # two envs per wave: U <= 32 and S, Us <= 8
     "mixed": ("partial-wave",),                                        # mixed blocks: 64 < U <= 128
 }
-
-
-def _ordered(x32):
-    """float32 -> int64 that counts representable numbers: neighbours differ by 1, -0.0 and +0.0 coincide."""
-    i = x32.view(np.int32).astype(np.int64)
-    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-
-
-def _where(name, idx, run):
-    """(slice position or slice, column) of a flat observation index: columns 0-2 are the metrics' slice drifts."""
-    c = run["case"]
-    w = 10 if name == "obs_inter" else 2 * c["Us"] + 9
-    return {"row": int(idx) // w, "column": int(idx) % w}
-
-
-def _check_obs(name, got, exp64, tag, run):
-    got = np.asarray(got, dtype=np.float32).ravel()
-    exp64 = np.asarray(exp64, dtype=np.float64).ravel()
-    err = np.abs(got.astype(np.float64) - exp64)
-    if not (err <= OBS_TOL).all():          # (NaN fails too)
-        k = int(np.argmax(np.where(np.isnan(err), np.inf, err)))
-        raise AssertionError(f"{name} differs by {err[k]:.3e} at {tag} {_where(name, k, run)}: device {got[k]!r}, oracle {exp64[k]!r}")
-    exp32 = exp64.astype(np.float32)
-    ulp = np.abs(_ordered(got) - _ordered(exp32))
-    big = np.abs(exp64) >= 2.0 ** -6
-    _SEEN["entries"] += got.size
-    if big.any():
-        _SEEN["ulp"] = max(_SEEN["ulp"], int(ulp[big].max()))
-    if (~big).any():
-        _SEEN["abs_small"] = max(_SEEN["abs_small"], float(np.abs(got.astype(np.float64) - exp32.astype(np.float64))[~big].max()))
-    bound = np.where(big, 0.0, 1e-9) + np.spacing(np.maximum(np.abs(exp32), np.float32(2.0 ** -126))).astype(np.float64)
-    bad = np.where(big, ulp > ULP_BOUND, np.abs(got.astype(np.float64) - exp32.astype(np.float64)) > bound)
-    if bad.any():
-        k = int(np.argmax(bad))
-        raise AssertionError(f"{name} is {ulp[k]} float32 ulps from the rounded oracle value at {tag} {_where(name, k, run)}: "
-                             f"device {got[k]!r}, oracle {exp64[k]!r}")
-
-
-def _check_env(run, t, b, g, obs_inter, obs_intra, rew, expected, what=""):
-    """One (env, TTI) pair: allocation and packet counts bit-exact, observations and rewards within the bars."""
-    count, raw, oo = expected[0], expected[1], expected[2]
-    tag = (run["case"]["name"], what, "TTI", t, "env", b, "scenario", int(run["scen"][b]))
-    if g is not None:
-        assert np.array_equal(g["rb_count"][b], count), (tag, "rb_count")
-        for name in PKT_COUNTS:
-            assert np.array_equal(g[name][b].astype(np.float64), raw[name]), (tag, name)
-    _check_obs("obs_inter", obs_inter[b], oo["obs_inter"], tag, run)
-    _check_obs("obs_intra", obs_intra[b], oo["obs_intra"], tag, run)
-    err = np.abs(rew[b] - oo["reward"])
-    if not (err <= REW_TOL).all():
-        k = int(np.argmax(np.where(np.isnan(err), np.inf, err)))
-        raise AssertionError(f"reward[{k}] ({'inter-slice' if k == 0 else f'slice {k - 1}'}) differs by {err[k]:.3e} at {tag}: "
-                             f"device {rew[b][k]!r}, oracle {oo['reward'][k]!r}")
-    _SEEN["pairs"] += 1
-
-
-def _check_all(run, t, env, obs, rew, what=""):
-    g = {n: x.cpu().numpy() for n, x in env.views().items()}
-    oi, oa, rw = obs["obs_inter"].cpu().numpy(), obs["obs_intra"].cpu().numpy(), rew.cpu().numpy()
-    for b, expected in enumerate(run["steps"][t][2]):
-        _check_env(run, t, b, g, oi, oa, rw, expected, what)
 
 
 def _step(run, env, t):
@@ -120,16 +59,24 @@ def _run_of(name, **override):
 # ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("build,name", [(b, n) for b, names in BUILDS.items() for n in names])
 def test_directed_case_vs_oracle(build, name, monkeypatch):
-    """step() per TTI: the caller's scores and intra choices, or MARR / MAPF with each intra scheduler on the device."""
+    """step() per TTI: the caller's scores and intra choices, or MARR / MAPF with each intra scheduler on the device.  Every launch
+    ran the build the case is listed under (the library's launch counters); ("packed", "no-remainder") runs with an even batch of 8,
+    since packed waves take an even number of envs."""
     need_gpu()
     select_build(monkeypatch, build)
-    run = _run_of(name)
+    run = _run_of(name, B=8) if (build, name) == ("packed", "no-remainder") else _run_of(name)
     env = device_env_of_run(run)
+    if build == "mixed":
+        env.set_option("compact", 1)             # (mixed blocks are compact steps: whatever knob the suite runs under)
     env.reset()
+    before = launches_since(env)
     for t in range(run["case"]["steps"]):
         obs, rew, done = _step(run, env, t)
         _check_all(run, t, env, obs, rew, build)
     assert int(done.sum()) == run["case"]["B"]
+    want = build_for(env, build, per_element=run["case"]["per_element"])
+    assert want == build, (build, name, want)     # (every listed case fits its build; the per-element case is listed under "lean" only)
+    assert_build_ran(env, before, want, many=False, count=run["case"]["steps"])
     env.close()
 
 

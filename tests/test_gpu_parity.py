@@ -10,13 +10,18 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests.common import OBS_TOL, PKT_COUNTS, TRACE_CASES, load_golden, oracle_envs, poisson_traffic_rows, rb_major, tables_from
-from tests.gpu_common import assert_matches_oracle, need_gpu, select_build
+from tests.gpu_common import assert_build_ran, assert_matches_oracle, build_for, launches_since, need_gpu, select_build
 from tests.synth import se_tile
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=["lean", "small", "gather", "packed", "packed-gather", "mixed", "mixed-gather"])
+class _Build(str):
+    """What the tests branch on ("gather" for every "*-gather" name), with the full select_build name as ``.name``."""
+    name = None
+
+
+@pytest.fixture(params=["lean", "small", "tiny1", "gather", "packed", "packed-gather", "mixed", "mixed-gather"])
 def build(request, monkeypatch):
     """The streaming step kernel has two builds (96 VGPRs / 8 SE loads in flight for batches that fill the CUs, 128 VGPRs /
     32 in flight for small ones); ranenv_create picks by batch size.  Test batches are small, so the choice is forced here
@@ -27,9 +32,14 @@ def build(request, monkeypatch):
     that the one-env-per-wave kernels keep their coverage at the reference's own size.
     "mixed" / "mixed-gather": whole-batch steps of two-wave workgroups (U > 64) as mixed blocks -- one block per env of more than 64
     slice members, one per two envs of at most 64 (ranenv_core_kernel_mixed) -- forced for these small batches (RANENV_MIX=2); the
-    other builds run with RANENV_MIX=0."""
+    other builds run with RANENV_MIX=0.
+    "lean" / "small" also switch the whole-row build off (RANENV_TINY_STEP=0), which a one-TTI step of a batch this small would run
+    instead; "tiny1" is that build.  Every test ends with the library's launch counters: the build build_for() states for the name,
+    the shape and the call ran, and no other -- the named one wherever its conditions hold."""
     select_build(monkeypatch, request.param)
-    return "gather" if request.param.endswith("gather") else request.param
+    b = _Build("gather" if request.param.endswith("gather") else request.param)
+    b.name = request.param
+    return b
 
 
 def _env(**kw):
@@ -52,7 +62,10 @@ class _GoldenTti:
 
 @pytest.mark.parametrize("case", TRACE_CASES)
 def test_golden_traces(case, build):
-    """Closed-loop traces whose agent side was produced by the reference's own code."""
+    """Closed-loop traces whose agent side was produced by the reference's own code.
+    The traces hand the traffic of every TTI over, and a step with explicit traffic runs at full width by design: "mixed" and
+    "mixed-gather" can never run mixed blocks here and assert the build such a step falls back to (the whole-row build; in gather
+    mode the gather build).  Packed waves do take explicit traffic."""
     need_gpu()
     fx = load_golden(case)
     cfg = fx["cfg"]
@@ -65,6 +78,7 @@ def test_golden_traces(case, build):
                n_scenarios=tabs.n_scenarios, bandwidth_hz=float(fx["bw"]), max_steps=steps_per_ep, max_age_cap=cap)
     env.load_scenarios(tabs)
     env.set_policy(0, 255)
+    launched = launches_since(env)
     k = 0
     pooled = build == "gather"     # the gather mode reads pooled tiles: the episode's tiles become a trace of the pool
     for ep, idx in enumerate(fx["scen_ids"]):
@@ -97,6 +111,9 @@ def test_golden_traces(case, build):
             k += 1
         assert np.array_equal(v["mask_inter"][0].cpu().numpy(), fx["mask_inter"][k - 1])
         assert np.array_equal(v["mask_intra"][0].cpu().numpy(), fx["mask_intra"][k - 1])
+    want = build_for(env, build.name, explicit_traffic=True, explicit_se=not pooled)
+    assert want != "mixed"
+    assert_build_ran(env, launched, want, many=False, count=k)
     env.close()
 
 
@@ -130,6 +147,9 @@ def test_batch_vs_oracle(policy, intra, size, build):
     env.set_episodes(scenario=scen, se_base=se_trace * trace_len, se_len=trace_len, se_offset=se_off,
                      trf_base=np.arange(B) * trace_len, trf_len=trace_len, trf_offset=trf_off)
     env.set_policy(policy, intra)
+    if build.name.startswith("mixed"):
+        env.set_option("compact", 1)             # (mixed blocks are compact steps: whatever knob the suite runs under)
+    launched = launches_since(env)
     oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps)
     t0 = np.zeros(B, dtype=np.int64)   # global step at which env b's current episode started
     tile_of = lambda b, t: int(se_trace[b] * trace_len + (se_off[b] + t - t0[b]) % trace_len)
@@ -172,6 +192,11 @@ def test_batch_vs_oracle(policy, intra, size, build):
             for b in np.nonzero(mask)[0]:
                 oenvs[b].reset(se_pool[tile_of(b, t + 1)])
                 np.testing.assert_allclose(after[b], oenvs[b].obs()["obs_inter"], rtol=0, atol=OBS_TOL)
+    # the reference size is packable (an even batch), the scaled one steps two waves per env (mixed blocks)
+    want = build_for(env, build.name)
+    if build.name.startswith("packed" if size == "ref" else "mixed"):
+        assert want == build.name.split("-")[0], (build.name, size, want)
+    assert_build_ran(env, launched, want, many=False, count=steps)
     env.close()
 
 
@@ -210,7 +235,10 @@ def test_shapes_vs_oracle(shape, variant, build):
     oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps, hist_depth=D)
     for b, o in enumerate(oenvs):
         o.reset(se_pool[b * steps])
+    if build.name.startswith("mixed"):
+        env.set_option("compact", 1)
     env.reset()
+    launched = launches_since(env)
     for t in range(steps):
         if variant == "external":
             sc = rng.uniform(-1, 1, (B, S)); ic = rng.integers(0, 3, (B, S)).astype(np.uint8)
@@ -223,6 +251,13 @@ def test_shapes_vs_oracle(shape, variant, build):
             counts.append(o.action_format(sc[b], ic[b], want_dense=False)[1])
             o.step(sc[b], ic[b], se_pool[b * steps + t], trf[b * steps + t])
         assert_matches_oracle(env, obs, rew, oenvs, (shape, variant, t), buffers=False, rb_count=counts)
+    # (packed waves at U = 7 and U = 30; mixed blocks at U = 128; every other shape asserts the build the name falls back to)
+    want = build_for(env, build.name)
+    if max(S, Us) <= 8 and U <= 32 and build.name.startswith("packed"):
+        assert want == "packed"
+    if 64 < U <= 128 and build.name.startswith("mixed"):
+        assert want == "mixed"
+    assert_build_ran(env, launched, want, many=False, count=steps)
     env.close()
 
 
@@ -250,6 +285,7 @@ def test_policy_switching_vs_oracle(build):
     env.set_episodes(scenario=scen, se_base=np.arange(B) * steps, se_len=steps, trf_base=np.arange(B) * steps, trf_len=steps)
     oenvs = oracle_envs(tabs, scen, (S, U, R, G, Us), steps)
     env.reset()
+    launched = launches_since(env)
     for b in range(B):
         oenvs[b].reset(se_pool[b * steps])
     dev = {"marr_rr": (1, 0), "mapf_pf": (2, 1), "mapf_mt": (2, 2)}
@@ -289,4 +325,8 @@ def test_policy_switching_vs_oracle(build):
             o.step(sc[b], ic[b], se_pool[idx[b]], trf[idx[b]])
         assert_matches_oracle(env, obs, rew, oenvs, (what, t), buffers=False, rb_count=counts)
         t += 1
+    # (dense steps and resets are not step-mode launches; one wave per env at this size: "mixed*" asserts its fallback, "packed*" packs)
+    want = build_for(env, build.name)
+    assert want == "packed" or not build.name.startswith("packed")
+    assert_build_ran(env, launched, want, many=False, count=sum(1 for w in plan if w not in ("reset", "dense")))
     env.close()

@@ -324,6 +324,10 @@ def test_options_table_of_the_library_matches_the_header_and_the_environment_is_
     # every documented env variable is RANENV_<KEY>, and getenv appears inside apply_env_options only
     env_fn = src[src.index("void apply_env_options"):src.index("}  // namespace", src.index("void apply_env_options"))]
     assert src.count("getenv(") == env_fn.count("getenv(") == 2
+    # the launch counters ("step_launches_<build>") are answered by ranenv_get_option alone: no row of the table (so no setter and no
+    # RANENV_ variable), and no step launch whose result is thrown away
+    assert not any(k.startswith("step_launches") for k in rows) and 'k.rfind("step_launches_", 0) == 0' in src
+    assert "step_launches" not in setter and not re.search(r"\(void\)\s*launch_step", src) and src.count("launch_step_counted(h, ") == 2
     assert "for (const Option &o : options)" in env_fn and '"RANENV_"' in env_fn and '"RANENV_FUSE_FIRST"' in env_fn
     for key in accepted - {"fuse_first0", "fuse_first9"}:
         assert rows[key] == "true", key

@@ -156,3 +156,35 @@ def test_a_range_intent_accumulates_in_the_oracle_and_is_refused_by_the_tables()
            "slice_1": {}}
     with pytest.raises(ValueError, match="once per slice"):
         tabs.set_from_reference(0, np.ones((1, 2)), np.eye(2, 4), req)
+
+
+# ---- the fuzz cases drawn for a build (tests/test_gpu_fuzz.py's "packed*" / "mixed*" columns) -----------------------------------------
+def test_draw_fuzz_case_is_what_it_was():
+    """replay_fuzz_case and the census depend on these draws: the first cases, field by field."""
+    assert ic.draw_fuzz_case(0) == dict(S=11, U=69, R=1, G=1, Us=4, D=1, load=0.2, low_se=0, how="external", policy=1, intra=0, steps=48)
+    assert ic.draw_fuzz_case(1) == dict(S=4, U=245, R=458, G=5, Us=11, D=10, load=1.0, low_se=0, how="device_steps", policy=2, intra=2, steps=12)
+
+
+@pytest.mark.parametrize("build", ["packed", "packed-gather", "mixed", "mixed-gather"])
+def test_fuzz_cases_drawn_for_a_build_meet_the_conditions_of_that_build(build):
+    """step_plan's conditions (csrc/ranenv_host.cpp) restated on the drawn shape: packed waves need row width 8, at most 32 UEs, one
+    wave per env and an even number of envs in every launch; mixed blocks need two waves per env and a launch of the whole batch.  And
+    the scenario generator accepts every drawn shape."""
+    hows = set()
+    for k in range(60):
+        c = ic.draw_fuzz_case_for(build, k)
+        assert c == ic.draw_fuzz_case_for(build.split("-")[0], k)                  # (the SE mode does not change the draw)
+        S, U, Us, B, parts = c["S"], c["U"], c["Us"], c["B"], c["parts"]
+        nt = max(-(-U // 64), -(-(S * 8) // 64)) * 64
+        assert 1 <= S <= 16 and 1 <= Us <= 16 and max(2, Us) <= U <= 256 and 1 <= c["G"] <= c["R"] <= 488
+        if build.startswith("packed"):
+            assert max(S, Us) <= 8 and U <= 32 and nt == 64 and B % 2 == 0, (k, c)
+            lo = ic.even_cut(B, parts if c["how"] == "device_rollout" else 1)
+            assert lo[-1] == B and all((b - a) % 2 == 0 and b > a for a, b in zip(lo, lo[1:])), (k, c, lo)
+        else:
+            assert 64 < U <= 128 and nt == 128 and parts == 1, (k, c)
+        tabs = ic.fuzz_scenarios(c, 1040 + k)                 # (the seed tests/test_gpu_fuzz.py uses for these columns)
+        assert (tabs.n_scenarios, tabs.n_slices, tabs.n_ues, tabs.max_ues_slice) == (4, S, U, Us)
+        assert (tabs.slice_nues.sum(axis=1) > 0).all(), (k, c)
+        hows.add(c["how"])
+    assert hows == {"external", "device_steps", "device_rollout"}
