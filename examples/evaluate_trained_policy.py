@@ -6,10 +6,15 @@ paper's violation / distance metrics (results/gen_results.py:874-1022, kept by t
 
     python examples/evaluate_trained_policy.py --random [--batch 1024] [--episodes 2] [--steps 200]
     python examples/evaluate_trained_policy.py --weights ckpt.pt [--intra-weights intra.pt] [--intra-input mask_obs] [--stochastic]
+    python examples/evaluate_trained_policy.py --random --hidden 512,512,512 --precision both [--json]
 
 --weights / --intra-weights: a torch state dict of an RLlib FullyConnectedNetwork (keys internal_model._hidden_layers.{i}._model.0.*,
 internal_model._logits._model.0.*; adapters.rllib_fcnet_layers) or of a torch.nn.Sequential of Linear + Tanh (keys {i}.weight /
 {i}.bias).  --random draws nets of --hidden widths instead.  Without intra weights the slices schedule with --fixed-intra.
+--precision bf16 runs the nets on the bf16 matrix cores (set_policy_network(precision="bf16"): weights, inputs and hidden
+activations rounded to bf16, include/ranenv.h); "both" evaluates the same episodes under the f32 and the bf16 nets and prints the
+metrics side by side with their largest relative difference -- how far the episode figures move.  With --random nets that says how
+sensitive these episodes are to a perturbation of the actions in the third digit, not how a trained policy behaves.
 """
 from __future__ import annotations
 
@@ -56,6 +61,8 @@ def main():
     ap.add_argument("--fixed-intra", default="pf", choices=sorted(INTRA))
     ap.add_argument("--stochastic", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--precision", default="f32", choices=("f32", "bf16", "both"))
+    ap.add_argument("--json", action="store_true", help="also print one JSON line: per agent the per-TTI means, and the f32 / bf16 difference")
     args = ap.parse_args()
     if not args.random and not args.weights:
         ap.error("give --weights or --random")
@@ -77,10 +84,11 @@ def main():
     env.set_episode_table(scenario=eps["scenario"], se_base=eps["se_base"], se_len=eps["se_len"], se_offset=eps["se_offset"],
                           trf_base=eps["trf_base"], trf_len=eps["trf_len"], trf_offset=eps["trf_offset"])
     results = {}
-    for name in ("network", "MARR", "MAPF"):
-        if name == "network":
+    precisions = ("f32", "bf16") if args.precision == "both" else (args.precision,)
+    for name in tuple(f"network {p}" for p in precisions) + ("MARR", "MAPF"):
+        if name.startswith("network"):
             env.set_policy_network(inter, intra, stochastic=args.stochastic, seed=args.seed, intra_input=args.intra_input,
-                                   activation=args.activation, fixed_intra=INTRA[args.fixed_intra])
+                                   activation=args.activation, fixed_intra=INTRA[args.fixed_intra], precision=name.split()[1])
         else:
             env.set_policy(_lib.POLICY_MARR if name == "MARR" else _lib.POLICY_MAPF, INTRA[args.fixed_intra])
         env.enable_autoreset(0, B, episode_numbers=np.arange(B, dtype=np.int32))
@@ -93,9 +101,22 @@ def main():
         results[name]["_s"] = t0.elapsed_time(t1) * 1e-3
     print(f"{B} envs x {n_ep} episodes of {args.steps} TTIs (S {env.S}, U {env.U}); per-TTI means over all episodes")
     print(f"{'metric':<22}" + "".join(f"{n:>14}" for n in results))
-    for m in ("reward", "violations", "priority_violations", "distance", "priority_distance", "pkts_sent", "pkts_dropped"):
-        print(f"{m:<22}" + "".join(f"{float(np.mean(r[m] / r['ttis'])):>14.4f}" for r in results.values()))
+    metrics = [m for m in env.METRIC_NAMES if m != "ttis"]
+    means = {n: {m: float(np.mean(r[m] / r["ttis"])) for m in metrics} | {"ttis": float(np.mean(r["ttis"]))} for n, r in results.items()}
+    for m in metrics:
+        print(f"{m:<22}" + "".join(f"{means[n][m]:>14.4f}" for n in results))
     print(f"{'env-steps/s':<22}" + "".join(f"{B * n_ep * args.steps / r['_s']:>14.3g}" for r in results.values()))
+    diff = None
+    if args.precision == "both":
+        a, b = means["network f32"], means["network bf16"]
+        diff = {m: abs(a[m] - b[m]) / max(abs(a[m]), 1e-300) for m in a}
+        worst = max(diff, key=diff.get)
+        print(f"f32 -> bf16: largest relative difference of the {len(diff)} episode metrics {diff[worst]:.3g} ({worst})")
+    if args.json:
+        import json
+        print(json.dumps({"batch": B, "episodes": n_ep, "steps": args.steps, "hidden": hidden, "activation": args.activation,
+                          "stochastic": args.stochastic, "means": means, "relative_difference": diff,
+                          "env_steps_per_s": {n: B * n_ep * args.steps / r["_s"] for n, r in results.items()}}))
     env.close()
 
 

@@ -61,6 +61,7 @@ enum { RANENV_POLICY_EXTERNAL = 0, RANENV_POLICY_MARR = 1, RANENV_POLICY_MAPF = 
 enum { RANENV_HEAD_DIST_GAUSS_CLIP = 0, RANENV_HEAD_DIST_GAUSS_TANH = 1 };
 enum { RANENV_ACT_TANH = 0, RANENV_ACT_RELU = 1 };
 enum { RANENV_NET_IN_OBS = 0, RANENV_NET_IN_MASK_OBS = 1 };
+enum { RANENV_NET_F32 = 0, RANENV_NET_BF16 = 1 };      /* ranenv_mlp.precision */
 enum { RANENV_INTRA_RR = 0, RANENV_INTRA_PF = 1, RANENV_INTRA_MT = 2, RANENV_INTRA_PER_SLICE = 255 };
 enum { RANENV_SE_STREAM = 0, RANENV_SE_GATHER = 1 };
 enum { RANENV_METRIC_THROUGHPUT = 0, RANENV_METRIC_RELIABILITY = 1, RANENV_METRIC_LATENCY = 2 };
@@ -233,6 +234,25 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra);
  *     a function of those numbers alone: independent of launches, partitions and ranges.
  *   Layers are GEMMs on the f32-input matrix cores (exact f32 products, f32 accumulation); results match a float32 torch
  *   forward to rounding, not bit for bit.
+ *   precision (per net; the copies of a per-slice set agree): RANENV_NET_F32, the above -- what a zeroed field asks for -- or
+ *   RANENV_NET_BF16, reduced-precision inference on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16).  THE CONTRACT of a bf16 net:
+ *     - W of every layer is rounded once, at bind, to bf16, round to nearest even (RNE); the biases stay float32.
+ *     - The input row is rounded to bf16 (RNE) on its way into LDS: the observation, and RANENV_NET_IN_MASK_OBS's 0 / 1 mask floats
+ *       (exact).  ranenv_collect goes on recording the unrounded float32 observation.
+ *     - Hidden layer: float32 accumulator, + the float32 bias, the activation in float32 (tanhf / fmaxf), then RNE to bf16 as the
+ *       next layer's input.  Output layer: accumulator + bias in float32, not rounded.
+ *     - The epilogue is the one above, float64 on those float32 outputs: masked Gaussian, clamp / tanh, argmax / categorical,
+ *       log-probabilities, Philox keying, the value column.
+ *     - Products of two bf16 numbers are exact in float32; the summation order and the matrix core's internal rounding are
+ *       unspecified.  adapters._mlp_forward(..., precision="bf16") is the float32 restatement.
+ *   Accepted for every actor and critic of ranenv_set_policy_network, _set_value_network, _set_intra_policy_networks,
+ *   _set_intra_value_networks, _set_head_policy_network and _set_head_value_network; an actor and its critic may differ.  Any other
+ *   value is RANENV_E_INVALID before any device call.  Not for SAC's training targets: ranenv_set_sac_critics with a bf16 critic is
+ *   RANENV_E_INVALID, ranenv_sac_targets while the head actor is a bf16 net RANENV_E_STATE.
+ *   Figures (DESIGN.md 4.p "Reduced precision"; tools/kernel_resources.py, tools/policy_bf16_probe.py on one MI355X): the bf16
+ *   kernels use 66-74 VGPRs, 0 AGPRs, no scratch, and 2 x 32 x (width + 16) x 2 bytes of LDS (67 584 at width 512; f32: 132 096);
+ *   rollout(200) with [512] x 3 inter + intra nets runs 2.2x (B 4096, S 10 / U 100) and 2.6x (B 16 384, S 5 / U 25) as fast as
+ *   under the f32 nets, with [64, 64] nets 1.02-1.09x; the f32 kernels and their results are unchanged.
  * ranenv_set_policy_network validates the shapes against S / Us (RANENV_E_INVALID); it does not change the policy:
  * ranenv_set_policy(h, RANENV_POLICY_NETWORK, fixed_intra) does.  Under that policy a TTI without scores and without a bound
  * net fails with RANENV_E_STATE, one without the obs_inter buffer (or obs_intra with an intra net) with RANENV_E_INVALID: the
@@ -244,7 +264,7 @@ typedef struct {
     int32_t n_hidden;         /* 1..4                                          */
     int32_t activation;       /* RANENV_ACT_TANH / RANENV_ACT_RELU              */
     int32_t input_layout;     /* RANENV_NET_IN_OBS / RANENV_NET_IN_MASK_OBS     */
-    int32_t reserved;
+    int32_t precision;        /* RANENV_NET_F32 (0) / RANENV_NET_BF16           */
     int32_t dims[6];
     const float *weight[5];
     const float *bias[5];
@@ -260,7 +280,7 @@ int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **de
  *     actions; not the sorted position.  n must equal S.  n == 0 with a NULL array unbinds that per-slice set; unbinding the
  *     actors unbinds the per-slice critics with them.
  *   Each net is validated as ranenv_set_policy_network's intra net / ranenv_set_value_network's intra critic, and all n must
- *     agree in n_hidden, dims, activation and input_layout (RLlib builds them from one model config); anything else is
+ *     agree in n_hidden, dims, activation, input_layout and precision (RLlib builds them from one model config); anything else is
  *     RANENV_E_INVALID.  Every validation error precedes every device call; the handle changes on success only.  The copies go
  *     into a packed buffer of the set's own, the S nets at equal stride (an outgrown buffer lives until ranenv_destroy).
  *   ranenv_set_intra_policy_networks needs a bound inter net (ranenv_set_policy_network; else RANENV_E_STATE) and acts with

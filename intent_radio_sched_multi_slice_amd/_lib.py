@@ -17,6 +17,8 @@ HEAD_DIST_GAUSS_CLIP, HEAD_DIST_GAUSS_TANH = 0, 1
 HEAD_SRC_HEAD, HEAD_SRC_INTER = 0, 1
 ACT_TANH, ACT_RELU = 0, 1
 NET_IN_OBS, NET_IN_MASK_OBS = 0, 1
+NET_F32, NET_BF16 = 0, 1
+NET_PRECISIONS = {"f32": NET_F32, "bf16": NET_BF16}
 NET_MAX_HIDDEN, NET_MAX_WIDTH = 4, 512
 INTRA_RR, INTRA_PF, INTRA_MT, INTRA_PER_SLICE = 0, 1, 2, 255
 F_CLEAR_HISTORY_ON_RESET, F_NO_RAW_OUTPUT, F_SYNC_CHECK, F_SCALE_PER_ELEMENT = 0x1, 0x2, 0x4, 0x8
@@ -70,7 +72,7 @@ VIEW_FIELDS = (
 
 class Mlp(C.Structure):
     """ranenv_mlp: n_hidden Linear + activation layers and an output Linear, torch layout, device pointers."""
-    _fields_ = [("n_hidden", C.c_int32), ("activation", C.c_int32), ("input_layout", C.c_int32), ("reserved", C.c_int32),
+    _fields_ = [("n_hidden", C.c_int32), ("activation", C.c_int32), ("input_layout", C.c_int32), ("precision", C.c_int32),
                 ("dims", C.c_int32 * 6), ("weight", C.c_void_p * 5), ("bias", C.c_void_p * 5)]
 
 

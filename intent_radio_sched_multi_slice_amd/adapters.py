@@ -335,18 +335,40 @@ def philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
     return c0, c1, c2, c3
 
 
-def _mlp_forward(x: torch.Tensor, layers, activation: str) -> torch.Tensor:
+def bf16_round(tensor: torch.Tensor) -> torch.Tensor:
+    """float32 values rounded to bfloat16, round to nearest even, as float32 again: the rounding of a RANENV_NET_BF16 net's
+    weights (once, at bind) and of its input and hidden activations (v_cvt_pk_bf16_f32 on the device).  On the bits, so it does
+    not depend on the torch build: add 0x7FFF + (bit 16) and drop the low 16 bits."""
+    x = torch.as_tensor(tensor).detach().to(torch.float32).contiguous()
+    bits = x.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    out = ((bits + 0x7FFF + ((bits >> 16) & 1)) & 0xFFFF0000).to(torch.int64)
+    out = torch.where(out >= 2 ** 31, out - 2 ** 32, out).to(torch.int32).view(torch.float32)
+    return torch.where(torch.isnan(x), x, out)
+
+
+def _mlp_forward(x: torch.Tensor, layers, activation: str, precision: str = "f32") -> torch.Tensor:
+    """The float32 forward of a (W, b) stack.  ``precision`` "bf16" is the normative restatement of a RANENV_NET_BF16 net
+    (include/ranenv.h): W and the input row rounded to bf16 (``bf16_round``), every hidden layer float32 accumulation + float32
+    bias + float32 activation and then rounded to bf16, the output layer float32 and not rounded.  Products of bf16 numbers are
+    exact in float32; the summation order is torch's here and the matrix core's on the device."""
+    if precision not in ("f32", "bf16"):
+        raise ValueError("precision must be 'f32' or 'bf16'")
+    bf = precision == "bf16"
     act = torch.tanh if activation == "tanh" else torch.relu
+    if bf:
+        x = bf16_round(x)
     for i, (w, b) in enumerate(layers):
-        x = x @ w.t() + b
+        x = x @ (bf16_round(w) if bf else w).t() + b
         if i < len(layers) - 1:
             x = act(x)
+            if bf:
+                x = bf16_round(x)
     return x
 
 
 def ibsched_policy_actions(obs_inter, mask_inter, inter, obs_intra=None, mask_intra=None, intra=None, stochastic: bool = False,
                            seed: int = 0, intra_input: str = "obs", activation: Optional[str] = None, env_ids=None, episode=None,
-                           step=None):
+                           step=None, precision: str = "f32"):
     """What the device computes under RANENV_POLICY_NETWORK, in plain torch / numpy (the normative statement the GPU tests
     compare against; include/ranenv.h spells out the same rules).
 
@@ -358,12 +380,13 @@ def ibsched_policy_actions(obs_inter, mask_inter, inter, obs_intra=None, mask_in
       intra: argmax of the 3 logits (lowest index on ties), or the categorical draw of Philox word 2 at (..., POLICY_TAG + slice).
     ``env_ids`` / ``episode`` / ``step``: [B] (the env's id base + index, views' episode_number and step_number before the TTI).
     ``intra`` may be a list of S nets (non-shared intra policies): slice index s's rows go through ``intra[s]``.
+    ``precision`` "bf16": every net as bound with ``precision="bf16"`` (``_mlp_forward``).
     Returns (scores float64 [B, S], intra uint8 [B, S] or None) as CPU tensors."""
     from .batched_env import per_slice_nets, policy_net_layers
     obs_inter = torch.as_tensor(obs_inter).detach().cpu().to(torch.float32)
     B, S = obs_inter.shape[0], obs_inter.shape[1] // 10
     layers, act = policy_net_layers(inter, activation, 10 * S, 2 * S)
-    out = _mlp_forward(obs_inter, [(w.cpu(), b.cpu()) for w, b in layers], act).to(torch.float64)
+    out = _mlp_forward(obs_inter, [(w.cpu(), b.cpu()) for w, b in layers], act, precision).to(torch.float64)
     mean, log_std = out[:, :S], out[:, S:]
     masked = sorted_action_mask(torch.as_tensor(mask_inter).cpu()) == 0
     draws = None
@@ -390,14 +413,14 @@ def ibsched_policy_actions(obs_inter, mask_inter, inter, obs_intra=None, mask_in
     nets = per_slice_nets(intra)
     if nets is None:
         il, iact = policy_net_layers(intra, activation, x.shape[1], 3)
-        lg = _mlp_forward(x, [(w.cpu(), b.cpu()) for w, b in il], iact).reshape(B, S, 3)
+        lg = _mlp_forward(x, [(w.cpu(), b.cpu()) for w, b in il], iact, precision).reshape(B, S, 3)
     else:
         if len(nets) != S:
             raise ValueError(f"{len(nets)} intra nets given: one per slice is {S}")
         per = []
         for s, net in enumerate(nets):
             il, iact = policy_net_layers(net, activation, x.shape[1], 3)
-            per.append(_mlp_forward(x.reshape(B, S, -1)[:, s], [(w.cpu(), b.cpu()) for w, b in il], iact))
+            per.append(_mlp_forward(x.reshape(B, S, -1)[:, s], [(w.cpu(), b.cpu()) for w, b in il], iact, precision))
         lg = torch.stack(per, dim=1)
     if not stochastic:
         l0, l1, l2 = lg[..., 0], lg[..., 1], lg[..., 2]
@@ -570,7 +593,7 @@ def head_policy_noise(env_ids, episode, step, S: int, seed: int):
 
 
 def head_policy_actions(head_obs, actor, dist: str = "gauss_clip", log_std=None, stochastic: bool = False, seed: int = 0,
-                        activation: Optional[str] = None, env_ids=None, episode=None, step=None):
+                        activation: Optional[str] = None, env_ids=None, episode=None, step=None, precision: str = "f32"):
     """What the device computes under RANENV_POLICY_HEAD_NETWORK, in plain torch / numpy (the normative statement the GPU tests
     compare against; include/ranenv.h spells out the same rules).
 
@@ -580,6 +603,7 @@ def head_policy_actions(head_obs, actor, dist: str = "gauss_clip", log_std=None,
       "gauss_tanh" (SB3 SAC): (mu | log_std) = net(obs) [2S], log_std clamped to [-20, 2]; a = mu, or mu + exp(log_std) * z;
           score = tanh(a);
       z = ``head_policy_noise`` at (env_ids + b, episode[b], step[b]).  Nothing is masked: the step applies the slice rules.
+    ``precision`` "bf16": the actor as bound with ``precision="bf16"`` (``_mlp_forward``).
     Returns (scores float64 [B, S], a float64 [B, S] -- the unclamped / unsquashed action) as CPU tensors."""
     from .batched_env import policy_net_layers
     head_obs = torch.as_tensor(head_obs).detach().cpu().to(torch.float32)
@@ -591,7 +615,7 @@ def head_policy_actions(head_obs, actor, dist: str = "gauss_clip", log_std=None,
     if activation is None and not isinstance(actor, torch.nn.Module):
         activation = "tanh" if dist == "gauss_clip" else "relu"
     layers, act = policy_net_layers(actor, activation, 10 * S, S if dist == "gauss_clip" else 2 * S)
-    out = _mlp_forward(head_obs, [(w.cpu(), b.cpu()) for w, b in layers], act).to(torch.float64)
+    out = _mlp_forward(head_obs, [(w.cpu(), b.cpu()) for w, b in layers], act, precision).to(torch.float64)
     if dist == "gauss_clip":
         a = out
         ls = torch.as_tensor(log_std).detach().cpu().to(torch.float32).to(torch.float64).reshape(1, S)

@@ -425,27 +425,35 @@ class BatchedRanEnv:
         return 10 * self.S, self.W + (self.Us if intra_input == "mask_obs" else 0)
 
     def set_policy_network(self, inter, intra=None, stochastic: bool = False, seed: int = 0, intra_input: str = "obs",
-                           activation: Optional[str] = None, fixed_intra: Optional[int] = None):
+                           activation: Optional[str] = None, fixed_intra: Optional[int] = None, precision: str = "f32"):
         """Run trained IBSched policy nets on the device in front of every TTI (RANENV_POLICY_NETWORK, include/ranenv.h):
         ``inter`` -> 2*S outputs (mean, log_std of the masked Gaussian), ``intra`` (None = ``fixed_intra``) -> 3 logits per
         (env, slice) from ``obs_intra`` ("obs") or ``[mask_intra, obs_intra]`` ("mask_obs", RLlib's flattened Dict).  Nets as
         for ``policy_net_layers``.  Switches the policy to NETWORK: ``step()`` / ``rollout()`` / ``evaluate()`` then need no
         actions.  ``stochastic``: sample (Philox noise keyed by ``seed``) instead of taking the mode.
         ``intra`` may be a list of S nets of one shape, non-shared intra policies (the reference's ``shared_policies=False``):
-        ``intra[s]`` serves slice index s, i.e. ``player_{s+1}`` (ranenv_set_intra_policy_networks)."""
+        ``intra[s]`` serves slice index s, i.e. ``player_{s+1}`` (ranenv_set_intra_policy_networks).
+        ``precision`` "bf16": every net of this call runs on the bf16 matrix cores -- weights rounded once at bind, input and hidden
+        activations rounded to bf16, float32 accumulation, biases, activations and outputs (the contract is in include/ranenv.h;
+        ``adapters._mlp_forward(..., precision="bf16")`` restates it).  Results then differ from the float32 nets' in the third or
+        fourth digit; "f32", the default, leaves them as they were."""
         in_inter, in_intra = self.net_input_dims(intra_input)
-        per_slice = self._net_list(per_slice_nets(intra), activation, in_intra, 3, NET_INPUTS[intra_input])
+        per_slice = self._net_list(per_slice_nets(intra), activation, in_intra, 3, NET_INPUTS[intra_input], precision)
         self._set_nets("policy_net", "ranenv_set_policy_network", [(inter, activation, in_inter, 2 * self.S, NET_IN_OBS),
                        (None if per_slice else intra, activation, in_intra, 3, NET_INPUTS[intra_input])], 1 if stochastic else 0,
-                       int(seed) & (2 ** 64 - 1))
+                       int(seed) & (2 ** 64 - 1), precision=precision)
         self._set_net_list("intra_policy_nets", "ranenv_set_intra_policy_networks", per_slice)
         self._intra_layout = None if intra is None else NET_INPUTS[intra_input]
         self._policy_views = None
         self.set_policy(POLICY_NETWORK, self.fixed_intra if fixed_intra is None else fixed_intra)
 
-    def _mlp_struct(self, layers, act: str, layout: int, keep: list):
+    def _mlp_struct(self, layers, act: str, layout: int, keep: list, precision="f32"):
+        """``precision``: a name of ``_lib.NET_PRECISIONS`` (or, for the library's own check, the raw integer of the field)."""
+        if not isinstance(precision, int) and precision not in _lib.NET_PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.NET_PRECISIONS)}")
         m = _lib.Mlp()
         m.n_hidden, m.activation, m.input_layout = len(layers) - 1, NET_ACTIVATIONS[act], layout
+        m.precision = precision if isinstance(precision, int) else _lib.NET_PRECISIONS[precision]
         m.dims[0] = layers[0][0].shape[1]
         for i, (w, b) in enumerate(layers):
             w, b = w.to(self.device).contiguous(), b.to(self.device).contiguous()
@@ -454,7 +462,7 @@ class BatchedRanEnv:
             m.weight[i], m.bias[i] = w.data_ptr(), b.data_ptr()
         return m
 
-    def _set_nets(self, key: str, call: str, nets, *args, keep=()):
+    def _set_nets(self, key: str, call: str, nets, *args, keep=(), precision="f32"):
         """One ``ranenv_set_*`` call that binds nets: per ranenv_mlp argument ``(net, activation, in_dim, out_dim, input layout)`` --
         a ``None`` net is passed as NULL, a callable layout is asked with the net's layers -- then ``args``, then the stream."""
         keep, structs = list(keep), []
@@ -463,12 +471,12 @@ class BatchedRanEnv:
                 structs.append(None)
                 continue
             layers, act = policy_net_layers(net, activation, in_dim, out_dim)
-            structs.append(C.byref(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep)))
+            structs.append(C.byref(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep, precision)))
         with torch.cuda.device(self.device):
             self._check(getattr(self._lib, call)(self._h, *structs, *args, self._stream()), call)
         self._keep[key] = keep                 # (the library copies on the current stream; keep the sources until it has)
 
-    def _net_list(self, nets, activation, in_dim, out_dim, layout):
+    def _net_list(self, nets, activation, in_dim, out_dim, layout, precision="f32"):
         """A list of S nets as the argument of a ``ranenv_set_intra_*_networks`` call: ``(array of ranenv_mlp pointers, what to
         keep alive)``, or None for None.  Raises ValueError -- before any library call: a per-slice bind is two of
         them, and the first one drops the previous set -- unless there are S valid nets of one shape and activation."""
@@ -484,7 +492,7 @@ class BatchedRanEnv:
             if shape != first:
                 raise ValueError(f"intra net {i} ({shape[0]}, {shape[1]}) differs from net 0 ({first[0]}, {first[1]}): "
                                  "the nets per slice have one shape and one activation")
-            structs.append(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep))
+            structs.append(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep, precision))
         return (C.POINTER(_lib.Mlp) * len(structs))(*[C.pointer(m) for m in structs]), keep + structs
 
     def _set_net_list(self, key: str, call: str, net_list):
@@ -495,20 +503,21 @@ class BatchedRanEnv:
             self._check(getattr(self._lib, call)(self._h, self.S, net_list[0], self._stream()), call)
         self._keep[key] = net_list[1]
 
-    def set_value_network(self, inter, intra=None, activation: Optional[str] = None):
+    def set_value_network(self, inter, intra=None, activation: Optional[str] = None, precision: str = "f32"):
         """Bind the critics that ``collect()`` evaluates beside the actors (ranenv_set_value_network): ``inter`` maps the
         inter-slice observation [10*S] to one value, ``intra`` (None = no intra critic: those columns of ``vf`` are 0) the
         intra actor's input row -- the layout given to ``set_policy_network`` -- to one value per (env, slice).  Nets as for
         ``policy_net_layers``.  Bind the actors first when there is an intra critic; re-binding either pair leaves the other.
         ``intra`` may be a list of S critics of one shape, ``intra[s]`` for slice index s (ranenv_set_intra_value_networks), with
-        shared or per-slice intra actors alike."""
+        shared or per-slice intra actors alike.  ``precision`` as for ``set_policy_network``, for every critic of this call; the
+        critics' precision is their own -- bf16 critics beside f32 actors and the reverse are both fine."""
         layout = lambda layers: NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS  # noqa: E731
-        per_slice = self._net_list(per_slice_nets(intra), activation, None, 1, layout)
+        per_slice = self._net_list(per_slice_nets(intra), activation, None, 1, layout, precision)
         if per_slice is not None and self._intra_layout != per_slice[0][0].contents.input_layout:
             raise ValueError("intra critics per slice read the intra actor's input row: " + (
                 "no intra actor is bound (set_policy_network)" if self._intra_layout is None else "its intra_input is the other layout"))
         self._set_nets("value_net", "ranenv_set_value_network", [(inter, activation, 10 * self.S, 1, NET_IN_OBS),
-                       (None if per_slice else intra, activation, None, 1, layout)])
+                       (None if per_slice else intra, activation, None, 1, layout)], precision=precision)
         self._set_net_list("intra_value_nets", "ranenv_set_intra_value_networks", per_slice)
 
     TRAJECTORY_SHAPES = {      # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S, Us, W)
@@ -574,7 +583,7 @@ class BatchedRanEnv:
     # -- the learned baselines SchedTWC / SchedColORAN (RANENV_POLICY_HEAD_NETWORK) ------------------------------------------------
     def set_head_policy_network(self, actor, dist: str = "gauss_clip", log_std=None, stochastic: bool = False, seed: int = 0,
                                 activation: Optional[str] = None, allow_sorted: bool = False, fixed_intra: Optional[int] = None,
-                                observation: str = "head"):
+                                observation: str = "head", precision: str = "f32"):
         """Run a trained SchedTWC / SchedColORAN actor on the device in front of every TTI (RANENV_POLICY_HEAD_NETWORK,
         include/ranenv.h): ``actor`` maps ``head_obs`` [10*S] to S outputs (``dist`` "gauss_clip": SB3 PPO, the mean; ``log_std``
         [S] is the policy's parameter) or 2*S outputs ("gauss_tanh": SB3 SAC, (mu | log_std); ``log_std`` must be None).  Nets as
@@ -586,7 +595,8 @@ class BatchedRanEnv:
         ``fixed_intra=INTRA_PF`` ``sb3_pf_sched`` --, the same SB3 actor on IBSched's own player_0 observation: it reads ``obs_inter``
         (slices in sorted positions, IBSched's default: no ``allow_sorted`` check), needs no ``enable_heads()``, and ``collect_head`` /
         the replay ring record the step's ``[S + 1]`` reward rows, whose column 0 (``reward="ibsched"``) is its reward.  The source
-        in force is ``self.head_observation``; changing it unbinds a bound replay ring."""
+        in force is ``self.head_observation``; changing it unbinds a bound replay ring.
+        ``precision`` as for ``set_policy_network``.  ``sac_targets()`` needs an f32 actor: training targets stay float32."""
         if observation not in HEAD_SOURCES:
             raise ValueError(f"observation must be one of {sorted(HEAD_SOURCES)}")
         if dist not in HEAD_DISTS:
@@ -610,7 +620,7 @@ class BatchedRanEnv:
                 raise ValueError(f"log_std: expected shape ({self.S},), got {tuple(ls.shape)}")
         self._set_nets("head_policy_net", "ranenv_set_head_policy_network",
                        [(actor, activation, 10 * self.S, self.S if dist == "gauss_clip" else 2 * self.S, NET_IN_OBS)],
-                       HEAD_DISTS[dist], _ptr(ls), 1 if stochastic else 0, int(seed) & (2 ** 64 - 1), keep=[ls])
+                       HEAD_DISTS[dist], _ptr(ls), 1 if stochastic else 0, int(seed) & (2 ** 64 - 1), keep=[ls], precision=precision)
         self._policy_views = None
         self._check(self._lib.ranenv_set_head_policy_source(self._h, HEAD_SOURCES[observation]), "ranenv_set_head_policy_source")
         if observation != self.head_observation:
@@ -618,10 +628,12 @@ class BatchedRanEnv:
         self.head_observation = observation
         self.set_policy(POLICY_HEAD_NETWORK, INTRA_RR if fixed_intra is None else fixed_intra)
 
-    def set_head_value_network(self, critic, activation: Optional[str] = None):
+    def set_head_value_network(self, critic, activation: Optional[str] = None, precision: str = "f32"):
         """Bind the critic ``collect_head()`` evaluates beside the head actor (ranenv_set_head_value_network): ``head_obs`` [10*S]
-        (``obs_inter`` under the head policy source "inter") -> one value.  Nets as for ``policy_net_layers``."""
-        self._set_nets("head_value_net", "ranenv_set_head_value_network", [(critic, activation, 10 * self.S, 1, NET_IN_OBS)])
+        (``obs_inter`` under the head policy source "inter") -> one value.  Nets as for ``policy_net_layers``; ``precision`` as
+        for ``set_policy_network``."""
+        self._set_nets("head_value_net", "ranenv_set_head_value_network", [(critic, activation, 10 * self.S, 1, NET_IN_OBS)],
+                       precision=precision)
 
     HEAD_TRAJECTORY_SHAPES = {     # field -> (dtype, slots beyond n_steps, shape of one slot in terms of B, S)
         "obs_head": (torch.float32, 0, lambda B, S: (B, 10 * S)), "action": (torch.float64, 0, lambda B, S: (B, S)),

@@ -2,8 +2,9 @@
 
 Six objects, compiled in parallel, then linked:
   ranenv_step.hip x 3   the builds of the step kernel for row widths NP = 8, 10, 16 (-DRANENV_NP=...)
-  ranenv_aux.hip        the small kernels (class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination)
-  ranenv_policy.hip     the policy networks (RANENV_POLICY_NETWORK: MLP forwards on the f32 matrix cores)
+  ranenv_aux.hip        the small kernels (class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination,
+                        bf16 weight packing)
+  ranenv_policy.hip     the policy networks (RANENV_POLICY_NETWORK: MLP forwards on the f32 matrix cores, or per net on the bf16 ones)
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants

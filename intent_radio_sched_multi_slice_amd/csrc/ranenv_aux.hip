@@ -745,9 +745,32 @@ __global__ void __launch_bounds__(256) ranenv_replay_sample_kernel(const ReplayS
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// A RANENV_NET_BF16 net's weights at bind: f32 W [N][K] -> bf16 [np][kp], round to nearest even (the conversion the policy kernel
+// applies to its activations: v_cvt_pk_bf16_f32), zeros in the padding.  A thread owns two neighbouring columns (kp is even).
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ranenv_pack_bf16_kernel(const float *src, int N, int K, int np, int kp, unsigned *dst)
+{
+    const long long pairs = (long long)np * (kp / 2);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (long long)gridDim.x * blockDim.x) {
+        const int n = (int)(i / (kp / 2)), k = 2 * (int)(i - (long long)n * (kp / 2));
+        const float lo = n < N && k < K ? src[(size_t)n * K + k] : 0.0f, hi = n < N && k + 1 < K ? src[(size_t)n * K + k + 1] : 0.0f;
+        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        const bf16x2 v = {(__bf16)lo, (__bf16)hi};
+        dst[i] = __builtin_bit_cast(unsigned, v);
+    }
+}
+
 }  // namespace
 
 namespace ranenv_dev {
+
+void launch_pack_bf16(hipStream_t s, const float *src, int N, int K, int np, int kp, unsigned short *dst)
+{
+    long long blocks = ((long long)np * (kp / 2) + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(ranenv_pack_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, N, K, np, kp, (unsigned *)dst);
+}
 
 void launch_copy_words(hipStream_t s, unsigned long long *dst0, const unsigned long long *src0, long long n0, unsigned long long *dst1,
                        const unsigned long long *src1, long long n1)

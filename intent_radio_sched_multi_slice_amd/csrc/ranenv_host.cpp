@@ -1218,6 +1218,8 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, Policy
     const bool intra = NET_ROLES[role].intra;
     if (m->n_hidden < 1 || m->n_hidden > NET_MAX_LAYERS - 1) return fail(h, RANENV_E_INVALID, "%s net: %d hidden layers (1..%d)", who, m->n_hidden, NET_MAX_LAYERS - 1);
     if (m->activation != RANENV_ACT_TANH && m->activation != RANENV_ACT_RELU) return fail(h, RANENV_E_INVALID, "%s net: unknown activation %d", who, m->activation);
+    if (m->precision != RANENV_NET_F32 && m->precision != RANENV_NET_BF16) return fail(h, RANENV_E_INVALID, "%s net: unknown precision %d", who, m->precision);
+    if (role == NET_SAC_Q && m->precision != RANENV_NET_F32) return fail(h, RANENV_E_INVALID, "SAC critic: precision %d (the training targets stay RANENV_NET_F32)", m->precision);
     int in_dim = role == NET_SAC_Q ? 11 * S : 10 * S;
     if (!intra && m->input_layout != RANENV_NET_IN_OBS) return fail(h, RANENV_E_INVALID, "%s net: input layout %d (only RANENV_NET_IN_OBS)", who, m->input_layout);
     if (intra) {
@@ -1233,10 +1235,11 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, Policy
     for (int i = 0; i < L; i++)
         if (!m->weight[i] || !m->bias[i]) return fail(h, RANENV_E_INVALID, "%s net: layer %d has no weight / bias", who, i);
     net = PolicyNet{};
-    net.n_layers = L; net.act = m->activation; net.layout = m->input_layout; net.in_dim = in_dim; net.out_dim = out_dim;
+    net.n_layers = L; net.act = m->activation; net.layout = m->input_layout; net.prec = m->precision; net.in_dim = in_dim; net.out_dim = out_dim;
+    const int per_float = net.prec == RANENV_NET_BF16 ? 2 : 1;      // weights per float of the packed copy
     for (int l = 0; l < L; l++) {
         net.kp[l] = (m->dims[l] + 31) / 32 * 32; net.np[l] = (m->dims[l + 1] + 31) / 32 * 32;
-        net.w_off[l] = off; off += (long long)net.kp[l] * net.np[l];
+        net.w_off[l] = off; off += (long long)net.kp[l] * net.np[l] / per_float;
         net.b_off[l] = off; off += net.np[l];
     }
     return RANENV_OK;
@@ -1246,10 +1249,12 @@ static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, 
 {
     for (int l = 0; l < net.n_layers; l++) {
         const int K = m->dims[l], N = m->dims[l + 1];
-        HIP_TRY(h, hipMemcpy2DAsync(dst + net.w_off[l], sizeof(float) * net.kp[l], m->weight[l], sizeof(float) * K, sizeof(float) * K, N,
+        if (net.prec == RANENV_NET_BF16) launch_pack_bf16(s, m->weight[l], N, K, net.np[l], net.kp[l], (unsigned short *)(dst + net.w_off[l]));
+        else HIP_TRY(h, hipMemcpy2DAsync(dst + net.w_off[l], sizeof(float) * net.kp[l], m->weight[l], sizeof(float) * K, sizeof(float) * K, N,
                                     hipMemcpyDeviceToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(dst + net.b_off[l], m->bias[l], sizeof(float) * N, hipMemcpyDeviceToDevice, s));
     }
+    if (net.prec == RANENV_NET_BF16) HIP_TRY(h, hipGetLastError());
     return RANENV_OK;
 }
 
@@ -1257,7 +1262,7 @@ static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, 
 // argument checks -- an error so far precedes every HIP call and leaves every slot as it was --, hipSetDevice, its own allocations,
 // net_commit for all of its nets.
 // PLAN: `copies` nets of one role (one, or one per slice) validated and laid out: net_layout's checks for every copy, and all copies of
-// one shape, activation and input layout.  No HIP call, nothing of the handle changes.
+// one shape, activation, input layout and precision.  No HIP call, nothing of the handle changes.
 struct NetBind {
     ranenv::NetSlot *slot; const ranenv_mlp *const *nets; int copies; NetRole role;
     PolicyNet net; long long floats;      // the plan: copy 0's layout with the copies' stride (one copy: 0), floats of all copies
@@ -1273,9 +1278,9 @@ static int net_plan(ranenv_handle h, NetBind *binds, int n)
             PolicyNet ni{};
             floats = 0;
             if (const int rc = net_layout(h, m, b->role, ni, floats); rc != RANENV_OK) return rc;
-            bool same = m->n_hidden == m0->n_hidden && m->activation == m0->activation && m->input_layout == m0->input_layout;
+            bool same = m->n_hidden == m0->n_hidden && m->activation == m0->activation && m->input_layout == m0->input_layout && m->precision == m0->precision;
             for (int l = 0; same && l <= m->n_hidden + 1; l++) same = m->dims[l] == m0->dims[l];
-            if (!same) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d differs from net 0 in shape, activation or input layout", who, i);
+            if (!same) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d differs from net 0 in shape, activation, input layout or precision", who, i);
             if (i == 0) b->net = ni;
         }
         b->net.slice_stride = b->copies > 1 ? floats : 0;
@@ -2297,6 +2302,7 @@ int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, co
     if (!h->head.on || h->head_dist != RANENV_HEAD_DIST_GAUSS_TANH)
         return fail(h, RANENV_E_STATE, "SAC targets need a GAUSS_TANH head actor (ranenv_set_head_policy_network)");
     if (!h->sac_q2.on) return fail(h, RANENV_E_STATE, "no SAC critics bound (ranenv_set_sac_critics)");
+    if (h->head.net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "SAC targets need an f32 head actor: the bound one is a RANENV_NET_BF16 net");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     SacArgs a{};
     a.n = n; a.S = h->cfg.n_slices;

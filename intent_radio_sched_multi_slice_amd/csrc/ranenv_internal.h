@@ -171,18 +171,22 @@ struct AdvanceArgs {
 // 32 (padded rows of W and entries of b are 0, so padded activations are act(0) = 0 and padded inputs add nothing).
 enum { NET_MAX_LAYERS = 5, NET_MAX_WIDTH = 512, NET_ROWS = 32 };   // NET_ROWS: GEMM rows (envs / env x slice) per workgroup
 struct PolicyNet {
-    const float *w;                       // packed [layer]: W [np][kp] row-major, then b [np]
+    const float *w;                       // packed [layer]: W [np][kp] row-major, then b [np].  prec RANENV_NET_BF16: W is bf16 (RNE of
+                                          // the caller's f32, half the floats), b stays f32; w_off / b_off count floats either way
     long long w_off[NET_MAX_LAYERS], b_off[NET_MAX_LAYERS];
     int kp[NET_MAX_LAYERS], np[NET_MAX_LAYERS];
     int n_layers;                         // Linear layers: hidden ones + the output layer
     int act;                              // RANENV_ACT_*
     int layout;                           // RANENV_NET_IN_*
     int in_dim, out_dim;                  // unpadded
+    int prec;                             // RANENV_NET_F32 / RANENV_NET_BF16 (include/ranenv.h: the numeric contract of a bf16 net); sits in
+                                          // what was padding in front of slice_stride: no other member moved
     long long slice_stride;               // sliced intra launches (non-shared intra policies): floats between two consecutive slices' packed
                                           // copies, slice s's at w + s * slice_stride; 0 = one net for all slices.  Read by no other kernel
 };
 // One launch's inputs and action outputs.  A head policy's launch (RANENV_POLICY_HEAD_NETWORK: one row per env, scores into the same
 // buffer) has the bound head observation [B][10*S] as its obs_inter and reads no masks.
+static_assert(sizeof(PolicyNet) == 160, "PolicyNet: prec fills the padding in front of slice_stride");
 struct PolicyIO {
     int B, S, Us, W;                      // W = 2 * Us + 9
     int dist;                             // head: RANENV_HEAD_DIST_*
@@ -334,5 +338,7 @@ struct ReplaySampleArgs {
     float *obs, *action, *reward, *next_obs; uint8_t *done; long long *index;
 };
 void launch_replay_sample(hipStream_t, const ReplaySampleArgs &);
+// A bf16 net's layer: the caller's f32 W [N][K] -> bf16 [np][kp] at dst (round to nearest even), zeros in the padding
+void launch_pack_bf16(hipStream_t, const float *src, int N, int K, int np, int kp, unsigned short *dst);
 
 }  // namespace ranenv_dev

@@ -11,32 +11,56 @@
 // permutation on both operands.  The next W float4s are requested before the current step's MFMAs.
 // A third agent kind, "head" (RANENV_POLICY_HEAD_NETWORK: the SB3 actors of SchedTWC / SchedColORAN on the head observation), shares
 // everything but its distribution: a compile-time branch of the one body below.
+//
+// A net bound with RANENV_NET_BF16 (include/ranenv.h states the contract) takes the bf16 form of the same decomposition: its rows sit
+// in LDS as bf16 (rounded to nearest even on the way in, and again behind every hidden layer's f32 bias + activation), its weights
+// were rounded once at bind, and per 32 k a lane loads 16 bytes of W per block column (row c, k = 8 (l >> 4) .. + 7), reads 16 bytes
+// of X per block row and issues 4 v_mfma_f32_16x16x32_bf16 -- 1/8 of the f32 form's MFMAs, half its weight bytes and LDS.  The
+// output layer's rows are f32 in LDS: the epilogues do not know the difference.  Precision is per net and a compile-time parameter of
+// the body (PREC: bit 0 the actor, bit 1 the critic of a recording launch -- a fused collect launch may pair a bf16 actor with an f32
+// critic or the reverse): the kernels of f32 nets are the PREC = 0 instances and hold no bf16 code, launches with a bf16 net take the
+// ranenv_*_bf16_* kernels.
 #include "ranenv_numeric.hpp"
+#include <type_traits>
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // LDS row stride in floats for a width x (a multiple of 32): = 4 mod 64, so that the 16 rows x 4 k of an operand load fall into
 // distinct banks
 __host__ __device__ inline int net_ld(int x) { return x + ((x & 63) ? 36 : 4); }
 
+// ... and in bf16 elements for the rows of a bf16 net: 2 x + 32 bytes, an odd multiple of 32 mod 256 (2 x is a multiple of 64).  The
+// LDS serves a 16-byte read in groups of 16 lanes that hold 16 distinct rows c, eight of them at k chunk q and eight at q + 1 (each
+// eight distinct mod 8): row c then starts at 16-byte slot 2 (odd c) mod 16 of the 256-byte bank row -- the even slots once each for
+// one chunk, the odd slots for the other -- so the 16 rows x 16 bytes of an operand read fall into distinct banks
+__host__ __device__ inline int net_ld16(int x) { return x + 16; }
+
+// Floats per row of an LDS buffer that holds any layer's input rows (BF: of a bf16 net) and the output layer's (f32) rows
+template <bool BF = false>
 __host__ __device__ inline int net_ld_max(const PolicyNet &net)
 {
     int m = net_ld(net.np[net.n_layers - 1]);
-    for (int l = 0; l < net.n_layers; l++) m = net_ld(net.kp[l]) > m ? net_ld(net.kp[l]) : m;
+    for (int l = 0; l < net.n_layers; l++) {
+        const int ld = BF ? net_ld16(net.kp[l]) / 2 : net_ld(net.kp[l]);
+        m = ld > m ? ld : m;
+    }
     return m;
 }
 
-// The workgroup's 32 LDS rows of K0 columns at `dst` (stride net_ld(K0)) from at(row, column); columns [skip0, skip1) are left to the caller
-template <class F>
+// The workgroup's 32 LDS rows of K0 columns at `dst` (stride net_ld(K0)) from at(row, column); columns [skip0, skip1) are left to the caller.
+// BF: the rows of a bf16 net, rounded to nearest even (v_cvt_pk_bf16_f32), stride net_ld16(K0) bf16
+template <bool BF = false, class F>
 __device__ __forceinline__ void load_rows(int K0, int skip0, int skip1, float *dst, int tid, F at)
 {
-    const int ld0 = net_ld(K0);
+    const int ld0 = BF ? net_ld16(K0) : net_ld(K0);
     for (int i = tid; i < NET_ROWS * K0; i += 256) {
         const int r = i / K0, k = i - r * K0;
         if (k >= skip0 && k < skip1) continue;
-        dst[r * ld0 + k] = at(r, k);
+        if constexpr (BF) ((__bf16 *)dst)[r * ld0 + k] = (__bf16)at(r, k);
+        else dst[r * ld0 + k] = at(r, k);
     }
 }
 
@@ -72,12 +96,13 @@ __device__ __forceinline__ RowAt row_at(int kind, int e0, int S, int sl, int g)
 }
 
 // Observation rows of `net`'s input -> LDS (zeros beyond the input and beyond the launch's rows).  REC: the rows are written to the
-// record's slot on the way (the observation the TTI's action is computed from).  `sl`: a sliced launch's slice (see row_at).
-template <bool REC, bool SLICED = false>
+// record's slot on the way (the observation the TTI's action is computed from -- unrounded, also for a bf16 net (BF)).  `sl`: a sliced
+// launch's slice (see row_at).
+template <bool REC, bool SLICED = false, bool BF = false>
 __device__ __forceinline__ void net_load_rows(const PolicyNet &net, const PolicyIO &io, const PolicyRec &rec, int kind, int e0, int row0, int n_rows,
                                               float *cur, int tid, int sl = 0)
 {
-    load_rows(net.kp[0], 0, 0, cur, tid, [&](int r, int k) {
+    load_rows<BF>(net.kp[0], 0, 0, cur, tid, [&](int r, int k) {
         const int g = row0 + r;
         if (kind == 0) return dense_at(io.obs_inter, REC ? rec.obs_inter : nullptr, e0 + g, e0 + n_rows, 10 * io.S, net.in_dim, k);
         if (g >= n_rows || k >= net.in_dim) return 0.0f;
@@ -90,13 +115,35 @@ __device__ __forceinline__ void net_load_rows(const PolicyNet &net, const Policy
     });
 }
 
-// The layers of `net`, its packed copy at `wb`, on the 32 rows in `cur`; on return `cur` holds the output layer's rows (stride net_ld(np[last])).
+// A wave's 32 x 32 output tile `nt` of a bf16 layer: per 32 k one 16-byte load of W per block column (row c of the block, k = 8 q ..
+// + 7: contiguous in the packed copy), one 16-byte LDS read of X per block row, 4 MFMAs; the next W loads are requested ahead
+__device__ __forceinline__ void tile_bf16(f32x4 (&acc)[2][2], const __bf16 *W, const __bf16 *x, int K, int ldi, int nt, int q, int c)
+{
+    const bf16x8 *w0 = (const bf16x8 *)(W + (size_t)(nt * 32 + c) * K) + q;
+    const bf16x8 *w1 = (const bf16x8 *)(W + (size_t)(nt * 32 + 16 + c) * K) + q;
+    const __bf16 *x0 = x + c * ldi + 8 * q, *x1 = x + (16 + c) * ldi + 8 * q;
+    bf16x8 b0 = w0[0], b1 = w1[0];
+    for (int k0 = 0; k0 < K; k0 += 32) {
+        const int kn = (k0 + 32 < K ? k0 + 32 : k0) >> 3;
+        const bf16x8 nb0 = w0[kn], nb1 = w1[kn];
+        const bf16x8 a0 = *(const bf16x8 *)(x0 + k0), a1 = *(const bf16x8 *)(x1 + k0);
+        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[1][1], 0, 0, 0);
+        b0 = nb0; b1 = nb1;
+    }
+}
+
+// The layers of `net`, its packed copy at `wb`, on the 32 rows in `cur`; on return `cur` holds the output layer's rows (f32, stride
+// net_ld(np[last])).  BF: a bf16 net -- bf16 rows in `cur` (stride net_ld16) and between the layers, bf16 W.
+template <bool BF = false>
 __device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb, float *&cur, float *&nxt, int lane, int wave)
 {
     const int q = lane >> 4, c = lane & 15;
     for (int l = 0; l < net.n_layers; l++) {
-        const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N);
         const bool last = l == net.n_layers - 1;
+        const int K = net.kp[l], N = net.np[l], ldi = BF ? net_ld16(K) : net_ld(K), ldo = BF && !last ? net_ld16(N) : net_ld(N);
         const float *W = wb + net.w_off[l], *bias = wb + net.b_off[l];
         for (int nt = wave; nt < N / 32; nt += 4) {
             f32x4 acc[2][2];
@@ -104,6 +151,8 @@ __device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb
             for (int i = 0; i < 2; i++)
 #pragma unroll
                 for (int j = 0; j < 2; j++) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if constexpr (BF) tile_bf16(acc, (const __bf16 *)W, (const __bf16 *)cur, K, ldi, nt, q, c);
+            else {
             const float4 *w0 = (const float4 *)(W + (size_t)(nt * 32 + c) * K) + q;
             const float4 *w1 = (const float4 *)(W + (size_t)(nt * 32 + 16 + c) * K) + q;
             const float *x0 = cur + c * ldi + 4 * q, *x1 = cur + (16 + c) * ldi + 4 * q;
@@ -123,6 +172,7 @@ __device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb
                             acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mi][j], bv[ni][j], acc[mi][ni], 0, 0, 0);
                 b0 = nb0; b1 = nb1;
             }
+            }
             // C/D map of the 16x16 block: column = lane & 15, row = 4 (lane >> 4) + register
 #pragma unroll
             for (int mi = 0; mi < 2; mi++)
@@ -134,7 +184,8 @@ __device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb
                     for (int r = 0; r < 4; r++) {
                         float v = acc[mi][ni][r] + bb;
                         if (!last) v = net.act == RANENV_ACT_RELU ? fmaxf(v, 0.0f) : tanhf(v);
-                        nxt[(mi * 16 + q * 4 + r) * ldo + col] = v;
+                        if (BF && !last) ((__bf16 *)nxt)[(mi * 16 + q * 4 + r) * ldo + col] = (__bf16)v;
+                        else nxt[(mi * 16 + q * 4 + r) * ldo + col] = v;
                     }
                 }
         }
@@ -193,7 +244,8 @@ __device__ __forceinline__ int active_slices(const PolicyIO &io, int e)
 // and reads slice sl's copy of each net, net.w + sl * net.slice_stride (stride 0: one net for all slices).  Slice-major numbering: the
 // workgroups resident at one time mostly walk one slice's weights (measured against tile * S + sl: never slower, 7 % faster with [512] x 3
 // nets at B 16 384 S 5).
-template <bool HEAD, bool REC, bool SLICED = false>
+// PREC (compile time): bit 0 = `net` is a bf16 net, bit 1 = `vnet` is.
+template <bool HEAD, bool REC, bool SLICED = false, int PREC = 0>
 __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNet &vnet, const PolicyIO &io, const PolicyRec &rec, int kind, int e0,
                                             int n_rows, float *lds)
 {
@@ -201,8 +253,9 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
     const int S = io.S;
     const int tiles = SLICED ? (n_rows + NET_ROWS - 1) / NET_ROWS : 1, sl = SLICED ? (int)blockIdx.x / tiles : 0;
     const int row0 = (SLICED ? (int)blockIdx.x - sl * tiles : (int)blockIdx.x) * NET_ROWS;
-    int ldm = net_ld_max(net);
-    if (REC && vnet.n_layers > 0) { const int lv = net_ld_max(vnet); ldm = lv > ldm ? lv : ldm; }
+    constexpr bool BFA = (PREC & 1) != 0, BFV = (PREC & 2) != 0;
+    int ldm = net_ld_max<BFA>(net);
+    if (REC && vnet.n_layers > 0) { const int lv = net_ld_max<BFV>(vnet); ldm = lv > ldm ? lv : ldm; }
     float *cur = lds, *nxt = lds + NET_ROWS * ldm;
 
     if (!REC || !rec.critic_only) {
@@ -217,9 +270,9 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
                     rec.mask_intra[o] = io.mask_intra[o];
                 }
     }
-    net_load_rows<REC, SLICED>(net, io, rec, kind, e0, row0, n_rows, cur, tid, sl);
+    net_load_rows<REC, SLICED, BFA>(net, io, rec, kind, e0, row0, n_rows, cur, tid, sl);
     __syncthreads();
-    net_layers(net, SLICED ? net.w + sl * net.slice_stride : net.w, cur, nxt, lane, wave);
+    net_layers<BFA>(net, SLICED ? net.w + sl * net.slice_stride : net.w, cur, nxt, lane, wave);
 
     // ---- epilogue: actions ----------------------------------------------------------------------------------------------
     const int ld = net_ld(net.np[net.n_layers - 1]);
@@ -316,9 +369,9 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         __syncthreads();                               // (the epilogue read both buffers)
         cur = lds; nxt = lds + NET_ROWS * ldm;
         const PolicyRec none{};
-        net_load_rows<false, SLICED>(vnet, io, none, kind, e0, row0, n_rows, cur, tid, sl);
+        net_load_rows<false, SLICED, BFV>(vnet, io, none, kind, e0, row0, n_rows, cur, tid, sl);
         __syncthreads();
-        net_layers(vnet, SLICED ? vnet.w + sl * vnet.slice_stride : vnet.w, cur, nxt, lane, wave);
+        net_layers<BFV>(vnet, SLICED ? vnet.w + sl * vnet.slice_stride : vnet.w, cur, nxt, lane, wave);
         const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
         for (int r = tid; r < NET_ROWS; r += 256) {
             const int g = row0 + r;
@@ -373,6 +426,49 @@ __global__ void __launch_bounds__(256) ranenv_head_policy_collect_kernel(PolicyN
     policy_body<true, true>(net, vnet, io, rec, 0, e0, n_rows, lds);
 }
 
+// The same six with a bf16 net (PREC as in policy_body: 1 for the acting kernels, 1..3 for the recording ones)
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_bf16_kernel(PolicyNet net, PolicyIO io, int kind, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    policy_body<false, false, false, PREC>(net, net, io, PolicyRec{}, kind, e0, n_rows, lds);
+}
+
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_bf16_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, int kind, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    policy_body<false, true, false, PREC>(net, vnet, io, rec, kind, e0, n_rows, lds);
+}
+
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_bf16_sliced_kernel(PolicyNet net, PolicyIO io, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, false, true, PREC>(net, net, io, PolicyRec{}, 1, e0, n_envs, lds);
+}
+
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_bf16_sliced_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, true, true, PREC>(net, vnet, io, rec, 1, e0, n_envs, lds);
+}
+
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_head_policy_bf16_kernel(PolicyNet net, PolicyIO io, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    policy_body<true, false, false, PREC>(net, net, io, PolicyRec{}, 0, e0, n_rows, lds);
+}
+
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_head_policy_bf16_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, int e0, int n_rows)
+{
+    extern __shared__ float lds[];
+    policy_body<true, true, false, PREC>(net, vnet, io, rec, 0, e0, n_rows, lds);
+}
+
 // ---- SAC's soft Bellman target (ranenv_sac_targets; the arithmetic is spelled out in include/ranenv.h) -----------------------------
 constexpr unsigned SAC_TAG = 0x53414300u;               // "SAC\0": counter word c3 of the target's Philox draws, + position
 
@@ -390,7 +486,7 @@ __device__ __forceinline__ void sac_critic_rows(const PolicyNet &q, const SacArg
 }
 
 // A workgroup owns 32 rows: the actor on next_obs, the squashed-Gaussian epilogue (a', log pi), then the two critics on [next_obs | a']
-// through the same two LDS buffers, then the target.  S <= 16: a thread owns at most two (row, position) pairs.
+// through the same two LDS buffers, then the target.  f32 nets only (the host refuses bf16 ones here).  S <= 16: a thread owns at most two (row, position) pairs.
 __global__ void __launch_bounds__(256) ranenv_sac_target_kernel(PolicyNet actor, PolicyNet q1, PolicyNet q2, SacArgs a)
 {
     extern __shared__ float lds[];
@@ -478,14 +574,27 @@ hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, c
     const bool sl = kind == 1 && (a.slice_stride != 0 || (vp && vp->slice_stride != 0));
     const int rows = kind == 1 && !sl ? n_envs * io.S : n_envs;
     const dim3 grid((unsigned)((rows + NET_ROWS - 1) / NET_ROWS) * (sl ? (unsigned)io.S : 1u));
+    const bool bfa = a.prec == RANENV_NET_BF16;
     if (!rec) {
-        if (sl) return launch_kernel<ranenv_policy_sliced_kernel>(grid, policy_lds_bytes(a), s, a, io, e0, rows);
-        if (head) return launch_kernel<ranenv_head_policy_kernel>(grid, policy_lds_bytes(a), s, a, io, e0, rows);
-        return launch_kernel<ranenv_policy_kernel>(grid, policy_lds_bytes(a), s, a, io, kind, e0, rows);
+        const size_t lds = policy_lds_bytes(a);
+        if (sl) return bfa ? launch_kernel<ranenv_policy_bf16_sliced_kernel<1>>(grid, lds, s, a, io, e0, rows) : launch_kernel<ranenv_policy_sliced_kernel>(grid, lds, s, a, io, e0, rows);
+        if (head) return bfa ? launch_kernel<ranenv_head_policy_bf16_kernel<1>>(grid, lds, s, a, io, e0, rows) : launch_kernel<ranenv_head_policy_kernel>(grid, lds, s, a, io, e0, rows);
+        return bfa ? launch_kernel<ranenv_policy_bf16_kernel<1>>(grid, lds, s, a, io, kind, e0, rows) : launch_kernel<ranenv_policy_kernel>(grid, lds, s, a, io, kind, e0, rows);
     }
     const PolicyNet none{};               // (n_layers 0: no critic)
     auto launch = [&](const PolicyNet &v, const PolicyRec &rc) {
         const size_t x = policy_lds_bytes(a), y = v.n_layers > 0 ? policy_lds_bytes(v) : 0, lds = x > y ? x : y;
+        auto as = [&](auto prec) {        // the recording kernels' PREC instance
+            constexpr int P = decltype(prec)::value;
+            if (sl) return launch_kernel<ranenv_policy_bf16_sliced_collect_kernel<P>>(grid, lds, s, a, v, io, rc, e0, rows);
+            if (head) return launch_kernel<ranenv_head_policy_bf16_collect_kernel<P>>(grid, lds, s, a, v, io, rc, e0, rows);
+            return launch_kernel<ranenv_policy_bf16_collect_kernel<P>>(grid, lds, s, a, v, io, rc, kind, e0, rows);
+        };
+        switch ((bfa ? 1 : 0) | (v.n_layers > 0 && v.prec == RANENV_NET_BF16 ? 2 : 0)) {
+        case 1: return as(std::integral_constant<int, 1>{});
+        case 2: return as(std::integral_constant<int, 2>{});
+        case 3: return as(std::integral_constant<int, 3>{});
+        }
         if (sl) return launch_kernel<ranenv_policy_sliced_collect_kernel>(grid, lds, s, a, v, io, rc, e0, rows);
         if (head) return launch_kernel<ranenv_head_policy_collect_kernel>(grid, lds, s, a, v, io, rc, e0, rows);
         return launch_kernel<ranenv_policy_collect_kernel>(grid, lds, s, a, v, io, rc, kind, e0, rows);
@@ -501,7 +610,10 @@ hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, c
 
 namespace ranenv_dev {
 
-size_t policy_lds_bytes(const PolicyNet &net) { return sizeof(float) * 2 * NET_ROWS * (size_t)net_ld_max(net); }
+size_t policy_lds_bytes(const PolicyNet &net)
+{
+    return sizeof(float) * 2 * NET_ROWS * (size_t)(net.prec == RANENV_NET_BF16 ? net_ld_max<true>(net) : net_ld_max<false>(net));
+}
 
 hipError_t launch_policy(hipStream_t s, const PolicyNets &n, const PolicyIO &io, const PolicyRec *rec, int e0, int n_envs)
 {
