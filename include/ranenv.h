@@ -298,6 +298,64 @@ int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **de
 int ranenv_set_intra_policy_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *actors, void *stream);
 int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *critics, void *stream);
 
+/* Populations: one net set per env group (the reference's fine-tuned agents, simu.py:427-443 -- one agent per scenario -- and its
+ * hyper-parameter search, agents/ray_agent.py:70-146,604-612: trials ranked by the episodes each played with its own weights), in
+ * one batch.
+ *
+ *   A population is n_members members, 1..64.  Member m owns the contiguous envs [first_env[m], first_env[m + 1]) with
+ *     0 = first_env[0] < first_env[1] < ... < first_env[n_members] = batch, and its own copy of every population net: inter actor,
+ *     intra actor, inter critic, intra critic.  Under RANENV_POLICY_NETWORK the policy launches of ranenv_step / _step_range /
+ *     _step_part, ranenv_rollout and ranenv_collect (its critics-only pass and the split critic launches included) act on env e with
+ *     the weights of the member that owns e.  Still one launch per TTI, partition and agent kind: member m contributes the rows of its
+ *     envs inside the launch's range -- one per env (inter), the contiguous env x S rows (intra) -- in ceil(rows / 32) workgroups of
+ *     its own, numbered member-major; the rows behind a member's last one are dead rows: they read and write nothing.  Everything
+ *     behind the policy (step kernels, auto-reset, metrics, traces, the record's layout) is as without a population.
+ *   ranenv_set_population: control plane; host_first_env [n_members + 1] is a host array, copied at the call.  n_members == 0 with
+ *     NULL removes the grouping and unbinds the population's nets.  Anything else that is no such table is RANENV_E_INVALID; a table
+ *     that differs from the current one while population nets are bound is RANENV_E_STATE (unbind or rebind the nets first).
+ *     ranenv_get_population reads it back (n_members 0: none; host_first_env [65] or NULL).
+ *   The table travels BY VALUE in the arguments of every population launch: a launch -- and a captured graph's node -- keeps the
+ *     grouping it was enqueued under, whatever ranenv_set_population does afterwards, as it keeps its weight buffer's address.
+ *   ranenv_set_population_policy / _value: the population forms of ranenv_set_policy_network / ranenv_set_value_network -- inter[m] /
+ *     intra[m] (the intra array may be NULL as the intra net may) are member m's.  n must equal the member count (RANENV_E_INVALID; no
+ *     population set: RANENV_E_STATE).  Every net is validated as its one-net counterpart validates it, and the n nets of a role must
+ *     agree in n_hidden, dims, activation, input_layout and precision (RANENV_E_INVALID); RANENV_NET_F32 and RANENV_NET_BF16 are both
+ *     accepted, per role.  Every validation error precedes every device call; the handle changes on success only.  The copies of a
+ *     role sit at equal stride in a packed buffer of the role's own (an outgrown buffer lives until ranenv_destroy).
+ *   ranenv_set_population_member: member's copies rebound IN PLACE on `stream`, NULL = that role stays as it is -- what a learner
+ *     calls when one trial finishes an update or PBT copies a winner over a loser.  A role without bound population nets is
+ *     RANENV_E_STATE, a net that differs from the bound set in shape, activation, input layout or precision RANENV_E_INVALID, both in
+ *     front of every device call.  No other member's weights are touched.
+ *   Who says what the policy is: the last policy-binding call, as above.  ranenv_set_population_policy unbinds the one inter net, a
+ *     shared intra net and both per-slice sets; a later ranenv_set_policy_network unbinds the population's actors AND critics (the
+ *     grouping stays).  ranenv_set_population_value unbinds the one-net critics and the per-slice critics, a later
+ *     ranenv_set_value_network the population's critics.  Population actors with one critic pair for all members, and one actor pair
+ *     with population critics (bound in that order), are both valid.  Nets per slice inside a population are not supported: while any
+ *     population net is bound, ranenv_set_intra_policy_networks / _intra_value_networks with nets return RANENV_E_STATE.
+ *   The head policies (ranenv_set_head_policy_network ...) and the SAC path (ranenv_set_sac_critics, ranenv_sac_targets) do not read
+ *     the population: one net for the whole batch.
+ *   Arithmetic, noise and record are the one-net path's: the draws are the function of (seed; env id, episode, step, tag + slice)
+ *     above, one seed for all members, and a member's rows depend on no other member -- n copies of one net give bit for bit what that
+ *     net gives alone, and member m's envs get bit for bit what a handle bound to member m's nets alone gives them.
+ *   ranenv_population_tiles: the geometry itself, a pure host function (no handle, no device) computed by the very function the
+ *     kernel and the launch use: for a launch over envs [e0, e0 + n_envs) with rows_per_env rows per env (1: inter, S: intra) the
+ *     workgroups' member, first row (relative to the launch's first row) and live row count (1..32), in launch order, and their
+ *     number.  The out arrays hold ceil(n_envs * rows_per_env / 32) + n_members entries at most; each may be NULL.  The table is
+ *     checked as ranenv_set_population checks it, with first_env[n_members] as the batch.
+ *   Figures (DESIGN.md 4.p "Populations"; tools/kernel_resources.py, tools/population_probe.py on one MI355X): the population kernels
+ *     use 52-68 VGPRs, 0 AGPRs, no scratch; rollout(200) / collect(200) under 8 and 64 copies of one net set take 1.02-1.04x the time
+ *     under the one set with [64, 64] nets and 1.11-1.13x (8) / 1.35-1.40x (64) with [512] x 3 nets, whose copies leave L2; the one-net
+ *     kernels and their results are unchanged. */
+int ranenv_set_population(ranenv_handle h, int32_t n_members, const int32_t *host_first_env);
+int ranenv_get_population(ranenv_handle h, int32_t *n_members, int32_t *host_first_env);
+int ranenv_set_population_policy(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
+                                 uint64_t seed, void *stream);
+int ranenv_set_population_value(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream);
+int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_mlp *inter, const ranenv_mlp *intra, const ranenv_mlp *v_inter,
+                                 const ranenv_mlp *v_intra, void *stream);
+int ranenv_population_tiles(int32_t n_members, const int32_t *first_env, int32_t e0, int32_t n_envs, int32_t rows_per_env, int32_t *out_member,
+                            int32_t *out_row0, int32_t *out_rows, int32_t *n_tiles);
+
 /* CommunicationEnv.reset for the envs with env_mask[b] != 0 (NULL = all): fresh buffers,
  * step 0, observation of the zero raw state with the episode's first SE tile.
  * Outputs may be NULL. dev_se_tiles: [B][U*R] explicit tiles or NULL to use the pool. */

@@ -192,7 +192,14 @@ FUNCTIONS = {
     "ranenv_bind_trace": (C.c_int, [_P, C.POINTER(Trace), _P]),
     "ranenv_get_trace_counts": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "ranenv_reset_trace": (C.c_int, [_P, _P]),
+    "ranenv_set_population": (C.c_int, [_P, _I32, C.POINTER(C.c_int32)]),
+    "ranenv_get_population": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ranenv_set_population_policy": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), C.POINTER(C.POINTER(Mlp)), _I32, C.c_uint64, _P]),
+    "ranenv_set_population_value": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), C.POINTER(C.POINTER(Mlp)), _P]),
+    "ranenv_set_population_member": (C.c_int, [_P, _I32] + [C.POINTER(Mlp)] * 4 + [_P]),
+    "ranenv_population_tiles": (C.c_int, [_I32, C.POINTER(C.c_int32), _I32, _I32, _I32] + [C.POINTER(C.c_int32)] * 4),
 }
+POPULATION_MAX = 64
 EXPORTS = tuple(FUNCTIONS)
 
 

@@ -145,6 +145,27 @@ def per_slice_nets(intra):
     return None
 
 
+def population_first(batch: int, first_env=None, sizes=None) -> np.ndarray:
+    """A population's table ``first_env`` [G + 1] (member m owns envs ``first_env[m] .. first_env[m + 1] - 1``) from itself or from the
+    members' ``sizes``; ValueError unless 1..64 members tile ``[0, batch)`` in order, none of them empty."""
+    if (first_env is None) == (sizes is None):
+        raise ValueError("give first_env or sizes")
+    first = np.asarray(first_env, dtype=np.int64) if sizes is None else np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))])
+    if first.ndim != 1 or not 2 <= first.size <= _lib.POPULATION_MAX + 1:
+        raise ValueError(f"a population has 1..{_lib.POPULATION_MAX} members")
+    if first[0] != 0 or first[-1] != batch or np.any(np.diff(first) <= 0):
+        raise ValueError(f"first_env must rise strictly from 0 to the batch, {batch}: {first.tolist()}")
+    return first.astype(np.int32)
+
+
+def population_means(result: Dict[str, np.ndarray], first_env) -> Dict[str, np.ndarray]:
+    """Per-member means of what ``evaluate()`` returns: every float metric [B, n_episodes, ...] -> [G, ...], the mean over the
+    member's envs and episodes (``np.mean`` of the member's block); integer entries ("scenario") are left out."""
+    first = np.asarray(first_env)
+    return {name: np.stack([np.mean(x[lo:hi], axis=(0, 1)) for lo, hi in zip(first[:-1], first[1:])])
+            for name, x in result.items() if np.issubdtype(np.asarray(x).dtype, np.floating)}
+
+
 class BatchedRanEnv:
     def __init__(self, batch: int, n_slices: int, n_ues: int, n_rbs: int, rbs_per_rbg: int = 1,
                  max_ues_slice: Optional[int] = None, n_scenarios: int = 1, bandwidth_hz: float = 100e6,
@@ -201,6 +222,7 @@ class BatchedRanEnv:
         self.se_mode = "stream"
         self._ranges = None          # set_ranges(): [(lo, hi)] for step_async / step_wait
         self._intra_layout = None    # input layout of the intra actor bound by set_policy_network (None: none)
+        self._population = None      # set_population's first_env table [G + 1] (None: no grouping)
         self.head_observation = "head"      # what the head nets read (set_head_policy_network): "head" = head_obs, "inter" = obs_inter
         # (the views are handed out once, here: ranenv_get_views ends the library's host shadow of the step counters -- the views are writable --,
         # and a first views() call in the middle of an auto-reset loop would switch the shortcut of enable_autoreset off until the next full reset)
@@ -436,8 +458,23 @@ class BatchedRanEnv:
         ``precision`` "bf16": every net of this call runs on the bf16 matrix cores -- weights rounded once at bind, input and hidden
         activations rounded to bf16, float32 accumulation, biases, activations and outputs (the contract is in include/ranenv.h;
         ``adapters._mlp_forward(..., precision="bf16")`` restates it).  Results then differ from the float32 nets' in the third or
-        fourth digit; "f32", the default, leaves them as they were."""
+        fourth digit; "f32", the default, leaves them as they were.
+        ``inter`` may be a list of G nets of one shape under ``set_population`` -- member m's envs act on ``inter[m]`` -- and ``intra``
+        then None or a list of G nets (ranenv_set_population_policy); a list of S intra nets beside ONE inter net keeps its per-slice
+        meaning."""
         in_inter, in_intra = self.net_input_dims(intra_input)
+        members = per_slice_nets(inter)
+        if members is not None:                # a population: inter[m] (and intra[m]) are member m's
+            G = self._population_size(len(members))
+            lists = [self._net_list(members, activation, in_inter, 2 * self.S, NET_IN_OBS, precision, count=G, per="member"),
+                     self._member_list(intra, G, activation, in_intra, 3, NET_INPUTS[intra_input], precision)]
+            self._set_population_nets("ranenv_set_population_policy", "population_policy", G, lists, 1 if stochastic else 0, int(seed) & (2 ** 64 - 1))
+            for key in ("policy_net", "intra_policy_nets"):
+                self._keep.pop(key, None)
+            self._intra_layout = None if intra is None else NET_INPUTS[intra_input]
+            self._policy_views = None
+            self.set_policy(POLICY_NETWORK, self.fixed_intra if fixed_intra is None else fixed_intra)
+            return
         per_slice = self._net_list(per_slice_nets(intra), activation, in_intra, 3, NET_INPUTS[intra_input], precision)
         self._set_nets("policy_net", "ranenv_set_policy_network", [(inter, activation, in_inter, 2 * self.S, NET_IN_OBS),
                        (None if per_slice else intra, activation, in_intra, 3, NET_INPUTS[intra_input])], 1 if stochastic else 0,
@@ -476,13 +513,16 @@ class BatchedRanEnv:
             self._check(getattr(self._lib, call)(self._h, *structs, *args, self._stream()), call)
         self._keep[key] = keep                 # (the library copies on the current stream; keep the sources until it has)
 
-    def _net_list(self, nets, activation, in_dim, out_dim, layout, precision="f32"):
+    def _net_list(self, nets, activation, in_dim, out_dim, layout, precision="f32", count=None, per="slice"):
         """A list of S nets as the argument of a ``ranenv_set_intra_*_networks`` call: ``(array of ranenv_mlp pointers, what to
         keep alive)``, or None for None.  Raises ValueError -- before any library call: a per-slice bind is two of
-        them, and the first one drops the previous set -- unless there are S valid nets of one shape and activation."""
+        them, and the first one drops the previous set -- unless there are S valid nets of one shape and activation.
+        ``count`` / ``per``: a population's list instead, one net per member."""
         if nets is None:
             return None
-        if len(nets) != self.S:
+        if per == "member" and len(nets) != count:
+            raise ValueError(f"{len(nets)} nets given: one per member is {count}")
+        if per == "slice" and len(nets) != self.S:
             raise ValueError(f"{len(nets)} intra nets given: one per slice is {self.S}")
         keep, structs, first = [], [], None
         for i, net in enumerate(nets):
@@ -490,8 +530,8 @@ class BatchedRanEnv:
             shape = ([tuple(w.shape) for w, _ in layers], act)
             first = shape if first is None else first
             if shape != first:
-                raise ValueError(f"intra net {i} ({shape[0]}, {shape[1]}) differs from net 0 ({first[0]}, {first[1]}): "
-                                 "the nets per slice have one shape and one activation")
+                raise ValueError(f"{'intra ' if per == 'slice' else ''}net {i} ({shape[0]}, {shape[1]}) differs from net 0 ({first[0]}, {first[1]}): "
+                                 f"the nets per {per} have one shape and one activation")
             structs.append(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep, precision))
         return (C.POINTER(_lib.Mlp) * len(structs))(*[C.pointer(m) for m in structs]), keep + structs
 
@@ -503,6 +543,91 @@ class BatchedRanEnv:
             self._check(getattr(self._lib, call)(self._h, self.S, net_list[0], self._stream()), call)
         self._keep[key] = net_list[1]
 
+    # ---- populations (ranenv_set_population ...; include/ranenv.h "Populations") ----------------------------------------------------
+    def set_population(self, first_env=None, sizes=None) -> None:
+        """Group the batch into G <= 64 members of contiguous envs: member m owns ``first_env[m] .. first_env[m + 1] - 1``
+        (``first_env`` [G + 1], from 0 to B), or give the members' ``sizes``.  ``set_policy_network`` / ``set_value_network`` then take
+        lists of G nets, and every policy launch acts on an env with its member's weights.  Neither argument: remove the grouping
+        (and the population's nets).  The grouping cannot change while population nets are bound."""
+        if first_env is None and sizes is None:
+            self._check(self._lib.ranenv_set_population(self._h, 0, None), "ranenv_set_population")
+            self._population = None
+            for key in ("population_policy", "population_value"):
+                self._keep.pop(key, None)
+            return
+        first = population_first(self.B, first_env, sizes)
+        self._check(self._lib.ranenv_set_population(self._h, len(first) - 1, first.ctypes.data_as(C.POINTER(C.c_int32))), "ranenv_set_population")
+        self._population = first
+
+    def population(self) -> Optional[np.ndarray]:
+        """The grouping as the library holds it: ``first_env`` [G + 1], or None."""
+        n, first = C.c_int32(), (C.c_int32 * (_lib.POPULATION_MAX + 1))()
+        self._check(self._lib.ranenv_get_population(self._h, C.byref(n), first), "ranenv_get_population")
+        return np.array(first[:n.value + 1], dtype=np.int32) if n.value > 0 else None
+
+    def population_slices(self):
+        """The G Python slices of the members' envs: ``rec[k][:, sl]`` of a ``collect()`` record, ``x[sl]`` of a [B, ...] tensor --
+        views, members being contiguous."""
+        first = self._population_first()
+        return [slice(int(lo), int(hi)) for lo, hi in zip(first[:-1], first[1:])]
+
+    def _population_first(self) -> np.ndarray:
+        if getattr(self, "_population", None) is None:
+            raise ValueError("no population set (set_population)")
+        return self._population
+
+    def _population_size(self, n_given: int) -> int:
+        G = len(self._population_first()) - 1
+        if n_given != G:
+            raise ValueError(f"{n_given} nets given: one per member is {G}")
+        return G
+
+    def _member_list(self, nets, G, activation, in_dim, out_dim, layout, precision):
+        """The intra argument beside a list of G inter nets: None, or a list of G nets"""
+        if nets is None:
+            return None
+        as_list = per_slice_nets(nets)
+        if as_list is None:
+            raise ValueError(f"beside a list of inter nets, intra is None or a list of nets, one per member ({G})")
+        return self._net_list(as_list, activation, in_dim, out_dim, layout, precision, count=G, per="member")
+
+    def _set_population_nets(self, call: str, key: str, G: int, lists, *args):
+        with torch.cuda.device(self.device):
+            self._check(getattr(self._lib, call)(self._h, G, lists[0][0], lists[1][0] if lists[1] else None, *args, self._stream()), call)
+        self._keep[key] = [x[1] for x in lists if x]
+
+    def set_population_member(self, m: int, inter=None, intra=None, v_inter=None, v_intra=None, activation: Optional[str] = None,
+                              precision: Optional[Dict[str, str]] = None) -> None:
+        """Rebind member ``m``'s copies in place (ranenv_set_population_member): the nets given replace that member's inter actor /
+        intra actor / inter critic / intra critic, None leaves a role as it is; shapes as bound.  ``precision``: {"policy": ...,
+        "value": ...} as given to the binding calls (default "f32" each).  No other member is touched."""
+        G = len(self._population_first()) - 1
+        if not 0 <= int(m) < G:
+            raise ValueError(f"member {m} outside the population's {G}")
+        precision = precision or {}
+        layout = NET_IN_OBS if self._intra_layout is None else self._intra_layout
+        in_intra = self.W + (self.Us if layout == NET_IN_MASK_OBS else 0)
+        keep, structs = [], []
+        for net, in_dim, out_dim, lay, prec in ((inter, 10 * self.S, 2 * self.S, NET_IN_OBS, "policy"), (intra, in_intra, 3, layout, "policy"),
+                                                (v_inter, 10 * self.S, 1, NET_IN_OBS, "value"), (v_intra, in_intra, 1, layout, "value")):
+            if net is None:
+                structs.append(None)
+                continue
+            layers, act = policy_net_layers(net, activation, in_dim, out_dim)
+            structs.append(C.byref(self._mlp_struct(layers, act, lay, keep, precision.get(prec, "f32"))))
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_set_population_member(self._h, int(m), *structs, self._stream()), "ranenv_set_population_member")
+        self._keep.setdefault("population_members", {})[int(m)] = keep
+
+    def evaluate_population(self, n_episodes: int, max_steps=None, per_slice: bool = False) -> Dict[str, np.ndarray]:
+        """``evaluate()`` and, per member, the mean of every metric over the member's envs and episodes: {metric: float64 [G]}
+        (``"slice"``: [G, S, 10]), plus ``"per_env"``, what ``evaluate()`` returned."""
+        first = self._population_first()
+        res = self.evaluate(n_episodes, max_steps=max_steps, per_slice=per_slice)
+        out = population_means(res, first)
+        out["per_env"] = res
+        return out
+
     def set_value_network(self, inter, intra=None, activation: Optional[str] = None, precision: str = "f32"):
         """Bind the critics that ``collect()`` evaluates beside the actors (ranenv_set_value_network): ``inter`` maps the
         inter-slice observation [10*S] to one value, ``intra`` (None = no intra critic: those columns of ``vf`` are 0) the
@@ -510,8 +635,22 @@ class BatchedRanEnv:
         ``policy_net_layers``.  Bind the actors first when there is an intra critic; re-binding either pair leaves the other.
         ``intra`` may be a list of S critics of one shape, ``intra[s]`` for slice index s (ranenv_set_intra_value_networks), with
         shared or per-slice intra actors alike.  ``precision`` as for ``set_policy_network``, for every critic of this call; the
-        critics' precision is their own -- bf16 critics beside f32 actors and the reverse are both fine."""
+        critics' precision is their own -- bf16 critics beside f32 actors and the reverse are both fine.
+        Under ``set_population``, ``inter`` may be a list of G critics (and ``intra`` then None or a list of G), member m's
+        (ranenv_set_population_value); population critics beside one actor pair and the reverse are both fine."""
         layout = lambda layers: NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS  # noqa: E731
+        members = per_slice_nets(inter)
+        if members is not None:                # a population's critics: inter[m] (and intra[m]) are member m's
+            G = self._population_size(len(members))
+            lists = [self._net_list(members, activation, 10 * self.S, 1, NET_IN_OBS, precision, count=G, per="member"),
+                     self._member_list(intra, G, activation, None, 1, layout, precision)]
+            if lists[1] is not None and self._intra_layout != lists[1][0][0].contents.input_layout:
+                raise ValueError("intra critics read the intra actor's input row: " + (
+                    "no intra actor is bound (set_policy_network)" if self._intra_layout is None else "its intra_input is the other layout"))
+            self._set_population_nets("ranenv_set_population_value", "population_value", G, lists)
+            for key in ("value_net", "intra_value_nets"):
+                self._keep.pop(key, None)
+            return
         per_slice = self._net_list(per_slice_nets(intra), activation, None, 1, layout, precision)
         if per_slice is not None and self._intra_layout != per_slice[0][0].contents.input_layout:
             raise ValueError("intra critics per slice read the intra actor's input row: " + (

@@ -103,14 +103,36 @@ struct ranenv {
     long long prof_env_ttis = 0;   // env-TTIs covered by the launches timed since ranenv_profile_begin
     // One bound net: its layout, and its packed weights in a buffer of the slot's own (cap floats; an outgrown buffer stays allocated
     // until ranenv_destroy).  A net per slice is S copies of one layout at net.slice_stride in that buffer, `net` describing slice 0's.
-    struct NetSlot { PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; };
+    // A population's net (pop_*) is G copies at member_stride, with the copies' unpadded widths in dims for ranenv_set_population_member.
+    struct NetSlot { PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; long long member_stride = 0; int32_t dims[6] = {}; };
     // ranenv_set_policy_network (actor, actor_intra: the shared intra net) and ranenv_set_intra_policy_networks (actor_ps: one intra net
     // per slice, standing where the shared one stands while on); the same three for their critics (ranenv_set_value_network,
     // ranenv_set_intra_value_networks); ranenv_set_head_policy_network / _head_value_network: SchedTWC / SchedColORAN's actor and critic
     // on the head observation; ranenv_set_sac_critics
     NetSlot actor, actor_intra, actor_ps, value, value_intra, value_ps, head, head_value, sac_q1, sac_q2;
-    const PolicyNet *intra_actor() const { return actor_ps.on ? &actor_ps.net : (actor_intra.on ? &actor_intra.net : nullptr); }
-    const PolicyNet *intra_critic() const { return value_ps.on ? &value_ps.net : (value_intra.on ? &value_intra.net : nullptr); }
+    // ranenv_set_population: the grouping (pop.n = 0: none), and the members' copies of the four IBSched nets (ranenv_set_population_policy /
+    // _value), each standing where its one-net slot stands while on -- the binding calls keep at most one of the two on per role
+    PopMap pop{};
+    NetSlot pop_actor, pop_intra, pop_value, pop_vintra;
+    bool pop_bound() const { return pop_actor.on || pop_intra.on || pop_value.on || pop_vintra.on; }
+    void pop_unbind() { pop_actor.on = pop_intra.on = pop_value.on = pop_vintra.on = false; }
+    bool have_actor() const { return actor.on || pop_actor.on; }
+    bool have_critic() const { return value.on || pop_value.on; }
+    const PolicyNet *inter_actor() const { return pop_actor.on ? &pop_actor.net : &actor.net; }
+    const PolicyNet *inter_critic() const { return pop_value.on ? &pop_value.net : &value.net; }
+    const PolicyNet *intra_actor() const { return pop_intra.on ? &pop_intra.net : (actor_ps.on ? &actor_ps.net : (actor_intra.on ? &actor_intra.net : nullptr)); }
+    const PolicyNet *intra_critic() const { return pop_vintra.on ? &pop_vintra.net : (value_ps.on ? &value_ps.net : (value_intra.on ? &value_intra.net : nullptr)); }
+    // The IBSched nets of a TTI's launches as they are bound (critics: a recording's), with the population map where a member's copy acts
+    PolicyNets ibsched_nets(bool critics) const
+    {
+        PolicyNets n{false, inter_actor(), intra_actor(), critics && have_critic() ? inter_critic() : nullptr, critics ? intra_critic() : nullptr};
+        if (pop_bound()) {
+            n.pop = &pop;
+            n.stride[0] = pop_actor.on ? pop_actor.member_stride : 0; n.stride[1] = pop_intra.on ? pop_intra.member_stride : 0;
+            n.stride[2] = pop_value.on ? pop_value.member_stride : 0; n.stride[3] = pop_vintra.on ? pop_vintra.member_stride : 0;
+        }
+        return n;
+    }
     // ... and the actions the step reads under RANENV_POLICY_NETWORK / _HEAD_NETWORK (shared: one policy acts at a time)
     int net_stochastic = 0; unsigned long long net_seed = 0;
     double *d_net_scores = nullptr; uint8_t *d_net_intra = nullptr;
@@ -1265,7 +1287,9 @@ static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, 
 // one shape, activation, input layout and precision.  No HIP call, nothing of the handle changes.
 struct NetBind {
     ranenv::NetSlot *slot; const ranenv_mlp *const *nets; int copies; NetRole role;
+    bool members = false;                 // the copies are a population's, one per member (else one per slice)
     PolicyNet net; long long floats;      // the plan: copy 0's layout with the copies' stride (one copy: 0), floats of all copies
+    long long stride;                     // ... floats between two copies
 };
 static int net_plan(ranenv_handle h, NetBind *binds, int n)
 {
@@ -1274,16 +1298,18 @@ static int net_plan(ranenv_handle h, NetBind *binds, int n)
         long long floats = 0;
         for (int i = 0; i < b->copies; i++) {
             const ranenv_mlp *m = b->nets[i], *m0 = b->nets[0];
-            if (!m) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d is null", who, i);
+            const char *per = b->members ? "member" : "slice";
+            if (!m) return fail(h, RANENV_E_INVALID, "%s nets per %s: net %d is null", who, per, i);
             PolicyNet ni{};
             floats = 0;
             if (const int rc = net_layout(h, m, b->role, ni, floats); rc != RANENV_OK) return rc;
             bool same = m->n_hidden == m0->n_hidden && m->activation == m0->activation && m->input_layout == m0->input_layout && m->precision == m0->precision;
             for (int l = 0; same && l <= m->n_hidden + 1; l++) same = m->dims[l] == m0->dims[l];
-            if (!same) return fail(h, RANENV_E_INVALID, "%s nets per slice: net %d differs from net 0 in shape, activation, input layout or precision", who, i);
+            if (!same) return fail(h, RANENV_E_INVALID, "%s nets per %s: net %d differs from net 0 in shape, activation, input layout or precision", who, per, i);
             if (i == 0) b->net = ni;
         }
-        b->net.slice_stride = b->copies > 1 ? floats : 0;
+        b->stride = floats;
+        b->net.slice_stride = b->copies > 1 && !b->members ? floats : 0;
         b->floats = floats * b->copies;
     }
     return RANENV_OK;
@@ -1305,8 +1331,11 @@ static int net_commit(ranenv_handle h, NetBind *binds, int n, hipStream_t s)
     }
     for (NetBind *b = binds; b < binds + n; b++)
         for (int i = 0; i < b->copies; i++)
-            if (const int rc = net_copy(h, b->nets[i], b->net, s, b->slot->w + (size_t)i * (size_t)b->net.slice_stride); rc != RANENV_OK) return rc;
-    for (NetBind *b = binds; b < binds + n; b++) { b->slot->net = b->net; b->slot->on = true; }
+            if (const int rc = net_copy(h, b->nets[i], b->net, s, b->slot->w + (size_t)i * (size_t)b->stride); rc != RANENV_OK) return rc;
+    for (NetBind *b = binds; b < binds + n; b++) {
+        b->slot->net = b->net; b->slot->on = true; b->slot->member_stride = b->members ? b->stride : 0;
+        for (int l = 0; l < 6; l++) b->slot->dims[l] = b->nets[0]->dims[l];
+    }
     return RANENV_OK;
 }
 
@@ -1324,7 +1353,7 @@ static int net_use(ranenv_handle h, KP &kp)
         return 1;
     }
     if (kp.scores || h->kp.policy != RANENV_POLICY_NETWORK) return 0;
-    if (!h->actor.on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!h->have_actor()) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
     if (!kp.obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
     if (h->intra_actor() && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
     kp.scores = h->d_net_scores;
@@ -1362,7 +1391,7 @@ static PolicyIO net_io(ranenv_handle h, const KP &kp)
 static hipError_t net_launch(ranenv_handle h, const KP &kp, int e0, int n, hipStream_t s)
 {
     const bool head = head_policy(h);
-    const PolicyNets nets{head, head ? &h->head.net : &h->actor.net, head ? nullptr : h->intra_actor(), nullptr, nullptr};
+    const PolicyNets nets = head ? PolicyNets{true, &h->head.net, nullptr, nullptr, nullptr} : h->ibsched_nets(false);
     return launch_policy(s, nets, net_io(h, kp), nullptr, e0, n);
 }
 
@@ -1389,6 +1418,7 @@ int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ra
     h->net_stochastic = stochastic != 0; h->net_seed = seed;
     h->actor_intra.on = intra != nullptr;         // (`intra`, NULL included, says what the intra policy is now)
     h->actor_ps.on = h->value_ps.on = false;
+    h->pop_unbind();                              // (... and that no population acts or values: the grouping stays)
     return RANENV_OK;
 }
 
@@ -1408,6 +1438,7 @@ int ranenv_set_intra_policy_networks(ranenv_handle h, int32_t n, const ranenv_ml
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (n == 0 && !actors) { h->actor_ps.on = h->value_ps.on = false; return RANENV_OK; }
+    if (h->pop_bound()) return fail(h, RANENV_E_STATE, "intra policy nets per slice while a population's nets are bound (ranenv_set_policy_network first)");
     if (!h->actor.on) return fail(h, RANENV_E_STATE, "intra policy nets per slice need a bound inter net (ranenv_set_policy_network)");
     return net_set_copies(h, h->actor_ps, n, actors, NET_INTRA, (hipStream_t)stream);
 }
@@ -1416,6 +1447,7 @@ int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (n == 0 && !critics) { h->value_ps.on = false; return RANENV_OK; }
+    if (h->pop_bound()) return fail(h, RANENV_E_STATE, "intra value nets per slice while a population's nets are bound (ranenv_set_policy_network first)");
     const PolicyNet *ia = h->intra_actor();
     if (!ia) return fail(h, RANENV_E_INVALID, "intra value nets need a bound intra policy net (ranenv_set_policy_network / ranenv_set_intra_policy_networks)");
     if (n == h->cfg.n_slices && critics && critics[0] && critics[0]->input_layout != ia->layout)
@@ -1426,8 +1458,8 @@ int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp
 int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra)
 {
     if (!h || !dev_scores || !dev_intra) return fail(h, RANENV_E_INVALID, "null argument");
-    if (!h->actor.on && !h->head.on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
-    *dev_scores = h->d_net_scores; *dev_intra = (h->actor.on && h->intra_actor()) ? h->d_net_intra : nullptr;
+    if (!h->have_actor() && !h->head.on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
+    *dev_scores = h->d_net_scores; *dev_intra = (h->have_actor() && h->intra_actor()) ? h->d_net_intra : nullptr;
     return RANENV_OK;
 }
 
@@ -1436,7 +1468,7 @@ int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ran
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice value net is required (intra may be NULL)");
     const PolicyNet *ia = h->intra_actor();
-    if (intra && !(h->actor.on && ia)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
+    if (intra && !(h->have_actor() && ia)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
     if (intra && intra->input_layout != ia->layout)
         return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, ia->layout);
     NetBind b[2] = {{&h->value, &inter, 1, NET_INTER_VALUE}, {&h->value_intra, &intra, 1, NET_INTRA_VALUE}};
@@ -1446,6 +1478,135 @@ int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ran
     if (const int rc = net_commit(h, b, n, (hipStream_t)stream); rc != RANENV_OK) return rc;
     h->value_intra.on = intra != nullptr;         // (`intra`, NULL included, says what the intra critic is now)
     h->value_ps.on = false;
+    h->pop_value.on = h->pop_vintra.on = false;   // (... and that the critics are no population's)
+    return RANENV_OK;
+}
+
+// ---- populations: one net set per env group ------------------------------------------------------------------------------------
+// A grouping as the ABI takes it: 1..POP_MAX members, first[0] = 0 < first[1] < ... < first[n] (= batch where one is given)
+static int pop_check(ranenv_handle h, int32_t n, const int32_t *first, int batch)
+{
+    if (n < 1 || n > POP_MAX) return fail(h, RANENV_E_INVALID, "a population has 1..%d members, not %d", (int)POP_MAX, n);
+    if (!first) return fail(h, RANENV_E_INVALID, "null first_env table");
+    if (first[0] != 0) return fail(h, RANENV_E_INVALID, "first_env[0] is %d: member 0 starts at env 0", first[0]);
+    for (int m = 0; m < n; m++)
+        if (first[m + 1] <= first[m]) return fail(h, RANENV_E_INVALID, "first_env is not strictly increasing at member %d (%d, %d)", m, first[m], first[m + 1]);
+    if (batch >= 0 && first[n] != batch) return fail(h, RANENV_E_INVALID, "first_env[%d] is %d: the last member ends at the batch, %d", n, first[n], batch);
+    return RANENV_OK;
+}
+
+int ranenv_set_population(ranenv_handle h, int32_t n_members, const int32_t *host_first_env)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n_members == 0 && !host_first_env) { h->pop = PopMap{}; h->pop_unbind(); return RANENV_OK; }
+    if (const int rc = pop_check(h, n_members, host_first_env, h->cfg.batch); rc != RANENV_OK) return rc;
+    PopMap map{};
+    map.n = n_members;
+    for (int m = 0; m <= n_members; m++) map.first[m] = host_first_env[m];
+    if (h->pop_bound() && memcmp(&map, &h->pop, sizeof(map)) != 0)
+        return fail(h, RANENV_E_STATE, "the grouping cannot change while a population's nets are bound (ranenv_set_policy_network, or n_members 0, unbinds them)");
+    h->pop = map;
+    return RANENV_OK;
+}
+
+int ranenv_get_population(ranenv_handle h, int32_t *n_members, int32_t *host_first_env)
+{
+    if (!h || !n_members) return fail(h, RANENV_E_INVALID, "null argument");
+    *n_members = h->pop.n;
+    if (host_first_env && h->pop.n > 0)
+        for (int m = 0; m <= h->pop.n; m++) host_first_env[m] = h->pop.first[m];
+    return RANENV_OK;
+}
+
+int ranenv_population_tiles(int32_t n_members, const int32_t *first_env, int32_t e0, int32_t n_envs, int32_t rows_per_env, int32_t *out_member,
+                            int32_t *out_row0, int32_t *out_rows, int32_t *n_tiles)
+{
+    if (!n_tiles) return fail(nullptr, RANENV_E_INVALID, "null n_tiles");
+    if (const int rc = pop_check(nullptr, n_members, first_env, -1); rc != RANENV_OK) return rc;
+    if (e0 < 0 || n_envs < 1 || (long long)e0 + n_envs > first_env[n_members]) return fail(nullptr, RANENV_E_INVALID, "envs [%d, %d + %d) outside the population's %d", e0, e0, n_envs, first_env[n_members]);
+    if (rows_per_env < 1 || (long long)n_envs * rows_per_env > INT32_MAX) return fail(nullptr, RANENV_E_INVALID, "rows_per_env %d", rows_per_env);
+    int k = 0;
+    for (int m = 0; m < n_members; m++) {
+        PopShare sh;
+        const int tiles = pop_member_tiles(first_env, m, e0, n_envs, rows_per_env, sh);
+        for (int t = 0; t < tiles; t++, k++) {
+            if (out_member) out_member[k] = m;
+            if (out_row0) out_row0[k] = sh.row0 + t * NET_ROWS;
+            if (out_rows) out_rows[k] = sh.rows - t * NET_ROWS < NET_ROWS ? sh.rows - t * NET_ROWS : NET_ROWS;
+        }
+    }
+    *n_tiles = k;
+    return RANENV_OK;
+}
+
+// ranenv_set_population_policy / _value: up to two roles' member copies (the intra array may be null) planned; the count against the grouping
+static int pop_plan(ranenv_handle h, int32_t n, NetBind *b, int n_binds)
+{
+    if (h->pop.n == 0) return fail(h, RANENV_E_STATE, "no population set (ranenv_set_population)");
+    if (n != h->pop.n) return fail(h, RANENV_E_INVALID, "%d nets given, the population has %d members", n, h->pop.n);
+    for (int i = 0; i < n_binds; i++) b[i].members = true;
+    return net_plan(h, b, n_binds);
+}
+
+int ranenv_set_population_policy(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
+                                 uint64_t seed, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!inter) return fail(h, RANENV_E_INVALID, "the members' inter-slice nets are required (intra may be NULL)");
+    NetBind b[2] = {{&h->pop_actor, inter, n, NET_INTER}, {&h->pop_intra, intra, n, NET_INTRA}};
+    const int nb = intra ? 2 : 1;
+    int rc = pop_plan(h, n, b, nb);
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((rc = net_action_buffers(h)) != RANENV_OK) return rc;
+    if ((rc = net_commit(h, b, nb, (hipStream_t)stream)) != RANENV_OK) return rc;
+    h->net_stochastic = stochastic != 0; h->net_seed = seed;
+    h->pop_intra.on = intra != nullptr;           // (`intra`, NULL included, says what the intra policy is now)
+    h->actor.on = h->actor_intra.on = h->actor_ps.on = h->value_ps.on = false;
+    return RANENV_OK;
+}
+
+int ranenv_set_population_value(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!inter) return fail(h, RANENV_E_INVALID, "the members' inter-slice value nets are required (intra may be NULL)");
+    const PolicyNet *ia = h->intra_actor();
+    if (intra && !(h->have_actor() && ia)) return fail(h, RANENV_E_INVALID, "intra value nets need a bound intra policy net");
+    if (intra && h->pop.n > 0 && n == h->pop.n && intra[0] && intra[0]->input_layout != ia->layout)
+        return fail(h, RANENV_E_INVALID, "intra value nets: input layout %d, the intra policy net has %d", intra[0]->input_layout, ia->layout);
+    NetBind b[2] = {{&h->pop_value, inter, n, NET_INTER_VALUE}, {&h->pop_vintra, intra, n, NET_INTRA_VALUE}};
+    const int nb = intra ? 2 : 1;
+    if (const int rc = pop_plan(h, n, b, nb); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (const int rc = net_commit(h, b, nb, (hipStream_t)stream); rc != RANENV_OK) return rc;
+    h->pop_vintra.on = intra != nullptr;          // (`intra`, NULL included, says what the intra critic is now)
+    h->value.on = h->value_intra.on = h->value_ps.on = false;
+    return RANENV_OK;
+}
+
+int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_mlp *inter, const ranenv_mlp *intra, const ranenv_mlp *v_inter,
+                                 const ranenv_mlp *v_intra, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (member < 0 || member >= h->pop.n) return fail(h, RANENV_E_INVALID, "member %d outside the population's %d", member, h->pop.n);
+    const struct { ranenv::NetSlot *slot; const ranenv_mlp *m; NetRole role; } roles[4] = {
+        {&h->pop_actor, inter, NET_INTER}, {&h->pop_intra, intra, NET_INTRA}, {&h->pop_value, v_inter, NET_INTER_VALUE}, {&h->pop_vintra, v_intra, NET_INTRA_VALUE}};
+    for (const auto &r : roles) {           // every check of every role in front of the first device call
+        if (!r.m) continue;
+        const char *who = NET_ROLES[r.role].who;
+        if (!r.slot->on) return fail(h, RANENV_E_STATE, "%s net of member %d: the population has no %s nets bound", who, member, who);
+        PolicyNet ni{};
+        long long floats = 0;
+        if (const int rc = net_layout(h, r.m, r.role, ni, floats); rc != RANENV_OK) return rc;
+        const PolicyNet &n0 = r.slot->net;
+        bool same = ni.n_layers == n0.n_layers && ni.act == n0.act && ni.layout == n0.layout && ni.prec == n0.prec;
+        for (int l = 0; same && l <= ni.n_layers; l++) same = r.m->dims[l] == r.slot->dims[l];
+        if (!same) return fail(h, RANENV_E_INVALID, "%s net of member %d differs from the bound set in shape, activation, input layout or precision", who, member);
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    for (const auto &r : roles)
+        if (r.m)
+            if (const int rc = net_copy(h, r.m, r.slot->net, (hipStream_t)stream, r.slot->w + (size_t)member * (size_t)r.slot->member_stride); rc != RANENV_OK) return rc;
     return RANENV_OK;
 }
 
@@ -1977,13 +2138,13 @@ static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kp
         rec.logp = slot(tr.rec.logp, C);
         rec.intra_actor = ia ? 1 : 0;
     }
-    const PolicyNet &actor = head ? h->head.net : h->actor.net, *intra = ia ? h->intra_actor() : nullptr;
-    const PolicyNet *critic = vc ? (head ? &h->head_value.net : &h->value.net) : nullptr, *vintra = ic ? h->intra_critic() : nullptr;
+    PolicyNets nets = head ? PolicyNets{true, &h->head.net, nullptr, vc ? &h->head_value.net : nullptr, nullptr} : h->ibsched_nets(vc);
+    const PolicyNet &actor = *nets.actor, *intra = nets.intra, *critic = nets.critic, *vintra = nets.vintra;
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
     // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").  Nets per
     // slice count with one slice's copy: the co-resident workgroups of a sliced launch mostly walk one slice's weights.
     if (!critic_only) rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, *intra, vintra) << 1 : 0);
-    return launch_policy(s, PolicyNets{head, &actor, intra, critic, vintra}, net_io(h, kpk), &rec, e0, n);
+    return launch_policy(s, nets, net_io(h, kpk), &rec, e0, n);
 }
 
 // One launch of a partition's walk: TTI `t` of its own count, kpk.n_tti TTIs (one under a policy net or a recording), for envs
@@ -2164,8 +2325,8 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
     if ((traj->adv || traj->vtarg) && !(traj->reward && traj->vf && traj->done))
         return fail(h, RANENV_E_INVALID, "adv / vtarg need the record's reward, vf and done");
     if (h->kp.policy != RANENV_POLICY_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect needs policy NETWORK (ranenv_set_policy)");
-    if (!h->actor.on) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
-    if (!h->value.on) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
+    if (!h->have_actor()) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!h->have_critic()) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
     if (h->intra_critic() && !(h->intra_actor() && h->intra_actor()->layout == h->intra_critic()->layout))
         return fail(h, RANENV_E_STATE, "the intra value net was bound for another intra policy net (bind it again, ranenv_set_value_network)");
     Record ppo;

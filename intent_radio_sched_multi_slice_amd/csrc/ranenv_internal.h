@@ -210,9 +210,26 @@ struct PolicyRec {
     int critic_only;                      // the pass behind the last TTI: no actors, no record, vf of the observation as it stands
     int split;                            // host side only: bit 0 / 1 = the inter (head) / intra critic runs as a launch of its own behind the actor's
 };
+// A population (ranenv_set_population): member m owns envs [first[m], first[m + 1]) and its own copy of every population net.  By value
+// in the arguments of the population kernels: a launch carries the grouping it was enqueued under.
+enum { POP_MAX = 64 };
+struct PopMap { int n; int first[POP_MAX + 1]; };
+// THE POPULATION GEOMETRY, one function for the kernel, launch_kind's grid and ranenv_population_tiles: member m's share of a launch
+// over envs [e0, e0 + n_envs) with rows_per_env rows per env (kind 0: 1, the flat intra rows: S) -- `rows` rows (0: none) from row
+// `row0` of the launch on, in the tiles (workgroups of NET_ROWS rows) the function returns.  Workgroups are numbered member-major.
+struct PopShare { int row0, rows; };
+__host__ __device__ inline int pop_member_tiles(const int *first, int m, int e0, int n_envs, int rows_per_env, PopShare &sh)
+{
+    const int lo = first[m] > e0 ? first[m] : e0, hi = first[m + 1] < e0 + n_envs ? first[m + 1] : e0 + n_envs;
+    sh.row0 = (lo - e0) * rows_per_env;
+    sh.rows = hi > lo ? (hi - lo) * rows_per_env : 0;
+    return (sh.rows + NET_ROWS - 1) / NET_ROWS;
+}
 // The nets of one TTI's policy launches.  head: `actor` / `critic` are the head policy's (one launch, no intra nets), else the inter
 // pair.  Null: intra = no intra actor (then vintra is null too), critic / vintra = no critic of that kind.
-struct PolicyNets { bool head; const PolicyNet *actor, *intra, *critic, *vintra; };
+// pop non-null: a population acts -- net X has a copy per member at X->w + m * stride[X] (floats; in the order actor, intra, critic,
+// vintra; 0: one net for every member), and a kind with such a net takes the population kernels.
+struct PolicyNets { bool head; const PolicyNet *actor, *intra, *critic, *vintra; const PopMap *pop = nullptr; long long stride[4] = {0, 0, 0, 0}; };
 // THE policy launch entry, for envs [e0, e0 + n_envs).  rec null: the acting launches (actors only; the critics are not read).  rec
 // non-null: the recording launches -- actor + critic per agent kind fused, or split by rec's bits; critic_only: the critics alone.  An
 // intra launch whose actor or critic has a slice_stride takes the sliced kernels (one workgroup column per slice).

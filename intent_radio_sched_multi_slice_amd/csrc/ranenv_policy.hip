@@ -245,14 +245,41 @@ __device__ __forceinline__ int active_slices(const PolicyIO &io, int e)
 // workgroups resident at one time mostly walk one slice's weights (measured against tile * S + sl: never slower, 7 % faster with [512] x 3
 // nets at B 16 384 S 5).
 // PREC (compile time): bit 0 = `net` is a bf16 net, bit 1 = `vnet` is.
-template <bool HEAD, bool REC, bool SLICED = false, int PREC = 0>
+// POP (compile time; kinds 0 and 1, ranenv_set_population): n_rows = the launch's ENVS; member m of `pop` contributes the rows of its
+// envs inside [e0, e0 + n_rows) -- pop_member_tiles, ranenv_internal.h -- in tiles of their own, workgroups numbered member-major (the
+// co-resident ones walk one member's weights, as slice-major does for SLICED).  Every wave finds the workgroup's (member, tile) from
+// blockIdx.x: lane m computes member m's tile count, an inclusive prefix sum over the wave and a ballot give the first member whose sum
+// exceeds blockIdx.x; member and row range are broadcast and made scalar, so the weights at net.w + member * wa (vnet: wv; floats, 0 =
+// one net for all members) are addressed as the one-net kernels address theirs.  From there on the workgroup is a one-net workgroup
+// whose launch ends at the member's last row: row0 (the row map's g = row0 + r stays launch-relative) carries the member's row origin,
+// n_rows becomes the member's end row, and the tail rows of the member's last tile are dead rows like the tail rows of a launch --
+// zeros in LDS, nothing read from and nothing written to the next member's envs.
+template <bool HEAD, bool REC, bool SLICED = false, int PREC = 0, bool POP = false>
 __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNet &vnet, const PolicyIO &io, const PolicyRec &rec, int kind, int e0,
-                                            int n_rows, float *lds)
+                                            int n_rows, float *lds, const PopMap *pop = nullptr, long long wa = 0, long long wv = 0)
 {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int S = io.S;
     const int tiles = SLICED ? (n_rows + NET_ROWS - 1) / NET_ROWS : 1, sl = SLICED ? (int)blockIdx.x / tiles : 0;
-    const int row0 = (SLICED ? (int)blockIdx.x - sl * tiles : (int)blockIdx.x) * NET_ROWS;
+    int row0 = (SLICED ? (int)blockIdx.x - sl * tiles : (int)blockIdx.x) * NET_ROWS;
+    int mem = 0;
+    if constexpr (POP) {
+        PopShare sh{0, 0};
+        const int mine = lane < pop->n ? pop_member_tiles(pop->first, lane, e0, n_rows, kind == 1 ? S : 1, sh) : 0;
+        int upto = mine;
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const int up = __shfl_up(upto, d);
+            if (lane >= d) upto += up;
+        }
+        const unsigned long long owners = __ballot(upto > (int)blockIdx.x);
+        if (owners == 0) return;                       // (a workgroup beyond the members' tiles: the host launches none)
+        mem = __ffsll(owners) - 1;
+        const int tile = (int)blockIdx.x - (__shfl(upto, mem) - __shfl(mine, mem));
+        const int org = __shfl(sh.row0, mem);
+        n_rows = __builtin_amdgcn_readfirstlane(org + __shfl(sh.rows, mem));
+        row0 = __builtin_amdgcn_readfirstlane(org + tile * NET_ROWS);
+        mem = __builtin_amdgcn_readfirstlane(mem);
+    }
     constexpr bool BFA = (PREC & 1) != 0, BFV = (PREC & 2) != 0;
     int ldm = net_ld_max<BFA>(net);
     if (REC && vnet.n_layers > 0) { const int lv = net_ld_max<BFV>(vnet); ldm = lv > ldm ? lv : ldm; }
@@ -272,7 +299,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
     }
     net_load_rows<REC, SLICED, BFA>(net, io, rec, kind, e0, row0, n_rows, cur, tid, sl);
     __syncthreads();
-    net_layers<BFA>(net, SLICED ? net.w + sl * net.slice_stride : net.w, cur, nxt, lane, wave);
+    net_layers<BFA>(net, SLICED ? net.w + sl * net.slice_stride : (POP ? net.w + mem * wa : net.w), cur, nxt, lane, wave);
 
     // ---- epilogue: actions ----------------------------------------------------------------------------------------------
     const int ld = net_ld(net.np[net.n_layers - 1]);
@@ -371,7 +398,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         const PolicyRec none{};
         net_load_rows<false, SLICED, BFV>(vnet, io, none, kind, e0, row0, n_rows, cur, tid, sl);
         __syncthreads();
-        net_layers<BFV>(vnet, SLICED ? vnet.w + sl * vnet.slice_stride : vnet.w, cur, nxt, lane, wave);
+        net_layers<BFV>(vnet, SLICED ? vnet.w + sl * vnet.slice_stride : (POP ? vnet.w + mem * wv : vnet.w), cur, nxt, lane, wave);
         const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
         for (int r = tid; r < NET_ROWS; r += 256) {
             const int g = row0 + r;
@@ -467,6 +494,23 @@ __global__ void __launch_bounds__(256) ranenv_head_policy_bf16_collect_kernel(Po
 {
     extern __shared__ float lds[];
     policy_body<true, true, false, PREC>(net, vnet, io, rec, 0, e0, n_rows, lds);
+}
+
+// A population's launches (ranenv_set_population_policy / _value): kinds 0 and 1 of the IBSched nets, acting and recording, PREC as in
+// policy_body (0: f32 nets).  n_envs: the launch's envs, whatever the kind; wa / wv: floats between two members' copies of net / vnet.
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_pop_kernel(PolicyNet net, PolicyIO io, PopMap pop, long long wa, int kind, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, false, false, PREC, true>(net, net, io, PolicyRec{}, kind, e0, n_envs, lds, &pop, wa, 0);
+}
+
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_pop_collect_kernel(PolicyNet net, PolicyNet vnet, PolicyIO io, PolicyRec rec, PopMap pop, long long wa,
+                                                                        long long wv, int kind, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, true, false, PREC, true>(net, vnet, io, rec, kind, e0, n_envs, lds, &pop, wa, wv);
 }
 
 // ---- SAC's soft Bellman target (ranenv_sac_targets; the arithmetic is spelled out in include/ranenv.h) -----------------------------
@@ -567,16 +611,27 @@ using ranenv_dev::policy_lds_bytes;
 // One agent kind's launch(es) of a TTI for envs [e0, e0 + n_envs): the actor `a` alone (rec null), or the recording launch -- actor +
 // critic `vp` (null: none) fused, or, split, the actor's launch and then the critic alone (the kernel's critic_only mode).  THE GEOMETRY:
 // kind 0 has one row per env; an intra launch (kind 1) has the flat env x S rows, or -- sliced, when its actor or its critic has a copy
-// per slice -- one row per env in S x tiles workgroups (see policy_body).
+// per slice -- one row per env in S x tiles workgroups (see policy_body).  pop non-null (a population's copies of the actor at stride
+// wa, of the critic at wv; never with nets per slice): the sum of the members' tiles, by pop_member_tiles.
 hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, const PolicyNet *vp, const PolicyIO &io, const PolicyRec *rec,
-                       int e0, int n_envs, bool split)
+                       int e0, int n_envs, bool split, const PopMap *pop = nullptr, long long wa = 0, long long wv = 0)
 {
     const bool sl = kind == 1 && (a.slice_stride != 0 || (vp && vp->slice_stride != 0));
     const int rows = kind == 1 && !sl ? n_envs * io.S : n_envs;
-    const dim3 grid((unsigned)((rows + NET_ROWS - 1) / NET_ROWS) * (sl ? (unsigned)io.S : 1u));
+    unsigned tiles = (unsigned)((rows + NET_ROWS - 1) / NET_ROWS) * (sl ? (unsigned)io.S : 1u);
+    if (pop) {
+        if (head || sl) return hipErrorInvalidValue;
+        tiles = 0;
+        PopShare sh;
+        for (int m = 0; m < pop->n; m++) tiles += (unsigned)pop_member_tiles(pop->first, m, e0, n_envs, kind == 1 ? io.S : 1, sh);
+        if (tiles == 0) return hipSuccess;
+    }
+    const dim3 grid(tiles);
     const bool bfa = a.prec == RANENV_NET_BF16;
     if (!rec) {
         const size_t lds = policy_lds_bytes(a);
+        if (pop) return bfa ? launch_kernel<ranenv_policy_pop_kernel<1>>(grid, lds, s, a, io, *pop, wa, kind, e0, n_envs)
+                            : launch_kernel<ranenv_policy_pop_kernel<0>>(grid, lds, s, a, io, *pop, wa, kind, e0, n_envs);
         if (sl) return bfa ? launch_kernel<ranenv_policy_bf16_sliced_kernel<1>>(grid, lds, s, a, io, e0, rows) : launch_kernel<ranenv_policy_sliced_kernel>(grid, lds, s, a, io, e0, rows);
         if (head) return bfa ? launch_kernel<ranenv_head_policy_bf16_kernel<1>>(grid, lds, s, a, io, e0, rows) : launch_kernel<ranenv_head_policy_kernel>(grid, lds, s, a, io, e0, rows);
         return bfa ? launch_kernel<ranenv_policy_bf16_kernel<1>>(grid, lds, s, a, io, kind, e0, rows) : launch_kernel<ranenv_policy_kernel>(grid, lds, s, a, io, kind, e0, rows);
@@ -590,7 +645,19 @@ hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, c
             if (head) return launch_kernel<ranenv_head_policy_bf16_collect_kernel<P>>(grid, lds, s, a, v, io, rc, e0, rows);
             return launch_kernel<ranenv_policy_bf16_collect_kernel<P>>(grid, lds, s, a, v, io, rc, kind, e0, rows);
         };
-        switch ((bfa ? 1 : 0) | (v.n_layers > 0 && v.prec == RANENV_NET_BF16 ? 2 : 0)) {
+        const int prec = (bfa ? 1 : 0) | (v.n_layers > 0 && v.prec == RANENV_NET_BF16 ? 2 : 0);
+        if (pop) {
+            auto pop_as = [&](auto p) {
+                return launch_kernel<ranenv_policy_pop_collect_kernel<decltype(p)::value>>(grid, lds, s, a, v, io, rc, *pop, wa, wv, kind, e0, n_envs);
+            };
+            switch (prec) {
+            case 1: return pop_as(std::integral_constant<int, 1>{});
+            case 2: return pop_as(std::integral_constant<int, 2>{});
+            case 3: return pop_as(std::integral_constant<int, 3>{});
+            }
+            return pop_as(std::integral_constant<int, 0>{});
+        }
+        switch (prec) {
         case 1: return as(std::integral_constant<int, 1>{});
         case 2: return as(std::integral_constant<int, 2>{});
         case 3: return as(std::integral_constant<int, 3>{});
@@ -621,8 +688,12 @@ hipError_t launch_policy(hipStream_t s, const PolicyNets &n, const PolicyIO &io,
     const PolicyNet *critic = rec ? n.critic : nullptr, *vintra = rec ? n.vintra : nullptr;
     const int split = rec ? rec->split : 0;
     hipError_t e = hipSuccess;
-    if (!critics || critic) e = launch_kind(s, n.head, 0, *n.actor, critic, io, rec, e0, n_envs, (split & 1) != 0);
-    if (e == hipSuccess && n.intra && (!critics || vintra)) e = launch_kind(s, false, 1, *n.intra, vintra, io, rec, e0, n_envs, (split & 2) != 0);
+    // (a kind none of whose nets has a copy per member runs the one-net kernels, population or not)
+    const bool pop0 = n.pop && (n.stride[0] != 0 || (critic && n.stride[2] != 0)), pop1 = n.pop && (n.stride[1] != 0 || (vintra && n.stride[3] != 0));
+    if (!critics || critic)
+        e = launch_kind(s, n.head, 0, *n.actor, critic, io, rec, e0, n_envs, (split & 1) != 0, pop0 ? n.pop : nullptr, n.stride[0], n.stride[2]);
+    if (e == hipSuccess && n.intra && (!critics || vintra))
+        e = launch_kind(s, false, 1, *n.intra, vintra, io, rec, e0, n_envs, (split & 2) != 0, pop1 ? n.pop : nullptr, n.stride[1], n.stride[3]);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
