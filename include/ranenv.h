@@ -356,6 +356,53 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
 int ranenv_population_tiles(int32_t n_members, const int32_t *first_env, int32_t e0, int32_t n_envs, int32_t rows_per_env, int32_t *out_member,
                             int32_t *out_row0, int32_t *out_rows, int32_t *n_tiles);
 
+/* Mixed populations: members that differ in net shape and in GAE gamma / lambda (the trials of the reference's hyper-parameter
+ * search, agents/ray_agent.py:61-67,112-145: every trial draws its own net_arch, gamma and lambda), still in one batch and one policy
+ * launch per TTI, partition and agent kind.  Opt-in: the calls above keep refusing lists of mixed shape.
+ *
+ *   ranenv_set_population_policy_mixed / _value_mixed: ranenv_set_population_policy / _value whose n nets of a role may differ in
+ *     n_hidden (1..4), hidden widths and activation.  Every member's net is validated on its own, as a one-net bind validates it; the
+ *     members of a role must still agree in input_layout and precision (RANENV_E_INVALID) -- precision is a compile-time property of a
+ *     role's kernel, the layout of its input rows.  They bind and unbind what their uniform counterparts bind and unbind, with the same
+ *     two phases: every check in front of the first device call, then the copies on `stream` without a host sync.
+ *   Extents: every member of a role owns an extent of equal size in the role's packed buffer, the LARGEST member's packed size
+ *     (ranenv_packed_net_floats); member m's layers sit at offsets of their own from the start of its extent, the rest of the extent is
+ *     zero.
+ *   Tables: per population role the handle keeps a device table of 64 net descriptors (160 bytes each: widths, offsets, activation,
+ *     the address of the member's copy), allocated once so that its address never changes.  Every population bind -- uniform ones
+ *     included -- writes its role's table on `stream`.  While a role of an agent kind is bound mixed, that kind's launches run the
+ *     mixed kernels, which take member m's descriptor of actor AND critic from the tables (a role that one net serves for all members
+ *     has n equal entries) and are from there on one-net workgroups on the member's own shape; all other launches run the kernels
+ *     they ran before.  The launch's dynamic LDS is the largest member's need, and ranenv_collect's fused-or-split rule counts a mixed
+ *     role with its extent.
+ *   ranenv_set_population_member on a mixed-bound role accepts any valid shape of the role's input layout and precision whose packed
+ *     size fits the member's extent -- PBT's copy of a winner into a loser of another architecture.  A net that does not fit is
+ *     RANENV_E_INVALID (the message names both sizes), in front of every device call of every role, with nothing changed.  On `stream`,
+ *     in this order: the extent is zeroed, the layers are copied, the member's table entry is rewritten.  The table entry follows the
+ *     contract the weight copy already has: it is ordered on the caller's stream against that stream's launches -- launches enqueued
+ *     before the call see the old net whole, launches enqueued after it the new one.  On a uniformly bound role the call is as above.
+ *   ranenv_get_population_net: what member `member` of `role` (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic) holds
+ *     now: n_hidden, dims [6] (unused entries 0), activation, the extent and the floats of it the net uses.  Any out pointer may be
+ *     NULL.  A role without population nets is RANENV_E_STATE.
+ *   ranenv_packed_net_floats: the size rule itself, no handle: floats of the packed copy of a net of widths dims [n_hidden + 2] --
+ *     every width padded to a multiple of 32, per layer kp * np weights (RANENV_NET_BF16: two per float) and np biases.  n_hidden
+ *     outside 1..4, a hidden width outside 1..512, an input or output width < 1 or an unknown precision are RANENV_E_INVALID.
+ *   ranenv_set_population_gae: host arrays of n = n_members (gamma, lambda) pairs, copied at the call; both NULL switches it off.
+ *     While set, the GAE pass of ranenv_collect uses member m's pair for the rows of member m's envs and IGNORES the call's scalar
+ *     gamma and lambda.  Removing or changing the grouping clears it.  ranenv_gae_population is ranenv_gae with such pairs, given with
+ *     the call.  The recurrence is ranenv_gae's, operation for operation: a member's rows equal bit for bit what the scalar pass gives
+ *     under that member's pair.
+ *   Nets per slice inside a population, the head policies and the SAC path are as above: refused, or not reading the population. */
+int ranenv_set_population_policy_mixed(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
+                                       uint64_t seed, void *stream);
+int ranenv_set_population_value_mixed(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream);
+int ranenv_get_population_net(ranenv_handle h, int32_t role, int32_t member, int32_t *n_hidden, int32_t *dims, int32_t *activation, int64_t *extent_floats,
+                              int64_t *used_floats);
+int ranenv_packed_net_floats(int32_t n_hidden, const int32_t *dims, int32_t precision, int64_t *floats);
+int ranenv_set_population_gae(ranenv_handle h, int32_t n, const double *host_gamma, const double *host_lambda);
+int ranenv_gae_population(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *dev_reward, const float *dev_vf, const uint8_t *dev_done, int32_t n,
+                          const double *host_gamma, const double *host_lambda, float *dev_adv, float *dev_vtarg, void *stream);
+
 /* CommunicationEnv.reset for the envs with env_mask[b] != 0 (NULL = all): fresh buffers,
  * step 0, observation of the zero raw state with the episode's first SE tile.
  * Outputs may be NULL. dev_se_tiles: [B][U*R] explicit tiles or NULL to use the pool. */

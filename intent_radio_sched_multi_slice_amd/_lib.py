@@ -198,8 +198,16 @@ FUNCTIONS = {
     "ranenv_set_population_value": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), C.POINTER(C.POINTER(Mlp)), _P]),
     "ranenv_set_population_member": (C.c_int, [_P, _I32] + [C.POINTER(Mlp)] * 4 + [_P]),
     "ranenv_population_tiles": (C.c_int, [_I32, C.POINTER(C.c_int32), _I32, _I32, _I32] + [C.POINTER(C.c_int32)] * 4),
+    "ranenv_set_population_policy_mixed": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), C.POINTER(C.POINTER(Mlp)), _I32, C.c_uint64, _P]),
+    "ranenv_set_population_value_mixed": (C.c_int, [_P, _I32, C.POINTER(C.POINTER(Mlp)), C.POINTER(C.POINTER(Mlp)), _P]),
+    "ranenv_get_population_net": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64)]),
+    "ranenv_packed_net_floats": (C.c_int, [_I32, C.POINTER(C.c_int32), _I32, C.POINTER(C.c_int64)]),
+    "ranenv_set_population_gae": (C.c_int, [_P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ranenv_gae_population": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P]),
 }
 POPULATION_MAX = 64
+POPULATION_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}
 EXPORTS = tuple(FUNCTIONS)
 
 

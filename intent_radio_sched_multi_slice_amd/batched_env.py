@@ -158,6 +158,26 @@ def population_first(batch: int, first_env=None, sizes=None) -> np.ndarray:
     return first.astype(np.int32)
 
 
+def packed_net_floats(layers, precision: str = "f32") -> int:
+    """Floats of the library's packed copy of a net (ranenv_packed_net_floats: widths padded to 32, bf16 halves the weights) -- what
+    decides whether ``set_population_member`` can put the net into a member of a mixed population (``population_net()["extent"]``).
+    ``layers``: a net as for ``policy_net_layers``, or its widths ``[in, hidden..., out]``."""
+    if precision not in _lib.NET_PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(_lib.NET_PRECISIONS)}")
+    if isinstance(layers, (list, tuple)) and len(layers) > 0 and all(isinstance(x, (int, np.integer)) for x in layers):
+        dims = [int(x) for x in layers]
+    else:
+        got = policy_net_layers(layers)[0]
+        dims = [got[0][0].shape[1]] + [w.shape[0] for w, _ in got]
+    if not 3 <= len(dims) <= NET_MAX_HIDDEN + 2:
+        raise ValueError(f"{len(dims) - 2} hidden layers: 1..{NET_MAX_HIDDEN} are supported")
+    out = C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_packed_net_floats(len(dims) - 2, (C.c_int32 * len(dims))(*dims), _lib.NET_PRECISIONS[precision], C.byref(out)),
+               "ranenv_packed_net_floats")
+    return out.value
+
+
 def population_means(result: Dict[str, np.ndarray], first_env) -> Dict[str, np.ndarray]:
     """Per-member means of what ``evaluate()`` returns: every float metric [B, n_episodes, ...] -> [G, ...], the mean over the
     member's envs and episodes (``np.mean`` of the member's block); integer entries ("scenario") are left out."""
@@ -223,6 +243,7 @@ class BatchedRanEnv:
         self._ranges = None          # set_ranges(): [(lo, hi)] for step_async / step_wait
         self._intra_layout = None    # input layout of the intra actor bound by set_policy_network (None: none)
         self._population = None      # set_population's first_env table [G + 1] (None: no grouping)
+        self._gae_per_member = False # collect() has set the members' (gamma, lambda) pairs (ranenv_set_population_gae)
         self.head_observation = "head"      # what the head nets read (set_head_policy_network): "head" = head_obs, "inter" = obs_inter
         # (the views are handed out once, here: ranenv_get_views ends the library's host shadow of the step counters -- the views are writable --,
         # and a first views() call in the middle of an auto-reset loop would switch the shortcut of enable_autoreset off until the next full reset)
@@ -447,7 +468,7 @@ class BatchedRanEnv:
         return 10 * self.S, self.W + (self.Us if intra_input == "mask_obs" else 0)
 
     def set_policy_network(self, inter, intra=None, stochastic: bool = False, seed: int = 0, intra_input: str = "obs",
-                           activation: Optional[str] = None, fixed_intra: Optional[int] = None, precision: str = "f32"):
+                           activation: Optional[str] = None, fixed_intra: Optional[int] = None, precision: str = "f32", mixed: bool = False):
         """Run trained IBSched policy nets on the device in front of every TTI (RANENV_POLICY_NETWORK, include/ranenv.h):
         ``inter`` -> 2*S outputs (mean, log_std of the masked Gaussian), ``intra`` (None = ``fixed_intra``) -> 3 logits per
         (env, slice) from ``obs_intra`` ("obs") or ``[mask_intra, obs_intra]`` ("mask_obs", RLlib's flattened Dict).  Nets as
@@ -461,14 +482,19 @@ class BatchedRanEnv:
         fourth digit; "f32", the default, leaves them as they were.
         ``inter`` may be a list of G nets of one shape under ``set_population`` -- member m's envs act on ``inter[m]`` -- and ``intra``
         then None or a list of G nets (ranenv_set_population_policy); a list of S intra nets beside ONE inter net keeps its per-slice
-        meaning."""
+        meaning.  ``mixed=True`` (lists under ``set_population`` only): the members' nets may differ in hidden widths, depth and
+        activation -- the trials of a hyper-parameter search -- (ranenv_set_population_policy_mixed); input and output width, layout and
+        precision stay common and are checked per net before any library call."""
         in_inter, in_intra = self.net_input_dims(intra_input)
         members = per_slice_nets(inter)
+        if mixed and members is None:
+            raise ValueError("mixed=True takes a list of inter nets, one per member of the population")
         if members is not None:                # a population: inter[m] (and intra[m]) are member m's
             G = self._population_size(len(members))
-            lists = [self._net_list(members, activation, in_inter, 2 * self.S, NET_IN_OBS, precision, count=G, per="member"),
-                     self._member_list(intra, G, activation, in_intra, 3, NET_INPUTS[intra_input], precision)]
-            self._set_population_nets("ranenv_set_population_policy", "population_policy", G, lists, 1 if stochastic else 0, int(seed) & (2 ** 64 - 1))
+            lists = [self._net_list(members, activation, in_inter, 2 * self.S, NET_IN_OBS, precision, count=G, per="member", mixed=mixed),
+                     self._member_list(intra, G, activation, in_intra, 3, NET_INPUTS[intra_input], precision, mixed)]
+            self._set_population_nets("ranenv_set_population_policy" + ("_mixed" if mixed else ""), "population_policy", G, lists, 1 if stochastic else 0,
+                                      int(seed) & (2 ** 64 - 1))
             for key in ("policy_net", "intra_policy_nets"):
                 self._keep.pop(key, None)
             self._intra_layout = None if intra is None else NET_INPUTS[intra_input]
@@ -513,11 +539,12 @@ class BatchedRanEnv:
             self._check(getattr(self._lib, call)(self._h, *structs, *args, self._stream()), call)
         self._keep[key] = keep                 # (the library copies on the current stream; keep the sources until it has)
 
-    def _net_list(self, nets, activation, in_dim, out_dim, layout, precision="f32", count=None, per="slice"):
+    def _net_list(self, nets, activation, in_dim, out_dim, layout, precision="f32", count=None, per="slice", mixed=False):
         """A list of S nets as the argument of a ``ranenv_set_intra_*_networks`` call: ``(array of ranenv_mlp pointers, what to
         keep alive)``, or None for None.  Raises ValueError -- before any library call: a per-slice bind is two of
         them, and the first one drops the previous set -- unless there are S valid nets of one shape and activation.
-        ``count`` / ``per``: a population's list instead, one net per member."""
+        ``count`` / ``per``: a population's list instead, one net per member; ``mixed``: its nets may differ in hidden shape and
+        activation, and must still agree in input layout."""
         if nets is None:
             return None
         if per == "member" and len(nets) != count:
@@ -529,7 +556,10 @@ class BatchedRanEnv:
             layers, act = policy_net_layers(net, activation, in_dim, out_dim)
             shape = ([tuple(w.shape) for w, _ in layers], act)
             first = shape if first is None else first
-            if shape != first:
+            if mixed:
+                if structs and (layout(layers) if callable(layout) else layout) != structs[0].input_layout:
+                    raise ValueError(f"net {i} reads another input layout than net 0: the nets per member have one input layout")
+            elif shape != first:
                 raise ValueError(f"{'intra ' if per == 'slice' else ''}net {i} ({shape[0]}, {shape[1]}) differs from net 0 ({first[0]}, {first[1]}): "
                                  f"the nets per {per} have one shape and one activation")
             structs.append(self._mlp_struct(layers, act, layout(layers) if callable(layout) else layout, keep, precision))
@@ -552,6 +582,7 @@ class BatchedRanEnv:
         if first_env is None and sizes is None:
             self._check(self._lib.ranenv_set_population(self._h, 0, None), "ranenv_set_population")
             self._population = None
+            self._gae_per_member = False     # (the library drops the members' GAE pairs with the grouping)
             for key in ("population_policy", "population_value"):
                 self._keep.pop(key, None)
             return
@@ -582,14 +613,14 @@ class BatchedRanEnv:
             raise ValueError(f"{n_given} nets given: one per member is {G}")
         return G
 
-    def _member_list(self, nets, G, activation, in_dim, out_dim, layout, precision):
+    def _member_list(self, nets, G, activation, in_dim, out_dim, layout, precision, mixed=False):
         """The intra argument beside a list of G inter nets: None, or a list of G nets"""
         if nets is None:
             return None
         as_list = per_slice_nets(nets)
         if as_list is None:
             raise ValueError(f"beside a list of inter nets, intra is None or a list of nets, one per member ({G})")
-        return self._net_list(as_list, activation, in_dim, out_dim, layout, precision, count=G, per="member")
+        return self._net_list(as_list, activation, in_dim, out_dim, layout, precision, count=G, per="member", mixed=mixed)
 
     def _set_population_nets(self, call: str, key: str, G: int, lists, *args):
         with torch.cuda.device(self.device):
@@ -599,8 +630,9 @@ class BatchedRanEnv:
     def set_population_member(self, m: int, inter=None, intra=None, v_inter=None, v_intra=None, activation: Optional[str] = None,
                               precision: Optional[Dict[str, str]] = None) -> None:
         """Rebind member ``m``'s copies in place (ranenv_set_population_member): the nets given replace that member's inter actor /
-        intra actor / inter critic / intra critic, None leaves a role as it is; shapes as bound.  ``precision``: {"policy": ...,
-        "value": ...} as given to the binding calls (default "f32" each).  No other member is touched."""
+        intra actor / inter critic / intra critic, None leaves a role as it is; shapes as bound -- or, for a role bound with
+        ``mixed=True``, any shape whose packed copy fits the member's extent (``population_net``, ``packed_net_floats``).  ``precision``:
+        {"policy": ..., "value": ...} as given to the binding calls (default "f32" each).  No other member is touched."""
         G = len(self._population_first()) - 1
         if not 0 <= int(m) < G:
             raise ValueError(f"member {m} outside the population's {G}")
@@ -619,6 +651,39 @@ class BatchedRanEnv:
             self._check(self._lib.ranenv_set_population_member(self._h, int(m), *structs, self._stream()), "ranenv_set_population_member")
         self._keep.setdefault("population_members", {})[int(m)] = keep
 
+    def population_net(self, role: str, m: int) -> Dict[str, object]:
+        """What member ``m`` holds now for ``role`` ("inter", "intra", "v_inter", "v_intra"; ranenv_get_population_net): {"hidden": its
+        hidden widths, "dims": [in, hidden..., out], "activation": "tanh" / "relu", "extent": floats of the member's extent in the role's
+        buffer, "used": floats of it the net's packed copy takes}."""
+        if role not in _lib.POPULATION_ROLES:
+            raise ValueError(f"role must be one of {sorted(_lib.POPULATION_ROLES)}")
+        G = len(self._population_first()) - 1
+        if not 0 <= int(m) < G:
+            raise ValueError(f"member {m} outside the population's {G}")
+        n_hidden, act, dims, extent, used = C.c_int32(), C.c_int32(), (C.c_int32 * 6)(), C.c_int64(), C.c_int64()
+        self._check(self._lib.ranenv_get_population_net(self._h, _lib.POPULATION_ROLES[role], int(m), C.byref(n_hidden), dims, C.byref(act),
+                                                        C.byref(extent), C.byref(used)), "ranenv_get_population_net")
+        dims = list(dims[:n_hidden.value + 2])
+        return {"hidden": dims[1:-1], "dims": dims, "activation": {v: k for k, v in NET_ACTIVATIONS.items()}[act.value], "extent": extent.value,
+                "used": used.value}
+
+    packed_net_floats = staticmethod(packed_net_floats)
+
+    def _gae_pairs(self, gamma, lam):
+        """``collect`` / ``gae``: None for two scalars, else the members' (gamma [G], lam [G]) as float64 arrays -- a scalar beside a
+        sequence stands for every member.  ValueError, before any library call, without a population or for another length than G."""
+        seqs = [not np.isscalar(x) and np.ndim(x) > 0 for x in (gamma, lam)]
+        if not any(seqs):
+            return None
+        G = len(self._population_first()) - 1
+        out = []
+        for name, x, seq in (("gamma", gamma, seqs[0]), ("lam", lam, seqs[1])):
+            a = np.asarray(x, dtype=np.float64).reshape(-1) if seq else np.full(G, float(x))
+            if a.size != G:
+                raise ValueError(f"{name}: {a.size} values given, one per member is {G}")
+            out.append(np.ascontiguousarray(a))
+        return out
+
     def evaluate_population(self, n_episodes: int, max_steps=None, per_slice: bool = False) -> Dict[str, np.ndarray]:
         """``evaluate()`` and, per member, the mean of every metric over the member's envs and episodes: {metric: float64 [G]}
         (``"slice"``: [G, S, 10]), plus ``"per_env"``, what ``evaluate()`` returned."""
@@ -628,7 +693,7 @@ class BatchedRanEnv:
         out["per_env"] = res
         return out
 
-    def set_value_network(self, inter, intra=None, activation: Optional[str] = None, precision: str = "f32"):
+    def set_value_network(self, inter, intra=None, activation: Optional[str] = None, precision: str = "f32", mixed: bool = False):
         """Bind the critics that ``collect()`` evaluates beside the actors (ranenv_set_value_network): ``inter`` maps the
         inter-slice observation [10*S] to one value, ``intra`` (None = no intra critic: those columns of ``vf`` are 0) the
         intra actor's input row -- the layout given to ``set_policy_network`` -- to one value per (env, slice).  Nets as for
@@ -637,17 +702,21 @@ class BatchedRanEnv:
         shared or per-slice intra actors alike.  ``precision`` as for ``set_policy_network``, for every critic of this call; the
         critics' precision is their own -- bf16 critics beside f32 actors and the reverse are both fine.
         Under ``set_population``, ``inter`` may be a list of G critics (and ``intra`` then None or a list of G), member m's
-        (ranenv_set_population_value); population critics beside one actor pair and the reverse are both fine."""
+        (ranenv_set_population_value); population critics beside one actor pair and the reverse are both fine.  ``mixed=True``: the
+        members' critics may differ in hidden widths, depth and activation, as for ``set_policy_network`` (ranenv_set_population_value_mixed);
+        mixed critics beside uniform actors and the reverse are both fine."""
         layout = lambda layers: NET_IN_MASK_OBS if layers[0][0].shape[1] == self.W + self.Us else NET_IN_OBS  # noqa: E731
         members = per_slice_nets(inter)
+        if mixed and members is None:
+            raise ValueError("mixed=True takes a list of inter critics, one per member of the population")
         if members is not None:                # a population's critics: inter[m] (and intra[m]) are member m's
             G = self._population_size(len(members))
-            lists = [self._net_list(members, activation, 10 * self.S, 1, NET_IN_OBS, precision, count=G, per="member"),
-                     self._member_list(intra, G, activation, None, 1, layout, precision)]
+            lists = [self._net_list(members, activation, 10 * self.S, 1, NET_IN_OBS, precision, count=G, per="member", mixed=mixed),
+                     self._member_list(intra, G, activation, None, 1, layout, precision, mixed)]
             if lists[1] is not None and self._intra_layout != lists[1][0][0].contents.input_layout:
                 raise ValueError("intra critics read the intra actor's input row: " + (
                     "no intra actor is bound (set_policy_network)" if self._intra_layout is None else "its intra_input is the other layout"))
-            self._set_population_nets("ranenv_set_population_value", "population_value", G, lists)
+            self._set_population_nets("ranenv_set_population_value" + ("_mixed" if mixed else ""), "population_value", G, lists)
             for key in ("value_net", "intra_value_nets"):
                 self._keep.pop(key, None)
             return
@@ -668,16 +737,26 @@ class BatchedRanEnv:
         "adv": (torch.float32, 0, lambda B, S, Us, W: (B, S + 1)), "vtarg": (torch.float32, 0, lambda B, S, Us, W: (B, S + 1)),
     }
 
-    def collect(self, n_steps: int, gamma: float = 0.99, lam: float = 0.95, record=_lib.TRAJECTORY_FIELDS) -> Dict[str, torch.Tensor]:
+    def collect(self, n_steps: int, gamma=0.99, lam=0.95, record=_lib.TRAJECTORY_FIELDS) -> Dict[str, torch.Tensor]:
         """``rollout(n_steps)`` under the policy nets that leaves a PPO batch on the device (ranenv_collect, include/ranenv.h):
         a dict of ``[n_steps, B, ...]`` tensors named as ranenv_trajectory's fields (``vf`` has ``n_steps + 1`` slots, the last
         one the bootstrap value), restricted to ``record``.  ``adv`` / ``vtarg`` are GAE(``gamma``, ``lam``) of the recorded
         ``reward`` / ``vf`` / ``done``.  Needs ``set_policy_network`` and ``set_value_network``.  The tensors are allocated once
         per (n_steps, record) and REUSED: the next ``collect`` of that shape overwrites them.  ``obs_intra`` / ``mask_intra`` /
         ``action_intra`` are only written with an intra actor bound.  The env's state, ``env.reward`` / ``env.done`` / the
-        observation buffers and ``policy_actions()`` afterwards are those of ``rollout(n_steps)``."""
+        observation buffers and ``policy_actions()`` afterwards are those of ``rollout(n_steps)``.
+        Under ``set_population``, ``gamma`` and ``lam`` may each be a sequence of G values, member m's (ranenv_set_population_gae):
+        ``adv`` / ``vtarg`` of member m's envs are then GAE(``gamma[m]``, ``lam[m]``)."""
         if self._recorder is not None:
             raise RanEnvError("collect() does not return between TTIs: the recorder needs step()")
+        pairs = self._gae_pairs(gamma, lam)
+        _pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        if pairs is not None:
+            self._check(self._lib.ranenv_set_population_gae(self._h, len(pairs[0]), _pd(pairs[0]), _pd(pairs[1])), "ranenv_set_population_gae")
+            gamma, lam = 0.0, 0.0              # (ignored while the members' pairs are set)
+        elif getattr(self, "_gae_per_member", False):
+            self._check(self._lib.ranenv_set_population_gae(self._h, 0, None, None), "ranenv_set_population_gae")
+        self._gae_per_member = pairs is not None
         return self._collect("collect", n_steps, record, _lib.Trajectory, _lib.TRAJECTORY_FIELDS, self.TRAJECTORY_SHAPES, "trajectories",
                              (self.B, self.S, self.Us, self.W), self._lib.ranenv_collect, (float(gamma), float(lam)))
 
@@ -702,10 +781,12 @@ class BatchedRanEnv:
             self._check(call(self._h, n_steps, C.byref(traj), *args, *self._p_out, self._stream()), f"ranenv_{name}")
         return out
 
-    def gae(self, reward: torch.Tensor, vf: torch.Tensor, done: torch.Tensor, gamma: float = 0.99, lam: float = 0.95,
+    def gae(self, reward: torch.Tensor, vf: torch.Tensor, done: torch.Tensor, gamma=0.99, lam=0.95,
             adv: Optional[torch.Tensor] = None, vtarg: Optional[torch.Tensor] = None):
         """The GAE pass alone (ranenv_gae): ``reward`` float64 [T, B, C], ``vf`` float32 [T + 1, B, C], ``done`` uint8 [T, B] on the
-        device -> (``adv``, ``vtarg``) float32 [T, B, C], written into the given tensors or new ones."""
+        device -> (``adv``, ``vtarg``) float32 [T, B, C], written into the given tensors or new ones.  ``gamma`` / ``lam``: scalars, or
+        under ``set_population`` sequences of G values, member m's for member m's envs (ranenv_gae_population)."""
+        pairs = self._gae_pairs(gamma, lam)
         T, B, Cn = reward.shape
         if B != self.B or tuple(vf.shape) != (T + 1, B, Cn) or tuple(done.shape) != (T, B):
             raise RanEnvError(f"gae: reward {tuple(reward.shape)}, vf {tuple(vf.shape)}, done {tuple(done.shape)} do not fit [T, {self.B}, C]")
@@ -714,6 +795,12 @@ class BatchedRanEnv:
         done = self._dev(done, torch.uint8, (T, B), "done")
         adv = torch.empty((T, B, Cn), dtype=torch.float32, device=self.device) if adv is None else self._dev(adv, torch.float32, (T, B, Cn), "adv")
         vtarg = torch.empty((T, B, Cn), dtype=torch.float32, device=self.device) if vtarg is None else self._dev(vtarg, torch.float32, (T, B, Cn), "vtarg")
+        if pairs is not None:
+            _pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+            with torch.cuda.device(self.device):
+                self._check(self._lib.ranenv_gae_population(self._h, T, Cn, _ptr(reward), _ptr(vf), _ptr(done), len(pairs[0]), _pd(pairs[0]), _pd(pairs[1]),
+                                                            _ptr(adv), _ptr(vtarg), self._stream()), "ranenv_gae_population")
+            return adv, vtarg
         with torch.cuda.device(self.device):
             self._check(self._lib.ranenv_gae(self._h, T, Cn, _ptr(reward), _ptr(vf), _ptr(done), float(gamma), float(lam), _ptr(adv), _ptr(vtarg),
                                              self._stream()), "ranenv_gae")

@@ -703,6 +703,51 @@ __global__ void __launch_bounds__(256) ranenv_gae_kernel(int n_steps, int B, int
     }
 }
 
+// ... under a population's per-member pairs: the lane finds the member that owns its env -- the last m with first[m] <= b, by binary
+// search -- once, in front of the T-step chain, then runs ranenv_gae_kernel's chain on that member's (gamma, lambda): the same
+// operations in the same order, written out a second time (sharing them through a function reorders ranenv_gae_kernel's instructions)
+__global__ void __launch_bounds__(256) ranenv_gae_pop_kernel(int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf,
+                                                             const uint8_t *done, GaePop g, float *adv, float *vtarg)
+{
+    const long long n = (long long)B * n_cols, i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long b = i / n_cols;
+    int lo = 0, hi = g.pop.n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)g.pop.first[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const double gamma = g.gamma[lo], lambda = g.lambda[lo];
+    const long long rn = (long long)B * reward_stride, ri = b * reward_stride + (i - b * n_cols);
+    const double gl = gamma * lambda;
+    double a_next = 0.0, v1 = (double)vf[(long long)n_steps * n + i];
+    double r = reward[(long long)(n_steps - 1) * rn + ri], v0 = (double)vf[(long long)(n_steps - 1) * n + i];
+    uint8_t d = done[(long long)(n_steps - 1) * B + b];
+    for (int t = n_steps - 1; t >= 0; t--) {
+        double rp = 0.0, vp = 0.0;
+        uint8_t dp = 0;
+        if (t > 0) { rp = reward[(long long)(t - 1) * rn + ri]; vp = (double)vf[(long long)(t - 1) * n + i]; dp = done[(long long)(t - 1) * B + b]; }
+        const double nd = d ? 0.0 : 1.0;
+        const double delta = (r + (gamma * v1) * nd) - v0;
+        const double a = delta + (gl * nd) * a_next;
+        if (adv) adv[(long long)t * n + i] = (float)a;
+        if (vtarg) vtarg[(long long)t * n + i] = (float)(a + v0);
+        a_next = a; v1 = v0;
+        r = rp; v0 = vp; d = dp;
+    }
+}
+
+// A population role's descriptor table (PolicyNets::tab): entry m0 + i = proto with its packed copy at proto.w + i * stride
+__global__ void __launch_bounds__(64) ranenv_net_table_kernel(PolicyNet *tab, int m0, int n, PolicyNet proto, long long stride)
+{
+    const int i = (int)threadIdx.x;
+    if (i >= n) return;
+    PolicyNet e = proto;
+    e.w = proto.w + (long long)i * stride;
+    tab[m0 + i] = e;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Off-policy collection (ranenv_collect_replay / ranenv_replay_sample; the rules are spelled out in include/ranenv.h).
 // ---------------------------------------------------------------------------------------------
@@ -792,6 +837,19 @@ void launch_gae(hipStream_t s, int n_steps, int B, int n_cols, const double *rew
     const long long n = (long long)B * n_cols;
     hipLaunchKernelGGL(ranenv_gae_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_steps, B, n_cols, reward, reward_stride, vf, done,
                        gamma, lambda, adv, vtarg);
+}
+
+void launch_gae_pop(hipStream_t s, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,
+                    const GaePop &g, float *adv, float *vtarg)
+{
+    const long long n = (long long)B * n_cols;
+    hipLaunchKernelGGL(ranenv_gae_pop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_steps, B, n_cols, reward, reward_stride, vf, done,
+                       g, adv, vtarg);
+}
+
+void launch_net_table(hipStream_t s, PolicyNet *tab, int m0, int n, const PolicyNet &proto, long long stride)
+{
+    hipLaunchKernelGGL(ranenv_net_table_kernel, dim3(1), dim3(POP_MAX), 0, s, tab, m0, n, proto, stride);
 }
 
 void launch_ddiv_selftest(hipStream_t s, const double *a, const double *b, double *fast, double *ieee, long long n)

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <array>
 #include <vector>
 
 #include "ranenv_internal.h"
@@ -104,7 +105,13 @@ struct ranenv {
     // One bound net: its layout, and its packed weights in a buffer of the slot's own (cap floats; an outgrown buffer stays allocated
     // until ranenv_destroy).  A net per slice is S copies of one layout at net.slice_stride in that buffer, `net` describing slice 0's.
     // A population's net (pop_*) is G copies at member_stride, with the copies' unpadded widths in dims for ranenv_set_population_member.
-    struct NetSlot { PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; long long member_stride = 0; int32_t dims[6] = {}; };
+    // A population's net also keeps every member's descriptor as the device table holds it (member[m].w = member m's copy) with its unpadded
+    // widths, and the largest member's LDS need; `mixed`: bound by ranenv_set_population_policy_mixed / _value_mixed -- the members may
+    // differ in shape, `net` is member 0's, and member_stride, the extent of every member, is the largest member's packed size.
+    struct NetSlot {
+        PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; long long member_stride = 0; int32_t dims[6] = {};
+        bool mixed = false; std::vector<PolicyNet> member; std::vector<std::array<int32_t, 6>> member_dims; size_t lds_max = 0;
+    };
     // ranenv_set_policy_network (actor, actor_intra: the shared intra net) and ranenv_set_intra_policy_networks (actor_ps: one intra net
     // per slice, standing where the shared one stands while on); the same three for their critics (ranenv_set_value_network,
     // ranenv_set_intra_value_networks); ranenv_set_head_policy_network / _head_value_network: SchedTWC / SchedColORAN's actor and critic
@@ -114,6 +121,16 @@ struct ranenv {
     // _value), each standing where its one-net slot stands while on -- the binding calls keep at most one of the two on per role
     PopMap pop{};
     NetSlot pop_actor, pop_intra, pop_value, pop_vintra;
+    // The population roles' descriptor tables on the device: [5][POP_MAX] entries in the order actor, intra, critic, vintra, then a table
+    // of zeros (n_layers 0: no net).  Allocated by the first population bind and never moved; every population bind writes its role's
+    // table on the caller's stream, and a one-net slot that serves a role beside a mixed one gets G entries of its one net.
+    PolicyNet *d_pop_tab = nullptr;
+    NetSlot *pop_slot(int role) { return role == 0 ? &pop_actor : (role == 1 ? &pop_intra : (role == 2 ? &pop_value : &pop_vintra)); }
+    const NetSlot *pop_slot(int role) const { return const_cast<ranenv *>(this)->pop_slot(role); }
+    const NetSlot *one_slot(int role) const { return role == 0 ? &actor : (role == 1 ? &actor_intra : (role == 2 ? &value : &value_intra)); }
+    bool pop_mixed() const { for (int r = 0; r < 4; r++) if (pop_slot(r)->on && pop_slot(r)->mixed) return true; return false; }
+    // ranenv_set_population_gae: a (gamma, lambda) pair per member for ranenv_collect's GAE pass
+    bool gae_on = false; double gae_gamma[POP_MAX] = {}, gae_lambda[POP_MAX] = {};
     bool pop_bound() const { return pop_actor.on || pop_intra.on || pop_value.on || pop_vintra.on; }
     void pop_unbind() { pop_actor.on = pop_intra.on = pop_value.on = pop_vintra.on = false; }
     bool have_actor() const { return actor.on || pop_actor.on; }
@@ -130,6 +147,15 @@ struct ranenv {
             n.pop = &pop;
             n.stride[0] = pop_actor.on ? pop_actor.member_stride : 0; n.stride[1] = pop_intra.on ? pop_intra.member_stride : 0;
             n.stride[2] = pop_value.on ? pop_value.member_stride : 0; n.stride[3] = pop_vintra.on ? pop_vintra.member_stride : 0;
+            // a kind with a mixed-bound role (of the nets this launch may run) reads every net of it through the tables
+            auto mixed = [&](int r) { return pop_slot(r)->on && pop_slot(r)->mixed; };
+            const bool mx[2] = {mixed(0) || (critics && mixed(2)), mixed(1) || (critics && mixed(3))};
+            n.tab_none = d_pop_tab + 4 * POP_MAX;
+            for (int r = 0; r < 4; r++) {
+                if (!mx[r & 1]) continue;
+                n.tab[r] = d_pop_tab + r * POP_MAX;
+                n.lds[r] = pop_slot(r)->on ? pop_slot(r)->lds_max : (one_slot(r)->on ? policy_lds_bytes(one_slot(r)->net) : 0);
+            }
         }
         return n;
     }
@@ -1233,6 +1259,19 @@ static const struct { const char *who; bool intra; int out_s, out_1; } NET_ROLES
     {"head", false, 1, 0}, {"head", false, 2, 0}, {"head value", false, 0, 1},                                     // output width out_s * S + out_1
     {"SAC critic", false, 0, 1}};                                                                                  // (input: [observation | action], 11*S)
 
+// THE SIZE RULE of a packed copy (ranenv_packed_net_floats exposes it): the L layers of widths dims[0..L] from float `off` on, every
+// width padded to 32, a bf16 net's weights two per float; returns the float behind the last bias
+static long long net_pack(const int32_t *dims, int L, int prec, PolicyNet &net, long long off)
+{
+    const int per_float = prec == RANENV_NET_BF16 ? 2 : 1;      // weights per float of the packed copy
+    for (int l = 0; l < L; l++) {
+        net.kp[l] = (dims[l] + 31) / 32 * 32; net.np[l] = (dims[l + 1] + 31) / 32 * 32;
+        net.w_off[l] = off; off += (long long)net.kp[l] * net.np[l] / per_float;
+        net.b_off[l] = off; off += net.np[l];
+    }
+    return off;
+}
+
 static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, PolicyNet &net, long long &off)
 {
     const int S = h->cfg.n_slices, Us = h->cfg.max_ues_slice;
@@ -1258,12 +1297,7 @@ static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, Policy
         if (!m->weight[i] || !m->bias[i]) return fail(h, RANENV_E_INVALID, "%s net: layer %d has no weight / bias", who, i);
     net = PolicyNet{};
     net.n_layers = L; net.act = m->activation; net.layout = m->input_layout; net.prec = m->precision; net.in_dim = in_dim; net.out_dim = out_dim;
-    const int per_float = net.prec == RANENV_NET_BF16 ? 2 : 1;      // weights per float of the packed copy
-    for (int l = 0; l < L; l++) {
-        net.kp[l] = (m->dims[l] + 31) / 32 * 32; net.np[l] = (m->dims[l + 1] + 31) / 32 * 32;
-        net.w_off[l] = off; off += (long long)net.kp[l] * net.np[l] / per_float;
-        net.b_off[l] = off; off += net.np[l];
-    }
+    off = net_pack(m->dims, L, net.prec, net, off);
     return RANENV_OK;
 }
 
@@ -1290,12 +1324,29 @@ struct NetBind {
     bool members = false;                 // the copies are a population's, one per member (else one per slice)
     PolicyNet net; long long floats;      // the plan: copy 0's layout with the copies' stride (one copy: 0), floats of all copies
     long long stride;                     // ... floats between two copies
+    bool mixed = false;                   // (members) the copies may differ in hidden widths, depth and activation: member[i] is copy i's layout
+    std::vector<PolicyNet> member;        // ... at offsets of its own from float 0 of its extent; stride: the largest copy's packed size
 };
 static int net_plan(ranenv_handle h, NetBind *binds, int n)
 {
     for (NetBind *b = binds; b < binds + n; b++) {
         const char *who = NET_ROLES[b->role].who;
         long long floats = 0;
+        if (b->mixed) {                   // every member on its own; the members agree in input layout and precision only
+            b->member.assign((size_t)b->copies, PolicyNet{});
+            for (int i = 0; i < b->copies; i++) {
+                const ranenv_mlp *m = b->nets[i], *m0 = b->nets[0];
+                if (!m) return fail(h, RANENV_E_INVALID, "%s nets per member: net %d is null", who, i);
+                long long mine = 0;
+                if (const int rc = net_layout(h, m, b->role, b->member[(size_t)i], mine); rc != RANENV_OK) return rc;
+                if (m->input_layout != m0->input_layout || m->precision != m0->precision)
+                    return fail(h, RANENV_E_INVALID, "%s nets per member (mixed): net %d differs from net 0 in input layout or precision", who, i);
+                floats = mine > floats ? mine : floats;
+            }
+            b->net = b->member[0];
+            b->stride = floats; b->floats = floats * b->copies;
+            continue;
+        }
         for (int i = 0; i < b->copies; i++) {
             const ranenv_mlp *m = b->nets[i], *m0 = b->nets[0];
             const char *per = b->members ? "member" : "slice";
@@ -1315,6 +1366,26 @@ static int net_plan(ranenv_handle h, NetBind *binds, int n)
     return RANENV_OK;
 }
 
+static int pop_role_of(ranenv_handle h, const ranenv::NetSlot *slot)
+{
+    for (int r = 0; r < 4; r++) if (h->pop_slot(r) == slot) return r;
+    return 0;
+}
+
+// The roles' descriptor tables, allocated (zeroed) once
+static int pop_tables(ranenv_handle h) { return h->d_pop_tab ? RANENV_OK : dev_alloc(h, &h->d_pop_tab, (size_t)5 * POP_MAX); }
+
+// While a mixed role is bound, the mixed kernels read every net of its kind through a table: a role that one net serves for all members
+// gets G entries of that net.  On the caller's stream, behind every call that binds a mixed role or a one net beside one.
+static int pop_tables_one_net(ranenv_handle h, hipStream_t s)
+{
+    if (!h->pop_mixed()) return RANENV_OK;
+    for (int r = 0; r < 4; r++)
+        if (!h->pop_slot(r)->on && h->one_slot(r)->on) launch_net_table(s, h->d_pop_tab + r * POP_MAX, 0, h->pop.n, h->one_slot(r)->net, 0);
+    HIP_TRY(h, hipGetLastError());
+    return RANENV_OK;
+}
+
 // COMMIT, on the caller's stream without a host sync: every slot's buffer grown -- the outgrown one stays allocated, the launches of
 // earlier calls may still read it -- or zeroed over the new nets' extent; then every copy's layers; then the slots change, all or none.
 static int net_commit(ranenv_handle h, NetBind *binds, int n, hipStream_t s)
@@ -1331,10 +1402,27 @@ static int net_commit(ranenv_handle h, NetBind *binds, int n, hipStream_t s)
     }
     for (NetBind *b = binds; b < binds + n; b++)
         for (int i = 0; i < b->copies; i++)
-            if (const int rc = net_copy(h, b->nets[i], b->net, s, b->slot->w + (size_t)i * (size_t)b->stride); rc != RANENV_OK) return rc;
+            if (const int rc = net_copy(h, b->nets[i], b->mixed ? b->member[(size_t)i] : b->net, s, b->slot->w + (size_t)i * (size_t)b->stride); rc != RANENV_OK) return rc;
+    for (NetBind *b = binds; b < binds + n; b++) {      // a population's role: its table -- entry i = copy i's layout at copy i's address
+        if (!b->members) continue;
+        if (!b->mixed) b->member.assign((size_t)b->copies, b->net);
+        for (int i = 0; i < b->copies; i++) b->member[(size_t)i].w = b->slot->w + (size_t)i * (size_t)b->stride;
+        PolicyNet *tab = h->d_pop_tab + pop_role_of(h, b->slot) * POP_MAX;
+        if (!b->mixed) launch_net_table(s, tab, 0, b->copies, b->member[0], b->stride);
+        else for (int i = 0; i < b->copies; i++) launch_net_table(s, tab, i, 1, b->member[(size_t)i], 0);
+        HIP_TRY(h, hipGetLastError());
+    }
     for (NetBind *b = binds; b < binds + n; b++) {
-        b->slot->net = b->net; b->slot->on = true; b->slot->member_stride = b->members ? b->stride : 0;
-        for (int l = 0; l < 6; l++) b->slot->dims[l] = b->nets[0]->dims[l];
+        ranenv::NetSlot &slot = *b->slot;
+        slot.net = b->net; slot.on = true; slot.member_stride = b->members ? b->stride : 0;
+        for (int l = 0; l < 6; l++) slot.dims[l] = b->nets[0]->dims[l];
+        slot.mixed = b->mixed; slot.lds_max = 0;
+        slot.member = b->member; slot.member_dims.assign(slot.member.size(), {});
+        for (size_t i = 0; i < slot.member.size(); i++) {
+            for (int l = 0; l < 6; l++) slot.member_dims[i][(size_t)l] = b->nets[i]->dims[l];
+            const size_t lds = policy_lds_bytes(slot.member[i]);
+            slot.lds_max = lds > slot.lds_max ? lds : slot.lds_max;
+        }
     }
     return RANENV_OK;
 }
@@ -1479,7 +1567,7 @@ int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ran
     h->value_intra.on = intra != nullptr;         // (`intra`, NULL included, says what the intra critic is now)
     h->value_ps.on = false;
     h->pop_value.on = h->pop_vintra.on = false;   // (... and that the critics are no population's)
-    return RANENV_OK;
+    return pop_tables_one_net(h, (hipStream_t)stream);
 }
 
 // ---- populations: one net set per env group ------------------------------------------------------------------------------------
@@ -1498,13 +1586,14 @@ static int pop_check(ranenv_handle h, int32_t n, const int32_t *first, int batch
 int ranenv_set_population(ranenv_handle h, int32_t n_members, const int32_t *host_first_env)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (n_members == 0 && !host_first_env) { h->pop = PopMap{}; h->pop_unbind(); return RANENV_OK; }
+    if (n_members == 0 && !host_first_env) { h->pop = PopMap{}; h->pop_unbind(); h->gae_on = false; return RANENV_OK; }
     if (const int rc = pop_check(h, n_members, host_first_env, h->cfg.batch); rc != RANENV_OK) return rc;
     PopMap map{};
     map.n = n_members;
     for (int m = 0; m <= n_members; m++) map.first[m] = host_first_env[m];
     if (h->pop_bound() && memcmp(&map, &h->pop, sizeof(map)) != 0)
         return fail(h, RANENV_E_STATE, "the grouping cannot change while a population's nets are bound (ranenv_set_policy_network, or n_members 0, unbinds them)");
+    if (memcmp(&map, &h->pop, sizeof(map)) != 0) h->gae_on = false;      // (the pairs were another grouping's)
     h->pop = map;
     return RANENV_OK;
 }
@@ -1540,33 +1629,45 @@ int ranenv_population_tiles(int32_t n_members, const int32_t *first_env, int32_t
 }
 
 // ranenv_set_population_policy / _value: up to two roles' member copies (the intra array may be null) planned; the count against the grouping
-static int pop_plan(ranenv_handle h, int32_t n, NetBind *b, int n_binds)
+static int pop_plan(ranenv_handle h, int32_t n, NetBind *b, int n_binds, bool mixed = false)
 {
     if (h->pop.n == 0) return fail(h, RANENV_E_STATE, "no population set (ranenv_set_population)");
     if (n != h->pop.n) return fail(h, RANENV_E_INVALID, "%d nets given, the population has %d members", n, h->pop.n);
-    for (int i = 0; i < n_binds; i++) b[i].members = true;
+    for (int i = 0; i < n_binds; i++) { b[i].members = true; b[i].mixed = mixed; }
     return net_plan(h, b, n_binds);
 }
 
-int ranenv_set_population_policy(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
-                                 uint64_t seed, void *stream)
+static int pop_set_policy(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
+                          uint64_t seed, void *stream, bool mixed)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!inter) return fail(h, RANENV_E_INVALID, "the members' inter-slice nets are required (intra may be NULL)");
     NetBind b[2] = {{&h->pop_actor, inter, n, NET_INTER}, {&h->pop_intra, intra, n, NET_INTRA}};
     const int nb = intra ? 2 : 1;
-    int rc = pop_plan(h, n, b, nb);
+    int rc = pop_plan(h, n, b, nb, mixed);
     if (rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((rc = net_action_buffers(h)) != RANENV_OK) return rc;
+    if ((rc = net_action_buffers(h)) != RANENV_OK || (rc = pop_tables(h)) != RANENV_OK) return rc;
     if ((rc = net_commit(h, b, nb, (hipStream_t)stream)) != RANENV_OK) return rc;
     h->net_stochastic = stochastic != 0; h->net_seed = seed;
     h->pop_intra.on = intra != nullptr;           // (`intra`, NULL included, says what the intra policy is now)
     h->actor.on = h->actor_intra.on = h->actor_ps.on = h->value_ps.on = false;
-    return RANENV_OK;
+    return pop_tables_one_net(h, (hipStream_t)stream);
 }
 
-int ranenv_set_population_value(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream)
+int ranenv_set_population_policy(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
+                                 uint64_t seed, void *stream)
+{
+    return pop_set_policy(h, n, inter, intra, stochastic, seed, stream, false);
+}
+
+int ranenv_set_population_policy_mixed(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
+                                       uint64_t seed, void *stream)
+{
+    return pop_set_policy(h, n, inter, intra, stochastic, seed, stream, true);
+}
+
+static int pop_set_value(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream, bool mixed)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (!inter) return fail(h, RANENV_E_INVALID, "the members' inter-slice value nets are required (intra may be NULL)");
@@ -1576,12 +1677,23 @@ int ranenv_set_population_value(ranenv_handle h, int32_t n, const ranenv_mlp *co
         return fail(h, RANENV_E_INVALID, "intra value nets: input layout %d, the intra policy net has %d", intra[0]->input_layout, ia->layout);
     NetBind b[2] = {{&h->pop_value, inter, n, NET_INTER_VALUE}, {&h->pop_vintra, intra, n, NET_INTRA_VALUE}};
     const int nb = intra ? 2 : 1;
-    if (const int rc = pop_plan(h, n, b, nb); rc != RANENV_OK) return rc;
+    if (const int rc = pop_plan(h, n, b, nb, mixed); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (const int rc = pop_tables(h); rc != RANENV_OK) return rc;
     if (const int rc = net_commit(h, b, nb, (hipStream_t)stream); rc != RANENV_OK) return rc;
     h->pop_vintra.on = intra != nullptr;          // (`intra`, NULL included, says what the intra critic is now)
     h->value.on = h->value_intra.on = h->value_ps.on = false;
-    return RANENV_OK;
+    return pop_tables_one_net(h, (hipStream_t)stream);
+}
+
+int ranenv_set_population_value(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream)
+{
+    return pop_set_value(h, n, inter, intra, stream, false);
+}
+
+int ranenv_set_population_value_mixed(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream)
+{
+    return pop_set_value(h, n, inter, intra, stream, true);
 }
 
 int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_mlp *inter, const ranenv_mlp *intra, const ranenv_mlp *v_inter,
@@ -1589,24 +1701,99 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (member < 0 || member >= h->pop.n) return fail(h, RANENV_E_INVALID, "member %d outside the population's %d", member, h->pop.n);
-    const struct { ranenv::NetSlot *slot; const ranenv_mlp *m; NetRole role; } roles[4] = {
-        {&h->pop_actor, inter, NET_INTER}, {&h->pop_intra, intra, NET_INTRA}, {&h->pop_value, v_inter, NET_INTER_VALUE}, {&h->pop_vintra, v_intra, NET_INTRA_VALUE}};
-    for (const auto &r : roles) {           // every check of every role in front of the first device call
+    struct { ranenv::NetSlot *slot; const ranenv_mlp *m; NetRole role; PolicyNet ni; } roles[4] = {
+        {&h->pop_actor, inter, NET_INTER, {}}, {&h->pop_intra, intra, NET_INTRA, {}}, {&h->pop_value, v_inter, NET_INTER_VALUE, {}}, {&h->pop_vintra, v_intra, NET_INTRA_VALUE, {}}};
+    for (auto &r : roles) {                 // every check of every role in front of the first device call
         if (!r.m) continue;
         const char *who = NET_ROLES[r.role].who;
         if (!r.slot->on) return fail(h, RANENV_E_STATE, "%s net of member %d: the population has no %s nets bound", who, member, who);
-        PolicyNet ni{};
+        PolicyNet &ni = r.ni;
         long long floats = 0;
         if (const int rc = net_layout(h, r.m, r.role, ni, floats); rc != RANENV_OK) return rc;
         const PolicyNet &n0 = r.slot->net;
+        if (r.slot->mixed) {                // any valid shape of the role's layout and precision that fits the member's extent
+            if (ni.layout != n0.layout || ni.prec != n0.prec)
+                return fail(h, RANENV_E_INVALID, "%s net of member %d differs from the bound set in input layout or precision", who, member);
+            if (floats > r.slot->member_stride)
+                return fail(h, RANENV_E_INVALID, "%s net of member %d: its packed copy has %lld floats, the member's extent %lld (the largest member's of the bind)",
+                            who, member, floats, r.slot->member_stride);
+            continue;
+        }
         bool same = ni.n_layers == n0.n_layers && ni.act == n0.act && ni.layout == n0.layout && ni.prec == n0.prec;
         for (int l = 0; same && l <= ni.n_layers; l++) same = r.m->dims[l] == r.slot->dims[l];
         if (!same) return fail(h, RANENV_E_INVALID, "%s net of member %d differs from the bound set in shape, activation, input layout or precision", who, member);
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    for (const auto &r : roles)
-        if (r.m)
-            if (const int rc = net_copy(h, r.m, r.slot->net, (hipStream_t)stream, r.slot->w + (size_t)member * (size_t)r.slot->member_stride); rc != RANENV_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for (auto &r : roles) {
+        if (!r.m) continue;
+        ranenv::NetSlot &slot = *r.slot;
+        float *dst = slot.w + (size_t)member * (size_t)slot.member_stride;
+        if (!slot.mixed) {
+            if (const int rc = net_copy(h, r.m, slot.net, s, dst); rc != RANENV_OK) return rc;
+            continue;
+        }
+        // a mixed role: the extent zeroed, the layers at the new shape's offsets, then the member's table entry -- in that order
+        HIP_TRY(h, hipMemsetAsync(dst, 0, sizeof(float) * (size_t)slot.member_stride, s));
+        r.ni.w = dst;
+        if (const int rc = net_copy(h, r.m, r.ni, s, dst); rc != RANENV_OK) return rc;
+        launch_net_table(s, h->d_pop_tab + pop_role_of(h, r.slot) * POP_MAX, member, 1, r.ni, 0);
+        HIP_TRY(h, hipGetLastError());
+        slot.member[(size_t)member] = r.ni;
+        for (int l = 0; l < 6; l++) slot.member_dims[(size_t)member][(size_t)l] = r.m->dims[l];
+        if (member == 0) { const float *w = slot.net.w; slot.net = r.ni; slot.net.w = w; for (int l = 0; l < 6; l++) slot.dims[l] = r.m->dims[l]; }
+        slot.lds_max = 0;
+        for (const PolicyNet &x : slot.member) { const size_t lds = policy_lds_bytes(x); slot.lds_max = lds > slot.lds_max ? lds : slot.lds_max; }
+    }
+    return RANENV_OK;
+}
+
+int ranenv_get_population_net(ranenv_handle h, int32_t role, int32_t member, int32_t *n_hidden, int32_t *dims, int32_t *activation, int64_t *extent_floats,
+                              int64_t *used_floats)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (role < 0 || role > 3) return fail(h, RANENV_E_INVALID, "role %d (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)", role);
+    if (member < 0 || member >= h->pop.n) return fail(h, RANENV_E_INVALID, "member %d outside the population's %d", member, h->pop.n);
+    const ranenv::NetSlot &slot = *h->pop_slot(role);
+    if (!slot.on) return fail(h, RANENV_E_STATE, "the population has no net of role %d bound", role);
+    const PolicyNet &net = slot.member[(size_t)member];
+    if (n_hidden) *n_hidden = net.n_layers - 1;
+    if (dims) for (int l = 0; l < 6; l++) dims[l] = l <= net.n_layers ? slot.member_dims[(size_t)member][(size_t)l] : 0;
+    if (activation) *activation = net.act;
+    if (extent_floats) *extent_floats = slot.member_stride;
+    if (used_floats) *used_floats = net.b_off[net.n_layers - 1] + net.np[net.n_layers - 1] - net.w_off[0];
+    return RANENV_OK;
+}
+
+int ranenv_packed_net_floats(int32_t n_hidden, const int32_t *dims, int32_t precision, int64_t *floats)
+{
+    if (!dims || !floats) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_hidden < 1 || n_hidden > NET_MAX_LAYERS - 1) return fail(nullptr, RANENV_E_INVALID, "%d hidden layers (1..%d)", n_hidden, NET_MAX_LAYERS - 1);
+    if (precision != RANENV_NET_F32 && precision != RANENV_NET_BF16) return fail(nullptr, RANENV_E_INVALID, "unknown precision %d", precision);
+    if (dims[0] < 1 || dims[n_hidden + 1] < 1) return fail(nullptr, RANENV_E_INVALID, "input width %d, output width %d", dims[0], dims[n_hidden + 1]);
+    for (int l = 1; l <= n_hidden; l++)
+        if (dims[l] < 1 || dims[l] > NET_MAX_WIDTH) return fail(nullptr, RANENV_E_INVALID, "hidden width %d (1..%d)", dims[l], NET_MAX_WIDTH);
+    PolicyNet net{};
+    *floats = net_pack(dims, n_hidden + 1, precision, net, 0);
+    return RANENV_OK;
+}
+
+// ranenv_set_population_gae / ranenv_gae_population: n pairs for the population's n members
+static int gae_pairs_check(ranenv_handle h, int32_t n, const double *gamma, const double *lambda)
+{
+    if (h->pop.n == 0) return fail(h, RANENV_E_STATE, "no population set (ranenv_set_population)");
+    if (n != h->pop.n) return fail(h, RANENV_E_INVALID, "%d (gamma, lambda) pairs given, the population has %d members", n, h->pop.n);
+    if (!gamma || !lambda) return fail(h, RANENV_E_INVALID, "gamma and lambda are both required");
+    return RANENV_OK;
+}
+
+int ranenv_set_population_gae(ranenv_handle h, int32_t n, const double *host_gamma, const double *host_lambda)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!host_gamma && !host_lambda) { h->gae_on = false; return RANENV_OK; }
+    if (const int rc = gae_pairs_check(h, n, host_gamma, host_lambda); rc != RANENV_OK) return rc;
+    for (int m = 0; m < n; m++) { h->gae_gamma[m] = host_gamma[m]; h->gae_lambda[m] = host_lambda[m]; }
+    h->gae_on = true;
     return RANENV_OK;
 }
 
@@ -2107,12 +2294,15 @@ static int rollout_persistent(ranenv_handle h, Rollout &r, hipStream_t stream)
 
 constexpr long long COLLECT_FUSED_MAX_BYTES = 3ll << 20;      // actor + critic weights that share an XCD's 4 MB of L2 with the activations' traffic
 
-static int collect_split_of(ranenv_handle h, const PolicyNet &a, const PolicyNet *v)
+// ma / mv: the role's population slot where one is bound mixed -- it counts with its largest member, the extent of every member
+static int collect_split_of(ranenv_handle h, const PolicyNet &a, const PolicyNet *v, const ranenv::NetSlot *ma = nullptr, const ranenv::NetSlot *mv = nullptr)
 {
     if (!v) return 0;
     if (h->collect_split >= 0) return h->collect_split;
-    auto floats = [](const PolicyNet &x) { return x.b_off[x.n_layers - 1] + x.np[x.n_layers - 1] - x.w_off[0]; };
-    return (floats(a) + floats(*v)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
+    auto floats = [](const PolicyNet &x, const ranenv::NetSlot *m) {
+        return m && m->on && m->mixed ? m->member_stride : x.b_off[x.n_layers - 1] + x.np[x.n_layers - 1] - x.w_off[0];
+    };
+    return (floats(a, ma) + floats(*v, mv)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
 }
 
 // ranenv_collect / ranenv_collect_head: the recording policy launches (actors, record, critics) of envs [e0, e0 + n) on `s` into slot t of
@@ -2143,7 +2333,9 @@ static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kp
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
     // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").  Nets per
     // slice count with one slice's copy: the co-resident workgroups of a sliced launch mostly walk one slice's weights.
-    if (!critic_only) rec.split = collect_split_of(h, actor, critic) | (ia ? collect_split_of(h, *intra, vintra) << 1 : 0);
+    if (!critic_only)
+        rec.split = head ? collect_split_of(h, actor, critic)
+                         : collect_split_of(h, actor, critic, &h->pop_actor, &h->pop_value) | (ia ? collect_split_of(h, *intra, vintra, &h->pop_intra, &h->pop_vintra) << 1 : 0);
     return launch_policy(s, nets, net_io(h, kpk), &rec, e0, n);
 }
 
@@ -2298,6 +2490,12 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
             HIP_TRY(h, hipMemcpyAsync(last_reward, rec->reward + last * C, sizeof(double) * B * C, hipMemcpyDeviceToDevice, stream));
         if (rec->done && done) HIP_TRY(h, hipMemcpyAsync(done, rec->done + last, B, hipMemcpyDeviceToDevice, stream));
         if (const Record *ppo = rec->ppo; ppo && (ppo->adv || ppo->vtarg)) {
+            if (h->gae_on && !head_policy(h)) {      // ranenv_set_population_gae: member m's pair for member m's envs
+                GaePop g{};
+                g.pop = h->pop;
+                for (int m = 0; m < h->pop.n; m++) { g.gamma[m] = h->gae_gamma[m]; g.lambda[m] = h->gae_lambda[m]; }
+                launch_gae_pop(stream, n_steps, h->cfg.batch, ppo->rec.cols, rec->reward + ppo->gae_col, (int)C, ppo->rec.vf, rec->done, g, ppo->adv, ppo->vtarg);
+            } else
             launch_gae(stream, n_steps, h->cfg.batch, ppo->rec.cols, rec->reward + ppo->gae_col, (int)C, ppo->rec.vf, rec->done, ppo->gamma,
                        ppo->lambda, ppo->adv, ppo->vtarg);
             HIP_TRY(h, hipGetLastError());
@@ -2483,6 +2681,22 @@ int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *r
     if (!reward || !vf || !done) return fail(h, RANENV_E_INVALID, "GAE reads reward, vf and done");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     launch_gae((hipStream_t)stream, n_steps, h->cfg.batch, n_cols, reward, n_cols, vf, done, gamma, lambda, adv, vtarg);
+    HIP_TRY(h, hipGetLastError());
+    return RANENV_OK;
+}
+
+int ranenv_gae_population(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *reward, const float *vf, const uint8_t *done, int32_t n,
+                          const double *host_gamma, const double *host_lambda, float *adv, float *vtarg, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (n_steps < 1 || n_cols < 1) return fail(h, RANENV_E_INVALID, "n_steps and n_cols must be >= 1");
+    if (!reward || !vf || !done) return fail(h, RANENV_E_INVALID, "GAE reads reward, vf and done");
+    if (const int rc = gae_pairs_check(h, n, host_gamma, host_lambda); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    GaePop g{};
+    g.pop = h->pop;
+    for (int m = 0; m < n; m++) { g.gamma[m] = host_gamma[m]; g.lambda[m] = host_lambda[m]; }
+    launch_gae_pop((hipStream_t)stream, n_steps, h->cfg.batch, n_cols, reward, n_cols, vf, done, g, adv, vtarg);
     HIP_TRY(h, hipGetLastError());
     return RANENV_OK;
 }

@@ -229,7 +229,14 @@ __host__ __device__ inline int pop_member_tiles(const int *first, int m, int e0,
 // pair.  Null: intra = no intra actor (then vintra is null too), critic / vintra = no critic of that kind.
 // pop non-null: a population acts -- net X has a copy per member at X->w + m * stride[X] (floats; in the order actor, intra, critic,
 // vintra; 0: one net for every member), and a kind with such a net takes the population kernels.
-struct PolicyNets { bool head; const PolicyNet *actor, *intra, *critic, *vintra; const PopMap *pop = nullptr; long long stride[4] = {0, 0, 0, 0}; };
+// tab[X] non-null for the nets of a kind (ranenv_set_population_policy_mixed / _value_mixed: a role of that kind is bound with members
+// of differing shape): the kind takes the mixed kernels, which read member m's descriptor of net X from the device table tab[X]
+// (POP_MAX entries; entry m's .w is member m's packed copy; a net the launch does not run: tab_none, a table of zeros -- n_layers 0) in place of
+// "X's layout + m * stride[X]"; lds[X]: the largest policy_lds_bytes over the table's entries.
+struct PolicyNets {
+    bool head; const PolicyNet *actor, *intra, *critic, *vintra; const PopMap *pop = nullptr; long long stride[4] = {0, 0, 0, 0};
+    const PolicyNet *tab[4] = {nullptr, nullptr, nullptr, nullptr}, *tab_none = nullptr; size_t lds[4] = {0, 0, 0, 0};
+};
 // THE policy launch entry, for envs [e0, e0 + n_envs).  rec null: the acting launches (actors only; the critics are not read).  rec
 // non-null: the recording launches -- actor + critic per agent kind fused, or split by rec's bits; critic_only: the critics alone.  An
 // intra launch whose actor or critic has a slice_stride takes the sliced kernels (one workgroup column per slice).
@@ -341,6 +348,13 @@ void launch_advance(hipStream_t, unsigned n_envs, const AdvanceArgs &);
 // reward_stride: doubles between two (env, column) entries' rewards' rows, i.e. reward[(t * B + b) * reward_stride + c] (n_cols: packed)
 void launch_gae(hipStream_t, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,
                 double gamma, double lambda, float *adv, float *vtarg);
+// ... with a (gamma, lambda) pair per population member (ranenv_set_population_gae / ranenv_gae_population): env b's lanes take the pair
+// of the member that owns b.  By value in the kernel's arguments, like the grouping.
+struct GaePop { PopMap pop; double gamma[POP_MAX], lambda[POP_MAX]; };
+void launch_gae_pop(hipStream_t, int n_steps, int B, int n_cols, const double *reward, int reward_stride, const float *vf, const uint8_t *done,
+                    const GaePop &, float *adv, float *vtarg);
+// Entries [m0, m0 + n) of a population role's descriptor table: `proto` with .w advanced by `stride` floats per entry
+void launch_net_table(hipStream_t, PolicyNet *tab, int m0, int n, const PolicyNet &proto, long long stride);
 void launch_idle_traffic(hipStream_t, unsigned n_eps, const ranenv_episode *eps, const int32_t *pool, int U, const int32_t *lane_slice,
                          const int32_t *lane_ue, int *violations);
 // ranenv_collect_replay: up to two ranges of 8-byte words copied device to device in one launch (n1 = 0: one range)

@@ -254,8 +254,12 @@ __device__ __forceinline__ int active_slices(const PolicyIO &io, int e)
 // whose launch ends at the member's last row: row0 (the row map's g = row0 + r stays launch-relative) carries the member's row origin,
 // n_rows becomes the member's end row, and the tail rows of the member's last tile are dead rows like the tail rows of a launch --
 // zeros in LDS, nothing read from and nothing written to the next member's envs.
-template <bool HEAD, bool REC, bool SLICED = false, int PREC = 0, bool POP = false>
-__device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNet &vnet, const PolicyIO &io, const PolicyRec &rec, int kind, int e0,
+// POP = 2 (the mixed population kernels below, ranenv_set_population_policy_mixed / _value_mixed): `net_` / `vnet_` are entry 0 of the
+// roles' device tables; the workgroup finds its member as under POP = 1 and takes ITS entries, whose .w point at the member's packed
+// copies -- by reference: mem is scalar, the fields come by scalar loads as they are used -- and is from there on a one-net workgroup on
+// that member's own shape and activation, the LDS buffers (ldm) sized from the member's own entries.
+template <bool HEAD, bool REC, bool SLICED = false, int PREC = 0, int POP = 0>
+__device__ __forceinline__ void policy_body(const PolicyNet &net_, const PolicyNet &vnet_, const PolicyIO &io, const PolicyRec &rec, int kind, int e0,
                                             int n_rows, float *lds, const PopMap *pop = nullptr, long long wa = 0, long long wv = 0)
 {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -263,7 +267,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
     const int tiles = SLICED ? (n_rows + NET_ROWS - 1) / NET_ROWS : 1, sl = SLICED ? (int)blockIdx.x / tiles : 0;
     int row0 = (SLICED ? (int)blockIdx.x - sl * tiles : (int)blockIdx.x) * NET_ROWS;
     int mem = 0;
-    if constexpr (POP) {
+    if constexpr (POP != 0) {
         PopShare sh{0, 0};
         const int mine = lane < pop->n ? pop_member_tiles(pop->first, lane, e0, n_rows, kind == 1 ? S : 1, sh) : 0;
         int upto = mine;
@@ -280,6 +284,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         row0 = __builtin_amdgcn_readfirstlane(org + tile * NET_ROWS);
         mem = __builtin_amdgcn_readfirstlane(mem);
     }
+    const PolicyNet &net = POP == 2 ? (&net_)[mem] : net_, &vnet = POP == 2 ? (&vnet_)[mem] : vnet_;
     constexpr bool BFA = (PREC & 1) != 0, BFV = (PREC & 2) != 0;
     int ldm = net_ld_max<BFA>(net);
     if (REC && vnet.n_layers > 0) { const int lv = net_ld_max<BFV>(vnet); ldm = lv > ldm ? lv : ldm; }
@@ -299,7 +304,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
     }
     net_load_rows<REC, SLICED, BFA>(net, io, rec, kind, e0, row0, n_rows, cur, tid, sl);
     __syncthreads();
-    net_layers<BFA>(net, SLICED ? net.w + sl * net.slice_stride : (POP ? net.w + mem * wa : net.w), cur, nxt, lane, wave);
+    net_layers<BFA>(net, SLICED ? net.w + sl * net.slice_stride : (POP == 1 ? net.w + mem * wa : net.w), cur, nxt, lane, wave);
 
     // ---- epilogue: actions ----------------------------------------------------------------------------------------------
     const int ld = net_ld(net.np[net.n_layers - 1]);
@@ -398,7 +403,7 @@ __device__ __forceinline__ void policy_body(const PolicyNet &net, const PolicyNe
         const PolicyRec none{};
         net_load_rows<false, SLICED, BFV>(vnet, io, none, kind, e0, row0, n_rows, cur, tid, sl);
         __syncthreads();
-        net_layers<BFV>(vnet, SLICED ? vnet.w + sl * vnet.slice_stride : (POP ? vnet.w + mem * wv : vnet.w), cur, nxt, lane, wave);
+        net_layers<BFV>(vnet, SLICED ? vnet.w + sl * vnet.slice_stride : (POP == 1 ? vnet.w + mem * wv : vnet.w), cur, nxt, lane, wave);
         const int ldv = net_ld(vnet.np[vnet.n_layers - 1]);
         for (int r = tid; r < NET_ROWS; r += 256) {
             const int g = row0 + r;
@@ -502,7 +507,7 @@ template <int PREC>
 __global__ void __launch_bounds__(256) ranenv_policy_pop_kernel(PolicyNet net, PolicyIO io, PopMap pop, long long wa, int kind, int e0, int n_envs)
 {
     extern __shared__ float lds[];
-    policy_body<false, false, false, PREC, true>(net, net, io, PolicyRec{}, kind, e0, n_envs, lds, &pop, wa, 0);
+    policy_body<false, false, false, PREC, 1>(net, net, io, PolicyRec{}, kind, e0, n_envs, lds, &pop, wa, 0);
 }
 
 template <int PREC>
@@ -510,7 +515,24 @@ __global__ void __launch_bounds__(256) ranenv_policy_pop_collect_kernel(PolicyNe
                                                                         long long wv, int kind, int e0, int n_envs)
 {
     extern __shared__ float lds[];
-    policy_body<false, true, false, PREC, true>(net, vnet, io, rec, kind, e0, n_envs, lds, &pop, wa, wv);
+    policy_body<false, true, false, PREC, 1>(net, vnet, io, rec, kind, e0, n_envs, lds, &pop, wa, wv);
+}
+
+// A mixed population's launches (ranenv_set_population_policy_mixed / _value_mixed): the same geometry, the member's descriptors from
+// the roles' device tables (policy_body, POP = 2).
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_mixed_kernel(const PolicyNet *__restrict__ tab_a, PolicyIO io, PopMap pop, int kind, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, false, false, PREC, 2>(*tab_a, *tab_a, io, PolicyRec{}, kind, e0, n_envs, lds, &pop);
+}
+
+template <int PREC>
+__global__ void __launch_bounds__(256) ranenv_policy_mixed_collect_kernel(const PolicyNet *__restrict__ tab_a, const PolicyNet *__restrict__ tab_v, PolicyIO io,
+                                                                          PolicyRec rec, PopMap pop, int kind, int e0, int n_envs)
+{
+    extern __shared__ float lds[];
+    policy_body<false, true, false, PREC, 2>(*tab_a, *tab_v, io, rec, kind, e0, n_envs, lds, &pop);
 }
 
 // ---- SAC's soft Bellman target (ranenv_sac_targets; the arithmetic is spelled out in include/ranenv.h) -----------------------------
@@ -608,13 +630,18 @@ hipError_t launch_kernel(dim3 grid, size_t lds, hipStream_t s, const A &...args)
 
 using ranenv_dev::policy_lds_bytes;
 
+// A kind's tables under a mixed population (PolicyNets::tab): actor, critic and the table of zeros, with the largest member's LDS need of each
+struct MixedKind { const PolicyNet *tab_a, *tab_v, *tab_none; size_t lds_a, lds_v; };
+
 // One agent kind's launch(es) of a TTI for envs [e0, e0 + n_envs): the actor `a` alone (rec null), or the recording launch -- actor +
 // critic `vp` (null: none) fused, or, split, the actor's launch and then the critic alone (the kernel's critic_only mode).  THE GEOMETRY:
 // kind 0 has one row per env; an intra launch (kind 1) has the flat env x S rows, or -- sliced, when its actor or its critic has a copy
 // per slice -- one row per env in S x tiles workgroups (see policy_body).  pop non-null (a population's copies of the actor at stride
-// wa, of the critic at wv; never with nets per slice): the sum of the members' tiles, by pop_member_tiles.
+// wa, of the critic at wv; never with nets per slice): the sum of the members' tiles, by pop_member_tiles.  mx non-null (with pop): the
+// mixed kernels on the kind's tables -- `a` / `vp` then only say which precision the role has and whether there is a critic, and the
+// dynamic LDS is the largest member's need of the nets the launch runs, not member 0's.
 hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, const PolicyNet *vp, const PolicyIO &io, const PolicyRec *rec,
-                       int e0, int n_envs, bool split, const PopMap *pop = nullptr, long long wa = 0, long long wv = 0)
+                       int e0, int n_envs, bool split, const PopMap *pop = nullptr, long long wa = 0, long long wv = 0, const MixedKind *mx = nullptr)
 {
     const bool sl = kind == 1 && (a.slice_stride != 0 || (vp && vp->slice_stride != 0));
     const int rows = kind == 1 && !sl ? n_envs * io.S : n_envs;
@@ -629,7 +656,9 @@ hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, c
     const dim3 grid(tiles);
     const bool bfa = a.prec == RANENV_NET_BF16;
     if (!rec) {
-        const size_t lds = policy_lds_bytes(a);
+        const size_t lds = mx ? mx->lds_a : policy_lds_bytes(a);
+        if (mx) return bfa ? launch_kernel<ranenv_policy_mixed_kernel<1>>(grid, lds, s, mx->tab_a, io, *pop, kind, e0, n_envs)
+                           : launch_kernel<ranenv_policy_mixed_kernel<0>>(grid, lds, s, mx->tab_a, io, *pop, kind, e0, n_envs);
         if (pop) return bfa ? launch_kernel<ranenv_policy_pop_kernel<1>>(grid, lds, s, a, io, *pop, wa, kind, e0, n_envs)
                             : launch_kernel<ranenv_policy_pop_kernel<0>>(grid, lds, s, a, io, *pop, wa, kind, e0, n_envs);
         if (sl) return bfa ? launch_kernel<ranenv_policy_bf16_sliced_kernel<1>>(grid, lds, s, a, io, e0, rows) : launch_kernel<ranenv_policy_sliced_kernel>(grid, lds, s, a, io, e0, rows);
@@ -638,7 +667,7 @@ hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, c
     }
     const PolicyNet none{};               // (n_layers 0: no critic)
     auto launch = [&](const PolicyNet &v, const PolicyRec &rc) {
-        const size_t x = policy_lds_bytes(a), y = v.n_layers > 0 ? policy_lds_bytes(v) : 0, lds = x > y ? x : y;
+        const size_t x = mx ? mx->lds_a : policy_lds_bytes(a), y = v.n_layers > 0 ? (mx ? mx->lds_v : policy_lds_bytes(v)) : 0, lds = x > y ? x : y;
         auto as = [&](auto prec) {        // the recording kernels' PREC instance
             constexpr int P = decltype(prec)::value;
             if (sl) return launch_kernel<ranenv_policy_bf16_sliced_collect_kernel<P>>(grid, lds, s, a, v, io, rc, e0, rows);
@@ -648,6 +677,8 @@ hipError_t launch_kind(hipStream_t s, bool head, int kind, const PolicyNet &a, c
         const int prec = (bfa ? 1 : 0) | (v.n_layers > 0 && v.prec == RANENV_NET_BF16 ? 2 : 0);
         if (pop) {
             auto pop_as = [&](auto p) {
+                if (mx) return launch_kernel<ranenv_policy_mixed_collect_kernel<decltype(p)::value>>(grid, lds, s, mx->tab_a, v.n_layers > 0 ? mx->tab_v : mx->tab_none,
+                                                                                                     io, rc, *pop, kind, e0, n_envs);
                 return launch_kernel<ranenv_policy_pop_collect_kernel<decltype(p)::value>>(grid, lds, s, a, v, io, rc, *pop, wa, wv, kind, e0, n_envs);
             };
             switch (prec) {
@@ -690,10 +721,14 @@ hipError_t launch_policy(hipStream_t s, const PolicyNets &n, const PolicyIO &io,
     hipError_t e = hipSuccess;
     // (a kind none of whose nets has a copy per member runs the one-net kernels, population or not)
     const bool pop0 = n.pop && (n.stride[0] != 0 || (critic && n.stride[2] != 0)), pop1 = n.pop && (n.stride[1] != 0 || (vintra && n.stride[3] != 0));
+    // (a kind with a role of mixed member shapes: the mixed kernels on the roles' tables)
+    const MixedKind mx0{n.tab[0], n.tab[2], n.tab_none, n.lds[0], n.lds[2]}, mx1{n.tab[1], n.tab[3], n.tab_none, n.lds[1], n.lds[3]};
     if (!critics || critic)
-        e = launch_kind(s, n.head, 0, *n.actor, critic, io, rec, e0, n_envs, (split & 1) != 0, pop0 ? n.pop : nullptr, n.stride[0], n.stride[2]);
+        e = launch_kind(s, n.head, 0, *n.actor, critic, io, rec, e0, n_envs, (split & 1) != 0, pop0 ? n.pop : nullptr, n.stride[0], n.stride[2],
+                        pop0 && n.tab[0] ? &mx0 : nullptr);
     if (e == hipSuccess && n.intra && (!critics || vintra))
-        e = launch_kind(s, false, 1, *n.intra, vintra, io, rec, e0, n_envs, (split & 2) != 0, pop1 ? n.pop : nullptr, n.stride[1], n.stride[3]);
+        e = launch_kind(s, false, 1, *n.intra, vintra, io, rec, e0, n_envs, (split & 2) != 0, pop1 ? n.pop : nullptr, n.stride[1], n.stride[3],
+                        pop1 && n.tab[1] ? &mx1 : nullptr);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
