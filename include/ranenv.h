@@ -639,6 +639,90 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
 int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *dev_reward, const float *dev_vf, const uint8_t *dev_done,
                double gamma, double lambda, float *dev_adv, float *dev_vtarg, void *stream);
 
+/* PPO update on the device: the bound actors and critics trained on a ranenv_collect record, one workgroup per population member and
+ * agent kind (the reference's regime, agents/ray_agent.py:154-166: train batch 2048, SGD minibatch 64, 10 SGD iterations, [64, 64]
+ * nets -- 320 optimiser steps per iteration on nets of some 12 K parameters -- and its search space over lr, sgd_minibatch_size,
+ * num_sgd_iter, clip_param, entropy_coeff, vf_loss_coeff and grad_clip, :90-134, one value per trial).
+ *
+ * The loss is the one the reference configures (:346-374 with kl_coeff 0 and vf_clip_param inf), per minibatch of n rows:
+ *     L = -mean(min(r A, clamp(r, 1 - clip, 1 + clip) A)) + vf_coeff * mean((V - vtarg)^2) - ent_coeff * mean(H),   r = exp(logp - logp_old)
+ *   inter rows (kind 0; record row t * B + b; column 0 of logp / adv / vtarg): the masked Gaussian.  n_act = the row's non-zero
+ *     mask_inter entries, the active positions are j0 = S - n_act .. S - 1 (the sorted mask); z_j = (a_j - mean_j) / exp(log_std_j) from
+ *     the recorded unclamped float64 action; logp as ranenv_trajectory states it, term by term; H = sum over the active positions of
+ *     (log_std_j + 0.5) + 0.5 ln(2 pi).  The masked positions' outputs get zero gradient.
+ *   intra rows (kind 1; record row (t * B + b) * S + s; column s + 1): Categorical over the 3 logits at the recorded choice; H = -sum p ln p.
+ *   critic: one output V per row against vtarg of the same column; a kind without a bound critic has no value term.
+ *   Everything from the float32 net outputs on is float64 (as the acting epilogue); the gradient at the outputs is rounded once to
+ *   float32.  min / clamp select as torch.minimum / torch.clamp do: d(surrogate)/dr = A where 1 - clip <= r <= 1 + clip or r A < clamp(r) A,
+ *   else 0.  The forward pass is the acting launches' own code: at unchanged weights logp is re-evaluated to the bit where the recorded
+ *   z was exact (mode actions, every intra row), within 1 float32 ulp otherwise.
+ *
+ * ranenv_ppo_hparams, one per member.  epochs == 0: the member is not touched at all.  grad_clip <= 0: no clipping.
+ *   adv_norm 0: advantages as given (RLlib standardises over the whole train batch: one torch op on the record);
+ *   adv_norm 1: per minibatch (A - mean) / (std + 1e-8), unbiased std, float64 (SB3; a one-row minibatch has std 0).
+ * ranenv_ppo_bind: allocates, per bound IBSched actor and critic slot (the one-net slots and a population's uniform ones), float32
+ *   Adam moments m, v and gradient scratch in the slot's packed layout, and one step counter per (member, kind); all zero.  Refused
+ *   with RANENV_E_STATE, before any device call: no bound inter actor + critic; a bf16 net among them; intra nets per slice
+ *   (ranenv_set_intra_policy_networks / _value_networks); a mixed population; policy RANENV_POLICY_HEAD_NETWORK; a net beyond THE LDS
+ *   PLAN: the workgroup keeps the 32-row input and every layer's 32-row output of one net in LDS at once (the backward pass overwrites
+ *   them in place), 4096 + 128 * sum over the input and the layers of ld(width padded to 32) bytes with ld(x) = x + 36 if x % 64 else
+ *   x + 4, at most 163 840.  [64, 64], [256, 256] and [400, 300] fit at S 10 / Us 100; [512, 512, 512] does not.
+ *   Re-binding: a binding call (ranenv_set_policy_network, _set_value_network, _set_population_policy / _value, _set_population_member)
+ *   that fits a slot's buffer ZEROES the moments of the nets it replaces (of the one member for _set_population_member) and the
+ *   step counters of their (member, kind) -- a new net starts a new optimiser.  Actor and critic of a kind share that counter, so the
+ *   moments of the PARTNER net (the critic of a re-bound actor, the actor of a re-bound critic; its weights stay) are zeroed with it:
+ *   old moments never meet the bias correction of t = 1.  One that outgrows a slot's buffer, or binds a slot that had no state, ends the binding:
+ *   ranenv_ppo_update is RANENV_E_STATE until the next ranenv_ppo_bind.
+ * ranenv_ppo_update: the whole SGD schedule of every member in ONE launch of (n_members, 2) workgroups of 256 threads; workgroup
+ *   (m, kind) trains member m's actor + critic of that kind and touches no other net: no reduction across workgroups, no atomics, a fixed
+ *   summation order -- the same call on the same state gives the same bytes.
+ *     traj: the record as ranenv_collect filled it for n_steps TTIs (obs_inter, mask_inter, action_inter, logp, adv, vtarg required;
+ *       with intra lists also obs_intra, action_intra, and mask_intra for RANENV_NET_IN_MASK_OBS nets).
+ *     n_members: the population's member count, 1 without population nets.  host_hparams [n_members], copied at the call.
+ *     dev_order_inter / _intra: int32 [max_epochs][N_kind] record rows, max_epochs = the largest epochs, N_kind = host_first_kind[n_members];
+ *       member m's rows of epoch k are entries [host_first[m], host_first[m + 1]) of row k (host arrays [n_members + 1] from 0, non-decreasing).  The caller
+ *       supplies the shuffles; intra lists hold rows with mask_inter != 0 only.  Minibatches are consecutive chunks of `minibatch`
+ *       entries, a short last chunk is a minibatch of its own.  An entry outside the record counts as a row of the minibatch and
+ *       contributes nothing.  dev_order_intra NULL: the inter kind alone is updated.
+ *     Per minibatch: gradient of L in float32 (matrix cores; per 32-row tile, accumulated in tile order), the joint L2 norm of the
+ *       actor's and critic's gradient in float64, scale = min(1, grad_clip / (norm + 1e-6)) rounded to float32, t += 1, then per element
+ *       g = g * scale;  m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  w = w - (float)(lr / (1 - b1^t)) * (m / (sqrtf(v) / (float)sqrt(1 - b2^t) + eps))
+ *       in float32 (b1, 1 - b1, b2, 1 - b2, eps rounded from the doubles; torch.optim.Adam's order), in place in the packed buffer the acting kernels
+ *       read: the next ranenv_collect uses the new weights with no rebind.
+ *     dev_stats f64 [n_members][2][max_epochs][8] (required): per epoch the row-weighted means of [0] policy loss, [1] value loss,
+ *       [2] entropy, [3] approx-KL mean(logp_old - logp), [4] clip fraction (r < 1 - clip or r > 1 + clip), [5] pre-clip gradient norm, then [6] rows used and
+ *       [7] minibatches.  Rows of epochs a member does not run, and of kinds not updated, are not written.
+ *     dev_grad f32 [n_members][2][ranenv_ppo_layout's grad_floats] or NULL: the unclipped packed gradient, actor then critic, of the last
+ *       minibatch of each (member, kind) -- a test and diagnostic hook.
+ *   Refusals, all before any device call: no ranenv_ppo_bind (or one ended by a re-binding), or what ranenv_ppo_bind refuses:
+ *     RANENV_E_STATE; minibatch < 1, epochs < 0, another n_members, a missing record field, an ill-formed first table: RANENV_E_INVALID.
+ *   The intended regime: thousands of rows per member, nets up to a few hundred wide.  A member's cost is linear in rows x epochs and
+ *     runs on ONE compute unit; a one-member batch of 262 144 rows belongs to torch.  Every optimiser step also passes over ALL
+ *     parameters (gradient zeroing, norm, Adam), a floor per step that small minibatches do not lower.  (The Python binding refuses
+ *     rows x epochs, and optimiser steps, of one member above its caps unless forced.)
+ * ranenv_ppo_layout: floats per (member, kind) of dev_grad and the launch's LDS bytes.  ranenv_ppo_state: device pointers to member's
+ *   moments of `role` (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic) in the packed layout, the (member, kind) step counter and the packed floats.
+ * ranenv_ppo_probe_logp: a second test and diagnostic hook.  dev_logp f32 [n_steps][B][S + 1] arms the NEXT ranenv_ppo_update on the
+ *   handle, and that one alone: it writes the log-probability it re-evaluates for a row there, each time the row is used.  The update
+ *   disarms the probe as it starts, served or refused, so the handle keeps no caller's pointer beyond one call; NULL disarms it at once.
+ * ranenv_get_net_weights: the bound float32 net of `role` (as above), member `member` (0 without a population), unpacked to torch Linear
+ *   layout.  out->weight[l] / bias[l] NULL: only n_hidden, activation, input_layout, precision and dims are filled; else they are
+ *   caller-owned DEVICE buffers [dims[l + 1]][dims[l]] / [dims[l + 1]] the call writes on `stream`.  bf16 nets and nets per slice: RANENV_E_STATE. */
+typedef struct {
+    double lr, clip, vf_coeff, ent_coeff, grad_clip, beta1, beta2, eps;
+    int32_t minibatch, epochs, adv_norm, reserved;
+} ranenv_ppo_hparams;
+#define RANENV_PPO_HPARAMS_BYTES 80
+#define RANENV_PPO_STATS 8
+int ranenv_ppo_bind(ranenv_handle h, void *stream);
+int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, int32_t n_members, const ranenv_ppo_hparams *host_hparams,
+                      const int32_t *dev_order_inter, const int32_t *host_first_inter, const int32_t *dev_order_intra, const int32_t *host_first_intra,
+                      double *dev_stats, float *dev_grad, void *stream);
+int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes);
+int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats);
+int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp);
+int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv_mlp *out, void *stream);
+
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,
  * results/gen_results.py:874-1022, kept as running sums so that a rollout needs no per-TTI read-back).  Per env 8
  * float64 sums over the TTIs of the current episode (a reset zeroes them):

@@ -88,6 +88,15 @@ class Trajectory(C.Structure):
 HEAD_TRAJECTORY_FIELDS = ("obs_head", "action", "logp", "vf", "reward_head", "done", "adv", "vtarg")
 
 
+class PpoHparams(C.Structure):
+    """ranenv_ppo_hparams: one member's hyper-parameters of ranenv_ppo_update."""
+    _fields_ = [(n, C.c_double) for n in ("lr", "clip", "vf_coeff", "ent_coeff", "grad_clip", "beta1", "beta2", "eps")] + [
+        (n, C.c_int32) for n in ("minibatch", "epochs", "adv_norm", "reserved")]
+
+
+PPO_STATS = ("policy_loss", "value_loss", "entropy", "kl", "clip_frac", "grad_norm", "rows", "minibatches")
+
+
 class HeadTrajectory(C.Structure):
     """ranenv_head_trajectory: caller-owned device pointers of a ranenv_collect_head record, [t]-major (NULL = not recorded)."""
     _fields_ = [(n, C.c_void_p) for n in HEAD_TRAJECTORY_FIELDS]
@@ -205,6 +214,12 @@ FUNCTIONS = {
     "ranenv_packed_net_floats": (C.c_int, [_I32, C.POINTER(C.c_int32), _I32, C.POINTER(C.c_int64)]),
     "ranenv_set_population_gae": (C.c_int, [_P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ranenv_gae_population": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P]),
+    "ranenv_ppo_bind": (C.c_int, [_P, _P]),
+    "ranenv_ppo_update": (C.c_int, [_P, _I32, C.POINTER(Trajectory), _I32, C.POINTER(PpoHparams), _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _P, _P, _P]),
+    "ranenv_ppo_layout": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ranenv_ppo_state": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "ranenv_ppo_probe_logp": (C.c_int, [_P, _P]),
+    "ranenv_get_net_weights": (C.c_int, [_P, _I32, _I32, C.POINTER(Mlp), _P]),
 }
 POPULATION_MAX = 64
 POPULATION_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}

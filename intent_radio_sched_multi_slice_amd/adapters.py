@@ -501,6 +501,165 @@ def gae(reward, vf, done, gamma: float = 0.99, lam: float = 0.95):
     return adv, vtarg
 
 
+# --------------------------------------------------------------------------------------------
+# the PPO update (ranenv_ppo_update, include/ranenv.h "PPO update"): the shuffles it takes and its float64 restatement
+# --------------------------------------------------------------------------------------------
+HALF_LN_2PI = 0.9189385332046727
+LN_1E9 = 20.72326583694641
+
+
+def ppo_row_order(rec, first_env, epochs: int, seed: int = 0, intra: bool = True) -> Dict[str, object]:
+    """The row lists of ``ppo_update`` for a ``collect()`` record: per epoch and member an independent shuffle of the member's rows,
+    built where the record lives in one batched ``argsort`` per kind.  ``first_env`` [G + 1]: the population's grouping (``[0, B]``: one
+    member).  Inter rows are ``t * B + b`` for every TTI t and env b of the member; intra rows ``(t * B + b) * S + s`` for the slices
+    that were live at that TTI (``mask_inter != 0``) only.  Returns ``order_inter`` int32 [epochs, N_inter] and ``first_inter`` int32
+    [G + 1] (member m's rows of an epoch: entries ``first[m] .. first[m + 1] - 1``), and the same for "intra" (None with ``intra=False``)."""
+    mask = rec["mask_inter"]
+    T, B, S = mask.shape
+    dev = mask.device
+    first = np.asarray(first_env, dtype=np.int64)
+    G = len(first) - 1
+    if first[0] != 0 or first[-1] != B or np.any(np.diff(first) <= 0):
+        raise ValueError(f"first_env runs from 0 to {B} strictly increasing")
+    member_of_env = torch.repeat_interleave(torch.arange(G, device=dev), torch.as_tensor(np.diff(first), device=dev))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+
+    def shuffled(rows, member):               # rows ascending; member [n] of each
+        counts = torch.bincount(member, minlength=G).cpu().numpy()
+        by_member = torch.argsort(member, stable=True)
+        rows, member = rows[by_member], member[by_member]
+        keys = (member.to(torch.int64) << 32)[None, :] + torch.randint(0, 2 ** 31, (int(epochs), rows.numel()), generator=gen, device=dev)
+        # (31 random bits per row tie now and then; a stable sort makes "same seed, same order" independent of the sort's tie handling)
+        order = rows[torch.argsort(keys, dim=1, stable=True)].to(torch.int32).contiguous()
+        return order, np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+
+    rows = torch.arange(T * B, device=dev)
+    out = {"order_intra": None, "first_intra": None}
+    out["order_inter"], out["first_inter"] = shuffled(rows, member_of_env[rows % B])
+    if intra:
+        rows = (mask != 0).reshape(-1).nonzero().squeeze(1)
+        out["order_intra"], out["first_intra"] = shuffled(rows, member_of_env[(rows // S) % B])
+    return out
+
+
+def ppo_rows(rec, kind: str, rows, layout: str = "obs", dtype=torch.float64) -> Dict[str, torch.Tensor]:
+    """The record rows ``rows`` (``ppo_row_order``'s numbering) of ``kind`` "inter" / "intra" as the update reads them: the net input
+    "x", the recorded action ("action" [n, S] with the sorted mask "active", or "choice" [n]) and "logp", "adv", "vtarg" of the row's column."""
+    rows = torch.as_tensor(rows, dtype=torch.int64, device=rec["logp"].device)
+    S = rec["mask_inter"].shape[-1]
+    cols = lambda name, r, c: rec[name][:rec["logp"].shape[0]].reshape(-1, S + 1)[r, c].to(dtype)  # noqa: E731
+    if kind == "inter":
+        out = {"x": rec["obs_inter"].reshape(-1, 10 * S)[rows].to(dtype), "action": rec["action_inter"].reshape(-1, S)[rows].to(dtype),
+               "active": sorted_action_mask(rec["mask_inter"].reshape(-1, S)[rows]) != 0}
+        r, c = rows, torch.zeros_like(rows)
+    else:
+        W = rec["obs_intra"].shape[-1]
+        x = rec["obs_intra"].reshape(-1, W)[rows].to(dtype)
+        if layout == "mask_obs":
+            x = torch.cat([rec["mask_intra"].reshape(-1, rec["mask_intra"].shape[-1])[rows].to(dtype), x], dim=1)
+        out = {"x": x, "choice": rec["action_intra"].reshape(-1)[rows].to(torch.int64)}
+        r, c = rows // S, 1 + rows % S
+    out.update(logp=cols("logp", r, c), adv=cols("adv", r, c), vtarg=cols("vtarg", r, c))
+    return out
+
+
+def ppo_loss_reference(actor, critic, batch, kind: str, clip: float, vf_coeff: float, ent_coeff: float, adv_norm: bool, act_actor: str = "tanh",
+                       act_critic: str = "tanh", slip: Optional[str] = None):
+    """The minibatch loss of ``ppo_update`` in torch (autograd differentiates it): ``actor`` / ``critic`` (None: no value term) lists of
+    ``(W, b)`` in the dtype to compute in, ``batch`` from ``ppo_rows``.  Returns (loss, {policy_loss, value_loss, entropy, kl,
+    clip_frac, logp}).  ``slip``: a deliberately wrong variant, for the tests that show the tolerances bite."""
+    def forward(x, layers, act):
+        for i, (w, b) in enumerate(layers):
+            x = x @ w.T + b
+            if i < len(layers) - 1:
+                y = torch.tanh(x) if act == "tanh" else torch.relu(x)
+                x = y.detach() + (x - x.detach()) if slip == "no_activation_derivative" else y
+        return x
+    out = forward(batch["x"], actor, act_actor)
+    if kind == "inter":
+        S = batch["action"].shape[1]
+        mean, ls = out[:, :S], out[:, S:]
+        active = torch.ones_like(batch["active"]) if slip == "masked_gradient" else batch["active"]
+        z = (batch["action"] - mean) / torch.exp(ls)
+        zero = torch.zeros_like(z)
+        logp = torch.where(active, (-0.5 * z) * z - ls - HALF_LN_2PI, zero).sum(dim=1) + (~batch["active"]).sum(dim=1).to(z.dtype) * (LN_1E9 - HALF_LN_2PI)
+        entropy = torch.where(active, ls + 0.5 + HALF_LN_2PI, zero).sum(dim=1)
+    else:
+        lsm = torch.log_softmax(out, dim=1)
+        logp = lsm.gather(1, batch["choice"][:, None])[:, 0]
+        entropy = -(torch.exp(lsm) * lsm).sum(dim=1)
+    adv, n = batch["adv"], batch["adv"].numel()
+    if adv_norm:
+        adv = (adv - adv.mean()) / ((adv.std() if n > 1 else torch.zeros((), dtype=adv.dtype)) + 1e-8)
+    mean_of = (lambda v: v.sum() / 32.0) if slip == "mean_over_32" else (lambda v: v.mean())
+    ratio = torch.exp(logp - batch["logp"])
+    surrogate = ratio * adv if slip == "unclipped" else torch.minimum(ratio * adv, ratio.clamp(1.0 - clip, 1.0 + clip) * adv)
+    stats = {"policy_loss": -mean_of(surrogate), "entropy": mean_of(entropy), "kl": mean_of(batch["logp"] - logp),
+             "clip_frac": mean_of(((ratio < 1.0 - clip) | (ratio > 1.0 + clip)).to(ratio.dtype)), "logp": logp, "value_loss": torch.zeros((), dtype=ratio.dtype)}
+    loss = stats["policy_loss"] - (-ent_coeff if slip == "entropy_sign" else ent_coeff) * stats["entropy"]
+    if critic is not None:
+        stats["value_loss"] = mean_of((forward(batch["x"], critic, act_critic)[:, 0] - batch["vtarg"]) ** 2)
+        loss = loss + vf_coeff * stats["value_loss"]
+    return loss, stats
+
+
+def ppo_adam_reference(params, grads, state, lr: float, grad_clip: float, betas=(0.9, 0.999), eps: float = 1e-8, slip: Optional[str] = None):
+    """Joint gradient clip (``clip_grad_norm_``: scale = min(1, grad_clip / (norm + 1e-6)); ``grad_clip`` <= 0: none) and one Adam step
+    in torch.optim.Adam's operation order, in the tensors' dtype and in place: ``params`` / ``grads`` lists of tensors, ``state``
+    {"m": [...], "v": [...], "t": int} (empty dict: a new optimiser).  Returns the pre-clip norm."""
+    if not state:
+        state.update(m=[torch.zeros_like(p) for p in params], v=[torch.zeros_like(p) for p in params], t=0)
+    norm = torch.sqrt(sum((g.to(torch.float64) ** 2).sum() for g in grads))
+    scale = min(1.0, grad_clip / (float(norm) + 1e-6)) if grad_clip > 0 else 1.0
+    state["t"] += 1
+    b1, b2, t = betas[0], betas[1], state["t"]
+    bc1, bc2 = (1.0, 1.0) if slip == "no_bias_correction" else (1.0 - b1 ** t, 1.0 - b2 ** t)
+    for p, g, m, v in zip(params, grads, state["m"], state["v"]):
+        g = g * scale
+        m.mul_(b1).add_((1.0 - b1) * g)
+        v.mul_(b2).add_(((1.0 - b2) * g) * g)
+        p.sub_((lr / bc1) * (m / (torch.sqrt(v) / np.sqrt(bc2) + eps)))
+    return float(norm)
+
+
+def ppo_update_reference(rec, kind: str, actor, critic, order, lo: int, hi: int, epochs: int = 10, minibatch: int = 64, lr: float = 3e-4,
+                         clip: float = 0.2, vf_coeff: float = 0.5, ent_coeff: float = 0.01, grad_clip: float = 0.5, adv_norm: bool = True,
+                         betas=(0.9, 0.999), eps: float = 1e-8, act_actor: str = "tanh", act_critic: str = "tanh", layout: str = "obs",
+                         state: Optional[dict] = None, dtype=torch.float64, slip: Optional[str] = None):
+    """THE NORMATIVE STATEMENT of ``ppo_update`` for one member and kind, float64 torch autograd on the CPU: ``actor`` / ``critic`` lists
+    of ``(W, b)`` (copied), the member's rows of epoch k are ``order[k, lo:hi]``, minibatches consecutive chunks of ``minibatch`` with a
+    short last one.  Returns {"actor", "critic": the trained layers, "state": Adam's, "stats": float64 [epochs, 8] as ``_lib.PPO_STATS``,
+    "grad": the last minibatch's unclipped gradients as lists of (dW, db) for actor and critic}."""
+    cpu = {k: v.detach().cpu() for k, v in rec.items() if isinstance(v, torch.Tensor)}
+    order = torch.as_tensor(order).cpu().to(torch.int64)
+    copy = lambda net: None if net is None else [(w.detach().cpu().to(dtype).clone().requires_grad_(True), b.detach().cpu().to(dtype).clone().requires_grad_(True))  # noqa: E731
+                                                  for w, b in net]
+    actor, critic = copy(actor), copy(critic)
+    params = [p for net in (actor, critic) if net is not None for wb in net for p in wb]
+    state = {} if state is None else state
+    stats, grads = np.zeros((epochs, 8)), None
+    n = hi - lo
+    for ep in range(epochs):
+        acc = np.zeros(6)
+        n_mb = 0
+        for c0 in range(0, n, minibatch):
+            rows = order[ep, lo + c0:lo + min(c0 + minibatch, n)]
+            batch = ppo_rows(cpu, kind, rows, layout, dtype)
+            loss, st = ppo_loss_reference(actor, critic, batch, kind, clip, vf_coeff, ent_coeff, adv_norm, act_actor, act_critic, slip)
+            grads = torch.autograd.grad(loss, params)
+            with torch.no_grad():
+                norm = ppo_adam_reference(params, list(grads), state, lr, grad_clip, betas, eps, slip)
+            nb = rows.numel()
+            acc += nb * np.array([float(st[k].detach()) for k in ("policy_loss", "value_loss", "entropy", "kl", "clip_frac")] + [norm])
+            n_mb += 1
+        stats[ep, :6], stats[ep, 6], stats[ep, 7] = acc / n, n, n_mb
+    pairs = lambda flat: [(flat[2 * i], flat[2 * i + 1]) for i in range(len(flat) // 2)]  # noqa: E731
+    na = 2 * len(actor)
+    return {"actor": [(w.detach(), b.detach()) for w, b in actor], "critic": None if critic is None else [(w.detach(), b.detach()) for w, b in critic],
+            "state": state, "stats": stats, "grad": {"actor": pairs(list(grads[:na])), "critic": pairs(list(grads[na:]))}}
+
+
 def rllib_per_slice_layers(weights_by_policy, S: int, policy_prefix: str = "intra_slice_sched_"):
     """The S intra policies of a non-shared IBSched checkpoint (agents/ray_agent.py:432-460) from ``{policy_id: state_dict}`` as
     ``Algorithm.get_weights()`` returns it: ``(actors, critics)``, two lists of S layer stacks in slice order -- entry s from

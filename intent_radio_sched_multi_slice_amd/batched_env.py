@@ -806,6 +806,147 @@ class BatchedRanEnv:
                                              self._stream()), "ranenv_gae")
         return adv, vtarg
 
+    # -- the PPO update on the device (ranenv_ppo_bind / ranenv_ppo_update; include/ranenv.h "PPO update") ---------------------------
+    PPO_ROW_EPOCHS_CAP = 1 << 20       # rows x epochs of ONE member (one compute unit works through them); the reference's regime is 2048 x 10
+    # Optimiser steps of ONE member in a launch: a step zeroes the gradient, takes the norm and runs Adam over ALL parameters, a floor
+    # no row count lowers.  The reference's search space needs 2048 / 8 x 20 = 5120 at the most, its default regime 320; at the 0.19 ms
+    # ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
+    PPO_STEPS_CAP = 1 << 13
+
+    def ppo_bind(self) -> None:
+        """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
+        one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header)."""
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_ppo_bind(self._h, self._stream()), "ranenv_ppo_bind")
+
+    def _ppo_members(self) -> int:
+        """Members the update trains: the population's while its inter actors are bound, else 1 (the library's own rule)."""
+        if getattr(self, "_population", None) is None:
+            return 1
+        bound = self._lib.ranenv_get_population_net(self._h, 0, 0, None, None, None, None, None) == 0
+        return len(self._population) - 1 if bound else 1
+
+    def ppo_update(self, rec, epochs=10, minibatch=64, lr=3e-4, clip=0.2, vf_coeff=0.5, ent_coeff=0.01, grad_clip=0.5, adv_norm="minibatch",
+                   betas=(0.9, 0.999), eps=1e-8, seed=0, order=None, grad: bool = False, probe_logp: bool = False, force: bool = False):
+        """Train the bound nets on the ``collect()`` record ``rec`` in one launch (ranenv_ppo_update): per member ``epochs`` passes
+        over its rows in shuffled minibatches of ``minibatch`` rows -- clipped-surrogate PPO loss, joint gradient clip, Adam -- written
+        in place, so the next ``collect()`` acts on the new weights.  Every hyper-parameter is a scalar or a sequence with one value
+        per member of the population (``betas``: one pair for all); ``grad_clip`` <= 0 or None: no clipping; ``adv_norm``:
+        "minibatch" (SB3's per-minibatch standardisation) or None (as given: standardise the record's ``adv`` yourself, as RLlib does).
+        ``order``: the shuffles as ``adapters.ppo_row_order`` returns them (default: drawn from ``seed``); without "order_intra" only the
+        inter nets are trained.  Returns {name: float64 array [G, 2, max epochs]} for the names of ``_lib.PPO_STATS`` (kind 0 inter, 1
+        intra); ``grad=True`` adds "grad" [G, 2, floats], the last minibatch's unclipped packed gradient (actor, then critic), and
+        ``probe_logp=True`` "logp" [T, B, S + 1], the log-probabilities the update re-evaluated.  A member works on ONE compute unit: more
+        than ``PPO_ROW_EPOCHS_CAP`` rows x epochs or ``PPO_STEPS_CAP`` optimiser steps for one member is refused unless ``force`` -- such
+        a batch belongs to torch."""
+        G = self._ppo_members()
+        def per_member(x, name, dtype=np.float64):      # noqa: E306
+            a = np.asarray(x, dtype=dtype).reshape(-1) if np.ndim(x) > 0 else np.full(G, x, dtype=dtype)
+            if a.size != G:
+                raise ValueError(f"{name}: {a.size} values given, one per member is {G}")
+            return a
+        norm = [adv_norm] * G if adv_norm is None or isinstance(adv_norm, str) else list(adv_norm)
+        if len(norm) != G or any(x not in ("minibatch", "none", None) for x in norm):
+            raise ValueError('adv_norm is "minibatch" or None, one for all or one per member')
+        cols = {"lr": per_member(lr, "lr"), "clip": per_member(clip, "clip"), "vf_coeff": per_member(vf_coeff, "vf_coeff"),
+                "ent_coeff": per_member(ent_coeff, "ent_coeff"), "grad_clip": per_member(0.0 if grad_clip is None else grad_clip, "grad_clip"),
+                "eps": per_member(eps, "eps"), "minibatch": per_member(minibatch, "minibatch", np.int64), "epochs": per_member(epochs, "epochs", np.int64)}
+        hp = (_lib.PpoHparams * G)()
+        for m in range(G):
+            for k, v in cols.items():
+                setattr(hp[m], k, v[m].item())
+            hp[m].beta1, hp[m].beta2, hp[m].adv_norm = float(betas[0]), float(betas[1]), 1 if norm[m] == "minibatch" else 0
+        max_epochs = int(cols["epochs"].max())
+        T = int(rec["logp"].shape[0])
+        if order is None:
+            from .adapters import ppo_row_order
+            first_env = self._population if G > 1 else [0, self.B]
+            order = ppo_row_order(rec, first_env, max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec)
+        kinds = [k for k in ("inter", "intra") if order.get("order_" + k) is not None]
+        firsts = {}
+        for k in kinds:
+            o, f = order["order_" + k], np.ascontiguousarray(order["first_" + k], dtype=np.int32)
+            if f.size != G + 1 or o.dtype != torch.int32 or o.dim() != 2 or o.shape[0] < max_epochs or o.shape[1] != int(f[-1]) or not o.is_contiguous():
+                raise ValueError(f"order_{k}: int32 [>= {max_epochs} epochs, first_{k}[-1]] with first_{k} of {G + 1} entries")
+            if not force and int((np.diff(f) * cols["epochs"]).max()) > self.PPO_ROW_EPOCHS_CAP:
+                raise RanEnvError(f"ppo_update: a member has more than {self.PPO_ROW_EPOCHS_CAP} rows x epochs ({k}); one compute unit works "
+                                  "through a member's rows -- train such a batch in torch, or pass force=True")
+            steps = -(-np.diff(f).astype(np.int64) // np.maximum(cols["minibatch"], 1)) * cols["epochs"]
+            if not force and int(steps.max()) > self.PPO_STEPS_CAP:
+                raise RanEnvError(f"ppo_update: a member has more than {self.PPO_STEPS_CAP} optimiser steps ({k}: {int(steps.max())}); every step "
+                                  "passes over all parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
+            firsts[k] = f
+        if "inter" not in kinds:
+            raise ValueError("order needs order_inter / first_inter")
+        traj, keep = _lib.Trajectory(), []
+        for f in _lib.TRAJECTORY_FIELDS:
+            if f in rec:
+                dt, extra, shape = self.TRAJECTORY_SHAPES[f]
+                keep.append(self._dev(rec[f], dt, (T + extra,) + shape(self.B, self.S, self.Us, self.W), f))
+                setattr(traj, f, keep[-1].data_ptr())
+        stats = torch.zeros((G, 2, max(max_epochs, 1), len(_lib.PPO_STATS)), dtype=torch.float64, device=self.device)
+        gbuf = None
+        if grad:
+            gf = C.c_int64()
+            self._check(self._lib.ranenv_ppo_layout(self._h, C.byref(gf), None), "ranenv_ppo_layout")
+            gbuf = torch.zeros((G, 2, gf.value), dtype=torch.float32, device=self.device)
+        lbuf = torch.zeros((T, self.B, self.S + 1), dtype=torch.float32, device=self.device) if probe_logp else None
+        _pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        none = torch.zeros(1, dtype=torch.int32, device=self.device)      # (a list without rows still is a list: not NULL)
+        lists = {k: order["order_" + k] if order["order_" + k].numel() else none for k in kinds}
+        with torch.cuda.device(self.device):
+            if probe_logp:          # (armed for the one update below, which disarms it whether it is served or refused)
+                self._check(self._lib.ranenv_ppo_probe_logp(self._h, _ptr(lbuf)), "ranenv_ppo_probe_logp")
+            self._check(self._lib.ranenv_ppo_update(
+                self._h, T, C.byref(traj), G, hp, _ptr(lists["inter"]), _pi(firsts["inter"]),
+                _ptr(lists["intra"]) if "intra" in kinds else None, _pi(firsts["intra"]) if "intra" in kinds else None,
+                _ptr(stats), _ptr(gbuf), self._stream()), "ranenv_ppo_update")
+        host = stats.cpu().numpy()             # (synchronises: the launch is over, `order` and `rec` may go)
+        out = {name: host[..., i] for i, name in enumerate(_lib.PPO_STATS)}
+        if grad:
+            out["grad"] = gbuf
+        if probe_logp:
+            out["logp"] = lbuf
+        return out
+
+    _NET_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}
+
+    def net_weights(self, role: str, m: int = 0):
+        """The bound float32 net of ``role`` ("inter", "intra", "v_inter", "v_intra"), member ``m`` of a population, as it is on the
+        device NOW -- after ``ppo_update``: the trained net -- as a list of ``(W, b)`` tensors in torch ``Linear`` layout
+        (ranenv_get_net_weights); with ``net_activation(role, m)`` what ``set_policy_network`` takes."""
+        layers, _ = self._net_weights(role, m)
+        return layers
+
+    def net_activation(self, role: str, m: int = 0) -> str:
+        return self._net_weights(role, m, copy=False)[1]
+
+    def _net_weights(self, role: str, m: int, copy: bool = True):
+        if role not in self._NET_ROLES:
+            raise ValueError(f"role must be one of {sorted(self._NET_ROLES)}")
+        out = _lib.Mlp()
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_get_net_weights(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), "ranenv_get_net_weights")
+            act = {v: k for k, v in NET_ACTIVATIONS.items()}[out.activation]
+            if not copy:
+                return None, act
+            dims = list(out.dims[:out.n_hidden + 2])
+            layers = [(torch.empty((dims[i + 1], dims[i]), dtype=torch.float32, device=self.device),
+                       torch.empty((dims[i + 1],), dtype=torch.float32, device=self.device)) for i in range(len(dims) - 1)]
+            for i, (w, b) in enumerate(layers):
+                out.weight[i], out.bias[i] = w.data_ptr(), b.data_ptr()
+            self._check(self._lib.ranenv_get_net_weights(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), "ranenv_get_net_weights")
+        return layers, act
+
+    def ppo_state(self, role: str, m: int = 0) -> Dict[str, torch.Tensor]:
+        """Zero-copy views of the optimiser state of ``role``'s net of member ``m`` (ranenv_ppo_state): Adam's "m" and "v" in the packed
+        layout (float32 [floats]) and "t", the (member, kind) step counter (int32 [1])."""
+        pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._lib.ranenv_ppo_state(self._h, self._NET_ROLES[role], int(m), C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), "ranenv_ppo_state")
+        return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
+                "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
+                "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}
+
     # -- the learned baselines SchedTWC / SchedColORAN (RANENV_POLICY_HEAD_NETWORK) ------------------------------------------------
     def set_head_policy_network(self, actor, dist: str = "gauss_clip", log_std=None, stochastic: bool = False, seed: int = 0,
                                 activation: Optional[str] = None, allow_sorted: bool = False, fixed_intra: Optional[int] = None,

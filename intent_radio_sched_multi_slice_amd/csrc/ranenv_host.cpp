@@ -111,6 +111,7 @@ struct ranenv {
     struct NetSlot {
         PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; long long member_stride = 0; int32_t dims[6] = {};
         bool mixed = false; std::vector<PolicyNet> member; std::vector<std::array<int32_t, 6>> member_dims; size_t lds_max = 0;
+        float *opt = nullptr; long long opt_cap = 0;      // ranenv_ppo_bind: Adam's m, v and the gradient scratch, opt_cap floats each, in the packed layout
     };
     // ranenv_set_policy_network (actor, actor_intra: the shared intra net) and ranenv_set_intra_policy_networks (actor_ps: one intra net
     // per slice, standing where the shared one stands while on); the same three for their critics (ranenv_set_value_network,
@@ -129,6 +130,9 @@ struct ranenv {
     const NetSlot *pop_slot(int role) const { return const_cast<ranenv *>(this)->pop_slot(role); }
     const NetSlot *one_slot(int role) const { return role == 0 ? &actor : (role == 1 ? &actor_intra : (role == 2 ? &value : &value_intra)); }
     bool pop_mixed() const { for (int r = 0; r < 4; r++) if (pop_slot(r)->on && pop_slot(r)->mixed) return true; return false; }
+    // ranenv_ppo_bind / ranenv_ppo_update: bound?, the (member, kind) step counters [POP_MAX][2], the call's hyper-parameters on the
+    // device [POP_MAX], the diagnostic log-probability buffer the NEXT update takes and forgets
+    bool ppo_on = false; int32_t *d_ppo_t = nullptr; ranenv_ppo_hparams *d_ppo_hp = nullptr; float *ppo_probe = nullptr;
     // ranenv_set_population_gae: a (gamma, lambda) pair per member for ranenv_collect's GAE pass
     bool gae_on = false; double gae_gamma[POP_MAX] = {}, gae_lambda[POP_MAX] = {};
     bool pop_bound() const { return pop_actor.on || pop_intra.on || pop_value.on || pop_vintra.on; }
@@ -1388,6 +1392,8 @@ static int pop_tables_one_net(ranenv_handle h, hipStream_t s)
 
 // COMMIT, on the caller's stream without a host sync: every slot's buffer grown -- the outgrown one stays allocated, the launches of
 // earlier calls may still read it -- or zeroed over the new nets' extent; then every copy's layers; then the slots change, all or none.
+static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s);
+
 static int net_commit(ranenv_handle h, NetBind *binds, int n, hipStream_t s)
 {
     for (NetBind *b = binds; b < binds + n; b++) {
@@ -1424,6 +1430,8 @@ static int net_commit(ranenv_handle h, NetBind *binds, int n, hipStream_t s)
             slot.lds_max = lds > slot.lds_max ? lds : slot.lds_max;
         }
     }
+    for (NetBind *b = binds; b < binds + n; b++)
+        if (const int rc = ppo_rebound(h, b->slot, -1, s); rc != RANENV_OK) return rc;
     return RANENV_OK;
 }
 
@@ -1731,6 +1739,7 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
         float *dst = slot.w + (size_t)member * (size_t)slot.member_stride;
         if (!slot.mixed) {
             if (const int rc = net_copy(h, r.m, slot.net, s, dst); rc != RANENV_OK) return rc;
+            if (const int rc = ppo_rebound(h, &slot, member, s); rc != RANENV_OK) return rc;
             continue;
         }
         // a mixed role: the extent zeroed, the layers at the new shape's offsets, then the member's table entry -- in that order
@@ -1794,6 +1803,245 @@ int ranenv_set_population_gae(ranenv_handle h, int32_t n, const double *host_gam
     if (const int rc = gae_pairs_check(h, n, host_gamma, host_lambda); rc != RANENV_OK) return rc;
     for (int m = 0; m < n; m++) { h->gae_gamma[m] = host_gamma[m]; h->gae_lambda[m] = host_lambda[m]; }
     h->gae_on = true;
+    return RANENV_OK;
+}
+
+// ---- PPO update (include/ranenv.h "PPO update"; the kernel: ranenv_ppo.hip) -----------------------------------------------------
+static_assert(sizeof(ranenv_ppo_hparams) == RANENV_PPO_HPARAMS_BYTES, "ranenv_ppo_hparams: 8 doubles and 4 int32");
+
+// Floats of one packed copy of `net`
+static long long net_floats(const PolicyNet &net) { return net.b_off[net.n_layers - 1] + net.np[net.n_layers - 1]; }
+
+// The slots the update trains, in the order inter actor, intra actor, inter critic, intra critic (null: none bound), and the member
+// count -- or what ranenv_ppo_bind refuses.  No device call.
+static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
+{
+    if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
+    if (h->actor_ps.on || h->value_ps.on) return fail(h, RANENV_E_STATE, "the PPO update does not train intra nets per slice (non-shared intra policies)");
+    if (h->pop_mixed()) return fail(h, RANENV_E_STATE, "the PPO update does not train a mixed population");
+    ranenv::NetSlot *one[4] = {&h->actor, &h->actor_intra, &h->value, &h->value_intra};
+    int n_pop = 0, n_one = 0;
+    for (int r = 0; r < 4; r++) {
+        slot[r] = h->pop_slot(r)->on ? h->pop_slot(r) : (one[r]->on ? one[r] : nullptr);
+        if (slot[r]) (h->pop_slot(r)->on ? n_pop : n_one) += 1;
+    }
+    if (!slot[0] || !slot[2]) return fail(h, RANENV_E_STATE, "the PPO update needs a bound inter actor and inter critic (ranenv_set_policy_network, ranenv_set_value_network)");
+    if (n_pop && n_one) return fail(h, RANENV_E_STATE, "the PPO update needs every net per member or every net single: a net the members share has no one owner");
+    members = n_pop ? h->pop.n : 1;
+    for (int r = 0; r < 4; r++)
+        if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
+    for (int k = 0; k < 2; k++) {
+        if (!slot[k]) continue;
+        const size_t lds = ppo_lds_bytes(slot[k]->net, slot[2 + k] ? &slot[2 + k]->net : nullptr);
+        if (lds > (size_t)PPO_LDS_MAX)
+            return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+    }
+    return RANENV_OK;
+}
+
+// A binding call has replaced `slot`'s nets (member < 0: all of them): their moments and their (member, kind) step counters start
+// again, on the caller's stream -- or, where the slot has no moments of its size, the PPO binding ends.
+static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s)
+{
+    if (!h->ppo_on) return RANENV_OK;
+    ranenv::NetSlot *all[8] = {&h->actor, &h->actor_intra, &h->value, &h->value_intra, &h->pop_actor, &h->pop_intra, &h->pop_value, &h->pop_vintra};
+    int at_r = -1;
+    for (int r = 0; r < 8; r++) if (all[r] == slot) at_r = r;
+    if (at_r < 0) return RANENV_OK;
+    const int kind = at_r & 1;
+    if (!slot->opt || slot->cap > slot->opt_cap) { h->ppo_on = false; return RANENV_OK; }
+    // (actor and critic of a kind share the step counter: the partner net -- critic of an actor, actor of a critic -- restarts with it,
+    //  or its old moments would meet the bias correction of t = 1)
+    ranenv::NetSlot *both[2] = {slot, all[at_r ^ 2]};
+    for (ranenv::NetSlot *x : both) {
+        if (!x->on || !x->opt || x->cap > x->opt_cap) continue;
+        if (member < 0) {
+            HIP_TRY(h, hipMemsetAsync(x->opt, 0, sizeof(float) * 2 * (size_t)x->opt_cap, s));
+            continue;
+        }
+        const size_t at = (size_t)member * (size_t)x->member_stride, n = (size_t)net_floats(x->net);
+        HIP_TRY(h, hipMemsetAsync(x->opt + at, 0, sizeof(float) * n, s));
+        HIP_TRY(h, hipMemsetAsync(x->opt + x->opt_cap + at, 0, sizeof(float) * n, s));
+    }
+    if (member < 0) HIP_TRY(h, hipMemset2DAsync(h->d_ppo_t + kind, 2 * sizeof(int32_t), 0, sizeof(int32_t), POP_MAX, s));
+    else HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + member * 2 + kind, 0, sizeof(int32_t), s));
+    return RANENV_OK;
+}
+
+int ranenv_ppo_bind(ranenv_handle h, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    ranenv::NetSlot *slot[4];
+    int members = 0;
+    if (const int rc = ppo_roles(h, slot, members); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->d_ppo_t) {
+        if (const int rc = dev_alloc(h, &h->d_ppo_t, (size_t)POP_MAX * 2); rc != RANENV_OK) return rc;
+        if (const int rc = dev_alloc(h, &h->d_ppo_hp, (size_t)POP_MAX); rc != RANENV_OK) return rc;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->d_ppo_t, 0, sizeof(int32_t) * POP_MAX * 2, s));
+    for (int r = 0; r < 4; r++) {
+        if (!slot[r]) continue;
+        if (slot[r]->opt_cap < slot[r]->cap) {       // (an outgrown one stays allocated, like the weights')
+            if (const int rc = dev_alloc(h, &slot[r]->opt, 3 * (size_t)slot[r]->cap); rc != RANENV_OK) return rc;
+            slot[r]->opt_cap = slot[r]->cap;
+        }
+        HIP_TRY(h, hipMemsetAsync(slot[r]->opt, 0, sizeof(float) * 3 * (size_t)slot[r]->opt_cap, s));
+    }
+    h->ppo_on = true;
+    return RANENV_OK;
+}
+
+// The bound state behind ranenv_ppo_bind, or RANENV_E_STATE
+static int ppo_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
+{
+    if (!h->ppo_on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
+    if (const int rc = ppo_roles(h, slot, members); rc != RANENV_OK) return rc;
+    for (int r = 0; r < 4; r++)
+        if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after ranenv_ppo_bind: bind again", NET_ROLES[r].who);
+    return RANENV_OK;
+}
+
+static PpoNet ppo_net(const ranenv::NetSlot *slot)
+{
+    PpoNet n{};
+    if (!slot) return n;
+    n.net = slot->net; n.net.w = nullptr;
+    n.w = slot->w; n.m = slot->opt; n.v = slot->opt + slot->opt_cap; n.g = slot->opt + 2 * slot->opt_cap;
+    n.stride = slot->member_stride; n.floats = net_floats(slot->net);
+    return n;
+}
+
+int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    ranenv::NetSlot *slot[4];
+    int members = 0;
+    if (const int rc = ppo_roles(h, slot, members); rc != RANENV_OK) return rc;
+    long long g = 0; size_t lds = 0;
+    for (int k = 0; k < 2; k++) {
+        if (!slot[k]) continue;
+        const long long f = net_floats(slot[k]->net) + (slot[2 + k] ? net_floats(slot[2 + k]->net) : 0);
+        g = f > g ? f : g;
+        const size_t l = ppo_lds_bytes(slot[k]->net, slot[2 + k] ? &slot[2 + k]->net : nullptr);
+        lds = l > lds ? l : lds;
+    }
+    if (grad_floats) *grad_floats = g;
+    if (lds_bytes) *lds_bytes = (int64_t)lds;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (role < 0 || role > 3) return fail(h, RANENV_E_INVALID, "role %d (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)", role);
+    ranenv::NetSlot *slot[4];
+    int members = 0;
+    if (const int rc = ppo_bound(h, slot, members); rc != RANENV_OK) return rc;
+    if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
+    if (!slot[role]) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
+    const size_t at = (size_t)member * (size_t)slot[role]->member_stride;
+    if (dev_m) *dev_m = slot[role]->opt + at;
+    if (dev_v) *dev_v = slot[role]->opt + slot[role]->opt_cap + at;
+    if (dev_t) *dev_t = h->d_ppo_t + member * 2 + (role & 1);
+    if (floats) *floats = net_floats(slot[role]->net);
+    return RANENV_OK;
+}
+
+int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    h->ppo_probe = dev_logp;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, int32_t n_members, const ranenv_ppo_hparams *hp,
+                      const int32_t *order_inter, const int32_t *first_inter, const int32_t *order_intra, const int32_t *first_intra, double *stats,
+                      float *grad, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    float *const probe_logp = h->ppo_probe;
+    h->ppo_probe = nullptr;          // (armed for ONE update, served or refused: the handle keeps no caller's pointer beyond it)
+    ranenv::NetSlot *slot[4];
+    int members = 0;
+    if (const int rc = ppo_bound(h, slot, members); rc != RANENV_OK) return rc;
+    if (n_steps < 1 || !traj || !hp || !order_inter || !first_inter || !stats) return fail(h, RANENV_E_INVALID, "n_steps >= 1, the record, the hyper-parameters, the inter row lists and dev_stats are required");
+    if (n_members != members) return fail(h, RANENV_E_INVALID, "%d members given, the bound nets have %d", n_members, members);
+    const bool intra = order_intra != nullptr;
+    if (intra && !first_intra) return fail(h, RANENV_E_INVALID, "intra row lists without host_first_intra");
+    if (intra && !slot[1]) return fail(h, RANENV_E_INVALID, "intra row lists but no intra actor is bound");
+    int max_epochs = 0;
+    for (int m = 0; m < members; m++) {
+        if (hp[m].minibatch < 1) return fail(h, RANENV_E_INVALID, "member %d: minibatch %d (>= 1)", m, hp[m].minibatch);
+        if (hp[m].epochs < 0) return fail(h, RANENV_E_INVALID, "member %d: epochs %d (>= 0)", m, hp[m].epochs);
+        max_epochs = hp[m].epochs > max_epochs ? hp[m].epochs : max_epochs;
+    }
+    if (!traj->obs_inter || !traj->mask_inter || !traj->action_inter || !traj->logp || !traj->adv || !traj->vtarg)
+        return fail(h, RANENV_E_INVALID, "the record needs obs_inter, mask_inter, action_inter, logp, adv and vtarg");
+    if (intra && (!traj->obs_intra || !traj->action_intra || (slot[1]->net.layout == RANENV_NET_IN_MASK_OBS && !traj->mask_intra)))
+        return fail(h, RANENV_E_INVALID, "the record needs obs_intra and action_intra (mask_intra for RANENV_NET_IN_MASK_OBS nets) for the intra rows");
+    const long long rows_max[2] = {(long long)n_steps * h->cfg.batch, (long long)n_steps * h->cfg.batch * h->cfg.n_slices};
+    if (rows_max[1] > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "the record has more than 2^31 - 1 intra rows");
+    PpoArgs a{};
+    for (int k = 0; k < (intra ? 2 : 1); k++) {
+        const int32_t *first = k ? first_intra : first_inter;
+        if (first[0] != 0) return fail(h, RANENV_E_INVALID, "host_first_%s[0] is %d, not 0", k ? "intra" : "inter", first[0]);
+        for (int m = 0; m < members; m++)
+            if (first[m + 1] < first[m]) return fail(h, RANENV_E_INVALID, "host_first_%s decreases at member %d", k ? "intra" : "inter", m);
+        for (int m = 0; m <= members; m++) a.first[k][m] = first[m];
+        a.order[k] = k ? order_intra : order_inter; a.order_stride[k] = first[members];
+        a.net[k][0] = ppo_net(slot[k]); a.net[k][1] = ppo_net(slot[2 + k]);
+    }
+    if (max_epochs == 0) return RANENV_OK;
+    a.T = n_steps; a.B = h->cfg.batch; a.S = h->cfg.n_slices; a.Us = h->cfg.max_ues_slice; a.W = 2 * a.Us + 9;
+    a.hp = h->d_ppo_hp; a.traj = *traj; a.t = h->d_ppo_t; a.max_epochs = max_epochs; a.stats = stats; a.grad = grad; a.probe_logp = probe_logp;
+    long long gf = 0; size_t lds = 0;
+    for (int k = 0; k < 2; k++) {
+        if (a.net[k][0].net.n_layers == 0) continue;
+        const long long f = a.net[k][0].floats + a.net[k][1].floats;
+        gf = f > gf ? f : gf;
+        const size_t l = ppo_lds_bytes(a.net[k][0].net, a.net[k][1].net.n_layers > 0 ? &a.net[k][1].net : nullptr);
+        lds = l > lds ? l : lds;
+    }
+    // (dev_grad's stride is ranenv_ppo_layout's: the larger kind's of the BOUND nets, whether or not this call updates the intra kind)
+    if (slot[1]) { const long long f = net_floats(slot[1]->net) + (slot[3] ? net_floats(slot[3]->net) : 0); gf = f > gf ? f : gf; }
+    a.grad_stride = gf;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)members, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_ppo_update(s, members, lds, a));
+    return RANENV_OK;
+}
+
+int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv_mlp *out, void *stream)
+{
+    if (!h || !out) return fail(h, RANENV_E_INVALID, "null argument");
+    if (role < 0 || role > 3) return fail(h, RANENV_E_INVALID, "role %d (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)", role);
+    const bool pop = h->pop_slot(role)->on;
+    if (!pop && ((role == 1 && h->actor_ps.on) || (role == 3 && h->value_ps.on))) return fail(h, RANENV_E_STATE, "the %s nets are bound per slice", NET_ROLES[role].who);
+    const ranenv::NetSlot *slot = pop ? h->pop_slot(role) : h->one_slot(role);
+    if (!slot->on) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
+    if (member < 0 || member >= (pop ? h->pop.n : 1)) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, pop ? h->pop.n : 1);
+    const PolicyNet &net = pop ? slot->member[(size_t)member] : slot->net;
+    if (net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the %s net is bf16: its float32 weights were rounded at bind", NET_ROLES[role].who);
+    const int32_t *dims = pop ? slot->member_dims[(size_t)member].data() : slot->dims;
+    const int L = net.n_layers;
+    for (int l = 0; l < L; l++)
+        if ((out->weight[l] == nullptr) != (out->weight[0] == nullptr) || (out->bias[l] == nullptr) != (out->weight[0] == nullptr))
+            return fail(h, RANENV_E_INVALID, "give every layer's weight and bias buffer, or none");
+    const bool copy = out->weight[0] != nullptr;
+    out->n_hidden = L - 1; out->activation = net.act; out->input_layout = net.layout; out->precision = net.prec;
+    for (int l = 0; l < 6; l++) out->dims[l] = l <= L ? dims[l] : 0;
+    if (!copy) return RANENV_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const float *src = pop ? net.w : slot->w;
+    for (int l = 0; l < L; l++) {
+        const int K = dims[l], N = dims[l + 1];
+        HIP_TRY(h, hipMemcpy2DAsync((void *)out->weight[l], sizeof(float) * K, src + net.w_off[l], sizeof(float) * net.kp[l], sizeof(float) * K, N, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync((void *)out->bias[l], src + net.b_off[l], sizeof(float) * N, hipMemcpyDeviceToDevice, s));
+    }
     return RANENV_OK;
 }
 

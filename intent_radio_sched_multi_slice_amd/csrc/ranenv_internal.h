@@ -253,6 +253,28 @@ struct SacArgs {
 };
 hipError_t launch_sac_targets(hipStream_t, const PolicyNet &actor, const PolicyNet &q1, const PolicyNet &q2, const SacArgs &);
 
+// ranenv_ppo_update (ranenv_ppo.hip; include/ranenv.h "PPO update"): one net of the update -- its layout (net.w unused), the slot's packed
+// weights, Adam moments and gradient scratch (member m's at + m * stride floats, `floats` of them in use; n_layers 0: not bound / not updated)
+struct PpoNet { PolicyNet net; float *w, *m, *v, *g; long long stride, floats; };
+// ... and one call: actor and critic per kind (0 inter, 1 intra), the members' shares of the row lists, the record
+struct PpoArgs {
+    PpoNet net[2][2];                     // [kind][0 the actor, 1 the critic]
+    int first[2][POP_MAX + 1];            // kind k, member m: entries [first[k][m], first[k][m + 1]) of every epoch's list
+    const int32_t *order[2]; long long order_stride[2];      // [max_epochs][order_stride[k]] record rows
+    int T, B, S, Us, W;
+    const ranenv_ppo_hparams *hp;         // device, [members]
+    ranenv_trajectory traj;
+    int32_t *t;                           // [POP_MAX][2] Adam step counters
+    int max_epochs;
+    double *stats;                        // [members][2][max_epochs][RANENV_PPO_STATS]
+    float *grad; long long grad_stride;   // [members][2][grad_stride] or null
+    float *probe_logp;                    // [T][B][S + 1] or null (ranenv_ppo_probe_logp)
+};
+// Bytes of LDS the update of this actor / critic pair needs (critic null or n_layers 0: none); the rule is in include/ranenv.h
+size_t ppo_lds_bytes(const PolicyNet &actor, const PolicyNet *critic);
+enum { PPO_LDS_MAX = 160 * 1024 };
+hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoArgs &);
+
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block
 

@@ -1,0 +1,378 @@
+// ranenv_ppo.hip -- the PPO update of the bound IBSched nets on the device (ranenv_ppo_update, include/ranenv.h "PPO update"): one
+// workgroup per (population member, agent kind) runs that member's whole SGD schedule -- epochs x minibatches of clipped-surrogate
+// loss, backward pass, joint gradient clip and Adam -- in one launch.  Nothing is shared between workgroups: no atomics, no reduction
+// across them, one summation order.
+//
+// Per 32-row tile of a minibatch the workgroup gathers the indexed record rows into LDS and runs the net forward with the acting
+// launches' own layers (net_layers<false, true>, ranenv_net.hpp), every layer's rows staying in LDS: buffer 0 the input rows, buffer
+// l + 1 layer l's output, back to back.  The loss gradient at the outputs (float64 per row, rounded once) overwrites the output rows,
+// and the backward pass walks the layers down, on the f32 matrix cores (v_mfma_f32_16x16x4_f32):
+//   dW[n][k] += sum_r dZ[r][n] A[r][k]     16 x 16 blocks of W, 8 MFMAs each (the 32 rows are the reduction), added to the workgroup's
+//                                          gradient scratch in global memory by plain load-add-store -- a wave owns its blocks
+//   db[n]    += sum_r dZ[r][n]             a thread per column, rows in ascending order
+//   dZ'[r][k] = (sum_n dZ[r][n] W[n][k]) act'(A[r][k])     32 x 16 blocks, written IN PLACE over A (a barrier behind dW, which read it)
+// so the LDS need is one net's rows of all layers, not twice that.  Rows beyond the minibatch and padded columns are exact zeros all the
+// way: a dead row's dZ is 0, a padded column's W and b are 0 and stay 0 under Adam (g = 0, m = v = 0).
+// The weights this launch reads were written by the launch itself one minibatch earlier: every weight read is a vector load at a
+// lane-dependent address behind a workgroup barrier (the forward's float4 / bias loads, the backward's W loads, Adam's own) -- none
+// through the scalar cache, which does not see the vector stores.
+#include "ranenv_net.hpp"
+
+namespace {
+
+constexpr int PPO_FIXED = 4096;           // bytes of LDS in front of the rows: reduction slots, per-row statistics, the tile's record rows
+constexpr int PPO_ROW_STATS = 6;          // per row: policy loss, entropy, logp_old - logp, clipped?, live?, value loss
+
+// Floats of LDS for the rows of `net`: the input and every layer's output, 32 rows each
+__host__ __device__ inline int ppo_act_floats(const PolicyNet &net)
+{
+    int n = NET_ROWS * net_ld(net.kp[0]);
+    for (int l = 0; l < net.n_layers; l++) n += NET_ROWS * net_ld(net.np[l]);
+    return n;
+}
+
+// The tile's rows of `net`'s input -> buffer 0: row r is record row idx[r] (< 0: a dead row, zeros), read as net_load_rows reads an
+// env's row -- the inter observation, or the slice's observation behind, for RANENV_NET_IN_MASK_OBS, its mask as floats
+__device__ __forceinline__ void ppo_load_rows(const PolicyNet &net, const PpoArgs &A, int kind, const int *idx, float *dst, int tid)
+{
+    load_rows(net.kp[0], 0, 0, dst, tid, [&](int r, int k) {
+        const int i = idx[r];
+        if (i < 0 || k >= net.in_dim) return 0.0f;
+        if (kind == 0) return A.traj.obs_inter[(size_t)i * (size_t)(10 * A.S) + k];
+        const int ko = net.layout == RANENV_NET_IN_MASK_OBS ? k - A.Us : k;
+        if (ko < 0) return (float)A.traj.mask_intra[(size_t)i * A.Us + k];
+        return A.traj.obs_intra[(size_t)i * A.W + ko];
+    });
+}
+
+// The backward pass of one tile: `out` = the output layer's rows, holding dL/d(output); the layers' inputs lie in front of it (see
+// the header).  Adds the tile's share to the packed gradient `g`; reads the weights `w`.  Ends without a barrier.
+__device__ __forceinline__ void ppo_backward(const PolicyNet &net, const float *w, float *g, float *out, int tid)
+{
+    const int lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
+    float *dz = out;
+    for (int l = net.n_layers - 1; l >= 0; l--) {
+        const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N), kb = K >> 4;
+        float *a = dz - NET_ROWS * ldi;
+        float *gW = g + net.w_off[l], *gb = g + net.b_off[l];
+        for (int blk = wave; blk < (N >> 4) * kb; blk += 4) {
+            const int nb = blk / kb, n0 = nb << 4, k0 = (blk - nb * kb) << 4;
+            f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int j = 0; j < 8; j++) {      // MFMA j: rows 4 j + q
+                const int r = 4 * j + q;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dz[r * ldo + n0 + c], a[r * ldi + k0 + c], acc, 0, 0, 0);
+            }
+            // C/D map of the 16x16 block: column (k) = lane & 15, row (n) = 4 (lane >> 4) + register
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                float *p = gW + (size_t)(n0 + 4 * q + i) * K + k0 + c;
+                *p = *p + acc[i];
+            }
+        }
+        for (int n = tid; n < N; n += 256) {
+            float s = 0.0f;
+#pragma unroll 4
+            for (int r = 0; r < NET_ROWS; r++) s += dz[r * ldo + n];
+            gb[n] = gb[n] + s;
+        }
+        if (l == 0) break;
+        __syncthreads();                       // (dW has read A: dZ' may overwrite it)
+        const float *W = w + net.w_off[l];
+        for (int blk = wave; blk < kb; blk += 4) {
+            const int k0 = blk << 4;
+            f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+            for (int n0 = 0; n0 < N; n0 += 16) {      // MFMA j: n = n0 + 4 q + j, the same permutation on both operands
+                const float4 d0 = *(const float4 *)(dz + c * ldo + n0 + 4 * q), d1 = *(const float4 *)(dz + (16 + c) * ldo + n0 + 4 * q);
+                const float *wp = W + (size_t)(n0 + 4 * q) * K + k0 + c;
+                const float wv[4] = {wp[0], wp[K], wp[2 * K], wp[3 * K]};
+                const float dv[2][4] = {{d0.x, d0.y, d0.z, d0.w}, {d1.x, d1.y, d1.z, d1.w}};
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+#pragma unroll
+                    for (int mi = 0; mi < 2; mi++) acc[mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[mi][j], wv[j], acc[mi], 0, 0, 0);
+            }
+#pragma unroll
+            for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    float *p = a + (mi * 16 + 4 * q + i) * ldi + k0 + c;
+                    const float av = *p;
+                    *p = acc[mi][i] * (net.act == RANENV_ACT_RELU ? (av > 0.0f ? 1.0f : 0.0f) : 1.0f - av * av);
+                }
+        }
+        __syncthreads();
+        dz = a;
+    }
+}
+
+// The sum of the workgroup's 256 partial sums, in slot order, in every thread (two barriers: the slots are free again on return)
+__device__ __forceinline__ double ppo_sum(double *red, double part, int tid)
+{
+    red[tid] = part;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 256; k++) tot += red[k];
+    __syncthreads();
+    return tot;
+}
+
+__device__ __forceinline__ void ppo_adam(float *w, float *m, float *v, const float *g, long long n, float scale, float b1, float omb1, float b2, float omb2,
+                                         float step, float sbc2, float eps, int tid)
+{
+#pragma unroll 1
+    for (long long i = tid; i < n; i += 256) {
+        const float gi = g[i] * scale;
+        const float mi = b1 * m[i] + omb1 * gi;
+        const float vi = b2 * v[i] + (omb2 * gi) * gi;
+        m[i] = mi; v[i] = vi;
+        w[i] = w[i] - step * (mi / (sqrtf(vi) / sbc2 + eps));
+    }
+}
+
+// b^t (t >= 1) in float64 by repeated squaring
+__device__ __forceinline__ double ppo_powi(double b, int t)
+{
+    double r = 1.0;
+#pragma unroll 1
+    for (; t > 0; t >>= 1) { if (t & 1) r *= b; b *= b; }
+    return r;
+}
+
+// The loss gradient at the actor's outputs for the tile's row r (thread r): `o` = the row's outputs, overwritten; the row's statistics
+__device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo_hparams &hp, int kind, int i, int np, float *o, double *rs, double wrow,
+                                              double a_mean, double a_den)
+{
+    const int S = A.S;
+    if (i < 0) {
+#pragma unroll 1
+        for (int j = 0; j < np; j++) o[j] = 0.0f;
+        rs[0] = rs[1] = rs[2] = rs[3] = rs[4] = 0.0;
+        return;
+    }
+    // the (logp, adv, vtarg) cell of record row i: column 0 of the inter row, column s + 1 of the env's row for slice s
+    const size_t at = kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S);
+    const double lp_old = (double)A.traj.logp[at];
+    const double adv = hp.adv_norm ? ((double)A.traj.adv[at] - a_mean) / a_den : (double)A.traj.adv[at];
+    double lp = 0.0, ent = 0.0;
+    int j0 = 0, ch = 0;
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    if (kind == 0) {
+        int n_act = 0;
+#pragma unroll 1
+        for (int s = 0; s < S; s++) n_act += A.traj.mask_inter[(size_t)i * S + s] != 0 ? 1 : 0;
+        j0 = S - n_act;
+#pragma unroll 1
+        for (int j = j0; j < S; j++) {
+            const double ls = (double)o[S + j];
+            const double z = (A.traj.action_inter[(size_t)i * S + j] - (double)o[j]) / exp(ls);
+            lp += RANENV_INTER_LOGP_TERM(z, ls);
+            ent += (ls + 0.5) + HALF_LN_2PI;
+        }
+        lp += RANENV_INTER_LOGP_MASKED(j0);
+    } else {
+        const float l0 = o[0], l1 = o[1], l2 = o[2];
+        ch = (int)A.traj.action_intra[i];
+        // (RANENV_INTRA_LOGP's expressions in its order, for all three logits: change the two together, ranenv_net.hpp)
+        const double mx = fmax(fmax((double)l0, (double)l1), (double)l2);
+        const double e0 = exp((double)l0 - mx), e1 = exp((double)l1 - mx), e2 = exp((double)l2 - mx);
+        const double sum = (e0 + e1) + e2, lsum = log(sum);
+        q0 = ((double)l0 - mx) - lsum; q1 = ((double)l1 - mx) - lsum; q2 = ((double)l2 - mx) - lsum;
+        p0 = e0 / sum; p1 = e1 / sum; p2 = e2 / sum;
+        lp = ch == 0 ? q0 : (ch == 1 ? q1 : q2);
+        ent = -((p0 * q0 + p1 * q1) + p2 * q2);
+    }
+    if (A.probe_logp) A.probe_logp[at] = (float)lp;
+    const double ratio = exp(lp - lp_old), c_lo = 1.0 - hp.clip, c_hi = 1.0 + hp.clip;
+    const bool inside = ratio >= c_lo && ratio <= c_hi;
+    const double s1 = ratio * adv, s2 = (ratio < c_lo ? c_lo : (ratio > c_hi ? c_hi : ratio)) * adv;
+    // torch.minimum / clamp: the unclipped branch carries the gradient where it is the smaller one, both where they tie
+    const double dsdr = inside || s1 < s2 ? adv : 0.0;
+    const double gl = -(dsdr * ratio) * wrow, ge = hp.ent_coeff * wrow;
+    rs[0] = -(s1 < s2 ? s1 : s2); rs[1] = ent; rs[2] = lp_old - lp; rs[3] = inside ? 0.0 : 1.0; rs[4] = 1.0;
+    if (kind == 0) {
+#pragma unroll 1
+        for (int j = 0; j < j0; j++) { o[j] = 0.0f; o[S + j] = 0.0f; }
+#pragma unroll 1
+        for (int j = j0; j < S; j++) {
+            const double sig = exp((double)o[S + j]);
+            const double z = (A.traj.action_inter[(size_t)i * S + j] - (double)o[j]) / sig;
+            o[j] = (float)(gl * (z / sig));
+            o[S + j] = (float)(gl * (z * z - 1.0) - ge);
+        }
+    } else {
+        o[0] = (float)(gl * ((ch == 0 ? 1.0 : 0.0) - p0) + ge * (p0 * (q0 + ent)));
+        o[1] = (float)(gl * ((ch == 1 ? 1.0 : 0.0) - p1) + ge * (p1 * (q1 + ent)));
+        o[2] = (float)(gl * ((ch == 2 ? 1.0 : 0.0) - p2) + ge * (p2 * (q2 + ent)));
+    }
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_update_kernel(PpoArgs A)
+{
+    extern __shared__ float lds[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mem = (int)blockIdx.x, kind = (int)blockIdx.y;
+    if (A.net[kind][0].net.n_layers == 0) return;
+    const ranenv_ppo_hparams &hp = A.hp[mem];
+    const int epochs = hp.epochs, minibatch = hp.minibatch;
+    if (epochs <= 0 || minibatch < 1) return;          // (minibatch < 1: the host refuses it)
+    const int lo = A.first[kind][mem], n = A.first[kind][mem + 1] - lo;
+    if (n <= 0) return;
+    const int n_nets = A.net[kind][1].net.n_layers > 0 ? 2 : 1;      // net 0 the actor, net 1 the critic
+
+    double *red = (double *)lds, *rowstat = red + 256;
+    int *rowidx = (int *)(rowstat + NET_ROWS * PPO_ROW_STATS);
+    float *act = lds + PPO_FIXED / 4;
+    const int S = A.S;
+    const long long n_record = (long long)A.T * A.B * (kind == 0 ? 1 : S);
+    int t = A.t[mem * 2 + kind];
+
+#pragma unroll 1
+    for (int ep = 0; ep < epochs; ep++) {
+        const int32_t *list = A.order[kind] + (size_t)ep * (size_t)A.order_stride[kind] + lo;
+        double st_pl = 0.0, st_vl = 0.0, st_ent = 0.0, st_kl = 0.0, st_cf = 0.0, st_gn = 0.0, st_rows = 0.0;      // (thread 0's)
+        int n_mb = 0;
+#pragma unroll 1
+        for (int c0 = 0; c0 < n; c0 += minibatch) {
+            const int nb = n - c0 < minibatch ? n - c0 : minibatch;
+            const double wrow = 1.0 / (double)nb;
+#pragma unroll 1
+            for (int k = 0; k < n_nets; k++) {
+                float *g = A.net[kind][k].g + mem * A.net[kind][k].stride;
+                const long long f = A.net[kind][k].floats;
+#pragma unroll 1
+                for (long long i = tid; i < f; i += 256) g[i] = 0.0f;
+            }
+            double a_mean = 0.0, a_den = 1.0;
+            if (hp.adv_norm) {                 // one float64 pass over the minibatch's advantages (entries outside the record: 0)
+                auto adv_at = [&](int k) {
+                    const int i = list[c0 + k];
+                    if (i < 0 || i >= n_record) return 0.0;
+                    return (double)A.traj.adv[kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S)];
+                };
+                double s = 0.0;
+#pragma unroll 1
+                for (int k = tid; k < nb; k += 256) s += adv_at(k);
+                a_mean = ppo_sum(red, s, tid) / (double)nb;
+                s = 0.0;
+#pragma unroll 1
+                for (int k = tid; k < nb; k += 256) { const double d = adv_at(k) - a_mean; s += d * d; }
+                const double ss = ppo_sum(red, s, tid);
+                a_den = (nb > 1 ? sqrt(ss / (double)(nb - 1)) : 0.0) + 1e-8;
+            }
+
+#pragma unroll 1
+            for (int t0 = 0; t0 < nb; t0 += NET_ROWS) {
+                __syncthreads();               // (the previous tile's backward pass and statistics are read)
+                if (tid < NET_ROWS) {
+                    int i = -1;
+                    if (t0 + tid < nb) { i = list[c0 + t0 + tid]; if (i < 0 || i >= n_record) i = -1; }
+                    rowidx[tid] = i;
+                }
+                // ---- per net: forward, dL/d(output) per row, backward ---------------------------------------------------------------
+#pragma unroll 1
+                for (int k = 0; k < n_nets; k++) {
+                    const PpoNet &pn = A.net[kind][k];
+                    float *w = pn.w + mem * pn.stride, *g = pn.g + mem * pn.stride;
+                    __syncthreads();           // (the tile's rows are listed; the actor's backward pass has read its rows)
+                    float *cur = act, *nxt = act + NET_ROWS * net_ld(pn.net.kp[0]);
+                    ppo_load_rows(pn.net, A, kind, rowidx, cur, tid);
+                    __syncthreads();
+                    net_layers<false, true>(pn.net, w, cur, nxt, lane, wave);
+                    if (tid < NET_ROWS) {
+                        const int i = rowidx[tid], np = pn.net.np[pn.net.n_layers - 1];
+                        float *o = cur + tid * net_ld(np);
+                        double *rs = rowstat + tid * PPO_ROW_STATS;
+                        if (k == 0) ppo_actor_row(A, hp, kind, i, np, o, rs, wrow, a_mean, a_den);
+                        else {                 // the critic: 2 vf_coeff (V - vtarg) / rows
+                            double vl = 0.0;
+                            if (i < 0) o[0] = 0.0f;
+                            else {
+                                const double d = (double)o[0] - (double)A.traj.vtarg[kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S)];
+                                vl = d * d;
+                                o[0] = (float)(((2.0 * d) * hp.vf_coeff) * wrow);
+                            }
+                            rs[5] = vl;
+                        }
+                    }
+                    __syncthreads();
+                    ppo_backward(pn.net, w, g, cur, tid);
+                }
+                if (tid == 0) {                // (rows 0..31 in order; the barriers above have published them)
+#pragma unroll 1
+                    for (int r = 0; r < NET_ROWS; r++) {
+                        const double *rs = rowstat + r * PPO_ROW_STATS;
+                        st_pl += rs[0]; st_ent += rs[1]; st_kl += rs[2]; st_cf += rs[3]; st_rows += rs[4];
+                        if (n_nets == 2) st_vl += rs[5];
+                    }
+                }
+            }
+            __syncthreads();
+
+            // ---- joint norm, clip, Adam -------------------------------------------------------------------------------------------
+            double s = 0.0;
+#pragma unroll 1
+            for (int k = 0; k < n_nets; k++) {
+                const float *g = A.net[kind][k].g + mem * A.net[kind][k].stride;
+                const long long f = A.net[kind][k].floats;
+#pragma unroll 1
+                for (long long i = tid; i < f; i += 256) { const double x = (double)g[i]; s += x * x; }
+            }
+            const double norm = sqrt(ppo_sum(red, s, tid));
+            double sc = 1.0;
+            if (hp.grad_clip > 0.0) { sc = hp.grad_clip / (norm + 1e-6); sc = sc < 1.0 ? sc : 1.0; }
+            t += 1;
+            const float step = (float)(hp.lr / (1.0 - ppo_powi(hp.beta1, t))), sbc2 = (float)sqrt(1.0 - ppo_powi(hp.beta2, t));
+            const float b1 = (float)hp.beta1, omb1 = (float)(1.0 - hp.beta1), b2 = (float)hp.beta2, omb2 = (float)(1.0 - hp.beta2), eps = (float)hp.eps;
+#pragma unroll 1
+            for (int k = 0; k < n_nets; k++) {
+                const PpoNet &pn = A.net[kind][k];
+                const long long at = mem * pn.stride;
+                ppo_adam(pn.w + at, pn.m + at, pn.v + at, pn.g + at, pn.floats, (float)sc, b1, omb1, b2, omb2, step, sbc2, eps, tid);
+            }
+            st_gn += norm * (double)nb;
+            n_mb += 1;
+            __syncthreads();                   // (the next minibatch reads the new weights)
+        }
+        if (tid == 0) {
+            double *out = A.stats + (((size_t)mem * 2 + kind) * (size_t)A.max_epochs + ep) * RANENV_PPO_STATS;
+            const double inv = 1.0 / (double)n;
+            out[0] = st_pl * inv; out[1] = st_vl * inv; out[2] = st_ent * inv; out[3] = st_kl * inv; out[4] = st_cf * inv; out[5] = st_gn * inv;
+            out[6] = st_rows; out[7] = (double)n_mb;
+        }
+    }
+    if (A.grad) {
+        float *out = A.grad + ((size_t)mem * 2 + kind) * (size_t)A.grad_stride;
+#pragma unroll 1
+        for (int k = 0; k < n_nets; k++) {
+            const float *g = A.net[kind][k].g + mem * A.net[kind][k].stride;
+            const long long f = A.net[kind][k].floats;
+#pragma unroll 1
+            for (long long i = tid; i < f; i += 256) out[i] = g[i];
+            out += f;
+        }
+    }
+    if (tid == 0) A.t[mem * 2 + kind] = t;
+}
+
+}  // namespace
+
+namespace ranenv_dev {
+
+size_t ppo_lds_bytes(const PolicyNet &actor, const PolicyNet *critic)
+{
+    int n = ppo_act_floats(actor);
+    if (critic && critic->n_layers > 0) { const int v = ppo_act_floats(*critic); n = v > n ? v : n; }
+    return (size_t)PPO_FIXED + sizeof(float) * (size_t)n;
+}
+
+hipError_t launch_ppo_update(hipStream_t s, int n_members, size_t lds, const PpoArgs &a)
+{
+    static const hipError_t attr = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(ranenv_ppo_update_kernel, dim3((unsigned)n_members, 2), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace ranenv_dev
