@@ -197,6 +197,28 @@ int ranenv_bind_se_pool(ranenv_handle h, const float *dev_pool, int64_t n_tiles,
  * ranenv_se_retile_quad converts an RB-major pool [n_tiles][R][U] (device pointers, no handle). */
 int ranenv_bind_se_pool_quad(ranenv_handle h, const float *dev_pool, int64_t n_tiles, int64_t tile_stride);
 int ranenv_se_retile_quad(const float *dev_rb_major, float *dev_quad, int64_t n_tiles, int32_t n_ues, int32_t n_rbs, void *stream);
+/* MEMBER LINES (option "member_lines" below): a compact streaming rollout needs the SE rows of slice members only, but either pool
+ * layout above interleaves the UEs (8 of them in every 128-byte line of the quad layout), so whole tiles are fetched.  The handle
+ * therefore keeps a copy of the bound pool in which every UE owns a row of whole 128-byte lines, float32 [tile][U][lines][32], laid
+ * out for eight lanes per UE.  A row is cut into numpy's pairwise leaves (every leaf a multiple of 8 RBs, the last one carrying the
+ * tail R mod 8); the whole 8-RB groups of a leaf go into chunks of 4 groups, one line per chunk: position 4*j + g of chunk c of the
+ * leaf that starts at RB L holds RB L + 8*(4*c + g) + j, and +0.0 where group 4*c + g lies beyond the leaf's last whole group; if
+ * R mod 8 != 0 one more line holds those last RBs at positions 0 .. R mod 8 - 1 and +0.0 behind them.  R = 135: leaves 64 + 71,
+ * 2 + 2 + 1 lines = 640 bytes per UE.  Lane j of a cluster of 8 loads bytes [16*j, 16*j + 16) of a line: four consecutive elements of
+ * accumulator j of numpy's 8-accumulator loop, so the sums keep their order and their bits (padding adds +0.0 to an accumulator that
+ * is never -0.0).  The copy is the handle's (n_tiles * U * lines * 128 bytes, released by ranenv_destroy), built by the first
+ * ranenv_rollout call that would use it -- never inside a stream capture -- and rebuilt after the pool is bound again; a pool whose
+ * VALUES are changed in place has to be bound again.  If its allocation fails no error is raised: rollouts keep reading the tiles.
+ * ranenv_se_retile_member_lines: the same transform for the caller's buffers (no handle): quad = 0 an RB-major, 1 an RB-quad-major
+ * pool, tiles tile_stride floats apart; dev_lines [n_tiles][U][lines][32], 16-byte aligned.
+ * ranenv_member_line_plan (host arithmetic only): returns the lines per UE for a row of n_rbs RBs (< 0: error) and fills, for up to
+ * max_lines of them, the line's leaf, its first RB and the whole groups it holds (0 = the tail line); any of the arrays may be NULL.
+ * ranenv_member_lines_row_sums_host (host arithmetic only): one UE's lines summed in the kernels' own order -- full = the sum over
+ * all RBs, part = over [rb_start, rb_start + rb_count) -- in float64: bit for bit np.sum of the float32 row as float64. */
+int ranenv_se_retile_member_lines(const float *dev_pool, int32_t quad, int64_t tile_stride, float *dev_lines, int64_t n_tiles, int32_t n_ues,
+                                  int32_t n_rbs, void *stream);
+int ranenv_member_line_plan(int32_t n_rbs, int32_t max_lines, int32_t *leaf, int32_t *first_rb, int32_t *groups);
+int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part);
 /* Traffic pool: int32 offered bits, row i = [U] at dev + i*U. */
 int ranenv_bind_traffic_pool(ranenv_handle h, const int32_t *dev_pool, int64_t n_rows);
 
@@ -927,8 +949,13 @@ int ranenv_autoreset_part(ranenv_handle h, int32_t part, const uint8_t *dev_done
  *   "autoreset_shortcut" RANENV_AUTORESET_SHORTCUT 0  1: ranenv_autoreset / _part trust the host's shadow of the step counters (see ranenv_autoreset) and
  *                                                 enqueue nothing at a TTI at which no episode ended; 0: the device reads dev_done every time.
  *                                                 (This one selects whose flags count -- with 1 the caller must not modify dev_done.)
- *   "last_rollout_persistent" / "last_rollout_launches" (read only)   what the last ranenv_rollout call ran: 1 = persistent work-queue
- *                                                 launches (else launches of <= 10 TTIs per partition); how many step-kernel launches it enqueued
+ *   "member_lines" RANENV_MEMBER_LINES   -1        compact streaming rollouts read the handle's member-lines copy of the pool (see "MEMBER LINES" at
+ *                                                 ranenv_bind_se_pool_quad) instead of whole tiles: -1 (auto) and 1: wherever the variant exists -- the
+ *                                                 launches of several TTIs of the lean build and the streaming persistent launches, i.e. batches above 8
+ *                                                 workgroups per CU; 0: never.  The copy costs n_tiles * U * lines * 128 bytes of device memory
+ *   "last_rollout_persistent" / "last_rollout_launches" / "last_rollout_member_lines" (read only)   what the last ranenv_rollout call ran: 1 =
+ *                                                 persistent work-queue launches (else launches of <= 10 TTIs per partition); how many step-kernel
+ *                                                 launches it enqueued; 1 = step launches of it read the member-lines copy
  *   "step_launches_<build>" / "step_launches_<build>_many" (read only)   which build of the step kernel the handle's step launches ran, <build> one of
  *                                                 lean, small, gather, tiny1, mixed, packed, persist, persist_tiny: launches of the step kernel in step mode
  *                                                 that succeeded since ranenv_create (resets and dense launches are not counted), and the share of them

@@ -70,6 +70,30 @@ __global__ void __launch_bounds__(256) ranenv_se_retile_quad_kernel(const float 
     }
 }
 
+// RB-major [n][R][U] or RB-quad-major [n][ceil(R/4)][U][4] (tiles `stride` floats apart) -> member lines [n][U][lines][32]
+// (ranenv_se_retile_member_lines; the layout: ranenv_numeric.hpp, "Member lines"): one float4 of the output per thread -- the 16 bytes
+// lane j of a cluster loads --, +0.0 wherever the layout pads
+__global__ void __launch_bounds__(256) ranenv_se_retile_member_lines_kernel(const float *src, long long stride, int quad, float *dst, long long n_f4,
+                                                                            int U, int R, const MemberLineTable tb)
+{
+    const long long per_tile = (long long)U * tb.lines * 8;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_f4; i += (long long)gridDim.x * blockDim.x) {
+        const long long t = i / per_tile;
+        const int rem = (int)(i - t * per_tile), u = rem / (tb.lines * 8), rl = rem - u * (tb.lines * 8), l = rl >> 3, j = rl & 7;
+        const float *tile = src + (size_t)t * (size_t)stride;
+        auto at = [&](int r) { return quad ? tile[((size_t)(r >> 2) * U + u) * 4 + (r & 3)] : tile[(size_t)r * U + u]; };
+        float v[4];
+        const int rb0 = tb.rb0[l], ng = tb.groups[l];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (ng > 0) v[k] = k < ng ? at(rb0 + 8 * k + j) : 0.0f;          // position 4 j + k: group k of the chunk, accumulator j
+            else v[k] = 4 * j + k < tb.tail ? at(rb0 + 4 * j + k) : 0.0f;     // the tail line: position = RB
+        }
+        se_v4f o; o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+        ((se_v4f *)dst)[i] = o;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Per-tile statistics of the SE pool (ranenv_build_se_stats): what the scenario load figures read of a tile
 // (results/gen_results.py:260-497, :1251-1451), per UE over its R RBs, in float64 on the float32 values:
@@ -887,6 +911,11 @@ void launch_se_sidecar_from_power(hipStream_t s, unsigned n_tiles, unsigned bloc
 void launch_se_retile_quad(hipStream_t s, unsigned blocks, const float *src, float *dst, long long n_quads, int U, int R)
 {
     hipLaunchKernelGGL(ranenv_se_retile_quad_kernel, dim3(blocks), dim3(256), 0, s, src, dst, n_quads, U, R);
+}
+void launch_se_retile_member_lines(hipStream_t s, unsigned blocks, const float *src, long long src_stride, int quad, float *dst, long long n_tiles,
+                                   int U, int R, const MemberLineTable &tb)
+{
+    hipLaunchKernelGGL(ranenv_se_retile_member_lines_kernel, dim3(blocks), dim3(256), 0, s, src, src_stride, quad, dst, n_tiles * (long long)U * tb.lines * 8, U, R, tb);
 }
 void launch_se_from_power(hipStream_t s, unsigned blocks, const double *power, float *se, long long n, double tx_per_rb, double noise)
 {

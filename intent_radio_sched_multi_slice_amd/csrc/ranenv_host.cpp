@@ -41,6 +41,12 @@ struct ranenv {
     // SE gather mode (ranenv_set_se_mode): sidecars of the bound pool, owned by the handle
     int se_mode = RANENV_SE_STREAM;
     double *d_se_mean = nullptr; float *d_se_um = nullptr; int se_rp = 0;
+    // member lines (option "member_lines"): the handle's per-UE line copy of the bound pool [se_tiles_n][U][lines][32] that compact
+    // streaming rollouts read instead of whole tiles (ml_stride floats per tile).  Built by the first rollout that would use it;
+    // a rebind of the pool invalidates it (the buffer stays for the rebuild); ml_failed: the allocation failed, the variant is off
+    float *d_ml = nullptr; int64_t ml_cap = 0; long long ml_stride = 0; bool ml_valid = false, ml_failed = false;
+    int member_lines = -1;         // -1 auto / 0 off / 1 on
+    int last_rollout_member_lines = 0;          // the last ranenv_rollout call's step launches read the copy (read-only option)
     // scenario load (ranenv_build_se_stats / ranenv_rbs_needed): per-tile statistics of the bound pool [se_stats_n][4][U] (se_stats_n = 0: none
     // valid; the buffer of se_stats_cap tiles stays for the next build), and the call's staging: descriptors, network rows
     double *d_se_stats = nullptr; int64_t se_stats_n = 0, se_stats_cap = 0;
@@ -392,6 +398,8 @@ StepPlan step_plan(ranenv_handle h, KP &kp, int e0, int n, bool gather)
     if (gather) l.build = SB_GATHER;
     else if (!pe && MODE == MODE_STEP && !many && h->tiny_step && persist_tiny(h)) l.build = SB_TINY1;
     else if (!pe && h->small_batch) l.build = SB_SMALL;
+    // (the rollout offered its member-lines copy: the lean build of several TTIs reads it where the step is compact)
+    l.members = l.build == SB_LEAN && MODE == MODE_STEP && many && !pe && kp.ml_pool != nullptr && kp.compact != 0 && kp.se_tiles == nullptr;
     return {l, grid, block};
 }
 
@@ -451,6 +459,7 @@ hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t strea
     if (pe != hipSuccess) return pe;
     const hipError_t le = launch_step_counted(h, p.l, p.grid, p.block, stream, ev0, ev1, ks);
     if (le != hipSuccess) return le;
+    if (p.l.members) h->last_rollout_member_lines = 1;
     if (kp.head_obs || kp.head_reward)
         launch_head(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp, (h->kp.acc && h->kp.head_reward) ? h->d_head_acc : nullptr,
                     MODE == MODE_RESET ? 1 : 0);
@@ -746,8 +755,10 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
         e = prof_events(h, n, n_tti, &ev0, &ev1);
         if (e != hipSuccess) return fail(h, RANENV_E_HIP, "hipEventCreate(&pe): %s", hipGetErrorString(e));
         const dim3 grid((unsigned)g), block((unsigned)((c + 1) * WAVE));
-        e = launch_step_counted(h, StepLaunch{h->np, (!gather && tiny) ? SB_PERSIST_TINY : SB_PERSIST, MODE_STEP, true, gather}, grid, block, s, ev0, ev1, kc);
+        const bool members = !gather && !tiny && kp.ml_pool != nullptr;      // (the rollout offered its member-lines copy)
+        e = launch_step_counted(h, StepLaunch{h->np, (!gather && tiny) ? SB_PERSIST_TINY : SB_PERSIST, MODE_STEP, true, gather, members}, grid, block, s, ev0, ev1, kc);
         if (e != hipSuccess) return fail(h, RANENV_E_HIP, "persistent rollout launch: %s", hipGetErrorString(e));
+        if (members) h->last_rollout_member_lines = 1;
         if (k > 0) HIP_TRY(h, hipEventRecord(h->part_done[(size_t)k], s));
         k++;
     }
@@ -805,6 +816,101 @@ int se_sidecars_rebuild(ranenv_handle h, size_t nt, Fill fill)
     return RANENV_OK;
 }
 
+// Member lines (ranenv_numeric.hpp, "Member lines"): the lines of one UE's row, in the order of the copy.  The leaves are numpy's
+// pairwise ones for ANY row length (the recursion itself, not the kernels' two levels): every leaf a multiple of 8 RBs except that
+// the last carries the tail R & 7; a leaf's whole 8-RB groups in chunks of 4, one line each; the tail line last (groups = 0).
+struct MemberLine { int leaf, rb0, groups; };
+void member_leaves(int lo, int n, std::vector<std::pair<int, int>> &out)
+{
+    if (n <= 128) { out.push_back({lo, n}); return; }
+    int n2 = n / 2; n2 -= n2 % 8;
+    member_leaves(lo, n2, out); member_leaves(lo + n2, n - n2, out);
+}
+std::vector<MemberLine> member_line_plan(int R)
+{
+    std::vector<std::pair<int, int>> leaves;
+    member_leaves(0, R, leaves);
+    std::vector<MemberLine> plan;
+    for (size_t k = 0; k < leaves.size(); k++) {
+        const int G = leaves[k].second >> 3;
+        for (int c = 0; 4 * c < G; c++) plan.push_back({(int)k, leaves[k].first + 32 * c, G - 4 * c < 4 ? G - 4 * c : 4});
+    }
+    if (R & 7) plan.push_back({(int)leaves.size() - 1, R - (R & 7), 0});
+    return plan;
+}
+// ... as the retile kernel takes it (false: more lines than its table holds -- no row length ranenv_create admits)
+bool member_line_table(int R, MemberLineTable *tb)
+{
+    const std::vector<MemberLine> plan = member_line_plan(R);
+    if (plan.size() > (size_t)MEMBER_LINES_MAX) return false;
+    *tb = MemberLineTable{};
+    tb->lines = (int)plan.size(); tb->tail = R & 7;
+    for (size_t l = 0; l < plan.size(); l++) { tb->rb0[l] = plan[l].rb0; tb->groups[l] = plan[l].groups; }
+    return true;
+}
+// `full` / `part` of rows [lo, lo + n) from the lines at `line` on (advanced), added in the kernel's order: per accumulator j the four
+// elements of a line one after the other, the leaf's tree, the tail sequentially, the halves as numpy's recursion folds them
+void member_lines_pairwise(const float *&line, int lo, int n, unsigned s, unsigned c, double &full, double &part)
+{
+    if (n > 128) {
+        int n2 = n / 2; n2 -= n2 % 8;
+        double f1, g1, f2, g2;
+        member_lines_pairwise(line, lo, n2, s, c, f1, g1); member_lines_pairwise(line, lo + n2, n - n2, s, c, f2, g2);
+        full = f1 + f2; part = g1 + g2;
+        return;
+    }
+    auto in = [&](int r) { return ((unsigned)r - s) < c ? 1.0 : 0.0; };
+    double f[8], g[8];
+    for (int j = 0; j < 8; j++) { f[j] = 0.0; g[j] = 0.0; }
+    const int G = n >> 3, tail = n & 7;
+    for (int c4 = 0; 4 * c4 < G; c4++, line += 32)
+        for (int j = 0; j < 8; j++)
+            for (int k = 0; k < 4; k++) {
+                const double d = (double)line[4 * j + k];
+                f[j] += d;
+                g[j] = std::fma(d, in(lo + 8 * (4 * c4 + k) + j), g[j]);
+            }
+    double fr = ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
+    double gr = ((g[0] + g[1]) + (g[2] + g[3])) + ((g[4] + g[5]) + (g[6] + g[7]));
+    if (tail > 0) {
+        for (int k = 0; k < tail; k++) { const double d = (double)line[k]; fr += d; gr = std::fma(d, in(lo + 8 * G + k), gr); }
+        line += 32;
+    }
+    full = fr; part = gr;
+}
+
+// The member-lines copy for the pool as it is bound now: there (true), or not and not to be built here -- no pool, a failed allocation
+// earlier, a capturing stream.  Built once per binding, in bursts like the sidecars, between a device and a stream synchronisation:
+// launches on other streams (the partitions' own) read it.  A failed allocation raises no error: the variant stays off for the handle.
+bool member_lines_ready(ranenv_handle h, hipStream_t stream)
+{
+    if (h->ml_valid) return true;
+    MemberLineTable tb;
+    if (h->ml_failed || !h->kp.se_pool || h->se_tiles_n < 1 || stream_capturing(stream) || !member_line_table(h->cfg.n_rbs, &tb)) return false;
+    const int U = h->cfg.n_ues, R = h->cfg.n_rbs;
+    const long long stride = (long long)U * tb.lines * 32;
+    const int64_t count = h->se_tiles_n * stride;
+    if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (!(h->d_ml && h->ml_cap >= count)) {
+        dev_drop(h, h->d_ml); h->d_ml = nullptr; h->ml_cap = 0;
+        void *ptr = nullptr;
+        if (hipMalloc(&ptr, (size_t)count * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); h->ml_failed = true; return false; }
+        h->allocs.push_back(ptr);
+        h->d_ml = (float *)ptr; h->ml_cap = count;
+    }
+    const long long burst = 1ll << 16;
+    for (long long t0 = 0; t0 < h->se_tiles_n; t0 += burst) {
+        const long long n = h->se_tiles_n - t0 < burst ? h->se_tiles_n - t0 : burst;
+        long long blocks = (n * U * tb.lines * 8 + 255) / 256;
+        if (blocks > 256 * 64) blocks = 256 * 64;
+        launch_se_retile_member_lines(stream, (unsigned)blocks, h->kp.se_pool + (size_t)t0 * (size_t)h->kp.se_stride, (long long)h->kp.se_stride,
+                                      h->kp.se_quad, h->d_ml + (size_t)t0 * (size_t)stride, n, U, R, tb);
+    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); h->ml_failed = true; return false; }
+    h->ml_stride = stride; h->ml_valid = true;
+    return true;
+}
+
 // Tuning / debug options (include/ranenv.h, "Options"): ONE table of the keys behind ranenv_set_option / _get_option, and ONE place where the
 // process environment is read (ranenv_create -> apply_env_options: RANENV_<KEY IN CAPITALS>=value presets the same
 // options for handles created afterwards; the test suite and the A/B tools run whole passes under them).
@@ -840,6 +946,7 @@ const Option options[] = {
     {"collect_split", true, [](H h, long long v) { h->collect_split = v < 0 ? -1 : (v != 0 ? 1 : 0); return 0; }, [](H h) -> long long { return h->collect_split; }},
     {"autoreset_shortcut", true, [](H h, long long v) { h->autoreset_shortcut = v != 0 ? 1 : 0; return 0; },
      [](H h) -> long long { return h->autoreset_shortcut; }},
+    {"member_lines", true, [](H h, long long v) { h->member_lines = v < 0 ? -1 : (v != 0 ? 1 : 0); return 0; }, [](H h) -> long long { return h->member_lines; }},
 };
 
 const Option *find_option(const std::string &k)
@@ -1008,6 +1115,7 @@ int ranenv_get_option(ranenv_handle h, const char *key, int64_t *value)
     }
     else if (k == "last_rollout_persistent") *value = h->last_rollout_persistent;      // what the last ranenv_rollout call ran:
     else if (k == "last_rollout_launches") *value = h->last_rollout_launches;          // 1 = persistent work-queue launches; step-kernel launches enqueued
+    else if (k == "last_rollout_member_lines") *value = h->last_rollout_member_lines;  // 1 = its step launches read the member-lines copy
     else if (k.rfind("step_launches_", 0) == 0) {      // MODE_STEP launches per build since ranenv_create; "..._many": those of several TTIs
         std::string b = k.substr(14);
         const bool many_only = b.size() > 5 && b.compare(b.size() - 5, 5, "_many") == 0;
@@ -1171,6 +1279,7 @@ int ranenv_bind_se_pool(ranenv_handle h, const float *dev_pool, int64_t n_tiles,
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     h->se_mode = RANENV_SE_STREAM;             // the sidecars describe the pool they were built from
     h->se_stats_n = 0;                         // ... and so do the tile statistics
+    h->ml_valid = false; h->ml_failed = false; // ... and the member-lines copy (rebuilt by the next rollout that would use it)
     if (dev_pool == nullptr) {
         h->kp.se_pool = nullptr; h->kp.se_stride = 0; h->se_tiles_n = 0; h->kp.se_quad = 0;
         return RANENV_OK;
@@ -1191,6 +1300,7 @@ int ranenv_bind_se_pool_quad(ranenv_handle h, const float *dev_pool, int64_t n_t
         return fail(h, RANENV_E_INVALID, "RB-quad-major SE pool needs n_tiles >= 1, tile_stride >= ceil(R/4)*U*4 = %lld floats and a multiple of 4, "
                     "and a 16-byte aligned pool", (long long)need);
     h->se_mode = RANENV_SE_STREAM; h->se_stats_n = 0;
+    h->ml_valid = false; h->ml_failed = false;
     h->kp.se_pool = dev_pool; h->kp.se_stride = tile_stride; h->se_tiles_n = n_tiles; h->kp.se_quad = 1;
     h->have_episodes = false;
     return RANENV_OK;
@@ -1208,6 +1318,50 @@ int ranenv_se_retile_quad(const float *dev_rb_major, float *dev_quad, int64_t n_
     launch_se_retile_quad((hipStream_t)stream, (unsigned)blocks, dev_rb_major, dev_quad, n_quads, (int)n_ues, (int)n_rbs);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, RANENV_E_HIP, "se_retile_quad launch: %s", hipGetErrorString(e));
+    return RANENV_OK;
+}
+
+int ranenv_se_retile_member_lines(const float *dev_pool, int32_t quad, int64_t tile_stride, float *dev_lines, int64_t n_tiles, int32_t n_ues,
+                                  int32_t n_rbs, void *stream)
+{
+    if (!dev_pool || !dev_lines) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_tiles < 0 || n_ues < 1 || n_rbs < 1) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    const int64_t need = quad ? (int64_t)((n_rbs + 3) / 4) * n_ues * 4 : (int64_t)n_ues * n_rbs;
+    if (tile_stride < need) return fail(nullptr, RANENV_E_INVALID, "tile_stride %lld is below a tile's %lld floats", (long long)tile_stride, (long long)need);
+    if (((uintptr_t)dev_lines & 15) != 0) return fail(nullptr, RANENV_E_INVALID, "the member-lines copy must be 16-byte aligned");
+    MemberLineTable tb;
+    if (!member_line_table((int)n_rbs, &tb)) return fail(nullptr, RANENV_E_INVALID, "n_rbs %d needs more than %d lines per UE", (int)n_rbs, (int)MEMBER_LINES_MAX);
+    const long long burst = 1ll << 16;
+    for (long long t0 = 0; t0 < n_tiles; t0 += burst) {
+        const long long n = n_tiles - t0 < burst ? n_tiles - t0 : burst;
+        long long blocks = (n * n_ues * tb.lines * 8 + 255) / 256;
+        if (blocks > 256 * 64) blocks = 256 * 64;
+        launch_se_retile_member_lines((hipStream_t)stream, (unsigned)blocks, dev_pool + (size_t)t0 * (size_t)tile_stride, (long long)tile_stride, quad ? 1 : 0,
+                                      dev_lines + (size_t)t0 * (size_t)n_ues * tb.lines * 32, n, (int)n_ues, (int)n_rbs, tb);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, RANENV_E_HIP, "se_retile_member_lines launch: %s", hipGetErrorString(e));
+    return RANENV_OK;
+}
+
+int ranenv_member_line_plan(int32_t n_rbs, int32_t max_lines, int32_t *leaf, int32_t *first_rb, int32_t *groups)
+{
+    if (n_rbs < 1 || max_lines < 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    const std::vector<MemberLine> plan = member_line_plan((int)n_rbs);
+    for (size_t l = 0; l < plan.size() && l < (size_t)max_lines; l++) {
+        if (leaf) leaf[l] = plan[l].leaf;
+        if (first_rb) first_rb[l] = plan[l].rb0;
+        if (groups) groups[l] = plan[l].groups;
+    }
+    return (int)plan.size();
+}
+
+int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part)
+{
+    if (!row_lines || !full || !part) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_rbs < 1 || rb_start < 0 || rb_count < 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    const float *line = row_lines;
+    member_lines_pairwise(line, 0, (int)n_rbs, (unsigned)rb_start, (unsigned)rb_count, *full, *part);
     return RANENV_OK;
 }
 
@@ -2305,6 +2459,7 @@ int ranenv_bind_se_gather_from_power(ranenv_handle h, const double *dev_power, i
     if (e != hipSuccess) return fail(h, RANENV_E_HIP, "SE sidecar-from-power launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(stream));        // (read by launches on other streams; the power array may be freed by the caller now)
     h->kp.se_pool = nullptr; h->kp.se_stride = 0;    // no RB-major pool: pooled tiles exist as sidecars only
+    h->ml_valid = false;                             // (... and no member-lines copy is ever built of them)
     h->se_tiles_n = n_tiles; h->se_mode = RANENV_SE_GATHER; h->se_stats_n = 0;
     h->have_episodes = false;                        // descriptors are re-validated against the new tile count
     return RANENV_OK;
@@ -2622,6 +2777,14 @@ static hipError_t rollout_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0
     return collect_policy(h, *ppo, kpk, t + 1, true, e0, n, s);
 }
 
+// TTIs per launch of the launch-per-chunk rollout (at most: a partition's first launch and an episode end may cut one short)
+static int rollout_fuse(ranenv_handle h, const Rollout &r)
+{
+    const int n_steps = r.n_steps;
+    if (r.kp.head_obs || r.kp.head_reward || r.net || slice_metrics_on(h) || trace_on(h)) return 1;
+    return h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
+}
+
 // Every partition walks through the TTIs in launches of its own, on its own stream
 static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
 {
@@ -2630,8 +2793,7 @@ static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
     // behind every step, and -- with auto-reset -- no episode end before the launch's last TTI.  How many: a quarter of
     // the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more and lengthen the
     // drain at the rollout's end, where the workgroups that waited for a free slot run last and alone).
-    int fuse = h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
-    if (r.kp.head_obs || r.kp.head_reward || r.net || slice_metrics_on(h) || trace_on(h)) fuse = 1;
+    const int fuse = rollout_fuse(h, r);
     // `pdone[k]` TTIs are enqueued for partition k
     const int np = h->n_parts > 1 ? h->n_parts : 1;
     std::vector<int> pdone((size_t)np, 0), pn((size_t)np, 0);
@@ -2693,7 +2855,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     Rollout r;
     r.n_steps = n_steps;
     r.kp = call_kp(h, obs_inter, obs_intra, reward, done);
-    h->last_rollout_persistent = 0; h->last_rollout_launches = 0;
+    h->last_rollout_persistent = 0; h->last_rollout_launches = 0; h->last_rollout_member_lines = 0;
     // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
     r.net = net_use(h, r.kp);
     if (r.net < 0) return r.net;
@@ -2726,6 +2888,19 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
         int n_ends = 0;
         (void)ttis_to_end(h, r, 0, h->cfg.batch, n_steps, &n_ends);
         if (n_ends > 2) persist_ok = false;
+    }
+    // Member lines (option "member_lines"; auto = on): a compact streaming rollout whose launches are the lean build of several TTIs or
+    // the streaming persistent build reads the handle's per-UE line copy of the pool instead of whole tiles.  The copy is built here, by
+    // the first rollout that would use it (never inside a stream capture: such a rollout uses it only if it is there already).
+    if (h->member_lines != 0 && h->se_mode != RANENV_SE_GATHER && r.kp.compact != 0 && !scale_per_element(h) && h->kp.se_pool != nullptr) {
+        bool runs = persist_ok && !persist_tiny(h);
+        if (!persist_ok && n_steps > 1 && rollout_fuse(h, r) > 1) {
+            KP kt = r.kp;
+            kt.n_tti = 2;
+            const bool parts = h->n_parts > 1;
+            runs = step_plan<MODE_STEP>(h, kt, parts ? h->part_lo[0] : 0, parts ? h->part_lo[1] - h->part_lo[0] : h->cfg.batch, false).l.build == SB_LEAN;
+        }
+        if (runs && member_lines_ready(h, stream)) { r.kp.ml_pool = h->d_ml; r.kp.ml_stride = h->ml_stride; }
     }
     rc = persist_ok ? rollout_persistent(h, r, stream) : rollout_chunks(h, r, stream);
     if (rc != RANENV_OK) return rc;

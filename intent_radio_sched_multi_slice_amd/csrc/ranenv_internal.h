@@ -148,6 +148,9 @@ struct KP {
     unsigned long long *p_slots;      // [8][p_cap] queue entries {index + 1, item}
     int p_cap;                        // entries per queue (a power of two >= the batch)
     int *p_err;                       // sticky error word of the handle (a wait gave up), in host memory mapped for the device
+    // member lines (ranenv_core_kernel_members / ranenv_persist_kernel_members): the handle's per-UE line copy of the bound pool,
+    // floats between two tiles' copies (U x lines per UE x 32); null: the variant is off
+    const float *ml_pool; long long ml_stride;
 };
 
 constexpr int WAVE = 64;
@@ -298,6 +301,7 @@ struct StepLaunch {
     int mode;           // MODE_STEP / MODE_DENSE / MODE_RESET, | MODE_PE for the per-element builds (lean / gather only)
     bool many;          // a launch of several TTIs (MODE_STEP only)
     bool gather;        // SB_MIXED / SB_PACKED / SB_PERSIST: the SE gather build
+    bool members = false;   // SB_LEAN (step, several TTIs, not per-element) / SB_PERSIST (streaming): the build that reads the member-lines copy
 };
 // ranenv_step.hip, one object per row width.  hipErrorInvalidDeviceFunction: that combination is not built.
 // ev0 / ev1 non-null: an extended launch that records the dispatch's own start / stop timestamps.
@@ -332,6 +336,12 @@ void launch_se_sidecar(hipStream_t, unsigned n_tiles, unsigned block, const floa
 void launch_se_sidecar_from_power(hipStream_t, unsigned n_tiles, unsigned block, const double *power, long long tile0, int U, int R, int Rp,
                                   double tx, double noise, double *mean, float *um);
 void launch_se_retile_quad(hipStream_t, unsigned blocks, const float *src, float *dst, long long n_quads, int U, int R);
+// Member-lines copy (ranenv_numeric.hpp, "Member lines") of tiles [0, n_tiles) of an RB-major (quad 0) or RB-quad-major pool: dst
+// [n_tiles][U][lines][32].  The plan's lines by value: first RB, whole 8-RB groups held (0: the tail line, which holds `tail` RBs)
+enum { MEMBER_LINES_MAX = 24 };
+struct MemberLineTable { int lines, tail; int rb0[MEMBER_LINES_MAX], groups[MEMBER_LINES_MAX]; };
+void launch_se_retile_member_lines(hipStream_t, unsigned blocks, const float *src, long long src_stride, int quad, float *dst, long long n_tiles,
+                                   int U, int R, const MemberLineTable &);
 // ranenv_build_se_stats: stats [n][4][U] (mean, std, min, max per UE over the R RBs) of tiles [tile0, tile0 + n_tiles), the sidecar launch's shape
 void launch_se_tile_stats(hipStream_t, unsigned n_tiles, unsigned block, const float *pool, long long stride, long long tile0, int U, int R,
                           int quad, double *stats);

@@ -320,6 +320,175 @@ struct SeStreamLane {
     DEVFN void refill(int d, int r0) { load(q[d], r0); }
 };
 
+// ---------------------------------------------------------------------------------------------
+// Member lines (compact streaming rollouts): the tile of slice MEMBERS only, from a transposed per-UE copy
+// ---------------------------------------------------------------------------------------------
+// The RB-quad-major tile puts 8 UEs into every 128-byte line, so a compact step -- which needs the rows of slice members only --
+// still fetches practically every line.  The member-lines copy (ranenv_se_retile_member_lines; built by the handle, see
+// ranenv_host.cpp) gives every UE a row of whole lines of its own, laid out for EIGHT lanes per UE: the row is cut into row_sums'
+// leaves, a leaf's 8-RB groups into chunks of 4 groups, and chunk c of the leaf that starts at RB L is one line of 32 floats whose
+// position 4 j + g' holds x[L + 8 (4 c + g') + j] (+0.0 where that group lies beyond the leaf's last whole group); a row with
+// R mod 8 != 0 ends in one more line with those last RBs at positions 0 .. R mod 8 - 1 and +0.0 behind them.  Lane j of a cluster
+// of 8 loads 16 bytes at line + 16 j: four CONSECUTIVE elements of accumulator j's sequential chain, which it adds in order into
+// one f and one masked g -- nothing crosses lanes inside a leaf.  At a leaf's end the 8 accumulators meet in row_sums' tree
+// ((f0+f1)+(f2+f3))+((f4+f5)+(f6+f7)) as a butterfly over lanes xor 1, 2, 4 (IEEE addition is commutative: whichever operand order
+// a lane sees, the grouping and so the bits are row_sums'), the tail line is added sequentially by the cluster's first two lanes, the
+// leaves fold as in row_sums.  The padding is exact: an accumulator is never -0.0 (it starts at +0.0), so acc + 0.0 == acc.
+// A wave walks its members 8 at a time: in pass q cluster c = lane >> 3 serves the wave's lane 8 q + c (its row offset and RB range
+// come through ds_bpermute, the sums go back the same way); a cluster whose lane holds no member gets an offset past the
+// descriptor, reads zeros and touches no memory.  DQ lines per lane rotate through fixed registers across the passes.
+template <int CTRL> DEVFN double dpp_f64(double v)
+{
+    const long long b = __builtin_bit_cast(long long, v);
+    const int lo = dpp_row<CTRL>((int)b), hi = dpp_row<CTRL>((int)(b >> 32));
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
+}
+DEVFN double lane_f64(double v, int byte_addr)       // ds_bpermute of a double: the value of lane byte_addr / 4
+{
+    const long long b = __builtin_bit_cast(long long, v);
+    const int lo = __builtin_amdgcn_ds_bpermute(byte_addr, (int)b), hi = __builtin_amdgcn_ds_bpermute(byte_addr, (int)(b >> 32));
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
+}
+DEVFN int member_line_chunks(int leaf_len) { return ((leaf_len >> 3) + 3) >> 2; }      // lines of a leaf's whole 8-RB groups
+DEVFN int member_lines_per_ue(const RowPlan &pl, int R)
+{
+    return member_line_chunks(pl.len0) + member_line_chunks(pl.len1) + member_line_chunks(pl.len2) + member_line_chunks(pl.len3) + ((R & 7) ? 1 : 0);
+}
+
+template <int DQ>                 // lines in flight per lane
+struct MemberLines {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    static constexpr unsigned OOB = 0x7ffffff0u;
+    v4f q[DQ];
+    __amdgpu_buffer_rsrc_t rsrc;   // descriptor of exactly this tile's copy
+    RowPlan pl;
+    int nl, total;                 // wave-uniform: lines per UE; lines this wave walks = passes x nl
+    unsigned my_voff;              // owner role: byte offset of this lane's member row (OOB: the lane holds no member)
+    int iq, il;                    // request cursor: pass, line
+    unsigned ld_voff;              // cluster role: the served member's row + 16 j
+    DEVFN void issue(v4f &dst)
+    {
+        if (il == 0)
+            ld_voff = (unsigned)__builtin_amdgcn_ds_bpermute((iq * 8 + (int)((threadIdx.x & 63u) >> 3)) * 4, (int)my_voff) + (threadIdx.x & 7u) * 16u;
+        // (the line's offset is the scalar part: it takes no part in the range check, which a missing member's OOB fails by itself)
+        dst = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ld_voff, il * 128, SE_AUX_NT));
+        if (++il == nl) { il = 0; iq++; }
+    }
+    DEVFN void init(const float *tile_lines, int U, int R, bool member, int u)
+    {
+        pl = make_row_plan(R);
+        nl = member_lines_per_ue(pl, R);
+        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tile_lines), 0, U * nl * 128, 0x00020000);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(member);
+        const int top = m != 0 ? 64 - __builtin_clzll(m) : 0;          // (members are the first lanes of an env; any pattern is served)
+        total = ((top + 7) >> 3) * nl;
+        my_voff = member ? (unsigned)(u * nl * 128) : OOB;
+        iq = 0; il = 0; ld_voff = OOB;
+#pragma unroll
+        for (int d = 0; d < DQ; d++) if (d < total) issue(q[d]);
+    }
+};
+
+// `full` / `part` of this lane's member row (0 for a lane without one), bit for bit row_sums' over the range [s, s + c).
+// `after_issue`: as in row_sums, once, in front of the last turn of the queue.
+template <int DQ, typename Hook>
+DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, double &full, double &part, Hook after_issue)
+{
+    typedef typename MemberLines<DQ>::v4f v4f;
+    const RowPlan pl = st.pl;
+    const int tail = R & 7, nl = st.nl, total = st.total;
+    const int j = (int)(threadIdx.x & 7u), cluster = (int)((threadIdx.x & 63u) >> 3);
+    const int my_sc = (int)(s | (c << 16));               // (R <= 512: both fit 16 bits)
+    double f = 0.0, g = 0.0, fr = 0.0, gr = 0.0, lf = 0.0, lg = 0.0, rf = 0.0, rg = 0.0;
+    int cq = 0, cl = 0, leaf = 0, left = 0, rb0 = 0, leaf_end = 0;      // wave-uniform cursor: pass, line, leaf, lines left in it, the line's first RB
+    int tj = 0; unsigned oc = 0;                                          // the served member's range: j - rb_start, rb_count
+    auto len_of = [&](int k) { return (k == 0) * pl.len0 + (k == 1) * pl.len1 + (k == 2) * pl.len2 + (k == 3) * pl.len3; };
+    auto fold = [&](int k) {
+        const bool left_half = pl.lsplit ? (k < 2) : (k < 1);
+        const bool first = pl.lsplit ? (k == 0 || k == 2) : (k <= 1);
+        if (left_half) { if (first) { lf = fr; lg = gr; } else { lf = lf + fr; lg = lg + gr; } }
+        else           { if (first) { rf = fr; rg = gr; } else { rf = rf + fr; rg = rg + gr; } }
+    };
+    auto tree = [](double v) {
+        v = v + dpp_f64<0xB1>(v);           // quad_perm [1,0,3,2]: lane ^ 1
+        v = v + dpp_f64<0x4E>(v);           // quad_perm [2,3,0,1]: lane ^ 2
+        return v + dpp_f64<0x141>(v);       // row_half_mirror: the other quad of the 8 (every lane of a quad holds the quad's sum)
+    };
+    full = 0.0; part = 0.0;
+    auto consume = [&](const v4f x) {
+        if (cl == 0) {
+            const int sc = __builtin_amdgcn_ds_bpermute((cq * 8 + cluster) * 4, my_sc);
+            tj = j - (sc & 0xffff); oc = (unsigned)sc >> 16;
+            leaf = 0; left = member_line_chunks(pl.len0); rb0 = 0; leaf_end = pl.len0; fr = 0.0; gr = 0.0;
+        }
+        if (tail > 0 && cl == nl - 1) {
+            // the row's last R mod 8 RBs, one after the other behind the tree: positions 0..3 are the cluster's first lane's, 4..6 its
+            // second lane's, so the chain runs through both -- the second lane takes the first one's sums over and ends up with the row's
+            const float e[4] = {x.x, x.y, x.z, x.w};
+            const int t0 = tj - j + (R - tail);          // (RB of position k) - rb_start = t0 + k
+            double a = fr, b = gr;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (k < tail) {
+                    const double d = (double)e[k];
+                    a += d;
+                    b = fma(d, (unsigned)(t0 + k) < oc ? 1.0 : 0.0, b);
+                }
+            }
+            a = dpp_f64<0xA0>(a); b = dpp_f64<0xA0>(b);      // quad_perm [0,0,2,2]: the first lane's sums, in the second lane
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                if (4 + k < tail) {
+                    const double d = (double)e[k];
+                    a += d;
+                    b = fma(d, (unsigned)(t0 + 4 + k) < oc ? 1.0 : 0.0, b);
+                }
+            }
+            fr = a; gr = b;
+            fold(pl.n_leaves - 1);
+        } else {
+            const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const double d = (double)e[k];
+                f += d;
+                g = fma(d, (unsigned)(tj + rb0 + 8 * k) < oc ? 1.0 : 0.0, g);
+            }
+            rb0 += 32;
+            if (--left == 0) {
+                fr = tree(f); gr = tree(g);
+                f = 0.0; g = 0.0;
+                if (!(leaf == pl.n_leaves - 1 && tail > 0)) fold(leaf);
+                leaf += 1;
+                left = member_line_chunks(len_of(leaf)); rb0 = leaf_end; leaf_end += len_of(leaf);
+            }
+        }
+        if (++cl == nl) {
+            // back to the owner: lane 8 cq + i takes the sums of cluster i from that cluster's first lane -- its second where a tail line
+            // ended the row there (without one every lane of the cluster holds the sums)
+            const double fv = pl.n_leaves == 1 ? lf : lf + rf, gv = pl.n_leaves == 1 ? lg : lg + rg;
+            const int from = j * 32 + (tail > 0 ? 4 : 0);
+            const double fo = lane_f64(fv, from), go = lane_f64(gv, from);
+            if (cluster == cq) { full = fo; part = go; }
+            cl = 0; cq += 1;
+        }
+    };
+    bool hooked = false;
+#pragma unroll 1
+    for (int base = 0; base < total; base += DQ) {
+        if (base + DQ >= total) { after_issue(); hooked = true; }
+#pragma unroll
+        for (int d = 0; d < DQ; d++) {
+            if (base + d < total) {
+                const v4f x = st.q[d];
+                if (base + d + DQ < total) st.issue(st.q[d]);
+                consume(x);
+            }
+        }
+    }
+    if (!hooked) after_issue();
+}
+
 // Sums of one row: `full` over all R RBs, `part` over the RBs selected by in(r).
 // Accumulators start at 0.0 instead of being initialised with the leaf's first group: 0.0 + x == x
 // exactly, so the result is numpy's bit for bit while the loop body stays branch-free; the only

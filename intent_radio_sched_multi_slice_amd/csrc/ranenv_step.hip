@@ -32,6 +32,7 @@ step_kernel_t pick(const StepLaunch &l)
             if (mode == MODE_DENSE) return ranenv_core_kernel<MODE_DENSE | MODE_PE, NPW, false>;
             return nullptr;
         }
+        if (mode == MODE_STEP && l.many && l.members) return ranenv_core_kernel_members<NPW>;
         if (mode == MODE_STEP) return l.many ? ranenv_core_kernel<MODE_STEP, NPW, true> : ranenv_core_kernel<MODE_STEP, NPW, false>;
         if (mode == MODE_DENSE) return ranenv_core_kernel<MODE_DENSE, NPW, false>;
         return ranenv_core_kernel<MODE_RESET, NPW, false>;
@@ -63,6 +64,7 @@ step_kernel_t pick(const StepLaunch &l)
         return nullptr;
 #endif
     case SB_PERSIST:
+        if (!l.gather && l.members) return ranenv_persist_kernel_members<NPW>;
         return l.gather ? ranenv_persist_kernel<true, NPW> : ranenv_persist_kernel<false, NPW>;
     case SB_PERSIST_TINY:
         return l.gather ? nullptr : ranenv_persist_kernel_tiny<NPW>;

@@ -394,7 +394,11 @@ struct StepCarry {
 #endif
 };
 
-template <int MODE_X, int NQ, bool GATHER, int NP, bool PERSIST = false, int PACK = 1, bool MIX = false, typename P>
+// MEMBERS (compact streaming rollouts, the lean MANY and the streaming persistent build): the stream phase reads the handle's
+// member-lines copy of the tile (MemberLines / member_line_sums, ranenv_numeric.hpp) -- the rows of slice members only, 8 lanes
+// per member -- instead of every UE's row of the bound tile; p.ml_pool / p.ml_stride describe the copy.  Same sums, bit for bit.
+struct NoMemberLines { };
+template <int MODE_X, int NQ, bool GATHER, int NP, bool PERSIST = false, int PACK = 1, bool MIX = false, bool MEMBERS = false, typename P>
 DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,   // warm: `cy` holds what the previous TTI of this launch left
                      std::conditional_t<PACK == 2, SeStreamLane<GATHER ? 1 : NQ>, SeStream<GATHER ? 1 : NQ>> *se_carry = nullptr,
                      const bool se_ready = false, const bool se_next = false, const bool narrow_in = false)
@@ -403,6 +407,7 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     constexpr bool PE = (MODE_X & MODE_PE) != 0;
     static_assert(!PE || (MODE != MODE_RESET && !PERSIST && PACK == 1 && !MIX), "per-element scaling: the lean step / dense builds");
     static_assert(!(GATHER && MODE == MODE_DENSE), "a dense sched_decision reads whole rows: streaming only");
+    static_assert(!MEMBERS || (MODE == MODE_STEP && !PE && !GATHER && PACK == 1 && !MIX && NQ < 8), "member lines: the lean step builds of rollouts");
     // PACK = 2 (envs of at most 32 UEs, one-wave workgroups): the wave steps TWO envs, lanes 0-31 the first, lanes 32-63 the second --
     // `tid` is the lane within the env's half, everything per env (index, counters, episode, tile, LDS image, row addresses) is a
     // per-lane value that happens to be equal across a half, and the 16-lane slice groups are DPP rows 0 / 2 of the wave.
@@ -601,7 +606,10 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     SeQ se_local;
     SeQ &se1 = SE_AHEAD ? *se_carry : se_local;
     const bool se_quad = !GATHER && p.se_quad != 0 && p.se_tiles == nullptr;   // (explicit per-step tiles are RB-major)
-    if (!GATHER && !(SE_AHEAD && se_ready)) se1.init(tile, U, u, R, se_quad);          // lane = UE
+    constexpr int ML_DEPTH = 4;                    // member lines in flight per lane: 4 KB per wave, as the quad stream's two groups (8 do not fit 96 VGPRs: 45 spilled)
+    std::conditional_t<MEMBERS, MemberLines<ML_DEPTH>, NoMemberLines> ml;
+    if constexpr (MEMBERS) ml.init(COLD(ml_pool) + (size_t)tile_no * (size_t)COLD(ml_stride), U, R, act, u);      // 8 lanes = one member
+    else if (!GATHER && !(SE_AHEAD && se_ready)) se1.init(tile, U, u, R, se_quad);          // lane = UE
     asm volatile("" ::: "memory");
     // wave 0 zeroes what can be read of the per-slice rows (NP positions of S slices: nothing reads further) and parks the tables.
     // A warm TTI finds both as it needs them: the tables are the scenario's, and every role writes a slice's rows at its
@@ -665,7 +673,8 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
         }
     } else if constexpr (MODE == MODE_STEP) {
         const unsigned us1 = (unsigned)rb_start, uc1 = (unsigned)rb_count;
-        row_sums<PE>(se1, R, [=](int r) { return ((unsigned)r - us1) < uc1; }, my_full, my_part, hook, PE ? COLD(bw_per_rb) : 1.0);
+        if constexpr (MEMBERS) member_line_sums(ml, R, us1, uc1, my_full, my_part, hook);
+        else row_sums<PE>(se1, R, [=](int r) { return ((unsigned)r - us1) < uc1; }, my_full, my_part, hook, PE ? COLD(bw_per_rb) : 1.0);
     } else if constexpr (MODE == MODE_DENSE) {
         const uint8_t *mrow = p.dense + ((size_t)e * U + u) * R;
         row_sums<PE>(se1, R, [=](int r) { return mrow[r] != 0; }, my_full, my_part, hook, PE ? COLD(bw_per_rb) : 1.0);
@@ -1106,7 +1115,7 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
 // steps its env again as soon as it is done, from the state it has just written (its own CU's L1 / L2 hold it), instead
 // of ending and being launched again.  Between TTIs without a warm entry: every store of the workgroup is out and visible to
 // its other waves (full_sync: explicit vmcnt(0) + barrier; the waves of a workgroup share their CU's L1).
-template <int MODE_X, int NQ, bool GATHER, int NP, bool MANY, int PACK = 1, bool MIX = false>      // MANY: the build for launches of more than one TTI
+template <int MODE_X, int NQ, bool GATHER, int NP, bool MANY, int PACK = 1, bool MIX = false, bool MEMBERS = false>      // MANY: the build for launches of more than one TTI
 DEVFN void step_loop(const KP &p)
 {
     constexpr int MODE = MODE_X & 3;
@@ -1151,7 +1160,7 @@ DEVFN void step_loop(const KP &p)
             // of the k-th CONTIGUOUS eighth of the launch's envs, so that an XCD touches one eighth of every per-env array (see persist_try_fresh)
             const int nb_ = (int)gridDim.x, xk_ = (int)blockIdx.x & 7, q_ = nb_ >> 3, r_ = nb_ & 7;
             const int b_perm = xk_ * q_ + (xk_ < r_ ? xk_ : r_) + ((int)blockIdx.x >> 3);
-            if (step_body<MODE_X, NQ, GATHER, NP, false, PACK, MIX>(*kc, cy, warm, MIX ? e_mix : kc->e0 + b_perm * PACK, nullptr, false, false, narrow)) return;
+            if (step_body<MODE_X, NQ, GATHER, NP, false, PACK, MIX, MEMBERS>(*kc, cy, warm, MIX ? e_mix : kc->e0 + b_perm * PACK, nullptr, false, false, narrow)) return;
             if (k + 1 < n) {
                 // The next TTI takes over in registers what it would otherwise load back (StepCarry): only LDS has to be handed over
                 // between the waves.
@@ -1304,7 +1313,7 @@ template <typename P> DEVFN int persist_finish(const P &p, PersistLocal &pl, int
     return 0;
 }
 
-template <int NQ, bool GATHER, int NP>
+template <int NQ, bool GATHER, int NP, bool MEMBERS = false>
 DEVFN void persist_loop()
 {
     typedef const __attribute__((address_space(4))) KP *kp_const_t;
@@ -1359,7 +1368,7 @@ DEVFN void persist_loop()
                 // -- the workgroup keeps its env at most chunk ends -- the next chunk's first (what is requested ahead for it is wasted
                 // when the env changes hands)
                 const bool ahead = done + k + 1 < n_tti;
-                (void)step_body<MODE_STEP, NQ, GATHER, NP, true>(*kc, cy, warm, e, &seq, se_ready, ahead);
+                (void)step_body<MODE_STEP, NQ, GATHER, NP, true, 1, false, MEMBERS>(*kc, cy, warm, e, &seq, se_ready, ahead);
                 se_ready = ahead;
                 if (k + 1 < n) { warm = true; wg_sync(); }
             }
@@ -1400,6 +1409,19 @@ __global__ void __launch_bounds__(CORE_NT) __attribute__((amdgpu_waves_per_eu(RA
 #endif
 }
 
+// ... and the streaming build whose stream phase reads the member-lines copy (step_body's MEMBERS): the two-wave class keeps the priority
+template <int NP>
+__global__ void __launch_bounds__(CORE_NT) __attribute__((amdgpu_waves_per_eu(RANENV_PERSIST_WPE, RANENV_PERSIST_WPE))) ranenv_persist_kernel_members(const KP p)
+{
+    (void)p;
+#if RANENV_DIAG == 0 || RANENV_DIAG == 12
+#if RANENV_CLASS_PRIO
+    if (blockDim.x != WAVE) __builtin_amdgcn_s_setprio(RANENV_CLASS_PRIO);
+#endif
+    persist_loop<SE_DEPTH_LEAN, false, NP, true>();
+#endif
+}
+
 // The same for a batch that leaves the chip at <= 2 waves per SIMD (BASELINE configs[1], B 1024): 256 VGPRs are there for the
 // taking, so a lane keeps its whole SE row in flight (16 groups of 8 loads): the stream phase of a workgroup's chain is one
 // memory latency instead of four (profiles/r04_ab_log.txt: 23.4 against 26.6 us per TTI).  Streaming only.
@@ -1432,6 +1454,12 @@ template <int MODE, int NP, bool MANY>
 __global__ void __launch_bounds__(CORE_NT) RANENV_CORE_ATTR ranenv_core_kernel(const KP p)
 {
     step_loop<MODE, ((MODE & 3) == MODE_DENSE || NP == 16) ? 1 : SE_DEPTH_LEAN, false, NP, MANY>(p);
+}
+// (the lean MANY step build reading the member-lines copy: compact streaming rollouts, step_body's MEMBERS; the 16-wide rows as in the gather build)
+template <int NP>
+__global__ void __launch_bounds__(CORE_NT) __attribute__((amdgpu_waves_per_eu(NP == 16 ? 4 : 5, NP == 16 ? 4 : 5))) ranenv_core_kernel_members(const KP p)
+{
+    step_loop<MODE_STEP, NP == 16 ? 1 : SE_DEPTH_LEAN, false, NP, true, 1, false, true>(p);
 }
 template <int MODE, int NP, bool MANY>
 __global__ void __launch_bounds__(CORE_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) ranenv_core_kernel_small(const KP p)

@@ -5,7 +5,7 @@
 An entry is one (schedule, SE mode): `stream_rollout`, `gather_rollout` (tools/profile_rollout.py: the headline's compact, fused
 rollouts over 3 partitions; <ttis> = the TTIs of the whole batch that process stepped, printed by the driver) or `stream`, `gather`
 (tools/profile_step.py: one full-width launch per TTI; <ttis> = its launches).  Per entry, over ALL launches of the STEP kernels
-(ranenv_core_kernel*<0, ...>, any build) of the process:
+(ranenv_core_kernel*<0, ...>, any build, the member-lines builds included) of the process:
   *_per_tti        = counter summed over the launches / ttis  (one TTI of the whole batch)
   ttis_per_launch  = ttis * partitions_seen / launches  is NOT derivable from counters; what is: launches and ttis, both listed
   hbm_bytes_per_tti = (2 * FETCH_SIZE + WRITE_SIZE) KiB -> bytes; the factor 2 on FETCH_SIZE is the gfx950 correction of
@@ -19,7 +19,7 @@ def summed(dirs, counter):
     for d in dirs:
         for f in glob.glob(d + "/*/*counter_collection.csv") + glob.glob(d + "/*counter_collection.csv"):
             for r in csv.DictReader(open(f)):
-                if r["Counter_Name"] == counter and re.search(r"ranenv_(core|persist)_kernel\w*<0[,>]|ranenv_persist_kernel|ranenv_core_kernel_packed", r["Kernel_Name"]):
+                if r["Counter_Name"] == counter and re.search(r"ranenv_(core|persist)_kernel\w*<0[,>]|ranenv_persist_kernel|ranenv_core_kernel_packed|ranenv_core_kernel_members", r["Kernel_Name"]):
                     tot += float(r["Counter_Value"]); n += 1
     return (tot, n) if n else (None, 0)
 
