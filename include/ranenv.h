@@ -705,7 +705,8 @@ int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *d
  *       member m's rows of epoch k are entries [host_first[m], host_first[m + 1]) of row k (host arrays [n_members + 1] from 0, non-decreasing).  The caller
  *       supplies the shuffles; intra lists hold rows with mask_inter != 0 only.  Minibatches are consecutive chunks of `minibatch`
  *       entries, a short last chunk is a minibatch of its own.  An entry outside the record counts as a row of the minibatch and
- *       contributes nothing.  dev_order_intra NULL: the inter kind alone is updated.
+ *       contributes nothing: the row weight stays 1 / (entries of the minibatch), and [6] counts the live rows.  Under adv_norm 1 such
+ *       an entry counts as an advantage of 0 in the minibatch's mean and std.  dev_order_intra NULL: the inter kind alone is updated.
  *     Per minibatch: gradient of L in float32 (matrix cores; per 32-row tile, accumulated in tile order), the joint L2 norm of the
  *       actor's and critic's gradient in float64, scale = min(1, grad_clip / (norm + 1e-6)) rounded to float32, t += 1, then per element
  *       g = g * scale;  m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  w = w - (float)(lr / (1 - b1^t)) * (m / (sqrtf(v) / (float)sqrt(1 - b2^t) + eps))

@@ -569,12 +569,22 @@ def ppo_loss_reference(actor, critic, batch, kind: str, clip: float, vf_coeff: f
     """The minibatch loss of ``ppo_update`` in torch (autograd differentiates it): ``actor`` / ``critic`` (None: no value term) lists of
     ``(W, b)`` in the dtype to compute in, ``batch`` from ``ppo_rows``.  Returns (loss, {policy_loss, value_loss, entropy, kl,
     clip_frac, logp}).  ``slip``: a deliberately wrong variant, for the tests that show the tolerances bite."""
-    def forward(x, layers, act):
+    def forward(x, layers, act, deriv=None):
         for i, (w, b) in enumerate(layers):
-            x = x @ w.T + b
+            if slip == "db_drops_row_32" and i == 0 and x.shape[0] > 32:      # (row 32 misses layer 0's bias reduction)
+                rows = b.expand(x.shape[0], -1)
+                x = x @ w.T + torch.cat([rows[:32], rows[32:33].detach(), rows[33:]])
+            else:
+                x = x @ w.T + b
             if i < len(layers) - 1:
                 y = torch.tanh(x) if act == "tanh" else torch.relu(x)
-                x = y.detach() + (x - x.detach()) if slip == "no_activation_derivative" else y
+                if slip == "no_activation_derivative":
+                    x = y.detach() + (x - x.detach())
+                elif deriv is not None and deriv != act:      # (the other activation's derivative, from the output as the kernel takes it)
+                    d = 1.0 - y * y if deriv == "tanh" else (y > 0).to(y.dtype)
+                    x = y.detach() + (x - x.detach()) * d.detach()
+                else:
+                    x = y
         return x
     out = forward(batch["x"], actor, act_actor)
     if kind == "inter":
@@ -599,7 +609,7 @@ def ppo_loss_reference(actor, critic, batch, kind: str, clip: float, vf_coeff: f
              "clip_frac": mean_of(((ratio < 1.0 - clip) | (ratio > 1.0 + clip)).to(ratio.dtype)), "logp": logp, "value_loss": torch.zeros((), dtype=ratio.dtype)}
     loss = stats["policy_loss"] - (-ent_coeff if slip == "entropy_sign" else ent_coeff) * stats["entropy"]
     if critic is not None:
-        stats["value_loss"] = mean_of((forward(batch["x"], critic, act_critic)[:, 0] - batch["vtarg"]) ** 2)
+        stats["value_loss"] = mean_of((forward(batch["x"], critic, act_critic, act_actor if slip == "critic_takes_actor_derivative" else None)[:, 0] - batch["vtarg"]) ** 2)
         loss = loss + vf_coeff * stats["value_loss"]
     return loss, stats
 

@@ -8,7 +8,6 @@ the step (the nets read those buffers before the step overwrites them), so a row
 from __future__ import annotations
 
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
@@ -18,33 +17,11 @@ torch = pytest.importorskip("torch")
 from tests import policy_ref as pr
 from tests.common import OBS_TOL, REW_TOL
 from tests.gpu_common import GRID, make_inter_net, make_net, need_gpu
+from tests.gpu_common import shaped_workload as _workload
 
 pytestmark = pytest.mark.gpu
 
 STATS = {"pairs": 0}          # (config, row) pairs compared, reported at the end of the module
-
-
-def _workload(S, Us, B, max_steps=1000, seed=10, U=None, R=25, G=1, trace_len=32):
-    """An env whose scenarios 0..3 have every slice active (every sorted position unmasked) and 4..7 from 1 to S slices; env b
-    plays scenario b % 8, so env 0 always has them all."""
-    from intent_radio_sched_multi_slice_amd import _lib
-    from intent_radio_sched_multi_slice_amd.scenario import generate_scaled_scenarios
-    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
-    U = min(S * Us, 256) if U is None else U
-    wl = make_mult_slice_workload(B, torch.device("cuda", 0), policy=_lib.POLICY_MAPF, intra=_lib.INTRA_PF, n_scenarios=8,
-                                  n_traces=8, trace_len=trace_len, seed=seed, n_slices=S, n_ues=U, n_rbs=R, rbs_per_rbg=G,
-                                  max_ues_slice=Us, max_steps=max_steps, min_slices=1, min_ues=1)
-    full = generate_scaled_scenarios(4, seed=seed + 1, n_slices=S, n_ues=U, max_ues_slice=Us, min_slices=S, min_ues=1)
-    for f in dataclasses.fields(full):
-        getattr(wl.tables, f.name)[:4] = getattr(full, f.name)
-    env = wl.env
-    env.load_scenarios(wl.tables)
-    eps = env.episodes
-    scen = np.arange(B) % 8
-    env.set_episodes(scenario=scen, se_base=eps["se_base"], se_len=eps["se_len"], se_offset=eps["se_offset"],
-                     trf_base=scen * trace_len, trf_len=trace_len, trf_offset=eps["trf_offset"])
-    wl.scenario = scen
-    return wl
 
 
 def _layers(net):

@@ -14,30 +14,15 @@ torch = pytest.importorskip("torch")
 
 from tests import collect_ref as cr
 from tests import ppo_update_ref as ref
-from tests.gpu_common import _ordered, need_gpu, to_host
+from tests.gpu_common import _ordered, to_host
 
 pytestmark = pytest.mark.gpu
 
 E_INVALID, E_STATE = -1, -3
-ALL = 1 << 20                 # a minibatch size beyond every member's rows: one minibatch per epoch
+ALL = ref.ALL                 # a minibatch size beyond every member's rows: one minibatch per epoch
 
 
-def _workload(B, trace_len=32, seed=10):
-    """The native shape (5 slices, 25 UEs, 135 RBs in groups of 5) with every env on a scenario that has an inactive slice"""
-    from intent_radio_sched_multi_slice_amd import _lib
-    from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
-    need_gpu()
-    wl = make_mult_slice_workload(B, torch.device("cuda", 0), policy=_lib.POLICY_MAPF, intra=_lib.INTRA_PF, n_scenarios=8, n_traces=8,
-                                  trace_len=trace_len, seed=seed, n_slices=ref.S, n_ues=25, n_rbs=135, rbs_per_rbg=5, max_ues_slice=ref.US,
-                                  max_steps=1000, min_slices=1, min_ues=1)
-    n_active = (np.asarray(wl.tables.slice_active) != 0).sum(axis=1)
-    partial = np.nonzero((n_active >= 1) & (n_active < ref.S))[0]
-    assert len(partial) >= 2, n_active
-    env, scen = wl.env, partial[np.arange(B) % len(partial)]
-    eps = env.episodes
-    env.set_episodes(scenario=scen, se_base=eps["se_base"], se_len=eps["se_len"], se_offset=eps["se_offset"], trf_base=scen * trace_len,
-                     trf_len=trace_len, trf_offset=eps["trf_offset"])
-    return env
+_workload = ref.native_workload
 
 
 def _env(case, pop=True, stochastic=True, first=ref.FIRST, seed=ref.SEED):
@@ -71,69 +56,12 @@ def _order(rec, first, epochs, seed=3):
     return ppo_row_order(rec, first, epochs, seed)
 
 
-def _weights(env, G, roles=ref.ROLES):
-    """Every role's read-back layers, [role][member] -> list of (W, b) on the host"""
-    return {r: [[(w.cpu().numpy().copy(), b.cpu().numpy().copy()) for w, b in env.net_weights(r, m)] for m in range(G)] for r in roles}
-
-
-def _state(env, G, roles=ref.ROLES):
-    """The whole trainable state as host bytes: weights, moments and counters of every role and member"""
-    out = {}
-    for r in roles:
-        for m in range(G):
-            for i, (w, b) in enumerate(env.net_weights(r, m)):
-                out[f"{r}/{m}/w{i}"], out[f"{r}/{m}/b{i}"] = w.cpu().numpy().copy(), b.cpu().numpy().copy()
-            st = env.ppo_state(r, m)
-            for k, v in st.items():
-                out[f"{r}/{m}/{k}"] = v.cpu().numpy().copy()
-    return out
-
-
-def _same_state(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].tobytes() == b[k].tobytes(), f"{what}: {k} differs"
+_weights, _state, _same_state = ref.weights, ref.state, ref.same_state
 
 
 def _check_against_twin(env, rec, order, case, out, weights, members, what, hp=None):
-    """dev_grad and the statistics of a one-minibatch, lr = 0 call against the float64 twin at ``weights``; the float32 twin is the
-    yardstick.  Asserts the gradient; returns the worst device / yardstick ratio and the statistics beyond 1e-6 relative or absolute."""
-    misses = []
-    hp = dict(clip=0.2, vf_coeff=0.5, ent_coeff=0.01, adv_norm=True) if hp is None else hp
-    host = {k: v.cpu() for k, v in rec.items()}
-    worst = 0.0
-    for kind_i, kind in enumerate(("inter", "intra")):
-        first = order["first_" + kind]
-        for m in members:
-            lo, hi = int(first[m]), int(first[m + 1])
-            if hi == lo:
-                continue
-            a, c = ("inter", "v_inter") if kind == "inter" else ("intra", "v_intra")
-            critic = weights[c][m] if c in weights else None         # (a kind without a bound critic: no value term, actor gradient only)
-            args = dict(rec=host, kind=kind, actor=ref.as_torch(weights[a][m]), critic=None if critic is None else ref.as_torch(critic), order=order["order_" + kind].cpu(),
-                        lo=lo, hi=hi, epochs=1, minibatch=ALL, lr=0.0, grad_clip=0.0, act_actor=ref.CASES[case][1], act_critic=ref.CASES[case][1],
-                        layout=ref.CASES[case][2], **hp)
-            from intent_radio_sched_multi_slice_amd.adapters import ppo_update_reference
-            t64, t32 = ppo_update_reference(dtype=torch.float64, **args), ppo_update_reference(dtype=torch.float32, **args)
-            dev = ref.unpack_grad(out["grad"][m, kind_i].cpu().numpy(), weights[a][m], critic or [])
-            for net in ("actor", "critic"):
-                for li, (g64, g32, gd) in enumerate(zip(t64["grad"][net], t32["grad"][net], dev[net])):
-                    for name, x64, x32, xd in zip("Wb", g64, g32, gd):
-                        x64, x32 = x64.numpy().astype(np.float64), x32.numpy().astype(np.float64)
-                        n64 = np.linalg.norm(x64)
-                        assert n64 > 0.0, f"{what}: {kind} member {m} {net} layer {li} {name}: the twin's gradient is zero"
-                        e_dev, e_32 = np.linalg.norm(xd - x64) / n64, np.linalg.norm(x32 - x64) / n64
-                        ratio = e_dev / max(e_32, 1e-6)
-                        worst = max(worst, ratio)
-                        assert ratio <= 8.0, f"{what}: {kind} member {m} {net} layer {li} {name}: device error {e_dev:.3g}, float32 torch {e_32:.3g}"
-            for i, name in enumerate(("policy_loss", "value_loss", "entropy", "kl", "clip_frac")):
-                got, want = out[name][m, kind_i, 0], t64["stats"][0, i]
-                print(f"{what} {kind} m{m} {name}: device {got:.9g} twin {want:.9g}")
-                if not abs(got - want) <= 1e-6 * max(1.0, abs(want)):
-                    misses.append(f"{what}: {kind} member {m} {name}: device {got:.9g}, twin {want:.9g}")
-            assert out["rows"][m, kind_i, 0] == hi - lo and out["minibatches"][m, kind_i, 0] == 1
-    print(f"{what}: worst gradient error, device / float32 torch yardstick: {worst:.3g}")
-    return worst, misses
+    """ref.check_against_twin with the case's one activation for both nets and its intra layout"""
+    return ref.check_against_twin(rec, order, out, weights, members, what, ref.CASES[case][1], ref.CASES[case][1], ref.CASES[case][2], hp=hp)
 
 
 _RUNS = {}
@@ -235,30 +163,7 @@ def test_one_adam_step_is_the_stated_float32_arithmetic_on_the_devices_own_gradi
     hp = dict(lr=np.array([3e-4, 1e-3, 5e-3]), grad_clip=np.array([0.5, 0.05, 0.0]), betas=(0.9, 0.999), eps=1e-8)
     out = env.ppo_update(rec, epochs=1, minibatch=ALL, order=order, grad=True, **hp)
     w1 = _weights(env, G)
-    worst, exact, total = 0, 0, 0
-    worst_mv, exact_mv, total_mv = 0, 0, 0
-    for kind_i, (a, c) in enumerate((("inter", "v_inter"), ("intra", "v_intra"))):
-        for m in range(G):
-            g = ref.unpack_grad(out["grad"][m, kind_i].cpu().numpy(), w0[a][m], w0[c][m], dtype=np.float32)
-            want, norm, want_m, want_v = ref.adam_step_f32(w0[a][m] + w0[c][m], g["actor"] + g["critic"], 1, float(hp["lr"][m]), float(hp["grad_clip"][m]),
-                                                           hp["betas"], hp["eps"], moments=True)
-            assert abs(out["grad_norm"][m, kind_i, 0] - norm) <= 1e-9 * norm
-            for (ww, wb), (gw, gb) in zip(want, w1[a][m] + w1[c][m]):
-                for x, y in ((ww, gw), (wb, gb)):
-                    d = np.abs(_ordered(x) - _ordered(y))
-                    worst, exact, total = max(worst, int(d.max())), exact + int((d == 0).sum()), total + d.size
-            sa, sc = env.ppo_state(a, m), env.ppo_state(c, m)
-            for name, want_x in (("m", want_m), ("v", want_v)):
-                got = ref.unpack_grad(np.concatenate([sa[name].cpu().numpy(), sc[name].cpu().numpy()]), w0[a][m], w0[c][m], dtype=np.float32)
-                for (xw, xb), (yw, yb) in zip(want_x, got["actor"] + got["critic"]):
-                    for x, y in ((xw, yw), (xb, yb)):
-                        d = np.abs(_ordered(x) - _ordered(y))
-                        worst_mv, exact_mv, total_mv = max(worst_mv, int(d.max())), exact_mv + int((d == 0).sum()), total_mv + d.size
-            assert int(sa["t"].cpu()[0]) == 1
-    print(f"{case}: Adam step, worst ulp distance {worst}; {exact} of {total} weights bit-equal to the numpy restatement")
-    print(f"{case}: Adam moments, worst ulp distance {worst_mv}; {exact_mv} of {total_mv} bit-equal to the numpy restatement")
-    assert worst <= 4
-    assert worst_mv <= 4
+    ref.check_adam_step(env, out, w0, w1, hp, G, case)
     assert any(not np.array_equal(x[0], y[0]) for x, y in zip(w0["inter"][0], w1["inter"][0])), "the weights did not move"
     env.close()
 
@@ -287,15 +192,7 @@ def _loop_run(case):
     followed, misses, steps, clipped = 0.0, [], 0, [0.0] * E
     for ep in range(E):
         for i in range(max(max(n_chunks[0]), max(n_chunks[1]))):
-            step = {}
-            for kind, f in (("inter", fi), ("intra", fa)):
-                rows, first = [], [0]
-                for m in range(G):
-                    lo, hi = int(f[m]), int(f[m + 1])
-                    chunk = order["order_" + kind][ep, lo + i * MB:min(lo + (i + 1) * MB, hi)] if lo + i * MB < hi else order["order_" + kind][ep, 0:0]
-                    rows.append(chunk)
-                    first.append(first[-1] + chunk.numel())
-                step["order_" + kind], step["first_" + kind] = torch.cat(rows)[None, :].contiguous(), np.array(first, dtype=np.int32)
+            step = ref.chunk_order(order, G, MB, ep, i)
             # (the twin follows EVERY step of both epochs, on the REAL call's dev_grad and statistics at the weights read back in front of it)
             weights = _weights(env_b, G)
             o = env_b.ppo_update(rec_b, epochs=1, minibatch=ALL, order=step, grad=True, **hp)
@@ -414,11 +311,7 @@ def test_rebinding_the_critic_restarts_the_actors_optimiser_with_the_shared_coun
     env.close()
 
 
-def _code(fn):
-    from intent_radio_sched_multi_slice_amd._lib import RanEnvError
-    with pytest.raises(RanEnvError) as e:
-        fn()
-    return int(str(e.value).split("(")[1].split(")")[0]), str(e.value)
+_code = ref.refusal
 
 
 def test_refusals_precede_every_device_call():

@@ -194,6 +194,106 @@ def test_a_planted_slip_in_the_gradient_leaves_the_gpu_tolerance(setup, slip):
         assert ratio > 8.0, (slip, kind, ratio)
 
 
+def _shape_setup(shape, seed=31):
+    """``setup`` for a SHAPES entry: a synthetic record of the entry's (S, Us) whose logp column is the members' nets' own
+    log-probability plus a perturbation, the nets the GPU file binds (ref.shape_nets), and the row lists of the population ref.FIRST"""
+    S, Us, layout, (aw, aa), (cw, ca) = ref.SHAPES[shape]
+    rec = ref.synthetic_record(seed=seed, S=S, Us=Us)
+    nets = ref.shape_nets(shape, 3)
+    order = ad.ppo_row_order(rec, ref.FIRST, 1, seed=4)
+    g = torch.Generator().manual_seed(5)
+    view = rec["logp"].reshape(-1, S + 1)
+    for kind in ("inter", "intra"):
+        rows = torch.arange(rec["mask_inter"].numel() // (S if kind == "inter" else 1))
+        envs = (rows // (1 if kind == "inter" else S)) % 12
+        batch = ad.ppo_rows(rec, kind, rows, layout)
+        for m in range(3):
+            with torch.no_grad():
+                _, st = ad.ppo_loss_reference([(w.double(), b.double()) for w, b in ref.layers_of(nets[kind][m])], None, batch, kind, 0.2, 0.5, 0.01, False, aa)
+            lp = (st["logp"] + 0.25 * torch.randn(st["logp"].shape, generator=g, dtype=torch.float64)).to(torch.float32)
+            mine = (envs >= ref.FIRST[m]) & (envs < ref.FIRST[m + 1])
+            if kind == "inter":
+                view[rows[mine], 0] = lp[mine]
+            else:
+                view[rows[mine] // S, 1 + rows[mine] % S] = lp[mine]
+    return {"rec": rec, "nets": nets, "order": order, "acts": (aa, ca), "layout": layout}
+
+
+def _shape_reference(su, kind, m, dtype=torch.float64, slip=None):
+    a, c = ("inter", "v_inter") if kind == "inter" else ("intra", "v_intra")
+    f = su["order"]["first_" + kind]
+    return ad.ppo_update_reference(su["rec"], kind, ref.layers_of(su["nets"][a][m]), ref.layers_of(su["nets"][c][m]), su["order"]["order_" + kind],
+                                   int(f[m]), int(f[m + 1]), epochs=1, minibatch=ref.ALL, lr=0.0, grad_clip=0.0, act_actor=su["acts"][0],
+                                   act_critic=su["acts"][1], layout=su["layout"], dtype=dtype, slip=slip, **HP)
+
+
+def _ratios(t64, t32, other):
+    """{(net, layer, "W" / "b"): the device / yardstick ratio the GPU test bounds by 8, with ``other`` for the device}"""
+    out = {}
+    for net in ("actor", "critic"):
+        for li, (g64, g32, go) in enumerate(zip(t64["grad"][net], t32["grad"][net], other["grad"][net])):
+            for name, x64, x32, xo in zip("Wb", g64, g32, go):
+                n = float(x64.norm())
+                out[net, li, name] = float((xo.double() - x64).norm()) / n / max(float((x32.double() - x64).norm()) / n, 1e-6)
+    return out
+
+
+def test_the_lds_formula_at_the_edge_of_the_plan():
+    """The header's formula (ref.lds_bytes) puts case A at 162 304 of 163 840 bytes for both kinds, [512, 512, 96] at S 5 beyond
+    (170 496), and every other grid case inside."""
+    S, Us, layout, (aw, _), (cw, _) = ref.SHAPES["A"]
+    assert ref.lds_bytes(S, Us, layout, aw, cw) == 4096 + 128 * (68 + 516 + 516 + 68 + 68) == 162304 <= ref.LDS_MAX
+    assert ref.lds_bytes(5, 5, "obs", [512, 512, 96], [512, 512, 96]) == 170496 > ref.LDS_MAX
+    assert [ref.net_ld(x) for x in (32, 64, 96, 128, 160, 256, 480, 512)] == [68, 68, 132, 132, 196, 260, 516, 516]
+    for S, Us, layout, (aw, _), (cw, _) in ref.SHAPES.values():
+        assert ref.lds_bytes(S, Us, layout, aw, cw) <= ref.LDS_MAX
+
+
+@pytest.mark.parametrize("shape", list(ref.SHAPES))
+def test_the_twin_is_healthy_on_the_shape_grid(shape):
+    """For every member of the GPU file's population and both kinds, with the nets it binds: every gradient tensor of the float64 twin
+    has a non-zero norm (a dead ReLU stack would make the GPU comparison vacuous -- and its "the twin's gradient is zero" assertion
+    fail), and the float32 yardstick is finite.  This guards ref.SHAPE_SEED: change the seed, not the shape."""
+    su = _shape_setup(shape)
+    for kind in ("inter", "intra"):
+        for m in range(3):
+            t64, t32 = _shape_reference(su, kind, m), _shape_reference(su, kind, m, torch.float32)
+            for net in ("actor", "critic"):
+                for li, (g64, g32) in enumerate(zip(t64["grad"][net], t32["grad"][net])):
+                    for name, x64, x32 in zip("Wb", g64, g32):
+                        assert float(x64.norm()) > 0.0, (shape, kind, m, net, li, name)
+                        assert bool(torch.isfinite(x32).all()), (shape, kind, m, net, li, name)
+            worst = max(_ratios(t64, t32, t32).values())
+            assert np.isfinite(worst) and worst <= 1.0 + 1e-9
+            assert np.isfinite(t64["stats"]).all() and np.isfinite(t32["stats"]).all()
+
+
+def test_planted_slips_at_width_leave_the_gpu_tolerance():
+    """On case E's intra nets ([255, 100] tanh actor over 33 inputs, [480] relu critic), member 2: a 16 x 16 block of the widest dW
+    zeroed, row 32 missing from one layer's db, and the actor's activation derivative taken for the critic each move the tensor they hit
+    beyond 8x the float32 yardstick."""
+    su = _shape_setup("E")
+    m, kind = 2, "intra"
+    f = su["order"]["first_intra"]
+    assert int(f[m + 1]) - int(f[m]) > 33
+    t64, t32 = _shape_reference(su, kind, m), _shape_reference(su, kind, m, torch.float32)
+    # (damage to the float32 twin's own gradient: block [16:32, 16:32] of the [100, 255] layer, the dW with the most blocks)
+    damaged = {"grad": {net: [(w.clone(), b.clone()) for w, b in t32["grad"][net]] for net in ("actor", "critic")}}
+    assert damaged["grad"]["actor"][1][0].shape == (100, 255)
+    damaged["grad"]["actor"][1][0][16:32, 16:32] = 0.0
+    r = _ratios(t64, t32, damaged)
+    print(f"a zeroed 16 x 16 block of dW: {r['actor', 1, 'W']:.3g} x the yardstick")
+    assert r["actor", 1, "W"] > 8.0
+    assert all(v <= 1.0 + 1e-9 for k, v in r.items() if k != ("actor", 1, "W"))
+    r = _ratios(t64, t32, _shape_reference(su, kind, m, slip="db_drops_row_32"))
+    print(f"row 32 missing from db of layer 0: actor {r['actor', 0, 'b']:.3g}, critic {r['critic', 0, 'b']:.3g} x the yardstick")
+    assert r["actor", 0, "b"] > 8.0 and r["critic", 0, "b"] > 8.0
+    r = _ratios(t64, t32, _shape_reference(su, kind, m, slip="critic_takes_actor_derivative"))
+    print(f"tanh's derivative on the relu critic: {r['critic', 0, 'W']:.3g} x the yardstick")
+    assert r["critic", 0, "W"] > 8.0 and r["critic", 0, "b"] > 8.0
+    assert all(v <= 1.0 + 1e-9 for k, v in r.items() if k[0] == "actor")
+
+
 def test_adam_slips_leave_four_ulp(setup):
     """Adam without bias correction, and the neighbour member's lr, each move a weight of the first step by more than 4 float32 ulp
     from the numpy restatement the GPU test compares with."""
