@@ -23,6 +23,11 @@ constexpr int N_STEP_BUILDS = SB_PERSIST_TINY + 1;          // (StepBuild, ranen
 
 }  // namespace
 
+// What a net is for (the first four: the ABI's role numbers of the IBSched nets), and the forms an IBSched role is bound in, in rising
+// precedence (ranenv::serving)
+enum NetRole { NET_INTER, NET_INTRA, NET_INTER_VALUE, NET_INTRA_VALUE, NET_HEAD_CLIP, NET_HEAD_TANH, NET_HEAD_VALUE, NET_SAC_Q };
+enum NetForm { FORM_ONE, FORM_SLICE, FORM_MEMBER };
+
 struct ranenv {
     ranenv_config cfg;
     KP kp;
@@ -108,63 +113,66 @@ struct ranenv {
     size_t prof_used = 0;
     long long prof_ttis = 0;       // TTIs covered by the launches timed since ranenv_profile_begin
     long long prof_env_ttis = 0;   // env-TTIs covered by the launches timed since ranenv_profile_begin
-    // One bound net: its layout, and its packed weights in a buffer of the slot's own (cap floats; an outgrown buffer stays allocated
-    // until ranenv_destroy).  A net per slice is S copies of one layout at net.slice_stride in that buffer, `net` describing slice 0's.
-    // A population's net (pop_*) is G copies at member_stride, with the copies' unpadded widths in dims for ranenv_set_population_member.
-    // A population's net also keeps every member's descriptor as the device table holds it (member[m].w = member m's copy) with its unpadded
-    // widths, and the largest member's LDS need; `mixed`: bound by ranenv_set_population_policy_mixed / _value_mixed -- the members may
-    // differ in shape, `net` is member 0's, and member_stride, the extent of every member, is the largest member's packed size.
+    // One bound net set: its copies' packed weights in a buffer of the slot's own (cap floats; an outgrown buffer stays allocated until
+    // ranenv_destroy, and a slot keeps its buffers while off).  member[i]: copy i's descriptor as the device sees it (.w = its address),
+    // member_dims[i]: its unpadded widths -- one entry for one net, one (slice 0's, the S copies standing at its slice_stride) for nets
+    // per slice, G entries at member_stride for a population's.  `mixed` (ranenv_set_population_policy_mixed / _value_mixed): the members
+    // may differ in shape; member_stride, the extent of every member, is the largest member's packed size.
     struct NetSlot {
-        PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; long long member_stride = 0; int32_t dims[6] = {};
+        int role; NetForm form;          // the IBSched role (-1: a head or SAC net) and the form of it: set once, here
+        NetSlot(int role_ = -1, NetForm form_ = FORM_ONE) : role(role_), form(form_) {}
+        PolicyNet net{}; bool on = false; float *w = nullptr; long long cap = 0; long long member_stride = 0;
         bool mixed = false; std::vector<PolicyNet> member; std::vector<std::array<int32_t, 6>> member_dims; size_t lds_max = 0;
         float *opt = nullptr; long long opt_cap = 0;      // ranenv_ppo_bind: Adam's m, v and the gradient scratch, opt_cap floats each, in the packed layout
+        // net -- copy 0's descriptor, PolicyNets points at it -- and lds_max, the largest copy's LDS need, follow from member[]
+        void derive() { net = member[0]; lds_max = 0; for (const PolicyNet &x : member) lds_max = std::max(lds_max, policy_lds_bytes(x)); }
     };
-    // ranenv_set_policy_network (actor, actor_intra: the shared intra net) and ranenv_set_intra_policy_networks (actor_ps: one intra net
-    // per slice, standing where the shared one stands while on); the same three for their critics (ranenv_set_value_network,
-    // ranenv_set_intra_value_networks); ranenv_set_head_policy_network / _head_value_network: SchedTWC / SchedColORAN's actor and critic
-    // on the head observation; ranenv_set_sac_critics
-    NetSlot actor, actor_intra, actor_ps, value, value_intra, value_ps, head, head_value, sac_q1, sac_q2;
-    // ranenv_set_population: the grouping (pop.n = 0: none), and the members' copies of the four IBSched nets (ranenv_set_population_policy /
-    // _value), each standing where its one-net slot stands while on -- the binding calls keep at most one of the two on per role
-    PopMap pop{};
-    NetSlot pop_actor, pop_intra, pop_value, pop_vintra;
+    // THE ROLE TABLE: the IBSched nets by the ABI's role number (NetRole: 0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)
+    // and form -- one net (ranenv_set_policy_network / _value_network), one per slice (ranenv_set_intra_policy_networks / _intra_value_networks:
+    // roles 1 and 3), one per member (ranenv_set_population_policy / _value).  Which forms a binding call switches on and off: BIND_RULES.
+    NetSlot nets[4][3] = {{{0, FORM_ONE}, {0, FORM_SLICE}, {0, FORM_MEMBER}}, {{1, FORM_ONE}, {1, FORM_SLICE}, {1, FORM_MEMBER}},
+                          {{2, FORM_ONE}, {2, FORM_SLICE}, {2, FORM_MEMBER}}, {{3, FORM_ONE}, {3, FORM_SLICE}, {3, FORM_MEMBER}}};
+    // ranenv_set_head_policy_network / _head_value_network: SchedTWC / SchedColORAN's actor and critic on the head observation;
+    // ranenv_set_sac_critics.  One form each.
+    NetSlot head, head_value, sac_q1, sac_q2;
+    PopMap pop{};      // ranenv_set_population: the grouping (pop.n = 0: none)
     // The population roles' descriptor tables on the device: [5][POP_MAX] entries in the order actor, intra, critic, vintra, then a table
     // of zeros (n_layers 0: no net).  Allocated by the first population bind and never moved; every population bind writes its role's
     // table on the caller's stream, and a one-net slot that serves a role beside a mixed one gets G entries of its one net.
     PolicyNet *d_pop_tab = nullptr;
-    NetSlot *pop_slot(int role) { return role == 0 ? &pop_actor : (role == 1 ? &pop_intra : (role == 2 ? &pop_value : &pop_vintra)); }
-    const NetSlot *pop_slot(int role) const { return const_cast<ranenv *>(this)->pop_slot(role); }
-    const NetSlot *one_slot(int role) const { return role == 0 ? &actor : (role == 1 ? &actor_intra : (role == 2 ? &value : &value_intra)); }
-    bool pop_mixed() const { for (int r = 0; r < 4; r++) if (pop_slot(r)->on && pop_slot(r)->mixed) return true; return false; }
+    // THE PRECEDENCE RULE: the slot that serves role r now -- the population's nets if on, else the nets per slice if on, else the one
+    // net if on, else null (no net of that role acts)
+    NetSlot *serving(int r) { for (int f = FORM_MEMBER; f >= FORM_ONE; f--) if (nets[r][f].on) return &nets[r][f]; return nullptr; }
+    const NetSlot *serving(int r) const { return const_cast<ranenv *>(this)->serving(r); }
+    const PolicyNet *serving_net(int r) const { const NetSlot *s = serving(r); return s ? &s->net : nullptr; }
+    // ... and the slot role r's device table describes while a mixed role is bound: nets per slice have no entries there
+    const NetSlot *tabled(int r) const { return nets[r][FORM_MEMBER].on ? &nets[r][FORM_MEMBER] : (nets[r][FORM_ONE].on ? &nets[r][FORM_ONE] : nullptr); }
+    bool pop_bound() const { for (int r = 0; r < 4; r++) if (nets[r][FORM_MEMBER].on) return true; return false; }
+    bool pop_mixed() const { for (int r = 0; r < 4; r++) if (nets[r][FORM_MEMBER].on && nets[r][FORM_MEMBER].mixed) return true; return false; }
     // ranenv_ppo_bind / ranenv_ppo_update: bound?, the (member, kind) step counters [POP_MAX][2], the call's hyper-parameters on the
     // device [POP_MAX], the diagnostic log-probability buffer the NEXT update takes and forgets
     bool ppo_on = false; int32_t *d_ppo_t = nullptr; ranenv_ppo_hparams *d_ppo_hp = nullptr; float *ppo_probe = nullptr;
     // ranenv_set_population_gae: a (gamma, lambda) pair per member for ranenv_collect's GAE pass
     bool gae_on = false; double gae_gamma[POP_MAX] = {}, gae_lambda[POP_MAX] = {};
-    bool pop_bound() const { return pop_actor.on || pop_intra.on || pop_value.on || pop_vintra.on; }
-    void pop_unbind() { pop_actor.on = pop_intra.on = pop_value.on = pop_vintra.on = false; }
-    bool have_actor() const { return actor.on || pop_actor.on; }
-    bool have_critic() const { return value.on || pop_value.on; }
-    const PolicyNet *inter_actor() const { return pop_actor.on ? &pop_actor.net : &actor.net; }
-    const PolicyNet *inter_critic() const { return pop_value.on ? &pop_value.net : &value.net; }
-    const PolicyNet *intra_actor() const { return pop_intra.on ? &pop_intra.net : (actor_ps.on ? &actor_ps.net : (actor_intra.on ? &actor_intra.net : nullptr)); }
-    const PolicyNet *intra_critic() const { return pop_vintra.on ? &pop_vintra.net : (value_ps.on ? &value_ps.net : (value_intra.on ? &value_intra.net : nullptr)); }
     // The IBSched nets of a TTI's launches as they are bound (critics: a recording's), with the population map where a member's copy acts
     PolicyNets ibsched_nets(bool critics) const
     {
-        PolicyNets n{false, inter_actor(), intra_actor(), critics && have_critic() ? inter_critic() : nullptr, critics ? intra_critic() : nullptr};
+        PolicyNets n{false, serving_net(NET_INTER), serving_net(NET_INTRA), critics ? serving_net(NET_INTER_VALUE) : nullptr,
+                     critics ? serving_net(NET_INTRA_VALUE) : nullptr};
         if (pop_bound()) {
             n.pop = &pop;
-            n.stride[0] = pop_actor.on ? pop_actor.member_stride : 0; n.stride[1] = pop_intra.on ? pop_intra.member_stride : 0;
-            n.stride[2] = pop_value.on ? pop_value.member_stride : 0; n.stride[3] = pop_vintra.on ? pop_vintra.member_stride : 0;
             // a kind with a mixed-bound role (of the nets this launch may run) reads every net of it through the tables
-            auto mixed = [&](int r) { return pop_slot(r)->on && pop_slot(r)->mixed; };
-            const bool mx[2] = {mixed(0) || (critics && mixed(2)), mixed(1) || (critics && mixed(3))};
+            bool mx[2] = {false, false};
+            for (int r = 0; r < 4; r++) {
+                const NetSlot &p = nets[r][FORM_MEMBER];
+                n.stride[r] = p.on ? p.member_stride : 0;
+                if (p.on && p.mixed && (critics || r < NET_INTER_VALUE)) mx[r & 1] = true;
+            }
             n.tab_none = d_pop_tab + 4 * POP_MAX;
             for (int r = 0; r < 4; r++) {
                 if (!mx[r & 1]) continue;
                 n.tab[r] = d_pop_tab + r * POP_MAX;
-                n.lds[r] = pop_slot(r)->on ? pop_slot(r)->lds_max : (one_slot(r)->on ? policy_lds_bytes(one_slot(r)->net) : 0);
+                n.lds[r] = tabled(r) ? tabled(r)->lds_max : 0;
             }
         }
         return n;
@@ -1411,7 +1419,6 @@ int ranenv_set_policy(ranenv_handle h, int32_t policy, int32_t fixed_intra)
 
 // ---- policy networks (RANENV_POLICY_NETWORK) --------------------------------------------------------------------------------
 // Validate one ranenv_mlp against the handle's sizes and lay it out in the packed buffer from float `off` on (widths padded to 32).
-enum NetRole { NET_INTER, NET_INTRA, NET_INTER_VALUE, NET_INTRA_VALUE, NET_HEAD_CLIP, NET_HEAD_TANH, NET_HEAD_VALUE, NET_SAC_Q };
 static const struct { const char *who; bool intra; int out_s, out_1; } NET_ROLES[] = {      // intra: the input is a slice's row, else the (head)
     {"inter", false, 2, 0}, {"intra", true, 0, 3}, {"inter value", false, 0, 1}, {"intra value", true, 0, 1},      // observation [10*S];
     {"head", false, 1, 0}, {"head", false, 2, 0}, {"head value", false, 0, 1},                                     // output width out_s * S + out_1
@@ -1428,6 +1435,18 @@ static long long net_pack(const int32_t *dims, int L, int prec, PolicyNet &net, 
         net.b_off[l] = off; off += net.np[l];
     }
     return off;
+}
+
+// Floats of one packed copy of `net` (every copy is laid out from float 0 of its extent)
+static long long net_floats(const PolicyNet &net) { return net.b_off[net.n_layers - 1] + net.np[net.n_layers - 1]; }
+
+// Floats a slot's copy counts with: a mixed population's with the extent of every member, the largest member's
+static long long slot_copy_floats(const ranenv::NetSlot &slot) { return slot.mixed ? slot.member_stride : net_floats(slot.net); }
+
+// An IBSched role number as the ABI takes it
+static int role_check(ranenv_handle h, int32_t role)
+{
+    return role >= NET_INTER && role <= NET_INTRA_VALUE ? RANENV_OK : fail(h, RANENV_E_INVALID, "role %d (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)", role);
 }
 
 static int net_layout(ranenv_handle h, const ranenv_mlp *m, NetRole role, PolicyNet &net, long long &off)
@@ -1474,64 +1493,59 @@ static int net_copy(ranenv_handle h, const ranenv_mlp *m, const PolicyNet &net, 
 
 // Binding has two phases, and every ranenv_set_*_network call goes through them in one order: net_plan for all of its nets and its own
 // argument checks -- an error so far precedes every HIP call and leaves every slot as it was --, hipSetDevice, its own allocations,
-// net_commit for all of its nets.
-// PLAN: `copies` nets of one role (one, or one per slice) validated and laid out: net_layout's checks for every copy, and all copies of
-// one shape, activation, input layout and precision.  No HIP call, nothing of the handle changes.
+// net_commit for all of its nets, and last bind_flags: which forms of the IBSched roles are on now (BIND_RULES).
+// THE SHAPE RULE of a slot's copies: net `a` of unpadded widths `da` beside copy 0 (or the bound set's net 0) `b` -- equal in shape,
+// activation, input layout and precision; mixed (the members of a mixed population): in input layout and precision only
+static bool net_agrees(bool mixed, const PolicyNet &a, const int32_t *da, const PolicyNet &b, const int32_t *db)
+{
+    bool same = a.layout == b.layout && a.prec == b.prec;
+    if (mixed) return same;
+    same = same && a.n_layers == b.n_layers && a.act == b.act;
+    for (int l = 0; same && l <= a.n_layers; l++) same = da[l] == db[l];
+    return same;
+}
+
+// PLAN: `copies` nets of one role (one, one per slice, or one per member: the slot's form) validated and laid out: net_layout's checks
+// for every copy, each from float 0 of its extent, and the shape rule.  No HIP call, nothing of the handle changes.
 struct NetBind {
     ranenv::NetSlot *slot; const ranenv_mlp *const *nets; int copies; NetRole role;
-    bool members = false;                 // the copies are a population's, one per member (else one per slice)
-    PolicyNet net; long long floats;      // the plan: copy 0's layout with the copies' stride (one copy: 0), floats of all copies
-    long long stride;                     // ... floats between two copies
-    bool mixed = false;                   // (members) the copies may differ in hidden widths, depth and activation: member[i] is copy i's layout
-    std::vector<PolicyNet> member;        // ... at offsets of its own from float 0 of its extent; stride: the largest copy's packed size
+    bool mixed = false;                   // (a population's) the copies may differ in hidden widths, depth and activation
+    std::vector<PolicyNet> member;        // the plan: copy i's layout (per slice: with the copies' stride) ...
+    long long stride, floats;             // ... floats between two copies -- the largest copy's packed size --, floats of all copies
 };
 static int net_plan(ranenv_handle h, NetBind *binds, int n)
 {
     for (NetBind *b = binds; b < binds + n; b++) {
-        const char *who = NET_ROLES[b->role].who;
-        long long floats = 0;
-        if (b->mixed) {                   // every member on its own; the members agree in input layout and precision only
-            b->member.assign((size_t)b->copies, PolicyNet{});
-            for (int i = 0; i < b->copies; i++) {
-                const ranenv_mlp *m = b->nets[i], *m0 = b->nets[0];
-                if (!m) return fail(h, RANENV_E_INVALID, "%s nets per member: net %d is null", who, i);
-                long long mine = 0;
-                if (const int rc = net_layout(h, m, b->role, b->member[(size_t)i], mine); rc != RANENV_OK) return rc;
-                if (m->input_layout != m0->input_layout || m->precision != m0->precision)
-                    return fail(h, RANENV_E_INVALID, "%s nets per member (mixed): net %d differs from net 0 in input layout or precision", who, i);
-                floats = mine > floats ? mine : floats;
-            }
-            b->net = b->member[0];
-            b->stride = floats; b->floats = floats * b->copies;
-            continue;
-        }
+        const char *who = NET_ROLES[b->role].who, *per = b->slot->form == FORM_MEMBER ? "member" : "slice";
+        b->member.assign((size_t)b->copies, PolicyNet{});
+        b->stride = 0;
         for (int i = 0; i < b->copies; i++) {
-            const ranenv_mlp *m = b->nets[i], *m0 = b->nets[0];
-            const char *per = b->members ? "member" : "slice";
+            const ranenv_mlp *m = b->nets[i];
             if (!m) return fail(h, RANENV_E_INVALID, "%s nets per %s: net %d is null", who, per, i);
-            PolicyNet ni{};
-            floats = 0;
-            if (const int rc = net_layout(h, m, b->role, ni, floats); rc != RANENV_OK) return rc;
-            bool same = m->n_hidden == m0->n_hidden && m->activation == m0->activation && m->input_layout == m0->input_layout && m->precision == m0->precision;
-            for (int l = 0; same && l <= m->n_hidden + 1; l++) same = m->dims[l] == m0->dims[l];
-            if (!same) return fail(h, RANENV_E_INVALID, "%s nets per %s: net %d differs from net 0 in shape, activation, input layout or precision", who, per, i);
-            if (i == 0) b->net = ni;
+            long long mine = 0;
+            if (const int rc = net_layout(h, m, b->role, b->member[(size_t)i], mine); rc != RANENV_OK) return rc;
+            if (!net_agrees(b->mixed, b->member[(size_t)i], m->dims, b->member[0], b->nets[0]->dims))
+                return b->mixed ? fail(h, RANENV_E_INVALID, "%s nets per member (mixed): net %d differs from net 0 in input layout or precision", who, i)
+                                : fail(h, RANENV_E_INVALID, "%s nets per %s: net %d differs from net 0 in shape, activation, input layout or precision", who, per, i);
+            b->stride = mine > b->stride ? mine : b->stride;
         }
-        b->stride = floats;
-        b->net.slice_stride = b->copies > 1 && !b->members ? floats : 0;
-        b->floats = floats * b->copies;
+        if (b->slot->form == FORM_SLICE && b->copies > 1) b->member[0].slice_stride = b->stride;      // (the entry the slot keeps)
+        b->floats = b->stride * b->copies;
     }
     return RANENV_OK;
 }
 
-static int pop_role_of(ranenv_handle h, const ranenv::NetSlot *slot)
-{
-    for (int r = 0; r < 4; r++) if (h->pop_slot(r) == slot) return r;
-    return 0;
-}
-
 // The roles' descriptor tables, allocated (zeroed) once
 static int pop_tables(ranenv_handle h) { return h->d_pop_tab ? RANENV_OK : dev_alloc(h, &h->d_pop_tab, (size_t)5 * POP_MAX); }
+
+// ranenv_set_population_policy / _value: up to two roles' member copies (the intra array may be null) planned; the count against the grouping
+static int pop_plan(ranenv_handle h, int32_t n, NetBind *b, int n_binds, bool mixed)
+{
+    if (h->pop.n == 0) return fail(h, RANENV_E_STATE, "no population set (ranenv_set_population)");
+    if (n != h->pop.n) return fail(h, RANENV_E_INVALID, "%d nets given, the population has %d members", n, h->pop.n);
+    for (int i = 0; i < n_binds; i++) b[i].mixed = mixed;
+    return net_plan(h, b, n_binds);
+}
 
 // While a mixed role is bound, the mixed kernels read every net of its kind through a table: a role that one net serves for all members
 // gets G entries of that net.  On the caller's stream, behind every call that binds a mixed role or a one net beside one.
@@ -1539,7 +1553,7 @@ static int pop_tables_one_net(ranenv_handle h, hipStream_t s)
 {
     if (!h->pop_mixed()) return RANENV_OK;
     for (int r = 0; r < 4; r++)
-        if (!h->pop_slot(r)->on && h->one_slot(r)->on) launch_net_table(s, h->d_pop_tab + r * POP_MAX, 0, h->pop.n, h->one_slot(r)->net, 0);
+        if (const ranenv::NetSlot *t = h->tabled(r); t && t->form == FORM_ONE) launch_net_table(s, h->d_pop_tab + r * POP_MAX, 0, h->pop.n, t->net, 0);
     HIP_TRY(h, hipGetLastError());
     return RANENV_OK;
 }
@@ -1558,31 +1572,25 @@ static int net_commit(ranenv_handle h, NetBind *binds, int n, hipStream_t s)
         } else {
             HIP_TRY(h, hipMemsetAsync(slot.w, 0, sizeof(float) * (size_t)b->floats, s));
         }
-        b->net.w = slot.w;
+        for (int i = 0; i < b->copies; i++) b->member[(size_t)i].w = slot.w + (size_t)i * (size_t)b->stride;
     }
     for (NetBind *b = binds; b < binds + n; b++)
         for (int i = 0; i < b->copies; i++)
-            if (const int rc = net_copy(h, b->nets[i], b->mixed ? b->member[(size_t)i] : b->net, s, b->slot->w + (size_t)i * (size_t)b->stride); rc != RANENV_OK) return rc;
+            if (const int rc = net_copy(h, b->nets[i], b->member[(size_t)i], s, b->slot->w + (size_t)i * (size_t)b->stride); rc != RANENV_OK) return rc;
     for (NetBind *b = binds; b < binds + n; b++) {      // a population's role: its table -- entry i = copy i's layout at copy i's address
-        if (!b->members) continue;
-        if (!b->mixed) b->member.assign((size_t)b->copies, b->net);
-        for (int i = 0; i < b->copies; i++) b->member[(size_t)i].w = b->slot->w + (size_t)i * (size_t)b->stride;
-        PolicyNet *tab = h->d_pop_tab + pop_role_of(h, b->slot) * POP_MAX;
+        if (b->slot->form != FORM_MEMBER) continue;
+        PolicyNet *tab = h->d_pop_tab + b->slot->role * POP_MAX;
         if (!b->mixed) launch_net_table(s, tab, 0, b->copies, b->member[0], b->stride);
         else for (int i = 0; i < b->copies; i++) launch_net_table(s, tab, i, 1, b->member[(size_t)i], 0);
         HIP_TRY(h, hipGetLastError());
     }
-    for (NetBind *b = binds; b < binds + n; b++) {
+    for (NetBind *b = binds; b < binds + n; b++) {      // (nets per slice keep slice 0's entry: its stride stands for the others)
         ranenv::NetSlot &slot = *b->slot;
-        slot.net = b->net; slot.on = true; slot.member_stride = b->members ? b->stride : 0;
-        for (int l = 0; l < 6; l++) slot.dims[l] = b->nets[0]->dims[l];
-        slot.mixed = b->mixed; slot.lds_max = 0;
-        slot.member = b->member; slot.member_dims.assign(slot.member.size(), {});
-        for (size_t i = 0; i < slot.member.size(); i++) {
-            for (int l = 0; l < 6; l++) slot.member_dims[i][(size_t)l] = b->nets[i]->dims[l];
-            const size_t lds = policy_lds_bytes(slot.member[i]);
-            slot.lds_max = lds > slot.lds_max ? lds : slot.lds_max;
-        }
+        const size_t kept = slot.form == FORM_MEMBER ? (size_t)b->copies : 1;
+        slot.on = true; slot.mixed = b->mixed; slot.member_stride = slot.form == FORM_MEMBER ? b->stride : 0;
+        slot.member.assign(b->member.begin(), b->member.begin() + (long)kept); slot.member_dims.assign(kept, {});
+        for (size_t i = 0; i < kept; i++) std::copy_n(b->nets[i]->dims, 6, slot.member_dims[i].begin());
+        slot.derive();
     }
     for (NetBind *b = binds; b < binds + n; b++)
         if (const int rc = ppo_rebound(h, b->slot, -1, s); rc != RANENV_OK) return rc;
@@ -1603,11 +1611,11 @@ static int net_use(ranenv_handle h, KP &kp)
         return 1;
     }
     if (kp.scores || h->kp.policy != RANENV_POLICY_NETWORK) return 0;
-    if (!h->have_actor()) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!h->serving(NET_INTER)) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
     if (!kp.obs_inter) return fail(h, RANENV_E_INVALID, "the policy network reads obs_inter: the step needs that buffer");
-    if (h->intra_actor() && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
+    if (h->serving_net(NET_INTRA) && !kp.obs_intra) return fail(h, RANENV_E_INVALID, "the intra-slice network reads obs_intra: the step needs that buffer");
     kp.scores = h->d_net_scores;
-    if (h->intra_actor()) { kp.intra = h->d_net_intra; kp.fixed_intra = RANENV_INTRA_PER_SLICE; }
+    if (h->serving_net(NET_INTRA)) { kp.intra = h->d_net_intra; kp.fixed_intra = RANENV_INTRA_PER_SLICE; }
     return 1;
 }
 
@@ -1654,82 +1662,131 @@ static int net_action_buffers(ranenv_handle h)
     return rc == RANENV_OK ? dev_alloc(h, &h->d_net_intra, BS) : rc;
 }
 
-int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed, void *stream)
+// THE EXCLUSIVITY RULES: what each binding call leaves on and off among the role table's slots, as sets of (role, form).  `on`: the
+// form the call binds; `on_if_intra`: on where the call's optional intra argument is given, off where it is NULL -- the argument, NULL
+// included, says what the intra net of that kind is now; `off`: forms that would stand in front of what the call binds, or whose
+// partner it replaces.  Deliberately asymmetric: a plain policy bind ends the population altogether (its critics too; the grouping
+// stays), while a population's policy bind leaves one-net critics standing -- one critic may value every member's envs.
+enum BindCall { BIND_POLICY, BIND_VALUE, BIND_INTRA_POLICY, UNBIND_INTRA_POLICY, BIND_INTRA_VALUE, UNBIND_INTRA_VALUE, BIND_POP_POLICY, BIND_POP_VALUE, UNBIND_POP };
+constexpr unsigned slot_bit(int role, NetForm form) { return 1u << (role * 3 + form); }
+constexpr unsigned ONE(int role) { return slot_bit(role, FORM_ONE); }
+constexpr unsigned SLICE(int role) { return slot_bit(role, FORM_SLICE); }
+constexpr unsigned POP(int role) { return slot_bit(role, FORM_MEMBER); }
+static const struct { unsigned on, on_if_intra, off; } BIND_RULES[] = {
+    /* BIND_POLICY         */ {ONE(0), ONE(1), SLICE(1) | SLICE(3) | POP(0) | POP(1) | POP(2) | POP(3)},
+    /* BIND_VALUE          */ {ONE(2), ONE(3), SLICE(3) | POP(2) | POP(3)},
+    /* BIND_INTRA_POLICY   */ {SLICE(1), 0, 0},                       // (refused while any population slot is on)
+    /* UNBIND_INTRA_POLICY */ {0, 0, SLICE(1) | SLICE(3)},            // (the critics per slice valued the actors per slice)
+    /* BIND_INTRA_VALUE    */ {SLICE(3), 0, 0},
+    /* UNBIND_INTRA_VALUE  */ {0, 0, SLICE(3)},
+    /* BIND_POP_POLICY     */ {POP(0), POP(1), ONE(0) | ONE(1) | SLICE(1) | SLICE(3)},
+    /* BIND_POP_VALUE      */ {POP(2), POP(3), ONE(2) | ONE(3) | SLICE(3)},
+    /* UNBIND_POP          */ {0, 0, POP(0) | POP(1) | POP(2) | POP(3)},
+};
+// The last step of a binding call, behind its net_commit: the slots' flags by the call's rule
+static void bind_flags(ranenv_handle h, BindCall call, bool intra = false)
 {
-    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice net is required (intra may be NULL)");
-    NetBind b[2] = {{&h->actor, &inter, 1, NET_INTER}, {&h->actor_intra, &intra, 1, NET_INTRA}};
-    const int n = intra ? 2 : 1;
-    int rc = net_plan(h, b, n);
-    if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((rc = net_action_buffers(h)) != RANENV_OK) return rc;
-    if ((rc = net_commit(h, b, n, (hipStream_t)stream)) != RANENV_OK) return rc;
-    h->net_stochastic = stochastic != 0; h->net_seed = seed;
-    h->actor_intra.on = intra != nullptr;         // (`intra`, NULL included, says what the intra policy is now)
-    h->actor_ps.on = h->value_ps.on = false;
-    h->pop_unbind();                              // (... and that no population acts or values: the grouping stays)
-    return RANENV_OK;
+    const auto &rule = BIND_RULES[call];
+    for (int r = 0; r < 4; r++)
+        for (ranenv::NetSlot &slot : h->nets[r]) {
+            const unsigned bit = slot_bit(r, slot.form);
+            slot.on = (rule.on & bit) ? true : ((rule.on_if_intra & bit) ? intra : ((rule.off & bit) ? false : slot.on));
+        }
 }
 
-// ranenv_set_intra_policy_networks / _intra_value_networks: n = S nets of one shape at equal stride in `slot`'s buffer
-static int net_set_copies(ranenv_handle h, ranenv::NetSlot &slot, int32_t n, const ranenv_mlp *const *nets, NetRole role, hipStream_t s)
+// ranenv_set_policy_network (form FORM_ONE: n = 1) / ranenv_set_population_policy[_mixed] (FORM_MEMBER: n = G): the actors in that form
+static int set_actors(ranenv_handle h, NetForm form, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
+                      uint64_t seed, void *stream, bool mixed = false)
+{
+    const bool pop = form == FORM_MEMBER;
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!inter) return fail(h, RANENV_E_INVALID, pop ? "the members' inter-slice nets are required (intra may be NULL)" : "the inter-slice net is required (intra may be NULL)");
+    NetBind b[2] = {{&h->nets[NET_INTER][form], inter, n, NET_INTER}, {&h->nets[NET_INTRA][form], intra, n, NET_INTRA}};
+    const int nb = intra ? 2 : 1;
+    int rc = pop ? pop_plan(h, n, b, nb, mixed) : net_plan(h, b, nb);
+    if (rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((rc = net_action_buffers(h)) != RANENV_OK || (pop && (rc = pop_tables(h)) != RANENV_OK)) return rc;
+    if ((rc = net_commit(h, b, nb, (hipStream_t)stream)) != RANENV_OK) return rc;
+    h->net_stochastic = stochastic != 0; h->net_seed = seed;
+    bind_flags(h, pop ? BIND_POP_POLICY : BIND_POLICY, intra != nullptr);
+    return pop_tables_one_net(h, (hipStream_t)stream);      // (none behind BIND_POLICY: it ends every population role)
+}
+
+int ranenv_set_policy_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, int32_t stochastic, uint64_t seed, void *stream)
+{
+    return set_actors(h, FORM_ONE, 1, inter ? &inter : nullptr, intra ? &intra : nullptr, stochastic, seed, stream);
+}
+
+// ranenv_set_intra_policy_networks / _intra_value_networks: n = S nets of one shape at equal stride in the role's per-slice slot
+static int net_set_copies(ranenv_handle h, BindCall call, int32_t n, const ranenv_mlp *const *nets, NetRole role, hipStream_t s)
 {
     const char *who = NET_ROLES[role].who;
     if (n != h->cfg.n_slices) return fail(h, RANENV_E_INVALID, "%s nets per slice: %d given, the handle has %d slices", who, n, h->cfg.n_slices);
     if (!nets) return fail(h, RANENV_E_INVALID, "%s nets per slice: null array", who);
-    NetBind b{&slot, nets, n, role};
+    NetBind b{&h->nets[role][FORM_SLICE], nets, n, role};
     if (const int rc = net_plan(h, &b, 1); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    return net_commit(h, &b, 1, s);
+    if (const int rc = net_commit(h, &b, 1, s); rc != RANENV_OK) return rc;
+    bind_flags(h, call);
+    return RANENV_OK;
 }
 
 int ranenv_set_intra_policy_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *actors, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (n == 0 && !actors) { h->actor_ps.on = h->value_ps.on = false; return RANENV_OK; }
+    if (n == 0 && !actors) { bind_flags(h, UNBIND_INTRA_POLICY); return RANENV_OK; }
     if (h->pop_bound()) return fail(h, RANENV_E_STATE, "intra policy nets per slice while a population's nets are bound (ranenv_set_policy_network first)");
-    if (!h->actor.on) return fail(h, RANENV_E_STATE, "intra policy nets per slice need a bound inter net (ranenv_set_policy_network)");
-    return net_set_copies(h, h->actor_ps, n, actors, NET_INTRA, (hipStream_t)stream);
+    if (!h->nets[NET_INTER][FORM_ONE].on) return fail(h, RANENV_E_STATE, "intra policy nets per slice need a bound inter net (ranenv_set_policy_network)");
+    return net_set_copies(h, BIND_INTRA_POLICY, n, actors, NET_INTRA, (hipStream_t)stream);
 }
 
 int ranenv_set_intra_value_networks(ranenv_handle h, int32_t n, const ranenv_mlp *const *critics, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (n == 0 && !critics) { h->value_ps.on = false; return RANENV_OK; }
+    if (n == 0 && !critics) { bind_flags(h, UNBIND_INTRA_VALUE); return RANENV_OK; }
     if (h->pop_bound()) return fail(h, RANENV_E_STATE, "intra value nets per slice while a population's nets are bound (ranenv_set_policy_network first)");
-    const PolicyNet *ia = h->intra_actor();
+    const PolicyNet *ia = h->serving_net(NET_INTRA);
     if (!ia) return fail(h, RANENV_E_INVALID, "intra value nets need a bound intra policy net (ranenv_set_policy_network / ranenv_set_intra_policy_networks)");
     if (n == h->cfg.n_slices && critics && critics[0] && critics[0]->input_layout != ia->layout)
         return fail(h, RANENV_E_INVALID, "intra value nets: input layout %d, the intra policy net has %d", critics[0]->input_layout, ia->layout);
-    return net_set_copies(h, h->value_ps, n, critics, NET_INTRA_VALUE, (hipStream_t)stream);
+    return net_set_copies(h, BIND_INTRA_VALUE, n, critics, NET_INTRA_VALUE, (hipStream_t)stream);
 }
 
 int ranenv_get_policy_actions(ranenv_handle h, double **dev_scores, uint8_t **dev_intra)
 {
     if (!h || !dev_scores || !dev_intra) return fail(h, RANENV_E_INVALID, "null argument");
-    if (!h->have_actor() && !h->head.on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
-    *dev_scores = h->d_net_scores; *dev_intra = (h->have_actor() && h->intra_actor()) ? h->d_net_intra : nullptr;
+    if (!h->serving(NET_INTER) && !h->head.on) return fail(h, RANENV_E_STATE, "no policy network bound (ranenv_set_policy_network)");
+    *dev_scores = h->d_net_scores; *dev_intra = (h->serving(NET_INTER) && h->serving_net(NET_INTRA)) ? h->d_net_intra : nullptr;
     return RANENV_OK;
+}
+
+// ranenv_set_value_network (form FORM_ONE: n = 1) / ranenv_set_population_value[_mixed] (FORM_MEMBER: n = G): the critics in that form
+static int set_critics(ranenv_handle h, NetForm form, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream, bool mixed = false)
+{
+    const bool pop = form == FORM_MEMBER;
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (!inter) return fail(h, RANENV_E_INVALID, pop ? "the members' inter-slice value nets are required (intra may be NULL)" : "the inter-slice value net is required (intra may be NULL)");
+    const PolicyNet *ia = h->serving_net(NET_INTRA);
+    if (intra && !(h->serving(NET_INTER) && ia))
+        return fail(h, RANENV_E_INVALID, pop ? "intra value nets need a bound intra policy net" : "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
+    // (a population's array is read only where it has the grouping's count of entries: the plan refuses every other)
+    if (intra && (!pop || (h->pop.n > 0 && n == h->pop.n)) && intra[0] && intra[0]->input_layout != ia->layout)
+        return fail(h, RANENV_E_INVALID, pop ? "intra value nets: input layout %d, the intra policy net has %d" : "intra value net: input layout %d, the intra policy net has %d",
+                    intra[0]->input_layout, ia->layout);
+    NetBind b[2] = {{&h->nets[NET_INTER_VALUE][form], inter, n, NET_INTER_VALUE}, {&h->nets[NET_INTRA_VALUE][form], intra, n, NET_INTRA_VALUE}};
+    const int nb = intra ? 2 : 1;
+    if (const int rc = pop ? pop_plan(h, n, b, nb, mixed) : net_plan(h, b, nb); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (const int rc = pop ? pop_tables(h) : RANENV_OK; rc != RANENV_OK) return rc;
+    if (const int rc = net_commit(h, b, nb, (hipStream_t)stream); rc != RANENV_OK) return rc;
+    bind_flags(h, pop ? BIND_POP_VALUE : BIND_VALUE, intra != nullptr);
+    return pop_tables_one_net(h, (hipStream_t)stream);
 }
 
 int ranenv_set_value_network(ranenv_handle h, const ranenv_mlp *inter, const ranenv_mlp *intra, void *stream)
 {
-    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (!inter) return fail(h, RANENV_E_INVALID, "the inter-slice value net is required (intra may be NULL)");
-    const PolicyNet *ia = h->intra_actor();
-    if (intra && !(h->have_actor() && ia)) return fail(h, RANENV_E_INVALID, "an intra value net needs a bound intra policy net (ranenv_set_policy_network)");
-    if (intra && intra->input_layout != ia->layout)
-        return fail(h, RANENV_E_INVALID, "intra value net: input layout %d, the intra policy net has %d", intra->input_layout, ia->layout);
-    NetBind b[2] = {{&h->value, &inter, 1, NET_INTER_VALUE}, {&h->value_intra, &intra, 1, NET_INTRA_VALUE}};
-    const int n = intra ? 2 : 1;
-    if (const int rc = net_plan(h, b, n); rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (const int rc = net_commit(h, b, n, (hipStream_t)stream); rc != RANENV_OK) return rc;
-    h->value_intra.on = intra != nullptr;         // (`intra`, NULL included, says what the intra critic is now)
-    h->value_ps.on = false;
-    h->pop_value.on = h->pop_vintra.on = false;   // (... and that the critics are no population's)
-    return pop_tables_one_net(h, (hipStream_t)stream);
+    return set_critics(h, FORM_ONE, 1, inter ? &inter : nullptr, intra ? &intra : nullptr, stream);
 }
 
 // ---- populations: one net set per env group ------------------------------------------------------------------------------------
@@ -1748,7 +1805,7 @@ static int pop_check(ranenv_handle h, int32_t n, const int32_t *first, int batch
 int ranenv_set_population(ranenv_handle h, int32_t n_members, const int32_t *host_first_env)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (n_members == 0 && !host_first_env) { h->pop = PopMap{}; h->pop_unbind(); h->gae_on = false; return RANENV_OK; }
+    if (n_members == 0 && !host_first_env) { h->pop = PopMap{}; bind_flags(h, UNBIND_POP); h->gae_on = false; return RANENV_OK; }
     if (const int rc = pop_check(h, n_members, host_first_env, h->cfg.batch); rc != RANENV_OK) return rc;
     PopMap map{};
     map.n = n_members;
@@ -1790,72 +1847,26 @@ int ranenv_population_tiles(int32_t n_members, const int32_t *first_env, int32_t
     return RANENV_OK;
 }
 
-// ranenv_set_population_policy / _value: up to two roles' member copies (the intra array may be null) planned; the count against the grouping
-static int pop_plan(ranenv_handle h, int32_t n, NetBind *b, int n_binds, bool mixed = false)
-{
-    if (h->pop.n == 0) return fail(h, RANENV_E_STATE, "no population set (ranenv_set_population)");
-    if (n != h->pop.n) return fail(h, RANENV_E_INVALID, "%d nets given, the population has %d members", n, h->pop.n);
-    for (int i = 0; i < n_binds; i++) { b[i].members = true; b[i].mixed = mixed; }
-    return net_plan(h, b, n_binds);
-}
-
-static int pop_set_policy(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
-                          uint64_t seed, void *stream, bool mixed)
-{
-    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (!inter) return fail(h, RANENV_E_INVALID, "the members' inter-slice nets are required (intra may be NULL)");
-    NetBind b[2] = {{&h->pop_actor, inter, n, NET_INTER}, {&h->pop_intra, intra, n, NET_INTRA}};
-    const int nb = intra ? 2 : 1;
-    int rc = pop_plan(h, n, b, nb, mixed);
-    if (rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((rc = net_action_buffers(h)) != RANENV_OK || (rc = pop_tables(h)) != RANENV_OK) return rc;
-    if ((rc = net_commit(h, b, nb, (hipStream_t)stream)) != RANENV_OK) return rc;
-    h->net_stochastic = stochastic != 0; h->net_seed = seed;
-    h->pop_intra.on = intra != nullptr;           // (`intra`, NULL included, says what the intra policy is now)
-    h->actor.on = h->actor_intra.on = h->actor_ps.on = h->value_ps.on = false;
-    return pop_tables_one_net(h, (hipStream_t)stream);
-}
-
 int ranenv_set_population_policy(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
                                  uint64_t seed, void *stream)
 {
-    return pop_set_policy(h, n, inter, intra, stochastic, seed, stream, false);
+    return set_actors(h, FORM_MEMBER, n, inter, intra, stochastic, seed, stream, false);
 }
 
 int ranenv_set_population_policy_mixed(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, int32_t stochastic,
                                        uint64_t seed, void *stream)
 {
-    return pop_set_policy(h, n, inter, intra, stochastic, seed, stream, true);
-}
-
-static int pop_set_value(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream, bool mixed)
-{
-    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (!inter) return fail(h, RANENV_E_INVALID, "the members' inter-slice value nets are required (intra may be NULL)");
-    const PolicyNet *ia = h->intra_actor();
-    if (intra && !(h->have_actor() && ia)) return fail(h, RANENV_E_INVALID, "intra value nets need a bound intra policy net");
-    if (intra && h->pop.n > 0 && n == h->pop.n && intra[0] && intra[0]->input_layout != ia->layout)
-        return fail(h, RANENV_E_INVALID, "intra value nets: input layout %d, the intra policy net has %d", intra[0]->input_layout, ia->layout);
-    NetBind b[2] = {{&h->pop_value, inter, n, NET_INTER_VALUE}, {&h->pop_vintra, intra, n, NET_INTRA_VALUE}};
-    const int nb = intra ? 2 : 1;
-    if (const int rc = pop_plan(h, n, b, nb, mixed); rc != RANENV_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (const int rc = pop_tables(h); rc != RANENV_OK) return rc;
-    if (const int rc = net_commit(h, b, nb, (hipStream_t)stream); rc != RANENV_OK) return rc;
-    h->pop_vintra.on = intra != nullptr;          // (`intra`, NULL included, says what the intra critic is now)
-    h->value.on = h->value_intra.on = h->value_ps.on = false;
-    return pop_tables_one_net(h, (hipStream_t)stream);
+    return set_actors(h, FORM_MEMBER, n, inter, intra, stochastic, seed, stream, true);
 }
 
 int ranenv_set_population_value(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream)
 {
-    return pop_set_value(h, n, inter, intra, stream, false);
+    return set_critics(h, FORM_MEMBER, n, inter, intra, stream, false);
 }
 
 int ranenv_set_population_value_mixed(ranenv_handle h, int32_t n, const ranenv_mlp *const *inter, const ranenv_mlp *const *intra, void *stream)
 {
-    return pop_set_value(h, n, inter, intra, stream, true);
+    return set_critics(h, FORM_MEMBER, n, inter, intra, stream, true);
 }
 
 int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_mlp *inter, const ranenv_mlp *intra, const ranenv_mlp *v_inter,
@@ -1863,50 +1874,43 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (member < 0 || member >= h->pop.n) return fail(h, RANENV_E_INVALID, "member %d outside the population's %d", member, h->pop.n);
-    struct { ranenv::NetSlot *slot; const ranenv_mlp *m; NetRole role; PolicyNet ni; } roles[4] = {
-        {&h->pop_actor, inter, NET_INTER, {}}, {&h->pop_intra, intra, NET_INTRA, {}}, {&h->pop_value, v_inter, NET_INTER_VALUE, {}}, {&h->pop_vintra, v_intra, NET_INTRA_VALUE, {}}};
-    for (auto &r : roles) {                 // every check of every role in front of the first device call
-        if (!r.m) continue;
-        const char *who = NET_ROLES[r.role].who;
-        if (!r.slot->on) return fail(h, RANENV_E_STATE, "%s net of member %d: the population has no %s nets bound", who, member, who);
-        PolicyNet &ni = r.ni;
+    const ranenv_mlp *given[4] = {inter, intra, v_inter, v_intra};      // by role number
+    PolicyNet ni[4];
+    for (int r = 0; r < 4; r++) {           // every check of every role in front of the first device call
+        const ranenv_mlp *m = given[r];
+        if (!m) continue;
+        const ranenv::NetSlot &slot = h->nets[r][FORM_MEMBER];
+        const char *who = NET_ROLES[r].who;
+        if (!slot.on) return fail(h, RANENV_E_STATE, "%s net of member %d: the population has no %s nets bound", who, member, who);
         long long floats = 0;
-        if (const int rc = net_layout(h, r.m, r.role, ni, floats); rc != RANENV_OK) return rc;
-        const PolicyNet &n0 = r.slot->net;
-        if (r.slot->mixed) {                // any valid shape of the role's layout and precision that fits the member's extent
-            if (ni.layout != n0.layout || ni.prec != n0.prec)
-                return fail(h, RANENV_E_INVALID, "%s net of member %d differs from the bound set in input layout or precision", who, member);
-            if (floats > r.slot->member_stride)
-                return fail(h, RANENV_E_INVALID, "%s net of member %d: its packed copy has %lld floats, the member's extent %lld (the largest member's of the bind)",
-                            who, member, floats, r.slot->member_stride);
-            continue;
-        }
-        bool same = ni.n_layers == n0.n_layers && ni.act == n0.act && ni.layout == n0.layout && ni.prec == n0.prec;
-        for (int l = 0; same && l <= ni.n_layers; l++) same = r.m->dims[l] == r.slot->dims[l];
-        if (!same) return fail(h, RANENV_E_INVALID, "%s net of member %d differs from the bound set in shape, activation, input layout or precision", who, member);
+        if (const int rc = net_layout(h, m, (NetRole)r, ni[r], floats); rc != RANENV_OK) return rc;
+        if (!net_agrees(slot.mixed, ni[r], m->dims, slot.member[0], slot.member_dims[0].data()))
+            return fail(h, RANENV_E_INVALID, "%s net of member %d differs from the bound set in %sinput layout or precision", who, member, slot.mixed ? "" : "shape, activation, ");
+        if (slot.mixed && floats > slot.member_stride)      // ... and any such shape fits the member's extent
+            return fail(h, RANENV_E_INVALID, "%s net of member %d: its packed copy has %lld floats, the member's extent %lld (the largest member's of the bind)",
+                        who, member, floats, slot.member_stride);
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    for (auto &r : roles) {
-        if (!r.m) continue;
-        ranenv::NetSlot &slot = *r.slot;
+    for (int r = 0; r < 4; r++) {
+        const ranenv_mlp *m = given[r];
+        if (!m) continue;
+        ranenv::NetSlot &slot = h->nets[r][FORM_MEMBER];
         float *dst = slot.w + (size_t)member * (size_t)slot.member_stride;
         if (!slot.mixed) {
-            if (const int rc = net_copy(h, r.m, slot.net, s, dst); rc != RANENV_OK) return rc;
+            if (const int rc = net_copy(h, m, slot.net, s, dst); rc != RANENV_OK) return rc;
             if (const int rc = ppo_rebound(h, &slot, member, s); rc != RANENV_OK) return rc;
             continue;
         }
         // a mixed role: the extent zeroed, the layers at the new shape's offsets, then the member's table entry -- in that order
         HIP_TRY(h, hipMemsetAsync(dst, 0, sizeof(float) * (size_t)slot.member_stride, s));
-        r.ni.w = dst;
-        if (const int rc = net_copy(h, r.m, r.ni, s, dst); rc != RANENV_OK) return rc;
-        launch_net_table(s, h->d_pop_tab + pop_role_of(h, r.slot) * POP_MAX, member, 1, r.ni, 0);
+        ni[r].w = dst;
+        if (const int rc = net_copy(h, m, ni[r], s, dst); rc != RANENV_OK) return rc;
+        launch_net_table(s, h->d_pop_tab + r * POP_MAX, member, 1, ni[r], 0);
         HIP_TRY(h, hipGetLastError());
-        slot.member[(size_t)member] = r.ni;
-        for (int l = 0; l < 6; l++) slot.member_dims[(size_t)member][(size_t)l] = r.m->dims[l];
-        if (member == 0) { const float *w = slot.net.w; slot.net = r.ni; slot.net.w = w; for (int l = 0; l < 6; l++) slot.dims[l] = r.m->dims[l]; }
-        slot.lds_max = 0;
-        for (const PolicyNet &x : slot.member) { const size_t lds = policy_lds_bytes(x); slot.lds_max = lds > slot.lds_max ? lds : slot.lds_max; }
+        slot.member[(size_t)member] = ni[r];
+        for (int l = 0; l < 6; l++) slot.member_dims[(size_t)member][(size_t)l] = m->dims[l];
+        slot.derive();
     }
     return RANENV_OK;
 }
@@ -1915,16 +1919,16 @@ int ranenv_get_population_net(ranenv_handle h, int32_t role, int32_t member, int
                               int64_t *used_floats)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (role < 0 || role > 3) return fail(h, RANENV_E_INVALID, "role %d (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)", role);
+    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
     if (member < 0 || member >= h->pop.n) return fail(h, RANENV_E_INVALID, "member %d outside the population's %d", member, h->pop.n);
-    const ranenv::NetSlot &slot = *h->pop_slot(role);
+    const ranenv::NetSlot &slot = h->nets[role][FORM_MEMBER];      // (on: it serves the role)
     if (!slot.on) return fail(h, RANENV_E_STATE, "the population has no net of role %d bound", role);
     const PolicyNet &net = slot.member[(size_t)member];
     if (n_hidden) *n_hidden = net.n_layers - 1;
     if (dims) for (int l = 0; l < 6; l++) dims[l] = l <= net.n_layers ? slot.member_dims[(size_t)member][(size_t)l] : 0;
     if (activation) *activation = net.act;
     if (extent_floats) *extent_floats = slot.member_stride;
-    if (used_floats) *used_floats = net.b_off[net.n_layers - 1] + net.np[net.n_layers - 1] - net.w_off[0];
+    if (used_floats) *used_floats = net_floats(net);
     return RANENV_OK;
 }
 
@@ -1963,22 +1967,18 @@ int ranenv_set_population_gae(ranenv_handle h, int32_t n, const double *host_gam
 // ---- PPO update (include/ranenv.h "PPO update"; the kernel: ranenv_ppo.hip) -----------------------------------------------------
 static_assert(sizeof(ranenv_ppo_hparams) == RANENV_PPO_HPARAMS_BYTES, "ranenv_ppo_hparams: 8 doubles and 4 int32");
 
-// Floats of one packed copy of `net`
-static long long net_floats(const PolicyNet &net) { return net.b_off[net.n_layers - 1] + net.np[net.n_layers - 1]; }
-
-// The slots the update trains, in the order inter actor, intra actor, inter critic, intra critic (null: none bound), and the member
-// count -- or what ranenv_ppo_bind refuses.  No device call.
+// The slots the update trains, by role number: the serving ones (null: none bound), and the member count -- or what ranenv_ppo_bind
+// refuses.  No device call.
 static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
 {
     if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
-    if (h->actor_ps.on || h->value_ps.on) return fail(h, RANENV_E_STATE, "the PPO update does not train intra nets per slice (non-shared intra policies)");
-    if (h->pop_mixed()) return fail(h, RANENV_E_STATE, "the PPO update does not train a mixed population");
-    ranenv::NetSlot *one[4] = {&h->actor, &h->actor_intra, &h->value, &h->value_intra};
     int n_pop = 0, n_one = 0;
     for (int r = 0; r < 4; r++) {
-        slot[r] = h->pop_slot(r)->on ? h->pop_slot(r) : (one[r]->on ? one[r] : nullptr);
-        if (slot[r]) (h->pop_slot(r)->on ? n_pop : n_one) += 1;
+        slot[r] = h->serving(r);
+        if (slot[r] && slot[r]->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the PPO update does not train intra nets per slice (non-shared intra policies)");
+        if (slot[r]) (slot[r]->form == FORM_MEMBER ? n_pop : n_one) += 1;
     }
+    if (h->pop_mixed()) return fail(h, RANENV_E_STATE, "the PPO update does not train a mixed population");
     if (!slot[0] || !slot[2]) return fail(h, RANENV_E_STATE, "the PPO update needs a bound inter actor and inter critic (ranenv_set_policy_network, ranenv_set_value_network)");
     if (n_pop && n_one) return fail(h, RANENV_E_STATE, "the PPO update needs every net per member or every net single: a net the members share has no one owner");
     members = n_pop ? h->pop.n : 1;
@@ -1998,15 +1998,12 @@ static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
 static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s)
 {
     if (!h->ppo_on) return RANENV_OK;
-    ranenv::NetSlot *all[8] = {&h->actor, &h->actor_intra, &h->value, &h->value_intra, &h->pop_actor, &h->pop_intra, &h->pop_value, &h->pop_vintra};
-    int at_r = -1;
-    for (int r = 0; r < 8; r++) if (all[r] == slot) at_r = r;
-    if (at_r < 0) return RANENV_OK;
-    const int kind = at_r & 1;
+    if (slot->role < 0 || slot->form == FORM_SLICE) return RANENV_OK;      // (a net the update never trains)
+    const int kind = slot->role & 1;
     if (!slot->opt || slot->cap > slot->opt_cap) { h->ppo_on = false; return RANENV_OK; }
     // (actor and critic of a kind share the step counter: the partner net -- critic of an actor, actor of a critic -- restarts with it,
     //  or its old moments would meet the bias correction of t = 1)
-    ranenv::NetSlot *both[2] = {slot, all[at_r ^ 2]};
+    ranenv::NetSlot *both[2] = {slot, &h->nets[slot->role ^ 2][slot->form]};
     for (ranenv::NetSlot *x : both) {
         if (!x->on || !x->opt || x->cap > x->opt_cap) continue;
         if (member < 0) {
@@ -2089,7 +2086,7 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
 int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (role < 0 || role > 3) return fail(h, RANENV_E_INVALID, "role %d (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)", role);
+    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
     ranenv::NetSlot *slot[4];
     int members = 0;
     if (const int rc = ppo_bound(h, slot, members); rc != RANENV_OK) return rc;
@@ -2171,15 +2168,15 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
 int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv_mlp *out, void *stream)
 {
     if (!h || !out) return fail(h, RANENV_E_INVALID, "null argument");
-    if (role < 0 || role > 3) return fail(h, RANENV_E_INVALID, "role %d (0 inter actor, 1 intra actor, 2 inter critic, 3 intra critic)", role);
-    const bool pop = h->pop_slot(role)->on;
-    if (!pop && ((role == 1 && h->actor_ps.on) || (role == 3 && h->value_ps.on))) return fail(h, RANENV_E_STATE, "the %s nets are bound per slice", NET_ROLES[role].who);
-    const ranenv::NetSlot *slot = pop ? h->pop_slot(role) : h->one_slot(role);
-    if (!slot->on) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
-    if (member < 0 || member >= (pop ? h->pop.n : 1)) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, pop ? h->pop.n : 1);
-    const PolicyNet &net = pop ? slot->member[(size_t)member] : slot->net;
+    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
+    const ranenv::NetSlot *slot = h->serving(role);
+    if (!slot) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
+    if (slot->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the %s nets are bound per slice", NET_ROLES[role].who);
+    const int members = (int)slot->member.size();
+    if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
+    const PolicyNet &net = slot->member[(size_t)member];
     if (net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the %s net is bf16: its float32 weights were rounded at bind", NET_ROLES[role].who);
-    const int32_t *dims = pop ? slot->member_dims[(size_t)member].data() : slot->dims;
+    const int32_t *dims = slot->member_dims[(size_t)member].data();
     const int L = net.n_layers;
     for (int l = 0; l < L; l++)
         if ((out->weight[l] == nullptr) != (out->weight[0] == nullptr) || (out->bias[l] == nullptr) != (out->weight[0] == nullptr))
@@ -2190,7 +2187,7 @@ int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv
     if (!copy) return RANENV_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    const float *src = pop ? net.w : slot->w;
+    const float *src = net.w;
     for (int l = 0; l < L; l++) {
         const int K = dims[l], N = dims[l + 1];
         HIP_TRY(h, hipMemcpy2DAsync((void *)out->weight[l], sizeof(float) * K, src + net.w_off[l], sizeof(float) * net.kp[l], sizeof(float) * K, N, hipMemcpyDeviceToDevice, s));
@@ -2697,15 +2694,12 @@ static int rollout_persistent(ranenv_handle h, Rollout &r, hipStream_t stream)
 
 constexpr long long COLLECT_FUSED_MAX_BYTES = 3ll << 20;      // actor + critic weights that share an XCD's 4 MB of L2 with the activations' traffic
 
-// ma / mv: the role's population slot where one is bound mixed -- it counts with its largest member, the extent of every member
-static int collect_split_of(ranenv_handle h, const PolicyNet &a, const PolicyNet *v, const ranenv::NetSlot *ma = nullptr, const ranenv::NetSlot *mv = nullptr)
+// a: the actor's slot, v: its critic's (null: none runs) -- each counts with one copy (slot_copy_floats)
+static int collect_split_of(ranenv_handle h, const ranenv::NetSlot &a, const ranenv::NetSlot *v)
 {
     if (!v) return 0;
     if (h->collect_split >= 0) return h->collect_split;
-    auto floats = [](const PolicyNet &x, const ranenv::NetSlot *m) {
-        return m && m->on && m->mixed ? m->member_stride : x.b_off[x.n_layers - 1] + x.np[x.n_layers - 1] - x.w_off[0];
-    };
-    return (floats(a, ma) + floats(*v, mv)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
+    return (slot_copy_floats(a) + slot_copy_floats(*v)) * (long long)sizeof(float) > COLLECT_FUSED_MAX_BYTES ? 1 : 0;
 }
 
 // ranenv_collect / ranenv_collect_head: the recording policy launches (actors, record, critics) of envs [e0, e0 + n) on `s` into slot t of
@@ -2714,7 +2708,7 @@ static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kp
 {
     const bool head = head_policy(h);
     const size_t B = (size_t)h->cfg.batch, S = (size_t)h->cfg.n_slices, Us = (size_t)h->cfg.max_ues_slice, W = 2 * Us + 9, C = (size_t)tr.rec.cols;
-    const bool ia = !head && h->intra_actor(), vc = tr.rec.vf != nullptr, ic = vc && !head && h->intra_critic();
+    const bool ia = !head && h->serving_net(NET_INTRA), vc = tr.rec.vf != nullptr, ic = vc && !head && h->serving_net(NET_INTRA_VALUE);
     auto slot = [&](auto *p, size_t stride) { return p ? p + (size_t)t * B * stride : nullptr; };
     PolicyRec rec{};
     rec.vf = slot(tr.rec.vf, C);
@@ -2732,13 +2726,13 @@ static hipError_t collect_policy(ranenv_handle h, const Record &tr, const KP &kp
         rec.intra_actor = ia ? 1 : 0;
     }
     PolicyNets nets = head ? PolicyNets{true, &h->head.net, nullptr, vc ? &h->head_value.net : nullptr, nullptr} : h->ibsched_nets(vc);
-    const PolicyNet &actor = *nets.actor, *intra = nets.intra, *critic = nets.critic, *vintra = nets.vintra;
     // Actor and critic in one launch share the L2 of their XCD (4 MB): fused where both weight sets fit in it together, else the
     // critic runs as a launch of its own behind the actor's, each with the L2 to itself (measured, DESIGN.md 4.p "Collection").  Nets per
     // slice count with one slice's copy: the co-resident workgroups of a sliced launch mostly walk one slice's weights.
     if (!critic_only)
-        rec.split = head ? collect_split_of(h, actor, critic)
-                         : collect_split_of(h, actor, critic, &h->pop_actor, &h->pop_value) | (ia ? collect_split_of(h, *intra, vintra, &h->pop_intra, &h->pop_vintra) << 1 : 0);
+        rec.split = head ? collect_split_of(h, h->head, vc ? &h->head_value : nullptr)
+                         : collect_split_of(h, *h->serving(NET_INTER), vc ? h->serving(NET_INTER_VALUE) : nullptr) |
+                               (ia ? collect_split_of(h, *h->serving(NET_INTRA), ic ? h->serving(NET_INTRA_VALUE) : nullptr) << 1 : 0);
     return launch_policy(s, nets, net_io(h, kpk), &rec, e0, n);
 }
 
@@ -2946,9 +2940,9 @@ int ranenv_collect(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *tr
     if ((traj->adv || traj->vtarg) && !(traj->reward && traj->vf && traj->done))
         return fail(h, RANENV_E_INVALID, "adv / vtarg need the record's reward, vf and done");
     if (h->kp.policy != RANENV_POLICY_NETWORK) return fail(h, RANENV_E_STATE, "ranenv_collect needs policy NETWORK (ranenv_set_policy)");
-    if (!h->have_actor()) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
-    if (!h->have_critic()) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
-    if (h->intra_critic() && !(h->intra_actor() && h->intra_actor()->layout == h->intra_critic()->layout))
+    if (!h->serving(NET_INTER)) return fail(h, RANENV_E_STATE, "policy NETWORK but no policy network bound (ranenv_set_policy_network)");
+    if (!h->serving(NET_INTER_VALUE)) return fail(h, RANENV_E_STATE, "no value network bound (ranenv_set_value_network)");
+    if (h->serving_net(NET_INTRA_VALUE) && !(h->serving_net(NET_INTRA) && h->serving_net(NET_INTRA)->layout == h->serving_net(NET_INTRA_VALUE)->layout))
         return fail(h, RANENV_E_STATE, "the intra value net was bound for another intra policy net (bind it again, ranenv_set_value_network)");
     Record ppo;
     ppo.rec.obs_inter = traj->obs_inter; ppo.rec.obs_intra = traj->obs_intra; ppo.rec.mask_inter = traj->mask_inter; ppo.rec.mask_intra = traj->mask_intra;
