@@ -294,14 +294,12 @@ int build_poisson_tables(ranenv_handle h, hipStream_t stream)
 
 // RANENV_F_SCALE_PER_ELEMENT: every step / dense launch runs the lean build compiled for that convention -- no mixed blocks, packed
 // waves, small-batch / whole-row builds or persistent launches (those exist for the default convention only)
-bool scale_per_element(ranenv_handle h) { return (h->cfg.flags & RANENV_F_SCALE_PER_ELEMENT) != 0; }
+bool scale_per_element(const ranenv *h) { return (h->cfg.flags & RANENV_F_SCALE_PER_ELEMENT) != 0; }
 
 // A batch whose widest blocks all together stay within 2 waves per SIMD (8 per CU): one class, and -- streaming -- the build
 // with the whole SE row in flight.
-bool persist_tiny(ranenv_handle h)
-{
-    return (long long)h->cfg.batch * (h->nt / WAVE) <= 8ll * h->n_cus;
-}
+constexpr long long TINY_MAX_WAVES_PER_CU = 8;
+bool persist_tiny(const ranenv *h) { return (long long)h->cfg.batch * (h->nt / WAVE) <= TINY_MAX_WAVES_PER_CU * h->n_cus; }
 
 bool stream_capturing(hipStream_t stream)      // (an error of the query itself counts as "capturing": the careful path)
 {
@@ -331,7 +329,7 @@ bool pack_fits_32_of(const ranenv_config &cfg, long long trf_rows_n, long long s
            B * D * U * 4 < lim && NS * S * 32 < lim && 2 * NS * S * 24 < lim && NS * S * 16 < lim && B * S * 8 < lim && B * (S + 1) * 8 < lim &&
            B * S * W * 4 < lim && (unsigned long long)trf_rows_n * U * 4 < lim && (unsigned long long)se_tiles_n * U * 8 < lim;
 }
-bool pack_fits_32(ranenv_handle h) { return pack_fits_32_of(h->cfg, h->trf_rows_n, h->se_tiles_n); }
+bool pack_fits_32(const ranenv *h) { return pack_fits_32_of(h->cfg, h->trf_rows_n, h->se_tiles_n); }
 
 // Under ranenv_profile_begin: the next (start, stop) pair of the event pool, for a launch of n envs through n_tti TTIs
 hipError_t prof_events(ranenv_handle h, int n, int n_tti, hipEvent_t *ev0, hipEvent_t *ev1)
@@ -360,6 +358,7 @@ hipError_t launch_step_counted(ranenv_handle h, const StepLaunch &l, dim3 grid, 
     const bool known = l.build >= 0 && l.build < N_STEP_BUILDS;
     if (e == hipSuccess) {
         if (known && (l.mode & 3) == MODE_STEP) h->step_launches[l.build][l.many ? 1 : 0]++;
+        if (l.members) h->last_rollout_member_lines = 1;
     } else {
         char buf[160];
         snprintf(buf, sizeof(buf), "step kernel build '%s' (row width %d, mode %d, %s, %s): %s", known ? step_build_names[l.build] : "?", l.np, l.mode,
@@ -369,15 +368,17 @@ hipError_t launch_step_counted(ranenv_handle h, const StepLaunch &l, dim3 grid, 
     return e;
 }
 
-// The build of the step kernel for one launch of envs [e0, e0 + n), with its grid and block; `kp` gets what every kernel of the
-// launch reads from it (the compact flag, the SE gather sidecars).  SB_MIXED: the class lists are the caller's to sort and bind.
-struct StepPlan { StepLaunch l; dim3 grid, block; };
-template <int MODE>
-StepPlan step_plan(ranenv_handle h, KP &kp, int e0, int n, bool gather)
+// THE STEP BUILD, chosen here and nowhere else, from the handle's shape and options (nothing is written) and what the launch is: mode, TTIs,
+// the compact value offered (2: a rollout's), the SE gather build?, envs [e0, e0 + n), a member-lines copy on offer?, an env mask?, the call's own
+// SE tiles?  With its grid and block and the compact value (0 / 1) its kernels then read.  SB_MIXED: the class lists are the caller's to sort and bind.
+struct StepFacts { int mode, n_tti, compact; bool gather; int e0, n; bool lines = false, masked = false, tiles = false; };
+struct StepChoice { StepLaunch l; dim3 grid, block; int compact; };
+StepChoice step_choice(const ranenv *h, const StepFacts &f)
 {
+    const bool step = f.mode == MODE_STEP;
     // RANENV_F_SCALE_PER_ELEMENT: the lean builds with the other rounding of the masked SE sum (MODE_PE); a reset sums no masked row
-    const bool pe = MODE != MODE_RESET && scale_per_element(h);
-    const bool many = MODE == MODE_STEP && kp.n_tti > 1;
+    const bool pe = f.mode != MODE_RESET && scale_per_element(h);
+    const bool many = step && f.n_tti > 1;
     // Compact steps pay off for the gather kernels throughout (-3...-7 %).  The streaming kernels want lane = UE: their row
     // loads are coalesced in that order (a wave reads 256 contiguous bytes per RB; slice members first scatters its lanes
     // over the whole 400-byte row), so they step compactly only where it was measured to win: under ranenv_rollout's
@@ -386,33 +387,38 @@ StepPlan step_plan(ranenv_handle h, KP &kp, int e0, int n, bool gather)
     // resident in one round.  For launches of the whole batch of two-wave workgroups, where a compact step is exact.
     // (whole-batch launches only: for the ranges of a partitioned batch per-range lists were built and measured -- two alternating
     // ranges 47.8 against 48.0 us per TTI in gather mode, and the streaming kernel loses the lane = UE order it wants there: dropped)
-    bool mixed = false;
-    if constexpr (MODE == MODE_STEP)
-        mixed = !pe && h->mix != 0 && kp.compact != 0 && h->nt == 2 * WAVE && e0 == 0 && n == h->cfg.batch && kp.env_mask == nullptr &&
-                (h->mix == 2 || !persist_tiny(h)) && RANENV_DIAG == 0;
-    if (!mixed && !gather && kp.compact != 2) kp.compact = 0;
-    if (kp.compact) kp.compact = 1;
-    if (gather) {
-        kp.se_pool = h->d_se_um; kp.se_stride = (long long)h->cfg.n_ues * h->se_rp;
-        kp.se_mean_pool = h->d_se_mean; kp.se_rp = h->se_rp;
-    }
-    const dim3 grid((unsigned)n), block((unsigned)h->nt);
-    if (mixed) return {{h->np, SB_MIXED, MODE_STEP, many, gather}, grid, dim3(2 * WAVE)};      // (grid: an upper bound of wide + ceil(narrow / 2))
+    const bool mixed = step && !pe && h->mix != 0 && f.compact != 0 && h->nt == 2 * WAVE && f.e0 == 0 && f.n == h->cfg.batch && !f.masked &&
+                       (h->mix == 2 || !persist_tiny(h)) && RANENV_DIAG == 0;
+    const int compact = f.compact != 0 && (mixed || f.gather || f.compact == 2) ? 1 : 0;
+    const dim3 grid((unsigned)f.n), block((unsigned)h->nt);
+    if (mixed) return {{h->np, SB_MIXED, MODE_STEP, many, f.gather}, grid, dim3(2 * WAVE), compact};      // (grid: an upper bound of wide + ceil(narrow / 2))
     // packed waves: two envs per wave for envs of <= 32 UEs / <= 8 slices (see ranenv_core_kernel_packed)
-    if (MODE == MODE_STEP && !pe && h->pack && h->np == 8 && h->cfg.n_ues <= 32 && h->nt == WAVE && (n & 1) == 0 && kp.env_mask == nullptr && pack_fits_32(h))
-        return {{8, SB_PACKED, MODE_STEP, many, gather}, dim3((unsigned)(n / 2)), dim3(WAVE)};
+    if (step && !pe && h->pack && h->np == 8 && h->cfg.n_ues <= 32 && h->nt == WAVE && (f.n & 1) == 0 && !f.masked && pack_fits_32(h))
+        return {{8, SB_PACKED, MODE_STEP, many, f.gather}, dim3((unsigned)(f.n / 2)), dim3(WAVE), compact};
     // SE gather mode, else -- one-TTI steps of a batch at <= 2 waves per SIMD -- the whole-row build, else the small-batch or the lean build
-    StepLaunch l{h->np, SB_LEAN, pe ? MODE | MODE_PE : MODE, many, gather};
-    if (gather) l.build = SB_GATHER;
-    else if (!pe && MODE == MODE_STEP && !many && h->tiny_step && persist_tiny(h)) l.build = SB_TINY1;
+    StepLaunch l{h->np, SB_LEAN, pe ? f.mode | MODE_PE : f.mode, many, f.gather};
+    if (f.gather) l.build = SB_GATHER;
+    else if (!pe && step && !many && h->tiny_step && persist_tiny(h)) l.build = SB_TINY1;
     else if (!pe && h->small_batch) l.build = SB_SMALL;
-    // (the rollout offered its member-lines copy: the lean build of several TTIs reads it where the step is compact)
-    l.members = l.build == SB_LEAN && MODE == MODE_STEP && many && !pe && kp.ml_pool != nullptr && kp.compact != 0 && kp.se_tiles == nullptr;
-    return {l, grid, block};
+    // THE MEMBER-LINES RULE, launches per chunk: the lean build of several TTIs reads an offered copy where the step is compact
+    l.members = l.build == SB_LEAN && many && !pe && f.lines && compact != 0 && !f.tiles;
+    return {l, grid, block, compact};
+}
+// ... and of a persistent class launch: the work-queue build of the SE mode; streaming, a batch of <= 2 waves per SIMD runs the whole-row
+// build, and any other reads an offered member-lines copy.  `plain`: the work-queue build whatever the batch (the occupancy query's).
+StepLaunch persist_choice(const ranenv *h, bool lines, bool plain = false)
+{
+    const bool gather = h->se_mode == RANENV_SE_GATHER, tiny = !gather && !plain && persist_tiny(h);
+    return {h->np, tiny ? SB_PERSIST_TINY : SB_PERSIST, MODE_STEP, true, gather, !gather && !tiny && lines};
+}
+void gather_kp(const ranenv *h, KP &kp)      // the SE gather builds read the sidecars of the bound pool instead of tiles
+{
+    kp.se_pool = h->d_se_um; kp.se_stride = (long long)h->cfg.n_ues * h->se_rp;
+    kp.se_mean_pool = h->d_se_mean; kp.se_rp = h->se_rp;
 }
 
 // Per-slice episode metrics are kept: the slice-metrics kernel follows every step and reset, one TTI per step launch
-bool slice_metrics_on(ranenv_handle h) { return h->slice_on && h->kp.acc != nullptr && h->d_slice_acc != nullptr; }
+bool slice_metrics_on(const ranenv *h) { return h->slice_on && h->kp.acc != nullptr && h->d_slice_acc != nullptr; }
 // ... then a call that steps needs the two outputs that kernel reads
 int slice_metrics_outputs(ranenv_handle h, const float *obs_intra, const double *reward)
 {
@@ -422,7 +428,7 @@ int slice_metrics_outputs(ranenv_handle h, const float *obs_intra, const double 
 }
 
 // A trace is bound: the trace kernel follows every step launch, one TTI per step launch (the conditions slice metrics impose)
-bool trace_on(ranenv_handle h) { return h->trace_on; }
+bool trace_on(const ranenv *h) { return h->trace_on; }
 // ... then a call that steps needs the outputs that kernel copies, and -- for the tile -- a float32 pool or the call's own tiles
 int trace_outputs(ranenv_handle h, const float *se_tiles, const float *obs_inter, const float *obs_intra, const double *reward, const uint8_t *done)
 {
@@ -456,7 +462,9 @@ hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t strea
     // SE gather mode: tiles replayed from the pool are read through the sidecars; explicit per-step tiles and dense
     // sched_decisions (whole rows are needed) keep the streaming kernel
     const bool gather = MODE != MODE_DENSE && h->se_mode == RANENV_SE_GATHER && kp.se_tiles == nullptr;
-    const StepPlan p = step_plan<MODE>(h, kp, e0, n, gather);
+    const StepChoice p = step_choice(h, {MODE, kp.n_tti, kp.compact, gather, e0, n, kp.ml_pool != nullptr, kp.env_mask != nullptr, kp.se_tiles != nullptr});
+    kp.compact = p.compact;
+    if (gather) gather_kp(h, kp);
     KP ks = kp;
     if (p.l.build == SB_MIXED) {
         if (persist_prepare(h, stream, false) != RANENV_OK) return hipErrorUnknown;
@@ -467,7 +475,6 @@ hipError_t launch_range(ranenv_handle h, KP kp, int e0, int n, hipStream_t strea
     if (pe != hipSuccess) return pe;
     const hipError_t le = launch_step_counted(h, p.l, p.grid, p.block, stream, ev0, ev1, ks);
     if (le != hipSuccess) return le;
-    if (p.l.members) h->last_rollout_member_lines = 1;
     if (kp.head_obs || kp.head_reward)
         launch_head(stream, dim3((unsigned)n), dim3((unsigned)h->nslot), kp, (h->kp.acc && h->kp.head_reward) ? h->d_head_acc : nullptr,
                     MODE == MODE_RESET ? 1 : 0);
@@ -601,7 +608,7 @@ AdvanceArgs advance_args(ranenv_handle h, const uint8_t *dev_done, float *obs_in
     return a;
 }
 
-int max_steps_of_env(ranenv_handle h, int b) { return h->host_max_steps.empty() ? h->cfg.max_steps : h->host_max_steps[(size_t)b]; }
+int max_steps_of_env(const ranenv *h, int b) { return h->host_max_steps.empty() ? h->cfg.max_steps : h->host_max_steps[(size_t)b]; }
 
 void shadow_steps_add(ranenv_handle h, int lo, int hi, int n, const uint8_t *done, hipStream_t stream)      // n TTIs enqueued for envs [lo, hi)
 {
@@ -710,22 +717,18 @@ int persist_check_errors(ranenv_handle h)
 int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
 {
     const int B = h->cfg.batch, NC = h->p_nclass;
-    const bool gather = h->se_mode == RANENV_SE_GATHER;
+    const StepLaunch l = persist_choice(h, kp.ml_pool != nullptr);      // (the rollout offered its member-lines copy?)
     kp.n_tti = n_tti; kp.compact = 1; kp.e0 = 0;
     // (a chunk is always shorter than the launch, so that the envs reach a chunk end inside it and find the exhausted env cursors
     // there, at different TTIs: without one all workgroups finish together and walk those cursors at once -- DESIGN.md 4.4, "Short
     // rollouts", profiles/r06_ab_log.txt)
     kp.p_chunk = h->persist_chunk < n_tti ? h->persist_chunk : (n_tti > 1 ? n_tti - 1 : 1);
     kp.p_cap = h->p_cap; kp.p_err = h->d_perr_dev;
-    if (gather) {
-        kp.se_pool = h->d_se_um; kp.se_stride = (long long)h->cfg.n_ues * h->se_rp;
-        kp.se_mean_pool = h->d_se_mean; kp.se_rp = h->se_rp;
-    }
-    const bool tiny = persist_tiny(h);            // (then every env is in the widest class and the grid is the batch)
-    int &slots_cu = h->p_wave_slots[gather ? 1 : 0];
+    if (l.gather) gather_kp(h, kp);
+    int &slots_cu = h->p_wave_slots[l.gather ? 1 : 0];
     if (slots_cu == 0) {
         int nb = 0;
-        const void *fn = step_kernel_ptr(StepLaunch{h->np, SB_PERSIST, MODE_STEP, true, gather});
+        const void *fn = step_kernel_ptr(persist_choice(h, false, true));
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, WAVE, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 16; }
         slots_cu = nb;
     }
@@ -763,10 +766,8 @@ int persist_launch(ranenv_handle h, KP kp, int n_tti, hipStream_t stream)
         e = prof_events(h, n, n_tti, &ev0, &ev1);
         if (e != hipSuccess) return fail(h, RANENV_E_HIP, "hipEventCreate(&pe): %s", hipGetErrorString(e));
         const dim3 grid((unsigned)g), block((unsigned)((c + 1) * WAVE));
-        const bool members = !gather && !tiny && kp.ml_pool != nullptr;      // (the rollout offered its member-lines copy)
-        e = launch_step_counted(h, StepLaunch{h->np, (!gather && tiny) ? SB_PERSIST_TINY : SB_PERSIST, MODE_STEP, true, gather, members}, grid, block, s, ev0, ev1, kc);
+        e = launch_step_counted(h, l, grid, block, s, ev0, ev1, kc);
         if (e != hipSuccess) return fail(h, RANENV_E_HIP, "persistent rollout launch: %s", hipGetErrorString(e));
-        if (members) h->last_rollout_member_lines = 1;
         if (k > 0) HIP_TRY(h, hipEventRecord(h->part_done[(size_t)k], s));
         k++;
     }
@@ -1079,7 +1080,7 @@ int ranenv_create(const ranenv_config *cfg, ranenv_handle *out)
             h->n_cus = prop.multiProcessorCount;
             h->small_batch = (long long)cfg->batch <= 8ll * prop.multiProcessorCount;
         }
-        e = hipFuncGetAttributes(&fa, step_kernel_ptr(StepLaunch{16, SB_LEAN, MODE_STEP, false, false}));
+        e = hipFuncGetAttributes(&fa, step_kernel_ptr(step_choice(h, {MODE_RESET, 1, 0, false, 0, cfg->batch}).l));      // (a reset of the whole batch)
         if (e != hipSuccess) {
             ranenv_destroy(h);
             return fail(nullptr, RANENV_E_HIP, "no usable gfx950 kernel image (hipFuncGetAttributes: %s)", hipGetErrorString(e));
@@ -2642,7 +2643,7 @@ struct Rollout {
 
 // TTIs from now until the first episode of envs [lo, hi) ends, that TTI included, between 1 and n.  `n_ends`: at how many different
 // TTIs before the n-th episodes end (counted up to 3).
-static int ttis_to_end(ranenv_handle h, const Rollout &r, int lo, int hi, int n, int *n_ends = nullptr)
+static int ttis_to_end(const ranenv *h, const Rollout &r, int lo, int hi, int n, int *n_ends = nullptr)
 {
     int first = n, ends[3], k = 0;
     for (int b = lo; b < hi; b++) {
@@ -2771,23 +2772,48 @@ static hipError_t rollout_tti(ranenv_handle h, Rollout &r, KP kpk, int t, int e0
     return collect_policy(h, *ppo, kpk, t + 1, true, e0, n, s);
 }
 
-// TTIs per launch of the launch-per-chunk rollout (at most: a partition's first launch and an episode end may cut one short)
-static int rollout_fuse(ranenv_handle h, const Rollout &r)
+// THE PLAN of a rollout: one persistent work-queue launch per class (rollout_persistent) or launches per chunk of at most `fuse` TTIs
+// (rollout_chunks), and whether those launches would read the member-lines copy.  Made once per call from the handle, the call's Rollout
+// -- compact steps decided, the step counters read back -- and whether the stream is capturing: no HIP call, nothing written.
+struct RolloutPlan { bool persistent; int fuse; bool member_lines; };
+// Auto persistent where it was measured to win or tie (profiles/r04_ab_log.txt, r05_ab_log.txt, r06_ab_log.txt): either mode
+// at <= 2 waves per SIMD (persist_tiny), SE gather mode up to ~2x what the chip holds (beyond, every chunk swaps envs), and streaming
+// rollouts of 4...64 TTIs at <= 20 envs per CU (the streaming kernel is bound by HBM either way: larger batches and longer rollouts tie or lose)
+constexpr long long PERSIST_GATHER_MAX_ENVS_PER_CU = 44, PERSIST_STREAM_MAX_ENVS_PER_CU = 20, PERSIST_STREAM_MIN_TTIS = 4, PERSIST_STREAM_MAX_TTIS = 64;
+// ... but not when episodes end at more than two different TTIs inside the call (per-env episode lengths, envs reset at different times): every
+// end stops the persistent launches, re-sorts the envs and reads the class counts back; launches per chunk follow the ends per partition without a host sync
+constexpr int PERSIST_MAX_EPISODE_ENDS = 2;
+// A launch per chunk takes its envs through several TTIs where nothing has to happen in between (see step_loop; with auto-reset: no episode
+// end before its last TTI): a quarter of the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more
+// and lengthen the drain at the rollout's end, where the workgroups that waited for a free slot run last and alone)
+constexpr int FUSE_ROLLOUT_PART = 4, FUSE_MAX_TTIS = 10;
+static RolloutPlan rollout_plan(const ranenv *h, const Rollout &r, bool capturing)
 {
-    const int n_steps = r.n_steps;
-    if (r.kp.head_obs || r.kp.head_reward || r.net || slice_metrics_on(h) || trace_on(h)) return 1;
-    return h->fuse > 0 ? h->fuse : (n_steps / 4 < 1 ? 1 : (n_steps / 4 > 10 ? 10 : n_steps / 4));
+    const int k = r.n_steps;
+    const long long B = h->cfg.batch, N = h->n_cus;
+    const bool gather = h->se_mode == RANENV_SE_GATHER;
+    // ONE TTI PER LAUNCH where something runs between two TTIs: the policy nets in front of every step, the head, slice-metrics or trace kernel behind it
+    const bool one_tti = r.kp.head_obs || r.kp.head_reward || r.net || slice_metrics_on(h) || trace_on(h);
+    RolloutPlan p{false, one_tti ? 1 : (h->fuse > 0 ? h->fuse : std::clamp(k / FUSE_ROLLOUT_PART, 1, FUSE_MAX_TTIS)), false};
+    const bool wins = persist_tiny(h) || (!h->small_batch && (gather ? B <= PERSIST_GATHER_MAX_ENVS_PER_CU * N
+                          : B <= PERSIST_STREAM_MAX_ENVS_PER_CU * N && k >= PERSIST_STREAM_MIN_TTIS && k <= PERSIST_STREAM_MAX_TTIS));
+    p.persistent = (RANENV_DIAG == 0 || RANENV_DIAG == 12) && (h->persist == 1 || (h->persist < 0 && wins)) && !one_tti && !scale_per_element(h) &&
+                   r.kp.compact != 0 && (B >> PERSIST_ENV_BITS) == 0 && !capturing;      // (its classes are those of the compact lane order; it reads the class counts back)
+    int n_ends = 0;
+    if (p.persistent && h->persist < 0 && r.follow) (void)ttis_to_end(h, r, 0, h->cfg.batch, k, &n_ends);
+    p.persistent = p.persistent && n_ends <= PERSIST_MAX_EPISODE_ENDS;
+    // Member lines (option "member_lines"; auto = on): wanted where the build of the persistent launches, or of the first partition's
+    // launches of several TTIs, reads an offered copy (persist_choice, step_choice: compact streaming rollouts)
+    const StepFacts chunk{MODE_STEP, 2, r.kp.compact, gather, 0, h->n_parts > 1 ? h->part_lo[1] : h->cfg.batch, true};
+    p.member_lines = h->member_lines != 0 && h->kp.se_pool != nullptr &&
+                     (p.persistent ? persist_choice(h, true).members : k > 1 && p.fuse > 1 && step_choice(h, chunk).l.members);
+    return p;
 }
 
-// Every partition walks through the TTIs in launches of its own, on its own stream
-static int rollout_chunks(ranenv_handle h, Rollout &r, hipStream_t stream)
+// Every partition walks through the TTIs in launches of its own, on its own stream, of at most `fuse` TTIs
+static int rollout_chunks(ranenv_handle h, Rollout &r, int fuse, hipStream_t stream)
 {
     const int n_steps = r.n_steps;
-    // A launch takes its envs through several TTIs where nothing has to happen in between (see step_loop): no head kernel
-    // behind every step, and -- with auto-reset -- no episode end before the launch's last TTI.  How many: a quarter of
-    // the rollout, at most 10 (measured, profiles/r03_ab_log.txt: longer launches gain nothing more and lengthen the
-    // drain at the rollout's end, where the workgroups that waited for a free slot run last and alone).
-    const int fuse = rollout_fuse(h, r);
     // `pdone[k]` TTIs are enqueued for partition k
     const int np = h->n_parts > 1 ? h->n_parts : 1;
     std::vector<int> pdone((size_t)np, 0), pn((size_t)np, 0);
@@ -2850,13 +2876,12 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     r.n_steps = n_steps;
     r.kp = call_kp(h, obs_inter, obs_intra, reward, done);
     h->last_rollout_persistent = 0; h->last_rollout_launches = 0; h->last_rollout_member_lines = 0;
-    // (policy network: its launch precedes every TTI of a partition -- one TTI per step launch, no persistent launches)
-    r.net = net_use(h, r.kp);
+    r.net = net_use(h, r.kp);                      // (policy network: its launch precedes every TTI of a partition, see rollout_plan)
     if (r.net < 0) return r.net;
     r.rec = rec;
     rc = compact_for(h, r.kp, stream, &r.kp.compact);
     if (rc != RANENV_OK) return rc;
-    if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_plan)
+    if (r.kp.compact) r.kp.compact = 2;             // (2: the streaming kernels may step compactly too, see step_choice)
     r.follow = h->ar_on;
     if (r.follow) {
         if (!done) return fail(h, RANENV_E_INVALID, "a rollout with auto-reset needs the done buffer");
@@ -2867,36 +2892,10 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
         r.adv = advance_args(h, done, obs_inter, obs_intra, nullptr, nullptr, nullptr);
         r.kpr = reset_behind(h, r.kp);
     }
-    // The persistent rollout needs compact steps (the classes are those of the compact lane order) and no head kernel behind every TTI.
-    // Auto: where it was measured to win or tie (profiles/r04_ab_log.txt, r05_ab_log.txt, r06_ab_log.txt): SE gather mode
-    // up to ~2x what the chip holds (beyond, every chunk swaps envs), either mode at <= 2 waves per SIMD, and streaming rollouts of 4...64
-    // TTIs at <= 20 envs per CU (the streaming kernel is bound by HBM either way: larger batches and longer rollouts tie or lose).
-    const bool stream_short = h->se_mode != RANENV_SE_GATHER && !h->small_batch && (long long)h->cfg.batch <= 20ll * h->n_cus && n_steps >= 4 && n_steps <= 64;
-    const bool persist_wanted = (RANENV_DIAG == 0 || RANENV_DIAG == 12) && (h->persist == 1 || (h->persist < 0 && ((h->se_mode == RANENV_SE_GATHER && !h->small_batch && (long long)h->cfg.batch <= 44ll * h->n_cus) || persist_tiny(h) || stream_short)));
-    // (auto: not when episodes end at many different TTIs inside this call -- per-env episode lengths, envs reset at different times:
-    // every episode end ends the persistent launches, re-sorts the envs and reads the class counts back; the launch-per-chunk
-    // rollout follows the ends per partition without a host sync)
-    bool persist_ok = persist_wanted && !r.net && !scale_per_element(h) && r.kp.compact != 0 && !(r.kp.head_obs || r.kp.head_reward) && !slice_metrics_on(h) && !trace_on(h) &&
-                      (h->cfg.batch >> PERSIST_ENV_BITS) == 0 && !stream_capturing(stream);      // (it reads the class counts back)
-    if (persist_ok && h->persist < 0 && r.follow) {
-        int n_ends = 0;
-        (void)ttis_to_end(h, r, 0, h->cfg.batch, n_steps, &n_ends);
-        if (n_ends > 2) persist_ok = false;
-    }
-    // Member lines (option "member_lines"; auto = on): a compact streaming rollout whose launches are the lean build of several TTIs or
-    // the streaming persistent build reads the handle's per-UE line copy of the pool instead of whole tiles.  The copy is built here, by
-    // the first rollout that would use it (never inside a stream capture: such a rollout uses it only if it is there already).
-    if (h->member_lines != 0 && h->se_mode != RANENV_SE_GATHER && r.kp.compact != 0 && !scale_per_element(h) && h->kp.se_pool != nullptr) {
-        bool runs = persist_ok && !persist_tiny(h);
-        if (!persist_ok && n_steps > 1 && rollout_fuse(h, r) > 1) {
-            KP kt = r.kp;
-            kt.n_tti = 2;
-            const bool parts = h->n_parts > 1;
-            runs = step_plan<MODE_STEP>(h, kt, parts ? h->part_lo[0] : 0, parts ? h->part_lo[1] - h->part_lo[0] : h->cfg.batch, false).l.build == SB_LEAN;
-        }
-        if (runs && member_lines_ready(h, stream)) { r.kp.ml_pool = h->d_ml; r.kp.ml_stride = h->ml_stride; }
-    }
-    rc = persist_ok ? rollout_persistent(h, r, stream) : rollout_chunks(h, r, stream);
+    const RolloutPlan plan = rollout_plan(h, r, stream_capturing(stream));
+    // (the handle's per-UE line copy of the pool is built by the first rollout that would use it, never inside a stream capture: member_lines_ready)
+    if (plan.member_lines && member_lines_ready(h, stream)) { r.kp.ml_pool = h->d_ml; r.kp.ml_stride = h->ml_stride; }
+    rc = plan.persistent ? rollout_persistent(h, r, stream) : rollout_chunks(h, r, plan.fuse, stream);
     if (rc != RANENV_OK) return rc;
     if (rec) {
         // (the partitions have joined the caller's stream)  The caller's reward -- under a head policy with source HEAD: the bound head rewards -- and

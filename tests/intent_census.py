@@ -213,7 +213,7 @@ def even_cut(B: int, parts: int):
 
 def draw_fuzz_case_for(build: str, k: int):
     """Case ``k`` of tests/test_gpu_fuzz.py's "packed*" and "mixed*" columns: draw_fuzz_case's fields on a seed stream of their own,
-    with the shape drawn inside what the build needs (csrc/ranenv_host.cpp: step_plan) -- none of draw_fuzz_case's first 24 shapes is
+    with the shape drawn inside what the build needs (csrc/ranenv_host.cpp: step_choice) -- none of draw_fuzz_case's first 24 shapes is
     packable and few can run mixed blocks.  "packed*": two envs per wave -- S and Us in 1..8 (row width 8), U <= 32 (one wave per
     env), an even batch ``B``, and for device_rollout a number of partitions ``parts`` whose ranges are all even.  "mixed*": 64 < U
     <= 128 (two waves per env) and whole-batch launches, so device_rollout runs unpartitioned.  The rest as draw_fuzz_case."""

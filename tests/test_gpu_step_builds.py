@@ -3,7 +3,7 @@ and no other -- ran.
 
 The step kernel exists in eight builds (StepBuild, csrc/ranenv_internal.h), each per row width (8, 10, 16), most of them for one
 TTI per launch and for several (MANY), several for both SE modes, two for the per-element rounding.  Which one a launch runs is
-decided by a dozen conditions on shape, batch size, options and call state (step_plan, rollout_run in csrc/ranenv_host.cpp), so a
+decided by a dozen conditions on shape, batch size, options and call state (step_choice, rollout_plan in csrc/ranenv_host.cpp), so a
 test that merely carries a build's name may never have run it.  Here every reachable (build, MANY, SE mode, rounding) runs at two
 shapes per row width -- one of one wave per env, one of two -- forced through set_option after create (not through the
 environment: the result does not depend on how the suite was started), steps a device policy (MAPF + PF) over an oracle replay of

@@ -167,7 +167,7 @@ def test_draw_fuzz_case_is_what_it_was():
 
 @pytest.mark.parametrize("build", ["packed", "packed-gather", "mixed", "mixed-gather"])
 def test_fuzz_cases_drawn_for_a_build_meet_the_conditions_of_that_build(build):
-    """step_plan's conditions (csrc/ranenv_host.cpp) restated on the drawn shape: packed waves need row width 8, at most 32 UEs, one
+    """step_choice's conditions (csrc/ranenv_host.cpp) restated on the drawn shape: packed waves need row width 8, at most 32 UEs, one
     wave per env and an even number of envs in every launch; mixed blocks need two waves per env and a launch of the whole batch.  And
     the scenario generator accepts every drawn shape."""
     hows = set()
