@@ -685,7 +685,7 @@ int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *d
  * ranenv_ppo_bind: allocates, per bound IBSched actor and critic slot (the one-net slots and a population's uniform ones), float32
  *   Adam moments m, v and gradient scratch in the slot's packed layout, and one step counter per (member, kind); all zero.  Refused
  *   with RANENV_E_STATE, before any device call: no bound inter actor + critic; a bf16 net among them; intra nets per slice
- *   (ranenv_set_intra_policy_networks / _value_networks); a mixed population; policy RANENV_POLICY_HEAD_NETWORK; a net beyond THE LDS
+ *   (ranenv_set_intra_policy_networks / _value_networks); a mixed population (ranenv_ppo_bind_mixed, below, trains it); policy RANENV_POLICY_HEAD_NETWORK; a net beyond THE LDS
  *   PLAN: the workgroup keeps the 32-row input and every layer's 32-row output of one net in LDS at once (the backward pass overwrites
  *   them in place), 4096 + 128 * sum over the input and the layers of ld(width padded to 32) bytes with ld(x) = x + 36 if x % 64 else
  *   x + 4, at most 163 840.  [64, 64], [256, 256] and [400, 300] fit at S 10 / Us 100; [512, 512, 512] does not.
@@ -744,6 +744,32 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
 int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes);
 int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats);
 int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp);
+/* Mixed populations (ranenv_set_population_policy_mixed / _value_mixed: members that differ in hidden widths, depth and activation)
+ * are trained through an entry of their own, as they are bound through one: ranenv_ppo_bind stays RANENV_E_STATE for them.
+ * ranenv_ppo_bind_mixed: ranenv_ppo_bind for a population in which at least one bound role is mixed (none: RANENV_E_STATE).  The other
+ *   rules are ranenv_ppo_bind's -- inter actor and inter critic bound, every bound role per member, float32, no nets per slice, no head
+ *   policy -- and THE LDS PLAN holds PER MEMBER: a member whose actor / critic pair of a kind needs more than 163 840 bytes refuses the
+ *   bind, the message naming the member, the kind and the bytes.  The reference's `verybig` net_arch, [512] x 3, therefore cannot be a
+ *   member of a device-trained population; `small` [64, 64], `medium` [256, 256], `big` [400, 300] and `deep` [256, 256, 256] can.
+ *   Moments and gradient scratch cover every member's extent (the largest member's packed size), whatever shape the member has now.
+ * ranenv_ppo_update then runs a second instance of the kernel: workgroup (m, kind) reads member m's actor and critic descriptors from
+ *   the role tables the mixed policy kernels read and is from there on a one-net workgroup on that member's shape, activation and layer
+ *   offsets, its 32-row buffers laid out by the member's own widths inside a launch whose LDS is the largest member's.  Arguments,
+ *   arithmetic, summation order and refusals are unchanged: member m's bytes equal those of a uniform population of m's shape given the
+ *   same rows.  dev_grad: the stride, ranenv_ppo_layout's grad_floats, is the largest (actor + critic floats) over members and kinds;
+ *   member m's block holds its actor's packed gradient, then its critic's, and is not written behind them.  ranenv_ppo_layout's lds_bytes
+ *   is the launch's: the maximum over members and kinds.  ranenv_ppo_state's floats and ranenv_get_net_weights are member m's own.
+ * Re-binding under a mixed binding: ranenv_set_population_member zeroes the member's WHOLE extent of m and v of the re-bound net and of
+ *   its partner net (another shape moves every offset: no moment of the old shape stays in the tail) and the (member, kind) counter; a
+ *   new shape beyond THE LDS PLAN is RANENV_E_STATE before any device call, and the member's weights, moments and counter keep their
+ *   bytes.  A whole-role re-bind follows the rule above: zeroed where it fits the slot, the binding ended where it outgrows it.
+ * ranenv_ppo_member_layout: what unpacks one member's block of dev_grad -- the packed floats of member `member`'s actor and critic of
+ *   `kind` (0 inter, 1 intra; critic 0: none bound) and the LDS bytes of that pair.  Uniform bindings: every member's are the same.
+ * ranenv_ppo_lds_bytes: THE LDS PLAN's formula without a handle (as ranenv_packed_net_floats), from n_hidden and dims of `actor` and
+ *   `critic` (NULL: no critic): the larger of the two nets' needs.  A search draws only trainable architectures before it binds any. */
+int ranenv_ppo_bind_mixed(ranenv_handle h, void *stream);
+int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int64_t *actor_floats, int64_t *critic_floats, int64_t *lds_bytes);
+int ranenv_ppo_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *bytes);
 int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv_mlp *out, void *stream);
 
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,

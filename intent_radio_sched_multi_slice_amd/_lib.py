@@ -223,6 +223,9 @@ FUNCTIONS = {
     "ranenv_ppo_state": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "ranenv_ppo_probe_logp": (C.c_int, [_P, _P]),
     "ranenv_get_net_weights": (C.c_int, [_P, _I32, _I32, C.POINTER(Mlp), _P]),
+    "ranenv_ppo_bind_mixed": (C.c_int, [_P, _P]),
+    "ranenv_ppo_member_layout": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ranenv_ppo_lds_bytes": (C.c_int, [C.POINTER(Mlp), C.POINTER(Mlp), C.POINTER(C.c_int64)]),
 }
 POPULATION_MAX = 64
 POPULATION_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}

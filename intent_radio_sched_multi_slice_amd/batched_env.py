@@ -164,6 +164,16 @@ def packed_net_floats(layers, precision: str = "f32") -> int:
     ``layers``: a net as for ``policy_net_layers``, or its widths ``[in, hidden..., out]``."""
     if precision not in _lib.NET_PRECISIONS:
         raise ValueError(f"precision must be one of {sorted(_lib.NET_PRECISIONS)}")
+    dims = _net_widths(layers)
+    out = C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_packed_net_floats(len(dims) - 2, (C.c_int32 * len(dims))(*dims), _lib.NET_PRECISIONS[precision], C.byref(out)),
+               "ranenv_packed_net_floats")
+    return out.value
+
+
+def _net_widths(layers):
+    """``[in, hidden..., out]`` of a net given as for ``policy_net_layers``, or as those widths themselves"""
     if isinstance(layers, (list, tuple)) and len(layers) > 0 and all(isinstance(x, (int, np.integer)) for x in layers):
         dims = [int(x) for x in layers]
     else:
@@ -171,10 +181,27 @@ def packed_net_floats(layers, precision: str = "f32") -> int:
         dims = [got[0][0].shape[1]] + [w.shape[0] for w, _ in got]
     if not 3 <= len(dims) <= NET_MAX_HIDDEN + 2:
         raise ValueError(f"{len(dims) - 2} hidden layers: 1..{NET_MAX_HIDDEN} are supported")
+    return dims
+
+
+def ppo_lds_bytes(actor_layers, critic_layers=None) -> int:
+    """Bytes of LDS the device PPO update needs for one member's actor / critic pair of a kind (ranenv_ppo_lds_bytes, the header's LDS
+    plan; at most 163 840): what decides, before anything is bound, whether an architecture can be a member of a device-trained
+    population.  ``actor_layers`` / ``critic_layers``: nets as for ``policy_net_layers``, or their widths ``[in, hidden..., out]``."""
+    mlps = []
+    for layers in (actor_layers, critic_layers):
+        if layers is None:
+            mlps.append(None)
+            continue
+        dims = _net_widths(layers)
+        mlp = _lib.Mlp()
+        mlp.n_hidden = len(dims) - 2
+        for i, d in enumerate(dims):
+            mlp.dims[i] = d
+        mlps.append(mlp)
     out = C.c_int64()
     lib = _lib.load()
-    _lib.check(lib, None, lib.ranenv_packed_net_floats(len(dims) - 2, (C.c_int32 * len(dims))(*dims), _lib.NET_PRECISIONS[precision], C.byref(out)),
-               "ranenv_packed_net_floats")
+    _lib.check(lib, None, lib.ranenv_ppo_lds_bytes(C.byref(mlps[0]), C.byref(mlps[1]) if mlps[1] is not None else None, C.byref(out)), "ranenv_ppo_lds_bytes")
     return out.value
 
 
@@ -668,6 +695,7 @@ class BatchedRanEnv:
                 "used": used.value}
 
     packed_net_floats = staticmethod(packed_net_floats)
+    ppo_lds_bytes = staticmethod(ppo_lds_bytes)
 
     def _gae_pairs(self, gamma, lam):
         """``collect`` / ``gae``: None for two scalars, else the members' (gamma [G], lam [G]) as float64 arrays -- a scalar beside a
@@ -813,11 +841,28 @@ class BatchedRanEnv:
     # ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
     PPO_STEPS_CAP = 1 << 13
 
-    def ppo_bind(self) -> None:
+    def ppo_bind(self, mixed: bool = False) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
-        one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header)."""
+        one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header).
+        ``mixed=True`` (ranenv_ppo_bind_mixed): the population was bound with ``mixed=True`` -- members of differing shape -- and
+        ``ppo_update`` trains each member on its own shape; every member's actor / critic pair must fit the LDS plan
+        (``ppo_lds_bytes``).  A mixed population is refused without it, a uniform one with it."""
         with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_ppo_bind(self._h, self._stream()), "ranenv_ppo_bind")
+            if mixed:
+                self._check(self._lib.ranenv_ppo_bind_mixed(self._h, self._stream()), "ranenv_ppo_bind_mixed")
+            else:
+                self._check(self._lib.ranenv_ppo_bind(self._h, self._stream()), "ranenv_ppo_bind")
+
+    def ppo_member_layout(self, m: int, kind: str = "inter") -> Dict[str, int]:
+        """What unpacks member ``m``'s block of ``ppo_update(grad=True)["grad"][m, kind]`` (ranenv_ppo_member_layout): the packed
+        floats of its "actor" and, behind them, its "critic" (0: none bound) of ``kind`` ("inter" / "intra"), and "lds_bytes", what
+        the update of that pair needs."""
+        if kind not in ("inter", "intra"):
+            raise ValueError('kind is "inter" or "intra"')
+        a, c, lds = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.ranenv_ppo_member_layout(self._h, int(m), 0 if kind == "inter" else 1, C.byref(a), C.byref(c), C.byref(lds)),
+                    "ranenv_ppo_member_layout")
+        return {"actor": a.value, "critic": c.value, "lds_bytes": lds.value}
 
     def _ppo_members(self) -> int:
         """Members the update trains: the population's while its inter actors are bound, else 1 (the library's own rule)."""

@@ -5,7 +5,8 @@ Seven objects, compiled in parallel, then linked:
   ranenv_aux.hip        the small kernels (class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination,
                         bf16 weight packing)
   ranenv_policy.hip     the policy networks (RANENV_POLICY_NETWORK: MLP forwards on the f32 matrix cores, or per net on the bf16 ones)
-  ranenv_ppo.hip        the PPO update of the bound nets (ranenv_ppo_update: forward, backward, clip and Adam, one workgroup per member)
+  ranenv_ppo.hip        the PPO update of the bound nets (ranenv_ppo_update: forward, backward, clip and Adam, one workgroup per member;
+                        its two kernels -- uniform and mixed populations -- expand one body, ranenv_ppo_body.hpp)
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants
@@ -23,7 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 HDR = os.path.join(REPO, "include", "ranenv.h")
 OUT = os.path.join(HERE, "libranenv_hip.so")
-SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
+SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_body.hpp", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
 # (object name, source, extra flags)
 UNITS = (("step_np10", "ranenv_step.hip", ("-DRANENV_NP=10",)), ("step_np8", "ranenv_step.hip", ("-DRANENV_NP=8",)),
          ("step_np16", "ranenv_step.hip", ("-DRANENV_NP=16",)), ("aux", "ranenv_aux.hip", ()),

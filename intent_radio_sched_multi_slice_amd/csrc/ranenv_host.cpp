@@ -152,6 +152,9 @@ struct ranenv {
     // ranenv_ppo_bind / ranenv_ppo_update: bound?, the (member, kind) step counters [POP_MAX][2], the call's hyper-parameters on the
     // device [POP_MAX], the diagnostic log-probability buffer the NEXT update takes and forgets
     bool ppo_on = false; int32_t *d_ppo_t = nullptr; ranenv_ppo_hparams *d_ppo_hp = nullptr; float *ppo_probe = nullptr;
+    // ranenv_ppo_bind_mixed: the binding trains a mixed population; the packed floats of member m's net of role r on the device,
+    // [4][POP_MAX] (0: the role is not bound), written at that bind and at every re-bind under it
+    bool ppo_mixed = false; long long *d_ppo_floats = nullptr, ppo_floats[4][POP_MAX] = {};      // (... and the host copy the upload reads)
     // ranenv_set_population_gae: a (gamma, lambda) pair per member for ranenv_collect's GAE pass
     bool gae_on = false; double gae_gamma[POP_MAX] = {}, gae_lambda[POP_MAX] = {};
     // The IBSched nets of a TTI's launches as they are bound (critics: a recording's), with the population map where a member's copy acts
@@ -1891,6 +1894,16 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
             return fail(h, RANENV_E_INVALID, "%s net of member %d: its packed copy has %lld floats, the member's extent %lld (the largest member's of the bind)",
                         who, member, floats, slot.member_stride);
     }
+    // while a mixed PPO binding is on, the member's new actor / critic pair of a kind keeps to the update's LDS plan: refused here, and
+    // the member's weights, moments and counter stay as they are
+    for (int k = 0; h->ppo_on && h->ppo_mixed && k < 2; k++) {
+        const ranenv::NetSlot &sa = h->nets[k][FORM_MEMBER], &sc = h->nets[2 + k][FORM_MEMBER];
+        if (!sa.on || (!given[k] && !given[2 + k])) continue;
+        const PolicyNet &a = given[k] ? ni[k] : sa.member[(size_t)member], *c = given[2 + k] ? &ni[2 + k] : (sc.on ? &sc.member[(size_t)member] : nullptr);
+        if (const size_t lds = ppo_lds_bytes(a, c); lds > (size_t)PPO_LDS_MAX)
+            return fail(h, RANENV_E_STATE, "member %d: its new %s nets need %zu bytes of LDS for their 32-row activations of all layers, the bound PPO update has %d",
+                        member, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+    }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     for (int r = 0; r < 4; r++) {
@@ -1912,6 +1925,7 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
         slot.member[(size_t)member] = ni[r];
         for (int l = 0; l < 6; l++) slot.member_dims[(size_t)member][(size_t)l] = m->dims[l];
         slot.derive();
+        if (const int rc = ppo_rebound(h, &slot, member, s); rc != RANENV_OK) return rc;
     }
     return RANENV_OK;
 }
@@ -1968,9 +1982,18 @@ int ranenv_set_population_gae(ranenv_handle h, int32_t n, const double *host_gam
 // ---- PPO update (include/ranenv.h "PPO update"; the kernel: ranenv_ppo.hip) -----------------------------------------------------
 static_assert(sizeof(ranenv_ppo_hparams) == RANENV_PPO_HPARAMS_BYTES, "ranenv_ppo_hparams: 8 doubles and 4 int32");
 
+// Member m's nets of kind k among the slots the update trains (ppo_roles): the packed floats of its actor and critic (0: none) and
+// the LDS bytes their update needs.  A uniform binding's members all have copy 0's shape.
+static void ppo_member_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, int m, int k, long long &actor_floats, long long &critic_floats, size_t &lds)
+{
+    const size_t i = mixed ? (size_t)m : 0;
+    const PolicyNet &a = slot[k]->member[i], *c = slot[2 + k] ? &slot[2 + k]->member[i] : nullptr;
+    actor_floats = net_floats(a); critic_floats = c ? net_floats(*c) : 0; lds = ppo_lds_bytes(a, c);
+}
+
 // The slots the update trains, by role number: the serving ones (null: none bound), and the member count -- or what ranenv_ppo_bind
-// refuses.  No device call.
-static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
+// (mixed: ranenv_ppo_bind_mixed, whose LDS plan holds per member) refuses.  No device call.
+static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false)
 {
     if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
     int n_pop = 0, n_one = 0;
@@ -1979,7 +2002,8 @@ static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
         if (slot[r] && slot[r]->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the PPO update does not train intra nets per slice (non-shared intra policies)");
         if (slot[r]) (slot[r]->form == FORM_MEMBER ? n_pop : n_one) += 1;
     }
-    if (h->pop_mixed()) return fail(h, RANENV_E_STATE, "the PPO update does not train a mixed population");
+    if (h->pop_mixed() && !mixed) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind does not train a mixed population: use ranenv_ppo_bind_mixed");
+    if (mixed && !h->pop_mixed()) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind_mixed trains a mixed population and no bound role is mixed: use ranenv_ppo_bind");
     if (!slot[0] || !slot[2]) return fail(h, RANENV_E_STATE, "the PPO update needs a bound inter actor and inter critic (ranenv_set_policy_network, ranenv_set_value_network)");
     if (n_pop && n_one) return fail(h, RANENV_E_STATE, "the PPO update needs every net per member or every net single: a net the members share has no one owner");
     members = n_pop ? h->pop.n : 1;
@@ -1987,10 +2011,28 @@ static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
         if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
     for (int k = 0; k < 2; k++) {
         if (!slot[k]) continue;
-        const size_t lds = ppo_lds_bytes(slot[k]->net, slot[2 + k] ? &slot[2 + k]->net : nullptr);
-        if (lds > (size_t)PPO_LDS_MAX)
+        for (int m = 0; m < (mixed ? members : 1); m++) {
+            long long af, cf; size_t lds;
+            ppo_member_shape(slot, mixed, m, k, af, cf, lds);
+            if (lds <= (size_t)PPO_LDS_MAX) continue;
+            if (mixed) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
             return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+        }
     }
+    return RANENV_OK;
+}
+
+// A mixed binding's per-member packed floats [4][POP_MAX] (0: the role is not bound) as the slots stand, to the device on the caller's stream
+static int ppo_floats_upload(ranenv_handle h, hipStream_t s)
+{
+    auto &f = h->ppo_floats;
+    memset(f, 0, sizeof(f));
+    for (int r = 0; r < 4; r++) {
+        const ranenv::NetSlot &slot = h->nets[r][FORM_MEMBER];
+        if (!slot.on) continue;
+        for (size_t m = 0; m < slot.member.size() && m < (size_t)POP_MAX; m++) f[r][m] = net_floats(slot.member[m]);
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_ppo_floats, f, sizeof(f), hipMemcpyHostToDevice, s));
     return RANENV_OK;
 }
 
@@ -2011,27 +2053,31 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
             HIP_TRY(h, hipMemsetAsync(x->opt, 0, sizeof(float) * 2 * (size_t)x->opt_cap, s));
             continue;
         }
-        const size_t at = (size_t)member * (size_t)x->member_stride, n = (size_t)net_floats(x->net);
+        // (a mixed binding: the member's WHOLE extent -- another shape moves every offset, and no moment of the old one may stay in the tail)
+        const size_t at = (size_t)member * (size_t)x->member_stride, n = (size_t)(h->ppo_mixed ? x->member_stride : net_floats(x->net));
         HIP_TRY(h, hipMemsetAsync(x->opt + at, 0, sizeof(float) * n, s));
         HIP_TRY(h, hipMemsetAsync(x->opt + x->opt_cap + at, 0, sizeof(float) * n, s));
     }
     if (member < 0) HIP_TRY(h, hipMemset2DAsync(h->d_ppo_t + kind, 2 * sizeof(int32_t), 0, sizeof(int32_t), POP_MAX, s));
     else HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + member * 2 + kind, 0, sizeof(int32_t), s));
-    return RANENV_OK;
+    return h->ppo_mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-int ranenv_ppo_bind(ranenv_handle h, void *stream)
+// ranenv_ppo_bind / ranenv_ppo_bind_mixed
+static int ppo_bind(ranenv_handle h, bool mixed, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    if (const int rc = ppo_roles(h, slot, members); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, slot, members, mixed); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     if (!h->d_ppo_t) {
         if (const int rc = dev_alloc(h, &h->d_ppo_t, (size_t)POP_MAX * 2); rc != RANENV_OK) return rc;
         if (const int rc = dev_alloc(h, &h->d_ppo_hp, (size_t)POP_MAX); rc != RANENV_OK) return rc;
     }
+    if (mixed && !h->d_ppo_floats)
+        if (const int rc = dev_alloc(h, &h->d_ppo_floats, (size_t)4 * POP_MAX); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipMemsetAsync(h->d_ppo_t, 0, sizeof(int32_t) * POP_MAX * 2, s));
     for (int r = 0; r < 4; r++) {
         if (!slot[r]) continue;
@@ -2041,15 +2087,18 @@ int ranenv_ppo_bind(ranenv_handle h, void *stream)
         }
         HIP_TRY(h, hipMemsetAsync(slot[r]->opt, 0, sizeof(float) * 3 * (size_t)slot[r]->opt_cap, s));
     }
-    h->ppo_on = true;
-    return RANENV_OK;
+    h->ppo_on = true; h->ppo_mixed = mixed;
+    return mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-// The bound state behind ranenv_ppo_bind, or RANENV_E_STATE
+int ranenv_ppo_bind(ranenv_handle h, void *stream) { return ppo_bind(h, false, stream); }
+int ranenv_ppo_bind_mixed(ranenv_handle h, void *stream) { return ppo_bind(h, true, stream); }
+
+// The bound state behind ranenv_ppo_bind / _bind_mixed, or RANENV_E_STATE
 static int ppo_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
 {
     if (!h->ppo_on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
-    if (const int rc = ppo_roles(h, slot, members); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, slot, members, h->ppo_mixed); rc != RANENV_OK) return rc;
     for (int r = 0; r < 4; r++)
         if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after ranenv_ppo_bind: bind again", NET_ROLES[r].who);
     return RANENV_OK;
@@ -2070,17 +2119,57 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    if (const int rc = ppo_roles(h, slot, members); rc != RANENV_OK) return rc;
+    const bool mixed = h->pop_mixed();
+    if (const int rc = ppo_roles(h, slot, members, mixed); rc != RANENV_OK) return rc;
     long long g = 0; size_t lds = 0;
     for (int k = 0; k < 2; k++) {
         if (!slot[k]) continue;
-        const long long f = net_floats(slot[k]->net) + (slot[2 + k] ? net_floats(slot[2 + k]->net) : 0);
-        g = f > g ? f : g;
-        const size_t l = ppo_lds_bytes(slot[k]->net, slot[2 + k] ? &slot[2 + k]->net : nullptr);
-        lds = l > lds ? l : lds;
+        for (int m = 0; m < (mixed ? members : 1); m++) {
+            long long af, cf; size_t l;
+            ppo_member_shape(slot, mixed, m, k, af, cf, l);
+            g = af + cf > g ? af + cf : g;
+            lds = l > lds ? l : lds;
+        }
     }
     if (grad_floats) *grad_floats = g;
     if (lds_bytes) *lds_bytes = (int64_t)lds;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int64_t *actor_floats, int64_t *critic_floats, int64_t *lds_bytes)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    ranenv::NetSlot *slot[4];
+    int members = 0;
+    const bool mixed = h->pop_mixed();
+    if (const int rc = ppo_roles(h, slot, members, mixed); rc != RANENV_OK) return rc;
+    if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
+    if (kind != 0 && kind != 1) return fail(h, RANENV_E_INVALID, "kind %d (0 inter, 1 intra)", kind);
+    if (!slot[kind]) return fail(h, RANENV_E_STATE, "no %s actor bound", kind ? "intra" : "inter");
+    long long af, cf; size_t lds;
+    ppo_member_shape(slot, mixed, member, kind, af, cf, lds);
+    if (actor_floats) *actor_floats = af;
+    if (critic_floats) *critic_floats = cf;
+    if (lds_bytes) *lds_bytes = (int64_t)lds;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *bytes)
+{
+    if (!actor || !bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    PolicyNet net[2] = {};
+    const ranenv_mlp *given[2] = {actor, critic};
+    for (int i = 0; i < 2; i++) {
+        const ranenv_mlp *m = given[i];
+        if (!m) continue;
+        if (m->n_hidden < 1 || m->n_hidden > NET_MAX_LAYERS - 1) return fail(nullptr, RANENV_E_INVALID, "%d hidden layers (1..%d)", m->n_hidden, NET_MAX_LAYERS - 1);
+        if (m->dims[0] < 1 || m->dims[m->n_hidden + 1] < 1) return fail(nullptr, RANENV_E_INVALID, "input width %d, output width %d", m->dims[0], m->dims[m->n_hidden + 1]);
+        for (int l = 1; l <= m->n_hidden; l++)
+            if (m->dims[l] < 1 || m->dims[l] > NET_MAX_WIDTH) return fail(nullptr, RANENV_E_INVALID, "hidden width %d (1..%d)", m->dims[l], NET_MAX_WIDTH);
+        net[i].n_layers = m->n_hidden + 1;
+        net_pack(m->dims, net[i].n_layers, RANENV_NET_F32, net[i], 0);
+    }
+    *bytes = (int64_t)ppo_lds_bytes(net[0], critic ? &net[1] : nullptr);
     return RANENV_OK;
 }
 
@@ -2097,7 +2186,7 @@ int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_
     if (dev_m) *dev_m = slot[role]->opt + at;
     if (dev_v) *dev_v = slot[role]->opt + slot[role]->opt_cap + at;
     if (dev_t) *dev_t = h->d_ppo_t + member * 2 + (role & 1);
-    if (floats) *floats = net_floats(slot[role]->net);
+    if (floats) *floats = net_floats(slot[role]->member[h->ppo_mixed ? (size_t)member : 0]);
     return RANENV_OK;
 }
 
@@ -2129,6 +2218,7 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
         if (hp[m].epochs < 0) return fail(h, RANENV_E_INVALID, "member %d: epochs %d (>= 0)", m, hp[m].epochs);
         max_epochs = hp[m].epochs > max_epochs ? hp[m].epochs : max_epochs;
     }
+    const bool mixed = h->ppo_mixed;
     if (!traj->obs_inter || !traj->mask_inter || !traj->action_inter || !traj->logp || !traj->adv || !traj->vtarg)
         return fail(h, RANENV_E_INVALID, "the record needs obs_inter, mask_inter, action_inter, logp, adv and vtarg");
     if (intra && (!traj->obs_intra || !traj->action_intra || (slot[1]->net.layout == RANENV_NET_IN_MASK_OBS && !traj->mask_intra)))
@@ -2148,21 +2238,29 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
     if (max_epochs == 0) return RANENV_OK;
     a.T = n_steps; a.B = h->cfg.batch; a.S = h->cfg.n_slices; a.Us = h->cfg.max_ues_slice; a.W = 2 * a.Us + 9;
     a.hp = h->d_ppo_hp; a.traj = *traj; a.t = h->d_ppo_t; a.max_epochs = max_epochs; a.stats = stats; a.grad = grad; a.probe_logp = probe_logp;
+    // The launch's LDS: the largest need over the kinds this call updates (a mixed binding: and over the members).  dev_grad's stride
+    // is ranenv_ppo_layout's: the largest of the BOUND nets, whether or not this call updates the intra kind
     long long gf = 0; size_t lds = 0;
     for (int k = 0; k < 2; k++) {
-        if (a.net[k][0].net.n_layers == 0) continue;
-        const long long f = a.net[k][0].floats + a.net[k][1].floats;
-        gf = f > gf ? f : gf;
-        const size_t l = ppo_lds_bytes(a.net[k][0].net, a.net[k][1].net.n_layers > 0 ? &a.net[k][1].net : nullptr);
-        lds = l > lds ? l : lds;
+        if (!slot[k]) continue;
+        for (int m = 0; m < (mixed ? members : 1); m++) {
+            long long af, cf; size_t l;
+            ppo_member_shape(slot, mixed, m, k, af, cf, l);
+            gf = af + cf > gf ? af + cf : gf;
+            if (a.net[k][0].net.n_layers > 0) lds = l > lds ? l : lds;
+        }
     }
-    // (dev_grad's stride is ranenv_ppo_layout's: the larger kind's of the BOUND nets, whether or not this call updates the intra kind)
-    if (slot[1]) { const long long f = net_floats(slot[1]->net) + (slot[3] ? net_floats(slot[3]->net) : 0); gf = f > gf ? f : gf; }
     a.grad_stride = gf;
+    PpoMixed x{};
+    if (mixed) {        // (every bound role is the population's: its table; the others the table of zeros)
+        for (int k = 0; k < 2; k++)
+            for (int i = 0; i < 2; i++) x.tab[k][i] = h->d_pop_tab + (slot[2 * i + k] ? 2 * i + k : 4) * POP_MAX;
+        x.floats = h->d_ppo_floats;
+    }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)members, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_ppo_update(s, members, lds, a));
+    HIP_TRY(h, launch_ppo_update(s, members, lds, a, mixed ? &x : nullptr));
     return RANENV_OK;
 }
 

@@ -276,7 +276,13 @@ struct PpoArgs {
 // Bytes of LDS the update of this actor / critic pair needs (critic null or n_layers 0: none); the rule is in include/ranenv.h
 size_t ppo_lds_bytes(const PolicyNet &actor, const PolicyNet *critic);
 enum { PPO_LDS_MAX = 160 * 1024 };
-hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoArgs &);
+// A mixed population's update (ranenv_ppo_bind_mixed), beside PpoArgs: workgroup (m, kind) takes net k's shape from entry m of tab[kind][k]
+// -- the role's device table the mixed policy kernels read, or the table of zeros for a role that is not bound -- and its packed floats
+// from floats[role * POP_MAX + m] (device, written at bind and re-bind; 0: not bound).  PpoNet's net / floats are member 0's there:
+// read for "is the role bound" alone.  lds: the largest ppo_lds_bytes over the members and the kinds of the call.
+struct PpoMixed { const PolicyNet *tab[2][2]; const long long *floats; };
+// mixed null: the uniform instance
+hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoArgs &, const PpoMixed *mixed);
 
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block
