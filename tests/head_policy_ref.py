@@ -134,20 +134,25 @@ SIZES = {"S10U100": dict(n_slices=10, n_ues=100, n_rbs=135, rbs_per_rbg=1, max_u
 EPISODE_LENGTHS = (5, 7, 8, 12, 24, 6)      # per env, cyclic: episodes end at different TTIs, several at TTI 24
 
 
+def size_of(size):
+    """The make_mult_slice_workload keywords of ``size``: a name of SIZES, or such a dict itself (tests/head_shapes_ref.py's grid)."""
+    return SIZES[size] if isinstance(size, str) else dict(size)
+
+
 def usecase_of(tables, seed=3):
     return (np.random.default_rng(seed).integers(0, 4, tables.slice_active.shape) * (tables.slice_has_req != 0)).astype(np.int32)
 
 
 def make_env(size, net, dist, B, stochastic=True, seed=11, autoreset=False, parts=1, se_mode="stream", critic=True, metrics=None,
              unsorted=True, trace_len=64, bind=True):
-    """A reset env with heads enabled under the head nets of (size, net, dist).  ``unsorted``: the scenario tables are reloaded with
+    """A reset env with heads enabled under the head nets of (size, net, dist); ``size`` as for size_of.  ``unsorted``: the scenario tables are reloaded with
     sorted_slices = identity (SchedTWC's enable_sort_slices=False), else left sorted and bound with allow_sorted.  ``metrics``:
     episode slots of enable_metrics (None: off).  autoreset: per-env episode lengths EPISODE_LENGTHS.
     Returns (workload, env, (actor, log_std, critic))."""
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     wl = make_mult_slice_workload(B, torch.device("cuda", 0), policy=_lib.POLICY_MAPF, intra=_lib.INTRA_RR, n_scenarios=8, n_traces=8,
-                                  trace_len=trace_len, max_steps=1000, **SIZES[size])
+                                  trace_len=trace_len, max_steps=1000, **size_of(size))
     env = wl.env
     if unsorted:
         wl.tables.sorted_slices[...] = np.arange(env.S, dtype=np.int32)

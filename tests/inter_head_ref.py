@@ -19,16 +19,16 @@ EPISODE_LENGTHS = hr.EPISODE_LENGTHS
 
 def make_env(size, net, dist, batch=B, stochastic=True, seed=11, autoreset=False, parts=1, se_mode="stream", critic=True, metrics=None,
              heads=False, intra=None, trace_len=64, bind=True, observation="inter"):
-    """A reset env on sorted scenario tables under the head nets of (size, net, dist) with ``observation`` as their source.
+    """A reset env on sorted scenario tables (S = 1 has nothing to sort) under the head nets of (size, net, dist; ``size`` as for hr.size_of) with ``observation`` as their source.
     ``heads``: head outputs bound as well (enable_heads, before the nets).  ``intra``: fixed_intra (None: round-robin).
     autoreset: per-env episode lengths EPISODE_LENGTHS.  Returns (workload, env, (actor, log_std, critic))."""
     from intent_radio_sched_multi_slice_amd import _lib
     from intent_radio_sched_multi_slice_amd.workloads import make_mult_slice_workload
     wl = make_mult_slice_workload(batch, torch.device("cuda", 0), policy=_lib.POLICY_MAPF, intra=_lib.INTRA_RR, n_scenarios=8, n_traces=8,
-                                  trace_len=trace_len, max_steps=1000, **SIZES[size])
+                                  trace_len=trace_len, max_steps=1000, **hr.size_of(size))
     env = wl.env
     ss = np.asarray(wl.tables.sorted_slices)
-    assert not np.array_equal(ss, np.broadcast_to(np.arange(ss.shape[-1]), ss.shape)), "the tables do not sort the slices"
+    assert ss.shape[-1] == 1 or not np.array_equal(ss, np.broadcast_to(np.arange(ss.shape[-1]), ss.shape)), "the tables do not sort the slices"
     env.set_se_mode(se_mode)
     if heads or observation == "head":
         env.enable_heads(hr.usecase_of(wl.tables))
