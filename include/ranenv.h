@@ -214,11 +214,20 @@ int ranenv_se_retile_quad(const float *dev_rb_major, float *dev_quad, int64_t n_
  * ranenv_member_line_plan (host arithmetic only): returns the lines per UE for a row of n_rbs RBs (< 0: error) and fills, for up to
  * max_lines of them, the line's leaf, its first RB and the whole groups it holds (0 = the tail line); any of the arrays may be NULL.
  * ranenv_member_lines_row_sums_host (host arithmetic only): one UE's lines summed in the kernels' own order -- full = the sum over
- * all RBs, part = over [rb_start, rb_start + rb_count) -- in float64: bit for bit np.sum of the float32 row as float64. */
+ * all RBs, part = over [rb_start, rb_start + rb_count) -- in float64: bit for bit np.sum of the float32 row as float64.
+ * ranenv_member_serving_order (host arithmetic only): the order in which a wave of the step kernel serves its lanes' member rows, 8
+ * per pass.  member_mask / holder_mask: bit l = lane l holds a slice member / a member with rb_count > 0 at this TTI (a holder that
+ * is no member is an error); lines_per_ue as ranenv_member_line_plan returns it; dq = lines the kernel requests per lane ahead of the
+ * allocation (4).  The lanes of the first P0 = ceil(dq / lines_per_ue) passes keep slot = lane (their lines are requested before the
+ * ranges are known; P0 > 8 is an error); behind them come the holders in lane order, then the members without an RB in lane order,
+ * then the lanes without a member.  slots[64] receives every lane's slot (pass slot / 8, cluster slot % 8), *masked_passes the
+ * passes that keep the masked sum: min(P0 + ceil(holders behind the prefix / 8), ceil((highest member lane + 1) / 8)); the passes
+ * behind them serve members without an RB only and add the full sum alone (their masked sum is +0.0). */
 int ranenv_se_retile_member_lines(const float *dev_pool, int32_t quad, int64_t tile_stride, float *dev_lines, int64_t n_tiles, int32_t n_ues,
                                   int32_t n_rbs, void *stream);
 int ranenv_member_line_plan(int32_t n_rbs, int32_t max_lines, int32_t *leaf, int32_t *first_rb, int32_t *groups);
 int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part);
+int ranenv_member_serving_order(uint64_t member_mask, uint64_t holder_mask, int32_t lines_per_ue, int32_t dq, int32_t *slots, int32_t *masked_passes);
 /* Traffic pool: int32 offered bits, row i = [U] at dev + i*U. */
 int ranenv_bind_traffic_pool(ranenv_handle h, const int32_t *dev_pool, int64_t n_rows);
 

@@ -1368,6 +1368,30 @@ int ranenv_member_line_plan(int32_t n_rbs, int32_t max_lines, int32_t *leaf, int
     return (int)plan.size();
 }
 
+// (restates member_line_sums' serving slots, ranenv_numeric.hpp: prefix lanes keep their number, then holders, members, the rest)
+int ranenv_member_serving_order(uint64_t member_mask, uint64_t holder_mask, int32_t lines_per_ue, int32_t dq, int32_t *slots, int32_t *masked_passes)
+{
+    if (!slots || !masked_passes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (lines_per_ue < 1 || dq < 1 || (holder_mask & ~member_mask) != 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes, or a holder that is no member");
+    const int p0 = (dq + lines_per_ue - 1) / lines_per_ue;
+    if (p0 > 8) return fail(nullptr, RANENV_E_INVALID, "dq %d at %d lines per UE: the prefix exceeds the wave", (int)dq, (int)lines_per_ue);
+    const int pre = p0 * 8;
+    int top = 0;
+    for (int l = 0; l < 64; l++) if (member_mask >> l & 1) top = l + 1;
+    int next = pre;
+    for (int l = 0; l < pre; l++) slots[l] = l;
+    for (int group = 0; group < 3; group++)          // holders, members without an RB, lanes without a member
+        for (int l = pre; l < 64; l++) {
+            const bool m = member_mask >> l & 1, hd = holder_mask >> l & 1;
+            if ((group == 0 && hd) || (group == 1 && m && !hd) || (group == 2 && !m)) slots[l] = next++;
+        }
+    int holders_behind = 0;
+    for (int l = pre; l < 64; l++) holders_behind += (int)(holder_mask >> l & 1);
+    const int passes = (top + 7) / 8, want = p0 + (holders_behind + 7) / 8;
+    *masked_passes = want < passes ? want : passes;
+    return RANENV_OK;
+}
+
 int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part)
 {
     if (!row_lines || !full || !part) return fail(nullptr, RANENV_E_INVALID, "null argument");

@@ -389,6 +389,22 @@ struct MemberLines {
     }
 };
 
+// The serving order (ranenv_member_serving_order restates it on the host).  init() requests the first DQ lines before the
+// allocation, when nobody knows the ranges: they belong to the first P0 = ceil(DQ / nl) passes, whose lanes 0 .. 8 P0 - 1 keep
+// slot = lane.  Behind that prefix the lanes are served holders first: members with rb_count > 0 in lane order, then members
+// without an RB in lane order, then the lanes without a member -- slot = rank within the group behind the groups in front (two
+// ballots, mbcnt).  Every lane pushes its row offset and its packed range to lane `slot` (ds_permute), pass q serves slots
+// 8 q .. 8 q + 7 from those copies, and the owner takes its sums back from cluster slot & 7 at the end of pass slot >> 3.  The
+// first M = P0 + ceil(holders behind the prefix / 8) passes (at most all of them) serve every holder; the passes behind them serve
+// members without an RB only and run the sum-only body: converts, f +=, the f tree, the f folds and the f tail -- no g, no
+// range word, no compare.  Exact: a member's `full` and `part` depend on its own lines and its own range alone, never on the
+// cluster or the pass that serves it, and the additions, their order, the tree and the folds per member are what they were;
+// for rb_count == 0 every fma(d, 0.0, g) leaves g at +0.0 (the SE is finite, and an accumulator that starts at +0.0 never
+// becomes -0.0), so the +0.0 that `part` keeps there is the masked body's result bit for bit.  The queue's slots are compile-time
+// registers, so the bodies change at a queue turn: the first turn that starts at or behind line M nl (the lines of members
+// without an RB in front of it run the masked body, which is exact for them as well).
+template <int DQ> DEVFN int member_prefix_passes(int nl) { return (DQ + nl - 1) / nl; }
+
 // `full` / `part` of this lane's member row (0 for a lane without one), bit for bit row_sums' over the range [s, s + c).
 // `after_issue`: as in row_sums, once, in front of the last turn of the queue.
 template <int DQ, typename Hook>
@@ -398,28 +414,56 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
     const RowPlan pl = st.pl;
     const int tail = R & 7, nl = st.nl, total = st.total;
     const int j = (int)(threadIdx.x & 7u), cluster = (int)((threadIdx.x & 63u) >> 3);
+    // ---- serving slots ----
+    const int lane = (int)(threadIdx.x & 63u);
+    const bool member = st.my_voff != MemberLines<DQ>::OOB;
+    const int pre = member_prefix_passes<DQ>(nl) * 8;                      // <= 32 (DQ <= 4 passes of one line)
+    const unsigned long long behind = ~0ull << pre;
+    const unsigned long long hb = __builtin_amdgcn_ballot_w64(member && c > 0) & behind;
+    const unsigned long long mb = __builtin_amdgcn_ballot_w64(member && c == 0) & behind;
+    const unsigned long long nb = behind & ~(hb | mb);
+    auto rank = [](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
+    const int nh = __builtin_popcountll(hb), nm = __builtin_popcountll(mb);
+    int slot = lane;
+    if (lane >= pre) slot = pre + (!member ? nh + nm + rank(nb) : (c > 0 ? rank(hb) : nh + rank(mb)));
     const int my_sc = (int)(s | (c << 16));               // (R <= 512: both fit 16 bits)
+    // (push: lane `slot` receives this lane's words; the slots are a permutation of the wave, so every lane receives one)
+    st.my_voff = (unsigned)__builtin_amdgcn_ds_permute(slot * 4, (int)st.my_voff);
+    const int slot_sc = __builtin_amdgcn_ds_permute(slot * 4, my_sc);
+    const int my_pass = slot >> 3, my_from = (slot & 7) * 32 + (tail > 0 ? 4 : 0);
+#if RANENV_DIAG == 11      /* ablation 11: the full sum alone, for every pass (timing only: `part` is wrong) */
+    const int sum_only_from = 0;
+#else
+    const int passes = total / nl, m_want = pre / 8 + ((nh + 7) >> 3);
+    const int masked_lines = (m_want < passes ? m_want : passes) * nl;
+    const int sum_only_from = ((masked_lines + DQ - 1) / DQ) * DQ;          // the first queue turn without a holder's line
+#endif
     double f = 0.0, g = 0.0, fr = 0.0, gr = 0.0, lf = 0.0, lg = 0.0, rf = 0.0, rg = 0.0;
     int cq = 0, cl = 0, leaf = 0, left = 0, rb0 = 0, leaf_end = 0;      // wave-uniform cursor: pass, line, leaf, lines left in it, the line's first RB
     int tj = 0; unsigned oc = 0;                                          // the served member's range: j - rb_start, rb_count
     auto len_of = [&](int k) { return (k == 0) * pl.len0 + (k == 1) * pl.len1 + (k == 2) * pl.len2 + (k == 3) * pl.len3; };
-    auto fold = [&](int k) {
-        const bool left_half = pl.lsplit ? (k < 2) : (k < 1);
-        const bool first = pl.lsplit ? (k == 0 || k == 2) : (k <= 1);
-        if (left_half) { if (first) { lf = fr; lg = gr; } else { lf = lf + fr; lg = lg + gr; } }
-        else           { if (first) { rf = fr; rg = gr; } else { rf = rf + fr; rg = rg + gr; } }
-    };
     auto tree = [](double v) {
         v = v + dpp_f64<0xB1>(v);           // quad_perm [1,0,3,2]: lane ^ 1
         v = v + dpp_f64<0x4E>(v);           // quad_perm [2,3,0,1]: lane ^ 2
         return v + dpp_f64<0x141>(v);       // row_half_mirror: the other quad of the 8 (every lane of a quad holds the quad's sum)
     };
     full = 0.0; part = 0.0;
-    auto consume = [&](const v4f x) {
+    // MASKED = false: the sum-only body (everything of g's side is gone, `part` keeps its +0.0)
+    auto consume = [&](const v4f x, auto masked_tag) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        auto fold = [&](int k) {
+            const bool left_half = pl.lsplit ? (k < 2) : (k < 1);
+            const bool first = pl.lsplit ? (k == 0 || k == 2) : (k <= 1);
+            if (left_half) { if (first) { lf = fr; if (MASKED) lg = gr; } else { lf = lf + fr; if (MASKED) lg = lg + gr; } }
+            else           { if (first) { rf = fr; if (MASKED) rg = gr; } else { rf = rf + fr; if (MASKED) rg = rg + gr; } }
+        };
         if (cl == 0) {
-            const int sc = __builtin_amdgcn_ds_bpermute((cq * 8 + cluster) * 4, my_sc);
-            tj = j - (sc & 0xffff); oc = (unsigned)sc >> 16;
-            leaf = 0; left = member_line_chunks(pl.len0); rb0 = 0; leaf_end = pl.len0; fr = 0.0; gr = 0.0;
+            if constexpr (MASKED) {
+                const int sc = __builtin_amdgcn_ds_bpermute((cq * 8 + cluster) * 4, slot_sc);
+                tj = j - (sc & 0xffff); oc = (unsigned)sc >> 16;
+                gr = 0.0;
+            }
+            leaf = 0; left = member_line_chunks(pl.len0); rb0 = 0; leaf_end = pl.len0; fr = 0.0;
         }
         if (tail > 0 && cl == nl - 1) {
             // the row's last R mod 8 RBs, one after the other behind the tree: positions 0..3 are the cluster's first lane's, 4..6 its
@@ -432,19 +476,21 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
                 if (k < tail) {
                     const double d = (double)e[k];
                     a += d;
-                    b = fma(d, (unsigned)(t0 + k) < oc ? 1.0 : 0.0, b);
+                    if constexpr (MASKED) b = fma(d, (unsigned)(t0 + k) < oc ? 1.0 : 0.0, b);
                 }
             }
-            a = dpp_f64<0xA0>(a); b = dpp_f64<0xA0>(b);      // quad_perm [0,0,2,2]: the first lane's sums, in the second lane
+            a = dpp_f64<0xA0>(a);                            // quad_perm [0,0,2,2]: the first lane's sums, in the second lane
+            if constexpr (MASKED) b = dpp_f64<0xA0>(b);
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 if (4 + k < tail) {
                     const double d = (double)e[k];
                     a += d;
-                    b = fma(d, (unsigned)(t0 + 4 + k) < oc ? 1.0 : 0.0, b);
+                    if constexpr (MASKED) b = fma(d, (unsigned)(t0 + 4 + k) < oc ? 1.0 : 0.0, b);
                 }
             }
-            fr = a; gr = b;
+            fr = a;
+            if constexpr (MASKED) gr = b;
             fold(pl.n_leaves - 1);
         } else {
             const float e[4] = {x.x, x.y, x.z, x.w};
@@ -452,40 +498,49 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
             for (int k = 0; k < 4; k++) {
                 const double d = (double)e[k];
                 f += d;
-                g = fma(d, (unsigned)(tj + rb0 + 8 * k) < oc ? 1.0 : 0.0, g);
+                if constexpr (MASKED) g = fma(d, (unsigned)(tj + rb0 + 8 * k) < oc ? 1.0 : 0.0, g);
             }
             rb0 += 32;
             if (--left == 0) {
-                fr = tree(f); gr = tree(g);
-                f = 0.0; g = 0.0;
+                fr = tree(f);
+                f = 0.0;
+                if constexpr (MASKED) { gr = tree(g); g = 0.0; }
                 if (!(leaf == pl.n_leaves - 1 && tail > 0)) fold(leaf);
                 leaf += 1;
                 left = member_line_chunks(len_of(leaf)); rb0 = leaf_end; leaf_end += len_of(leaf);
             }
         }
         if (++cl == nl) {
-            // back to the owner: lane 8 cq + i takes the sums of cluster i from that cluster's first lane -- its second where a tail line
-            // ended the row there (without one every lane of the cluster holds the sums)
-            const double fv = pl.n_leaves == 1 ? lf : lf + rf, gv = pl.n_leaves == 1 ? lg : lg + rg;
-            const int from = j * 32 + (tail > 0 ? 4 : 0);
-            const double fo = lane_f64(fv, from), go = lane_f64(gv, from);
-            if (cluster == cq) { full = fo; part = go; }
+            // back to the owner: the lane with slot 8 cq + i takes the sums of cluster i from that cluster's first lane -- its second
+            // where a tail line ended the row there (without one every lane of the cluster holds the sums)
+            const double fv = pl.n_leaves == 1 ? lf : lf + rf;
+            const double fo = lane_f64(fv, my_from);
+            if (my_pass == cq) full = fo;
+            if constexpr (MASKED) {
+                const double gv = pl.n_leaves == 1 ? lg : lg + rg;
+                const double go = lane_f64(gv, my_from);
+                if (my_pass == cq) part = go;
+            }
             cl = 0; cq += 1;
         }
     };
     bool hooked = false;
-#pragma unroll 1
-    for (int base = 0; base < total; base += DQ) {
+    auto turn = [&](int base, auto masked_tag) {
         if (base + DQ >= total) { after_issue(); hooked = true; }
 #pragma unroll
         for (int d = 0; d < DQ; d++) {
             if (base + d < total) {
                 const v4f x = st.q[d];
                 if (base + d + DQ < total) st.issue(st.q[d]);
-                consume(x);
+                consume(x, masked_tag);
             }
         }
-    }
+    };
+    int base = 0;
+#pragma unroll 1
+    for (; base < total && base < sum_only_from; base += DQ) turn(base, std::true_type());
+#pragma unroll 1
+    for (; base < total; base += DQ) turn(base, std::false_type());
     if (!hooked) after_issue();
 }
 
