@@ -213,11 +213,20 @@ int ranenv_se_retile_quad(const float *dev_rb_major, float *dev_quad, int64_t n_
  * pool, tiles tile_stride floats apart; dev_lines [n_tiles][U][lines][32], 16-byte aligned.
  * ranenv_member_line_plan (host arithmetic only): returns the lines per UE for a row of n_rbs RBs (< 0: error) and fills, for up to
  * max_lines of them, the line's leaf, its first RB and the whole groups it holds (0 = the tail line); any of the arrays may be NULL.
- * ranenv_member_lines_row_sums_host (host arithmetic only): one UE's lines summed in the kernels' own order -- full = the sum over
- * all RBs, part = over [rb_start, rb_start + rb_count) -- in float64: bit for bit np.sum of the float32 row as float64.
+ * ranenv_member_lines_row_sums_host (host arithmetic only): one UE's lines summed line by line, the tail line included -- full =
+ * the sum over all RBs, part = over [rb_start, rb_start + rb_count) -- in float64: bit for bit np.sum of the float32 row as float64.
+ * The step kernels do NOT walk the tail line with their clusters of eight lanes: a cluster walks a UE's whole-group lines only
+ * (lines_per_ue - 1 of them when R mod 8 != 0: R = 135 walks 4) and hands back, per sum, the folded left half A (rows of more than
+ * one leaf), the right half's first leaf B (a split right half only) and the tree T of the last leaf's whole groups (+0.0 if none);
+ * the lane that owns the member loads the first 32 bytes of its tail line itself and finishes in numpy's order: T + e0 + ... one after
+ * the other, then t | A + t | A + (B + t), the masked sum likewise over its own range.  Same additions, same grouping, same bits.
+ * ranenv_member_lines_owner_tail_sums_host (host arithmetic only) restates exactly that in plain C++ -- the cluster's part over the
+ * whole-group lines, then the owner's finish over the tail line's first R mod 8 floats (numpy's recursion to any depth: one left
+ * sibling per level of the right spine) -- and returns full, part and *walked_lines, the lines per UE the clusters walk.
  * ranenv_member_serving_order (host arithmetic only): the order in which a wave of the step kernel serves its lanes' member rows, 8
  * per pass.  member_mask / holder_mask: bit l = lane l holds a slice member / a member with rb_count > 0 at this TTI (a holder that
- * is no member is an error); lines_per_ue as ranenv_member_line_plan returns it; dq = lines the kernel requests per lane ahead of the
+ * is no member is an error); lines_per_ue = the lines per UE the kernel WALKS -- the plan's lines without the tail line, as
+ * ranenv_member_lines_owner_tail_sums_host returns them (the arithmetic is the same for any count >= 1) --; dq = lines the kernel requests per lane ahead of the
  * allocation (4).  The lanes of the first P0 = ceil(dq / lines_per_ue) passes keep slot = lane (their lines are requested before the
  * ranges are known; P0 > 8 is an error); behind them come the holders in lane order, then the members without an RB in lane order,
  * then the lanes without a member.  slots[64] receives every lane's slot (pass slot / 8, cluster slot % 8), *masked_passes the
@@ -227,6 +236,8 @@ int ranenv_se_retile_member_lines(const float *dev_pool, int32_t quad, int64_t t
                                   int32_t n_rbs, void *stream);
 int ranenv_member_line_plan(int32_t n_rbs, int32_t max_lines, int32_t *leaf, int32_t *first_rb, int32_t *groups);
 int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part);
+int ranenv_member_lines_owner_tail_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part,
+                                             int32_t *walked_lines);
 int ranenv_member_serving_order(uint64_t member_mask, uint64_t holder_mask, int32_t lines_per_ue, int32_t dq, int32_t *slots, int32_t *masked_passes);
 /* Traffic pool: int32 offered bits, row i = [U] at dev + i*U. */
 int ranenv_bind_traffic_pool(ranenv_handle h, const int32_t *dev_pool, int64_t n_rows);

@@ -860,6 +860,24 @@ bool member_line_table(int R, MemberLineTable *tb)
     for (size_t l = 0; l < plan.size(); l++) { tb->rb0[l] = plan[l].rb0; tb->groups[l] = plan[l].groups; }
     return true;
 }
+// The whole 8-RB groups of the leaf [lo, lo + n), n <= 128, from the lines at `line` on (advanced): a cluster's part of a leaf -- per
+// accumulator j the four elements of a line one after the other, then the tree (+0.0 for a leaf without a whole group)
+void member_leaf_groups(const float *&line, int lo, int n, unsigned s, unsigned c, double &fr, double &gr)
+{
+    auto in = [&](int r) { return ((unsigned)r - s) < c ? 1.0 : 0.0; };
+    double f[8], g[8];
+    for (int j = 0; j < 8; j++) { f[j] = 0.0; g[j] = 0.0; }
+    const int G = n >> 3;
+    for (int c4 = 0; 4 * c4 < G; c4++, line += 32)
+        for (int j = 0; j < 8; j++)
+            for (int k = 0; k < 4; k++) {
+                const double d = (double)line[4 * j + k];
+                f[j] += d;
+                g[j] = std::fma(d, in(lo + 8 * (4 * c4 + k) + j), g[j]);
+            }
+    fr = ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
+    gr = ((g[0] + g[1]) + (g[2] + g[3])) + ((g[4] + g[5]) + (g[6] + g[7]));
+}
 // `full` / `part` of rows [lo, lo + n) from the lines at `line` on (advanced), added in the kernel's order: per accumulator j the four
 // elements of a line one after the other, the leaf's tree, the tail sequentially, the halves as numpy's recursion folds them
 void member_lines_pairwise(const float *&line, int lo, int n, unsigned s, unsigned c, double &full, double &part)
@@ -872,18 +890,9 @@ void member_lines_pairwise(const float *&line, int lo, int n, unsigned s, unsign
         return;
     }
     auto in = [&](int r) { return ((unsigned)r - s) < c ? 1.0 : 0.0; };
-    double f[8], g[8];
-    for (int j = 0; j < 8; j++) { f[j] = 0.0; g[j] = 0.0; }
     const int G = n >> 3, tail = n & 7;
-    for (int c4 = 0; 4 * c4 < G; c4++, line += 32)
-        for (int j = 0; j < 8; j++)
-            for (int k = 0; k < 4; k++) {
-                const double d = (double)line[4 * j + k];
-                f[j] += d;
-                g[j] = std::fma(d, in(lo + 8 * (4 * c4 + k) + j), g[j]);
-            }
-    double fr = ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
-    double gr = ((g[0] + g[1]) + (g[2] + g[3])) + ((g[4] + g[5]) + (g[6] + g[7]));
+    double fr, gr;
+    member_leaf_groups(line, lo, n, s, c, fr, gr);
     if (tail > 0) {
         for (int k = 0; k < tail; k++) { const double d = (double)line[k]; fr += d; gr = std::fma(d, in(lo + 8 * G + k), gr); }
         line += 32;
@@ -1398,6 +1407,40 @@ int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int
     if (n_rbs < 1 || rb_start < 0 || rb_count < 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
     const float *line = row_lines;
     member_lines_pairwise(line, 0, (int)n_rbs, (unsigned)rb_start, (unsigned)rb_count, *full, *part);
+    return RANENV_OK;
+}
+
+// (restates member_line_sums + member_line_finish, ranenv_numeric.hpp.  The kernels' rows have at most two levels of halves -- A, B, T --;
+// this follows numpy's recursion to any depth: the left siblings along the right spine, outermost first, then the last leaf)
+int ranenv_member_lines_owner_tail_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part,
+                                             int32_t *walked_lines)
+{
+    if (!row_lines || !full || !part || !walked_lines) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_rbs < 1 || rb_start < 0 || rb_count < 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    const unsigned s = (unsigned)rb_start, c = (unsigned)rb_count;
+    const int R = (int)n_rbs, tail = R & 7;
+    // ---- the cluster's part: the whole-group lines alone
+    const float *line = row_lines;
+    std::vector<std::pair<double, double>> left;          // (f, g) of A, B, ...
+    int lo = 0, n = R;
+    while (n > 128) {
+        int n2 = n / 2; n2 -= n2 % 8;
+        double f1, g1;
+        member_lines_pairwise(line, lo, n2, s, c, f1, g1);       // (a left sibling is a multiple of 8 long: no tail line in there)
+        left.push_back({f1, g1});
+        lo += n2; n -= n2;
+    }
+    double t, tg;
+    member_leaf_groups(line, lo, n, s, c, t, tg);                 // T
+    *walked_lines = (int32_t)((line - row_lines) / 32);
+    // ---- the owner's finish: its own tail line's first `tail` floats, then the halves from the innermost outwards
+    for (int k = 0; k < tail; k++) {
+        const double d = (double)line[k];
+        t += d;
+        tg = std::fma(d, ((unsigned)(R - tail + k) - s) < c ? 1.0 : 0.0, tg);
+    }
+    for (size_t i = left.size(); i-- > 0;) { t = left[i].first + t; tg = left[i].second + tg; }
+    *full = t; *part = tg;
     return RANENV_OK;
 }
 

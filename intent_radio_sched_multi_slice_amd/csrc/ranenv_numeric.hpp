@@ -332,11 +332,21 @@ struct SeStreamLane {
 // of 8 loads 16 bytes at line + 16 j: four CONSECUTIVE elements of accumulator j's sequential chain, which it adds in order into
 // one f and one masked g -- nothing crosses lanes inside a leaf.  At a leaf's end the 8 accumulators meet in row_sums' tree
 // ((f0+f1)+(f2+f3))+((f4+f5)+(f6+f7)) as a butterfly over lanes xor 1, 2, 4 (IEEE addition is commutative: whichever operand order
-// a lane sees, the grouping and so the bits are row_sums'), the tail line is added sequentially by the cluster's first two lanes, the
-// leaves fold as in row_sums.  The padding is exact: an accumulator is never -0.0 (it starts at +0.0), so acc + 0.0 == acc.
+// a lane sees, the grouping and so the bits are row_sums'), the leaves fold as in row_sums.  The padding is exact: an accumulator is
+// never -0.0 (it starts at +0.0), so acc + 0.0 == acc.
 // A wave walks its members 8 at a time: in pass q cluster c = lane >> 3 serves the wave's lane 8 q + c (its row offset and RB range
 // come through ds_bpermute, the sums go back the same way); a cluster whose lane holds no member gets an offset past the
 // descriptor, reads zeros and touches no memory.  DQ lines per lane rotate through fixed registers across the passes.
+// THE TAIL LINE IS NOT PART OF THE WALK.  It stays in the copy (line nl - 1 of a UE when R mod 8 != 0), but a row's last R mod 8
+// RBs belong to one member and numpy adds them one after the other behind the last leaf's tree: nothing there is work for eight
+// lanes, let alone once per pass for all 64.  The clusters walk nlw = nl - 1 lines per member (R = 135: 4 = the queue's depth, one
+// queue turn per pass; R < 8: none) and do NOT fold the row's last leaf: at the end of a pass up to three doubles per sum go back
+// to the owner -- A, the folded left half (rows of more than one leaf); B, the right half's first leaf (a split right half only);
+// T, the tree of the last leaf's whole groups (+0.0 where it has none).  The owner -- the lane that holds the member -- loads the
+// first 32 bytes of its own tail line when the walk is over (the queue's registers are free; the round trip is the one the rest of
+// the UE's state has behind the stream anyway) and finishes in numpy's order: t = T, t += e0, ..., t += e(tail-1), then full = t
+// | A + t | A + (B + t); `part` likewise with fma(d, in own range ? 1.0 : 0.0, .).  These are the additions the cluster made
+// when it walked the tail line: same operands, same grouping, once per TTI in 64 lanes side by side instead of once per pass.
 template <int CTRL> DEVFN double dpp_f64(double v)
 {
     const long long b = __builtin_bit_cast(long long, v);
@@ -362,8 +372,14 @@ struct MemberLines {
     v4f q[DQ];
     __amdgpu_buffer_rsrc_t rsrc;   // descriptor of exactly this tile's copy
     RowPlan pl;
-    int nl, total;                 // wave-uniform: lines per UE; lines this wave walks = passes x nl
+    int nl, nlw, total;            // wave-uniform: lines per UE in the copy; lines per UE the clusters walk (nl without the tail line); lines this wave walks = passes x nlw
     unsigned my_voff;              // owner role: byte offset of this lane's member row (OOB: the lane holds no member)
+    int own_u; bool own_member;    // owner role: what my_voff was made of (member_line_sums overwrites it; the owner's tail loads form it again)
+    // owner role, between member_line_sums and member_line_finish: what came back from the clusters, and the owner's own tail.  A row
+    // without a tail: ft / gt are the folded row sums.  A row with one: ft / gt = T, the tree of the last leaf's whole groups (+0.0 where
+    // it has none); fa / ga = A, the folded left half (rows of more than one leaf); fb / gb = B, the right half's first leaf (rsplit).
+    double fa, ga, fb, gb, ft, gt;
+    v4f e0, e1;
     int iq, il;                    // request cursor: pass, line
     unsigned ld_voff;              // cluster role: the served member's row + 16 j
     DEVFN void issue(v4f &dst)
@@ -372,51 +388,62 @@ struct MemberLines {
             ld_voff = (unsigned)__builtin_amdgcn_ds_bpermute((iq * 8 + (int)((threadIdx.x & 63u) >> 3)) * 4, (int)my_voff) + (threadIdx.x & 7u) * 16u;
         // (the line's offset is the scalar part: it takes no part in the range check, which a missing member's OOB fails by itself)
         dst = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ld_voff, il * 128, SE_AUX_NT));
-        if (++il == nl) { il = 0; iq++; }
+        if (++il == nlw) { il = 0; iq++; }
+    }
+    // the owner's own tail line (R mod 8 != 0): its first 32 bytes, straight into the lane that owns the member (zeros for a lane without one)
+    DEVFN void tail_request()
+    {
+        const unsigned tv = own_member ? (unsigned)(own_u * nl * 128) : OOB;
+        e0 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)tv, (nl - 1) * 128, SE_AUX_NT));
+        e1 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(tv + 16u), (nl - 1) * 128, SE_AUX_NT));
     }
     DEVFN void init(const float *tile_lines, int U, int R, bool member, int u)
     {
         pl = make_row_plan(R);
         nl = member_lines_per_ue(pl, R);
+        nlw = nl - ((R & 7) ? 1 : 0);
         rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tile_lines), 0, U * nl * 128, 0x00020000);
         const unsigned long long m = __builtin_amdgcn_ballot_w64(member);
         const int top = m != 0 ? 64 - __builtin_clzll(m) : 0;          // (members are the first lanes of an env; any pattern is served)
-        total = ((top + 7) >> 3) * nl;
+        total = ((top + 7) >> 3) * nlw;
         my_voff = member ? (unsigned)(u * nl * 128) : OOB;
+        own_u = u; own_member = member;
         iq = 0; il = 0; ld_voff = OOB;
 #pragma unroll
         for (int d = 0; d < DQ; d++) if (d < total) issue(q[d]);
     }
 };
 
-// The serving order (ranenv_member_serving_order restates it on the host).  init() requests the first DQ lines before the
-// allocation, when nobody knows the ranges: they belong to the first P0 = ceil(DQ / nl) passes, whose lanes 0 .. 8 P0 - 1 keep
+// The serving order (ranenv_member_serving_order restates it on the host, called with the WALKED lines per UE, nlw).  init() requests
+// the first DQ lines before the allocation, when nobody knows the ranges: they belong to the first P0 = ceil(DQ / nlw) passes, whose lanes 0 .. 8 P0 - 1 keep
 // slot = lane.  Behind that prefix the lanes are served holders first: members with rb_count > 0 in lane order, then members
 // without an RB in lane order, then the lanes without a member -- slot = rank within the group behind the groups in front (two
 // ballots, mbcnt).  Every lane pushes its row offset and its packed range to lane `slot` (ds_permute), pass q serves slots
 // 8 q .. 8 q + 7 from those copies, and the owner takes its sums back from cluster slot & 7 at the end of pass slot >> 3.  The
 // first M = P0 + ceil(holders behind the prefix / 8) passes (at most all of them) serve every holder; the passes behind them serve
-// members without an RB only and run the sum-only body: converts, f +=, the f tree, the f folds and the f tail -- no g, no
+// members without an RB only and run the sum-only body: converts, f +=, the f tree and the f folds -- no g, no
 // range word, no compare.  Exact: a member's `full` and `part` depend on its own lines and its own range alone, never on the
 // cluster or the pass that serves it, and the additions, their order, the tree and the folds per member are what they were;
 // for rb_count == 0 every fma(d, 0.0, g) leaves g at +0.0 (the SE is finite, and an accumulator that starts at +0.0 never
 // becomes -0.0), so the +0.0 that `part` keeps there is the masked body's result bit for bit.  The queue's slots are compile-time
-// registers, so the bodies change at a queue turn: the first turn that starts at or behind line M nl (the lines of members
-// without an RB in front of it run the masked body, which is exact for them as well).
+// registers, so the bodies change at a queue turn: the first turn that starts at or behind line M nlw (the lines of members
+// without an RB in front of it run the masked body, which is exact for them as well; where nlw == DQ a pass is a turn and there are none).
 template <int DQ> DEVFN int member_prefix_passes(int nl) { return (DQ + nl - 1) / nl; }
 
 // `full` / `part` of this lane's member row (0 for a lane without one), bit for bit row_sums' over the range [s, s + c).
+// Two halves: member_line_sums walks the lines and, for a row with a tail, requests the owner's tail loads; member_line_finish gives the
+// sums.  What the caller loads between the two shares the tail loads' round trip.
 // `after_issue`: as in row_sums, once, in front of the last turn of the queue.
 template <int DQ, typename Hook>
-DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, double &full, double &part, Hook after_issue)
+DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, Hook after_issue)
 {
     typedef typename MemberLines<DQ>::v4f v4f;
     const RowPlan pl = st.pl;
-    const int tail = R & 7, nl = st.nl, total = st.total;
+    const int tail = R & 7, nl = st.nlw > 0 ? st.nlw : 1, total = st.total;      // (nl: the WALKED lines per UE; R < 8 walks none: total == 0)
     const int j = (int)(threadIdx.x & 7u), cluster = (int)((threadIdx.x & 63u) >> 3);
     // ---- serving slots ----
     const int lane = (int)(threadIdx.x & 63u);
-    const bool member = st.my_voff != MemberLines<DQ>::OOB;
+    const bool member = st.own_member;
     const int pre = member_prefix_passes<DQ>(nl) * 8;                      // <= 32 (DQ <= 4 passes of one line)
     const unsigned long long behind = ~0ull << pre;
     const unsigned long long hb = __builtin_amdgcn_ballot_w64(member && c > 0) & behind;
@@ -430,7 +457,7 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
     // (push: lane `slot` receives this lane's words; the slots are a permutation of the wave, so every lane receives one)
     st.my_voff = (unsigned)__builtin_amdgcn_ds_permute(slot * 4, (int)st.my_voff);
     const int slot_sc = __builtin_amdgcn_ds_permute(slot * 4, my_sc);
-    const int my_pass = slot >> 3, my_from = (slot & 7) * 32 + (tail > 0 ? 4 : 0);
+    const int my_pass = slot >> 3, my_from = (slot & 7) * 32;            // (behind a leaf's tree every lane of the cluster holds the sums)
 #if RANENV_DIAG == 11      /* ablation 11: the full sum alone, for every pass (timing only: `part` is wrong) */
     const int sum_only_from = 0;
 #else
@@ -447,8 +474,8 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
         v = v + dpp_f64<0x4E>(v);           // quad_perm [2,3,0,1]: lane ^ 2
         return v + dpp_f64<0x141>(v);       // row_half_mirror: the other quad of the 8 (every lane of a quad holds the quad's sum)
     };
-    full = 0.0; part = 0.0;
-    // MASKED = false: the sum-only body (everything of g's side is gone, `part` keeps its +0.0)
+    double fa = 0.0, ga = 0.0, fb = 0.0, gb = 0.0, ft = 0.0, gt = 0.0;      // what comes back to the owner (see MemberLines)
+    // MASKED = false: the sum-only body (everything of g's side is gone, ga / gb / gt keep their +0.0)
     auto consume = [&](const v4f x, auto masked_tag) {
         constexpr bool MASKED = decltype(masked_tag)::value;
         auto fold = [&](int k) {
@@ -465,61 +492,47 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
             }
             leaf = 0; left = member_line_chunks(pl.len0); rb0 = 0; leaf_end = pl.len0; fr = 0.0;
         }
-        if (tail > 0 && cl == nl - 1) {
-            // the row's last R mod 8 RBs, one after the other behind the tree: positions 0..3 are the cluster's first lane's, 4..6 its
-            // second lane's, so the chain runs through both -- the second lane takes the first one's sums over and ends up with the row's
-            const float e[4] = {x.x, x.y, x.z, x.w};
-            const int t0 = tj - j + (R - tail);          // (RB of position k) - rb_start = t0 + k
-            double a = fr, b = gr;
+        const float e[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (k < tail) {
-                    const double d = (double)e[k];
-                    a += d;
-                    if constexpr (MASKED) b = fma(d, (unsigned)(t0 + k) < oc ? 1.0 : 0.0, b);
-                }
-            }
-            a = dpp_f64<0xA0>(a);                            // quad_perm [0,0,2,2]: the first lane's sums, in the second lane
-            if constexpr (MASKED) b = dpp_f64<0xA0>(b);
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                if (4 + k < tail) {
-                    const double d = (double)e[k];
-                    a += d;
-                    if constexpr (MASKED) b = fma(d, (unsigned)(t0 + 4 + k) < oc ? 1.0 : 0.0, b);
-                }
-            }
-            fr = a;
-            if constexpr (MASKED) gr = b;
-            fold(pl.n_leaves - 1);
-        } else {
-            const float e[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const double d = (double)e[k];
-                f += d;
-                if constexpr (MASKED) g = fma(d, (unsigned)(tj + rb0 + 8 * k) < oc ? 1.0 : 0.0, g);
-            }
-            rb0 += 32;
-            if (--left == 0) {
-                fr = tree(f);
-                f = 0.0;
-                if constexpr (MASKED) { gr = tree(g); g = 0.0; }
-                if (!(leaf == pl.n_leaves - 1 && tail > 0)) fold(leaf);
-                leaf += 1;
-                left = member_line_chunks(len_of(leaf)); rb0 = leaf_end; leaf_end += len_of(leaf);
-            }
+        for (int k = 0; k < 4; k++) {
+            const double d = (double)e[k];
+            f += d;
+            if constexpr (MASKED) g = fma(d, (unsigned)(tj + rb0 + 8 * k) < oc ? 1.0 : 0.0, g);
+        }
+        rb0 += 32;
+        if (--left == 0) {
+            fr = tree(f);
+            f = 0.0;
+            if constexpr (MASKED) { gr = tree(g); g = 0.0; }
+            if (!(leaf == pl.n_leaves - 1 && tail > 0)) fold(leaf);
+            leaf += 1;
+            left = member_line_chunks(len_of(leaf)); rb0 = leaf_end; leaf_end += len_of(leaf);
         }
         if (++cl == nl) {
-            // back to the owner: the lane with slot 8 cq + i takes the sums of cluster i from that cluster's first lane -- its second
-            // where a tail line ended the row there (without one every lane of the cluster holds the sums)
+            // back to the owner: the lane with slot 8 cq + i takes the sums of cluster i from that cluster's first lane
+            const bool mine = my_pass == cq;
+            // A row without a tail sends its folded sums; one with a tail was not folded behind its last leaf: fr / gr are that leaf's
+            // tree (T), lf / lg the left half (A), rf / rg the right half's first leaf (B).
+            // (the three transfers are kept apart on purpose -- an opaque no-op in two of them: merged into one block behind a
+            // selected destination, the six sums end up in a stack table)
             const double fv = pl.n_leaves == 1 ? lf : lf + rf;
-            const double fo = lane_f64(fv, my_from);
-            if (my_pass == cq) full = fo;
+            const double to = lane_f64(tail == 0 ? fv : fr, my_from);
+            if (mine) ft = to;
             if constexpr (MASKED) {
                 const double gv = pl.n_leaves == 1 ? lg : lg + rg;
-                const double go = lane_f64(gv, my_from);
-                if (my_pass == cq) part = go;
+                const double go = lane_f64(tail == 0 ? gv : gr, my_from);
+                if (mine) gt = go;
+            }
+            if (tail > 0 && pl.n_leaves > 1) {
+                double ao = lane_f64(lf, my_from);
+                asm volatile("" : "+v"(ao));
+                if (mine) fa = ao;
+                if constexpr (MASKED) { const double go = lane_f64(lg, my_from); if (mine) ga = go; }
+            }
+            if (tail > 0 && pl.rsplit) {
+                const double bo = lane_f64(rf, my_from);
+                if (mine) fb = bo;
+                if constexpr (MASKED) { double go = lane_f64(rg, my_from); asm volatile("" : "+v"(go)); if (mine) gb = go; }
             }
             cl = 0; cq += 1;
         }
@@ -542,6 +555,40 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
 #pragma unroll 1
     for (; base < total; base += DQ) turn(base, std::false_type());
     if (!hooked) after_issue();
+    st.fa = fa; st.ga = ga; st.fb = fb; st.gb = gb; st.ft = ft; st.gt = gt;
+    // (the queue's registers are free here)
+    if (tail > 0) st.tail_request();
+}
+
+// The owner's finish: the row's last R mod 8 RBs belong to one member, and numpy adds them one after the other behind the last
+// leaf's tree -- so the lane that owns the member adds its own, once per TTI, all 64 owners side by side, and folds the halves:
+// the additions that a cluster made per pass when the tail line was part of the walk, on the same operands in the same grouping.
+template <int DQ>
+DEVFN void member_line_finish(MemberLines<DQ> &st, int R, unsigned s, unsigned c, double &full, double &part)
+{
+    typedef typename MemberLines<DQ>::v4f v4f;
+    const RowPlan pl = st.pl;
+    const int tail = R & 7;
+    const bool member = st.own_member;
+    const double fa = st.fa, ga = st.ga, fb = st.fb, gb = st.gb, ft = st.ft, gt = st.gt;
+    if (tail == 0) { full = ft; part = gt; return; }
+    const v4f e0 = st.e0, e1 = st.e1;
+    double t = ft, tg = gt;
+    // the masked chain, on the owner's own range -- skipped where no lane's range reaches [R - tail, R): every fma(d, 0.0, tg) would
+    // leave tg as it is (d is finite, and tg, sums that started at +0.0, is never -0.0)
+    const bool reach = __builtin_amdgcn_ballot_w64(member && c > 0 && s + c > (unsigned)(R - tail)) != 0;
+    const unsigned t0 = (unsigned)(R - tail) - s;           // (RB of position k) - rb_start = t0 + k
+    auto add = [&](float x, int k) {                        // (no array of the seven: indexed by a loop it ends up in scratch)
+        if (k < tail) {
+            const double d = (double)x;
+            t += d;
+            if (reach) tg = fma(d, (t0 + (unsigned)k) < c ? 1.0 : 0.0, tg);
+        }
+    };
+    add(e0.x, 0); add(e0.y, 1); add(e0.z, 2); add(e0.w, 3); add(e1.x, 4); add(e1.y, 5); add(e1.z, 6);
+    if (pl.n_leaves == 1) { full = t; part = tg; }
+    else if (!pl.rsplit) { full = fa + t; part = ga + tg; }
+    else { full = fa + (fb + t); part = ga + (gb + tg); }
 }
 
 // Sums of one row: `full` over all R RBs, `part` over the RBs selected by in(r).

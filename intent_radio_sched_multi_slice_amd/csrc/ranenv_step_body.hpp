@@ -673,7 +673,7 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
         }
     } else if constexpr (MODE == MODE_STEP) {
         const unsigned us1 = (unsigned)rb_start, uc1 = (unsigned)rb_count;
-        if constexpr (MEMBERS) member_line_sums(ml, R, us1, uc1, my_full, my_part, hook);
+        if constexpr (MEMBERS) member_line_sums(ml, R, us1, uc1, hook);
         else row_sums<PE>(se1, R, [=](int r) { return ((unsigned)r - us1) < uc1; }, my_full, my_part, hook, PE ? COLD(bw_per_rb) : 1.0);
     } else if constexpr (MODE == MODE_DENSE) {
         const uint8_t *mrow = p.dense + ((size_t)e * U + u) * R;
@@ -682,6 +682,8 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
         row_sums(se1, R, [](int) { return false; }, my_full, my_part, hook);
     }
     if constexpr (!STATE_AT_ENTRY) rest_of_state();        // after the stream: its latency is exposed, its registers were free for the queue
+    // (members: the owner's tail loads were requested at the end of the walk and share that round trip; their use comes behind it)
+    if constexpr (MEMBERS) member_line_finish(ml, R, (unsigned)rb_start, (unsigned)rb_count, my_full, my_part);
     if constexpr (SE_AHEAD && CARRY) {
         // The next TTI's tile of this env (the position it will derive itself: cy.se_pos below), requested as soon as the queue's
         // registers are free: in a carried TTI nothing the UE step needs is loaded behind it (in the first TTI of a chunk the UE step's
