@@ -1000,9 +1000,22 @@ int ranenv_autoreset_part(ranenv_handle h, int32_t part, const uint8_t *dev_done
  *                                                 ranenv_bind_se_pool_quad) instead of whole tiles: -1 (auto) and 1: wherever the variant exists -- the
  *                                                 launches of several TTIs of the lean build and the streaming persistent launches, i.e. batches above 8
  *                                                 workgroups per CU; 0: never.  The copy costs n_tiles * U * lines * 128 bytes of device memory
- *   "last_rollout_persistent" / "last_rollout_launches" / "last_rollout_member_lines" (read only)   what the last ranenv_rollout call ran: 1 =
- *                                                 persistent work-queue launches (else launches of <= 10 TTIs per partition); how many step-kernel
- *                                                 launches it enqueued; 1 = step launches of it read the member-lines copy
+ *   "lean_tail"    RANENV_LEAN_TAIL      1         launches that take their envs through several TTIs (ranenv_rollout / ranenv_collect* under a device
+ *                                                 policy with nothing between two TTIs: launches per chunk and persistent launches): 1 = only an env's
+ *                                                 LAST TTI of a launch computes and stores dev_obs_inter, dev_obs_intra, dev_reward, dev_done and the raw
+ *                                                 per-UE outputs (pkt_incoming, pkt_throughputs, pkt_effective_thr, dropped_pkts) -- the earlier TTIs'
+ *                                                 values would be overwritten before any kernel or the host could read them --, and without
+ *                                                 ranenv_enable_metrics the earlier TTIs skip the intent drift and the reward arithmetic as well; 0 = every
+ *                                                 TTI of every launch runs all of it (for A/B runs and bisection).  Whatever the value, every buffer holds
+ *                                                 the same bits wherever it can be read: every launch boundary, every end of a persistent launch and every
+ *                                                 episode end is a last TTI.  One-TTI launches (ranenv_step, rollouts under a policy net, a head, slice
+ *                                                 metrics or a trace), resets and dense launches always run all of it
+ *   "last_rollout_persistent" / "last_rollout_launches" / "last_rollout_member_lines" / "last_rollout_lean_ttis" (read only)   what the last
+ *                                                 ranenv_rollout / ranenv_collect* call ran: 1 = persistent work-queue launches (else launches of <= 10
+ *                                                 TTIs per partition); how many step-kernel launches it enqueued; 1 = step launches of it read the
+ *                                                 member-lines copy; the TTIs its step launches enqueued WITHOUT the observation tail ("lean_tail"),
+ *                                                 summed over the launches: n_tti - 1 for a launch of n_tti TTIs, 0 for one-TTI launches and with
+ *                                                 "lean_tail" = 0
  *   "step_launches_<build>" / "step_launches_<build>_many" (read only)   which build of the step kernel the handle's step launches ran, <build> one of
  *                                                 lean, small, gather, tiny1, mixed, packed, persist, persist_tiny: launches of the step kernel in step mode
  *                                                 that succeeded since ranenv_create (resets and dense launches are not counted), and the share of them

@@ -94,6 +94,7 @@ struct ranenv {
     int *d_perr_dev = nullptr;     // ... its address as the device sees it
     int perr_seen = 0;             // ... what of it has been reported
     int last_rollout_persistent = 0, last_rollout_launches = 0;   // what the last ranenv_rollout call ran (read-only options)
+    long long last_rollout_lean_ttis = 0;   // ... and the TTIs its step launches enqueued without the observation tail (option "lean_tail": n_tti - 1 per launch)
     // MODE_STEP launches of the step kernel that succeeded since ranenv_create, per StepBuild; [1]: those of several TTIs (read-only options
     // "step_launches_<build>" / "..._many").  Enqueues: a replayed graph counts once, at its capture.
     uint64_t step_launches[N_STEP_BUILDS][2] = {};
@@ -362,6 +363,8 @@ hipError_t launch_step_counted(ranenv_handle h, const StepLaunch &l, dim3 grid, 
     if (e == hipSuccess) {
         if (known && (l.mode & 3) == MODE_STEP) h->step_launches[l.build][l.many ? 1 : 0]++;
         if (l.members) h->last_rollout_member_lines = 1;
+        // (a build of several TTIs runs the whole observation tail at an env's last TTI of the launch only: KP::lean_tail, step_body's LEAN)
+        if ((l.mode & 3) == MODE_STEP && l.many && kp.lean_tail != 0 && kp.n_tti > 1) h->last_rollout_lean_ttis += kp.n_tti - 1;
     } else {
         char buf[160];
         snprintf(buf, sizeof(buf), "step kernel build '%s' (row width %d, mode %d, %s, %s): %s", known ? step_build_names[l.build] : "?", l.np, l.mode,
@@ -968,6 +971,8 @@ const Option options[] = {
     {"autoreset_shortcut", true, [](H h, long long v) { h->autoreset_shortcut = v != 0 ? 1 : 0; return 0; },
      [](H h) -> long long { return h->autoreset_shortcut; }},
     {"member_lines", true, [](H h, long long v) { h->member_lines = v < 0 ? -1 : (v != 0 ? 1 : 0); return 0; }, [](H h) -> long long { return h->member_lines; }},
+    // (kept in the handle's argument block: every call's KP is a copy of it)
+    {"lean_tail", true, [](H h, long long v) { h->kp.lean_tail = v != 0 ? 1 : 0; return 0; }, [](H h) -> long long { return h->kp.lean_tail; }},
 };
 
 const Option *find_option(const std::string &k)
@@ -1063,6 +1068,7 @@ int ranenv_create(const ranenv_config *cfg, ranenv_handle *out)
     kp.policy = RANENV_POLICY_MARR; kp.fixed_intra = RANENV_INTRA_RR;
     kp.bw_hz = cfg->bandwidth_hz; kp.bw_per_rb = cfg->bandwidth_hz / (double)R; kp.over = cfg->overfulfill;
     kp.norm_traffic = cfg->norm_traffic; kp.norm_ues = cfg->norm_ues; kp.norm_se = cfg->norm_se;
+    kp.lean_tail = 1;
     int rc = RANENV_OK;
 #define ALLOC(field, count) if (rc == RANENV_OK) rc = dev_alloc(h, &field, (count))
     const size_t NSL = (size_t)S * GRP;
@@ -1137,6 +1143,7 @@ int ranenv_get_option(ranenv_handle h, const char *key, int64_t *value)
     else if (k == "last_rollout_persistent") *value = h->last_rollout_persistent;      // what the last ranenv_rollout call ran:
     else if (k == "last_rollout_launches") *value = h->last_rollout_launches;          // 1 = persistent work-queue launches; step-kernel launches enqueued
     else if (k == "last_rollout_member_lines") *value = h->last_rollout_member_lines;  // 1 = its step launches read the member-lines copy
+    else if (k == "last_rollout_lean_ttis") *value = h->last_rollout_lean_ttis;        // TTIs its step launches enqueued without the observation tail
     else if (k.rfind("step_launches_", 0) == 0) {      // MODE_STEP launches per build since ranenv_create; "..._many": those of several TTIs
         std::string b = k.substr(14);
         const bool many_only = b.size() > 5 && b.compare(b.size() - 5, 5, "_many") == 0;
@@ -3040,7 +3047,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     Rollout r;
     r.n_steps = n_steps;
     r.kp = call_kp(h, obs_inter, obs_intra, reward, done);
-    h->last_rollout_persistent = 0; h->last_rollout_launches = 0; h->last_rollout_member_lines = 0;
+    h->last_rollout_persistent = 0; h->last_rollout_launches = 0; h->last_rollout_member_lines = 0; h->last_rollout_lean_ttis = 0;
     r.net = net_use(h, r.kp);                      // (policy network: its launch precedes every TTI of a partition, see rollout_plan)
     if (r.net < 0) return r.net;
     r.rec = rec;

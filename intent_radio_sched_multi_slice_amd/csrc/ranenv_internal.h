@@ -147,11 +147,16 @@ struct KP {
     struct PersistCtl *p_ctl;         // the class's counters and per-XCD queue heads
     unsigned long long *p_slots;      // [8][p_cap] queue entries {index + 1, item}
     int p_cap;                        // entries per queue (a power of two >= the batch)
+    // launches of several TTIs (option "lean_tail"): != 0 = only an env's last TTI of the launch runs the whole observation tail and
+    // stores the outputs nobody can read in between (step_body's LEAN); 0 = every TTI does.  Sits in what was padding in front of
+    // p_err: no other member moved
+    int lean_tail;
     int *p_err;                       // sticky error word of the handle (a wait gave up), in host memory mapped for the device
     // member lines (ranenv_core_kernel_members / ranenv_persist_kernel_members): the handle's per-UE line copy of the bound pool,
     // floats between two tiles' copies (U x lines per UE x 32); null: the variant is off
     const float *ml_pool; long long ml_stride;
 };
+static_assert(offsetof(KP, p_err) - offsetof(KP, lean_tail) == 4 && offsetof(KP, lean_tail) - offsetof(KP, p_cap) == 4, "KP: lean_tail fills the padding behind p_cap");
 
 constexpr int WAVE = 64;
 constexpr int GRP = 16;   // lanes per (env) group in alloc1/obs and per (env, slice) group in alloc2

@@ -398,10 +398,14 @@ struct StepCarry {
 // member-lines copy of the tile (MemberLines / member_line_sums, ranenv_numeric.hpp) -- the rows of slice members only, 8 lanes
 // per member -- instead of every UE's row of the bound tile; p.ml_pool / p.ml_stride describe the copy.  Same sums, bit for bit.
 struct NoMemberLines { };
-template <int MODE_X, int NQ, bool GATHER, int NP, bool PERSIST = false, int PACK = 1, bool MIX = false, bool MEMBERS = false, typename P>
+// LEAN (every build that steps several TTIs per launch: MANY, the persistent ones): `tail_in` = this is the env's last TTI in this launch.
+// A TTI that is not runs no part of the roles whose results the launch's next TTI of the env overwrites before any kernel or the host can
+// read them ("The last TTI's tail"): the observation rows, the reward and done stores, the raw per-UE outputs, and -- with the
+// episode-metric accumulators off -- the intent drift, the per-slice means and the reward arithmetic.  Other builds: always the whole tail.
+template <int MODE_X, int NQ, bool GATHER, int NP, bool PERSIST = false, int PACK = 1, bool MIX = false, bool MEMBERS = false, bool LEAN = false, typename P>
 DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,   // warm: `cy` holds what the previous TTI of this launch left
                      std::conditional_t<PACK == 2, SeStreamLane<GATHER ? 1 : NQ>, SeStream<GATHER ? 1 : NQ>> *se_carry = nullptr,
-                     const bool se_ready = false, const bool se_next = false, const bool narrow_in = false)
+                     const bool se_ready = false, const bool se_next = false, const bool narrow_in = false, const bool tail_in = true)
 {                                     // -> true: this wave has left for good (nothing to do at later TTIs of the launch either)
     constexpr int MODE = MODE_X & 3;
     constexpr bool PE = (MODE_X & MODE_PE) != 0;
@@ -412,6 +416,7 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     // `tid` is the lane within the env's half, everything per env (index, counters, episode, tile, LDS image, row addresses) is a
     // per-lane value that happens to be equal across a half, and the 16-lane slice groups are DPP rows 0 / 2 of the wave.
     static_assert(PACK == 1 || (PACK == 2 && MODE == MODE_STEP && !PERSIST), "packed waves: step launches only");
+    static_assert(!LEAN || MODE == MODE_STEP, "a launch of several TTIs steps");
     constexpr int LW = WAVE / PACK;                  // lanes per env
     constexpr int GDEPTH = (GATHER && NQ == 0) ? 1 : 2;      // gather builds: NQ = 0 asks for one 8-RB group in flight instead of two
     // CARRY (persistent builds with registers to spare): a TTI that follows another TTI of the same env in the same chunk loads
@@ -461,6 +466,16 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     kp_const_t kc = (kp_const_t)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kc));
 #define COLD(f) (kc->f)
+    // TAIL: the whole observation tail runs (uniform over the workgroup, a scalar).  ROWS: the drift, the per-slice means and the reward
+    // arithmetic run -- on a lean TTI only for the episode-metric accumulators.  Outside the LEAN builds both are the constant `true` in a
+    // form the front end folds: those builds' code is what it was without the conditions (tools/isa_compare.py)
+    bool tail_v = true, rows_v = true;
+    if constexpr (LEAN) {
+        tail_v = __builtin_amdgcn_readfirstlane(tail_in ? 1 : 0) != 0;
+        rows_v = tail_v || COLD(acc) != nullptr;
+    }
+#define TAIL (!LEAN || tail_v)
+#define ROWS (!LEAN || rows_v)
     ranenv_episode ep;
     int t, hlen, npush, se_pos, trf_pos;
     if (!warm) {
@@ -809,9 +824,12 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
         UE4(queue_pkts) = total; UE8(queue_age_sum) = sum_age;
         UE4(front) = front; UE4(front_rem) = front_rem; UE4(fifo) = fifo;
         UE8(win_sent) = win_sent; UE8(win_dropped) = win_drop;
-        UE4(pkt_effective_thr) = (int32_t)sent; UE4(dropped_pkts) = (int32_t)dropped;
-        if (!(COLD(flags) & RANENV_F_NO_RAW_OUTPUT)) {
-            nt_store<GATHER>(UE4(pkt_incoming), (int32_t)pkt_in); nt_store<GATHER>(UE4(pkt_throughputs), (int32_t)pkt_thr);
+        // (the raw outputs: read by kernels that follow a one-TTI launch and by the host, never inside a launch of several TTIs -- the last TTI's stand)
+        if (TAIL) {
+            UE4(pkt_effective_thr) = (int32_t)sent; UE4(dropped_pkts) = (int32_t)dropped;
+            if (!(COLD(flags) & RANENV_F_NO_RAW_OUTPUT)) {
+                nt_store<GATHER>(UE4(pkt_incoming), (int32_t)pkt_in); nt_store<GATHER>(UE4(pkt_throughputs), (int32_t)pkt_thr);
+            }
         }
         sent_u = sent; drop_u = dropped;
 
@@ -846,6 +864,8 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
             }
             cy.pf_old_s = ps; cy.pf_old_d = pd; cy.pf_traffic = pt; cy.pf1 = e1; cy.pf2 = e2;
         }
+        // (a lean TTI without episode metrics stops here: the drift feeds the observation and the reward alone)
+        if (ROWS) {
         const double occ_new = ddiv((double)total, (double)max_pkts);
         const double lat_new = total > 0 ? ddiv((double)sum_age, (double)total) : 0.0;
         // ---- intent drift of this UE (agents/common.py:68-340) ----------------------------------------
@@ -906,11 +926,12 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
             srow(sh, slc, 0)[ue_pos] = dres[0]; srow(sh, slc, 1)[ue_pos] = dres[1]; srow(sh, slc, 2)[ue_pos] = dres[2];
             srow(sh, slc, 3)[ue_pos] = se_mean_new;
             sh.cnt[slc][ue_pos] = rb_count;
-            if (COLD(obs_intra) && ue_pos < Us) {                                          // per-UE entries (:186-200)
+            if (TAIL && COLD(obs_intra) && ue_pos < Us) {                                  // per-UE entries (:186-200)
                 float *oa = sh.ob_intra + slc * W;
                 oa[9 + ue_pos] = (float)occ_new;
                 oa[9 + Us + ue_pos] = (float)ddiv(se_mean_new, COLD(norm_se));
             }
+        }
         }
     }
     if (MODE != MODE_RESET && COLD(acc) != nullptr) {
@@ -928,9 +949,23 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
             asm volatile("" ::: "memory");
         }
     }
-    wg_sync(narrow);
+    // (a lean TTI without episode metrics has written no LDS row behind the barrier in front of the UE step and reads none below: its
+    // next barrier is the one between two TTIs of a launch -- step_loop's, the persistent loops' -- which every non-last TTI is followed by)
+    if (ROWS) wg_sync(narrow);
     RANENV_STAMP(6);
     do {
+    if constexpr (LEAN) if (!rows_v) {
+        // lean TTI, no episode metrics: nothing of (3) but the per-env counters, by thread 0 as below -- EVERY TTI stores them (the next
+        // TTI of a workgroup that picks the env up cold, and the next launch, read them)
+        if (tid == 0) {
+            ST_step_no(p)[e] = t + 1; ST_hist_len(p)[e] = hlen_new; ST_n_push(p)[e] = npush + 1 == D ? 0 : npush + 1;
+            ST_push_total(p)[e] = ptot + 1;
+            if (ptot + 1 - cmark > 2 * D) ST_clear_mark(p)[e] = ptot + 1 - 2 * D;      // (a step never clears the window: MODE_STEP)
+            ST_se_pos(p)[e] = se_pos + 1 >= ep.se_len ? 0 : se_pos + 1;
+            ST_trf_pos(p)[e] = trf_pos + 1 >= ep.trf_len ? 0 : trf_pos + 1;
+        }
+        break;
+    }
 #if RANENV_DIAG == 4      /* ablation: no observation tail, but the per-env counters move on (tiles keep changing) */
     if (my_full >= -1.0) {
         if (tid == 0) {
@@ -990,6 +1025,7 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
             sv[m] = undeclared ? 0.0 : sv[m];
         }
         const double se_slice = n > 0 ? mean_row[3] : 0.0;                                      // :146-157
+        if (TAIL) {                          // (a lean TTI that keeps episode metrics: the reward arithmetic below, none of the rows)
         const float o0 = (float)sv[0], o1 = (float)sv[1], o2 = (float)sv[2];
         const float a0 = (float)am[0], a1 = (float)am[1], a2 = (float)am[2];
         const float tr = (float)ddiv(traffic_req, COLD(norm_traffic)), nu = (float)ddiv((double)n, COLD(norm_ues));
@@ -1004,13 +1040,14 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
             oa[6] = (float)ddiv((double)rbs_s, (double)R); oa[7] = tr; oa[8] = nu;
             for (int k = n; k < Us; k++) { oa[9 + k] = 0.0f; oa[9 + Us + k] = 0.0f; }
         }
+        }
         // player_{s+1} reward (common.py:428-437)
         double r = 0.0; int cnt = 0;
 #pragma unroll
         for (int m = 0; m < 3; m++) {
             if (am[m] > 0.0) { r = (cnt == 0 || sv[m] < r) ? sv[m] : r; cnt++; }
         }
-        if (COLD(reward)) row_at<PACK>(COLD(reward), (size_t)e * (S + 1) * 8, (unsigned)(s + 1) * 8u) = cnt > 0 ? r : 0.0;
+        if (TAIL && COLD(reward)) row_at<PACK>(COLD(reward), (size_t)e * (S + 1) * 8, (unsigned)(s + 1) * 8u) = cnt > 0 ? r : 0.0;
         if (MODE == MODE_RESET) {
             ST_mask_inter(p)[(size_t)e * S + s] = (int8_t)active;
             for (int k = 0; k < Us; k++) ST_mask_intra(p)[((size_t)e * S + s) * Us + k] = k < n ? 1 : 0;
@@ -1052,7 +1089,7 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     if (tid == 0) {
         double rew = np_sum_lds<NP>(xr[2], m_sel) / (double)m_sel;
         if (mode_sel == 1) rew -= 1.0;
-        if (COLD(reward)) COLD(reward)[(size_t)e * (S + 1)] = rew;
+        if (TAIL && COLD(reward)) COLD(reward)[(size_t)e * (S + 1)] = rew;
         // Episode metrics (ranenv_enable_metrics): running sums of what the paper's evaluation reads per TTI
         // (results/gen_results.py:874-1022: slices in violation, distance to fulfilment, all slices / priority slices
         // only), of the inter-slice reward and of the packet totals.  One writer per env and TTI; fire-and-forget adds.
@@ -1081,13 +1118,15 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
             ST_se_pos(p)[e] = se_pos + 1 >= ep.se_len ? 0 : se_pos + 1;
             ST_trf_pos(p)[e] = trf_pos + 1 >= ep.trf_len ? 0 : trf_pos + 1;
         }
-        const int max_steps_e = COLD(max_steps_env) ? COLD(max_steps_env)[e] : COLD(max_steps);
-        if (COLD(done)) COLD(done)[e] = (MODE != MODE_RESET && step_new >= max_steps_e) ? 1 : 0;
+        if (TAIL) {
+            const int max_steps_e = COLD(max_steps_env) ? COLD(max_steps_env)[e] : COLD(max_steps);
+            if (COLD(done)) COLD(done)[e] = (MODE != MODE_RESET && step_new >= max_steps_e) ? 1 : 0;
+        }
     }
     } while (0);
     // wave 0 writes the staged observation rows out, a float per lane and whole lines per instruction (the per-UE entries were
     // staged before the barrier in front of (3), the per-slice ones by this wave's first 16 lanes just now)
-    if (tid < WAVE && (COLD(obs_inter) || COLD(obs_intra))) {
+    if (TAIL && tid < WAVE && (COLD(obs_inter) || COLD(obs_intra))) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (COLD(obs_inter)) {
             float *dst = COLD(obs_inter) + (size_t)e * S * 10;
@@ -1111,6 +1150,8 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     return false;
 #undef UE4
 #undef UE8
+#undef TAIL
+#undef ROWS
 }
 
 // Several TTIs of one env in one launch (ranenv_rollout with a device policy, no episode end in between): the workgroup
@@ -1162,7 +1203,9 @@ DEVFN void step_loop(const KP &p)
             // of the k-th CONTIGUOUS eighth of the launch's envs, so that an XCD touches one eighth of every per-env array (see persist_try_fresh)
             const int nb_ = (int)gridDim.x, xk_ = (int)blockIdx.x & 7, q_ = nb_ >> 3, r_ = nb_ & 7;
             const int b_perm = xk_ * q_ + (xk_ < r_ ? xk_ : r_) + ((int)blockIdx.x >> 3);
-            if (step_body<MODE_X, NQ, GATHER, NP, false, PACK, MIX, MEMBERS>(*kc, cy, warm, MIX ? e_mix : kc->e0 + b_perm * PACK, nullptr, false, false, narrow)) return;
+            // (MANY: the env's last TTI in this launch runs the whole observation tail, the others what the next TTI needs -- option lean_tail)
+            const bool tail = !MANY || k + 1 == n || kc->lean_tail == 0;
+            if (step_body<MODE_X, NQ, GATHER, NP, false, PACK, MIX, MEMBERS, MANY>(*kc, cy, warm, MIX ? e_mix : kc->e0 + b_perm * PACK, nullptr, false, false, narrow, tail)) return;
             if (k + 1 < n) {
                 // The next TTI takes over in registers what it would otherwise load back (StepCarry): only LDS has to be handed over
                 // between the waves.
@@ -1370,7 +1413,8 @@ DEVFN void persist_loop()
                 // -- the workgroup keeps its env at most chunk ends -- the next chunk's first (what is requested ahead for it is wasted
                 // when the env changes hands)
                 const bool ahead = done + k + 1 < n_tti;
-                (void)step_body<MODE_STEP, NQ, GATHER, NP, true, 1, false, MEMBERS>(*kc, cy, warm, e, &seq, se_ready, ahead);
+                // (... and this one, the env's last TTI of the launch if none follows, runs the whole observation tail: option lean_tail)
+                (void)step_body<MODE_STEP, NQ, GATHER, NP, true, 1, false, MEMBERS, true>(*kc, cy, warm, e, &seq, se_ready, ahead, false, !ahead || kc->lean_tail == 0);
                 se_ready = ahead;
                 if (k + 1 < n) { warm = true; wg_sync(); }
             }
