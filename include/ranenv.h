@@ -206,11 +206,22 @@ int ranenv_se_retile_quad(const float *dev_rb_major, float *dev_quad, int64_t n_
  * R mod 8 != 0 one more line holds those last RBs at positions 0 .. R mod 8 - 1 and +0.0 behind them.  R = 135: leaves 64 + 71,
  * 2 + 2 + 1 lines = 640 bytes per UE.  Lane j of a cluster of 8 loads bytes [16*j, 16*j + 16) of a line: four consecutive elements of
  * accumulator j of numpy's 8-accumulator loop, so the sums keep their order and their bits (padding adds +0.0 to an accumulator that
- * is never -0.0).  The copy is the handle's (n_tiles * U * lines * 128 bytes, released by ranenv_destroy), built by the first
+ * is never -0.0).
+ * THE HANDLE'S COPY IS PACKED: a tail line of its own per UE is a whole 128-byte line fetched for its first R mod 8 floats, so the
+ * handle keeps, per tile, float32 [U][nlw][32] WALK LINES -- exactly the whole-group lines above in the order above, nlw = lines
+ * without the tail line (R = 135: 4) -- followed by ONE TAIL BLOCK [U][8]: UE u's last R mod 8 RBs at positions 0 .. R mod 8 - 1 of
+ * its 32-byte slot, +0.0 behind them.  The tile stride is rounded up to a multiple of 128 bytes (+0.0), so every tile's walk lines
+ * stay line-aligned (U = 25, R = 135: 12 800 + 800 -> 13 696 bytes; U = 100: 51 200 + 3 200 = 54 400 instead of 64 000).  R mod 8
+ * == 0: no block, the copy is [U][lines][32] as above; R < 8: no walk lines, the block only.  The sums do not change: the owner
+ * reads the same floats from another address.  The copy is the handle's (n_tiles * tile bytes, released by ranenv_destroy), built by the first
  * ranenv_rollout call that would use it -- never inside a stream capture -- and rebuilt after the pool is bound again; a pool whose
  * VALUES are changed in place has to be bound again.  If its allocation fails no error is raised: rollouts keep reading the tiles.
  * ranenv_se_retile_member_lines: the same transform for the caller's buffers (no handle): quad = 0 an RB-major, 1 an RB-quad-major
- * pool, tiles tile_stride floats apart; dev_lines [n_tiles][U][lines][32], 16-byte aligned.
+ * pool, tiles tile_stride floats apart; dev_lines [n_tiles][U][lines][32], 16-byte aligned (the unpacked layout, tail line included).
+ * ranenv_se_retile_member_lines_packed: the handle's packed layout for the caller's buffers: dev_lines holds n_tiles tiles of
+ * ranenv_member_lines_packed_layout's tile_bytes each, 16-byte aligned; one launch writes walk lines, block and the padding (+0.0).
+ * ranenv_member_lines_packed_layout (host arithmetic only): for (n_ues, n_rbs) the lines per UE the clusters walk, the tail block's
+ * byte offset within a tile (= n_ues * walked_lines * 128, also where a row has no tail and no block) and the tile's bytes.
  * ranenv_member_line_plan (host arithmetic only): returns the lines per UE for a row of n_rbs RBs (< 0: error) and fills, for up to
  * max_lines of them, the line's leaf, its first RB and the whole groups it holds (0 = the tail line); any of the arrays may be NULL.
  * ranenv_member_lines_row_sums_host (host arithmetic only): one UE's lines summed line by line, the tail line included -- full =
@@ -223,6 +234,9 @@ int ranenv_se_retile_quad(const float *dev_rb_major, float *dev_quad, int64_t n_
  * ranenv_member_lines_owner_tail_sums_host (host arithmetic only) restates exactly that in plain C++ -- the cluster's part over the
  * whole-group lines, then the owner's finish over the tail line's first R mod 8 floats (numpy's recursion to any depth: one left
  * sibling per level of the right spine) -- and returns full, part and *walked_lines, the lines per UE the clusters walk.
+ * ranenv_member_lines_packed_sums_host (host arithmetic only): the same restatement -- cluster part, then the owner's finish -- on the
+ * packed layout: walk_lines = the UE's walked lines [nlw][32] (may be NULL where n_rbs < 8), tail_slot = its 8-float slot of the
+ * tail block (may be NULL where n_rbs mod 8 == 0).
  * ranenv_member_serving_order (host arithmetic only): the order in which a wave of the step kernel serves its lanes' member rows, 8
  * per pass.  member_mask / holder_mask: bit l = lane l holds a slice member / a member with rb_count > 0 at this TTI (a holder that
  * is no member is an error); lines_per_ue = the lines per UE the kernel WALKS -- the plan's lines without the tail line, as
@@ -238,6 +252,11 @@ int ranenv_member_line_plan(int32_t n_rbs, int32_t max_lines, int32_t *leaf, int
 int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part);
 int ranenv_member_lines_owner_tail_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part,
                                              int32_t *walked_lines);
+int ranenv_se_retile_member_lines_packed(const float *dev_pool, int32_t quad, int64_t tile_stride, float *dev_lines, int64_t n_tiles, int32_t n_ues,
+                                         int32_t n_rbs, void *stream);
+int ranenv_member_lines_packed_layout(int32_t n_ues, int32_t n_rbs, int32_t *walked_lines, int64_t *block_offset, int64_t *tile_bytes);
+int ranenv_member_lines_packed_sums_host(const float *walk_lines, const float *tail_slot, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full,
+                                         double *part);
 int ranenv_member_serving_order(uint64_t member_mask, uint64_t holder_mask, int32_t lines_per_ue, int32_t dq, int32_t *slots, int32_t *masked_passes);
 /* Traffic pool: int32 offered bits, row i = [U] at dev + i*U. */
 int ranenv_bind_traffic_pool(ranenv_handle h, const int32_t *dev_pool, int64_t n_rows);
@@ -999,7 +1018,8 @@ int ranenv_autoreset_part(ranenv_handle h, int32_t part, const uint8_t *dev_done
  *   "member_lines" RANENV_MEMBER_LINES   -1        compact streaming rollouts read the handle's member-lines copy of the pool (see "MEMBER LINES" at
  *                                                 ranenv_bind_se_pool_quad) instead of whole tiles: -1 (auto) and 1: wherever the variant exists -- the
  *                                                 launches of several TTIs of the lean build and the streaming persistent launches, i.e. batches above 8
- *                                                 workgroups per CU; 0: never.  The copy costs n_tiles * U * lines * 128 bytes of device memory
+ *                                                 workgroups per CU; 0: never.  The packed copy costs n_tiles * ranenv_member_lines_packed_layout's
+ *                                                 tile_bytes of device memory (U 100, R 135: 54 400 bytes per tile)
  *   "lean_tail"    RANENV_LEAN_TAIL      1         launches that take their envs through several TTIs (ranenv_rollout / ranenv_collect* under a device
  *                                                 policy with nothing between two TTIs: launches per chunk and persistent launches): 1 = only an env's
  *                                                 LAST TTI of a launch computes and stores dev_obs_inter, dev_obs_intra, dev_reward, dev_done and the raw

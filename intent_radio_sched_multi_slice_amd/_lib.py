@@ -178,6 +178,9 @@ FUNCTIONS = {
     "ranenv_member_line_plan": (C.c_int, [_I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ranenv_member_lines_row_sums_host": (C.c_int, [_P, _I32, _I32, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ranenv_member_lines_owner_tail_sums_host": (C.c_int, [_P, _I32, _I32, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "ranenv_se_retile_member_lines_packed": (C.c_int, [_P, _I32, _I64, _P, _I64, _I32, _I32, _P]),
+    "ranenv_member_lines_packed_layout": (C.c_int, [_I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ranenv_member_lines_packed_sums_host": (C.c_int, [_P, _P, _I32, _I32, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ranenv_member_serving_order": (C.c_int, [C.c_uint64, C.c_uint64, _I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ranenv_selftest_ddiv": (C.c_int, [_P, _P, _P, _P, _I64, _P]),
     "ranenv_set_policy_network": (C.c_int, [_P, C.POINTER(Mlp), C.POINTER(Mlp), _I32, C.c_uint64, _P]),

@@ -72,22 +72,35 @@ __global__ void __launch_bounds__(256) ranenv_se_retile_quad_kernel(const float 
 
 // RB-major [n][R][U] or RB-quad-major [n][ceil(R/4)][U][4] (tiles `stride` floats apart) -> member lines [n][U][lines][32]
 // (ranenv_se_retile_member_lines; the layout: ranenv_numeric.hpp, "Member lines"): one float4 of the output per thread -- the 16 bytes
-// lane j of a cluster loads --, +0.0 wherever the layout pads
+// lane j of a cluster loads --, +0.0 wherever the layout pads.
+// packed_f4 > 0 (ranenv_se_retile_member_lines_packed; the handle's copy): a tile of the output is packed_f4 float4s -- the
+// whole-group lines [U][lines - 1][32], the tail block [U][8] (UE u's last R mod 8 RBs at the head of its 32-byte slot) and +0.0 up
+// to the stride; a row without a tail has no block and is laid out as above.
 __global__ void __launch_bounds__(256) ranenv_se_retile_member_lines_kernel(const float *src, long long stride, int quad, float *dst, long long n_f4,
-                                                                            int U, int R, const MemberLineTable tb)
+                                                                            int U, int R, const MemberLineTable tb, long long packed_f4)
 {
-    const long long per_tile = (long long)U * tb.lines * 8;
+    const int nlw = packed_f4 > 0 && tb.tail > 0 ? tb.lines - 1 : tb.lines;          // lines per UE in front of the block
+    const long long per_tile = packed_f4 > 0 ? packed_f4 : (long long)U * tb.lines * 8;
+    const int walk_f4 = U * nlw * 8;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_f4; i += (long long)gridDim.x * blockDim.x) {
         const long long t = i / per_tile;
-        const int rem = (int)(i - t * per_tile), u = rem / (tb.lines * 8), rl = rem - u * (tb.lines * 8), l = rl >> 3, j = rl & 7;
+        const int rem = (int)(i - t * per_tile);
         const float *tile = src + (size_t)t * (size_t)stride;
-        auto at = [&](int r) { return quad ? tile[((size_t)(r >> 2) * U + u) * 4 + (r & 3)] : tile[(size_t)r * U + u]; };
-        float v[4];
-        const int rb0 = tb.rb0[l], ng = tb.groups[l];
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (rem < walk_f4) {
+            const int u = rem / (nlw * 8), rl = rem - u * (nlw * 8), l = rl >> 3, j = rl & 7;
+            auto at = [&](int r) { return quad ? tile[((size_t)(r >> 2) * U + u) * 4 + (r & 3)] : tile[(size_t)r * U + u]; };
+            const int rb0 = tb.rb0[l], ng = tb.groups[l];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (ng > 0) v[k] = k < ng ? at(rb0 + 8 * k + j) : 0.0f;          // position 4 j + k: group k of the chunk, accumulator j
-            else v[k] = 4 * j + k < tb.tail ? at(rb0 + 4 * j + k) : 0.0f;     // the tail line: position = RB
+            for (int k = 0; k < 4; k++) {
+                if (ng > 0) v[k] = k < ng ? at(rb0 + 8 * k + j) : 0.0f;          // position 4 j + k: group k of the chunk, accumulator j
+                else v[k] = 4 * j + k < tb.tail ? at(rb0 + 4 * j + k) : 0.0f;     // the tail line: position = RB
+            }
+        } else if (rem < walk_f4 + 2 * U && nlw < tb.lines) {
+            const int q = rem - walk_f4, u = q >> 1, p0 = (q & 1) * 4, rb0 = R - tb.tail;      // the block: slot u, its first or second 16 bytes
+            auto at = [&](int r) { return quad ? tile[((size_t)(r >> 2) * U + u) * 4 + (r & 3)] : tile[(size_t)r * U + u]; };
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = p0 + k < tb.tail ? at(rb0 + p0 + k) : 0.0f;
         }
         se_v4f o; o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
         ((se_v4f *)dst)[i] = o;
@@ -913,9 +926,10 @@ void launch_se_retile_quad(hipStream_t s, unsigned blocks, const float *src, flo
     hipLaunchKernelGGL(ranenv_se_retile_quad_kernel, dim3(blocks), dim3(256), 0, s, src, dst, n_quads, U, R);
 }
 void launch_se_retile_member_lines(hipStream_t s, unsigned blocks, const float *src, long long src_stride, int quad, float *dst, long long n_tiles,
-                                   int U, int R, const MemberLineTable &tb)
+                                   int U, int R, const MemberLineTable &tb, long long packed_f4)
 {
-    hipLaunchKernelGGL(ranenv_se_retile_member_lines_kernel, dim3(blocks), dim3(256), 0, s, src, src_stride, quad, dst, n_tiles * (long long)U * tb.lines * 8, U, R, tb);
+    const long long per_tile = packed_f4 > 0 ? packed_f4 : (long long)U * tb.lines * 8;
+    hipLaunchKernelGGL(ranenv_se_retile_member_lines_kernel, dim3(blocks), dim3(256), 0, s, src, src_stride, quad, dst, n_tiles * per_tile, U, R, tb, packed_f4);
 }
 void launch_se_from_power(hipStream_t s, unsigned blocks, const double *power, float *se, long long n, double tx_per_rb, double noise)
 {

@@ -46,7 +46,7 @@ struct ranenv {
     // SE gather mode (ranenv_set_se_mode): sidecars of the bound pool, owned by the handle
     int se_mode = RANENV_SE_STREAM;
     double *d_se_mean = nullptr; float *d_se_um = nullptr; int se_rp = 0;
-    // member lines (option "member_lines"): the handle's per-UE line copy of the bound pool [se_tiles_n][U][lines][32] that compact
+    // member lines (option "member_lines"): the handle's packed per-UE line copy of the bound pool, per tile [U][nlw][32] + tail block [U][8], that compact
     // streaming rollouts read instead of whole tiles (ml_stride floats per tile).  Built by the first rollout that would use it;
     // a rebind of the pool invalidates it (the buffer stays for the rebuild); ml_failed: the allocation failed, the variant is off
     float *d_ml = nullptr; int64_t ml_cap = 0; long long ml_stride = 0; bool ml_valid = false, ml_failed = false;
@@ -903,16 +903,44 @@ void member_lines_pairwise(const float *&line, int lo, int n, unsigned s, unsign
     full = fr; part = gr;
 }
 
+// The packed copy of a tile (ranenv_numeric.hpp, "Member lines"): [U][nlw][32] whole-group lines, then the tail block [U][8] where
+// R mod 8 != 0, the tile rounded up to whole lines.  false: more lines than the retile kernel's table holds.
+struct PackedLayout { int nlw; long long block_off, tile_bytes; };
+static bool member_lines_packed_layout(int U, int R, PackedLayout *pk, MemberLineTable *tb)
+{
+    if (!member_line_table(R, tb)) return false;
+    const int tail = R & 7;
+    pk->nlw = tb->lines - (tail ? 1 : 0);
+    pk->block_off = (long long)U * pk->nlw * 128;
+    pk->tile_bytes = (pk->block_off + (tail ? 32ll * U : 0) + 127) / 128 * 128;
+    return true;
+}
+
+// tiles [0, n_tiles) of a pool -> the packed copy at dst, in bursts (one launch writes walk lines, block and padding)
+static void retile_member_lines_packed(hipStream_t stream, const float *pool, long long pool_stride, int quad, float *dst, long long n_tiles, int U, int R,
+                                       const MemberLineTable &tb, const PackedLayout &pk)
+{
+    const long long burst = 1ll << 16, f4 = pk.tile_bytes / 16;
+    for (long long t0 = 0; t0 < n_tiles; t0 += burst) {
+        const long long n = n_tiles - t0 < burst ? n_tiles - t0 : burst;
+        long long blocks = (n * f4 + 255) / 256;
+        if (blocks > 256 * 64) blocks = 256 * 64;
+        launch_se_retile_member_lines(stream, (unsigned)blocks, pool + (size_t)t0 * (size_t)pool_stride, pool_stride, quad, dst + (size_t)t0 * (size_t)(pk.tile_bytes / 4),
+                                      n, U, R, tb, f4);
+    }
+}
+
 // The member-lines copy for the pool as it is bound now: there (true), or not and not to be built here -- no pool, a failed allocation
 // earlier, a capturing stream.  Built once per binding, in bursts like the sidecars, between a device and a stream synchronisation:
 // launches on other streams (the partitions' own) read it.  A failed allocation raises no error: the variant stays off for the handle.
 bool member_lines_ready(ranenv_handle h, hipStream_t stream)
 {
     if (h->ml_valid) return true;
-    MemberLineTable tb;
-    if (h->ml_failed || !h->kp.se_pool || h->se_tiles_n < 1 || stream_capturing(stream) || !member_line_table(h->cfg.n_rbs, &tb)) return false;
+    MemberLineTable tb; PackedLayout pk;
+    if (h->ml_failed || !h->kp.se_pool || h->se_tiles_n < 1 || stream_capturing(stream) || !member_lines_packed_layout(h->cfg.n_ues, h->cfg.n_rbs, &pk, &tb))
+        return false;
     const int U = h->cfg.n_ues, R = h->cfg.n_rbs;
-    const long long stride = (long long)U * tb.lines * 32;
+    const long long stride = pk.tile_bytes / 4;
     const int64_t count = h->se_tiles_n * stride;
     if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return false; }
     if (!(h->d_ml && h->ml_cap >= count)) {
@@ -922,14 +950,7 @@ bool member_lines_ready(ranenv_handle h, hipStream_t stream)
         h->allocs.push_back(ptr);
         h->d_ml = (float *)ptr; h->ml_cap = count;
     }
-    const long long burst = 1ll << 16;
-    for (long long t0 = 0; t0 < h->se_tiles_n; t0 += burst) {
-        const long long n = h->se_tiles_n - t0 < burst ? h->se_tiles_n - t0 : burst;
-        long long blocks = (n * U * tb.lines * 8 + 255) / 256;
-        if (blocks > 256 * 64) blocks = 256 * 64;
-        launch_se_retile_member_lines(stream, (unsigned)blocks, h->kp.se_pool + (size_t)t0 * (size_t)h->kp.se_stride, (long long)h->kp.se_stride,
-                                      h->kp.se_quad, h->d_ml + (size_t)t0 * (size_t)stride, n, U, R, tb);
-    }
+    retile_member_lines_packed(stream, h->kp.se_pool, (long long)h->kp.se_stride, h->kp.se_quad, h->d_ml, (long long)h->se_tiles_n, U, R, tb, pk);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); h->ml_failed = true; return false; }
     h->ml_stride = stride; h->ml_valid = true;
     return true;
@@ -1418,16 +1439,13 @@ int ranenv_member_lines_row_sums_host(const float *row_lines, int32_t n_rbs, int
 }
 
 // (restates member_line_sums + member_line_finish, ranenv_numeric.hpp.  The kernels' rows have at most two levels of halves -- A, B, T --;
-// this follows numpy's recursion to any depth: the left siblings along the right spine, outermost first, then the last leaf)
-int ranenv_member_lines_owner_tail_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part,
-                                             int32_t *walked_lines)
+// this follows numpy's recursion to any depth: the left siblings along the right spine, outermost first, then the last leaf.
+// `walk`: the UE's whole-group lines; `tail8`: the R mod 8 floats the owner adds -- null: they follow the walked lines, the old layout's tail line)
+static int member_owner_tail_sums(const float *walk, const float *tail8, int R, unsigned s, unsigned c, double *full, double *part)
 {
-    if (!row_lines || !full || !part || !walked_lines) return fail(nullptr, RANENV_E_INVALID, "null argument");
-    if (n_rbs < 1 || rb_start < 0 || rb_count < 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
-    const unsigned s = (unsigned)rb_start, c = (unsigned)rb_count;
-    const int R = (int)n_rbs, tail = R & 7;
+    const int tail = R & 7;
     // ---- the cluster's part: the whole-group lines alone
-    const float *line = row_lines;
+    const float *line = walk;
     std::vector<std::pair<double, double>> left;          // (f, g) of A, B, ...
     int lo = 0, n = R;
     while (n > 128) {
@@ -1439,15 +1457,64 @@ int ranenv_member_lines_owner_tail_sums_host(const float *row_lines, int32_t n_r
     }
     double t, tg;
     member_leaf_groups(line, lo, n, s, c, t, tg);                 // T
-    *walked_lines = (int32_t)((line - row_lines) / 32);
-    // ---- the owner's finish: its own tail line's first `tail` floats, then the halves from the innermost outwards
+    const int walked = (int)((line - walk) / 32);
+    // ---- the owner's finish: its own `tail` floats, then the halves from the innermost outwards
+    if (!tail8) tail8 = line;
     for (int k = 0; k < tail; k++) {
-        const double d = (double)line[k];
+        const double d = (double)tail8[k];
         t += d;
         tg = std::fma(d, ((unsigned)(R - tail + k) - s) < c ? 1.0 : 0.0, tg);
     }
     for (size_t i = left.size(); i-- > 0;) { t = left[i].first + t; tg = left[i].second + tg; }
     *full = t; *part = tg;
+    return walked;
+}
+
+int ranenv_member_lines_owner_tail_sums_host(const float *row_lines, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full, double *part,
+                                             int32_t *walked_lines)
+{
+    if (!row_lines || !full || !part || !walked_lines) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_rbs < 1 || rb_start < 0 || rb_count < 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    *walked_lines = (int32_t)member_owner_tail_sums(row_lines, nullptr, (int)n_rbs, (unsigned)rb_start, (unsigned)rb_count, full, part);
+    return RANENV_OK;
+}
+
+int ranenv_member_lines_packed_layout(int32_t n_ues, int32_t n_rbs, int32_t *walked_lines, int64_t *block_offset, int64_t *tile_bytes)
+{
+    if (!walked_lines || !block_offset || !tile_bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_ues < 1 || n_rbs < 1) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    PackedLayout pk; MemberLineTable tb;
+    if (!member_lines_packed_layout((int)n_ues, (int)n_rbs, &pk, &tb))
+        return fail(nullptr, RANENV_E_INVALID, "n_rbs %d needs more than %d lines per UE", (int)n_rbs, (int)MEMBER_LINES_MAX);
+    *walked_lines = pk.nlw; *block_offset = pk.block_off; *tile_bytes = pk.tile_bytes;
+    return RANENV_OK;
+}
+
+int ranenv_se_retile_member_lines_packed(const float *dev_pool, int32_t quad, int64_t tile_stride, float *dev_lines, int64_t n_tiles, int32_t n_ues,
+                                         int32_t n_rbs, void *stream)
+{
+    if (!dev_pool || !dev_lines) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_tiles < 0 || n_ues < 1 || n_rbs < 1) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    const int64_t need = quad ? (int64_t)((n_rbs + 3) / 4) * n_ues * 4 : (int64_t)n_ues * n_rbs;
+    if (tile_stride < need) return fail(nullptr, RANENV_E_INVALID, "tile_stride %lld is below a tile's %lld floats", (long long)tile_stride, (long long)need);
+    if (((uintptr_t)dev_lines & 15) != 0) return fail(nullptr, RANENV_E_INVALID, "the member-lines copy must be 16-byte aligned");
+    PackedLayout pk; MemberLineTable tb;
+    if (!member_lines_packed_layout((int)n_ues, (int)n_rbs, &pk, &tb))
+        return fail(nullptr, RANENV_E_INVALID, "n_rbs %d needs more than %d lines per UE", (int)n_rbs, (int)MEMBER_LINES_MAX);
+    retile_member_lines_packed((hipStream_t)stream, dev_pool, (long long)tile_stride, quad ? 1 : 0, dev_lines, (long long)n_tiles, (int)n_ues, (int)n_rbs, tb, pk);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, RANENV_E_HIP, "se_retile_member_lines_packed launch: %s", hipGetErrorString(e));
+    return RANENV_OK;
+}
+
+int ranenv_member_lines_packed_sums_host(const float *walk_lines, const float *tail_slot, int32_t n_rbs, int32_t rb_start, int32_t rb_count, double *full,
+                                         double *part)
+{
+    if (!full || !part) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_rbs < 1 || rb_start < 0 || rb_count < 0) return fail(nullptr, RANENV_E_INVALID, "bad sizes");
+    if ((n_rbs >= 8 && !walk_lines) || ((n_rbs & 7) != 0 && !tail_slot)) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    static const float none[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    (void)member_owner_tail_sums(walk_lines, tail_slot ? tail_slot : none, (int)n_rbs, (unsigned)rb_start, (unsigned)rb_count, full, part);
     return RANENV_OK;
 }
 

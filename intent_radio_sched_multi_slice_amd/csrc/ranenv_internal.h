@@ -352,7 +352,8 @@ void launch_se_retile_quad(hipStream_t, unsigned blocks, const float *src, float
 enum { MEMBER_LINES_MAX = 24 };
 struct MemberLineTable { int lines, tail; int rb0[MEMBER_LINES_MAX], groups[MEMBER_LINES_MAX]; };
 void launch_se_retile_member_lines(hipStream_t, unsigned blocks, const float *src, long long src_stride, int quad, float *dst, long long n_tiles,
-                                   int U, int R, const MemberLineTable &);
+                                   int U, int R, const MemberLineTable &, long long packed_f4 = 0);
+// the packed copy (ranenv_se_retile_member_lines_packed): packed_f4 = float4s per tile of the output (the tile stride), see ranenv_member_lines_packed_layout
 // ranenv_build_se_stats: stats [n][4][U] (mean, std, min, max per UE over the R RBs) of tiles [tile0, tile0 + n_tiles), the sidecar launch's shape
 void launch_se_tile_stats(hipStream_t, unsigned n_tiles, unsigned block, const float *pool, long long stride, long long tile0, int U, int R,
                           int quad, double *stats);

@@ -327,8 +327,9 @@ struct SeStreamLane {
 // still fetches practically every line.  The member-lines copy (ranenv_se_retile_member_lines; built by the handle, see
 // ranenv_host.cpp) gives every UE a row of whole lines of its own, laid out for EIGHT lanes per UE: the row is cut into row_sums'
 // leaves, a leaf's 8-RB groups into chunks of 4 groups, and chunk c of the leaf that starts at RB L is one line of 32 floats whose
-// position 4 j + g' holds x[L + 8 (4 c + g') + j] (+0.0 where that group lies beyond the leaf's last whole group); a row with
-// R mod 8 != 0 ends in one more line with those last RBs at positions 0 .. R mod 8 - 1 and +0.0 behind them.  Lane j of a cluster
+// position 4 j + g' holds x[L + 8 (4 c + g') + j] (+0.0 where that group lies beyond the leaf's last whole group); in the unpacked
+// layout (ranenv_se_retile_member_lines, the caller's buffers) a row with R mod 8 != 0 ends in one more line with those last RBs at
+// positions 0 .. R mod 8 - 1 and +0.0 behind them; the handle's copy packs them into a tail block (below).  Lane j of a cluster
 // of 8 loads 16 bytes at line + 16 j: four CONSECUTIVE elements of accumulator j's sequential chain, which it adds in order into
 // one f and one masked g -- nothing crosses lanes inside a leaf.  At a leaf's end the 8 accumulators meet in row_sums' tree
 // ((f0+f1)+(f2+f3))+((f4+f5)+(f6+f7)) as a butterfly over lanes xor 1, 2, 4 (IEEE addition is commutative: whichever operand order
@@ -337,13 +338,17 @@ struct SeStreamLane {
 // A wave walks its members 8 at a time: in pass q cluster c = lane >> 3 serves the wave's lane 8 q + c (its row offset and RB range
 // come through ds_bpermute, the sums go back the same way); a cluster whose lane holds no member gets an offset past the
 // descriptor, reads zeros and touches no memory.  DQ lines per lane rotate through fixed registers across the passes.
-// THE TAIL LINE IS NOT PART OF THE WALK.  It stays in the copy (line nl - 1 of a UE when R mod 8 != 0), but a row's last R mod 8
+// THE HANDLE'S COPY IS PACKED (ranenv_se_retile_member_lines_packed; ranenv_member_lines_packed_layout): per tile the whole-group
+// lines [U][nlw][32] in the order above, then -- R mod 8 != 0 -- ONE TAIL BLOCK [U][8]: UE u's last R mod 8 RBs at positions
+// 0 .. R mod 8 - 1 of its 32-byte slot, +0.0 behind them; the tile stride is rounded up to whole lines (+0.0).  A tail line of
+// its own per UE would be a 128-byte line fetched for 32 bytes: the block puts four owners' slots into a line.
+// THE TAIL IS NOT PART OF THE WALK.  A row's last R mod 8
 // RBs belong to one member and numpy adds them one after the other behind the last leaf's tree: nothing there is work for eight
-// lanes, let alone once per pass for all 64.  The clusters walk nlw = nl - 1 lines per member (R = 135: 4 = the queue's depth, one
+// lanes, let alone once per pass for all 64.  The clusters walk nlw lines per member (R = 135: 4 = the queue's depth, one
 // queue turn per pass; R < 8: none) and do NOT fold the row's last leaf: at the end of a pass up to three doubles per sum go back
 // to the owner -- A, the folded left half (rows of more than one leaf); B, the right half's first leaf (a split right half only);
-// T, the tree of the last leaf's whole groups (+0.0 where it has none).  The owner -- the lane that holds the member -- loads the
-// first 32 bytes of its own tail line when the walk is over (the queue's registers are free; the round trip is the one the rest of
+// T, the tree of the last leaf's whole groups (+0.0 where it has none).  The owner -- the lane that holds the member -- loads
+// its own 32-byte slot of the tail block when the walk is over (the queue's registers are free; the round trip is the one the rest of
 // the UE's state has behind the stream anyway) and finishes in numpy's order: t = T, t += e0, ..., t += e(tail-1), then full = t
 // | A + t | A + (B + t); `part` likewise with fma(d, in own range ? 1.0 : 0.0, .).  These are the additions the cluster made
 // when it walked the tail line: same operands, same grouping, once per TTI in 64 lanes side by side instead of once per pass.
@@ -372,7 +377,7 @@ struct MemberLines {
     v4f q[DQ];
     __amdgpu_buffer_rsrc_t rsrc;   // descriptor of exactly this tile's copy
     RowPlan pl;
-    int nl, nlw, total;            // wave-uniform: lines per UE in the copy; lines per UE the clusters walk (nl without the tail line); lines this wave walks = passes x nlw
+    int blk, nlw, total;           // wave-uniform: byte offset of the tile's tail block (= U x nlw x 128); lines per UE in the copy = lines the clusters walk; lines this wave walks = passes x nlw
     unsigned my_voff;              // owner role: byte offset of this lane's member row (OOB: the lane holds no member)
     int own_u; bool own_member;    // owner role: what my_voff was made of (member_line_sums overwrites it; the owner's tail loads form it again)
     // owner role, between member_line_sums and member_line_finish: what came back from the clusters, and the owner's own tail.  A row
@@ -390,23 +395,26 @@ struct MemberLines {
         dst = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ld_voff, il * 128, SE_AUX_NT));
         if (++il == nlw) { il = 0; iq++; }
     }
-    // the owner's own tail line (R mod 8 != 0): its first 32 bytes, straight into the lane that owns the member (zeros for a lane without one)
-    DEVFN void tail_request()
+    // the owner's own slot of the tile's tail block (R mod 8 != 0): 32 bytes, straight into the lane that owns the member (zeros for a
+    // lane without one; the block's base is the scalar part).  The second half holds RBs only where R mod 8 > 4 (wave-uniform).
+    DEVFN void tail_request(int tail)
     {
-        const unsigned tv = own_member ? (unsigned)(own_u * nl * 128) : OOB;
-        e0 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)tv, (nl - 1) * 128, SE_AUX_NT));
-        e1 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(tv + 16u), (nl - 1) * 128, SE_AUX_NT));
+        const unsigned tv = own_member ? (unsigned)(own_u * 32) : OOB;
+        e0 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)tv, blk, SE_AUX_NT));
+        if (tail > 4) e1 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(tv + 16u), blk, SE_AUX_NT));
+        else e1 = v4f{0.0f, 0.0f, 0.0f, 0.0f};
     }
     DEVFN void init(const float *tile_lines, int U, int R, bool member, int u)
     {
         pl = make_row_plan(R);
-        nl = member_lines_per_ue(pl, R);
-        nlw = nl - ((R & 7) ? 1 : 0);
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tile_lines), 0, U * nl * 128, 0x00020000);
+        nlw = member_lines_per_ue(pl, R) - ((R & 7) ? 1 : 0);
+        blk = U * nlw * 128;
+        // (the descriptor ends with the block's last slot: the padding up to the tile stride is nobody's)
+        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tile_lines), 0, blk + ((R & 7) ? U * 32 : 0), 0x00020000);
         const unsigned long long m = __builtin_amdgcn_ballot_w64(member);
         const int top = m != 0 ? 64 - __builtin_clzll(m) : 0;          // (members are the first lanes of an env; any pattern is served)
         total = ((top + 7) >> 3) * nlw;
-        my_voff = member ? (unsigned)(u * nl * 128) : OOB;
+        my_voff = member ? (unsigned)(u * nlw * 128) : OOB;
         own_u = u; own_member = member;
         iq = 0; il = 0; ld_voff = OOB;
 #pragma unroll
@@ -557,7 +565,7 @@ DEVFN void member_line_sums(MemberLines<DQ> &st, int R, unsigned s, unsigned c, 
     if (!hooked) after_issue();
     st.fa = fa; st.ga = ga; st.fb = fb; st.gb = gb; st.ft = ft; st.gt = gt;
     // (the queue's registers are free here)
-    if (tail > 0) st.tail_request();
+    if (tail > 0) st.tail_request(tail);
 }
 
 // The owner's finish: the row's last R mod 8 RBs belong to one member, and numpy adds them one after the other behind the last
