@@ -724,7 +724,7 @@ int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *d
  * ranenv_ppo_bind: allocates, per bound IBSched actor and critic slot (the one-net slots and a population's uniform ones), float32
  *   Adam moments m, v and gradient scratch in the slot's packed layout, and one step counter per (member, kind); all zero.  Refused
  *   with RANENV_E_STATE, before any device call: no bound inter actor + critic; a bf16 net among them; intra nets per slice
- *   (ranenv_set_intra_policy_networks / _value_networks); a mixed population (ranenv_ppo_bind_mixed, below, trains it); policy RANENV_POLICY_HEAD_NETWORK; a net beyond THE LDS
+ *   (ranenv_set_intra_policy_networks / _value_networks); a mixed population (ranenv_ppo_bind_mixed, below, trains it); policy RANENV_POLICY_HEAD_NETWORK (ranenv_ppo_bind_head / ranenv_ppo_update_head, below, train the head policies); a net beyond THE LDS
  *   PLAN: the workgroup keeps the 32-row input and every layer's 32-row output of one net in LDS at once (the backward pass overwrites
  *   them in place), 4096 + 128 * sum over the input and the layers of ld(width padded to 32) bytes with ld(x) = x + 36 if x % 64 else
  *   x + 4, at most 163 840.  [64, 64], [256, 256] and [400, 300] fit at S 10 / Us 100; [512, 512, 512] does not.
@@ -1187,6 +1187,65 @@ int ranenv_set_head_policy_source(ranenv_handle h, int32_t source);
 int ranenv_get_head_metrics(ranenv_handle h, double **dev_running, double **dev_episode_log, int32_t *episode_slots);
 int ranenv_collect_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, int32_t reward_col, double gamma, double lambda,
                         float *dev_obs_inter, float *dev_obs_intra, double *dev_reward, uint8_t *dev_done, void *stream);
+
+/* PPO update of the head policies: the SB3 PPO("MlpPolicy") agents of the reference -- SchedTWC and SchedColORAN on the head observation
+ * (agents/sched_twc.py:111-118, agents/sched_colran.py), IBSchedSB3 on player_0's row (agents/sb3_sched.py:104-111, sb3_pf_sched.py;
+ * RANENV_HEAD_SRC_INTER) -- trained on a ranenv_collect_head record.  Not a third `kind` of ranenv_ppo_update: SB3's Gaussian has a
+ * state-independent log_std [S] that is a trained parameter of its own, beside the actor and the critic.  ranenv_ppo_bind and
+ * ranenv_ppo_update keep every refusal they have (RANENV_POLICY_HEAD_NETWORK among them); the IBSched binding and the head binding
+ * may coexist on one handle and touch nothing of each other.
+ *
+ * The loss is SB3's PPO.train with clip_range_vf=None, per minibatch of n rows:
+ *     L = -mean(min(r A, clamp(r, 1 - clip, 1 + clip) A)) + vf_coeff * mean((V - vtarg)^2) - ent_coeff * mean(H),   r = exp(logp - logp_old)
+ *   logp = sum over ALL positions j = 0..S-1, ascending, of RANENV_INTER_LOGP_TERM(z_j, log_std_j) = ((-0.5 z_j) z_j - log_std_j) - 0.5 ln(2 pi),
+ *     z_j = (a_j - mean_j) / exp(log_std_j) from the recorded unclamped float64 action; no mask and no masked term.
+ *   H = sum over j of (log_std_j + 0.5) + 0.5 ln(2 pi).
+ *   Everything from the float32 net outputs and the float32 log_std on is float64; the gradient is rounded once to float32:
+ *     gl = d L / d logp of the row = -(A where 1 - clip <= r <= 1 + clip or r A < clamp(r) A, else 0) r / n,   ge = ent_coeff / n
+ *     at the outputs      d / d mean_j    = gl * z_j / sigma_j                       (rounded per row, then the backward pass)
+ *     for the parameter   d / d log_std_j = sum over the minibatch's rows of (gl * (z_j^2 - 1) - ge), accumulated in float64 in row order
+ *                                           by one thread per j, rounded once per minibatch
+ *   The joint L2 norm covers the actor, the critic AND log_std (SB3 clips over policy.parameters()); Adam runs over all three with
+ *   ONE step counter, in the float32 operation order stated for ranenv_ppo_update.  log_std is updated in the handle's own copy: the
+ *   next ranenv_collect_head acts on it, as on the new weights, with no rebind.
+ *   Statistics: the eight columns of ranenv_ppo_update.  [3] keeps this project's definition mean(logp_old - logp); SB3 logs another
+ *   estimator, mean((r - 1) - ln r).  A one-row minibatch under adv_norm 1 keeps the rule above (std 0: the advantage becomes 0); SB3
+ *   skips the normalisation of a one-row minibatch instead.
+ *   stable-baselines3 is not part of this project's test environment: parity with SB3 itself is UNPINNED; the normative statement is
+ *   the float64 torch-autograd twin (adapters.ppo_head_update_reference).
+ *
+ * ranenv_ppo_bind_head: allocates and zeroes Adam's m, v and the gradient scratch of the head actor slot, the head critic slot and the
+ *   [S] log_std vector, and one step counter.  RANENV_E_STATE, before any device call: no head actor and head critic bound; the
+ *   distribution is GAUSS_TANH; a net is bf16; the pair is beyond THE LDS PLAN (ranenv_ppo_lds_bytes of the pair, at most 163 840).
+ *   Re-binding: ranenv_set_head_policy_network zeroes the actor's and log_std's moments, the counter and -- they share the counter --
+ *   the critic's moments; ranenv_set_head_value_network likewise the other way round.  A bind that outgrows its slot ends the head
+ *   binding (ranenv_ppo_update_head: RANENV_E_STATE until the next ranenv_ppo_bind_head).  ranenv_set_head_policy_source does not touch
+ *   the binding: both sources feed rows of width 10*S.
+ * ranenv_ppo_update_head: ONE launch of ONE workgroup of 256 threads runs host_hparams->epochs epochs (<= max_epochs).
+ *     traj: the record as ranenv_collect_head filled it for n_steps TTIs under either head policy source; obs_head, action, logp, adv
+ *       and vtarg are required.
+ *     dev_order int32 [max_epochs][n_rows] of record rows t * B + b.  Minibatches are consecutive chunks of `minibatch` entries, a short
+ *       last chunk is a minibatch of its own.  An entry outside the record counts as a row of the minibatch and contributes nothing: the
+ *       row weight stays 1 / (entries of the minibatch), and [6] counts the live rows.  Under adv_norm 1 such an entry counts as an
+ *       advantage of 0 in the minibatch's mean and std.
+ *     dev_stats f64 [max_epochs][RANENV_PPO_STATS] (required); rows of epochs not run are not written.
+ *     dev_grad f32 [actor floats + critic floats + S] or NULL: the last minibatch's unclipped gradient, actor packed, then critic packed,
+ *       then log_std.
+ *   RANENV_E_INVALID: minibatch < 1, epochs < 0 or > max_epochs, a missing record field or argument.  RANENV_E_STATE: no head binding, or
+ *   what ranenv_ppo_bind_head refuses.  All before any device call.  epochs 0 or n_rows 0: nothing is launched.  The call keeps no
+ *   caller pointer and disarms nothing.  One agent works on ONE compute unit (the head path has no population).
+ * ranenv_ppo_head_layout: the packed floats of actor and critic -- the layout of dev_grad -- and the launch's LDS bytes.
+ * ranenv_ppo_head_state: device pointers to Adam's m and v of `which` (0 actor, 1 critic: packed layout; 2 log_std: [S]), the one
+ *   counter and the float count.
+ * ranenv_get_head_net_weights: ranenv_get_net_weights for the head actor (which 0) or the head critic (which 1).
+ * ranenv_get_head_log_std: the handle's log_std float32 [S] to the caller's device buffer on `stream`. */
+int ranenv_ppo_bind_head(ranenv_handle h, void *stream);
+int ranenv_ppo_update_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, const ranenv_ppo_hparams *host_hparams,
+                           const int32_t *dev_order, int32_t n_rows, int32_t max_epochs, double *dev_stats, float *dev_grad, void *stream);
+int ranenv_ppo_head_layout(ranenv_handle h, int64_t *actor_floats, int64_t *critic_floats, int64_t *lds_bytes);
+int ranenv_ppo_head_state(ranenv_handle h, int32_t which, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats);
+int ranenv_get_head_net_weights(ranenv_handle h, int32_t which, ranenv_mlp *out, void *stream);
+int ranenv_get_head_log_std(ranenv_handle h, float *dev_out, void *stream);
 
 /* Off-policy collection (SAC): the reference builds every SB3 agent in two flavours, agent_type "ppo" and "sac"
  * (agents/sched_twc.py:111-133, agents/sched_colran.py:111-133 on the head observation; agents/sb3_sched.py:104-120,

@@ -231,6 +231,12 @@ FUNCTIONS = {
     "ranenv_ppo_bind_mixed": (C.c_int, [_P, _P]),
     "ranenv_ppo_member_layout": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ranenv_ppo_lds_bytes": (C.c_int, [C.POINTER(Mlp), C.POINTER(Mlp), C.POINTER(C.c_int64)]),
+    "ranenv_ppo_bind_head": (C.c_int, [_P, _P]),
+    "ranenv_ppo_update_head": (C.c_int, [_P, _I32, C.POINTER(HeadTrajectory), C.POINTER(PpoHparams), _P, _I32, _I32, _P, _P, _P]),
+    "ranenv_ppo_head_layout": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ranenv_ppo_head_state": (C.c_int, [_P, _I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "ranenv_get_head_net_weights": (C.c_int, [_P, _I32, C.POINTER(Mlp), _P]),
+    "ranenv_get_head_log_std": (C.c_int, [_P, _P, _P]),
 }
 POPULATION_MAX = 64
 POPULATION_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}

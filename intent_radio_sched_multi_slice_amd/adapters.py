@@ -670,6 +670,121 @@ def ppo_update_reference(rec, kind: str, actor, critic, order, lo: int, hi: int,
             "state": state, "stats": stats, "grad": {"actor": pairs(list(grads[:na])), "critic": pairs(list(grads[na:]))}}
 
 
+# --------------------------------------------------------------------------------------------
+# the PPO update of the head policies (ranenv_ppo_update_head, include/ranenv.h): its shuffles and its float64 restatement
+# --------------------------------------------------------------------------------------------
+def ppo_head_row_order(rec, epochs: int, seed: int = 0) -> torch.Tensor:
+    """The row lists of ``ppo_update_head`` for a ``collect_head()`` record: int32 [epochs, T * B], per epoch an independent
+    permutation of the record rows ``t * B + b``, drawn where the record lives from ``seed``."""
+    T, B = rec["logp"].shape[:2]
+    dev = rec["logp"].device
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    # (31 random bits per row tie now and then; a stable sort makes "same seed, same order" independent of the sort's tie handling)
+    keys = torch.randint(0, 2 ** 31, (int(epochs), int(T) * int(B)), generator=gen, device=dev)
+    return torch.argsort(keys, dim=1, stable=True).to(torch.int32).contiguous()
+
+
+def ppo_head_update_reference(rec, actor, log_std, critic, order, epochs: int = 10, minibatch: int = 64, lr: float = 3e-4, clip: float = 0.2,
+                              vf_coeff: float = 0.5, ent_coeff: float = 0.0, grad_clip: float = 0.5, adv_norm: bool = True, betas=(0.9, 0.999),
+                              eps: float = 1e-5, act_actor: str = "tanh", act_critic: str = "tanh", state: Optional[dict] = None,
+                              dtype=torch.float64, slip: Optional[str] = None):
+    """THE NORMATIVE STATEMENT of ``ppo_update_head``, torch autograd on the CPU (float64 unless ``dtype``): SB3's ``PPO.train`` with
+    ``clip_range_vf=None`` on a ``collect_head()`` record -- ``actor`` / ``critic`` lists of ``(W, b)`` (copied), ``log_std`` [S] an
+    ``nn.Parameter`` of a diagonal Gaussian over ALL S positions, the joint clip ``clip_grad_norm_`` over actor, critic and ``log_std``,
+    Adam over the three with one counter (``ppo_adam_reference``: torch.optim.Adam's order).  Epoch k's rows are ``order[k]``,
+    minibatches consecutive chunks of ``minibatch`` with a short last one; every entry must lie inside the record.  "kl" is this
+    project's mean(logp_old - logp), not SB3's logged estimator; a one-row minibatch under ``adv_norm`` gets advantage 0 (SB3 skips the
+    normalisation there).  Returns {"actor", "critic": the trained layers, "log_std", "state": Adam's (params in the order actor,
+    critic, log_std), "stats": float64 [epochs, 8] as ``_lib.PPO_STATS``, "grad": {"actor": [(dW, db)], "critic": [...], "log_std"} of the
+    last minibatch, unclipped, "logp": the last minibatch's re-evaluated log-probabilities, "clip_fracs": every minibatch's}.
+    ``slip``: a deliberately wrong variant, for the tests that show the tolerances bite."""
+    cpu = {k: v.detach().cpu() for k, v in rec.items() if isinstance(v, torch.Tensor)}
+    order = torch.as_tensor(order).cpu().to(torch.int64)
+    leaf = lambda x: torch.as_tensor(x).detach().cpu().to(dtype).clone().requires_grad_(True)  # noqa: E731
+    actor, critic = [(leaf(w), leaf(b)) for w, b in actor], [(leaf(w), leaf(b)) for w, b in critic]
+    log_std = torch.nn.Parameter(torch.as_tensor(log_std).detach().cpu().to(dtype).clone())
+    log_std0 = log_std.detach().clone()
+    S = log_std.numel()
+    T = cpu["logp"].shape[0]
+    n_record = T * cpu["logp"].shape[1]
+    obs, action = cpu["obs_head"].reshape(n_record, 10 * S).to(dtype), cpu["action"].reshape(n_record, S).to(dtype)
+    cell = lambda name: cpu[name][:T].reshape(-1).to(dtype)  # noqa: E731
+    logp_old, adv_all, vtarg = cell("logp"), cell("adv"), cell("vtarg")
+    params = [p for net in (actor, critic) for wb in net for p in wb] + [log_std]
+    state = {} if state is None else state
+
+    def forward(x, layers, act):
+        for i, (w, b) in enumerate(layers):
+            x = x @ w.T + b
+            if i < len(layers) - 1:
+                x = torch.tanh(x) if act == "tanh" else torch.relu(x)
+        return x
+
+    stats, grads, logp, clip_fracs = np.zeros((epochs, 8)), None, None, []
+    n, step = order.shape[1], 0
+    for ep in range(epochs):
+        acc, n_mb = np.zeros(6), 0
+        for c0 in range(0, n, minibatch):
+            rows = order[ep, c0:min(c0 + minibatch, n)]
+            nb = rows.numel()
+            cells = (rows * (S + 1)) % n_record if slip == "cell_stride" else rows      # (the IBSched record's column 0)
+            ls = log_std0 + (log_std - log_std.detach()) if slip == "stale_log_std" and step >= 1 else log_std
+            mean = forward(obs[rows], actor, act_actor)
+            dist = torch.distributions.Normal(mean, torch.exp(ls).expand_as(mean))
+            terms = dist.log_prob(action[rows])
+            if slip == "short_logp":
+                terms = terms[:, :S - 1]
+            elif slip == "masked_term":                      # (the inter kind with position 0 masked)
+                terms = torch.cat([torch.full_like(terms[:, :1], LN_1E9 - HALF_LN_2PI), terms[:, 1:]], dim=1)
+            logp = terms.sum(dim=1)
+            ent_ls = ls.detach() if slip == "no_entropy_gradient" else ls
+            entropy = torch.distributions.Normal(mean, torch.exp(ent_ls).expand_as(mean)).entropy().sum(dim=1)
+            adv = adv_all[cells]
+            if adv_norm:
+                adv = (adv - adv.mean()) / ((adv.std() if nb > 1 else torch.zeros((), dtype=dtype)) + 1e-8)
+            ratio = torch.exp(logp - logp_old[cells])
+            surrogate = torch.minimum(ratio * adv, ratio.clamp(1.0 - clip, 1.0 + clip) * adv)
+            value_loss = ((forward(obs[rows], critic, act_critic)[:, 0] - vtarg[cells]) ** 2).mean()
+            policy_loss, ent = -surrogate.mean(), entropy.mean()
+            loss = policy_loss + vf_coeff * value_loss - ent_coeff * ent
+            for p in params:
+                p.grad = None
+            loss.backward()
+            grads = [p.grad.detach().clone() for p in params]
+            clipped = params[:-1] if slip == "log_std_outside_norm" else params
+            norm = float(torch.nn.utils.clip_grad_norm_(clipped, grad_clip if grad_clip > 0 else float("inf")))
+            with torch.no_grad():
+                ppo_adam_reference(params, [p.grad for p in params], state, lr, 0.0, betas, eps)
+            cf = float(((ratio < 1.0 - clip) | (ratio > 1.0 + clip)).to(dtype).mean())
+            clip_fracs.append(cf)
+            acc += nb * np.array([float(x.detach()) for x in (policy_loss, value_loss, ent, (logp_old[cells] - logp).mean())] + [cf, norm])
+            n_mb += 1
+            step += 1
+        stats[ep, :6], stats[ep, 6], stats[ep, 7] = acc / n, n, n_mb
+    pairs = lambda flat: [(flat[2 * i], flat[2 * i + 1]) for i in range(len(flat) // 2)]  # noqa: E731
+    na, nc = 2 * len(actor), 2 * len(critic)
+    return {"actor": [(w.detach(), b.detach()) for w, b in actor], "critic": [(w.detach(), b.detach()) for w, b in critic],
+            "log_std": log_std.detach(), "state": state, "stats": stats,
+            "grad": {"actor": pairs(grads[:na]), "critic": pairs(grads[na:na + nc]), "log_std": grads[-1]},
+            "logp": None if logp is None else logp.detach(), "clip_fracs": clip_fracs}
+
+
+def sb3_ppo_state_dict(actor_layers, log_std, critic_layers):
+    """The inverse of ``sb3_ppo_layers``: an SB3 ``PPO`` ``MlpPolicy`` state dict (separate pi / vf ``net_arch``) from the actor layers,
+    ``log_std`` [S] and the critic layers, e.g. ``head_net_weights("actor")``, ``head_log_std()``, ``head_net_weights("critic")`` after
+    ``ppo_update_head``: ``sb3_ppo_layers(sb3_ppo_state_dict(a, ls, c))`` returns the same tensors.  Key names restated from SB3's
+    documented module layout: parity with SB3 itself is unpinned, no real checkpoint has been written or read."""
+    if len(actor_layers) < 2 or len(critic_layers) < 2:
+        raise ValueError("an MlpPolicy has at least one hidden layer in front of action_net / value_net")
+    out = {"log_std": torch.as_tensor(log_std).detach().clone()}
+    for prefix, last, layers in (("mlp_extractor.policy_net.", "action_net", actor_layers), ("mlp_extractor.value_net.", "value_net", critic_layers)):
+        for i, (w, b) in enumerate(layers[:-1]):
+            out[f"{prefix}{2 * i}.weight"], out[f"{prefix}{2 * i}.bias"] = torch.as_tensor(w).detach().clone(), torch.as_tensor(b).detach().clone()
+        out[f"{last}.weight"], out[f"{last}.bias"] = torch.as_tensor(layers[-1][0]).detach().clone(), torch.as_tensor(layers[-1][1]).detach().clone()
+    return out
+
+
 def rllib_per_slice_layers(weights_by_policy, S: int, policy_prefix: str = "intra_slice_sched_"):
     """The S intra policies of a non-shared IBSched checkpoint (agents/ray_agent.py:432-460) from ``{policy_id: state_dict}`` as
     ``Algorithm.get_weights()`` returns it: ``(actors, critics)``, two lists of S layer stacks in slice order -- entry s from

@@ -841,14 +841,20 @@ class BatchedRanEnv:
     # ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
     PPO_STEPS_CAP = 1 << 13
 
-    def ppo_bind(self, mixed: bool = False) -> None:
+    def ppo_bind(self, mixed: bool = False, head: bool = False) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
         one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header).
         ``mixed=True`` (ranenv_ppo_bind_mixed): the population was bound with ``mixed=True`` -- members of differing shape -- and
         ``ppo_update`` trains each member on its own shape; every member's actor / critic pair must fit the LDS plan
-        (``ppo_lds_bytes``).  A mixed population is refused without it, a uniform one with it."""
+        (``ppo_lds_bytes``).  A mixed population is refused without it, a uniform one with it.
+        ``head=True`` (ranenv_ppo_bind_head): the state of the head actor, the head critic and ``log_std`` with one step counter, for
+        ``ppo_update_head``; it stands beside the IBSched nets' binding.  ``mixed`` and ``head`` exclude each other."""
+        if mixed and head:
+            raise ValueError("ppo_bind: mixed and head exclude each other")
         with torch.cuda.device(self.device):
-            if mixed:
+            if head:
+                self._check(self._lib.ranenv_ppo_bind_head(self._h, self._stream()), "ranenv_ppo_bind_head")
+            elif mixed:
                 self._check(self._lib.ranenv_ppo_bind_mixed(self._h, self._stream()), "ranenv_ppo_bind_mixed")
             else:
                 self._check(self._lib.ranenv_ppo_bind(self._h, self._stream()), "ranenv_ppo_bind")
@@ -1076,6 +1082,104 @@ class BatchedRanEnv:
         shapes, cache_key = self._head_shapes(self.HEAD_TRAJECTORY_SHAPES, "head_trajectories")
         return self._collect("collect_head", n_steps, record, _lib.HeadTrajectory, _lib.HEAD_TRAJECTORY_FIELDS, shapes,
                              cache_key, (self.B, self.S), self._lib.ranenv_collect_head, (col, float(gamma), float(lam)))
+
+    # -- the PPO update of the head policies (ranenv_ppo_bind_head / ranenv_ppo_update_head; include/ranenv.h) ----------------------
+    def ppo_update_head(self, rec, epochs=10, minibatch=64, lr=3e-4, clip=0.2, vf_coeff=0.5, ent_coeff=0.0, grad_clip=0.5, adv_norm="minibatch",
+                        betas=(0.9, 0.999), eps=1e-5, seed=0, order=None, grad: bool = False, force: bool = False):
+        """Train the head actor, the head critic and ``log_std`` on the ``collect_head()`` record ``rec`` in one launch of one workgroup
+        (ranenv_ppo_update_head): SB3's ``PPO.train`` with ``clip_range_vf=None`` -- the defaults are SB3's -- written in place, so the
+        next ``collect_head()`` acts on the trained policy.  ``order``: int32 [>= epochs, n_rows] record rows ``t * B + b`` (default:
+        ``adapters.ppo_head_row_order(rec, epochs, seed)``).  ``adv_norm``: "minibatch" or None; ``grad_clip`` <= 0 or None: no clipping.
+        Returns {name: float64 array [max epochs]} for the names of ``_lib.PPO_STATS``; ``grad=True`` adds "grad" [actor floats + critic
+        floats + S], the last minibatch's unclipped gradient: actor packed, critic packed, ``log_std``.  More than ``PPO_ROW_EPOCHS_CAP``
+        rows x epochs or ``PPO_STEPS_CAP`` optimiser steps is refused unless ``force``: one compute unit works through them."""
+        if adv_norm not in ("minibatch", "none", None):
+            raise ValueError('adv_norm is "minibatch" or None')
+        epochs, minibatch = int(epochs), int(minibatch)
+        T = int(rec["logp"].shape[0])
+        if order is None:
+            from .adapters import ppo_head_row_order
+            order = ppo_head_row_order(rec, max(epochs, 1), seed)
+        if order.dtype != torch.int32 or order.dim() != 2 or order.shape[0] < epochs or not order.is_contiguous():
+            raise ValueError(f"order: contiguous int32 [>= {epochs} epochs, n_rows]")
+        order = order.to(self.device)
+        max_epochs, n_rows = int(order.shape[0]), int(order.shape[1])
+        if not force and n_rows * max(epochs, 0) > self.PPO_ROW_EPOCHS_CAP:
+            raise RanEnvError(f"ppo_update_head: more than {self.PPO_ROW_EPOCHS_CAP} rows x epochs; one compute unit works through them -- "
+                              "train such a batch in torch, or pass force=True")
+        steps = -(-n_rows // max(minibatch, 1)) * max(epochs, 0)
+        if not force and steps > self.PPO_STEPS_CAP:
+            raise RanEnvError(f"ppo_update_head: more than {self.PPO_STEPS_CAP} optimiser steps ({steps}); every step passes over all "
+                              "parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
+        hp = _lib.PpoHparams()
+        hp.lr, hp.clip, hp.vf_coeff, hp.ent_coeff, hp.eps = float(lr), float(clip), float(vf_coeff), float(ent_coeff), float(eps)
+        hp.grad_clip = 0.0 if grad_clip is None else float(grad_clip)
+        hp.beta1, hp.beta2, hp.minibatch, hp.epochs, hp.adv_norm = float(betas[0]), float(betas[1]), minibatch, epochs, 1 if adv_norm == "minibatch" else 0
+        shapes, _ = self._head_shapes(self.HEAD_TRAJECTORY_SHAPES, "")
+        traj, keep = _lib.HeadTrajectory(), []
+        for f in _lib.HEAD_TRAJECTORY_FIELDS:
+            if f in rec:
+                dt, extra, shape = shapes[f]
+                keep.append(self._dev(rec[f], dt, (T + extra,) + shape(self.B, self.S), f))
+                setattr(traj, f, keep[-1].data_ptr())
+        stats = torch.zeros((max(max_epochs, 1), len(_lib.PPO_STATS)), dtype=torch.float64, device=self.device)
+        gbuf = None
+        if grad:
+            a, c = C.c_int64(), C.c_int64()
+            self._check(self._lib.ranenv_ppo_head_layout(self._h, C.byref(a), C.byref(c), None), "ranenv_ppo_head_layout")
+            gbuf = torch.zeros((a.value + c.value + self.S,), dtype=torch.float32, device=self.device)
+        none = torch.zeros(1, dtype=torch.int32, device=self.device)      # (a list without rows still is a list: not NULL)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_ppo_update_head(self._h, T, C.byref(traj), C.byref(hp), _ptr(order if order.numel() else none), n_rows,
+                                                         max_epochs, _ptr(stats), _ptr(gbuf), self._stream()), "ranenv_ppo_update_head")
+        host = stats.cpu().numpy()             # (synchronises: the launch is over, `order` and `rec` may go)
+        out = {name: host[:max_epochs, i] for i, name in enumerate(_lib.PPO_STATS)}
+        if grad:
+            out["grad"] = gbuf
+        return out
+
+    def ppo_head_layout(self) -> Dict[str, int]:
+        """The packed floats of the head "actor" and "critic" -- the layout of ``ppo_update_head(grad=True)["grad"]``, ``log_std`` [S]
+        behind them -- and "lds_bytes" of the launch (ranenv_ppo_head_layout)."""
+        a, c, lds = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.ranenv_ppo_head_layout(self._h, C.byref(a), C.byref(c), C.byref(lds)), "ranenv_ppo_head_layout")
+        return {"actor": a.value, "critic": c.value, "lds_bytes": lds.value}
+
+    _HEAD_NETS = {"actor": 0, "critic": 1, "log_std": 2}
+
+    def head_net_weights(self, which: str):
+        """The head "actor" or "critic" as it is on the device NOW -- after ``ppo_update_head``: the trained net -- as a list of
+        ``(W, b)`` tensors in torch ``Linear`` layout (ranenv_get_head_net_weights)."""
+        if which not in ("actor", "critic"):
+            raise ValueError('which is "actor" or "critic"')
+        out = _lib.Mlp()
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_get_head_net_weights(self._h, self._HEAD_NETS[which], C.byref(out), self._stream()), "ranenv_get_head_net_weights")
+            dims = list(out.dims[:out.n_hidden + 2])
+            layers = [(torch.empty((dims[i + 1], dims[i]), dtype=torch.float32, device=self.device),
+                       torch.empty((dims[i + 1],), dtype=torch.float32, device=self.device)) for i in range(len(dims) - 1)]
+            for i, (w, b) in enumerate(layers):
+                out.weight[i], out.bias[i] = w.data_ptr(), b.data_ptr()
+            self._check(self._lib.ranenv_get_head_net_weights(self._h, self._HEAD_NETS[which], C.byref(out), self._stream()), "ranenv_get_head_net_weights")
+        return layers
+
+    def head_log_std(self) -> torch.Tensor:
+        """A copy of the handle's ``log_std`` float32 [S] as it is NOW (ranenv_get_head_log_std)."""
+        out = torch.empty((self.S,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_get_head_log_std(self._h, _ptr(out), self._stream()), "ranenv_get_head_log_std")
+        return out
+
+    def ppo_head_state(self, which: str) -> Dict[str, torch.Tensor]:
+        """Zero-copy views of the optimiser state of the head "actor", "critic" (packed layout) or "log_std" ([S]): Adam's "m" and "v"
+        and "t", the one step counter (ranenv_ppo_head_state)."""
+        if which not in self._HEAD_NETS:
+            raise ValueError(f"which must be one of {sorted(self._HEAD_NETS)}")
+        pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._lib.ranenv_ppo_head_state(self._h, self._HEAD_NETS[which], C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), "ranenv_ppo_head_state")
+        return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
+                "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
+                "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}
 
     # -- off-policy (SAC) collection: replay ring, sampler, targets (include/ranenv.h "Off-policy collection") ----------------------
     REPLAY_SHAPES = {          # field -> (dtype, shape of one slot in terms of B, S)

@@ -156,6 +156,9 @@ struct ranenv {
     // ranenv_ppo_bind_mixed: the binding trains a mixed population; the packed floats of member m's net of role r on the device,
     // [4][POP_MAX] (0: the role is not bound), written at that bind and at every re-bind under it
     bool ppo_mixed = false; long long *d_ppo_floats = nullptr, ppo_floats[4][POP_MAX] = {};      // (... and the host copy the upload reads)
+    // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
+    // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
+    bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
     // ranenv_set_population_gae: a (gamma, lambda) pair per member for ranenv_collect's GAE pass
     bool gae_on = false; double gae_gamma[POP_MAX] = {}, gae_lambda[POP_MAX] = {};
     // The IBSched nets of a TTI's launches as they are bound (critics: a recording's), with the population map where a member's copy acts
@@ -2179,8 +2182,10 @@ static int ppo_floats_upload(ranenv_handle h, hipStream_t s)
 
 // A binding call has replaced `slot`'s nets (member < 0: all of them): their moments and their (member, kind) step counters start
 // again, on the caller's stream -- or, where the slot has no moments of its size, the PPO binding ends.
+static int ppo_head_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
 static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s)
 {
+    if (slot == &h->head || slot == &h->head_value) return ppo_head_rebound(h, slot, s);
     if (!h->ppo_on) return RANENV_OK;
     if (slot->role < 0 || slot->form == FORM_SLICE) return RANENV_OK;      // (a net the update never trains)
     const int kind = slot->role & 1;
@@ -2405,17 +2410,11 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
     return RANENV_OK;
 }
 
-int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv_mlp *out, void *stream)
+// Copy `member` of `slot` (`who` for the messages) unpacked to torch Linear layout: ranenv_get_net_weights / ranenv_get_head_net_weights
+static int net_export(ranenv_handle h, const ranenv::NetSlot *slot, int member, const char *who, ranenv_mlp *out, void *stream)
 {
-    if (!h || !out) return fail(h, RANENV_E_INVALID, "null argument");
-    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
-    const ranenv::NetSlot *slot = h->serving(role);
-    if (!slot) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
-    if (slot->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the %s nets are bound per slice", NET_ROLES[role].who);
-    const int members = (int)slot->member.size();
-    if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
     const PolicyNet &net = slot->member[(size_t)member];
-    if (net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the %s net is bf16: its float32 weights were rounded at bind", NET_ROLES[role].who);
+    if (net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the %s net is bf16: its float32 weights were rounded at bind", who);
     const int32_t *dims = slot->member_dims[(size_t)member].data();
     const int L = net.n_layers;
     for (int l = 0; l < L; l++)
@@ -2433,6 +2432,152 @@ int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv
         HIP_TRY(h, hipMemcpy2DAsync((void *)out->weight[l], sizeof(float) * K, src + net.w_off[l], sizeof(float) * net.kp[l], sizeof(float) * K, N, hipMemcpyDeviceToDevice, s));
         HIP_TRY(h, hipMemcpyAsync((void *)out->bias[l], src + net.b_off[l], sizeof(float) * N, hipMemcpyDeviceToDevice, s));
     }
+    return RANENV_OK;
+}
+
+int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv_mlp *out, void *stream)
+{
+    if (!h || !out) return fail(h, RANENV_E_INVALID, "null argument");
+    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
+    const ranenv::NetSlot *slot = h->serving(role);
+    if (!slot) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
+    if (slot->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the %s nets are bound per slice", NET_ROLES[role].who);
+    const int members = (int)slot->member.size();
+    if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
+    return net_export(h, slot, member, NET_ROLES[role].who, out, stream);
+}
+
+// ---- PPO update of the head policies (include/ranenv.h "PPO update of the head policies"; ranenv_ppo_update_kernel_head) -----------
+// What ranenv_ppo_bind_head refuses.  No device call.
+static int ppo_head_roles(ranenv_handle h, size_t &lds)
+{
+    if (!h->head.on || !h->head_value.on)
+        return fail(h, RANENV_E_STATE, "the head PPO update needs a bound head actor and head critic (ranenv_set_head_policy_network, ranenv_set_head_value_network)");
+    if (h->head_dist != RANENV_HEAD_DIST_GAUSS_CLIP) return fail(h, RANENV_E_STATE, "the head PPO update trains GAUSS_CLIP (PPO) policies: the head actor is GAUSS_TANH");
+    if (h->head.net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the head net is bf16");
+    if (h->head_value.net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the head value net is bf16");
+    lds = ppo_lds_bytes(h->head.net, &h->head_value.net);
+    if (lds > (size_t)PPO_LDS_MAX)
+        return fail(h, RANENV_E_STATE, "the head nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", lds, (int)PPO_LDS_MAX);
+    return RANENV_OK;
+}
+
+// ... and the bound state behind it, or RANENV_E_STATE
+static int ppo_head_bound(ranenv_handle h, size_t &lds)
+{
+    if (!h->ppo_head_on) return fail(h, RANENV_E_STATE, "no head PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind_head)");
+    if (const int rc = ppo_head_roles(h, lds); rc != RANENV_OK) return rc;
+    for (const ranenv::NetSlot *x : {&h->head, &h->head_value})
+        if (!x->opt || x->opt_cap < x->cap) return fail(h, RANENV_E_STATE, "a head net was bound after ranenv_ppo_bind_head: bind again");
+    return RANENV_OK;
+}
+
+// A binding call has replaced the head actor or the head critic: the moments of both nets and of log_std and the one counter start
+// again, on the caller's stream -- or, where the slot has no moments of its size, the head binding ends.
+static int ppo_head_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
+{
+    if (!h->ppo_head_on) return RANENV_OK;
+    if (!slot->opt || slot->cap > slot->opt_cap) { h->ppo_head_on = false; return RANENV_OK; }
+    for (ranenv::NetSlot *x : {&h->head, &h->head_value})
+        if (x->on && x->opt && x->cap <= x->opt_cap) HIP_TRY(h, hipMemsetAsync(x->opt, 0, sizeof(float) * 2 * (size_t)x->opt_cap, s));
+    HIP_TRY(h, hipMemsetAsync(h->d_head_ls_opt, 0, sizeof(float) * 2 * (size_t)h->cfg.n_slices, s));
+    HIP_TRY(h, hipMemsetAsync(h->d_ppo_head_t, 0, sizeof(int32_t), s));
+    return RANENV_OK;
+}
+
+int ranenv_ppo_bind_head(ranenv_handle h, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    size_t lds = 0;
+    if (const int rc = ppo_head_roles(h, lds); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t S = (size_t)h->cfg.n_slices;
+    if (!h->d_ppo_head_t) {
+        if (const int rc = dev_alloc(h, &h->d_ppo_head_t, (size_t)1); rc != RANENV_OK) return rc;
+        if (const int rc = dev_alloc(h, &h->d_head_ls_opt, 3 * S); rc != RANENV_OK) return rc;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->d_ppo_head_t, 0, sizeof(int32_t), s));
+    HIP_TRY(h, hipMemsetAsync(h->d_head_ls_opt, 0, sizeof(float) * 3 * S, s));
+    for (ranenv::NetSlot *x : {&h->head, &h->head_value}) {
+        if (x->opt_cap < x->cap) {       // (an outgrown one stays allocated, like the weights')
+            if (const int rc = dev_alloc(h, &x->opt, 3 * (size_t)x->cap); rc != RANENV_OK) return rc;
+            x->opt_cap = x->cap;
+        }
+        HIP_TRY(h, hipMemsetAsync(x->opt, 0, sizeof(float) * 3 * (size_t)x->opt_cap, s));
+    }
+    h->ppo_head_on = true;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_head_layout(ranenv_handle h, int64_t *actor_floats, int64_t *critic_floats, int64_t *lds_bytes)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    size_t lds = 0;
+    if (const int rc = ppo_head_roles(h, lds); rc != RANENV_OK) return rc;
+    if (actor_floats) *actor_floats = net_floats(h->head.net);
+    if (critic_floats) *critic_floats = net_floats(h->head_value.net);
+    if (lds_bytes) *lds_bytes = (int64_t)lds;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_head_state(ranenv_handle h, int32_t which, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (which < 0 || which > 2) return fail(h, RANENV_E_INVALID, "which %d (0 actor, 1 critic, 2 log_std)", which);
+    size_t lds = 0;
+    if (const int rc = ppo_head_bound(h, lds); rc != RANENV_OK) return rc;
+    const ranenv::NetSlot *x = which == 0 ? &h->head : &h->head_value;
+    const long long S = h->cfg.n_slices;
+    if (dev_m) *dev_m = which == 2 ? h->d_head_ls_opt : x->opt;
+    if (dev_v) *dev_v = which == 2 ? h->d_head_ls_opt + S : x->opt + x->opt_cap;
+    if (dev_t) *dev_t = h->d_ppo_head_t;
+    if (floats) *floats = which == 2 ? S : net_floats(x->net);
+    return RANENV_OK;
+}
+
+int ranenv_ppo_update_head(ranenv_handle h, int32_t n_steps, const ranenv_head_trajectory *traj, const ranenv_ppo_hparams *hp, const int32_t *order,
+                           int32_t n_rows, int32_t max_epochs, double *stats, float *grad, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    size_t lds = 0;
+    if (const int rc = ppo_head_bound(h, lds); rc != RANENV_OK) return rc;
+    if (n_steps < 1 || !traj || !hp || !order || !stats || n_rows < 0 || max_epochs < 0)
+        return fail(h, RANENV_E_INVALID, "n_steps >= 1, the record, the hyper-parameters, the row lists (n_rows >= 0, max_epochs >= 0) and dev_stats are required");
+    if (hp->minibatch < 1) return fail(h, RANENV_E_INVALID, "minibatch %d (>= 1)", hp->minibatch);
+    if (hp->epochs < 0) return fail(h, RANENV_E_INVALID, "epochs %d (>= 0)", hp->epochs);
+    if (hp->epochs > max_epochs) return fail(h, RANENV_E_INVALID, "epochs %d, the row lists and dev_stats have %d", hp->epochs, max_epochs);
+    if (!traj->obs_head || !traj->action || !traj->logp || !traj->adv || !traj->vtarg)
+        return fail(h, RANENV_E_INVALID, "the record needs obs_head, action, logp, adv and vtarg");
+    if ((long long)n_steps * h->cfg.batch > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "the record has more than 2^31 - 1 rows");
+    if (hp->epochs == 0 || n_rows == 0) return RANENV_OK;
+    PpoHeadArgs a{};
+    a.net[0] = ppo_net(&h->head); a.net[1] = ppo_net(&h->head_value);
+    const int S = h->cfg.n_slices;
+    a.log_std = h->d_head_log_std; a.ls_m = h->d_head_ls_opt; a.ls_v = a.ls_m + S; a.ls_g = a.ls_v + S;
+    a.order = order; a.n_rows = n_rows; a.T = n_steps; a.B = h->cfg.batch; a.S = S;
+    a.hp = *hp; a.traj = *traj; a.t = h->d_ppo_head_t; a.stats = stats; a.grad = grad;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, launch_ppo_update_head((hipStream_t)stream, lds, a));
+    return RANENV_OK;
+}
+
+int ranenv_get_head_net_weights(ranenv_handle h, int32_t which, ranenv_mlp *out, void *stream)
+{
+    if (!h || !out) return fail(h, RANENV_E_INVALID, "null argument");
+    if (which != 0 && which != 1) return fail(h, RANENV_E_INVALID, "which %d (0 actor, 1 critic)", which);
+    const ranenv::NetSlot *slot = which == 0 ? &h->head : &h->head_value;
+    const char *who = which == 0 ? "head" : "head value";
+    if (!slot->on) return fail(h, RANENV_E_STATE, "no %s net bound", who);
+    return net_export(h, slot, 0, who, out, stream);
+}
+
+int ranenv_get_head_log_std(ranenv_handle h, float *dev_out, void *stream)
+{
+    if (!h || !dev_out) return fail(h, RANENV_E_INVALID, "null argument");
+    if (!h->head.on || h->head_dist != RANENV_HEAD_DIST_GAUSS_CLIP) return fail(h, RANENV_E_STATE, "no GAUSS_CLIP head actor bound: the handle holds no log_std");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipMemcpyAsync(dev_out, h->d_head_log_std, sizeof(float) * (size_t)h->cfg.n_slices, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return RANENV_OK;
 }
 

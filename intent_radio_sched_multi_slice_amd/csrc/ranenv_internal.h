@@ -288,6 +288,21 @@ enum { PPO_LDS_MAX = 160 * 1024 };
 struct PpoMixed { const PolicyNet *tab[2][2]; const long long *floats; };
 // mixed null: the uniform instance
 hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoArgs &, const PpoMixed *mixed);
+// ranenv_ppo_update_head (include/ranenv.h "PPO update of the head policies"): the head actor and critic (net[0], net[1]; stride unused),
+// the handle's log_std [S] with its moments and gradient scratch, the call's hyper-parameters by value, the row lists
+// [max_epochs][n_rows] and the ranenv_collect_head record.  One workgroup.
+struct PpoHeadArgs {
+    PpoNet net[2];
+    float *log_std, *ls_m, *ls_v, *ls_g;  // [S] each
+    const int32_t *order; int n_rows;
+    int T, B, S;
+    ranenv_ppo_hparams hp;
+    ranenv_head_trajectory traj;
+    int32_t *t;                           // the one Adam step counter
+    double *stats;                        // [max_epochs][RANENV_PPO_STATS]
+    float *grad;                          // [actor floats + critic floats + S] or null
+};
+hipError_t launch_ppo_update_head(hipStream_t, size_t lds, const PpoHeadArgs &);
 
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block

@@ -233,6 +233,221 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_mixed(PpoArgs A,
 #undef PPO_NET
 #undef PPO_FLOATS
 
+// ---- the head policies (ranenv_ppo_update_head; include/ranenv.h "PPO update of the head policies") ----------------------------------
+// ONE workgroup trains the head actor, the head critic and the state-independent log_std [S] of SB3's Gaussian on a ranenv_collect_head
+// record.  A body of its own beside ranenv_ppo_body.hpp -- no population, no kinds, no mask, a third parameter tensor -- from the same
+// parts (net_layers<false, true>, ppo_backward, ppo_sum, ppo_adam, ppo_powi, the tile loop), so the two kernels above keep their text.
+// log_std is a weight this launch rewrites: its working copy lies in the fixed LDS region (`lsw`, loaded and reloaded by lane j at a
+// lane-dependent address behind Adam's own store of the same lane), never read through a wave-uniform address.  sig[j] = exp(log_std_j)
+// in float64 is parked in the reduction slots between two ppo_sum calls (refilled per minibatch behind the advantage pass).
+constexpr int PPO_HEAD_ROW_STATS = 7;     // PPO_ROW_STATS' six, then gl = dL/d(logp) of the row
+static_assert(PPO_FIXED >= (256 + NET_ROWS * PPO_HEAD_ROW_STATS) * 8 + NET_ROWS * 4 + 16 * 4, "the fixed LDS region holds the head kernel's row statistics and log_std");
+
+__device__ __forceinline__ void ppo_head_load_rows(const PolicyNet &net, const PpoHeadArgs &A, const int *idx, float *dst, int tid)
+{
+    load_rows(net.kp[0], 0, 0, dst, tid, [&](int r, int k) {
+        const int i = idx[r];
+        if (i < 0 || k >= net.in_dim) return 0.0f;
+        return A.traj.obs_head[(size_t)i * (size_t)(10 * A.S) + k];
+    });
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs A)
+{
+    extern __shared__ float lds[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const ranenv_ppo_hparams &hp = A.hp;
+    const int epochs = hp.epochs, minibatch = hp.minibatch, n = A.n_rows, S = A.S;
+    if (epochs <= 0 || minibatch < 1 || n <= 0) return;      // (the host refuses or serves them without a launch)
+
+    double *red = (double *)lds, *rowstat = red + 256, *sig = red;
+    int *rowidx = (int *)(rowstat + NET_ROWS * PPO_HEAD_ROW_STATS);
+    float *lsw = (float *)(rowidx + NET_ROWS);
+    float *act = lds + PPO_FIXED / 4;
+    const long long n_record = (long long)A.T * A.B;
+    int t = A.t[0];
+    if (tid < S) lsw[tid] = A.log_std[tid];
+    __syncthreads();
+
+#pragma unroll 1
+    for (int ep = 0; ep < epochs; ep++) {
+        const int32_t *list = A.order + (size_t)ep * (size_t)n;
+        double st_pl = 0.0, st_vl = 0.0, st_ent = 0.0, st_kl = 0.0, st_cf = 0.0, st_gn = 0.0, st_rows = 0.0;      // (thread 0's)
+        int n_mb = 0;
+#pragma unroll 1
+        for (int c0 = 0; c0 < n; c0 += minibatch) {
+            const int nb = n - c0 < minibatch ? n - c0 : minibatch;
+            const double wrow = 1.0 / (double)nb, ge = hp.ent_coeff * wrow;
+#pragma unroll 1
+            for (int k = 0; k < 2; k++) {
+                float *g = A.net[k].g;
+                const long long f = A.net[k].floats;
+#pragma unroll 1
+                for (long long i = tid; i < f; i += 256) g[i] = 0.0f;
+            }
+            double g_ls = 0.0;                 // (thread j < S: d/d log_std_j of the minibatch, rows in order)
+            double a_mean = 0.0, a_den = 1.0;
+            if (hp.adv_norm) {                 // one float64 pass over the minibatch's advantages (entries outside the record: 0)
+                auto adv_at = [&](int k) {
+                    const int i = list[c0 + k];
+                    if (i < 0 || i >= n_record) return 0.0;
+                    return (double)A.traj.adv[i];
+                };
+                double s = 0.0;
+#pragma unroll 1
+                for (int k = tid; k < nb; k += 256) s += adv_at(k);
+                a_mean = ppo_sum(red, s, tid) / (double)nb;
+                s = 0.0;
+#pragma unroll 1
+                for (int k = tid; k < nb; k += 256) { const double d = adv_at(k) - a_mean; s += d * d; }
+                const double ss = ppo_sum(red, s, tid);
+                a_den = (nb > 1 ? sqrt(ss / (double)(nb - 1)) : 0.0) + 1e-8;
+            }
+            if (tid < S) sig[tid] = exp((double)lsw[tid]);      // (published by the tile loop's first barrier; the slots are free until the norm)
+
+#pragma unroll 1
+            for (int t0 = 0; t0 < nb; t0 += NET_ROWS) {
+                __syncthreads();               // (the previous tile's backward pass and statistics are read)
+                if (tid < NET_ROWS) {
+                    int i = -1;
+                    if (t0 + tid < nb) { i = list[c0 + t0 + tid]; if (i < 0 || i >= n_record) i = -1; }
+                    rowidx[tid] = i;
+                }
+#pragma unroll 1
+                for (int k = 0; k < 2; k++) {
+                    const PpoNet &pn = A.net[k];
+                    const PolicyNet &net = pn.net;
+                    __syncthreads();           // (the tile's rows are listed; the actor's backward pass has read its rows)
+                    float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
+                    ppo_head_load_rows(net, A, rowidx, cur, tid);
+                    __syncthreads();
+                    net_layers<false, true>(net, pn.w, cur, nxt, lane, wave);
+                    const int np = net.np[net.n_layers - 1], ldo = net_ld(np);
+                    if (k == 1) {              // the critic: 2 vf_coeff (V - vtarg) / rows
+                        if (tid < NET_ROWS) {
+                            const int i = rowidx[tid];
+                            float *o = cur + tid * ldo;
+                            double vl = 0.0;
+                            if (i < 0) o[0] = 0.0f;
+                            else {
+                                const double d = (double)o[0] - (double)A.traj.vtarg[i];
+                                vl = d * d;
+                                o[0] = (float)(((2.0 * d) * hp.vf_coeff) * wrow);
+                            }
+                            rowstat[tid * PPO_HEAD_ROW_STATS + 5] = vl;
+                        }
+                    } else {
+                        // 1. the row's log-probability, ratio and statistics (thread r); the outputs stay
+                        if (tid < NET_ROWS) {
+                            const int i = rowidx[tid];
+                            const float *o = cur + tid * ldo;
+                            double *rs = rowstat + tid * PPO_HEAD_ROW_STATS;
+                            if (i < 0) rs[0] = rs[1] = rs[2] = rs[3] = rs[4] = rs[6] = 0.0;
+                            else {
+                                const double lp_old = (double)A.traj.logp[i];
+                                const double adv = hp.adv_norm ? ((double)A.traj.adv[i] - a_mean) / a_den : (double)A.traj.adv[i];
+                                double lp = 0.0, ent = 0.0;
+#pragma unroll 1
+                                for (int j = 0; j < S; j++) {
+                                    const double ls = (double)lsw[j];
+                                    const double z = (A.traj.action[(size_t)i * S + j] - (double)o[j]) / sig[j];
+                                    lp += RANENV_INTER_LOGP_TERM(z, ls);
+                                    ent += (ls + 0.5) + HALF_LN_2PI;
+                                }
+                                const double ratio = exp(lp - lp_old), c_lo = 1.0 - hp.clip, c_hi = 1.0 + hp.clip;
+                                const bool inside = ratio >= c_lo && ratio <= c_hi;
+                                const double s1 = ratio * adv, s2 = (ratio < c_lo ? c_lo : (ratio > c_hi ? c_hi : ratio)) * adv;
+                                const double dsdr = inside || s1 < s2 ? adv : 0.0;
+                                rs[0] = -(s1 < s2 ? s1 : s2); rs[1] = ent; rs[2] = lp_old - lp; rs[3] = inside ? 0.0 : 1.0; rs[4] = 1.0;
+                                rs[6] = -(dsdr * ratio) * wrow;
+                            }
+                        }
+                        __syncthreads();
+                        // 2. d/d log_std_j (thread j), rows in ascending order, float64
+                        if (tid < S) {
+                            const double sj = sig[tid];
+#pragma unroll 1
+                            for (int r = 0; r < NET_ROWS; r++) {
+                                const int i = rowidx[r];
+                                if (i < 0) continue;
+                                const double z = (A.traj.action[(size_t)i * S + tid] - (double)cur[r * ldo + tid]) / sj;
+                                g_ls += rowstat[r * PPO_HEAD_ROW_STATS + 6] * (z * z - 1.0) - ge;
+                            }
+                        }
+                        __syncthreads();
+                        // 3. d/d mean_j over the outputs, element by element; dead rows and padded columns: zeros
+#pragma unroll 1
+                        for (int e = tid; e < NET_ROWS * np; e += 256) {
+                            const int r = e / np, j = e - r * np, i = rowidx[r];
+                            float *o = cur + r * ldo + j;
+                            float v = 0.0f;
+                            if (i >= 0 && j < S) {
+                                const double sj = sig[j], z = (A.traj.action[(size_t)i * S + j] - (double)*o) / sj;
+                                v = (float)(rowstat[r * PPO_HEAD_ROW_STATS + 6] * (z / sj));
+                            }
+                            *o = v;
+                        }
+                    }
+                    __syncthreads();
+                    ppo_backward(net, pn.w, pn.g, cur, tid);
+                }
+                if (tid == 0) {                // (rows 0..31 in order; the barriers above have published them)
+#pragma unroll 1
+                    for (int r = 0; r < NET_ROWS; r++) {
+                        const double *rs = rowstat + r * PPO_HEAD_ROW_STATS;
+                        st_pl += rs[0]; st_ent += rs[1]; st_kl += rs[2]; st_cf += rs[3]; st_rows += rs[4]; st_vl += rs[5];
+                    }
+                }
+            }
+            __syncthreads();
+
+            // ---- joint norm over actor, critic and log_std; clip; Adam with the one counter -----------------------------------------
+            if (tid < S) A.ls_g[tid] = (float)g_ls;          // (rounded once; read back by this thread alone)
+            double s = 0.0;
+#pragma unroll 1
+            for (int k = 0; k < 2; k++) {
+                const float *g = A.net[k].g;
+                const long long f = A.net[k].floats;
+#pragma unroll 1
+                for (long long i = tid; i < f; i += 256) { const double x = (double)g[i]; s += x * x; }
+            }
+            if (tid < S) { const double x = (double)A.ls_g[tid]; s += x * x; }
+            const double norm = sqrt(ppo_sum(red, s, tid));
+            double sc = 1.0;
+            if (hp.grad_clip > 0.0) { sc = hp.grad_clip / (norm + 1e-6); sc = sc < 1.0 ? sc : 1.0; }
+            t += 1;
+            const float step = (float)(hp.lr / (1.0 - ppo_powi(hp.beta1, t))), sbc2 = (float)sqrt(1.0 - ppo_powi(hp.beta2, t));
+            const float b1 = (float)hp.beta1, omb1 = (float)(1.0 - hp.beta1), b2 = (float)hp.beta2, omb2 = (float)(1.0 - hp.beta2), eps = (float)hp.eps;
+#pragma unroll 1
+            for (int k = 0; k < 2; k++) ppo_adam(A.net[k].w, A.net[k].m, A.net[k].v, A.net[k].g, A.net[k].floats, (float)sc, b1, omb1, b2, omb2, step, sbc2, eps, tid);
+            ppo_adam(A.log_std, A.ls_m, A.ls_v, A.ls_g, S, (float)sc, b1, omb1, b2, omb2, step, sbc2, eps, tid);
+            if (tid < S) lsw[tid] = A.log_std[tid];          // (lane j reloads what lane j stored: the handle's copy the next collect acts on)
+            st_gn += norm * (double)nb;
+            n_mb += 1;
+            __syncthreads();                   // (the next minibatch reads the new weights and log_std)
+        }
+        if (tid == 0) {
+            double *out = A.stats + (size_t)ep * RANENV_PPO_STATS;
+            const double inv = 1.0 / (double)n;
+            out[0] = st_pl * inv; out[1] = st_vl * inv; out[2] = st_ent * inv; out[3] = st_kl * inv; out[4] = st_cf * inv; out[5] = st_gn * inv;
+            out[6] = st_rows; out[7] = (double)n_mb;
+        }
+    }
+    if (A.grad) {
+        float *out = A.grad;
+#pragma unroll 1
+        for (int k = 0; k < 2; k++) {
+            const float *g = A.net[k].g;
+            const long long f = A.net[k].floats;
+#pragma unroll 1
+            for (long long i = tid; i < f; i += 256) out[i] = g[i];
+            out += f;
+        }
+        if (tid < S) out[tid] = A.ls_g[tid];
+    }
+    if (tid == 0) A.t[0] = t;
+}
+
 }  // namespace
 
 namespace ranenv_dev {
@@ -255,6 +470,14 @@ hipError_t launch_ppo_update(hipStream_t s, int n_members, size_t lds, const Ppo
     static const hipError_t attr_mixed = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_mixed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
     if (attr_mixed != hipSuccess) return attr_mixed;
     hipLaunchKernelGGL(ranenv_ppo_update_kernel_mixed, dim3((unsigned)n_members, 2), dim3(256), lds, s, a, *mixed);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_update_head(hipStream_t s, size_t lds, const PpoHeadArgs &a)
+{
+    static const hipError_t attr = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_head, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(ranenv_ppo_update_kernel_head, dim3(1, 1), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
