@@ -8,6 +8,8 @@ Per iteration: one `collect()` for all members (every member's advantages under 
 in which workgroup (member, kind) runs that member's whole SGD schedule on the member's own net shape (`ppo_bind(mixed=True)`).  The
 architectures are drawn from those of the reference's `net_arch` choices whose 32-row activations fit the update's LDS plan
 (`ppo_lds_bytes`, asked before anything is bound): [64, 64], [256, 256], [400, 300] and [256, 256, 256]; [512, 512, 512] does not.
+With --wide the population is bound with `ppo_bind(mixed=True, wide=True)` -- two row buffers in LDS, the layers' rows parked in a
+scratch in global memory -- and `verybig` [512, 512, 512] is drawn with the others: all five architectures of the reference's search.
 Then the worst member by mean collected reward becomes a copy of the best through `set_population_member` -- trained weights into
 another member's extent, whatever the two shapes; the library restarts that member's optimiser -- and training goes on.
 --random: random initial weights -- no trial checkpoints are shipped; a few iterations show the plumbing, not a learning curve.
@@ -66,6 +68,7 @@ def main():
     ap.add_argument("--steps", type=int, default=64, help="TTIs per collected batch")
     ap.add_argument("--iterations", type=int, default=3, help="collect + update rounds before and after the exploit step")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--wide", action="store_true", help="bind the update wide: [512, 512, 512] becomes trainable")
     args = ap.parse_args()
     if not args.random:
         ap.error("give --random: no trial checkpoints are shipped")
@@ -78,7 +81,7 @@ def main():
 
     # only architectures a member can be trained with: the LDS need of the actor / critic pair of both kinds, before any bind
     def lds_need(h):
-        return max(ppo_lds_bytes([10 * S] + h + [2 * S], [10 * S] + h + [1]), ppo_lds_bytes([W] + h + [3], [W] + h + [1]))
+        return max(ppo_lds_bytes([10 * S] + h + [2 * S], [10 * S] + h + [1], wide=args.wide), ppo_lds_bytes([W] + h + [3], [W] + h + [1], wide=args.wide))
     trainable = [name for name, h in NET_ARCH.items() if lds_need(h) <= PPO_LDS_MAX]
     print("LDS bytes of the update per architecture: " + ", ".join(f"{n} {lds_need(h)}" for n, h in NET_ARCH.items()) + f"; trainable: {trainable}")
     rng = np.random.default_rng(args.seed)
@@ -94,7 +97,7 @@ def main():
     env.set_population(sizes=[args.envs_per_member] * G)
     env.set_policy_network([n["inter"] for n in nets], [n["intra"] for n in nets], stochastic=True, seed=args.seed, mixed=True)
     env.set_value_network([n["v_inter"] for n in nets], [n["v_intra"] for n in nets], mixed=True)
-    env.ppo_bind(mixed=True)
+    env.ppo_bind(mixed=True, wide=args.wide)
     env.reset()
     col = lambda k: [t[k] for t in trials]  # noqa: E731
 

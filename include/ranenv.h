@@ -727,7 +727,8 @@ int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *d
  *   (ranenv_set_intra_policy_networks / _value_networks); a mixed population (ranenv_ppo_bind_mixed, below, trains it); policy RANENV_POLICY_HEAD_NETWORK (ranenv_ppo_bind_head / ranenv_ppo_update_head, below, train the head policies); a net beyond THE LDS
  *   PLAN: the workgroup keeps the 32-row input and every layer's 32-row output of one net in LDS at once (the backward pass overwrites
  *   them in place), 4096 + 128 * sum over the input and the layers of ld(width padded to 32) bytes with ld(x) = x + 36 if x % 64 else
- *   x + 4, at most 163 840.  [64, 64], [256, 256] and [400, 300] fit at S 10 / Us 100; [512, 512, 512] does not.
+ *   x + 4, at most 163 840.  [64, 64], [256, 256] and [400, 300] fit at S 10 / Us 100; [512, 512, 512] does not (ranenv_ppo_bind_wide,
+ *   below, trains it).
  *   Re-binding: a binding call (ranenv_set_policy_network, _set_value_network, _set_population_policy / _value, _set_population_member)
  *   that fits a slot's buffer ZEROES the moments of the nets it replaces (of the one member for _set_population_member) and the
  *   step counters of their (member, kind) -- a new net starts a new optimiser.  Actor and critic of a kind share that counter, so the
@@ -789,7 +790,8 @@ int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp);
  *   rules are ranenv_ppo_bind's -- inter actor and inter critic bound, every bound role per member, float32, no nets per slice, no head
  *   policy -- and THE LDS PLAN holds PER MEMBER: a member whose actor / critic pair of a kind needs more than 163 840 bytes refuses the
  *   bind, the message naming the member, the kind and the bytes.  The reference's `verybig` net_arch, [512] x 3, therefore cannot be a
- *   member of a device-trained population; `small` [64, 64], `medium` [256, 256], `big` [400, 300] and `deep` [256, 256, 256] can.
+ *   member of a population trained under this binding (ranenv_ppo_bind_wide with mixed 1, below, takes it); `small` [64, 64], `medium`
+ *   [256, 256], `big` [400, 300] and `deep` [256, 256, 256] can.
  *   Moments and gradient scratch cover every member's extent (the largest member's packed size), whatever shape the member has now.
  * ranenv_ppo_update then runs a second instance of the kernel: workgroup (m, kind) reads member m's actor and critic descriptors from
  *   the role tables the mixed policy kernels read and is from there on a one-net workgroup on that member's shape, activation and layer
@@ -810,6 +812,30 @@ int ranenv_ppo_bind_mixed(ranenv_handle h, void *stream);
 int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int64_t *actor_floats, int64_t *critic_floats, int64_t *lds_bytes);
 int ranenv_ppo_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *bytes);
 int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv_mlp *out, void *stream);
+/* Nets beyond THE LDS PLAN -- the reference's `verybig` [512, 512, 512], the net of its pre-computed agent -- train under a second,
+ * opt-in binding, "wide".
+ * THE WIDE PLAN: the workgroup keeps TWO 32-row buffers in LDS, the input and the output rows of the layer it works on, and parks every
+ *   layer's input rows in a scratch of its own in global memory (written and read back by the workgroup alone, behind its barriers).
+ *   LDS: 4096 + 128 * max over the nets and layers of (ld(layer's input width) + ld(layer's output width)) bytes, widths padded to 32,
+ *   at most 136 192: every net the acting path accepts fits.  Scratch per workgroup: 32 * max over actor and critic of the sum over the
+ *   layers of ld(layer's input width) floats; actor and critic run one after the other and share it.
+ * ranenv_ppo_bind_wide: mixed 0 binds as ranenv_ppo_bind, mixed 1 as ranenv_ppo_bind_mixed (another value: RANENV_E_INVALID), with every
+ *   refusal of that entry in the same words -- except that the nets (mixed 1: every member's) are held against THE WIDE PLAN, not THE LDS
+ *   PLAN -- and allocates the scratch for members x 2 workgroups at the largest need among the bound nets.  A handle has ONE binding of
+ *   the IBSched nets, plain or wide: the later bind call replaces the earlier one and zeroes moments and counters, as a second
+ *   ranenv_ppo_bind does.
+ * ranenv_ppo_update under a wide binding launches the wide instances of the two kernels: same arguments, refusals, arithmetic and
+ *   summation order.  For nets that fit both plans the bytes -- weights, moments, counters, statistics, dev_grad -- equal the plain
+ *   binding's.  No update call allocates.  ranenv_ppo_layout and ranenv_ppo_member_layout report THE WIDE PLAN's lds_bytes while the
+ *   binding is wide.
+ * Re-binding under a wide binding follows the rules above (moments and counters restart).  ranenv_set_population_member under a mixed
+ *   wide binding checks the member's new shape against THE WIDE PLAN and against the scratch share the bind gave every workgroup: a
+ *   shape that parks more floats is RANENV_E_STATE before any device call and moves nothing.  A whole-role re-bind to such a shape
+ *   leaves ranenv_ppo_update RANENV_E_STATE until the next bind.
+ * ranenv_ppo_wide_bytes: THE WIDE PLAN's two formulas without a handle and without a device call, the counterpart of
+ *   ranenv_ppo_lds_bytes (either output may be NULL, not both). */
+int ranenv_ppo_bind_wide(ranenv_handle h, int32_t mixed, void *stream);
+int ranenv_ppo_wide_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *lds_bytes, int64_t *scratch_floats);
 
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,
  * results/gen_results.py:874-1022, kept as running sums so that a rollout needs no per-TTI read-back).  Per env 8

@@ -184,10 +184,8 @@ def _net_widths(layers):
     return dims
 
 
-def ppo_lds_bytes(actor_layers, critic_layers=None) -> int:
-    """Bytes of LDS the device PPO update needs for one member's actor / critic pair of a kind (ranenv_ppo_lds_bytes, the header's LDS
-    plan; at most 163 840): what decides, before anything is bound, whether an architecture can be a member of a device-trained
-    population.  ``actor_layers`` / ``critic_layers``: nets as for ``policy_net_layers``, or their widths ``[in, hidden..., out]``."""
+def _ppo_shape_pair(actor_layers, critic_layers):
+    """The two nets' shapes as ranenv_mlp (critic None: none) for the handle-free formulas"""
     mlps = []
     for layers in (actor_layers, critic_layers):
         if layers is None:
@@ -199,10 +197,37 @@ def ppo_lds_bytes(actor_layers, critic_layers=None) -> int:
         for i, d in enumerate(dims):
             mlp.dims[i] = d
         mlps.append(mlp)
+    return C.byref(mlps[0]), (C.byref(mlps[1]) if mlps[1] is not None else None)
+
+
+def _ppo_wide_bytes(actor_layers, critic_layers):
+    actor, critic = _ppo_shape_pair(actor_layers, critic_layers)
+    lds, park = C.c_int64(), C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_ppo_wide_bytes(actor, critic, C.byref(lds), C.byref(park)), "ranenv_ppo_wide_bytes")
+    return lds.value, park.value
+
+
+def ppo_lds_bytes(actor_layers, critic_layers=None, wide: bool = False) -> int:
+    """Bytes of LDS the device PPO update needs for one member's actor / critic pair of a kind (ranenv_ppo_lds_bytes, the header's LDS
+    plan; at most 163 840): what decides, before anything is bound, whether an architecture can be a member of a device-trained
+    population.  ``actor_layers`` / ``critic_layers``: nets as for ``policy_net_layers``, or their widths ``[in, hidden..., out]``.
+    ``wide=True``: under the wide plan of ``ppo_bind(wide=True)`` (ranenv_ppo_wide_bytes; at most 136 192 -- every net the acting
+    path accepts fits it)."""
+    if wide:
+        return _ppo_wide_bytes(actor_layers, critic_layers)[0]
+    actor, critic = _ppo_shape_pair(actor_layers, critic_layers)
     out = C.c_int64()
     lib = _lib.load()
-    _lib.check(lib, None, lib.ranenv_ppo_lds_bytes(C.byref(mlps[0]), C.byref(mlps[1]) if mlps[1] is not None else None, C.byref(out)), "ranenv_ppo_lds_bytes")
+    _lib.check(lib, None, lib.ranenv_ppo_lds_bytes(actor, critic, C.byref(out)), "ranenv_ppo_lds_bytes")
     return out.value
+
+
+def ppo_wide_scratch_floats(actor_layers, critic_layers=None) -> int:
+    """Floats of global memory in which ONE workgroup of a wide binding parks the 32 input rows of every layer of a net -- the larger
+    of the actor's and the critic's need, the two run one after the other (ranenv_ppo_wide_bytes); ``ppo_bind(wide=True)`` allocates
+    members x 2 workgroups of the largest need among the bound pairs."""
+    return _ppo_wide_bytes(actor_layers, critic_layers)[1]
 
 
 def population_means(result: Dict[str, np.ndarray], first_env) -> Dict[str, np.ndarray]:
@@ -696,6 +721,7 @@ class BatchedRanEnv:
 
     packed_net_floats = staticmethod(packed_net_floats)
     ppo_lds_bytes = staticmethod(ppo_lds_bytes)
+    ppo_wide_scratch_floats = staticmethod(ppo_wide_scratch_floats)
 
     def _gae_pairs(self, gamma, lam):
         """``collect`` / ``gae``: None for two scalars, else the members' (gamma [G], lam [G]) as float64 arrays -- a scalar beside a
@@ -841,18 +867,27 @@ class BatchedRanEnv:
     # ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
     PPO_STEPS_CAP = 1 << 13
 
-    def ppo_bind(self, mixed: bool = False, head: bool = False) -> None:
+    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
         one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header).
         ``mixed=True`` (ranenv_ppo_bind_mixed): the population was bound with ``mixed=True`` -- members of differing shape -- and
         ``ppo_update`` trains each member on its own shape; every member's actor / critic pair must fit the LDS plan
         (``ppo_lds_bytes``).  A mixed population is refused without it, a uniform one with it.
         ``head=True`` (ranenv_ppo_bind_head): the state of the head actor, the head critic and ``log_std`` with one step counter, for
-        ``ppo_update_head``; it stands beside the IBSched nets' binding.  ``mixed`` and ``head`` exclude each other."""
+        ``ppo_update_head``; it stands beside the IBSched nets' binding.  ``mixed`` and ``head`` exclude each other.
+        ``wide=True`` (ranenv_ppo_bind_wide), with or without ``mixed``: the binding for nets beyond the LDS plan, such as the
+        reference's ``verybig`` [512, 512, 512] -- two row buffers in LDS and the layers' rows parked in a scratch allocated here
+        (``ppo_lds_bytes(..., wide=True)``, ``ppo_wide_scratch_floats``).  Nets that fit both plans train to the same bytes under
+        either.  A handle has one binding of the IBSched nets: the later ``ppo_bind`` replaces the earlier one and restarts the
+        optimiser.  The head pair trains under the plain plan alone: ``wide`` and ``head`` exclude each other."""
         if mixed and head:
             raise ValueError("ppo_bind: mixed and head exclude each other")
+        if wide and head:
+            raise ValueError("ppo_bind: wide and head exclude each other (the head nets train under the plain plan)")
         with torch.cuda.device(self.device):
-            if head:
+            if wide:
+                self._check(self._lib.ranenv_ppo_bind_wide(self._h, 1 if mixed else 0, self._stream()), "ranenv_ppo_bind_wide")
+            elif head:
                 self._check(self._lib.ranenv_ppo_bind_head(self._h, self._stream()), "ranenv_ppo_bind_head")
             elif mixed:
                 self._check(self._lib.ranenv_ppo_bind_mixed(self._h, self._stream()), "ranenv_ppo_bind_mixed")

@@ -6,8 +6,8 @@ Seven objects, compiled in parallel, then linked:
                         bf16 weight packing)
   ranenv_policy.hip     the policy networks (RANENV_POLICY_NETWORK: MLP forwards on the f32 matrix cores, or per net on the bf16 ones)
   ranenv_ppo.hip        the PPO update of the bound nets (ranenv_ppo_update: forward, backward, clip and Adam, one workgroup per member;
-                        its two kernels -- uniform and mixed populations -- expand one body, ranenv_ppo_body.hpp; a third trains
-                        the head policies, ranenv_ppo_update_head)
+                        its four kernels -- uniform and mixed populations, each under the plain and the wide LDS plan -- expand one
+                        body, ranenv_ppo_body.hpp; a fifth trains the head policies, ranenv_ppo_update_head)
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants

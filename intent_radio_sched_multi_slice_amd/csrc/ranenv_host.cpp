@@ -156,6 +156,9 @@ struct ranenv {
     // ranenv_ppo_bind_mixed: the binding trains a mixed population; the packed floats of member m's net of role r on the device,
     // [4][POP_MAX] (0: the role is not bound), written at that bind and at every re-bind under it
     bool ppo_mixed = false; long long *d_ppo_floats = nullptr, ppo_floats[4][POP_MAX] = {};      // (... and the host copy the upload reads)
+    // ranenv_ppo_bind_wide: the binding follows the wide plan; the parked rows of the members' workgroups, [members][2][ppo_park_stride]
+    // floats, allocated at that bind (an outgrown one stays allocated, like the weights'), never by an update
+    bool ppo_wide = false; float *d_ppo_park = nullptr; long long ppo_park_stride = 0, ppo_park_cap = 0;
     // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
     // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
     bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
@@ -2044,6 +2047,15 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
         const ranenv::NetSlot &sa = h->nets[k][FORM_MEMBER], &sc = h->nets[2 + k][FORM_MEMBER];
         if (!sa.on || (!given[k] && !given[2 + k])) continue;
         const PolicyNet &a = given[k] ? ni[k] : sa.member[(size_t)member], *c = given[2 + k] ? &ni[2 + k] : (sc.on ? &sc.member[(size_t)member] : nullptr);
+        if (h->ppo_wide) {        // (the wide plan in its place, and the share of the scratch the bind gave every workgroup)
+            if (const size_t lds = ppo_wide_lds_bytes(a, c); lds > (size_t)PPO_LDS_MAX)
+                return fail(h, RANENV_E_STATE, "member %d: its new %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the bound PPO update has %d",
+                            member, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+            if (const long long p = ppo_wide_scratch(a, c); p > h->ppo_park_stride)
+                return fail(h, RANENV_E_STATE, "member %d: its new %s nets park %lld floats of rows per workgroup, ranenv_ppo_bind_wide allocated %lld",
+                            member, k ? "intra" : "inter", p, h->ppo_park_stride);
+            continue;
+        }
         if (const size_t lds = ppo_lds_bytes(a, c); lds > (size_t)PPO_LDS_MAX)
             return fail(h, RANENV_E_STATE, "member %d: its new %s nets need %zu bytes of LDS for their 32-row activations of all layers, the bound PPO update has %d",
                         member, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
@@ -2127,17 +2139,21 @@ int ranenv_set_population_gae(ranenv_handle h, int32_t n, const double *host_gam
 static_assert(sizeof(ranenv_ppo_hparams) == RANENV_PPO_HPARAMS_BYTES, "ranenv_ppo_hparams: 8 doubles and 4 int32");
 
 // Member m's nets of kind k among the slots the update trains (ppo_roles): the packed floats of its actor and critic (0: none) and
-// the LDS bytes their update needs.  A uniform binding's members all have copy 0's shape.
-static void ppo_member_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, int m, int k, long long &actor_floats, long long &critic_floats, size_t &lds)
+// the LDS bytes their update needs -- `wide`: under the wide plan, and `park`, the floats of scratch its workgroup parks its rows in.
+// A uniform binding's members all have copy 0's shape.
+static void ppo_member_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, int m, int k, long long &actor_floats, long long &critic_floats, size_t &lds,
+                             bool wide = false, long long *park = nullptr)
 {
     const size_t i = mixed ? (size_t)m : 0;
     const PolicyNet &a = slot[k]->member[i], *c = slot[2 + k] ? &slot[2 + k]->member[i] : nullptr;
-    actor_floats = net_floats(a); critic_floats = c ? net_floats(*c) : 0; lds = ppo_lds_bytes(a, c);
+    actor_floats = net_floats(a); critic_floats = c ? net_floats(*c) : 0; lds = wide ? ppo_wide_lds_bytes(a, c) : ppo_lds_bytes(a, c);
+    if (park) *park = wide ? ppo_wide_scratch(a, c) : 0;
 }
 
 // The slots the update trains, by role number: the serving ones (null: none bound), and the member count -- or what ranenv_ppo_bind
-// (mixed: ranenv_ppo_bind_mixed, whose LDS plan holds per member) refuses.  No device call.
-static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false)
+// (mixed: ranenv_ppo_bind_mixed, whose LDS plan holds per member; wide: ranenv_ppo_bind_wide, which checks the wide plan in its place)
+// refuses.  No device call.
+static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false, bool wide = false)
 {
     if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
     int n_pop = 0, n_one = 0;
@@ -2157,8 +2173,9 @@ static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members,
         if (!slot[k]) continue;
         for (int m = 0; m < (mixed ? members : 1); m++) {
             long long af, cf; size_t lds;
-            ppo_member_shape(slot, mixed, m, k, af, cf, lds);
+            ppo_member_shape(slot, mixed, m, k, af, cf, lds, wide);
             if (lds <= (size_t)PPO_LDS_MAX) continue;
+            if (wide) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
             if (mixed) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
             return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
         }
@@ -2209,15 +2226,33 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
     return h->ppo_mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-// ranenv_ppo_bind / ranenv_ppo_bind_mixed
-static int ppo_bind(ranenv_handle h, bool mixed, void *stream)
+// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide
+static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    if (const int rc = ppo_roles(h, slot, members, mixed); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
+    if (wide) {         // the parked rows: the largest need over the members and the kinds, for members x 2 workgroups
+        long long park = 0;
+        for (int k = 0; k < 2; k++) {
+            if (!slot[k]) continue;
+            for (int m = 0; m < (mixed ? members : 1); m++) {
+                long long af, cf, p; size_t lds;
+                ppo_member_shape(slot, mixed, m, k, af, cf, lds, true, &p);
+                park = p > park ? p : park;
+            }
+        }
+        const long long need = park * 2 * members;
+        if (h->ppo_park_cap < need) {
+            if (const int rc = dev_alloc(h, &h->d_ppo_park, (size_t)need); rc != RANENV_OK) return rc;
+            h->ppo_park_cap = need;
+        }
+        h->ppo_park_stride = h->ppo_park_cap / (2 * members);       // (a kept larger allocation serves larger re-bound shapes)
+        h->ppo_park_stride -= h->ppo_park_stride % 4;               // (every workgroup's share starts on a 16-byte boundary)
+    }
     if (!h->d_ppo_t) {
         if (const int rc = dev_alloc(h, &h->d_ppo_t, (size_t)POP_MAX * 2); rc != RANENV_OK) return rc;
         if (const int rc = dev_alloc(h, &h->d_ppo_hp, (size_t)POP_MAX); rc != RANENV_OK) return rc;
@@ -2233,20 +2268,37 @@ static int ppo_bind(ranenv_handle h, bool mixed, void *stream)
         }
         HIP_TRY(h, hipMemsetAsync(slot[r]->opt, 0, sizeof(float) * 3 * (size_t)slot[r]->opt_cap, s));
     }
-    h->ppo_on = true; h->ppo_mixed = mixed;
+    h->ppo_on = true; h->ppo_mixed = mixed; h->ppo_wide = wide;
     return mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-int ranenv_ppo_bind(ranenv_handle h, void *stream) { return ppo_bind(h, false, stream); }
-int ranenv_ppo_bind_mixed(ranenv_handle h, void *stream) { return ppo_bind(h, true, stream); }
+int ranenv_ppo_bind(ranenv_handle h, void *stream) { return ppo_bind(h, false, false, stream); }
+int ranenv_ppo_bind_mixed(ranenv_handle h, void *stream) { return ppo_bind(h, true, false, stream); }
+int ranenv_ppo_bind_wide(ranenv_handle h, int32_t mixed, void *stream)
+{
+    if (mixed != 0 && mixed != 1) return fail(h, RANENV_E_INVALID, "mixed %d (0 as ranenv_ppo_bind, 1 as ranenv_ppo_bind_mixed)", mixed);
+    return ppo_bind(h, mixed == 1, true, stream);
+}
 
 // The bound state behind ranenv_ppo_bind / _bind_mixed, or RANENV_E_STATE
 static int ppo_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
 {
     if (!h->ppo_on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
-    if (const int rc = ppo_roles(h, slot, members, h->ppo_mixed); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, slot, members, h->ppo_mixed, h->ppo_wide); rc != RANENV_OK) return rc;
     for (int r = 0; r < 4; r++)
         if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after ranenv_ppo_bind: bind again", NET_ROLES[r].who);
+    if (!h->ppo_wide) return RANENV_OK;
+    // a wide binding: every workgroup's parked rows fit the share of the scratch it was given at bind
+    if ((long long)members * 2 * h->ppo_park_stride > h->ppo_park_cap) return fail(h, RANENV_E_STATE, "the population has grown since ranenv_ppo_bind_wide: bind again");
+    for (int k = 0; k < 2; k++) {
+        if (!slot[k]) continue;
+        for (int m = 0; m < (h->ppo_mixed ? members : 1); m++) {
+            long long af, cf, p; size_t lds;
+            ppo_member_shape(slot, h->ppo_mixed, m, k, af, cf, lds, true, &p);
+            if (p > h->ppo_park_stride)
+                return fail(h, RANENV_E_STATE, "the %s nets park %lld floats of rows per workgroup, ranenv_ppo_bind_wide allocated %lld: bind again", k ? "intra" : "inter", p, h->ppo_park_stride);
+        }
+    }
     return RANENV_OK;
 }
 
@@ -2265,14 +2317,14 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    const bool mixed = h->pop_mixed();
-    if (const int rc = ppo_roles(h, slot, members, mixed); rc != RANENV_OK) return rc;
+    const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide;
+    if (const int rc = ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
     long long g = 0; size_t lds = 0;
     for (int k = 0; k < 2; k++) {
         if (!slot[k]) continue;
         for (int m = 0; m < (mixed ? members : 1); m++) {
             long long af, cf; size_t l;
-            ppo_member_shape(slot, mixed, m, k, af, cf, l);
+            ppo_member_shape(slot, mixed, m, k, af, cf, l, wide);
             g = af + cf > g ? af + cf : g;
             lds = l > lds ? l : lds;
         }
@@ -2287,23 +2339,22 @@ int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int6
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    const bool mixed = h->pop_mixed();
-    if (const int rc = ppo_roles(h, slot, members, mixed); rc != RANENV_OK) return rc;
+    const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide;
+    if (const int rc = ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
     if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
     if (kind != 0 && kind != 1) return fail(h, RANENV_E_INVALID, "kind %d (0 inter, 1 intra)", kind);
     if (!slot[kind]) return fail(h, RANENV_E_STATE, "no %s actor bound", kind ? "intra" : "inter");
     long long af, cf; size_t lds;
-    ppo_member_shape(slot, mixed, member, kind, af, cf, lds);
+    ppo_member_shape(slot, mixed, member, kind, af, cf, lds, wide);
     if (actor_floats) *actor_floats = af;
     if (critic_floats) *critic_floats = cf;
     if (lds_bytes) *lds_bytes = (int64_t)lds;
     return RANENV_OK;
 }
 
-int ranenv_ppo_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *bytes)
+// The padded layouts of an actor / critic pair given by shape alone (critic null: none): ranenv_ppo_lds_bytes / ranenv_ppo_wide_bytes
+static int ppo_shape_pair(const ranenv_mlp *actor, const ranenv_mlp *critic, PolicyNet (&net)[2])
 {
-    if (!actor || !bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
-    PolicyNet net[2] = {};
     const ranenv_mlp *given[2] = {actor, critic};
     for (int i = 0; i < 2; i++) {
         const ranenv_mlp *m = given[i];
@@ -2315,7 +2366,25 @@ int ranenv_ppo_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int6
         net[i].n_layers = m->n_hidden + 1;
         net_pack(m->dims, net[i].n_layers, RANENV_NET_F32, net[i], 0);
     }
+    return RANENV_OK;
+}
+
+int ranenv_ppo_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *bytes)
+{
+    if (!actor || !bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    PolicyNet net[2] = {};
+    if (const int rc = ppo_shape_pair(actor, critic, net); rc != RANENV_OK) return rc;
     *bytes = (int64_t)ppo_lds_bytes(net[0], critic ? &net[1] : nullptr);
+    return RANENV_OK;
+}
+
+int ranenv_ppo_wide_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *lds_bytes, int64_t *scratch_floats)
+{
+    if (!actor || (!lds_bytes && !scratch_floats)) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    PolicyNet net[2] = {};
+    if (const int rc = ppo_shape_pair(actor, critic, net); rc != RANENV_OK) return rc;
+    if (lds_bytes) *lds_bytes = (int64_t)ppo_wide_lds_bytes(net[0], critic ? &net[1] : nullptr);
+    if (scratch_floats) *scratch_floats = (int64_t)ppo_wide_scratch(net[0], critic ? &net[1] : nullptr);
     return RANENV_OK;
 }
 
@@ -2364,7 +2433,7 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
         if (hp[m].epochs < 0) return fail(h, RANENV_E_INVALID, "member %d: epochs %d (>= 0)", m, hp[m].epochs);
         max_epochs = hp[m].epochs > max_epochs ? hp[m].epochs : max_epochs;
     }
-    const bool mixed = h->ppo_mixed;
+    const bool mixed = h->ppo_mixed, wide = h->ppo_wide;
     if (!traj->obs_inter || !traj->mask_inter || !traj->action_inter || !traj->logp || !traj->adv || !traj->vtarg)
         return fail(h, RANENV_E_INVALID, "the record needs obs_inter, mask_inter, action_inter, logp, adv and vtarg");
     if (intra && (!traj->obs_intra || !traj->action_intra || (slot[1]->net.layout == RANENV_NET_IN_MASK_OBS && !traj->mask_intra)))
@@ -2391,7 +2460,7 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
         if (!slot[k]) continue;
         for (int m = 0; m < (mixed ? members : 1); m++) {
             long long af, cf; size_t l;
-            ppo_member_shape(slot, mixed, m, k, af, cf, l);
+            ppo_member_shape(slot, mixed, m, k, af, cf, l, wide);
             gf = af + cf > gf ? af + cf : gf;
             if (a.net[k][0].net.n_layers > 0) lds = l > lds ? l : lds;
         }
@@ -2406,7 +2475,8 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)members, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_ppo_update(s, members, lds, a, mixed ? &x : nullptr));
+    const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_bound: every workgroup's rows fit its share)
+    HIP_TRY(h, launch_ppo_update(s, members, lds, a, mixed ? &x : nullptr, wide ? &y : nullptr));
     return RANENV_OK;
 }
 

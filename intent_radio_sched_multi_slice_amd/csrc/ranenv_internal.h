@@ -286,8 +286,14 @@ enum { PPO_LDS_MAX = 160 * 1024 };
 // from floats[role * POP_MAX + m] (device, written at bind and re-bind; 0: not bound).  PpoNet's net / floats are member 0's there:
 // read for "is the role bound" alone.  lds: the largest ppo_lds_bytes over the members and the kinds of the call.
 struct PpoMixed { const PolicyNet *tab[2][2]; const long long *floats; };
-// mixed null: the uniform instance
-hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoArgs &, const PpoMixed *mixed);
+// A wide binding's update (ranenv_ppo_bind_wide), beside PpoArgs: two row buffers in LDS, and workgroup (m, kind) parks every layer's 32
+// input rows in its own `stride` floats of `scratch` at (m * 2 + kind) * stride -- slab l at stride net_ld(kp[l]), back to back; actor and
+// critic run one after the other and share it.  The LDS bytes and scratch floats of one actor / critic pair under that plan:
+struct PpoWide { float *scratch; long long stride; };
+size_t ppo_wide_lds_bytes(const PolicyNet &actor, const PolicyNet *critic);
+long long ppo_wide_scratch(const PolicyNet &actor, const PolicyNet *critic);
+// mixed null: the uniform instance; wide non-null: the wide instance of either
+hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoArgs &, const PpoMixed *mixed, const PpoWide *wide = nullptr);
 // ranenv_ppo_update_head (include/ranenv.h "PPO update of the head policies"): the head actor and critic (net[0], net[1]; stride unused),
 // the handle's log_std [S] with its moments and gradient scratch, the call's hyper-parameters by value, the row lists
 // [max_epochs][n_rows] and the ranenv_collect_head record.  One workgroup.

@@ -180,6 +180,57 @@ __device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb
 }
 __device__ __forceinline__ void net_layers(const PolicyNet &net, float *&cur, float *&nxt, int lane, int wave) { net_layers(net, net.w, cur, nxt, lane, wave); }
 
+// ONE f32 layer `l` of `net` from the 32 rows at `in` (stride net_ld(kp[l])) to `out` (stride net_ld(np[l])): net_layers<false>'s tiling,
+// k order, bias and activation, operation for operation -- the wide PPO update's forward pass (ranenv_ppo.hip), which decides per
+// layer where the rows lie.  Ends without a barrier.  CHANGE THE TWO TOGETHER: the wide update is bit-equal to the plain one only
+// while they agree, and tests/test_gpu_ppo_wide.py holds that.
+__device__ __forceinline__ void net_layer_f32(const PolicyNet &net, int l, const float *wb, const float *in, float *out, int lane, int wave)
+{
+    const int q = lane >> 4, c = lane & 15;
+    const bool last = l == net.n_layers - 1;
+    const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N);
+    const float *W = wb + net.w_off[l], *bias = wb + net.b_off[l];
+    for (int nt = wave; nt < N / 32; nt += 4) {
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int j = 0; j < 2; j++) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float4 *w0 = (const float4 *)(W + (size_t)(nt * 32 + c) * K) + q;
+        const float4 *w1 = (const float4 *)(W + (size_t)(nt * 32 + 16 + c) * K) + q;
+        const float *x0 = in + c * ldi + 4 * q, *x1 = in + (16 + c) * ldi + 4 * q;
+        float4 b0 = w0[0], b1 = w1[0];
+        for (int k0 = 0; k0 < K; k0 += 16) {
+            const int kn = (k0 + 16 < K ? k0 + 16 : k0) >> 2;
+            const float4 nb0 = w0[kn], nb1 = w1[kn];
+            const float4 a0 = *(const float4 *)(x0 + k0), a1 = *(const float4 *)(x1 + k0);
+            const float av[2][4] = {{a0.x, a0.y, a0.z, a0.w}, {a1.x, a1.y, a1.z, a1.w}};
+            const float bv[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                    for (int ni = 0; ni < 2; ni++)
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mi][j], bv[ni][j], acc[mi][ni], 0, 0, 0);
+            b0 = nb0; b1 = nb1;
+        }
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+            for (int ni = 0; ni < 2; ni++) {
+                const int col = nt * 32 + ni * 16 + c;
+                const float bb = bias[col];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    float v = acc[mi][ni][r] + bb;
+                    if (!last) v = net.act == RANENV_ACT_RELU ? fmaxf(v, 0.0f) : tanhf(v);
+                    out[(mi * 16 + q * 4 + r) * ldo + col] = v;
+                }
+            }
+    }
+}
+
 constexpr double HALF_LN_2PI = 0.9189385332046727;      // 0.5 ln(2 pi)
 constexpr double LN_1E9 = 20.72326583694641;            // ln(1e9): -ln of the masked positions' std
 

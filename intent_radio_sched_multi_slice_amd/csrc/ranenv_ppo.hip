@@ -16,6 +16,9 @@
 // The weights this launch reads were written by the launch itself one minibatch earlier: every weight read is a vector load at a
 // lane-dependent address behind a workgroup barrier (the forward's float4 / bias loads, the backward's W loads, Adam's own) -- none
 // through the scalar cache, which does not see the vector stores.
+// Nets beyond that LDS plan train under the WIDE plan (ranenv_ppo_bind_wide; "the wide plan" below): two row buffers in LDS, every
+// layer's input rows parked in a scratch of the workgroup's own in global memory -- written and read back by vector loads and stores
+// at lane-dependent addresses behind workgroup barriers, as the weights are -- and the same arithmetic in the same order.
 #include "ranenv_net.hpp"
 
 namespace {
@@ -45,15 +48,72 @@ __device__ __forceinline__ void ppo_load_rows(const PolicyNet &net, const PpoArg
     });
 }
 
+// ---- the wide plan (ranenv_ppo_bind_wide): two row buffers in LDS, every layer's input rows parked in the workgroup's scratch --------
+// Rows array j of a net -- 0 its input, j >= 1 layer j - 1's output -- lies in the buffer that grows up from `base` (even j) or in the
+// one that ends at `top` (odd j), `top` - `base` = ppo_wide_floats(net): arrays j and j + 1, the only two alive at a time, never meet.
+__host__ __device__ inline int ppo_wide_floats(const PolicyNet &net)
+{
+    int n = 0;
+    for (int l = 0; l < net.n_layers; l++) { const int v = NET_ROWS * (net_ld(net.kp[l]) + net_ld(net.np[l])); n = v > n ? v : n; }
+    return n;
+}
+// Floats of scratch for the parked rows of `net`: slab l = layer l's 32 input rows at stride net_ld(kp[l]), back to back
+__host__ __device__ inline long long ppo_wide_scratch_floats(const PolicyNet &net)
+{
+    long long n = 0;
+    for (int l = 0; l < net.n_layers; l++) n += NET_ROWS * net_ld(net.kp[l]);
+    return n;
+}
+__device__ __forceinline__ float *ppo_wide_buf(const PolicyNet &net, int j, float *base, float *top)
+{
+    return (j & 1) ? top - NET_ROWS * net_ld(j == 0 ? net.kp[0] : net.np[j - 1]) : base;
+}
+// 32 rows x K columns at stride net_ld(K) from `src` to `dst` (LDS to scratch or back): a float4 per thread at a lane-dependent address
+__device__ __forceinline__ void ppo_copy_rows(float *dst, const float *src, int K, int tid)
+{
+    const int ld = net_ld(K), kq = K >> 2;
+    for (int i = tid; i < NET_ROWS * kq; i += 256) {
+        const int r = i / kq, at = r * ld + ((i - r * kq) << 2);
+        *(float4 *)(dst + at) = *(const float4 *)(src + at);
+    }
+}
+// The forward pass of one tile on the two buffers: the input rows lie at `base` behind a barrier.  Layer l parks its input rows in
+// slab l of `park` while it reads them (the barrier in front published them; nothing overwrites them before the layer's own barrier)
+// and writes the other buffer.  Returns the output layer's rows.
+__device__ __forceinline__ float *ppo_forward_wide(const PolicyNet &net, const float *w, float *base, float *top, float *park, int tid)
+{
+    float *in = base;
+    for (int l = 0; l < net.n_layers; l++) {
+        float *out = ppo_wide_buf(net, l + 1, base, top);
+        ppo_copy_rows(park, in, net.kp[l], tid);
+        net_layer_f32(net, l, w, in, out, tid & 63, tid >> 6);
+        __syncthreads();
+        park += NET_ROWS * net_ld(net.kp[l]);
+        in = out;
+    }
+    return in;
+}
+
 // The backward pass of one tile: `out` = the output layer's rows, holding dL/d(output); the layers' inputs lie in front of it (see
 // the header).  Adds the tile's share to the packed gradient `g`; reads the weights `w`.  Ends without a barrier.
-__device__ __forceinline__ void ppo_backward(const PolicyNet &net, const float *w, float *g, float *out, int tid)
+// WIDE: layer l's input rows A come back from slab l of `park` into the buffer dZ does not hold (a barrier behind the load; the
+// buffer is free: what it held, the dZ of layer l + 1, was last read in front of that layer's closing barrier), the arithmetic is the same.
+template <bool WIDE = false>
+__device__ __forceinline__ void ppo_backward(const PolicyNet &net, const float *w, float *g, float *out, int tid, float *base = nullptr, float *top = nullptr,
+                                             const float *park = nullptr)
 {
     const int lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
     float *dz = out;
+    if constexpr (WIDE) park += ppo_wide_scratch_floats(net);
     for (int l = net.n_layers - 1; l >= 0; l--) {
         const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N), kb = K >> 4;
         float *a = dz - NET_ROWS * ldi;
+        if constexpr (WIDE) {
+            a = ppo_wide_buf(net, l, base, top);
+            park -= NET_ROWS * ldi;
+            ppo_copy_rows(a, park, K, tid);
+            __syncthreads();
+        }
         float *gW = g + net.w_off[l], *gb = g + net.b_off[l];
         for (int blk = wave; blk < (N >> 4) * kb; blk += 4) {
             const int nb = blk / kb, n0 = nb << 4, k0 = (blk - nb * kb) << 4;
@@ -214,20 +274,37 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
 // entry `member` of the binding's per-member array.  The rows lie in LDS at the member's own strides; w, m, v and g at member x stride
 // as ever.  The body (ranenv_ppo_body.hpp) is program text expanded into each kernel, and what differs are expression macros, not
 // inline functions: the uniform kernel compiles the text it always had, instruction for instruction.
+// WIDE (ranenv_ppo_bind_wide): the forward and backward pass of a tile follow the wide plan above, on the workgroup's share of Y.scratch;
+// every other line of the body is the same text.
 #define PPO_NET(k) (MIXED ? park[k] : A.net[kind][k].net)
 #define PPO_FLOATS(k) (MIXED ? ((k) == 0 ? fl0 : fl1) : A.net[kind][k].floats)
 static_assert(PPO_FIXED >= (256 + NET_ROWS * PPO_ROW_STATS) * 8 + NET_ROWS * 4 + 2 * (int)sizeof(PolicyNet), "the fixed LDS region holds the two parked descriptors");
 
 __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel(PpoArgs A)
 {
-    constexpr bool MIXED = false;
+    constexpr bool MIXED = false, WIDE = false;
     const PpoMixed X{};
+    const PpoWide Y{};
 #include "ranenv_ppo_body.hpp"
 }
 
 __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_mixed(PpoArgs A, PpoMixed X)
 {
-    constexpr bool MIXED = true;
+    constexpr bool MIXED = true, WIDE = false;
+    const PpoWide Y{};
+#include "ranenv_ppo_body.hpp"
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_wide(PpoArgs A, PpoWide Y)
+{
+    constexpr bool MIXED = false, WIDE = true;
+    const PpoMixed X{};
+#include "ranenv_ppo_body.hpp"
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_mixed_wide(PpoArgs A, PpoMixed X, PpoWide Y)
+{
+    constexpr bool MIXED = true, WIDE = true;
 #include "ranenv_ppo_body.hpp"
 }
 #undef PPO_NET
@@ -459,8 +536,34 @@ size_t ppo_lds_bytes(const PolicyNet &actor, const PolicyNet *critic)
     return (size_t)PPO_FIXED + sizeof(float) * (size_t)n;
 }
 
-hipError_t launch_ppo_update(hipStream_t s, int n_members, size_t lds, const PpoArgs &a, const PpoMixed *mixed)
+size_t ppo_wide_lds_bytes(const PolicyNet &actor, const PolicyNet *critic)
 {
+    int n = ppo_wide_floats(actor);
+    if (critic && critic->n_layers > 0) { const int v = ppo_wide_floats(*critic); n = v > n ? v : n; }
+    return (size_t)PPO_FIXED + sizeof(float) * (size_t)n;
+}
+
+long long ppo_wide_scratch(const PolicyNet &actor, const PolicyNet *critic)
+{
+    long long n = ppo_wide_scratch_floats(actor);
+    if (critic && critic->n_layers > 0) { const long long v = ppo_wide_scratch_floats(*critic); n = v > n ? v : n; }
+    return n;
+}
+
+hipError_t launch_ppo_update(hipStream_t s, int n_members, size_t lds, const PpoArgs &a, const PpoMixed *mixed, const PpoWide *wide)
+{
+    if (wide && !mixed) {
+        static const hipError_t attr_wide = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
+        if (attr_wide != hipSuccess) return attr_wide;
+        hipLaunchKernelGGL(ranenv_ppo_update_kernel_wide, dim3((unsigned)n_members, 2), dim3(256), lds, s, a, *wide);
+        return hipGetLastError();
+    }
+    if (wide) {
+        static const hipError_t attr_mixed_wide = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_mixed_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
+        if (attr_mixed_wide != hipSuccess) return attr_mixed_wide;
+        hipLaunchKernelGGL(ranenv_ppo_update_kernel_mixed_wide, dim3((unsigned)n_members, 2), dim3(256), lds, s, a, *mixed, *wide);
+        return hipGetLastError();
+    }
     static const hipError_t attr = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
     if (attr != hipSuccess) return attr;
     if (!mixed) {

@@ -1,6 +1,6 @@
 // ranenv_ppo_body.hpp -- the body of the PPO update kernels (ranenv_ppo.hip expands it once per kernel: no include guard).  In scope where
-// it is expanded: the kernel's arguments `A` (PpoArgs) and `X` (PpoMixed), `constexpr bool MIXED`, and the macros PPO_NET(k) / PPO_FLOATS(k)
-// -- net k's descriptor and packed floats of this workgroup's member.
+// it is expanded: the kernel's arguments `A` (PpoArgs), `X` (PpoMixed) and `Y` (PpoWide), `constexpr bool MIXED` and `WIDE`, and the macros
+// PPO_NET(k) / PPO_FLOATS(k) -- net k's descriptor and packed floats of this workgroup's member.
     extern __shared__ float lds[];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int mem = (int)blockIdx.x, kind = (int)blockIdx.y;
@@ -30,6 +30,7 @@
     const int S = A.S;
     const long long n_record = (long long)A.T * A.B * (kind == 0 ? 1 : S);
     int t = A.t[mem * 2 + kind];
+    float *const wpark = WIDE ? Y.scratch + ((size_t)mem * 2 + kind) * (size_t)Y.stride : nullptr;      // (the workgroup's parked rows)
 
 #pragma unroll 1
     for (int ep = 0; ep < epochs; ep++) {
@@ -83,7 +84,8 @@
                     float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
                     ppo_load_rows(net, A, kind, rowidx, cur, tid);
                     __syncthreads();
-                    net_layers<false, true>(net, w, cur, nxt, lane, wave);
+                    if constexpr (WIDE) cur = ppo_forward_wide(net, w, act, act + ppo_wide_floats(net), wpark, tid);
+                    else net_layers<false, true>(net, w, cur, nxt, lane, wave);
                     if (tid < NET_ROWS) {
                         const int i = rowidx[tid], np = net.np[net.n_layers - 1];
                         float *o = cur + tid * net_ld(np);
@@ -101,7 +103,8 @@
                         }
                     }
                     __syncthreads();
-                    ppo_backward(net, w, g, cur, tid);
+                    if constexpr (WIDE) ppo_backward<true>(net, w, g, cur, tid, act, act + ppo_wide_floats(net), wpark);
+                    else ppo_backward(net, w, g, cur, tid);
                 }
                 if (tid == 0) {                // (rows 0..31 in order; the barriers above have published them)
 #pragma unroll 1
