@@ -1277,7 +1277,8 @@ int ranenv_get_head_log_std(ranenv_handle h, float *dev_out, void *stream);
  * (agents/sched_twc.py:111-133, agents/sched_colran.py:111-133 on the head observation; agents/sb3_sched.py:104-120,
  * agents/sb3_pf_sched.py on IBSched's player_0 observation, RANENV_HEAD_SRC_INTER above); the SAC flavour is SB3's
  * SAC("MlpPolicy", ...): an Actor (RANENV_HEAD_DIST_GAUSS_TANH above), two ContinuousCritic Q-nets and their target copies, a ReplayBuffer, uniform minibatches, and per minibatch the soft Bellman target.  What of that needs no gradient
- * runs here: the replay ring, the sampler, the target.  The learner's losses, optimiser and polyak update stay with the caller.
+ * runs in the entries right below: the replay ring, the sampler, the target.  The learner's losses, optimisers and polyak update run on the
+ * device too, in ranenv_sac_update ("SAC update" further down), or stay with the caller who prefers them there.
  * stable-baselines3 is not part of this project's test environment: everything below is restated from SB3's documented module
  * layout, parity with SB3 itself is UNPINNED (as for the head policies above).
  *
@@ -1352,6 +1353,82 @@ int ranenv_set_sac_critics(ranenv_handle h, const ranenv_mlp *q1, const ranenv_m
 int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, const float *dev_reward, const uint8_t *dev_done, double gamma,
                        double ent_coef, int32_t stochastic, uint64_t seed, uint64_t draw, float *dev_target, float *dev_next_action,
                        float *dev_next_logp, float *dev_q, void *stream);
+
+/* SAC update: the gradient steps of SB3's SAC.train (defaults: no gradient clip, one learning rate, Adam betas 0.9 / 0.999, eps 1e-8)
+ * on a batch of transitions in caller memory -- what ranenv_replay_sample returns -- so that the off-policy half of the agent table
+ * trains at SB3's settings (minibatch 256) without the host between the kernels.  Updated in place: the bound head actor (the buffer
+ * the acting kernels read: the next ranenv_collect_replay acts on the trained actor, no re-bind), two LIVE critics the binding owns,
+ * the entropy coefficient, and the bound target critics (the buffer ranenv_sac_targets reads).  Every launch is enqueued on the
+ * caller's stream; the call never waits for the device.  As for ranenv_sac_targets, parity with SB3 itself is UNPINNED; the
+ * normative statement is the torch-autograd twin adapters.sac_update_reference.
+ *
+ * One step, on minibatch g of a call = rows [g n, (g + 1) n) of the batch (n = minibatch); row k of it has the global index
+ * i = first_row + g n + k, the first counter word of its Philox draws.  alpha = exp((double)log_ent_coef) as the PREVIOUS step
+ * left it (SB3 detaches it), the same value in 1, 3 and the statistics.  Float64 epilogues on the float32 net outputs, nothing
+ * contracted, every stored value rounded once.
+ *   1. target y_i: ranenv_sac_targets' rule on next_obs, under the actor and the TARGET critics, stochastic, with that entry's counter
+ *      (i lo, i hi, draw lo, 0x53414300 + j), ent_coef = alpha and the call's gamma: bit for bit what ranenv_sac_targets(n_steps * n rows,
+ *      ent_coef = alpha, seed, draw) gives for first_row = 0.                                     -> dev_target [n_steps * n] or NULL
+ *   2. critics: L_Q = 0.5 (mean (Q1 - y)^2 + mean (Q2 - y)^2) on [obs | action] (the sampler's float32 action), the LIVE critics:
+ *      dL/dQk of a row = (float)(((double)Qk - (double)y) / n); the backward pass; Adam over both critics.
+ *   3. actor, under the critics AS UPDATED in 2:  (mu | log_std) = actor(obs);  ls_j = clamp(log_std_j, -20, 2);
+ *      z_j = the Box-Muller draw of Philox-4x32-10(counter = (i lo, i hi, draw lo, 0x53415000 + j), key = (seed lo, seed hi)) -- a tag
+ *      of its own ("SAP\0"), distinct from the target's;  u_j = mu_j + exp(ls_j) z_j;  a_j = tanh(u_j);  a32 = (float)a;
+ *      logp = sum over j ascending of ((((-0.5 z_j) z_j - ls_j) - 0.5 ln(2 pi)) - log((1.0 - a_j a_j) + 1e-6))   (the target's epilogue)
+ *      L_pi = mean(alpha logp - min(Q1, Q2)([obs | a32])).  The gradient flows through the smaller critic's INPUT (its action columns
+ *      10 S .. 11 S - 1) to a, and through logp, into mu and log_std; a row whose Q2 < Q1 takes Q2, every other row -- A TIE INCLUDED --
+ *      takes Q1.  With dq_j = d(-Qmin / n)/d a32_j from the float32 backward pass through that critic (output gradient (float)(-1.0 / n)):
+ *          du_j        = (alpha / n) * ((2 a_j (1 - a_j^2)) / ((1 - a_j^2) + 1e-6)) + dq_j * (1 - a_j^2)
+ *          d / d mu_j      = (float)du_j
+ *          d / d log_std_j = (float)(du_j * (exp(ls_j) z_j) - alpha / n)   where -20 <= log_std_j <= 2, else 0: a CLAMPED log_std gets
+ *                            no gradient (torch.clamp passes it on the closed interval)
+ *      then the backward pass and Adam over the actor.
+ *   4. coefficient (auto_flag != 0, SB3's ent_coef="auto"): d / d log_ent_coef = (float)(-mean(logp + target_entropy)) with 3's logp;
+ *      Adam on the scalar.  A fixed coefficient (auto_flag 0) has no optimiser: the scalar, its moments and its counter stay.
+ *   5. polyak, float32, per element of the target critics:  omt = (float)(1.0 - tau), tf = (float)tau,
+ *      target <- omt * target + tf * critic  with the critic as updated in 2 -- the two products each rounded to float32, then their sum
+ *      rounded to float32, never fused: a numpy float32 restatement is bit-exact.
+ *   Adam is ranenv_ppo_update's float32 operation order with scale 1 (no clip).  A step counter per trained tensor (actor, q1, q2,
+ *   coefficient), all advanced by one per step: they are equal unless a re-bind restarted one of them (below).
+ *   Geometry: tiles of 32 rows, min(tiles, slabs) workgroups of 256 threads per pass; workgroup w walks tiles w, w + grid, ... in
+ *   ascending order and adds into gradient slab w; the elementwise apply launch forms g[e] = slab_0[e] + slab_1[e] + ... over the USED
+ *   slabs in ascending order (float32) and zeroes them.  No atomics: the result is a function of the inputs and `slabs` alone, and a
+ *   handle bound with more slabs than a minibatch has tiles gives the bytes of one bound with exactly that many.
+ *   THE LDS PLAN: 5120 bytes + 128 * sum over the input and the layers of ld(width padded to 32) of the LARGER of actor and critic
+ *   (ld as for ranenv_ppo_lds_bytes), at most 163 840: SB3's [256, 256] fits at every S <= 16.  ranenv_sac_lds_bytes tells the need
+ *   by shape alone.
+ *
+ * ranenv_sac_bind: the live critics become a copy of the bound target critics (SB3 starts them equal); Adam's moments zero, counters 0;
+ *   log_ent_coef = (float)log(ent_coef_init); `slabs` (1..256) gradient slabs allocated and zeroed.  target_entropy: SB3's default is -S.
+ *   RANENV_E_STATE, before any device call: no GAUSS_TANH head actor or no critics bound; a bf16 actor; a need beyond the LDS plan
+ *   (the message names LDS).  RANENV_E_INVALID: slabs out of range, ent_coef_init not positive and finite.
+ *   Re-binding: ranenv_set_head_policy_network zeroes the actor's moments and counter; ranenv_set_sac_critics makes the live critics
+ *   copies of the new targets and zeroes their moments and counters.  A re-bind of a different packed size ends the binding
+ *   (ranenv_sac_update: RANENV_E_STATE until the next ranenv_sac_bind).  ranenv_ppo_bind_head refuses GAUSS_TANH and this entry
+ *   refuses GAUSS_CLIP: the two head bindings cannot meet on one actor.
+ * ranenv_sac_update: n_steps steps on rows [0, n_steps * minibatch) of dev_obs / dev_next_obs f32 [..][10*S], dev_action f32 [..][S],
+ *   dev_reward f32 [..], dev_done u8 [..].
+ *     dev_stats f64 [n_steps][8] (required): critic loss L_Q, actor loss L_pi, coefficient loss -log_ent_coef * mean(logp + target_entropy)
+ *       (0 for a fixed coefficient), alpha, mean logp, mean Q1, mean Q2 (the live critics of 2, before their step), mean y.
+ *     dev_grad f32 [actor floats + 2 * critic floats + 1] or NULL: the LAST step's gradients [actor | q1 | q2 | log_ent_coef] in the
+ *       packed layouts (padding: exact zeros; the scalar 0 for a fixed coefficient).
+ *   RANENV_E_STATE: no binding, or what ranenv_sac_bind refuses.  RANENV_E_INVALID: n_steps < 1, minibatch < 1, first_row < 0, a NULL
+ *   batch pointer or dev_stats.  All before any device call, the state unchanged.  No graph capture.
+ * ranenv_sac_layout: the packed floats of the actor and of ONE critic -- the layout of dev_grad -- and the passes' LDS bytes.
+ * ranenv_sac_state: device pointers to Adam's m and v of `which` (0 actor, 1 q1, 2 q2: packed layout; 3 log_ent_coef: one float),
+ *   that tensor's counter and the float count.
+ * ranenv_get_sac_net_weights: ranenv_get_net_weights for which = 0 actor, 1 q1, 2 q2 (live; need the binding), 3 q1_target, 4 q2_target.
+ * ranenv_get_sac_log_ent_coef: the scalar as it is now, to the caller's device buffer on `stream`. */
+#define RANENV_SAC_STATS 8
+int ranenv_sac_bind(ranenv_handle h, double ent_coef_init, int32_t auto_flag, double target_entropy, int32_t slabs, void *stream);
+int ranenv_sac_update(ranenv_handle h, int32_t n_steps, int32_t minibatch, int64_t first_row, const float *dev_obs, const float *dev_action,
+                      const float *dev_reward, const float *dev_next_obs, const uint8_t *dev_done, double lr, double gamma, double tau, uint64_t seed,
+                      uint64_t draw, double *dev_stats, float *dev_grad, float *dev_target, void *stream);
+int ranenv_sac_layout(ranenv_handle h, int64_t *actor_floats, int64_t *critic_floats, int64_t *lds_bytes);
+int ranenv_sac_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *bytes);
+int ranenv_sac_state(ranenv_handle h, int32_t which, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats);
+int ranenv_get_sac_net_weights(ranenv_handle h, int32_t which, ranenv_mlp *out, void *stream);
+int ranenv_get_sac_log_ent_coef(ranenv_handle h, float *dev_out, void *stream);
 /* SchedColORAN's slice-name table (sched_colran.py:356-367) as data: host array [count][S], bit 0 = eMBB,
  * bit 1 = URLLC, for scenario-pool rows [first, first+count).  Default 0 (no reward term). */
 int ranenv_set_slice_usecase(ranenv_handle h, int32_t first, int32_t count, const int32_t *usecase, void *stream);

@@ -95,6 +95,9 @@ class PpoHparams(C.Structure):
 
 
 PPO_STATS = ("policy_loss", "value_loss", "entropy", "kl", "clip_frac", "grad_norm", "rows", "minibatches")
+SAC_STATS = ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef", "logp_mean", "q1_mean", "q2_mean", "target_mean")
+SAC_NETS = {"actor": 0, "q1": 1, "q2": 2, "q1_target": 3, "q2_target": 4}
+SAC_ACTOR_TAG = 0x53415000       # counter word c3 of the SAC update's actor-pass draws: tag + position (include/ranenv.h "SAC update")
 
 
 class HeadTrajectory(C.Structure):
@@ -239,6 +242,13 @@ FUNCTIONS = {
     "ranenv_ppo_head_state": (C.c_int, [_P, _I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "ranenv_get_head_net_weights": (C.c_int, [_P, _I32, C.POINTER(Mlp), _P]),
     "ranenv_get_head_log_std": (C.c_int, [_P, _P, _P]),
+    "ranenv_sac_bind": (C.c_int, [_P, _F64, _I32, _F64, _I32, _P]),
+    "ranenv_sac_update": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _F64, _F64, _F64, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
+    "ranenv_sac_layout": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ranenv_sac_lds_bytes": (C.c_int, [C.POINTER(Mlp), C.POINTER(Mlp), C.POINTER(C.c_int64)]),
+    "ranenv_sac_state": (C.c_int, [_P, _I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "ranenv_get_sac_net_weights": (C.c_int, [_P, _I32, C.POINTER(Mlp), _P]),
+    "ranenv_get_sac_log_ent_coef": (C.c_int, [_P, _P, _P]),
 }
 POPULATION_MAX = 64
 POPULATION_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}

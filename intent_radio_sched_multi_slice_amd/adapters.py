@@ -992,6 +992,187 @@ def sac_targets_torch(next_obs, reward, done, actor, q1, q2, gamma: float = 0.99
             "z": cpu(z), "logp64": cpu(logp)}
 
 
+# --------------------------------------------------------------------------------------------
+# The SAC update (ranenv_sac_update, include/ranenv.h "SAC update"): the actor pass's draws and the torch-autograd statement of a step
+# --------------------------------------------------------------------------------------------
+SAC_ACTOR_TAG = 0x53415000       # counter word c3 of the actor pass's Philox draws: tag + position ("SAP\0"; the target's is SAC_TAG)
+SAC_UPDATE_SLIPS = ("stale_critics", "larger_critic", "clamped_gradient", "coef_after_update", "target_noise_for_actor", "short_logp",
+                    "action_columns_pad32", "polyak_live")
+
+
+def _sac_noise(n: int, S: int, seed: int, draw: int, first_row: int, tag: int) -> np.ndarray:
+    i = (np.arange(int(n), dtype=np.uint64) + np.uint64(int(first_row))).reshape(-1, 1)
+    c3 = tag + np.arange(S, dtype=np.int64)[None, :]
+    d = philox4x32_10(i & np.uint64(0xFFFFFFFF), i >> np.uint64(32), int(draw) & 0xFFFFFFFF, c3, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    u1 = (d[0].astype(np.float64) + 1.0) * 2.0 ** -32
+    u2 = d[1].astype(np.float64) * 2.0 ** -32
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+
+
+def sac_actor_noise(n: int, S: int, seed: int, draw: int, first_row: int = 0) -> np.ndarray:
+    """The actor pass's draws z float64 [n, S] of ``sac_update``: row k is the global row i = ``first_row`` + k; Box-Muller of Philox
+    words 0 / 1 at counter (i lo, i hi, draw lo, SAC_ACTOR_TAG + j), key = seed.  The target pass of the same step draws
+    ``sac_target_noise`` at the same rows: counter word 3 is SAC_TAG + j there."""
+    return _sac_noise(n, S, seed, draw, first_row, SAC_ACTOR_TAG)
+
+
+def sac_update_reference(batch, actor, q1, q2, q1_target, q2_target, log_ent_coef, steps: int = 1, minibatch: int = 256, lr: float = 3e-4,
+                         gamma: float = 0.99, tau: float = 0.005, seed: int = 0, draw: int = 0, first_row: int = 0, auto: bool = True,
+                         target_entropy: Optional[float] = None, act_actor: str = "relu", act_critic: str = "relu", state: Optional[dict] = None,
+                         dtype=torch.float64, slip: Optional[str] = None):
+    """THE NORMATIVE STATEMENT of ``sac_update``, torch autograd on the CPU: ``steps`` gradient steps of SB3's ``SAC.train`` with its
+    defaults.  ``dtype`` is the nets': their weights, forwards, gradients and Adam run in it (float64: the reference; float32: the
+    yardstick, the device's own split), while the epilogues -- the squashed Gaussian, the target, the losses -- are float64 on the nets'
+    outputs either way, as on the device and in ``sac_targets_torch``.  ``batch``: ``obs`` / ``action`` / ``reward`` / ``next_obs`` / ``done`` with at least ``steps *
+    minibatch`` rows, step g takes rows [g n, (g + 1) n); the five nets lists of ``(W, b)`` (copied); ``log_ent_coef`` a float32 scalar.
+    Per step, with alpha = exp(log_ent_coef) as the previous step left it:
+      1. y = float32(reward + (1 - done) gamma (min(Q1', Q2')(next_obs, a') - alpha logp(a')))  under the actor and the TARGET critics,
+         a' from ``sac_target_noise`` at the rows' global indices -- ``sac_targets_torch``'s rule
+      2. L_Q = 0.5 (mean (Q1 - y)^2 + mean (Q2 - y)^2) on [obs | action]; Adam over both critics
+      3. under the critics AS UPDATED: ls = clamp(log_std, -20, 2), a = tanh(mu + exp(ls) z) with z = ``sac_actor_noise``,
+         L_pi = mean(alpha logp - torch.minimum(Q1, Q2)([obs | float32(a)])); Adam over the actor.  (torch.minimum halves the gradient
+         at a tie, the device takes Q1: the tests' inputs have none.)
+      4. ``auto``: L_alpha = -mean(log_ent_coef (logp + target_entropy)) with 3's logp detached; Adam on the scalar
+      5. target <- (1 - tau) target + tau critic
+    Adam is ``ppo_adam_reference`` without a clip, eps 1e-8, a state per tensor.  Returns {"actor", "q1", "q2", "q1_target",
+    "q2_target": the new layers, "log_ent_coef", "state", "stats": float64 [steps, 8] as ``_lib.SAC_STATS``, "grad": the LAST step's
+    {"actor", "q1", "q2": [(dW, db)], "log_ent_coef"}, "target": every step's y}.  ``slip``: a deliberately wrong variant
+    (``SAC_UPDATE_SLIPS``), for the tests that show the tolerances bite."""
+    assert slip is None or slip in SAC_UPDATE_SLIPS, slip
+    leaf = lambda x: torch.as_tensor(x).detach().cpu().to(dtype).clone().requires_grad_(True)  # noqa: E731
+    held = lambda net: [(torch.as_tensor(w).detach().cpu().to(dtype).clone(), torch.as_tensor(b).detach().cpu().to(dtype).clone()) for w, b in net]  # noqa: E731
+    actor, q1, q2 = ([(leaf(w), leaf(b)) for w, b in net] for net in (actor, q1, q2))
+    targets = [held(q1_target), held(q2_target)]
+    lec = torch.as_tensor(log_ent_coef).detach().cpu().reshape(()).to(torch.float32).to(dtype).clone().requires_grad_(True)
+    cpu = {k: torch.as_tensor(v).detach().cpu() for k, v in batch.items()}
+    n, S = int(minibatch), cpu["action"].shape[1]
+    te = -float(S) if target_entropy is None else float(target_entropy)
+    state = {"actor": {}, "q1": {}, "q2": {}, "log_ent_coef": {}} if state is None else state
+    flat = lambda net: [p for wb in net for p in wb]  # noqa: E731
+    pairs = lambda fl: [(fl[2 * i].detach().clone(), fl[2 * i + 1].detach().clone()) for i in range(len(fl) // 2)]  # noqa: E731
+
+    def forward(x, layers, act):
+        x = x.to(dtype)
+        for i, (w, b) in enumerate(layers):
+            x = x @ w.T + b
+            if i < len(layers) - 1:
+                x = torch.tanh(x) if act == "tanh" else torch.relu(x)
+        return x.to(torch.float64)
+
+    def squashed(out, z, positions=None):
+        mu, raw = out[:, :S], out[:, S:]
+        ls = raw.clamp(LOG_STD_MIN, LOG_STD_MAX)
+        if slip == "clamped_gradient":
+            ls = raw + (ls - raw).detach()
+        a = torch.tanh(mu + torch.exp(ls) * z)
+        terms = (((-0.5 * z) * z - ls) - HALF_LN_2PI) - torch.log((1.0 - a * a) + 1e-6)
+        return a, terms[:, :S if positions is None else positions].sum(dim=1)
+
+    f32 = lambda t: t.to(torch.float32).to(torch.float64)  # noqa: E731
+    stats, grads, ys = np.zeros((steps, 8)), None, []
+    for g in range(steps):
+        rows = slice(g * n, (g + 1) * n)
+        obs, nxt = cpu["obs"][rows].to(torch.float32).to(torch.float64), cpu["next_obs"][rows].to(torch.float32).to(torch.float64)
+        act, rew = f32(cpu["action"][rows]), f32(cpu["reward"][rows])
+        nd = torch.where(cpu["done"][rows] != 0, 0.0, 1.0).to(torch.float64)
+        z_t = torch.from_numpy(_sac_noise(n, S, seed, draw, first_row + g * n, SAC_TAG))
+        z_a = z_t if slip == "target_noise_for_actor" else torch.from_numpy(sac_actor_noise(n, S, seed, draw, first_row + g * n))
+
+        def coef_step(logp):
+            loss = -(lec * (logp.detach() + te)).mean()
+            g_ent = torch.autograd.grad(loss, [lec])
+            with torch.no_grad():
+                ppo_adam_reference([lec], list(g_ent), state["log_ent_coef"], lr, 0.0, (0.9, 0.999), 1e-8)
+            return loss.detach(), g_ent[0].detach().clone()
+
+        lec_used, early = lec.detach().clone(), None
+        if slip == "coef_after_update" and auto:
+            with torch.no_grad():
+                _, lp0 = squashed(forward(obs, actor, act_actor), z_a)
+            early = coef_step(lp0)
+        alpha = torch.exp(lec.detach())
+        with torch.no_grad():
+            a_t, lp_t = squashed(forward(nxt, actor, act_actor), z_t)
+            xa = torch.cat([nxt, f32(a_t)], dim=1)
+            qt = torch.minimum(forward(xa, targets[0], act_critic)[:, 0], forward(xa, targets[1], act_critic)[:, 0])
+            y = f32(rew + nd * (gamma * (qt - alpha * lp_t)))
+        ys.append(y.clone())
+        x = torch.cat([obs, act], dim=1)
+        qv = [forward(x, q, act_critic)[:, 0] for q in (q1, q2)]
+        loss_q = 0.5 * (((qv[0] - y) ** 2).mean() + ((qv[1] - y) ** 2).mean())
+        g_q = torch.autograd.grad(loss_q, flat(q1) + flat(q2))
+        stale = [[(w.detach().clone(), b.detach().clone()) for w, b in q] for q in (q1, q2)]
+        with torch.no_grad():
+            ppo_adam_reference(flat(q1), list(g_q[:len(flat(q1))]), state["q1"], lr, 0.0, (0.9, 0.999), 1e-8)
+            ppo_adam_reference(flat(q2), list(g_q[len(flat(q1)):]), state["q2"], lr, 0.0, (0.9, 0.999), 1e-8)
+        a, lp = squashed(forward(obs, actor, act_actor), z_a, S - 1 if slip == "short_logp" else None)
+        a32 = a + (f32(a) - a).detach()
+        if slip == "action_columns_pad32":       # d/da_j taken from input column pad32(10 S) + j of the padded row: action column P + j, or padding
+            P = (10 * S + 31) // 32 * 32 - 10 * S
+            moved = [a32[:, m].detach() + ((a32[:, m - P] - a32[:, m - P].detach()) if m >= P else 0.0) for m in range(S)]
+            a32 = torch.stack(moved, dim=1)
+        xa = torch.cat([obs, a32], dim=1)
+        qa = [forward(xa, q, act_critic)[:, 0] for q in ((stale[0], stale[1]) if slip == "stale_critics" else (q1, q2))]
+        qmin = torch.maximum(qa[0], qa[1]) if slip == "larger_critic" else torch.minimum(qa[0], qa[1])
+        loss_pi = (alpha * lp - qmin).mean()
+        g_pi = torch.autograd.grad(loss_pi, flat(actor))
+        with torch.no_grad():
+            ppo_adam_reference(flat(actor), list(g_pi), state["actor"], lr, 0.0, (0.9, 0.999), 1e-8)
+        loss_ent, g_ent = torch.zeros((), dtype=torch.float64), torch.zeros((), dtype=torch.float64)
+        if auto:
+            loss_ent, g_ent = early if early is not None else coef_step(lp)
+        with torch.no_grad():
+            for tg, q in zip(targets, (q1, q2)):
+                for (tw, tb), (w, b) in zip(tg, q):
+                    if slip == "polyak_live":
+                        w.copy_((1.0 - tau) * tw + tau * w)
+                        b.copy_((1.0 - tau) * tb + tau * b)
+                    else:
+                        tw.copy_((1.0 - tau) * tw + tau * w)
+                        tb.copy_((1.0 - tau) * tb + tau * b)
+        stats[g] = [float(loss_q.detach()), float(loss_pi.detach()), float(loss_ent), float(torch.exp(lec_used)) if slip != "coef_after_update" else float(alpha),
+                    float(lp.detach().mean()), float(qv[0].detach().mean()), float(qv[1].detach().mean()), float(y.mean())]
+        nq = len(flat(q1))
+        grads = {"actor": pairs(list(g_pi)), "q1": pairs(list(g_q[:nq])), "q2": pairs(list(g_q[nq:])), "log_ent_coef": g_ent}
+    det = lambda net: [(w.detach(), b.detach()) for w, b in net]  # noqa: E731
+    return {"actor": det(actor), "q1": det(q1), "q2": det(q2), "q1_target": targets[0], "q2_target": targets[1], "log_ent_coef": lec.detach(),
+            "state": state, "stats": stats, "grad": grads, "target": torch.cat(ys)}
+
+
+def sb3_sac_state_dict(actor_layers, q1, q2, q1_target, q2_target, log_ent_coef=None):
+    """The inverse of ``sb3_sac_actor_layers`` plus the critics: an SB3 ``SAC`` ``MlpPolicy`` state dict from the stacked actor layers
+    (``sac_net_weights("actor")``: the (mu | log_std) output layer is split into ``actor.mu`` / ``actor.log_std``), the live critics as
+    ``critic.qf0`` / ``critic.qf1`` and the target critics as ``critic_target.qf0`` / ``critic_target.qf1`` (``create_mlp``
+    Sequentials: Linear layers at the even indices), and, if given, ``log_ent_coef`` [1] (a parameter of SB3's algorithm object, not
+    of its policy: returned under that name for the caller to place).  ``sb3_sac_actor_layers`` of the result returns the actor's
+    tensors.  Key names restated from SB3's documented module layout: parity with SB3 itself is unpinned."""
+    if len(actor_layers) < 2:
+        raise ValueError("an SAC actor has at least one hidden layer in front of mu / log_std")
+    t = lambda x: torch.as_tensor(x).detach().clone()  # noqa: E731
+    out = {}
+    for i, (w, b) in enumerate(actor_layers[:-1]):
+        out[f"actor.latent_pi.{2 * i}.weight"], out[f"actor.latent_pi.{2 * i}.bias"] = t(w), t(b)
+    w, b = actor_layers[-1]
+    if w.shape[0] % 2:
+        raise ValueError(f"the actor's output layer stacks (mu | log_std): {w.shape[0]} rows cannot be split")
+    S = w.shape[0] // 2
+    out["actor.mu.weight"], out["actor.mu.bias"] = t(w[:S]), t(b[:S])
+    out["actor.log_std.weight"], out["actor.log_std.bias"] = t(w[S:]), t(b[S:])
+    for prefix, nets in (("critic", (q1, q2)), ("critic_target", (q1_target, q2_target))):
+        for k, net in enumerate(nets):
+            for i, (w, b) in enumerate(net):
+                out[f"{prefix}.qf{k}.{2 * i}.weight"], out[f"{prefix}.qf{k}.{2 * i}.bias"] = t(w), t(b)
+    if log_ent_coef is not None:
+        out["log_ent_coef"] = t(log_ent_coef).reshape(1)
+    return out
+
+
+def sb3_sac_critic_layers(state_dict, prefix: str = "critic"):
+    """(q1, q2) of an SB3 ``SAC`` policy state dict: the ``{prefix}.qf0`` / ``{prefix}.qf1`` Sequentials (``prefix`` "critic" or
+    "critic_target") as lists of (W, b) -- what ``set_sac_critics`` takes."""
+    return tuple(_sb3_sequential(state_dict, f"{prefix}.qf{k}.", f"{prefix}.qf{k}") for k in (0, 1))
+
+
 def _sb3_sequential(state_dict, prefix: str, what: str):
     """(W, b) of the Linear layers of an SB3 ``create_mlp`` Sequential under ``prefix`` (indices 0, 2, 4, ...: activations between)."""
     found = {}

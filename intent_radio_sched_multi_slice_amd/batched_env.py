@@ -223,6 +223,17 @@ def ppo_lds_bytes(actor_layers, critic_layers=None, wide: bool = False) -> int:
     return out.value
 
 
+def sac_lds_bytes(actor_layers, critic_layers) -> int:
+    """Bytes of LDS the passes of the device SAC update need for this actor / critic shape (ranenv_sac_lds_bytes, the header's LDS plan
+    under "SAC update": a fixed region and the LARGER net's rows; at most 163 840), before anything is bound.  Nets as for
+    ``ppo_lds_bytes``: the actor ``[10 S, hidden..., 2 S]``, one critic ``[11 S, hidden..., 1]``."""
+    actor, critic = _ppo_shape_pair(actor_layers, critic_layers)
+    out = C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_sac_lds_bytes(actor, critic, C.byref(out)), "ranenv_sac_lds_bytes")
+    return out.value
+
+
 def ppo_wide_scratch_floats(actor_layers, critic_layers=None) -> int:
     """Floats of global memory in which ONE workgroup of a wide binding parks the 32 input rows of every layer of a net -- the larger
     of the actor's and the critic's need, the two run one after the other (ranenv_ppo_wide_bytes); ``ppo_bind(wide=True)`` allocates
@@ -1310,6 +1321,113 @@ class BatchedRanEnv:
                                                      *(_ptr(out.get(f)) for f in ("target", "next_action", "next_logp", "q")), self._stream()),
                         "ranenv_sac_targets")
         return out
+
+    # -- the SAC update (ranenv_sac_bind / ranenv_sac_update; include/ranenv.h "SAC update") ---------------------------------------------
+    sac_lds_bytes = staticmethod(sac_lds_bytes)
+
+    def sac_bind(self, ent_coef="auto", target_entropy: Optional[float] = None, slabs: int = 32) -> None:
+        """Bind the learner state of SB3's SAC to the bound "gauss_tanh" head actor and the ``set_sac_critics`` pair (ranenv_sac_bind):
+        two LIVE critics that start as copies of the bound (target) critics, Adam's moments and counters at zero, the entropy
+        coefficient, ``slabs`` gradient slabs (1..256: the most workgroups a pass spreads a minibatch's 32-row tiles over).
+        ``ent_coef``: "auto" (trained from 1.0, SB3's default), "auto_0.1" (trained from that value) or a float (fixed).
+        ``target_entropy`` None: -S, SB3's default for a Box action space."""
+        auto, init = 0, 1.0
+        if isinstance(ent_coef, str):
+            if not ent_coef.startswith("auto"):
+                raise ValueError('ent_coef is "auto", "auto_<initial value>" or a float')
+            auto = 1
+            if "_" in ent_coef:
+                init = float(ent_coef.split("_")[1])
+        else:
+            init = float(ent_coef)
+        te = -float(self.S) if target_entropy is None else float(target_entropy)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_sac_bind(self._h, init, auto, te, int(slabs), self._stream()), "ranenv_sac_bind")
+
+    def sac_layout(self) -> Dict[str, int]:
+        """The packed floats of the "actor" and of one "critic" -- ``sac_update(grad=True)["grad"]`` is [actor | q1 | q2 |
+        log_ent_coef] -- and "lds_bytes" of the passes (ranenv_sac_layout)."""
+        a, c, lds = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.ranenv_sac_layout(self._h, C.byref(a), C.byref(c), C.byref(lds)), "ranenv_sac_layout")
+        return {"actor": a.value, "critic": c.value, "lds_bytes": lds.value}
+
+    def sac_update(self, batch, steps: int, minibatch: int = 256, lr: float = 3e-4, gamma: float = 0.99, tau: float = 0.005, seed: int = 0,
+                   draw: int = 0, first_row: int = 0, grad: bool = False, target: bool = False) -> Dict[str, object]:
+        """``steps`` gradient steps of SB3's ``SAC.train`` on the device (ranenv_sac_update; the defaults are SB3's): step g takes rows
+        ``[g * minibatch, (g + 1) * minibatch)`` of ``batch`` -- a ``replay_sample(steps * minibatch)`` or any dict of ``obs`` /
+        ``next_obs`` float32 [n, 10*S], ``action`` float32 [n, S], ``reward`` float32 [n], ``done`` uint8 [n] with at least that many
+        rows -- and updates in place the live critics, the head actor (the next ``collect_replay()`` acts on it), the entropy
+        coefficient and the bound target critics (``sac_targets()`` reads them).  Row k of step g draws its noise at the global index
+        ``first_row + g * minibatch + k`` under (``seed``, ``draw``).  Returns {name: float64 array [steps]} for ``_lib.SAC_STATS``;
+        ``grad=True`` adds "grad", the LAST step's float32 [actor | q1 | q2 | log_ent_coef] in the packed layouts (``sac_layout``);
+        ``target=True`` adds "target" float32 [steps * minibatch], every step's soft Bellman targets."""
+        steps, minibatch = int(steps), int(minibatch)
+        n = max(steps, 0) * max(minibatch, 0)
+        rows = {"obs": (torch.float32, (10 * self.S,)), "action": (torch.float32, (self.S,)), "reward": (torch.float32, ()),
+                "next_obs": (torch.float32, (10 * self.S,)), "done": (torch.uint8, ())}
+        dev = {}
+        for f, (dt, tail) in rows.items():
+            t = batch[f]
+            if t.shape[0] < n:
+                raise ValueError(f"batch[{f!r}] has {t.shape[0]} rows, {steps} steps of {minibatch} need {n}")
+            dev[f] = self._dev(t, dt, (t.shape[0],) + tail, f)
+        stats = torch.zeros((max(steps, 1), len(_lib.SAC_STATS)), dtype=torch.float64, device=self.device)
+        gbuf = tbuf = None
+        if grad:
+            lay = self.sac_layout()
+            gbuf = torch.zeros((lay["actor"] + 2 * lay["critic"] + 1,), dtype=torch.float32, device=self.device)
+        if target:
+            tbuf = torch.zeros((max(n, 1),), dtype=torch.float32, device=self.device)
+        m64 = 2 ** 64 - 1
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_sac_update(self._h, steps, minibatch, int(first_row), *(_ptr(dev[f]) for f in rows), float(lr), float(gamma),
+                                                    float(tau), int(seed) & m64, int(draw) & m64, _ptr(stats), _ptr(gbuf), _ptr(tbuf), self._stream()),
+                        "ranenv_sac_update")
+        host = stats.cpu().numpy()             # (synchronises: the launches are over, the batch may go)
+        out = {name: host[:steps, i] for i, name in enumerate(_lib.SAC_STATS)}
+        if grad:
+            out["grad"] = gbuf
+        if target:
+            out["target"] = tbuf[:n]
+        return out
+
+    def sac_net_weights(self, which: str):
+        """One of the SAC binding's nets as it is on the device NOW, as a list of ``(W, b)`` tensors in torch ``Linear`` layout
+        (ranenv_get_sac_net_weights): "actor" (the head actor), "q1" / "q2" (the live critics), "q1_target" / "q2_target" (the bound
+        ones ``sac_targets()`` reads)."""
+        if which not in _lib.SAC_NETS:
+            raise ValueError(f"which must be one of {sorted(_lib.SAC_NETS)}")
+        out = _lib.Mlp()
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_get_sac_net_weights(self._h, _lib.SAC_NETS[which], C.byref(out), self._stream()), "ranenv_get_sac_net_weights")
+            dims = list(out.dims[:out.n_hidden + 2])
+            layers = [(torch.empty((dims[i + 1], dims[i]), dtype=torch.float32, device=self.device),
+                       torch.empty((dims[i + 1],), dtype=torch.float32, device=self.device)) for i in range(len(dims) - 1)]
+            for i, (w, b) in enumerate(layers):
+                out.weight[i], out.bias[i] = w.data_ptr(), b.data_ptr()
+            self._check(self._lib.ranenv_get_sac_net_weights(self._h, _lib.SAC_NETS[which], C.byref(out), self._stream()), "ranenv_get_sac_net_weights")
+        return layers
+
+    def sac_log_ent_coef(self) -> torch.Tensor:
+        """A copy of the binding's ``log_ent_coef`` float32 [1] as it is NOW (ranenv_get_sac_log_ent_coef); the coefficient the next
+        step uses is ``exp`` of it in float64."""
+        out = torch.empty((1,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_get_sac_log_ent_coef(self._h, _ptr(out), self._stream()), "ranenv_get_sac_log_ent_coef")
+        return out
+
+    _SAC_STATE = {"actor": 0, "q1": 1, "q2": 2, "log_ent_coef": 3}
+
+    def sac_state(self, which: str) -> Dict[str, torch.Tensor]:
+        """Zero-copy views of the optimiser state of "actor", "q1", "q2" (packed layout) or "log_ent_coef" ([1]): Adam's "m" and "v"
+        and "t", that tensor's step counter (ranenv_sac_state)."""
+        if which not in self._SAC_STATE:
+            raise ValueError(f"which must be one of {sorted(self._SAC_STATE)}")
+        pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._lib.ranenv_sac_state(self._h, self._SAC_STATE[which], C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), "ranenv_sac_state")
+        return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
+                "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
+                "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}
 
     def head_episode_metrics(self) -> Dict[str, torch.Tensor]:
         """Zero-copy views of the episode sums of the two head rewards (columns: SchedTWC, SchedColORAN): ``running`` [B, 2]

@@ -1,6 +1,6 @@
 """Build libranenv_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
-Seven objects, compiled in parallel, then linked:
+Eight objects, compiled in parallel, then linked:
   ranenv_step.hip x 3   the builds of the step kernel for row widths NP = 8, 10, 16 (-DRANENV_NP=...)
   ranenv_aux.hip        the small kernels (class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination,
                         bf16 weight packing)
@@ -8,6 +8,8 @@ Seven objects, compiled in parallel, then linked:
   ranenv_ppo.hip        the PPO update of the bound nets (ranenv_ppo_update: forward, backward, clip and Adam, one workgroup per member;
                         its four kernels -- uniform and mixed populations, each under the plain and the wide LDS plan -- expand one
                         body, ranenv_ppo_body.hpp; a fifth trains the head policies, ranenv_ppo_update_head)
+  ranenv_sac.hip        the SAC update (ranenv_sac_update: per gradient step a critic pass, an actor pass and two elementwise applies,
+                        the rows of a minibatch spread over workgroups; shares ranenv_ppo_parts.hpp with ranenv_ppo.hip)
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants
@@ -25,12 +27,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 HDR = os.path.join(REPO, "include", "ranenv.h")
 OUT = os.path.join(HERE, "libranenv_hip.so")
-SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_body.hpp", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
+SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_body.hpp", "ranenv_ppo_parts.hpp", "ranenv_sac.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
 # (object name, source, extra flags)
 UNITS = (("step_np10", "ranenv_step.hip", ("-DRANENV_NP=10",)), ("step_np8", "ranenv_step.hip", ("-DRANENV_NP=8",)),
          ("step_np16", "ranenv_step.hip", ("-DRANENV_NP=16",)), ("aux", "ranenv_aux.hip", ()),
          # (the policy network's MFMA accumulators in VGPRs: the library's kernels use no AGPRs, tests/test_kernel_resources.py)
          ("policy", "ranenv_policy.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")), ("ppo", "ranenv_ppo.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")),
+         ("sac", "ranenv_sac.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")),
          ("host", "ranenv_host.cpp", ()))
 CFLAGS = ("-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-pass-failed",
           "-ffp-contract=off",     # numpy rounds a*b and +c separately; fma() is written out where it is exact

@@ -162,6 +162,16 @@ struct ranenv {
     // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
     // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
     bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
+    // ranenv_sac_bind / ranenv_sac_update: bound?, the packed floats of the actor and of one critic at the bind (a re-bind of another
+    // size ends the binding), the slab count, the coefficient's mode and the target entropy; the live critics with their moments
+    // [6][sac_q_cap] (q1, q2, m of both, v of both), the actor's moments [2][sac_a_cap], the gradient slabs [slabs][actor + 2 critics],
+    // the passes' partial sums [256][8], the coefficient {log_ent_coef, m, v, -} and the tensors' step counters [4] (actor, q1, q2,
+    // coefficient) with their host shadow: every launch is enqueued in order, so the host knows the counters without reading them
+    bool sac_on = false; long long sac_af = 0, sac_qf = 0; int sac_slabs = 0, sac_auto = 0; double sac_target_entropy = 0.0;
+    float *d_sac_q = nullptr; long long sac_q_cap = 0;
+    float *d_sac_a_opt = nullptr; long long sac_a_cap = 0;
+    float *d_sac_slab = nullptr; long long sac_slab_cap = 0;
+    double *d_sac_partial = nullptr; float *d_sac_ent = nullptr; int32_t *d_sac_t = nullptr; int32_t sac_t[4] = {0, 0, 0, 0};
     // ranenv_set_population_gae: a (gamma, lambda) pair per member for ranenv_collect's GAE pass
     bool gae_on = false; double gae_gamma[POP_MAX] = {}, gae_lambda[POP_MAX] = {};
     // The IBSched nets of a TTI's launches as they are bound (critics: a recording's), with the population map where a member's copy acts
@@ -2200,8 +2210,11 @@ static int ppo_floats_upload(ranenv_handle h, hipStream_t s)
 // A binding call has replaced `slot`'s nets (member < 0: all of them): their moments and their (member, kind) step counters start
 // again, on the caller's stream -- or, where the slot has no moments of its size, the PPO binding ends.
 static int ppo_head_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
+static int sac_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
 static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s)
 {
+    if (slot == &h->head || slot == &h->sac_q1 || slot == &h->sac_q2)
+        if (const int rc = sac_rebound(h, slot, s); rc != RANENV_OK) return rc;
     if (slot == &h->head || slot == &h->head_value) return ppo_head_rebound(h, slot, s);
     if (!h->ppo_on) return RANENV_OK;
     if (slot->role < 0 || slot->form == FORM_SLICE) return RANENV_OK;      // (a net the update never trains)
@@ -2481,7 +2494,7 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
 }
 
 // Copy `member` of `slot` (`who` for the messages) unpacked to torch Linear layout: ranenv_get_net_weights / ranenv_get_head_net_weights
-static int net_export(ranenv_handle h, const ranenv::NetSlot *slot, int member, const char *who, ranenv_mlp *out, void *stream)
+static int net_export(ranenv_handle h, const ranenv::NetSlot *slot, int member, const char *who, ranenv_mlp *out, void *stream, const float *packed = nullptr)
 {
     const PolicyNet &net = slot->member[(size_t)member];
     if (net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the %s net is bf16: its float32 weights were rounded at bind", who);
@@ -2496,7 +2509,7 @@ static int net_export(ranenv_handle h, const ranenv::NetSlot *slot, int member, 
     if (!copy) return RANENV_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    const float *src = net.w;
+    const float *src = packed ? packed : net.w;      // (packed: another copy in the slot's layout -- the SAC binding's live critics)
     for (int l = 0; l < L; l++) {
         const int K = dims[l], N = dims[l + 1];
         HIP_TRY(h, hipMemcpy2DAsync((void *)out->weight[l], sizeof(float) * K, src + net.w_off[l], sizeof(float) * net.kp[l], sizeof(float) * K, N, hipMemcpyDeviceToDevice, s));
@@ -3540,6 +3553,207 @@ int ranenv_sac_targets(ranenv_handle h, int64_t n, const float *dev_next_obs, co
     a.target = dev_target; a.next_action = dev_next_action; a.next_logp = dev_next_logp; a.q = dev_q;
     const hipError_t le = launch_sac_targets((hipStream_t)stream, h->head.net, h->sac_q1.net, h->sac_q2.net, a);
     if (le != hipSuccess) return fail(h, RANENV_E_HIP, "SAC target launch: %s", hipGetErrorString(le));
+    return RANENV_OK;
+}
+
+// ---- the SAC update (include/ranenv.h "SAC update"; ranenv_sac.hip) ------------------------------------------------------------------
+// What ranenv_sac_bind refuses.  No device call.
+static int sac_roles(ranenv_handle h, size_t &lds)
+{
+    if (!h->head.on || h->head_dist != RANENV_HEAD_DIST_GAUSS_TANH)
+        return fail(h, RANENV_E_STATE, "the SAC update needs a GAUSS_TANH head actor (ranenv_set_head_policy_network)");
+    if (!h->sac_q1.on || !h->sac_q2.on) return fail(h, RANENV_E_STATE, "the SAC update needs bound critics (ranenv_set_sac_critics)");
+    if (h->head.net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the SAC update trains float32 nets: the head actor is bf16");
+    lds = sac_lds_bytes(h->head.net, h->sac_q1.net);
+    if (lds > (size_t)PPO_LDS_MAX)
+        return fail(h, RANENV_E_STATE, "the SAC nets need %zu bytes of LDS for the larger net's 32-row activations of all layers, the update has %d", lds, (int)PPO_LDS_MAX);
+    return RANENV_OK;
+}
+
+// ... and the bound state behind it, or RANENV_E_STATE
+static int sac_bound(ranenv_handle h, size_t &lds)
+{
+    if (!h->sac_on) return fail(h, RANENV_E_STATE, "no SAC state bound, or a binding call of another packed size has ended it (ranenv_sac_bind)");
+    return sac_roles(h, lds);
+}
+
+// Tensor x (0 actor, 1 q1, 2 q2) of the binding: the weights the update trains, Adam's m and v
+static float *sac_w(ranenv_handle h, int x) { return x == 0 ? h->head.w : h->d_sac_q + (size_t)(x - 1) * (size_t)h->sac_q_cap; }
+static float *sac_m(ranenv_handle h, int x) { return x == 0 ? h->d_sac_a_opt : h->d_sac_q + (size_t)(1 + x) * (size_t)h->sac_q_cap; }
+static float *sac_v(ranenv_handle h, int x) { return x == 0 ? h->d_sac_a_opt + h->sac_a_cap : h->d_sac_q + (size_t)(3 + x) * (size_t)h->sac_q_cap; }
+
+// The live critic x (1, 2) becomes a copy of its bound target; tensor x's moments and counter start again.  On the caller's stream.
+static int sac_restart(ranenv_handle h, int x, hipStream_t s)
+{
+    const size_t f = (size_t)(x == 0 ? h->sac_af : h->sac_qf);
+    if (x > 0) HIP_TRY(h, hipMemcpyAsync(sac_w(h, x), (x == 1 ? h->sac_q1 : h->sac_q2).w, sizeof(float) * f, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(sac_m(h, x), 0, sizeof(float) * f, s));
+    HIP_TRY(h, hipMemsetAsync(sac_v(h, x), 0, sizeof(float) * f, s));
+    HIP_TRY(h, hipMemsetAsync(h->d_sac_t + x, 0, sizeof(int32_t), s));
+    h->sac_t[x] = 0;
+    return RANENV_OK;
+}
+
+// A binding call has replaced the head actor or a target critic: a copy of another packed size ends the SAC binding; else that
+// tensor starts again (sac_restart: a critic's live copy follows its new target).
+static int sac_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
+{
+    if (!h->sac_on) return RANENV_OK;
+    const int x = slot == &h->head ? 0 : (slot == &h->sac_q1 ? 1 : 2);
+    if (net_floats(slot->net) != (x == 0 ? h->sac_af : h->sac_qf)) { h->sac_on = false; return RANENV_OK; }
+    return sac_restart(h, x, s);
+}
+
+int ranenv_sac_bind(ranenv_handle h, double ent_coef_init, int32_t auto_flag, double target_entropy, int32_t slabs, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    size_t lds = 0;
+    if (const int rc = sac_roles(h, lds); rc != RANENV_OK) return rc;
+    if (slabs < 1 || slabs > 256) return fail(h, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    if (!(ent_coef_init > 0.0) || !std::isfinite(ent_coef_init)) return fail(h, RANENV_E_INVALID, "the entropy coefficient must be positive and finite");
+    if (!std::isfinite(target_entropy)) return fail(h, RANENV_E_INVALID, "the target entropy must be finite");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const long long af = net_floats(h->head.net), qf = net_floats(h->sac_q1.net), stride = af + 2 * qf;
+    if (!h->d_sac_t) {
+        if (const int rc = dev_alloc(h, &h->d_sac_t, (size_t)4); rc != RANENV_OK) return rc;
+        if (const int rc = dev_alloc(h, &h->d_sac_ent, (size_t)4); rc != RANENV_OK) return rc;
+        if (const int rc = dev_alloc(h, &h->d_sac_partial, (size_t)256 * 8); rc != RANENV_OK) return rc;
+    }
+    if (h->sac_q_cap < qf) {             // (an outgrown one stays allocated, like the weights')
+        if (const int rc = dev_alloc(h, &h->d_sac_q, 6 * (size_t)qf); rc != RANENV_OK) return rc;
+        h->sac_q_cap = qf;
+    }
+    if (h->sac_a_cap < af) {
+        if (const int rc = dev_alloc(h, &h->d_sac_a_opt, 2 * (size_t)af); rc != RANENV_OK) return rc;
+        h->sac_a_cap = af;
+    }
+    if (h->sac_slab_cap < stride * slabs) {
+        if (const int rc = dev_alloc(h, &h->d_sac_slab, (size_t)stride * (size_t)slabs); rc != RANENV_OK) return rc;
+        h->sac_slab_cap = stride * slabs;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->d_sac_slab, 0, sizeof(float) * (size_t)h->sac_slab_cap, s));
+    HIP_TRY(h, hipMemsetAsync(h->d_sac_partial, 0, sizeof(double) * 256 * 8, s));
+    h->sac_af = af; h->sac_qf = qf; h->sac_slabs = slabs; h->sac_auto = auto_flag != 0; h->sac_target_entropy = target_entropy;
+    for (int x = 0; x < 3; x++)
+        if (const int rc = sac_restart(h, x, s); rc != RANENV_OK) return rc;
+    const float ent[4] = {(float)std::log(ent_coef_init), 0.0f, 0.0f, 0.0f};
+    HIP_TRY(h, hipMemcpyAsync(h->d_sac_ent, ent, sizeof(ent), hipMemcpyHostToDevice, s));      // (pageable: staged before the call returns)
+    HIP_TRY(h, hipMemsetAsync(h->d_sac_t + 3, 0, sizeof(int32_t), s));
+    h->sac_t[3] = 0;
+    h->sac_on = true;
+    return RANENV_OK;
+}
+
+int ranenv_sac_update(ranenv_handle h, int32_t n_steps, int32_t minibatch, int64_t first_row, const float *dev_obs, const float *dev_action,
+                      const float *dev_reward, const float *dev_next_obs, const uint8_t *dev_done, double lr, double gamma, double tau, uint64_t seed,
+                      uint64_t draw, double *dev_stats, float *dev_grad, float *dev_target, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    size_t lds = 0;
+    if (const int rc = sac_bound(h, lds); rc != RANENV_OK) return rc;
+    if (n_steps < 1 || minibatch < 1) return fail(h, RANENV_E_INVALID, "n_steps %d and minibatch %d must be >= 1", n_steps, minibatch);
+    if (first_row < 0) return fail(h, RANENV_E_INVALID, "first_row must be >= 0");
+    if (!dev_obs || !dev_action || !dev_reward || !dev_next_obs || !dev_done || !dev_stats)
+        return fail(h, RANENV_E_INVALID, "the SAC update needs obs, action, reward, next_obs, done and dev_stats");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const int S = h->cfg.n_slices;
+    const long long af = h->sac_af, qf = h->sac_qf, n = minibatch;
+    const int tiles = (int)((n + NET_ROWS - 1) / NET_ROWS), grid = tiles < h->sac_slabs ? tiles : h->sac_slabs;
+    SacPassArgs p{};
+    p.actor = SacNet{h->head.net, h->head.w};
+    p.q[0] = SacNet{h->sac_q1.net, sac_w(h, 1)}; p.q[1] = SacNet{h->sac_q2.net, sac_w(h, 2)};
+    p.qt[0] = SacNet{h->sac_q1.net, h->sac_q1.w}; p.qt[1] = SacNet{h->sac_q2.net, h->sac_q2.w};
+    p.actor.net.w = p.q[0].net.w = p.q[1].net.w = p.qt[0].net.w = p.qt[1].net.w = nullptr;
+    p.slab = h->d_sac_slab; p.slab_stride = af + 2 * qf; p.off[0] = 0; p.off[1] = af; p.off[2] = af + qf;
+    p.partial = h->d_sac_partial; p.n = n; p.S = S;
+    p.gamma = gamma; p.target_entropy = h->sac_target_entropy; p.seed = seed; p.draw = draw; p.log_ent_coef = h->d_sac_ent;
+    for (int g = 0; g < n_steps; g++) {
+        const size_t r0 = (size_t)g * (size_t)n;
+        const bool last = g == n_steps - 1;
+        p.first_row = first_row + (long long)r0;
+        p.obs = dev_obs + r0 * (size_t)(10 * S); p.action = dev_action + r0 * (size_t)S; p.reward = dev_reward + r0;
+        p.next_obs = dev_next_obs + r0 * (size_t)(10 * S); p.done = dev_done + r0; p.target = dev_target ? dev_target + r0 : nullptr;
+        float *grad = last ? dev_grad : nullptr;
+        HIP_TRY(h, launch_sac_pass(s, 0, grid, lds, p));
+        SacApplyArgs a{};
+        a.slab = p.slab; a.slab_stride = p.slab_stride; a.used = grid; a.lr = lr; a.tau = tau; a.n = n;
+        a.n_seg = 2;
+        for (int x = 1; x <= 2; x++)
+            a.seg[x - 1] = SacApplySeg{sac_w(h, x), sac_m(h, x), sac_v(h, x), nullptr, grad ? grad + p.off[x] : nullptr, p.off[x], qf, h->sac_t[x] + 1, SAC_OP_ADAM};
+        HIP_TRY(h, launch_sac_apply(s, a));
+        HIP_TRY(h, launch_sac_pass(s, 1, grid, lds, p));
+        a.n_seg = 3;
+        a.seg[0] = SacApplySeg{sac_w(h, 0), sac_m(h, 0), sac_v(h, 0), nullptr, grad, 0, af, h->sac_t[0] + 1, SAC_OP_ADAM};
+        a.seg[1] = SacApplySeg{sac_w(h, 1), nullptr, nullptr, h->sac_q1.w, nullptr, 0, qf, 0, SAC_OP_POLYAK};
+        a.seg[2] = SacApplySeg{sac_w(h, 2), nullptr, nullptr, h->sac_q2.w, nullptr, 0, qf, 0, SAC_OP_POLYAK};
+        a.last = 1; a.auto_coef = h->sac_auto; a.t_ent = h->sac_t[3] + 1;
+        a.ent = h->d_sac_ent; a.partial = h->d_sac_partial; a.stats = dev_stats + (size_t)g * 8; a.grad_ent = grad ? grad + af + 2 * qf : nullptr;
+        a.dev_t = h->d_sac_t;
+        for (int x = 0; x < 4; x++) a.t_new[x] = h->sac_t[x] + (x < 3 || h->sac_auto ? 1 : 0);
+        HIP_TRY(h, launch_sac_apply(s, a));
+        for (int x = 0; x < 4; x++) h->sac_t[x] = a.t_new[x];
+    }
+    return RANENV_OK;
+}
+
+int ranenv_sac_layout(ranenv_handle h, int64_t *actor_floats, int64_t *critic_floats, int64_t *lds_bytes)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    size_t lds = 0;
+    if (const int rc = sac_roles(h, lds); rc != RANENV_OK) return rc;
+    if (actor_floats) *actor_floats = net_floats(h->head.net);
+    if (critic_floats) *critic_floats = net_floats(h->sac_q1.net);
+    if (lds_bytes) *lds_bytes = (int64_t)lds;
+    return RANENV_OK;
+}
+
+int ranenv_sac_lds_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *bytes)
+{
+    if (!actor || !critic || !bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    PolicyNet net[2] = {};
+    if (const int rc = ppo_shape_pair(actor, critic, net); rc != RANENV_OK) return rc;
+    *bytes = (int64_t)sac_lds_bytes(net[0], net[1]);
+    return RANENV_OK;
+}
+
+int ranenv_sac_state(ranenv_handle h, int32_t which, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (which < 0 || which > 3) return fail(h, RANENV_E_INVALID, "which %d (0 actor, 1 q1, 2 q2, 3 log_ent_coef)", which);
+    size_t lds = 0;
+    if (const int rc = sac_bound(h, lds); rc != RANENV_OK) return rc;
+    if (dev_m) *dev_m = which == 3 ? h->d_sac_ent + 1 : sac_m(h, which);
+    if (dev_v) *dev_v = which == 3 ? h->d_sac_ent + 2 : sac_v(h, which);
+    if (dev_t) *dev_t = h->d_sac_t + which;
+    if (floats) *floats = which == 3 ? 1 : (which == 0 ? h->sac_af : h->sac_qf);
+    return RANENV_OK;
+}
+
+int ranenv_get_sac_net_weights(ranenv_handle h, int32_t which, ranenv_mlp *out, void *stream)
+{
+    if (!h || !out) return fail(h, RANENV_E_INVALID, "null argument");
+    if (which < 0 || which > 4) return fail(h, RANENV_E_INVALID, "which %d (0 actor, 1 q1, 2 q2, 3 q1_target, 4 q2_target)", which);
+    const ranenv::NetSlot *slot = which == 0 ? &h->head : (which == 1 || which == 3 ? &h->sac_q1 : &h->sac_q2);
+    const char *who = which == 0 ? "head" : "SAC critic";
+    if (!slot->on) return fail(h, RANENV_E_STATE, "no %s net bound", who);
+    const float *live = nullptr;
+    if (which == 1 || which == 2) {          // (the live critics exist under a binding alone)
+        size_t lds = 0;
+        if (const int rc = sac_bound(h, lds); rc != RANENV_OK) return rc;
+        live = sac_w(h, which);
+    }
+    return net_export(h, slot, 0, who, out, stream, live);
+}
+
+int ranenv_get_sac_log_ent_coef(ranenv_handle h, float *dev_out, void *stream)
+{
+    if (!h || !dev_out) return fail(h, RANENV_E_INVALID, "null argument");
+    size_t lds = 0;
+    if (const int rc = sac_bound(h, lds); rc != RANENV_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipMemcpyAsync(dev_out, h->d_sac_ent, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return RANENV_OK;
 }
 

@@ -310,6 +310,41 @@ struct PpoHeadArgs {
 };
 hipError_t launch_ppo_update_head(hipStream_t, size_t lds, const PpoHeadArgs &);
 
+// ranenv_sac_update (ranenv_sac.hip; include/ranenv.h "SAC update"): one gradient step is a critic pass, an apply, an actor pass and
+// a second apply.  A net of a pass: its layout (net.w unused) and the packed weights the pass reads.
+struct SacNet { PolicyNet net; const float *w; };
+// One pass over one minibatch of n rows: workgroup w of `grid` walks tiles w, w + grid, ... and adds into gradient slab w -- tensor x
+// (0 actor, 1 q1, 2 q2) at slab + w * slab_stride + off[x] -- and writes its share of the statistics into partial[w][8] (the critic
+// pass entries 0..4, the actor pass 5..7).  first_row: the global index of the minibatch's row 0, the rows' Philox counter.
+struct SacPassArgs {
+    SacNet actor, q[2], qt[2];            // the head actor, the live critics, the target critics
+    float *slab; long long slab_stride, off[3];
+    double *partial;
+    long long n, first_row; int S;
+    const float *obs, *action, *reward, *next_obs; const uint8_t *done;      // the minibatch's rows
+    double gamma, target_entropy; unsigned long long seed, draw;
+    const float *log_ent_coef;            // the coefficient's logarithm as the previous step left it
+    float *target;                        // [n] or null
+};
+// The elementwise launch behind a pass: segment k (workgroup row k) sums its `floats` elements of the `used` slabs in ascending order,
+// zeroes them, and steps Adam at counter t (SAC_OP_ADAM: w, m, v; grad non-null: the gradient is stored there), and / or moves
+// tgt towards w (SAC_OP_POLYAK).  last != 0, the step's second apply: thread 0 of workgroup (0, 0) sums the partials, steps the
+// coefficient ent = {log_ent_coef, m, v} (auto_coef) at counter t_ent, writes the step's eight statistics and the counters.
+enum { SAC_OP_ADAM = 1, SAC_OP_POLYAK = 2 };
+struct SacApplySeg { float *w, *m, *v, *tgt, *grad; long long slab_off, floats; int t, op; };
+struct SacApplyArgs {
+    SacApplySeg seg[3]; int n_seg;
+    float *slab; long long slab_stride; int used;
+    double lr, tau;
+    int last, auto_coef, t_ent; long long n;
+    float *ent; const double *partial; double *stats; float *grad_ent;
+    int32_t *dev_t; int32_t t_new[4];
+};
+// Bytes of LDS of the passes for this actor / critic shape: the fixed region and the larger net's 32 rows of all layers
+size_t sac_lds_bytes(const PolicyNet &actor, const PolicyNet &critic);
+hipError_t launch_sac_pass(hipStream_t, int which, int grid, size_t lds, const SacPassArgs &);      // which: 0 the critic pass, 1 the actor pass
+hipError_t launch_sac_apply(hipStream_t, const SacApplyArgs &);
+
 enum { PERSIST_ENV_BITS = 20 };          // persistent rollout: queue item = env | TTIs done << 20
 constexpr int CORE_NT = GRP * GRP;   // 256 = largest U = threads of the widest step-kernel block
 

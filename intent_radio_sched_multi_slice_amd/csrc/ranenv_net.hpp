@@ -1,5 +1,5 @@
 // ranenv_net.hpp -- what the kernels that run the bound MLPs share (ranenv_policy.hip: the acting and recording launches;
-// ranenv_ppo.hip: the PPO update): the LDS row strides, the row loaders, the layers on the f32 / bf16 matrix cores and the
+// ranenv_ppo.hip: the PPO update; ranenv_sac.hip: the SAC update): the LDS row strides, the row loaders, the layers on the f32 / bf16 matrix cores and the
 // float64 log-probability arithmetic of the IBSched distributions.  ranenv_policy.hip's header comment describes the decomposition.
 #pragma once
 #include "ranenv_numeric.hpp"
@@ -230,6 +230,18 @@ __device__ __forceinline__ void net_layer_f32(const PolicyNet &net, int l, const
             }
     }
 }
+
+// The standard normal draw from words 0 and 1 of a Philox block (Box-Muller)
+__device__ __forceinline__ double box_muller(const unsigned (&o)[4])
+{
+    const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+// The Gaussian sample, and SB3's clamp of a squashed Gaussian's log_std in front of it (HEAD / GAUSS_TANH, the SAC target and the SAC
+// update: a = tanh(sample))
+__device__ __forceinline__ double gauss_sample(double mu, double ls, double z) { return mu + exp(ls) * z; }
+__device__ __forceinline__ double clamp_log_std(double ls) { return ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls); }
 
 constexpr double HALF_LN_2PI = 0.9189385332046727;      // 0.5 ln(2 pi)
 constexpr double LN_1E9 = 20.72326583694641;            // ln(1e9): -ln of the masked positions' std

@@ -34,22 +34,13 @@ __device__ __forceinline__ void draw_words(const PolicyIO &io, int e, unsigned t
                   (unsigned)(io.seed >> 32), o);
 }
 
-// ... and the standard normal draw from words 0 and 1 (Box-Muller)
-__device__ __forceinline__ double box_muller(const unsigned (&o)[4])
-{
-    const double u1 = ((double)o[0] + 1.0) * 0x1p-32, u2 = (double)o[1] * 0x1p-32;
-    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-}
+// ... and the standard normal draw from words 0 and 1 (box_muller, ranenv_net.hpp)
 __device__ __forceinline__ double gauss_draw(const PolicyIO &io, int e, unsigned tag)
 {
     unsigned o[4];
     draw_words(io, e, tag, o);
     return box_muller(o);
 }
-
-// The Gaussian sample, and SB3's clamp of a squashed Gaussian's log_std in front of it (HEAD / GAUSS_TANH and the SAC target: a = tanh(sample))
-__device__ __forceinline__ double gauss_sample(double mu, double ls, double z) { return mu + exp(ls) * z; }
-__device__ __forceinline__ double clamp_log_std(double ls) { return ls < -20.0 ? -20.0 : (ls > 2.0 ? 2.0 : ls); }
 
 __device__ __forceinline__ int active_slices(const PolicyIO &io, int e)
 {
