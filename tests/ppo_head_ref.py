@@ -19,6 +19,9 @@ from tests import ppo_update_ref as ref
 B, T = 12, 8
 N = B * T                                # 96 rows: three tiles
 MINIBATCH = 12
+T_LONG = 24                              # the long record of tests/ppo_head_shapes_ref.py: B x T_LONG = 288 rows, nine tiles, more than 256
+N_LONG = B * T_LONG
+LONG_MINIBATCH = 257                     # ... in minibatches of 257 and 31 rows
 SEED = 0x2468_ACE0_1357
 FACTOR, FLOOR = 8.0, 1e-6                # ppo_update_ref.check_against_twin's constants
 ALL = ref.ALL
@@ -27,15 +30,21 @@ CASES = {"base": (5, [24], "relu", [40, 24], "tanh", "head", "twc"),
          "sb3": (16, [64, 64], "tanh", [64, 64], "tanh", "head", "colran"),           # SB3's default pair; the epilogue fills 16 positions
          "deg": (1, [7, 100], "relu", [96], "tanh", "head", "twc"),
          "inter": (3, [33, 160, 7, 96], "relu", [96], "tanh", "inter", "ibsched")}
-ENV_SIZES = {5: "S5U25", 16: hs.ENV_SHAPES[16], 1: hs.ENV_SHAPES[1], 3: hs.ENV_SHAPES[3]}
+ENV_SIZES = {5: "S5U25", 16: hs.ENV_SHAPES[16], 1: hs.ENV_SHAPES[1], 3: hs.ENV_SHAPES[3],
+             6: hs.ENV_SHAPES[6], 8: hs.ENV_SHAPES[8], 10: "S10U100"}      # (6, 8, 10: tests/ppo_head_shapes_ref.py's grid)
 HP = dict(clip=0.2, vf_coeff=0.5, ent_coeff=0.01, adv_norm=True)
 NOISE = (0.05, 0.6)                      # |noise| on logp, one of the two per row: exp(0.05) is inside the clip range 0.2, exp(0.6) outside
 SLIPS = ("no_entropy_gradient", "log_std_outside_norm", "stale_log_std", "short_logp", "masked_term", "cell_stride")
 
 
+def spec(case):
+    """A case's tuple: ``case`` a name of CASES, or such a tuple itself (tests/ppo_head_shapes_ref.py's grid)"""
+    return CASES[case] if isinstance(case, str) else tuple(case)
+
+
 def head_nets(case, seed=61):
     """(actor, log_std float32 [S] in [-1, 0.5], critic) of the case as torch modules / tensor"""
-    S, aw, aa, cw, ca = CASES[case][:5]
+    S, aw, aa, cw, ca = spec(case)[:5]
     g = torch.Generator().manual_seed(seed + 1)
     log_std = (torch.rand(S, generator=g) * 1.5 - 1.0).to(torch.float32)
     return hr.mlp([10 * S] + aw + [S], aa, seed), log_std, hr.mlp([10 * S] + cw + [1], ca, seed + 2)
@@ -64,11 +73,15 @@ def _noise_seed():
     """The first seed from 7 on whose large-noise rows number 3 .. 7 in every 12-row chunk of ``row_order(2)``.  Those rows clip
     from the start; at the sb3 case (16 positions) sixteen steps of 3e-4 move the policy far enough to clip up to three small-noise rows
     more, so the room above is theirs.  tests/test_ppo_head_cpu.py holds the twin's clip fraction of every such minibatch strictly
-    inside (0.1, 0.9)."""
-    order = row_order(2).long()
+    inside (0.1, 0.9).  The same share -- a quarter to seven twelfths -- holds in every chunk of the long record's order
+    (``row_order(2, n=N_LONG)`` in minibatches of LONG_MINIBATCH: 257 and 31 rows per epoch) and so in its 288 rows as one minibatch;
+    tests/test_ppo_head_shapes_cpu.py holds the twin's clip fractions there."""
+    order, long_order = row_order(2).long(), row_order(2, n=N_LONG).long()
     for seed in range(7, 1000):
         big = (logp_noise(N, seed).abs() > 0.3).to(torch.float64)[order]
-        if all(3 <= int(c.sum()) <= 7 for ep in big for c in ep.split(MINIBATCH)):
+        long_big = (logp_noise(N_LONG, seed).abs() > 0.3).to(torch.float64)[long_order]
+        if all(3 <= int(c.sum()) <= 7 for ep in big for c in ep.split(MINIBATCH)) and all(
+                3 * len(c) <= 12 * int(c.sum()) <= 7 * len(c) for ep in long_big for c in ep.split(LONG_MINIBATCH)):
             return seed
     raise AssertionError("no seed")
 
@@ -85,12 +98,13 @@ NOISE_SEED = _noise_seed()
 _SYNTH = {}
 
 
-def synthetic_record(case, seed=3):
-    """A record shaped as ``collect_head()`` fills it, on the CPU (computed once, shared, never modified): random observations,
+def synthetic_record(case, seed=3, T=T, net_seed=61):
+    """A record of ``T`` TTIs shaped as ``collect_head()`` fills it, on the CPU (computed once, shared, never modified): random observations,
     actions drawn from the case's own policy, logp that policy's log-probability plus ``logp_noise``, random adv / vtarg."""
-    if (case, seed) not in _SYNTH:
-        S = CASES[case][0]
-        actor, log_std, _ = head_nets(case)
+    key = (repr(case), seed, T, net_seed)
+    if key not in _SYNTH:
+        S = spec(case)[0]
+        actor, log_std, _ = head_nets(case, net_seed)
         g = torch.Generator().manual_seed(seed)
         obs = torch.rand((T, B, 10 * S), generator=g)
         with torch.no_grad():
@@ -99,17 +113,17 @@ def synthetic_record(case, seed=3):
         sd = torch.exp(log_std.double())
         action = mean + sd * torch.randn((T, B, S), generator=g, dtype=torch.float64)
         logp = torch.distributions.Normal(mean, sd.expand_as(mean)).log_prob(action).sum(dim=-1)
-        _SYNTH[(case, seed)] = {"obs_head": obs, "action": action, "logp": logp.to(torch.float32) + logp_noise(N, NOISE_SEED).reshape(T, B),
+        _SYNTH[key] = {"obs_head": obs, "action": action, "logp": logp.to(torch.float32) + logp_noise(T * B, NOISE_SEED).reshape(T, B),
                                 "adv": torch.randn((T, B), generator=g), "vtarg": torch.randn((T, B), generator=g),
                                 "vf": torch.randn((T + 1, B), generator=g)}
-    return _SYNTH[(case, seed)]
+    return _SYNTH[key]
 
 
 def twin(case, rec, order, lay=None, dtype=torch.float64, slip=None, **kw):
     from intent_radio_sched_multi_slice_amd.adapters import ppo_head_update_reference
     actor, log_std, critic = layers(case) if lay is None else lay
-    return ppo_head_update_reference({k: v.cpu() for k, v in rec.items()}, actor, log_std, critic, order, act_actor=CASES[case][2],
-                                     act_critic=CASES[case][4], dtype=dtype, slip=slip, **kw)
+    return ppo_head_update_reference({k: v.cpu() for k, v in rec.items()}, actor, log_std, critic, order, act_actor=spec(case)[2],
+                                     act_critic=spec(case)[4], dtype=dtype, slip=slip, **kw)
 
 
 def packed_floats(net):
@@ -156,10 +170,10 @@ def forward_bounds(case, rec, rows, lay, clip):
     / sigma_j, so a row's logp moves by at most E = sum_j (|z_j| + d_j / 2) d_j with d_j = t_j / sigma_j, its ratio r by r expm1(E), and
     min(r A, clamp(r) A) -- 1-Lipschitz in r A -- by |A| r expm1(E); the statistics are the rows' means."""
     from tests import policy_ref as pr
-    S = CASES[case][0]
+    S = spec(case)[0]
     rows = torch.as_tensor(rows).long().reshape(-1)
     x = rec["obs_head"].reshape(-1, 10 * S)[rows].cpu().numpy()
-    mean, t = pr.mlp64(x, [(w.numpy(), b.numpy()) for w, b in lay[0]], CASES[case][2])
+    mean, t = pr.mlp64(x, [(w.numpy(), b.numpy()) for w, b in lay[0]], spec(case)[2])
     sd = np.exp(lay[1].numpy().astype(np.float64))
     z = (rec["action"].reshape(-1, S)[rows].cpu().numpy() - mean) / sd
     d = t / sd
@@ -180,7 +194,7 @@ def check_head_against_twin(case, rec, order, out, lay, what, hp=None, twin_orde
     twin_order = order if twin_order is None else twin_order
     args = dict(epochs=1, minibatch=ALL, lr=0.0, grad_clip=0.0, **hp)
     t64, t32 = twin(case, rec, twin_order, lay, **args), twin(case, rec, twin_order, lay, dtype=torch.float32, **args)
-    S = CASES[case][0]
+    S = spec(case)[0]
     dev = tensors(unpack_head_grad(out["grad"].cpu().numpy(), lay[0], lay[2], S))
     r = ratios(dev, tensors(t64["grad"]), tensors(t32["grad"]), scale)
     worst = max(v[0] for v in r.values())
@@ -204,17 +218,17 @@ def check_head_against_twin(case, rec, order, out, lay, what, hp=None, twin_orde
 
 
 # ---- GPU fixtures -------------------------------------------------------------------------------------------------------------------
-def make_env(case, stochastic=True, bind=True, ppo=True, seed=SEED):
+def make_env(case, stochastic=True, bind=True, ppo=True, seed=SEED, net_seed=61):
     """A reset env of B envs at the case's shape under the case's head nets (head PPO state bound); returns (env, (actor layers,
     log_std, critic layers))"""
     from tests import inter_head_ref as ih
-    S, _, aa, _, ca, observation, _ = CASES[case]
+    S, _, aa, _, ca, observation, _ = spec(case)
     if observation == "inter":
         _, env, _ = ih.make_env(ENV_SIZES[S], "64x64", "gauss_clip", B, bind=False)
     else:
         _, env, _ = hr.make_env(ENV_SIZES[S], "64x64", "gauss_clip", B, bind=False)
     assert env.S == S
-    lay = layers(case)
+    lay = layers(case, net_seed)
     if bind:
         bind_nets(env, case, lay, stochastic, seed)
         if ppo:
@@ -224,15 +238,15 @@ def make_env(case, stochastic=True, bind=True, ppo=True, seed=SEED):
 
 
 def bind_nets(env, case, lay, stochastic=True, seed=SEED):
-    _, _, aa, _, ca, observation, _ = CASES[case]
+    _, _, aa, _, ca, observation, _ = spec(case)
     env.set_head_policy_network(lay[0], "gauss_clip", lay[1], stochastic=stochastic, seed=seed, activation=aa, observation=observation,
                                 allow_sorted=observation == "inter")
     env.set_head_value_network(lay[2], activation=ca)
 
 
-def collect(env, case):
+def collect(env, case, T=T):
     """A private copy of ``collect_head(T)``'s record (the env reuses its tensors)"""
-    return {k: v.clone() for k, v in env.collect_head(T, reward=CASES[case][6]).items()}
+    return {k: v.clone() for k, v in env.collect_head(T, reward=spec(case)[6]).items()}
 
 
 def head_weights(env):

@@ -17,7 +17,12 @@ SEED = 7400                              # the nets' seed: tests/test_ppo_wide_c
 RECORD_SEED = 23
 # name -> (hidden widths, activation, intra input layout): the reference's `verybig`, and the shape one step past the plain plan's limit
 # (170 496 bytes there, tests/test_gpu_ppo_update_shapes.py)
-BEYOND = {"verybig": ([512, 512, 512], "tanh", "obs"), "past_limit": ([512, 512, 96], "relu", "mask_obs")}
+# (170 496 bytes there, tests/test_gpu_ppo_update_shapes.py), and `deepest`, the largest net the acting path accepts: the wide plan's LDS
+# need does not grow with depth, its parked rows and its layer loop do
+BEYOND = {"verybig": ([512, 512, 512], "tanh", "obs"), "past_limit": ([512, 512, 96], "relu", "mask_obs"),
+          "deepest": ([512, 512, 512, 512], "tanh", "obs")}
+# The shapes of ref.SHAPES that fit BOTH plans: the bit-identity test of the GPU file runs on every one of them
+BOTH_PLANS_SHAPES = ("A", "B", "C", "D", "E", "F")
 # The mixed population: [(hidden widths, activation)] per member, actor and critic alike; members 0 and 2 fit the plain plan
 MIXED = [([64, 64], "tanh"), ([512, 512, 512], "tanh"), ([256, 256, 256], "relu")]
 MIXED_LAYOUT = "obs"

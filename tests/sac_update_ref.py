@@ -23,7 +23,8 @@ from tests import sac_ref as sr
 # name -> (S, actor widths, actor activation, critic widths, critic activation)
 CASES = {"base": (5, [24], "relu", [40, 24], "tanh"), "deg": (1, [7, 100], "relu", [96], "tanh"),
          "stride": (6, [40, 24], "tanh", [160, 7, 96], "relu"), "two_pair": (16, [64, 64], "relu", [64, 64], "relu")}
-ENV_SHAPES = {5: hr.SIZES["S5U25"], 1: hs.ENV_SHAPES[1], 6: hs.ENV_SHAPES[6], 16: hs.ENV_SHAPES[16]}
+ENV_SHAPES = {5: hr.SIZES["S5U25"], 1: hs.ENV_SHAPES[1], 6: hs.ENV_SHAPES[6], 16: hs.ENV_SHAPES[16],
+              3: hs.ENV_SHAPES[3], 8: hs.ENV_SHAPES[8], 10: hr.SIZES["S10U100"]}      # (3, 8, 10: tests/sac_update_shapes_ref.py's grid)
 B, RING_SLOTS, ROWS = 12, 4, 96          # a ring of four TTIs of twelve envs; the longest batch: three tiles
 NET_SEED, BATCH_SEED = 31, 5             # tests/test_sac_update_cpu.py holds the conditions on the inputs for these
 SEED, DRAW = 77, 3
@@ -34,6 +35,11 @@ FACTOR, FLOOR = 8.0, 1e-6
 TENSORS = ("actor", "q1", "q2")
 
 
+def spec(case):
+    """A case's tuple: ``case`` a name of CASES, or such a tuple itself (tests/sac_update_shapes_ref.py's grid)"""
+    return CASES[case] if isinstance(case, str) else tuple(case)
+
+
 def nets(case, seed=NET_SEED):
     """(actor, q1, q2) modules of a case, in head_shapes_ref.sac_nets' manner: the log_std half of the actor's output bias sits around
     the lower clamp at positions 0, 8, .., above the upper clamp at 1, 9, .., elsewhere at a small deviation -- more than half of the
@@ -42,7 +48,7 @@ def nets(case, seed=NET_SEED):
     of the actor's.  The second critic's output bias is moved so that, over the synthetic batch under the actor's own actions (the
     actor pass's draws at first_row 0), each critic is the smaller one on about half of the rows and zero lies in the middle of the
     widest gap between two neighbouring values of Q1 - Q2 among the central quarter: no row comes near a tie."""
-    S, aw, aact, qw, qact = CASES[case]
+    S, aw, aact, qw, qact = spec(case)
     actor = hr.mlp([10 * S] + aw + [2 * S], aact, seed, sr.OUT_SCALE)
     lo, hi, mid = sr.LOG_STD_BIAS
     with torch.no_grad():
@@ -78,7 +84,7 @@ def case_layers(case, seed=NET_SEED):
 
 
 def _observations(case, n, seed):
-    S = CASES[case][0]
+    S = spec(case)[0]
     rng = np.random.default_rng(seed)
     shape = (n, 10 * S)
     obs = rng.standard_normal(shape) * rng.choice([0.05, 0.25, 1.0], size=shape) * sr.OBS_SCALE
@@ -89,7 +95,7 @@ def _observations(case, n, seed):
 def synthetic_batch(case, n=ROWS, seed=BATCH_SEED):
     """A batch shaped as ``replay_sample`` returns it, on the CPU: sac_ref.sac_inputs' observations, actions inside (-1, 1) with some on
     the boundary, rewards of both signs, a third of the rows terminal."""
-    S = CASES[case][0]
+    S = spec(case)[0]
     rng = np.random.default_rng(seed + 1000)
     action = np.tanh(rng.standard_normal((n, S)) * 1.5).astype(np.float32)
     action[rng.random((n, S)) < 0.05] = 1.0
@@ -105,7 +111,7 @@ def head(batch, n):
 def twin(case, batch, nets_, lec, dtype=torch.float64, **kw):
     """adapters.sac_update_reference on a case: ``nets_`` = (actor, q1, q2, q1_target, q2_target) layer lists"""
     from intent_radio_sched_multi_slice_amd.adapters import sac_update_reference
-    _, _, aact, _, qact = CASES[case]
+    _, _, aact, _, qact = spec(case)
     args = dict(gamma=GAMMA, tau=TAU, seed=SEED, draw=DRAW, act_actor=aact, act_critic=qact)
     args.update(kw)
     return sac_update_reference({k: torch.as_tensor(v).cpu() for k, v in batch.items()}, *nets_, lec, dtype=dtype, **args)
@@ -175,7 +181,7 @@ def conditions(case, batch, nets_, lec, first_row=0):
     """The figures the tests' inputs are held to, on one minibatch = the whole ``batch``: the critics' separation against sac_ref's
     rigorous float32 bounds on [obs | a32], the share of rows on which each critic is the smaller, and the clamp census of log_std."""
     from intent_radio_sched_multi_slice_amd.adapters import sac_actor_noise
-    S, _, aact, _, qact = CASES[case]
+    S, _, aact, _, qact = spec(case)
     actor, q1, q2 = pu.as_sequential(nets_[0], aact), pu.as_sequential(nets_[1], qact), pu.as_sequential(nets_[2], qact)      # (modules: they carry the activation)
     obs = torch.as_tensor(batch["obs"]).detach().cpu().numpy().astype(np.float32)
     n = obs.shape[0]
@@ -192,7 +198,7 @@ def conditions(case, batch, nets_, lec, first_row=0):
 def make_env(case, slabs=32, ent_coef="auto_%g" % ENT_INIT, bind=True, seed=NET_SEED):
     """A reset env of the case's shape under the case's actor ("gauss_tanh", stochastic) and critics, a ring of RING_SLOTS TTIs filled
     by one real ``collect_replay``, and -- ``bind`` -- the SAC binding.  Returns (env, (actor, q1, q2) layer lists)."""
-    S = CASES[case][0]
+    S = spec(case)[0]
     _, env, _ = hr.make_env(ENV_SHAPES[S], "64x64", "gauss_tanh", B, bind=False)
     actor, q1, q2 = nets(case, seed)
     env.set_head_policy_network(actor, "gauss_tanh", stochastic=True, seed=1)

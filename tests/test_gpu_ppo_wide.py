@@ -25,7 +25,9 @@ ALL = ref.ALL
 G = wd.G
 HP_LOOP = dict(lr=2e-3, clip=0.2, vf_coeff=0.5, ent_coeff=0.01, grad_clip=0.5)
 KINDS = (("inter", "inter", "v_inter"), ("intra", "intra", "v_intra"))
-BOTH_PLANS = ["tanh40x24", "B", "E", "F"]          # ref.CASES' and ref.SHAPES'
+# ref.CASES' tanh40x24 and every shape of ref.SHAPES that fits both plans (tests/test_ppo_wide_cpu.py holds that list to ref.SHAPES): A is
+# the plain plan's own edge [512, 512, 32], C is S 16 with 2 S = 32 outputs and no padding, D is S 1
+BOTH_PLANS = ["tanh40x24"] + list(wd.BOTH_PLANS_SHAPES)
 
 
 def _order(rec, first, epochs, seed=3):
@@ -159,12 +161,13 @@ def _on_device(env, d):
 
 @pytest.mark.parametrize("case", list(wd.BEYOND))
 def test_nets_beyond_the_plain_plan_against_the_float64_twin(case):
-    """[512, 512, 512] tanh and [512, 512, 96] relu actors and critics, inter and intra, members of 2 / 4 / 6 envs.  One minibatch of
+    """[512, 512, 512] tanh, [512, 512, 96] relu and [512, 512, 512, 512] tanh (`deepest`: the largest net the acting path accepts, five
+    layers of parked rows) actors and critics, inter and intra, members of 2 / 4 / 6 envs.  One minibatch of
     all rows at lr 0: dev_grad per layer tensor (padding exact zeros) within 8x the float32-torch yardstick of the float64 twin and
     the five statistics within 1e-6; then one Adam step within 4 float32 ulp of ref.adam_step_f32 on the device's own gradient, the
     padding of m and v exact zeros, the counters reading 1.  The launch's LDS bytes are the restated wide formula.
-    Measured on one MI355X, worst device error over the yardstick: 1.72 (verybig), 0.93 (past_limit); Adam 0 ulp on all 6 544 941 /
-    3 980 685 weights and on their moments."""
+    Measured on one MI355X, worst device error over the yardstick: 1.72 (verybig), 0.93 (past_limit), 1.77 (deepest); Adam 0 ulp on
+    all 6 544 941 / 3 980 685 / 9 696 813 weights and on their moments."""
     widths, act, layout = wd.BEYOND[case]
     env = _beyond_env(case)
     rec, order = _on_device(env, wd.beyond_record(case)), _on_device(env, wd.order(wd.beyond_record(case), 1))

@@ -112,6 +112,26 @@ def test_the_shapes_the_gpu_file_relies_on():
     assert packed_net_floats(wd.kind_dims(wd.OUTGROWS_EXTENT, wd.MIXED_LAYOUT)["inter"][0]) > extent
 
 
+def test_the_bit_identity_list_is_every_shape_that_fits_both_plans():
+    """wd.BOTH_PLANS_SHAPES is every entry of ref.SHAPES whose nets fit the plain plan (the wide plan holds every net); A sits at that
+    plan's own edge, 162 304 of 163 840 bytes.  `deepest` is the largest net the acting path accepts: it sits AT the wide plan's bound,
+    parks four slabs of 516 floats a row behind the input's, and lies far beyond the plain plan."""
+    from intent_radio_sched_multi_slice_amd.batched_env import ppo_lds_bytes, ppo_wide_scratch_floats
+    fits = []
+    for name, (S_, Us, layout, (aw, _), (cw, _)) in ref.SHAPES.items():
+        if ref.lds_bytes(S_, Us, layout, aw, cw) <= ref.LDS_MAX:
+            fits.append(name)
+    assert tuple(fits) == tuple(wd.BOTH_PLANS_SHAPES) == tuple(ref.SHAPES)
+    S_, Us, layout, (aw, _), (cw, _) = ref.SHAPES["A"]
+    assert ref.lds_bytes(S_, Us, layout, aw, cw) == 162304
+    widths, _, layout = wd.BEYOND["deepest"]
+    assert widths == [512] * 4
+    for actor, critic in wd.kind_dims(widths, layout).values():
+        assert ppo_lds_bytes(actor, critic) > ref.LDS_MAX
+        assert ppo_lds_bytes(actor, critic, wide=True) == wd.WIDE_LDS_MAX
+        assert ppo_wide_scratch_floats(actor, critic) == 32 * (ref.net_ld(ref.pad32(actor[0])) + 4 * 516)
+
+
 def _twin_is_healthy(rec, nets, acts, layout, what):
     from intent_radio_sched_multi_slice_amd import adapters as ad
     o = wd.order(rec, 1)
