@@ -9,7 +9,10 @@ Eight objects, compiled in parallel, then linked:
                         its four kernels -- uniform and mixed populations, each under the plain and the wide LDS plan -- expand one
                         body, ranenv_ppo_body.hpp; a fifth trains the head policies, ranenv_ppo_update_head)
   ranenv_sac.hip        the SAC update (ranenv_sac_update: per gradient step a critic pass, an actor pass and two elementwise applies,
-                        the rows of a minibatch spread over workgroups; shares ranenv_ppo_parts.hpp with ranenv_ppo.hip)
+                        the rows of a minibatch spread over workgroups)
+                        Both are built from ranenv_ppo_parts.hpp, the one statement of every step they share: the backward pass and
+                        its dZ' walk, Adam's constants and element step, and the steps of a PPO minibatch (advantage mean and std,
+                        row list, clipped surrogate, critic row, joint norm and clip, statistics)
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <array>
@@ -2160,6 +2161,47 @@ static void ppo_member_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, int 
     if (park) *park = wide ? ppo_wide_scratch(a, c) : 0;
 }
 
+// THE walk over the shapes the update trains: f(member, kind, actor + critic floats, LDS bytes, parked floats) for every bound kind
+// and (a mixed binding) every one of the `members`, in order, until one returns other than RANENV_OK
+static int ppo_each_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wide, int members, const std::function<int(int, int, long long, size_t, long long)> &f)
+{
+    for (int k = 0; k < 2; k++) {
+        if (!slot[k]) continue;
+        for (int m = 0; m < (mixed ? members : 1); m++) {
+            long long af, cf, park; size_t lds;
+            ppo_member_shape(slot, mixed, m, k, af, cf, lds, wide, &park);
+            if (const int rc = f(m, k, af + cf, lds, park); rc != RANENV_OK) return rc;
+        }
+    }
+    return RANENV_OK;
+}
+
+// The largest needs over that walk: the gradient's floats, the LDS bytes -- of kinds < lds_kinds alone: a call that updates no intra
+// rows launches with the inter nets' -- and (wide) the parked floats per workgroup
+struct PpoPlan { long long grad_floats; size_t lds; long long park; };
+static PpoPlan ppo_plan(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wide, int members, int lds_kinds = 2)
+{
+    PpoPlan p{};
+    ppo_each_shape(slot, mixed, wide, members, [&](int, int k, long long floats, size_t lds, long long park) {
+        p.grad_floats = std::max(p.grad_floats, floats);
+        if (k < lds_kinds) p.lds = std::max(p.lds, lds);
+        p.park = std::max(p.park, park);
+        return (int)RANENV_OK;
+    });
+    return p;
+}
+
+// `slot`'s Adam moments and gradient scratch (3 x cap floats; an outgrown allocation grows, a larger one stays, like the weights'), zeroed
+static int opt_ensure(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
+{
+    if (slot->opt_cap < slot->cap) {
+        if (const int rc = dev_alloc(h, &slot->opt, 3 * (size_t)slot->cap); rc != RANENV_OK) return rc;
+        slot->opt_cap = slot->cap;
+    }
+    HIP_TRY(h, hipMemsetAsync(slot->opt, 0, sizeof(float) * 3 * (size_t)slot->opt_cap, s));
+    return RANENV_OK;
+}
+
 // The slots the update trains, by role number: the serving ones (null: none bound), and the member count -- or what ranenv_ppo_bind
 // (mixed: ranenv_ppo_bind_mixed, whose LDS plan holds per member; wide: ranenv_ppo_bind_wide, which checks the wide plan in its place)
 // refuses.  No device call.
@@ -2179,18 +2221,12 @@ static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members,
     members = n_pop ? h->pop.n : 1;
     for (int r = 0; r < 4; r++)
         if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
-    for (int k = 0; k < 2; k++) {
-        if (!slot[k]) continue;
-        for (int m = 0; m < (mixed ? members : 1); m++) {
-            long long af, cf; size_t lds;
-            ppo_member_shape(slot, mixed, m, k, af, cf, lds, wide);
-            if (lds <= (size_t)PPO_LDS_MAX) continue;
-            if (wide) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
-            if (mixed) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
-            return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
-        }
-    }
-    return RANENV_OK;
+    return ppo_each_shape(slot, mixed, wide, members, [&](int m, int k, long long, size_t lds, long long) {
+        if (lds <= (size_t)PPO_LDS_MAX) return (int)RANENV_OK;
+        if (wide) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+        if (mixed) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+        return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+    });
 }
 
 // A mixed binding's per-member packed floats [4][POP_MAX] (0: the role is not bound) as the slots stand, to the device on the caller's stream
@@ -2249,16 +2285,7 @@ static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     if (wide) {         // the parked rows: the largest need over the members and the kinds, for members x 2 workgroups
-        long long park = 0;
-        for (int k = 0; k < 2; k++) {
-            if (!slot[k]) continue;
-            for (int m = 0; m < (mixed ? members : 1); m++) {
-                long long af, cf, p; size_t lds;
-                ppo_member_shape(slot, mixed, m, k, af, cf, lds, true, &p);
-                park = p > park ? p : park;
-            }
-        }
-        const long long need = park * 2 * members;
+        const long long need = ppo_plan(slot, mixed, true, members).park * 2 * members;
         if (h->ppo_park_cap < need) {
             if (const int rc = dev_alloc(h, &h->d_ppo_park, (size_t)need); rc != RANENV_OK) return rc;
             h->ppo_park_cap = need;
@@ -2273,14 +2300,9 @@ static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream)
     if (mixed && !h->d_ppo_floats)
         if (const int rc = dev_alloc(h, &h->d_ppo_floats, (size_t)4 * POP_MAX); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipMemsetAsync(h->d_ppo_t, 0, sizeof(int32_t) * POP_MAX * 2, s));
-    for (int r = 0; r < 4; r++) {
-        if (!slot[r]) continue;
-        if (slot[r]->opt_cap < slot[r]->cap) {       // (an outgrown one stays allocated, like the weights')
-            if (const int rc = dev_alloc(h, &slot[r]->opt, 3 * (size_t)slot[r]->cap); rc != RANENV_OK) return rc;
-            slot[r]->opt_cap = slot[r]->cap;
-        }
-        HIP_TRY(h, hipMemsetAsync(slot[r]->opt, 0, sizeof(float) * 3 * (size_t)slot[r]->opt_cap, s));
-    }
+    for (int r = 0; r < 4; r++)
+        if (slot[r])
+            if (const int rc = opt_ensure(h, slot[r], s); rc != RANENV_OK) return rc;
     h->ppo_on = true; h->ppo_mixed = mixed; h->ppo_wide = wide;
     return mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
@@ -2303,16 +2325,10 @@ static int ppo_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
     if (!h->ppo_wide) return RANENV_OK;
     // a wide binding: every workgroup's parked rows fit the share of the scratch it was given at bind
     if ((long long)members * 2 * h->ppo_park_stride > h->ppo_park_cap) return fail(h, RANENV_E_STATE, "the population has grown since ranenv_ppo_bind_wide: bind again");
-    for (int k = 0; k < 2; k++) {
-        if (!slot[k]) continue;
-        for (int m = 0; m < (h->ppo_mixed ? members : 1); m++) {
-            long long af, cf, p; size_t lds;
-            ppo_member_shape(slot, h->ppo_mixed, m, k, af, cf, lds, true, &p);
-            if (p > h->ppo_park_stride)
-                return fail(h, RANENV_E_STATE, "the %s nets park %lld floats of rows per workgroup, ranenv_ppo_bind_wide allocated %lld: bind again", k ? "intra" : "inter", p, h->ppo_park_stride);
-        }
-    }
-    return RANENV_OK;
+    return ppo_each_shape(slot, h->ppo_mixed, true, members, [&](int, int k, long long, size_t, long long p) {
+        if (p <= h->ppo_park_stride) return (int)RANENV_OK;
+        return fail(h, RANENV_E_STATE, "the %s nets park %lld floats of rows per workgroup, ranenv_ppo_bind_wide allocated %lld: bind again", k ? "intra" : "inter", p, h->ppo_park_stride);
+    });
 }
 
 static PpoNet ppo_net(const ranenv::NetSlot *slot)
@@ -2332,18 +2348,9 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
     int members = 0;
     const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide;
     if (const int rc = ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
-    long long g = 0; size_t lds = 0;
-    for (int k = 0; k < 2; k++) {
-        if (!slot[k]) continue;
-        for (int m = 0; m < (mixed ? members : 1); m++) {
-            long long af, cf; size_t l;
-            ppo_member_shape(slot, mixed, m, k, af, cf, l, wide);
-            g = af + cf > g ? af + cf : g;
-            lds = l > lds ? l : lds;
-        }
-    }
-    if (grad_floats) *grad_floats = g;
-    if (lds_bytes) *lds_bytes = (int64_t)lds;
+    const PpoPlan plan = ppo_plan(slot, mixed, wide, members);
+    if (grad_floats) *grad_floats = plan.grad_floats;
+    if (lds_bytes) *lds_bytes = (int64_t)plan.lds;
     return RANENV_OK;
 }
 
@@ -2468,17 +2475,8 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
     a.hp = h->d_ppo_hp; a.traj = *traj; a.t = h->d_ppo_t; a.max_epochs = max_epochs; a.stats = stats; a.grad = grad; a.probe_logp = probe_logp;
     // The launch's LDS: the largest need over the kinds this call updates (a mixed binding: and over the members).  dev_grad's stride
     // is ranenv_ppo_layout's: the largest of the BOUND nets, whether or not this call updates the intra kind
-    long long gf = 0; size_t lds = 0;
-    for (int k = 0; k < 2; k++) {
-        if (!slot[k]) continue;
-        for (int m = 0; m < (mixed ? members : 1); m++) {
-            long long af, cf; size_t l;
-            ppo_member_shape(slot, mixed, m, k, af, cf, l, wide);
-            gf = af + cf > gf ? af + cf : gf;
-            if (a.net[k][0].net.n_layers > 0) lds = l > lds ? l : lds;
-        }
-    }
-    a.grad_stride = gf;
+    const PpoPlan plan = ppo_plan(slot, mixed, wide, members, intra ? 2 : 1);
+    a.grad_stride = plan.grad_floats;
     PpoMixed x{};
     if (mixed) {        // (every bound role is the population's: its table; the others the table of zeros)
         for (int k = 0; k < 2; k++)
@@ -2489,7 +2487,7 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)members, hipMemcpyHostToDevice, s));
     const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_bound: every workgroup's rows fit its share)
-    HIP_TRY(h, launch_ppo_update(s, members, lds, a, mixed ? &x : nullptr, wide ? &y : nullptr));
+    HIP_TRY(h, launch_ppo_update(s, members, plan.lds, a, mixed ? &x : nullptr, wide ? &y : nullptr));
     return RANENV_OK;
 }
 
@@ -2582,13 +2580,8 @@ int ranenv_ppo_bind_head(ranenv_handle h, void *stream)
     }
     HIP_TRY(h, hipMemsetAsync(h->d_ppo_head_t, 0, sizeof(int32_t), s));
     HIP_TRY(h, hipMemsetAsync(h->d_head_ls_opt, 0, sizeof(float) * 3 * S, s));
-    for (ranenv::NetSlot *x : {&h->head, &h->head_value}) {
-        if (x->opt_cap < x->cap) {       // (an outgrown one stays allocated, like the weights')
-            if (const int rc = dev_alloc(h, &x->opt, 3 * (size_t)x->cap); rc != RANENV_OK) return rc;
-            x->opt_cap = x->cap;
-        }
-        HIP_TRY(h, hipMemsetAsync(x->opt, 0, sizeof(float) * 3 * (size_t)x->opt_cap, s));
-    }
+    for (ranenv::NetSlot *x : {&h->head, &h->head_value})
+        if (const int rc = opt_ensure(h, x, s); rc != RANENV_OK) return rc;
     h->ppo_head_on = true;
     return RANENV_OK;
 }

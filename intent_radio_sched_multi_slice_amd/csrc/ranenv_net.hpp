@@ -263,4 +263,15 @@ constexpr double LN_1E9 = 20.72326583694641;            // ln(1e9): -ln of the m
         out = (float)((lc - mx) - log(sum));                                                                        \
     }
 
+// Enqueue a training kernel (ranenv_ppo.hip, ranenv_sac.hip) with `lds` bytes of dynamic LDS: the kernel's limit is raised to
+// PPO_LDS_MAX once per kernel and process (the static of the kernel's own instance), the launch's error returned
+template <auto KERNEL, class... A>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args)
+{
+    static const hipError_t attr = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, s, args...);
+    return hipGetLastError();
+}
+
 }  // namespace

@@ -19,13 +19,18 @@
 // Nets beyond that LDS plan train under the WIDE plan (ranenv_ppo_bind_wide; "the wide plan" below): two row buffers in LDS, every
 // layer's input rows parked in a scratch of the workgroup's own in global memory -- written and read back by vector loads and stores
 // at lane-dependent addresses behind workgroup barriers, as the weights are -- and the same arithmetic in the same order.
-// The backward pass, the workgroup sum and Adam's step live in ranenv_ppo_parts.hpp: the SAC update (ranenv_sac.hip) is built from them too.
+// Every step the training kernels share -- the backward pass, the workgroup sum, Adam, and the steps of a minibatch around the tile loop
+// (advantage mean and std, row list, clipped surrogate, critic row, joint norm and clip, statistics) -- is a function of
+// ranenv_ppo_parts.hpp, stated once: the kernels here and the SAC update (ranenv_sac.hip) call them.
 #include "ranenv_ppo_parts.hpp"
 
 namespace {
 
 constexpr int PPO_FIXED = 4096;           // bytes of LDS in front of the rows: reduction slots, per-row statistics, the tile's record rows
 constexpr int PPO_ROW_STATS = 6;          // per row: policy loss, entropy, logp_old - logp, clipped?, live?, value loss
+
+// The (logp, adv, vtarg) cell of record row i: column 0 of the inter row, column s + 1 of the env's row for slice s
+__device__ __forceinline__ size_t ppo_cell(int kind, int i, int S) { return kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S); }
 
 // The tile's rows of `net`'s input -> buffer 0: row r is record row idx[r] (< 0: a dead row, zeros), read as net_load_rows reads an
 // env's row -- the inter observation, or the slice's observation behind, for RANENV_NET_IN_MASK_OBS, its mask as floats
@@ -69,8 +74,7 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
         rs[0] = rs[1] = rs[2] = rs[3] = rs[4] = 0.0;
         return;
     }
-    // the (logp, adv, vtarg) cell of record row i: column 0 of the inter row, column s + 1 of the env's row for slice s
-    const size_t at = kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S);
+    const size_t at = ppo_cell(kind, i, S);
     const double lp_old = (double)A.traj.logp[at];
     const double adv = hp.adv_norm ? ((double)A.traj.adv[at] - a_mean) / a_den : (double)A.traj.adv[at];
     double lp = 0.0, ent = 0.0;
@@ -102,13 +106,7 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
         ent = -((p0 * q0 + p1 * q1) + p2 * q2);
     }
     if (A.probe_logp) A.probe_logp[at] = (float)lp;
-    const double ratio = exp(lp - lp_old), c_lo = 1.0 - hp.clip, c_hi = 1.0 + hp.clip;
-    const bool inside = ratio >= c_lo && ratio <= c_hi;
-    const double s1 = ratio * adv, s2 = (ratio < c_lo ? c_lo : (ratio > c_hi ? c_hi : ratio)) * adv;
-    // torch.minimum / clamp: the unclipped branch carries the gradient where it is the smaller one, both where they tie
-    const double dsdr = inside || s1 < s2 ? adv : 0.0;
-    const double gl = -(dsdr * ratio) * wrow, ge = hp.ent_coeff * wrow;
-    rs[0] = -(s1 < s2 ? s1 : s2); rs[1] = ent; rs[2] = lp_old - lp; rs[3] = inside ? 0.0 : 1.0; rs[4] = 1.0;
+    const double gl = ppo_surrogate(lp, lp_old, adv, ent, hp.clip, wrow, rs), ge = hp.ent_coeff * wrow;
     if (kind == 0) {
 #pragma unroll 1
         for (int j = 0; j < j0; j++) { o[j] = 0.0f; o[S + j] = 0.0f; }
@@ -130,8 +128,8 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
 // workgroup on the member's OWN shape -- net k's descriptor is entry `member` of the role's device table, parked in the fixed LDS region
 // at entry (the launch never writes a descriptor; A.net[kind][k].net, member 0's, says only whether the role is bound), its packed floats
 // entry `member` of the binding's per-member array.  The rows lie in LDS at the member's own strides; w, m, v and g at member x stride
-// as ever.  The body (ranenv_ppo_body.hpp) is program text expanded into each kernel, and what differs are expression macros, not
-// inline functions: the uniform kernel compiles the text it always had, instruction for instruction.
+// as ever.  The body (ranenv_ppo_body.hpp) is program text expanded into each kernel; what differs between the kernels are the two
+// expression macros below, and its steps are ranenv_ppo_parts.hpp's functions.
 // WIDE (ranenv_ppo_bind_wide): the forward and backward pass of a tile follow the wide plan above, on the workgroup's share of Y.scratch;
 // every other line of the body is the same text.
 #define PPO_NET(k) (MIXED ? park[k] : A.net[kind][k].net)
@@ -170,8 +168,10 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_mixed_wide(PpoAr
 
 // ---- the head policies (ranenv_ppo_update_head; include/ranenv.h "PPO update of the head policies") ----------------------------------
 // ONE workgroup trains the head actor, the head critic and the state-independent log_std [S] of SB3's Gaussian on a ranenv_collect_head
-// record.  A body of its own beside ranenv_ppo_body.hpp -- no population, no kinds, no mask, a third parameter tensor -- from the same
-// parts (net_layers<false, true>, ppo_backward, ppo_sum, ppo_adam, ppo_powi, the tile loop), so the two kernels above keep their text.
+// record.  A body of its own beside ranenv_ppo_body.hpp -- no population, no kinds, no mask, a third parameter tensor -- whose every
+// step that the body has too is the same ranenv_ppo_parts.hpp function (ppo_zero, ppo_adv_norm, ppo_list_rows, ppo_surrogate,
+// ppo_critic_row, ppo_backward, ppo_tile_stats, ppo_sq_sum, ppo_clip_scale, adam_step / ppo_adam, ppo_epoch_stats, ppo_grad_out).  Its
+// own: log_std and sig[], the three-step gradient at the actor's outputs, and g_ls.
 // log_std is a weight this launch rewrites: its working copy lies in the fixed LDS region (`lsw`, loaded and reloaded by lane j at a
 // lane-dependent address behind Adam's own store of the same lane), never read through a wave-uniform address.  sig[j] = exp(log_std_j)
 // in float64 is parked in the reduction slots between two ppo_sum calls (refilled per minibatch behind the advantage pass).
@@ -207,47 +207,26 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs
 #pragma unroll 1
     for (int ep = 0; ep < epochs; ep++) {
         const int32_t *list = A.order + (size_t)ep * (size_t)n;
-        double st_pl = 0.0, st_vl = 0.0, st_ent = 0.0, st_kl = 0.0, st_cf = 0.0, st_gn = 0.0, st_rows = 0.0;      // (thread 0's)
-        int n_mb = 0;
+        PpoEpoch st;                           // (thread 0's)
 #pragma unroll 1
         for (int c0 = 0; c0 < n; c0 += minibatch) {
             const int nb = n - c0 < minibatch ? n - c0 : minibatch;
             const double wrow = 1.0 / (double)nb, ge = hp.ent_coeff * wrow;
 #pragma unroll 1
-            for (int k = 0; k < 2; k++) {
-                float *g = A.net[k].g;
-                const long long f = A.net[k].floats;
-#pragma unroll 1
-                for (long long i = tid; i < f; i += 256) g[i] = 0.0f;
-            }
+            for (int k = 0; k < 2; k++) ppo_zero(A.net[k].g, A.net[k].floats, tid);
             double g_ls = 0.0;                 // (thread j < S: d/d log_std_j of the minibatch, rows in order)
             double a_mean = 0.0, a_den = 1.0;
-            if (hp.adv_norm) {                 // one float64 pass over the minibatch's advantages (entries outside the record: 0)
-                auto adv_at = [&](int k) {
+            if (hp.adv_norm)
+                ppo_adv_norm(red, nb, tid, [&](int k) {
                     const int i = list[c0 + k];
-                    if (i < 0 || i >= n_record) return 0.0;
-                    return (double)A.traj.adv[i];
-                };
-                double s = 0.0;
-#pragma unroll 1
-                for (int k = tid; k < nb; k += 256) s += adv_at(k);
-                a_mean = ppo_sum(red, s, tid) / (double)nb;
-                s = 0.0;
-#pragma unroll 1
-                for (int k = tid; k < nb; k += 256) { const double d = adv_at(k) - a_mean; s += d * d; }
-                const double ss = ppo_sum(red, s, tid);
-                a_den = (nb > 1 ? sqrt(ss / (double)(nb - 1)) : 0.0) + 1e-8;
-            }
+                    return i < 0 || i >= n_record ? 0.0 : (double)A.traj.adv[i];
+                }, a_mean, a_den);
             if (tid < S) sig[tid] = exp((double)lsw[tid]);      // (published by the tile loop's first barrier; the slots are free until the norm)
 
 #pragma unroll 1
             for (int t0 = 0; t0 < nb; t0 += NET_ROWS) {
                 __syncthreads();               // (the previous tile's backward pass and statistics are read)
-                if (tid < NET_ROWS) {
-                    int i = -1;
-                    if (t0 + tid < nb) { i = list[c0 + t0 + tid]; if (i < 0 || i >= n_record) i = -1; }
-                    rowidx[tid] = i;
-                }
+                ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
 #pragma unroll 1
                 for (int k = 0; k < 2; k++) {
                     const PpoNet &pn = A.net[k];
@@ -258,18 +237,10 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs
                     __syncthreads();
                     net_layers<false, true>(net, pn.w, cur, nxt, lane, wave);
                     const int np = net.np[net.n_layers - 1], ldo = net_ld(np);
-                    if (k == 1) {              // the critic: 2 vf_coeff (V - vtarg) / rows
+                    if (k == 1) {
                         if (tid < NET_ROWS) {
                             const int i = rowidx[tid];
-                            float *o = cur + tid * ldo;
-                            double vl = 0.0;
-                            if (i < 0) o[0] = 0.0f;
-                            else {
-                                const double d = (double)o[0] - (double)A.traj.vtarg[i];
-                                vl = d * d;
-                                o[0] = (float)(((2.0 * d) * hp.vf_coeff) * wrow);
-                            }
-                            rowstat[tid * PPO_HEAD_ROW_STATS + 5] = vl;
+                            rowstat[tid * PPO_HEAD_ROW_STATS + 5] = ppo_critic_row(cur + tid * ldo, i, [&] { return A.traj.vtarg[i]; }, hp.vf_coeff, wrow);
                         }
                     } else {
                         // 1. the row's log-probability, ratio and statistics (thread r); the outputs stay
@@ -289,12 +260,7 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs
                                     lp += RANENV_INTER_LOGP_TERM(z, ls);
                                     ent += (ls + 0.5) + HALF_LN_2PI;
                                 }
-                                const double ratio = exp(lp - lp_old), c_lo = 1.0 - hp.clip, c_hi = 1.0 + hp.clip;
-                                const bool inside = ratio >= c_lo && ratio <= c_hi;
-                                const double s1 = ratio * adv, s2 = (ratio < c_lo ? c_lo : (ratio > c_hi ? c_hi : ratio)) * adv;
-                                const double dsdr = inside || s1 < s2 ? adv : 0.0;
-                                rs[0] = -(s1 < s2 ? s1 : s2); rs[1] = ent; rs[2] = lp_old - lp; rs[3] = inside ? 0.0 : 1.0; rs[4] = 1.0;
-                                rs[6] = -(dsdr * ratio) * wrow;
+                                rs[6] = ppo_surrogate(lp, lp_old, adv, ent, hp.clip, wrow, rs);
                             }
                         }
                         __syncthreads();
@@ -326,13 +292,7 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs
                     __syncthreads();
                     ppo_backward(net, pn.w, pn.g, cur, tid);
                 }
-                if (tid == 0) {                // (rows 0..31 in order; the barriers above have published them)
-#pragma unroll 1
-                    for (int r = 0; r < NET_ROWS; r++) {
-                        const double *rs = rowstat + r * PPO_HEAD_ROW_STATS;
-                        st_pl += rs[0]; st_ent += rs[1]; st_kl += rs[2]; st_cf += rs[3]; st_rows += rs[4]; st_vl += rs[5];
-                    }
-                }
+                if (tid == 0) ppo_tile_stats(st, rowstat, PPO_HEAD_ROW_STATS, true);      // (the barriers above have published the rows')
             }
             __syncthreads();
 
@@ -340,43 +300,28 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs
             if (tid < S) A.ls_g[tid] = (float)g_ls;          // (rounded once; read back by this thread alone)
             double s = 0.0;
 #pragma unroll 1
-            for (int k = 0; k < 2; k++) {
-                const float *g = A.net[k].g;
-                const long long f = A.net[k].floats;
-#pragma unroll 1
-                for (long long i = tid; i < f; i += 256) { const double x = (double)g[i]; s += x * x; }
-            }
+            for (int k = 0; k < 2; k++) s = ppo_sq_sum(A.net[k].g, A.net[k].floats, tid, s);
             if (tid < S) { const double x = (double)A.ls_g[tid]; s += x * x; }
             const double norm = sqrt(ppo_sum(red, s, tid));
-            double sc = 1.0;
-            if (hp.grad_clip > 0.0) { sc = hp.grad_clip / (norm + 1e-6); sc = sc < 1.0 ? sc : 1.0; }
+            const float sc = (float)ppo_clip_scale(hp.grad_clip, norm);
             t += 1;
-            const float step = (float)(hp.lr / (1.0 - ppo_powi(hp.beta1, t))), sbc2 = (float)sqrt(1.0 - ppo_powi(hp.beta2, t));
-            const float b1 = (float)hp.beta1, omb1 = (float)(1.0 - hp.beta1), b2 = (float)hp.beta2, omb2 = (float)(1.0 - hp.beta2), eps = (float)hp.eps;
+            const AdamStep adam = adam_step(hp.lr, hp.beta1, hp.beta2, hp.eps, t);
 #pragma unroll 1
-            for (int k = 0; k < 2; k++) ppo_adam(A.net[k].w, A.net[k].m, A.net[k].v, A.net[k].g, A.net[k].floats, (float)sc, b1, omb1, b2, omb2, step, sbc2, eps, tid);
-            ppo_adam(A.log_std, A.ls_m, A.ls_v, A.ls_g, S, (float)sc, b1, omb1, b2, omb2, step, sbc2, eps, tid);
+            for (int k = 0; k < 2; k++) ppo_adam(A.net[k].w, A.net[k].m, A.net[k].v, A.net[k].g, A.net[k].floats, sc, adam, tid);
+            ppo_adam(A.log_std, A.ls_m, A.ls_v, A.ls_g, S, sc, adam, tid);
             if (tid < S) lsw[tid] = A.log_std[tid];          // (lane j reloads what lane j stored: the handle's copy the next collect acts on)
-            st_gn += norm * (double)nb;
-            n_mb += 1;
+            st.gn += norm * (double)nb;
+            st.n_mb += 1;
             __syncthreads();                   // (the next minibatch reads the new weights and log_std)
         }
-        if (tid == 0) {
-            double *out = A.stats + (size_t)ep * RANENV_PPO_STATS;
-            const double inv = 1.0 / (double)n;
-            out[0] = st_pl * inv; out[1] = st_vl * inv; out[2] = st_ent * inv; out[3] = st_kl * inv; out[4] = st_cf * inv; out[5] = st_gn * inv;
-            out[6] = st_rows; out[7] = (double)n_mb;
-        }
+        if (tid == 0) ppo_epoch_stats(A.stats + (size_t)ep * RANENV_PPO_STATS, st, n);
     }
     if (A.grad) {
         float *out = A.grad;
 #pragma unroll 1
         for (int k = 0; k < 2; k++) {
-            const float *g = A.net[k].g;
-            const long long f = A.net[k].floats;
-#pragma unroll 1
-            for (long long i = tid; i < f; i += 256) out[i] = g[i];
-            out += f;
+            ppo_grad_out(out, A.net[k].g, A.net[k].floats, tid);
+            out += A.net[k].floats;
         }
         if (tid < S) out[tid] = A.ls_g[tid];
     }
@@ -410,36 +355,13 @@ long long ppo_wide_scratch(const PolicyNet &actor, const PolicyNet *critic)
 
 hipError_t launch_ppo_update(hipStream_t s, int n_members, size_t lds, const PpoArgs &a, const PpoMixed *mixed, const PpoWide *wide)
 {
-    if (wide && !mixed) {
-        static const hipError_t attr_wide = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
-        if (attr_wide != hipSuccess) return attr_wide;
-        hipLaunchKernelGGL(ranenv_ppo_update_kernel_wide, dim3((unsigned)n_members, 2), dim3(256), lds, s, a, *wide);
-        return hipGetLastError();
-    }
-    if (wide) {
-        static const hipError_t attr_mixed_wide = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_mixed_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
-        if (attr_mixed_wide != hipSuccess) return attr_mixed_wide;
-        hipLaunchKernelGGL(ranenv_ppo_update_kernel_mixed_wide, dim3((unsigned)n_members, 2), dim3(256), lds, s, a, *mixed, *wide);
-        return hipGetLastError();
-    }
-    static const hipError_t attr = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
-    if (attr != hipSuccess) return attr;
-    if (!mixed) {
-        hipLaunchKernelGGL(ranenv_ppo_update_kernel, dim3((unsigned)n_members, 2), dim3(256), lds, s, a);
-        return hipGetLastError();
-    }
-    static const hipError_t attr_mixed = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_mixed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
-    if (attr_mixed != hipSuccess) return attr_mixed;
-    hipLaunchKernelGGL(ranenv_ppo_update_kernel_mixed, dim3((unsigned)n_members, 2), dim3(256), lds, s, a, *mixed);
-    return hipGetLastError();
+    const dim3 grid((unsigned)n_members, 2), block(256);
+    if (mixed && wide) return launch_lds<ranenv_ppo_update_kernel_mixed_wide>(grid, block, lds, s, a, *mixed, *wide);
+    if (wide) return launch_lds<ranenv_ppo_update_kernel_wide>(grid, block, lds, s, a, *wide);
+    if (mixed) return launch_lds<ranenv_ppo_update_kernel_mixed>(grid, block, lds, s, a, *mixed);
+    return launch_lds<ranenv_ppo_update_kernel>(grid, block, lds, s, a);
 }
 
-hipError_t launch_ppo_update_head(hipStream_t s, size_t lds, const PpoHeadArgs &a)
-{
-    static const hipError_t attr = hipFuncSetAttribute((const void *)ranenv_ppo_update_kernel_head, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(ranenv_ppo_update_kernel_head, dim3(1, 1), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
+hipError_t launch_ppo_update_head(hipStream_t s, size_t lds, const PpoHeadArgs &a) { return launch_lds<ranenv_ppo_update_kernel_head>(dim3(1, 1), dim3(256), lds, s, a); }
 
 }  // namespace ranenv_dev

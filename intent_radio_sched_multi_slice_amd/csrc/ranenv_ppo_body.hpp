@@ -35,45 +35,24 @@
 #pragma unroll 1
     for (int ep = 0; ep < epochs; ep++) {
         const int32_t *list = A.order[kind] + (size_t)ep * (size_t)A.order_stride[kind] + lo;
-        double st_pl = 0.0, st_vl = 0.0, st_ent = 0.0, st_kl = 0.0, st_cf = 0.0, st_gn = 0.0, st_rows = 0.0;      // (thread 0's)
-        int n_mb = 0;
+        PpoEpoch st;                           // (thread 0's)
 #pragma unroll 1
         for (int c0 = 0; c0 < n; c0 += minibatch) {
             const int nb = n - c0 < minibatch ? n - c0 : minibatch;
             const double wrow = 1.0 / (double)nb;
 #pragma unroll 1
-            for (int k = 0; k < n_nets; k++) {
-                float *g = A.net[kind][k].g + mem * A.net[kind][k].stride;
-                const long long f = PPO_FLOATS(k);
-#pragma unroll 1
-                for (long long i = tid; i < f; i += 256) g[i] = 0.0f;
-            }
+            for (int k = 0; k < n_nets; k++) ppo_zero(A.net[kind][k].g + mem * A.net[kind][k].stride, PPO_FLOATS(k), tid);
             double a_mean = 0.0, a_den = 1.0;
-            if (hp.adv_norm) {                 // one float64 pass over the minibatch's advantages (entries outside the record: 0)
-                auto adv_at = [&](int k) {
+            if (hp.adv_norm)
+                ppo_adv_norm(red, nb, tid, [&](int k) {
                     const int i = list[c0 + k];
-                    if (i < 0 || i >= n_record) return 0.0;
-                    return (double)A.traj.adv[kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S)];
-                };
-                double s = 0.0;
-#pragma unroll 1
-                for (int k = tid; k < nb; k += 256) s += adv_at(k);
-                a_mean = ppo_sum(red, s, tid) / (double)nb;
-                s = 0.0;
-#pragma unroll 1
-                for (int k = tid; k < nb; k += 256) { const double d = adv_at(k) - a_mean; s += d * d; }
-                const double ss = ppo_sum(red, s, tid);
-                a_den = (nb > 1 ? sqrt(ss / (double)(nb - 1)) : 0.0) + 1e-8;
-            }
+                    return i < 0 || i >= n_record ? 0.0 : (double)A.traj.adv[ppo_cell(kind, i, S)];
+                }, a_mean, a_den);
 
 #pragma unroll 1
             for (int t0 = 0; t0 < nb; t0 += NET_ROWS) {
                 __syncthreads();               // (the previous tile's backward pass and statistics are read)
-                if (tid < NET_ROWS) {
-                    int i = -1;
-                    if (t0 + tid < nb) { i = list[c0 + t0 + tid]; if (i < 0 || i >= n_record) i = -1; }
-                    rowidx[tid] = i;
-                }
+                ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
                 // ---- per net: forward, dL/d(output) per row, backward ---------------------------------------------------------------
 #pragma unroll 1
                 for (int k = 0; k < n_nets; k++) {
@@ -91,73 +70,42 @@
                         float *o = cur + tid * net_ld(np);
                         double *rs = rowstat + tid * PPO_ROW_STATS;
                         if (k == 0) ppo_actor_row(A, hp, kind, i, np, o, rs, wrow, a_mean, a_den);
-                        else {                 // the critic: 2 vf_coeff (V - vtarg) / rows
-                            double vl = 0.0;
-                            if (i < 0) o[0] = 0.0f;
-                            else {
-                                const double d = (double)o[0] - (double)A.traj.vtarg[kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S)];
-                                vl = d * d;
-                                o[0] = (float)(((2.0 * d) * hp.vf_coeff) * wrow);
-                            }
-                            rs[5] = vl;
-                        }
+                        else rs[5] = ppo_critic_row(o, i, [&] { return A.traj.vtarg[ppo_cell(kind, i, S)]; }, hp.vf_coeff, wrow);
                     }
                     __syncthreads();
                     if constexpr (WIDE) ppo_backward<true>(net, w, g, cur, tid, act, act + ppo_wide_floats(net), wpark);
                     else ppo_backward(net, w, g, cur, tid);
                 }
-                if (tid == 0) {                // (rows 0..31 in order; the barriers above have published them)
-#pragma unroll 1
-                    for (int r = 0; r < NET_ROWS; r++) {
-                        const double *rs = rowstat + r * PPO_ROW_STATS;
-                        st_pl += rs[0]; st_ent += rs[1]; st_kl += rs[2]; st_cf += rs[3]; st_rows += rs[4];
-                        if (n_nets == 2) st_vl += rs[5];
-                    }
-                }
+                if (tid == 0) ppo_tile_stats(st, rowstat, PPO_ROW_STATS, n_nets == 2);      // (the barriers above have published the rows')
             }
             __syncthreads();
 
             // ---- joint norm, clip, Adam -------------------------------------------------------------------------------------------
             double s = 0.0;
 #pragma unroll 1
-            for (int k = 0; k < n_nets; k++) {
-                const float *g = A.net[kind][k].g + mem * A.net[kind][k].stride;
-                const long long f = PPO_FLOATS(k);
-#pragma unroll 1
-                for (long long i = tid; i < f; i += 256) { const double x = (double)g[i]; s += x * x; }
-            }
+            for (int k = 0; k < n_nets; k++) s = ppo_sq_sum(A.net[kind][k].g + mem * A.net[kind][k].stride, PPO_FLOATS(k), tid, s);
             const double norm = sqrt(ppo_sum(red, s, tid));
-            double sc = 1.0;
-            if (hp.grad_clip > 0.0) { sc = hp.grad_clip / (norm + 1e-6); sc = sc < 1.0 ? sc : 1.0; }
+            const float sc = (float)ppo_clip_scale(hp.grad_clip, norm);
             t += 1;
-            const float step = (float)(hp.lr / (1.0 - ppo_powi(hp.beta1, t))), sbc2 = (float)sqrt(1.0 - ppo_powi(hp.beta2, t));
-            const float b1 = (float)hp.beta1, omb1 = (float)(1.0 - hp.beta1), b2 = (float)hp.beta2, omb2 = (float)(1.0 - hp.beta2), eps = (float)hp.eps;
+            const AdamStep adam = adam_step(hp.lr, hp.beta1, hp.beta2, hp.eps, t);
 #pragma unroll 1
             for (int k = 0; k < n_nets; k++) {
                 const PpoNet &pn = A.net[kind][k];
                 const long long at = mem * pn.stride;
-                ppo_adam(pn.w + at, pn.m + at, pn.v + at, pn.g + at, PPO_FLOATS(k), (float)sc, b1, omb1, b2, omb2, step, sbc2, eps, tid);
+                ppo_adam(pn.w + at, pn.m + at, pn.v + at, pn.g + at, PPO_FLOATS(k), sc, adam, tid);
             }
-            st_gn += norm * (double)nb;
-            n_mb += 1;
+            st.gn += norm * (double)nb;
+            st.n_mb += 1;
             __syncthreads();                   // (the next minibatch reads the new weights)
         }
-        if (tid == 0) {
-            double *out = A.stats + (((size_t)mem * 2 + kind) * (size_t)A.max_epochs + ep) * RANENV_PPO_STATS;
-            const double inv = 1.0 / (double)n;
-            out[0] = st_pl * inv; out[1] = st_vl * inv; out[2] = st_ent * inv; out[3] = st_kl * inv; out[4] = st_cf * inv; out[5] = st_gn * inv;
-            out[6] = st_rows; out[7] = (double)n_mb;
-        }
+        if (tid == 0) ppo_epoch_stats(A.stats + (((size_t)mem * 2 + kind) * (size_t)A.max_epochs + ep) * RANENV_PPO_STATS, st, n);
     }
     if (A.grad) {
         float *out = A.grad + ((size_t)mem * 2 + kind) * (size_t)A.grad_stride;
 #pragma unroll 1
         for (int k = 0; k < n_nets; k++) {
-            const float *g = A.net[kind][k].g + mem * A.net[kind][k].stride;
-            const long long f = PPO_FLOATS(k);
-#pragma unroll 1
-            for (long long i = tid; i < f; i += 256) out[i] = g[i];
-            out += f;
+            ppo_grad_out(out, A.net[kind][k].g + mem * A.net[kind][k].stride, PPO_FLOATS(k), tid);
+            out += PPO_FLOATS(k);
         }
     }
     if (tid == 0) A.t[mem * 2 + kind] = t;

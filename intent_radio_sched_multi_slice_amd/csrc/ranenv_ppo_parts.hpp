@@ -1,7 +1,9 @@
-// ranenv_ppo_parts.hpp -- the device functions the training kernels share (ranenv_ppo.hip: the PPO updates; ranenv_sac.hip: the SAC
-// update): the LDS size of a net's rows, the backward pass of one 32-row tile on the f32 matrix cores, the workgroup sum in slot order,
-// Adam's float32 step and the bias corrections' powers.  ranenv_ppo.hip's header comment describes the plan they belong to; the text
-// is what stood there, so the kernels built from it keep their instructions.
+// ranenv_ppo_parts.hpp -- the one statement of every step the training kernels share (ranenv_ppo.hip: the PPO updates of the bound nets
+// and of the head policies; ranenv_sac.hip: the SAC update): the LDS size of a net's rows, the backward pass of one 32-row tile on the
+// f32 matrix cores and its dZ' block walk, the workgroup sum in slot order, Adam's constants and float32 element step, and the steps
+// of a PPO minibatch -- zeroing, the advantages' mean and std, the tile's row list, the clipped surrogate, the critic row, the joint
+// norm and clip scale, the statistics, the gradient copy.  A rule that lives here (the 1e-6 of the clip, the 1e-8 of the std, the tie
+// rule of torch.minimum, Adam's operation order) has no second text.  ranenv_ppo.hip's header comment describes the plan they belong to.
 #pragma once
 #include "ranenv_net.hpp"
 
@@ -42,6 +44,41 @@ __device__ __forceinline__ void ppo_copy_rows(float *dst, const float *src, int 
     for (int i = tid; i < NET_ROWS * kq; i += 256) {
         const int r = i / kq, at = r * ld + ((i - r * kq) << 2);
         *(float4 *)(dst + at) = *(const float4 *)(src + at);
+    }
+}
+
+// dZ'[r][k] = (sum_n dZ[r][n] W[n][k]) act'(A[r][k]) for the 16-column blocks [b0, b1) of layer l's input rows `a`, written in place
+// over them (the activation's derivative is taken from its value; layer 0's "activation" is the input: factor 1).  `W` = layer l's
+// weights, `dz` its output rows' gradient.  No barrier: the caller holds one in front (whoever read A is done) and one behind.
+// The empty asm makes the four W values of a step live at one point, so their loads are in flight together and the step waits once.
+// Left to itself the register allocator gave the four one register in some kernels (a wait per load) and two in others, by what else
+// the kernel held: the walk's time then moved by a few per cent, up or down, with any edit of a caller.
+__device__ __forceinline__ void ppo_dz_blocks(const PolicyNet &net, int l, const float *W, const float *dz, float *a, int b0, int b1, int tid)
+{
+    const int lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
+    const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N);
+    for (int blk = b0 + wave; blk < b1; blk += 4) {
+        const int k0 = blk << 4;
+        f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+        for (int n0 = 0; n0 < N; n0 += 16) {      // MFMA j: n = n0 + 4 q + j, the same permutation on both operands
+            const float4 d0 = *(const float4 *)(dz + c * ldo + n0 + 4 * q), d1 = *(const float4 *)(dz + (16 + c) * ldo + n0 + 4 * q);
+            const float *wp = W + (size_t)(n0 + 4 * q) * K + k0 + c;
+            const float wv[4] = {wp[0], wp[K], wp[2 * K], wp[3 * K]};
+            asm volatile("" ::"v"(wv[0]), "v"(wv[1]), "v"(wv[2]), "v"(wv[3]));
+            const float dv[2][4] = {{d0.x, d0.y, d0.z, d0.w}, {d1.x, d1.y, d1.z, d1.w}};
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) acc[mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[mi][j], wv[j], acc[mi], 0, 0, 0);
+        }
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                float *p = a + (mi * 16 + 4 * q + i) * ldi + k0 + c;
+                const float av = *p;
+                *p = acc[mi][i] * (l == 0 ? 1.0f : (net.act == RANENV_ACT_RELU ? (av > 0.0f ? 1.0f : 0.0f) : 1.0f - av * av));
+            }
     }
 }
 
@@ -89,29 +126,7 @@ __device__ __forceinline__ void ppo_backward(const PolicyNet &net, const float *
         }
         if (l == 0) break;
         __syncthreads();                       // (dW has read A: dZ' may overwrite it)
-        const float *W = w + net.w_off[l];
-        for (int blk = wave; blk < kb; blk += 4) {
-            const int k0 = blk << 4;
-            f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
-            for (int n0 = 0; n0 < N; n0 += 16) {      // MFMA j: n = n0 + 4 q + j, the same permutation on both operands
-                const float4 d0 = *(const float4 *)(dz + c * ldo + n0 + 4 * q), d1 = *(const float4 *)(dz + (16 + c) * ldo + n0 + 4 * q);
-                const float *wp = W + (size_t)(n0 + 4 * q) * K + k0 + c;
-                const float wv[4] = {wp[0], wp[K], wp[2 * K], wp[3 * K]};
-                const float dv[2][4] = {{d0.x, d0.y, d0.z, d0.w}, {d1.x, d1.y, d1.z, d1.w}};
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-#pragma unroll
-                    for (int mi = 0; mi < 2; mi++) acc[mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[mi][j], wv[j], acc[mi], 0, 0, 0);
-            }
-#pragma unroll
-            for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    float *p = a + (mi * 16 + 4 * q + i) * ldi + k0 + c;
-                    const float av = *p;
-                    *p = acc[mi][i] * (net.act == RANENV_ACT_RELU ? (av > 0.0f ? 1.0f : 0.0f) : 1.0f - av * av);
-                }
-        }
+        ppo_dz_blocks(net, l, w + net.w_off[l], dz, a, 0, kb, tid);
         __syncthreads();
         dz = a;
     }
@@ -129,19 +144,6 @@ __device__ __forceinline__ double ppo_sum(double *red, double part, int tid)
     return tot;
 }
 
-__device__ __forceinline__ void ppo_adam(float *w, float *m, float *v, const float *g, long long n, float scale, float b1, float omb1, float b2, float omb2,
-                                         float step, float sbc2, float eps, int tid)
-{
-#pragma unroll 1
-    for (long long i = tid; i < n; i += 256) {
-        const float gi = g[i] * scale;
-        const float mi = b1 * m[i] + omb1 * gi;
-        const float vi = b2 * v[i] + (omb2 * gi) * gi;
-        m[i] = mi; v[i] = vi;
-        w[i] = w[i] - step * (mi / (sqrtf(vi) / sbc2 + eps));
-    }
-}
-
 // b^t (t >= 1) in float64 by repeated squaring
 __device__ __forceinline__ double ppo_powi(double b, int t)
 {
@@ -149,6 +151,125 @@ __device__ __forceinline__ double ppo_powi(double b, int t)
 #pragma unroll 1
     for (; t > 0; t >>= 1) { if (t & 1) r *= b; b *= b; }
     return r;
+}
+
+// Adam at step t (>= 1): the constants in float64, rounded once -- step = lr / (1 - b1^t), sbc2 = sqrt(1 - b2^t) -- and the float32
+// element step on an already scaled gradient g, torch's operation order: m, v, then w - step * (m / (sqrt(v) / sbc2 + eps))
+struct AdamStep { float b1, omb1, b2, omb2, eps, step, sbc2; };
+__device__ __forceinline__ AdamStep adam_step(double lr, double beta1, double beta2, double eps, int t)
+{
+    return AdamStep{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                    (float)(lr / (1.0 - ppo_powi(beta1, t))), (float)sqrt(1.0 - ppo_powi(beta2, t))};
+}
+__device__ __forceinline__ void adam_elem(float &w, float &m, float &v, float g, const AdamStep &a)
+{
+    const float mi = a.b1 * m + a.omb1 * g;
+    const float vi = a.b2 * v + (a.omb2 * g) * g;
+    m = mi; v = vi;
+    w = w - a.step * (mi / (sqrtf(vi) / a.sbc2 + a.eps));
+}
+__device__ __forceinline__ void ppo_adam(float *w, float *m, float *v, const float *g, long long n, float scale, const AdamStep &a, int tid)
+{
+#pragma unroll 1
+    for (long long i = tid; i < n; i += 256) adam_elem(w[i], m[i], v[i], g[i] * scale, a);
+}
+
+// ---- the steps of a PPO minibatch (ranenv_ppo_body.hpp and ranenv_ppo_update_kernel_head) ----------------------------------------------
+__device__ __forceinline__ void ppo_zero(float *g, long long floats, int tid)
+{
+#pragma unroll 1
+    for (long long i = tid; i < floats; i += 256) g[i] = 0.0f;
+}
+
+// The minibatch's advantage mean and std + 1e-8 (torch's unbiased std; one row: 0): two float64 passes over adv_at(k), k < nb -- the
+// caller's cell of list entry k, 0.0 for an entry outside the record
+template <class F>
+__device__ __forceinline__ void ppo_adv_norm(double *red, int nb, int tid, F adv_at, double &a_mean, double &a_den)
+{
+    double s = 0.0;
+#pragma unroll 1
+    for (int k = tid; k < nb; k += 256) s += adv_at(k);
+    a_mean = ppo_sum(red, s, tid) / (double)nb;
+    s = 0.0;
+#pragma unroll 1
+    for (int k = tid; k < nb; k += 256) { const double d = adv_at(k) - a_mean; s += d * d; }
+    const double ss = ppo_sum(red, s, tid);
+    a_den = (nb > 1 ? sqrt(ss / (double)(nb - 1)) : 0.0) + 1e-8;
+}
+
+// The tile's record rows: rowidx[r] = entry c0 + t0 + r of `list`, or -1 beyond the minibatch's nb entries and outside the record
+__device__ __forceinline__ void ppo_list_rows(int *rowidx, const int32_t *list, int c0, int t0, int nb, long long n_record, int tid)
+{
+    if (tid >= NET_ROWS) return;
+    int i = -1;
+    if (t0 + tid < nb) { i = list[c0 + t0 + tid]; if (i < 0 || i >= n_record) i = -1; }
+    rowidx[tid] = i;
+}
+
+// The clipped surrogate of one live row: rs[0..4] = policy loss, entropy (the caller's `ent`), logp_old - logp, clipped?, live;
+// returns gl = dL/d(logp) of the row.  torch.minimum / clamp: the unclipped branch carries the gradient where it is the smaller one,
+// both where they tie
+__device__ __forceinline__ double ppo_surrogate(double lp, double lp_old, double adv, double ent, double clip, double wrow, double *rs)
+{
+    const double ratio = exp(lp - lp_old), c_lo = 1.0 - clip, c_hi = 1.0 + clip;
+    const bool inside = ratio >= c_lo && ratio <= c_hi;
+    const double s1 = ratio * adv, s2 = (ratio < c_lo ? c_lo : (ratio > c_hi ? c_hi : ratio)) * adv;
+    const double dsdr = inside || s1 < s2 ? adv : 0.0;
+    rs[0] = -(s1 < s2 ? s1 : s2); rs[1] = ent; rs[2] = lp_old - lp; rs[3] = inside ? 0.0 : 1.0; rs[4] = 1.0;
+    return -(dsdr * ratio) * wrow;
+}
+
+// The critic's row i (< 0: dead): o[0] = V becomes dL/dV = 2 vf_coeff (V - vtarg) / rows; returns the squared error.  vtarg_at():
+// the row's target, read for a live row alone
+template <class F>
+__device__ __forceinline__ double ppo_critic_row(float *o, int i, F vtarg_at, double vf_coeff, double wrow)
+{
+    if (i < 0) { o[0] = 0.0f; return 0.0; }
+    const double d = (double)o[0] - (double)vtarg_at();
+    o[0] = (float)(((2.0 * d) * vf_coeff) * wrow);
+    return d * d;
+}
+
+// Thread 0's statistics of an epoch; a tile's rows 0..31 added in order from their `stride` doubles each (ppo_surrogate's five, then
+// the value loss where `critic`), and the epoch's eight outputs over its n rows
+struct PpoEpoch { double pl = 0.0, vl = 0.0, ent = 0.0, kl = 0.0, cf = 0.0, gn = 0.0, rows = 0.0; int n_mb = 0; };
+__device__ __forceinline__ void ppo_tile_stats(PpoEpoch &st, const double *rowstat, int stride, bool critic)
+{
+#pragma unroll 1
+    for (int r = 0; r < NET_ROWS; r++) {
+        const double *rs = rowstat + r * stride;
+        st.pl += rs[0]; st.ent += rs[1]; st.kl += rs[2]; st.cf += rs[3]; st.rows += rs[4];
+        if (critic) st.vl += rs[5];
+    }
+}
+__device__ __forceinline__ void ppo_epoch_stats(double *out, const PpoEpoch &st, int n)
+{
+    const double inv = 1.0 / (double)n;
+    out[0] = st.pl * inv; out[1] = st.vl * inv; out[2] = st.ent * inv; out[3] = st.kl * inv; out[4] = st.cf * inv; out[5] = st.gn * inv;
+    out[6] = st.rows; out[7] = (double)st.n_mb;
+}
+
+// The thread's share of a gradient tensor's sum of squares, added to `s` element by element: the nets of a minibatch continue ONE
+// accumulator, so the joint norm's summation order does not depend on where a tensor ends
+__device__ __forceinline__ double ppo_sq_sum(const float *g, long long floats, int tid, double s)
+{
+#pragma unroll 1
+    for (long long i = tid; i < floats; i += 256) { const double x = (double)g[i]; s += x * x; }
+    return s;
+}
+
+// torch's clip_grad_norm_ factor for the joint norm (grad_clip <= 0: no clip)
+__device__ __forceinline__ double ppo_clip_scale(double grad_clip, double norm)
+{
+    if (!(grad_clip > 0.0)) return 1.0;
+    const double sc = grad_clip / (norm + 1e-6);
+    return sc < 1.0 ? sc : 1.0;
+}
+
+__device__ __forceinline__ void ppo_grad_out(float *out, const float *g, long long floats, int tid)
+{
+#pragma unroll 1
+    for (long long i = tid; i < floats; i += 256) out[i] = g[i];
 }
 
 }  // namespace

@@ -56,40 +56,15 @@ __device__ __forceinline__ SacDraw sac_draw(const float *o, int ld, int S, int r
 __device__ __forceinline__ double sac_logp_term(const SacDraw &d) { return ((((-0.5 * d.z) * d.z - d.ls) - HALF_LN_2PI)) - log((1.0 - d.a * d.a) + 1e-6); }
 
 // dL/d(input) of one tile through `net`: `out` = the output layer's rows, holding dL/d(output); the layers' inputs lie in front of it.
-// ppo_backward's dZ' step alone -- no dW, no db -- carried through EVERY layer, layer 0 included (whose "activation" is the input: factor
-// 1), in place over the layers' input rows; of layer 0 only the 16-column blocks that hold columns [c0, c1).  Rows are independent.
+// ppo_backward's dZ' step alone (ppo_dz_blocks) -- no dW, no db -- carried through EVERY layer, layer 0 included, in place over the
+// layers' input rows; of layer 0 only the 16-column blocks that hold columns [c0, c1).  Rows are independent.
 // Ends behind a barrier: the input rows' columns [c0, c1) hold the gradient.
 __device__ __forceinline__ void sac_input_grad(const PolicyNet &net, const float *w, float *out, int tid, int c0, int c1)
 {
-    const int lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
     float *dz = out;
     for (int l = net.n_layers - 1; l >= 0; l--) {
-        const int K = net.kp[l], N = net.np[l], ldi = net_ld(K), ldo = net_ld(N), kb = K >> 4;
-        float *a = dz - NET_ROWS * ldi;
-        const float *W = w + net.w_off[l];
-        const int b0 = l == 0 ? c0 >> 4 : 0, b1 = l == 0 ? (c1 + 15) >> 4 : kb;
-        for (int blk = b0 + wave; blk < b1; blk += 4) {
-            const int k0 = blk << 4;
-            f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
-            for (int n0 = 0; n0 < N; n0 += 16) {      // MFMA j: n = n0 + 4 q + j, the same permutation on both operands
-                const float4 d0 = *(const float4 *)(dz + c * ldo + n0 + 4 * q), d1 = *(const float4 *)(dz + (16 + c) * ldo + n0 + 4 * q);
-                const float *wp = W + (size_t)(n0 + 4 * q) * K + k0 + c;
-                const float wv[4] = {wp[0], wp[K], wp[2 * K], wp[3 * K]};
-                const float dv[2][4] = {{d0.x, d0.y, d0.z, d0.w}, {d1.x, d1.y, d1.z, d1.w}};
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-#pragma unroll
-                    for (int mi = 0; mi < 2; mi++) acc[mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(dv[mi][j], wv[j], acc[mi], 0, 0, 0);
-            }
-#pragma unroll
-            for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    float *p = a + (mi * 16 + 4 * q + i) * ldi + k0 + c;
-                    const float av = *p;
-                    *p = acc[mi][i] * (l == 0 ? 1.0f : (net.act == RANENV_ACT_RELU ? (av > 0.0f ? 1.0f : 0.0f) : 1.0f - av * av));
-                }
-        }
+        float *a = dz - NET_ROWS * net_ld(net.kp[l]);
+        ppo_dz_blocks(net, l, w + net.w_off[l], dz, a, l == 0 ? c0 >> 4 : 0, l == 0 ? (c1 + 15) >> 4 : net.kp[l] >> 4, tid);
         __syncthreads();
         dz = a;
     }
@@ -324,7 +299,6 @@ __global__ void __launch_bounds__(256) ranenv_sac_apply_kernel(SacApplyArgs A)
 {
     const SacApplySeg &s = A.seg[blockIdx.y];
     const long long e = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
-    const float b1 = (float)0.9, omb1 = (float)(1.0 - 0.9), b2 = (float)0.999, omb2 = (float)(1.0 - 0.999), eps = (float)1e-8;
     if (e < s.floats) {
         if (s.op & SAC_OP_ADAM) {
             float *p = A.slab + s.slab_off + e;
@@ -337,11 +311,7 @@ __global__ void __launch_bounds__(256) ranenv_sac_apply_kernel(SacApplyArgs A)
                 *p = 0.0f;
             }
             if (s.grad) s.grad[e] = g;
-            const float step = (float)(A.lr / (1.0 - ppo_powi(0.9, s.t))), sbc2 = (float)sqrt(1.0 - ppo_powi(0.999, s.t));
-            const float mi = b1 * s.m[e] + omb1 * g;
-            const float vi = b2 * s.v[e] + (omb2 * g) * g;
-            s.m[e] = mi; s.v[e] = vi;
-            s.w[e] = s.w[e] - step * (mi / (sqrtf(vi) / sbc2 + eps));
+            adam_elem(s.w[e], s.m[e], s.v[e], g, adam_step(A.lr, 0.9, 0.999, 1e-8, s.t));
         }
         if (s.op & SAC_OP_POLYAK) {
             const float omt = (float)(1.0 - A.tau), tf = (float)A.tau;
@@ -365,11 +335,7 @@ __global__ void __launch_bounds__(256) ranenv_sac_apply_kernel(SacApplyArgs A)
     float g = 0.0f;
     if (A.auto_coef) {
         g = (float)(-mean_e);
-        const float step = (float)(A.lr / (1.0 - ppo_powi(0.9, A.t_ent))), sbc2 = (float)sqrt(1.0 - ppo_powi(0.999, A.t_ent));
-        const float mi = b1 * A.ent[1] + omb1 * g;
-        const float vi = b2 * A.ent[2] + (omb2 * g) * g;
-        A.ent[1] = mi; A.ent[2] = vi;
-        A.ent[0] = lec - step * (mi / (sqrtf(vi) / sbc2 + eps));
+        adam_elem(A.ent[0], A.ent[1], A.ent[2], g, adam_step(A.lr, 0.9, 0.999, 1e-8, A.t_ent));
     }
     if (A.grad_ent) A.grad_ent[0] = g;
 #pragma unroll
@@ -388,16 +354,7 @@ size_t sac_lds_bytes(const PolicyNet &actor, const PolicyNet &critic)
 
 hipError_t launch_sac_pass(hipStream_t s, int which, int grid, size_t lds, const SacPassArgs &a)
 {
-    if (which == 0) {
-        static const hipError_t attr = hipFuncSetAttribute((const void *)ranenv_sac_critic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(ranenv_sac_critic_kernel, dim3((unsigned)grid), dim3(256), lds, s, a);
-        return hipGetLastError();
-    }
-    static const hipError_t attr = hipFuncSetAttribute((const void *)ranenv_sac_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPO_LDS_MAX);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(ranenv_sac_actor_kernel, dim3((unsigned)grid), dim3(256), lds, s, a);
-    return hipGetLastError();
+    return which == 0 ? launch_lds<ranenv_sac_critic_kernel>(dim3((unsigned)grid), dim3(256), lds, s, a) : launch_lds<ranenv_sac_actor_kernel>(dim3((unsigned)grid), dim3(256), lds, s, a);
 }
 
 hipError_t launch_sac_apply(hipStream_t s, const SacApplyArgs &a)
