@@ -836,6 +836,37 @@ int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv
  *   ranenv_ppo_lds_bytes (either output may be NULL, not both). */
 int ranenv_ppo_bind_wide(ranenv_handle h, int32_t mixed, void *stream);
 int ranenv_ppo_wide_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int64_t *lds_bytes, int64_t *scratch_floats);
+/* Non-shared intra policies (ranenv_set_intra_policy_networks / _intra_value_networks: one intra actor, and optionally one intra critic,
+ * PER SLICE -- the reference's `shared_policies=False`, one RLlib policy per slice) train under a third, opt-in binding, "per slice".
+ * ranenv_ppo_bind, _bind_mixed, _bind_wide, ranenv_ppo_update and ranenv_get_net_weights keep refusing such nets.
+ * ranenv_ppo_bind_slices: the handle must have ONE inter actor and ONE inter critic, S intra actors per slice, and S intra critics per
+ *   slice or no intra critic at all.  RANENV_E_STATE, the text naming what is wrong: a population is bound; the intra actors or the intra
+ *   critics are one shared net ("a net the slices share has no one owner"); a net is bf16; a pair does not fit THE LDS PLAN (wide 0) or
+ *   THE WIDE PLAN (wide 1; another value: RANENV_E_INVALID).  Allocates and zeroes the moments and gradient scratch of the four slots --
+ *   slice s's at s * the slot's slice stride, the packed layout at the offsets of its weights --, 1 + S step counters and, wide 1, the
+ *   scratch for 1 + S workgroups.  A handle still has ONE binding of the IBSched nets: the later bind call replaces the earlier one.
+ * ranenv_ppo_update_slices: ONE launch of 1 + S workgroups.  Workgroup 0 trains the inter pair on dev_order_inter [max epochs][n_inter];
+ *   workgroup 1 + s trains slice s's pair on entries [host_first_slice[s], host_first_slice[s + 1]) of every epoch's row of
+ *   dev_order_intra [max epochs][host_first_slice[S]] -- record rows (t * B + b) * S + s of ITS OWN slice (the call does not read the
+ *   lists: a row of another slice in a share trains that share's nets on it), the cells logp / adv / vtarg [t][b][1 + s].  The update
+ *   is in place in the buffers the sliced acting kernels read: the next ranenv_collect acts on the trained nets.  host_hparams is ONE
+ *   ranenv_ppo_hparams for all 1 + S policies, as RLlib's one config.  dev_order_intra NULL: the inter pair alone (one workgroup).
+ *   dev_stats [1 + S][epochs][RANENV_PPO_STATS] and dev_grad (optional) [1 + S][ranenv_ppo_layout's grad_floats]: row 0 the inter pair,
+ *   row 1 + s slice s.  A slice whose share is empty is not touched: weights, moments and counter keep their bytes, its dev_stats rows
+ *   are not written.  Validation, arithmetic, summation order and ranenv_ppo_probe_logp are ranenv_ppo_update's: slice s's bytes equal
+ *   those of ranenv_ppo_update on one shared intra pair of slice s's nets given the same rows, the inter pair's those of the plain binding.
+ *   While this binding stands ranenv_ppo_layout and ranenv_ppo_member_layout (member: the slice for kind 1, 0 for kind 0) answer for it.
+ * ranenv_get_slice_net_weights: ranenv_get_net_weights for roles 1 and 3 bound per slice: slice `slice`'s net.
+ * ranenv_ppo_slice_state: ranenv_ppo_state under this binding; roles 0 and 2 ignore `slice`; dev_t is the workgroup's counter.
+ * Re-binding under this binding: a re-bind of the per-slice actors or critics zeroes the moments of both nets of EVERY slice and the S
+ *   counters; a re-bind of an inter net restarts the inter pair.  A re-bind that outgrows the state, or after which the nets are no
+ *   longer of the per-slice form, ends the binding: the next ranenv_ppo_update_slices is RANENV_E_STATE ("bind again"). */
+int ranenv_ppo_bind_slices(ranenv_handle h, int32_t wide, void *stream);
+int ranenv_ppo_update_slices(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, const ranenv_ppo_hparams *host_hparams,
+                             const int32_t *dev_order_inter, int32_t n_inter, const int32_t *dev_order_intra, const int32_t *host_first_slice,
+                             double *dev_stats, float *dev_grad, void *stream);
+int ranenv_get_slice_net_weights(ranenv_handle h, int32_t role, int32_t slice, ranenv_mlp *out, void *stream);
+int ranenv_ppo_slice_state(ranenv_handle h, int32_t role, int32_t slice, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats);
 
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,
  * results/gen_results.py:874-1022, kept as running sums so that a rollout needs no per-TTI read-back).  Per env 8

@@ -508,12 +508,15 @@ HALF_LN_2PI = 0.9189385332046727
 LN_1E9 = 20.72326583694641
 
 
-def ppo_row_order(rec, first_env, epochs: int, seed: int = 0, intra: bool = True) -> Dict[str, object]:
+def ppo_row_order(rec, first_env, epochs: int, seed: int = 0, intra: bool = True, per_slice: bool = False) -> Dict[str, object]:
     """The row lists of ``ppo_update`` for a ``collect()`` record: per epoch and member an independent shuffle of the member's rows,
     built where the record lives in one batched ``argsort`` per kind.  ``first_env`` [G + 1]: the population's grouping (``[0, B]``: one
     member).  Inter rows are ``t * B + b`` for every TTI t and env b of the member; intra rows ``(t * B + b) * S + s`` for the slices
     that were live at that TTI (``mask_inter != 0``) only.  Returns ``order_inter`` int32 [epochs, N_inter] and ``first_inter`` int32
-    [G + 1] (member m's rows of an epoch: entries ``first[m] .. first[m + 1] - 1``), and the same for "intra" (None with ``intra=False``)."""
+    [G + 1] (member m's rows of an epoch: entries ``first[m] .. first[m + 1] - 1``), and the same for "intra" (None with ``intra=False``).
+    ``per_slice=True`` (``ppo_update_per_slice``, non-shared intra policies; one member only): the live intra rows are grouped by
+    slice and shuffled within it, and ``first_intra`` is [S + 1] -- slice s's share of an epoch is entries ``first_intra[s] ..
+    first_intra[s + 1] - 1``, every one a row of slice s.  ``order_inter`` is the same tensor either way for one seed."""
     mask = rec["mask_inter"]
     T, B, S = mask.shape
     dev = mask.device
@@ -525,7 +528,10 @@ def ppo_row_order(rec, first_env, epochs: int, seed: int = 0, intra: bool = True
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
 
-    def shuffled(rows, member):               # rows ascending; member [n] of each
+    if per_slice and G != 1:
+        raise ValueError("per_slice=True takes one member: there is no population of non-shared agents")
+
+    def shuffled(rows, member, G=G):          # rows ascending; member [n] of each
         counts = torch.bincount(member, minlength=G).cpu().numpy()
         by_member = torch.argsort(member, stable=True)
         rows, member = rows[by_member], member[by_member]
@@ -539,7 +545,7 @@ def ppo_row_order(rec, first_env, epochs: int, seed: int = 0, intra: bool = True
     out["order_inter"], out["first_inter"] = shuffled(rows, member_of_env[rows % B])
     if intra:
         rows = (mask != 0).reshape(-1).nonzero().squeeze(1)
-        out["order_intra"], out["first_intra"] = shuffled(rows, member_of_env[(rows // S) % B])
+        out["order_intra"], out["first_intra"] = shuffled(rows, rows % S, S) if per_slice else shuffled(rows, member_of_env[(rows // S) % B])
     return out
 
 
@@ -798,6 +804,27 @@ def rllib_per_slice_layers(weights_by_policy, S: int, policy_prefix: str = "intr
         actors.append(rllib_fcnet_layers(weights_by_policy[name]))
         critics.append(rllib_fcnet_value_layers(weights_by_policy[name]))
     return actors, critics
+
+
+def rllib_per_slice_weights(actors, critics, policy_prefix: str = "intra_slice_sched_", prefix: str = "internal_model."):
+    """The inverse of ``rllib_per_slice_layers``: ``{"{policy_prefix}{s}": state_dict}`` from S actor layer stacks and S critic
+    layer stacks in slice order -- e.g. ``env.net_weights("intra", slice=s)`` / ``("v_intra", slice=s)`` after
+    ``ppo_update_per_slice`` -- with a separate value branch (``vf_share_layers`` off), so that
+    ``rllib_per_slice_layers(rllib_per_slice_weights(a, c), S)`` returns the same tensors.  The key names rest on RLlib's source as
+    ``rllib_fcnet_layers`` assumes it: parity with RLlib itself is unpinned, no real checkpoint has been written or read."""
+    if len(actors) != len(critics):
+        raise ValueError(f"{len(actors)} actors and {len(critics)} critics: one pair per slice")
+    out = {}
+    for s, (actor, critic) in enumerate(zip(actors, critics)):
+        if len(actor) < 2 or len(critic) < 2:
+            raise ValueError("a FullyConnectedNetwork has at least one hidden layer in front of its logits / value head")
+        sd = {}
+        for body, head, layers in (("_hidden_layers", "_logits", actor), ("_value_branch_separate", "_value_branch", critic)):
+            for i, (w, b) in enumerate(layers[:-1]):
+                sd[f"{prefix}{body}.{i}._model.0.weight"], sd[f"{prefix}{body}.{i}._model.0.bias"] = torch.as_tensor(w).detach().clone(), torch.as_tensor(b).detach().clone()
+            sd[f"{prefix}{head}._model.0.weight"], sd[f"{prefix}{head}._model.0.bias"] = torch.as_tensor(layers[-1][0]).detach().clone(), torch.as_tensor(layers[-1][1]).detach().clone()
+        out[f"{policy_prefix}{s}"] = sd
+    return out
 
 
 def rllib_fcnet_value_layers(state_dict, prefix: str = "internal_model."):

@@ -878,7 +878,7 @@ class BatchedRanEnv:
     # ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
     PPO_STEPS_CAP = 1 << 13
 
-    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False) -> None:
+    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
         one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header).
         ``mixed=True`` (ranenv_ppo_bind_mixed): the population was bound with ``mixed=True`` -- members of differing shape -- and
@@ -890,13 +890,21 @@ class BatchedRanEnv:
         reference's ``verybig`` [512, 512, 512] -- two row buffers in LDS and the layers' rows parked in a scratch allocated here
         (``ppo_lds_bytes(..., wide=True)``, ``ppo_wide_scratch_floats``).  Nets that fit both plans train to the same bytes under
         either.  A handle has one binding of the IBSched nets: the later ``ppo_bind`` replaces the earlier one and restarts the
-        optimiser.  The head pair trains under the plain plan alone: ``wide`` and ``head`` exclude each other."""
+        optimiser.  The head pair trains under the plain plan alone: ``wide`` and ``head`` exclude each other.
+        ``per_slice=True`` (ranenv_ppo_bind_slices), with or without ``wide``: the binding for non-shared intra policies -- one inter
+        actor and critic, ``intra`` a list of S nets in ``set_policy_network`` and a list of S critics, or none, in
+        ``set_value_network`` -- which ``ppo_update_per_slice`` trains, one workgroup per policy.  Every other binding refuses such
+        nets.  It excludes ``mixed`` and ``head``."""
+        if per_slice and (mixed or head):
+            raise ValueError("ppo_bind: per_slice excludes mixed and head (no population of non-shared agents; the head pair has no slices)")
         if mixed and head:
             raise ValueError("ppo_bind: mixed and head exclude each other")
         if wide and head:
             raise ValueError("ppo_bind: wide and head exclude each other (the head nets train under the plain plan)")
         with torch.cuda.device(self.device):
-            if wide:
+            if per_slice:
+                self._check(self._lib.ranenv_ppo_bind_slices(self._h, 1 if wide else 0, self._stream()), "ranenv_ppo_bind_slices")
+            elif wide:
                 self._check(self._lib.ranenv_ppo_bind_wide(self._h, 1 if mixed else 0, self._stream()), "ranenv_ppo_bind_wide")
             elif head:
                 self._check(self._lib.ranenv_ppo_bind_head(self._h, self._stream()), "ranenv_ppo_bind_head")
@@ -908,7 +916,8 @@ class BatchedRanEnv:
     def ppo_member_layout(self, m: int, kind: str = "inter") -> Dict[str, int]:
         """What unpacks member ``m``'s block of ``ppo_update(grad=True)["grad"][m, kind]`` (ranenv_ppo_member_layout): the packed
         floats of its "actor" and, behind them, its "critic" (0: none bound) of ``kind`` ("inter" / "intra"), and "lds_bytes", what
-        the update of that pair needs."""
+        the update of that pair needs.  Under ``ppo_bind(per_slice=True)`` ``m`` is the slice (0 for "inter"): what unpacks row
+        ``1 + m`` (row 0) of ``ppo_update_per_slice(grad=True)["grad"]``."""
         if kind not in ("inter", "intra"):
             raise ValueError('kind is "inter" or "intra"')
         a, c, lds = C.c_int64(), C.c_int64(), C.c_int64()
@@ -1006,24 +1015,101 @@ class BatchedRanEnv:
             out["logp"] = lbuf
         return out
 
+    def ppo_update_per_slice(self, rec, epochs=10, minibatch=64, lr=3e-4, clip=0.2, vf_coeff=0.5, ent_coeff=0.01, grad_clip=0.5, adv_norm="minibatch",
+                             betas=(0.9, 0.999), eps=1e-8, seed=0, order=None, grad: bool = False, probe_logp: bool = False, force: bool = False):
+        """Train the non-shared IBSched agent on the ``collect()`` record ``rec`` in one launch of 1 + S workgroups
+        (ranenv_ppo_update_slices, under ``ppo_bind(per_slice=True)``): the inter pair, and slice s's actor / critic pair on the live
+        rows of slice s alone, each with its own Adam state, written in place -- the next ``collect()`` acts on the trained nets.  The
+        hyper-parameters are scalars, one set for all 1 + S policies as RLlib's one config; their meaning is ``ppo_update``'s.
+        ``order``: as ``adapters.ppo_row_order(..., per_slice=True)`` returns it (default: drawn from ``seed``) -- "first_intra" is
+        [S + 1], slice s's share of every epoch's row of "order_intra"; without "order_intra" only the inter pair trains.  Returns
+        {name: float64 [1 + S, epochs]} for ``_lib.PPO_STATS``: row 0 the inter pair, row 1 + s slice s (a slice without rows: zeros);
+        ``grad=True`` adds "grad" [1 + S, floats] and ``probe_logp=True`` "logp" [T, B, S + 1], as ``ppo_update`` does.
+        ``PPO_ROW_EPOCHS_CAP`` and ``PPO_STEPS_CAP`` hold per policy unless ``force``."""
+        if adv_norm not in ("minibatch", "none", None):
+            raise ValueError('adv_norm is "minibatch" or None')
+        for name, x in (("epochs", epochs), ("minibatch", minibatch), ("lr", lr), ("clip", clip), ("vf_coeff", vf_coeff), ("ent_coeff", ent_coeff),
+                        ("grad_clip", 0.0 if grad_clip is None else grad_clip), ("eps", eps)):
+            if np.ndim(x) != 0:
+                raise ValueError(f"{name}: ppo_update_per_slice takes one value for all policies")
+        hp = _lib.PpoHparams()
+        hp.lr, hp.clip, hp.vf_coeff, hp.ent_coeff, hp.grad_clip, hp.eps = float(lr), float(clip), float(vf_coeff), float(ent_coeff), float(grad_clip or 0.0), float(eps)
+        hp.beta1, hp.beta2, hp.adv_norm, hp.minibatch, hp.epochs = float(betas[0]), float(betas[1]), 1 if adv_norm == "minibatch" else 0, int(minibatch), int(epochs)
+        epochs, S = int(epochs), self.S
+        T = int(rec["logp"].shape[0])
+        if order is None:
+            from .adapters import ppo_row_order
+            order = ppo_row_order(rec, [0, self.B], max(epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec, per_slice=True)
+        kinds = [k for k in ("inter", "intra") if order.get("order_" + k) is not None]
+        if "inter" not in kinds:
+            raise ValueError("order needs order_inter / first_inter")
+        firsts = {}
+        for k in kinds:
+            o, f = order["order_" + k], np.ascontiguousarray(order["first_" + k], dtype=np.int32)
+            n = 2 if k == "inter" else S + 1
+            if f.size != n or f[0] != 0 or o.dtype != torch.int32 or o.dim() != 2 or o.shape[0] < epochs or o.shape[1] != int(f[-1]) or not o.is_contiguous():
+                raise ValueError(f"order_{k}: int32 [>= {epochs} epochs, first_{k}[-1]] with first_{k} of {n} entries from 0"
+                                 + (" (adapters.ppo_row_order(..., per_slice=True))" if k == "intra" else ""))
+            rows = int(np.diff(f).max())
+            if not force and rows * epochs > self.PPO_ROW_EPOCHS_CAP:
+                raise RanEnvError(f"ppo_update_per_slice: a policy has more than {self.PPO_ROW_EPOCHS_CAP} rows x epochs ({k}); one compute unit works "
+                                  "through a policy's rows -- train such a batch in torch, or pass force=True")
+            steps = -(-rows // max(int(minibatch), 1)) * epochs
+            if not force and steps > self.PPO_STEPS_CAP:
+                raise RanEnvError(f"ppo_update_per_slice: a policy has more than {self.PPO_STEPS_CAP} optimiser steps ({k}: {steps}); every step "
+                                  "passes over all parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
+            firsts[k] = f
+        traj, keep = _lib.Trajectory(), []
+        for f in _lib.TRAJECTORY_FIELDS:
+            if f in rec:
+                dt, extra, shape = self.TRAJECTORY_SHAPES[f]
+                keep.append(self._dev(rec[f], dt, (T + extra,) + shape(self.B, self.S, self.Us, self.W), f))
+                setattr(traj, f, keep[-1].data_ptr())
+        stats = torch.zeros((1 + S, max(epochs, 1), len(_lib.PPO_STATS)), dtype=torch.float64, device=self.device)
+        gbuf = None
+        if grad:
+            gf = C.c_int64()
+            self._check(self._lib.ranenv_ppo_layout(self._h, C.byref(gf), None), "ranenv_ppo_layout")
+            gbuf = torch.zeros((1 + S, gf.value), dtype=torch.float32, device=self.device)
+        lbuf = torch.zeros((T, self.B, S + 1), dtype=torch.float32, device=self.device) if probe_logp else None
+        none = torch.zeros(1, dtype=torch.int32, device=self.device)      # (a list without rows still is a list: not NULL)
+        lists = {k: order["order_" + k] if order["order_" + k].numel() else none for k in kinds}
+        with torch.cuda.device(self.device):
+            if probe_logp:          # (armed for the one update below, which disarms it whether it is served or refused)
+                self._check(self._lib.ranenv_ppo_probe_logp(self._h, _ptr(lbuf)), "ranenv_ppo_probe_logp")
+            self._check(self._lib.ranenv_ppo_update_slices(
+                self._h, T, C.byref(traj), C.byref(hp), _ptr(lists["inter"]), int(firsts["inter"][1]),
+                _ptr(lists["intra"]) if "intra" in kinds else None,
+                firsts["intra"].ctypes.data_as(C.POINTER(C.c_int32)) if "intra" in kinds else None,
+                _ptr(stats), _ptr(gbuf), self._stream()), "ranenv_ppo_update_slices")
+        host = stats.cpu().numpy()             # (synchronises: the launch is over, `order` and `rec` may go)
+        out = {name: host[..., i] for i, name in enumerate(_lib.PPO_STATS)}
+        if grad:
+            out["grad"] = gbuf
+        if probe_logp:
+            out["logp"] = lbuf
+        return out
+
     _NET_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}
 
-    def net_weights(self, role: str, m: int = 0):
+    def net_weights(self, role: str, m: int = 0, slice: Optional[int] = None):
         """The bound float32 net of ``role`` ("inter", "intra", "v_inter", "v_intra"), member ``m`` of a population, as it is on the
         device NOW -- after ``ppo_update``: the trained net -- as a list of ``(W, b)`` tensors in torch ``Linear`` layout
-        (ranenv_get_net_weights); with ``net_activation(role, m)`` what ``set_policy_network`` takes."""
-        layers, _ = self._net_weights(role, m)
+        (ranenv_get_net_weights); with ``net_activation(role, m)`` what ``set_policy_network`` takes.  ``slice=s``: slice s's net of
+        "intra" / "v_intra" bound per slice (ranenv_get_slice_net_weights), which ``m`` cannot name."""
+        layers, _ = self._net_weights(role, m, slice=slice)
         return layers
 
-    def net_activation(self, role: str, m: int = 0) -> str:
-        return self._net_weights(role, m, copy=False)[1]
+    def net_activation(self, role: str, m: int = 0, slice: Optional[int] = None) -> str:
+        return self._net_weights(role, m, copy=False, slice=slice)[1]
 
-    def _net_weights(self, role: str, m: int, copy: bool = True):
+    def _net_weights(self, role: str, m: int, copy: bool = True, slice: Optional[int] = None):
         if role not in self._NET_ROLES:
             raise ValueError(f"role must be one of {sorted(self._NET_ROLES)}")
         out = _lib.Mlp()
+        call, m = ("ranenv_get_net_weights", m) if slice is None else ("ranenv_get_slice_net_weights", slice)
         with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_get_net_weights(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), "ranenv_get_net_weights")
+            self._check(getattr(self._lib, call)(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), call)
             act = {v: k for k, v in NET_ACTIVATIONS.items()}[out.activation]
             if not copy:
                 return None, act
@@ -1032,14 +1118,16 @@ class BatchedRanEnv:
                        torch.empty((dims[i + 1],), dtype=torch.float32, device=self.device)) for i in range(len(dims) - 1)]
             for i, (w, b) in enumerate(layers):
                 out.weight[i], out.bias[i] = w.data_ptr(), b.data_ptr()
-            self._check(self._lib.ranenv_get_net_weights(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), "ranenv_get_net_weights")
+            self._check(getattr(self._lib, call)(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), call)
         return layers, act
 
-    def ppo_state(self, role: str, m: int = 0) -> Dict[str, torch.Tensor]:
+    def ppo_state(self, role: str, m: int = 0, slice: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Zero-copy views of the optimiser state of ``role``'s net of member ``m`` (ranenv_ppo_state): Adam's "m" and "v" in the packed
-        layout (float32 [floats]) and "t", the (member, kind) step counter (int32 [1])."""
+        layout (float32 [floats]) and "t", the (member, kind) step counter (int32 [1]).  ``slice=s``: under ``ppo_bind(per_slice=True)``
+        (ranenv_ppo_slice_state) slice s's net of "intra" / "v_intra" with that slice's counter; "inter" / "v_inter" ignore ``s``."""
         pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        self._check(self._lib.ranenv_ppo_state(self._h, self._NET_ROLES[role], int(m), C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), "ranenv_ppo_state")
+        call, m = ("ranenv_ppo_state", m) if slice is None else ("ranenv_ppo_slice_state", slice)
+        self._check(getattr(self._lib, call)(self._h, self._NET_ROLES[role], int(m), C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), call)
         return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
                 "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
                 "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}

@@ -6,8 +6,8 @@ Eight objects, compiled in parallel, then linked:
                         bf16 weight packing)
   ranenv_policy.hip     the policy networks (RANENV_POLICY_NETWORK: MLP forwards on the f32 matrix cores, or per net on the bf16 ones)
   ranenv_ppo.hip        the PPO update of the bound nets (ranenv_ppo_update: forward, backward, clip and Adam, one workgroup per member;
-                        its four kernels -- uniform and mixed populations, each under the plain and the wide LDS plan -- expand one
-                        body, ranenv_ppo_body.hpp; a fifth trains the head policies, ranenv_ppo_update_head)
+                        its six kernels -- uniform populations, mixed populations and nets per slice, each under the plain and the
+                        wide LDS plan -- expand one body, ranenv_ppo_body.hpp; a seventh trains the head policies, ranenv_ppo_update_head)
   ranenv_sac.hip        the SAC update (ranenv_sac_update: per gradient step a critic pass, an actor pass and two elementwise applies,
                         the rows of a minibatch spread over workgroups)
                         Both are built from ranenv_ppo_parts.hpp, the one statement of every step they share: the backward pass and

@@ -160,6 +160,9 @@ struct ranenv {
     // ranenv_ppo_bind_wide: the binding follows the wide plan; the parked rows of the members' workgroups, [members][2][ppo_park_stride]
     // floats, allocated at that bind (an outgrown one stays allocated, like the weights'), never by an update
     bool ppo_wide = false; float *d_ppo_park = nullptr; long long ppo_park_stride = 0, ppo_park_cap = 0;
+    // ranenv_ppo_bind_slices: the binding trains one intra pair per slice; the counters d_ppo_t and a wide binding's parked rows are
+    // numbered by workgroup, [1 + S] (0 the inter pair, 1 + s slice s), not [members][2]
+    bool ppo_slices = false;
     // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
     // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
     bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
@@ -2229,6 +2232,29 @@ static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members,
     });
 }
 
+// The slots the per-slice update trains, by role number -- the one-net inter pair, the intra actors per slice, the intra critics per
+// slice or none -- or what ranenv_ppo_bind_slices refuses.  No device call.
+static int ppo_slice_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], bool wide)
+{
+    if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
+    for (int r = 0; r < 4; r++) {
+        slot[r] = h->serving(r);
+        if (slot[r] && slot[r]->form == FORM_MEMBER) return fail(h, RANENV_E_STATE, "the per-slice PPO update trains no population: the %s nets are bound per member", NET_ROLES[r].who);
+    }
+    if (!slot[0] || !slot[2]) return fail(h, RANENV_E_STATE, "the PPO update needs a bound inter actor and inter critic (ranenv_set_policy_network, ranenv_set_value_network)");
+    if (!slot[1]) return fail(h, RANENV_E_STATE, "the per-slice PPO update needs intra actors per slice (ranenv_set_intra_policy_networks)");
+    for (int r = 1; r < 4; r += 2)
+        if (slot[r] && slot[r]->form != FORM_SLICE)
+            return fail(h, RANENV_E_STATE, "the per-slice PPO update needs the %s nets per slice: a net the slices share has no one owner", NET_ROLES[r].who);
+    for (int r = 0; r < 4; r++)
+        if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
+    return ppo_each_shape(slot, false, wide, 1, [&](int, int k, long long, size_t lds, long long) {
+        if (lds <= (size_t)PPO_LDS_MAX) return (int)RANENV_OK;
+        if (wide) return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+        return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+    });
+}
+
 // A mixed binding's per-member packed floats [4][POP_MAX] (0: the role is not bound) as the slots stand, to the device on the caller's stream
 static int ppo_floats_upload(ranenv_handle h, hipStream_t s)
 {
@@ -2247,13 +2273,30 @@ static int ppo_floats_upload(ranenv_handle h, hipStream_t s)
 // again, on the caller's stream -- or, where the slot has no moments of its size, the PPO binding ends.
 static int ppo_head_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
 static int sac_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
+// ... under ranenv_ppo_bind_slices: the inter pair lives in the one-net slots, the intra pairs in the per-slice slots.  A re-bound net of
+// another form takes the nets out of the per-slice form, and a slot without moments of its size has outgrown the state: the binding
+// ends.  Else the slot's and its partner's moments restart -- of every slice: a per-slice bind replaces all S copies -- with the inter
+// counter or the S slice counters.
+static int ppo_slices_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
+{
+    const int kind = slot->role & 1;
+    if (slot->form != (kind ? FORM_SLICE : FORM_ONE) || !slot->opt || slot->cap > slot->opt_cap) { h->ppo_on = false; return RANENV_OK; }
+    ranenv::NetSlot *both[2] = {slot, &h->nets[slot->role ^ 2][slot->form]};
+    for (ranenv::NetSlot *x : both)
+        if (x->on && x->opt && x->cap <= x->opt_cap) HIP_TRY(h, hipMemsetAsync(x->opt, 0, sizeof(float) * 2 * (size_t)x->opt_cap, s));
+    HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + (kind ? 1 : 0), 0, sizeof(int32_t) * (size_t)(kind ? h->cfg.n_slices : 1), s));
+    return RANENV_OK;
+}
+
 static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s)
 {
     if (slot == &h->head || slot == &h->sac_q1 || slot == &h->sac_q2)
         if (const int rc = sac_rebound(h, slot, s); rc != RANENV_OK) return rc;
     if (slot == &h->head || slot == &h->head_value) return ppo_head_rebound(h, slot, s);
     if (!h->ppo_on) return RANENV_OK;
-    if (slot->role < 0 || slot->form == FORM_SLICE) return RANENV_OK;      // (a net the update never trains)
+    if (slot->role < 0) return RANENV_OK;      // (a net the update never trains)
+    if (h->ppo_slices) return ppo_slices_rebound(h, slot, s);
+    if (slot->form == FORM_SLICE) return RANENV_OK;      // (... nor does this binding train the nets per slice)
     const int kind = slot->role & 1;
     if (!slot->opt || slot->cap > slot->opt_cap) { h->ppo_on = false; return RANENV_OK; }
     // (actor and critic of a kind share the step counter: the partner net -- critic of an actor, actor of a critic -- restarts with it,
@@ -2275,22 +2318,23 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
     return h->ppo_mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide
-static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream)
+// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide / ranenv_ppo_bind_slices (slices: one member, 1 + S workgroups)
+static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream, bool slices = false)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
-    int members = 0;
-    if (const int rc = ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    int members = 1;
+    if (const int rc = slices ? ppo_slice_roles(h, slot, wide) : ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    if (wide) {         // the parked rows: the largest need over the members and the kinds, for members x 2 workgroups
-        const long long need = ppo_plan(slot, mixed, true, members).park * 2 * members;
+    const int wgs = slices ? 1 + h->cfg.n_slices : 2 * members;      // the workgroups of an update launch
+    if (wide) {         // the parked rows: the largest need over the members and the kinds, for every workgroup
+        const long long need = ppo_plan(slot, mixed, true, members).park * wgs;
         if (h->ppo_park_cap < need) {
             if (const int rc = dev_alloc(h, &h->d_ppo_park, (size_t)need); rc != RANENV_OK) return rc;
             h->ppo_park_cap = need;
         }
-        h->ppo_park_stride = h->ppo_park_cap / (2 * members);       // (a kept larger allocation serves larger re-bound shapes)
+        h->ppo_park_stride = h->ppo_park_cap / wgs;                 // (a kept larger allocation serves larger re-bound shapes)
         h->ppo_park_stride -= h->ppo_park_stride % 4;               // (every workgroup's share starts on a 16-byte boundary)
     }
     if (!h->d_ppo_t) {
@@ -2303,7 +2347,7 @@ static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream)
     for (int r = 0; r < 4; r++)
         if (slot[r])
             if (const int rc = opt_ensure(h, slot[r], s); rc != RANENV_OK) return rc;
-    h->ppo_on = true; h->ppo_mixed = mixed; h->ppo_wide = wide;
+    h->ppo_on = true; h->ppo_mixed = mixed; h->ppo_wide = wide; h->ppo_slices = slices;
     return mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
@@ -2319,6 +2363,7 @@ int ranenv_ppo_bind_wide(ranenv_handle h, int32_t mixed, void *stream)
 static int ppo_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
 {
     if (!h->ppo_on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
+    if (h->ppo_slices) return fail(h, RANENV_E_STATE, "the PPO state was bound per slice (ranenv_ppo_bind_slices): ranenv_ppo_update_slices trains it");
     if (const int rc = ppo_roles(h, slot, members, h->ppo_mixed, h->ppo_wide); rc != RANENV_OK) return rc;
     for (int r = 0; r < 4; r++)
         if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after ranenv_ppo_bind: bind again", NET_ROLES[r].who);
@@ -2331,13 +2376,38 @@ static int ppo_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
     });
 }
 
+// ---- non-shared intra policies (include/ranenv.h "per slice"): ranenv_ppo_bind_slices / ranenv_ppo_update_slices ------------------
+int ranenv_ppo_bind_slices(ranenv_handle h, int32_t wide, void *stream)
+{
+    if (wide != 0 && wide != 1) return fail(h, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
+    return ppo_bind(h, false, wide == 1, stream, true);
+}
+
+// The bound state behind ranenv_ppo_bind_slices, or RANENV_E_STATE
+static int ppo_slices_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4])
+{
+    if (!h->ppo_on || !h->ppo_slices) return fail(h, RANENV_E_STATE, "no per-slice PPO state bound, or a binding call has outgrown it or left the per-slice form: bind again (ranenv_ppo_bind_slices)");
+    for (int r = 0; r < 4; r++)
+        if (const ranenv::NetSlot *x = h->serving(r); (r == 1 && !x) || (x && x->form != ((r & 1) ? FORM_SLICE : FORM_ONE)))
+            return fail(h, RANENV_E_STATE, "the %s nets have left the per-slice form since ranenv_ppo_bind_slices: bind again", NET_ROLES[r].who);
+    if (const int rc = ppo_slice_roles(h, slot, h->ppo_wide); rc != RANENV_OK) return rc;
+    for (int r = 0; r < 4; r++)
+        if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after ranenv_ppo_bind_slices: bind again", NET_ROLES[r].who);
+    if (!h->ppo_wide) return RANENV_OK;
+    if ((long long)(1 + h->cfg.n_slices) * h->ppo_park_stride > h->ppo_park_cap) return fail(h, RANENV_E_STATE, "the parked rows were allocated for another binding: bind again");
+    return ppo_each_shape(slot, false, true, 1, [&](int, int k, long long, size_t, long long p) {
+        if (p <= h->ppo_park_stride) return (int)RANENV_OK;
+        return fail(h, RANENV_E_STATE, "the %s nets park %lld floats of rows per workgroup, ranenv_ppo_bind_slices allocated %lld: bind again", k ? "intra" : "inter", p, h->ppo_park_stride);
+    });
+}
+
 static PpoNet ppo_net(const ranenv::NetSlot *slot)
 {
     PpoNet n{};
     if (!slot) return n;
     n.net = slot->net; n.net.w = nullptr;
     n.w = slot->w; n.m = slot->opt; n.v = slot->opt + slot->opt_cap; n.g = slot->opt + 2 * slot->opt_cap;
-    n.stride = slot->member_stride; n.floats = net_floats(slot->net);
+    n.stride = slot->form == FORM_SLICE ? slot->net.slice_stride : slot->member_stride; n.floats = net_floats(slot->net);
     return n;
 }
 
@@ -2347,7 +2417,7 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
     ranenv::NetSlot *slot[4];
     int members = 0;
     const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide;
-    if (const int rc = ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    if (const int rc = h->ppo_on && h->ppo_slices ? ppo_slice_roles(h, slot, wide) : ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
     const PpoPlan plan = ppo_plan(slot, mixed, wide, members);
     if (grad_floats) *grad_floats = plan.grad_floats;
     if (lds_bytes) *lds_bytes = (int64_t)plan.lds;
@@ -2359,8 +2429,9 @@ int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int6
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide;
-    if (const int rc = ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide, slices = h->ppo_on && h->ppo_slices;
+    if (const int rc = slices ? ppo_slice_roles(h, slot, wide) : ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    if (slices) members = kind == 1 ? h->cfg.n_slices : 1;      // (the slices' pairs have one shape: slice 0's entry answers for all)
     if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
     if (kind != 0 && kind != 1) return fail(h, RANENV_E_INVALID, "kind %d (0 inter, 1 intra)", kind);
     if (!slot[kind]) return fail(h, RANENV_E_STATE, "no %s actor bound", kind ? "intra" : "inter");
@@ -2432,6 +2503,17 @@ int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp)
     return RANENV_OK;
 }
 
+// What an update needs of the record: the inter columns, the intra ones where the call trains `intra_actor`'s rows, rows an int32 numbers
+static int ppo_record_check(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, const ranenv::NetSlot *intra_actor)
+{
+    if (!traj->obs_inter || !traj->mask_inter || !traj->action_inter || !traj->logp || !traj->adv || !traj->vtarg)
+        return fail(h, RANENV_E_INVALID, "the record needs obs_inter, mask_inter, action_inter, logp, adv and vtarg");
+    if (intra_actor && (!traj->obs_intra || !traj->action_intra || (intra_actor->net.layout == RANENV_NET_IN_MASK_OBS && !traj->mask_intra)))
+        return fail(h, RANENV_E_INVALID, "the record needs obs_intra and action_intra (mask_intra for RANENV_NET_IN_MASK_OBS nets) for the intra rows");
+    if ((long long)n_steps * h->cfg.batch * h->cfg.n_slices > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "the record has more than 2^31 - 1 intra rows");
+    return RANENV_OK;
+}
+
 int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, int32_t n_members, const ranenv_ppo_hparams *hp,
                       const int32_t *order_inter, const int32_t *first_inter, const int32_t *order_intra, const int32_t *first_intra, double *stats,
                       float *grad, void *stream)
@@ -2454,12 +2536,7 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
         max_epochs = hp[m].epochs > max_epochs ? hp[m].epochs : max_epochs;
     }
     const bool mixed = h->ppo_mixed, wide = h->ppo_wide;
-    if (!traj->obs_inter || !traj->mask_inter || !traj->action_inter || !traj->logp || !traj->adv || !traj->vtarg)
-        return fail(h, RANENV_E_INVALID, "the record needs obs_inter, mask_inter, action_inter, logp, adv and vtarg");
-    if (intra && (!traj->obs_intra || !traj->action_intra || (slot[1]->net.layout == RANENV_NET_IN_MASK_OBS && !traj->mask_intra)))
-        return fail(h, RANENV_E_INVALID, "the record needs obs_intra and action_intra (mask_intra for RANENV_NET_IN_MASK_OBS nets) for the intra rows");
-    const long long rows_max[2] = {(long long)n_steps * h->cfg.batch, (long long)n_steps * h->cfg.batch * h->cfg.n_slices};
-    if (rows_max[1] > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "the record has more than 2^31 - 1 intra rows");
+    if (const int rc = ppo_record_check(h, n_steps, traj, intra ? slot[1] : nullptr); rc != RANENV_OK) return rc;
     PpoArgs a{};
     for (int k = 0; k < (intra ? 2 : 1); k++) {
         const int32_t *first = k ? first_intra : first_inter;
@@ -2488,6 +2565,76 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
     HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)members, hipMemcpyHostToDevice, s));
     const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_bound: every workgroup's rows fit its share)
     HIP_TRY(h, launch_ppo_update(s, members, plan.lds, a, mixed ? &x : nullptr, wide ? &y : nullptr));
+    return RANENV_OK;
+}
+
+// ranenv_ppo_update_slices: ranenv_ppo_update's checks and arguments in the per-slice geometry -- "member" s of kind 1 is slice s
+int ranenv_ppo_update_slices(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, const ranenv_ppo_hparams *hp, const int32_t *order_inter,
+                             int32_t n_inter, const int32_t *order_intra, const int32_t *first_slice, double *stats, float *grad, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    float *const probe_logp = h->ppo_probe;
+    h->ppo_probe = nullptr;          // (armed for ONE update, served or refused)
+    ranenv::NetSlot *slot[4];
+    if (const int rc = ppo_slices_bound(h, slot); rc != RANENV_OK) return rc;
+    if (n_steps < 1 || !traj || !hp || !order_inter || !stats) return fail(h, RANENV_E_INVALID, "n_steps >= 1, the record, the hyper-parameters, the inter row list and dev_stats are required");
+    if (n_inter < 0) return fail(h, RANENV_E_INVALID, "n_inter %d (>= 0)", n_inter);
+    const bool intra = order_intra != nullptr;
+    if (intra && !first_slice) return fail(h, RANENV_E_INVALID, "intra row lists without host_first_slice");
+    if (hp->minibatch < 1) return fail(h, RANENV_E_INVALID, "minibatch %d (>= 1)", hp->minibatch);
+    if (hp->epochs < 0) return fail(h, RANENV_E_INVALID, "epochs %d (>= 0)", hp->epochs);
+    if (const int rc = ppo_record_check(h, n_steps, traj, intra ? slot[1] : nullptr); rc != RANENV_OK) return rc;
+    const int S = h->cfg.n_slices;
+    PpoArgs a{};
+    a.first[0][1] = n_inter; a.order[0] = order_inter; a.order_stride[0] = n_inter;
+    a.net[0][0] = ppo_net(slot[0]); a.net[0][1] = ppo_net(slot[2]);
+    if (intra) {
+        if (first_slice[0] != 0) return fail(h, RANENV_E_INVALID, "host_first_slice[0] is %d, not 0", first_slice[0]);
+        for (int sl = 0; sl < S; sl++)
+            if (first_slice[sl + 1] < first_slice[sl]) return fail(h, RANENV_E_INVALID, "host_first_slice decreases at slice %d", sl);
+        for (int sl = 0; sl <= S; sl++) a.first[1][sl] = first_slice[sl];
+        a.order[1] = order_intra; a.order_stride[1] = first_slice[S];
+        a.net[1][0] = ppo_net(slot[1]); a.net[1][1] = ppo_net(slot[3]);
+    }
+    if (hp->epochs == 0) return RANENV_OK;
+    a.T = n_steps; a.B = h->cfg.batch; a.S = S; a.Us = h->cfg.max_ues_slice; a.W = 2 * a.Us + 9;
+    a.hp = h->d_ppo_hp; a.traj = *traj; a.t = h->d_ppo_t; a.max_epochs = hp->epochs; a.stats = stats; a.grad = grad; a.probe_logp = probe_logp;
+    const PpoPlan plan = ppo_plan(slot, false, h->ppo_wide, 1, intra ? 2 : 1);
+    a.grad_stride = plan.grad_floats;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams), hipMemcpyHostToDevice, s));
+    const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_slices_bound: every workgroup's rows fit its share)
+    HIP_TRY(h, launch_ppo_update_slices(s, intra ? S : 0, plan.lds, a, h->ppo_wide ? &y : nullptr));
+    return RANENV_OK;
+}
+
+// A role's slot and the float offset of slice `slice`'s copy in it, for ranenv_get_slice_net_weights (roles 1 and 3 alone) and
+// ranenv_ppo_slice_state (roles 0 and 2: offset 0, `slice` ignored)
+static int slice_copy(ranenv_handle h, int32_t role, int32_t slice, bool intra_only, ranenv::NetSlot *&slot, size_t &at)
+{
+    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
+    slot = h->serving(role); at = 0;
+    if (!slot) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
+    if (!(role & 1)) return intra_only ? fail(h, RANENV_E_INVALID, "role %d: the nets per slice are roles 1 (intra actors) and 3 (intra critics)", role) : (int)RANENV_OK;
+    if (slot->form != FORM_SLICE) return fail(h, RANENV_E_STATE, "the %s nets are not bound per slice", NET_ROLES[role].who);
+    if (slice < 0 || slice >= h->cfg.n_slices) return fail(h, RANENV_E_INVALID, "slice %d outside the %d", slice, h->cfg.n_slices);
+    at = (size_t)slice * (size_t)slot->net.slice_stride;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_slice_state(ranenv_handle h, int32_t role, int32_t slice, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
+    ranenv::NetSlot *slot[4], *x = nullptr;
+    if (const int rc = ppo_slices_bound(h, slot); rc != RANENV_OK) return rc;
+    size_t at = 0;
+    if (const int rc = slice_copy(h, role, slice, false, x, at); rc != RANENV_OK) return rc;
+    if (dev_m) *dev_m = x->opt + at;
+    if (dev_v) *dev_v = x->opt + x->opt_cap + at;
+    if (dev_t) *dev_t = h->d_ppo_t + ((role & 1) ? 1 + slice : 0);
+    if (floats) *floats = net_floats(x->net);
     return RANENV_OK;
 }
 
@@ -2526,6 +2673,15 @@ int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv
     const int members = (int)slot->member.size();
     if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
     return net_export(h, slot, member, NET_ROLES[role].who, out, stream);
+}
+
+int ranenv_get_slice_net_weights(ranenv_handle h, int32_t role, int32_t slice, ranenv_mlp *out, void *stream)
+{
+    if (!h || !out) return fail(h, RANENV_E_INVALID, "null argument");
+    ranenv::NetSlot *slot = nullptr;
+    size_t at = 0;
+    if (const int rc = slice_copy(h, role, slice, true, slot, at); rc != RANENV_OK) return rc;
+    return net_export(h, slot, 0, NET_ROLES[role].who, out, stream, slot->w + at);      // (slice 0's entry is every slice's layout)
 }
 
 // ---- PPO update of the head policies (include/ranenv.h "PPO update of the head policies"; ranenv_ppo_update_kernel_head) -----------

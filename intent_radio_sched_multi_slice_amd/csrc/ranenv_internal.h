@@ -294,6 +294,10 @@ size_t ppo_wide_lds_bytes(const PolicyNet &actor, const PolicyNet *critic);
 long long ppo_wide_scratch(const PolicyNet &actor, const PolicyNet *critic);
 // mixed null: the uniform instance; wide non-null: the wide instance of either
 hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoArgs &, const PpoMixed *mixed, const PpoWide *wide = nullptr);
+// ranenv_ppo_update_slices (ranenv_ppo_bind_slices): 1 + n_slices workgroups -- workgroup 0 the inter pair (net[0], first[0][0..1], hp[0]),
+// workgroup 1 + s slice s's intra pair: net[1]'s copies at s * stride, entries [first[1][s], first[1][s + 1]) of the intra lists.  t, stats,
+// grad and the wide scratch are numbered by workgroup: [1 + S] in place of [members][2].  n_slices 0: the inter pair alone.
+hipError_t launch_ppo_update_slices(hipStream_t, int n_slices, size_t lds, const PpoArgs &, const PpoWide *wide);
 // ranenv_ppo_update_head (include/ranenv.h "PPO update of the head policies"): the head actor and critic (net[0], net[1]; stride unused),
 // the handle's log_std [S] with its moments and gradient scratch, the call's hyper-parameters by value, the row lists
 // [max_epochs][n_rows] and the ranenv_collect_head record.  One workgroup.

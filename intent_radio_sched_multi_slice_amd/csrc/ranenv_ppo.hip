@@ -16,6 +16,8 @@
 // The weights this launch reads were written by the launch itself one minibatch earlier: every weight read is a vector load at a
 // lane-dependent address behind a workgroup barrier (the forward's float4 / bias loads, the backward's W loads, Adam's own) -- none
 // through the scalar cache, which does not see the vector stores.
+// Non-shared intra policies (ranenv_ppo_bind_slices, ranenv_ppo_update_slices) train in a launch of 1 + S workgroups of the same body: one
+// for the inter pair and one per slice, each on its own rows, nets, counter, statistics and gradient block.
 // Nets beyond that LDS plan train under the WIDE plan (ranenv_ppo_bind_wide; "the wide plan" below): two row buffers in LDS, every
 // layer's input rows parked in a scratch of the workgroup's own in global memory -- written and read back by vector loads and stores
 // at lane-dependent addresses behind workgroup barriers, as the weights are -- and the same arithmetic in the same order.
@@ -132,13 +134,18 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
 // expression macros below, and its steps are ranenv_ppo_parts.hpp's functions.
 // WIDE (ranenv_ppo_bind_wide): the forward and backward pass of a tile follow the wide plan above, on the workgroup's share of Y.scratch;
 // every other line of the body is the same text.
+// SLICES (ranenv_ppo_bind_slices: one intra actor / critic pair per slice): a launch of 1 + S workgroups -- workgroup 0 the inter pair,
+// workgroup 1 + s slice s's pair, whose weights, moments and gradient stand at s x the slot's slice stride and whose rows are its own
+// share of the intra list.  What differs is where a workgroup finds its work (PPO_WG, and `mem` / `kind` at the body's top).
 #define PPO_NET(k) (MIXED ? park[k] : A.net[kind][k].net)
 #define PPO_FLOATS(k) (MIXED ? ((k) == 0 ? fl0 : fl1) : A.net[kind][k].floats)
+#define PPO_WG (SLICES ? (size_t)blockIdx.x : (size_t)mem * 2 + kind)
+#define PPO_WG_I (SLICES ? (int)blockIdx.x : mem * 2 + kind)
 static_assert(PPO_FIXED >= (256 + NET_ROWS * PPO_ROW_STATS) * 8 + NET_ROWS * 4 + 2 * (int)sizeof(PolicyNet), "the fixed LDS region holds the two parked descriptors");
 
 __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel(PpoArgs A)
 {
-    constexpr bool MIXED = false, WIDE = false;
+    constexpr bool MIXED = false, WIDE = false, SLICES = false;
     const PpoMixed X{};
     const PpoWide Y{};
 #include "ranenv_ppo_body.hpp"
@@ -146,25 +153,42 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel(PpoArgs A)
 
 __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_mixed(PpoArgs A, PpoMixed X)
 {
-    constexpr bool MIXED = true, WIDE = false;
+    constexpr bool MIXED = true, WIDE = false, SLICES = false;
     const PpoWide Y{};
 #include "ranenv_ppo_body.hpp"
 }
 
 __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_wide(PpoArgs A, PpoWide Y)
 {
-    constexpr bool MIXED = false, WIDE = true;
+    constexpr bool MIXED = false, WIDE = true, SLICES = false;
     const PpoMixed X{};
 #include "ranenv_ppo_body.hpp"
 }
 
 __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_mixed_wide(PpoArgs A, PpoMixed X, PpoWide Y)
 {
-    constexpr bool MIXED = true, WIDE = true;
+    constexpr bool MIXED = true, WIDE = true, SLICES = false;
+#include "ranenv_ppo_body.hpp"
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_slices(PpoArgs A)
+{
+    constexpr bool MIXED = false, WIDE = false, SLICES = true;
+    const PpoMixed X{};
+    const PpoWide Y{};
+#include "ranenv_ppo_body.hpp"
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_slices_wide(PpoArgs A, PpoWide Y)
+{
+    constexpr bool MIXED = false, WIDE = true, SLICES = true;
+    const PpoMixed X{};
 #include "ranenv_ppo_body.hpp"
 }
 #undef PPO_NET
 #undef PPO_FLOATS
+#undef PPO_WG
+#undef PPO_WG_I
 
 // ---- the head policies (ranenv_ppo_update_head; include/ranenv.h "PPO update of the head policies") ----------------------------------
 // ONE workgroup trains the head actor, the head critic and the state-independent log_std [S] of SB3's Gaussian on a ranenv_collect_head
@@ -360,6 +384,13 @@ hipError_t launch_ppo_update(hipStream_t s, int n_members, size_t lds, const Ppo
     if (wide) return launch_lds<ranenv_ppo_update_kernel_wide>(grid, block, lds, s, a, *wide);
     if (mixed) return launch_lds<ranenv_ppo_update_kernel_mixed>(grid, block, lds, s, a, *mixed);
     return launch_lds<ranenv_ppo_update_kernel>(grid, block, lds, s, a);
+}
+
+hipError_t launch_ppo_update_slices(hipStream_t s, int n_slices, size_t lds, const PpoArgs &a, const PpoWide *wide)
+{
+    const dim3 grid(1u + (unsigned)n_slices), block(256);
+    if (wide) return launch_lds<ranenv_ppo_update_kernel_slices_wide>(grid, block, lds, s, a, *wide);
+    return launch_lds<ranenv_ppo_update_kernel_slices>(grid, block, lds, s, a);
 }
 
 hipError_t launch_ppo_update_head(hipStream_t s, size_t lds, const PpoHeadArgs &a) { return launch_lds<ranenv_ppo_update_kernel_head>(dim3(1, 1), dim3(256), lds, s, a); }

@@ -1,11 +1,14 @@
 // ranenv_ppo_body.hpp -- the body of the PPO update kernels (ranenv_ppo.hip expands it once per kernel: no include guard).  In scope where
-// it is expanded: the kernel's arguments `A` (PpoArgs), `X` (PpoMixed) and `Y` (PpoWide), `constexpr bool MIXED` and `WIDE`, and the macros
-// PPO_NET(k) / PPO_FLOATS(k) -- net k's descriptor and packed floats of this workgroup's member.
+// it is expanded: the kernel's arguments `A` (PpoArgs), `X` (PpoMixed) and `Y` (PpoWide), `constexpr bool MIXED`, `WIDE` and `SLICES`, and the
+// macros PPO_NET(k) / PPO_FLOATS(k) -- net k's descriptor and packed floats of this workgroup's member -- and PPO_WG / PPO_WG_I, the
+// workgroup's number among the call's (size_t / int): where its step counter, statistics, gradient block and parked rows lie.
+// SLICES (ranenv_ppo_bind_slices): workgroup 0 is (member 0, inter), workgroup 1 + s is (`mem` = s, intra) -- slice s's copy of the intra
+// nets stands at s x stride as a member's does, its share of the row list is first[1][s] .. first[1][s + 1], and hp[0] serves all.
     extern __shared__ float lds[];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mem = (int)blockIdx.x, kind = (int)blockIdx.y;
+    const int mem = SLICES ? ((int)blockIdx.x > 0 ? (int)blockIdx.x - 1 : 0) : (int)blockIdx.x, kind = SLICES ? ((int)blockIdx.x > 0 ? 1 : 0) : (int)blockIdx.y;
     if (A.net[kind][0].net.n_layers == 0) return;
-    const ranenv_ppo_hparams &hp = A.hp[mem];
+    const ranenv_ppo_hparams &hp = A.hp[SLICES ? 0 : mem];
     const int epochs = hp.epochs, minibatch = hp.minibatch;
     if (epochs <= 0 || minibatch < 1) return;          // (minibatch < 1: the host refuses it)
     const int lo = A.first[kind][mem], n = A.first[kind][mem + 1] - lo;
@@ -29,8 +32,8 @@
     }
     const int S = A.S;
     const long long n_record = (long long)A.T * A.B * (kind == 0 ? 1 : S);
-    int t = A.t[mem * 2 + kind];
-    float *const wpark = WIDE ? Y.scratch + ((size_t)mem * 2 + kind) * (size_t)Y.stride : nullptr;      // (the workgroup's parked rows)
+    int t = A.t[PPO_WG_I];
+    float *const wpark = WIDE ? Y.scratch + PPO_WG * (size_t)Y.stride : nullptr;      // (the workgroup's parked rows)
 
 #pragma unroll 1
     for (int ep = 0; ep < epochs; ep++) {
@@ -98,14 +101,14 @@
             st.n_mb += 1;
             __syncthreads();                   // (the next minibatch reads the new weights)
         }
-        if (tid == 0) ppo_epoch_stats(A.stats + (((size_t)mem * 2 + kind) * (size_t)A.max_epochs + ep) * RANENV_PPO_STATS, st, n);
+        if (tid == 0) ppo_epoch_stats(A.stats + (PPO_WG * (size_t)A.max_epochs + ep) * RANENV_PPO_STATS, st, n);
     }
     if (A.grad) {
-        float *out = A.grad + ((size_t)mem * 2 + kind) * (size_t)A.grad_stride;
+        float *out = A.grad + PPO_WG * (size_t)A.grad_stride;
 #pragma unroll 1
         for (int k = 0; k < n_nets; k++) {
             ppo_grad_out(out, A.net[kind][k].g + mem * A.net[kind][k].stride, PPO_FLOATS(k), tid);
             out += PPO_FLOATS(k);
         }
     }
-    if (tid == 0) A.t[mem * 2 + kind] = t;
+    if (tid == 0) A.t[PPO_WG_I] = t;
