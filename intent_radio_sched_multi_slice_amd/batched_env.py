@@ -249,6 +249,69 @@ def population_means(result: Dict[str, np.ndarray], first_env) -> Dict[str, np.n
             for name, x in result.items() if np.issubdtype(np.asarray(x).dtype, np.floating)}
 
 
+PPO_ROW_EPOCHS_CAP = 1 << 20       # rows x epochs of ONE member (one compute unit works through them); the reference's regime is 2048 x 10
+# Optimiser steps of ONE member in a launch: a step zeroes the gradient, takes the norm and runs Adam over ALL parameters, a floor
+# no row count lowers.  The reference's search space needs 2048 / 8 x 20 = 5120 at the most, its default regime 320; at the 0.19 ms
+# ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
+PPO_STEPS_CAP = 1 << 13
+
+
+def ppo_hparams(G: int, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, grad_clip, adv_norm, betas, eps):
+    """``ranenv_ppo_hparams[G]`` of the ``ppo_update*`` methods' arguments: every one a scalar, one value for all, or a sequence of G
+    values, member m's (``betas``: one pair for all; ``grad_clip`` None: 0.0, no clipping; ``adv_norm`` "minibatch", or "none" / None).
+    Returns (the ctypes array, epochs int64 [G], minibatch int64 [G])."""
+    def per_member(x, name, dtype=np.float64):
+        a = np.asarray(x, dtype=dtype).reshape(-1) if np.ndim(x) > 0 else np.full(G, x, dtype=dtype)
+        if a.size != G:
+            raise ValueError(f"{name}: {a.size} values given, one per member is {G}")
+        return a
+    norm = [adv_norm] * G if adv_norm is None or isinstance(adv_norm, str) else list(adv_norm)
+    if len(norm) != G or any(x not in ("minibatch", "none", None) for x in norm):
+        raise ValueError('adv_norm is "minibatch" or None, one for all or one per member')
+    cols = {"lr": per_member(lr, "lr"), "clip": per_member(clip, "clip"), "vf_coeff": per_member(vf_coeff, "vf_coeff"),
+            "ent_coeff": per_member(ent_coeff, "ent_coeff"), "grad_clip": per_member(0.0 if grad_clip is None else grad_clip, "grad_clip"),
+            "eps": per_member(eps, "eps"), "minibatch": per_member(minibatch, "minibatch", np.int64), "epochs": per_member(epochs, "epochs", np.int64)}
+    hp = (_lib.PpoHparams * G)()
+    for m in range(G):
+        for k, v in cols.items():
+            setattr(hp[m], k, v[m].item())
+        hp[m].beta1, hp[m].beta2, hp[m].adv_norm = float(betas[0]), float(betas[1]), 1 if norm[m] == "minibatch" else 0
+    return hp, cols["epochs"], cols["minibatch"]
+
+
+def ppo_order_firsts(order, units: Dict[str, int], epochs, minibatch, caps=(PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP), method: str = "ppo_update",
+                     per_slice: bool = False, force: bool = False) -> Dict[str, np.ndarray]:
+    """The ``first_<kind>`` tables, int32 [units[kind] + 1], of an ``order`` dict as ``adapters.ppo_row_order`` returns it -- or what
+    ``method`` ("ppo_update" / "ppo_update_per_slice") refuses in it: per kind "inter" / "intra" with an "order_<kind>" a contiguous
+    int32 [>= max epochs, first[-1]] tensor of rows beside a table of that size (``per_slice``: which starts at 0), and no unit of
+    more than ``caps[0]`` rows x epochs or ``caps[1]`` optimiser steps -- ceil(rows / minibatch) per epoch -- unless ``force``.
+    ``epochs`` / ``minibatch``: per unit, or one value for all.  The units are members, or (``per_slice``) policies."""
+    epochs, minibatch = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (epochs, minibatch))
+    max_epochs, unit = int(epochs.max()), "policy" if per_slice else "member"
+    kinds = [k for k in ("inter", "intra") if order.get("order_" + k) is not None]
+    if per_slice and "inter" not in kinds:
+        raise ValueError("order needs order_inter / first_inter")
+    firsts = {}
+    for k in kinds:
+        o, f, n = order["order_" + k], np.ascontiguousarray(order["first_" + k], dtype=np.int32), units[k] + 1
+        if (f.size != n or (per_slice and f[0] != 0) or o.dtype != torch.int32 or o.dim() != 2 or o.shape[0] < max_epochs or o.shape[1] != int(f[-1])
+                or not o.is_contiguous()):
+            raise ValueError(f"order_{k}: int32 [>= {max_epochs} epochs, first_{k}[-1]] with first_{k} of {n} entries" + (" from 0" if per_slice else "")
+                             + (" (adapters.ppo_row_order(..., per_slice=True))" if per_slice and k == "intra" else ""))
+        rows = np.diff(f).astype(np.int64)
+        if not force and int((rows * epochs).max()) > caps[0]:
+            raise RanEnvError(f"{method}: a {unit} has more than {caps[0]} rows x epochs ({k}); one compute unit works "
+                              f"through a {unit}'s rows -- train such a batch in torch, or pass force=True")
+        steps = int((-(-rows // np.maximum(minibatch, 1)) * epochs).max())
+        if not force and steps > caps[1]:
+            raise RanEnvError(f"{method}: a {unit} has more than {caps[1]} optimiser steps ({k}: {steps}); every step "
+                              "passes over all parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
+        firsts[k] = f
+    if "inter" not in kinds:
+        raise ValueError("order needs order_inter / first_inter")
+    return firsts
+
+
 class BatchedRanEnv:
     def __init__(self, batch: int, n_slices: int, n_ues: int, n_rbs: int, rbs_per_rbg: int = 1,
                  max_ues_slice: Optional[int] = None, n_scenarios: int = 1, bandwidth_hz: float = 100e6,
@@ -872,11 +935,7 @@ class BatchedRanEnv:
         return adv, vtarg
 
     # -- the PPO update on the device (ranenv_ppo_bind / ranenv_ppo_update; include/ranenv.h "PPO update") ---------------------------
-    PPO_ROW_EPOCHS_CAP = 1 << 20       # rows x epochs of ONE member (one compute unit works through them); the reference's regime is 2048 x 10
-    # Optimiser steps of ONE member in a launch: a step zeroes the gradient, takes the norm and runs Adam over ALL parameters, a floor
-    # no row count lowers.  The reference's search space needs 2048 / 8 x 20 = 5120 at the most, its default regime 320; at the 0.19 ms
-    # ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
-    PPO_STEPS_CAP = 1 << 13
+    PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP = PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP      # (per handle: an attribute of the instance overrides them)
 
     def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
@@ -946,70 +1005,53 @@ class BatchedRanEnv:
         than ``PPO_ROW_EPOCHS_CAP`` rows x epochs or ``PPO_STEPS_CAP`` optimiser steps for one member is refused unless ``force`` -- such
         a batch belongs to torch."""
         G = self._ppo_members()
-        def per_member(x, name, dtype=np.float64):      # noqa: E306
-            a = np.asarray(x, dtype=dtype).reshape(-1) if np.ndim(x) > 0 else np.full(G, x, dtype=dtype)
-            if a.size != G:
-                raise ValueError(f"{name}: {a.size} values given, one per member is {G}")
-            return a
-        norm = [adv_norm] * G if adv_norm is None or isinstance(adv_norm, str) else list(adv_norm)
-        if len(norm) != G or any(x not in ("minibatch", "none", None) for x in norm):
-            raise ValueError('adv_norm is "minibatch" or None, one for all or one per member')
-        cols = {"lr": per_member(lr, "lr"), "clip": per_member(clip, "clip"), "vf_coeff": per_member(vf_coeff, "vf_coeff"),
-                "ent_coeff": per_member(ent_coeff, "ent_coeff"), "grad_clip": per_member(0.0 if grad_clip is None else grad_clip, "grad_clip"),
-                "eps": per_member(eps, "eps"), "minibatch": per_member(minibatch, "minibatch", np.int64), "epochs": per_member(epochs, "epochs", np.int64)}
-        hp = (_lib.PpoHparams * G)()
-        for m in range(G):
-            for k, v in cols.items():
-                setattr(hp[m], k, v[m].item())
-            hp[m].beta1, hp[m].beta2, hp[m].adv_norm = float(betas[0]), float(betas[1]), 1 if norm[m] == "minibatch" else 0
-        max_epochs = int(cols["epochs"].max())
-        T = int(rec["logp"].shape[0])
+        hp, epochs, minibatch = ppo_hparams(G, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, grad_clip, adv_norm, betas, eps)
+        max_epochs = int(epochs.max())
         if order is None:
             from .adapters import ppo_row_order
             first_env = self._population if G > 1 else [0, self.B]
             order = ppo_row_order(rec, first_env, max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec)
-        kinds = [k for k in ("inter", "intra") if order.get("order_" + k) is not None]
-        firsts = {}
-        for k in kinds:
-            o, f = order["order_" + k], np.ascontiguousarray(order["first_" + k], dtype=np.int32)
-            if f.size != G + 1 or o.dtype != torch.int32 or o.dim() != 2 or o.shape[0] < max_epochs or o.shape[1] != int(f[-1]) or not o.is_contiguous():
-                raise ValueError(f"order_{k}: int32 [>= {max_epochs} epochs, first_{k}[-1]] with first_{k} of {G + 1} entries")
-            if not force and int((np.diff(f) * cols["epochs"]).max()) > self.PPO_ROW_EPOCHS_CAP:
-                raise RanEnvError(f"ppo_update: a member has more than {self.PPO_ROW_EPOCHS_CAP} rows x epochs ({k}); one compute unit works "
-                                  "through a member's rows -- train such a batch in torch, or pass force=True")
-            steps = -(-np.diff(f).astype(np.int64) // np.maximum(cols["minibatch"], 1)) * cols["epochs"]
-            if not force and int(steps.max()) > self.PPO_STEPS_CAP:
-                raise RanEnvError(f"ppo_update: a member has more than {self.PPO_STEPS_CAP} optimiser steps ({k}: {int(steps.max())}); every step "
-                                  "passes over all parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
-            firsts[k] = f
-        if "inter" not in kinds:
-            raise ValueError("order needs order_inter / first_inter")
-        traj, keep = _lib.Trajectory(), []
-        for f in _lib.TRAJECTORY_FIELDS:
+        firsts = ppo_order_firsts(order, {"inter": G, "intra": G}, epochs, minibatch, (self.PPO_ROW_EPOCHS_CAP, self.PPO_STEPS_CAP), "ppo_update", force=force)
+        lists, _pi = self._ppo_lists(order, firsts), lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        return self._ppo_launch("ranenv_ppo_update", lambda T, traj, stats, gbuf, stream: self._lib.ranenv_ppo_update(
+            self._h, T, traj, G, hp, _ptr(lists["inter"]), _pi(firsts["inter"]), _ptr(lists.get("intra")), _pi(firsts["intra"]) if "intra" in firsts else None,
+            stats, gbuf, stream), rec, (G, 2, max(max_epochs, 1)), (lambda: (G, 2, self._ppo_grad_floats())) if grad else None, probe_logp)
+
+    def _ppo_lists(self, order, firsts):
+        """The row lists of the kinds in ``firsts`` as the C call takes them: a list without rows still is a list, not NULL."""
+        none = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return {k: order["order_" + k] if order["order_" + k].numel() else none for k in firsts}
+
+    def _ppo_grad_floats(self) -> int:
+        gf = C.c_int64()
+        self._check(self._lib.ranenv_ppo_layout(self._h, C.byref(gf), None), "ranenv_ppo_layout")
+        return gf.value
+
+    def _ppo_launch(self, name, call, rec, stats_shape, grad_shape=None, probe_logp=False, head=False):
+        """What the three ``ppo_update*`` share behind their checks: the record ``rec`` marshalled into a ``Trajectory`` (``head``: a
+        ``HeadTrajectory``), the statistics [*stats_shape, len(PPO_STATS)], the gradient buffer of ``grad_shape()`` (None: none) and the
+        log-probability buffer of an armed probe, the C ``call(T, traj, stats, grad, stream)`` of ``name``, and the result dict."""
+        T = int(rec["logp"].shape[0])
+        if head:
+            struct, fields, shapes, sizes = _lib.HeadTrajectory, _lib.HEAD_TRAJECTORY_FIELDS, self._head_shapes(self.HEAD_TRAJECTORY_SHAPES, "")[0], (self.B, self.S)
+        else:
+            struct, fields, shapes, sizes = _lib.Trajectory, _lib.TRAJECTORY_FIELDS, self.TRAJECTORY_SHAPES, (self.B, self.S, self.Us, self.W)
+        traj, keep = struct(), []
+        for f in fields:
             if f in rec:
-                dt, extra, shape = self.TRAJECTORY_SHAPES[f]
-                keep.append(self._dev(rec[f], dt, (T + extra,) + shape(self.B, self.S, self.Us, self.W), f))
+                dt, extra, shape = shapes[f]
+                keep.append(self._dev(rec[f], dt, (T + extra,) + shape(*sizes), f))
                 setattr(traj, f, keep[-1].data_ptr())
-        stats = torch.zeros((G, 2, max(max_epochs, 1), len(_lib.PPO_STATS)), dtype=torch.float64, device=self.device)
-        gbuf = None
-        if grad:
-            gf = C.c_int64()
-            self._check(self._lib.ranenv_ppo_layout(self._h, C.byref(gf), None), "ranenv_ppo_layout")
-            gbuf = torch.zeros((G, 2, gf.value), dtype=torch.float32, device=self.device)
+        stats = torch.zeros(tuple(stats_shape) + (len(_lib.PPO_STATS),), dtype=torch.float64, device=self.device)
+        gbuf = torch.zeros(grad_shape(), dtype=torch.float32, device=self.device) if grad_shape is not None else None
         lbuf = torch.zeros((T, self.B, self.S + 1), dtype=torch.float32, device=self.device) if probe_logp else None
-        _pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
-        none = torch.zeros(1, dtype=torch.int32, device=self.device)      # (a list without rows still is a list: not NULL)
-        lists = {k: order["order_" + k] if order["order_" + k].numel() else none for k in kinds}
         with torch.cuda.device(self.device):
             if probe_logp:          # (armed for the one update below, which disarms it whether it is served or refused)
                 self._check(self._lib.ranenv_ppo_probe_logp(self._h, _ptr(lbuf)), "ranenv_ppo_probe_logp")
-            self._check(self._lib.ranenv_ppo_update(
-                self._h, T, C.byref(traj), G, hp, _ptr(lists["inter"]), _pi(firsts["inter"]),
-                _ptr(lists["intra"]) if "intra" in kinds else None, _pi(firsts["intra"]) if "intra" in kinds else None,
-                _ptr(stats), _ptr(gbuf), self._stream()), "ranenv_ppo_update")
+            self._check(call(T, C.byref(traj), _ptr(stats), _ptr(gbuf), self._stream()), name)
         host = stats.cpu().numpy()             # (synchronises: the launch is over, `order` and `rec` may go)
-        out = {name: host[..., i] for i, name in enumerate(_lib.PPO_STATS)}
-        if grad:
+        out = {stat: host[..., i] for i, stat in enumerate(_lib.PPO_STATS)}
+        if gbuf is not None:
             out["grad"] = gbuf
         if probe_logp:
             out["logp"] = lbuf
@@ -1032,63 +1074,18 @@ class BatchedRanEnv:
                         ("grad_clip", 0.0 if grad_clip is None else grad_clip), ("eps", eps)):
             if np.ndim(x) != 0:
                 raise ValueError(f"{name}: ppo_update_per_slice takes one value for all policies")
-        hp = _lib.PpoHparams()
-        hp.lr, hp.clip, hp.vf_coeff, hp.ent_coeff, hp.grad_clip, hp.eps = float(lr), float(clip), float(vf_coeff), float(ent_coeff), float(grad_clip or 0.0), float(eps)
-        hp.beta1, hp.beta2, hp.adv_norm, hp.minibatch, hp.epochs = float(betas[0]), float(betas[1]), 1 if adv_norm == "minibatch" else 0, int(minibatch), int(epochs)
-        epochs, S = int(epochs), self.S
-        T = int(rec["logp"].shape[0])
+        hp, epochs, minibatch = ppo_hparams(1, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, grad_clip, adv_norm, betas, eps)
+        max_epochs, S = int(epochs[0]), self.S
         if order is None:
             from .adapters import ppo_row_order
-            order = ppo_row_order(rec, [0, self.B], max(epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec, per_slice=True)
-        kinds = [k for k in ("inter", "intra") if order.get("order_" + k) is not None]
-        if "inter" not in kinds:
-            raise ValueError("order needs order_inter / first_inter")
-        firsts = {}
-        for k in kinds:
-            o, f = order["order_" + k], np.ascontiguousarray(order["first_" + k], dtype=np.int32)
-            n = 2 if k == "inter" else S + 1
-            if f.size != n or f[0] != 0 or o.dtype != torch.int32 or o.dim() != 2 or o.shape[0] < epochs or o.shape[1] != int(f[-1]) or not o.is_contiguous():
-                raise ValueError(f"order_{k}: int32 [>= {epochs} epochs, first_{k}[-1]] with first_{k} of {n} entries from 0"
-                                 + (" (adapters.ppo_row_order(..., per_slice=True))" if k == "intra" else ""))
-            rows = int(np.diff(f).max())
-            if not force and rows * epochs > self.PPO_ROW_EPOCHS_CAP:
-                raise RanEnvError(f"ppo_update_per_slice: a policy has more than {self.PPO_ROW_EPOCHS_CAP} rows x epochs ({k}); one compute unit works "
-                                  "through a policy's rows -- train such a batch in torch, or pass force=True")
-            steps = -(-rows // max(int(minibatch), 1)) * epochs
-            if not force and steps > self.PPO_STEPS_CAP:
-                raise RanEnvError(f"ppo_update_per_slice: a policy has more than {self.PPO_STEPS_CAP} optimiser steps ({k}: {steps}); every step "
-                                  "passes over all parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
-            firsts[k] = f
-        traj, keep = _lib.Trajectory(), []
-        for f in _lib.TRAJECTORY_FIELDS:
-            if f in rec:
-                dt, extra, shape = self.TRAJECTORY_SHAPES[f]
-                keep.append(self._dev(rec[f], dt, (T + extra,) + shape(self.B, self.S, self.Us, self.W), f))
-                setattr(traj, f, keep[-1].data_ptr())
-        stats = torch.zeros((1 + S, max(epochs, 1), len(_lib.PPO_STATS)), dtype=torch.float64, device=self.device)
-        gbuf = None
-        if grad:
-            gf = C.c_int64()
-            self._check(self._lib.ranenv_ppo_layout(self._h, C.byref(gf), None), "ranenv_ppo_layout")
-            gbuf = torch.zeros((1 + S, gf.value), dtype=torch.float32, device=self.device)
-        lbuf = torch.zeros((T, self.B, S + 1), dtype=torch.float32, device=self.device) if probe_logp else None
-        none = torch.zeros(1, dtype=torch.int32, device=self.device)      # (a list without rows still is a list: not NULL)
-        lists = {k: order["order_" + k] if order["order_" + k].numel() else none for k in kinds}
-        with torch.cuda.device(self.device):
-            if probe_logp:          # (armed for the one update below, which disarms it whether it is served or refused)
-                self._check(self._lib.ranenv_ppo_probe_logp(self._h, _ptr(lbuf)), "ranenv_ppo_probe_logp")
-            self._check(self._lib.ranenv_ppo_update_slices(
-                self._h, T, C.byref(traj), C.byref(hp), _ptr(lists["inter"]), int(firsts["inter"][1]),
-                _ptr(lists["intra"]) if "intra" in kinds else None,
-                firsts["intra"].ctypes.data_as(C.POINTER(C.c_int32)) if "intra" in kinds else None,
-                _ptr(stats), _ptr(gbuf), self._stream()), "ranenv_ppo_update_slices")
-        host = stats.cpu().numpy()             # (synchronises: the launch is over, `order` and `rec` may go)
-        out = {name: host[..., i] for i, name in enumerate(_lib.PPO_STATS)}
-        if grad:
-            out["grad"] = gbuf
-        if probe_logp:
-            out["logp"] = lbuf
-        return out
+            order = ppo_row_order(rec, [0, self.B], max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec, per_slice=True)
+        firsts = ppo_order_firsts(order, {"inter": 1, "intra": S}, epochs, minibatch, (self.PPO_ROW_EPOCHS_CAP, self.PPO_STEPS_CAP), "ppo_update_per_slice",
+                                  per_slice=True, force=force)
+        lists = self._ppo_lists(order, firsts)
+        return self._ppo_launch("ranenv_ppo_update_slices", lambda T, traj, stats, gbuf, stream: self._lib.ranenv_ppo_update_slices(
+            self._h, T, traj, hp, _ptr(lists["inter"]), int(firsts["inter"][1]), _ptr(lists.get("intra")),
+            firsts["intra"].ctypes.data_as(C.POINTER(C.c_int32)) if "intra" in firsts else None, stats, gbuf, stream),
+            rec, (1 + S, max(max_epochs, 1)), (lambda: (1 + S, self._ppo_grad_floats())) if grad else None, probe_logp)
 
     _NET_ROLES = {"inter": 0, "intra": 1, "v_inter": 2, "v_intra": 3}
 
@@ -1106,10 +1103,15 @@ class BatchedRanEnv:
     def _net_weights(self, role: str, m: int, copy: bool = True, slice: Optional[int] = None):
         if role not in self._NET_ROLES:
             raise ValueError(f"role must be one of {sorted(self._NET_ROLES)}")
-        out = _lib.Mlp()
         call, m = ("ranenv_get_net_weights", m) if slice is None else ("ranenv_get_slice_net_weights", slice)
+        return self._export_net(call, self._NET_ROLES[role], int(m), copy=copy)
+
+    def _export_net(self, call: str, *ids, copy: bool = True):
+        """The two-call export behind ``net_weights`` / ``head_net_weights`` / ``sac_net_weights``: ``call(handle, *ids, mlp, stream)``
+        once for the net's shape, then again with ``(W, b)`` tensors of that shape to fill -> (layers, activation)."""
+        out = _lib.Mlp()
         with torch.cuda.device(self.device):
-            self._check(getattr(self._lib, call)(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), call)
+            self._check(getattr(self._lib, call)(self._h, *ids, C.byref(out), self._stream()), call)
             act = {v: k for k, v in NET_ACTIVATIONS.items()}[out.activation]
             if not copy:
                 return None, act
@@ -1118,19 +1120,23 @@ class BatchedRanEnv:
                        torch.empty((dims[i + 1],), dtype=torch.float32, device=self.device)) for i in range(len(dims) - 1)]
             for i, (w, b) in enumerate(layers):
                 out.weight[i], out.bias[i] = w.data_ptr(), b.data_ptr()
-            self._check(getattr(self._lib, call)(self._h, self._NET_ROLES[role], int(m), C.byref(out), self._stream()), call)
+            self._check(getattr(self._lib, call)(self._h, *ids, C.byref(out), self._stream()), call)
         return layers, act
+
+    def _opt_views(self, call: str, *ids) -> Dict[str, torch.Tensor]:
+        """``ppo_state`` / ``ppo_head_state`` / ``sac_state``: zero-copy views of what ``call(handle, *ids, &m, &v, &t, &floats)`` points at."""
+        pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(getattr(self._lib, call)(self._h, *ids, C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), call)
+        return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
+                "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
+                "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}
 
     def ppo_state(self, role: str, m: int = 0, slice: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Zero-copy views of the optimiser state of ``role``'s net of member ``m`` (ranenv_ppo_state): Adam's "m" and "v" in the packed
         layout (float32 [floats]) and "t", the (member, kind) step counter (int32 [1]).  ``slice=s``: under ``ppo_bind(per_slice=True)``
         (ranenv_ppo_slice_state) slice s's net of "intra" / "v_intra" with that slice's counter; "inter" / "v_inter" ignore ``s``."""
-        pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
         call, m = ("ranenv_ppo_state", m) if slice is None else ("ranenv_ppo_slice_state", slice)
-        self._check(getattr(self._lib, call)(self._h, self._NET_ROLES[role], int(m), C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), call)
-        return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
-                "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
-                "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}
+        return self._opt_views(call, self._NET_ROLES[role], int(m))
 
     # -- the learned baselines SchedTWC / SchedColORAN (RANENV_POLICY_HEAD_NETWORK) ------------------------------------------------
     def set_head_policy_network(self, actor, dist: str = "gauss_clip", log_std=None, stochastic: bool = False, seed: int = 0,
@@ -1230,7 +1236,6 @@ class BatchedRanEnv:
         if adv_norm not in ("minibatch", "none", None):
             raise ValueError('adv_norm is "minibatch" or None')
         epochs, minibatch = int(epochs), int(minibatch)
-        T = int(rec["logp"].shape[0])
         if order is None:
             from .adapters import ppo_head_row_order
             order = ppo_head_row_order(rec, max(epochs, 1), seed)
@@ -1245,32 +1250,18 @@ class BatchedRanEnv:
         if not force and steps > self.PPO_STEPS_CAP:
             raise RanEnvError(f"ppo_update_head: more than {self.PPO_STEPS_CAP} optimiser steps ({steps}); every step passes over all "
                               "parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
-        hp = _lib.PpoHparams()
-        hp.lr, hp.clip, hp.vf_coeff, hp.ent_coeff, hp.eps = float(lr), float(clip), float(vf_coeff), float(ent_coeff), float(eps)
-        hp.grad_clip = 0.0 if grad_clip is None else float(grad_clip)
-        hp.beta1, hp.beta2, hp.minibatch, hp.epochs, hp.adv_norm = float(betas[0]), float(betas[1]), minibatch, epochs, 1 if adv_norm == "minibatch" else 0
-        shapes, _ = self._head_shapes(self.HEAD_TRAJECTORY_SHAPES, "")
-        traj, keep = _lib.HeadTrajectory(), []
-        for f in _lib.HEAD_TRAJECTORY_FIELDS:
-            if f in rec:
-                dt, extra, shape = shapes[f]
-                keep.append(self._dev(rec[f], dt, (T + extra,) + shape(self.B, self.S), f))
-                setattr(traj, f, keep[-1].data_ptr())
-        stats = torch.zeros((max(max_epochs, 1), len(_lib.PPO_STATS)), dtype=torch.float64, device=self.device)
-        gbuf = None
-        if grad:
+        lr, clip, vf_coeff, ent_coeff, eps = float(lr), float(clip), float(vf_coeff), float(ent_coeff), float(eps)      # (one value each)
+        hp, _, _ = ppo_hparams(1, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, None if grad_clip is None else float(grad_clip), adv_norm, betas, eps)
+
+        def grad_shape():
             a, c = C.c_int64(), C.c_int64()
             self._check(self._lib.ranenv_ppo_head_layout(self._h, C.byref(a), C.byref(c), None), "ranenv_ppo_head_layout")
-            gbuf = torch.zeros((a.value + c.value + self.S,), dtype=torch.float32, device=self.device)
+            return (a.value + c.value + self.S,)
         none = torch.zeros(1, dtype=torch.int32, device=self.device)      # (a list without rows still is a list: not NULL)
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_ppo_update_head(self._h, T, C.byref(traj), C.byref(hp), _ptr(order if order.numel() else none), n_rows,
-                                                         max_epochs, _ptr(stats), _ptr(gbuf), self._stream()), "ranenv_ppo_update_head")
-        host = stats.cpu().numpy()             # (synchronises: the launch is over, `order` and `rec` may go)
-        out = {name: host[:max_epochs, i] for i, name in enumerate(_lib.PPO_STATS)}
-        if grad:
-            out["grad"] = gbuf
-        return out
+        out = self._ppo_launch("ranenv_ppo_update_head", lambda T, traj, stats, gbuf, stream: self._lib.ranenv_ppo_update_head(
+            self._h, T, traj, hp, _ptr(order if order.numel() else none), n_rows, max_epochs, stats, gbuf, stream),
+            rec, (max(max_epochs, 1),), grad_shape if grad else None, head=True)
+        return {k: v if k == "grad" else v[:max_epochs] for k, v in out.items()}
 
     def ppo_head_layout(self) -> Dict[str, int]:
         """The packed floats of the head "actor" and "critic" -- the layout of ``ppo_update_head(grad=True)["grad"]``, ``log_std`` [S]
@@ -1286,16 +1277,7 @@ class BatchedRanEnv:
         ``(W, b)`` tensors in torch ``Linear`` layout (ranenv_get_head_net_weights)."""
         if which not in ("actor", "critic"):
             raise ValueError('which is "actor" or "critic"')
-        out = _lib.Mlp()
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_get_head_net_weights(self._h, self._HEAD_NETS[which], C.byref(out), self._stream()), "ranenv_get_head_net_weights")
-            dims = list(out.dims[:out.n_hidden + 2])
-            layers = [(torch.empty((dims[i + 1], dims[i]), dtype=torch.float32, device=self.device),
-                       torch.empty((dims[i + 1],), dtype=torch.float32, device=self.device)) for i in range(len(dims) - 1)]
-            for i, (w, b) in enumerate(layers):
-                out.weight[i], out.bias[i] = w.data_ptr(), b.data_ptr()
-            self._check(self._lib.ranenv_get_head_net_weights(self._h, self._HEAD_NETS[which], C.byref(out), self._stream()), "ranenv_get_head_net_weights")
-        return layers
+        return self._export_net("ranenv_get_head_net_weights", self._HEAD_NETS[which])[0]
 
     def head_log_std(self) -> torch.Tensor:
         """A copy of the handle's ``log_std`` float32 [S] as it is NOW (ranenv_get_head_log_std)."""
@@ -1309,11 +1291,7 @@ class BatchedRanEnv:
         and "t", the one step counter (ranenv_ppo_head_state)."""
         if which not in self._HEAD_NETS:
             raise ValueError(f"which must be one of {sorted(self._HEAD_NETS)}")
-        pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        self._check(self._lib.ranenv_ppo_head_state(self._h, self._HEAD_NETS[which], C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), "ranenv_ppo_head_state")
-        return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
-                "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
-                "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}
+        return self._opt_views("ranenv_ppo_head_state", self._HEAD_NETS[which])
 
     # -- off-policy (SAC) collection: replay ring, sampler, targets (include/ranenv.h "Off-policy collection") ----------------------
     REPLAY_SHAPES = {          # field -> (dtype, shape of one slot in terms of B, S)
@@ -1485,16 +1463,7 @@ class BatchedRanEnv:
         ones ``sac_targets()`` reads)."""
         if which not in _lib.SAC_NETS:
             raise ValueError(f"which must be one of {sorted(_lib.SAC_NETS)}")
-        out = _lib.Mlp()
-        with torch.cuda.device(self.device):
-            self._check(self._lib.ranenv_get_sac_net_weights(self._h, _lib.SAC_NETS[which], C.byref(out), self._stream()), "ranenv_get_sac_net_weights")
-            dims = list(out.dims[:out.n_hidden + 2])
-            layers = [(torch.empty((dims[i + 1], dims[i]), dtype=torch.float32, device=self.device),
-                       torch.empty((dims[i + 1],), dtype=torch.float32, device=self.device)) for i in range(len(dims) - 1)]
-            for i, (w, b) in enumerate(layers):
-                out.weight[i], out.bias[i] = w.data_ptr(), b.data_ptr()
-            self._check(self._lib.ranenv_get_sac_net_weights(self._h, _lib.SAC_NETS[which], C.byref(out), self._stream()), "ranenv_get_sac_net_weights")
-        return layers
+        return self._export_net("ranenv_get_sac_net_weights", _lib.SAC_NETS[which])[0]
 
     def sac_log_ent_coef(self) -> torch.Tensor:
         """A copy of the binding's ``log_ent_coef`` float32 [1] as it is NOW (ranenv_get_sac_log_ent_coef); the coefficient the next
@@ -1511,11 +1480,7 @@ class BatchedRanEnv:
         and "t", that tensor's step counter (ranenv_sac_state)."""
         if which not in self._SAC_STATE:
             raise ValueError(f"which must be one of {sorted(self._SAC_STATE)}")
-        pm, pv, pt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        self._check(self._lib.ranenv_sac_state(self._h, self._SAC_STATE[which], C.byref(pm), C.byref(pv), C.byref(pt), C.byref(n)), "ranenv_sac_state")
-        return {"m": torch.as_tensor(_DevArray(pm.value, (n.value,), "f4", self), device=self.device),
-                "v": torch.as_tensor(_DevArray(pv.value, (n.value,), "f4", self), device=self.device),
-                "t": torch.as_tensor(_DevArray(pt.value, (1,), "i4", self), device=self.device)}
+        return self._opt_views("ranenv_sac_state", self._SAC_STATE[which])
 
     def head_episode_metrics(self) -> Dict[str, torch.Tensor]:
         """Zero-copy views of the episode sums of the two head rewards (columns: SchedTWC, SchedColORAN): ``running`` [B, 2]

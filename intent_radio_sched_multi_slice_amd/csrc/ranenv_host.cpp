@@ -151,18 +151,29 @@ struct ranenv {
     const NetSlot *tabled(int r) const { return nets[r][FORM_MEMBER].on ? &nets[r][FORM_MEMBER] : (nets[r][FORM_ONE].on ? &nets[r][FORM_ONE] : nullptr); }
     bool pop_bound() const { for (int r = 0; r < 4; r++) if (nets[r][FORM_MEMBER].on) return true; return false; }
     bool pop_mixed() const { for (int r = 0; r < 4; r++) if (nets[r][FORM_MEMBER].on && nets[r][FORM_MEMBER].mixed) return true; return false; }
-    // ranenv_ppo_bind / ranenv_ppo_update: bound?, the (member, kind) step counters [POP_MAX][2], the call's hyper-parameters on the
-    // device [POP_MAX], the diagnostic log-probability buffer the NEXT update takes and forgets
-    bool ppo_on = false; int32_t *d_ppo_t = nullptr; ranenv_ppo_hparams *d_ppo_hp = nullptr; float *ppo_probe = nullptr;
-    // ranenv_ppo_bind_mixed: the binding trains a mixed population; the packed floats of member m's net of role r on the device,
-    // [4][POP_MAX] (0: the role is not bound), written at that bind and at every re-bind under it
-    bool ppo_mixed = false; long long *d_ppo_floats = nullptr, ppo_floats[4][POP_MAX] = {};      // (... and the host copy the upload reads)
-    // ranenv_ppo_bind_wide: the binding follows the wide plan; the parked rows of the members' workgroups, [members][2][ppo_park_stride]
-    // floats, allocated at that bind (an outgrown one stays allocated, like the weights'), never by an update
-    bool ppo_wide = false; float *d_ppo_park = nullptr; long long ppo_park_stride = 0, ppo_park_cap = 0;
-    // ranenv_ppo_bind_slices: the binding trains one intra pair per slice; the counters d_ppo_t and a wide binding's parked rows are
-    // numbered by workgroup, [1 + S] (0 the inter pair, 1 + s slice s), not [members][2]
-    bool ppo_slices = false;
+    // THE PPO BINDING of the IBSched nets: what ranenv_ppo_bind (plain), _bind_mixed (mixed: a mixed population, each member on its own
+    // shape), _bind_wide (wide: the wide plan, with or without mixed) or _bind_slices (slices: one intra pair per slice, with or without
+    // wide) bound, and the geometry that follows from it, stated here alone.  A handle has one; a binding that ends is `{}` again, so
+    // no flag outlives `on`.  An update UNIT is what one workgroup trains: member m's pair of a kind, or (slices) the inter pair and
+    // slice s's intra pair.
+    struct PpoBinding {
+        bool on = false, mixed = false, wide = false, slices = false;
+        int units(int kind, int members, int S) const { return slices ? (kind == 1 ? S : 1) : members; }      // ... of a kind
+        int workgroups(int members, int S) const { return slices ? 1 + S : 2 * members; }                    // ... of an update launch
+        // unit u of `kind` by workgroup number: its step counter in d_ppo_t and its share of the parked rows in d_ppo_park
+        int wg(int kind, int u) const { return slices ? (kind ? 1 + u : 0) : u * 2 + kind; }
+        // the entry point the messages name (parked: where they speak of the parked rows, which ranenv_ppo_bind_wide allocates)
+        const char *entry(bool parked = false) const { return slices ? "ranenv_ppo_bind_slices" : (parked ? "ranenv_ppo_bind_wide" : "ranenv_ppo_bind"); }
+    } ppo;
+    // ... its step counters by workgroup number [POP_MAX * 2], the call's hyper-parameters on the device [POP_MAX], the diagnostic
+    // log-probability buffer the NEXT update takes and forgets
+    int32_t *d_ppo_t = nullptr; ranenv_ppo_hparams *d_ppo_hp = nullptr; float *ppo_probe = nullptr;
+    // mixed: the packed floats of member m's net of role r on the device, [4][POP_MAX] (0: the role is not bound), written at that
+    // bind and at every re-bind under it
+    long long *d_ppo_floats = nullptr, ppo_floats[4][POP_MAX] = {};      // (... and the host copy the upload reads)
+    // wide: the parked rows of the workgroups, [workgroups][ppo_park_stride] floats, allocated at that bind (an outgrown one stays
+    // allocated, like the weights'), never by an update
+    float *d_ppo_park = nullptr; long long ppo_park_stride = 0, ppo_park_cap = 0;
     // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
     // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
     bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
@@ -2057,11 +2068,11 @@ int ranenv_set_population_member(ranenv_handle h, int32_t member, const ranenv_m
     }
     // while a mixed PPO binding is on, the member's new actor / critic pair of a kind keeps to the update's LDS plan: refused here, and
     // the member's weights, moments and counter stay as they are
-    for (int k = 0; h->ppo_on && h->ppo_mixed && k < 2; k++) {
+    for (int k = 0; h->ppo.mixed && k < 2; k++) {
         const ranenv::NetSlot &sa = h->nets[k][FORM_MEMBER], &sc = h->nets[2 + k][FORM_MEMBER];
         if (!sa.on || (!given[k] && !given[2 + k])) continue;
         const PolicyNet &a = given[k] ? ni[k] : sa.member[(size_t)member], *c = given[2 + k] ? &ni[2 + k] : (sc.on ? &sc.member[(size_t)member] : nullptr);
-        if (h->ppo_wide) {        // (the wide plan in its place, and the share of the scratch the bind gave every workgroup)
+        if (h->ppo.wide) {        // (the wide plan in its place, and the share of the scratch the bind gave every workgroup)
             if (const size_t lds = ppo_wide_lds_bytes(a, c); lds > (size_t)PPO_LDS_MAX)
                 return fail(h, RANENV_E_STATE, "member %d: its new %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the bound PPO update has %d",
                             member, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
@@ -2205,53 +2216,42 @@ static int opt_ensure(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
     return RANENV_OK;
 }
 
-// The slots the update trains, by role number: the serving ones (null: none bound), and the member count -- or what ranenv_ppo_bind
-// (mixed: ranenv_ppo_bind_mixed, whose LDS plan holds per member; wide: ranenv_ppo_bind_wide, which checks the wide plan in its place)
-// refuses.  No device call.
-static int ppo_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false, bool wide = false)
+// The slots the update trains, by role number -- the serving ones (null: none bound) -- and the member count, or what the bind of that
+// geometry refuses: ranenv_ppo_bind (mixed: ranenv_ppo_bind_mixed, whose LDS plan holds per member; wide: ranenv_ppo_bind_wide, which
+// checks the wide plan in its place), or (slices) ranenv_ppo_bind_slices -- the one-net inter pair, the intra actors per slice, the
+// intra critics per slice or none.  The two geometries differ in the forms they take, the two rule blocks; their place around the
+// inter pair's check is the order in which a caller who breaks two rules hears of them.  No device call.
+static int ppo_roles(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false, bool wide = false)
 {
     if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
     int n_pop = 0, n_one = 0;
     for (int r = 0; r < 4; r++) {
         slot[r] = h->serving(r);
-        if (slot[r] && slot[r]->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the PPO update does not train intra nets per slice (non-shared intra policies)");
-        if (slot[r]) (slot[r]->form == FORM_MEMBER ? n_pop : n_one) += 1;
+        if (!slot[r]) continue;
+        if (slices && slot[r]->form == FORM_MEMBER) return fail(h, RANENV_E_STATE, "the per-slice PPO update trains no population: the %s nets are bound per member", NET_ROLES[r].who);
+        if (!slices && slot[r]->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the PPO update does not train intra nets per slice (non-shared intra policies)");
+        (slot[r]->form == FORM_MEMBER ? n_pop : n_one) += 1;
     }
-    if (h->pop_mixed() && !mixed) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind does not train a mixed population: use ranenv_ppo_bind_mixed");
-    if (mixed && !h->pop_mixed()) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind_mixed trains a mixed population and no bound role is mixed: use ranenv_ppo_bind");
+    if (!slices && h->pop_mixed() && !mixed) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind does not train a mixed population: use ranenv_ppo_bind_mixed");
+    if (!slices && mixed && !h->pop_mixed()) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind_mixed trains a mixed population and no bound role is mixed: use ranenv_ppo_bind");
     if (!slot[0] || !slot[2]) return fail(h, RANENV_E_STATE, "the PPO update needs a bound inter actor and inter critic (ranenv_set_policy_network, ranenv_set_value_network)");
-    if (n_pop && n_one) return fail(h, RANENV_E_STATE, "the PPO update needs every net per member or every net single: a net the members share has no one owner");
+    if (slices) {       // the intra nets per slice, every one
+        if (!slot[1]) return fail(h, RANENV_E_STATE, "the per-slice PPO update needs intra actors per slice (ranenv_set_intra_policy_networks)");
+        for (int r = 1; r < 4; r += 2)
+            if (slot[r] && slot[r]->form != FORM_SLICE)
+                return fail(h, RANENV_E_STATE, "the per-slice PPO update needs the %s nets per slice: a net the slices share has no one owner", NET_ROLES[r].who);
+    } else if (n_pop && n_one)      // every net per member, or every net single
+        return fail(h, RANENV_E_STATE, "the PPO update needs every net per member or every net single: a net the members share has no one owner");
     members = n_pop ? h->pop.n : 1;
     for (int r = 0; r < 4; r++)
         if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
     return ppo_each_shape(slot, mixed, wide, members, [&](int m, int k, long long, size_t lds, long long) {
         if (lds <= (size_t)PPO_LDS_MAX) return (int)RANENV_OK;
-        if (wide) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
-        if (mixed) return fail(h, RANENV_E_STATE, "member %d: its %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", m, k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
-        return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
-    });
-}
-
-// The slots the per-slice update trains, by role number -- the one-net inter pair, the intra actors per slice, the intra critics per
-// slice or none -- or what ranenv_ppo_bind_slices refuses.  No device call.
-static int ppo_slice_roles(ranenv_handle h, ranenv::NetSlot *(&slot)[4], bool wide)
-{
-    if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
-    for (int r = 0; r < 4; r++) {
-        slot[r] = h->serving(r);
-        if (slot[r] && slot[r]->form == FORM_MEMBER) return fail(h, RANENV_E_STATE, "the per-slice PPO update trains no population: the %s nets are bound per member", NET_ROLES[r].who);
-    }
-    if (!slot[0] || !slot[2]) return fail(h, RANENV_E_STATE, "the PPO update needs a bound inter actor and inter critic (ranenv_set_policy_network, ranenv_set_value_network)");
-    if (!slot[1]) return fail(h, RANENV_E_STATE, "the per-slice PPO update needs intra actors per slice (ranenv_set_intra_policy_networks)");
-    for (int r = 1; r < 4; r += 2)
-        if (slot[r] && slot[r]->form != FORM_SLICE)
-            return fail(h, RANENV_E_STATE, "the per-slice PPO update needs the %s nets per slice: a net the slices share has no one owner", NET_ROLES[r].who);
-    for (int r = 0; r < 4; r++)
-        if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
-    return ppo_each_shape(slot, false, wide, 1, [&](int, int k, long long, size_t lds, long long) {
-        if (lds <= (size_t)PPO_LDS_MAX) return (int)RANENV_OK;
-        if (wide) return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for two 32-row buffers of the wide plan, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
-        return fail(h, RANENV_E_STATE, "the %s nets need %zu bytes of LDS for their 32-row activations of all layers, the update has %d", k ? "intra" : "inter", lds, (int)PPO_LDS_MAX);
+        char whose[40];      // (a member binding under either of its plans names the member)
+        if (!slices && (mixed || wide)) snprintf(whose, sizeof(whose), "member %d: its %s nets", m, k ? "intra" : "inter");
+        else snprintf(whose, sizeof(whose), "the %s nets", k ? "intra" : "inter");
+        return fail(h, RANENV_E_STATE, "%s need %zu bytes of LDS for %s, the update has %d", whose, lds,
+                    wide ? "two 32-row buffers of the wide plan" : "their 32-row activations of all layers", (int)PPO_LDS_MAX);
     });
 }
 
@@ -2269,36 +2269,24 @@ static int ppo_floats_upload(ranenv_handle h, hipStream_t s)
     return RANENV_OK;
 }
 
-// A binding call has replaced `slot`'s nets (member < 0: all of them): their moments and their (member, kind) step counters start
-// again, on the caller's stream -- or, where the slot has no moments of its size, the PPO binding ends.
+// A binding call has replaced `slot`'s nets (member < 0: all of them): their moments and their units' step counters start again, on
+// the caller's stream -- or, where the slot has no moments of its size, the PPO binding ends.  Under ranenv_ppo_bind_slices the inter
+// pair lives in the one-net slots and the intra pairs in the per-slice slots: a re-bound net of another form takes the nets out of
+// that form, which ends the binding too, and a per-slice bind replaces all S copies -- their moments and the S slice counters restart.
 static int ppo_head_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
 static int sac_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
-// ... under ranenv_ppo_bind_slices: the inter pair lives in the one-net slots, the intra pairs in the per-slice slots.  A re-bound net of
-// another form takes the nets out of the per-slice form, and a slot without moments of its size has outgrown the state: the binding
-// ends.  Else the slot's and its partner's moments restart -- of every slice: a per-slice bind replaces all S copies -- with the inter
-// counter or the S slice counters.
-static int ppo_slices_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
-{
-    const int kind = slot->role & 1;
-    if (slot->form != (kind ? FORM_SLICE : FORM_ONE) || !slot->opt || slot->cap > slot->opt_cap) { h->ppo_on = false; return RANENV_OK; }
-    ranenv::NetSlot *both[2] = {slot, &h->nets[slot->role ^ 2][slot->form]};
-    for (ranenv::NetSlot *x : both)
-        if (x->on && x->opt && x->cap <= x->opt_cap) HIP_TRY(h, hipMemsetAsync(x->opt, 0, sizeof(float) * 2 * (size_t)x->opt_cap, s));
-    HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + (kind ? 1 : 0), 0, sizeof(int32_t) * (size_t)(kind ? h->cfg.n_slices : 1), s));
-    return RANENV_OK;
-}
-
 static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s)
 {
     if (slot == &h->head || slot == &h->sac_q1 || slot == &h->sac_q2)
         if (const int rc = sac_rebound(h, slot, s); rc != RANENV_OK) return rc;
     if (slot == &h->head || slot == &h->head_value) return ppo_head_rebound(h, slot, s);
-    if (!h->ppo_on) return RANENV_OK;
+    const ranenv::PpoBinding b = h->ppo;
+    if (!b.on) return RANENV_OK;
     if (slot->role < 0) return RANENV_OK;      // (a net the update never trains)
-    if (h->ppo_slices) return ppo_slices_rebound(h, slot, s);
-    if (slot->form == FORM_SLICE) return RANENV_OK;      // (... nor does this binding train the nets per slice)
+    if (!b.slices && slot->form == FORM_SLICE) return RANENV_OK;      // (... nor does a member binding train the nets per slice)
     const int kind = slot->role & 1;
-    if (!slot->opt || slot->cap > slot->opt_cap) { h->ppo_on = false; return RANENV_OK; }
+    if ((b.slices && slot->form != (kind ? FORM_SLICE : FORM_ONE)) || !slot->opt || slot->cap > slot->opt_cap) { h->ppo = {}; return RANENV_OK; }
+    if (b.slices) member = -1;
     // (actor and critic of a kind share the step counter: the partner net -- critic of an actor, actor of a critic -- restarts with it,
     //  or its old moments would meet the bias correction of t = 1)
     ranenv::NetSlot *both[2] = {slot, &h->nets[slot->role ^ 2][slot->form]};
@@ -2309,27 +2297,29 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
             continue;
         }
         // (a mixed binding: the member's WHOLE extent -- another shape moves every offset, and no moment of the old one may stay in the tail)
-        const size_t at = (size_t)member * (size_t)x->member_stride, n = (size_t)(h->ppo_mixed ? x->member_stride : net_floats(x->net));
+        const size_t at = (size_t)member * (size_t)x->member_stride, n = (size_t)(b.mixed ? x->member_stride : net_floats(x->net));
         HIP_TRY(h, hipMemsetAsync(x->opt + at, 0, sizeof(float) * n, s));
         HIP_TRY(h, hipMemsetAsync(x->opt + x->opt_cap + at, 0, sizeof(float) * n, s));
     }
-    if (member < 0) HIP_TRY(h, hipMemset2DAsync(h->d_ppo_t + kind, 2 * sizeof(int32_t), 0, sizeof(int32_t), POP_MAX, s));
-    else HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + member * 2 + kind, 0, sizeof(int32_t), s));
-    return h->ppo_mixed ? ppo_floats_upload(h, s) : RANENV_OK;
+    // the counters of the kind's units: the slices' lie side by side, the members' two apart
+    if (b.slices) HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + b.wg(kind, 0), 0, sizeof(int32_t) * (size_t)b.units(kind, 1, h->cfg.n_slices), s));
+    else if (member < 0) HIP_TRY(h, hipMemset2DAsync(h->d_ppo_t + b.wg(kind, 0), 2 * sizeof(int32_t), 0, sizeof(int32_t), POP_MAX, s));
+    else HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + b.wg(kind, member), 0, sizeof(int32_t), s));
+    return b.mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide / ranenv_ppo_bind_slices (slices: one member, 1 + S workgroups)
-static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream, bool slices = false)
+// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide / ranenv_ppo_bind_slices
+static int ppo_bind(ranenv_handle h, ranenv::PpoBinding b, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 1;
-    if (const int rc = slices ? ppo_slice_roles(h, slot, wide) : ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, b.slices, slot, members, b.mixed, b.wide); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    const int wgs = slices ? 1 + h->cfg.n_slices : 2 * members;      // the workgroups of an update launch
-    if (wide) {         // the parked rows: the largest need over the members and the kinds, for every workgroup
-        const long long need = ppo_plan(slot, mixed, true, members).park * wgs;
+    if (b.wide) {       // the parked rows: the largest need over the members and the kinds, for every workgroup
+        const int wgs = b.workgroups(members, h->cfg.n_slices);
+        const long long need = ppo_plan(slot, b.mixed, true, members).park * wgs;
         if (h->ppo_park_cap < need) {
             if (const int rc = dev_alloc(h, &h->d_ppo_park, (size_t)need); rc != RANENV_OK) return rc;
             h->ppo_park_cap = need;
@@ -2341,63 +2331,54 @@ static int ppo_bind(ranenv_handle h, bool mixed, bool wide, void *stream, bool s
         if (const int rc = dev_alloc(h, &h->d_ppo_t, (size_t)POP_MAX * 2); rc != RANENV_OK) return rc;
         if (const int rc = dev_alloc(h, &h->d_ppo_hp, (size_t)POP_MAX); rc != RANENV_OK) return rc;
     }
-    if (mixed && !h->d_ppo_floats)
+    if (b.mixed && !h->d_ppo_floats)
         if (const int rc = dev_alloc(h, &h->d_ppo_floats, (size_t)4 * POP_MAX); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipMemsetAsync(h->d_ppo_t, 0, sizeof(int32_t) * POP_MAX * 2, s));
     for (int r = 0; r < 4; r++)
         if (slot[r])
             if (const int rc = opt_ensure(h, slot[r], s); rc != RANENV_OK) return rc;
-    h->ppo_on = true; h->ppo_mixed = mixed; h->ppo_wide = wide; h->ppo_slices = slices;
-    return mixed ? ppo_floats_upload(h, s) : RANENV_OK;
+    h->ppo = b;
+    return b.mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-int ranenv_ppo_bind(ranenv_handle h, void *stream) { return ppo_bind(h, false, false, stream); }
-int ranenv_ppo_bind_mixed(ranenv_handle h, void *stream) { return ppo_bind(h, true, false, stream); }
+int ranenv_ppo_bind(ranenv_handle h, void *stream) { return ppo_bind(h, {true, false, false, false}, stream); }
+int ranenv_ppo_bind_mixed(ranenv_handle h, void *stream) { return ppo_bind(h, {true, true, false, false}, stream); }
 int ranenv_ppo_bind_wide(ranenv_handle h, int32_t mixed, void *stream)
 {
     if (mixed != 0 && mixed != 1) return fail(h, RANENV_E_INVALID, "mixed %d (0 as ranenv_ppo_bind, 1 as ranenv_ppo_bind_mixed)", mixed);
-    return ppo_bind(h, mixed == 1, true, stream);
+    return ppo_bind(h, {true, mixed == 1, true, false}, stream);
 }
-
-// The bound state behind ranenv_ppo_bind / _bind_mixed, or RANENV_E_STATE
-static int ppo_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4], int &members)
-{
-    if (!h->ppo_on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
-    if (h->ppo_slices) return fail(h, RANENV_E_STATE, "the PPO state was bound per slice (ranenv_ppo_bind_slices): ranenv_ppo_update_slices trains it");
-    if (const int rc = ppo_roles(h, slot, members, h->ppo_mixed, h->ppo_wide); rc != RANENV_OK) return rc;
-    for (int r = 0; r < 4; r++)
-        if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after ranenv_ppo_bind: bind again", NET_ROLES[r].who);
-    if (!h->ppo_wide) return RANENV_OK;
-    // a wide binding: every workgroup's parked rows fit the share of the scratch it was given at bind
-    if ((long long)members * 2 * h->ppo_park_stride > h->ppo_park_cap) return fail(h, RANENV_E_STATE, "the population has grown since ranenv_ppo_bind_wide: bind again");
-    return ppo_each_shape(slot, h->ppo_mixed, true, members, [&](int, int k, long long, size_t, long long p) {
-        if (p <= h->ppo_park_stride) return (int)RANENV_OK;
-        return fail(h, RANENV_E_STATE, "the %s nets park %lld floats of rows per workgroup, ranenv_ppo_bind_wide allocated %lld: bind again", k ? "intra" : "inter", p, h->ppo_park_stride);
-    });
-}
-
-// ---- non-shared intra policies (include/ranenv.h "per slice"): ranenv_ppo_bind_slices / ranenv_ppo_update_slices ------------------
+// (non-shared intra policies, include/ranenv.h "per slice")
 int ranenv_ppo_bind_slices(ranenv_handle h, int32_t wide, void *stream)
 {
     if (wide != 0 && wide != 1) return fail(h, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
-    return ppo_bind(h, false, wide == 1, stream, true);
+    return ppo_bind(h, {true, false, wide == 1, true}, stream);
 }
 
-// The bound state behind ranenv_ppo_bind_slices, or RANENV_E_STATE
-static int ppo_slices_bound(ranenv_handle h, ranenv::NetSlot *(&slot)[4])
+// The bound state behind the binding of the caller's geometry (slices: ranenv_ppo_bind_slices, else one of the member bindings), or
+// RANENV_E_STATE
+static int ppo_bound(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], int &members)
 {
-    if (!h->ppo_on || !h->ppo_slices) return fail(h, RANENV_E_STATE, "no per-slice PPO state bound, or a binding call has outgrown it or left the per-slice form: bind again (ranenv_ppo_bind_slices)");
+    const ranenv::PpoBinding &b = h->ppo;
+    if (slices) {
+        if (!b.on || !b.slices) return fail(h, RANENV_E_STATE, "no per-slice PPO state bound, or a binding call has outgrown it or left the per-slice form: bind again (ranenv_ppo_bind_slices)");
+        for (int r = 0; r < 4; r++)
+            if (const ranenv::NetSlot *x = h->serving(r); (r == 1 && !x) || (x && x->form != ((r & 1) ? FORM_SLICE : FORM_ONE)))
+                return fail(h, RANENV_E_STATE, "the %s nets have left the per-slice form since ranenv_ppo_bind_slices: bind again", NET_ROLES[r].who);
+    } else {
+        if (!b.on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
+        if (b.slices) return fail(h, RANENV_E_STATE, "the PPO state was bound per slice (ranenv_ppo_bind_slices): ranenv_ppo_update_slices trains it");
+    }
+    if (const int rc = ppo_roles(h, slices, slot, members, b.mixed, b.wide); rc != RANENV_OK) return rc;
     for (int r = 0; r < 4; r++)
-        if (const ranenv::NetSlot *x = h->serving(r); (r == 1 && !x) || (x && x->form != ((r & 1) ? FORM_SLICE : FORM_ONE)))
-            return fail(h, RANENV_E_STATE, "the %s nets have left the per-slice form since ranenv_ppo_bind_slices: bind again", NET_ROLES[r].who);
-    if (const int rc = ppo_slice_roles(h, slot, h->ppo_wide); rc != RANENV_OK) return rc;
-    for (int r = 0; r < 4; r++)
-        if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after ranenv_ppo_bind_slices: bind again", NET_ROLES[r].who);
-    if (!h->ppo_wide) return RANENV_OK;
-    if ((long long)(1 + h->cfg.n_slices) * h->ppo_park_stride > h->ppo_park_cap) return fail(h, RANENV_E_STATE, "the parked rows were allocated for another binding: bind again");
-    return ppo_each_shape(slot, false, true, 1, [&](int, int k, long long, size_t, long long p) {
+        if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after %s: bind again", NET_ROLES[r].who, b.entry());
+    if (!b.wide) return RANENV_OK;
+    // a wide binding: every workgroup's parked rows fit the share of the scratch it was given at bind
+    if ((long long)b.workgroups(members, h->cfg.n_slices) * h->ppo_park_stride > h->ppo_park_cap)
+        return fail(h, RANENV_E_STATE, slices ? "the parked rows were allocated for another binding: bind again" : "the population has grown since ranenv_ppo_bind_wide: bind again");
+    return ppo_each_shape(slot, b.mixed, true, members, [&](int, int k, long long, size_t, long long p) {
         if (p <= h->ppo_park_stride) return (int)RANENV_OK;
-        return fail(h, RANENV_E_STATE, "the %s nets park %lld floats of rows per workgroup, ranenv_ppo_bind_slices allocated %lld: bind again", k ? "intra" : "inter", p, h->ppo_park_stride);
+        return fail(h, RANENV_E_STATE, "the %s nets park %lld floats of rows per workgroup, %s allocated %lld: bind again", k ? "intra" : "inter", p, b.entry(true), h->ppo_park_stride);
     });
 }
 
@@ -2416,8 +2397,8 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide;
-    if (const int rc = h->ppo_on && h->ppo_slices ? ppo_slice_roles(h, slot, wide) : ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    const bool mixed = h->pop_mixed(), wide = h->ppo.wide;
+    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide); rc != RANENV_OK) return rc;
     const PpoPlan plan = ppo_plan(slot, mixed, wide, members);
     if (grad_floats) *grad_floats = plan.grad_floats;
     if (lds_bytes) *lds_bytes = (int64_t)plan.lds;
@@ -2429,9 +2410,9 @@ int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int6
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 0;
-    const bool mixed = h->pop_mixed(), wide = h->ppo_on && h->ppo_wide, slices = h->ppo_on && h->ppo_slices;
-    if (const int rc = slices ? ppo_slice_roles(h, slot, wide) : ppo_roles(h, slot, members, mixed, wide); rc != RANENV_OK) return rc;
-    if (slices) members = kind == 1 ? h->cfg.n_slices : 1;      // (the slices' pairs have one shape: slice 0's entry answers for all)
+    const bool mixed = h->pop_mixed(), wide = h->ppo.wide;
+    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    members = h->ppo.units(kind, members, h->cfg.n_slices);      // (the slices' pairs have one shape: slice 0's entry answers for all)
     if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
     if (kind != 0 && kind != 1) return fail(h, RANENV_E_INVALID, "kind %d (0 inter, 1 intra)", kind);
     if (!slot[kind]) return fail(h, RANENV_E_STATE, "no %s actor bound", kind ? "intra" : "inter");
@@ -2479,23 +2460,6 @@ int ranenv_ppo_wide_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int
     return RANENV_OK;
 }
 
-int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
-{
-    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
-    ranenv::NetSlot *slot[4];
-    int members = 0;
-    if (const int rc = ppo_bound(h, slot, members); rc != RANENV_OK) return rc;
-    if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
-    if (!slot[role]) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
-    const size_t at = (size_t)member * (size_t)slot[role]->member_stride;
-    if (dev_m) *dev_m = slot[role]->opt + at;
-    if (dev_v) *dev_v = slot[role]->opt + slot[role]->opt_cap + at;
-    if (dev_t) *dev_t = h->d_ppo_t + member * 2 + (role & 1);
-    if (floats) *floats = net_floats(slot[role]->member[h->ppo_mixed ? (size_t)member : 0]);
-    return RANENV_OK;
-}
-
 int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
@@ -2514,99 +2478,85 @@ static int ppo_record_check(ranenv_handle h, int32_t n_steps, const ranenv_traje
     return RANENV_OK;
 }
 
-int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, int32_t n_members, const ranenv_ppo_hparams *hp,
-                      const int32_t *order_inter, const int32_t *first_inter, const int32_t *order_intra, const int32_t *first_intra, double *stats,
-                      float *grad, void *stream)
+// THE update behind ranenv_ppo_update and ranenv_ppo_update_slices, which bring their arguments into one form: per kind the row list
+// `order[k]` (null: the kind is not trained) and `first[k]`, unit u's share [first[k][u], first[k][u + 1]) of every epoch's row of it
+// -- the units of the binding's geometry -- and `n_hp` hyper-parameter sets, one per member (slices: one for all units).
+static int ppo_update(ranenv_handle h, bool slices, int32_t n_steps, const ranenv_trajectory *traj, int32_t n_hp, const ranenv_ppo_hparams *hp,
+                      const int32_t *const (&order)[2], const int32_t *const (&first)[2], double *stats, float *grad, void *stream)
 {
-    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     float *const probe_logp = h->ppo_probe;
     h->ppo_probe = nullptr;          // (armed for ONE update, served or refused: the handle keeps no caller's pointer beyond it)
     ranenv::NetSlot *slot[4];
     int members = 0;
-    if (const int rc = ppo_bound(h, slot, members); rc != RANENV_OK) return rc;
-    if (n_steps < 1 || !traj || !hp || !order_inter || !first_inter || !stats) return fail(h, RANENV_E_INVALID, "n_steps >= 1, the record, the hyper-parameters, the inter row lists and dev_stats are required");
-    if (n_members != members) return fail(h, RANENV_E_INVALID, "%d members given, the bound nets have %d", n_members, members);
-    const bool intra = order_intra != nullptr;
-    if (intra && !first_intra) return fail(h, RANENV_E_INVALID, "intra row lists without host_first_intra");
+    if (const int rc = ppo_bound(h, slices, slot, members); rc != RANENV_OK) return rc;
+    const ranenv::PpoBinding &b = h->ppo;
+    const int S = h->cfg.n_slices;
+    if (n_steps < 1 || !traj || !hp || !order[0] || !first[0] || !stats)
+        return fail(h, RANENV_E_INVALID, "n_steps >= 1, the record, the hyper-parameters, the inter row list%s and dev_stats are required", slices ? "" : "s");
+    if (slices && first[0][1] < 0) return fail(h, RANENV_E_INVALID, "n_inter %d (>= 0)", first[0][1]);
+    if (n_hp != members) return fail(h, RANENV_E_INVALID, "%d members given, the bound nets have %d", n_hp, members);
+    const bool intra = order[1] != nullptr;
+    if (intra && !first[1]) return fail(h, RANENV_E_INVALID, "intra row lists without host_first_%s", slices ? "slice" : "intra");
     if (intra && !slot[1]) return fail(h, RANENV_E_INVALID, "intra row lists but no intra actor is bound");
     int max_epochs = 0;
-    for (int m = 0; m < members; m++) {
-        if (hp[m].minibatch < 1) return fail(h, RANENV_E_INVALID, "member %d: minibatch %d (>= 1)", m, hp[m].minibatch);
-        if (hp[m].epochs < 0) return fail(h, RANENV_E_INVALID, "member %d: epochs %d (>= 0)", m, hp[m].epochs);
+    for (int m = 0; m < n_hp; m++) {
+        char whose[24] = "";
+        if (!slices) snprintf(whose, sizeof(whose), "member %d: ", m);
+        if (hp[m].minibatch < 1) return fail(h, RANENV_E_INVALID, "%sminibatch %d (>= 1)", whose, hp[m].minibatch);
+        if (hp[m].epochs < 0) return fail(h, RANENV_E_INVALID, "%sepochs %d (>= 0)", whose, hp[m].epochs);
         max_epochs = hp[m].epochs > max_epochs ? hp[m].epochs : max_epochs;
     }
-    const bool mixed = h->ppo_mixed, wide = h->ppo_wide;
     if (const int rc = ppo_record_check(h, n_steps, traj, intra ? slot[1] : nullptr); rc != RANENV_OK) return rc;
     PpoArgs a{};
     for (int k = 0; k < (intra ? 2 : 1); k++) {
-        const int32_t *first = k ? first_intra : first_inter;
-        if (first[0] != 0) return fail(h, RANENV_E_INVALID, "host_first_%s[0] is %d, not 0", k ? "intra" : "inter", first[0]);
-        for (int m = 0; m < members; m++)
-            if (first[m + 1] < first[m]) return fail(h, RANENV_E_INVALID, "host_first_%s decreases at member %d", k ? "intra" : "inter", m);
-        for (int m = 0; m <= members; m++) a.first[k][m] = first[m];
-        a.order[k] = k ? order_intra : order_inter; a.order_stride[k] = first[members];
+        const int units = b.units(k, members, S);
+        const char *list = slices ? "slice" : (k ? "intra" : "inter");
+        if (first[k][0] != 0) return fail(h, RANENV_E_INVALID, "host_first_%s[0] is %d, not 0", list, first[k][0]);
+        for (int u = 0; u < units; u++)
+            if (first[k][u + 1] < first[k][u]) return fail(h, RANENV_E_INVALID, "host_first_%s decreases at %s %d", list, slices ? "slice" : "member", u);
+        for (int u = 0; u <= units; u++) a.first[k][u] = first[k][u];
+        a.order[k] = order[k]; a.order_stride[k] = first[k][units];
         a.net[k][0] = ppo_net(slot[k]); a.net[k][1] = ppo_net(slot[2 + k]);
     }
     if (max_epochs == 0) return RANENV_OK;
-    a.T = n_steps; a.B = h->cfg.batch; a.S = h->cfg.n_slices; a.Us = h->cfg.max_ues_slice; a.W = 2 * a.Us + 9;
+    a.T = n_steps; a.B = h->cfg.batch; a.S = S; a.Us = h->cfg.max_ues_slice; a.W = 2 * a.Us + 9;
     a.hp = h->d_ppo_hp; a.traj = *traj; a.t = h->d_ppo_t; a.max_epochs = max_epochs; a.stats = stats; a.grad = grad; a.probe_logp = probe_logp;
     // The launch's LDS: the largest need over the kinds this call updates (a mixed binding: and over the members).  dev_grad's stride
     // is ranenv_ppo_layout's: the largest of the BOUND nets, whether or not this call updates the intra kind
-    const PpoPlan plan = ppo_plan(slot, mixed, wide, members, intra ? 2 : 1);
+    const PpoPlan plan = ppo_plan(slot, b.mixed, b.wide, members, intra ? 2 : 1);
     a.grad_stride = plan.grad_floats;
     PpoMixed x{};
-    if (mixed) {        // (every bound role is the population's: its table; the others the table of zeros)
+    if (b.mixed) {      // (every bound role is the population's: its table; the others the table of zeros)
         for (int k = 0; k < 2; k++)
             for (int i = 0; i < 2; i++) x.tab[k][i] = h->d_pop_tab + (slot[2 * i + k] ? 2 * i + k : 4) * POP_MAX;
         x.floats = h->d_ppo_floats;
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)members, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)n_hp, hipMemcpyHostToDevice, s));
     const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_bound: every workgroup's rows fit its share)
-    HIP_TRY(h, launch_ppo_update(s, members, plan.lds, a, mixed ? &x : nullptr, wide ? &y : nullptr));
+    if (slices) HIP_TRY(h, launch_ppo_update_slices(s, intra ? S : 0, plan.lds, a, b.wide ? &y : nullptr));
+    else HIP_TRY(h, launch_ppo_update(s, members, plan.lds, a, b.mixed ? &x : nullptr, b.wide ? &y : nullptr));
     return RANENV_OK;
 }
 
-// ranenv_ppo_update_slices: ranenv_ppo_update's checks and arguments in the per-slice geometry -- "member" s of kind 1 is slice s
+int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, int32_t n_members, const ranenv_ppo_hparams *hp,
+                      const int32_t *order_inter, const int32_t *first_inter, const int32_t *order_intra, const int32_t *first_intra, double *stats,
+                      float *grad, void *stream)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    const int32_t *const order[2] = {order_inter, order_intra}, *const first[2] = {first_inter, first_intra};
+    return ppo_update(h, false, n_steps, traj, n_members, hp, order, first, stats, grad, stream);
+}
+
+// ranenv_ppo_update_slices: the per-slice geometry -- unit s of kind 1 is slice s, and the one inter unit's share is all n_inter rows
 int ranenv_ppo_update_slices(ranenv_handle h, int32_t n_steps, const ranenv_trajectory *traj, const ranenv_ppo_hparams *hp, const int32_t *order_inter,
                              int32_t n_inter, const int32_t *order_intra, const int32_t *first_slice, double *stats, float *grad, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
-    float *const probe_logp = h->ppo_probe;
-    h->ppo_probe = nullptr;          // (armed for ONE update, served or refused)
-    ranenv::NetSlot *slot[4];
-    if (const int rc = ppo_slices_bound(h, slot); rc != RANENV_OK) return rc;
-    if (n_steps < 1 || !traj || !hp || !order_inter || !stats) return fail(h, RANENV_E_INVALID, "n_steps >= 1, the record, the hyper-parameters, the inter row list and dev_stats are required");
-    if (n_inter < 0) return fail(h, RANENV_E_INVALID, "n_inter %d (>= 0)", n_inter);
-    const bool intra = order_intra != nullptr;
-    if (intra && !first_slice) return fail(h, RANENV_E_INVALID, "intra row lists without host_first_slice");
-    if (hp->minibatch < 1) return fail(h, RANENV_E_INVALID, "minibatch %d (>= 1)", hp->minibatch);
-    if (hp->epochs < 0) return fail(h, RANENV_E_INVALID, "epochs %d (>= 0)", hp->epochs);
-    if (const int rc = ppo_record_check(h, n_steps, traj, intra ? slot[1] : nullptr); rc != RANENV_OK) return rc;
-    const int S = h->cfg.n_slices;
-    PpoArgs a{};
-    a.first[0][1] = n_inter; a.order[0] = order_inter; a.order_stride[0] = n_inter;
-    a.net[0][0] = ppo_net(slot[0]); a.net[0][1] = ppo_net(slot[2]);
-    if (intra) {
-        if (first_slice[0] != 0) return fail(h, RANENV_E_INVALID, "host_first_slice[0] is %d, not 0", first_slice[0]);
-        for (int sl = 0; sl < S; sl++)
-            if (first_slice[sl + 1] < first_slice[sl]) return fail(h, RANENV_E_INVALID, "host_first_slice decreases at slice %d", sl);
-        for (int sl = 0; sl <= S; sl++) a.first[1][sl] = first_slice[sl];
-        a.order[1] = order_intra; a.order_stride[1] = first_slice[S];
-        a.net[1][0] = ppo_net(slot[1]); a.net[1][1] = ppo_net(slot[3]);
-    }
-    if (hp->epochs == 0) return RANENV_OK;
-    a.T = n_steps; a.B = h->cfg.batch; a.S = S; a.Us = h->cfg.max_ues_slice; a.W = 2 * a.Us + 9;
-    a.hp = h->d_ppo_hp; a.traj = *traj; a.t = h->d_ppo_t; a.max_epochs = hp->epochs; a.stats = stats; a.grad = grad; a.probe_logp = probe_logp;
-    const PpoPlan plan = ppo_plan(slot, false, h->ppo_wide, 1, intra ? 2 : 1);
-    a.grad_stride = plan.grad_floats;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams), hipMemcpyHostToDevice, s));
-    const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_slices_bound: every workgroup's rows fit its share)
-    HIP_TRY(h, launch_ppo_update_slices(s, intra ? S : 0, plan.lds, a, h->ppo_wide ? &y : nullptr));
-    return RANENV_OK;
+    const int32_t first_inter[2] = {0, n_inter};
+    const int32_t *const order[2] = {order_inter, order_intra}, *const first[2] = {first_inter, first_slice};
+    return ppo_update(h, true, n_steps, traj, 1, hp, order, first, stats, grad, stream);
 }
 
 // A role's slot and the float offset of slice `slice`'s copy in it, for ranenv_get_slice_net_weights (roles 1 and 3 alone) and
@@ -2623,17 +2573,44 @@ static int slice_copy(ranenv_handle h, int32_t role, int32_t slice, bool intra_o
     return RANENV_OK;
 }
 
-int ranenv_ppo_slice_state(ranenv_handle h, int32_t role, int32_t slice, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
+// ranenv_ppo_state / ranenv_ppo_slice_state: unit `u`'s copy of `role`'s net in the bound state of that geometry -- the slot, the
+// float offset of the copy in it and the unit's step counter
+static int ppo_state_at(ranenv_handle h, bool slices, int32_t role, int32_t u, ranenv::NetSlot *&x, size_t &at, int32_t *&t)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     if (const int rc = role_check(h, role); rc != RANENV_OK) return rc;
-    ranenv::NetSlot *slot[4], *x = nullptr;
-    if (const int rc = ppo_slices_bound(h, slot); rc != RANENV_OK) return rc;
-    size_t at = 0;
-    if (const int rc = slice_copy(h, role, slice, false, x, at); rc != RANENV_OK) return rc;
+    ranenv::NetSlot *slot[4];
+    int members = 0;
+    if (const int rc = ppo_bound(h, slices, slot, members); rc != RANENV_OK) return rc;
+    if (slices) {
+        if (const int rc = slice_copy(h, role, u, false, x, at); rc != RANENV_OK) return rc;
+    } else {
+        if (u < 0 || u >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", u, members);
+        if (!slot[role]) return fail(h, RANENV_E_STATE, "no %s net bound", NET_ROLES[role].who);
+        x = slot[role]; at = (size_t)u * (size_t)x->member_stride;
+    }
+    t = h->d_ppo_t + h->ppo.wg(role & 1, u);
+    return RANENV_OK;
+}
+
+int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
+{
+    ranenv::NetSlot *x = nullptr; size_t at = 0; int32_t *t = nullptr;
+    if (const int rc = ppo_state_at(h, false, role, member, x, at, t); rc != RANENV_OK) return rc;
     if (dev_m) *dev_m = x->opt + at;
     if (dev_v) *dev_v = x->opt + x->opt_cap + at;
-    if (dev_t) *dev_t = h->d_ppo_t + ((role & 1) ? 1 + slice : 0);
+    if (dev_t) *dev_t = t;
+    if (floats) *floats = net_floats(x->member[h->ppo.mixed ? (size_t)member : 0]);
+    return RANENV_OK;
+}
+
+int ranenv_ppo_slice_state(ranenv_handle h, int32_t role, int32_t slice, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats)
+{
+    ranenv::NetSlot *x = nullptr; size_t at = 0; int32_t *t = nullptr;
+    if (const int rc = ppo_state_at(h, true, role, slice, x, at, t); rc != RANENV_OK) return rc;
+    if (dev_m) *dev_m = x->opt + at;
+    if (dev_v) *dev_v = x->opt + x->opt_cap + at;
+    if (dev_t) *dev_t = t;
     if (floats) *floats = net_floats(x->net);
     return RANENV_OK;
 }
