@@ -867,6 +867,45 @@ int ranenv_ppo_update_slices(ranenv_handle h, int32_t n_steps, const ranenv_traj
                              double *dev_stats, float *dev_grad, void *stream);
 int ranenv_get_slice_net_weights(ranenv_handle h, int32_t role, int32_t slice, ranenv_mlp *out, void *stream);
 int ranenv_ppo_slice_state(ranenv_handle h, int32_t role, int32_t slice, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats);
+/* One agent over the chip: every binding above gives a policy pair to ONE workgroup on ONE compute unit, which walks all rows and passes
+ * over all parameters alone.  A fifth, opt-in binding, "spread", trains ONE agent -- the one-net slots, or a population of one member --
+ * with every step of the update spread over the chip, for the batches ranenv_collect leaves a single agent (B 4096 x 64 TTIs: 262 144
+ * inter rows).
+ * ranenv_ppo_bind_spread: ranenv_ppo_bind's rules (wide 0) or ranenv_ppo_bind_wide's (wide 1; another value: RANENV_E_INVALID) in their
+ *   words -- inter actor and critic bound, float32, no nets per slice, no mixed population, no head policy, the pair within THE LDS PLAN
+ *   or THE WIDE PLAN -- and a population of more than one member: RANENV_E_STATE.  slabs outside 1..256: RANENV_E_INVALID.  Allocates,
+ *   beside the moments, gradient scratch and counters of ranenv_ppo_bind: per bound kind `slabs` gradient slabs of the pair's packed
+ *   floats (actor, then critic), zeroed, and wide 1 as many shares of parked rows (ranenv_ppo_spread_bytes: the two together); the
+ *   blocks' partial sums of squares, the slabs' row statistics and the epoch's running sums.  No update call allocates; an allocation
+ *   that fails (RANENV_E_NOMEM) leaves the earlier binding as it was.  A handle still has ONE binding of the IBSched nets: the later
+ *   bind call replaces the earlier one and restarts the optimiser.  Re-binding follows ranenv_ppo_bind's rules; a re-bound net that
+ *   needs more slab or parked floats than the bind allocated leaves ranenv_ppo_update RANENV_E_STATE until the next bind.
+ * ranenv_ppo_update under this binding (n_members 1; same arguments, validation, loss, per-row arithmetic, statistics and probe):
+ *   the two kinds are independent optimisers with steps_kind = epochs x ceil(N_kind / minibatch) optimiser steps each, and the call
+ *   enqueues three launches per step on `stream` until the kind with more steps is through -- no cooperative launch, no grid-wide
+ *   barrier, no flag, no atomics; order comes from launch order alone, and what a launch writes is read by later launches only.
+ *     the pass: min(tiles of the minibatch, slabs) workgroups of 256 threads per kind, a tile being 32 entries of the minibatch;
+ *       workgroup w walks tiles w, w + grid, ... in ascending order -- forward, loss gradient, backward as ranenv_ppo_update's tile --
+ *       and adds into slab w; the advantage mean and std of the minibatch are computed by every workgroup in the same order.
+ *     the reduce: elementwise over the kind's packed floats in blocks of 1024: g[i] = the used slabs' [i] summed in ascending slab
+ *       order in float32, the cells zeroed; per block a float64 sum of squares.
+ *     the apply: the joint norm = sqrt of the block sums added in ascending block order, the clip scale, Adam at counter t0 + step
+ *       (t0: the counter as the call found it), in place in the buffers the acting kernels read; the statistics of the slabs are added
+ *       in ascending slab order; dev_grad is the g of the kind's last step; the kind's last step stores the counter.
+ *   The result is a function of the inputs and of min(tiles, slabs) alone: a handle bound with more slabs than a minibatch has tiles
+ *   gives the bytes of one bound with exactly that many.  With one slab the tile order and the adds are ranenv_ppo_update's: dev_grad of
+ *   a one-minibatch call equals the plain binding's bit for bit.  The norm is summed in another order than the plain binding's, so
+ *   weights behind Adam agree with it to rounding, not to the bit.  For nets that fit both plans wide 1 gives wide 0's bytes.
+ *   ranenv_ppo_layout, _member_layout (member 0), _state, _probe_logp and ranenv_get_net_weights serve this binding as the plain one.
+ *   A minibatch of 32 rows or fewer stays one workgroup per kind in the pass: one tile's layers are not split over workgroups.
+ * ranenv_ppo_spread_bytes: 4 x slabs x (actor floats + critic floats + (wide: ranenv_ppo_wide_bytes' scratch_floats)) for ONE kind's
+ *   pair (critic NULL: none), without a handle; a handle with both kinds bound holds the two pairs' sum.
+ * ranenv_ppo_spread_plan: the geometry of one kind as the host computes it, without a handle: steps = epochs x ceil(n_rows / minibatch);
+ *   grid = min(ceil(min(minibatch, n_rows) / 32), slabs), the first minibatch's workgroups; tiles_last = the tiles of an epoch's last
+ *   (possibly short) minibatch.  n_rows 0: all three 0.  Any output may be NULL. */
+int ranenv_ppo_bind_spread(ranenv_handle h, int32_t slabs, int32_t wide, void *stream);
+int ranenv_ppo_spread_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t slabs, int32_t wide, int64_t *bytes);
+int ranenv_ppo_spread_plan(int64_t n_rows, int32_t minibatch, int32_t epochs, int32_t slabs, int64_t *steps, int32_t *grid, int32_t *tiles_last);
 
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,
  * results/gen_results.py:874-1022, kept as running sums so that a rollout needs no per-TTI read-back).  Per env 8

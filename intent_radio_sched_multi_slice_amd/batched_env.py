@@ -241,6 +241,17 @@ def ppo_wide_scratch_floats(actor_layers, critic_layers=None) -> int:
     return _ppo_wide_bytes(actor_layers, critic_layers)[1]
 
 
+def ppo_spread_bytes(actor_layers, critic_layers=None, slabs: int = 64, wide: bool = False) -> int:
+    """Device bytes ``ppo_bind(spread=True, slabs=slabs)`` allocates for ONE kind's actor / critic pair beside the moments
+    (ranenv_ppo_spread_bytes): ``slabs`` gradient slabs of the pair's packed floats and, ``wide=True``, as many shares of parked rows
+    (``ppo_wide_scratch_floats``).  A handle with both kinds bound holds the sum of the two pairs'.  Nets as for ``ppo_lds_bytes``."""
+    actor, critic = _ppo_shape_pair(actor_layers, critic_layers)
+    out = C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_ppo_spread_bytes(actor, critic, int(slabs), 1 if wide else 0, C.byref(out)), "ranenv_ppo_spread_bytes")
+    return out.value
+
+
 def population_means(result: Dict[str, np.ndarray], first_env) -> Dict[str, np.ndarray]:
     """Per-member means of what ``evaluate()`` returns: every float metric [B, n_episodes, ...] -> [G, ...], the mean over the
     member's envs and episodes (``np.mean`` of the member's block); integer entries ("scenario") are left out."""
@@ -254,6 +265,9 @@ PPO_ROW_EPOCHS_CAP = 1 << 20       # rows x epochs of ONE member (one compute un
 # no row count lowers.  The reference's search space needs 2048 / 8 x 20 = 5120 at the most, its default regime 320; at the 0.19 ms
 # ([64, 64]) .. 0.92 ms ([256, 256]) measured per 64-row step, 8192 steps are 1.6 s .. 7.5 s (an estimate; no launch of that length was measured)
 PPO_STEPS_CAP = 1 << 13
+# Under ppo_bind(spread=True) the rows of a minibatch are spread over the chip: no cap on rows x epochs (an int64 cannot be exceeded by
+# int32 rows x int32 epochs).  The steps cap stays: a step is three launches
+PPO_SPREAD_CAPS = (np.iinfo(np.int64).max, PPO_STEPS_CAP)
 
 
 def ppo_hparams(G: int, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, grad_clip, adv_norm, betas, eps):
@@ -937,7 +951,7 @@ class BatchedRanEnv:
     # -- the PPO update on the device (ranenv_ppo_bind / ranenv_ppo_update; include/ranenv.h "PPO update") ---------------------------
     PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP = PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP      # (per handle: an attribute of the instance overrides them)
 
-    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False) -> None:
+    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False, spread: bool = False, slabs: int = 64) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
         one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header).
         ``mixed=True`` (ranenv_ppo_bind_mixed): the population was bound with ``mixed=True`` -- members of differing shape -- and
@@ -953,7 +967,18 @@ class BatchedRanEnv:
         ``per_slice=True`` (ranenv_ppo_bind_slices), with or without ``wide``: the binding for non-shared intra policies -- one inter
         actor and critic, ``intra`` a list of S nets in ``set_policy_network`` and a list of S critics, or none, in
         ``set_value_network`` -- which ``ppo_update_per_slice`` trains, one workgroup per policy.  Every other binding refuses such
-        nets.  It excludes ``mixed`` and ``head``."""
+        nets.  It excludes ``mixed`` and ``head``.
+        ``spread=True`` (ranenv_ppo_bind_spread), with or without ``wide``: the binding for ONE agent on a large batch -- every
+        optimiser step of ``ppo_update`` is spread over the chip, the 32-row tiles of a minibatch over up to ``slabs`` (1..256)
+        workgroups per kind, each adding into a gradient slab of its own (``ppo_spread_bytes``); summed in a fixed order, so the
+        result depends on the inputs and on min(tiles, slabs) alone.  No population, no nets per slice: it excludes ``mixed``,
+        ``head`` and ``per_slice``."""
+        if spread and mixed:
+            raise ValueError("ppo_bind: spread and mixed exclude each other (the spread binding trains one agent, no population)")
+        if spread and head:
+            raise ValueError("ppo_bind: spread and head exclude each other (the head nets train under the plain plan)")
+        if spread and per_slice:
+            raise ValueError("ppo_bind: spread and per_slice exclude each other (the spread binding trains one shared intra pair)")
         if per_slice and (mixed or head):
             raise ValueError("ppo_bind: per_slice excludes mixed and head (no population of non-shared agents; the head pair has no slices)")
         if mixed and head:
@@ -961,16 +986,20 @@ class BatchedRanEnv:
         if wide and head:
             raise ValueError("ppo_bind: wide and head exclude each other (the head nets train under the plain plan)")
         with torch.cuda.device(self.device):
-            if per_slice:
+            if spread:
+                self._check(self._lib.ranenv_ppo_bind_spread(self._h, int(slabs), 1 if wide else 0, self._stream()), "ranenv_ppo_bind_spread")
+            elif per_slice:
                 self._check(self._lib.ranenv_ppo_bind_slices(self._h, 1 if wide else 0, self._stream()), "ranenv_ppo_bind_slices")
             elif wide:
                 self._check(self._lib.ranenv_ppo_bind_wide(self._h, 1 if mixed else 0, self._stream()), "ranenv_ppo_bind_wide")
             elif head:
                 self._check(self._lib.ranenv_ppo_bind_head(self._h, self._stream()), "ranenv_ppo_bind_head")
+                return                         # (beside the IBSched nets' binding: which one that is stays as it was)
             elif mixed:
                 self._check(self._lib.ranenv_ppo_bind_mixed(self._h, self._stream()), "ranenv_ppo_bind_mixed")
             else:
                 self._check(self._lib.ranenv_ppo_bind(self._h, self._stream()), "ranenv_ppo_bind")
+        self._ppo_spread = bool(spread)
 
     def ppo_member_layout(self, m: int, kind: str = "inter") -> Dict[str, int]:
         """What unpacks member ``m``'s block of ``ppo_update(grad=True)["grad"][m, kind]`` (ranenv_ppo_member_layout): the packed
@@ -1003,7 +1032,8 @@ class BatchedRanEnv:
         intra); ``grad=True`` adds "grad" [G, 2, floats], the last minibatch's unclipped packed gradient (actor, then critic), and
         ``probe_logp=True`` "logp" [T, B, S + 1], the log-probabilities the update re-evaluated.  A member works on ONE compute unit: more
         than ``PPO_ROW_EPOCHS_CAP`` rows x epochs or ``PPO_STEPS_CAP`` optimiser steps for one member is refused unless ``force`` -- such
-        a batch belongs to torch."""
+        a batch belongs to torch.  Under ``ppo_bind(spread=True)`` the rows are spread over the chip and only ``PPO_STEPS_CAP`` holds
+        (a step there is three launches)."""
         G = self._ppo_members()
         hp, epochs, minibatch = ppo_hparams(G, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, grad_clip, adv_norm, betas, eps)
         max_epochs = int(epochs.max())
@@ -1011,7 +1041,8 @@ class BatchedRanEnv:
             from .adapters import ppo_row_order
             first_env = self._population if G > 1 else [0, self.B]
             order = ppo_row_order(rec, first_env, max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec)
-        firsts = ppo_order_firsts(order, {"inter": G, "intra": G}, epochs, minibatch, (self.PPO_ROW_EPOCHS_CAP, self.PPO_STEPS_CAP), "ppo_update", force=force)
+        caps = (PPO_SPREAD_CAPS[0], self.PPO_STEPS_CAP) if getattr(self, "_ppo_spread", False) else (self.PPO_ROW_EPOCHS_CAP, self.PPO_STEPS_CAP)
+        firsts = ppo_order_firsts(order, {"inter": G, "intra": G}, epochs, minibatch, caps, "ppo_update", force=force)
         lists, _pi = self._ppo_lists(order, firsts), lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
         return self._ppo_launch("ranenv_ppo_update", lambda T, traj, stats, gbuf, stream: self._lib.ranenv_ppo_update(
             self._h, T, traj, G, hp, _ptr(lists["inter"]), _pi(firsts["inter"]), _ptr(lists.get("intra")), _pi(firsts["intra"]) if "intra" in firsts else None,

@@ -1,6 +1,6 @@
 """Build libranenv_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
-Eight objects, compiled in parallel, then linked:
+Nine objects, compiled in parallel, then linked:
   ranenv_step.hip x 3   the builds of the step kernel for row widths NP = 8, 10, 16 (-DRANENV_NP=...)
   ranenv_aux.hip        the small kernels (class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination,
                         bf16 weight packing)
@@ -10,7 +10,9 @@ Eight objects, compiled in parallel, then linked:
                         wide LDS plan -- expand one body, ranenv_ppo_body.hpp; a seventh trains the head policies, ranenv_ppo_update_head)
   ranenv_sac.hip        the SAC update (ranenv_sac_update: per gradient step a critic pass, an actor pass and two elementwise applies,
                         the rows of a minibatch spread over workgroups)
-                        Both are built from ranenv_ppo_parts.hpp, the one statement of every step they share: the backward pass and
+  ranenv_ppo_spread.hip the PPO update of ONE agent spread over the chip (ranenv_ppo_bind_spread: per optimiser step a pass of
+                        min(tiles, slabs) workgroups into gradient slabs of their own, an elementwise reduce and an elementwise apply)
+                        All three are built from ranenv_ppo_parts.hpp, the one statement of every step they share: the backward pass and
                         its dZ' walk, Adam's constants and element step, and the steps of a PPO minibatch (advantage mean and std,
                         row list, clipped surrogate, critic row, joint norm and clip, statistics)
   ranenv_host.cpp       the host side of the C ABI
@@ -30,13 +32,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 HDR = os.path.join(REPO, "include", "ranenv.h")
 OUT = os.path.join(HERE, "libranenv_hip.so")
-SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_body.hpp", "ranenv_ppo_parts.hpp", "ranenv_sac.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
+SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_body.hpp", "ranenv_ppo_parts.hpp", "ranenv_ppo_spread.hip", "ranenv_sac.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
 # (object name, source, extra flags)
 UNITS = (("step_np10", "ranenv_step.hip", ("-DRANENV_NP=10",)), ("step_np8", "ranenv_step.hip", ("-DRANENV_NP=8",)),
          ("step_np16", "ranenv_step.hip", ("-DRANENV_NP=16",)), ("aux", "ranenv_aux.hip", ()),
          # (the policy network's MFMA accumulators in VGPRs: the library's kernels use no AGPRs, tests/test_kernel_resources.py)
          ("policy", "ranenv_policy.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")), ("ppo", "ranenv_ppo.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")),
-         ("sac", "ranenv_sac.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")),
+         ("sac", "ranenv_sac.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")), ("ppo_spread", "ranenv_ppo_spread.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")),
          ("host", "ranenv_host.cpp", ()))
 CFLAGS = ("-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-pass-failed",
           "-ffp-contract=off",     # numpy rounds a*b and +c separately; fma() is written out where it is exact

@@ -152,18 +152,20 @@ struct ranenv {
     bool pop_bound() const { for (int r = 0; r < 4; r++) if (nets[r][FORM_MEMBER].on) return true; return false; }
     bool pop_mixed() const { for (int r = 0; r < 4; r++) if (nets[r][FORM_MEMBER].on && nets[r][FORM_MEMBER].mixed) return true; return false; }
     // THE PPO BINDING of the IBSched nets: what ranenv_ppo_bind (plain), _bind_mixed (mixed: a mixed population, each member on its own
-    // shape), _bind_wide (wide: the wide plan, with or without mixed) or _bind_slices (slices: one intra pair per slice, with or without
+    // shape), _bind_wide (wide: the wide plan, with or without mixed), _bind_slices (slices: one intra pair per slice, with or without
+    // wide) or _bind_spread (slabs > 0: ONE agent, every optimiser step spread over up to `slabs` workgroups per kind, with or without
     // wide) bound, and the geometry that follows from it, stated here alone.  A handle has one; a binding that ends is `{}` again, so
-    // no flag outlives `on`.  An update UNIT is what one workgroup trains: member m's pair of a kind, or (slices) the inter pair and
-    // slice s's intra pair.
+    // no flag outlives `on`.  An update UNIT is what one optimiser trains: member m's pair of a kind, or (slices) the inter pair and
+    // slice s's intra pair; a spread binding has the one member's two.
     struct PpoBinding {
         bool on = false, mixed = false, wide = false, slices = false;
+        int slabs = 0;                                                                                        // > 0: the spread binding
         int units(int kind, int members, int S) const { return slices ? (kind == 1 ? S : 1) : members; }      // ... of a kind
-        int workgroups(int members, int S) const { return slices ? 1 + S : 2 * members; }                    // ... of an update launch
-        // unit u of `kind` by workgroup number: its step counter in d_ppo_t and its share of the parked rows in d_ppo_park
+        int workgroups(int members, int S) const { return slabs ? 2 * slabs : (slices ? 1 + S : 2 * members); }      // ... of an update launch at most
+        // unit u of `kind` by workgroup number: its step counter in d_ppo_t and (not spread) its share of the parked rows in d_ppo_park
         int wg(int kind, int u) const { return slices ? (kind ? 1 + u : 0) : u * 2 + kind; }
         // the entry point the messages name (parked: where they speak of the parked rows, which ranenv_ppo_bind_wide allocates)
-        const char *entry(bool parked = false) const { return slices ? "ranenv_ppo_bind_slices" : (parked ? "ranenv_ppo_bind_wide" : "ranenv_ppo_bind"); }
+        const char *entry(bool parked = false) const { return slabs ? "ranenv_ppo_bind_spread" : (slices ? "ranenv_ppo_bind_slices" : (parked ? "ranenv_ppo_bind_wide" : "ranenv_ppo_bind")); }
     } ppo;
     // ... its step counters by workgroup number [POP_MAX * 2], the call's hyper-parameters on the device [POP_MAX], the diagnostic
     // log-probability buffer the NEXT update takes and forgets
@@ -174,6 +176,13 @@ struct ranenv {
     // wide: the parked rows of the workgroups, [workgroups][ppo_park_stride] floats, allocated at that bind (an outgrown one stays
     // allocated, like the weights'), never by an update
     float *d_ppo_park = nullptr; long long ppo_park_stride = 0, ppo_park_cap = 0;
+    // spread: the gradient slabs [2][slabs][the kind's actor + critic floats] (zero between two optimiser steps), and per kind the reduce
+    // blocks' sums of squares [ppo_spread_blocks], the pass workgroups' statistics [PPO_SPREAD_SLABS_MAX][PPO_SPREAD_STATS] and the
+    // epoch's running sums [RANENV_PPO_STATS] in one array of doubles; the parked rows (wide) lie in d_ppo_park, [2][slabs][the kind's
+    // need].  The call's copy of the two step counters: d_ppo_t[2], [3] (a spread binding has one member: [0], [1] are its counters).
+    // All allocated at the bind, never by an update
+    float *d_ppo_slab = nullptr; long long ppo_slab_cap = 0;
+    double *d_ppo_spread = nullptr; long long ppo_spread_blocks = 0;
     // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
     // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
     bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
@@ -2218,10 +2227,10 @@ static int opt_ensure(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
 
 // The slots the update trains, by role number -- the serving ones (null: none bound) -- and the member count, or what the bind of that
 // geometry refuses: ranenv_ppo_bind (mixed: ranenv_ppo_bind_mixed, whose LDS plan holds per member; wide: ranenv_ppo_bind_wide, which
-// checks the wide plan in its place), or (slices) ranenv_ppo_bind_slices -- the one-net inter pair, the intra actors per slice, the
+// checks the wide plan in its place; spread: ranenv_ppo_bind_spread, which takes one member alone), or (slices) ranenv_ppo_bind_slices -- the one-net inter pair, the intra actors per slice, the
 // intra critics per slice or none.  The two geometries differ in the forms they take, the two rule blocks; their place around the
 // inter pair's check is the order in which a caller who breaks two rules hears of them.  No device call.
-static int ppo_roles(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false, bool wide = false)
+static int ppo_roles(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false, bool wide = false, bool spread = false)
 {
     if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
     int n_pop = 0, n_one = 0;
@@ -2243,12 +2252,13 @@ static int ppo_roles(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], 
     } else if (n_pop && n_one)      // every net per member, or every net single
         return fail(h, RANENV_E_STATE, "the PPO update needs every net per member or every net single: a net the members share has no one owner");
     members = n_pop ? h->pop.n : 1;
+    if (spread && members > 1) return fail(h, RANENV_E_STATE, "the spread PPO update trains no population: the nets are bound per member and the population has %d", members);
     for (int r = 0; r < 4; r++)
         if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
     return ppo_each_shape(slot, mixed, wide, members, [&](int m, int k, long long, size_t lds, long long) {
         if (lds <= (size_t)PPO_LDS_MAX) return (int)RANENV_OK;
         char whose[40];      // (a member binding under either of its plans names the member)
-        if (!slices && (mixed || wide)) snprintf(whose, sizeof(whose), "member %d: its %s nets", m, k ? "intra" : "inter");
+        if (!slices && !spread && (mixed || wide)) snprintf(whose, sizeof(whose), "member %d: its %s nets", m, k ? "intra" : "inter");
         else snprintf(whose, sizeof(whose), "the %s nets", k ? "intra" : "inter");
         return fail(h, RANENV_E_STATE, "%s need %zu bytes of LDS for %s, the update has %d", whose, lds,
                     wide ? "two 32-row buffers of the wide plan" : "their 32-row activations of all layers", (int)PPO_LDS_MAX);
@@ -2308,16 +2318,47 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
     return b.mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
 
-// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide / ranenv_ppo_bind_slices
+// What a spread binding of these slots holds beside the moments: floats of gradient slabs and of parked rows (wide) -- per bound kind
+// `slabs` times the pair's need, the kinds back to back --, and the reduce / apply blocks of the larger kind.  The doubles of one
+// kind: block partials, slab statistics, running sums.
+struct PpoSpreadNeed { long long slab, park, blocks; };
+static PpoSpreadNeed ppo_spread_need(ranenv::NetSlot *const (&slot)[4], bool wide, int slabs)
+{
+    PpoSpreadNeed n{};
+    ppo_each_shape(slot, false, wide, 1, [&](int, int, long long floats, size_t, long long park) {
+        n.slab += floats * slabs; n.park += park * slabs;
+        n.blocks = std::max(n.blocks, (floats + PPO_SPREAD_BLOCK - 1) / PPO_SPREAD_BLOCK);
+        return (int)RANENV_OK;
+    });
+    return n;
+}
+static long long ppo_spread_doubles(long long blocks) { return blocks + PPO_SPREAD_SLABS_MAX * PPO_SPREAD_STATS + RANENV_PPO_STATS; }
+
+// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide / ranenv_ppo_bind_slices / ranenv_ppo_bind_spread
 static int ppo_bind(ranenv_handle h, ranenv::PpoBinding b, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 1;
-    if (const int rc = ppo_roles(h, b.slices, slot, members, b.mixed, b.wide); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, b.slices, slot, members, b.mixed, b.wide, b.slabs > 0); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    if (b.wide) {       // the parked rows: the largest need over the members and the kinds, for every workgroup
+    if (b.slabs) {      // the spread binding's own: slabs, block partials, slab statistics and running sums, and (wide) the parked rows per slab
+        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs);
+        if (h->ppo_slab_cap < need.slab) {
+            if (const int rc = dev_alloc(h, &h->d_ppo_slab, (size_t)need.slab); rc != RANENV_OK) return rc;
+            h->ppo_slab_cap = need.slab;
+        }
+        if (!h->d_ppo_spread || h->ppo_spread_blocks < need.blocks) {
+            if (const int rc = dev_alloc(h, &h->d_ppo_spread, 2 * (size_t)ppo_spread_doubles(need.blocks)); rc != RANENV_OK) return rc;
+            h->ppo_spread_blocks = need.blocks;
+        }
+        if (h->ppo_park_cap < need.park) {
+            if (const int rc = dev_alloc(h, &h->d_ppo_park, (size_t)need.park); rc != RANENV_OK) return rc;
+            h->ppo_park_cap = need.park;
+        }
+        HIP_TRY(h, hipMemsetAsync(h->d_ppo_slab, 0, sizeof(float) * (size_t)h->ppo_slab_cap, s));
+    } else if (b.wide) {       // the parked rows: the largest need over the members and the kinds, for every workgroup
         const int wgs = b.workgroups(members, h->cfg.n_slices);
         const long long need = ppo_plan(slot, b.mixed, true, members).park * wgs;
         if (h->ppo_park_cap < need) {
@@ -2354,6 +2395,13 @@ int ranenv_ppo_bind_slices(ranenv_handle h, int32_t wide, void *stream)
     if (wide != 0 && wide != 1) return fail(h, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
     return ppo_bind(h, {true, false, wide == 1, true}, stream);
 }
+// (one agent over the chip, include/ranenv.h "One agent over the chip")
+int ranenv_ppo_bind_spread(ranenv_handle h, int32_t slabs, int32_t wide, void *stream)
+{
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(h, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    if (wide != 0 && wide != 1) return fail(h, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
+    return ppo_bind(h, {true, false, wide == 1, false, slabs}, stream);
+}
 
 // The bound state behind the binding of the caller's geometry (slices: ranenv_ppo_bind_slices, else one of the member bindings), or
 // RANENV_E_STATE
@@ -2369,9 +2417,15 @@ static int ppo_bound(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], 
         if (!b.on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
         if (b.slices) return fail(h, RANENV_E_STATE, "the PPO state was bound per slice (ranenv_ppo_bind_slices): ranenv_ppo_update_slices trains it");
     }
-    if (const int rc = ppo_roles(h, slices, slot, members, b.mixed, b.wide); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, slices, slot, members, b.mixed, b.wide, b.slabs > 0); rc != RANENV_OK) return rc;
     for (int r = 0; r < 4; r++)
         if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after %s: bind again", NET_ROLES[r].who, b.entry());
+    if (b.slabs) {      // a spread binding: the slabs, block partials and parked rows of the nets as they stand fit what the bind allocated
+        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs);
+        if (need.slab > h->ppo_slab_cap || need.blocks > h->ppo_spread_blocks || need.park > h->ppo_park_cap)
+            return fail(h, RANENV_E_STATE, "the bound nets need more slab or parked floats than ranenv_ppo_bind_spread allocated: bind again");
+        return RANENV_OK;
+    }
     if (!b.wide) return RANENV_OK;
     // a wide binding: every workgroup's parked rows fit the share of the scratch it was given at bind
     if ((long long)b.workgroups(members, h->cfg.n_slices) * h->ppo_park_stride > h->ppo_park_cap)
@@ -2398,7 +2452,7 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
     ranenv::NetSlot *slot[4];
     int members = 0;
     const bool mixed = h->pop_mixed(), wide = h->ppo.wide;
-    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide, h->ppo.slabs > 0); rc != RANENV_OK) return rc;
     const PpoPlan plan = ppo_plan(slot, mixed, wide, members);
     if (grad_floats) *grad_floats = plan.grad_floats;
     if (lds_bytes) *lds_bytes = (int64_t)plan.lds;
@@ -2411,7 +2465,7 @@ int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int6
     ranenv::NetSlot *slot[4];
     int members = 0;
     const bool mixed = h->pop_mixed(), wide = h->ppo.wide;
-    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide, h->ppo.slabs > 0); rc != RANENV_OK) return rc;
     members = h->ppo.units(kind, members, h->cfg.n_slices);      // (the slices' pairs have one shape: slice 0's entry answers for all)
     if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
     if (kind != 0 && kind != 1) return fail(h, RANENV_E_INVALID, "kind %d (0 inter, 1 intra)", kind);
@@ -2460,6 +2514,31 @@ int ranenv_ppo_wide_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int
     return RANENV_OK;
 }
 
+int ranenv_ppo_spread_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t slabs, int32_t wide, int64_t *bytes)
+{
+    if (!actor || !bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(nullptr, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    if (wide != 0 && wide != 1) return fail(nullptr, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
+    PolicyNet net[2] = {};
+    if (const int rc = ppo_shape_pair(actor, critic, net); rc != RANENV_OK) return rc;
+    const long long floats = net_floats(net[0]) + (critic ? net_floats(net[1]) : 0);
+    *bytes = (int64_t)sizeof(float) * slabs * (floats + (wide ? ppo_wide_scratch(net[0], critic ? &net[1] : nullptr) : 0));
+    return RANENV_OK;
+}
+
+int ranenv_ppo_spread_plan(int64_t n_rows, int32_t minibatch, int32_t epochs, int32_t slabs, int64_t *steps, int32_t *grid, int32_t *tiles_last)
+{
+    if (n_rows < 0 || n_rows > 0x7fffffffLL) return fail(nullptr, RANENV_E_INVALID, "n_rows %lld (0..2^31 - 1)", (long long)n_rows);
+    if (minibatch < 1) return fail(nullptr, RANENV_E_INVALID, "minibatch %d (>= 1)", minibatch);
+    if (epochs < 0) return fail(nullptr, RANENV_E_INVALID, "epochs %d (>= 0)", epochs);
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(nullptr, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    const int n = (int)n_rows, per_epoch = ppo_spread_per_epoch(n, minibatch);
+    if (steps) *steps = (int64_t)epochs * per_epoch;
+    if (grid) *grid = n > 0 ? ppo_spread_step(n, minibatch, slabs, 0).grid : 0;
+    if (tiles_last) *tiles_last = n > 0 ? ppo_spread_step(n, minibatch, slabs, per_epoch - 1).tiles : 0;
+    return RANENV_OK;
+}
+
 int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
@@ -2475,6 +2554,41 @@ static int ppo_record_check(ranenv_handle h, int32_t n_steps, const ranenv_traje
     if (intra_actor && (!traj->obs_intra || !traj->action_intra || (intra_actor->net.layout == RANENV_NET_IN_MASK_OBS && !traj->mask_intra)))
         return fail(h, RANENV_E_INVALID, "the record needs obs_intra and action_intra (mask_intra for RANENV_NET_IN_MASK_OBS nets) for the intra rows");
     if ((long long)n_steps * h->cfg.batch * h->cfg.n_slices > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "the record has more than 2^31 - 1 intra rows");
+    return RANENV_OK;
+}
+
+// ranenv_ppo_update under a spread binding: `a` as the update below filled it (nets, lists, record, counters, outputs).  Per kind the
+// schedule's geometry and the kind's share of the binding's buffers, then three launches per optimiser step until the kind with more
+// steps is through; a kind the call does not train, or whose list is empty, has no steps.
+static int ppo_update_spread(ranenv_handle h, ranenv::NetSlot *const (&slot)[4], const PpoArgs &a, const ranenv_ppo_hparams &hp, bool intra, size_t lds, hipStream_t s)
+{
+    const ranenv::PpoBinding &b = h->ppo;
+    PpoSpreadArgs p{};
+    p.a = a; p.a.hp = nullptr; p.hp = hp; p.slabs = b.slabs;
+    float *slab = h->d_ppo_slab, *park = h->d_ppo_park;
+    long long steps = 0;
+    for (int k = 0; k < 2; k++) {
+        if (!slot[k]) continue;
+        PpoSpreadKind &K = p.k[k];
+        const PolicyNet *critic = slot[2 + k] ? &slot[2 + k]->net : nullptr;
+        const long long floats = net_floats(slot[k]->net) + (critic ? net_floats(*critic) : 0);
+        K.slab = slab; K.slab_stride = floats; slab += floats * b.slabs;
+        if (b.wide) { K.park = park; K.park_stride = ppo_wide_scratch(slot[k]->net, critic); park += K.park_stride * b.slabs; }
+        K.bpart = h->d_ppo_spread + k * ppo_spread_doubles(h->ppo_spread_blocks);
+        K.wstat = K.bpart + h->ppo_spread_blocks; K.run = K.wstat + PPO_SPREAD_SLABS_MAX * PPO_SPREAD_STATS;
+        K.t0 = h->d_ppo_t + 2 + k;
+        K.blocks = (int)((floats + PPO_SPREAD_BLOCK - 1) / PPO_SPREAD_BLOCK);
+        if (k == 1 && !intra) continue;
+        K.n = a.first[k][1];
+        const long long k_steps = (long long)hp.epochs * ppo_spread_per_epoch(K.n, hp.minibatch);
+        if (k_steps > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "%lld optimiser steps (epochs x minibatches of the %s kind): more than 2^31 - 1", k_steps, k ? "intra" : "inter");
+        K.steps = (int)k_steps;
+        steps = std::max(steps, k_steps);
+    }
+    for (long long i = 0; i < steps; i++) {
+        p.step = (int)i;
+        HIP_TRY(h, launch_ppo_spread_step(s, lds, p, b.wide));
+    }
     return RANENV_OK;
 }
 
@@ -2533,6 +2647,7 @@ static int ppo_update(ranenv_handle h, bool slices, int32_t n_steps, const ranen
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
+    if (b.slabs) return ppo_update_spread(h, slot, a, hp[0], intra, plan.lds, s);
     HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)n_hp, hipMemcpyHostToDevice, s));
     const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_bound: every workgroup's rows fit its share)
     if (slices) HIP_TRY(h, launch_ppo_update_slices(s, intra ? S : 0, plan.lds, a, b.wide ? &y : nullptr));

@@ -298,6 +298,44 @@ hipError_t launch_ppo_update(hipStream_t, int n_members, size_t lds, const PpoAr
 // workgroup 1 + s slice s's intra pair: net[1]'s copies at s * stride, entries [first[1][s], first[1][s + 1]) of the intra lists.  t, stats,
 // grad and the wide scratch are numbered by workgroup: [1 + S] in place of [members][2].  n_slices 0: the inter pair alone.
 hipError_t launch_ppo_update_slices(hipStream_t, int n_slices, size_t lds, const PpoArgs &, const PpoWide *wide);
+// ranenv_ppo_update under ranenv_ppo_bind_spread (ranenv_ppo_spread.hip; include/ranenv.h "One agent over the chip"): ONE agent's update,
+// three launches per optimiser step.  THE GEOMETRY of one kind's schedule, one function for the host (launch grids,
+// ranenv_ppo_spread_plan) and the three kernels: n rows in minibatches of `minibatch` entries, `epochs` times -- optimiser step `step`
+// is minibatch step % per_epoch of epoch step / per_epoch, entries [c0, c0 + nb) of the epoch's list, in `tiles` tiles of NET_ROWS rows
+// that `grid` = min(tiles, slabs) workgroups walk: workgroup w the tiles w, w + grid, ... into gradient slab w.
+enum { PPO_SPREAD_BLOCK = 1024,           // floats of a kind's packed gradient (actor, then critic) per block of the reduce and the apply
+       PPO_SPREAD_STATS = 6,              // doubles per slab: policy loss, entropy, logp_old - logp, clipped, live rows, value loss
+       PPO_SPREAD_SLABS_MAX = 256 };
+struct PpoSpreadStep { int ep, mb, c0, nb, tiles, grid; };
+__host__ __device__ inline int ppo_spread_per_epoch(int n, int minibatch) { return n > 0 ? (int)(((long long)n + minibatch - 1) / minibatch) : 0; }
+__host__ __device__ inline PpoSpreadStep ppo_spread_step(int n, int minibatch, int slabs, int step)
+{
+    PpoSpreadStep g;
+    const int per_epoch = ppo_spread_per_epoch(n, minibatch);
+    g.ep = step / per_epoch; g.mb = step - g.ep * per_epoch;
+    g.c0 = g.mb * minibatch; g.nb = n - g.c0 < minibatch ? n - g.c0 : minibatch;
+    g.tiles = (g.nb + NET_ROWS - 1) / NET_ROWS; g.grid = g.tiles < slabs ? g.tiles : slabs;
+    return g;
+}
+// One kind's share of the binding's buffers and of the call: every array is written by one launch and read by later ones alone
+struct PpoSpreadKind {
+    float *slab; long long slab_stride;   // [slabs][slab_stride]: the actor's packed gradient, then the critic's; zero between two steps
+    float *park; long long park_stride;   // wide: [slabs][park_stride] parked rows
+    double *bpart;                        // [blocks] the reduce blocks' sums of squares
+    double *wstat;                        // [slabs][PPO_SPREAD_STATS] the pass workgroups' row statistics
+    double *run;                          // [RANENV_PPO_STATS] the epoch's running sums between two steps (PpoEpoch's fields in order)
+    int32_t *t0;                          // the kind's step counter as the call found it (the first pass copies it)
+    int n, steps, blocks;                 // rows of an epoch's list, optimiser steps of the call (0: the kind is not updated), reduce / apply blocks
+};
+struct PpoSpreadArgs {
+    PpoArgs a;                            // nets, lists, record, counters t[kind], stats [2][max_epochs][RANENV_PPO_STATS], grad [2][grad_stride]; a.hp unused
+    ranenv_ppo_hparams hp;
+    PpoSpreadKind k[2];
+    int slabs, step;
+};
+// The three launches of optimiser step a.step (grid_pass / blocks: the larger kind's); wide: the pass under the wide plan
+hipError_t launch_ppo_spread_step(hipStream_t, size_t lds, const PpoSpreadArgs &, bool wide);
+
 // ranenv_ppo_update_head (include/ranenv.h "PPO update of the head policies"): the head actor and critic (net[0], net[1]; stride unused),
 // the handle's log_std [S] with its moments and gradient scratch, the call's hyper-parameters by value, the row lists
 // [max_epochs][n_rows] and the ranenv_collect_head record.  One workgroup.

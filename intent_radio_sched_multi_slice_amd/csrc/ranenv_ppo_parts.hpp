@@ -1,8 +1,9 @@
 // ranenv_ppo_parts.hpp -- the one statement of every step the training kernels share (ranenv_ppo.hip: the PPO updates of the bound nets
-// and of the head policies; ranenv_sac.hip: the SAC update): the LDS size of a net's rows, the backward pass of one 32-row tile on the
+// and of the head policies; ranenv_ppo_spread.hip: one agent's PPO update spread over the chip; ranenv_sac.hip: the SAC update): the LDS size of a net's rows, the backward pass of one 32-row tile on the
 // f32 matrix cores and its dZ' block walk, the workgroup sum in slot order, Adam's constants and float32 element step, and the steps
 // of a PPO minibatch -- zeroing, the advantages' mean and std, the tile's row list, the clipped surrogate, the critic row, the joint
-// norm and clip scale, the statistics, the gradient copy.  A rule that lives here (the 1e-6 of the clip, the 1e-8 of the std, the tie
+// norm and clip scale, the statistics, the gradient copy -- and the steps of a tile of the IBSched nets that the member update and the
+// spread update share: the record cell, the tile's input rows, the wide forward pass, the actor's row.  A rule that lives here (the 1e-6 of the clip, the 1e-8 of the std, the tie
 // rule of torch.minimum, Adam's operation order) has no second text.  ranenv_ppo.hip's header comment describes the plan they belong to.
 #pragma once
 #include "ranenv_net.hpp"
@@ -270,6 +271,105 @@ __device__ __forceinline__ void ppo_grad_out(float *out, const float *g, long lo
 {
 #pragma unroll 1
     for (long long i = tid; i < floats; i += 256) out[i] = g[i];
+}
+
+// ---- the steps of a tile of the IBSched nets (ranenv_ppo_body.hpp and the spread update, ranenv_ppo_spread.hip) -----------------------
+constexpr int PPO_FIXED = 4096;           // bytes of LDS in front of the rows: reduction slots, per-row statistics, the tile's record rows
+constexpr int PPO_ROW_STATS = 6;          // per row: policy loss, entropy, logp_old - logp, clipped?, live?, value loss
+
+// The (logp, adv, vtarg) cell of record row i: column 0 of the inter row, column s + 1 of the env's row for slice s
+__device__ __forceinline__ size_t ppo_cell(int kind, int i, int S) { return kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S); }
+
+// The tile's rows of `net`'s input -> buffer 0: row r is record row idx[r] (< 0: a dead row, zeros), read as net_load_rows reads an
+// env's row -- the inter observation, or the slice's observation behind, for RANENV_NET_IN_MASK_OBS, its mask as floats
+__device__ __forceinline__ void ppo_load_rows(const PolicyNet &net, const PpoArgs &A, int kind, const int *idx, float *dst, int tid)
+{
+    load_rows(net.kp[0], 0, 0, dst, tid, [&](int r, int k) {
+        const int i = idx[r];
+        if (i < 0 || k >= net.in_dim) return 0.0f;
+        if (kind == 0) return A.traj.obs_inter[(size_t)i * (size_t)(10 * A.S) + k];
+        const int ko = net.layout == RANENV_NET_IN_MASK_OBS ? k - A.Us : k;
+        if (ko < 0) return (float)A.traj.mask_intra[(size_t)i * A.Us + k];
+        return A.traj.obs_intra[(size_t)i * A.W + ko];
+    });
+}
+
+// The forward pass of one tile on the two buffers: the input rows lie at `base` behind a barrier.  Layer l parks its input rows in
+// slab l of `park` while it reads them (the barrier in front published them; nothing overwrites them before the layer's own barrier)
+// and writes the other buffer.  Returns the output layer's rows.
+__device__ __forceinline__ float *ppo_forward_wide(const PolicyNet &net, const float *w, float *base, float *top, float *park, int tid)
+{
+    float *in = base;
+    for (int l = 0; l < net.n_layers; l++) {
+        float *out = ppo_wide_buf(net, l + 1, base, top);
+        ppo_copy_rows(park, in, net.kp[l], tid);
+        net_layer_f32(net, l, w, in, out, tid & 63, tid >> 6);
+        __syncthreads();
+        park += NET_ROWS * net_ld(net.kp[l]);
+        in = out;
+    }
+    return in;
+}
+
+// The loss gradient at the actor's outputs for the tile's row r (thread r): `o` = the row's outputs, overwritten; the row's statistics
+__device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo_hparams &hp, int kind, int i, int np, float *o, double *rs, double wrow,
+                                              double a_mean, double a_den)
+{
+    const int S = A.S;
+    if (i < 0) {
+#pragma unroll 1
+        for (int j = 0; j < np; j++) o[j] = 0.0f;
+        rs[0] = rs[1] = rs[2] = rs[3] = rs[4] = 0.0;
+        return;
+    }
+    const size_t at = ppo_cell(kind, i, S);
+    const double lp_old = (double)A.traj.logp[at];
+    const double adv = hp.adv_norm ? ((double)A.traj.adv[at] - a_mean) / a_den : (double)A.traj.adv[at];
+    double lp = 0.0, ent = 0.0;
+    int j0 = 0, ch = 0;
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    if (kind == 0) {
+        int n_act = 0;
+#pragma unroll 1
+        for (int s = 0; s < S; s++) n_act += A.traj.mask_inter[(size_t)i * S + s] != 0 ? 1 : 0;
+        j0 = S - n_act;
+#pragma unroll 1
+        for (int j = j0; j < S; j++) {
+            const double ls = (double)o[S + j];
+            const double z = (A.traj.action_inter[(size_t)i * S + j] - (double)o[j]) / exp(ls);
+            lp += RANENV_INTER_LOGP_TERM(z, ls);
+            ent += (ls + 0.5) + HALF_LN_2PI;
+        }
+        lp += RANENV_INTER_LOGP_MASKED(j0);
+    } else {
+        const float l0 = o[0], l1 = o[1], l2 = o[2];
+        ch = (int)A.traj.action_intra[i];
+        // (RANENV_INTRA_LOGP's expressions in its order, for all three logits: change the two together, ranenv_net.hpp)
+        const double mx = fmax(fmax((double)l0, (double)l1), (double)l2);
+        const double e0 = exp((double)l0 - mx), e1 = exp((double)l1 - mx), e2 = exp((double)l2 - mx);
+        const double sum = (e0 + e1) + e2, lsum = log(sum);
+        q0 = ((double)l0 - mx) - lsum; q1 = ((double)l1 - mx) - lsum; q2 = ((double)l2 - mx) - lsum;
+        p0 = e0 / sum; p1 = e1 / sum; p2 = e2 / sum;
+        lp = ch == 0 ? q0 : (ch == 1 ? q1 : q2);
+        ent = -((p0 * q0 + p1 * q1) + p2 * q2);
+    }
+    if (A.probe_logp) A.probe_logp[at] = (float)lp;
+    const double gl = ppo_surrogate(lp, lp_old, adv, ent, hp.clip, wrow, rs), ge = hp.ent_coeff * wrow;
+    if (kind == 0) {
+#pragma unroll 1
+        for (int j = 0; j < j0; j++) { o[j] = 0.0f; o[S + j] = 0.0f; }
+#pragma unroll 1
+        for (int j = j0; j < S; j++) {
+            const double sig = exp((double)o[S + j]);
+            const double z = (A.traj.action_inter[(size_t)i * S + j] - (double)o[j]) / sig;
+            o[j] = (float)(gl * (z / sig));
+            o[S + j] = (float)(gl * (z * z - 1.0) - ge);
+        }
+    } else {
+        o[0] = (float)(gl * ((ch == 0 ? 1.0 : 0.0) - p0) + ge * (p0 * (q0 + ent)));
+        o[1] = (float)(gl * ((ch == 1 ? 1.0 : 0.0) - p1) + ge * (p1 * (q1 + ent)));
+        o[2] = (float)(gl * ((ch == 2 ? 1.0 : 0.0) - p2) + ge * (p2 * (q2 + ent)));
+    }
 }
 
 }  // namespace
