@@ -1,6 +1,7 @@
 """Train the reference's SB3 PPO("MlpPolicy") agents with collection AND the SGD on the device: the host touches it once per batch.
 
     python examples/train_sb3_ppo_on_device.py --agent twc|colran|ibsched [--batch 64] [--episode-len 32] [--iters 5] [--out policy.pt]
+    python examples/train_sb3_ppo_on_device.py --agent twc --spread 64 --batch 4096 --episode-len 64 --epochs 4 --minibatch 8192
 
 --agent twc / colran: SchedTWC / SchedColORAN on the head observation (agents/sched_twc.py:111-118, agents/sched_colran.py), scenario
 tables without slice sorting; --agent ibsched: IBSchedSB3 on player_0's row of obs_inter (agents/sb3_sched.py:104-111), round-robin inside
@@ -15,6 +16,11 @@ the slices.  Per iteration:
 Printed per iteration: the mean episode reward of the agent's own reward from the device-side episode sums, and the update's statistics.
 The default batch is SB3's: n_steps 2048 rows per update (64 envs x 32 TTIs).  At the end the trained policy is written as an SB3
 state dict (adapters.sb3_ppo_state_dict; key names restated from SB3's documented module layout, parity with SB3 itself is unpinned).
+
+--spread [SLABS] (default 64 slabs): the head binding's spread form, `env.ppo_bind(head=True, spread=True, slabs=SLABS)` -- every
+optimiser step of `ppo_update_head` runs as three launches spread over up to SLABS workgroups, for batches one workgroup cannot digest:
+the second command line trains on 262 144 rows per update (4096 envs x 64 TTIs), which the plain head binding refuses (more than 2^20
+rows x epochs) and the spread one takes; `ppo_head_spread_bytes` tells what the slabs cost.
 """
 from __future__ import annotations
 
@@ -46,6 +52,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--minibatch", type=int, default=64)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--spread", type=int, nargs="?", const=64, default=None, metavar="SLABS",
+                    help="the spread head binding: every optimiser step over up to SLABS (1..256, default 64) workgroups")
     ap.add_argument("--out", default="sb3_ppo_policy.pt")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -64,7 +72,13 @@ def main():
     env.set_head_policy_network(layers([10 * S, 64, 64, S], args.seed), "gauss_clip", torch.zeros(S), stochastic=True, seed=args.seed,
                                 activation="tanh", observation="inter" if inter else "head")
     env.set_head_value_network(layers([10 * S, 64, 64, 1], args.seed + 1), activation="tanh")
-    env.ppo_bind(head=True)
+    if args.spread is None:
+        env.ppo_bind(head=True)
+    else:
+        from intent_radio_sched_multi_slice_amd.batched_env import ppo_head_spread_bytes
+        env.ppo_bind(head=True, spread=True, slabs=args.spread)
+        kib = ppo_head_spread_bytes([10 * S, 64, 64, S], [10 * S, 64, 64, 1], S, args.spread) / 1024
+        print(f"spread head binding: {args.spread} slabs, {kib:.0f} KiB of gradient slabs; {B * L} rows per update")
     env.reset()
     reward = {"twc": "twc", "colran": "colran", "ibsched": "ibsched"}[args.agent]
     t0 = time.perf_counter()

@@ -1343,6 +1343,38 @@ int ranenv_ppo_head_state(ranenv_handle h, int32_t which, float **dev_m, float *
 int ranenv_get_head_net_weights(ranenv_handle h, int32_t which, ranenv_mlp *out, void *stream);
 int ranenv_get_head_log_std(ranenv_handle h, float *dev_out, void *stream);
 
+/* Head policies over the chip: the second form of the head binding.  ranenv_ppo_update_head under ranenv_ppo_bind_head is one workgroup
+ * on one compute unit; under ranenv_ppo_bind_head_spread it keeps its signature, arguments, arithmetic per row and outputs, and runs
+ * every optimiser step as THREE launches on `stream` (ranenv_ppo_spread.hip), as "One agent over the chip" above does for the IBSched pair:
+ *   pass    min(tiles of the minibatch, slabs) workgroups of 256 threads; workgroup w walks the 32-row tiles w, w + grid, ... in
+ *           ascending order on THE LDS PLAN, adds its backward passes into gradient slab w, keeps d / d log_std_j of its tiles in
+ *           float64 (thread j) and writes it unrounded to gls[w][j], and its rows' statistics to a slot of its own.  Every workgroup
+ *           computes the minibatch's advantage mean and std and sigma_j = exp(log_std_j) itself: same function, same order, same bits.
+ *   reduce  elementwise over the packed floats (actor, then critic), 1024 per block: g[i] = the used slabs' [i] summed in ascending
+ *           slab order in float32, the cells zeroed; a float64 sum of squares per block.  Block 0 also sums gls[0..used)[j] in
+ *           ascending order in float64, rounds once into log_std's gradient -- where the one-workgroup kernel rounds -- and adds its
+ *           squares to its partial: the joint norm covers log_std.
+ *   apply   every block adds ALL block partials in ascending order, takes the clip factor and Adam's constants at counter t0 + step + 1
+ *           and updates its elements in place; block 0 updates log_std, keeps the epoch's statistics, writes them at the epoch's last
+ *           step, and at the call's last step stores the counter and dev_grad (actor, critic, log_std).
+ * What a launch writes is read by later launches only: no cooperative launch, no grid-wide barrier, no flag, no atomics, no graph; the
+ * counter is read once as t0 through a cell of the binding.  The result is a function of the inputs and min(tiles, slabs) alone; with
+ * one slab dev_grad equals the one-workgroup form's byte for byte.  The statistics are summed per slab, then over the slabs.
+ *
+ * ranenv_ppo_bind_head_spread: what ranenv_ppo_bind_head does and refuses, in its words, plus buffers of the head binding's own,
+ *   allocated here and never by an update, none shared with ranenv_ppo_bind_spread's (both bindings may stand on one handle): gradient
+ *   slabs f32 [slabs][actor floats + critic floats], zeroed, and gls f64 [slabs][S] (ranenv_ppo_head_spread_bytes: the two together);
+ *   block partials, [256][6] slab statistics, running sums and the t0 cell.  slabs outside 1..256: RANENV_E_INVALID "slabs %d (1..256)".
+ *   The later of ranenv_ppo_bind_head / ranenv_ppo_bind_head_spread replaces the earlier one and restarts the head optimiser: the
+ *   moments of both nets and of log_std, and the counter.  Re-binding a head net restarts the optimiser as under ranenv_ppo_bind_head;
+ *   ranenv_ppo_update_head also checks that the nets as they stand fit the slabs the bind allocated (RANENV_E_STATE, "bind again").
+ *   ranenv_ppo_head_layout, ranenv_ppo_head_state, ranenv_get_head_net_weights, ranenv_get_head_log_std and dev_grad serve both forms.
+ * ranenv_ppo_head_spread_bytes: slabs x (4 x (actor floats + critic floats) + 8 x n_slices), without a handle; both nets are required,
+ *   n_slices 1..16, slabs 1..256 (RANENV_E_INVALID).  ranenv_ppo_spread_plan states the geometry (n_rows of the head list).
+ * Out of scope, each still refused: the wide plan for the head pair, bf16 nets, populations of head agents. */
+int ranenv_ppo_bind_head_spread(ranenv_handle h, int32_t slabs, void *stream);
+int ranenv_ppo_head_spread_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t n_slices, int32_t slabs, int64_t *bytes);
+
 /* Off-policy collection (SAC): the reference builds every SB3 agent in two flavours, agent_type "ppo" and "sac"
  * (agents/sched_twc.py:111-133, agents/sched_colran.py:111-133 on the head observation; agents/sb3_sched.py:104-120,
  * agents/sb3_pf_sched.py on IBSched's player_0 observation, RANENV_HEAD_SRC_INTER above); the SAC flavour is SB3's

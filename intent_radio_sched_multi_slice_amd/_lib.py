@@ -249,6 +249,8 @@ FUNCTIONS = {
     "ranenv_ppo_head_state": (C.c_int, [_P, _I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "ranenv_get_head_net_weights": (C.c_int, [_P, _I32, C.POINTER(Mlp), _P]),
     "ranenv_get_head_log_std": (C.c_int, [_P, _P, _P]),
+    "ranenv_ppo_bind_head_spread": (C.c_int, [_P, _I32, _P]),
+    "ranenv_ppo_head_spread_bytes": (C.c_int, [C.POINTER(Mlp), C.POINTER(Mlp), _I32, _I32, C.POINTER(C.c_int64)]),
     "ranenv_sac_bind": (C.c_int, [_P, _F64, _I32, _F64, _I32, _P]),
     "ranenv_sac_update": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _F64, _F64, _F64, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
     "ranenv_sac_layout": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -252,6 +252,17 @@ def ppo_spread_bytes(actor_layers, critic_layers=None, slabs: int = 64, wide: bo
     return out.value
 
 
+def ppo_head_spread_bytes(actor_layers, critic_layers, S: int, slabs: int = 64) -> int:
+    """Device bytes ``ppo_bind(head=True, spread=True, slabs=slabs)`` allocates for the head pair beside the moments
+    (ranenv_ppo_head_spread_bytes): ``slabs`` gradient slabs of the pair's packed floats and ``slabs`` float64 rows of ``log_std``'s
+    ``S`` partial gradients.  Nets as for ``ppo_lds_bytes``; both are required (the head update trains a pair)."""
+    actor, critic = _ppo_shape_pair(actor_layers, critic_layers)
+    out = C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_ppo_head_spread_bytes(actor, critic, int(S), int(slabs), C.byref(out)), "ranenv_ppo_head_spread_bytes")
+    return out.value
+
+
 def population_means(result: Dict[str, np.ndarray], first_env) -> Dict[str, np.ndarray]:
     """Per-member means of what ``evaluate()`` returns: every float metric [B, n_episodes, ...] -> [G, ...], the mean over the
     member's envs and episodes (``np.mean`` of the member's block); integer entries ("scenario") are left out."""
@@ -951,7 +962,7 @@ class BatchedRanEnv:
     # -- the PPO update on the device (ranenv_ppo_bind / ranenv_ppo_update; include/ranenv.h "PPO update") ---------------------------
     PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP = PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP      # (per handle: an attribute of the instance overrides them)
 
-    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False, spread: bool = False, slabs: int = 64) -> None:
+    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False, spread: bool = False, slabs: Optional[int] = None) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
         one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header).
         ``mixed=True`` (ranenv_ppo_bind_mixed): the population was bound with ``mixed=True`` -- members of differing shape -- and
@@ -969,14 +980,20 @@ class BatchedRanEnv:
         ``set_value_network`` -- which ``ppo_update_per_slice`` trains, one workgroup per policy.  Every other binding refuses such
         nets.  It excludes ``mixed`` and ``head``.
         ``spread=True`` (ranenv_ppo_bind_spread), with or without ``wide``: the binding for ONE agent on a large batch -- every
-        optimiser step of ``ppo_update`` is spread over the chip, the 32-row tiles of a minibatch over up to ``slabs`` (1..256)
+        optimiser step of ``ppo_update`` is spread over the chip, the 32-row tiles of a minibatch over up to ``slabs`` (1..256, default 64)
         workgroups per kind, each adding into a gradient slab of its own (``ppo_spread_bytes``); summed in a fixed order, so the
-        result depends on the inputs and on min(tiles, slabs) alone.  No population, no nets per slice: it excludes ``mixed``,
-        ``head`` and ``per_slice``."""
+        result depends on the inputs and on min(tiles, slabs) alone.  No population, no nets per slice: it excludes ``mixed``
+        and ``per_slice``.
+        ``head=True, spread=True, slabs=N`` (ranenv_ppo_bind_head_spread): the head binding's second form -- every optimiser step of
+        ``ppo_update_head`` spread over up to ``slabs`` workgroups in the same three launches, ``log_std`` included
+        (``ppo_head_spread_bytes``).  The later of the two head bindings replaces the earlier and restarts the head optimiser; either
+        stands beside whatever binding the IBSched nets have, the spread one included.  The head pair trains under the plain LDS plan
+        alone: ``head`` with ``spread`` and ``wide`` is refused like ``head`` with ``wide``.  ``slabs`` has no default in this form:
+        ``spread`` and ``head`` without it raise ``ValueError``, as the two together always did before this form existed."""
         if spread and mixed:
             raise ValueError("ppo_bind: spread and mixed exclude each other (the spread binding trains one agent, no population)")
-        if spread and head:
-            raise ValueError("ppo_bind: spread and head exclude each other (the head nets train under the plain plan)")
+        if spread and head and wide:
+            raise ValueError("ppo_bind: head, spread and wide exclude each other (the head nets train under the plain plan, spread or not)")
         if spread and per_slice:
             raise ValueError("ppo_bind: spread and per_slice exclude each other (the spread binding trains one shared intra pair)")
         if per_slice and (mixed or head):
@@ -985,8 +1002,15 @@ class BatchedRanEnv:
             raise ValueError("ppo_bind: mixed and head exclude each other")
         if wide and head:
             raise ValueError("ppo_bind: wide and head exclude each other (the head nets train under the plain plan)")
+        if spread and head and slabs is None:
+            raise ValueError("ppo_bind: spread and head together name the head binding's spread form, which takes its slab count: pass slabs=1..256")
+        slabs = 64 if slabs is None else slabs
         with torch.cuda.device(self.device):
-            if spread:
+            if head and spread:
+                self._check(self._lib.ranenv_ppo_bind_head_spread(self._h, int(slabs), self._stream()), "ranenv_ppo_bind_head_spread")
+                self._ppo_head_spread = True
+                return                         # (beside the IBSched nets' binding: which one that is stays as it was)
+            elif spread:
                 self._check(self._lib.ranenv_ppo_bind_spread(self._h, int(slabs), 1 if wide else 0, self._stream()), "ranenv_ppo_bind_spread")
             elif per_slice:
                 self._check(self._lib.ranenv_ppo_bind_slices(self._h, 1 if wide else 0, self._stream()), "ranenv_ppo_bind_slices")
@@ -994,6 +1018,7 @@ class BatchedRanEnv:
                 self._check(self._lib.ranenv_ppo_bind_wide(self._h, 1 if mixed else 0, self._stream()), "ranenv_ppo_bind_wide")
             elif head:
                 self._check(self._lib.ranenv_ppo_bind_head(self._h, self._stream()), "ranenv_ppo_bind_head")
+                self._ppo_head_spread = False
                 return                         # (beside the IBSched nets' binding: which one that is stays as it was)
             elif mixed:
                 self._check(self._lib.ranenv_ppo_bind_mixed(self._h, self._stream()), "ranenv_ppo_bind_mixed")
@@ -1263,7 +1288,9 @@ class BatchedRanEnv:
         ``adapters.ppo_head_row_order(rec, epochs, seed)``).  ``adv_norm``: "minibatch" or None; ``grad_clip`` <= 0 or None: no clipping.
         Returns {name: float64 array [max epochs]} for the names of ``_lib.PPO_STATS``; ``grad=True`` adds "grad" [actor floats + critic
         floats + S], the last minibatch's unclipped gradient: actor packed, critic packed, ``log_std``.  More than ``PPO_ROW_EPOCHS_CAP``
-        rows x epochs or ``PPO_STEPS_CAP`` optimiser steps is refused unless ``force``: one compute unit works through them."""
+        rows x epochs or ``PPO_STEPS_CAP`` optimiser steps is refused unless ``force``: one compute unit works through them.  Under
+        ``ppo_bind(head=True, spread=True)`` every optimiser step is three launches spread over the chip: the rows x epochs cap does not
+        apply, ``PPO_STEPS_CAP`` does."""
         if adv_norm not in ("minibatch", "none", None):
             raise ValueError('adv_norm is "minibatch" or None')
         epochs, minibatch = int(epochs), int(minibatch)
@@ -1274,13 +1301,14 @@ class BatchedRanEnv:
             raise ValueError(f"order: contiguous int32 [>= {epochs} epochs, n_rows]")
         order = order.to(self.device)
         max_epochs, n_rows = int(order.shape[0]), int(order.shape[1])
-        if not force and n_rows * max(epochs, 0) > self.PPO_ROW_EPOCHS_CAP:
+        if not force and not getattr(self, "_ppo_head_spread", False) and n_rows * max(epochs, 0) > self.PPO_ROW_EPOCHS_CAP:
             raise RanEnvError(f"ppo_update_head: more than {self.PPO_ROW_EPOCHS_CAP} rows x epochs; one compute unit works through them -- "
                               "train such a batch in torch, or pass force=True")
         steps = -(-n_rows // max(minibatch, 1)) * max(epochs, 0)
         if not force and steps > self.PPO_STEPS_CAP:
             raise RanEnvError(f"ppo_update_head: more than {self.PPO_STEPS_CAP} optimiser steps ({steps}); every step passes over all "
-                              "parameters on one compute unit -- use larger minibatches or fewer epochs, or pass force=True")
+                              "parameters" + (" in three launches" if getattr(self, "_ppo_head_spread", False) else " on one compute unit") +
+                              " -- use larger minibatches or fewer epochs, or pass force=True")
         lr, clip, vf_coeff, ent_coeff, eps = float(lr), float(clip), float(vf_coeff), float(ent_coeff), float(eps)      # (one value each)
         hp, _, _ = ppo_hparams(1, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, None if grad_clip is None else float(grad_clip), adv_norm, betas, eps)
 

@@ -186,6 +186,14 @@ struct ranenv {
     // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
     // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
     bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
+    // ranenv_ppo_bind_head_spread: the head binding's form (slabs > 0: every optimiser step spread over up to `slabs` workgroups) and
+    // its own buffers, none shared with the IBSched spread binding's: the gradient slabs [slabs][actor + critic floats] (zero between two
+    // optimiser steps), and in one array of doubles gls [slabs][S], the reduce blocks' sums of squares [ppo_head_blocks], the pass
+    // workgroups' statistics [PPO_SPREAD_SLABS_MAX][PPO_SPREAD_STATS] and the epoch's running sums [RANENV_PPO_STATS].  The call's
+    // copy of the step counter: d_ppo_head_t[1].  All allocated at the bind, never by an update
+    int ppo_head_slabs = 0;
+    float *d_ppo_head_slab = nullptr; long long ppo_head_slab_cap = 0;
+    double *d_ppo_head_spread = nullptr; long long ppo_head_blocks = 0; int ppo_head_gls_slabs = 0;
     // ranenv_sac_bind / ranenv_sac_update: bound?, the packed floats of the actor and of one critic at the bind (a re-bind of another
     // size ends the binding), the slab count, the coefficient's mode and the target entropy; the live critics with their moments
     // [6][sac_q_cap] (q1, q2, m of both, v of both), the actor's moments [2][sac_a_cap], the gradient slabs [slabs][actor + 2 critics],
@@ -2791,6 +2799,18 @@ static int ppo_head_roles(ranenv_handle h, size_t &lds)
     return RANENV_OK;
 }
 
+// What the spread head binding holds beside the moments, for the head nets as they stand: floats of gradient slabs and reduce / apply blocks
+struct PpoHeadSpreadNeed { long long floats, slab, blocks; };
+static PpoHeadSpreadNeed ppo_head_spread_need(ranenv_handle h, int slabs)
+{
+    PpoHeadSpreadNeed n{};
+    n.floats = net_floats(h->head.net) + net_floats(h->head_value.net);
+    n.slab = n.floats * slabs;
+    n.blocks = (n.floats + PPO_SPREAD_BLOCK - 1) / PPO_SPREAD_BLOCK;
+    return n;
+}
+static long long ppo_head_spread_doubles(long long blocks, int slabs, int S) { return (long long)slabs * S + blocks + PPO_SPREAD_SLABS_MAX * PPO_SPREAD_STATS + RANENV_PPO_STATS; }
+
 // ... and the bound state behind it, or RANENV_E_STATE
 static int ppo_head_bound(ranenv_handle h, size_t &lds)
 {
@@ -2798,6 +2818,11 @@ static int ppo_head_bound(ranenv_handle h, size_t &lds)
     if (const int rc = ppo_head_roles(h, lds); rc != RANENV_OK) return rc;
     for (const ranenv::NetSlot *x : {&h->head, &h->head_value})
         if (!x->opt || x->opt_cap < x->cap) return fail(h, RANENV_E_STATE, "a head net was bound after ranenv_ppo_bind_head: bind again");
+    if (h->ppo_head_slabs) {      // the spread form: the slabs and block partials of the nets as they stand fit what the bind allocated
+        const PpoHeadSpreadNeed need = ppo_head_spread_need(h, h->ppo_head_slabs);
+        if (need.slab > h->ppo_head_slab_cap || need.blocks > h->ppo_head_blocks || h->ppo_head_slabs > h->ppo_head_gls_slabs)
+            return fail(h, RANENV_E_STATE, "the head nets need more slab floats than ranenv_ppo_bind_head_spread allocated: bind again");
+    }
     return RANENV_OK;
 }
 
@@ -2814,7 +2839,8 @@ static int ppo_head_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t 
     return RANENV_OK;
 }
 
-int ranenv_ppo_bind_head(ranenv_handle h, void *stream)
+// ranenv_ppo_bind_head (slabs 0) / ranenv_ppo_bind_head_spread (slabs 1..256): the later one replaces the earlier and restarts the optimiser
+static int ppo_bind_head(ranenv_handle h, int slabs, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     size_t lds = 0;
@@ -2822,8 +2848,22 @@ int ranenv_ppo_bind_head(ranenv_handle h, void *stream)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const size_t S = (size_t)h->cfg.n_slices;
+    if (slabs) {      // the spread form's own: slabs (zeroed), gls, block partials, slab statistics and running sums
+        const PpoHeadSpreadNeed need = ppo_head_spread_need(h, slabs);
+        if (h->ppo_head_slab_cap < need.slab) {
+            if (const int rc = dev_alloc(h, &h->d_ppo_head_slab, (size_t)need.slab); rc != RANENV_OK) return rc;
+            h->ppo_head_slab_cap = need.slab;
+        }
+        if (!h->d_ppo_head_spread || h->ppo_head_blocks < need.blocks || h->ppo_head_gls_slabs < slabs) {
+            const long long blocks = std::max(need.blocks, h->ppo_head_blocks);
+            const int gls = std::max(slabs, h->ppo_head_gls_slabs);
+            if (const int rc = dev_alloc(h, &h->d_ppo_head_spread, (size_t)ppo_head_spread_doubles(blocks, gls, (int)S)); rc != RANENV_OK) return rc;
+            h->ppo_head_blocks = blocks; h->ppo_head_gls_slabs = gls;
+        }
+        HIP_TRY(h, hipMemsetAsync(h->d_ppo_head_slab, 0, sizeof(float) * (size_t)h->ppo_head_slab_cap, s));
+    }
     if (!h->d_ppo_head_t) {
-        if (const int rc = dev_alloc(h, &h->d_ppo_head_t, (size_t)1); rc != RANENV_OK) return rc;
+        if (const int rc = dev_alloc(h, &h->d_ppo_head_t, (size_t)2); rc != RANENV_OK) return rc;
         if (const int rc = dev_alloc(h, &h->d_head_ls_opt, 3 * S); rc != RANENV_OK) return rc;
     }
     HIP_TRY(h, hipMemsetAsync(h->d_ppo_head_t, 0, sizeof(int32_t), s));
@@ -2831,6 +2871,26 @@ int ranenv_ppo_bind_head(ranenv_handle h, void *stream)
     for (ranenv::NetSlot *x : {&h->head, &h->head_value})
         if (const int rc = opt_ensure(h, x, s); rc != RANENV_OK) return rc;
     h->ppo_head_on = true;
+    h->ppo_head_slabs = slabs;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_bind_head(ranenv_handle h, void *stream) { return ppo_bind_head(h, 0, stream); }
+// (the head policies over the chip, include/ranenv.h "Head policies over the chip")
+int ranenv_ppo_bind_head_spread(ranenv_handle h, int32_t slabs, void *stream)
+{
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(h, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    return ppo_bind_head(h, slabs, stream);
+}
+
+int ranenv_ppo_head_spread_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t n_slices, int32_t slabs, int64_t *bytes)
+{
+    if (!actor || !critic || !bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_slices < 1 || n_slices > 16) return fail(nullptr, RANENV_E_INVALID, "n_slices %d (1..16)", n_slices);
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(nullptr, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    PolicyNet net[2] = {};
+    if (const int rc = ppo_shape_pair(actor, critic, net); rc != RANENV_OK) return rc;
+    *bytes = (int64_t)slabs * ((int64_t)sizeof(float) * (net_floats(net[0]) + net_floats(net[1])) + (int64_t)sizeof(double) * n_slices);
     return RANENV_OK;
 }
 
@@ -2882,7 +2942,26 @@ int ranenv_ppo_update_head(ranenv_handle h, int32_t n_steps, const ranenv_head_t
     a.order = order; a.n_rows = n_rows; a.T = n_steps; a.B = h->cfg.batch; a.S = S;
     a.hp = *hp; a.traj = *traj; a.t = h->d_ppo_head_t; a.stats = stats; a.grad = grad;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, launch_ppo_update_head((hipStream_t)stream, lds, a));
+    if (!h->ppo_head_slabs) {
+        HIP_TRY(h, launch_ppo_update_head((hipStream_t)stream, lds, a));
+        return RANENV_OK;
+    }
+    // the spread form: three launches per optimiser step on the head binding's own buffers
+    const long long steps = (long long)hp->epochs * ppo_spread_per_epoch(n_rows, hp->minibatch);
+    if (steps > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "%lld optimiser steps (epochs x minibatches): more than 2^31 - 1", steps);
+    PpoHeadSpreadArgs p{};
+    p.a = a;
+    PpoHeadSpread &K = p.k;
+    K.slabs = h->ppo_head_slabs; K.steps = (int)steps;
+    K.slab = h->d_ppo_head_slab; K.slab_stride = a.net[0].floats + a.net[1].floats;
+    K.blocks = (int)((K.slab_stride + PPO_SPREAD_BLOCK - 1) / PPO_SPREAD_BLOCK);
+    K.gls = h->d_ppo_head_spread; K.bpart = K.gls + (size_t)h->ppo_head_gls_slabs * S;
+    K.wstat = K.bpart + h->ppo_head_blocks; K.run = K.wstat + PPO_SPREAD_SLABS_MAX * PPO_SPREAD_STATS;
+    K.t0 = h->d_ppo_head_t + 1;
+    for (long long i = 0; i < steps; i++) {
+        K.step = (int)i;
+        HIP_TRY(h, launch_ppo_spread_head_step((hipStream_t)stream, lds, p));
+    }
     return RANENV_OK;
 }
 

@@ -351,6 +351,21 @@ struct PpoHeadArgs {
     float *grad;                          // [actor floats + critic floats + S] or null
 };
 hipError_t launch_ppo_update_head(hipStream_t, size_t lds, const PpoHeadArgs &);
+// ranenv_ppo_update_head under ranenv_ppo_bind_head_spread (ranenv_ppo_spread.hip; include/ranenv.h "Head policies over the chip"): the
+// head binding's own buffers -- never the IBSched spread binding's -- and optimiser step `step` of `steps`; the geometry is
+// ppo_spread_step(a.n_rows, a.hp.minibatch, slabs, step).  Every array is written by one launch and read by later ones alone.
+struct PpoHeadSpread {
+    float *slab; long long slab_stride;   // [slabs][slab_stride]: the actor's packed gradient, then the critic's; zero between two steps
+    double *gls;                          // [slabs][S] the pass workgroups' d/d log_std, unrounded
+    double *bpart;                        // [blocks] the reduce blocks' sums of squares (block 0's with log_std's)
+    double *wstat;                        // [slabs][PPO_SPREAD_STATS] the pass workgroups' row statistics
+    double *run;                          // [RANENV_PPO_STATS] the epoch's running sums between two steps
+    int32_t *t0;                          // the step counter as the call found it (the first pass copies it)
+    int slabs, step, steps, blocks;
+};
+struct PpoHeadSpreadArgs { PpoHeadArgs a; PpoHeadSpread k; };
+// The three launches of optimiser step a.k.step
+hipError_t launch_ppo_spread_head_step(hipStream_t, size_t lds, const PpoHeadSpreadArgs &);
 
 // ranenv_sac_update (ranenv_sac.hip; include/ranenv.h "SAC update"): one gradient step is a critic pass, an apply, an actor pass and
 // a second apply.  A net of a pass: its layout (net.w unused) and the packed weights the pass reads.

@@ -99,22 +99,11 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_slices_wide(PpoA
 // record.  A body of its own beside ranenv_ppo_body.hpp -- no population, no kinds, no mask, a third parameter tensor -- whose every
 // step that the body has too is the same ranenv_ppo_parts.hpp function (ppo_zero, ppo_adv_norm, ppo_list_rows, ppo_surrogate,
 // ppo_critic_row, ppo_backward, ppo_tile_stats, ppo_sq_sum, ppo_clip_scale, adam_step / ppo_adam, ppo_epoch_stats, ppo_grad_out).  Its
-// own: log_std and sig[], the three-step gradient at the actor's outputs, and g_ls.
+// own: log_std and sig[], the three-step gradient at the actor's outputs (ppo_head_actor_tile, shared with the spread head update of
+// ranenv_ppo_spread.hip, as are ppo_head_load_rows and PPO_HEAD_ROW_STATS), and g_ls.
 // log_std is a weight this launch rewrites: its working copy lies in the fixed LDS region (`lsw`, loaded and reloaded by lane j at a
 // lane-dependent address behind Adam's own store of the same lane), never read through a wave-uniform address.  sig[j] = exp(log_std_j)
 // in float64 is parked in the reduction slots between two ppo_sum calls (refilled per minibatch behind the advantage pass).
-constexpr int PPO_HEAD_ROW_STATS = 7;     // PPO_ROW_STATS' six, then gl = dL/d(logp) of the row
-static_assert(PPO_FIXED >= (256 + NET_ROWS * PPO_HEAD_ROW_STATS) * 8 + NET_ROWS * 4 + 16 * 4, "the fixed LDS region holds the head kernel's row statistics and log_std");
-
-__device__ __forceinline__ void ppo_head_load_rows(const PolicyNet &net, const PpoHeadArgs &A, const int *idx, float *dst, int tid)
-{
-    load_rows(net.kp[0], 0, 0, dst, tid, [&](int r, int k) {
-        const int i = idx[r];
-        if (i < 0 || k >= net.in_dim) return 0.0f;
-        return A.traj.obs_head[(size_t)i * (size_t)(10 * A.S) + k];
-    });
-}
-
 __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs A)
 {
     extern __shared__ float lds[];
@@ -139,7 +128,7 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs
 #pragma unroll 1
         for (int c0 = 0; c0 < n; c0 += minibatch) {
             const int nb = n - c0 < minibatch ? n - c0 : minibatch;
-            const double wrow = 1.0 / (double)nb, ge = hp.ent_coeff * wrow;
+            const double wrow = 1.0 / (double)nb;
 #pragma unroll 1
             for (int k = 0; k < 2; k++) ppo_zero(A.net[k].g, A.net[k].floats, tid);
             double g_ls = 0.0;                 // (thread j < S: d/d log_std_j of the minibatch, rows in order)
@@ -170,53 +159,7 @@ __global__ void __launch_bounds__(256) ranenv_ppo_update_kernel_head(PpoHeadArgs
                             const int i = rowidx[tid];
                             rowstat[tid * PPO_HEAD_ROW_STATS + 5] = ppo_critic_row(cur + tid * ldo, i, [&] { return A.traj.vtarg[i]; }, hp.vf_coeff, wrow);
                         }
-                    } else {
-                        // 1. the row's log-probability, ratio and statistics (thread r); the outputs stay
-                        if (tid < NET_ROWS) {
-                            const int i = rowidx[tid];
-                            const float *o = cur + tid * ldo;
-                            double *rs = rowstat + tid * PPO_HEAD_ROW_STATS;
-                            if (i < 0) rs[0] = rs[1] = rs[2] = rs[3] = rs[4] = rs[6] = 0.0;
-                            else {
-                                const double lp_old = (double)A.traj.logp[i];
-                                const double adv = hp.adv_norm ? ((double)A.traj.adv[i] - a_mean) / a_den : (double)A.traj.adv[i];
-                                double lp = 0.0, ent = 0.0;
-#pragma unroll 1
-                                for (int j = 0; j < S; j++) {
-                                    const double ls = (double)lsw[j];
-                                    const double z = (A.traj.action[(size_t)i * S + j] - (double)o[j]) / sig[j];
-                                    lp += RANENV_INTER_LOGP_TERM(z, ls);
-                                    ent += (ls + 0.5) + HALF_LN_2PI;
-                                }
-                                rs[6] = ppo_surrogate(lp, lp_old, adv, ent, hp.clip, wrow, rs);
-                            }
-                        }
-                        __syncthreads();
-                        // 2. d/d log_std_j (thread j), rows in ascending order, float64
-                        if (tid < S) {
-                            const double sj = sig[tid];
-#pragma unroll 1
-                            for (int r = 0; r < NET_ROWS; r++) {
-                                const int i = rowidx[r];
-                                if (i < 0) continue;
-                                const double z = (A.traj.action[(size_t)i * S + tid] - (double)cur[r * ldo + tid]) / sj;
-                                g_ls += rowstat[r * PPO_HEAD_ROW_STATS + 6] * (z * z - 1.0) - ge;
-                            }
-                        }
-                        __syncthreads();
-                        // 3. d/d mean_j over the outputs, element by element; dead rows and padded columns: zeros
-#pragma unroll 1
-                        for (int e = tid; e < NET_ROWS * np; e += 256) {
-                            const int r = e / np, j = e - r * np, i = rowidx[r];
-                            float *o = cur + r * ldo + j;
-                            float v = 0.0f;
-                            if (i >= 0 && j < S) {
-                                const double sj = sig[j], z = (A.traj.action[(size_t)i * S + j] - (double)*o) / sj;
-                                v = (float)(rowstat[r * PPO_HEAD_ROW_STATS + 6] * (z / sj));
-                            }
-                            *o = v;
-                        }
-                    }
+                    } else ppo_head_actor_tile(A, rowidx, cur, np, ldo, rowstat, lsw, sig, wrow, a_mean, a_den, g_ls, tid);
                     __syncthreads();
                     ppo_backward(net, pn.w, pn.g, cur, tid);
                 }

@@ -1,5 +1,7 @@
 // ranenv_ppo_parts.hpp -- the one statement of every step the training kernels share (ranenv_ppo.hip: the PPO updates of the bound nets
-// and of the head policies; ranenv_ppo_spread.hip: one agent's PPO update spread over the chip; ranenv_sac.hip: the SAC update): the LDS size of a net's rows, the backward pass of one 32-row tile on the
+// and of the head policies; ranenv_ppo_spread.hip: one agent's PPO update spread over the chip, the IBSched pair's and the head pair's
+// -- whose tile steps (ppo_head_load_rows, ppo_head_actor_tile) and elementwise reduce / apply steps (ppo_spread_*) stand at the end;
+// ranenv_sac.hip: the SAC update): the LDS size of a net's rows, the backward pass of one 32-row tile on the
 // f32 matrix cores and its dZ' block walk, the workgroup sum in slot order, Adam's constants and float32 element step, and the steps
 // of a PPO minibatch -- zeroing, the advantages' mean and std, the tile's row list, the clipped surrogate, the critic row, the joint
 // norm and clip scale, the statistics, the gradient copy -- and the steps of a tile of the IBSched nets that the member update and the
@@ -370,6 +372,146 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
         o[1] = (float)(gl * ((ch == 1 ? 1.0 : 0.0) - p1) + ge * (p1 * (q1 + ent)));
         o[2] = (float)(gl * ((ch == 2 ? 1.0 : 0.0) - p2) + ge * (p2 * (q2 + ent)));
     }
+}
+
+// ---- the steps of a tile of the head policies (ranenv_ppo_update_kernel_head and the spread head update, ranenv_ppo_spread.hip) -------
+constexpr int PPO_HEAD_ROW_STATS = 7;     // PPO_ROW_STATS' six, then gl = dL/d(logp) of the row
+static_assert(PPO_FIXED >= (256 + NET_ROWS * PPO_HEAD_ROW_STATS) * 8 + NET_ROWS * 4 + 16 * 4, "the fixed LDS region holds the head kernels' row statistics and log_std");
+
+__device__ __forceinline__ void ppo_head_load_rows(const PolicyNet &net, const PpoHeadArgs &A, const int *idx, float *dst, int tid)
+{
+    load_rows(net.kp[0], 0, 0, dst, tid, [&](int r, int k) {
+        const int i = idx[r];
+        if (i < 0 || k >= net.in_dim) return 0.0f;
+        return A.traj.obs_head[(size_t)i * (size_t)(10 * A.S) + k];
+    });
+}
+
+// The loss gradient at the head actor's outputs for one tile, three steps with a barrier between them (the caller holds one in front
+// -- the forward pass has written `cur` -- and one behind): `cur` = the output rows at stride `ldo`, overwritten; `lsw` = log_std [S]
+// and `sig` = exp(log_std) in float64, both in LDS; rowstat[r][0..4], [6] = the row's statistics and gl; thread j < S adds the tile's
+// d/d log_std_j to its `g_ls`, rows in ascending order.
+__device__ __forceinline__ void ppo_head_actor_tile(const PpoHeadArgs &A, const int *rowidx, float *cur, int np, int ldo, double *rowstat, const float *lsw,
+                                                    const double *sig, double wrow, double a_mean, double a_den, double &g_ls, int tid)
+{
+    const ranenv_ppo_hparams &hp = A.hp;
+    const int S = A.S;
+    const double ge = hp.ent_coeff * wrow;
+    // 1. the row's log-probability, ratio and statistics (thread r); the outputs stay
+    if (tid < NET_ROWS) {
+        const int i = rowidx[tid];
+        const float *o = cur + tid * ldo;
+        double *rs = rowstat + tid * PPO_HEAD_ROW_STATS;
+        if (i < 0) rs[0] = rs[1] = rs[2] = rs[3] = rs[4] = rs[6] = 0.0;
+        else {
+            const double lp_old = (double)A.traj.logp[i];
+            const double adv = hp.adv_norm ? ((double)A.traj.adv[i] - a_mean) / a_den : (double)A.traj.adv[i];
+            double lp = 0.0, ent = 0.0;
+#pragma unroll 1
+            for (int j = 0; j < S; j++) {
+                const double ls = (double)lsw[j];
+                const double z = (A.traj.action[(size_t)i * S + j] - (double)o[j]) / sig[j];
+                lp += RANENV_INTER_LOGP_TERM(z, ls);
+                ent += (ls + 0.5) + HALF_LN_2PI;
+            }
+            rs[6] = ppo_surrogate(lp, lp_old, adv, ent, hp.clip, wrow, rs);
+        }
+    }
+    __syncthreads();
+    // 2. d/d log_std_j (thread j), rows in ascending order, float64
+    if (tid < S) {
+        const double sj = sig[tid];
+#pragma unroll 1
+        for (int r = 0; r < NET_ROWS; r++) {
+            const int i = rowidx[r];
+            if (i < 0) continue;
+            const double z = (A.traj.action[(size_t)i * S + tid] - (double)cur[r * ldo + tid]) / sj;
+            g_ls += rowstat[r * PPO_HEAD_ROW_STATS + 6] * (z * z - 1.0) - ge;
+        }
+    }
+    __syncthreads();
+    // 3. d/d mean_j over the outputs, element by element; dead rows and padded columns: zeros
+#pragma unroll 1
+    for (int e = tid; e < NET_ROWS * np; e += 256) {
+        const int r = e / np, j = e - r * np, i = rowidx[r];
+        float *o = cur + r * ldo + j;
+        float v = 0.0f;
+        if (i >= 0 && j < S) {
+            const double sj = sig[j], z = (A.traj.action[(size_t)i * S + j] - (double)*o) / sj;
+            v = (float)(rowstat[r * PPO_HEAD_ROW_STATS + 6] * (z / sj));
+        }
+        *o = v;
+    }
+}
+
+// ---- the elementwise steps of a spread update (ranenv_ppo_spread.hip: the IBSched kinds' and the head pair's reduce and apply) --------
+// Element e of the packed floats the launch covers: the four arrays' cells, by the caller's layout (actor below its floats, critic behind)
+struct PpoSpreadCell { float *g, *w, *m, *v; };
+
+// The reduce of the block's PPO_SPREAD_BLOCK elements: g[e] = the `used` slabs' [e] summed in ascending slab order, the cells zeroed
+// for the next step; returns the thread's float64 share of the block's sum of squares
+template <class F>
+__device__ __forceinline__ double ppo_spread_reduce_elems(float *slab, long long slab_stride, int used, long long floats, int tid, F cell_at)
+{
+    double s = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < PPO_SPREAD_BLOCK / 256; j++) {
+        const long long e = (long long)blockIdx.x * PPO_SPREAD_BLOCK + j * 256 + tid;
+        if (e >= floats) break;
+        float *p = slab + e;
+        float g = *p;
+        *p = 0.0f;
+#pragma unroll 1
+        for (int u = 1; u < used; u++) {
+            p += slab_stride;
+            g = g + *p;
+            *p = 0.0f;
+        }
+        *cell_at(e).g = g;
+        s += (double)g * (double)g;
+    }
+    return s;
+}
+
+// The joint norm's square: ALL block partials in ascending order, in every thread of every block
+__device__ __forceinline__ double ppo_spread_norm2(const double *bpart, int blocks)
+{
+    double tot = 0.0;
+#pragma unroll 1
+    for (int b = 0; b < blocks; b++) tot += bpart[b];
+    return tot;
+}
+
+// The apply of the block's elements: Adam in place on the scaled gradient; `grad` (or null): the unclipped gradient's copy
+template <class F>
+__device__ __forceinline__ void ppo_spread_apply_elems(long long floats, float *grad, float sc, const AdamStep &adam, int tid, F cell_at)
+{
+#pragma unroll 1
+    for (int j = 0; j < PPO_SPREAD_BLOCK / 256; j++) {
+        const long long e = (long long)blockIdx.x * PPO_SPREAD_BLOCK + j * 256 + tid;
+        if (e >= floats) break;
+        const PpoSpreadCell c = cell_at(e);
+        const float g = *c.g;
+        if (grad) grad[e] = g;
+        adam_elem(*c.w, *c.m, *c.v, g * sc, adam);
+    }
+}
+
+// One thread's: the epoch's running sums `run` (PpoEpoch's fields in order) take this step's slab statistics wstat[0..geo.grid) in
+// ascending order and the norm; the epoch's last step writes its eight outputs to `out`, every other one stores the sums back
+__device__ __forceinline__ void ppo_spread_stats(double *run, const double *wstat, const PpoSpreadStep &geo, double norm, bool epoch_end, double *out, int n)
+{
+    PpoEpoch st;
+    if (geo.mb > 0) { st.pl = run[0]; st.vl = run[1]; st.ent = run[2]; st.kl = run[3]; st.cf = run[4]; st.gn = run[5]; st.rows = run[6]; st.n_mb = (int)run[7]; }
+#pragma unroll 1
+    for (int u = 0; u < geo.grid; u++) {
+        const double *ws = wstat + (size_t)u * PPO_SPREAD_STATS;
+        st.pl += ws[0]; st.ent += ws[1]; st.kl += ws[2]; st.cf += ws[3]; st.rows += ws[4]; st.vl += ws[5];
+    }
+    st.gn += norm * (double)geo.nb;
+    st.n_mb += 1;
+    if (epoch_end) ppo_epoch_stats(out, st, n);
+    else { run[0] = st.pl; run[1] = st.vl; run[2] = st.ent; run[3] = st.kl; run[4] = st.cf; run[5] = st.gn; run[6] = st.rows; run[7] = (double)st.n_mb; }
 }
 
 }  // namespace

@@ -16,6 +16,7 @@
 // pass copies it to a cell of the binding's (t0), every apply reads that cell, and the last apply's block 0 stores t0 + steps to the
 // counter, which no block of an apply reads.  The result is a function of the inputs and of min(tiles, slabs) alone; with one slab the
 // tile order and the adds are the plain kernel's.
+// The head policies (ranenv_ppo_bind_head_spread) have three kernels of the same pattern below, on the same elementwise functions.
 #include "ranenv_ppo_parts.hpp"
 
 namespace {
@@ -169,6 +170,132 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_apply_kernel(PpoSpreadA
 }
 #undef SPREAD_AT
 
+// (the same for the head pair's kernels, as the cell the shared elementwise functions of ranenv_ppo_parts.hpp take)
+#define SPREAD_CELL(n0, n1) [&](long long e) { return e < af ? PpoSpreadCell{(n0).g + e, (n0).w + e, (n0).m + e, (n0).v + e} \
+                                                             : PpoSpreadCell{(n1).g + (e - af), (n1).w + (e - af), (n1).m + (e - af), (n1).v + (e - af)}; }
+
+// ---- the head policies over the chip (ranenv_ppo_bind_head_spread; include/ranenv.h "Head policies over the chip") -------------------
+// The same three launches for the head actor, the head critic and log_std [S] on a ranenv_collect_head record: no kinds (a 1-D grid),
+// the tile steps of ranenv_ppo_update_kernel_head, and a third parameter tensor.  Thread j < S of pass workgroup w keeps the
+// workgroup's d/d log_std_j in float64 over its tiles and writes it UNROUNDED to gls[w][j]; block 0 of the reduce adds the used slabs'
+// in ascending order in float64 and rounds once into ls_g[j] -- where the one-workgroup kernel rounds -- and adds the squares into its
+// block partial, so the joint norm covers log_std; block 0 of the apply runs Adam on log_std beside its elements.
+// log_std is a weight the previous apply rewrote: the pass loads it into LDS (`lsw`) by lane j at a lane-dependent address, as
+// ranenv_ppo.hip's header asks of every weight; sig[j] = exp(log_std_j) in float64 stands in the reduction slots behind the advantage pass.
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_head_pass_kernel(PpoHeadSpreadArgs P)
+{
+    extern __shared__ float lds[];
+    const PpoHeadArgs &A = P.a;
+    const ranenv_ppo_hparams &hp = A.hp;
+    const PpoHeadSpread &K = P.k;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, S = A.S;
+    const PpoSpreadStep geo = ppo_spread_step(A.n_rows, hp.minibatch, K.slabs, K.step);
+    const int w = (int)blockIdx.x;
+    if (w >= geo.grid) return;
+    if (K.step == 0 && w == 0 && tid == 0) K.t0[0] = A.t[0];
+
+    double *red = (double *)lds, *rowstat = red + 256, *sig = red;
+    int *rowidx = (int *)(rowstat + NET_ROWS * PPO_HEAD_ROW_STATS);
+    float *lsw = (float *)(rowidx + NET_ROWS);
+    float *act = lds + PPO_FIXED / 4;
+    const int c0 = geo.c0, nb = geo.nb;
+    const long long n_record = (long long)A.T * A.B;
+    const int32_t *list = A.order + (size_t)geo.ep * (size_t)A.n_rows;
+    const double wrow = 1.0 / (double)nb;
+    float *const slab = K.slab + (size_t)w * (size_t)K.slab_stride;
+    PpoEpoch st;                               // (thread 0's: this workgroup's tiles)
+    if (tid < S) lsw[tid] = A.log_std[tid];
+
+    double g_ls = 0.0;                         // (thread j < S: d/d log_std_j of this workgroup's tiles, rows in order)
+    double a_mean = 0.0, a_den = 1.0;
+    if (hp.adv_norm)
+        ppo_adv_norm(red, nb, tid, [&](int k) {
+            const int i = list[c0 + k];
+            return i < 0 || i >= n_record ? 0.0 : (double)A.traj.adv[i];
+        }, a_mean, a_den);
+    if (tid < S) sig[tid] = exp((double)lsw[tid]);      // (thread j reads what thread j wrote; published by the tile loop's first barrier)
+
+#pragma unroll 1
+    for (int t0 = w * NET_ROWS; t0 < nb; t0 += geo.grid * NET_ROWS) {
+        __syncthreads();                       // (the previous tile's backward pass and statistics are read)
+        ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
+#pragma unroll 1
+        for (int k = 0; k < 2; k++) {
+            const PpoNet &pn = A.net[k];
+            const PolicyNet &net = pn.net;
+            __syncthreads();                   // (the tile's rows are listed; the actor's backward pass has read its rows)
+            float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
+            ppo_head_load_rows(net, A, rowidx, cur, tid);
+            __syncthreads();
+            net_layers<false, true>(net, pn.w, cur, nxt, lane, wave);
+            const int np = net.np[net.n_layers - 1], ldo = net_ld(np);
+            if (k == 1) {
+                if (tid < NET_ROWS) {
+                    const int i = rowidx[tid];
+                    rowstat[tid * PPO_HEAD_ROW_STATS + 5] = ppo_critic_row(cur + tid * ldo, i, [&] { return A.traj.vtarg[i]; }, hp.vf_coeff, wrow);
+                }
+            } else ppo_head_actor_tile(A, rowidx, cur, np, ldo, rowstat, lsw, sig, wrow, a_mean, a_den, g_ls, tid);
+            __syncthreads();
+            ppo_backward(net, pn.w, slab + (k == 0 ? 0 : A.net[0].floats), cur, tid);
+        }
+        if (tid == 0) ppo_tile_stats(st, rowstat, PPO_HEAD_ROW_STATS, true);      // (the barriers above have published the rows')
+    }
+    if (tid < S) K.gls[(size_t)w * S + tid] = g_ls;
+    if (tid == 0) {
+        double *out = K.wstat + (size_t)w * PPO_SPREAD_STATS;
+        out[0] = st.pl; out[1] = st.ent; out[2] = st.kl; out[3] = st.cf; out[4] = st.rows; out[5] = st.vl;
+    }
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_head_reduce_kernel(PpoHeadSpreadArgs P)
+{
+    __shared__ double red[256];
+    const PpoHeadArgs &A = P.a;
+    const PpoHeadSpread &K = P.k;
+    const int tid = (int)threadIdx.x, S = A.S;
+    const int used = ppo_spread_step(A.n_rows, A.hp.minibatch, K.slabs, K.step).grid;
+    const long long af = A.net[0].floats, floats = af + A.net[1].floats;
+    double s = ppo_spread_reduce_elems(K.slab, K.slab_stride, used, floats, tid, SPREAD_CELL(A.net[0], A.net[1]));
+    if (blockIdx.x == 0 && tid < S) {          // log_std: the slabs' float64 partials in ascending order, rounded once
+        double g = K.gls[tid];
+#pragma unroll 1
+        for (int u = 1; u < used; u++) g += K.gls[(size_t)u * S + tid];
+        const float gf = (float)g;
+        A.ls_g[tid] = gf;
+        s += (double)gf * (double)gf;
+    }
+    const double tot = ppo_sum(red, s, tid);
+    if (tid == 0) K.bpart[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_head_apply_kernel(PpoHeadSpreadArgs P)
+{
+    const PpoHeadArgs &A = P.a;
+    const ranenv_ppo_hparams &hp = A.hp;
+    const PpoHeadSpread &K = P.k;
+    const int tid = (int)threadIdx.x, S = A.S;
+    const double norm = sqrt(ppo_spread_norm2(K.bpart, K.blocks));
+    const float sc = (float)ppo_clip_scale(hp.grad_clip, norm);
+    const int t_call = K.t0[0];
+    const AdamStep adam = adam_step(hp.lr, hp.beta1, hp.beta2, hp.eps, t_call + K.step + 1);
+    const bool last = K.step == K.steps - 1;
+    const long long af = A.net[0].floats, floats = af + A.net[1].floats;
+    float *const grad = last ? A.grad : nullptr;
+    ppo_spread_apply_elems(floats, grad, sc, adam, tid, SPREAD_CELL(A.net[0], A.net[1]));
+    if (blockIdx.x != 0) return;
+    // ---- block 0: log_std, the epoch's statistics and the counter --------------------------------------------------------------------
+    if (tid < S) {
+        const float g = A.ls_g[tid];
+        if (grad) grad[floats + tid] = g;
+        adam_elem(A.log_std[tid], A.ls_m[tid], A.ls_v[tid], g * sc, adam);
+    }
+    if (tid != 0) return;
+    const PpoSpreadStep geo = ppo_spread_step(A.n_rows, hp.minibatch, K.slabs, K.step);
+    ppo_spread_stats(K.run, K.wstat, geo, norm, geo.mb == ppo_spread_per_epoch(A.n_rows, hp.minibatch) - 1, A.stats + (size_t)geo.ep * RANENV_PPO_STATS, A.n_rows);
+    if (last) A.t[0] = t_call + K.steps;
+}
+#undef SPREAD_CELL
+
 }  // namespace
 
 namespace ranenv_dev {
@@ -188,6 +315,17 @@ hipError_t launch_ppo_spread_step(hipStream_t s, size_t lds, const PpoSpreadArgs
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ranenv_ppo_spread_reduce_kernel, elem, block, 0, s, a);
     hipLaunchKernelGGL(ranenv_ppo_spread_apply_kernel, elem, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_spread_head_step(hipStream_t s, size_t lds, const PpoHeadSpreadArgs &a)
+{
+    const int grid = ppo_spread_step(a.a.n_rows, a.a.hp.minibatch, a.k.slabs, a.k.step).grid;
+    const dim3 pass((unsigned)grid), elem((unsigned)a.k.blocks), block(256);
+    const hipError_t e = launch_lds<ranenv_ppo_spread_head_pass_kernel>(pass, block, lds, s, a);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ranenv_ppo_spread_head_reduce_kernel, elem, block, 0, s, a);
+    hipLaunchKernelGGL(ranenv_ppo_spread_head_apply_kernel, elem, block, 0, s, a);
     return hipGetLastError();
 }
 
