@@ -7,15 +7,16 @@ Nine objects, compiled in parallel, then linked:
   ranenv_policy.hip     the policy networks (RANENV_POLICY_NETWORK: MLP forwards on the f32 matrix cores, or per net on the bf16 ones)
   ranenv_ppo.hip        the PPO update of the bound nets (ranenv_ppo_update: forward, backward, clip and Adam, one workgroup per member;
                         its six kernels -- uniform populations, mixed populations and nets per slice, each under the plain and the
-                        wide LDS plan -- expand one body, ranenv_ppo_body.hpp; a seventh trains the head policies, ranenv_ppo_update_head)
+                        wide LDS plan -- call one body, a function template; a seventh trains the head policies, ranenv_ppo_update_head)
   ranenv_sac.hip        the SAC update (ranenv_sac_update: per gradient step a critic pass, an actor pass and two elementwise applies,
                         the rows of a minibatch spread over workgroups)
   ranenv_ppo_spread.hip the PPO update of ONE agent spread over the chip (ranenv_ppo_bind_spread: per optimiser step a pass of
                         min(tiles, slabs) workgroups into gradient slabs of their own, an elementwise reduce and an elementwise apply;
                         three more kernels of the same pattern train the head policies with log_std, ranenv_ppo_bind_head_spread)
                         All three are built from ranenv_ppo_parts.hpp, the one statement of every step they share: the backward pass and
-                        its dZ' walk, Adam's constants and element step, and the steps of a PPO minibatch (advantage mean and std,
-                        row list, clipped surrogate, critic row, joint norm and clip, statistics)
+                        its dZ' walk, Adam's constants and element step, the steps of a PPO minibatch (advantage mean and std,
+                        row list, clipped surrogate, critic row, joint norm and clip, statistics), the 32-row tile of the IBSched
+                        nets and of the head pair, and the elementwise reduce and apply of the spread updates
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants
@@ -33,7 +34,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 HDR = os.path.join(REPO, "include", "ranenv.h")
 OUT = os.path.join(HERE, "libranenv_hip.so")
-SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_body.hpp", "ranenv_ppo_parts.hpp", "ranenv_ppo_spread.hip", "ranenv_sac.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
+SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_parts.hpp", "ranenv_ppo_spread.hip", "ranenv_sac.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
 # (object name, source, extra flags)
 UNITS = (("step_np10", "ranenv_step.hip", ("-DRANENV_NP=10",)), ("step_np8", "ranenv_step.hip", ("-DRANENV_NP=8",)),
          ("step_np16", "ranenv_step.hip", ("-DRANENV_NP=16",)), ("aux", "ranenv_aux.hip", ()),

@@ -1,11 +1,12 @@
 // ranenv_ppo_parts.hpp -- the one statement of every step the training kernels share (ranenv_ppo.hip: the PPO updates of the bound nets
 // and of the head policies; ranenv_ppo_spread.hip: one agent's PPO update spread over the chip, the IBSched pair's and the head pair's
-// -- whose tile steps (ppo_head_load_rows, ppo_head_actor_tile) and elementwise reduce / apply steps (ppo_spread_*) stand at the end;
-// ranenv_sac.hip: the SAC update): the LDS size of a net's rows, the backward pass of one 32-row tile on the
-// f32 matrix cores and its dZ' block walk, the workgroup sum in slot order, Adam's constants and float32 element step, and the steps
-// of a PPO minibatch -- zeroing, the advantages' mean and std, the tile's row list, the clipped surrogate, the critic row, the joint
-// norm and clip scale, the statistics, the gradient copy -- and the steps of a tile of the IBSched nets that the member update and the
-// spread update share: the record cell, the tile's input rows, the wide forward pass, the actor's row.  A rule that lives here (the 1e-6 of the clip, the 1e-8 of the std, the tie
+// -- whose elementwise reduce / apply steps (ppo_spread_*) stand at the end; ranenv_sac.hip: the SAC update): the LDS size of a net's
+// rows, the backward pass of one 32-row tile on the f32 matrix cores and its dZ' block walk, the workgroup sum in slot order, Adam's
+// constants and float32 element step, and the steps of a PPO minibatch -- zeroing, the advantages' mean and std, the tile's row list,
+// the clipped surrogate, the critic row, the joint norm and clip scale, the statistics, the gradient copy -- and the 32-row tile
+// itself, once per pair of nets: ppo_tile for the IBSched nets (the member update and the spread pass; its steps: the record cell, the
+// input rows, the wide forward pass, the actor's row) and ppo_head_tile for the head pair (ppo_head_load_rows, ppo_head_actor_tile).
+// A rule that lives here (the weight-read rule at ppo_tile, the tiles' barriers, the 1e-6 of the clip, the 1e-8 of the std, the tie
 // rule of torch.minimum, Adam's operation order) has no second text.  ranenv_ppo.hip's header comment describes the plan they belong to.
 #pragma once
 #include "ranenv_net.hpp"
@@ -177,7 +178,7 @@ __device__ __forceinline__ void ppo_adam(float *w, float *m, float *v, const flo
     for (long long i = tid; i < n; i += 256) adam_elem(w[i], m[i], v[i], g[i] * scale, a);
 }
 
-// ---- the steps of a PPO minibatch (ranenv_ppo_body.hpp and ranenv_ppo_update_kernel_head) ----------------------------------------------
+// ---- the steps of a PPO minibatch (ppo_update_body and ranenv_ppo_update_kernel_head, ranenv_ppo.hip) -------------------------------------
 __device__ __forceinline__ void ppo_zero(float *g, long long floats, int tid)
 {
 #pragma unroll 1
@@ -275,7 +276,7 @@ __device__ __forceinline__ void ppo_grad_out(float *out, const float *g, long lo
     for (long long i = tid; i < floats; i += 256) out[i] = g[i];
 }
 
-// ---- the steps of a tile of the IBSched nets (ranenv_ppo_body.hpp and the spread update, ranenv_ppo_spread.hip) -----------------------
+// ---- the tile of the IBSched nets and its steps (ppo_update_body, ranenv_ppo.hip, and the spread pass, ranenv_ppo_spread.hip) ----------
 constexpr int PPO_FIXED = 4096;           // bytes of LDS in front of the rows: reduction slots, per-row statistics, the tile's record rows
 constexpr int PPO_ROW_STATS = 6;          // per row: policy loss, entropy, logp_old - logp, clipped?, live?, value loss
 
@@ -374,7 +375,49 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
     }
 }
 
-// ---- the steps of a tile of the head policies (ranenv_ppo_update_kernel_head and the spread head update, ranenv_ppo_spread.hip) -------
+// One 32-row tile of a minibatch, entries c0 + t0 .. of `list`: the rows are listed, then per net (0 the actor, 1 the critic) loaded,
+// run forward, turned into dL/d(output) and run backward, and thread 0 adds the rows' statistics to `st`.  The callers differ in where
+// net k's descriptor lies (net_at(k) -> const PolicyNet &: the kernel argument, or the member's copy in LDS), where its weights are
+// (w_at(k)) and where its gradient goes (g_at(k): the member's block, or the workgroup's slab).  WIDE: on the workgroup's parked rows
+// `wpark`.  THE WEIGHT-READ RULE of the training kernels stands here and at ppo_head_tile: the weights are what the launch itself, or
+// the launch before, wrote by vector stores, so every weight read -- the forward's float4 and bias loads, the backward's W loads -- is
+// a vector load at a lane-dependent address behind a workgroup barrier, never a read through the scalar cache; log_std is read through
+// its LDS copy.  Ends without a barrier: the next tile's first, or the caller's, is the one behind the backward pass.
+template <bool WIDE, class NetAt, class WAt, class GAt>
+__device__ __forceinline__ void ppo_tile(const PpoArgs &A, const ranenv_ppo_hparams &hp, int kind, int n_nets, const int32_t *list, int c0, int t0, int nb,
+                                         long long n_record, double wrow, double a_mean, double a_den, double *rowstat, int *rowidx, float *act, float *wpark,
+                                         PpoEpoch &st, int tid, NetAt net_at, WAt w_at, GAt g_at)
+{
+    const int lane = tid & 63, wave = tid >> 6, S = A.S;
+    __syncthreads();                           // (the previous tile's backward pass and statistics are read)
+    ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
+    // ---- per net: forward, dL/d(output) per row, backward ---------------------------------------------------------------------------
+#pragma unroll 1
+    for (int k = 0; k < n_nets; k++) {
+        const PolicyNet &net = net_at(k);
+        const float *w = w_at(k);
+        float *g = g_at(k);
+        __syncthreads();                       // (the tile's rows are listed; the actor's backward pass has read its rows)
+        float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
+        ppo_load_rows(net, A, kind, rowidx, cur, tid);
+        __syncthreads();
+        if constexpr (WIDE) cur = ppo_forward_wide(net, w, act, act + ppo_wide_floats(net), wpark, tid);
+        else net_layers<false, true>(net, w, cur, nxt, lane, wave);
+        if (tid < NET_ROWS) {
+            const int i = rowidx[tid], np = net.np[net.n_layers - 1];
+            float *o = cur + tid * net_ld(np);
+            double *rs = rowstat + tid * PPO_ROW_STATS;
+            if (k == 0) ppo_actor_row(A, hp, kind, i, np, o, rs, wrow, a_mean, a_den);
+            else rs[5] = ppo_critic_row(o, i, [&] { return A.traj.vtarg[ppo_cell(kind, i, S)]; }, hp.vf_coeff, wrow);
+        }
+        __syncthreads();
+        if constexpr (WIDE) ppo_backward<true>(net, w, g, cur, tid, act, act + ppo_wide_floats(net), wpark);
+        else ppo_backward(net, w, g, cur, tid);
+    }
+    if (tid == 0) ppo_tile_stats(st, rowstat, PPO_ROW_STATS, n_nets == 2);      // (the barriers above have published the rows')
+}
+
+// ---- the tile of the head policies and its steps (ranenv_ppo_update_kernel_head and the spread head pass, ranenv_ppo_spread.hip) ------
 constexpr int PPO_HEAD_ROW_STATS = 7;     // PPO_ROW_STATS' six, then gl = dL/d(logp) of the row
 static_assert(PPO_FIXED >= (256 + NET_ROWS * PPO_HEAD_ROW_STATS) * 8 + NET_ROWS * 4 + 16 * 4, "the fixed LDS region holds the head kernels' row statistics and log_std");
 
@@ -444,9 +487,46 @@ __device__ __forceinline__ void ppo_head_actor_tile(const PpoHeadArgs &A, const 
     }
 }
 
+// One 32-row tile of a minibatch of the head pair, ppo_tile's steps on the head record (its weight-read rule holds here): the actor's
+// gradient at its outputs is ppo_head_actor_tile's, which adds to thread j's `g_ls`; g_at(k): where net k's gradient goes.
+template <class GAt>
+__device__ __forceinline__ void ppo_head_tile(const PpoHeadArgs &A, const int32_t *list, int c0, int t0, int nb, long long n_record, double wrow, double a_mean,
+                                              double a_den, double *rowstat, int *rowidx, const float *lsw, const double *sig, float *act, double &g_ls,
+                                              PpoEpoch &st, int tid, GAt g_at)
+{
+    const ranenv_ppo_hparams &hp = A.hp;
+    const int lane = tid & 63, wave = tid >> 6;
+    __syncthreads();                           // (the previous tile's backward pass and statistics are read)
+    ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
+#pragma unroll 1
+    for (int k = 0; k < 2; k++) {
+        const PpoNet &pn = A.net[k];
+        const PolicyNet &net = pn.net;
+        __syncthreads();                       // (the tile's rows are listed; the actor's backward pass has read its rows)
+        float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
+        ppo_head_load_rows(net, A, rowidx, cur, tid);
+        __syncthreads();
+        net_layers<false, true>(net, pn.w, cur, nxt, lane, wave);
+        const int np = net.np[net.n_layers - 1], ldo = net_ld(np);
+        if (k == 1) {
+            if (tid < NET_ROWS) {
+                const int i = rowidx[tid];
+                rowstat[tid * PPO_HEAD_ROW_STATS + 5] = ppo_critic_row(cur + tid * ldo, i, [&] { return A.traj.vtarg[i]; }, hp.vf_coeff, wrow);
+            }
+        } else ppo_head_actor_tile(A, rowidx, cur, np, ldo, rowstat, lsw, sig, wrow, a_mean, a_den, g_ls, tid);
+        __syncthreads();
+        ppo_backward(net, pn.w, g_at(k), cur, tid);
+    }
+    if (tid == 0) ppo_tile_stats(st, rowstat, PPO_HEAD_ROW_STATS, true);      // (the barriers above have published the rows')
+}
+
 // ---- the elementwise steps of a spread update (ranenv_ppo_spread.hip: the IBSched kinds' and the head pair's reduce and apply) --------
-// Element e of the packed floats the launch covers: the four arrays' cells, by the caller's layout (actor below its floats, critic behind)
+// Element e of the packed floats the launch covers: the four arrays' cells -- the actor's (n0) below its floats `af`, the critic's behind
 struct PpoSpreadCell { float *g, *w, *m, *v; };
+__device__ __forceinline__ PpoSpreadCell ppo_spread_cell(const PpoNet &n0, const PpoNet &n1, long long af, long long e)
+{
+    return e < af ? PpoSpreadCell{n0.g + e, n0.w + e, n0.m + e, n0.v + e} : PpoSpreadCell{n1.g + (e - af), n1.w + (e - af), n1.m + (e - af), n1.v + (e - af)};
+}
 
 // The reduce of the block's PPO_SPREAD_BLOCK elements: g[e] = the `used` slabs' [e] summed in ascending slab order, the cells zeroed
 // for the next step; returns the thread's float64 share of the block's sum of squares
@@ -495,6 +575,12 @@ __device__ __forceinline__ void ppo_spread_apply_elems(long long floats, float *
         if (grad) grad[e] = g;
         adam_elem(*c.w, *c.m, *c.v, g * sc, adam);
     }
+}
+
+// One thread's: a pass workgroup's row statistics of its tiles -> its PPO_SPREAD_STATS doubles of wstat, which ppo_spread_stats reads back
+__device__ __forceinline__ void ppo_spread_wstat(double *out, const PpoEpoch &st)
+{
+    out[0] = st.pl; out[1] = st.ent; out[2] = st.kl; out[3] = st.cf; out[4] = st.rows; out[5] = st.vl;
 }
 
 // One thread's: the epoch's running sums `run` (PpoEpoch's fields in order) take this step's slab statistics wstat[0..geo.grid) in

@@ -3,7 +3,7 @@
 // optimiser step is three launches on the caller's stream, blockIdx.y the kind (0 inter, 1 intra: two independent optimisers, each with
 // its own step count -- a kind whose steps are used up returns at once):
 //   pass     min(tiles of the minibatch, slabs) workgroups per kind.  Workgroup w walks tiles w, w + grid, ... in ascending order and does
-//            per tile what ranenv_ppo_body.hpp does between its barriers -- the same ranenv_ppo_parts.hpp functions on the same LDS plan,
+//            per tile what a member's workgroup does (ranenv_ppo.hip) -- the one ppo_tile of ranenv_ppo_parts.hpp on the same LDS plan,
 //            plain or wide -- with the backward pass adding into gradient slab w, and writes its rows' statistics to wstat[w].  Every
 //            workgroup computes the minibatch's advantage mean and std itself: the same function in the same order, the same bits.
 //   reduce   elementwise over the kind's packed floats (actor, then critic), PPO_SPREAD_BLOCK per block: g[i] = the used slabs' [i]
@@ -29,7 +29,7 @@ __device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P)
     extern __shared__ float lds[];
     const PpoArgs &A = P.a;
     const ranenv_ppo_hparams &hp = P.hp;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, kind = (int)blockIdx.y;
+    const int tid = (int)threadIdx.x, kind = (int)blockIdx.y;
     const PpoSpreadKind &K = P.k[kind];
     if (P.step >= K.steps) return;
     const PpoSpreadStep geo = ppo_spread_step(K.n, hp.minibatch, P.slabs, P.step);
@@ -57,46 +57,17 @@ __device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P)
         }, a_mean, a_den);
 
 #pragma unroll 1
-    for (int t0 = w * NET_ROWS; t0 < nb; t0 += geo.grid * NET_ROWS) {
-        __syncthreads();                       // (the previous tile's backward pass and statistics are read)
-        ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
-#pragma unroll 1
-        for (int k = 0; k < n_nets; k++) {
-            const PpoNet &pn = A.net[kind][k];
-            const PolicyNet &net = pn.net;
-            const float *wt = pn.w;
-            float *g = slab + (k == 0 ? 0 : A.net[kind][0].floats);
-            __syncthreads();                   // (the tile's rows are listed; the actor's backward pass has read its rows)
-            float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
-            ppo_load_rows(net, A, kind, rowidx, cur, tid);
-            __syncthreads();
-            if constexpr (WIDE) cur = ppo_forward_wide(net, wt, act, act + ppo_wide_floats(net), wpark, tid);
-            else net_layers<false, true>(net, wt, cur, nxt, lane, wave);
-            if (tid < NET_ROWS) {
-                const int i = rowidx[tid], np = net.np[net.n_layers - 1];
-                float *o = cur + tid * net_ld(np);
-                double *rs = rowstat + tid * PPO_ROW_STATS;
-                if (k == 0) ppo_actor_row(A, hp, kind, i, np, o, rs, wrow, a_mean, a_den);
-                else rs[5] = ppo_critic_row(o, i, [&] { return A.traj.vtarg[ppo_cell(kind, i, S)]; }, hp.vf_coeff, wrow);
-            }
-            __syncthreads();
-            if constexpr (WIDE) ppo_backward<true>(net, wt, g, cur, tid, act, act + ppo_wide_floats(net), wpark);
-            else ppo_backward(net, wt, g, cur, tid);
-        }
-        if (tid == 0) ppo_tile_stats(st, rowstat, PPO_ROW_STATS, n_nets == 2);      // (the barriers above have published the rows')
-    }
-    if (tid == 0) {
-        double *out = K.wstat + (size_t)w * PPO_SPREAD_STATS;
-        out[0] = st.pl; out[1] = st.ent; out[2] = st.kl; out[3] = st.cf; out[4] = st.rows; out[5] = st.vl;
-    }
+    for (int t0 = w * NET_ROWS; t0 < nb; t0 += geo.grid * NET_ROWS)
+        ppo_tile<WIDE>(A, hp, kind, n_nets, list, c0, t0, nb, n_record, wrow, a_mean, a_den, rowstat, rowidx, act, wpark, st, tid,
+                       [&](int k) -> const PolicyNet & { return A.net[kind][k].net; }, [&](int k) -> const float * { return A.net[kind][k].w; },
+                       [&](int k) { return slab + (k == 0 ? 0 : A.net[kind][0].floats); });
+    if (tid == 0) ppo_spread_wstat(K.wstat + (size_t)w * PPO_SPREAD_STATS, st);
 }
 
 __global__ void __launch_bounds__(256) ranenv_ppo_spread_pass_kernel(PpoSpreadArgs P) { spread_pass<false>(P); }
 __global__ void __launch_bounds__(256) ranenv_ppo_spread_pass_kernel_wide(PpoSpreadArgs P) { spread_pass<true>(P); }
 
-// Element e of the kind's packed floats: the actor's below its floats, the critic's behind
-#define SPREAD_AT(field, e) ((e) < af ? A.net[kind][0].field + (e) : A.net[kind][1].field + ((e) - af))
-
+// The reduce and the apply are the elementwise functions of ranenv_ppo_parts.hpp (ppo_spread_*), the head pair's kernels' too
 __global__ void __launch_bounds__(256) ranenv_ppo_spread_reduce_kernel(PpoSpreadArgs P)
 {
     __shared__ double red[256];
@@ -106,23 +77,7 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_reduce_kernel(PpoSpread
     if (P.step >= K.steps || (int)blockIdx.x >= K.blocks) return;
     const int used = ppo_spread_step(K.n, P.hp.minibatch, P.slabs, P.step).grid;
     const long long af = A.net[kind][0].floats, floats = spread_floats(A, kind);
-    double s = 0.0;
-#pragma unroll 1
-    for (int j = 0; j < PPO_SPREAD_BLOCK / 256; j++) {
-        const long long e = (long long)blockIdx.x * PPO_SPREAD_BLOCK + j * 256 + tid;
-        if (e >= floats) break;
-        float *p = K.slab + e;
-        float g = *p;
-        *p = 0.0f;
-#pragma unroll 1
-        for (int u = 1; u < used; u++) {
-            p += K.slab_stride;
-            g = g + *p;
-            *p = 0.0f;
-        }
-        *SPREAD_AT(g, e) = g;
-        s += (double)g * (double)g;
-    }
+    const double s = ppo_spread_reduce_elems(K.slab, K.slab_stride, used, floats, tid, [&](long long e) { return ppo_spread_cell(A.net[kind][0], A.net[kind][1], af, e); });
     const double tot = ppo_sum(red, s, tid);
     if (tid == 0) K.bpart[blockIdx.x] = tot;
 }
@@ -134,61 +89,37 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_apply_kernel(PpoSpreadA
     const int tid = (int)threadIdx.x, kind = (int)blockIdx.y;
     const PpoSpreadKind &K = P.k[kind];
     if (P.step >= K.steps || (int)blockIdx.x >= K.blocks) return;
-    double tot = 0.0;
-#pragma unroll 1
-    for (int b = 0; b < K.blocks; b++) tot += K.bpart[b];
-    const double norm = sqrt(tot);
+    const double norm = sqrt(ppo_spread_norm2(K.bpart, K.blocks));
     const float sc = (float)ppo_clip_scale(hp.grad_clip, norm);
     const int t_call = K.t0[0];
     const AdamStep adam = adam_step(hp.lr, hp.beta1, hp.beta2, hp.eps, t_call + P.step + 1);
     const bool last = P.step == K.steps - 1;
     const long long af = A.net[kind][0].floats, floats = spread_floats(A, kind);
     float *const grad = last && A.grad ? A.grad + (size_t)kind * (size_t)A.grad_stride : nullptr;
-#pragma unroll 1
-    for (int j = 0; j < PPO_SPREAD_BLOCK / 256; j++) {
-        const long long e = (long long)blockIdx.x * PPO_SPREAD_BLOCK + j * 256 + tid;
-        if (e >= floats) break;
-        const float g = *SPREAD_AT(g, e);
-        if (grad) grad[e] = g;
-        adam_elem(*SPREAD_AT(w, e), *SPREAD_AT(m, e), *SPREAD_AT(v, e), g * sc, adam);
-    }
+    ppo_spread_apply_elems(floats, grad, sc, adam, tid, [&](long long e) { return ppo_spread_cell(A.net[kind][0], A.net[kind][1], af, e); });
     if (blockIdx.x != 0 || tid != 0) return;
     // ---- block 0: the epoch's statistics and the counter ---------------------------------------------------------------------------
     const PpoSpreadStep geo = ppo_spread_step(K.n, hp.minibatch, P.slabs, P.step);
-    PpoEpoch st;
-    if (geo.mb > 0) { st.pl = K.run[0]; st.vl = K.run[1]; st.ent = K.run[2]; st.kl = K.run[3]; st.cf = K.run[4]; st.gn = K.run[5]; st.rows = K.run[6]; st.n_mb = (int)K.run[7]; }
-#pragma unroll 1
-    for (int u = 0; u < geo.grid; u++) {
-        const double *ws = K.wstat + (size_t)u * PPO_SPREAD_STATS;
-        st.pl += ws[0]; st.ent += ws[1]; st.kl += ws[2]; st.cf += ws[3]; st.rows += ws[4]; st.vl += ws[5];
-    }
-    st.gn += norm * (double)geo.nb;
-    st.n_mb += 1;
-    if (geo.mb == ppo_spread_per_epoch(K.n, hp.minibatch) - 1) ppo_epoch_stats(A.stats + ((size_t)kind * (size_t)A.max_epochs + geo.ep) * RANENV_PPO_STATS, st, K.n);
-    else { K.run[0] = st.pl; K.run[1] = st.vl; K.run[2] = st.ent; K.run[3] = st.kl; K.run[4] = st.cf; K.run[5] = st.gn; K.run[6] = st.rows; K.run[7] = (double)st.n_mb; }
+    ppo_spread_stats(K.run, K.wstat, geo, norm, geo.mb == ppo_spread_per_epoch(K.n, hp.minibatch) - 1,
+                     A.stats + ((size_t)kind * (size_t)A.max_epochs + geo.ep) * RANENV_PPO_STATS, K.n);
     if (last) A.t[kind] = t_call + K.steps;
 }
-#undef SPREAD_AT
-
-// (the same for the head pair's kernels, as the cell the shared elementwise functions of ranenv_ppo_parts.hpp take)
-#define SPREAD_CELL(n0, n1) [&](long long e) { return e < af ? PpoSpreadCell{(n0).g + e, (n0).w + e, (n0).m + e, (n0).v + e} \
-                                                             : PpoSpreadCell{(n1).g + (e - af), (n1).w + (e - af), (n1).m + (e - af), (n1).v + (e - af)}; }
 
 // ---- the head policies over the chip (ranenv_ppo_bind_head_spread; include/ranenv.h "Head policies over the chip") -------------------
 // The same three launches for the head actor, the head critic and log_std [S] on a ranenv_collect_head record: no kinds (a 1-D grid),
-// the tile steps of ranenv_ppo_update_kernel_head, and a third parameter tensor.  Thread j < S of pass workgroup w keeps the
+// the tile of ranenv_ppo_update_kernel_head (ppo_head_tile), and a third parameter tensor.  Thread j < S of pass workgroup w keeps the
 // workgroup's d/d log_std_j in float64 over its tiles and writes it UNROUNDED to gls[w][j]; block 0 of the reduce adds the used slabs'
 // in ascending order in float64 and rounds once into ls_g[j] -- where the one-workgroup kernel rounds -- and adds the squares into its
 // block partial, so the joint norm covers log_std; block 0 of the apply runs Adam on log_std beside its elements.
 // log_std is a weight the previous apply rewrote: the pass loads it into LDS (`lsw`) by lane j at a lane-dependent address, as
-// ranenv_ppo.hip's header asks of every weight; sig[j] = exp(log_std_j) in float64 stands in the reduction slots behind the advantage pass.
+// the weight-read rule at ppo_tile asks of every weight; sig[j] = exp(log_std_j) in float64 stands in the reduction slots behind the advantage pass.
 __global__ void __launch_bounds__(256) ranenv_ppo_spread_head_pass_kernel(PpoHeadSpreadArgs P)
 {
     extern __shared__ float lds[];
     const PpoHeadArgs &A = P.a;
     const ranenv_ppo_hparams &hp = A.hp;
     const PpoHeadSpread &K = P.k;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, S = A.S;
+    const int tid = (int)threadIdx.x, S = A.S;
     const PpoSpreadStep geo = ppo_spread_step(A.n_rows, hp.minibatch, K.slabs, K.step);
     const int w = (int)blockIdx.x;
     if (w >= geo.grid) return;
@@ -216,35 +147,11 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_head_pass_kernel(PpoHea
     if (tid < S) sig[tid] = exp((double)lsw[tid]);      // (thread j reads what thread j wrote; published by the tile loop's first barrier)
 
 #pragma unroll 1
-    for (int t0 = w * NET_ROWS; t0 < nb; t0 += geo.grid * NET_ROWS) {
-        __syncthreads();                       // (the previous tile's backward pass and statistics are read)
-        ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
-#pragma unroll 1
-        for (int k = 0; k < 2; k++) {
-            const PpoNet &pn = A.net[k];
-            const PolicyNet &net = pn.net;
-            __syncthreads();                   // (the tile's rows are listed; the actor's backward pass has read its rows)
-            float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
-            ppo_head_load_rows(net, A, rowidx, cur, tid);
-            __syncthreads();
-            net_layers<false, true>(net, pn.w, cur, nxt, lane, wave);
-            const int np = net.np[net.n_layers - 1], ldo = net_ld(np);
-            if (k == 1) {
-                if (tid < NET_ROWS) {
-                    const int i = rowidx[tid];
-                    rowstat[tid * PPO_HEAD_ROW_STATS + 5] = ppo_critic_row(cur + tid * ldo, i, [&] { return A.traj.vtarg[i]; }, hp.vf_coeff, wrow);
-                }
-            } else ppo_head_actor_tile(A, rowidx, cur, np, ldo, rowstat, lsw, sig, wrow, a_mean, a_den, g_ls, tid);
-            __syncthreads();
-            ppo_backward(net, pn.w, slab + (k == 0 ? 0 : A.net[0].floats), cur, tid);
-        }
-        if (tid == 0) ppo_tile_stats(st, rowstat, PPO_HEAD_ROW_STATS, true);      // (the barriers above have published the rows')
-    }
+    for (int t0 = w * NET_ROWS; t0 < nb; t0 += geo.grid * NET_ROWS)
+        ppo_head_tile(A, list, c0, t0, nb, n_record, wrow, a_mean, a_den, rowstat, rowidx, lsw, sig, act, g_ls, st, tid,
+                      [&](int k) { return slab + (k == 0 ? 0 : A.net[0].floats); });
     if (tid < S) K.gls[(size_t)w * S + tid] = g_ls;
-    if (tid == 0) {
-        double *out = K.wstat + (size_t)w * PPO_SPREAD_STATS;
-        out[0] = st.pl; out[1] = st.ent; out[2] = st.kl; out[3] = st.cf; out[4] = st.rows; out[5] = st.vl;
-    }
+    if (tid == 0) ppo_spread_wstat(K.wstat + (size_t)w * PPO_SPREAD_STATS, st);
 }
 
 __global__ void __launch_bounds__(256) ranenv_ppo_spread_head_reduce_kernel(PpoHeadSpreadArgs P)
@@ -255,7 +162,7 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_head_reduce_kernel(PpoH
     const int tid = (int)threadIdx.x, S = A.S;
     const int used = ppo_spread_step(A.n_rows, A.hp.minibatch, K.slabs, K.step).grid;
     const long long af = A.net[0].floats, floats = af + A.net[1].floats;
-    double s = ppo_spread_reduce_elems(K.slab, K.slab_stride, used, floats, tid, SPREAD_CELL(A.net[0], A.net[1]));
+    double s = ppo_spread_reduce_elems(K.slab, K.slab_stride, used, floats, tid, [&](long long e) { return ppo_spread_cell(A.net[0], A.net[1], af, e); });
     if (blockIdx.x == 0 && tid < S) {          // log_std: the slabs' float64 partials in ascending order, rounded once
         double g = K.gls[tid];
 #pragma unroll 1
@@ -281,7 +188,7 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_head_apply_kernel(PpoHe
     const bool last = K.step == K.steps - 1;
     const long long af = A.net[0].floats, floats = af + A.net[1].floats;
     float *const grad = last ? A.grad : nullptr;
-    ppo_spread_apply_elems(floats, grad, sc, adam, tid, SPREAD_CELL(A.net[0], A.net[1]));
+    ppo_spread_apply_elems(floats, grad, sc, adam, tid, [&](long long e) { return ppo_spread_cell(A.net[0], A.net[1], af, e); });
     if (blockIdx.x != 0) return;
     // ---- block 0: log_std, the epoch's statistics and the counter --------------------------------------------------------------------
     if (tid < S) {
@@ -294,7 +201,6 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_head_apply_kernel(PpoHe
     ppo_spread_stats(K.run, K.wstat, geo, norm, geo.mb == ppo_spread_per_epoch(A.n_rows, hp.minibatch) - 1, A.stats + (size_t)geo.ep * RANENV_PPO_STATS, A.n_rows);
     if (last) A.t[0] = t_call + K.steps;
 }
-#undef SPREAD_CELL
 
 }  // namespace
 
