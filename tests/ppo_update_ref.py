@@ -60,14 +60,16 @@ def net_ld(x):
     return x + (36 if x % 64 else 4)
 
 
+def pair_lds_bytes(*nets):
+    """The header's formula for ONE kind's pair, nets given as widths [in, hidden..., out] (None: not bound): 4096 + 128 * sum over the
+    input and the layers of ld(width padded to 32), the larger of actor and critic"""
+    return max(4096 + 128 * sum(net_ld(pad32(w)) for w in dims) for dims in nets if dims is not None)
+
+
 def lds_bytes(S_, Us, layout, actor_widths, critic_widths):
-    """The header's formula: 4096 + 128 * sum over the input and the layers of ld(width padded to 32), the larger of actor and critic,
-    the larger of the two kinds"""
-    need = 0
-    for n_in, n_out in ((10 * S_, 2 * S_), (intra_width(Us, layout), 3)):
-        for widths, out in ((actor_widths, n_out), (critic_widths, 1)):
-            need = max(need, 4096 + 128 * sum(net_ld(pad32(w)) for w in [n_in] + list(widths) + [out]))
-    return need
+    """... and the larger of the two kinds' pairs"""
+    return max(pair_lds_bytes([n_in] + list(actor_widths) + [n_out], [n_in] + list(critic_widths) + [1])
+               for n_in, n_out in ((10 * S_, 2 * S_), (intra_width(Us, layout), 3)))
 
 
 def member_nets(case, G, seed=4100):

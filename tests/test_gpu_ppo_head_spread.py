@@ -19,10 +19,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import ppo_bindings_shapes_ref as bs
 from tests import ppo_head_ref as hd
-from tests import ppo_head_shapes_ref as hg
 from tests import ppo_update_ref as ref
-from tests.gpu_common import _ordered, need_gpu
+from tests.gpu_common import need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -32,35 +32,7 @@ TRAIN = dict(lr=3e-4, grad_clip=0.5, clip=0.2, vf_coeff=0.5, ent_coeff=0.01)
 STAT_NAMES = ("policy_loss", "value_loss", "entropy", "kl", "clip_frac")
 
 
-def _spec(case):
-    return hg.CASES[case] if case in hg.CASES else case
-
-
-def _env(case, slabs=None, T=hd.T, **kw):
-    """(env, layers, noisy record) of a case under the plain head binding (slabs None) or the spread one"""
-    need_gpu()
-    env, lay = (hg.make_env(case, ppo=False, **kw) if case in hg.CASES else hd.make_env(case, ppo=False, **kw))
-    _bind(env, slabs)
-    return env, lay, hd.with_noise(hd.collect(env, _spec(case), T=T))
-
-
-def _bind(env, slabs):
-    if slabs is None:
-        env.ppo_bind(head=True)
-    else:
-        env.ppo_bind(head=True, spread=True, slabs=slabs)
-
-
-def _dev(order, env):
-    return order.to(env.device).contiguous()
-
-
-def _twins(case, slabs_a, slabs_b, **kw):
-    a, lay, rec_a = _env(case, slabs_a, **kw)
-    b, _, rec_b = _env(case, slabs_b, **kw)
-    for k in rec_a:
-        assert torch.equal(rec_a[k], rec_b[k]), k
-    return a, rec_a, b, rec_b, lay
+_spec, _env, _bind, _dev, _twins = bs.head_spec, bs.head_env, bs.head_bind, bs.to_dev, bs.head_twins
 
 
 # ---- 1. one slab ----------------------------------------------------------------------------------------------------------------------
@@ -124,33 +96,7 @@ def test_one_adam_step_at_three_slabs(case):
     S = hd.CASES[case][0]
     hp = dict(ONE, lr=1e-3, grad_clip=0.05)
     out = env.ppo_update_head(rec, order=_dev(hd.row_order(1), env), grad=True, eps=1e-5, **hp)
-    g = hd.unpack_head_grad(out["grad"].cpu().numpy(), lay[0], lay[2], S, dtype=np.float32)
-    none = np.zeros(0, dtype=np.float32)
-    w0 = [(w.numpy(), b.numpy()) for w, b in lay[0] + lay[2]] + [(lay[1].numpy(), none)]
-    want, norm, want_m, want_v = ref.adam_step_f32(w0, g["actor"] + g["critic"] + [(g["log_std"], none)], 1, 1e-3, 0.05, (0.9, 0.999), 1e-5, moments=True)
-    assert abs(out["grad_norm"][0] - norm) <= 1e-9 * norm and norm > 0.05
-    no_ls = float(np.sqrt(sum(float((x.astype(np.float64) ** 2).sum()) for pair in g["actor"] + g["critic"] for x in pair)))
-    assert abs(out["grad_norm"][0] - no_ls) > 100 * 1e-9 * norm, "a norm without log_std's gradient"
-    a1, ls1, c1 = hd.head_weights(env)
-    got = [(w.numpy(), b.numpy()) for w, b in a1 + c1] + [(ls1.numpy(), none)]
-    worst = 0
-    for (xw, xb), (yw, yb) in zip(want, got):
-        for x, y in ((xw, yw), (xb, yb)):
-            if x.size:
-                worst = max(worst, int(np.abs(_ordered(x) - _ordered(y)).max()))
-    st = {k: env.ppo_head_state(k) for k in ("actor", "critic", "log_std")}
-    assert st["log_std"]["m"].numel() == S and int(st["actor"]["t"].cpu()[0]) == 1
-    worst_mv = 0
-    for name, want_x in (("m", want_m), ("v", want_v)):
-        nets = ref.unpack_grad(np.concatenate([st["actor"][name].cpu().numpy(), st["critic"][name].cpu().numpy()]), lay[0], lay[2], dtype=np.float32)
-        got_x = nets["actor"] + nets["critic"] + [(st["log_std"][name].cpu().numpy(), none)]
-        for (xw, xb), (yw, yb) in zip(want_x, got_x):
-            for x, y in ((xw, yw), (xb, yb)):
-                if x.size:
-                    worst_mv = max(worst_mv, int(np.abs(_ordered(x) - _ordered(y)).max()))
-    print(f"{case}, 3 slabs: Adam step, worst ulp distance {worst} (weights, log_std), {worst_mv} (moments)")
-    assert worst <= 4 and worst_mv <= 4
-    assert not np.array_equal(ls1.numpy(), lay[1].numpy()) and st["log_std"]["m"].cpu().numpy().any()
+    bs.check_head_adam_step(env, lay, out, S, f"{case}, 3 slabs", 1e-3, 0.05, 1e-5)
     env.close()
 
 

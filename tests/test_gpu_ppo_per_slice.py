@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import ppo_bindings_shapes_ref as bs
 from tests import ppo_update_ref as ref
 from tests.gpu_common import need_gpu, shaped_workload, to_host
 
@@ -25,7 +26,7 @@ S, US, B, T, MB = 3, 4, 6, 8, 12
 SMALL, BIG = 20, 40
 ALL = ref.ALL
 HP = dict(lr=2e-3, clip=0.2, vf_coeff=0.5, ent_coeff=0.01, grad_clip=0.5)
-STAT_NAMES = ("policy_loss", "value_loss", "entropy", "kl", "clip_frac", "grad_norm", "rows", "minibatches")
+STAT_NAMES = bs.STAT_NAMES
 
 
 def _nets(case, seed=4100):
@@ -61,64 +62,11 @@ def _shared_env(case, nets, s):
 
 
 def _order(rec, epochs, empty=None, seed=3):
-    """Explicit row lists with the docstring's shares; returns (order, the slices' shares [S]).  Asserts the counts."""
-    mask = rec["mask_inter"].cpu().numpy() != 0
-    live = [np.nonzero(mask[:, :, s].reshape(-1))[0] * S + s for s in range(S)]          # rows (t * B + b) * S + s, ascending
-    big = int(np.argmax([len(x) for x in live]))
-    small = (big + 1) % S
-    rest = 3 - big - small
-    assert len(live[big]) >= BIG and len(live[small]) >= SMALL and len(live[rest]) >= 32, [len(x) for x in live]
-    rng = lambda *key: np.random.default_rng([seed, *key])  # noqa: E731  (one stream per draw: an emptied share moves no other draw)
-    keep = {big: rng(100, big).permutation(live[big])[:BIG], small: rng(100, small).permutation(live[small])[:SMALL], rest: live[rest]}
-    if empty is not None:
-        keep[empty] = keep[empty][:0]
-    counts = [len(keep[s]) for s in range(S)]
-    assert empty == small or (counts[small] == SMALL and SMALL < 32 and SMALL % MB != 0), "a share below one tile with a short last minibatch"
-    assert empty == big or (counts[big] == BIG and BIG > 32 and BIG % MB != 0), "a share beyond one tile with a short last minibatch"
-    assert empty is None or counts[empty] == 0
-    intra = np.stack([np.concatenate([rng(ep, s).permutation(keep[s]) for s in range(S)]) for ep in range(epochs)]).astype(np.int32)
-    inter = np.stack([rng(ep, S).permutation(T * B) for ep in range(epochs)]).astype(np.int32)
-    dev = rec["logp"].device
-    order = {"order_inter": torch.as_tensor(inter, device=dev).contiguous(), "first_inter": np.array([0, T * B], dtype=np.int32),
-             "order_intra": torch.as_tensor(intra.reshape(epochs, -1), device=dev).contiguous(),
-             "first_intra": np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)}
-    return order, counts
+    """Explicit row lists with the docstring's shares (bs.slice_order); returns (order, the slices' shares [S]).  Asserts the counts."""
+    return bs.slice_order(rec, epochs, MB, SMALL, BIG, empty, seed)
 
 
-def _share(order, s):
-    """The lists of a plain one-member call that trains the inter pair and slice s's share alone"""
-    lo, hi = int(order["first_intra"][s]), int(order["first_intra"][s + 1])
-    return dict(order, order_intra=order["order_intra"][:, lo:hi].contiguous(), first_intra=np.array([0, hi - lo], dtype=np.int32))
-
-
-def _host(layers):
-    return [(w.cpu().numpy().copy(), b.cpu().numpy().copy()) for w, b in layers]
-
-
-def _slice_state(env, s):
-    """Slice s's trainable state (s None: the inter pair's) as host bytes: weights, moments, counter"""
-    out = {}
-    for r in (("inter", "v_inter") if s is None else ("intra", "v_intra")):
-        for i, (w, b) in enumerate(_host(env.net_weights(r) if s is None else env.net_weights(r, slice=s))):
-            out[f"{r}/w{i}"], out[f"{r}/b{i}"] = w, b
-        for k, v in env.ppo_state(r, slice=0 if s is None else s).items():
-            out[f"{r}/{k}"] = v.cpu().numpy().copy()
-    return out
-
-
-def _plain_state(env, kind):
-    out = {}
-    for r in (("inter", "v_inter") if kind == 0 else ("intra", "v_intra")):
-        for i, (w, b) in enumerate(_host(env.net_weights(r))):
-            out[f"{r}/w{i}"], out[f"{r}/b{i}"] = w, b
-        for k, v in env.ppo_state(r).items():
-            out[f"{r}/{k}"] = v.cpu().numpy().copy()
-    return out
-
-
-def _row(out, wg):
-    """Workgroup wg's statistics [epochs, 8] and gradient bytes of a per-slice call"""
-    return np.stack([out[n][wg] for n in STAT_NAMES], axis=-1), out["grad"][wg].cpu().numpy()
+_share, _host, _slice_state, _plain_state, _row = bs.share, bs.host, bs.slice_state, bs.plain_state, bs.wg_row
 
 
 _RUNS = {}
@@ -164,23 +112,7 @@ def test_every_slice_bit_for_bit_against_the_plain_kernel_on_one_shared_pair(cas
     assert all(run["slices"][s][k].tobytes() != run["start"][s][k].tobytes() for s in range(S) for k in ("intra/w0", "v_intra/w0")), "a slice did not train"
 
 
-class _SliceView:
-    """Slice s of a per-slice handle as the one member of the comparisons in tests/ppo_update_ref.py"""
-    def __init__(self, env, s):
-        self.env, self.s = env, s
-
-    def ppo_state(self, role, m=0):
-        return self.env.ppo_state(role, slice=self.s)
-
-    def weights(self):
-        return {"inter": {0: _host(self.env.net_weights("inter"))}, "v_inter": {0: _host(self.env.net_weights("v_inter"))},
-                "intra": {0: _host(self.env.net_weights("intra", slice=self.s))}, "v_intra": {0: _host(self.env.net_weights("v_intra", slice=self.s))}}
-
-    def out(self, out):
-        """A per-slice call's result in ``ppo_update``'s shape for one member: kind 0 the inter pair, kind 1 this slice"""
-        o = {n: np.stack([out[n][0], out[n][1 + self.s]])[None] for n in STAT_NAMES}
-        o["grad"] = torch.stack([out["grad"][0], out["grad"][1 + self.s]])[None]
-        return o
+_SliceView = bs.SliceView
 
 
 @pytest.mark.parametrize("case", list(ref.CASES))
