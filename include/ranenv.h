@@ -1126,12 +1126,24 @@ int ranenv_autoreset_part(ranenv_handle h, int32_t part, const uint8_t *dev_done
  *                                                 the same bits wherever it can be read: every launch boundary, every end of a persistent launch and every
  *                                                 episode end is a last TTI.  One-TTI launches (ranenv_step, rollouts under a policy net, a head, slice
  *                                                 metrics or a trace), resets and dense launches always run all of it
- *   "last_rollout_persistent" / "last_rollout_launches" / "last_rollout_member_lines" / "last_rollout_lean_ttis" (read only)   what the last
+ *   "lean_state"   RANENV_LEAN_STATE     1         the same launches: 1 = only an env's last TTI before another workgroup, another kernel or the host can
+ *                                                 look -- the launch's last TTI, and in a persistent launch the last TTI of every chunk -- stores the per-UE
+ *                                                 state that the next TTI of the same workgroup holds in registers or never reads (queue_pkts, win_sent,
+ *                                                 se_mean, rb_start, rb_count, the UE's push counter), and that TTI does not load it back; every build
+ *                                                 but the packed-waves one keeps queue_age_sum, win_dropped and the age list's head the same way.
+ *                                                 The age list's entries and the window's slots are written every TTI.  0 = every TTI stores and loads
+ *                                                 all of it (for A/B runs and bisection).  Whatever the value, every buffer and every view holds the same
+ *                                                 bits wherever it can be read.  One-TTI launches, resets and dense launches always store all of it
+ *                                                 (counted by the read-only "last_rollout_kept_state_ttis", below)
+ *   "last_rollout_persistent" / "last_rollout_launches" / "last_rollout_member_lines" / "last_rollout_lean_ttis" / "last_rollout_kept_state_ttis" (read only)   what the last
  *                                                 ranenv_rollout / ranenv_collect* call ran: 1 = persistent work-queue launches (else launches of <= 10
  *                                                 TTIs per partition); how many step-kernel launches it enqueued; 1 = step launches of it read the
  *                                                 member-lines copy; the TTIs its step launches enqueued WITHOUT the observation tail ("lean_tail"),
  *                                                 summed over the launches: n_tti - 1 for a launch of n_tti TTIs, 0 for one-TTI launches and with
- *                                                 "lean_tail" = 0
+ *                                                 "lean_tail" = 0; and the TTIs they enqueued WITHOUT the per-UE state's stores ("lean_state"), counted the
+ *                                                 same way: n_tti - 1 per launch, 0 for one-TTI launches and with "lean_state" = 0.  For a persistent
+ *                                                 launch that is the upper bound, reached when no chunk ends inside the launch: every chunk end stores the
+ *                                                 state as well
  *   "step_launches_<build>" / "step_launches_<build>_many" (read only)   which build of the step kernel the handle's step launches ran, <build> one of
  *                                                 lean, small, gather, tiny1, mixed, packed, persist, persist_tiny: launches of the step kernel in step mode
  *                                                 that succeeded since ranenv_create (resets and dense launches are not counted), and the share of them

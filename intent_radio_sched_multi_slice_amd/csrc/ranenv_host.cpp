@@ -95,6 +95,7 @@ struct ranenv {
     int *d_perr_dev = nullptr;     // ... its address as the device sees it
     int perr_seen = 0;             // ... what of it has been reported
     int last_rollout_persistent = 0, last_rollout_launches = 0;   // what the last ranenv_rollout call ran (read-only options)
+    long long last_rollout_kept_state_ttis = 0;   // ... and the TTIs they enqueued without the per-UE state's stores (option "lean_state": n_tti - 1 per launch)
     long long last_rollout_lean_ttis = 0;   // ... and the TTIs its step launches enqueued without the observation tail (option "lean_tail": n_tti - 1 per launch)
     // MODE_STEP launches of the step kernel that succeeded since ranenv_create, per StepBuild; [1]: those of several TTIs (read-only options
     // "step_launches_<build>" / "..._many").  Enqueues: a replayed graph counts once, at its capture.
@@ -413,6 +414,9 @@ hipError_t launch_step_counted(ranenv_handle h, const StepLaunch &l, dim3 grid, 
         if (l.members) h->last_rollout_member_lines = 1;
         // (a build of several TTIs runs the whole observation tail at an env's last TTI of the launch only: KP::lean_tail, step_body's LEAN)
         if ((l.mode & 3) == MODE_STEP && l.many && kp.lean_tail != 0 && kp.n_tti > 1) h->last_rollout_lean_ttis += kp.n_tti - 1;
+        // (... and stores the per-UE state at an env's last TTI before it can go cold only: KP::lean_state.  A persistent launch flushes at every
+        // chunk end as well: the figure is its upper bound, reached when no chunk ends inside the launch)
+        if ((l.mode & 3) == MODE_STEP && l.many && kp.lean_state != 0 && kp.n_tti > 1) h->last_rollout_kept_state_ttis += kp.n_tti - 1;
     } else {
         char buf[160];
         snprintf(buf, sizeof(buf), "step kernel build '%s' (row width %d, mode %d, %s, %s): %s", known ? step_build_names[l.build] : "?", l.np, l.mode,
@@ -442,7 +446,7 @@ StepChoice step_choice(const ranenv *h, const StepFacts &f)
     // (whole-batch launches only: for the ranges of a partitioned batch per-range lists were built and measured -- two alternating
     // ranges 47.8 against 48.0 us per TTI in gather mode, and the streaming kernel loses the lane = UE order it wants there: dropped)
     const bool mixed = step && !pe && h->mix != 0 && f.compact != 0 && h->nt == 2 * WAVE && f.e0 == 0 && f.n == h->cfg.batch && !f.masked &&
-                       (h->mix == 2 || !persist_tiny(h)) && RANENV_DIAG == 0;
+                       (h->mix == 2 || !persist_tiny(h)) && (RANENV_DIAG == 0 || RANENV_DIAG == 13);
     const int compact = f.compact != 0 && (mixed || f.gather || f.compact == 2) ? 1 : 0;
     const dim3 grid((unsigned)f.n), block((unsigned)h->nt);
     if (mixed) return {{h->np, SB_MIXED, MODE_STEP, many, f.gather}, grid, dim3(2 * WAVE), compact};      // (grid: an upper bound of wide + ceil(narrow / 2))
@@ -1042,6 +1046,7 @@ const Option options[] = {
     {"member_lines", true, [](H h, long long v) { h->member_lines = v < 0 ? -1 : (v != 0 ? 1 : 0); return 0; }, [](H h) -> long long { return h->member_lines; }},
     // (kept in the handle's argument block: every call's KP is a copy of it)
     {"lean_tail", true, [](H h, long long v) { h->kp.lean_tail = v != 0 ? 1 : 0; return 0; }, [](H h) -> long long { return h->kp.lean_tail; }},
+    {"lean_state", true, [](H h, long long v) { h->kp.lean_state = v != 0 ? 1 : 0; return 0; }, [](H h) -> long long { return h->kp.lean_state; }},
 };
 
 const Option *find_option(const std::string &k)
@@ -1138,6 +1143,7 @@ int ranenv_create(const ranenv_config *cfg, ranenv_handle *out)
     kp.bw_hz = cfg->bandwidth_hz; kp.bw_per_rb = cfg->bandwidth_hz / (double)R; kp.over = cfg->overfulfill;
     kp.norm_traffic = cfg->norm_traffic; kp.norm_ues = cfg->norm_ues; kp.norm_se = cfg->norm_se;
     kp.lean_tail = 1;
+    kp.lean_state = 1;
     int rc = RANENV_OK;
 #define ALLOC(field, count) if (rc == RANENV_OK) rc = dev_alloc(h, &field, (count))
     const size_t NSL = (size_t)S * GRP;
@@ -1212,6 +1218,7 @@ int ranenv_get_option(ranenv_handle h, const char *key, int64_t *value)
     else if (k == "last_rollout_persistent") *value = h->last_rollout_persistent;      // what the last ranenv_rollout call ran:
     else if (k == "last_rollout_launches") *value = h->last_rollout_launches;          // 1 = persistent work-queue launches; step-kernel launches enqueued
     else if (k == "last_rollout_member_lines") *value = h->last_rollout_member_lines;  // 1 = its step launches read the member-lines copy
+    else if (k == "last_rollout_kept_state_ttis") *value = h->last_rollout_kept_state_ttis;      // TTIs its step launches enqueued without the per-UE state's stores
     else if (k == "last_rollout_lean_ttis") *value = h->last_rollout_lean_ttis;        // TTIs its step launches enqueued without the observation tail
     else if (k.rfind("step_launches_", 0) == 0) {      // MODE_STEP launches per build since ranenv_create; "..._many": those of several TTIs
         std::string b = k.substr(14);
@@ -3584,7 +3591,7 @@ static RolloutPlan rollout_plan(const ranenv *h, const Rollout &r, bool capturin
     RolloutPlan p{false, one_tti ? 1 : (h->fuse > 0 ? h->fuse : std::clamp(k / FUSE_ROLLOUT_PART, 1, FUSE_MAX_TTIS)), false};
     const bool wins = persist_tiny(h) || (!h->small_batch && (gather ? B <= PERSIST_GATHER_MAX_ENVS_PER_CU * N
                           : B <= PERSIST_STREAM_MAX_ENVS_PER_CU * N && k >= PERSIST_STREAM_MIN_TTIS && k <= PERSIST_STREAM_MAX_TTIS));
-    p.persistent = (RANENV_DIAG == 0 || RANENV_DIAG == 12) && (h->persist == 1 || (h->persist < 0 && wins)) && !one_tti && !scale_per_element(h) &&
+    p.persistent = (RANENV_DIAG == 0 || RANENV_DIAG == 12 || RANENV_DIAG == 13) && (h->persist == 1 || (h->persist < 0 && wins)) && !one_tti && !scale_per_element(h) &&
                    r.kp.compact != 0 && (B >> PERSIST_ENV_BITS) == 0 && !capturing;      // (its classes are those of the compact lane order; it reads the class counts back)
     int n_ends = 0;
     if (p.persistent && h->persist < 0 && r.follow) (void)ttis_to_end(h, r, 0, h->cfg.batch, k, &n_ends);
@@ -3662,7 +3669,7 @@ static int rollout_run(ranenv_handle h, int32_t n_steps, float *obs_inter, float
     Rollout r;
     r.n_steps = n_steps;
     r.kp = call_kp(h, obs_inter, obs_intra, reward, done);
-    h->last_rollout_persistent = 0; h->last_rollout_launches = 0; h->last_rollout_member_lines = 0; h->last_rollout_lean_ttis = 0;
+    h->last_rollout_persistent = 0; h->last_rollout_launches = 0; h->last_rollout_member_lines = 0; h->last_rollout_lean_ttis = 0; h->last_rollout_kept_state_ttis = 0;
     r.net = net_use(h, r.kp);                      // (policy network: its launch precedes every TTI of a partition, see rollout_plan)
     if (r.net < 0) return r.net;
     r.rec = rec;

@@ -15,7 +15,13 @@
 #ifndef RANENV_DIAG
 #define RANENV_DIAG 0   /* diagnostic builds only (tools/build_variants.sh; see the table in DESIGN.md section 8): 3 / 4 / 7 / 11 skip the UE step / the
                            observation tail / the allocation / the masked half of the stream (tools/valu_phases.sh counts instructions by difference),
-                           9 / 12 stamp s_memtime at the phase boundaries of the one-TTI / the persistent launches (tools/stamps.py, persist_phases.py) */
+                           9 / 12 stamp s_memtime at the phase boundaries of the one-TTI / the persistent launches (tools/stamps.py, persist_phases.py),
+                           13 neither stores nor loads, and does not carry, the per-UE state on the inner TTIs of a launch (what "lean_state" can
+                           save at most; wrong results, timing only) */
+#endif
+#ifndef RANENV_KEEP_STATE
+#define RANENV_KEEP_STATE 1     /* the multi-TTI builds of one env per wave or more hand the rest of a UE's state to the next warm TTI in registers
+                                   (step_body's KEEPS); 0: they only skip the stores nobody reads, like the packed-waves build (A/B builds) */
 #endif
 
 namespace ranenv_dev {
@@ -124,6 +130,10 @@ struct KP {
     int se_quad;                                 // the bound pool is RB-quad-major [R/4][U][4] (ranenv_bind_se_pool_quad); explicit per-step tiles stay RB-major
     const double *se_mean_pool;                  // gather kernels: [tile][U] mean SE over the RBs of every pooled tile (sidecar)
     int se_rp;                                   // gather kernels: floats per UE row of the UE-major copy (R rounded up to 8)
+    // launches of several TTIs (option "lean_state"): != 0 = only an env's last TTI before it can go cold -- the launch's last, a persistent
+    // chunk's last -- stores the per-UE state that the next TTI of the same workgroup has in registers, and that TTI does not load it back
+    // (step_body's FLUSH / KEEPS); 0 = every TTI stores and loads all of it.  Sits in what was padding behind se_rp: no other member moved
+    int lean_state;
     const int32_t *trf_pool;
     // counter-based traffic (ranenv_set_traffic_generator): Poisson draws keyed (seed; env id, episode, step, UE)
     int trf_gen; int env_id_base; unsigned long long trf_seed;
@@ -157,6 +167,7 @@ struct KP {
     const float *ml_pool; long long ml_stride;
 };
 static_assert(offsetof(KP, p_err) - offsetof(KP, lean_tail) == 4 && offsetof(KP, lean_tail) - offsetof(KP, p_cap) == 4, "KP: lean_tail fills the padding behind p_cap");
+static_assert(offsetof(KP, trf_pool) - offsetof(KP, lean_state) == 4 && offsetof(KP, lean_state) - offsetof(KP, se_rp) == 4, "KP: lean_state fills the padding behind se_rp");
 
 constexpr int WAVE = 64;
 constexpr int GRP = 16;   // lanes per (env) group in alloc1/obs and per (env, slice) group in alloc2

@@ -402,10 +402,17 @@ struct NoMemberLines { };
 // A TTI that is not runs no part of the roles whose results the launch's next TTI of the env overwrites before any kernel or the host can
 // read them ("The last TTI's tail"): the observation rows, the reward and done stores, the raw per-UE outputs, and -- with the
 // episode-metric accumulators off -- the intent drift, the per-slice means and the reward arithmetic.  Other builds: always the whole tail.
+// `flush_in` (LEAN builds, option lean_state) = this TTI stores the per-UE state: the env's last TTI before it can go cold -- the launch's last
+// TTI, a persistent chunk's last.  A TTI that does not flush is followed by a warm TTI of the same workgroup, which takes queue_pkts, win_sent,
+// se_mean from StepCarry, knows last_push (the lane has just pushed) and never reads rb_start / rb_count: those six stores are skipped, and
+// the warm TTI does not load last_push.  KEEPS builds (every build of one env per wave or more; not the packed waves) hand the other five fields -- queue_age_sum, front,
+// front_rem, fifo, win_dropped -- over in StepCarry as well and neither store nor load them in between ("The state of a
+// launch's inner TTIs").  Other builds: every TTI stores and loads all of it.
 template <int MODE_X, int NQ, bool GATHER, int NP, bool PERSIST = false, int PACK = 1, bool MIX = false, bool MEMBERS = false, bool LEAN = false, typename P>
 DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,   // warm: `cy` holds what the previous TTI of this launch left
                      std::conditional_t<PACK == 2, SeStreamLane<GATHER ? 1 : NQ>, SeStream<GATHER ? 1 : NQ>> *se_carry = nullptr,
-                     const bool se_ready = false, const bool se_next = false, const bool narrow_in = false, const bool tail_in = true)
+                     const bool se_ready = false, const bool se_next = false, const bool narrow_in = false, const bool tail_in = true,
+                     const bool flush_in = true)
 {                                     // -> true: this wave has left for good (nothing to do at later TTIs of the launch either)
     constexpr int MODE = MODE_X & 3;
     constexpr bool PE = (MODE_X & MODE_PE) != 0;
@@ -476,6 +483,16 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     }
 #define TAIL (!LEAN || tail_v)
 #define ROWS (!LEAN || rows_v)
+    // FLUSH: this TTI stores the per-UE state (uniform, a scalar).  keep_v: this warm TTI follows one that may have kept its state on chip --
+    // it loads none of what the previous TTI handed over.  With the option off every TTI flushes and loads as the other builds do.
+    constexpr bool KEEPS = LEAN && RANENV_DIAG != 13 && (CARRY || (PACK == 1 && RANENV_KEEP_STATE != 0));
+    bool flush_v = true, keep_v = false;
+    if constexpr (LEAN) {
+        const bool on = COLD(lean_state) != 0;
+        flush_v = __builtin_amdgcn_readfirstlane(flush_in ? 1 : 0) != 0 || !on;
+        keep_v = warm && on;
+    }
+#define FLUSH (!LEAN || flush_v)
     ranenv_episode ep;
     int t, hlen, npush, se_pos, trf_pos;
     if (!warm) {
@@ -546,7 +563,12 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
     // waves as the env's class needs)
     if (!PERSIST && PACK == 1 && !warm && compact && __builtin_amdgcn_ballot_w64(act) == 0 && tid >= WAVE) return true;
     const size_t er4 = (size_t)e * U * 4, er8 = (size_t)e * U * 8;      // this env's row of a per-UE array of 4- / 8-byte elements
-    const unsigned u4 = (unsigned)u * 4u, u8 = (unsigned)u * 8u;
+    unsigned u4 = (unsigned)u * 4u, u8 = (unsigned)u * 8u;
+    // (KEEPS builds stand at the 96-register limit: who this lane is -- UE, slice, position -- as ONE word through the stream phase, where the state
+    // the previous TTI handed over is alive beside the queue; taken apart again behind the stream)
+    constexpr bool WHO = KEEPS && !CARRY;
+    [[maybe_unused]] unsigned who = 0;
+    if constexpr (WHO) who = (unsigned)u | ((unsigned)(slc + 1) << 16) | ((unsigned)ue_pos << 24);
 #define UE4(f) row_at<PACK>(ST_##f(p), er4, u4)
 #define UE8(f) row_at<PACK>(ST_##f(p), er8, u8)
     // window pushes of this env so far (wraps; only differences are used); index of the first push behind the last clearing
@@ -575,11 +597,27 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
             if (!gen_traffic) traffic = (double)cy.pf_traffic;
             return;
         }
+        if constexpr (LEAN) {
+            // (a warm TTI: this lane pushed at the previous TTI, lastp == ptot already; a KEEPS build finds the rest in StepCarry)
+#if RANENV_DIAG == 13     /* ablation: a warm TTI loads none of the state a non-flushing TTI did not store, and nothing carries it (wrong results: timing only) */
+            const bool kept = keep_v;
+#else
+            const bool kept = KEEPS && keep_v;
+            if constexpr (KEEPS) if (kept) { sum_age = cy.sum_age; front = cy.front; front_rem = cy.front_rem; fifo = cy.fifo; win_drop = cy.win_drop; }
+#endif
+            if (!kept) {
+                sum_age = UE8(queue_age_sum);
+                front = UE4(front); front_rem = UE4(front_rem); fifo = UE4(fifo);
+                win_drop = UE8(win_dropped);
+            }
+            if (!keep_v) lastp = UE4(last_push);
+        } else {
         if (MODE != MODE_RESET) {
             sum_age = UE8(queue_age_sum);
             front = UE4(front); front_rem = UE4(front_rem); fifo = UE4(fifo);
         }
         if (!clear_hist) { win_drop = UE8(win_dropped); lastp = UE4(last_push); }
+        }
         if (hlen == D) { old_s = *ring_s(); old_d = *ring_d(); }
         if (MODE != MODE_RESET && !gen_traffic)
             traffic = p.traffic_bits ? row_at<PACK>(p.traffic_bits, er8, u8)
@@ -695,6 +733,11 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
         row_sums<PE>(se1, R, [=](int r) { return mrow[r] != 0; }, my_full, my_part, hook, PE ? COLD(bw_per_rb) : 1.0);
     } else {
         row_sums(se1, R, [](int) { return false; }, my_full, my_part, hook);
+    }
+    if constexpr (WHO) {
+        asm volatile("" : "+v"(who));           // (opaque: nothing derived from u, slc, ue_pos in front of the stream is kept for the roles behind it)
+        u = (int)(who & 0xffffu); slc = (int)((who >> 16) & 0xffu) - 1; ue_pos = (int)(who >> 24);
+        u4 = (unsigned)u * 4u; u8 = (unsigned)u * 8u;
     }
     if constexpr (!STATE_AT_ENTRY) rest_of_state();        // after the stream: its latency is exposed, its registers were free for the queue
     // (members: the owner's tail loads were requested at the end of the walk and share that round trip; their use comes behind it)
@@ -820,10 +863,22 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
         // push into the 10-TTI window (IBSched.last_unformatted_obs.appendleft, ib_sched.py:64)
         win_sent += sent - old_s; win_drop += dropped - old_d;
         nt_store<GATHER>(*ring_s(), (int32_t)sent); nt_store<GATHER>(*ring_d(), (int32_t)dropped);
+        if constexpr (LEAN) {
+            // (the state a TTI that does not flush leaves on chip: the six fields the next TTI has in StepCarry or never reads, and in a KEEPS
+            // build the five it hands over besides; ablation 13 drops all eleven)
+            if (FLUSH) {
+                UE4(last_push) = ptot + 1; UE4(queue_pkts) = total; UE8(win_sent) = win_sent;
+                UE8(se_mean) = se_mean_new; UE4(rb_start) = rb_start; UE4(rb_count) = rb_count;
+            }
+            if (FLUSH || !(KEEPS || RANENV_DIAG == 13)) {
+                UE8(queue_age_sum) = sum_age; UE4(front) = front; UE4(front_rem) = front_rem; UE4(fifo) = fifo; UE8(win_dropped) = win_drop;
+            }
+        } else {
         UE4(last_push) = ptot + 1;
         UE4(queue_pkts) = total; UE8(queue_age_sum) = sum_age;
         UE4(front) = front; UE4(front_rem) = front_rem; UE4(fifo) = fifo;
         UE8(win_sent) = win_sent; UE8(win_dropped) = win_drop;
+        }
         // (the raw outputs: read by kernels that follow a one-TTI launch and by the host, never inside a launch of several TTIs -- the last TTI's stand)
         if (TAIL) {
             UE4(pkt_effective_thr) = (int32_t)sent; UE4(dropped_pkts) = (int32_t)dropped;
@@ -833,8 +888,9 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
         }
         sent_u = sent; drop_u = dropped;
 
-        UE8(se_mean) = se_mean_new; sem_new = se_mean_new;
-        UE4(rb_start) = rb_start; UE4(rb_count) = rb_count;
+        sem_new = se_mean_new;
+        if constexpr (!LEAN) { UE8(se_mean) = se_mean_new; UE4(rb_start) = rb_start; UE4(rb_count) = rb_count; }
+        if constexpr (KEEPS && !CARRY) { cy.sum_age = sum_age; cy.win_drop = win_drop; cy.front = front; cy.front_rem = front_rem; cy.fifo = fifo; }
         if constexpr (CARRY) {
             // Hand-over to the next TTI of this chunk (if there is one): the state in registers, and -- requested here, behind this
             // TTI's stores (catch-up and push included: a load behind a store of the same lane sees it) -- what its position determines.
@@ -1152,6 +1208,7 @@ DEVFN bool step_body(const P &p, StepCarry &cy, const bool warm, const int e_in,
 #undef UE8
 #undef TAIL
 #undef ROWS
+#undef FLUSH
 }
 
 // Several TTIs of one env in one launch (ranenv_rollout with a device policy, no episode end in between): the workgroup
@@ -1205,7 +1262,9 @@ DEVFN void step_loop(const KP &p)
             const int b_perm = xk_ * q_ + (xk_ < r_ ? xk_ : r_) + ((int)blockIdx.x >> 3);
             // (MANY: the env's last TTI in this launch runs the whole observation tail, the others what the next TTI needs -- option lean_tail)
             const bool tail = !MANY || k + 1 == n || kc->lean_tail == 0;
-            if (step_body<MODE_X, NQ, GATHER, NP, false, PACK, MIX, MEMBERS, MANY>(*kc, cy, warm, MIX ? e_mix : kc->e0 + b_perm * PACK, nullptr, false, false, narrow, tail)) return;
+            // (... and stores the per-UE state: no TTI of this workgroup follows it -- option lean_state)
+            const bool flush = !MANY || k + 1 == n;
+            if (step_body<MODE_X, NQ, GATHER, NP, false, PACK, MIX, MEMBERS, MANY>(*kc, cy, warm, MIX ? e_mix : kc->e0 + b_perm * PACK, nullptr, false, false, narrow, tail, flush)) return;
             if (k + 1 < n) {
                 // The next TTI takes over in registers what it would otherwise load back (StepCarry): only LDS has to be handed over
                 // between the waves.
@@ -1414,7 +1473,10 @@ DEVFN void persist_loop()
                 // when the env changes hands)
                 const bool ahead = done + k + 1 < n_tti;
                 // (... and this one, the env's last TTI of the launch if none follows, runs the whole observation tail: option lean_tail)
-                (void)step_body<MODE_STEP, NQ, GATHER, NP, true, 1, false, MEMBERS, true>(*kc, cy, warm, e, &seq, se_ready, ahead, false, !ahead || kc->lean_tail == 0);
+                // (the chunk's last TTI stores the per-UE state -- persist_finish may hand the env to another workgroup behind it --, and so
+                // does the launch's last: option lean_state.  Known before the TTI starts)
+                const bool flush = k + 1 == n || !ahead;
+                (void)step_body<MODE_STEP, NQ, GATHER, NP, true, 1, false, MEMBERS, true>(*kc, cy, warm, e, &seq, se_ready, ahead, false, !ahead || kc->lean_tail == 0, flush);
                 se_ready = ahead;
                 if (k + 1 < n) { warm = true; wg_sync(); }
             }
@@ -1447,7 +1509,7 @@ template <bool GATHER, int NP>
 __global__ void __launch_bounds__(CORE_NT) __attribute__((amdgpu_waves_per_eu(RANENV_PERSIST_WPE, RANENV_PERSIST_WPE))) ranenv_persist_kernel(const KP p)
 {
     (void)p;                                         // (read in place, like step_loop)
-#if RANENV_DIAG == 0 || RANENV_DIAG == 12            /* (the other diagnostic / ablation builds run the launch-per-chunk rollout only) */
+#if RANENV_DIAG == 0 || RANENV_DIAG == 12 || RANENV_DIAG == 13     /* (the other diagnostic / ablation builds run the launch-per-chunk rollout only) */
 #if RANENV_CLASS_PRIO
     if ((blockDim.x == WAVE) == GATHER) __builtin_amdgcn_s_setprio(RANENV_CLASS_PRIO);
 #endif
@@ -1460,7 +1522,7 @@ template <int NP>
 __global__ void __launch_bounds__(CORE_NT) __attribute__((amdgpu_waves_per_eu(RANENV_PERSIST_WPE, RANENV_PERSIST_WPE))) ranenv_persist_kernel_members(const KP p)
 {
     (void)p;
-#if RANENV_DIAG == 0 || RANENV_DIAG == 12
+#if RANENV_DIAG == 0 || RANENV_DIAG == 12 || RANENV_DIAG == 13
 #if RANENV_CLASS_PRIO
     if (blockDim.x != WAVE) __builtin_amdgcn_s_setprio(RANENV_CLASS_PRIO);
 #endif
@@ -1475,7 +1537,7 @@ template <int NP>
 __global__ void __launch_bounds__(CORE_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) ranenv_persist_kernel_tiny(const KP p)
 {
     (void)p;
-#if RANENV_DIAG == 0 || RANENV_DIAG == 12
+#if RANENV_DIAG == 0 || RANENV_DIAG == 12 || RANENV_DIAG == 13
     persist_loop<SE_DEPTH_TINY, false, NP>();
 #endif
 }
