@@ -1,7 +1,7 @@
 """The loop of examples/train_ppo_on_device.py with BOTH halves on the device: `collect()` records the batch, `ppo_update()` under the
 spread binding trains ONE agent on it with every optimiser step spread over the chip.
 
-    python examples/train_ppo_large_batch_on_device.py [--batch 4096] [--ttis 64] [--iters 10] [--epochs 4] [--minibatch 65536] [--slabs 64]
+    python examples/train_ppo_large_batch_on_device.py [--batch 4096] [--ttis 64] [--iters 10] [--epochs 4] [--minibatch 65536] [--slabs 64] [--bf16]
 
 Per iteration:
 
@@ -14,6 +14,10 @@ Per iteration:
 The plain binding gives an agent to one workgroup and refuses such a batch (`PPO_ROW_EPOCHS_CAP`); the eager-torch loop of
 examples/train_ppo_on_device.py spends 98 % of its time in the SGD half.  Prints env-steps/s with the updates included, the share of
 collection in it, and per iteration the mean inter-slice reward and the last epoch's statistics of the inter kind.
+
+`--bf16`: the same loop a second time with every net bound with precision="bf16" under `ppo_bind(spread=True, bf16=True)` -- acting and
+learning both on the bf16 matrix cores, float32 master weights behind the acting copy -- from the same initial weights and seeds, and
+the two runs' losses and rates side by side.  The runs differ from the first collect() on: the bf16 nets act on rounded weights.
 """
 import argparse
 import os
@@ -36,6 +40,18 @@ def mlp(n_in, n_out, width=64):
 
 
 def main():
+    args = parse()
+    f32 = run(args, False)
+    if args.bf16:
+        bf16 = run(args, True)
+        print("iteration: inter policy loss, value loss, KL -- float32 nets | bf16 nets")
+        for it, (a, b) in enumerate(zip(f32["stats"], bf16["stats"])):
+            print(f"{it + 1:9d}: {a[0]:+.4f} {a[1]:.4f} {a[2]:+.5f} | {b[0]:+.4f} {b[1]:.4f} {b[2]:+.5f}")
+        print(f"env-steps/s with the updates included: float32 {f32['rate'] / 1e6:.2f} M, bf16 {bf16['rate'] / 1e6:.2f} M; "
+              f"collection alone: float32 {f32['collect_rate'] / 1e6:.2f} M, bf16 {bf16['collect_rate'] / 1e6:.2f} M")
+
+
+def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--ttis", type=int, default=64, help="TTIs per collect() call: the train batch is batch x ttis env-steps")
@@ -45,7 +61,11 @@ def main():
     ap.add_argument("--slabs", type=int, default=64, help="gradient slabs: workgroups per kind that share a minibatch's tiles (1..256)")
     ap.add_argument("--episode-len", type=int, default=100)
     ap.add_argument("--se-mode", choices=("stream", "gather"), default="gather")
-    args = ap.parse_args()
+    ap.add_argument("--bf16", action="store_true", help="run the loop a second time with bf16 nets under ppo_bind(spread=True, bf16=True)")
+    return ap.parse_args()
+
+
+def run(args, bf16):
     dev = torch.device("cuda", 0)
     B, T, L = args.batch, args.ttis, args.episode_len
     n_ep = 64
@@ -61,10 +81,12 @@ def main():
     pi_inter, vf_inter, pi_intra, vf_intra = mlp(10 * S, 2 * S), mlp(10 * S, 1), mlp(W, 3), mlp(W, 1)
     with torch.no_grad():
         pi_inter[-1].bias[S:].fill_(-0.5)          # initial log_std
-    env.set_policy_network(pi_inter, pi_intra, stochastic=True, seed=1000)
-    env.set_value_network(vf_inter, vf_intra)
-    env.ppo_bind(spread=True, slabs=args.slabs)
+    precision = "bf16" if bf16 else "f32"
+    env.set_policy_network(pi_inter, pi_intra, stochastic=True, seed=1000, precision=precision)
+    env.set_value_network(vf_inter, vf_intra, precision=precision)
+    env.ppo_bind(spread=True, slabs=args.slabs, bf16=bf16)
     env.reset()
+    stats = []
     torch.cuda.synchronize()
     t_collect, t0 = 0.0, time.perf_counter()
     for it in range(args.iters):
@@ -76,16 +98,18 @@ def main():
                              grad_clip=GRAD_CLIP, seed=it)
         r = rec["reward"][..., 0].mean().item()
         last = args.epochs - 1
-        print(f"iteration {it + 1:3d}: mean inter-slice reward {r:+.4f}, {int(rec['done'].sum())} episode ends; inter policy loss "
+        stats.append((out["policy_loss"][0, 0, last], out["value_loss"][0, 0, last], out["kl"][0, 0, last]))
+        print(f"{precision} iteration {it + 1:3d}: mean inter-slice reward {r:+.4f}, {int(rec['done'].sum())} episode ends; inter policy loss "
               f"{out['policy_loss'][0, 0, last]:+.4f}, value loss {out['value_loss'][0, 0, last]:.4f}, KL {out['kl'][0, 0, last]:+.5f}, "
               f"{int(out['minibatches'][0, 0, last])} + {int(out['minibatches'][0, 1, last])} steps per epoch", flush=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = B * T * args.iters
-    print(f"{B} envs x {T} TTIs x {args.iters} iterations, {args.epochs} epochs of minibatch {args.minibatch} each on {args.slabs} slabs "
+    print(f"{precision} nets: {B} envs x {T} TTIs x {args.iters} iterations, {args.epochs} epochs of minibatch {args.minibatch} each on {args.slabs} slabs "
           f"(SE mode {args.se_mode}): {n / dt / 1e6:.2f} M env-steps/s with the updates included; collection alone "
           f"{n / t_collect / 1e6:.2f} M env-steps/s ({100 * t_collect / dt:.0f} % of the time)")
     env.close()
+    return {"stats": stats, "rate": n / dt, "collect_rate": n / t_collect}
 
 
 if __name__ == "__main__":

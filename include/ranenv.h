@@ -906,6 +906,52 @@ int ranenv_ppo_slice_state(ranenv_handle h, int32_t role, int32_t slice, float *
 int ranenv_ppo_bind_spread(ranenv_handle h, int32_t slabs, int32_t wide, void *stream);
 int ranenv_ppo_spread_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t slabs, int32_t wide, int64_t *bytes);
 int ranenv_ppo_spread_plan(int64_t n_rows, int32_t minibatch, int32_t epochs, int32_t slabs, int64_t *steps, int32_t *grid, int32_t *tiles_last);
+/* bf16 nets over the chip: every binding above trains float32 nets, so whoever trains on the device collects with the slowest matrix
+ * path of the chip.  A sixth, opt-in binding trains the ONE agent's nets where they are RANENV_NET_BF16 nets: standard mixed-precision
+ * training -- f32 master weights, bf16 acting weights re-rounded from them behind every optimiser step.
+ * ranenv_ppo_bind_spread_bfloat: ranenv_ppo_bind_spread's rules (wide 0) with these differences, RANENV_E_STATE in words of their own:
+ *   EVERY bound IBSched role (inter actor and critic; intra actor and critic where bound) must be a RANENV_NET_BF16 net -- float32 nets
+ *   ("the bound nets are float32") and pairs of mixed precision ("nets of one precision") are refused --; every role is served by its
+ *   one-net slot (no population, not even of one member; no nets per slice); each pair fits THE BF16 LDS PLAN: 4096 bytes and, for the
+ *   larger net of the pair, 32 rows of the input and of every hidden layer in bf16 at a stride of (padded width + 16) elements and
+ *   the 32 f32 rows of the output layer at ranenv_ppo_lds_bytes' stride, at most 163 840 in all ([512] x 3 on the inter input at S 5:
+ *   119 296; the largest pair a handle can hold, four hidden layers of 512 at S 16: 159 232 -- so under today's limits of
+ *   ranenv_create the refusal by size is a guard no handle reaches).  A refused bind moves no weight.  Every other binding still refuses bf16 nets, in its words.
+ *   Allocates per trained net, in the F32 packed layout (ranenv_packed_net_floats of RANENV_NET_F32): the f32 MASTER copy, Adam's m and
+ *   v and the gradient cell; a transposed bf16 copy Wt [kp][np] per layer for the backward product; and ranenv_ppo_bind_spread's slabs
+ *   (of the F32 layout's floats), block partials and slab statistics.  The master is SEEDED FROM THE ACTING COPY: the bf16 W widened,
+ *   the f32 biases copied, so acting == bf16(master) holds from the first step -- resuming from float32 weights therefore rounds them
+ *   once, at ranenv_set_policy_network / _value_network.
+ *   Re-binding a role under the binding: the master re-seeded from the new acting copy, Wt rebuilt, the moments of both nets of that
+ *   kind and the kind's counter restarted; a net that no longer fits what the bind allocated, or is no longer bf16, ends the binding.
+ * ranenv_ppo_update under this binding: ranenv_ppo_bind_spread's schedule, launches and arguments.  dev_grad, the stride of
+ *   ranenv_ppo_layout and ranenv_ppo_member_layout's floats are in the F32 packed layout; ranenv_ppo_state returns m and v in it;
+ *   ranenv_get_net_weights returns the f32 MASTER weights (it still refuses a bf16 net without this binding); out->precision stays
+ *   RANENV_NET_BF16, the precision the net is bound and acts in: fed back to ranenv_set_policy_network as it is, the struct binds
+ *   bf16(master), the acting copy.
+ * THE NUMERIC CONTRACT of a step (all roundings to nearest even; products of bf16 numbers are exact in float32; the summation order
+ *   and the matrix core's internal rounding are unspecified; adapters.ppo_update_reference(..., precision="bf16") restates it):
+ *     1. Forward: THE CONTRACT of a bf16 net above, on the acting copy Wq = bf16(master), by the acting kernels' own tile function.
+ *        With unchanged weights the re-evaluated log-probability therefore equals the recorded one bit for bit.
+ *     2. Loss and G = dL/d(output): ranenv_ppo_update's, float64 from the f32 outputs, G rounded to f32.
+ *     3. Backward, layer l from last to first, A_{l-1} the bf16 rows the forward held (layer 0: the rounded input row):
+ *          D_L = bf16(G);
+ *          dW_l += D_l^T A_{l-1} and db_l += sum_r D_l[r]: bf16 operands, f32 accumulation over the tile's 32 rows, the sum added in
+ *            f32 into the workgroup's slab;
+ *          D_{l-1} = bf16((D_l Wq_l) * act'(A_{l-1})): f32 accumulation, act' from the ROUNDED value (1 - a * a in f32, or a > 0),
+ *            ONE rounding, behind the product.  The roundings of the forward pass have derivative 1.
+ *     4. Reduce, joint norm, clip, Adam: ranenv_ppo_bind_spread's elementwise steps, on the masters, in f32.
+ *     5. Re-round: the apply launch that ran Adam on an element stores bf16(master) into the acting copy and into Wt, a bias into the
+ *        acting copy's f32 bias.  Behind every optimiser step acting == bf16(master): the next pass and the next ranenv_collect read
+ *        trained weights with no re-bind.  Launch order on `stream` is the only synchronisation.
+ *   No loss scaling: bf16 has float32's exponent range.
+ * ranenv_ppo_spread_bfloat_bytes: without a handle, for ONE kind's pair (critic NULL: none): lds_bytes, THE BF16 LDS PLAN's need (the
+ *   caller compares it with 163 840), and device_bytes = 4 x (slabs x F + per net (4 F_net + its packed RANENV_NET_BF16 floats)),
+ *   F the pair's F32 packed floats.  Either output may be NULL, not both; slabs outside 1..256: RANENV_E_INVALID.
+ * Out of scope, each still refused: bf16 nets under the plain, mixed, wide, per-slice, head and head-spread bindings, populations,
+ *   the SAC update, and seeding masters from float32 weights. */
+int ranenv_ppo_bind_spread_bfloat(ranenv_handle h, int32_t slabs, void *stream);
+int ranenv_ppo_spread_bfloat_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t slabs, int64_t *lds_bytes, int64_t *device_bytes);
 
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,
  * results/gen_results.py:874-1022, kept as running sums so that a rollout needs no per-TTI read-back).  Per env 8

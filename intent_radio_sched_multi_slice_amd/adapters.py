@@ -570,12 +570,97 @@ def ppo_rows(rec, kind: str, rows, layout: str = "obs", dtype=torch.float64) -> 
     return out
 
 
+PPO_BF16_SLIPS = ("bf16_trunc_d", "bf16_unrounded_d", "bf16_unrounded_dl", "bf16_act_unrounded", "bf16_master_backward", "bf16_stale_acting",
+                  "bf16_wt_swapped")
+
+
+def _bf16_of(x: torch.Tensor, mode: str = "rne") -> torch.Tensor:
+    """``x`` rounded to bf16 in its own dtype: "rne" (``bf16_round``), "trunc" (the low 16 bits dropped: a planted slip) or "none"."""
+    if mode == "none":
+        return x
+    if mode == "rne":
+        return bf16_round(x).to(x.dtype)
+    bits = x.detach().to(torch.float32).contiguous().view(torch.int32) & -65536
+    return bits.view(torch.float32).to(x.dtype)
+
+
+class _Bf16Linear(torch.autograd.Function):
+    """Contract steps 1 and 3 of one layer of a bf16-trained net: forward ``a @ bf16(W).T + b`` on the acting copy (``wq`` given: that
+    copy, else the master ``w`` rounded); backward with the incoming D_l: dW = D_l^T a to the MASTER (the rounding has derivative 1),
+    db the column sums, and D_l Wq to the input.  ``slip``: the product on the master, or on a copy whose k columns are swapped in pairs."""
+    @staticmethod
+    def forward(ctx, a, w, b, wq, slip):
+        wq = bf16_round(w).to(w.dtype) if wq is None else wq
+        ctx.save_for_backward(a, w, wq)
+        ctx.slip = slip
+        return a @ wq.t() + b
+
+    @staticmethod
+    def backward(ctx, g):
+        a, w, wq = ctx.saved_tensors
+        wb = w if ctx.slip == "bf16_master_backward" else wq
+        if ctx.slip == "bf16_wt_swapped":
+            k = torch.arange(wb.shape[1])
+            wb = wb[:, torch.where((k ^ 1) < wb.shape[1], k ^ 1, k)]
+        return g @ wb, g.t() @ a, g.sum(dim=0), None, None
+
+
+class _Bf16Act(torch.autograd.Function):
+    """A hidden layer's activation under the contract: a = bf16(act(z)); backward D = bf16(g * act'(a)), act' from the ROUNDED value,
+    one rounding behind the product.  ``slip``: D truncated or unrounded, act' from the unrounded value."""
+    @staticmethod
+    def forward(ctx, z, act, slip):
+        y = torch.tanh(z) if act == "tanh" else torch.relu(z)
+        a = _bf16_of(y)
+        ctx.save_for_backward(y if slip == "bf16_act_unrounded" else a)
+        ctx.act, ctx.slip = act, slip
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        s, = ctx.saved_tensors
+        d = 1.0 - s * s if ctx.act == "tanh" else (s > 0).to(s.dtype)
+        return _bf16_of(g * d, {"bf16_trunc_d": "trunc", "bf16_unrounded_d": "none"}.get(ctx.slip, "rne")), None, None
+
+
+class _Bf16Grad(torch.autograd.Function):
+    """Identity whose gradient is rounded to bf16 on the way back: D_L = bf16(G) at the output layer (``mode`` "none": a slip)."""
+    @staticmethod
+    def forward(ctx, x, mode):
+        ctx.mode = mode
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _bf16_of(g, ctx.mode), None
+
+
+def _mlp_forward_bf16_trained(x: torch.Tensor, layers, activation: str, acting=None, slip: Optional[str] = None) -> torch.Tensor:
+    """The forward of a bf16-trained net on its MASTER ``layers`` whose autograd backward is contract step 3 (include/ranenv.h "bf16 nets
+    over the chip"); in float32 its value is ``_mlp_forward(..., precision="bf16")``'s bit for bit.  ``acting``: the acting copy's
+    ``(Wq, b)`` where it is not bf16 of the masters (the stale-copy slip)."""
+    a = _bf16_of(x)
+    for i, (w, b) in enumerate(layers):
+        z = _Bf16Linear.apply(a, w, b, None if acting is None else acting[i][0], slip)
+        if i < len(layers) - 1:
+            a = _Bf16Act.apply(z, activation, slip)
+    return _Bf16Grad.apply(z, "none" if slip == "bf16_unrounded_dl" else "rne")
+
+
 def ppo_loss_reference(actor, critic, batch, kind: str, clip: float, vf_coeff: float, ent_coeff: float, adv_norm: bool, act_actor: str = "tanh",
-                       act_critic: str = "tanh", slip: Optional[str] = None):
+                       act_critic: str = "tanh", slip: Optional[str] = None, precision: str = "f32", acting=None):
     """The minibatch loss of ``ppo_update`` in torch (autograd differentiates it): ``actor`` / ``critic`` (None: no value term) lists of
     ``(W, b)`` in the dtype to compute in, ``batch`` from ``ppo_rows``.  Returns (loss, {policy_loss, value_loss, entropy, kl,
-    clip_frac, logp}).  ``slip``: a deliberately wrong variant, for the tests that show the tolerances bite."""
+    clip_frac, logp}).  ``slip``: a deliberately wrong variant, for the tests that show the tolerances bite.  ``precision`` "bf16":
+    the nets are the MASTERS of a bf16-trained pair (``ppo_bind(spread=True, bf16=True)``): forward and backward are the numeric
+    contract's (``_mlp_forward_bf16_trained``; ``slip`` one of ``PPO_BF16_SLIPS``, ``acting`` = (actor, critic) acting copies for the
+    stale-copy slip); the loss on the outputs is the same."""
+    if precision not in ("f32", "bf16"):
+        raise ValueError("precision must be 'f32' or 'bf16'")
+
     def forward(x, layers, act, deriv=None):
+        if precision == "bf16":
+            return _mlp_forward_bf16_trained(x, layers, act, None if acting is None else acting[0 if layers is actor else 1], slip)
         for i, (w, b) in enumerate(layers):
             if slip == "db_drops_row_32" and i == 0 and x.shape[0] > 32:      # (row 32 misses layer 0's bias reduction)
                 rows = b.expand(x.shape[0], -1)
@@ -642,17 +727,25 @@ def ppo_adam_reference(params, grads, state, lr: float, grad_clip: float, betas=
 def ppo_update_reference(rec, kind: str, actor, critic, order, lo: int, hi: int, epochs: int = 10, minibatch: int = 64, lr: float = 3e-4,
                          clip: float = 0.2, vf_coeff: float = 0.5, ent_coeff: float = 0.01, grad_clip: float = 0.5, adv_norm: bool = True,
                          betas=(0.9, 0.999), eps: float = 1e-8, act_actor: str = "tanh", act_critic: str = "tanh", layout: str = "obs",
-                         state: Optional[dict] = None, dtype=torch.float64, slip: Optional[str] = None):
+                         state: Optional[dict] = None, dtype=torch.float64, slip: Optional[str] = None, precision: str = "f32"):
     """THE NORMATIVE STATEMENT of ``ppo_update`` for one member and kind, float64 torch autograd on the CPU: ``actor`` / ``critic`` lists
     of ``(W, b)`` (copied), the member's rows of epoch k are ``order[k, lo:hi]``, minibatches consecutive chunks of ``minibatch`` with a
     short last one.  Returns {"actor", "critic": the trained layers, "state": Adam's, "stats": float64 [epochs, 8] as ``_lib.PPO_STATS``,
-    "grad": the last minibatch's unclipped gradients as lists of (dW, db) for actor and critic}."""
+    "grad": the last minibatch's unclipped gradients as lists of (dW, db) for actor and critic}.
+    ``precision`` "bf16": the twin of ``ppo_bind(spread=True, bf16=True)`` -- ``actor`` / ``critic`` are the MASTER weights, kept in
+    ``dtype``; every pass runs the header's numeric contract on the acting copy bf16(master) (``ppo_loss_reference``), Adam steps the
+    masters, and the acting copy is re-rounded from them behind every optimiser step, so it is the multi-step twin too; the result
+    has "acting": {"actor", "critic"}, the acting copies behind the last step.  The default "f32" is the path above, untouched."""
+    if precision not in ("f32", "bf16"):
+        raise ValueError("precision must be 'f32' or 'bf16'")
+    rounded = lambda net: None if net is None else [(_bf16_of(w.detach()), b.detach().clone()) for w, b in net]  # noqa: E731
     cpu = {k: v.detach().cpu() for k, v in rec.items() if isinstance(v, torch.Tensor)}
     order = torch.as_tensor(order).cpu().to(torch.int64)
     copy = lambda net: None if net is None else [(w.detach().cpu().to(dtype).clone().requires_grad_(True), b.detach().cpu().to(dtype).clone().requires_grad_(True))  # noqa: E731
                                                   for w, b in net]
     actor, critic = copy(actor), copy(critic)
     params = [p for net in (actor, critic) if net is not None for wb in net for p in wb]
+    stale = (rounded(actor), rounded(critic)) if slip == "bf16_stale_acting" else None      # (the acting copy never re-rounded: a slip)
     state = {} if state is None else state
     stats, grads = np.zeros((epochs, 8)), None
     n = hi - lo
@@ -662,7 +755,7 @@ def ppo_update_reference(rec, kind: str, actor, critic, order, lo: int, hi: int,
         for c0 in range(0, n, minibatch):
             rows = order[ep, lo + c0:lo + min(c0 + minibatch, n)]
             batch = ppo_rows(cpu, kind, rows, layout, dtype)
-            loss, st = ppo_loss_reference(actor, critic, batch, kind, clip, vf_coeff, ent_coeff, adv_norm, act_actor, act_critic, slip)
+            loss, st = ppo_loss_reference(actor, critic, batch, kind, clip, vf_coeff, ent_coeff, adv_norm, act_actor, act_critic, slip, precision, stale)
             grads = torch.autograd.grad(loss, params)
             with torch.no_grad():
                 norm = ppo_adam_reference(params, list(grads), state, lr, grad_clip, betas, eps, slip)
@@ -672,8 +765,11 @@ def ppo_update_reference(rec, kind: str, actor, critic, order, lo: int, hi: int,
         stats[ep, :6], stats[ep, 6], stats[ep, 7] = acc / n, n, n_mb
     pairs = lambda flat: [(flat[2 * i], flat[2 * i + 1]) for i in range(len(flat) // 2)]  # noqa: E731
     na = 2 * len(actor)
-    return {"actor": [(w.detach(), b.detach()) for w, b in actor], "critic": None if critic is None else [(w.detach(), b.detach()) for w, b in critic],
-            "state": state, "stats": stats, "grad": {"actor": pairs(list(grads[:na])), "critic": pairs(list(grads[na:]))}}
+    out = {"actor": [(w.detach(), b.detach()) for w, b in actor], "critic": None if critic is None else [(w.detach(), b.detach()) for w, b in critic],
+           "state": state, "stats": stats, "grad": {"actor": pairs(list(grads[:na])), "critic": pairs(list(grads[na:]))}}
+    if precision == "bf16":
+        out["acting"] = {"actor": stale[0] if stale else rounded(actor), "critic": stale[1] if stale else rounded(critic)}
+    return out
 
 
 # --------------------------------------------------------------------------------------------

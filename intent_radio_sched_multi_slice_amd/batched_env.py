@@ -252,6 +252,18 @@ def ppo_spread_bytes(actor_layers, critic_layers=None, slabs: int = 64, wide: bo
     return out.value
 
 
+def ppo_spread_bf16_bytes(actor_layers, critic_layers=None, slabs: int = 64) -> Dict[str, int]:
+    """What ``ppo_bind(spread=True, slabs=slabs, bf16=True)`` needs for ONE kind's actor / critic pair of bf16 nets, before anything is
+    bound (ranenv_ppo_spread_bfloat_bytes): "lds" -- the bf16 LDS plan's bytes, which the bind refuses above 163 840 -- and "device",
+    the bytes it allocates: ``slabs`` gradient slabs of the pair's float32 packed floats and per net the float32 master, Adam's m and
+    v, the gradient cell and a transposed bf16 copy of the weights.  Nets as for ``ppo_lds_bytes``."""
+    actor, critic = _ppo_shape_pair(actor_layers, critic_layers)
+    lds, dev = C.c_int64(), C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_ppo_spread_bfloat_bytes(actor, critic, int(slabs), C.byref(lds), C.byref(dev)), "ranenv_ppo_spread_bfloat_bytes")
+    return {"lds": lds.value, "device": dev.value}
+
+
 def ppo_head_spread_bytes(actor_layers, critic_layers, S: int, slabs: int = 64) -> int:
     """Device bytes ``ppo_bind(head=True, spread=True, slabs=slabs)`` allocates for the head pair beside the moments
     (ranenv_ppo_head_spread_bytes): ``slabs`` gradient slabs of the pair's packed floats and ``slabs`` float64 rows of ``log_std``'s
@@ -962,7 +974,8 @@ class BatchedRanEnv:
     # -- the PPO update on the device (ranenv_ppo_bind / ranenv_ppo_update; include/ranenv.h "PPO update") ---------------------------
     PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP = PPO_ROW_EPOCHS_CAP, PPO_STEPS_CAP      # (per handle: an attribute of the instance overrides them)
 
-    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False, spread: bool = False, slabs: Optional[int] = None) -> None:
+    def ppo_bind(self, mixed: bool = False, head: bool = False, wide: bool = False, per_slice: bool = False, spread: bool = False, slabs: Optional[int] = None,
+                 bf16: bool = False) -> None:
         """Allocate and zero the optimiser state of the bound actors and critics (ranenv_ppo_bind): Adam moments, gradient scratch,
         one step counter per (member, kind).  Bind the nets first; re-binding a net afterwards restarts its optimiser (see the header).
         ``mixed=True`` (ranenv_ppo_bind_mixed): the population was bound with ``mixed=True`` -- members of differing shape -- and
@@ -989,7 +1002,19 @@ class BatchedRanEnv:
         (``ppo_head_spread_bytes``).  The later of the two head bindings replaces the earlier and restarts the head optimiser; either
         stands beside whatever binding the IBSched nets have, the spread one included.  The head pair trains under the plain LDS plan
         alone: ``head`` with ``spread`` and ``wide`` is refused like ``head`` with ``wide``.  ``slabs`` has no default in this form:
-        ``spread`` and ``head`` without it raise ``ValueError``, as the two together always did before this form existed."""
+        ``spread`` and ``head`` without it raise ``ValueError``, as the two together always did before this form existed.
+        ``spread=True, bf16=True`` (ranenv_ppo_bind_spread_bfloat): the spread binding for nets bound with ``precision="bf16"`` --
+        every bound IBSched net must be one --, mixed-precision training: float32 master weights seeded from the acting copy (so
+        float32 weights are rounded once, when they are bound), Adam on the masters, and the bf16 acting weights re-rounded from
+        them behind every optimiser step, so the next ``collect()`` acts on the trained net (the header's numeric contract;
+        ``adapters.ppo_update_reference(..., precision="bf16")`` restates it).  Under it ``net_weights`` returns the masters and
+        ``ppo_state`` / ``grad=True`` are in the float32 packed layout.  ``ppo_spread_bf16_bytes`` tells its LDS and device needs.
+        Only this binding takes bf16 nets: ``bf16`` needs ``spread`` and excludes ``wide``, ``mixed``, ``per_slice`` and ``head``."""
+        if bf16 and not spread:
+            raise ValueError("ppo_bind: bf16 needs spread=True (only the one-agent spread binding trains bf16 nets)")
+        for other, on in (("wide", wide), ("mixed", mixed), ("per_slice", per_slice), ("head", head)):
+            if bf16 and on:
+                raise ValueError(f"ppo_bind: bf16 and {other} exclude each other (bf16 nets train under the one-agent spread binding's own LDS plan alone)")
         if spread and mixed:
             raise ValueError("ppo_bind: spread and mixed exclude each other (the spread binding trains one agent, no population)")
         if spread and head and wide:
@@ -1010,6 +1035,8 @@ class BatchedRanEnv:
                 self._check(self._lib.ranenv_ppo_bind_head_spread(self._h, int(slabs), self._stream()), "ranenv_ppo_bind_head_spread")
                 self._ppo_head_spread = True
                 return                         # (beside the IBSched nets' binding: which one that is stays as it was)
+            elif bf16:
+                self._check(self._lib.ranenv_ppo_bind_spread_bfloat(self._h, int(slabs), self._stream()), "ranenv_ppo_bind_spread_bfloat")
             elif spread:
                 self._check(self._lib.ranenv_ppo_bind_spread(self._h, int(slabs), 1 if wide else 0, self._stream()), "ranenv_ppo_bind_spread")
             elif per_slice:
@@ -1149,7 +1176,9 @@ class BatchedRanEnv:
         """The bound float32 net of ``role`` ("inter", "intra", "v_inter", "v_intra"), member ``m`` of a population, as it is on the
         device NOW -- after ``ppo_update``: the trained net -- as a list of ``(W, b)`` tensors in torch ``Linear`` layout
         (ranenv_get_net_weights); with ``net_activation(role, m)`` what ``set_policy_network`` takes.  ``slice=s``: slice s's net of
-        "intra" / "v_intra" bound per slice (ranenv_get_slice_net_weights), which ``m`` cannot name."""
+        "intra" / "v_intra" bound per slice (ranenv_get_slice_net_weights), which ``m`` cannot name.  A bf16 net has no float32 weights
+        to return -- they were rounded at bind -- except under ``ppo_bind(spread=True, bf16=True)``: then these are the float32 MASTER
+        weights the optimiser steps, of which the acting copy is the bf16 rounding."""
         layers, _ = self._net_weights(role, m, slice=slice)
         return layers
 

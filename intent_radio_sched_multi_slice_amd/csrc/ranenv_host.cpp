@@ -161,12 +161,13 @@ struct ranenv {
     struct PpoBinding {
         bool on = false, mixed = false, wide = false, slices = false;
         int slabs = 0;                                                                                        // > 0: the spread binding
+        bool bf16 = false;                                                                                    // ... of RANENV_NET_BF16 nets (ranenv_ppo_bind_spread_bfloat)
         int units(int kind, int members, int S) const { return slices ? (kind == 1 ? S : 1) : members; }      // ... of a kind
         int workgroups(int members, int S) const { return slabs ? 2 * slabs : (slices ? 1 + S : 2 * members); }      // ... of an update launch at most
         // unit u of `kind` by workgroup number: its step counter in d_ppo_t and (not spread) its share of the parked rows in d_ppo_park
         int wg(int kind, int u) const { return slices ? (kind ? 1 + u : 0) : u * 2 + kind; }
         // the entry point the messages name (parked: where they speak of the parked rows, which ranenv_ppo_bind_wide allocates)
-        const char *entry(bool parked = false) const { return slabs ? "ranenv_ppo_bind_spread" : (slices ? "ranenv_ppo_bind_slices" : (parked ? "ranenv_ppo_bind_wide" : "ranenv_ppo_bind")); }
+        const char *entry(bool parked = false) const { return bf16 ? "ranenv_ppo_bind_spread_bfloat" : slabs ? "ranenv_ppo_bind_spread" : (slices ? "ranenv_ppo_bind_slices" : (parked ? "ranenv_ppo_bind_wide" : "ranenv_ppo_bind")); }
     } ppo;
     // ... its step counters by workgroup number [POP_MAX * 2], the call's hyper-parameters on the device [POP_MAX], the diagnostic
     // log-probability buffer the NEXT update takes and forgets
@@ -184,6 +185,10 @@ struct ranenv {
     // All allocated at the bind, never by an update
     float *d_ppo_slab = nullptr; long long ppo_slab_cap = 0;
     double *d_ppo_spread = nullptr; long long ppo_spread_blocks = 0;
+    // ranenv_ppo_bind_spread_bfloat: per role the trained bf16 net's f32 state in the F32 packed layout -- master, m, v, g, ppo_bf_cap[r]
+    // floats each -- and behind them the transposed bf16 copy, ppo_bf_cap16[r] floats (the acting copy's packed size).  Allocated at the
+    // bind (an outgrown one stays allocated), seeded from the acting copy at the bind and at every re-bind of the role
+    float *d_ppo_bf[4] = {nullptr, nullptr, nullptr, nullptr}; long long ppo_bf_cap[4] = {0, 0, 0, 0}, ppo_bf_cap16[4] = {0, 0, 0, 0};
     // ranenv_ppo_bind_head / ranenv_ppo_update_head: bound?, the one step counter, and log_std's Adam moments and gradient scratch
     // [3][S] (m, v, g); the actor's and the critic's lie on the head and head_value slots (opt)
     bool ppo_head_on = false; int32_t *d_ppo_head_t = nullptr; float *d_head_ls_opt = nullptr;
@@ -2187,27 +2192,43 @@ int ranenv_set_population_gae(ranenv_handle h, int32_t n, const double *host_gam
 // ---- PPO update (include/ranenv.h "PPO update"; the kernel: ranenv_ppo.hip) -----------------------------------------------------
 static_assert(sizeof(ranenv_ppo_hparams) == RANENV_PPO_HPARAMS_BYTES, "ranenv_ppo_hparams: 8 doubles and 4 int32");
 
+// Floats of `net`'s F32 packed layout whatever its precision (net_pack's rule for RANENV_NET_F32); bf non-null: its offsets there
+static long long net_floats_f32(const PolicyNet &net, PpoBf16Net *bf = nullptr)
+{
+    long long off = 0;
+    for (int l = 0; l < net.n_layers; l++) {
+        if (bf) bf->w_off[l] = off;
+        off += (long long)net.kp[l] * net.np[l];
+        if (bf) bf->b_off[l] = off;
+        off += net.np[l];
+    }
+    return off;
+}
+
 // Member m's nets of kind k among the slots the update trains (ppo_roles): the packed floats of its actor and critic (0: none) and
 // the LDS bytes their update needs -- `wide`: under the wide plan, and `park`, the floats of scratch its workgroup parks its rows in.
-// A uniform binding's members all have copy 0's shape.
+// A uniform binding's members all have copy 0's shape.  bf16 (ranenv_ppo_bind_spread_bfloat): the floats of the nets' F32 packed layout
+// -- the masters', moments', slabs' and gradient's -- and the LDS bytes of the bf16 plan.
 static void ppo_member_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, int m, int k, long long &actor_floats, long long &critic_floats, size_t &lds,
-                             bool wide = false, long long *park = nullptr)
+                             bool wide = false, long long *park = nullptr, bool bf16 = false)
 {
     const size_t i = mixed ? (size_t)m : 0;
     const PolicyNet &a = slot[k]->member[i], *c = slot[2 + k] ? &slot[2 + k]->member[i] : nullptr;
-    actor_floats = net_floats(a); critic_floats = c ? net_floats(*c) : 0; lds = wide ? ppo_wide_lds_bytes(a, c) : ppo_lds_bytes(a, c);
+    if (bf16) { actor_floats = net_floats_f32(a); critic_floats = c ? net_floats_f32(*c) : 0; lds = ppo_bf16_lds_bytes(a, c); }
+    else { actor_floats = net_floats(a); critic_floats = c ? net_floats(*c) : 0; lds = wide ? ppo_wide_lds_bytes(a, c) : ppo_lds_bytes(a, c); }
     if (park) *park = wide ? ppo_wide_scratch(a, c) : 0;
 }
 
 // THE walk over the shapes the update trains: f(member, kind, actor + critic floats, LDS bytes, parked floats) for every bound kind
 // and (a mixed binding) every one of the `members`, in order, until one returns other than RANENV_OK
-static int ppo_each_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wide, int members, const std::function<int(int, int, long long, size_t, long long)> &f)
+static int ppo_each_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wide, int members, const std::function<int(int, int, long long, size_t, long long)> &f,
+                          bool bf16 = false)
 {
     for (int k = 0; k < 2; k++) {
         if (!slot[k]) continue;
         for (int m = 0; m < (mixed ? members : 1); m++) {
             long long af, cf, park; size_t lds;
-            ppo_member_shape(slot, mixed, m, k, af, cf, lds, wide, &park);
+            ppo_member_shape(slot, mixed, m, k, af, cf, lds, wide, &park, bf16);
             if (const int rc = f(m, k, af + cf, lds, park); rc != RANENV_OK) return rc;
         }
     }
@@ -2217,7 +2238,7 @@ static int ppo_each_shape(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wi
 // The largest needs over that walk: the gradient's floats, the LDS bytes -- of kinds < lds_kinds alone: a call that updates no intra
 // rows launches with the inter nets' -- and (wide) the parked floats per workgroup
 struct PpoPlan { long long grad_floats; size_t lds; long long park; };
-static PpoPlan ppo_plan(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wide, int members, int lds_kinds = 2)
+static PpoPlan ppo_plan(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wide, int members, int lds_kinds = 2, bool bf16 = false)
 {
     PpoPlan p{};
     ppo_each_shape(slot, mixed, wide, members, [&](int, int k, long long floats, size_t lds, long long park) {
@@ -2225,7 +2246,7 @@ static PpoPlan ppo_plan(ranenv::NetSlot *const (&slot)[4], bool mixed, bool wide
         if (k < lds_kinds) p.lds = std::max(p.lds, lds);
         p.park = std::max(p.park, park);
         return (int)RANENV_OK;
-    });
+    }, bf16);
     return p;
 }
 
@@ -2245,13 +2266,18 @@ static int opt_ensure(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s)
 // checks the wide plan in its place; spread: ranenv_ppo_bind_spread, which takes one member alone), or (slices) ranenv_ppo_bind_slices -- the one-net inter pair, the intra actors per slice, the
 // intra critics per slice or none.  The two geometries differ in the forms they take, the two rule blocks; their place around the
 // inter pair's check is the order in which a caller who breaks two rules hears of them.  No device call.
-static int ppo_roles(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false, bool wide = false, bool spread = false)
+// bf16 (ranenv_ppo_bind_spread_bfloat, a spread binding): every bound role a RANENV_NET_BF16 one-net slot, the pairs within the bf16 LDS plan.
+static int ppo_roles(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], int &members, bool mixed = false, bool wide = false, bool spread = false,
+                     bool bf16 = false)
 {
     if (h->kp.policy == RANENV_POLICY_HEAD_NETWORK) return fail(h, RANENV_E_STATE, "the PPO update trains the IBSched nets: the policy is RANENV_POLICY_HEAD_NETWORK");
     int n_pop = 0, n_one = 0;
     for (int r = 0; r < 4; r++) {
         slot[r] = h->serving(r);
         if (!slot[r]) continue;
+        if (bf16 && slot[r]->form != FORM_ONE)
+            return fail(h, RANENV_E_STATE, "the bf16 spread PPO update trains one agent's single nets, no population and no nets per slice: the %s nets are bound per %s",
+                        NET_ROLES[r].who, slot[r]->form == FORM_MEMBER ? "member" : "slice");
         if (slices && slot[r]->form == FORM_MEMBER) return fail(h, RANENV_E_STATE, "the per-slice PPO update trains no population: the %s nets are bound per member", NET_ROLES[r].who);
         if (!slices && slot[r]->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the PPO update does not train intra nets per slice (non-shared intra policies)");
         (slot[r]->form == FORM_MEMBER ? n_pop : n_one) += 1;
@@ -2268,16 +2294,25 @@ static int ppo_roles(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], 
         return fail(h, RANENV_E_STATE, "the PPO update needs every net per member or every net single: a net the members share has no one owner");
     members = n_pop ? h->pop.n : 1;
     if (spread && members > 1) return fail(h, RANENV_E_STATE, "the spread PPO update trains no population: the nets are bound per member and the population has %d", members);
-    for (int r = 0; r < 4; r++)
-        if (slot[r] && slot[r]->net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
+    int n_bf = 0, n_f32 = 0, first_f32 = -1;
+    for (int r = 0; r < 4; r++) {
+        if (!slot[r]) continue;
+        if (slot[r]->net.prec != RANENV_NET_F32) {
+            if (!bf16) return fail(h, RANENV_E_STATE, "the PPO update trains float32 nets: the %s net is bf16", NET_ROLES[r].who);
+            n_bf++;
+        } else if (n_f32++ == 0) first_f32 = r;
+    }
+    if (bf16 && n_bf == 0) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind_spread_bfloat trains RANENV_NET_BF16 nets: the bound nets are float32 (ranenv_ppo_bind_spread trains those)");
+    if (bf16 && n_f32) return fail(h, RANENV_E_STATE, "ranenv_ppo_bind_spread_bfloat trains nets of one precision: the %s net is float32 beside bf16 nets", NET_ROLES[first_f32].who);
     return ppo_each_shape(slot, mixed, wide, members, [&](int m, int k, long long, size_t lds, long long) {
         if (lds <= (size_t)PPO_LDS_MAX) return (int)RANENV_OK;
         char whose[40];      // (a member binding under either of its plans names the member)
         if (!slices && !spread && (mixed || wide)) snprintf(whose, sizeof(whose), "member %d: its %s nets", m, k ? "intra" : "inter");
         else snprintf(whose, sizeof(whose), "the %s nets", k ? "intra" : "inter");
         return fail(h, RANENV_E_STATE, "%s need %zu bytes of LDS for %s, the update has %d", whose, lds,
-                    wide ? "two 32-row buffers of the wide plan" : "their 32-row activations of all layers", (int)PPO_LDS_MAX);
-    });
+                    bf16 ? "their 32-row bf16 activations of all layers" : (wide ? "two 32-row buffers of the wide plan" : "their 32-row activations of all layers"),
+                    (int)PPO_LDS_MAX);
+    }, bf16);
 }
 
 // A mixed binding's per-member packed floats [4][POP_MAX] (0: the role is not bound) as the slots stand, to the device on the caller's stream
@@ -2300,6 +2335,39 @@ static int ppo_floats_upload(ranenv_handle h, hipStream_t s)
 // that form, which ends the binding too, and a per-slice bind replaces all S copies -- their moments and the S slice counters restart.
 static int ppo_head_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
 static int sac_rebound(ranenv_handle h, ranenv::NetSlot *slot, hipStream_t s);
+
+// ranenv_ppo_bind_spread_bfloat: what the kernels take of the one-net slot `slot` beside its PpoNet -- the F32 layout's offsets, the acting
+// copy and the transposed one -- and its PpoNet: the master, m, v and g in role r's buffer, ppo_bf_cap[r] floats each
+static PpoBf16Net ppo_bf16_net(ranenv_handle h, const ranenv::NetSlot *slot)
+{
+    PpoBf16Net n{};
+    if (!slot) return n;
+    net_floats_f32(slot->net, &n);
+    n.acting = slot->w; n.wt = h->d_ppo_bf[slot->role] + 4 * h->ppo_bf_cap[slot->role];
+    return n;
+}
+static PpoNet ppo_bf16_state(ranenv_handle h, const ranenv::NetSlot *slot)
+{
+    PpoNet n{};
+    if (!slot) return n;
+    const long long cap = h->ppo_bf_cap[slot->role];
+    n.net = slot->net; n.net.w = nullptr;
+    n.w = h->d_ppo_bf[slot->role]; n.m = n.w + cap; n.v = n.w + 2 * cap; n.g = n.w + 3 * cap;
+    n.floats = net_floats_f32(slot->net);
+    return n;
+}
+static bool ppo_bf16_fits(ranenv_handle h, const ranenv::NetSlot *slot)
+{
+    const int r = slot->role;
+    return slot->net.prec == RANENV_NET_BF16 && h->d_ppo_bf[r] && net_floats_f32(slot->net) <= h->ppo_bf_cap[r] && net_floats(slot->net) <= h->ppo_bf_cap16[r];
+}
+// The master and the transposed copy of `slot`'s net from its acting copy, on the caller's stream (the bind and every re-bind)
+static int ppo_bf16_seed(ranenv_handle h, const ranenv::NetSlot *slot, hipStream_t s)
+{
+    HIP_TRY(h, launch_ppo_bf16_seed(s, slot->net, ppo_bf16_net(h, slot), h->d_ppo_bf[slot->role], net_floats_f32(slot->net)));
+    return RANENV_OK;
+}
+
 static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipStream_t s)
 {
     if (slot == &h->head || slot == &h->sac_q1 || slot == &h->sac_q2)
@@ -2308,6 +2376,15 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
     const ranenv::PpoBinding b = h->ppo;
     if (!b.on) return RANENV_OK;
     if (slot->role < 0) return RANENV_OK;      // (a net the update never trains)
+    if (b.bf16) {       // the master re-seeded from the new acting copy, Wt rebuilt, the kind's moments and counter restarted -- or the binding ends
+        if (slot->form != FORM_ONE) return RANENV_OK;      // (nets per slice or per member now serve the role: the next update refuses them in its words)
+        if (!ppo_bf16_fits(h, slot)) { h->ppo = {}; return RANENV_OK; }
+        if (const int rc = ppo_bf16_seed(h, slot, s); rc != RANENV_OK) return rc;
+        for (const int r : {slot->role, slot->role ^ 2})
+            if (h->d_ppo_bf[r]) HIP_TRY(h, hipMemsetAsync(h->d_ppo_bf[r] + h->ppo_bf_cap[r], 0, sizeof(float) * 2 * (size_t)h->ppo_bf_cap[r], s));
+        HIP_TRY(h, hipMemsetAsync(h->d_ppo_t + b.wg(slot->role & 1, 0), 0, sizeof(int32_t), s));
+        return RANENV_OK;
+    }
     if (!b.slices && slot->form == FORM_SLICE) return RANENV_OK;      // (... nor does a member binding train the nets per slice)
     const int kind = slot->role & 1;
     if ((b.slices && slot->form != (kind ? FORM_SLICE : FORM_ONE)) || !slot->opt || slot->cap > slot->opt_cap) { h->ppo = {}; return RANENV_OK; }
@@ -2337,14 +2414,14 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
 // `slabs` times the pair's need, the kinds back to back --, and the reduce / apply blocks of the larger kind.  The doubles of one
 // kind: block partials, slab statistics, running sums.
 struct PpoSpreadNeed { long long slab, park, blocks; };
-static PpoSpreadNeed ppo_spread_need(ranenv::NetSlot *const (&slot)[4], bool wide, int slabs)
+static PpoSpreadNeed ppo_spread_need(ranenv::NetSlot *const (&slot)[4], bool wide, int slabs, bool bf16 = false)
 {
     PpoSpreadNeed n{};
     ppo_each_shape(slot, false, wide, 1, [&](int, int, long long floats, size_t, long long park) {
         n.slab += floats * slabs; n.park += park * slabs;
         n.blocks = std::max(n.blocks, (floats + PPO_SPREAD_BLOCK - 1) / PPO_SPREAD_BLOCK);
         return (int)RANENV_OK;
-    });
+    }, bf16);
     return n;
 }
 static long long ppo_spread_doubles(long long blocks) { return blocks + PPO_SPREAD_SLABS_MAX * PPO_SPREAD_STATS + RANENV_PPO_STATS; }
@@ -2355,11 +2432,11 @@ static int ppo_bind(ranenv_handle h, ranenv::PpoBinding b, void *stream)
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
     ranenv::NetSlot *slot[4];
     int members = 1;
-    if (const int rc = ppo_roles(h, b.slices, slot, members, b.mixed, b.wide, b.slabs > 0); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, b.slices, slot, members, b.mixed, b.wide, b.slabs > 0, b.bf16); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     if (b.slabs) {      // the spread binding's own: slabs, block partials, slab statistics and running sums, and (wide) the parked rows per slab
-        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs);
+        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs, b.bf16);
         if (h->ppo_slab_cap < need.slab) {
             if (const int rc = dev_alloc(h, &h->d_ppo_slab, (size_t)need.slab); rc != RANENV_OK) return rc;
             h->ppo_slab_cap = need.slab;
@@ -2390,9 +2467,22 @@ static int ppo_bind(ranenv_handle h, ranenv::PpoBinding b, void *stream)
     if (b.mixed && !h->d_ppo_floats)
         if (const int rc = dev_alloc(h, &h->d_ppo_floats, (size_t)4 * POP_MAX); rc != RANENV_OK) return rc;
     HIP_TRY(h, hipMemsetAsync(h->d_ppo_t, 0, sizeof(int32_t) * POP_MAX * 2, s));
-    for (int r = 0; r < 4; r++)
-        if (slot[r])
+    for (int r = 0; r < 4; r++) {
+        if (!slot[r]) continue;
+        if (!b.bf16) {
             if (const int rc = opt_ensure(h, slot[r], s); rc != RANENV_OK) return rc;
+            continue;
+        }
+        // a bf16 net's f32 state (an outgrown allocation grows, a larger one stays): zeroed, then master and Wt seeded from the acting copy
+        const long long f32 = net_floats_f32(slot[r]->net), f16 = net_floats(slot[r]->net);
+        if (!h->d_ppo_bf[r] || h->ppo_bf_cap[r] < f32 || h->ppo_bf_cap16[r] < f16) {
+            const long long c32 = std::max(f32, h->ppo_bf_cap[r]), c16 = std::max(f16, h->ppo_bf_cap16[r]);
+            if (const int rc = dev_alloc(h, &h->d_ppo_bf[r], (size_t)(4 * c32 + c16)); rc != RANENV_OK) return rc;
+            h->ppo_bf_cap[r] = c32; h->ppo_bf_cap16[r] = c16;
+        }
+        HIP_TRY(h, hipMemsetAsync(h->d_ppo_bf[r], 0, sizeof(float) * (size_t)(4 * h->ppo_bf_cap[r] + h->ppo_bf_cap16[r]), s));
+        if (const int rc = ppo_bf16_seed(h, slot[r], s); rc != RANENV_OK) return rc;
+    }
     h->ppo = b;
     return b.mixed ? ppo_floats_upload(h, s) : RANENV_OK;
 }
@@ -2417,6 +2507,12 @@ int ranenv_ppo_bind_spread(ranenv_handle h, int32_t slabs, int32_t wide, void *s
     if (wide != 0 && wide != 1) return fail(h, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
     return ppo_bind(h, {true, false, wide == 1, false, slabs}, stream);
 }
+// (bf16 nets over the chip, include/ranenv.h "bf16 nets over the chip")
+int ranenv_ppo_bind_spread_bfloat(ranenv_handle h, int32_t slabs, void *stream)
+{
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(h, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    return ppo_bind(h, {true, false, false, false, slabs, true}, stream);
+}
 
 // The bound state behind the binding of the caller's geometry (slices: ranenv_ppo_bind_slices, else one of the member bindings), or
 // RANENV_E_STATE
@@ -2432,13 +2528,14 @@ static int ppo_bound(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], 
         if (!b.on) return fail(h, RANENV_E_STATE, "no PPO state bound, or a binding call has outgrown it (ranenv_ppo_bind)");
         if (b.slices) return fail(h, RANENV_E_STATE, "the PPO state was bound per slice (ranenv_ppo_bind_slices): ranenv_ppo_update_slices trains it");
     }
-    if (const int rc = ppo_roles(h, slices, slot, members, b.mixed, b.wide, b.slabs > 0); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, slices, slot, members, b.mixed, b.wide, b.slabs > 0, b.bf16); rc != RANENV_OK) return rc;
     for (int r = 0; r < 4; r++)
-        if (slot[r] && (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)) return fail(h, RANENV_E_STATE, "the %s net was bound after %s: bind again", NET_ROLES[r].who, b.entry());
+        if (slot[r] && (b.bf16 ? !ppo_bf16_fits(h, slot[r]) : (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)))
+            return fail(h, RANENV_E_STATE, "the %s net was bound after %s: bind again", NET_ROLES[r].who, b.entry());
     if (b.slabs) {      // a spread binding: the slabs, block partials and parked rows of the nets as they stand fit what the bind allocated
-        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs);
+        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs, b.bf16);
         if (need.slab > h->ppo_slab_cap || need.blocks > h->ppo_spread_blocks || need.park > h->ppo_park_cap)
-            return fail(h, RANENV_E_STATE, "the bound nets need more slab or parked floats than ranenv_ppo_bind_spread allocated: bind again");
+            return fail(h, RANENV_E_STATE, "the bound nets need more slab or parked floats than %s allocated: bind again", b.entry());
         return RANENV_OK;
     }
     if (!b.wide) return RANENV_OK;
@@ -2467,8 +2564,8 @@ int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes)
     ranenv::NetSlot *slot[4];
     int members = 0;
     const bool mixed = h->pop_mixed(), wide = h->ppo.wide;
-    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide, h->ppo.slabs > 0); rc != RANENV_OK) return rc;
-    const PpoPlan plan = ppo_plan(slot, mixed, wide, members);
+    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide, h->ppo.slabs > 0, h->ppo.bf16); rc != RANENV_OK) return rc;
+    const PpoPlan plan = ppo_plan(slot, mixed, wide, members, 2, h->ppo.bf16);
     if (grad_floats) *grad_floats = plan.grad_floats;
     if (lds_bytes) *lds_bytes = (int64_t)plan.lds;
     return RANENV_OK;
@@ -2480,13 +2577,13 @@ int ranenv_ppo_member_layout(ranenv_handle h, int32_t member, int32_t kind, int6
     ranenv::NetSlot *slot[4];
     int members = 0;
     const bool mixed = h->pop_mixed(), wide = h->ppo.wide;
-    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide, h->ppo.slabs > 0); rc != RANENV_OK) return rc;
+    if (const int rc = ppo_roles(h, h->ppo.slices, slot, members, mixed, wide, h->ppo.slabs > 0, h->ppo.bf16); rc != RANENV_OK) return rc;
     members = h->ppo.units(kind, members, h->cfg.n_slices);      // (the slices' pairs have one shape: slice 0's entry answers for all)
     if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
     if (kind != 0 && kind != 1) return fail(h, RANENV_E_INVALID, "kind %d (0 inter, 1 intra)", kind);
     if (!slot[kind]) return fail(h, RANENV_E_STATE, "no %s actor bound", kind ? "intra" : "inter");
     long long af, cf; size_t lds;
-    ppo_member_shape(slot, mixed, member, kind, af, cf, lds, wide);
+    ppo_member_shape(slot, mixed, member, kind, af, cf, lds, wide, nullptr, h->ppo.bf16);
     if (actor_floats) *actor_floats = af;
     if (critic_floats) *critic_floats = cf;
     if (lds_bytes) *lds_bytes = (int64_t)lds;
@@ -2541,6 +2638,26 @@ int ranenv_ppo_spread_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, i
     return RANENV_OK;
 }
 
+int ranenv_ppo_spread_bfloat_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t slabs, int64_t *lds_bytes, int64_t *device_bytes)
+{
+    if (!actor || (!lds_bytes && !device_bytes)) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(nullptr, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    PolicyNet net[2] = {};
+    if (const int rc = ppo_shape_pair(actor, critic, net); rc != RANENV_OK) return rc;      // (kp, np: the same in either precision)
+    if (lds_bytes) *lds_bytes = (int64_t)ppo_bf16_lds_bytes(net[0], critic ? &net[1] : nullptr);
+    if (device_bytes) {      // slabs of the pair's f32 floats; per net master, m, v, g in f32 and the transposed bf16 weights beside its biases
+        long long floats = 0, state = 0;
+        for (int i = 0; i < (critic ? 2 : 1); i++) {
+            const long long f32 = net_floats_f32(net[i]);
+            long long w = 0;
+            for (int l = 0; l < net[i].n_layers; l++) w += (long long)net[i].kp[l] * net[i].np[l];
+            floats += f32; state += 4 * f32 + (f32 - w / 2);
+        }
+        *device_bytes = (int64_t)sizeof(float) * (slabs * floats + state);
+    }
+    return RANENV_OK;
+}
+
 int ranenv_ppo_spread_plan(int64_t n_rows, int32_t minibatch, int32_t epochs, int32_t slabs, int64_t *steps, int32_t *grid, int32_t *tiles_last)
 {
     if (n_rows < 0 || n_rows > 0x7fffffffLL) return fail(nullptr, RANENV_E_INVALID, "n_rows %lld (0..2^31 - 1)", (long long)n_rows);
@@ -2586,7 +2703,8 @@ static int ppo_update_spread(ranenv_handle h, ranenv::NetSlot *const (&slot)[4],
         if (!slot[k]) continue;
         PpoSpreadKind &K = p.k[k];
         const PolicyNet *critic = slot[2 + k] ? &slot[2 + k]->net : nullptr;
-        const long long floats = net_floats(slot[k]->net) + (critic ? net_floats(*critic) : 0);
+        const long long floats = b.bf16 ? net_floats_f32(slot[k]->net) + (critic ? net_floats_f32(*critic) : 0)
+                                        : net_floats(slot[k]->net) + (critic ? net_floats(*critic) : 0);
         K.slab = slab; K.slab_stride = floats; slab += floats * b.slabs;
         if (b.wide) { K.park = park; K.park_stride = ppo_wide_scratch(slot[k]->net, critic); park += K.park_stride * b.slabs; }
         K.bpart = h->d_ppo_spread + k * ppo_spread_doubles(h->ppo_spread_blocks);
@@ -2599,6 +2717,17 @@ static int ppo_update_spread(ranenv_handle h, ranenv::NetSlot *const (&slot)[4],
         if (k_steps > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "%lld optimiser steps (epochs x minibatches of the %s kind): more than 2^31 - 1", k_steps, k ? "intra" : "inter");
         K.steps = (int)k_steps;
         steps = std::max(steps, k_steps);
+    }
+    if (b.bf16) {
+        PpoSpreadBf16Args q{};
+        q.p = p;
+        for (int k = 0; k < 2; k++)
+            for (int i = 0; i < 2; i++) q.bf[k][i] = ppo_bf16_net(h, slot[2 * i + k]);
+        for (long long i = 0; i < steps; i++) {
+            q.p.step = (int)i;
+            HIP_TRY(h, launch_ppo_spread_step_bf16(s, lds, q));
+        }
+        return RANENV_OK;
     }
     for (long long i = 0; i < steps; i++) {
         p.step = (int)i;
@@ -2645,14 +2774,15 @@ static int ppo_update(ranenv_handle h, bool slices, int32_t n_steps, const ranen
             if (first[k][u + 1] < first[k][u]) return fail(h, RANENV_E_INVALID, "host_first_%s decreases at %s %d", list, slices ? "slice" : "member", u);
         for (int u = 0; u <= units; u++) a.first[k][u] = first[k][u];
         a.order[k] = order[k]; a.order_stride[k] = first[k][units];
-        a.net[k][0] = ppo_net(slot[k]); a.net[k][1] = ppo_net(slot[2 + k]);
+        if (b.bf16) { a.net[k][0] = ppo_bf16_state(h, slot[k]); a.net[k][1] = ppo_bf16_state(h, slot[2 + k]); }
+        else { a.net[k][0] = ppo_net(slot[k]); a.net[k][1] = ppo_net(slot[2 + k]); }
     }
     if (max_epochs == 0) return RANENV_OK;
     a.T = n_steps; a.B = h->cfg.batch; a.S = S; a.Us = h->cfg.max_ues_slice; a.W = 2 * a.Us + 9;
     a.hp = h->d_ppo_hp; a.traj = *traj; a.t = h->d_ppo_t; a.max_epochs = max_epochs; a.stats = stats; a.grad = grad; a.probe_logp = probe_logp;
     // The launch's LDS: the largest need over the kinds this call updates (a mixed binding: and over the members).  dev_grad's stride
     // is ranenv_ppo_layout's: the largest of the BOUND nets, whether or not this call updates the intra kind
-    const PpoPlan plan = ppo_plan(slot, b.mixed, b.wide, members, intra ? 2 : 1);
+    const PpoPlan plan = ppo_plan(slot, b.mixed, b.wide, members, intra ? 2 : 1, b.bf16);
     a.grad_stride = plan.grad_floats;
     PpoMixed x{};
     if (b.mixed) {      // (every bound role is the population's: its table; the others the table of zeros)
@@ -2727,6 +2857,14 @@ int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_
 {
     ranenv::NetSlot *x = nullptr; size_t at = 0; int32_t *t = nullptr;
     if (const int rc = ppo_state_at(h, false, role, member, x, at, t); rc != RANENV_OK) return rc;
+    if (h->ppo.bf16) {      // (the moments of a bf16 net lie beside its f32 master, in the F32 packed layout)
+        const PpoNet n = ppo_bf16_state(h, x);
+        if (dev_m) *dev_m = n.m;
+        if (dev_v) *dev_v = n.v;
+        if (dev_t) *dev_t = t;
+        if (floats) *floats = n.floats;
+        return RANENV_OK;
+    }
     if (dev_m) *dev_m = x->opt + at;
     if (dev_v) *dev_v = x->opt + x->opt_cap + at;
     if (dev_t) *dev_t = t;
@@ -2746,9 +2884,17 @@ int ranenv_ppo_slice_state(ranenv_handle h, int32_t role, int32_t slice, float *
 }
 
 // Copy `member` of `slot` (`who` for the messages) unpacked to torch Linear layout: ranenv_get_net_weights / ranenv_get_head_net_weights
-static int net_export(ranenv_handle h, const ranenv::NetSlot *slot, int member, const char *who, ranenv_mlp *out, void *stream, const float *packed = nullptr)
+// master: a bf16 net's f32 master copy under ranenv_ppo_bind_spread_bfloat, in the F32 packed layout -- the one form of a bf16 net that exports
+static int net_export(ranenv_handle h, const ranenv::NetSlot *slot, int member, const char *who, ranenv_mlp *out, void *stream, const float *packed = nullptr,
+                      const float *master = nullptr)
 {
-    const PolicyNet &net = slot->member[(size_t)member];
+    PolicyNet net = slot->member[(size_t)member];
+    if (master) {
+        PpoBf16Net f32{};
+        net_floats_f32(net, &f32);
+        for (int l = 0; l < net.n_layers; l++) { net.w_off[l] = f32.w_off[l]; net.b_off[l] = f32.b_off[l]; }
+        net.prec = RANENV_NET_F32; packed = master;
+    }
     if (net.prec != RANENV_NET_F32) return fail(h, RANENV_E_STATE, "the %s net is bf16: its float32 weights were rounded at bind", who);
     const int32_t *dims = slot->member_dims[(size_t)member].data();
     const int L = net.n_layers;
@@ -2756,7 +2902,7 @@ static int net_export(ranenv_handle h, const ranenv::NetSlot *slot, int member, 
         if ((out->weight[l] == nullptr) != (out->weight[0] == nullptr) || (out->bias[l] == nullptr) != (out->weight[0] == nullptr))
             return fail(h, RANENV_E_INVALID, "give every layer's weight and bias buffer, or none");
     const bool copy = out->weight[0] != nullptr;
-    out->n_hidden = L - 1; out->activation = net.act; out->input_layout = net.layout; out->precision = net.prec;
+    out->n_hidden = L - 1; out->activation = net.act; out->input_layout = net.layout; out->precision = slot->member[(size_t)member].prec;
     for (int l = 0; l < 6; l++) out->dims[l] = l <= L ? dims[l] : 0;
     if (!copy) return RANENV_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -2779,7 +2925,8 @@ int ranenv_get_net_weights(ranenv_handle h, int32_t role, int32_t member, ranenv
     if (slot->form == FORM_SLICE) return fail(h, RANENV_E_STATE, "the %s nets are bound per slice", NET_ROLES[role].who);
     const int members = (int)slot->member.size();
     if (member < 0 || member >= members) return fail(h, RANENV_E_INVALID, "member %d outside the %d", member, members);
-    return net_export(h, slot, member, NET_ROLES[role].who, out, stream);
+    const bool master = h->ppo.on && h->ppo.bf16 && slot->form == FORM_ONE && ppo_bf16_fits(h, slot);
+    return net_export(h, slot, member, NET_ROLES[role].who, out, stream, nullptr, master ? h->d_ppo_bf[role] : nullptr);
 }
 
 int ranenv_get_slice_net_weights(ranenv_handle h, int32_t role, int32_t slice, ranenv_mlp *out, void *stream)

@@ -346,6 +346,19 @@ struct PpoSpreadArgs {
 };
 // The three launches of optimiser step a.step (grid_pass / blocks: the larger kind's); wide: the pass under the wide plan
 hipError_t launch_ppo_spread_step(hipStream_t, size_t lds, const PpoSpreadArgs &, bool wide);
+// ... under ranenv_ppo_bind_spread_bfloat (include/ranenv.h "bf16 nets over the chip"): the nets are RANENV_NET_BF16 ones.  PpoNet of such a
+// net: `net` the ACTING copy's layout (bf16 W, two per float); w the f32 MASTER copy Adam steps, and m, v, g, `floats`, all in the F32
+// packed layout, the slabs' and dev_grad's.  Beside it that layout's offsets, the acting copy the pass's forward reads
+// (acting == bf16(master) behind every apply) and the transposed bf16 copy its backward product reads: layer l's Wt [kp][np] at float
+// net.w_off[l] of `wt`.
+struct PpoBf16Net { long long w_off[NET_MAX_LAYERS], b_off[NET_MAX_LAYERS]; float *acting, *wt; };
+struct PpoSpreadBf16Args { PpoSpreadArgs p; PpoBf16Net bf[2][2]; };      // bf[kind][0 the actor, 1 the critic]
+// Bytes of LDS of a bf16 pair's pass: PPO_FIXED and the larger net's rows -- bf16 rows of the input and every hidden layer at stride
+// net_ld16, the output layer's f32 rows
+size_t ppo_bf16_lds_bytes(const PolicyNet &actor, const PolicyNet *critic);
+hipError_t launch_ppo_spread_step_bf16(hipStream_t, size_t lds, const PpoSpreadBf16Args &);
+// master and wt of one net from its acting copy (the bind and every re-bind): bf16 W widened, f32 biases copied, Wt transposed
+hipError_t launch_ppo_bf16_seed(hipStream_t, const PolicyNet &net, const PpoBf16Net &bf, float *master, long long floats);
 
 // ranenv_ppo_update_head (include/ranenv.h "PPO update of the head policies"): the head actor and critic (net[0], net[1]; stride unused),
 // the handle's log_std [S] with its moments and gradient scratch, the call's hyper-parameters by value, the row lists

@@ -120,7 +120,8 @@ __device__ __forceinline__ void tile_bf16(f32x4 (&acc)[2][2], const __bf16 *W, c
 // The layers of `net`, its packed copy at `wb`, on the 32 rows in `cur`; on return `cur` holds the output layer's rows (f32, stride
 // net_ld(np[last])).  BF: a bf16 net -- bf16 rows in `cur` (stride net_ld16) and between the layers, bf16 W.
 // KEEP (the PPO update's backward pass reads them): every layer's rows stay -- layer l writes behind its input rows, at cur + 32 net_ld(kp[l])
-// floats, so `nxt` is cur + 32 net_ld(kp[0]) on entry; on return `cur` holds the output layer's rows and `nxt` points behind them.
+// floats (BF: 32 net_ld16(kp[l]) bf16, half as many floats), so `nxt` is cur + 32 net_ld(kp[0]) (BF: cur + 16 net_ld16(kp[0])) on entry;
+// on return `cur` holds the output layer's rows and `nxt` points behind them.
 template <bool BF = false, bool KEEP = false>
 __device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb, float *&cur, float *&nxt, int lane, int wave)
 {
@@ -174,7 +175,7 @@ __device__ __forceinline__ void net_layers(const PolicyNet &net, const float *wb
                 }
         }
         __syncthreads();
-        if constexpr (KEEP) { cur = nxt; nxt += NET_ROWS * ldo; }
+        if constexpr (KEEP) { cur = nxt; nxt += NET_ROWS * (BF && !last ? ldo / 2 : ldo); }      // (bf16 rows: two elements per float)
         else { float *t = cur; cur = nxt; nxt = t; }
     }
 }

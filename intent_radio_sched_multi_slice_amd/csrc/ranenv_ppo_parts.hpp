@@ -1,7 +1,8 @@
 // ranenv_ppo_parts.hpp -- the one statement of every step the training kernels share (ranenv_ppo.hip: the PPO updates of the bound nets
 // and of the head policies; ranenv_ppo_spread.hip: one agent's PPO update spread over the chip, the IBSched pair's and the head pair's
 // -- whose elementwise reduce / apply steps (ppo_spread_*) stand at the end; ranenv_sac.hip: the SAC update): the LDS size of a net's
-// rows, the backward pass of one 32-row tile on the f32 matrix cores and its dZ' block walk, the workgroup sum in slot order, Adam's
+// rows, the backward pass of one 32-row tile on the f32 matrix cores and its dZ' block walk (ppo_backward_bf16: a bf16 net's, on the
+// bf16 matrix cores, with ppo_bf16_reround, which keeps its acting copies at bf16 of the master), the workgroup sum in slot order, Adam's
 // constants and float32 element step, and the steps of a PPO minibatch -- zeroing, the advantages' mean and std, the tile's row list,
 // the clipped surrogate, the critic row, the joint norm and clip scale, the statistics, the gradient copy -- and the 32-row tile
 // itself, once per pair of nets: ppo_tile for the IBSched nets (the member update and the spread pass; its steps: the record cell, the
@@ -19,6 +20,15 @@ __host__ __device__ inline int ppo_act_floats(const PolicyNet &net)
     int n = NET_ROWS * net_ld(net.kp[0]);
     for (int l = 0; l < net.n_layers; l++) n += NET_ROWS * net_ld(net.np[l]);
     return n;
+}
+
+// Bytes of LDS for the rows of a bf16 net (ranenv_ppo_bind_spread_bfloat): the input's and every hidden layer's 32 rows in bf16 at stride
+// net_ld16, the output layer's in f32 at stride net_ld -- net_layers<true, true>'s layout
+__host__ __device__ inline int ppo_bf16_act_bytes(const PolicyNet &net)
+{
+    int n = 0;
+    for (int l = 0; l < net.n_layers; l++) n += NET_ROWS * net_ld16(net.kp[l]) * 2;
+    return n + NET_ROWS * net_ld(net.np[net.n_layers - 1]) * 4;
 }
 
 // ---- the wide plan (ranenv_ppo_bind_wide): two row buffers in LDS, every layer's input rows parked in the workgroup's scratch --------
@@ -131,6 +141,83 @@ __device__ __forceinline__ void ppo_backward(const PolicyNet &net, const float *
         if (l == 0) break;
         __syncthreads();                       // (dW has read A: dZ' may overwrite it)
         ppo_dz_blocks(net, l, w + net.w_off[l], dz, a, 0, kb, tid);
+        __syncthreads();
+        dz = a;
+    }
+}
+
+// The backward pass of one tile of a bf16 net (ranenv_ppo_bind_spread_bfloat; include/ranenv.h states the contract) on the bf16 matrix
+// cores: `out` = the output layer's f32 rows, holding G = dL/d(output); in front of them the bf16 rows of every layer's input, as
+// net_layers<true, true> left them.  D_L = bf16(G) is written over G first (a bf16 row lies below the f32 row it comes from, so chunks
+// of 256 elements in ascending order, each read in front of a barrier and written behind it, never overwrite a value still to be read).
+// Layer l: dW_l = D_l^T A_{l-1} -- the tile's 32 rows are ONE MFMA's K, a 16x16 block of dW is one MFMA; both operands are column
+// reads of the row-major rows (16-bit LDS reads) --, db_l the column sums of D_l, both added in f32 into `g` (the F32 packed layout:
+// bf.w_off / b_off); then D_{l-1} = bf16((D_l Wq_l) act'(A_{l-1})) over A_{l-1} in place: D_l by rows from LDS, Wq_l from the
+// transposed copy bf.wt (Wt [kp][np]: a 16-byte load per lane and 32 n, a vector load at a lane-dependent address -- THE WEIGHT-READ
+// RULE at ppo_tile holds for both bf16 copies), act' from the rounded activation.  Dead rows are zero rows of G.  Ends without a barrier.
+__device__ __forceinline__ void ppo_backward_bf16(const PolicyNet &net, const PpoBf16Net &bf, float *g, float *out, int tid)
+{
+    const int lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
+    const int L = net.n_layers;
+    {
+        const int N = net.np[L - 1], ldf = net_ld(N), ldo = net_ld16(N);
+        __bf16 *d = (__bf16 *)out;
+        for (int e0 = 0; e0 < NET_ROWS * N; e0 += 256) {
+            const int e = e0 + tid, r = e / N, n = e - r * N;
+            const float v = out[r * ldf + n];
+            __syncthreads();
+            d[r * ldo + n] = (__bf16)v;
+        }
+        __syncthreads();
+    }
+    __bf16 *dz = (__bf16 *)out;
+    for (int l = L - 1; l >= 0; l--) {
+        const int K = net.kp[l], N = net.np[l], ldi = net_ld16(K), ldo = net_ld16(N), kb = K >> 4;
+        __bf16 *a = dz - NET_ROWS * ldi;
+        float *gW = g + bf.w_off[l], *gb = g + bf.b_off[l];
+        for (int blk = wave; blk < (N >> 4) * kb; blk += 4) {
+            const int nb = blk / kb, n0 = nb << 4, k0 = (blk - nb * kb) << 4;
+            bf16x8 dv, av;                     // operand element j: tile row 8 q + j
+#pragma unroll
+            for (int j = 0; j < 8; j++) { dv[j] = dz[(8 * q + j) * ldo + n0 + c]; av[j] = a[(8 * q + j) * ldi + k0 + c]; }
+            const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dv, av, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+            // C/D map of the 16x16 block: column (k) = lane & 15, row (n) = 4 (lane >> 4) + register
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                float *p = gW + (size_t)(n0 + 4 * q + i) * K + k0 + c;
+                *p = *p + acc[i];
+            }
+        }
+        for (int n = tid; n < N; n += 256) {
+            float s = 0.0f;
+#pragma unroll 4
+            for (int r = 0; r < NET_ROWS; r++) s += (float)dz[r * ldo + n];
+            gb[n] = gb[n] + s;
+        }
+        if (l == 0) break;
+        __syncthreads();                       // (dW has read A: D' may overwrite it)
+        const __bf16 *Wt = (const __bf16 *)(bf.wt + net.w_off[l]);
+        for (int blk = wave; blk < kb; blk += 4) {
+            const int k0 = blk << 4;
+            f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+            const bf16x8 *wp = (const bf16x8 *)(Wt + (size_t)(k0 + c) * N) + q;      // MFMA k: n = n0 + 8 q .. + 7 on both operands
+            const __bf16 *d0 = dz + c * ldo + 8 * q, *d1 = dz + (16 + c) * ldo + 8 * q;
+            bf16x8 b = wp[0];
+            for (int n0 = 0; n0 < N; n0 += 32) {
+                const bf16x8 nb = wp[(n0 + 32 < N ? n0 + 32 : n0) >> 3];
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8 *)(d0 + n0), b, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8 *)(d1 + n0), b, acc[1], 0, 0, 0);
+                b = nb;
+            }
+#pragma unroll
+            for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    __bf16 *p = a + (mi * 16 + 4 * q + i) * ldi + k0 + c;
+                    const float av = (float)*p;
+                    *p = (__bf16)(acc[mi][i] * (net.act == RANENV_ACT_RELU ? (av > 0.0f ? 1.0f : 0.0f) : 1.0f - av * av));
+                }
+        }
         __syncthreads();
         dz = a;
     }
@@ -284,10 +371,12 @@ constexpr int PPO_ROW_STATS = 6;          // per row: policy loss, entropy, logp
 __device__ __forceinline__ size_t ppo_cell(int kind, int i, int S) { return kind == 0 ? (size_t)i * (S + 1) : (size_t)(i / S) * (S + 1) + 1 + (i % S); }
 
 // The tile's rows of `net`'s input -> buffer 0: row r is record row idx[r] (< 0: a dead row, zeros), read as net_load_rows reads an
-// env's row -- the inter observation, or the slice's observation behind, for RANENV_NET_IN_MASK_OBS, its mask as floats
+// env's row -- the inter observation, or the slice's observation behind, for RANENV_NET_IN_MASK_OBS, its mask as floats.  BF: a bf16
+// net's rows, rounded to bf16 at stride net_ld16 (load_rows)
+template <bool BF = false>
 __device__ __forceinline__ void ppo_load_rows(const PolicyNet &net, const PpoArgs &A, int kind, const int *idx, float *dst, int tid)
 {
-    load_rows(net.kp[0], 0, 0, dst, tid, [&](int r, int k) {
+    load_rows<BF>(net.kp[0], 0, 0, dst, tid, [&](int r, int k) {
         const int i = idx[r];
         if (i < 0 || k >= net.in_dim) return 0.0f;
         if (kind == 0) return A.traj.obs_inter[(size_t)i * (size_t)(10 * A.S) + k];
@@ -383,11 +472,15 @@ __device__ __forceinline__ void ppo_actor_row(const PpoArgs &A, const ranenv_ppo
 // the launch before, wrote by vector stores, so every weight read -- the forward's float4 and bias loads, the backward's W loads -- is
 // a vector load at a lane-dependent address behind a workgroup barrier, never a read through the scalar cache; log_std is read through
 // its LDS copy.  Ends without a barrier: the next tile's first, or the caller's, is the one behind the backward pass.
-template <bool WIDE, class NetAt, class WAt, class GAt>
+// BF (ranenv_ppo_bind_spread_bfloat; never WIDE): the nets are bf16 ones -- net_at(k) the acting copy's layout, w_at(k) that copy, on which
+// the forward pass is the acting kernels' (net_layers<true>: the re-evaluated log-probability is the recorded one while the weights
+// stand), bf[k] the f32 layout's offsets and the transposed copy for ppo_backward_bf16, g_at(k) in the f32 layout.
+template <bool WIDE, bool BF = false, class NetAt, class WAt, class GAt>
 __device__ __forceinline__ void ppo_tile(const PpoArgs &A, const ranenv_ppo_hparams &hp, int kind, int n_nets, const int32_t *list, int c0, int t0, int nb,
                                          long long n_record, double wrow, double a_mean, double a_den, double *rowstat, int *rowidx, float *act, float *wpark,
-                                         PpoEpoch &st, int tid, NetAt net_at, WAt w_at, GAt g_at)
+                                         PpoEpoch &st, int tid, NetAt net_at, WAt w_at, GAt g_at, const PpoBf16Net *bf = nullptr)
 {
+    static_assert(!(WIDE && BF), "bf16 rows fit the LDS plan where the wide plan was needed");
     const int lane = tid & 63, wave = tid >> 6, S = A.S;
     __syncthreads();                           // (the previous tile's backward pass and statistics are read)
     ppo_list_rows(rowidx, list, c0, t0, nb, n_record, tid);
@@ -398,11 +491,11 @@ __device__ __forceinline__ void ppo_tile(const PpoArgs &A, const ranenv_ppo_hpar
         const float *w = w_at(k);
         float *g = g_at(k);
         __syncthreads();                       // (the tile's rows are listed; the actor's backward pass has read its rows)
-        float *cur = act, *nxt = act + NET_ROWS * net_ld(net.kp[0]);
-        ppo_load_rows(net, A, kind, rowidx, cur, tid);
+        float *cur = act, *nxt = act + NET_ROWS * (BF ? net_ld16(net.kp[0]) / 2 : net_ld(net.kp[0]));
+        ppo_load_rows<BF>(net, A, kind, rowidx, cur, tid);
         __syncthreads();
         if constexpr (WIDE) cur = ppo_forward_wide(net, w, act, act + ppo_wide_floats(net), wpark, tid);
-        else net_layers<false, true>(net, w, cur, nxt, lane, wave);
+        else net_layers<BF, true>(net, w, cur, nxt, lane, wave);
         if (tid < NET_ROWS) {
             const int i = rowidx[tid], np = net.np[net.n_layers - 1];
             float *o = cur + tid * net_ld(np);
@@ -411,7 +504,8 @@ __device__ __forceinline__ void ppo_tile(const PpoArgs &A, const ranenv_ppo_hpar
             else rs[5] = ppo_critic_row(o, i, [&] { return A.traj.vtarg[ppo_cell(kind, i, S)]; }, hp.vf_coeff, wrow);
         }
         __syncthreads();
-        if constexpr (WIDE) ppo_backward<true>(net, w, g, cur, tid, act, act + ppo_wide_floats(net), wpark);
+        if constexpr (BF) ppo_backward_bf16(net, bf[k], g, cur, tid);
+        else if constexpr (WIDE) ppo_backward<true>(net, w, g, cur, tid, act, act + ppo_wide_floats(net), wpark);
         else ppo_backward(net, w, g, cur, tid);
     }
     if (tid == 0) ppo_tile_stats(st, rowstat, PPO_ROW_STATS, n_nets == 2);      // (the barriers above have published the rows')
@@ -562,9 +656,10 @@ __device__ __forceinline__ double ppo_spread_norm2(const double *bpart, int bloc
     return tot;
 }
 
-// The apply of the block's elements: Adam in place on the scaled gradient; `grad` (or null): the unclipped gradient's copy
-template <class F>
-__device__ __forceinline__ void ppo_spread_apply_elems(long long floats, float *grad, float sc, const AdamStep &adam, int tid, F cell_at)
+// The apply of the block's elements: Adam in place on the scaled gradient; `grad` (or null): the unclipped gradient's copy.
+// stepped(e, w): what the bf16 binding does with element e's new value (ppo_bf16_reround)
+template <class F, class R>
+__device__ __forceinline__ void ppo_spread_apply_elems(long long floats, float *grad, float sc, const AdamStep &adam, int tid, F cell_at, R stepped)
 {
 #pragma unroll 1
     for (int j = 0; j < PPO_SPREAD_BLOCK / 256; j++) {
@@ -574,6 +669,30 @@ __device__ __forceinline__ void ppo_spread_apply_elems(long long floats, float *
         const float g = *c.g;
         if (grad) grad[e] = g;
         adam_elem(*c.w, *c.m, *c.v, g * sc, adam);
+        stepped(e, *c.w);
+    }
+}
+template <class F>
+__device__ __forceinline__ void ppo_spread_apply_elems(long long floats, float *grad, float sc, const AdamStep &adam, int tid, F cell_at)
+{
+    ppo_spread_apply_elems(floats, grad, sc, adam, tid, cell_at, [](long long, float) {});
+}
+
+// Element x of a bf16 net's F32 packed layout has the value w (the master's, behind Adam or at the seed): a weight W_l[n][k] goes,
+// rounded to nearest even, to the acting copy (bf16 [np][kp] at float net.w_off[l]) and to the transposed copy (Wt [kp][np] at the same
+// float of bf.wt); a bias to the acting copy's f32 bias.  So acting == bf16(master) and Wt == acting^T behind every launch that calls it.
+__device__ __forceinline__ void ppo_bf16_reround(const PolicyNet &net, const PpoBf16Net &bf, long long x, float w)
+{
+    for (int l = 0; l < net.n_layers; l++) {
+        if (x < bf.b_off[l]) {
+            const long long i = x - bf.w_off[l];
+            const int K = net.kp[l], n = (int)(i / K), k = (int)(i - (long long)n * K);
+            const __bf16 b = (__bf16)w;
+            ((__bf16 *)(bf.acting + net.w_off[l]))[i] = b;
+            ((__bf16 *)(bf.wt + net.w_off[l]))[(size_t)k * net.np[l] + n] = b;
+            return;
+        }
+        if (x < bf.b_off[l] + net.np[l]) { bf.acting[net.b_off[l] + (x - bf.b_off[l])] = w; return; }
     }
 }
 

@@ -23,8 +23,8 @@ namespace {
 
 __device__ __forceinline__ long long spread_floats(const PpoArgs &A, int kind) { return A.net[kind][0].floats + A.net[kind][1].floats; }
 
-template <bool WIDE>
-__device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P)
+template <bool WIDE, bool BF = false>
+__device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P, const PpoBf16Net (*bf)[2] = nullptr)
 {
     extern __shared__ float lds[];
     const PpoArgs &A = P.a;
@@ -58,9 +58,9 @@ __device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P)
 
 #pragma unroll 1
     for (int t0 = w * NET_ROWS; t0 < nb; t0 += geo.grid * NET_ROWS)
-        ppo_tile<WIDE>(A, hp, kind, n_nets, list, c0, t0, nb, n_record, wrow, a_mean, a_den, rowstat, rowidx, act, wpark, st, tid,
-                       [&](int k) -> const PolicyNet & { return A.net[kind][k].net; }, [&](int k) -> const float * { return A.net[kind][k].w; },
-                       [&](int k) { return slab + (k == 0 ? 0 : A.net[kind][0].floats); });
+        ppo_tile<WIDE, BF>(A, hp, kind, n_nets, list, c0, t0, nb, n_record, wrow, a_mean, a_den, rowstat, rowidx, act, wpark, st, tid,
+                           [&](int k) -> const PolicyNet & { return A.net[kind][k].net; }, [&](int k) -> const float * { return BF ? bf[kind][k].acting : A.net[kind][k].w; },
+                           [&](int k) { return slab + (k == 0 ? 0 : A.net[kind][0].floats); }, BF ? bf[kind] : nullptr);
     if (tid == 0) ppo_spread_wstat(K.wstat + (size_t)w * PPO_SPREAD_STATS, st);
 }
 
@@ -82,7 +82,9 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_reduce_kernel(PpoSpread
     if (tid == 0) K.bpart[blockIdx.x] = tot;
 }
 
-__global__ void __launch_bounds__(256) ranenv_ppo_spread_apply_kernel(PpoSpreadArgs P)
+// stepped(kind, e, w): element e of the kind's packed floats has the new value w (the bf16 binding re-rounds it into the acting copies)
+template <class R>
+__device__ __forceinline__ void spread_apply(const PpoSpreadArgs &P, R stepped)
 {
     const PpoArgs &A = P.a;
     const ranenv_ppo_hparams &hp = P.hp;
@@ -96,13 +98,50 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_apply_kernel(PpoSpreadA
     const bool last = P.step == K.steps - 1;
     const long long af = A.net[kind][0].floats, floats = spread_floats(A, kind);
     float *const grad = last && A.grad ? A.grad + (size_t)kind * (size_t)A.grad_stride : nullptr;
-    ppo_spread_apply_elems(floats, grad, sc, adam, tid, [&](long long e) { return ppo_spread_cell(A.net[kind][0], A.net[kind][1], af, e); });
+    ppo_spread_apply_elems(floats, grad, sc, adam, tid, [&](long long e) { return ppo_spread_cell(A.net[kind][0], A.net[kind][1], af, e); },
+                           [&](long long e, float w) { stepped(kind, e, w); });
     if (blockIdx.x != 0 || tid != 0) return;
     // ---- block 0: the epoch's statistics and the counter ---------------------------------------------------------------------------
     const PpoSpreadStep geo = ppo_spread_step(K.n, hp.minibatch, P.slabs, P.step);
     ppo_spread_stats(K.run, K.wstat, geo, norm, geo.mb == ppo_spread_per_epoch(K.n, hp.minibatch) - 1,
                      A.stats + ((size_t)kind * (size_t)A.max_epochs + geo.ep) * RANENV_PPO_STATS, K.n);
     if (last) A.t[kind] = t_call + K.steps;
+}
+
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_apply_kernel(PpoSpreadArgs P) { spread_apply(P, [](int, long long, float) {}); }
+
+// ---- bf16 nets over the chip (ranenv_ppo_bind_spread_bfloat; include/ranenv.h "bf16 nets over the chip") ---------------------------------
+// The same three launches for RANENV_NET_BF16 nets.  The pass is spread_pass on the bf16 tile (ppo_tile<false, true>): the forward on
+// the acting copy as the acting kernels run it, the backward on the bf16 matrix cores (ppo_backward_bf16), the slabs in the F32 packed
+// layout.  The reduce is the f32 binding's kernel: PpoNet's g and floats are in that layout.  The apply steps the f32 MASTER copy
+// (PpoSpreadCell's w) and stores bf16(master) into the acting copy and the transposed one, a bias into the acting copy's f32 bias: the
+// next pass and the next ranenv_collect read trained weights, by launch order alone.
+static_assert(sizeof(PpoSpreadBf16Args) <= 4096, "the bf16 spread launches' arguments fit a kernel's argument segment");
+
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_pass_kernel_bf16(PpoSpreadBf16Args Q) { spread_pass<false, true>(Q.p, Q.bf); }
+
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_apply_kernel_bf16(PpoSpreadBf16Args Q)
+{
+    spread_apply(Q.p, [&](int kind, long long e, float w) {
+        const long long af = Q.p.a.net[kind][0].floats;
+        const int k = e < af ? 0 : 1;
+        ppo_bf16_reround(Q.p.a.net[kind][k].net, Q.bf[kind][k], e - (k ? af : 0), w);
+    });
+}
+
+// The bind's and a re-bind's seed of one net: element x of the F32 layout's master from the acting copy -- a bf16 weight widened, an
+// f32 bias copied -- and, through ppo_bf16_reround (which stores back into the acting copy the value read from it), the transposed copy
+__global__ void __launch_bounds__(256) ranenv_ppo_bf16_seed_kernel(PolicyNet net, PpoBf16Net bf, float *master, long long floats)
+{
+    const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (x >= floats) return;
+    float w = 0.0f;
+    for (int l = 0; l < net.n_layers; l++) {
+        if (x < bf.b_off[l]) { w = (float)((const __bf16 *)(bf.acting + net.w_off[l]))[x - bf.w_off[l]]; break; }
+        if (x < bf.b_off[l] + net.np[l]) { w = bf.acting[net.b_off[l] + (x - bf.b_off[l])]; break; }
+    }
+    master[x] = w;
+    ppo_bf16_reround(net, bf, x, w);
 }
 
 // ---- the head policies over the chip (ranenv_ppo_bind_head_spread; include/ranenv.h "Head policies over the chip") -------------------
@@ -221,6 +260,38 @@ hipError_t launch_ppo_spread_step(hipStream_t s, size_t lds, const PpoSpreadArgs
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ranenv_ppo_spread_reduce_kernel, elem, block, 0, s, a);
     hipLaunchKernelGGL(ranenv_ppo_spread_apply_kernel, elem, block, 0, s, a);
+    return hipGetLastError();
+}
+
+size_t ppo_bf16_lds_bytes(const PolicyNet &actor, const PolicyNet *critic)
+{
+    int n = ppo_bf16_act_bytes(actor);
+    if (critic && critic->n_layers > 0) { const int v = ppo_bf16_act_bytes(*critic); n = v > n ? v : n; }
+    return (size_t)PPO_FIXED + (size_t)n;
+}
+
+hipError_t launch_ppo_spread_step_bf16(hipStream_t s, size_t lds, const PpoSpreadBf16Args &q)
+{
+    const PpoSpreadArgs &a = q.p;
+    int grid = 0, blocks = 0;
+    for (int k = 0; k < 2; k++) {
+        if (a.step >= a.k[k].steps) continue;
+        const int g = ppo_spread_step(a.k[k].n, a.hp.minibatch, a.slabs, a.step).grid;
+        grid = g > grid ? g : grid;
+        blocks = a.k[k].blocks > blocks ? a.k[k].blocks : blocks;
+    }
+    if (grid == 0) return hipSuccess;
+    const dim3 pass((unsigned)grid, 2), elem((unsigned)blocks, 2), block(256);
+    const hipError_t e = launch_lds<ranenv_ppo_spread_pass_kernel_bf16>(pass, block, lds, s, q);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ranenv_ppo_spread_reduce_kernel, elem, block, 0, s, a);
+    hipLaunchKernelGGL(ranenv_ppo_spread_apply_kernel_bf16, elem, block, 0, s, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_bf16_seed(hipStream_t s, const PolicyNet &net, const PpoBf16Net &bf, float *master, long long floats)
+{
+    hipLaunchKernelGGL(ranenv_ppo_bf16_seed_kernel, dim3((unsigned)((floats + 255) / 256)), dim3(256), 0, s, net, bf, master, floats);
     return hipGetLastError();
 }
 

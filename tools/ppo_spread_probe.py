@@ -30,7 +30,8 @@ import ppo_update_probe as up  # noqa: E402
 import ppo_wide_probe as wp  # noqa: E402
 
 OUT = os.path.join(REPO, "profiles", "ppo_spread_probe.json")
-NEW_EXPORTS = ("ranenv_ppo_bind_spread", "ranenv_ppo_spread_bytes", "ranenv_ppo_spread_plan")
+NEW_EXPORTS = ("ranenv_ppo_bind_spread", "ranenv_ppo_spread_bytes", "ranenv_ppo_spread_plan",
+               "ranenv_ppo_bind_spread_bfloat", "ranenv_ppo_spread_bfloat_bytes")      # (... and tools/ppo_bf16_probe.py's, which runs part (c) against its parent)
 
 
 def _agent(torch, B, T, widths, epochs, nets=None, **bind):
