@@ -1,7 +1,7 @@
 """The loop of examples/train_ppo_on_device.py with BOTH halves on the device: `collect()` records the batch, `ppo_update()` under the
 spread binding trains ONE agent on it with every optimiser step spread over the chip.
 
-    python examples/train_ppo_large_batch_on_device.py [--batch 4096] [--ttis 64] [--iters 10] [--epochs 4] [--minibatch 65536] [--slabs 64] [--bf16]
+    python examples/train_ppo_large_batch_on_device.py [--batch 4096] [--ttis 64] [--iters 10] [--epochs 4] [--minibatch 65536] [--slabs 64] [--bf16] [--device-order]
 
 Per iteration:
 
@@ -18,6 +18,9 @@ collection in it, and per iteration the mean inter-slice reward and the last epo
 `--bf16`: the same loop a second time with every net bound with precision="bf16" under `ppo_bind(spread=True, bf16=True)` -- acting and
 learning both on the bf16 matrix cores, float32 master weights behind the acting copy -- from the same initial weights and seeds, and
 the two runs' losses and rates side by side.  The runs differ from the first collect() on: the bf16 nets act on rounded weights.
+
+`--device-order`: the minibatch row lists come from the library's own kernels (`ppo_update(..., order="device")`: a stable
+compaction of the live intra rows and a keyed per-entry shuffle, no sort and no key tensor) instead of torch's generator and argsort.
 """
 import argparse
 import os
@@ -61,6 +64,7 @@ def parse():
     ap.add_argument("--slabs", type=int, default=64, help="gradient slabs: workgroups per kind that share a minibatch's tiles (1..256)")
     ap.add_argument("--episode-len", type=int, default=100)
     ap.add_argument("--se-mode", choices=("stream", "gather"), default="gather")
+    ap.add_argument("--device-order", action="store_true", help='draw the row lists on the device: ppo_update(..., order="device")')
     ap.add_argument("--bf16", action="store_true", help="run the loop a second time with bf16 nets under ppo_bind(spread=True, bf16=True)")
     return ap.parse_args()
 
@@ -95,7 +99,7 @@ def run(args, bf16):
         torch.cuda.synchronize()
         t_collect += time.perf_counter() - tc
         out = env.ppo_update(rec, epochs=args.epochs, minibatch=args.minibatch, lr=LR, clip=CLIP, vf_coeff=VF_COEFF, ent_coeff=ENT_COEFF,
-                             grad_clip=GRAD_CLIP, seed=it)
+                             grad_clip=GRAD_CLIP, seed=it, order="device" if args.device_order else None)
         r = rec["reward"][..., 0].mean().item()
         last = args.epochs - 1
         stats.append((out["policy_loss"][0, 0, last], out["value_loss"][0, 0, last], out["kl"][0, 0, last]))

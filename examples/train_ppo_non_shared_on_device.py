@@ -1,7 +1,7 @@
 """The reference's non-shared IBSched training entry in miniature with BOTH halves on the device: `collect()` records the batch and
 `ppo_update_per_slice()` trains the 1 + S policies in one launch -- nothing leaves the device between a `collect()` and the next.
 
-    python examples/train_ppo_non_shared_on_device.py [--batch 64] [--ttis 32] [--iters 5] [--epochs 10] [--minibatch 64] [--width 64]
+    python examples/train_ppo_non_shared_on_device.py [--batch 64] [--ttis 32] [--iters 5] [--epochs 10] [--minibatch 64] [--width 64] [--device-order]
 
 The reference's `scratch_ray_ib_sched_non_shared` agent (simu.py: "train": True, "shared_policies": False) trains one RLlib PPO policy
 for the inter-slice agent and one per slice for the intra-slice agents (agents/ray_agent.py:420-460), each a FullyConnectedNetwork
@@ -48,6 +48,7 @@ def main():
     ap.add_argument("--minibatch", type=int, default=64)
     ap.add_argument("--width", type=int, default=64)
     ap.add_argument("--episode-len", type=int, default=100)
+    ap.add_argument("--device-order", action="store_true", help='draw the row lists on the device: ppo_update_per_slice(..., order="device")')
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     B, T, L = args.batch, args.ttis, args.episode_len
@@ -72,7 +73,7 @@ def main():
     t0 = time.perf_counter()
     for it in range(args.iters):
         rec = env.collect(T, gamma=GAMMA, lam=LAMBDA)
-        st = env.ppo_update_per_slice(rec, epochs=args.epochs, minibatch=args.minibatch, seed=it, **HP)
+        st = env.ppo_update_per_slice(rec, epochs=args.epochs, minibatch=args.minibatch, seed=it, order="device" if args.device_order else None, **HP)
         r = rec["reward"][..., 0].mean().item()
         rows = st["rows"][:, 0].astype(int).tolist()
         print(f"iteration {it + 1:3d}: mean inter-slice reward {r:+.4f}; rows per policy {rows}; last epoch's policy loss "

@@ -1,6 +1,6 @@
 """Train the reference's SB3 PPO("MlpPolicy") agents with collection AND the SGD on the device: the host touches it once per batch.
 
-    python examples/train_sb3_ppo_on_device.py --agent twc|colran|ibsched [--batch 64] [--episode-len 32] [--iters 5] [--out policy.pt]
+    python examples/train_sb3_ppo_on_device.py --agent twc|colran|ibsched [--batch 64] [--episode-len 32] [--iters 5] [--out policy.pt] [--device-order]
     python examples/train_sb3_ppo_on_device.py --agent twc --spread 64 --batch 4096 --episode-len 64 --epochs 4 --minibatch 8192
 
 --agent twc / colran: SchedTWC / SchedColORAN on the head observation (agents/sched_twc.py:111-118, agents/sched_colran.py), scenario
@@ -54,6 +54,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--spread", type=int, nargs="?", const=64, default=None, metavar="SLABS",
                     help="the spread head binding: every optimiser step over up to SLABS (1..256, default 64) workgroups")
+    ap.add_argument("--device-order", action="store_true", help='draw the row lists on the device: ppo_update_head(..., order="device")')
     ap.add_argument("--out", default="sb3_ppo_policy.pt")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -85,7 +86,7 @@ def main():
     for it in range(args.iters):
         env.enable_metrics(2)                      # (zeroes the sums: every iteration plays one whole episode per env)
         rec = env.collect_head(L, reward=reward)
-        st = env.ppo_update_head(rec, epochs=args.epochs, minibatch=args.minibatch, seed=args.seed + it)
+        st = env.ppo_update_head(rec, epochs=args.epochs, minibatch=args.minibatch, seed=args.seed + it, order="device" if args.device_order else None)
         if inter:
             ep = env.episode_metrics()["episode_log"][:, 0, 1]
         else:

@@ -743,7 +743,7 @@ int ranenv_gae(ranenv_handle h, int32_t n_steps, int32_t n_cols, const double *d
  *     n_members: the population's member count, 1 without population nets.  host_hparams [n_members], copied at the call.
  *     dev_order_inter / _intra: int32 [max_epochs][N_kind] record rows, max_epochs = the largest epochs, N_kind = host_first_kind[n_members];
  *       member m's rows of epoch k are entries [host_first[m], host_first[m + 1]) of row k (host arrays [n_members + 1] from 0, non-decreasing).  The caller
- *       supplies the shuffles; intra lists hold rows with mask_inter != 0 only.  Minibatches are consecutive chunks of `minibatch`
+ *       supplies the shuffles (its own, or ranenv_ppo_row_order's: "Row lists on the device" below); intra lists hold rows with mask_inter != 0 only.  Minibatches are consecutive chunks of `minibatch`
  *       entries, a short last chunk is a minibatch of its own.  An entry outside the record counts as a row of the minibatch and
  *       contributes nothing: the row weight stays 1 / (entries of the minibatch), and [6] counts the live rows.  Under adv_norm 1 such
  *       an entry counts as an advantage of 0 in the minibatch's mean and std.  dev_order_intra NULL: the inter kind alone is updated.
@@ -784,6 +784,49 @@ int ranenv_ppo_update(ranenv_handle h, int32_t n_steps, const ranenv_trajectory 
 int ranenv_ppo_layout(ranenv_handle h, int64_t *grad_floats, int64_t *lds_bytes);
 int ranenv_ppo_state(ranenv_handle h, int32_t role, int32_t member, float **dev_m, float **dev_v, int32_t **dev_t, int64_t *floats);
 int ranenv_ppo_probe_logp(ranenv_handle h, float *dev_logp);
+/* Row lists on the device (ranenv_ppo_row_count / ranenv_ppo_row_order): the dev_order_* / host_first_* arguments of ranenv_ppo_update,
+ * ranenv_ppo_update_slices and ranenv_ppo_update_head as a pure function of (mask, grouping, seed, epoch), computed by the library's own
+ * kernels -- a caller that binds to this header alone can train.  Nothing is sorted and no key array exists; numpy twin:
+ * adapters.ppo_row_permutation / adapters.ppo_row_order_reference.
+ *   Grouping.  RANENV_PPO_ROWS_MEMBERS: the units are the handle's population members (one unit without a population).
+ *     RANENV_PPO_ROWS_SLICES: the units are the S slices; only a handle with one member may use it.
+ *   Base lists, per kind:
+ *     inter (kind 0), unit m: the rows t * B + b for first_env[m] <= b < first_env[m + 1], ascending; the j-th is
+ *       (j / Bm) * B + first_env[m] + j % Bm, Bm the member's envs.  No memory is read for it.
+ *     intra (kind 1): the cells (t * B + b) * S + s with mask_inter[t][b][s] != 0, ascending within the unit -- the member of b under
+ *       MEMBERS, s under SLICES.  Under SLICES the inter kind has one unit.
+ *     first_kind[u] is the prefix sum of the units' counts: the table ranenv_ppo_update / _update_slices take.
+ *   The list.  order_kind[k][first[u] + i] = base_u[ P(n_u, seed, k, u, kind)(i) ] for epoch k and 0 <= i < n_u.
+ *   P is a keyed bijection of [0, n), computed per element:
+ *     n == 1: the identity.  Otherwise h = max(1, ceil(bit_length(n - 1) / 2)) and mask = 2^h - 1; the domain is 2^(2h), less than 4n.
+ *     Keys key[4 j + w], j = 0, 1 and w = 0..3: word w of Philox-4x32-10 at counter (c0 = k, c1 = u, c2 = kind, c3 = 0x53485546 + j)
+ *       under the key (k0 = seed's low word, k1 = seed's high word).  The tag spells "SHUF"; the words in the order
+ *       adapters.philox4x32_10 returns them.
+ *     One pass over x: split L = x >> h, R = x & mask; eight rounds r = 0..7 of
+ *       (L, R) <- (R, L ^ (fmix32((R + key[r]) mod 2^32) & mask)); recombine x = (L << h) | R.
+ *       fmix32 is murmur3's finaliser: x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16, all mod 2^32.
+ *     The pass is repeated while x >= n (cycle walking).  The walk terminates because the pass is a bijection of the domain; a pass
+ *       leaves the domain's excess with probability below 3/4.
+ *   The record is limited to n_steps * B * S <= 2^31 - 1 cells (else RANENV_E_INVALID); under that limit h <= 16 and x fits 32 bits.
+ * ranenv_ppo_row_count counts and compacts: it fills the two host tables, units + 1 entries each (the inter table is arithmetic), and
+ *   keeps the compacted base list in a buffer of the handle -- allocated when first needed, grown when a larger record comes, never
+ *   inside ranenv_ppo_row_order.  It waits on `stream` once, for the counts: the caller needs them to size its lists.
+ *   dev_mask_inter [n_steps][B][S] as ranenv_collect recorded it; NULL: the inter kind alone (host_first_intra may then be NULL) --
+ *   what the head agents use, whose list is the one-member inter list.
+ * ranenv_ppo_row_order fills the caller's lists, int32 [epochs][N_kind] with N_kind = first_kind[units].  It must follow a
+ *   ranenv_ppo_row_count of the same n_steps, mask pointer and grouping under the same population (else RANENV_E_STATE; so is an
+ *   intra list asked for after a count without a mask).  dev_order_intra NULL: the inter lists alone.  Enqueued on `stream`; waits for
+ *   nothing.  The mask is not read again: the lists are those of the mask as the count found it.
+ *   Refusals, all before any device call: n_steps < 1, epochs < 1, an unknown grouping, SLICES on a population of more than one
+ *   member, a record beyond the int32 limit: RANENV_E_INVALID.  A unit with no live rows has an empty range and no entries.
+ *   Four kernels (count, scan, compact, shuffle) without atomics, barriers across workgroups or flags: what a launch writes, only later
+ *   launches read, so the same call gives the same bytes. */
+#define RANENV_PPO_ROWS_MEMBERS 0
+#define RANENV_PPO_ROWS_SLICES  1
+int ranenv_ppo_row_count(ranenv_handle h, int32_t n_steps, const int8_t *dev_mask_inter, int32_t grouping,
+                         int32_t *host_first_inter, int32_t *host_first_intra, void *stream);
+int ranenv_ppo_row_order(ranenv_handle h, int32_t n_steps, const int8_t *dev_mask_inter, int32_t grouping, int32_t epochs, uint64_t seed,
+                         int32_t *dev_order_inter, int32_t *dev_order_intra, void *stream);
 /* Mixed populations (ranenv_set_population_policy_mixed / _value_mixed: members that differ in hidden widths, depth and activation)
  * are trained through an entry of their own, as they are bound through one: ranenv_ppo_bind stays RANENV_E_STATE for them.
  * ranenv_ppo_bind_mixed: ranenv_ppo_bind for a population in which at least one bound role is mixed (none: RANENV_E_STATE).  The other

@@ -94,6 +94,7 @@ class PpoHparams(C.Structure):
         (n, C.c_int32) for n in ("minibatch", "epochs", "adv_norm", "reserved")]
 
 
+PPO_ROWS_MEMBERS, PPO_ROWS_SLICES = 0, 1      # ranenv_ppo_row_count / _row_order: the grouping
 PPO_STATS = ("policy_loss", "value_loss", "entropy", "kl", "clip_frac", "grad_norm", "rows", "minibatches")
 SAC_STATS = ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef", "logp_mean", "q1_mean", "q2_mean", "target_mean")
 SAC_NETS = {"actor": 0, "q1": 1, "q2": 2, "q1_target": 3, "q2_target": 4}
@@ -230,6 +231,8 @@ FUNCTIONS = {
     "ranenv_ppo_layout": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ranenv_ppo_state": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "ranenv_ppo_probe_logp": (C.c_int, [_P, _P]),
+    "ranenv_ppo_row_count": (C.c_int, [_P, _I32, _P, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "ranenv_ppo_row_order": (C.c_int, [_P, _I32, _P, _I32, _I32, C.c_uint64, _P, _P, _P]),
     "ranenv_get_net_weights": (C.c_int, [_P, _I32, _I32, C.POINTER(Mlp), _P]),
     "ranenv_ppo_bind_mixed": (C.c_int, [_P, _P]),
     "ranenv_ppo_member_layout": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -549,6 +549,110 @@ def ppo_row_order(rec, first_env, epochs: int, seed: int = 0, intra: bool = True
     return out
 
 
+ROWS_TAG = 0x53485546            # "SHUF": counter word c3 of the row lists' Philox keys, + block (include/ranenv.h "Row lists on the device")
+PPO_ROWS_MEMBERS, PPO_ROWS_SLICES = 0, 1
+
+
+PPO_ROW_SLIPS = ("no_cycle_walk", "no_unit", "no_epoch", "member_shift", "slice_div", "keep_masked")
+
+
+def ppo_row_permutation(n: int, seed: int, epoch: int, unit: int, kind: int, slip: Optional[str] = None) -> np.ndarray:
+    """THE NORMATIVE STATEMENT of the device row lists' shuffle (ranenv_ppo_row_order, include/ranenv.h "Row lists on the device"):
+    the keyed bijection P of ``[0, n)`` for (``seed``, ``epoch``, ``unit``, ``kind`` 0 inter / 1 intra) as int64 [n], numpy,
+    vectorised over the positions.  An eight-round Feistel network on the 2h-bit domain that covers n (h = max(1,
+    ceil(bit_length(n - 1) / 2))), round function murmur3's finaliser of (R + key[r]), keys the eight words of two Philox-4x32-10
+    blocks at counter (epoch, unit, kind, "SHUF" + block) under the seed's two words; a position that leaves ``[0, n)`` takes the
+    pass again (cycle walking).  Nothing is sorted, and entry i needs nothing but i.  ``slip``: a planted mistake for the tests
+    ("no_cycle_walk": one pass, values clamped into the range; "no_unit" / "no_epoch": that word left out of the counter)."""
+    n = int(n)
+    if slip == "no_unit":
+        unit = 0
+    if slip == "no_epoch":
+        epoch = 0
+    if n < 1:
+        return np.zeros(0, dtype=np.int64)
+    if n == 1:
+        return np.zeros(1, dtype=np.int64)
+    h = max(1, -(-int(n - 1).bit_length() // 2))
+    m32, mask, hh = np.uint64(0xFFFFFFFF), np.uint64((1 << h) - 1), np.uint64(h)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    keys = []
+    for j in range(2):
+        keys += [np.uint64(int(w)) for w in philox4x32_10(int(epoch), int(unit), int(kind), ROWS_TAG + j, seed & 0xFFFFFFFF, seed >> 32)]
+
+    def one_pass(x):
+        left, right = x >> hh, x & mask
+        for r in range(8):
+            f = (right + keys[r]) & m32
+            f ^= f >> np.uint64(16)
+            f = (f * np.uint64(0x85EBCA6B)) & m32
+            f ^= f >> np.uint64(13)
+            f = (f * np.uint64(0xC2B2AE35)) & m32
+            f ^= f >> np.uint64(16)
+            left, right = right, left ^ (f & mask)
+        return (left << hh) | right
+
+    x = one_pass(np.arange(n, dtype=np.uint64))
+    if slip == "no_cycle_walk":
+        return np.minimum(x, np.uint64(n - 1)).astype(np.int64)
+    while True:
+        out = np.nonzero(x >= np.uint64(n))[0]
+        if out.size == 0:
+            return x.astype(np.int64)
+        x[out] = one_pass(x[out])
+
+
+def ppo_row_order_reference(mask_inter, first_env, epochs: int, seed: int, intra: bool = True, per_slice: bool = False,
+                            slip: Optional[str] = None) -> Dict[str, object]:
+    """The numpy twin of ``BatchedRanEnv.ppo_row_order`` (ranenv_ppo_row_count + ranenv_ppo_row_order): ``adapters.ppo_row_order``'s
+    dict as numpy arrays -- ``order_<kind>`` int32 [epochs, N_kind], ``first_<kind>`` int32 [units + 1] -- for the record's
+    ``mask_inter`` [T, B, S] (with ``intra=False`` a ``(T, B, S)`` shape will do: no mask is read).  Unit u's base list is its inter
+    rows ``t * B + b`` or its live intra cells ``(t * B + b) * S + s`` in ascending order -- the units are the members of
+    ``first_env``, or with ``per_slice=True`` (one member only) the one inter agent and the S slices -- and epoch k's entries
+    ``first[u] + i`` are ``base_u[ppo_row_permutation(n_u, seed, k, u, kind)[i]]``.  ``slip``: one of ``PPO_ROW_SLIPS``, a planted
+    mistake for the tests (the permutation's three; "member_shift": the members' inner boundaries one env late; "slice_div": the
+    slices' grouping by ``cell // S % S``; "keep_masked": a compaction that keeps every cell)."""
+    if isinstance(mask_inter, tuple):
+        if intra:
+            raise ValueError("the intra lists read mask_inter: a shape alone gives the inter lists")
+        (T, B, S), mask = (int(x) for x in mask_inter), None
+    else:
+        mask = mask_inter.detach().cpu().numpy() if isinstance(mask_inter, torch.Tensor) else np.asarray(mask_inter)
+        T, B, S = mask.shape
+    if T * B * S > 2 ** 31 - 1:
+        raise ValueError("the record is limited to T * B * S <= 2^31 - 1 cells")
+    first = np.asarray(first_env, dtype=np.int64)
+    G = len(first) - 1
+    if first[0] != 0 or first[-1] != B or np.any(np.diff(first) <= 0):
+        raise ValueError(f"first_env runs from 0 to {B} strictly increasing")
+    if per_slice and G != 1:
+        raise ValueError("per_slice=True takes one member: there is no population of non-shared agents")
+    epochs = int(epochs)
+    if slip is not None and slip not in PPO_ROW_SLIPS:
+        raise ValueError(f"slip: one of {PPO_ROW_SLIPS}")
+    if slip == "member_shift":
+        first = np.concatenate([first[:1], np.minimum(first[1:-1] + 1, B), first[-1:]])
+
+    def lists(bases, kind):
+        counts = [len(b) for b in bases]
+        firsts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        order = np.zeros((epochs, int(firsts[-1])), dtype=np.int32)
+        for u, base in enumerate(bases):
+            for k in range(epochs):
+                if len(base):
+                    order[k, firsts[u]:firsts[u + 1]] = base[ppo_row_permutation(len(base), seed, k, u, kind, slip)]
+        return order, firsts
+
+    t_rows = np.arange(T, dtype=np.int64)[:, None] * B
+    out = {"order_intra": None, "first_intra": None}
+    out["order_inter"], out["first_inter"] = lists([(t_rows + np.arange(first[m], first[m + 1])[None, :]).reshape(-1) for m in range(G)], 0)
+    if intra:
+        cells = np.arange(T * B * S, dtype=np.int64) if slip == "keep_masked" else np.nonzero(mask.reshape(-1) != 0)[0].astype(np.int64)
+        unit = ((cells // S) % S if slip == "slice_div" else cells % S) if per_slice else np.searchsorted(first, (cells // S) % B, side="right") - 1
+        out["order_intra"], out["first_intra"] = lists([cells[unit == u] for u in range(S if per_slice else G)], 1)
+    return out
+
+
 def ppo_rows(rec, kind: str, rows, layout: str = "obs", dtype=torch.float64) -> Dict[str, torch.Tensor]:
     """The record rows ``rows`` (``ppo_row_order``'s numbering) of ``kind`` "inter" / "intra" as the update reads them: the net input
     "x", the recorded action ("action" [n, S] with the sorted mask "active", or "choice" [n]) and "logp", "adv", "vtarg" of the row's column."""

@@ -1079,7 +1079,8 @@ class BatchedRanEnv:
         in place, so the next ``collect()`` acts on the new weights.  Every hyper-parameter is a scalar or a sequence with one value
         per member of the population (``betas``: one pair for all); ``grad_clip`` <= 0 or None: no clipping; ``adv_norm``:
         "minibatch" (SB3's per-minibatch standardisation) or None (as given: standardise the record's ``adv`` yourself, as RLlib does).
-        ``order``: the shuffles as ``adapters.ppo_row_order`` returns them (default: drawn from ``seed``); without "order_intra" only the
+        ``order``: the shuffles as ``adapters.ppo_row_order`` returns them (default: drawn from ``seed``), or "device": drawn from ``seed``
+        by ``self.ppo_row_order``, the library's own kernels (other lists than the default's); without "order_intra" only the
         inter nets are trained.  Returns {name: float64 array [G, 2, max epochs]} for the names of ``_lib.PPO_STATS`` (kind 0 inter, 1
         intra); ``grad=True`` adds "grad" [G, 2, floats], the last minibatch's unclipped packed gradient (actor, then critic), and
         ``probe_logp=True`` "logp" [T, B, S + 1], the log-probabilities the update re-evaluated.  A member works on ONE compute unit: more
@@ -1089,6 +1090,8 @@ class BatchedRanEnv:
         G = self._ppo_members()
         hp, epochs, minibatch = ppo_hparams(G, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, grad_clip, adv_norm, betas, eps)
         max_epochs = int(epochs.max())
+        if self._device_order(order):
+            order = self.ppo_row_order(rec, max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec)
         if order is None:
             from .adapters import ppo_row_order
             first_env = self._population if G > 1 else [0, self.B]
@@ -1104,6 +1107,51 @@ class BatchedRanEnv:
         """The row lists of the kinds in ``firsts`` as the C call takes them: a list without rows still is a list, not NULL."""
         none = torch.zeros(1, dtype=torch.int32, device=self.device)
         return {k: order["order_" + k] if order["order_" + k].numel() else none for k in firsts}
+
+    def ppo_row_order(self, rec, epochs: int, seed: int = 0, intra: bool = True, per_slice: bool = False) -> Dict[str, object]:
+        """``adapters.ppo_row_order``'s dict for the ``collect()`` record ``rec``, drawn by the library's own kernels
+        (ranenv_ppo_row_count + ranenv_ppo_row_order, include/ranenv.h "Row lists on the device"): ``order_<kind>`` int32 device tensors
+        [epochs, N_kind] and ``first_<kind>`` int32 numpy arrays ("intra": None with ``intra=False``).  The units are the handle's
+        population members, or with ``per_slice=True`` (one member only) the one inter agent and the S slices.  A pure function of
+        (``rec["mask_inter"]``, grouping, ``seed``, epoch) -- ``adapters.ppo_row_order_reference`` gives the same bytes in numpy, whatever
+        the torch build -- and NOT the lists ``adapters.ppo_row_order`` draws from the same seed.  Nothing is sorted; the call waits for
+        the device once, for the counts that size the lists."""
+        T, B, S = (int(rec["mask_inter"].shape[0]) if "mask_inter" in rec else int(rec["logp"].shape[0])), self.B, self.S
+        mask = self._dev(rec["mask_inter"], torch.int8, (T, B, S), "mask_inter") if intra else None
+        grouping = _lib.PPO_ROWS_SLICES if per_slice else _lib.PPO_ROWS_MEMBERS
+        epochs = int(epochs)
+        fi, fa, n = (C.c_int32 * (_lib.POPULATION_MAX + 1))(), (C.c_int32 * (_lib.POPULATION_MAX + 1))(), C.c_int32()
+        with torch.cuda.device(self.device):
+            self._check(self._lib.ranenv_get_population(self._h, C.byref(n), None), "ranenv_get_population")
+            units = {"inter": 1 if per_slice else max(n.value, 1), "intra": S if per_slice else max(n.value, 1)}
+            self._check(self._lib.ranenv_ppo_row_count(self._h, T, _ptr(mask), grouping, fi, fa if intra else None, self._stream()), "ranenv_ppo_row_count")
+            out = {"order_intra": None, "first_intra": None, "first_inter": np.array(fi[:units["inter"] + 1], dtype=np.int32)}
+            out["order_inter"] = torch.empty((max(epochs, 0), int(out["first_inter"][-1])), dtype=torch.int32, device=self.device)
+            if intra:
+                out["first_intra"] = np.array(fa[:units["intra"] + 1], dtype=np.int32)
+                out["order_intra"] = torch.empty((max(epochs, 0), int(out["first_intra"][-1])), dtype=torch.int32, device=self.device)
+            lists = [_ptr(o) if o is not None and o.numel() else None for o in (out["order_inter"], out["order_intra"])]
+            self._check(self._lib.ranenv_ppo_row_order(self._h, T, _ptr(mask), grouping, epochs, int(seed) & 0xFFFFFFFFFFFFFFFF, lists[0], lists[1],
+                                                       self._stream()), "ranenv_ppo_row_order")
+        return out
+
+    def ppo_head_row_order(self, rec, epochs: int, seed: int = 0) -> torch.Tensor:
+        """The row lists of ``ppo_update_head`` for a ``collect_head()`` record, drawn by the library's own kernels: int32
+        [epochs, T * B], per epoch a permutation of the record rows ``t * B + b``.  This is the one-member inter list of
+        ``ppo_row_order`` -- equal to ``ppo_row_order(...)["order_inter"]`` for the same seed and record length -- so a handle with a
+        population of more than one member is refused.  Not the lists ``adapters.ppo_head_row_order`` draws from the same seed."""
+        if getattr(self, "_population", None) is not None and len(self._population) > 2:
+            raise RanEnvError("ppo_head_row_order: the head agents' list is the one-member inter list; this handle has a population")
+        return self.ppo_row_order(rec, epochs, seed, intra=False)["order_inter"]
+
+    @staticmethod
+    def _device_order(order) -> bool:
+        """``order="device"`` of the three ``ppo_update*``: the lists come from this handle's ``ppo_row_order`` / ``ppo_head_row_order``."""
+        if isinstance(order, str):
+            if order != "device":
+                raise ValueError(f'order is a dict / tensor of row lists, None (drawn in torch from seed) or "device", not {order!r}')
+            return True
+        return False
 
     def _ppo_grad_floats(self) -> int:
         gf = C.c_int64()
@@ -1146,7 +1194,8 @@ class BatchedRanEnv:
         (ranenv_ppo_update_slices, under ``ppo_bind(per_slice=True)``): the inter pair, and slice s's actor / critic pair on the live
         rows of slice s alone, each with its own Adam state, written in place -- the next ``collect()`` acts on the trained nets.  The
         hyper-parameters are scalars, one set for all 1 + S policies as RLlib's one config; their meaning is ``ppo_update``'s.
-        ``order``: as ``adapters.ppo_row_order(..., per_slice=True)`` returns it (default: drawn from ``seed``) -- "first_intra" is
+        ``order``: as ``adapters.ppo_row_order(..., per_slice=True)`` returns it (default: drawn from ``seed``; "device": drawn from
+        ``seed`` by ``self.ppo_row_order(..., per_slice=True)``) -- "first_intra" is
         [S + 1], slice s's share of every epoch's row of "order_intra"; without "order_intra" only the inter pair trains.  Returns
         {name: float64 [1 + S, epochs]} for ``_lib.PPO_STATS``: row 0 the inter pair, row 1 + s slice s (a slice without rows: zeros);
         ``grad=True`` adds "grad" [1 + S, floats] and ``probe_logp=True`` "logp" [T, B, S + 1], as ``ppo_update`` does.
@@ -1159,6 +1208,8 @@ class BatchedRanEnv:
                 raise ValueError(f"{name}: ppo_update_per_slice takes one value for all policies")
         hp, epochs, minibatch = ppo_hparams(1, epochs, minibatch, lr, clip, vf_coeff, ent_coeff, grad_clip, adv_norm, betas, eps)
         max_epochs, S = int(epochs[0]), self.S
+        if self._device_order(order):
+            order = self.ppo_row_order(rec, max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec, per_slice=True)
         if order is None:
             from .adapters import ppo_row_order
             order = ppo_row_order(rec, [0, self.B], max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec, per_slice=True)
@@ -1314,7 +1365,7 @@ class BatchedRanEnv:
         """Train the head actor, the head critic and ``log_std`` on the ``collect_head()`` record ``rec`` in one launch of one workgroup
         (ranenv_ppo_update_head): SB3's ``PPO.train`` with ``clip_range_vf=None`` -- the defaults are SB3's -- written in place, so the
         next ``collect_head()`` acts on the trained policy.  ``order``: int32 [>= epochs, n_rows] record rows ``t * B + b`` (default:
-        ``adapters.ppo_head_row_order(rec, epochs, seed)``).  ``adv_norm``: "minibatch" or None; ``grad_clip`` <= 0 or None: no clipping.
+        ``adapters.ppo_head_row_order(rec, epochs, seed)``; "device": ``self.ppo_head_row_order(rec, epochs, seed)``).  ``adv_norm``: "minibatch" or None; ``grad_clip`` <= 0 or None: no clipping.
         Returns {name: float64 array [max epochs]} for the names of ``_lib.PPO_STATS``; ``grad=True`` adds "grad" [actor floats + critic
         floats + S], the last minibatch's unclipped gradient: actor packed, critic packed, ``log_std``.  More than ``PPO_ROW_EPOCHS_CAP``
         rows x epochs or ``PPO_STEPS_CAP`` optimiser steps is refused unless ``force``: one compute unit works through them.  Under
@@ -1323,6 +1374,8 @@ class BatchedRanEnv:
         if adv_norm not in ("minibatch", "none", None):
             raise ValueError('adv_norm is "minibatch" or None')
         epochs, minibatch = int(epochs), int(minibatch)
+        if self._device_order(order):
+            order = self.ppo_head_row_order(rec, max(epochs, 1), seed)
         if order is None:
             from .adapters import ppo_head_row_order
             order = ppo_head_row_order(rec, max(epochs, 1), seed)

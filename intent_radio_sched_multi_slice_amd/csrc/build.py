@@ -1,6 +1,6 @@
 """Build libranenv_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
-Nine objects, compiled in parallel, then linked:
+Ten objects, compiled in parallel, then linked:
   ranenv_step.hip x 3   the builds of the step kernel for row widths NP = 8, 10, 16 (-DRANENV_NP=...)
   ranenv_aux.hip        the small kernels (class sort, sidecars, re-tiling, ingest, heads, episode advance, traffic examination,
                         bf16 weight packing)
@@ -18,6 +18,8 @@ Nine objects, compiled in parallel, then linked:
                         its dZ' walk, Adam's constants and element step, the steps of a PPO minibatch (advantage mean and std,
                         row list, clipped surrogate, critic row, joint norm and clip, statistics), the 32-row tile of the IBSched
                         nets and of the head pair, and the elementwise reduce and apply of the spread updates
+  ranenv_rows.hip       the PPO row lists (ranenv_ppo_row_count / ranenv_ppo_row_order: count, scan and compact the live intra cells
+                        of a record by member or by slice, and a keyed per-entry shuffle of every unit's rows per epoch; no atomics)
   ranenv_host.cpp       the host side of the C ABI
 
     python -m intent_radio_sched_multi_slice_amd.csrc.build [--force] [-o other.so] [-DFLAG ...]    # extra -D flags: diagnostic variants
@@ -35,14 +37,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 HDR = os.path.join(REPO, "include", "ranenv.h")
 OUT = os.path.join(HERE, "libranenv_hip.so")
-SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_parts.hpp", "ranenv_ppo_spread.hip", "ranenv_sac.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
+SOURCES = ("ranenv_step.hip", "ranenv_aux.hip", "ranenv_policy.hip", "ranenv_ppo.hip", "ranenv_ppo_parts.hpp", "ranenv_ppo_spread.hip", "ranenv_sac.hip", "ranenv_rows.hip", "ranenv_host.cpp", "ranenv_step_body.hpp", "ranenv_numeric.hpp", "ranenv_net.hpp", "ranenv_internal.h")
 # (object name, source, extra flags)
 UNITS = (("step_np10", "ranenv_step.hip", ("-DRANENV_NP=10",)), ("step_np8", "ranenv_step.hip", ("-DRANENV_NP=8",)),
          ("step_np16", "ranenv_step.hip", ("-DRANENV_NP=16",)), ("aux", "ranenv_aux.hip", ()),
          # (the policy network's MFMA accumulators in VGPRs: the library's kernels use no AGPRs, tests/test_kernel_resources.py)
          ("policy", "ranenv_policy.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")), ("ppo", "ranenv_ppo.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")),
          ("sac", "ranenv_sac.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")), ("ppo_spread", "ranenv_ppo_spread.hip", ("-mllvm", "-amdgpu-mfma-vgpr-form")),
-         ("host", "ranenv_host.cpp", ()))
+         ("rows", "ranenv_rows.hip", ()), ("host", "ranenv_host.cpp", ()))
 CFLAGS = ("-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-pass-failed",
           "-ffp-contract=off",     # numpy rounds a*b and +c separately; fma() is written out where it is exact
           "-mllvm", "-amdgpu-atomic-optimizer-strategy=None",   # the kernel's few atomic adds come from one lane each

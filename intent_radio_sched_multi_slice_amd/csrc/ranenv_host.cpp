@@ -210,6 +210,16 @@ struct ranenv {
     float *d_sac_a_opt = nullptr; long long sac_a_cap = 0;
     float *d_sac_slab = nullptr; long long sac_slab_cap = 0;
     double *d_sac_partial = nullptr; float *d_sac_ent = nullptr; int32_t *d_sac_t = nullptr; int32_t sac_t[4] = {0, 0, 0, 0};
+    // ranenv_ppo_row_count / ranenv_ppo_row_order: the last count's arguments, geometry and host tables (valid: a count succeeded and
+    // ranenv_ppo_row_order may follow it), the chunks' counts and offsets [2][chunks_cap] with the units' table [POP_MAX + 1] behind
+    // them in one array, and the compacted cells [base_cap].  The arrays grow with the record (the outgrown one is freed) and are
+    // the handle's own until ranenv_destroy
+    struct RowLists {
+        bool valid = false; int n_steps = 0, grouping = 0; const int8_t *mask = nullptr; PopMap pop{};
+        RowsGeom geom{}; int first[2][POP_MAX + 1] = {};
+        int32_t *d_chunks = nullptr; long long chunks_cap = 0;
+        int32_t *d_base = nullptr; long long base_cap = 0;
+    } rows;
     // ranenv_set_population_gae: a (gamma, lambda) pair per member for ranenv_collect's GAE pass
     bool gae_on = false; double gae_gamma[POP_MAX] = {}, gae_lambda[POP_MAX] = {};
     // The IBSched nets of a TTI's launches as they are bound (critics: a recording's), with the population map where a member's copy acts
@@ -1250,6 +1260,8 @@ int ranenv_destroy(ranenv_handle h)
     for (auto &st : h->part_stream) if (st) (void)hipStreamDestroy(st);
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
     for (void *p : h->allocs) (void)hipFree(p);
+    if (h->rows.d_chunks) (void)hipFree(h->rows.d_chunks);
+    if (h->rows.d_base) (void)hipFree(h->rows.d_base);
     if (h->h_perr) (void)hipHostFree(h->h_perr);
     delete h;
     return RANENV_OK;
@@ -4256,6 +4268,116 @@ int ranenv_gae_population(ranenv_handle h, int32_t n_steps, int32_t n_cols, cons
     for (int m = 0; m < n; m++) { g.gamma[m] = host_gamma[m]; g.lambda[m] = host_lambda[m]; }
     launch_gae_pop((hipStream_t)stream, n_steps, h->cfg.batch, n_cols, reward, n_cols, vf, done, g, adv, vtarg);
     HIP_TRY(h, hipGetLastError());
+    return RANENV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row lists on the device (include/ranenv.h)
+// ---------------------------------------------------------------------------------------------
+// What both entries refuse before any device call, and the grouping's env ranges: the population's, or {0, B}
+static int rows_check(ranenv_handle h, int32_t n_steps, int32_t grouping, PopMap &map)
+{
+    if (n_steps < 1) return fail(h, RANENV_E_INVALID, "n_steps must be >= 1");
+    if (grouping != RANENV_PPO_ROWS_MEMBERS && grouping != RANENV_PPO_ROWS_SLICES)
+        return fail(h, RANENV_E_INVALID, "grouping %d is neither RANENV_PPO_ROWS_MEMBERS nor RANENV_PPO_ROWS_SLICES", grouping);
+    if (grouping == RANENV_PPO_ROWS_SLICES && h->pop.n > 1)
+        return fail(h, RANENV_E_INVALID, "RANENV_PPO_ROWS_SLICES takes one member: the handle has a population of %d", h->pop.n);
+    if (h->cfg.n_slices > POP_MAX) return fail(h, RANENV_E_INVALID, "the row lists take at most %d slices", (int)POP_MAX);
+    if ((long long)n_steps * h->cfg.batch * h->cfg.n_slices > 2147483647LL)
+        return fail(h, RANENV_E_INVALID, "a record of %d x %d x %d cells is beyond the row lists' int32 limit (2^31 - 1)", n_steps, h->cfg.batch, h->cfg.n_slices);
+    map = PopMap{};
+    if (grouping == RANENV_PPO_ROWS_MEMBERS && h->pop.n > 0) map = h->pop;
+    else { map.n = 1; map.first[0] = 0; map.first[1] = h->cfg.batch; }
+    return RANENV_OK;
+}
+
+// A device array of the row lists grown to `need` elements (with `slack` on top when it has to move); the outgrown one is freed
+static int rows_grow(ranenv_handle h, int32_t **arr, long long *cap, long long need, long long slack)
+{
+    if (need <= *cap) return RANENV_OK;
+    void *ptr = nullptr;
+    const hipError_t e = hipMalloc(&ptr, sizeof(int32_t) * (size_t)(need + slack));
+    if (e != hipSuccess) return fail(h, RANENV_E_NOMEM, "row lists (%.3f GB): %s", (double)(need + slack) * sizeof(int32_t) / 1e9, hipGetErrorString(e));
+    if (*arr) (void)hipFree(*arr);      // (waits for the device: nothing enqueued still reads it)
+    *arr = (int32_t *)ptr; *cap = need + slack;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_row_count(ranenv_handle h, int32_t n_steps, const int8_t *dev_mask_inter, int32_t grouping, int32_t *host_first_inter,
+                         int32_t *host_first_intra, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    PopMap map;
+    if (const int rc = rows_check(h, n_steps, grouping, map); rc != RANENV_OK) return rc;
+    if (!host_first_inter || (dev_mask_inter && !host_first_intra)) return fail(h, RANENV_E_INVALID, "null table (host_first_intra may be NULL without a mask only)");
+    ranenv::RowLists &r = h->rows;
+    r.valid = false;
+    const int B = h->cfg.batch, S = h->cfg.n_slices;
+    const bool slices = grouping == RANENV_PPO_ROWS_SLICES;
+    // the inter kind: arithmetic
+    for (int m = 0; m <= map.n; m++) r.first[0][m] = n_steps * map.first[m];
+    // the intra kind's geometry: chunks of one unit each, unit-major
+    RowsGeom &g = r.geom;
+    g = RowsGeom{};
+    g.T = n_steps; g.B = B; g.S = S; g.grouping = grouping; g.units = slices ? S : map.n;
+    for (int m = 0; m <= map.n; m++) g.first_env[m] = map.first[m];
+    long long chunks = 0;
+    for (int u = 0; u < g.units; u++) {
+        const long long per = slices ? ((long long)n_steps * B + ROWS_CHUNK - 1) / ROWS_CHUNK
+                                     : ((long long)(map.first[u + 1] - map.first[u]) * S + ROWS_CHUNK - 1) / ROWS_CHUNK;
+        g.chunk_first[u] = (int)chunks; g.chunks_per[u] = (int)per;
+        chunks += slices ? per : per * n_steps;
+        if (chunks > 2147483647LL) return fail(h, RANENV_E_INVALID, "the record's cells make more than 2^31 - 1 chunks");
+    }
+    g.chunk_first[g.units] = g.n_chunks = (int)chunks;
+    for (int u = 0; u <= POP_MAX; u++) r.first[1][u] = 0;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t stream = (hipStream_t)stream_;
+    if (dev_mask_inter) {
+        const long long tab = POP_MAX + 1;
+        if (const int rc = rows_grow(h, &r.d_chunks, &r.chunks_cap, 2 * chunks + tab, 0); rc != RANENV_OK) return rc;
+        int32_t *counts = r.d_chunks, *offsets = r.d_chunks + chunks, *first = r.d_chunks + 2 * chunks;
+        launch_rows_count(stream, g, dev_mask_inter, counts, offsets, first);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(r.first[1], first, sizeof(int32_t) * (size_t)(g.units + 1), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipStreamSynchronize(stream));      // the one wait: the caller sizes its lists by these counts
+        const long long total = r.first[1][g.units], cells = (long long)n_steps * B * S;
+        if (total < 0 || total > cells) return fail(h, RANENV_E_HIP, "row count: %lld live cells of %lld", total, cells);
+        if (const int rc = rows_grow(h, &r.d_base, &r.base_cap, std::max(total, 1LL), std::min(cells - total, total / 4 + 1024)); rc != RANENV_OK) return rc;
+        launch_rows_compact(stream, g, dev_mask_inter, offsets, r.d_base, total);
+        HIP_TRY(h, hipGetLastError());
+        for (int u = 0; u <= g.units; u++) host_first_intra[u] = r.first[1][u];
+    }
+    for (int m = 0; m <= map.n; m++) host_first_inter[m] = r.first[0][m];
+    r.valid = true; r.n_steps = n_steps; r.grouping = grouping; r.mask = dev_mask_inter; r.pop = map;
+    return RANENV_OK;
+}
+
+int ranenv_ppo_row_order(ranenv_handle h, int32_t n_steps, const int8_t *dev_mask_inter, int32_t grouping, int32_t epochs, uint64_t seed,
+                         int32_t *dev_order_inter, int32_t *dev_order_intra, void *stream_)
+{
+    if (!h) return fail(h, RANENV_E_INVALID, "null handle");
+    PopMap map;
+    if (const int rc = rows_check(h, n_steps, grouping, map); rc != RANENV_OK) return rc;
+    if (epochs < 1) return fail(h, RANENV_E_INVALID, "epochs must be >= 1");
+    const ranenv::RowLists &r = h->rows;
+    if (!r.valid || r.n_steps != n_steps || r.mask != dev_mask_inter || r.grouping != grouping || memcmp(&map, &r.pop, sizeof(map)) != 0)
+        return fail(h, RANENV_E_STATE, "ranenv_ppo_row_order follows a ranenv_ppo_row_count of the same n_steps, mask and grouping under the same population");
+    if (dev_order_intra && !dev_mask_inter) return fail(h, RANENV_E_STATE, "the count had no mask: it gave the inter kind alone");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t stream = (hipStream_t)stream_;
+    for (int kind = 0; kind < 2; kind++) {
+        int32_t *out = kind ? dev_order_intra : dev_order_inter;
+        RowsShuffle a{};
+        a.kind = kind; a.units = kind ? r.geom.units : map.n; a.B = h->cfg.batch; a.seed = seed;
+        a.n = r.first[kind][a.units];
+        if (!out || a.n == 0) continue;
+        for (int u = 0; u <= a.units; u++) a.first[u] = r.first[kind][u];
+        for (int m = 0; m <= map.n; m++) a.first_env[m] = map.first[m];
+        a.base = kind ? r.d_base : nullptr; a.out = out;
+        launch_rows_shuffle(stream, epochs, a);
+        HIP_TRY(h, hipGetLastError());
+    }
     return RANENV_OK;
 }
 

@@ -391,6 +391,26 @@ struct PpoHeadSpreadArgs { PpoHeadArgs a; PpoHeadSpread k; };
 // The three launches of optimiser step a.k.step
 hipError_t launch_ppo_spread_head_step(hipStream_t, size_t lds, const PpoHeadSpreadArgs &);
 
+// ranenv_ppo_row_count / ranenv_ppo_row_order (ranenv_rows.hip; include/ranenv.h "Row lists on the device").  THE GEOMETRY of the
+// compaction, by value in the kernels' arguments: the record's T x B x S cells are cut into chunks of at most ROWS_CHUNK cells that lie
+// in ONE unit each, numbered unit-major -- unit u's are chunk_first[u] .. chunk_first[u + 1] - 1, in ascending order of their cells.
+// Grouping MEMBERS: unit m is the member of envs [first_env[m], first_env[m + 1]); at one TTI its cells are contiguous in [t][b][s] and
+// take chunks_per[m] chunks, TTI-major.  Grouping SLICES: unit s is slice s, its cells the record rows t * B + b at that s, ROWS_CHUNK
+// rows per chunk (first_env = {0, B}: the inter kind's one unit).
+enum { ROWS_CHUNK = 2048 };
+struct RowsGeom { int T, B, S, grouping, units, n_chunks; int chunk_first[POP_MAX + 1], chunks_per[POP_MAX], first_env[POP_MAX + 1]; };
+// One kind's lists: out[k][p] for epochs k0 <= k < k0 + (the launch's epochs) and 0 <= p < n = first[units], the kind's table;
+// first_env: the inter kind's env ranges (one per unit); base: the intra kind's compacted cells
+struct RowsShuffle {
+    int kind, units, B, k0; long long n; unsigned long long seed;
+    int first[POP_MAX + 1], first_env[POP_MAX + 1];
+    const int32_t *base; int32_t *out;
+};
+// (enqueue only; errors through hipGetLastError)  count + scan: counts / offsets [n_chunks], first [units + 1]
+void launch_rows_count(hipStream_t, const RowsGeom &, const int8_t *mask, int32_t *counts, int32_t *offsets, int32_t *first);
+void launch_rows_compact(hipStream_t, const RowsGeom &, const int8_t *mask, const int32_t *offsets, int32_t *base, long long n_base);
+void launch_rows_shuffle(hipStream_t, int epochs, const RowsShuffle &);
+
 // ranenv_sac_update (ranenv_sac.hip; include/ranenv.h "SAC update"): one gradient step is a critic pass, an apply, an actor pass and
 // a second apply.  A net of a pass: its layout (net.w unused) and the packed weights the pass reads.
 struct SacNet { PolicyNet net; const float *w; };
