@@ -995,6 +995,47 @@ int ranenv_ppo_spread_plan(int64_t n_rows, int32_t minibatch, int32_t epochs, in
  *   the SAC update, and seeding masters from float32 weights. */
 int ranenv_ppo_bind_spread_bfloat(ranenv_handle h, int32_t slabs, void *stream);
 int ranenv_ppo_spread_bfloat_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t slabs, int64_t *lds_bytes, int64_t *device_bytes);
+/* Nets per slice over the chip: "per slice" gives each of the 1 + S policies of the non-shared agent to one workgroup, and "spread"
+ * states "no nets per slice", so the non-shared agent was the one IBSched form that could not train on the batch ranenv_collect
+ * leaves.  A seventh, opt-in binding, "per slice over the chip", is the per-slice binding's geometry -- 1 + S independent policies:
+ * UNIT 0 the inter pair, unit 1 + s slice s's intra pair -- under the spread binding's schedule: three launches per optimiser step,
+ * gradient slabs, a fixed reduce order, no atomics.
+ * ranenv_ppo_bind_slices_spread: ranenv_ppo_bind_slices' rules in its words -- one inter actor and one inter critic, S intra actors
+ *   per slice, S intra critics per slice or none, no population, float32 nets, each pair within THE LDS PLAN (wide 0) or THE WIDE
+ *   PLAN (wide 1; another value: RANENV_E_INVALID).  slabs outside 1..256: RANENV_E_INVALID.  Allocates the per-slice binding's state
+ *   (moments and gradient cell per slot, slice s's at s * the slot's slice stride; 1 + S counters) and per UNIT `slabs` zeroed gradient
+ *   slabs of the pair's packed floats and, wide 1, as many shares of parked rows (ranenv_ppo_slices_spread_bytes: all of them), the
+ *   block partials, slab statistics, running sums and a t0 cell.  No update call allocates; an allocation that fails (RANENV_E_NOMEM)
+ *   leaves the earlier binding as it was.  A handle still has ONE binding of the IBSched nets: the later bind call replaces the earlier
+ *   one and restarts the optimiser.  Re-binding follows ranenv_ppo_bind_slices' rules; a re-bound net that needs more slab or parked
+ *   floats than the bind allocated leaves ranenv_ppo_update_slices RANENV_E_STATE ("bind again") until the next bind.
+ * ranenv_ppo_update_slices under this binding: arguments, validation, loss, per-row arithmetic, statistics, probe, dev_stats
+ *   [1 + S][epochs][RANENV_PPO_STATS] and dev_grad [1 + S][grad_floats] are unchanged.  The 1 + S units are independent optimisers
+ *   with steps_u = epochs x ceil(n_u / minibatch) steps each, n_u the unit's share of a list; the call enqueues three launches per
+ *   step -- blockIdx.y the unit -- until the unit with most steps is through.  A unit whose steps are used up returns at once in all
+ *   three launches, and a slice whose share is empty is not touched: weights, moments and counter keep their bytes, its dev_stats rows
+ *   are not written.  The spread binding's rule holds per unit: what a launch writes only later launches read; a unit's counter is
+ *   read once as t0, and the unit's LAST apply stores t0 + steps_u to it; no atomics, no cross-workgroup barrier, no flag.
+ *   ranenv_ppo_layout, _member_layout, _slice_state, _probe_logp and ranenv_get_slice_net_weights serve this binding as the per-slice one.
+ * THE CONTRACT:
+ *   1. Unit u's bytes -- weights, moments, counter, statistics, last gradient -- are those of ranenv_ppo_bind_spread(slabs, wide) on a
+ *      handle that holds u's nets as its one shared pair and is given u's share of the lists.
+ *   2. So the result is a function of the inputs and of min(tiles, slabs) per unit alone, and with one slab and one minibatch dev_grad
+ *      equals ranenv_ppo_bind_slices' bit for bit.
+ *   3. Still refused, each in its words: bf16 nets, a population, the head pair, a mixed population.
+ * ranenv_ppo_slices_spread_bytes: without a handle or a device call: ranenv_ppo_spread_bytes of the inter pair plus n_slices times that
+ *   of ONE intra pair (critics may be NULL).  The cost grows with S x slabs x the pair's floats: at S 10, 256 slabs and [512] x 3 nets
+ *   it is 12.7 gigabytes (13.3 under the wide plan), where [64, 64] nets at S 5 and 64 slabs take 27 megabytes -- ask before binding, and
+ *   take fewer slabs for wide nets: a slice's minibatch rarely has 256 tiles.
+ * ranenv_ppo_slices_spread_plan: host arithmetic, the function the update sizes its launches with: unit_steps [1 + S] = epochs x
+ *   ceil(n_u / minibatch) with n_0 = n_inter and n_{1 + s} = host_first_slice[s + 1] - host_first_slice[s]; unit_grid [1 + S] = the
+ *   first minibatch's workgroups, min(ceil(min(minibatch, n_u) / 32), slabs); call_steps = the largest unit_steps.  A unit with no
+ *   rows has 0 / 0.  Any output may be NULL. */
+int ranenv_ppo_bind_slices_spread(ranenv_handle h, int32_t slabs, int32_t wide, void *stream);
+int ranenv_ppo_slices_spread_bytes(const ranenv_mlp *inter_actor, const ranenv_mlp *inter_critic, const ranenv_mlp *intra_actor, const ranenv_mlp *intra_critic,
+                                   int32_t n_slices, int32_t slabs, int32_t wide, int64_t *bytes);
+int ranenv_ppo_slices_spread_plan(int32_t n_slices, int32_t n_inter, const int32_t *host_first_slice, int32_t minibatch, int32_t epochs, int32_t slabs,
+                                  int64_t *unit_steps, int32_t *unit_grid, int64_t *call_steps);
 
 /* Episode metrics on the device (what the paper's evaluation derives per TTI from the history files,
  * results/gen_results.py:874-1022, kept as running sums so that a rollout needs no per-TTI read-back).  Per env 8

@@ -243,6 +243,9 @@ FUNCTIONS = {
     "ranenv_ppo_bind_spread": (C.c_int, [_P, _I32, _I32, _P]),
     "ranenv_ppo_spread_bytes": (C.c_int, [C.POINTER(Mlp), C.POINTER(Mlp), _I32, _I32, C.POINTER(C.c_int64)]),
     "ranenv_ppo_spread_plan": (C.c_int, [C.c_int64, _I32, _I32, _I32, C.POINTER(C.c_int64), C.POINTER(_I32), C.POINTER(_I32)]),
+    "ranenv_ppo_bind_slices_spread": (C.c_int, [_P, _I32, _I32, _P]),
+    "ranenv_ppo_slices_spread_bytes": (C.c_int, [C.POINTER(Mlp), C.POINTER(Mlp), C.POINTER(Mlp), C.POINTER(Mlp), _I32, _I32, _I32, C.POINTER(C.c_int64)]),
+    "ranenv_ppo_slices_spread_plan": (C.c_int, [_I32, _I32, C.POINTER(_I32), _I32, _I32, _I32, C.POINTER(C.c_int64), C.POINTER(_I32), C.POINTER(C.c_int64)]),
     "ranenv_ppo_bind_spread_bfloat": (C.c_int, [_P, _I32, _P]),
     "ranenv_ppo_spread_bfloat_bytes": (C.c_int, [C.POINTER(Mlp), C.POINTER(Mlp), _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ranenv_ppo_update_slices": (C.c_int, [_P, _I32, C.POINTER(Trajectory), C.POINTER(PpoHparams), _P, _I32, _P, C.POINTER(C.c_int32), _P, _P, _P]),

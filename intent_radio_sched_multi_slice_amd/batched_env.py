@@ -252,6 +252,18 @@ def ppo_spread_bytes(actor_layers, critic_layers=None, slabs: int = 64, wide: bo
     return out.value
 
 
+def ppo_slices_spread_bytes(inter_actor, inter_critic, intra_actor, intra_critic, S: int, slabs: int = 64, wide: bool = False) -> int:
+    """Device bytes ``ppo_bind(per_slice=True, spread=True, slabs=slabs)`` allocates beside the moments for the non-shared agent
+    (ranenv_ppo_slices_spread_bytes): ``ppo_spread_bytes`` of the inter pair plus ``S`` times that of ONE slice's intra pair (every net
+    as ``ppo_lds_bytes`` takes it; a critic may be None).  No handle and no device is needed: ask before binding -- at S 10, 256 slabs
+    and [512] x 3 nets the answer is 12.7 gigabytes."""
+    inter, intra = _ppo_shape_pair(inter_actor, inter_critic), _ppo_shape_pair(intra_actor, intra_critic)
+    out = C.c_int64()
+    lib = _lib.load()
+    _lib.check(lib, None, lib.ranenv_ppo_slices_spread_bytes(*inter, *intra, int(S), int(slabs), 1 if wide else 0, C.byref(out)), "ranenv_ppo_slices_spread_bytes")
+    return out.value
+
+
 def ppo_spread_bf16_bytes(actor_layers, critic_layers=None, slabs: int = 64) -> Dict[str, int]:
     """What ``ppo_bind(spread=True, slabs=slabs, bf16=True)`` needs for ONE kind's actor / critic pair of bf16 nets, before anything is
     bound (ranenv_ppo_spread_bfloat_bytes): "lds" -- the bf16 LDS plan's bytes, which the bind refuses above 163 840 -- and "device",
@@ -996,7 +1008,13 @@ class BatchedRanEnv:
         optimiser step of ``ppo_update`` is spread over the chip, the 32-row tiles of a minibatch over up to ``slabs`` (1..256, default 64)
         workgroups per kind, each adding into a gradient slab of its own (``ppo_spread_bytes``); summed in a fixed order, so the
         result depends on the inputs and on min(tiles, slabs) alone.  No population, no nets per slice: it excludes ``mixed``
-        and ``per_slice``.
+        and ``per_slice`` -- unless ``slabs`` is given with the latter:
+        ``per_slice=True, spread=True, slabs=N`` (ranenv_ppo_bind_slices_spread), with or without ``wide``: the per-slice binding's 1 + S
+        policies under the spread schedule -- every optimiser step of ``ppo_update_per_slice`` is three launches in which each policy's
+        minibatch is spread over up to ``slabs`` workgroups and slabs of its own (``ppo_slices_spread_bytes`` tells the bytes: they grow
+        with S x slabs).  Policy u's bytes are those of ``ppo_bind(spread=True, slabs=N)`` on a handle that holds u's nets as its one
+        shared pair and is given u's rows.  ``slabs`` has no default in this form: ``spread`` and ``per_slice`` without it raise
+        ``ValueError``, as the two together always did before this form existed.
         ``head=True, spread=True, slabs=N`` (ranenv_ppo_bind_head_spread): the head binding's second form -- every optimiser step of
         ``ppo_update_head`` spread over up to ``slabs`` workgroups in the same three launches, ``log_std`` included
         (``ppo_head_spread_bytes``).  The later of the two head bindings replaces the earlier and restarts the head optimiser; either
@@ -1019,7 +1037,7 @@ class BatchedRanEnv:
             raise ValueError("ppo_bind: spread and mixed exclude each other (the spread binding trains one agent, no population)")
         if spread and head and wide:
             raise ValueError("ppo_bind: head, spread and wide exclude each other (the head nets train under the plain plan, spread or not)")
-        if spread and per_slice:
+        if spread and per_slice and (slabs is None or head):      # (with slabs: the per-slice binding's spread form, below)
             raise ValueError("ppo_bind: spread and per_slice exclude each other (the spread binding trains one shared intra pair)")
         if per_slice and (mixed or head):
             raise ValueError("ppo_bind: per_slice excludes mixed and head (no population of non-shared agents; the head pair has no slices)")
@@ -1037,6 +1055,8 @@ class BatchedRanEnv:
                 return                         # (beside the IBSched nets' binding: which one that is stays as it was)
             elif bf16:
                 self._check(self._lib.ranenv_ppo_bind_spread_bfloat(self._h, int(slabs), self._stream()), "ranenv_ppo_bind_spread_bfloat")
+            elif spread and per_slice:
+                self._check(self._lib.ranenv_ppo_bind_slices_spread(self._h, int(slabs), 1 if wide else 0, self._stream()), "ranenv_ppo_bind_slices_spread")
             elif spread:
                 self._check(self._lib.ranenv_ppo_bind_spread(self._h, int(slabs), 1 if wide else 0, self._stream()), "ranenv_ppo_bind_spread")
             elif per_slice:
@@ -1052,6 +1072,7 @@ class BatchedRanEnv:
             else:
                 self._check(self._lib.ranenv_ppo_bind(self._h, self._stream()), "ranenv_ppo_bind")
         self._ppo_spread = bool(spread)
+        self._ppo_slices_spread = bool(spread and per_slice)
 
     def ppo_member_layout(self, m: int, kind: str = "inter") -> Dict[str, int]:
         """What unpacks member ``m``'s block of ``ppo_update(grad=True)["grad"][m, kind]`` (ranenv_ppo_member_layout): the packed
@@ -1199,7 +1220,9 @@ class BatchedRanEnv:
         [S + 1], slice s's share of every epoch's row of "order_intra"; without "order_intra" only the inter pair trains.  Returns
         {name: float64 [1 + S, epochs]} for ``_lib.PPO_STATS``: row 0 the inter pair, row 1 + s slice s (a slice without rows: zeros);
         ``grad=True`` adds "grad" [1 + S, floats] and ``probe_logp=True`` "logp" [T, B, S + 1], as ``ppo_update`` does.
-        ``PPO_ROW_EPOCHS_CAP`` and ``PPO_STEPS_CAP`` hold per policy unless ``force``."""
+        ``PPO_ROW_EPOCHS_CAP`` and ``PPO_STEPS_CAP`` hold per policy unless ``force``.  Under ``ppo_bind(per_slice=True, spread=True,
+        slabs=N)`` every optimiser step is three launches spread over the chip: the rows x epochs cap does not apply, ``PPO_STEPS_CAP``
+        does, per policy."""
         if adv_norm not in ("minibatch", "none", None):
             raise ValueError('adv_norm is "minibatch" or None')
         for name, x in (("epochs", epochs), ("minibatch", minibatch), ("lr", lr), ("clip", clip), ("vf_coeff", vf_coeff), ("ent_coeff", ent_coeff),
@@ -1213,8 +1236,8 @@ class BatchedRanEnv:
         if order is None:
             from .adapters import ppo_row_order
             order = ppo_row_order(rec, [0, self.B], max(max_epochs, 1), seed, intra=self._intra_layout is not None and "obs_intra" in rec, per_slice=True)
-        firsts = ppo_order_firsts(order, {"inter": 1, "intra": S}, epochs, minibatch, (self.PPO_ROW_EPOCHS_CAP, self.PPO_STEPS_CAP), "ppo_update_per_slice",
-                                  per_slice=True, force=force)
+        caps = (PPO_SPREAD_CAPS[0], self.PPO_STEPS_CAP) if getattr(self, "_ppo_slices_spread", False) else (self.PPO_ROW_EPOCHS_CAP, self.PPO_STEPS_CAP)
+        firsts = ppo_order_firsts(order, {"inter": 1, "intra": S}, epochs, minibatch, caps, "ppo_update_per_slice", per_slice=True, force=force)
         lists = self._ppo_lists(order, firsts)
         return self._ppo_launch("ranenv_ppo_update_slices", lambda T, traj, stats, gbuf, stream: self._lib.ranenv_ppo_update_slices(
             self._h, T, traj, hp, _ptr(lists["inter"]), int(firsts["inter"][1]), _ptr(lists.get("intra")),

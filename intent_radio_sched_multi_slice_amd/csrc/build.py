@@ -13,7 +13,9 @@ Ten objects, compiled in parallel, then linked:
   ranenv_ppo_spread.hip the PPO update of ONE agent spread over the chip (ranenv_ppo_bind_spread: per optimiser step a pass of
                         min(tiles, slabs) workgroups into gradient slabs of their own, an elementwise reduce and an elementwise apply;
                         three more kernels of the same pattern train the head policies with log_std, ranenv_ppo_bind_head_spread;
-                        a bf16 pass, a re-rounding apply and a seed kernel train RANENV_NET_BF16 nets, ranenv_ppo_bind_spread_bfloat)
+                        a bf16 pass, a re-rounding apply and a seed kernel train RANENV_NET_BF16 nets, ranenv_ppo_bind_spread_bfloat;
+                        four more instances of the pass, reduce and apply text train the 1 + S policies of nets per slice, a unit
+                        per workgroup row, ranenv_ppo_bind_slices_spread)
                         All three are built from ranenv_ppo_parts.hpp, the one statement of every step they share: the backward pass and
                         its dZ' walk, Adam's constants and element step, the steps of a PPO minibatch (advantage mean and std,
                         row list, clipped surrogate, critic row, joint norm and clip, statistics), the 32-row tile of the IBSched

@@ -155,9 +155,10 @@ struct ranenv {
     // THE PPO BINDING of the IBSched nets: what ranenv_ppo_bind (plain), _bind_mixed (mixed: a mixed population, each member on its own
     // shape), _bind_wide (wide: the wide plan, with or without mixed), _bind_slices (slices: one intra pair per slice, with or without
     // wide) or _bind_spread (slabs > 0: ONE agent, every optimiser step spread over up to `slabs` workgroups per kind, with or without
-    // wide) bound, and the geometry that follows from it, stated here alone.  A handle has one; a binding that ends is `{}` again, so
-    // no flag outlives `on`.  An update UNIT is what one optimiser trains: member m's pair of a kind, or (slices) the inter pair and
-    // slice s's intra pair; a spread binding has the one member's two.
+    // wide; slices and slabs > 0: _bind_slices_spread, the per-slice units under the spread schedule) bound, and the geometry that
+    // follows from it, stated here alone.  A handle has one; a binding that ends is `{}` again, so no flag outlives `on`.  An update
+    // UNIT is what one optimiser trains: member m's pair of a kind, or (slices) the inter pair and slice s's intra pair; a spread
+    // binding has the one member's two.
     struct PpoBinding {
         bool on = false, mixed = false, wide = false, slices = false;
         int slabs = 0;                                                                                        // > 0: the spread binding
@@ -167,7 +168,7 @@ struct ranenv {
         // unit u of `kind` by workgroup number: its step counter in d_ppo_t and (not spread) its share of the parked rows in d_ppo_park
         int wg(int kind, int u) const { return slices ? (kind ? 1 + u : 0) : u * 2 + kind; }
         // the entry point the messages name (parked: where they speak of the parked rows, which ranenv_ppo_bind_wide allocates)
-        const char *entry(bool parked = false) const { return bf16 ? "ranenv_ppo_bind_spread_bfloat" : slabs ? "ranenv_ppo_bind_spread" : (slices ? "ranenv_ppo_bind_slices" : (parked ? "ranenv_ppo_bind_wide" : "ranenv_ppo_bind")); }
+        const char *entry(bool parked = false) const { return bf16 ? "ranenv_ppo_bind_spread_bfloat" : slabs ? (slices ? "ranenv_ppo_bind_slices_spread" : "ranenv_ppo_bind_spread") : (slices ? "ranenv_ppo_bind_slices" : (parked ? "ranenv_ppo_bind_wide" : "ranenv_ppo_bind")); }
     } ppo;
     // ... its step counters by workgroup number [POP_MAX * 2], the call's hyper-parameters on the device [POP_MAX], the diagnostic
     // log-probability buffer the NEXT update takes and forgets
@@ -182,9 +183,11 @@ struct ranenv {
     // blocks' sums of squares [ppo_spread_blocks], the pass workgroups' statistics [PPO_SPREAD_SLABS_MAX][PPO_SPREAD_STATS] and the
     // epoch's running sums [RANENV_PPO_STATS] in one array of doubles; the parked rows (wide) lie in d_ppo_park, [2][slabs][the kind's
     // need].  The call's copy of the two step counters: d_ppo_t[2], [3] (a spread binding has one member: [0], [1] are its counters).
-    // All allocated at the bind, never by an update
+    // All allocated at the bind, never by an update.  ranenv_ppo_bind_slices_spread: the same arrays per UNIT (unit 0 the inter pair,
+    // unit 1 + s slice s) -- the slabs and parked rows of unit 0, then the slices' back to back; the doubles [ppo_spread_units] times
+    // one kind's; the call's copies of the 1 + S counters at d_ppo_t[POP_MAX + u]
     float *d_ppo_slab = nullptr; long long ppo_slab_cap = 0;
-    double *d_ppo_spread = nullptr; long long ppo_spread_blocks = 0;
+    double *d_ppo_spread = nullptr; long long ppo_spread_blocks = 0; int ppo_spread_units = 0;
     // ranenv_ppo_bind_spread_bfloat: per role the trained bf16 net's f32 state in the F32 packed layout -- master, m, v, g, ppo_bf_cap[r]
     // floats each -- and behind them the transposed bf16 copy, ppo_bf_cap16[r] floats (the acting copy's packed size).  Allocated at the
     // bind (an outgrown one stays allocated), seeded from the acting copy at the bind and at every re-bind of the role
@@ -2425,12 +2428,15 @@ static int ppo_rebound(ranenv_handle h, ranenv::NetSlot *slot, int member, hipSt
 // What a spread binding of these slots holds beside the moments: floats of gradient slabs and of parked rows (wide) -- per bound kind
 // `slabs` times the pair's need, the kinds back to back --, and the reduce / apply blocks of the larger kind.  The doubles of one
 // kind: block partials, slab statistics, running sums.
-struct PpoSpreadNeed { long long slab, park, blocks; };
-static PpoSpreadNeed ppo_spread_need(ranenv::NetSlot *const (&slot)[4], bool wide, int slabs, bool bf16 = false)
+// n_slices > 0 (ranenv_ppo_bind_slices_spread): the intra kind's need once per slice, and 1 + n_slices units of doubles for the two kinds'.
+struct PpoSpreadNeed { long long slab, park, blocks; int units; };
+static PpoSpreadNeed ppo_spread_need(ranenv::NetSlot *const (&slot)[4], bool wide, int slabs, bool bf16 = false, int n_slices = 0)
 {
     PpoSpreadNeed n{};
-    ppo_each_shape(slot, false, wide, 1, [&](int, int, long long floats, size_t, long long park) {
-        n.slab += floats * slabs; n.park += park * slabs;
+    n.units = n_slices > 0 ? 1 + n_slices : 2;
+    ppo_each_shape(slot, false, wide, 1, [&](int, int k, long long floats, size_t, long long park) {
+        const long long copies = (long long)slabs * (k == 1 && n_slices > 0 ? n_slices : 1);
+        n.slab += floats * copies; n.park += park * copies;
         n.blocks = std::max(n.blocks, (floats + PPO_SPREAD_BLOCK - 1) / PPO_SPREAD_BLOCK);
         return (int)RANENV_OK;
     }, bf16);
@@ -2438,7 +2444,7 @@ static PpoSpreadNeed ppo_spread_need(ranenv::NetSlot *const (&slot)[4], bool wid
 }
 static long long ppo_spread_doubles(long long blocks) { return blocks + PPO_SPREAD_SLABS_MAX * PPO_SPREAD_STATS + RANENV_PPO_STATS; }
 
-// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide / ranenv_ppo_bind_slices / ranenv_ppo_bind_spread
+// ranenv_ppo_bind / ranenv_ppo_bind_mixed / ranenv_ppo_bind_wide / ranenv_ppo_bind_slices / ranenv_ppo_bind_spread / ranenv_ppo_bind_slices_spread
 static int ppo_bind(ranenv_handle h, ranenv::PpoBinding b, void *stream)
 {
     if (!h) return fail(h, RANENV_E_INVALID, "null handle");
@@ -2448,14 +2454,16 @@ static int ppo_bind(ranenv_handle h, ranenv::PpoBinding b, void *stream)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     if (b.slabs) {      // the spread binding's own: slabs, block partials, slab statistics and running sums, and (wide) the parked rows per slab
-        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs, b.bf16);
+        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs, b.bf16, b.slices ? h->cfg.n_slices : 0);
         if (h->ppo_slab_cap < need.slab) {
             if (const int rc = dev_alloc(h, &h->d_ppo_slab, (size_t)need.slab); rc != RANENV_OK) return rc;
             h->ppo_slab_cap = need.slab;
         }
-        if (!h->d_ppo_spread || h->ppo_spread_blocks < need.blocks) {
-            if (const int rc = dev_alloc(h, &h->d_ppo_spread, 2 * (size_t)ppo_spread_doubles(need.blocks)); rc != RANENV_OK) return rc;
-            h->ppo_spread_blocks = need.blocks;
+        if (!h->d_ppo_spread || h->ppo_spread_blocks < need.blocks || h->ppo_spread_units < need.units) {      // (an outgrown one grows in both extents)
+            const long long blocks = std::max(need.blocks, h->ppo_spread_blocks);
+            const int units = std::max(need.units, h->ppo_spread_units);
+            if (const int rc = dev_alloc(h, &h->d_ppo_spread, (size_t)units * (size_t)ppo_spread_doubles(blocks)); rc != RANENV_OK) return rc;
+            h->ppo_spread_blocks = blocks; h->ppo_spread_units = units;
         }
         if (h->ppo_park_cap < need.park) {
             if (const int rc = dev_alloc(h, &h->d_ppo_park, (size_t)need.park); rc != RANENV_OK) return rc;
@@ -2519,6 +2527,13 @@ int ranenv_ppo_bind_spread(ranenv_handle h, int32_t slabs, int32_t wide, void *s
     if (wide != 0 && wide != 1) return fail(h, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
     return ppo_bind(h, {true, false, wide == 1, false, slabs}, stream);
 }
+// (nets per slice over the chip, include/ranenv.h "Nets per slice over the chip")
+int ranenv_ppo_bind_slices_spread(ranenv_handle h, int32_t slabs, int32_t wide, void *stream)
+{
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(h, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    if (wide != 0 && wide != 1) return fail(h, RANENV_E_INVALID, "wide %d (0 the LDS plan, 1 the wide plan)", wide);
+    return ppo_bind(h, {true, false, wide == 1, true, slabs}, stream);
+}
 // (bf16 nets over the chip, include/ranenv.h "bf16 nets over the chip")
 int ranenv_ppo_bind_spread_bfloat(ranenv_handle h, int32_t slabs, void *stream)
 {
@@ -2545,8 +2560,8 @@ static int ppo_bound(ranenv_handle h, bool slices, ranenv::NetSlot *(&slot)[4], 
         if (slot[r] && (b.bf16 ? !ppo_bf16_fits(h, slot[r]) : (!slot[r]->opt || slot[r]->opt_cap < slot[r]->cap)))
             return fail(h, RANENV_E_STATE, "the %s net was bound after %s: bind again", NET_ROLES[r].who, b.entry());
     if (b.slabs) {      // a spread binding: the slabs, block partials and parked rows of the nets as they stand fit what the bind allocated
-        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs, b.bf16);
-        if (need.slab > h->ppo_slab_cap || need.blocks > h->ppo_spread_blocks || need.park > h->ppo_park_cap)
+        const PpoSpreadNeed need = ppo_spread_need(slot, b.wide, b.slabs, b.bf16, b.slices ? h->cfg.n_slices : 0);
+        if (need.slab > h->ppo_slab_cap || need.blocks > h->ppo_spread_blocks || need.units > h->ppo_spread_units || need.park > h->ppo_park_cap)
             return fail(h, RANENV_E_STATE, "the bound nets need more slab or parked floats than %s allocated: bind again", b.entry());
         return RANENV_OK;
     }
@@ -2650,6 +2665,18 @@ int ranenv_ppo_spread_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, i
     return RANENV_OK;
 }
 
+int ranenv_ppo_slices_spread_bytes(const ranenv_mlp *inter_actor, const ranenv_mlp *inter_critic, const ranenv_mlp *intra_actor, const ranenv_mlp *intra_critic,
+                                   int32_t n_slices, int32_t slabs, int32_t wide, int64_t *bytes)
+{
+    if (!inter_actor || !intra_actor || !bytes) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (n_slices < 1) return fail(nullptr, RANENV_E_INVALID, "n_slices %d (>= 1)", n_slices);
+    int64_t inter = 0, intra = 0;
+    if (const int rc = ranenv_ppo_spread_bytes(inter_actor, inter_critic, slabs, wide, &inter); rc != RANENV_OK) return rc;
+    if (const int rc = ranenv_ppo_spread_bytes(intra_actor, intra_critic, slabs, wide, &intra); rc != RANENV_OK) return rc;
+    *bytes = inter + (int64_t)n_slices * intra;
+    return RANENV_OK;
+}
+
 int ranenv_ppo_spread_bfloat_bytes(const ranenv_mlp *actor, const ranenv_mlp *critic, int32_t slabs, int64_t *lds_bytes, int64_t *device_bytes)
 {
     if (!actor || (!lds_bytes && !device_bytes)) return fail(nullptr, RANENV_E_INVALID, "null argument");
@@ -2680,6 +2707,41 @@ int ranenv_ppo_spread_plan(int64_t n_rows, int32_t minibatch, int32_t epochs, in
     if (steps) *steps = (int64_t)epochs * per_epoch;
     if (grid) *grid = n > 0 ? ppo_spread_step(n, minibatch, slabs, 0).grid : 0;
     if (tiles_last) *tiles_last = n > 0 ? ppo_spread_step(n, minibatch, slabs, per_epoch - 1).tiles : 0;
+    return RANENV_OK;
+}
+
+// The units' schedule of a per-slice spread call from its tables: ppo_slices_spread_unit and ppo_spread_step, the update's own functions
+static void ppo_slices_spread_plan(const int (*first)[POP_MAX + 1], int n_units, int minibatch, int epochs, int slabs, int64_t *unit_steps, int32_t *unit_grid,
+                                   int64_t *call_steps)
+{
+    int64_t most = 0;
+    for (int u = 0; u < n_units; u++) {
+        const PpoSliceUnit x = ppo_slices_spread_unit(first, u, 1, minibatch);      // (steps of ONE epoch: the product is taken in 64 bits here)
+        const int64_t steps = (int64_t)epochs * x.steps;
+        if (unit_steps) unit_steps[u] = steps;
+        if (unit_grid) unit_grid[u] = x.n > 0 ? ppo_spread_step(x.n, minibatch, slabs, 0).grid : 0;
+        most = std::max(most, steps);
+    }
+    if (call_steps) *call_steps = most;
+}
+
+int ranenv_ppo_slices_spread_plan(int32_t n_slices, int32_t n_inter, const int32_t *host_first_slice, int32_t minibatch, int32_t epochs, int32_t slabs,
+                                  int64_t *unit_steps, int32_t *unit_grid, int64_t *call_steps)
+{
+    if (n_slices < 1 || n_slices > POP_MAX) return fail(nullptr, RANENV_E_INVALID, "n_slices %d (1..%d)", n_slices, (int)POP_MAX);
+    if (n_inter < 0) return fail(nullptr, RANENV_E_INVALID, "n_inter %d (>= 0)", n_inter);
+    if (!host_first_slice) return fail(nullptr, RANENV_E_INVALID, "null argument");
+    if (minibatch < 1) return fail(nullptr, RANENV_E_INVALID, "minibatch %d (>= 1)", minibatch);
+    if (epochs < 0) return fail(nullptr, RANENV_E_INVALID, "epochs %d (>= 0)", epochs);
+    if (slabs < 1 || slabs > PPO_SPREAD_SLABS_MAX) return fail(nullptr, RANENV_E_INVALID, "slabs %d (1..256)", slabs);
+    int first[2][POP_MAX + 1] = {};
+    first[0][1] = n_inter;
+    if (host_first_slice[0] != 0) return fail(nullptr, RANENV_E_INVALID, "host_first_slice[0] is %d, not 0", host_first_slice[0]);
+    for (int s = 0; s < n_slices; s++) {
+        if (host_first_slice[s + 1] < host_first_slice[s]) return fail(nullptr, RANENV_E_INVALID, "host_first_slice decreases at slice %d", s);
+        first[1][s + 1] = host_first_slice[s + 1];
+    }
+    ppo_slices_spread_plan(first, 1 + n_slices, minibatch, epochs, slabs, unit_steps, unit_grid, call_steps);
     return RANENV_OK;
 }
 
@@ -2748,6 +2810,47 @@ static int ppo_update_spread(ranenv_handle h, ranenv::NetSlot *const (&slot)[4],
     return RANENV_OK;
 }
 
+// ranenv_ppo_update_slices under ranenv_ppo_bind_slices_spread: `a` as the update below filled it.  Per kind the buffers of its first
+// unit and the strides between two slices', then three launches per optimiser step until the unit with most steps is through; the
+// units' rows and steps follow from a.first and hp on the device as here (ppo_slices_spread_plan).
+static int ppo_update_slices_spread(ranenv_handle h, ranenv::NetSlot *const (&slot)[4], const PpoArgs &a, const ranenv_ppo_hparams &hp, bool intra, size_t lds, hipStream_t s)
+{
+    const ranenv::PpoBinding &b = h->ppo;
+    const int S = h->cfg.n_slices;
+    PpoSpreadSlicesArgs q{};
+    PpoSpreadArgs &p = q.p;
+    p.a = a; p.a.hp = nullptr; p.hp = hp; p.slabs = b.slabs;
+    q.x.n_units = intra ? 1 + S : 1;
+    q.x.dbl_unit = ppo_spread_doubles(h->ppo_spread_blocks);
+    float *slab = h->d_ppo_slab, *park = h->d_ppo_park;
+    for (int k = 0; k < 2; k++) {
+        PpoSpreadKind &K = p.k[k];
+        const PolicyNet *critic = slot[2 + k] ? &slot[2 + k]->net : nullptr;
+        const long long floats = net_floats(slot[k]->net) + (critic ? net_floats(*critic) : 0);
+        const long long copies = (long long)b.slabs * (k ? S : 1);
+        K.slab = slab; K.slab_stride = floats; slab += floats * copies;
+        if (k) q.x.slab_unit = floats * b.slabs;
+        if (b.wide) {
+            K.park = park; K.park_stride = ppo_wide_scratch(slot[k]->net, critic); park += K.park_stride * copies;
+            if (k) q.x.park_unit = K.park_stride * b.slabs;
+        }
+        K.bpart = h->d_ppo_spread + k * q.x.dbl_unit;      // (unit 0 and unit 1: slice s's lie s x dbl_unit behind the latter)
+        K.wstat = K.bpart + h->ppo_spread_blocks; K.run = K.wstat + PPO_SPREAD_SLABS_MAX * PPO_SPREAD_STATS;
+        K.t0 = h->d_ppo_t + POP_MAX + k;
+        K.blocks = (int)((floats + PPO_SPREAD_BLOCK - 1) / PPO_SPREAD_BLOCK);
+        K.steps = k == 0 || intra ? 1 : 0;
+    }
+    int64_t unit_steps[POP_MAX + 1], steps = 0;
+    ppo_slices_spread_plan(p.a.first, q.x.n_units, hp.minibatch, hp.epochs, b.slabs, unit_steps, nullptr, &steps);
+    for (int u = 0; u < q.x.n_units; u++)
+        if (unit_steps[u] > 0x7fffffffLL) return fail(h, RANENV_E_INVALID, "%lld optimiser steps (epochs x minibatches of policy %d): more than 2^31 - 1", (long long)unit_steps[u], u);
+    for (int64_t i = 0; i < steps; i++) {
+        p.step = (int)i;
+        HIP_TRY(h, launch_ppo_spread_slices_step(s, lds, q, b.wide));
+    }
+    return RANENV_OK;
+}
+
 // THE update behind ranenv_ppo_update and ranenv_ppo_update_slices, which bring their arguments into one form: per kind the row list
 // `order[k]` (null: the kind is not trained) and `first[k]`, unit u's share [first[k][u], first[k][u + 1]) of every epoch's row of it
 // -- the units of the binding's geometry -- and `n_hp` hyper-parameter sets, one per member (slices: one for all units).
@@ -2804,6 +2907,7 @@ static int ppo_update(ranenv_handle h, bool slices, int32_t n_steps, const ranen
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
+    if (b.slabs && slices) return ppo_update_slices_spread(h, slot, a, hp[0], intra, plan.lds, s);
     if (b.slabs) return ppo_update_spread(h, slot, a, hp[0], intra, plan.lds, s);
     HIP_TRY(h, hipMemcpyAsync(h->d_ppo_hp, hp, sizeof(ranenv_ppo_hparams) * (size_t)n_hp, hipMemcpyHostToDevice, s));
     const PpoWide y{h->d_ppo_park, h->ppo_park_stride};      // (ppo_bound: every workgroup's rows fit its share)

@@ -346,6 +346,36 @@ struct PpoSpreadArgs {
 };
 // The three launches of optimiser step a.step (grid_pass / blocks: the larger kind's); wide: the pass under the wide plan
 hipError_t launch_ppo_spread_step(hipStream_t, size_t lds, const PpoSpreadArgs &, bool wide);
+// ranenv_ppo_update_slices under ranenv_ppo_bind_slices_spread (include/ranenv.h "Nets per slice over the chip"): the per-slice
+// binding's 1 + S policies under the same three launches, blockIdx.y the UNIT u -- unit 0 the inter pair (kind 0, `mem` 0), unit 1 + s
+// slice s's intra pair (kind 1, `mem` s), ppo_update_body<.., SLICES>'s numbering.  `p` is the spread binding's argument block with
+// p.a as ranenv_ppo_update_slices fills it (first[1][s]: the slices' shares; t, stats and grad numbered by unit) and p.k[kind] the
+// buffers of the kind's FIRST unit: all slices have one shape, so unit 1 + s's lie at p.k[1]'s pointers + s x the strides below, and
+// no table per unit goes into the arguments.  p.k[kind].steps is 0 or 1 there -- is the kind trained by this call? -- and .n unused:
+// a unit's rows n_u = first[kind][mem + 1] - first[kind][mem] and steps = epochs x ppo_spread_per_epoch(n_u, minibatch) are computed
+// where they are needed, on the device and for the launch grids, by ppo_slices_spread_unit.
+struct PpoSpreadSlices {
+    long long slab_unit, park_unit;       // floats between two slices' slabs ([slabs][slab_stride]) and parked rows ([slabs][park_stride])
+    long long dbl_unit;                   // doubles between two units' block partials, slab statistics and running sums
+    int n_units;                          // 1 + S, or 1: the inter pair alone
+};
+struct PpoSpreadSlicesArgs { PpoSpreadArgs p; PpoSpreadSlices x; };
+// THE UNIT GEOMETRY, one function for the kernels, the launch grids and ranenv_ppo_slices_spread_plan: unit u's kind and `mem`, the
+// first entry `lo` and the count `n` of its share of every epoch's list, and its optimiser steps (saturated at 2^31 - 1, which the
+// host refuses before any launch)
+struct PpoSliceUnit { int kind, mem, lo, n, steps; };
+__host__ __device__ inline PpoSliceUnit ppo_slices_spread_unit(const int (*first)[POP_MAX + 1], int u, int epochs, int minibatch)
+{
+    PpoSliceUnit x;
+    x.kind = u > 0 ? 1 : 0; x.mem = u > 0 ? u - 1 : 0;
+    x.lo = first[x.kind][x.mem]; x.n = first[x.kind][x.mem + 1] - x.lo;
+    const long long steps = (long long)epochs * ppo_spread_per_epoch(x.n, minibatch);
+    x.steps = steps > 0x7fffffffLL ? 0x7fffffff : (int)steps;
+    return x;
+}
+// The three launches of optimiser step a.p.step: the pass grid (the largest grid of that step over the live units, n_units), the
+// elementwise grid (the larger kind's blocks, n_units); units and blocks beyond their own extent return
+hipError_t launch_ppo_spread_slices_step(hipStream_t, size_t lds, const PpoSpreadSlicesArgs &, bool wide);
 // ... under ranenv_ppo_bind_spread_bfloat (include/ranenv.h "bf16 nets over the chip"): the nets are RANENV_NET_BF16 ones.  PpoNet of such a
 // net: `net` the ACTING copy's layout (bf16 W, two per float); w the f32 MASTER copy Adam steps, and m, v, g, `floats`, all in the F32
 // packed layout, the slabs' and dev_grad's.  Beside it that layout's offsets, the acting copy the pass's forward reads

@@ -17,25 +17,62 @@
 // counter, which no block of an apply reads.  The result is a function of the inputs and of min(tiles, slabs) alone; with one slab the
 // tile order and the adds are the plain kernel's.
 // The head policies (ranenv_ppo_bind_head_spread) have three kernels of the same pattern below, on the same elementwise functions.
+// Nets per slice (ranenv_ppo_bind_slices_spread) have four kernels of the SAME TEXT: blockIdx.y is one of 1 + S units there, not a kind.
 #include "ranenv_ppo_parts.hpp"
 
 namespace {
 
 __device__ __forceinline__ long long spread_floats(const PpoArgs &A, int kind) { return A.net[kind][0].floats + A.net[kind][1].floats; }
 
-template <bool WIDE, bool BF = false>
-__device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P, const PpoBf16Net (*bf)[2] = nullptr)
+// SLICES (ranenv_ppo_bind_slices_spread; "Nets per slice over the chip" below): blockIdx.y is the unit, and what differs is where a
+// workgroup finds its work -- spread_unit, at the top of each of the three functions; every other line is the same.
+// The unit of this workgroup: its kind, its copy `mem` of the kind's nets, its number `u` among the call's units (counter, statistics,
+// gradient block), the first entry `lo` of its share of the lists, and (SLICES alone; else the kind's own P.k[kind] serves) `K`, its
+// share of the binding's buffers with its rows and steps
+struct SpreadUnit { int kind, mem, u, lo; PpoSpreadKind K; };
+template <bool SLICES>
+__device__ __forceinline__ void spread_unit(const PpoSpreadArgs &P, const PpoSpreadSlices *X, SpreadUnit &U)
+{
+    U.u = (int)blockIdx.y;
+    if constexpr (!SLICES) { U.kind = U.u; U.mem = 0; U.lo = 0; }
+    else {
+        const PpoSliceUnit x = ppo_slices_spread_unit(P.a.first, U.u, P.hp.epochs, P.hp.minibatch);
+        U.kind = x.kind; U.mem = x.mem; U.lo = x.lo;
+        PpoSpreadKind &K = U.K;
+        K = P.k[x.kind];
+        K.slab += (size_t)x.mem * (size_t)X->slab_unit;
+        K.park += (size_t)x.mem * (size_t)X->park_unit;      // (unit 0: mem 0; not wide: park_unit 0 and the pointer is not read)
+        K.bpart += (size_t)x.mem * (size_t)X->dbl_unit; K.wstat += (size_t)x.mem * (size_t)X->dbl_unit; K.run += (size_t)x.mem * (size_t)X->dbl_unit;
+        K.t0 += x.mem;
+        K.n = x.n; K.steps = K.steps ? x.steps : 0;          // (P.k[kind].steps: is the kind trained by this call)
+    }
+}
+// Net k of the unit's kind: where its weights, moments and gradient cell start (SLICES: copy `mem` of the slot, ppo_update_body's rule)
+template <bool SLICES>
+__device__ __forceinline__ long long spread_at(const PpoArgs &A, int kind, int k, int mem) { return SLICES ? mem * A.net[kind][k].stride : 0; }
+template <bool SLICES>
+__device__ __forceinline__ PpoSpreadCell spread_cell(const PpoArgs &A, int kind, int mem, long long af, long long e)
+{
+    PpoSpreadCell c = ppo_spread_cell(A.net[kind][0], A.net[kind][1], af, e);
+    if constexpr (SLICES) { const long long at = spread_at<true>(A, kind, e < af ? 0 : 1, mem); c.g += at; c.w += at; c.m += at; c.v += at; }
+    return c;
+}
+
+template <bool WIDE, bool BF = false, bool SLICES = false>
+__device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P, const PpoBf16Net (*bf)[2] = nullptr, const PpoSpreadSlices *X = nullptr)
 {
     extern __shared__ float lds[];
     const PpoArgs &A = P.a;
     const ranenv_ppo_hparams &hp = P.hp;
-    const int tid = (int)threadIdx.x, kind = (int)blockIdx.y;
-    const PpoSpreadKind &K = P.k[kind];
+    SpreadUnit U;
+    spread_unit<SLICES>(P, X, U);
+    const int tid = (int)threadIdx.x, kind = U.kind, mem = U.mem;
+    const PpoSpreadKind &K = SLICES ? U.K : P.k[kind];
     if (P.step >= K.steps) return;
     const PpoSpreadStep geo = ppo_spread_step(K.n, hp.minibatch, P.slabs, P.step);
     const int w = (int)blockIdx.x;
     if (w >= geo.grid) return;
-    if (P.step == 0 && w == 0 && tid == 0) K.t0[0] = A.t[kind];
+    if (P.step == 0 && w == 0 && tid == 0) K.t0[0] = A.t[U.u];
     const int n_nets = A.net[kind][1].net.n_layers > 0 ? 2 : 1;      // net 0 the actor, net 1 the critic
 
     double *red = (double *)lds, *rowstat = red + 256;
@@ -43,7 +80,7 @@ __device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P, const PpoBf1
     float *act = lds + PPO_FIXED / 4;
     const int S = A.S, c0 = geo.c0, nb = geo.nb;
     const long long n_record = (long long)A.T * A.B * (kind == 0 ? 1 : S);
-    const int32_t *list = A.order[kind] + (size_t)geo.ep * (size_t)A.order_stride[kind];
+    const int32_t *list = A.order[kind] + (size_t)geo.ep * (size_t)A.order_stride[kind] + U.lo;
     const double wrow = 1.0 / (double)nb;
     float *const slab = K.slab + (size_t)w * (size_t)K.slab_stride;
     float *const wpark = WIDE ? K.park + (size_t)w * (size_t)K.park_stride : nullptr;      // (the workgroup's parked rows)
@@ -59,7 +96,8 @@ __device__ __forceinline__ void spread_pass(const PpoSpreadArgs &P, const PpoBf1
 #pragma unroll 1
     for (int t0 = w * NET_ROWS; t0 < nb; t0 += geo.grid * NET_ROWS)
         ppo_tile<WIDE, BF>(A, hp, kind, n_nets, list, c0, t0, nb, n_record, wrow, a_mean, a_den, rowstat, rowidx, act, wpark, st, tid,
-                           [&](int k) -> const PolicyNet & { return A.net[kind][k].net; }, [&](int k) -> const float * { return BF ? bf[kind][k].acting : A.net[kind][k].w; },
+                           [&](int k) -> const PolicyNet & { return A.net[kind][k].net; },
+                           [&](int k) -> const float * { return (BF ? bf[kind][k].acting : A.net[kind][k].w) + spread_at<SLICES>(A, kind, k, mem); },
                            [&](int k) { return slab + (k == 0 ? 0 : A.net[kind][0].floats); }, BF ? bf[kind] : nullptr);
     if (tid == 0) ppo_spread_wstat(K.wstat + (size_t)w * PPO_SPREAD_STATS, st);
 }
@@ -68,28 +106,35 @@ __global__ void __launch_bounds__(256) ranenv_ppo_spread_pass_kernel(PpoSpreadAr
 __global__ void __launch_bounds__(256) ranenv_ppo_spread_pass_kernel_wide(PpoSpreadArgs P) { spread_pass<true>(P); }
 
 // The reduce and the apply are the elementwise functions of ranenv_ppo_parts.hpp (ppo_spread_*), the head pair's kernels' too
-__global__ void __launch_bounds__(256) ranenv_ppo_spread_reduce_kernel(PpoSpreadArgs P)
+template <bool SLICES = false>
+__device__ __forceinline__ void spread_reduce(const PpoSpreadArgs &P, const PpoSpreadSlices *X = nullptr)
 {
     __shared__ double red[256];
     const PpoArgs &A = P.a;
-    const int tid = (int)threadIdx.x, kind = (int)blockIdx.y;
-    const PpoSpreadKind &K = P.k[kind];
+    SpreadUnit U;
+    spread_unit<SLICES>(P, X, U);
+    const int tid = (int)threadIdx.x, kind = U.kind, mem = U.mem;
+    const PpoSpreadKind &K = SLICES ? U.K : P.k[kind];
     if (P.step >= K.steps || (int)blockIdx.x >= K.blocks) return;
     const int used = ppo_spread_step(K.n, P.hp.minibatch, P.slabs, P.step).grid;
     const long long af = A.net[kind][0].floats, floats = spread_floats(A, kind);
-    const double s = ppo_spread_reduce_elems(K.slab, K.slab_stride, used, floats, tid, [&](long long e) { return ppo_spread_cell(A.net[kind][0], A.net[kind][1], af, e); });
+    const double s = ppo_spread_reduce_elems(K.slab, K.slab_stride, used, floats, tid, [&](long long e) { return spread_cell<SLICES>(A, kind, mem, af, e); });
     const double tot = ppo_sum(red, s, tid);
     if (tid == 0) K.bpart[blockIdx.x] = tot;
 }
 
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_reduce_kernel(PpoSpreadArgs P) { spread_reduce(P); }
+
 // stepped(kind, e, w): element e of the kind's packed floats has the new value w (the bf16 binding re-rounds it into the acting copies)
-template <class R>
-__device__ __forceinline__ void spread_apply(const PpoSpreadArgs &P, R stepped)
+template <bool SLICES = false, class R>
+__device__ __forceinline__ void spread_apply(const PpoSpreadArgs &P, R stepped, const PpoSpreadSlices *X = nullptr)
 {
     const PpoArgs &A = P.a;
     const ranenv_ppo_hparams &hp = P.hp;
-    const int tid = (int)threadIdx.x, kind = (int)blockIdx.y;
-    const PpoSpreadKind &K = P.k[kind];
+    SpreadUnit U;
+    spread_unit<SLICES>(P, X, U);
+    const int tid = (int)threadIdx.x, kind = U.kind, mem = U.mem;
+    const PpoSpreadKind &K = SLICES ? U.K : P.k[kind];
     if (P.step >= K.steps || (int)blockIdx.x >= K.blocks) return;
     const double norm = sqrt(ppo_spread_norm2(K.bpart, K.blocks));
     const float sc = (float)ppo_clip_scale(hp.grad_clip, norm);
@@ -97,18 +142,29 @@ __device__ __forceinline__ void spread_apply(const PpoSpreadArgs &P, R stepped)
     const AdamStep adam = adam_step(hp.lr, hp.beta1, hp.beta2, hp.eps, t_call + P.step + 1);
     const bool last = P.step == K.steps - 1;
     const long long af = A.net[kind][0].floats, floats = spread_floats(A, kind);
-    float *const grad = last && A.grad ? A.grad + (size_t)kind * (size_t)A.grad_stride : nullptr;
-    ppo_spread_apply_elems(floats, grad, sc, adam, tid, [&](long long e) { return ppo_spread_cell(A.net[kind][0], A.net[kind][1], af, e); },
+    float *const grad = last && A.grad ? A.grad + (size_t)U.u * (size_t)A.grad_stride : nullptr;
+    ppo_spread_apply_elems(floats, grad, sc, adam, tid, [&](long long e) { return spread_cell<SLICES>(A, kind, mem, af, e); },
                            [&](long long e, float w) { stepped(kind, e, w); });
     if (blockIdx.x != 0 || tid != 0) return;
     // ---- block 0: the epoch's statistics and the counter ---------------------------------------------------------------------------
     const PpoSpreadStep geo = ppo_spread_step(K.n, hp.minibatch, P.slabs, P.step);
     ppo_spread_stats(K.run, K.wstat, geo, norm, geo.mb == ppo_spread_per_epoch(K.n, hp.minibatch) - 1,
-                     A.stats + ((size_t)kind * (size_t)A.max_epochs + geo.ep) * RANENV_PPO_STATS, K.n);
-    if (last) A.t[kind] = t_call + K.steps;
+                     A.stats + ((size_t)U.u * (size_t)A.max_epochs + geo.ep) * RANENV_PPO_STATS, K.n);
+    if (last) A.t[U.u] = t_call + K.steps;
 }
 
 __global__ void __launch_bounds__(256) ranenv_ppo_spread_apply_kernel(PpoSpreadArgs P) { spread_apply(P, [](int, long long, float) {}); }
+
+// ---- nets per slice over the chip (ranenv_ppo_bind_slices_spread; include/ranenv.h "Nets per slice over the chip") -----------------------
+// The per-slice binding's 1 + S policies (ranenv_ppo.hip, SLICES) under the three launches above: blockIdx.y is the unit, every unit an
+// optimiser of its own with its own rows, steps, slabs, partials, running sums, t0 cell and counter -- so the rule above holds per
+// unit, and a unit whose steps are used up, or whose share is empty, returns at once in all three launches and keeps its bytes.
+static_assert(sizeof(PpoSpreadSlicesArgs) <= 4096, "the per-slice spread launches' arguments fit a kernel's argument segment");
+
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_slices_pass_kernel(PpoSpreadSlicesArgs Q) { spread_pass<false, false, true>(Q.p, nullptr, &Q.x); }
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_slices_pass_kernel_wide(PpoSpreadSlicesArgs Q) { spread_pass<true, false, true>(Q.p, nullptr, &Q.x); }
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_slices_reduce_kernel(PpoSpreadSlicesArgs Q) { spread_reduce<true>(Q.p, &Q.x); }
+__global__ void __launch_bounds__(256) ranenv_ppo_spread_slices_apply_kernel(PpoSpreadSlicesArgs Q) { spread_apply<true>(Q.p, [](int, long long, float) {}, &Q.x); }
 
 // ---- bf16 nets over the chip (ranenv_ppo_bind_spread_bfloat; include/ranenv.h "bf16 nets over the chip") ---------------------------------
 // The same three launches for RANENV_NET_BF16 nets.  The pass is spread_pass on the bf16 tile (ppo_tile<false, true>): the forward on
@@ -260,6 +316,26 @@ hipError_t launch_ppo_spread_step(hipStream_t s, size_t lds, const PpoSpreadArgs
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ranenv_ppo_spread_reduce_kernel, elem, block, 0, s, a);
     hipLaunchKernelGGL(ranenv_ppo_spread_apply_kernel, elem, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_spread_slices_step(hipStream_t s, size_t lds, const PpoSpreadSlicesArgs &q, bool wide)
+{
+    const PpoSpreadArgs &a = q.p;
+    int grid = 0, blocks = 0;
+    for (int u = 0; u < q.x.n_units; u++) {
+        const PpoSliceUnit x = ppo_slices_spread_unit(a.a.first, u, a.hp.epochs, a.hp.minibatch);
+        if (!a.k[x.kind].steps || a.step >= x.steps) continue;
+        const int g = ppo_spread_step(x.n, a.hp.minibatch, a.slabs, a.step).grid;
+        grid = g > grid ? g : grid;
+        blocks = a.k[x.kind].blocks > blocks ? a.k[x.kind].blocks : blocks;
+    }
+    if (grid == 0) return hipSuccess;
+    const dim3 pass((unsigned)grid, (unsigned)q.x.n_units), elem((unsigned)blocks, (unsigned)q.x.n_units), block(256);
+    const hipError_t e = wide ? launch_lds<ranenv_ppo_spread_slices_pass_kernel_wide>(pass, block, lds, s, q) : launch_lds<ranenv_ppo_spread_slices_pass_kernel>(pass, block, lds, s, q);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ranenv_ppo_spread_slices_reduce_kernel, elem, block, 0, s, q);
+    hipLaunchKernelGGL(ranenv_ppo_spread_slices_apply_kernel, elem, block, 0, s, q);
     return hipGetLastError();
 }
 
