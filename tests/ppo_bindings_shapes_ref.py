@@ -11,6 +11,8 @@ its live rows.  S 1 has one slice, which cannot hold both shares: the twin test 
     plain plan (ref.SHAPES):   D  S 1          C  S 16, Us 16, mask_obs, critic deeper          F  S 10, a 7-wide bottleneck
                                B  S 13, mask_obs, relu, critic shallower
     beyond the plan (wd.BEYOND at S 2, Us 5):   verybig [512] x 3 tanh          past_limit [512, 512, 96] relu, mask_obs
+tests/test_gpu_ppo_per_slice_spread_shapes.py runs the same cases, and ``intra_heavy`` (S 3; below), under the per-slice SPREAD binding
+(ranenv_ppo_bind_slices_spread) at the figures of tests/ppo_per_slice_spread_ref.py; ``slice_block_claims`` states what that grid covers.
 
 SPREAD.  One agent of ref.SHAPES A..F at B 12, T 8, plus ``lopsided``: shape A's inter pair beside relu24's intra pair on the native
 shape.  ref.make_role_nets gives the two kinds of an agent the same hidden widths, so no shape of A..F has kinds whose packed floats differ
@@ -41,12 +43,24 @@ SLICE_SHAPES = ("D", "C", "F", "B")
 SLICE_BEYOND = ("verybig", "past_limit")
 BEYOND_S, BEYOND_US = 2, 5
 SLICE_SEED = 6300                        # the nets' seed: tests/test_ppo_bindings_shapes_cpu.py guards the twin's gradients with it
+# PER SLICE OVER THE CHIP (ranenv_ppo_bind_slices_spread; tests/test_gpu_ppo_per_slice_spread_shapes.py) runs the six cases above at the
+# figures of tests/ppo_per_slice_spread_ref.py (T 24, minibatch 72, shares of 20 and 100 rows) and one case more.  ref.make_role_nets gives
+# the two kinds the same hidden widths and 10 S >= the intra input, so in all six the inter pair has at least the intra pair's reduce /
+# apply blocks; ``intra_heavy`` is the other way round: a [24] inter pair (5 blocks, the fewest a pair can have) beside S 3 intra pairs of
+# [160, 96] / [255] (40 blocks).  ``slice_block_claims`` states what that grid covers.
+SLICE_LOPSIDED = "intra_heavy"
+LOPSIDED_S, LOPSIDED_US, LOPSIDED_LAYOUT, LOPSIDED_ACT = 3, 4, "obs", "tanh"
+LOPSIDED_WIDTHS = {"inter": ([24], [24]), "intra": ([160, 96], [255])}      # kind -> (actor hidden widths, critic hidden widths)
+SLICE_SPREAD_SHAPES = SLICE_SHAPES + (SLICE_LOPSIDED,)
 
 
 def slice_spec(case):
     """(S, Us, layout, (actor widths, activation), (critic widths, activation)) of a per-slice case"""
     if case in ref.SHAPES:
         return ref.SHAPES[case]
+    if case == SLICE_LOPSIDED:               # (the widths are the intra pairs'; the inter pair's are LOPSIDED_WIDTHS["inter"])
+        aw, cw = LOPSIDED_WIDTHS["intra"]
+        return LOPSIDED_S, LOPSIDED_US, LOPSIDED_LAYOUT, (aw, LOPSIDED_ACT), (cw, LOPSIDED_ACT)
     widths, act, layout = wd.BEYOND[case]
     return BEYOND_S, BEYOND_US, layout, (widths, act), (widths, act)
 
@@ -55,6 +69,9 @@ def slice_nets(case, seed=SLICE_SEED):
     """The inter pair and S distinct intra pairs of the case: {"inter", "v_inter": net, "intra", "v_intra": [S nets]}"""
     S, Us, layout, (aw, aa), (cw, ca) = slice_spec(case)
     per = [ref.make_role_nets(S, Us, aw, aa, layout, seed + 10 * s, cw, ca) for s in range(S)]
+    if case == SLICE_LOPSIDED:
+        small = ref.make_role_nets(S, Us, LOPSIDED_WIDTHS["inter"][0], aa, layout, seed + 7, LOPSIDED_WIDTHS["inter"][1], ca)
+        per[0] = dict(per[0], inter=small["inter"], v_inter=small["v_inter"])
     return {"inter": per[0]["inter"], "v_inter": per[0]["v_inter"], "intra": [p["intra"] for p in per], "v_intra": [p["v_intra"] for p in per]}
 
 
@@ -66,7 +83,32 @@ def kind_dims(S, Us, layout, aw, cw):
 
 def slice_dims(case):
     S, Us, layout, (aw, _), (cw, _) = slice_spec(case)
+    if case == SLICE_LOPSIDED:
+        return {"inter": kind_dims(S, Us, layout, *LOPSIDED_WIDTHS["inter"])["inter"], "intra": kind_dims(S, Us, layout, aw, cw)["intra"]}
     return kind_dims(S, Us, layout, aw, cw)
+
+
+def slice_kind_floats(case):
+    """{kind: (the actor's packed floats ``af``, the pair's)} of a per-slice case; one intra pair's, not S times it"""
+    return {k: (sp.packed_floats(a), sp.packed_floats(a) + sp.packed_floats(c)) for k, (a, c) in slice_dims(case).items()}
+
+
+def slice_block_claims(cases=None):
+    """What the per-slice spread grid covers, from the packed float counts alone: {claim: the cases that hold it}.  The reduce / apply
+    grid of a step is the larger kind's blocks for every unit: the units of the smaller kind return beyond their own."""
+    cases = SLICE_SPREAD_SHAPES + SLICE_BEYOND if cases is None else cases
+    out = {"inter pair has more blocks": [], "intra pair has more blocks": [], "af off the block grid, inter": [], "af off the block grid, intra": []}
+    for case in cases:
+        kf = slice_kind_floats(case)
+        b = {k: blocks_of(f) for k, (_, f) in kf.items()}
+        if b["inter"] > b["intra"]:
+            out["inter pair has more blocks"].append(case)
+        if b["intra"] > b["inter"]:
+            out["intra pair has more blocks"].append(case)
+        for k in kf:
+            if kf[k][0] % SPREAD_BLOCK != 0:
+                out[f"af off the block grid, {k}"].append(case)
+    return out
 
 
 def slice_order(rec, epochs, minibatch, small, big_rows, empty=None, seed=3, only=None):

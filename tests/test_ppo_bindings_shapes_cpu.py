@@ -51,6 +51,45 @@ def test_no_gradient_tensor_of_the_twin_is_zero_for_any_slice_of_the_per_slice_c
     assert len({nets["intra"][s][0].weight.detach().numpy().tobytes() for s in range(S)}) == S, "the slices' nets are distinct"
 
 
+@pytest.mark.parametrize("case", bs.SLICE_SPREAD_SHAPES + bs.SLICE_BEYOND)
+def test_no_gradient_tensor_of_the_twin_is_zero_on_a_share_of_twenty_rows_at_24_steps(case):
+    """The per-slice spread module's smallest share: tests/test_gpu_ppo_per_slice_spread_shapes.py gives 20 rows to the right neighbour of
+    the slice with the most live rows, whichever that is on the device's record -- so every slice's own pair on 20 rows of its share of a
+    synthetic record of T 24, and the inter pair on all 288 rows"""
+    from tests import ppo_per_slice_spread_ref as ps
+    S, Us, layout, (_, aa), (_, ca) = bs.slice_spec(case)
+    nets = bs.slice_nets(case)
+    rec = ref.synthetic_record(B=ps.B, seed=11, T_=ps.T, layout=layout, S=S, Us=Us)
+    order = ad.ppo_row_order(rec, [0, ps.B], 1, seed=3, per_slice=True)
+    first, rows = order["first_intra"], order["order_intra"][0].numpy()
+    assert order["order_inter"].shape[1] == ps.B * ps.T == 288
+    _no_zero_tensor(rec, "inter", nets["inter"], nets["v_inter"], order["order_inter"][0].numpy(), aa, ca, layout, f"{case} inter")
+    for s in range(S):
+        share = rows[first[s]:first[s + 1]]
+        assert len(share) >= ps.SMALL, (case, s, len(share))
+        _no_zero_tensor(rec, "intra", nets["intra"][s], nets["v_intra"][s], share[:ps.SMALL], aa, ca, layout, f"{case} slice {s}, 20 rows")
+    assert len({nets["intra"][s][0].weight.detach().numpy().tobytes() for s in range(S)}) == S, "the slices' nets are distinct"
+
+
+def test_what_the_per_slice_spread_grid_covers_by_its_block_counts():
+    """One elementwise grid serves all units of a step, sized by the larger kind: the grid holds cases whose inter pair has more reduce /
+    apply blocks than an intra pair, one the other way round (``intra_heavy``, why the grid has it), and an actor / critic boundary off
+    the 1024-float block grid in both kinds; every case is named, so a case taken from the grid fails this"""
+    cases = bs.SLICE_SPREAD_SHAPES + bs.SLICE_BEYOND
+    claims = bs.slice_block_claims()
+    print(claims)
+    assert claims == bs.slice_block_claims(cases)
+    assert claims["inter pair has more blocks"] == ["C", "F", "B"]
+    assert claims["intra pair has more blocks"] == [bs.SLICE_LOPSIDED]
+    assert claims["af off the block grid, inter"] == list(cases) == claims["af off the block grid, intra"] and len(cases) == 7
+    assert not bs.slice_block_claims(bs.SLICE_SHAPES + bs.SLICE_BEYOND)["intra pair has more blocks"], "why the grid has the intra-heavy case"
+    kf = bs.slice_kind_floats(bs.SLICE_LOPSIDED)
+    assert bs.blocks_of(kf["inter"][1]) == bs.MIN_PAIR_BLOCKS == 5 and bs.blocks_of(kf["intra"][1]) == 40
+    for case in cases:                           # (the counts are the library's own packed floats)
+        for kind, (a, c) in bs.slice_dims(case).items():
+            assert bs.slice_kind_floats(case)[kind] == (be.packed_net_floats(a), be.packed_net_floats(a) + be.packed_net_floats(c)), (case, kind)
+
+
 @pytest.mark.parametrize("case", SPREAD_CASES)
 def test_no_gradient_tensor_of_the_twin_is_zero_for_any_net_of_the_spread_cases(case):
     S, Us, layout, aa, ca, _ = bs.spread_spec(case)

@@ -15,6 +15,7 @@ import torch
 
 from intent_radio_sched_multi_slice_amd import _lib
 from intent_radio_sched_multi_slice_amd import batched_env as be
+from tests import ppo_bindings_shapes_ref as bs
 from tests import ppo_per_slice_spread_ref as ps
 from tests import ppo_spread_ref as sp
 
@@ -105,6 +106,63 @@ def test_slices_spread_bytes_against_the_restated_formula_on_200_seeded_shapes()
     # the header's warning: S 10, 256 slabs, [512] x 3 -- 12.7 gigabytes, 13.3 under the wide plan
     verybig = ([100, 512, 512, 512, 20], [100, 512, 512, 512, 1], [19, 512, 512, 512, 3], [19, 512, 512, 512, 1])
     assert round(be.ppo_slices_spread_bytes(*verybig, 10, 256) / 1e9, 1) == 12.7 and round(be.ppo_slices_spread_bytes(*verybig, 10, 256, wide=True) / 1e9, 1) == 13.3
+
+
+GRID_SLICES, GRID_SLABS, GRID_INTER = (1, 10, 13, 16), (2, 3, 8, 256), (0, ps.SMALL, ps.B * ps.T)
+
+
+def _grid_tables(n_slices):
+    """The first-tables tests/test_gpu_ppo_per_slice_spread_shapes.py runs at ``n_slices``: one share of 100 rows, its right neighbour 20,
+    every other slice all its live rows (192 .. 288 of them); the same with the last share empty; S 1: the one share of 20 or of 100"""
+    if n_slices == 1:
+        tables = [[ps.SMALL], [ps.MID]]
+    else:
+        shares = [192 + (37 * s) % 97 for s in range(n_slices)]
+        big = n_slices // 3
+        shares[big], shares[(big + 1) % n_slices] = ps.MID, ps.SMALL
+        tables = [shares, shares[:-1] + [0]]
+    return [np.concatenate([[0], np.cumsum(t)]).astype(np.int32) for t in tables]
+
+
+def test_plan_on_the_shape_grid_and_the_planted_slips_at_sixteen_slices():
+    """S 1, 10, 13 and 16 at minibatch 72 and 2 epochs, under 2, 3, 8 and 256 slabs, beside an inter list of 0, 20 and 288 rows, with and
+    without an empty share: ranenv_ppo_slices_spread_plan gives the restatement's figures, and at S 16 each of the three planted slips
+    leaves them on every table"""
+    lib = _lib.load()
+    assert {bs.slice_spec(c)[0] for c in bs.SLICE_SHAPES} == set(GRID_SLICES) and GRID_INTER == (0, 20, 288)
+    for n_slices in GRID_SLICES:
+        for first in _grid_tables(n_slices):
+            for n_inter in GRID_INTER:
+                for slabs in GRID_SLABS:
+                    args = (n_inter, first, ps.MB, ps.EPOCHS, slabs)
+                    got = _lib_plan(lib, *args)
+                    assert got == ps.plan(*args), (n_slices, first.tolist(), n_inter, slabs)
+                    steps, grid, call = got
+                    rows = ps.unit_rows(n_inter, first)
+                    assert steps == [ps.EPOCHS * -(-r // ps.MB) for r in rows] and call == max(steps)
+                    assert grid == [min(sp.tiles_of(min(r, ps.MB)), slabs) for r in rows]
+                    if n_slices == 16:
+                        for slip in ps.SLIPS:
+                            assert ps.plan(*args, slip) != got, (slip, first.tolist(), n_inter, slabs)
+    # the shares of 20 and 100 rows beside 288 inter rows: 2, 4 and 8 steps; an inter list of 20 rows is through first
+    first = _grid_tables(16)[0]
+    steps = _lib_plan(lib, 288, first, ps.MB, ps.EPOCHS, 3)[0]
+    assert steps[0] == 8 and sorted(set(steps[1:])) == [2, 4, 6, 8]
+    assert _lib_plan(lib, 20, first, ps.MB, ps.EPOCHS, 3)[0][0] == 2 and _lib_plan(lib, 0, first, ps.MB, ps.EPOCHS, 3)[0][0] == 0
+
+
+def test_slices_spread_bytes_of_every_grid_case_against_the_restated_formula():
+    """Every case tests/test_gpu_ppo_per_slice_spread_shapes.py binds, at 2, 3, 8 and 256 slabs, under both plans"""
+    for case in bs.SLICE_SPREAD_SHAPES + bs.SLICE_BEYOND:
+        n_slices, dims = bs.slice_spec(case)[0], bs.slice_dims(case)
+        for slabs in GRID_SLABS:
+            for wide in (False, True):
+                got = be.ppo_slices_spread_bytes(*dims["inter"], *dims["intra"], n_slices, slabs, wide)
+                assert got == ps.slices_spread_bytes(*dims["inter"], *dims["intra"], n_slices, slabs, wide), (case, slabs, wide)
+                assert got == 4 * slabs * sum(n * (f + (bs.wd.wide_scratch_floats(*dims[k]) if wide else 0))
+                                              for k, n, f in (("inter", 1, bs.slice_kind_floats(case)["inter"][1]), ("intra", n_slices, bs.slice_kind_floats(case)["intra"][1])))
+    b, c = bs.slice_dims("B"), bs.slice_dims("C")
+    assert be.ppo_slices_spread_bytes(*b["inter"], *b["intra"], 13, 256) == 454033408 < 512 << 20 < be.ppo_slices_spread_bytes(*c["inter"], *c["intra"], 16, 256) == 546209792
 
 
 def test_the_entries_refuse_their_arguments_before_a_handle():
